@@ -7,17 +7,19 @@ rank 0's line; invoked by torch.distributed.run it is one of those ranks.
 
 A "step" is one batch of `--batch` query vectors matched against the whole gallery through the library's default
 dispatch (fir_search_top1_keys_dev): for batches >= 128 that is the fp16 matrix-core nomination pass + exact re-rank +
-certificate (identical keys to the exact scan, checked in this run), plus, for N > 1, the RCCL all-reduce(MIN) of the
+certificate (identical keys to the exact scan, checked by `--full`), plus, for N > 1, the RCCL all-reduce(MIN) of the
 packed (distance, index) keys that the LIBRARY issues (fir_sharded_*, ncclAllReduce(ncclMin, ncclUint64)). Queries and
-gallery are resident in HBM before the timed region starts. `value` is that loop.
+gallery are resident in HBM before the timed region starts. `value` is that loop. A plain run does nothing else: set-up,
+warm-up, the timed steps, the last step's answers to `--dump-outputs DIR` when given, the line.
 
-The same run also times, with the same steps / warmup:
+With `--full` the same run also checks the headline keys against the exact scan and times, with the same steps / warmup:
   * the exact streaming scan at 8 queries per gallery pass (matrix-core path switched off, 256-query steps): the
     metric's "achieved HBM GB/s" clause -> `roofline`;
   * N = 1: chi-square / KL / top-5 scans of the same gallery (BASELINE config 3), the 100k x 512 gallery (config 2),
     the float64 PNN / kNN classifiers (K3);
   * a 10M x 512 gallery split over the N ranks (BASELINE config 4) -> `config4`;
-  * N = 1: the reference's own recognize_image_bf and the OpenMP restatement on ALL host cores -> `cpu_baseline`, `cpu_all`.
+  * N = 1: the reference's own recognize_image_bf and the OpenMP restatement on ALL host cores -> `cpu_baseline`, `cpu_all`;
+  * N = 1: a rocprofv3 FETCH_SIZE counter pass in a child process -> `roofline.traffic`.
 
 Multi-GPU: the SAME 1M x 512 gallery is sharded by rows over the N ranks ("scaling": "strong"); `config4` is the
 larger gallery of BASELINE.json configs[3].
@@ -94,6 +96,36 @@ def emit_line(text):
         data = data[os.write(fd, data):]
 
 
+def headline(args, world, n, d, qb, elapsed):
+    """The fields of the result line that the headline loop alone determines."""
+    return {"metric": "query-vectors/sec brute-force L2 top-1, 1Mx512 gallery", "value": qb * args.steps / elapsed, "unit": "queries/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{n}x{d} f32 gallery, batched L2 top-1 through the library's default dispatch (the metric's 1Mx512 size; "
+                                   "configs[1]'s kernel is the exact-scan loop under `roofline`, --full)",
+                       "query_batch": qb}}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, fir, keys):
+    """What a caller of the timed path receives for the last step, unpacked from the (distance, index) keys: per query the
+    global row of its nearest gallery row (`top1_index.npy`, float64: exact for any row number) and that distance
+    (`top1_distance.npy`, float32, the library's bits). Batches too large for DUMP_BYTES_MAX keep a fixed, seeded sample of
+    queries, whose numbers go to `query.npy`."""
+    idx, dist = fir.keys_unpack(keys.cpu().numpy().view(np.uint64))
+    arrays = {"top1_index": idx.astype(np.float64), "top1_distance": dist}
+    cap = DUMP_BYTES_MAX // 12
+    if idx.size > cap:
+        sel = np.sort(np.random.default_rng(0).choice(idx.size, cap, replace=False))
+        arrays = {k: v[sel] for k, v in arrays.items()}
+        arrays["query"] = sel.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -120,7 +152,13 @@ def parse_args(argv=None):
     ap.add_argument("--shards-per-device", type=int, default=1, help="logical shards per rank (exercises the split on few GPUs)")
     ap.add_argument("--backend", default="nccl", help="'gloo' rehearses the N>1 path with all ranks on ONE GPU (keys exchanged through host memory)")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, shard arithmetic and key exchange only, no GPU work (CPU test of the launch path)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline loop: host-pointer step, exact-scan roofline and "
+                                                         "verification, other scans and configurations, CPU baselines, the rocprofv3 counter pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's top-1 answers to DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -395,8 +433,8 @@ def main():
 
     n, qb = args.rows, args.batch
     m, row_lo, row_hi, shard = build(n)
-    host_shard = shard.cpu().numpy() if (world == 1 and args.cpu_seconds > 0 and not args.pmc_child) else None
-    small_src = shard[:100_000].clone() if (world == 1 and not args.no_extras and n >= 100_000) else None
+    host_shard = shard.cpu().numpy() if (args.full and world == 1 and args.cpu_seconds > 0 and not args.pmc_child) else None
+    small_src = shard[:100_000].clone() if (args.full and world == 1 and not args.no_extras and n >= 100_000) else None
     del shard
     torch.cuda.empty_cache()
     q, planted = make_queries(qb, n)
@@ -406,6 +444,20 @@ def main():
     elapsed, k_ms, x_ms, disp = timed_loop(m, q, qb, keys, args.steps, args.warmup)
     keys_default = keys.clone()
     head = {"elapsed": elapsed, "kernel_ms": k_ms, "exch_ms": x_ms, "disp": disp}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fir, keys_default)
+    if not args.full:
+        line = headline(args, world, n, d, qb, elapsed)
+        line["config"].update({"path": disp["path"], "fallback_queries_in_timed_steps": disp["fallback_queries"],
+                               "second_pass_queries_in_timed_steps": disp["second_pass_queries"],
+                               "row_sharding": f"{world} rank(s) x {args.shards_per_device} shard(s), {row_hi - row_lo} rows on this rank"})
+        m.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            emit_line(json.dumps(line))
+        return
     # "t_batch includes H2D of queries and D2H of results; report kernel-only too" -- the same step through the HOST-pointer entry
     # point (fir_search_top1: what the reference's call takes, db_features.cpp:319): queries from pinned host memory, indices and distances back
     # to host arrays, inside the timed region. `value` stays the device-resident rate.
@@ -512,23 +564,11 @@ def main():
                              "stream_GBps": gbs, "peak_GBps": peak_gbs, "frac_of_hbm_peak": gbs / peak_gbs, "traffic": traffic.get("mfma"),
                              "kernel_time_share_of_step": float(np.sum(head["kernel_ms"])) / (head["elapsed"] * 1e3) if world == 1 else None,
                              "l2_to_cu": l2_to_cu(row_hi - row_lo, d, hd["queries_per_pass"], h_avg), **h_blk}
-        out = {
-            "metric": "query-vectors/sec brute-force L2 top-1, 1Mx512 gallery",
-            "value": qb * args.steps / head["elapsed"],
-            "value_host_pointers": host_rate["value_host_pointers"] if host_rate else None,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": head["elapsed"] / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
+        out = headline(args, world, n, d, qb, head["elapsed"])
+        out["value_host_pointers"] = host_rate["value_host_pointers"] if host_rate else None
+        out.update({
             "config": {
-                "workload": f"{n}x{d} f32 gallery, batched L2 top-1 through the library's default dispatch (the metric's 1Mx512 size; configs[1]'s kernel is the exact-scan loop under `roofline`)",
-                "query_batch": qb,
+                **out["config"],
                 "path": hd["path"],
                 "path_note": "fp16 MFMA (one term, power-of-two-scaled operands, 128 queries per gallery read) nominates rows, the reference's f32 arithmetic re-ranks every row "
                              "inside the rounding window, a rounding-error certificate proves the rest cannot win, uncertified queries go through the exact scan" if hd["path"] == "mfma" else "exact streaming scan",
@@ -555,7 +595,7 @@ def main():
             "roofline_mfma": roofline_mfma,
             "config4": cfg4,
             "config5": cfg5,
-        }
+        })
         if also:
             for kname in ("roofline_chi2", "roofline_kl", "roofline_chi2_exact", "roofline_kl_exact"):
                 out[kname] = also.pop(kname, None)
@@ -1081,7 +1121,7 @@ def pmc_traffic(args, n, d, world):
         out_dir = tempfile.mkdtemp(prefix="fir_pmc_")
         cmd = ["rocprofv3", "--pmc", "FETCH_SIZE", "--output-format", "csv", "-d", out_dir, "-o", "pmc", "--",
                sys.executable, os.path.abspath(__file__), "--pmc-child", "--steps", "3", "--warmup", "1", "--rows", str(n), "--dim", str(d),
-               "--batch", str(min(args.batch, 32768)), "--scan-batch", str(args.scan_batch), "--cpu-seconds", "0", "--no-extras"]
+               "--batch", str(min(args.batch, 32768)), "--scan-batch", str(args.scan_batch), "--cpu-seconds", "0", "--no-extras", "--full"]
         if not args.no_extras and d == 512:
             cmd += ["--pmc-config2"]
         if args.qpp:

@@ -1,11 +1,13 @@
 """bench.py on the GPU box: the N > 1 launch path invoked plainly (two ranks sharing GPU 0, keys exchanged through gloo --
 the in-library RCCL exchange cannot put two ranks on one device), and the one-rank run through the sharded handle and its
-RCCL communicator (--force-dist) with logical shards."""
+RCCL communicator (--force-dist) with logical shards; both with --full, whose checks they read. A plain run prints the
+headline alone and writes the last step's answers with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,7 @@ def run_bench(*flags):
 
 def test_two_ranks_started_by_bench_itself():
     rec = run_bench("--gpus", "2", "--backend", "gloo", "--rows", "140625", "--batch", "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
-                    "--no-extras", "--no-pmc")
+                    "--no-extras", "--no-pmc", "--full")
     assert rec["n_gpus"] == 2 and rec["value"] > 0 and rec["steps"] == 2
     assert rec["config"]["identical_keys_to_exact_scan"] is True and rec["config"]["planted_queries_found"] is True
     assert rec["config"]["path"] == "mfma"                       # 78125 rows per rank, 256 queries: the default dispatch
@@ -36,8 +38,23 @@ def test_two_ranks_started_by_bench_itself():
 
 def test_one_rank_through_the_sharded_handle_and_rccl():
     rec = run_bench("--gpus", "1", "--force-dist", "--shards-per-device", "2", "--rows", "250000", "--batch", "512", "--steps", "2", "--warmup", "1",
-                    "--cpu-seconds", "0", "--no-extras", "--no-pmc")
+                    "--cpu-seconds", "0", "--no-extras", "--no-pmc", "--full")
     assert rec["n_gpus"] == 1 and rec["value"] > 0
     assert "ncclAllReduce" in rec["config"]["key_exchange"]
     assert rec["config"]["exchange_us_per_step"] is not None and rec["config"]["exchange_us_per_step"] >= 0
     assert rec["config"]["identical_keys_to_exact_scan"] is True and rec["config"]["planted_queries_found"] is True
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    rec = run_bench("--gpus", "1", "--rows", "140625", "--batch", "256", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert rec["value"] > 0 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] / 1e3 - 256) < 1e-6 * 256
+    assert rec["unit"] == "queries/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    for moved in ("roofline", "roofline_mfma", "cpu_baseline", "config4", "config5"):
+        assert moved not in rec
+    idx = np.load(tmp_path / "top1_index.npy")
+    dist = np.load(tmp_path / "top1_distance.npy")
+    assert idx.dtype == np.float64 and dist.dtype == np.float32 and idx.shape == dist.shape == (256,)
+    assert np.all((idx >= 0) & (idx < 140625)) and np.all(np.isfinite(dist))
+    odd = np.arange(256) % 2 == 1                      # bench.make_queries: odd queries are perturbed copies of rows of chunk 0
+    assert np.array_equal(idx[odd], (np.arange(256)[odd] * 977 + 11) % 15625)

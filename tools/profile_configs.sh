@@ -8,7 +8,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
-bash tools/kstats_any.sh bench bench.py --steps 10 --warmup 3 --no-pmc --cpu-seconds 0 --no-extras --no-verify | head -6
+bash tools/kstats_any.sh bench bench.py --full --steps 10 --warmup 3 --no-pmc --cpu-seconds 0 --no-extras --no-verify | head -6
 bash tools/kstats_any.sh config5 tools/cfg5_bench_block.py 1 | head -8
 bash tools/kstats_any.sh config3_chi2 tools/chi2_bench.py --metric 1 | head -8
 bash tools/kstats_any.sh config3_kl tools/chi2_bench.py --metric 2 | head -8
