@@ -120,6 +120,11 @@ struct fir_gallery {
     std::vector<hipEvent_t> ev;   // pairs
     size_t ev_used = 0;
     double last_bytes = 0.0;
+
+    // call order (FirCallOrder, fir_internal.h): the end of the most recent call on this handle or a fir_gemm state over it
+    hipEvent_t last_done = nullptr;
+    hipStream_t last_stream = nullptr;   // the stream last_done was recorded on (nullptr: no call yet)
+    int call_depth = 0;                  // > 0 inside a call
 };
 
 namespace {
@@ -629,6 +634,18 @@ int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t s
     const bool was_profiling = g->profiling, was_quiet = g->quiet;
     g->profiling = false;
     g->quiet = true;
+    // the row samples hand the handle back as they found it, on every way out (a failed launch must not leave later calls quiet)
+    bool samples_done = false;
+    auto end_samples = [&] {
+        if (samples_done) return;
+        samples_done = true;
+        g->tiles_limit = 0;
+        g->tile_begin = 0;
+        g->sample_groups = 0;
+        g->profiling = was_profiling;
+        g->quiet = was_quiet;
+    };
+    auto end_samples_on_exit = fir_on_exit(end_samples);
     FIR_HIP(hipMemsetAsync(flag, 0, 4, st));
     // chi-square / KL nomination: the row samples run the NOMINATION metric too (2.25 / 3 issue slots per element instead of the
     // exact metric's 11 / ~35: the samples were 0.9 of a 256-query call's 12.3 ms). A sampled minimum is then within B of the
@@ -701,10 +718,7 @@ int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t s
             rc = top1_dev(g, d_queries, qb, start, end, skeys + (size_t)i * qb, st);
         }
     }
-    g->tiles_limit = 0;
-    g->tile_begin = 0;
-    g->profiling = was_profiling;
-    g->quiet = was_quiet;
+    end_samples();
     if (rc) return rc;
     hipLaunchKernelGGL(k_topk_tau, dim3((qpad + 63) / 64), dim3(64), 0, st, skeys, qb, qpad, k, tau, counts, flag, tau_scale, sample_stride);
     // (1.5 B over an exact sample; 2.5 B over a sample in the nomination metric -- the kernels multiply by 1.5)
@@ -910,9 +924,16 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
     hipError_t e;
     e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete g; return fail(FIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+    e = hipEventCreateWithFlags(&g->last_done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipStreamDestroy(g->stream);
+        delete g;
+        return fail(FIR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
+    }
     const size_t f4 = (size_t)std::max<int64_t>(g->tiles, 1) * g->dp4 * 64;
     e = hipMalloc((void**)&g->gal4, f4 * sizeof(float4));
     if (e != hipSuccess) {
+        (void)hipEventDestroy(g->last_done);
         (void)hipStreamDestroy(g->stream);
         delete g;
         return fail(FIR_ERR_NOMEM, "hipMalloc of %zu gallery bytes: %s", f4 * sizeof(float4), hipGetErrorString(e));
@@ -921,6 +942,7 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
     if (e == hipSuccess) e = hipMemset(g->range, 0, 2 * sizeof(int32_t));
     if (e != hipSuccess) {
         (void)hipFree(g->gal4); (void)hipFree(g->range);
+        (void)hipEventDestroy(g->last_done);
         (void)hipStreamDestroy(g->stream);
         delete g;
         return fail(FIR_ERR_NOMEM, "hipMalloc of the range flags: %s", hipGetErrorString(e));
@@ -950,6 +972,24 @@ int fir_gallery_view_(fir_gallery* g, fir_gallery_view* out) {
     if (!g || !out) return FIR_ERR_ARG;
     out->device = g->device; out->cus = g->cus; out->n = g->n; out->d = g->d; out->metric = g->metric; out->row_offset = g->row_offset;
     out->cls = g->cls; out->stream = g->stream;
+    return FIR_OK;
+}
+int fir_gallery_call_begin_(fir_gallery* g, hipStream_t st) {
+    if (!g || g->call_depth++ > 0) return FIR_OK;
+    if (g->last_stream && g->last_stream != st) {          // (same stream: stream order already does it)
+        const hipError_t e = hipStreamWaitEvent(st, g->last_done, 0);
+        if (e != hipSuccess) return fail(FIR_ERR_HIP, "hipStreamWaitEvent (call order): %s", hipGetErrorString(e));
+    }
+    return FIR_OK;
+}
+void fir_gallery_call_end_(fir_gallery* g, hipStream_t st, int finished) {
+    if (!g || --g->call_depth > 0) return;
+    if (finished) g->last_stream = nullptr;                 // (its stream had passed the wait for every earlier call, too)
+    else if (hipEventRecord(g->last_done, st) == hipSuccess) g->last_stream = st;
+}
+int fir_gallery_wait_calls_(fir_gallery* g) {
+    if (!g || !g->last_stream) return FIR_OK;
+    FIR_HIP(hipEventSynchronize(g->last_done));
     return FIR_OK;
 }
 __global__ void k_runtime_warmup(int* p) {
@@ -1006,7 +1046,10 @@ int fir_subrange_distances_dev_(fir_gallery* g, const float* d_queries, int32_t 
         return fail(FIR_ERR_ARG, "sub-ranges of %d features do not tile [%d,%d) inside [0,%d)", step, start, end, g->d);
     if (g->n == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
-    return subranges_dev(g, d_queries, qb, start, end, step, d_out, stream ? (hipStream_t)stream : g->stream);
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    return subranges_dev(g, d_queries, qb, start, end, step, d_out, st);
 }
 int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t split, int32_t end, float* d_out, void* stream) {
     if (!g || !d_queries || !d_out) return fail(FIR_ERR_ARG, "NULL argument");
@@ -1015,6 +1058,8 @@ int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb,
     if (g->n == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
     hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
     if (split % (4 * kUSub) == 0 && (end - split) % (4 * kUSub) == 0) return subranges_dev(g, d_queries, qb, 0, end, split, d_out, st, end - split);
     const int rc = range_dev(g, d_queries, qb, 0, split, d_out, st);
     if (rc) return rc;
@@ -1128,6 +1173,7 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
 int fir_gallery_destroy(fir_gallery* g) {
     if (!g) return FIR_OK;
     (void)hipSetDevice(g->device);
+    (void)fir_gallery_wait_calls_(g);         // calls queued on the callers' streams may still use what is freed below
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
     for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
@@ -1136,6 +1182,7 @@ int fir_gallery_destroy(fir_gallery* g) {
     (void)hipFree(g->part); (void)hipFree(g->dout); (void)hipFree(g->didx); (void)hipFree(g->range); (void)hipFree(g->one_keys); (void)hipFree(g->rowsum);
     if (g->pin) (void)hipHostFree(g->pin);
     for (void* p : g->scratch) if (p) (void)hipFree(p);
+    if (g->last_done) (void)hipEventDestroy(g->last_done);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
     return FIR_OK;
@@ -1345,8 +1392,11 @@ int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int3
     const int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
     const fir_dispatch_info saved = g->last;          // the caller's dispatch record stays the matrix-core pass's, not this fallback's
-    const int rc2 = topk_dev(g, d_queries, qb, 0, end_pos, k, d_keys, stream ? (hipStream_t)stream : g->stream, true, false);
+    const int rc2 = topk_dev(g, d_queries, qb, 0, end_pos, k, d_keys, st, true, false);
     g->last = saved;
     return rc2;
 }
@@ -1360,6 +1410,8 @@ int fir_search_top1_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb,
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
     hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
     g->call_launches = 0;
     g->warm_left = 0;
     rc = try_mfma(g, d_queries, qb, start_pos, end_pos, d_keys, st);
@@ -1375,11 +1427,14 @@ int fir_search_top1_exact_keys_dev_(fir_gallery* g, const float* d_queries, int3
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
-    const bool was_profiling = g->profiling;
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    const bool was_profiling = g->profiling, was_quiet = g->quiet;
     g->profiling = false;
     g->quiet = true;
-    rc = top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, stream ? (hipStream_t)stream : g->stream);
-    g->quiet = false;
+    rc = top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, st);
+    g->quiet = was_quiet;
     g->profiling = was_profiling;
     return rc;
 }
@@ -1552,6 +1607,8 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);               // (a host-pointer call is a call on the handle's own stream)
+    if (order.rc) return order.rc;
     const bool mfma = wants_mfma(g, qb, start_pos, end_pos);
     g->call_launches = 0;
     if (!mfma && (size_t)qb * g->d * sizeof(float) <= kPinQueryBytes && (size_t)qb <= kPinKeys) {
@@ -1565,7 +1622,7 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
             for (int k = g->d; k < g->dp4 * 4; ++k) hq[k] = 0.0f;        // the one-query tile, zero padded
             rc = top1_one_query(g, hq, start_pos, end_pos, hk);
             if (rc < 0) return rc;
-            if (rc == FIR_OK) return fir_keys_unpack(hk, 1, idx, dist);
+            if (rc == FIR_OK) { order.done(); return fir_keys_unpack(hk, 1, idx, dist); }
         }
         rc = try_mfma(g, hq, qb, start_pos, end_pos, g->dkeys, g->stream);              // (the few-query form on large galleries; else 1)
         if (rc < 0) return rc;
@@ -1575,6 +1632,7 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         FIR_HIP(hipGetLastError());
         if (ticket) { if ((rc = wait_ticket(g, hk + qb, ticket))) return rc; }
         else FIR_HIP(hipStreamSynchronize(g->stream));
+        order.done();
         return fir_keys_unpack(hk, qb, idx, dist);
     }
     if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
@@ -1590,6 +1648,7 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     std::vector<uint64_t> keys((size_t)qb);
     FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, (size_t)qb * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
     FIR_HIP(hipStreamSynchronize(g->stream));
+    order.done();
     return fir_keys_unpack(keys.data(), qb, idx, dist);
 }
 
@@ -1617,6 +1676,8 @@ int fir_gallery_classes_of(fir_gallery* g, const int32_t* idx, int32_t n, int32_
     if (!g->cls) return fail(FIR_ERR_STATE, "gallery was created without class labels");
     if (n <= 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);
+    if (order.rc) return order.rc;
     int rc = grow(g->didx, g->didx_cap, (size_t)2 * n);
     if (rc) return rc;
     FIR_HIP(hipMemcpyAsync(g->didx, idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
@@ -1637,7 +1698,10 @@ int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb,
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
-    return topk_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, stream ? (hipStream_t)stream : g->stream);
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    return topk_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, st);
 }
 
 int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
@@ -1649,6 +1713,8 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);
+    if (order.rc) return order.rc;
     if ((rc = grow(g->dkeys, g->dkeys_cap, (size_t)qb * k))) return rc;
     if ((size_t)qb * g->d * sizeof(float) <= kPinQueryBytes && qb * k <= kBlock && qb < 8 && !g->profiling) {
         // small call (below the candidate-list form, which synchronises by itself): pinned queries in, keys + ticket out, as in fir_search_top1
@@ -1661,6 +1727,7 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         hipLaunchKernelGGL(k_publish_keys, dim3(1), dim3(kBlock), 0, g->stream, g->dkeys, qb * k, hk, ticket);
         FIR_HIP(hipGetLastError());
         if ((rc = wait_ticket(g, hk + qb * k, ticket))) return rc;
+        order.done();
         return fir_keys_unpack(hk, qb * k, idx, dist);
     }
     if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
@@ -1679,6 +1746,7 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     std::vector<uint64_t> keys((size_t)qb * k);
     FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, keys.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
     FIR_HIP(hipStreamSynchronize(g->stream));
+    order.done();
     return fir_keys_unpack(keys.data(), qb * k, idx, dist);
 }
 
@@ -1690,7 +1758,10 @@ int fir_range_distances_dev(fir_gallery* g, const float* d_queries, int32_t qb, 
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
-    return range_dev(g, d_queries, qb, start_pos, end_pos, d_out, stream ? (hipStream_t)stream : g->stream);
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    return range_dev(g, d_queries, qb, start_pos, end_pos, d_out, st);
 }
 
 int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, float* out) {
@@ -1700,6 +1771,8 @@ int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);
+    if (order.rc) return order.rc;
     if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
     if ((rc = grow(g->dout, g->dout_cap, (size_t)qb * g->n))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
@@ -1735,6 +1808,8 @@ int fir_profile_read(fir_gallery* g, float* ms, int32_t cap, int32_t* count, dou
 int fir_gallery_sync(fir_gallery* g) {
     if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
     FIR_HIP(hipSetDevice(g->device));
+    const int rc = fir_gallery_wait_calls_(g);      // the most recent call, on whatever stream it was given (and so every call before it)
+    if (rc) return rc;
     FIR_HIP(hipStreamSynchronize(g->stream));
     return FIR_OK;
 }
@@ -1743,6 +1818,8 @@ int fir_gallery_value_range(fir_gallery* g, int32_t* gallery_plain, int32_t* las
     if (!g || !gallery_plain || !last_queries_plain) return fail(FIR_ERR_ARG, "fir_gallery_value_range: null argument");
     FIR_HIP(hipSetDevice(g->device));
     int32_t h[2] = {0, 0};
+    const int rc = fir_gallery_wait_calls_(g);
+    if (rc) return rc;
     FIR_HIP(hipStreamSynchronize(g->stream));
     FIR_HIP(hipMemcpy(h, g->range, sizeof h, hipMemcpyDeviceToHost));
     *gallery_plain = h[0] == 0;

@@ -522,6 +522,8 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
     int rc = fir_gallery_info(g, nullptr, nullptr, &metric, nullptr);
     if (rc) return rc;
     DEM_HIP(hipSetDevice(v.device));
+    FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
+    if (order.rc) return order.rc;
     // candidates per wave: 4 while the workgroup's 1 + 16 rows fit 64 KiB of LDS (d <= 960), else 1; rows beyond 2 048 features
     // go through LDS in pieces of 512 float4
     const int cpw = (size_t)17 * dp4 * 16 <= 64 * 1024 ? 4 : 1;

@@ -1847,6 +1847,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
 int fir_gemm_destroy(fir_gemm* m) {
     if (!m) return FIR_OK;
     (void)hipSetDevice(m->v.device);
+    (void)fir_gallery_wait_calls_(m->g);      // calls queued on the callers' streams may still use what is freed below
     if (m->v.stream || !m->f64) (void)hipStreamSynchronize(m->v.stream);
     if (m->side) { (void)hipStreamSynchronize(m->side); (void)hipStreamDestroy(m->side); }
     for (int b = 0; b < 2; ++b) {
@@ -1971,6 +1972,8 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     if (qb == 0) return FIR_OK;
     GEMM_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
+    FirCallOrder order(m->g, st);   // this state's scratch, and the gallery's, is shared with every other call on the gallery
+    if (order.rc) return order.rc;
     const int d = m->feat;          // features compared
     const int qs = m->v.d;          // floats between consecutive queries (and gallery rows): the whole row
     const int64_t n = m->v.n;
@@ -2363,6 +2366,8 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (m->precision != FIR_GEMM_F16) return gemm_fail(FIR_ERR_ARG, "the few-query form needs the fp16 copy");
     GEMM_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
+    FirCallOrder order(m->g, st);
+    if (order.rc) return order.rc;
     const int d = m->feat, qs = m->v.d;
     const int64_t n = m->v.n;
     if (n == 0) return fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, d, d_keys, st);

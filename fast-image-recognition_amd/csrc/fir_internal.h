@@ -17,6 +17,38 @@ struct fir_gallery_view {
     hipStream_t stream;     // the handle's own stream
 };
 extern "C" int fir_gallery_view_(fir_gallery* g, fir_gallery_view* out);
+
+// Call order of one gallery handle (include/fir_amd.h: calls on one handle take effect in call order, whatever stream they are
+// given). Every entry point that queues work on the handle -- or on a fir_gemm state over it: they share its scratch -- holds a
+// FirCallOrder for the call, on the stream the call queues on (host-pointer calls: the handle's own). The outermost one makes that
+// stream wait for the end of the handle's previous call when that call ran on another stream, and records the end of this call
+// on the way out, error returns included; nested ones (entry points other entry points call) do nothing. g may be NULL (no-op).
+// A call that has seen all of its work finish on the device before returning (host-pointer calls) says so with done(): it
+// records nothing, and the next call, whatever its stream, has nothing to wait for.
+extern "C" int fir_gallery_call_begin_(fir_gallery* g, hipStream_t st);
+extern "C" void fir_gallery_call_end_(fir_gallery* g, hipStream_t st, int finished);
+// Host side: block until the handle's most recent call (and so every call before it) has finished on the device. Before anything
+// that frees what calls may still be using, and before reporting.
+extern "C" int fir_gallery_wait_calls_(fir_gallery* g);
+struct FirCallOrder {
+    fir_gallery* g;
+    hipStream_t st;
+    int rc;
+    bool finished = false;
+    FirCallOrder(fir_gallery* g_, hipStream_t st_) : g(g_), st(st_) { rc = fir_gallery_call_begin_(g, st); }
+    ~FirCallOrder() { fir_gallery_call_end_(g, st, finished); }
+    void done() { finished = true; }
+    FirCallOrder(const FirCallOrder&) = delete;
+    FirCallOrder& operator=(const FirCallOrder&) = delete;
+};
+// Runs f when the scope is left, however it is left.
+template <typename F>
+struct FirOnExit {
+    F f;
+    ~FirOnExit() { f(); }
+};
+template <typename F>
+FirOnExit<F> fir_on_exit(F f) { return FirOnExit<F>{f}; }
 extern "C" void fir_set_last_error_(const char* msg);
 // Every environment knob the library honours goes through here: getenv(name), and a set one is remembered (once) in the list
 // fir_gallery_last_dispatch reports in fir_dispatch_info::knobs -- a stray variable in a production environment is visible.

@@ -1201,6 +1201,8 @@ int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32
         return twd_fail(FIR_ERR_ARG, "num_classes=%d outside [5, 7680] (top-5 posteriors, ImageTesting.cpp:141; LDS table)", num_classes);
     if (qb == 0) return FIR_OK;
     TWD_HIP(hipSetDevice(v.device));
+    FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
+    if (order.rc) return order.rc;
     const int n = (int)v.n;
     const int batch = std::min(batch_for(n, 8), std::max(8, (qb + 7) / 8 * 8));
     TWD_SLOT(dq, 0, (size_t)batch * v.d * 4);
@@ -1368,6 +1370,8 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
     if (!(threshold > 0)) return twd_fail(FIR_ERR_ARG, "threshold must be > 0");
     if (qb == 0) return FIR_OK;
     TWD_HIP(hipSetDevice(v.device));
+    FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
+    if (order.rc) return order.rc;
     const int n = (int)v.n;
     // chunks cover [0,256) in steps of reduced_features_count; the reference reads past 256 when the step does not
     // divide it (ImageTesting.cpp:229,250) -- only steps that divide 256 are accepted here

@@ -93,7 +93,18 @@ int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_
 int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                     int32_t* idx, float* dist);
 
-/* Device-resident form. d_keys[qb] receives one packed key per query:
+/* Streams. The *_dev calls (and the fir_gemm_search_*_keys_dev calls below) queue their work on `stream` (NULL: the handle's own
+ * stream) and, but for the forms noted below that synchronise `stream` once, return without waiting for it. Calls on ONE gallery handle -- and on the fir_gemm states over it, which share its
+ * scratch -- take effect in call order whatever stream each is given: a call on another stream than the handle's previous call
+ * first makes its stream wait for that call's end (a device-side wait: the host does not block), and host-pointer calls count as
+ * calls on the handle's own stream. Calls on the same stream pay nothing for this but one event record each. Calls on different
+ * handles are independent. What a call reads and writes through the caller's pointers is ordered on `stream` only: the caller
+ * makes `stream` wait for whatever produced the queries, and waits for `stream` (or fir_gallery_sync) before reading the keys.
+ * fir_gallery_sync, fir_gallery_destroy, fir_gemm_destroy, and the settings that free a matrix-core state
+ * (fir_gallery_set_large_batch_mfma(g, 0), fir_gallery_set_shadow_copies, fir_gallery_set_row_offset) first wait on the host
+ * for the handle's most recent call.
+ *
+ * Device-resident form. d_keys[qb] receives one packed key per query:
  *   (orderable(float bits of distance) << 32) | uint32(row index + row offset),
  * FIR_KEY_NONE when no row qualifies. Keys order exactly like (distance, index), so the minimum
  * of the keys of several row shards is the reference's answer on the whole gallery: reduce them
@@ -453,7 +464,8 @@ int fir_gallery_last_dispatch(fir_gallery* g, fir_dispatch_info* out);
  * search on this handle. Synchronises the handle's stream. */
 int fir_gallery_value_range(fir_gallery* g, int32_t* gallery_plain, int32_t* last_queries_plain);
 
-/* Block until all work queued by this handle is done. */
+/* Block until all work queued by this handle is done: its most recent call, on whatever stream it was given, and with it every
+ * earlier call (see "Streams" above fir_search_top1_keys_dev). */
 int fir_gallery_sync(fir_gallery* g);
 
 /* Tunables (for experiments). queries_per_pass: 1, 2, 4, 8 or 16; 0 keeps the current setting, < 0 returns to the
