@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/fir_amd.h"
@@ -516,7 +517,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_bf16_wide(const ui
     const int units = dk16 / kUnitW;
     int64_t rg = blockIdx.x;
     if (rg >= nrg) return;                           // uniform per workgroup
-    // The gallery stream is a double buffer of kUnitW k-blocks (see k_gemm_proxy_f16): all loads of the next unit -- of this
+    // The gallery stream is a double buffer of kUnitW k-blocks (see k_gemm_proxy_f16x): all loads of the next unit -- of this
     // row block or of the wave's next one -- leave before the 96 MFMAs of the current unit.
 #define FIR_W_BLOCK(RG) (gb + (size_t)(((RG) * wpb + wave) < rb_end ? ((RG) * wpb + wave) : rb_end - 1) * dk16 * 128 + lane)
     const uint4* a_cur = FIR_W_BLOCK(rg);            // inactive waves stream a valid block and drop it
@@ -599,9 +600,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_bf16_wide(const ui
 // the exact scan like any other. Operands are scaled by powers of two into fp16's normal range (the gallery by one
 // factor, every query by its own; undone per query column in the epilogue, exact), so rounding is relative (2^-11 per
 // operand) for every element within 2^-27 of the largest; smaller ones lose at most 2^-38 of that largest value each.
-// The query tile (4 blocks x 32 k-blocks x 1 KiB = 128 KiB at 512 features) stays in LDS for a whole pass when d <= 512;
-// the gallery stream is double-buffered sixteen k-blocks (16 KiB per wave) at a time and runs on into the wave's NEXT
-// row block, so it never drains between row groups.
+// The query tile (128 queries x 32 k-blocks x 1 KiB = 128 KiB at 512 features) stays in LDS for a whole pass when d <= 512;
+// the gallery stream is double-buffered and runs on into the wave's NEXT row block, so it never drains between row groups.
+// The kernels are in fir_gemm_f16x.h; what follows here is shared with fir_gemm_fb.h and fir_gemm_f64.h.
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f16x8 as_f16x8(const uint4 v) {
@@ -625,35 +626,6 @@ __global__ void __launch_bounds__(256) k_gemm_absmax(const float4* __restrict__ 
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax((unsigned int*)out, __float_as_uint(m));     // non-negative floats order like their bits
-}
-
-// tiled f32 gallery * scale (a power of two) -> gh[(rb * dk16 + kb)][lane] (uint4 = 8 fp16), round to nearest even
-__global__ void __launch_bounds__(256) k_gemm_pack_gallery_f16(const float4* __restrict__ gal4, int64_t n, int dp4, int dk16, float scale,
-                                                                uint4* __restrict__ gh, int kmax) {
-    // kmax: features [0, kmax) of every row are packed, the rest of the fragments is zero (kmax = dp4 * 4: the whole row)
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (rb, kb, lane)
-    const int64_t rblocks = (n + 31) / 32;
-    if (o >= rblocks * dk16 * 64) return;
-    const int l = (int)(o & 63);
-    const int64_t t = o >> 6;
-    const int kb = (int)(t % dk16);
-    const int64_t rb = t / dk16;
-    const int64_t row = rb * 32 + (l & 31);
-    const int h = l >> 5;
-    f16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = 16 * kb + 8 * h + j;
-        float x = 0.f;
-        if (row < n && k < kmax) {
-            const float4 g = gal4[((row >> 6) * dp4 + (k >> 2)) * 64 + (row & 63)];
-            x = (k & 3) == 0 ? g.x : (k & 3) == 1 ? g.y : (k & 3) == 2 ? g.z : g.w;
-        }
-        v[j] = (_Float16)(x * scale);
-    }
-    uint4 u;
-    __builtin_memcpy(&u, &v, 16);
-    gh[o] = u;
 }
 
 // Per query (one wave each): |q|^2, its own power-of-two scale qmul (largest |q_k| -> [2^13, 2^14)) and
@@ -716,293 +688,7 @@ __global__ void __launch_bounds__(64) k_gemm_qprep_f16(const float* __restrict__
     }
 }
 
-// queries * qmul -> qh[((pair * 4 + jb) * dk16 + kb)][lane] (uint4 = 8 fp16); blockIdx.y = pair of 64-query passes
-__global__ void __launch_bounds__(256) k_gemm_pack_queries_f16(const float* q, int nq, int d, int dk16, const float* __restrict__ qmul, uint4* qh,
-                                                                int qstride) {
-    const int q_base = (int)blockIdx.y * 2 * kQT;
-    qh += (size_t)blockIdx.y * 4 * dk16 * 64;
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= 4 * dk16 * 64) return;
-    const int l = o & 63;
-    const int t = o >> 6;
-    const int kb = t % dk16, jb = t / dk16;
-    const int qi = q_base + jb * 32 + (l & 31), h = l >> 5;
-    const float mul = qi < nq ? qmul[qi] : 0.f;
-    f16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = 16 * kb + 8 * h + j;
-        const float x = (qi < nq && k < d) ? q[(size_t)qi * qstride + k] : 0.f;
-        v[j] = (_Float16)(x * mul);
-    }
-    uint4 u;
-    __builtin_memcpy(&u, &v, 16);
-    qh[o] = u;
-}
-
-// One wave: 32 rows x 128 queries. MODE 0: proxies of rows [row_begin, row_end) -> sample; MODE 1: append rows below tau.
-// Dynamic LDS: kHalfLds. blockIdx.y = pair of passes; all per-pass scratch is laid out pass-major (128 consecutive queries).
-// dk16 is a multiple of kRing here (the fp16 fragments are padded to 256-feature units). The gallery stream is a double
-// buffer of kRing k-blocks (16 KiB per wave, 128 KiB per CU in flight): the loads of the NEXT unit -- the next half of this
-// row block, or the first half of the wave's next row block -- are all issued before the sixteen MFMA steps of the current
-// one, so the only wait per unit is at its end, 2048 MFMA cycles after the loads left. (A ring that reloads each slot
-// right after use needs counted waits inside a loop, which the compiler turns into vmcnt(0) per step: one memory latency
-// per k-block -- measured 358 us per pass against 158 us of gallery stream.)
-// STREAMED = 1 (rows longer than 512 features: the 128-query tile does not fit LDS): the query fragments go through two
-// 64-KiB LDS buffers of one unit (16 k-blocks) each, filled by global_load_lds (no registers, asynchronous): the slab of
-// the NEXT unit is requested before the current unit's MFMAs, lands under them, and one workgroup barrier per unit
-// publishes it. (Staging slabs with ordinary loads between two barriers, as the resident form does once per pass, cost
-// 40 % at d = 1280: 740 us per pass against 394 us of gallery stream.)
-template <int MODE, int STREAMED>
-__global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* qh,
-                                                                   const float* __restrict__ qinv, int64_t n, int64_t row_begin, int64_t row_end,
-                                                                   int dk16, const float* tau, unsigned long long* lists, int* counts,
-                                                                   float* sample, int sample_rows, int share, int nt) {
-    extern __shared__ __attribute__((aligned(16))) uint4 lqb[];
-    __shared__ float tau_s[2 * kQT], qinv_s[2 * kQT];
-    // Which pair of passes (128 queries) and which row groups this workgroup takes.
-    // share == 0: blockIdx.y = pair, row groups blockIdx.x, + gridDim.x, ... (the sample pass).
-    // share == P (a power of two, the full pass): ONE workgroup per CU, all resident at once; the P pairs of the launch read the
-    // gallery TOGETHER: the row groups are cut into gridDim.x / P contiguous ranges and P workgroups -- one per pair, placed on the
-    // same XCD (blocks b and b + 8 share one) -- walk the same range at the same time, so the fp16 gallery stream leaves HBM once
-    // per P * 128 queries and the other P - 1 readers hit in the XCD's L2 (or, when they drift apart, in the Infinity Cache).
-    int pair_of_wg = (int)blockIdx.y;
-    int64_t rg_first = blockIdx.x, rg_step = gridDim.x, rg_last = -1;      // rg_last < 0: up to nrg
-    if (share > 0) {
-        const int w = (int)blockIdx.x, xcd = w & 7, slot = w >> 3;
-        const int ranges = ((int)gridDim.x >> 3) / share * 8;             // whole groups of `share` slots per XCD
-        const int range = xcd + 8 * (slot / share);
-        if (range >= ranges) return;                                       // uniform per workgroup
-        pair_of_wg = slot % share;
-        const int64_t nrg_all = (((row_end + 31) / 32 - row_begin / 32) + (blockDim.x >> 6) - 1) / (blockDim.x >> 6);
-        rg_first = nrg_all * range / ranges;
-        rg_last = nrg_all * (range + 1) / ranges;
-        rg_step = 1;
-    }
-    {
-        const size_t pr = (size_t)pair_of_wg;
-        qh += pr * 4 * dk16 * 64;
-        qinv += pr * 2 * kQT;
-        tau += pr * 2 * kQT;
-        lists += pr * 2 * kQT * kListCap;
-        counts += pr * 2 * kQT;
-        sample += pr * 2 * kQT * ((sample_rows + 31) / 32);      // MODE 0 writes one minimum per (row block, query)
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wpb = blockDim.x >> 6;
-    if (threadIdx.x < 2 * kQT) {
-        tau_s[threadIdx.x] = MODE == 1 ? tau[threadIdx.x] : 0.f;
-        qinv_s[threadIdx.x] = qinv[threadIdx.x];
-    }
-    const int64_t rb_begin = row_begin / 32, rb_end = (row_end + 31) / 32;
-    const int64_t nrg = (rb_end - rb_begin + wpb - 1) / wpb;
-    const int units = dk16 / kRing;                  // units of kRing k-blocks per row block
-    const int nslab = (dk16 + kSlabH - 1) / kSlabH;
-    const int64_t rg_end = rg_last >= 0 ? rg_last : nrg;
-    int64_t rg = rg_first;
-    if (rg >= rg_end) return;                        // uniform per workgroup
-    // streamed once per launch from HBM: non-temporal; shared between the pairs of a launch: ordinary loads, so that the line
-    // stays in L2 for the other readers
-#define FIR_H_LD(P) (nt ? ld_nt(P) : *(P))
-#define FIR_H_BLOCK(RG) (gh + (size_t)((rb_begin + (RG) * wpb + wave) < rb_end ? (rb_begin + (RG) * wpb + wave) : rb_end - 1) * dk16 * 64 + lane)
-    const uint4* a_cur = FIR_H_BLOCK(rg);            // waves past the last row block stream a valid one and drop the result
-    uint4 cur[kRing], nxt[kRing];
-#pragma unroll
-    for (int u = 0; u < kRing; ++u) cur[u] = FIR_H_LD(a_cur + (size_t)u * 64);
-    constexpr int kUnitsPerSlab = kSlabH / kRing;
-    const bool resident = !STREAMED && nslab == 1;   // the whole 128-query tile stays in LDS for the launch (d <= 512)
-    // STREAMED: unit hq of the query tile -> LDS buffer bsel; every wave moves its share of the 4 * kRing one-KiB pieces
-    // (piece = (query block jb, k-block kb): 64 lanes x 16 B, contiguous in qh and in LDS)
-    auto request_slab = [&](int hq, int bsel) {
-        uint4* dst = lqb + (size_t)bsel * 4 * kRing * 64;
-        const int per_wave = 4 * kRing / wpb;
-        for (int c = 0; c < per_wave; ++c) {
-            const int piece = wave * per_wave + c, jb = piece / kRing, kb = piece - jb * kRing;
-            __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(qh + ((size_t)jb * dk16 + (size_t)hq * kRing + kb) * 64 + lane),
-                                             (void __attribute__((address_space(3)))*)(dst + (size_t)(kb * 4 + jb) * 64), 16, 0, 0);
-        }
-    };
-    int tsel = 0;                                    // STREAMED: LDS buffer of the current unit
-    if (STREAMED) {
-        request_slab(0, 0);
-        __builtin_amdgcn_s_waitcnt(0);               // (also the prologue's gallery loads: once per kernel)
-        __syncthreads();
-    } else if (resident) {
-        for (int i = threadIdx.x; i < 4 * dk16 * 64; i += blockDim.x) {
-            const int jb = i / (dk16 * 64), r = i - jb * dk16 * 64;
-            lqb[(size_t)((r >> 6) * 4 + jb) * 64 + (r & 63)] = qh[(size_t)jb * dk16 * 64 + r];
-        }
-        __syncthreads();
-    }
-    // LDS image of the query tile: k-block major, the four query blocks of a k-block side by side -- (kb * 4 + jb) * 1 KiB -- so that
-    // the reads of a unit sit within the 64 KiB an LDS instruction's immediate offset reaches from ONE base register
-    constexpr int jstride = 64;                                      // uint4s between the query blocks of a k-block
-    // the four query fragments of the k-block the next MFMA group consumes: always read one group ahead
-    uint4 b0, b1, b2, b3, c0, c1, c2, c3;
-    if (resident) { const uint4* bu = lqb + lane; b0 = bu[0]; b1 = bu[jstride]; b2 = bu[2 * jstride]; b3 = bu[3 * jstride]; }
-    for (; rg < rg_end; rg += rg_step) {
-        const int64_t rb = rb_begin + rg * wpb + wave;
-        const bool active = rb < rb_end;
-        const int64_t rgn = rg + rg_step;
-        const uint4* a_nxt = FIR_H_BLOCK(rgn < rg_end ? rgn : rg);
-        f32x16 acc0 = {0.f}, acc1 = {0.f}, acc2 = {0.f}, acc3 = {0.f};
-        float4 gn4[4];                               // this lane's 16 squared row norms (rows 8g + 4h + 0..3 of the block), for the epilogue
-        const bool full_block = active && rb * 32 >= row_begin && rb * 32 + 32 <= row_end && rb * 32 + 32 <= n && (MODE == 1 || rb * 32 + 32 <= sample_rows);
-        // one unit of kRing k-blocks: the loads of the NEXT unit go into N while the MFMAs consume C. Units are taken in pairs with
-        // the two buffers swapping roles, so that no register copies sit between the MFMAs (a `cur = nxt` copy per unit was one
-        // vector instruction per MFMA on a SIMD whose vector issue the MFMAs and the epilogue already fill to ~85 %)
-        auto unit = [&](uint4 (&C)[kRing], uint4 (&N)[kRing], int h) {
-            const uint4* src = h + 1 < units ? a_cur + (size_t)(h + 1) * kRing * 64 : a_nxt;
-            if (STREAMED) request_slab(h + 1 < units ? h + 1 : 0, tsel ^ 1);   // its last readers passed the barrier that ended the previous unit
-            if (nt) {
-#pragma unroll
-                for (int u = 0; u < kRing; ++u) N[u] = ld_nt(src + (size_t)u * 64);
-            } else {
-#pragma unroll
-                for (int u = 0; u < kRing; ++u) N[u] = src[(size_t)u * 64];
-            }
-            if (h == units - 1 && full_block) {
-                const float4* gp = (const float4*)(gnorm + rb * 32 + 4 * (lane >> 5));
-#pragma unroll
-                for (int g = 0; g < 4; ++g) gn4[g] = gp[2 * g];
-            }
-            if (!STREAMED && !resident && (h % kUnitsPerSlab) == 0) {      // forced non-streamed form with rows longer than a slab: re-stage
-                const int k0 = h * kRing;
-                const int kw = dk16 - k0 < kSlabH ? dk16 - k0 : kSlabH;
-                __syncthreads();                                            // everyone is done with the previous slab
-                for (int i = threadIdx.x; i < 4 * kw * 64; i += blockDim.x) {
-                    const int jb = i / (kw * 64), r = i - jb * kw * 64;
-                    lqb[(size_t)((r >> 6) * 4 + jb) * 64 + (r & 63)] = qh[((size_t)jb * dk16 + k0) * 64 + r];
-                }
-                __syncthreads();
-            }
-            const uint4* bq = STREAMED ? lqb + lane + (size_t)tsel * 4 * kRing * 64 : lqb + lane + (size_t)(h % kUnitsPerSlab) * kRing * 4 * 64;
-            if (!resident) { b0 = bq[0]; b1 = bq[jstride]; b2 = bq[2 * jstride]; b3 = bq[3 * jstride]; }
-            // where the fragments of the k-block AFTER this unit live, when that is known now (resident tile): the pipeline runs on
-            // through the unit boundary and through the epilogue into the wave's next row block
-            const uint4* bq_after = lqb + lane + (size_t)((h + 1 < units ? h + 1 : 0) % kUnitsPerSlab) * kRing * 4 * 64;
-            // two sets of query fragments, (b0..b3) and (c0..c3), swap roles every k-block: the reads of k-block u + 1 go into the
-            // set the MFMAs of k-block u do not use. (A rotation `b = next` through one set was compiled into eight 64-bit
-            // register copies per k-block -- two vector instructions per MFMA on an already full vector issue port.)
-#define FIR_H_STEP(U, X0, X1, X2, X3, Y0, Y1, Y2, Y3)                                                              \
-            {                                                                                                      \
-                if ((U) + 1 < kRing) {                                                                             \
-                    const uint4* bu = bq + (size_t)((U) + 1) * 4 * 64;                                             \
-                    Y0 = bu[0]; Y1 = bu[jstride]; Y2 = bu[2 * jstride]; Y3 = bu[3 * jstride];                      \
-                } else if (resident) {                                                                             \
-                    Y0 = bq_after[0]; Y1 = bq_after[jstride]; Y2 = bq_after[2 * jstride]; Y3 = bq_after[3 * jstride]; \
-                }                                                                                                  \
-                __builtin_amdgcn_sched_barrier(0); /* the four reads of the next group stay ahead of this group's MFMAs */ \
-                const f16x8 av = as_f16x8(C[U]);                                                                   \
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, as_f16x8(X0), acc0, 0, 0, 0);                    \
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, as_f16x8(X1), acc1, 0, 0, 0);                    \
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, as_f16x8(X2), acc2, 0, 0, 0);                    \
-                acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, as_f16x8(X3), acc3, 0, 0, 0);                    \
-            }
-            static_assert(kRing == 8, "the unrolled k-block steps below are written out for kRing = 8");
-            FIR_H_STEP(0, b0, b1, b2, b3, c0, c1, c2, c3)
-            FIR_H_STEP(1, c0, c1, c2, c3, b0, b1, b2, b3)
-            FIR_H_STEP(2, b0, b1, b2, b3, c0, c1, c2, c3)
-            FIR_H_STEP(3, c0, c1, c2, c3, b0, b1, b2, b3)
-            FIR_H_STEP(4, b0, b1, b2, b3, c0, c1, c2, c3)
-            FIR_H_STEP(5, c0, c1, c2, c3, b0, b1, b2, b3)
-            FIR_H_STEP(6, b0, b1, b2, b3, c0, c1, c2, c3)
-            FIR_H_STEP(7, c0, c1, c2, c3, b0, b1, b2, b3)
-#undef FIR_H_STEP
-            if (STREAMED) {
-                __builtin_amdgcn_s_waitcnt(0);       // this wave's pieces of the next slab have landed (they left before N's loads)
-                __syncthreads();                     // ... and everyone's; and nobody still reads the buffer the next request overwrites
-                tsel ^= 1;
-            }
-        };
-        int h = 0;
-        for (; h + 1 < units; h += 2) {
-            unit(cur, nxt, h);
-            unit(nxt, cur, h + 1);
-        }
-        if (h < units) {                             // an odd number of units per row block: the buffers end up swapped once
-            unit(cur, nxt, h);
-#pragma unroll
-            for (int u = 0; u < kRing; ++u) cur[u] = nxt[u];
-        }
-        a_cur = a_nxt;
-        if (!active) continue;
-        if (full_block) {
-            // every row of the block is a live row of the pass: p = |g|^2 - 2 q.g per accumulator, one running minimum per lane and
-            // tile; only a lane whose minimum is below its query's tau looks at its 16 values again
-            const float gnv[16] = {gn4[0].x, gn4[0].y, gn4[0].z, gn4[0].w, gn4[1].x, gn4[1].y, gn4[1].z, gn4[1].w,
-                                   gn4[2].x, gn4[2].y, gn4[2].z, gn4[2].w, gn4[3].x, gn4[3].y, gn4[3].z, gn4[3].w};
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) {
-                const int q = jb * 32 + (lane & 31);
-                const float m2 = 2.0f * qinv_s[q];
-                const float tq = tau_s[q];
-                float pv[16];
-                float mn = __builtin_huge_valf();
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const float dot = jb == 0 ? acc0[reg] : jb == 1 ? acc1[reg] : jb == 2 ? acc2[reg] : acc3[reg];
-                    pv[reg] = __builtin_fmaf(-m2, dot, gnv[reg]);            // one instruction: the proxy only has to be the same number wherever it is compared
-                    mn = fminf(mn, pv[reg]);                                 // NaN never enters, like k_gemm_tau's ordering
-                }
-                if (MODE == 1) {
-                    if (mn < tq) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            if (pv[reg] < tq) {
-                                const int64_t row = rb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                                const int slot = atomicAdd(&counts[q], 1);
-                                if (slot < kListCap) lists[(size_t)q * kListCap + slot] = fir::key_pack(pv[reg], (uint32_t)row);
-                            }
-                        }
-                    }
-                } else {
-                    const float o = __shfl_xor(mn, 32, 64);
-                    mn = o < mn ? o : mn;
-                    if (lane < 32) sample[(size_t)(rb - rb_begin) * (2 * kQT) + q] = mn;
-                }
-            }
-            continue;
-        }
-        // a block that straddles the end of the rows (or of the sample): row by row
-        const int64_t nrow = rb * 32 + (lane & 31);
-        const float gn_lane = nrow < n ? gnorm[nrow] : 0.0f;
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-            const int q = jb * 32 + (lane & 31);
-            const float m2 = 2.0f * qinv_s[q];
-            const float tq = tau_s[q];
-            float mn = __builtin_huge_valf();
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int roff = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                const int64_t row = rb * 32 + roff;
-                const float gn = __shfl(gn_lane, roff, 64);
-                if (row >= n || row < row_begin || row >= row_end) continue;
-                const float dot = jb == 0 ? acc0[reg] : jb == 1 ? acc1[reg] : jb == 2 ? acc2[reg] : acc3[reg];
-                const float p = gn - m2 * dot;
-                if (MODE == 0) {
-                    if (row < sample_rows) mn = p < mn ? p : mn;         // NaN never enters, like k_gemm_tau's ordering
-                } else if (p < tq) {
-                    const int slot = atomicAdd(&counts[q], 1);
-                    if (slot < kListCap) lists[(size_t)q * kListCap + slot] = fir::key_pack(p, (uint32_t)row);
-                }
-            }
-            if (MODE == 0) {
-                // what tau needs from the sample is one minimum per (row block, query): sample[(row block) * 128 + query],
-                // the two half-waves hold the block's rows 4..7 mod 8 and 0..3 mod 8
-                const float o = __shfl_xor(mn, 32, 64);
-                mn = o < mn ? o : mn;
-                if (lane < 32) sample[(size_t)(rb - rb_begin) * (2 * kQT) + q] = mn;
-            }
-        }
-    }
-#undef FIR_H_BLOCK
-#undef FIR_H_LD
-}
-
 #include "fir_gemm_f16x.h"
-#include "fir_gemm_regtile.h"
 
 // tau[q] = kCand-th smallest sampled proxy, nudged up so that ties with it are appended too. One block per
 // query, ONE pass over the samples: every thread keeps its kCand smallest keys sorted in registers, then kCand
@@ -1016,7 +702,7 @@ __global__ void __launch_bounds__(256) k_gemm_tau(const float* __restrict__ samp
     // kth_window (top-K, K <= kCand): the bound is the kCand-th smallest sampled proxy PLUS one window -- at least K rows
     // lie at or below the kCand-th smallest, and every row within a window of the K-th best one must be appended for the
     // certificate of rank K to be able to hold
-    // qgroup > 1 (fp16 flow): the sample of a group of qgroup queries is laid out [value][query of the group] and holds one
+    // qgroup > 1 (the fp16 order-statistic flow, removed; every caller passes 1): the sample of a group of qgroup queries is laid out [value][query of the group] and holds one
     // MINIMUM per 32-row block instead of every proxy: the kCand-th smallest block minimum still has kCand sampled rows at or
     // below it, which is all the append pass needs, and is within a rank or two of the exact order statistic
     __shared__ unsigned long long red[4];
@@ -1208,71 +894,10 @@ __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __
 // ---- calls of 1..8 queries against a gallery that does not fit the caches ----
 // Such a call is one gallery pass whatever it computes, so it is bound by the bytes of that pass: the exact f32 scan reads n*d*4
 // (337 us at 1M x 512), this nomination scan reads the fp16 copy, n*d*2. No matrix cores (eight queries would fill 1/16 of a
-// tile): v_dot2c_f32_f16 on the same fragments, lane l = row l & 31, k-half l >> 5. Every proxy is written out (n floats per
+// tile): v_dot2c_f32_f16 on the same fragments (k_gemm_scan_f16x, fir_gemm_f16x.h). Every proxy is written out (n floats per
 // query) together with the smallest one per query; tau = smallest proxy of ALL rows + one window (k_gemm_tau_min), the rows
 // below it are collected (k_gemm_select) and re-ranked exactly with the usual certificate (k_gemm_rerank) -- which holds by
 // construction here: every excluded row is a full window above the smallest proxy.
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-template <int NQ>
-__global__ void __launch_bounds__(256) k_gemm_scan_f16(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* __restrict__ qh,
-                                                        const float* __restrict__ qinv, int64_t n, int dk16, float* __restrict__ proxies,
-                                                        unsigned int* __restrict__ smin) {
-    extern __shared__ __attribute__((aligned(16))) uint4 qsf[];           // [k-block][k-half][query]
-    for (int idx = threadIdx.x; idx < dk16 * 2 * NQ; idx += blockDim.x) {
-        const int i = idx % NQ, h = (idx / NQ) & 1, kb = idx / (2 * NQ);
-        qsf[idx] = qh[(size_t)kb * 64 + 32 * h + i];                      // queries 0..7 sit in query block 0 of the pair's fragments
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, h = lane >> 5;
-    const int64_t gw = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const int64_t nrb = (n + 31) / 32;
-    float m2[NQ], smallest[NQ];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) { m2[i] = 2.0f * qinv[i]; smallest[i] = __builtin_huge_valf(); }
-    for (int64_t rb = gw; rb < nrb; rb += nw) {
-        const uint4* a = gh + (size_t)rb * dk16 * 64 + lane;
-        float acc[NQ];
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) acc[i] = 0.f;
-        for (int kb0 = 0; kb0 < dk16; kb0 += 8) {                          // dk16 is a multiple of 8
-            uint4 g[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g[u] = ld_nt(a + (size_t)(kb0 + u) * 64);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                f16x2 gv[4];
-                __builtin_memcpy(gv, &g[u], 16);
-#pragma unroll
-                for (int i = 0; i < NQ; ++i) {
-                    const uint4 qq = qsf[((kb0 + u) * 2 + h) * NQ + i];
-                    f16x2 qv[4];
-                    __builtin_memcpy(qv, &qq, 16);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) acc[i] = __builtin_amdgcn_fdot2(gv[t], qv[t], acc[i], false);
-                }
-            }
-        }
-        const int64_t row = rb * 32 + (lane & 31);
-        const float gn = row < n ? gnorm[row] : 0.f;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-            const float dot = acc[i] + __shfl_xor(acc[i], 32, 64);        // the two k-halves of the row
-            if (lane < 32 && row < n) {
-                const float p = __builtin_fmaf(-m2[i], dot, gn);
-                proxies[(size_t)i * n + row] = p;
-                smallest[i] = fminf(smallest[i], p);                       // NaN never enters
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        float v = smallest[i];
-#pragma unroll
-        for (int off = 16; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-        if (lane == 0 && v < __builtin_huge_valf()) atomicMin(&smin[i], fir::f32_orderable(v));
-    }
-}
-
 // lists[q] <- every row whose proxy is below tau[q] (blockIdx.y = query)
 __global__ void __launch_bounds__(256) k_gemm_select(const float* __restrict__ proxies, int64_t n, const float* __restrict__ tau,
                                                       unsigned long long* __restrict__ lists, int* __restrict__ counts) {
@@ -1532,7 +1157,7 @@ struct fir_gemm {
     float4* qm[2] = {nullptr, nullptr};
     float* qnorm[2] = {nullptr, nullptr};
     float* tau[2] = {nullptr, nullptr};
-    float* sample = nullptr;
+    float* sample = nullptr;    // f32 / bf16: every sampled proxy of a super-batch (k_gemm_tau), allocated on first use
     unsigned long long* lists[2] = {nullptr, nullptr};
     int* counts[2] = {nullptr, nullptr};
     hipStream_t side = nullptr;
@@ -1555,42 +1180,80 @@ struct fir_gemm {
     int fb_grid = 0;
     int64_t passes = 0;
     int rerank_group = kRerankGroup;      // candidate rows the re-rank stages in LDS at a time
-    int streamed = -1;                    // fp16: query slabs through the LDS double buffer (-1: when the tile does not fit, d > 512)
     bool wide = true;                     // bf16: pairs of passes through k_gemm_proxy_bf16_wide (FIR_GEMM_WIDE=0 turns it off)
-    unsigned int* smin[2] = {nullptr, nullptr};   // register-tile flow: smallest sampled proxy per query (orderable bits)
+    unsigned int* smin[2] = {nullptr, nullptr};   // fp16 sample flow: smallest sampled proxy per query (orderable bits; top-K: per subset)
     int rt_sample_rows = 0;                // ... over this many rows (n / 32)
-    int regtile = -1;                     // fp16 full pass through the register-tile kernel: -1 = where it measured faster (rows up to 256 features), 0 / 1 = never / wherever it exists (FIR_GEMM_REGTILE)                  // fp16 full pass: query fragments in registers, gallery through the LDS-DMA ring (FIR_GEMM_REGTILE=0: the LDS-tile kernel)
-    int mfma16 = 0;                       // fp16: both operands in the 16-row fragment order, every pass on v_mfma_f32_16x16x32_f16 (fir_gemm_f16x.h): the default since it was
-                                          // measured against the 32x32x16 kernels at the same wave tile (profiles/r03_mfma_shape_ab.txt); FIR_GEMM_MFMA16=0 brings those back
     bool f64 = false;                     // the nomination state of a float64 training set owned by fir_cls.hip (fir_gemm_f64.h)
     const double2* gal2 = nullptr; int dp2 = 0;
+    int adaptive = 1;                     // fp16 top-1: the append threshold is found during the full pass (k_gemm_proxy_f16x<3, *>), no sample pass
+                                          // (profiles/r03_adaptive_threshold.txt); FIR_GEMM_ADAPTIVE=0: the sample flow, 2: the pass on the way whatever the shape
     int adaptive_topk = 1;                // ... and for the K nearest rows (k_gemm_proxy_f16x<4, *>: K slot minima per query); FIR_GEMM_ADAPTIVE_TOPK=0: the sample flow
-    int adaptive = 1;                     // 16-row top-1 flow: the append threshold is found during the full pass (k_gemm_proxy_f16x<3, *>), no sample pass
-                                          // (profiles/r03_adaptive_threshold.txt); FIR_GEMM_ADAPTIVE=0: the sample flow
     float* awin[2] = {nullptr, nullptr};  // ... its per-query windows
     unsigned int* aT[2] = {nullptr, nullptr};   // ... and the ranks' shared T (float bits)
-    float erel_scale = 1.0f;              // AUDIT KNOB, never set in production: the certificate's relative error bound is multiplied by this (FIR_GEMM_EREL_SCALE);
-                                          // tests/test_gpu_gemm.py shows that a bound shrunk to a quarter returns a wrong row on a crafted near-tie, i.e. that the suite can see an unsound bound
-    int dbg_block = kGemmBlock;           // timing experiments (audit build, FIR_GEMM_DBG_BLOCK=256): the resident adaptive pass with four waves per workgroup = ONE wave per SIMD
+    // AUDIT KNOBS, honoured by the audit build only and never set in production (gemm_read_knobs_)
+    float erel_scale = 1.0f;              // the certificate's relative error bound is multiplied by this (FIR_GEMM_EREL_SCALE); tests/test_gpu_gemm.py shows that a bound
+                                          // shrunk to a quarter returns a wrong row on a crafted near-tie, i.e. that the suite can see an unsound bound
+    int dbg_block = kGemmBlock;           // timing experiments (FIR_GEMM_DBG_BLOCK=256): the resident adaptive pass with four waves per workgroup = ONE wave per SIMD
     int dbg_skip = 0;                     // timing experiments: bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no query-fragment re-reads (FIR_GEMM_DBG_SKIP; wrong answers)
-    int no_block_bound = 0;               // A/B: the append forms compute all eight proxies of every query block (FIR_GEMM_NO_BLOCK_BOUND)
-    int prio = 0;                         // mfma16 experiment: s_setprio 2 around the MFMA phase of a row block (FIR_GEMM_PRIO)
-    int stagger = 0;                      // mfma16 experiment: the second wave of every SIMD starts half a unit late (FIR_GEMM_STAGGER)
-    int share_streamed = 8;               // ... of them when the query slabs are streamed (FIR_GEMM_SHARE_STREAMED)
-    int few_blocks = 1;                   // calls of <= 32 queries multiply against the live query blocks only (FIR_GEMM_FEW_BLOCKS=0: the whole tile, for A/B runs)
-    int share_max = 16;                   // fp16: up to this many pairs of passes (x 128 queries) read the gallery together in one launch (FIR_GEMM_SHARE; 0 = the old one-pair-at-a-time grid)
+    int adapt_dbg = 0;                    // nt_flags bits 2, 3 of the adaptive pass (FIR_GEMM_ADAPT_DBG): 1 = no refresh, 2 = no exchange of the bound between workgroups (still
+                                          // sound: a looser bound appends more -- this is how the tests drive lists into overflow and the second-chance pass on benign data)
+    bool debug_counts = false;            // appended rows per query of a call's last super-batch on stderr (FIR_GEMM_DEBUG_COUNTS; synchronises)
+    std::string dump_phases;              // with FIR_GEMM_DBG_SKIP=256: the file the load-burst timestamps of the last super-batch's first pair go to (FIR_GEMM_DUMP_PHASES)
 };
 
+// The knobs every kind of state honours (this file's and fir_gemm_f64.h's): each is read once, when the state is created.
+static void gemm_read_knobs_(fir_gemm* m) {
+    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE")) m->adaptive = std::atoi(w);
+    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE_TOPK")) m->adaptive_topk = std::atoi(w) != 0;
+#ifdef FIR_AUDIT      // knobs that change answers: the audit build only (libfir_amd_audit.so; fir_internal.h)
+    if (const char* w = fir_knob_("FIR_GEMM_DBG_SKIP")) m->dbg_skip = std::atoi(w) & 1023;
+    if (const char* w = fir_knob_("FIR_GEMM_DBG_BLOCK")) m->dbg_block = std::atoi(w) == 256 ? 256 : kGemmBlock;     // timing experiments only: the answers are wrong
+    if (const char* w = fir_knob_("FIR_GEMM_EREL_SCALE")) m->erel_scale = (float)std::atof(w);
+    if (const char* w = fir_knob_("FIR_GEMM_ADAPT_DBG")) m->adapt_dbg = (std::atoi(w) & 3) << 2;
+    if (fir_knob_("FIR_GEMM_DEBUG_COUNTS")) m->debug_counts = true;
+    if (const char* w = fir_knob_("FIR_GEMM_DUMP_PHASES")) m->dump_phases = w;
+#endif
+}
 
+// fp16: up to kShareMax pairs of passes (x 128 queries) read the gallery together in one launch (k_gemm_proxy_f16x, `share`). Rows longer
+// than the LDS tile (query slabs streamed per unit): 16 readers of one range drift apart, kShareStreamed measured better.
+constexpr int kShareMax = 16, kShareStreamed = 8;
+// fp16: rows longer than the 512 features whose 128-query tile fits LDS take the kernels that stream the query slabs (STREAMED = 1)
+static bool gemm_streamed_(const fir_gemm* m) { return m->dk16 > kSlabH; }
+// pairs of passes the next launch takes: the largest power of two within what is left and within cap
+static int launch_pairs_(int left, int cap) {
+    int P = 1;
+    while (P * 2 <= left && P * 2 <= cap) P *= 2;
+    return P;
+}
 
-// the 16-row kernels by (mode, query slabs streamed, odd number of units per row block)
+// The 16-row kernels by (mode, query slabs streamed, odd number of units per row block, live query blocks): ONE table gives the
+// function and the name fir_gallery_last_dispatch reports for it.
 typedef void (*fir_x_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int64_t, int64_t, int, const float*, unsigned long long*, int*, float*,
                          int, int, int, int, unsigned int*, int);
+struct fir_x_entry {
+    int mode, streamed, odd, njb;
+    fir_x_fn fn;
+    const char* name;
+};
+#define FIR_X(M, S, O) {M, S, O, 8, k_gemm_proxy_f16x<M, S, O>, "fir::k_gemm_proxy_f16x<" #M ", " #S ", " #O ">"}
+#define FIR_X_FEW(S, J) {3, S, 0, J, k_gemm_proxy_f16x<3, S, 0, 0, J>, "fir::k_gemm_proxy_f16x<3, " #S ", 0, 0, " #J ">"}
+static const fir_x_entry kXTable[] = {
+    FIR_X(1, 0, 0), FIR_X(1, 0, 1), FIR_X(1, 1, 0), FIR_X(1, 1, 1), FIR_X(2, 0, 0), FIR_X(2, 0, 1), FIR_X(2, 1, 0), FIR_X(2, 1, 1),
+    FIR_X(3, 0, 0), FIR_X(3, 0, 1), FIR_X(3, 1, 0), FIR_X(3, 1, 1), FIR_X(4, 0, 0), FIR_X(4, 0, 1), FIR_X(4, 1, 0), FIR_X(4, 1, 1),
+    FIR_X_FEW(0, 1), FIR_X_FEW(1, 1), FIR_X_FEW(0, 2), FIR_X_FEW(1, 2),     // a call of <= 16 / <= 32 queries (top-1, threshold found on the way)
+};
+#undef FIR_X
+#undef FIR_X_FEW
+// mode: 1 = append below tau, 2 = the sample pass, 3 / 4 = the threshold found on the way (top-1 / the K nearest); njb < 8 exists for
+// mode 3 with an even number of units only, anything else takes the whole tile
+static const fir_x_entry& find_x(int mode, bool streamed, bool odd, int njb = 8) {
+    if (!(mode == 3 && !odd && (njb == 1 || njb == 2))) njb = 8;
+    for (const fir_x_entry& e : kXTable)
+        if (e.mode == mode && e.streamed == (int)streamed && e.odd == (int)odd && e.njb == njb) return e;
+    return kXTable[4 + 2 * (int)streamed + (int)odd];      // (not a mode: as the sample pass)
+}
 static fir_x_fn pick_x(int mode, bool streamed, bool odd, int dbg = 0, int njb = 8) {
-    if (njb < 8 && mode == 3 && !odd && !dbg) {        // a call of <= 16 / <= 32 queries (top-1, threshold found on the way)
-        if (njb == 1) return streamed ? k_gemm_proxy_f16x<3, 1, 0, 0, 1> : k_gemm_proxy_f16x<3, 0, 0, 0, 1>;
-        if (njb == 2) return streamed ? k_gemm_proxy_f16x<3, 1, 0, 0, 2> : k_gemm_proxy_f16x<3, 0, 0, 0, 2>;
-    }
 #ifdef FIR_AUDIT      // (the timing forms are instantiated in the audit build only: the shipped library cannot select them)
     if (dbg && mode == 3 && !streamed && !odd) {       // timing experiments (FIR_GEMM_DBG_SKIP): wrong answers
         switch (dbg & 1023) {
@@ -1611,19 +1274,15 @@ static fir_x_fn pick_x(int mode, bool streamed, bool odd, int dbg = 0, int njb =
         }
     }
 #endif
-    if (mode == 1) return streamed ? (odd ? k_gemm_proxy_f16x<1, 1, 1> : k_gemm_proxy_f16x<1, 1, 0>) : (odd ? k_gemm_proxy_f16x<1, 0, 1> : k_gemm_proxy_f16x<1, 0, 0>);
-    if (mode == 3) return streamed ? (odd ? k_gemm_proxy_f16x<3, 1, 1> : k_gemm_proxy_f16x<3, 1, 0>) : (odd ? k_gemm_proxy_f16x<3, 0, 1> : k_gemm_proxy_f16x<3, 0, 0>);
-    if (mode == 4) return streamed ? (odd ? k_gemm_proxy_f16x<4, 1, 1> : k_gemm_proxy_f16x<4, 1, 0>) : (odd ? k_gemm_proxy_f16x<4, 0, 1> : k_gemm_proxy_f16x<4, 0, 0>);
-    return streamed ? (odd ? k_gemm_proxy_f16x<2, 1, 1> : k_gemm_proxy_f16x<2, 1, 0>) : (odd ? k_gemm_proxy_f16x<2, 0, 1> : k_gemm_proxy_f16x<2, 0, 0>);
+    return find_x(mode, streamed, odd, dbg ? 8 : njb).fn;
 }
-static const char* name_x(bool streamed, bool odd, bool adaptive = false, bool slots = false, int njb = 8) {
-    if (njb < 8 && adaptive && !slots && !odd) {
-        if (njb == 1) return streamed ? "fir::k_gemm_proxy_f16x<3, 1, 0, 0, 1>" : "fir::k_gemm_proxy_f16x<3, 0, 0, 0, 1>";
-        if (njb == 2) return streamed ? "fir::k_gemm_proxy_f16x<3, 1, 0, 0, 2>" : "fir::k_gemm_proxy_f16x<3, 0, 0, 0, 2>";
+// every kernel of the table may take the whole query tile as dynamic LDS
+static hipError_t gemm_x_lds_attr_() {
+    for (const fir_x_entry& e : kXTable) {
+        const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
+        if (err != hipSuccess) return err;
     }
-    if (adaptive && slots) return streamed ? (odd ? "fir::k_gemm_proxy_f16x<4, 1, 1>" : "fir::k_gemm_proxy_f16x<4, 1, 0>") : (odd ? "fir::k_gemm_proxy_f16x<4, 0, 1>" : "fir::k_gemm_proxy_f16x<4, 0, 0>");
-    if (adaptive) return streamed ? (odd ? "fir::k_gemm_proxy_f16x<3, 1, 1>" : "fir::k_gemm_proxy_f16x<3, 1, 0>") : (odd ? "fir::k_gemm_proxy_f16x<3, 0, 1>" : "fir::k_gemm_proxy_f16x<3, 0, 0>");
-    return streamed ? (odd ? "fir::k_gemm_proxy_f16x<1, 1, 1>" : "fir::k_gemm_proxy_f16x<1, 1, 0>") : (odd ? "fir::k_gemm_proxy_f16x<1, 0, 1>" : "fir::k_gemm_proxy_f16x<1, 0, 0>");
+    return hipSuccess;
 }
 
 extern "C" {
@@ -1663,6 +1322,11 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     if (fir_gallery_view_(g, &m->v) != FIR_OK || fir_gallery_tiled_(g, &gp, &m->dp4) != FIR_OK) { delete m; return gemm_fail(FIR_ERR_ARG, "bad gallery"); }
     m->gal4 = (const float4*)gp;
     m->precision = precision;
+    if (precision == FIR_GEMM_F16 && !(m->v.cus >= 8 && (m->v.cus & 7) == 0)) {     // (as fir_gemm_create_f64_; no gfx950 partition mode has such a count)
+        const int cus = m->v.cus;
+        delete m;
+        return gemm_fail(FIR_ERR_ARG, "the 16-row kernels want CUs in eights (%d)", cus);
+    }
     // a prefix [0, end_pos) of every row (the reference's "BF, 64" / "BF, 256" classifiers, ImageTesting.cpp:526-529): its own
     // fp16 fragments and row norms; whole 16-feature k-blocks, fp16 form only
     m->feat = end_pos > 0 && end_pos < m->v.d ? end_pos : m->v.d;
@@ -1736,47 +1400,15 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_bf16_wide, hipFuncAttributeMaxDynamicSharedMemorySize, kWideLds);
     {   // the re-rank keeps the query and up to kRerankGroup candidate rows in LDS
         const size_t row_bytes = (size_t)(m->dp4 + 1) * sizeof(float4);
-        size_t want_group = kRerankGroup;
-        if (const char* w = fir_knob_("FIR_GEMM_RERANK_GROUP")) want_group = (size_t)std::max(1, std::min(64, std::atoi(w)));      // experiments
-        m->rerank_group = (int)std::min<size_t>(want_group, kRerankLdsMax / row_bytes > 1 ? kRerankLdsMax / row_bytes - 1 : 0);
+        m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes > 1 ? kRerankLdsMax / row_bytes - 1 : 0);
         if (m->rerank_group < 1) { delete m; return gemm_fail(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's re-rank", m->v.d); }
         if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
             e = hipFuncSetAttribute((const void*)k_gemm_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
         if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
             e = hipFuncSetAttribute((const void*)k_gemm_rerank_topk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-#define FIR_RT_ATTR(D) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16_regtile<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RegTile<D>::lds_bytes); \
-                       if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16_regtile<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RegTile<D>::lds_bytes);
-    FIR_RT_ATTR(8) FIR_RT_ATTR(16) FIR_RT_ATTR(32)
-#undef FIR_RT_ATTR
-#define FIR_X_ATTR(M, S, O) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16x<M, S, O>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-    FIR_X_ATTR(1, 0, 0) FIR_X_ATTR(1, 0, 1) FIR_X_ATTR(1, 1, 0) FIR_X_ATTR(1, 1, 1) FIR_X_ATTR(2, 0, 0) FIR_X_ATTR(2, 0, 1) FIR_X_ATTR(2, 1, 0) FIR_X_ATTR(2, 1, 1)
-    FIR_X_ATTR(3, 0, 0) FIR_X_ATTR(3, 0, 1) FIR_X_ATTR(3, 1, 0) FIR_X_ATTR(3, 1, 1)
-    FIR_X_ATTR(4, 0, 0) FIR_X_ATTR(4, 0, 1) FIR_X_ATTR(4, 1, 0) FIR_X_ATTR(4, 1, 1)
-#undef FIR_X_ATTR
-    m->mfma16 = precision == FIR_GEMM_F16;
-    if (const char* w = fir_knob_("FIR_GEMM_MFMA16")) m->mfma16 = std::atoi(w) != 0 && precision == FIR_GEMM_F16;
-    if (const char* w = fir_knob_("FIR_GEMM_STAGGER")) m->stagger = std::atoi(w);     // 1 = half a unit, 2 = half a row block at 512 features
-    if (const char* w = fir_knob_("FIR_GEMM_PRIO")) m->prio = std::atoi(w) != 0;
-    if (const char* w = fir_knob_("FIR_GEMM_NO_BLOCK_BOUND")) m->no_block_bound = std::atoi(w) != 0;
-#ifdef FIR_AUDIT      // knobs that change answers: the audit build only (libfir_amd_audit.so; fir_internal.h)
-    if (const char* w = fir_knob_("FIR_GEMM_DBG_SKIP")) m->dbg_skip = std::atoi(w) & 1023;
-    if (const char* w = fir_knob_("FIR_GEMM_DBG_BLOCK")) m->dbg_block = std::atoi(w) == 256 ? 256 : kGemmBlock;     // timing experiments only: the answers are wrong
-    if (const char* w = fir_knob_("FIR_GEMM_EREL_SCALE")) m->erel_scale = (float)std::atof(w);
-#endif
-    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE")) m->adaptive = std::atoi(w);
-    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE_TOPK")) m->adaptive_topk = std::atoi(w) != 0;
-    if (const char* w = fir_knob_("FIR_GEMM_SHARE_STREAMED")) m->share_streamed = std::max(1, std::min(16, std::atoi(w)));
-    if (const char* w = fir_knob_("FIR_GEMM_FEW_BLOCKS")) m->few_blocks = std::atoi(w) != 0;
-    if (const char* w = fir_knob_("FIR_GEMM_SHARE")) m->share_max = std::max(0, std::min(16, std::atoi(w)));
-    // the 16-row kernels always run the smallest-proxy sample flow with its XCD-shared launches: one workgroup per CU, CUs in eights
-    if (m->mfma16 && !(m->share_max > 0 && (m->v.cus & 7) == 0 && m->v.cus >= 8)) m->mfma16 = 0;
-    if (const char* w = fir_knob_("FIR_GEMM_REGTILE")) m->regtile = std::atoi(w);
-    if (const char* w = fir_knob_("FIR_GEMM_STREAMED")) m->streamed = std::atoi(w);   // experiments: 0 / 1 force the form, -1 = by row length
+    if (e == hipSuccess && precision == FIR_GEMM_F16) e = gemm_x_lds_attr_();
+    gemm_read_knobs_(m);
     if (e == hipSuccess && m->v.n > 0) {
         // row norms come from the f32 packer (run on a one-group scratch when only the bf16 fragments are kept)
         if (precision == FIR_GEMM_BF16_SPLIT) {
@@ -1798,11 +1430,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
             else m->gallery_exp = h_max > 0.f ? 1000 : 0;      // non-finite gallery value: every query is left to the exact scan
             const float scale = (m->gallery_exp >= -100 && m->gallery_exp <= 100) ? std::ldexp(1.0f, m->gallery_exp) : 0.f;
             const int64_t totalh = rblocks * m->dk16 * 64;
-            if (m->mfma16)
-                hipLaunchKernelGGL(k_gemm_pack_gallery_f16x, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4,
-                                   m->dk16, scale, m->gh, m->feat == m->v.d ? m->dp4 * 4 : m->feat);
-            else
-            hipLaunchKernelGGL(k_gemm_pack_gallery_f16, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4,
+            hipLaunchKernelGGL(k_gemm_pack_gallery_f16x, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4,
                                m->dk16, scale, m->gh, m->feat == m->v.d ? m->dp4 * 4 : m->feat);
             hipLaunchKernelGGL(k_gemm_row_norms, dim3((unsigned)((m->v.n + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4, m->gnorm, (m->feat + 3) / 4);
         }
@@ -1911,10 +1539,9 @@ int fir_gemm_stats(const fir_gemm* m, int64_t* passes, int64_t* fallback_queries
 
 // Everything a call still owes its uncertified queries, queued on `st` behind the last re-rank (fir_gemm_fb.h): second-chance rounds
 // (sc_rounds > 0: the 16-row fp16 flow only), the collection of what is left, the exact device scan (K launches for the K nearest).
-static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds) {
+static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds, bool streamed) {
     const int d = m->feat, qs = m->v.d;
     const int64_t n = m->v.n;
-    const bool streamed = m->dk16 > kSlabH || m->streamed > 0;
     const size_t rr_lds = (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4);
     for (int r = 0; r < sc_rounds; ++r) {
         const int off = r * kScQueries;
@@ -1924,7 +1551,7 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
                            m->sc_qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
         // one pair over all CUs (share = 1: 256 row ranges), the gallery stream read once (nt)
         hipLaunchKernelGGL(pick_x(1, streamed, (m->dk16 / kRing) & 1), dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
-                           (int64_t)0, n, m->dk16, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1 | (m->no_block_bound ? 64 : 0), 1,
+                           (int64_t)0, n, m->dk16, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
                            (unsigned int*)m->fb_state, off);
         const RerankFb fb = {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off};
         if (k == 1)
@@ -1940,6 +1567,61 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
                            (const int*)m->fb_list2, (unsigned long long*)d_keys, k, r);
     GEMM_HIP(hipGetLastError());
     return FIR_OK;
+}
+
+// ---- one search call ----
+// d_queries / d_keys: device pointers. Everything is queued on `stream` (and the handle's side streams, joined before the call
+// returns control of `stream`): no host synchronisation -- the keys are final in stream order.
+//
+// super-batch = the queries of ONE set of launches (preparation, full passes, re-rank): up to kPasses passes of 64 queries.
+// Two streams. `st` carries the full passes over the gallery, back to back; `side` carries the exact re-rank + certificate of
+// super-batch i under super-batch i+1's full passes, and (host-pointer calls) the preparation of super-batch i+1 -- query norms /
+// scales / fragments, the sample pass, tau -- behind its upload. prep(i+2) reuses the scratch set rerank(i) has just finished with.
+struct GemmCall {
+    const float* d_queries;
+    const float* h_queries;     // non-NULL: the queries are still in host memory; d_queries is the device buffer they go to, one super-batch
+                                // at a time, each upload queued (on its own stream) right before that super-batch's preparation
+    int32_t qb;
+    int k;                      // the K nearest rows of every query: d_keys[q * k + r], ascending
+    uint64_t* d_keys;
+    hipStream_t st;
+    int d, qs;                  // features compared; floats between consecutive queries (and gallery rows): the whole row
+    int64_t n;
+    float e_rel;
+    int grid;                   // one 512-thread workgroup per CU
+    int sbq, nsb;               // queries per super-batch, super-batches of the call
+    // A super-batch's preparation (query packing, the top-K sample pass) runs on the MAIN stream right in front of its full passes: alone on
+    // the chip it is 25 us (top-K: + 0.3 ms of sample passes); on the side stream, "under" the previous super-batch's full passes, its small
+    // kernels only got the CUs a full-pass workgroup had just left and slowed those passes down (1M x 512, 32 768 queries per call: top-1
+    // 1.253 -> 1.296 M q/s, top-5 1.018 -> 1.071 M). Host-pointer calls keep the side stream: there the preparation waits for the
+    // super-batch's upload, which is what overlaps the passes.
+    bool serial_prep;
+    // a call of ONE super-batch whose preparation runs on `st` has nothing to put under anything: its re-rank follows its pass on `st`
+    // as well -- every hop to the side stream and back is 10-12 us of a 300-us call
+    bool one_stream;
+    bool streamed, odd;         // fp16: gemm_streamed_, an odd number of units per row block
+    size_t lds;                 // f32 / bf16: dynamic LDS of the pass kernels
+
+    int sb_queries(int sb) const { return std::min(sbq, qb - sb * sbq); }
+    const float* sb_first(int sb) const { return d_queries + (size_t)sb * sbq * qs; }
+};
+
+// Which fp16 super-batches find their threshold on the way. Until round 4's second half the answer depended on how many row groups a
+// workgroup sees ((row groups) * (pairs per launch) / CUs: below a dozen the bound is still loose when the workgroup ends, 1 000-2 400
+// appended rows per query at 100k x 512 with 256 queries) and such super-batches kept the sample flow. Since an appended row no longer
+// waits for the gallery prefetch and a wave's first row block is summed once, the pass on the way is never slower for top-1 and
+// 10-23 % faster wherever the sample flow used to run (8 192 .. 700 000 rows x 128 .. 4 096 queries, no second pass anywhere:
+// profiles/r04_adaptive_cutoff.txt): top-1 always takes it. The K-nearest form (eight slots per query fill more slowly) wins from eight
+// pairs per launch on and on cache-sized galleries, and loses 3-35 % with one or two pairs over 100 000+ rows: those keep the sample flow.
+static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
+    if (m->precision != FIR_GEMM_F16 || m->adaptive <= 0 || (c.k > 1 && !m->adaptive_topk)) return false;
+    if (m->adaptive > 1 || c.k == 1) return true;                       // FIR_GEMM_ADAPTIVE=2: always
+    const int pairs_sb = ((nq_sb + kQT - 1) / kQT + 1) / 2;
+    const int P = launch_pairs_(pairs_sb, c.streamed ? kShareStreamed : kShareMax);
+    const int64_t row_groups = ((c.n + 31) / 32 + kGemmBlock / 64 - 1) / (kGemmBlock / 64);
+    // (256 queries against 1M x 512 measured 479 k q/s against the sample flow's 514 k, 4 096 queries 1.02 M against 0.92 M --
+    // profiles/r04_topk_slots.txt)
+    return P >= 8 || c.n <= 65536 || row_groups * P / std::max(c.grid, 1) >= 100;
 }
 
 // the per-call buffers of the uncertified-query lists (and the certificate flags), grown to the largest call seen
@@ -1958,14 +1640,232 @@ static int gemm_fb_reserve_(fir_gemm* m, int32_t qb) {
     return FIR_OK;
 }
 
-// d_queries / d_keys: device pointers. Everything is queued on `stream` (and the handle's side streams, joined before the call
-// returns control of `stream`): no host synchronisation -- the keys are final in stream order.
+// What a call needs beyond the state's fixed scratch. Candidate lists and counts: sized by the super-batch in use (whole 128-query
+// pairs), not by the largest one possible -- a cache-resident gallery that gets 128-query calls holds 8 MiB of lists, not 512
+// (ADVICE r2). f32 / bf16: the sample of the order-statistic flow (every sampled proxy), on first use.
+static int gemm_reserve_(fir_gemm* m, const GemmCall& c) {
+    const int rcr = gemm_fb_reserve_(m, c.qb);
+    if (rcr) return rcr;
+    const int need = (std::min(c.sbq, c.qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
+    if (need > m->lists_cap) {
+        GEMM_HIP(hipStreamSynchronize(c.st));
+        GEMM_HIP(hipStreamSynchronize(m->side));
+        for (int b = 0; b < 2; ++b) {
+            (void)hipFree(m->lists[b]); (void)hipFree(m->counts[b]);
+            m->lists[b] = nullptr; m->counts[b] = nullptr;
+        }
+        m->lists_cap = 0;
+        for (int b = 0; b < 2; ++b) {
+            GEMM_HIP(hipMalloc((void**)&m->lists[b], (size_t)need * kListCap * sizeof(unsigned long long)));
+            GEMM_HIP(hipMalloc((void**)&m->counts[b], (size_t)need * sizeof(int)));
+        }
+        m->lists_cap = need;
+    }
+    if (m->precision != FIR_GEMM_F16 && !m->sample)
+        GEMM_HIP(hipMalloc((void**)&m->sample, (size_t)kPasses * kQT * m->sample_rows * sizeof(float)));
+    return FIR_OK;
+}
 
-// The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev):
-// d_keys[q * k + r], ascending.
+// fp16 preparation of one super-batch on `ps`: per-query norms and scales, the query fragments and -- unless the full pass finds its
+// threshold on the way -- the sample flow: the smallest proxy of a row sample per query (k_gemm_proxy_f16x<2, *> over rt_sample_rows
+// rows), tau = that + one window (top-1: k_gemm_tau_min), the K-th smallest of kRtSubsets disjoint subsets' minima + one window
+// (top-K: k_gemm_tau_kmin).
+static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb) {
+    const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
+    const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;        // 128 queries per gallery read; a half-filled pair is zero-padded
+    const float* dq = c.sb_first(sb);
+    const bool adaptive = adaptive_for_(m, c, nq);
+    // (the candidate counts are cleared, the call's two list lengths by its first super-batch and, for the adaptive pass, the per-query
+    // windows and start values are set by the same launch)
+    hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, c.d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], c.qs,
+                       m->counts[b], adaptive ? m->awin[b] : (float*)nullptr, adaptive ? m->aT[b] : (unsigned int*)nullptr,
+                       (const float*)m->gmax, c.e_rel, k > 1 ? k : 0, (unsigned int*)nullptr, sb == 0 ? m->fb_state : (int*)nullptr);
+    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk16, m->qmul[b],
+                       m->qbf[b], c.qs);
+    if (adaptive) return FIR_OK;
+    const int sub_stride = k > 1 ? kPasses * kQT : 0;      // top-K: the sample as kRtSubsets subset minima per query
+    GEMM_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
+    // every rb_stride-th row block: the sample is spread over the whole gallery
+    const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
+    const int rb_stride = (int)std::max<int64_t>(1, ((c.n + 31) / 32) / sample_blocks);
+    for (int p0 = 0; p0 < pairs;) {
+        const int P = launch_pairs_(pairs - p0, kShareMax);
+        const size_t qo = (size_t)p0;
+        hipLaunchKernelGGL(pick_x(2, c.streamed, c.odd), dim3(c.grid), dim3(kGemmBlock), kHalfLds, ps, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
+                           m->qinv[b] + qo * 2 * kQT, c.n, (int64_t)0, sample_blocks * 32, m->dk16, m->tau[b], m->lists[b], m->counts[b], (float*)nullptr,
+                           0, P, P <= 1 ? 1 : 0, rb_stride, m->smin[b] + qo * 2 * kQT, sub_stride);
+        p0 += P;
+    }
+    if (sub_stride)
+        hipLaunchKernelGGL(k_gemm_tau_kmin, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], sub_stride, k, m->tau[b], pairs * 2 * kQT, nq,
+                           m->qnorm[b], m->gmax, c.e_rel);
+    else
+        hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, c.e_rel);
+    return FIR_OK;
+}
+
+// f32 / bf16-split preparation of one super-batch on `ps`: norms, fragments, every proxy of the first sample_rows rows, tau = the
+// kCand-th smallest of them (k_gemm_tau)
+static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb) {
+    const int b = sb & 1, nq = c.sb_queries(sb), np = (nq + kQT - 1) / kQT;
+    const float* dq = c.sb_first(sb);
+    const int sample_rows = m->sample_rows, sample_grid = (sample_rows + 63) / 64;
+    hipLaunchKernelGGL(k_gemm_qnorm, dim3(np * kQT), dim3(64), 0, ps, dq, nq, c.d, m->qnorm[b]);
+    GEMM_HIP(hipMemsetAsync(m->counts[b], 0, (size_t)np * kQT * sizeof(int), ps));
+    if (m->precision == FIR_GEMM_F32) {
+        hipLaunchKernelGGL(k_gemm_pack_queries, dim3(((kQT / 32) * m->dq8 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dq8, m->qm[b]);
+        hipLaunchKernelGGL(k_gemm_proxy<0>, dim3(sample_grid, np), dim3(128), c.lds, ps, m->gm, m->gnorm, m->qm[b], c.n, (int64_t)0,
+                           (int64_t)sample_rows, m->dq8, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+    } else {
+        hipLaunchKernelGGL(k_gemm_pack_queries_bf16, dim3(((kQT / 32) * m->dk16 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dk16,
+                           m->qbf[b]);
+        hipLaunchKernelGGL(k_gemm_proxy_bf16<0>, dim3(sample_grid, np), dim3(128), 0, ps, m->gb, m->gnorm, m->qbf[b], c.n, (int64_t)0,
+                           (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+    }
+    hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, m->tau[b], 0x7FFFFFFF, m->qnorm[b], m->gmax, c.e_rel, 1,
+                       c.k > 1 ? 1 : 0);
+    return FIR_OK;
+}
+
+// Preparation of super-batch sb: (host-pointer calls) its upload, then everything its full passes need, on the stream GemmCall::serial_prep names
+static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
+    hipStream_t ps = c.serial_prep ? c.st : m->side;
+    const int b = sb & 1;
+    if (c.serial_prep && sb >= 2) GEMM_HIP(hipStreamWaitEvent(c.st, m->rerank_done[b], 0));      // the re-rank of sb - 2 read this buffer
+    if (c.h_queries) {
+        const size_t off = (size_t)sb * c.sbq * c.qs;
+        GEMM_HIP(hipMemcpyAsync((void*)(c.d_queries + off), c.h_queries + off, (size_t)c.sb_queries(sb) * c.qs * sizeof(float), hipMemcpyHostToDevice, m->copy));
+        GEMM_HIP(hipEventRecord(m->copy_done[b], m->copy));
+        GEMM_HIP(hipStreamWaitEvent(ps, m->copy_done[b], 0));
+    }
+    const int rc = m->precision == FIR_GEMM_F16 ? gemm_prep_f16_(m, c, ps, sb) : gemm_prep_f32_bf16_(m, c, ps, sb);
+    if (rc) return rc;
+    GEMM_HIP(hipGetLastError());
+    GEMM_HIP(hipEventRecord(m->prep_done[b], ps));
+    return FIR_OK;
+}
+
+// The fp16 full passes of one super-batch on `st` -- the launches fir_profile_read times and fir_gallery_last_dispatch names. The pairs
+// of the super-batch read the gallery together, a power of two of them per launch. Two shapes: the threshold found on the way
+// (k_gemm_proxy_f16x<3 | 4, *>, then k_gemm_adapt_final hands the re-rank its bound) or, after the sample flow, append below tau (<1, *>).
+static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
+    const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
+    const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;
+    const int64_t n = c.n;
+    const bool adaptive = adaptive_for_(m, c, nq);
+    // (a super-batch of at most 16 / 32 queries: one / two query blocks of the tile are live -- the pass multiplies against those only;
+    // whole, even numbers of the form's units per row: eight pieces streamed, sixteen resident)
+    const bool njb_shape = c.streamed ? !c.odd : (m->dk16 % (4 * kRing)) == 0;
+    const int njb = (k == 1 && adaptive && !m->dbg_skip && njb_shape) ? (nq <= 16 ? 1 : nq <= 32 ? 2 : 8) : 8;
+    const int mode = adaptive ? (k > 1 ? 4 : 3) : 1;
+    // algorithmic bytes of ONE launch (what fir_profile_read's event pairs bracket): the fp16 fragments once for the pairs that
+    // read them together, every pair's query tile and keys
+    auto launch_bytes = [&](int P) { return (double)((n + 31) / 32) * m->dk16 * 1024.0 + P * (4.0 * m->dk16 * 1024.0 + 128.0 * 8.0); };
+    int nlaunch = 0, p_first = 1, rc = FIR_OK;
+    for (int p0 = 0; p0 < pairs; ++nlaunch) {
+        const int P = launch_pairs_(pairs - p0, c.streamed ? kShareStreamed : kShareMax);
+        if (p0 == 0) p_first = P;
+        const int nt = P <= 1 ? 1 : 0;                           // read once per launch: non-temporal
+        const size_t qo = (size_t)p0;
+        if ((rc = fir_gallery_profile_begin_(m->g, c.st))) return rc;
+        if (adaptive)
+            hipLaunchKernelGGL(pick_x(mode, c.streamed, c.odd, k > 1 ? 0 : m->dbg_skip, njb), dim3(c.grid, 1), dim3(c.streamed ? kGemmBlock : m->dbg_block), kHalfLds, c.st,
+                               m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->awin[b] + qo * 2 * kQT,
+                               m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->qnorm[b] + qo * 2 * kQT, m->sample_rows, P, nt | m->adapt_dbg, 1,
+                               m->aT[b] + qo * 2 * kQT * (k > 1 ? 8 : 1), k > 1 ? k : 0);
+        else
+            hipLaunchKernelGGL(pick_x(mode, c.streamed, c.odd), dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
+                               m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap,
+                               m->counts[b] + qo * 2 * kQT, (float*)nullptr, m->sample_rows, P, nt, 1, (unsigned int*)nullptr, 0);
+        if ((rc = fir_gallery_profile_end_(m->g, c.st, launch_bytes(P)))) return rc;
+        p0 += P;
+    }
+    const fir_x_entry& ran = find_x(mode, c.streamed, c.odd, njb);
+    fir_gallery_note_dispatch_(m->g, (const void*)ran.fn, ran.name, sb == 0, c.grid, nlaunch, kGemmBlock, kHalfLds, 128 * p_first, launch_bytes(p_first),
+                               2.0 * (double)n * c.d * 128.0 * p_first);
+    if (adaptive)
+        hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, k > 1 ? k : 0);
+    return FIR_OK;
+}
+
+// The f32 / bf16-split full passes of one super-batch on `st`: every row below tau is appended
+static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
+    const int b = sb & 1, np = (c.sb_queries(sb) + kQT - 1) / kQT, grid = c.grid, sample_rows = m->sample_rows;
+    const int64_t n = c.n;
+    if (m->precision == FIR_GEMM_F32) {
+        hipLaunchKernelGGL(k_gemm_proxy<1>, dim3(grid, np), dim3(kGemmBlock), c.lds, c.st, m->gm, m->gnorm, m->qm[b], n, (int64_t)0, n, m->dq8,
+                           m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+        fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy<1>, "fir::k_gemm_proxy<1>", sb == 0, grid, np, kGemmBlock, c.lds, 64,
+                                   np * ((double)((n + 31) / 32) * m->dq8 * 1024.0), 2.0 * (double)n * c.d * 64.0 * np);
+        return;
+    }
+    // pairs of passes share one read of the gallery (128 queries per wave); an odd last pass goes alone
+    const int pairs = m->wide ? np / 2 : 0;
+    if (pairs > 0)
+        hipLaunchKernelGGL(k_gemm_proxy_bf16_wide, dim3(grid, pairs), dim3(kGemmBlock), kWideLds, c.st, m->gb, m->gnorm, m->qbf[b], n, m->dk16,
+                           m->tau[b], m->lists[b], m->counts[b]);
+    if (np > 2 * pairs) {
+        const size_t p0 = (size_t)2 * pairs;
+        hipLaunchKernelGGL(k_gemm_proxy_bf16<1>, dim3(grid, np - 2 * pairs), dim3(kGemmBlock), c.lds, c.st, m->gb, m->gnorm,
+                           m->qbf[b] + p0 * (kQT / 32) * m->dk16 * 128, n, (int64_t)0, n, m->dk16, m->tau[b] + p0 * kQT,
+                           m->lists[b] + p0 * kQT * kListCap, m->counts[b] + p0 * kQT, m->sample + p0 * kQT * sample_rows, sample_rows);
+    }
+    fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy_bf16_wide, pairs > 0 ? "fir::k_gemm_proxy_bf16_wide" : "fir::k_gemm_proxy_bf16<1>", sb == 0,
+                               grid, pairs > 0 ? pairs : np, kGemmBlock, pairs > 0 ? (size_t)kWideLds : c.lds, pairs > 0 ? 128 : 64,
+                               (pairs + (np - 2 * pairs)) * ((double)((n + 31) / 32) * m->dk16 * 2048.0), 2.0 * (double)n * c.d * 64.0 * np);
+}
+
+// exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list
+static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
+    const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
+    const size_t rr_lds = (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4);
+    const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0};
+    if (c.k == 1)
+        hipLaunchKernelGGL(k_gemm_rerank, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax, c.n, c.d,
+                           m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, (unsigned long long*)c.d_keys + q0, m->ok + q0, c.qs, m->rowmajor, fb);
+    else
+        hipLaunchKernelGGL(k_gemm_rerank_topk, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax, c.n,
+                           c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k, (unsigned long long*)c.d_keys + (size_t)q0 * c.k, m->ok + q0, c.qs, m->rowmajor, fb);
+}
+
+#ifdef FIR_AUDIT
+// audit builds: what FIR_GEMM_DUMP_PHASES / FIR_GEMM_DEBUG_COUNTS ask for about the call's last super-batch (synchronises)
+static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
+    const int last = c.nsb - 1, b = last & 1;
+    if (!m->dump_phases.empty()) {                     // with FIR_GEMM_DBG_SKIP=256: the load-burst timestamps of the first pair
+        GEMM_HIP(hipStreamSynchronize(c.st));
+        std::vector<unsigned long long> h(8 * 256);
+        GEMM_HIP(hipMemcpy(h.data(), m->lists[b] + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
+        if (FILE* f = std::fopen(m->dump_phases.c_str(), "w")) {
+            for (int w = 0; w < 8; ++w)
+                for (int u = 0; u < 240; ++u) std::fprintf(f, "%d %d %llu %llu\n", w, u, h[(size_t)w * 256 + u] >> 20, h[(size_t)w * 256 + u] & 0xFFFFFull);
+            std::fclose(f);
+        }
+    }
+    if (m->debug_counts) {                             // appended rows per query
+        GEMM_HIP(hipStreamSynchronize(c.st));
+        const int nql = c.sb_queries(last);
+        std::vector<int> hc((size_t)nql), h_ok((size_t)nql);
+        GEMM_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
+        GEMM_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)last * c.sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
+        long long sum = 0;
+        int mx = 0, bad = 0;
+        for (int v : hc) { sum += v; mx = std::max(mx, v); }
+        for (int v : h_ok) bad += v ? 0 : 1;
+        std::vector<float> ht((size_t)nql);
+        GEMM_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
+        double ts = 0;
+        int ninf = 0;
+        for (float v : ht) { if (v < 1e30f) ts += v; else ++ninf; }
+        std::fprintf(stderr, "fir_gemm: appended rows per query (last super-batch of %d): mean %.1f, max %d; tau: mean %.6f, %d not finite; %d uncertified\n", nql,
+                     (double)sum / nql, mx, ts / std::max(1, nql - ninf), ninf, bad);
+    }
+    return FIR_OK;
+}
+#endif
+
+// The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev)
 static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr) {
-    // h_queries: the queries are still in host memory; d_queries is the device buffer they go to, one super-batch at a time,
-    // each upload queued (on its own stream) right before that super-batch's preparation
     if (!m || !d_keys || (qb > 0 && !d_queries)) return gemm_fail(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return gemm_fail(FIR_ERR_ARG, "qb < 0");
     if (k < 1 || k > kTopKMax) return gemm_fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kTopKMax);
@@ -1974,378 +1874,68 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);   // this state's scratch, and the gallery's, is shared with every other call on the gallery
     if (order.rc) return order.rc;
-    const int d = m->feat;          // features compared
-    const int qs = m->v.d;          // floats between consecutive queries (and gallery rows): the whole row
-    const int64_t n = m->v.n;
-    if (n == 0 && h_queries) GEMM_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * qs * sizeof(float), hipMemcpyHostToDevice, st));
-    if (n == 0)
-        return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, d, d_keys, st)
-                      : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, d, k, d_keys, st);
-    {
-        const int rcr = gemm_fb_reserve_(m, qb);
-        if (rcr) return rcr;
-    }
-    // this call's two list lengths (the fp16 forms clear them in the first super-batch's query preparation: one launch less per call)
-    if (m->precision != FIR_GEMM_F16) GEMM_HIP(hipMemsetAsync(m->fb_state, 0, 2 * sizeof(int), st));
-    const size_t lds = m->precision == FIR_GEMM_F32 ? (size_t)(kQT / 32) * std::min(m->dq8, kSlab8) * 64 * sizeof(float4)
-                                                    : (size_t)(kQT / 32) * std::min(m->dk16, kSlab16) * 128 * sizeof(uint4);
+    GemmCall c;
+    c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
+    c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
+    if (c.n == 0 && h_queries) GEMM_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
+    if (c.n == 0)
+        return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
+                      : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
+    c.streamed = gemm_streamed_(m);
+    c.odd = (m->dk16 / kRing) & 1;
+    c.lds = m->precision == FIR_GEMM_F32 ? (size_t)(kQT / 32) * std::min(m->dq8, kSlab8) * 64 * sizeof(float4)
+                                         : (size_t)(kQT / 32) * std::min(m->dk16, kSlab16) * 128 * sizeof(uint4);
     // fp16: both operands rounded to 11 bits -> |q~.g~ - q.g| <= (2^-10 + 2^-22) sum|q_k g_k| + the sub-normal tails
     // (< 2^-27 |q||g| for d <= 2^20), doubled in p and with |q||g| <= (|q|^2 + max|g|^2) / 2: 2^-10 (1 + 2^-4) covers it
-    const float e_rel = m->erel_scale * (8.0f * (float)d * 5.9604645e-8f +
-                        (m->precision == FIR_GEMM_BF16_SPLIT ? 6.1035156e-5f : m->precision == FIR_GEMM_F16 ? 9.765625e-4f * 1.0625f : 0.0f));
-    const int grid = m->v.cus;      // one 512-thread workgroup per CU
-    const int sample_rows = m->sample_rows;
-    const int sample_grid = (sample_rows + 63) / 64;
-    // super-batch = the queries of ONE set of launches (preparation, full passes, re-rank): up to kPasses passes of 64 queries. Large
-    // sets amortise the boundaries between full passes (where the small kernels run: they cannot share a CU with a full-pass
-    // workgroup), but a call needs a few super-batches for its preparation / re-rank to overlap anything: a quarter of the call,
-    // in whole 1 024-query launches
+    c.e_rel = m->erel_scale * (8.0f * (float)c.d * 5.9604645e-8f +
+              (m->precision == FIR_GEMM_BF16_SPLIT ? 6.1035156e-5f : m->precision == FIR_GEMM_F16 ? 9.765625e-4f * 1.0625f : 0.0f));
+    // Large super-batches amortise the boundaries between full passes (where the small kernels run: they cannot share a CU with a
+    // full-pass workgroup), but a call needs a few super-batches for its preparation / re-rank to overlap anything: a quarter of the
+    // call, in whole 1 024-query launches.
     // Galleries whose 1 024-query launch is short (n d <= 1.5e8: under ~0.25 ms) take the whole call (up to kPasses passes) as ONE
     // super-batch: between two super-batches the next one's preparation queues behind the previous one's re-rank, which runs squeezed
     // between the full pass's workgroups (100 000 x 512, 4 096 queries: ~65 us of bubble per boundary and a re-rank four times
     // slower than alone, for 110 us launches -- profiles/r03_small_call_timeline.txt)
-    const bool short_launches = (double)n * (double)d <= 1.5e8 && !fir_knob_("FIR_GEMM_QUARTERS");
-    const int sbq = short_launches ? std::min(kPasses * kQT, std::max(1024, (qb + 1023) / 1024 * 1024))
-                                   : std::min(kPasses * kQT, std::max(1024, (qb / 4 + 1023) / 1024 * 1024));
-    const int nsb = (qb + sbq - 1) / sbq;
-    {   // candidate lists and counts: sized by the super-batch in use (whole 128-query pairs), not by the largest one possible --
-        // a cache-resident gallery that gets 128-query calls holds 8 MiB of lists, not 512
-        const int need = (std::min(sbq, qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
-        if (need > m->lists_cap) {
-            GEMM_HIP(hipStreamSynchronize(st));
-            GEMM_HIP(hipStreamSynchronize(m->side));
-            for (int b = 0; b < 2; ++b) {
-                (void)hipFree(m->lists[b]); (void)hipFree(m->counts[b]);
-                m->lists[b] = nullptr; m->counts[b] = nullptr;
-            }
-            m->lists_cap = 0;
-            for (int b = 0; b < 2; ++b) {
-                GEMM_HIP(hipMalloc((void**)&m->lists[b], (size_t)need * kListCap * sizeof(unsigned long long)));
-                GEMM_HIP(hipMalloc((void**)&m->counts[b], (size_t)need * sizeof(int)));
-            }
-            m->lists_cap = need;
-        }
-    }
-    // Two streams. `st` carries only the full passes over the gallery, back to back; `side` carries everything small:
-    // the preparation of super-batch i+1 (query norms / scales / fragments, the sample pass, tau) and the exact re-rank +
-    // certificate of super-batch i, both under super-batch i's (or i+1's) full pass. Order on `side`:
-    // prep(0) prep(1) rerank(0) prep(2) rerank(1) ... -- prep(i+2) reuses the scratch set rerank(i) has just finished with.
-    // (a call of ONE super-batch whose preparation runs on `st` has nothing to put under anything: its re-rank follows its pass on `st`
-    // as well -- every hop to the side stream and back is 10-12 us of a 300-us call)
-    const char* sp_env = fir_knob_("FIR_GEMM_SERIAL_PREP");
-    const bool serial_prep = !(sp_env && std::atoi(sp_env) == 0) && !h_queries;        // (see the note on prep() below)
-    const bool one_stream = nsb == 1 && serial_prep && !fir_knob_("FIR_GEMM_TWO_STREAMS");
-    if (!one_stream) {
+    const bool short_launches = (double)c.n * (double)c.d <= 1.5e8;
+    c.sbq = std::min(kPasses * kQT, std::max(1024, ((short_launches ? qb : qb / 4) + 1023) / 1024 * 1024));
+    c.nsb = (qb + c.sbq - 1) / c.sbq;
+    c.serial_prep = !h_queries;
+    c.one_stream = c.nsb == 1 && c.serial_prep;
+    int rc = gemm_reserve_(m, c);
+    if (rc) return rc;
+    // this call's two list lengths (the fp16 form clears them in the first super-batch's query preparation: one launch less per call)
+    if (m->precision != FIR_GEMM_F16) GEMM_HIP(hipMemsetAsync(m->fb_state, 0, 2 * sizeof(int), st));
+    if (!c.one_stream) {
         GEMM_HIP(hipEventRecord(m->queries_ready, st));
         GEMM_HIP(hipStreamWaitEvent(m->side, m->queries_ready, 0));
     }
-    // the register-tile flow (fir_gemm_regtile.h) for fp16 galleries whose rows fit the compute waves' registers
-    typedef void (*rt_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int64_t, int, const float*, unsigned long long*, int*, unsigned int*, int, int, int);
-    rt_fn rt_main = nullptr, rt_sample = nullptr;
-    size_t rt_lds = 0;
-    if (m->precision == FIR_GEMM_F16 && !m->mfma16 && m->share_max > 0 && (grid & 7) == 0 && grid >= 8) {
-#define FIR_RT_PICK(D) if (m->dk16 == D) { rt_main = k_gemm_proxy_f16_regtile<D, false>; rt_sample = k_gemm_proxy_f16_regtile<D, true>; rt_lds = RegTile<D>::lds_bytes; }
-        FIR_RT_PICK(8) FIR_RT_PICK(16) FIR_RT_PICK(32)
-#undef FIR_RT_PICK
-    }
-    // sample pass + tau through the register-tile kernel: the smallest sampled proxy + one window (top-1), the K-th smallest of 64
-    // disjoint subsets' minima + one window (top-K); other row lengths: the block-minimum sample + k_gemm_tau
-    // the same flow on the 16-row fragment order: k_gemm_proxy_f16x<2, *> is its sample pass, for any row length
-    const bool x_flow = m->precision == FIR_GEMM_F16 && m->mfma16 && m->share_max > 0 && (grid & 7) == 0 && grid >= 8;
-    const bool rt_flow = rt_main != nullptr || x_flow;
-    // Which super-batches find their threshold on the way. Until round 4's second half the answer depended on how many row groups a
-    // workgroup sees ((row groups) * (pairs per launch) / CUs: below a dozen the bound is still loose when the workgroup ends, 1 000-2 400
-    // appended rows per query at 100k x 512 with 256 queries) and such super-batches kept the sample flow. Since an appended row no longer
-    // waits for the gallery prefetch and a wave's first row block is summed once, the pass on the way is never slower for top-1 and
-    // 10-23 % faster wherever the sample flow used to run (8 192 .. 700 000 rows x 128 .. 4 096 queries, no second pass anywhere:
-    // profiles/r04_adaptive_cutoff.txt): top-1 always takes it. The K-nearest form (eight slots per query fill more slowly) wins from eight
-    // pairs per launch on and on cache-sized galleries, and loses 3-35 % with one or two pairs over 100 000+ rows: those keep the sample flow.
-    auto adaptive_for = [&](int nq_sb) -> bool {
-        if (!(x_flow && m->adaptive > 0 && (k == 1 || m->adaptive_topk))) return false;
-        if (m->adaptive > 1) return true;                                   // FIR_GEMM_ADAPTIVE=2: always
-        const int pairs_sb = ((nq_sb + kQT - 1) / kQT + 1) / 2;
-        const bool str = m->dk16 > kSlabH || m->streamed > 0;
-        int P = 1;
-        while (P * 2 <= pairs_sb && P * 2 <= (str ? std::min(m->share_max, m->share_streamed) : m->share_max)) P *= 2;
-        const int64_t row_groups = ((n + 31) / 32 + kGemmBlock / 64 - 1) / (kGemmBlock / 64);
-        // (the K-nearest form's eight slots per query fill more slowly: 256 queries against 1M x 512 measured 479 k q/s against the sample
-        // flow's 514 k, 4 096 queries 1.02 M against 0.92 M -- profiles/r04_topk_slots.txt)
-        if (k == 1) return true;
-        return P >= 8 || n <= 65536 || row_groups * P / std::max(grid, 1) >= 100;
-    };
-#ifdef FIR_AUDIT
-    // 1 = no refresh, 2 = no exchange of the adaptive bound between workgroups (still sound: a looser bound appends more -- this is how
-    // the tests drive lists into overflow and the second-chance pass on benign data)
-    const int adapt_dbg = fir_knob_("FIR_GEMM_ADAPT_DBG") ? (std::atoi(fir_knob_("FIR_GEMM_ADAPT_DBG")) & 3) << 2 : 0;
-#else
-    const int adapt_dbg = 0;
-#endif
-    const int sub_stride = k > 1 ? kPasses * kQT : 0;      // top-K: the sample as kRtSubsets subset minima per query (k_gemm_tau_kmin)
-    // the full pass: both kernels run at ~1 KiB of LDS traffic per MFMA and within 7 % of each other (profiles/r02_gemm_kernel_choice.txt):
-    // register tile ahead up to 256 features, LDS tile ahead at 512
-    const bool rt_full = rt_main != nullptr && (m->regtile > 0 || (m->regtile < 0 && m->dk16 <= 16));
-    if (!rt_flow && !m->sample) {
-        // the sample of the order-statistic flow, on first use: one block minimum per 32 sampled rows and query (fp16), every proxy (f32 / bf16)
-        const size_t per_query = m->precision == FIR_GEMM_F16 ? (size_t)(m->sample_rows + 31) / 32 : (size_t)m->sample_rows;
-        GEMM_HIP(hipMalloc((void**)&m->sample, (size_t)kPasses * kQT * per_query * sizeof(float)));
-    }
-    // A super-batch's preparation (query packing, the top-K sample pass) runs on the MAIN stream right in front of its full passes: alone on
-    // the chip it is 25 us (top-K: + 0.3 ms of sample passes); on the side stream, "under" the previous super-batch's full passes, its small
-    // kernels only got the CUs a full-pass workgroup had just left and slowed those passes down (1M x 512, 32 768 queries per call: top-1
-    // 1.253 -> 1.296 M q/s, top-5 1.018 -> 1.071 M; FIR_GEMM_SERIAL_PREP=0 is the old placement). Host-pointer calls keep the side stream:
-    // there the preparation waits for the super-batch's upload, which is what overlaps the passes.
-    auto prep = [&](int sb) -> int {
-        hipStream_t ps = serial_prep ? st : m->side;
-        if (serial_prep && sb >= 2) GEMM_HIP(hipStreamWaitEvent(st, m->rerank_done[sb & 1], 0));      // the re-rank of sb - 2 read this buffer
-        const int q0 = sb * sbq;
-        const int nq = std::min(sbq, qb - q0);
-        if (h_queries) {
-            GEMM_HIP(hipMemcpyAsync((void*)(d_queries + (size_t)q0 * qs), h_queries + (size_t)q0 * qs, (size_t)nq * qs * sizeof(float), hipMemcpyHostToDevice, m->copy));
-            GEMM_HIP(hipEventRecord(m->copy_done[sb & 1], m->copy));
-            GEMM_HIP(hipStreamWaitEvent(ps, m->copy_done[sb & 1], 0));
-        }
-        const int np = (nq + kQT - 1) / kQT;
+    // order on `side` when it prepares: prep(0) prep(1) rerank(0) prep(2) rerank(1) ...
+    if ((rc = gemm_prep_(m, c, 0))) return rc;
+    for (int sb = 0; sb < c.nsb; ++sb) {
         const int b = sb & 1;
-        const float* dq = d_queries + (size_t)q0 * qs;
-        if (m->precision == FIR_GEMM_F16) {
-            const int pairs = (np + 1) / 2;                      // 128 queries per gallery read; a half-filled pair is zero-padded
-            // (the candidate counts are cleared and, for the adaptive pass, its per-query state is set by the same launch)
-            const bool adaptive_prep = adaptive_for(nq);
-            hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], qs,
-                               m->counts[b], adaptive_prep ? m->awin[b] : (float*)nullptr, adaptive_prep ? m->aT[b] : (unsigned int*)nullptr,
-                               (const float*)m->gmax, e_rel, k > 1 ? k : 0, (unsigned int*)nullptr, sb == 0 ? m->fb_state : (int*)nullptr);
-            if (m->mfma16)
-                hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, d, m->dk16, m->qmul[b],
-                                   m->qbf[b], qs);
-            else
-            hipLaunchKernelGGL(k_gemm_pack_queries_f16, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, d, m->dk16, m->qmul[b],
-                               m->qbf[b], qs);
-            const bool adaptive = adaptive_for(nq);
-            if (adaptive) {
-                // no sample pass: the full pass finds its threshold on the way (k_gemm_proxy_f16x<3, *>)
-                // (k_gemm_qprep_f16 has set the windows and start values)
-            } else if (rt_flow) {
-                // the smallest proxy of a row sample per query (register-tile kernel over rows [0, rt_sample_rows)), tau = that + one window
-                GEMM_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
-                for (int p0 = 0; p0 < pairs;) {
-                    int P = 1;
-                    while (P * 2 <= pairs - p0 && P * 2 <= m->share_max) P *= 2;
-                    const size_t qo = (size_t)p0;
-                    // every rb_stride-th row block: the sample is spread over the whole gallery
-                    const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
-                    const int rb_stride = (int)std::max<int64_t>(1, ((n + 31) / 32) / sample_blocks);
-                    if (x_flow) {
-                        const bool xs = m->dk16 > kSlabH || m->streamed > 0;
-                        hipLaunchKernelGGL(pick_x(2, xs, (m->dk16 / kRing) & 1), dim3(grid), dim3(kGemmBlock), kHalfLds, ps, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
-                                           m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, sample_blocks * 32, m->dk16, m->tau[b], m->lists[b], m->counts[b], (float*)nullptr,
-                                           0, P, P <= 1 ? 1 : 0, rb_stride, m->smin[b] + qo * 2 * kQT, sub_stride);
-                    } else
-                    hipLaunchKernelGGL(rt_sample, dim3(grid), dim3(512), rt_lds, ps, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n,
-                                       sample_blocks * 32, rb_stride, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT,
-                                       m->smin[b] + qo * 2 * kQT, P, P <= 1 ? 1 : 0, sub_stride);
-                    p0 += P;
-                }
-                if (sub_stride)
-                    hipLaunchKernelGGL(k_gemm_tau_kmin, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], sub_stride, k, m->tau[b], pairs * 2 * kQT, nq,
-                                       m->qnorm[b], m->gmax, e_rel);
-                else
-                    hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, e_rel);
-            } else {
-            const int wpb = kGemmBlock / 64;
-            const int sample_wgs = (int)((((int64_t)sample_rows + 31) / 32 + wpb - 1) / wpb);
-            const bool streamed = m->mfma16 ? (m->dk16 > kSlabH || m->streamed > 0) : (m->streamed >= 0 ? m->streamed != 0 : m->dk16 > kSlabH);
-            const dim3 sgrid(std::min(sample_wgs, grid), pairs);
-            if (streamed)
-                hipLaunchKernelGGL((k_gemm_proxy_f16<0, 1>), sgrid, dim3(kGemmBlock), kHalfLds, ps, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, (int64_t)0,
-                                   (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows, 0, 1);
-            else
-                hipLaunchKernelGGL((k_gemm_proxy_f16<0, 0>), sgrid, dim3(kGemmBlock), kHalfLds, ps, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, (int64_t)0,
-                                   (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows, 0, 1);
-            hipLaunchKernelGGL(k_gemm_tau, dim3(pairs * 2 * kQT), dim3(256), 0, ps, m->sample, (sample_rows + 31) / 32, m->tau[b], nq, m->qnorm[b], m->gmax,
-                               e_rel, 2 * kQT, k > 1 ? 1 : 0);
-            }
-        } else {
-            hipLaunchKernelGGL(k_gemm_qnorm, dim3(np * kQT), dim3(64), 0, ps, dq, nq, d, m->qnorm[b]);
-            GEMM_HIP(hipMemsetAsync(m->counts[b], 0, (size_t)np * kQT * sizeof(int), ps));
-            if (m->precision == FIR_GEMM_F32) {
-                hipLaunchKernelGGL(k_gemm_pack_queries, dim3(((kQT / 32) * m->dq8 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, d, m->dq8, m->qm[b]);
-                hipLaunchKernelGGL(k_gemm_proxy<0>, dim3(sample_grid, np), dim3(128), lds, ps, m->gm, m->gnorm, m->qm[b], n, (int64_t)0,
-                                   (int64_t)sample_rows, m->dq8, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
-            } else {
-                hipLaunchKernelGGL(k_gemm_pack_queries_bf16, dim3(((kQT / 32) * m->dk16 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, d, m->dk16,
-                                   m->qbf[b]);
-                hipLaunchKernelGGL(k_gemm_proxy_bf16<0>, dim3(sample_grid, np), dim3(128), 0, ps, m->gb, m->gnorm, m->qbf[b], n, (int64_t)0,
-                                   (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
-            }
-            hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, m->tau[b], 0x7FFFFFFF, m->qnorm[b], m->gmax, e_rel, 1,
-                               k > 1 ? 1 : 0);
-        }
-        GEMM_HIP(hipGetLastError());
-        GEMM_HIP(hipEventRecord(m->prep_done[b], ps));
-        return FIR_OK;
-    };
-    int rcp = prep(0);
-    if (rcp) return rcp;
-    for (int sb = 0; sb < nsb; ++sb) {
-        const int q0 = sb * sbq;
-        const int nq = std::min(sbq, qb - q0);
-        const int np = (nq + kQT - 1) / kQT;
-        const int b = sb & 1;
-        const float* dq = d_queries + (size_t)q0 * qs;
-        if (serial_prep) { if (sb >= 1 && (rcp = prep(sb))) return rcp; }
-        else if (sb + 1 < nsb && (rcp = prep(sb + 1))) return rcp;
-        const bool adaptive = adaptive_for(nq);
+        if (c.serial_prep) { if (sb >= 1 && (rc = gemm_prep_(m, c, sb))) return rc; }
+        else if (sb + 1 < c.nsb && (rc = gemm_prep_(m, c, sb + 1))) return rc;
         GEMM_HIP(hipStreamWaitEvent(st, m->prep_done[b], 0));
-        // ---- the full pass(es) over the gallery: the launch fir_profile_read times and fir_gallery_last_dispatch names ----
-        if (m->precision == FIR_GEMM_F16) {
-            const int pairs = (np + 1) / 2;
-            // (a super-batch of at most 16 / 32 queries: one / two query blocks of the tile are live -- the pass multiplies against those only)
-            const bool streamed = m->mfma16 ? (m->dk16 > kSlabH || m->streamed > 0) : (m->streamed >= 0 ? m->streamed != 0 : m->dk16 > kSlabH);
-            // (whole, even numbers of the form's units per row: eight pieces streamed, sixteen resident)
-            const bool njb_shape = streamed ? !((m->dk16 / kRing) & 1) : (m->dk16 % (4 * kRing)) == 0;
-            const int njb = (k == 1 && adaptive && m->mfma16 && !m->dbg_skip && njb_shape && m->few_blocks) ? (nq <= 16 ? 1 : nq <= 32 ? 2 : 8) : 8;
-            const int64_t rblocks = (n + 31) / 32;
-            // rows longer than the LDS tile (query slabs streamed per unit): 16 readers of one range drift apart, 8 measured better
-            const int share_cap = m->share_max > 0 ? (streamed ? std::min(m->share_max, m->share_streamed) : m->share_max) : 16;
-            int nlaunch = 0, p_first = 1;
-            for (int p0 = 0; p0 < pairs;) {
-                int P = 1;
-                while (P * 2 <= pairs - p0 && P * 2 <= share_cap) P *= 2;
-                if (p0 == 0) p_first = P;
-                p0 += P;
-                ++nlaunch;
-            }
-            // algorithmic bytes of ONE launch (what fir_profile_read's event pairs bracket): the fp16 fragments once for the pairs that
-            // read them together (once per pair without sharing), every pair's query tile and keys
-            auto launch_bytes = [&](int P) { return (m->share_max > 0 ? 1 : P) * ((double)rblocks * m->dk16 * 1024.0) + P * (4.0 * m->dk16 * 1024.0 + 128.0 * 8.0); };
-            const double bytes = launch_bytes(p_first);
-            const double flops = 2.0 * (double)n * d * 128.0 * p_first;
-            int rc2 = FIR_OK;
-            bool used_rt = false;
-            size_t used_rt_lds = 0;
-            // the pairs of the super-batch read the gallery together, a power of two (<= share_max) of them per launch
-            for (int p0 = 0; p0 < pairs;) {
-                int P = 1;
-                while (P * 2 <= pairs - p0 && P * 2 <= share_cap) P *= 2;
-                const int share = m->share_max > 0 ? P : 0;
-                const dim3 g1 = share > 0 ? dim3(grid, 1) : dim3(grid, P);
-                const int nt = (share <= 1) ? 1 : 0;
-                const size_t qo = (size_t)p0;
-                if ((rc2 = fir_gallery_profile_begin_(m->g, st))) return rc2;
-                if (rt_full && share > 0 && grid / 8 >= share) {
-                    hipLaunchKernelGGL(rt_main, dim3(grid), dim3(512), rt_lds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n, n, 1,
-                                       m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->smin[b] + qo * 2 * kQT, share, nt, 0);
-                    used_rt = true;
-                    used_rt_lds = rt_lds;
-                } else if (adaptive)
-                    hipLaunchKernelGGL(pick_x(k > 1 ? 4 : 3, streamed, (m->dk16 / kRing) & 1, k > 1 ? 0 : m->dbg_skip, njb), g1, dim3(streamed ? kGemmBlock : m->dbg_block), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
-                                       m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap,
-                                       m->counts[b] + qo * 2 * kQT, m->qnorm[b] + qo * 2 * kQT, sample_rows, share, nt | adapt_dbg | (m->stagger ? 2 : 0) | (m->stagger > 1 ? 32 : 0) | (m->prio ? 16 : 0) | (m->no_block_bound ? 64 : 0), 1,
-                                       m->aT[b] + qo * 2 * kQT * (k > 1 ? 8 : 1), k > 1 ? k : 0);
-                else if (m->mfma16)
-                    hipLaunchKernelGGL(pick_x(1, streamed, (m->dk16 / kRing) & 1), g1, dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
-                                       m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap,
-                                       m->counts[b] + qo * 2 * kQT, m->sample, sample_rows, share, nt | (m->stagger ? 2 : 0) | (m->stagger > 1 ? 32 : 0) | (m->prio ? 16 : 0) | (m->no_block_bound ? 64 : 0), 1, (unsigned int*)nullptr, 0);
-                else if (streamed)
-                    hipLaunchKernelGGL((k_gemm_proxy_f16<1, 1>), g1, dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT,
-                                       n, (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->sample,
-                                       sample_rows, share, nt);
-                else
-                    hipLaunchKernelGGL((k_gemm_proxy_f16<1, 0>), g1, dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT,
-                                       n, (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->sample,
-                                       sample_rows, share, nt);
-                if ((rc2 = fir_gallery_profile_end_(m->g, st, launch_bytes(P)))) return rc2;
-                p0 += P;
-            }
-            if (used_rt) {
-                char nm[64];
-                std::snprintf(nm, sizeof nm, "fir::k_gemm_proxy_f16_regtile<%d, false>", m->dk16);
-                const void* fp = (const void*)rt_main;
-                fir_gallery_note_dispatch_(m->g, fp, nm, sb == 0, grid, nlaunch, 512, used_rt_lds, 128 * p_first, bytes, flops);
-            } else
-            fir_gallery_note_dispatch_(m->g, m->mfma16 ? (const void*)pick_x(adaptive ? (k > 1 ? 4 : 3) : 1, streamed, (m->dk16 / kRing) & 1, 0, njb)
-                                                       : (streamed ? (const void*)k_gemm_proxy_f16<1, 1> : (const void*)k_gemm_proxy_f16<1, 0>),
-                                       m->mfma16 ? name_x(streamed, (m->dk16 / kRing) & 1, adaptive, k > 1, njb)
-                                                 : (streamed ? "fir::k_gemm_proxy_f16<1, 1>" : "fir::k_gemm_proxy_f16<1, 0>"), sb == 0, grid, m->share_max > 0 ? nlaunch : pairs, kGemmBlock, kHalfLds,
-                                       m->share_max > 0 ? 128 * p_first : 128, bytes, flops);
-        } else if (m->precision == FIR_GEMM_F32) {
-            hipLaunchKernelGGL(k_gemm_proxy<1>, dim3(grid, np), dim3(kGemmBlock), lds, st, m->gm, m->gnorm, m->qm[b], n, (int64_t)0, n, m->dq8,
-                               m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
-            fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy<1>, "fir::k_gemm_proxy<1>", sb == 0, grid, np, kGemmBlock, lds, 64,
-                                       np * ((double)((n + 31) / 32) * m->dq8 * 1024.0), 2.0 * (double)n * d * 64.0 * np);
-        } else {
-            // pairs of passes share one read of the gallery (128 queries per wave); an odd last pass goes alone
-            const int pairs = m->wide ? np / 2 : 0;
-            if (pairs > 0)
-                hipLaunchKernelGGL(k_gemm_proxy_bf16_wide, dim3(grid, pairs), dim3(kGemmBlock), kWideLds, st, m->gb, m->gnorm, m->qbf[b], n, m->dk16,
-                                   m->tau[b], m->lists[b], m->counts[b]);
-            if (np > 2 * pairs) {
-                const size_t p0 = (size_t)2 * pairs;
-                hipLaunchKernelGGL(k_gemm_proxy_bf16<1>, dim3(grid, np - 2 * pairs), dim3(kGemmBlock), lds, st, m->gb, m->gnorm,
-                                   m->qbf[b] + p0 * (kQT / 32) * m->dk16 * 128, n, (int64_t)0, n, m->dk16, m->tau[b] + p0 * kQT,
-                                   m->lists[b] + p0 * kQT * kListCap, m->counts[b] + p0 * kQT, m->sample + p0 * kQT * sample_rows, sample_rows);
-            }
-            fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy_bf16_wide, pairs > 0 ? "fir::k_gemm_proxy_bf16_wide" : "fir::k_gemm_proxy_bf16<1>", sb == 0,
-                                       grid, pairs > 0 ? pairs : np, kGemmBlock, pairs > 0 ? (size_t)kWideLds : lds, pairs > 0 ? 128 : 64,
-                                       (pairs + (np - 2 * pairs)) * ((double)((n + 31) / 32) * m->dk16 * 2048.0), 2.0 * (double)n * d * 64.0 * np);
-        }
-        if (adaptive) {
-            const int pairs_a = (np + 1) / 2;
-            hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs_a * 2 * kQT + 255) / 256), dim3(256), 0, st, m->aT[b], m->qnorm[b], m->tau[b], pairs_a * 2 * kQT, nq, k > 1 ? k : 0);
-        }
+        if (m->precision == FIR_GEMM_F16) { if ((rc = gemm_pass_f16_(m, c, sb))) return rc; }
+        else gemm_pass_f32_bf16_(m, c, sb);
         GEMM_HIP(hipEventRecord(m->main_done[b], st));
-        // exact re-rank + certificate of this super-batch on the side stream, under the next one's full pass
-        hipStream_t rs = one_stream ? st : m->side;
-        if (!one_stream) GEMM_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
-        const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0};     // uncertified queries go on the call's list
-        if (k == 1)
-            hipLaunchKernelGGL(k_gemm_rerank, dim3(nq), dim3(64), (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4), rs, m->lists[b], m->counts[b],
-                               m->tau[b], m->gal4, dq, m->qnorm[b], m->gmax, n, d, m->dp4, m->v.row_offset, e_rel, m->rerank_group,
-                               (unsigned long long*)d_keys + q0, m->ok + q0, qs, m->rowmajor, fb);
-        else
-            hipLaunchKernelGGL(k_gemm_rerank_topk, dim3(nq), dim3(64), (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4), rs, m->lists[b],
-                               m->counts[b], m->tau[b], m->gal4, dq, m->qnorm[b], m->gmax, n, d, m->dp4, m->v.row_offset, e_rel, m->rerank_group, k,
-                               (unsigned long long*)d_keys + (size_t)q0 * k, m->ok + q0, qs, m->rowmajor, fb);
+        // on the side stream, the re-rank runs under the next super-batch's full passes
+        hipStream_t rs = c.one_stream ? st : m->side;
+        if (!c.one_stream) GEMM_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
+        gemm_rerank_(m, c, sb, rs);
         GEMM_HIP(hipEventRecord(m->rerank_done[b], rs));
-        m->passes += np;
+        m->passes += (c.sb_queries(sb) + kQT - 1) / kQT;
     }
-    if (!one_stream) GEMM_HIP(hipStreamWaitEvent(st, m->rerank_done[(nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
+    if (!c.one_stream) GEMM_HIP(hipStreamWaitEvent(st, m->rerank_done[(c.nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
     GEMM_HIP(hipGetLastError());
 #ifdef FIR_AUDIT
-    if (const char* path = fir_knob_("FIR_GEMM_DUMP_PHASES")) {     // audit builds, with FIR_GEMM_DBG_SKIP=256: the load-burst timestamps of the last super-batch's first pair
-        GEMM_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h(8 * 256);
-        GEMM_HIP(hipMemcpy(h.data(), m->lists[(nsb - 1) & 1] + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = std::fopen(path, "w")) {
-            for (int w = 0; w < 8; ++w)
-                for (int u = 0; u < 240; ++u) std::fprintf(f, "%d %d %llu %llu\n", w, u, h[(size_t)w * 256 + u] >> 20, h[(size_t)w * 256 + u] & 0xFFFFFull);
-            std::fclose(f);
-        }
-    }
-    if (fir_knob_("FIR_GEMM_DEBUG_COUNTS")) {       // audit builds: appended rows per query of the last super-batch (synchronises)
-        GEMM_HIP(hipStreamSynchronize(st));
-        const int nql = std::min(sbq, qb - (nsb - 1) * sbq);
-        std::vector<int> hc((size_t)nql), h_ok((size_t)nql);
-        GEMM_HIP(hipMemcpy(hc.data(), m->counts[(nsb - 1) & 1], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
-        GEMM_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)(nsb - 1) * sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
-        long long sum = 0;
-        int mx = 0, bad = 0;
-        for (int v : hc) { sum += v; mx = std::max(mx, v); }
-        for (int v : h_ok) bad += v ? 0 : 1;
-        std::vector<float> ht((size_t)nql);
-        GEMM_HIP(hipMemcpy(ht.data(), m->tau[(nsb - 1) & 1], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
-        double ts = 0;
-        int ninf = 0;
-        for (float v : ht) { if (v < 1e30f) ts += v; else ++ninf; }
-        std::fprintf(stderr, "fir_gemm: appended rows per query (last super-batch of %d): mean %.1f, max %d; tau: mean %.6f, %d not finite; %d uncertified\n", nql,
-                     (double)sum / nql, mx, ts / std::max(1, nql - ninf), ninf, bad);
-    }
+    if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
     // uncertified queries: a second matrix-core pass with the tightest bound the first one can justify, then the exact device scan
     // (calls of at most 32 queries skip the second-chance rounds: the exact device scan reads the gallery once per eight queries, about what
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
-    const int sc_rounds = x_flow && qb > 32 ? std::min(kScRounds, (qb + kScQueries - 1) / kScQueries) : 0;
-    return gemm_finish_(m, d_queries, k, d_keys, st, e_rel, sc_rounds);
+    const int sc_rounds = m->precision == FIR_GEMM_F16 && qb > 32 ? std::min(kScRounds, (qb + kScQueries - 1) / kScQueries) : 0;
+    return gemm_finish_(m, d_queries, k, d_keys, st, c.e_rel, sc_rounds, c.streamed);
 }
 
 extern "C" {
@@ -2358,7 +1948,7 @@ int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t q
     return gemm_search(m, d_queries, qb, k, d_keys, stream);
 }
 
-// 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16), the rows within one
+// 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one
 // window of the smallest proxy of ALL rows, exact re-rank, certificate; everything on `stream`, one synchronisation.
 int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, uint64_t* d_keys, void* stream) {
     if (!m || !d_keys || !d_queries) return gemm_fail(FIR_ERR_ARG, "NULL argument");
@@ -2399,23 +1989,19 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     const int b = 0;
     hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(2 * kQT), dim3(64), 0, st, d_queries, qb, d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], qs, m->counts[b],
                        (float*)nullptr, (unsigned int*)nullptr, (const float*)nullptr, 0.f, 0, m->smin[b], m->fb_state);
-    if (m->mfma16) hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, qb, d, m->dk16, m->qmul[b], m->qbf[b], qs);
-    else hipLaunchKernelGGL(k_gemm_pack_queries_f16, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, qb, d, m->dk16, m->qmul[b], m->qbf[b], qs);
+    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, qb, d, m->dk16, m->qmul[b], m->qbf[b], qs);
     const dim3 grid((unsigned)std::min<int64_t>((int64_t)m->v.cus * 8, ((n + 31) / 32 + 3) / 4));
     const size_t lds = (size_t)m->dk16 * 2 * nqt * sizeof(uint4);
-#define FIR_FEW(NQ) do { if (m->mfma16) hipLaunchKernelGGL(k_gemm_scan_f16x<NQ>, grid, dim3(256), lds, st, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, m->dk16, m->proxies, m->smin[b]); \
-                         else hipLaunchKernelGGL(k_gemm_scan_f16<NQ>, grid, dim3(256), lds, st, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, m->dk16, m->proxies, m->smin[b]); } while (0)
+    typedef void (*scan_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int, float*, unsigned int*);
+    const scan_fn scan = nqt == 1 ? k_gemm_scan_f16x<1> : nqt == 2 ? k_gemm_scan_f16x<2> : nqt == 4 ? k_gemm_scan_f16x<4> : k_gemm_scan_f16x<8>;
+    const double bytes = (double)((n + 31) / 32) * m->dk16 * 1024.0 + (double)nqt * n * 4.0;
     {
         int rcp = fir_gallery_profile_begin_(m->g, st);              // (no-ops unless profiling is on: a profiled run takes the same path as an unprofiled one)
         if (rcp) return rcp;
-        if (nqt == 1) FIR_FEW(1); else if (nqt == 2) FIR_FEW(2); else if (nqt == 4) FIR_FEW(4); else FIR_FEW(8);
-        if ((rcp = fir_gallery_profile_end_(m->g, st, (double)((n + 31) / 32) * m->dk16 * 1024.0 + (double)nqt * n * 4.0))) return rcp;
+        hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, m->dk16, m->proxies, m->smin[b]);
+        if ((rcp = fir_gallery_profile_end_(m->g, st, bytes))) return rcp;
     }
-#undef FIR_FEW
-    fir_gallery_note_dispatch_(m->g, nqt == 1 ? (const void*)k_gemm_scan_f16<1> : nqt == 2 ? (const void*)k_gemm_scan_f16<2> : nqt == 4 ? (const void*)k_gemm_scan_f16<4>
-                                                                                                                                             : (const void*)k_gemm_scan_f16<8>,
-                               "fir::k_gemm_scan_f16", 1, (int)grid.x, 1, 256, lds, nqt, (double)((n + 31) / 32) * m->dk16 * 1024.0 + (double)nqt * n * 4.0,
-                               2.0 * (double)n * d * nqt);
+    fir_gallery_note_dispatch_(m->g, (const void*)scan, "fir::k_gemm_scan_f16x", 1, (int)grid.x, 1, 256, lds, nqt, bytes, 2.0 * (double)n * d * nqt);
     hipLaunchKernelGGL(k_gemm_tau_min, dim3(1), dim3(256), 0, st, m->smin[b], m->tau[b], 2 * kQT, qb, m->qnorm[b], m->gmax, e_rel);
     hipLaunchKernelGGL(k_gemm_select, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256), qb), dim3(256), 0, st, m->proxies, n, m->tau[b], m->lists[b], m->counts[b]);
     const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0};
@@ -2425,7 +2011,7 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     m->passes += 1;
     // (the bound of this form already is the smallest proxy of ALL rows + one window: a second pass could not do better; what is
     // not certified -- NaN operands, thousands of ties -- goes to the exact device scan, in stream order)
-    return gemm_finish_(m, d_queries, 1, d_keys, st, e_rel, 0);
+    return gemm_finish_(m, d_queries, 1, d_keys, st, e_rel, 0, gemm_streamed_(m));
 }
 
 // Host-pointer form for fir_search_top1 / fir_search_topk: h_queries -> d_stage (qb rows of the gallery's length) super-batch by

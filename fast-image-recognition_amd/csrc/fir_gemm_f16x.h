@@ -1,21 +1,23 @@
-// fir_gemm_f16x.h -- the LDS-tile pass of the fp16 matrix-core path on v_mfma_f32_16x16x32_f16 (included by fir_gemm.hip,
-// inside its anonymous namespace). Same per-wave output tile as k_gemm_proxy_f16 (32 rows x 128 queries), same bytes per
-// MFMA cycle from LDS and from the gallery stream; what differs is the MFMA shape, which the chip clocks differently under
-// load (MI355X_MICROARCH.md, DVFS give-back item 7: build both at the same output tile per wave, keep the faster by wall
-// on random data). fir_gemm::mfma16 selects it; the fragment order of both operands is then the "16-row" one:
+// fir_gemm_f16x.h -- the fp16 matrix-core kernels (FIR_GEMM_F16), on v_mfma_f32_16x16x32_f16 (included by fir_gemm.hip,
+// inside its anonymous namespace). One wave computes 32 rows x 128 queries with the query tile in LDS. This is the only fp16
+// form: a 32x32x16 kernel at the same per-wave tile (same bytes per MFMA cycle from LDS and from the gallery stream; the chip
+// clocks the two MFMA shapes differently under load) and a kernel with the query fragments in registers were measured against
+// it and removed (profiles/r03_mfma_shape_ab.txt, profiles/fp16_single_form_ab.txt). Both operands are in the "16-row"
+// fragment order:
 //
 //   gallery  gh[(rb * dk16 + 2 * kk + s) * 64 + l]   row 32 rb + 16 s + (l & 15),   features 32 kk + 8 (l >> 4) + 0..7
 //   queries  qh[((pair * 8 + jb) * dk32 + kk) * 64 + l]   query 128 pair + 16 jb + (l & 15),   the same features
 //
-// (dk32 = dk16 / 2; a row block is still dk16 consecutive one-KiB pieces, so the gallery stream and its double buffer are
-// addressed exactly as in k_gemm_proxy_f16.) Accumulator tile (s, jb): f32x4, lane l holds query 16 jb + (l & 15) against
+// (dk32 = dk16 / 2; a row block is dk16 consecutive one-KiB pieces, dk16 a multiple of kRing: the fp16 fragments are padded to
+// whole double-buffer units.) Accumulator tile (s, jb): f32x4, lane l holds query 16 jb + (l & 15) against
 // rows 16 s + 4 (l >> 4) + 0..3 of the block.
 #pragma once
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// rows of the tiled f32 gallery * scale -> 16-row fragment order (see above); kmax as k_gemm_pack_gallery_f16
+// rows of the tiled f32 gallery * scale (a power of two) -> 16-row fragment order (see above), round to nearest even
+// kmax: features [0, kmax) of every row are packed, the rest of the fragments is zero (kmax = dp4 * 4: the whole row)
 __global__ void __launch_bounds__(256) k_gemm_pack_gallery_f16x(const float4* __restrict__ gal4, int64_t n, int dp4, int dk16, float scale,
                                                                  uint4* __restrict__ gh, int kmax) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (rb, piece, lane)
@@ -75,7 +77,17 @@ __global__ void __launch_bounds__(256) k_gemm_pack_queries_f16x(const float* q, 
     qh[o] = u;
 }
 
-// One wave: 32 rows x 128 queries. Parameters, grid shapes and the `share` placement as k_gemm_proxy_f16.
+// One wave: 32 rows x 128 queries. Dynamic LDS: kHalfLds. All per-pass scratch is laid out pass-major (128 consecutive queries
+// per pair of passes). Which pair and which row groups a workgroup takes:
+// share == 0: blockIdx.y = pair, row groups blockIdx.x, + gridDim.x, ...
+// share == P (a power of two): ONE workgroup per CU, all resident at once; the P pairs of the launch read the gallery TOGETHER:
+// the row groups are cut into gridDim.x / P contiguous ranges and P workgroups -- one per pair, placed on the same XCD (blocks b
+// and b + 8 share one) -- walk the same range at the same time, so the fp16 gallery stream leaves HBM once per P * 128 queries and
+// the other P - 1 readers hit in the XCD's L2 (or, when they drift apart, in the Infinity Cache).
+// The gallery stream is a double buffer of kRing pieces: the loads of the NEXT unit -- of this row block, or the first of the
+// wave's next row block -- are all issued before the MFMA steps of the current one, so the only wait per unit is at its end. (A
+// ring that reloads each slot right after use needs counted waits inside a loop, which the compiler turns into vmcnt(0) per
+// step: one memory latency per k-block -- measured 358 us per pass against 158 us of gallery stream.)
 // ODD = units (of kRing pieces) per row block is odd: only then do the two gallery buffers end a row block in swapped roles
 // and need a copy; with the even form compiled separately the common row lengths (256, 512, 1280 features) carry neither the
 // copy nor the merge point the compiler hung an s_waitcnt vmcnt(0) on.
@@ -102,9 +114,10 @@ __global__ void __launch_bounds__(256) k_gemm_pack_queries_f16x(const float* q, 
 // A unit is kRing = 8 gallery pieces = four 32-feature steps; per step two A fragments (the row halves) against eight B
 // fragments: sixteen MFMAs of 16 cycles. The eight B fragments are ONE register set that rolls: fragment j is re-read for
 // the next step right behind the two MFMAs that used it, fourteen MFMAs before its next use.
-// Bit 1 of `nt_flags` (experiment, FIR_GEMM_STAGGER): waves 4-7 -- the partners of waves 0-3 on their SIMDs -- run half a unit of
-// throw-away MFMAs first, so that partners do not reach their epilogues and their end-of-unit waits together. Bit 0: the
-// gallery stream is read once per launch (non-temporal loads).
+// `nt_flags` bit 0: the gallery stream is read once per launch (non-temporal loads; pairs that share it use ordinary loads, so that
+// the line stays in L2 for the other readers). Bits 2, 3: the audit build's looser adaptive bound (no refresh / no exchange).
+// Bits 1, 4, 5, 6 belonged to experiments that were measured and not kept (partner waves staggered by half a unit or half a row
+// block, s_setprio around the MFMA phase, all eight proxies of every query block: DESIGN.md section 4, "The 16-row kernels") -- every caller passes 0.
 constexpr int kXStage = 16;             // staged appends per query and workgroup
 // NJB: query blocks of 16 the wave multiplies against (8 = the whole 128-query tile). A call of at most 16 / 32 queries fills one / two
 // blocks; with NJB = 1 / 2 the pass does an eighth / a quarter of the MFMAs and LDS reads and is what such a call should be: one read
@@ -277,7 +290,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         f32x4 junk = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int r = 0; r < 32; ++r) junk = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(B[r & (NJB - 1)]), as_f16x8(B[(r + 1) & (NJB - 1)]), junk, 0, 0, 0);
-        if (nt_flags & 32)                               // (FIR_GEMM_STAGGER=2: half a row block at 512 features instead of half a unit)
+        if (nt_flags & 32)                               // (half a row block at 512 features instead of half a unit)
             for (int r = 0; r < 96; ++r) junk = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(B[r & (NJB - 1)]), as_f16x8(B[(r + 1) & (NJB - 1)]), junk, 0, 0, 0);
         asm volatile("" ::"v"(junk));
     }
@@ -554,7 +567,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 hq3 = hq3 + 1 == units ? 0 : hq3 + 1;
             }
         };
-        if (nt_flags & 16) __builtin_amdgcn_s_setprio(2);       // (experiment, FIR_GEMM_PRIO: the wave in its MFMA phase goes ahead of its partner's epilogue)
+        if (nt_flags & 16) __builtin_amdgcn_s_setprio(2);       // (experiment: the wave in its MFMA phase goes ahead of its partner's epilogue)
         if (!ODD) {
             unit(cur, nxt, 0, std::true_type());
             pend = false;
@@ -773,7 +786,64 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #undef FIR_X_LD
 }
 
-// k_gemm_scan_f16 (the one-to-eight-query nomination scan, below in fir_gemm.hip) on the 16-row fragment order: lane l of
+// tau for the smallest-proxy sample flow (MODE 2 above is its sample pass): the smallest SAMPLED proxy plus one rounding window (2.5 E d, as k_gemm_rerank's 2 E d
+// with room). Every row that can still be the nearest has a proxy within 2 E d of the smallest proxy of ALL rows, which is
+// not above the smallest sampled one: it is appended. And the certificate holds for the rest with room to spare: a row
+// that was not appended has p >= tau, i.e. a reference distance >= (|q|^2 + p_s + 2.5 E d)/d - E, while the winner's is
+// <= (|q|^2 + p_s)/d + E. About n / sample_rows + (rows inside the window) rows pass per query -- tens, not hundreds, which
+// is what keeps the append path out of the full pass's way.
+constexpr int kRtSubsets = 64;
+// Top-K form of k_gemm_tau_min: the sample arrives as kRtSubsets disjoint subsets' minima per query; K of them are at or below the
+// K-th smallest of these minima, so at least K rows of the gallery are: tau = that + one window appends every row that can be
+// among the K nearest, and leaves room for the certificate of rank K. (With K << kRtSubsets the K smallest sampled proxies sit
+// in different subsets almost always: the bound is within a rank or two of the K-th smallest of the whole sample.)
+__global__ void __launch_bounds__(256) k_gemm_tau_kmin(const unsigned int* __restrict__ smin, int sub_stride, int k, float* __restrict__ tau,
+                                                        int nq_total, int nq_valid, const float* __restrict__ qnorm,
+                                                        const float* __restrict__ gnorm_max_p, float e_rel) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq_total) return;
+    if (q >= nq_valid) { tau[q] = -__builtin_huge_valf(); return; }
+    unsigned int best[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) best[i] = 0xFFFFFFFFu;
+    for (int s = 0; s < kRtSubsets; ++s) {
+        unsigned int v = smin[(size_t)s * sub_stride + q];
+        if (v == 0xFF800000u) continue;                                    // an empty subset (+inf preset)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool sw = v < best[i];
+            const unsigned int t = best[i];
+            best[i] = sw ? v : t;
+            v = sw ? t : v;
+        }
+    }
+    unsigned int kth = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kth = i == k - 1 ? best[i] : kth;
+    float t = __builtin_huge_valf();                                      // fewer than K sampled subsets: everything passes, the list cap decides
+    if (kth != 0xFFFFFFFFu) {
+        const float v = fir::f32_from_orderable(kth) + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);
+        t = v + fabsf(v) * 1e-6f + 1e-30f;
+    }
+    tau[q] = t;
+}
+
+__global__ void __launch_bounds__(256) k_gemm_tau_min(const unsigned int* __restrict__ smin, float* __restrict__ tau, int nq_total, int nq_valid,
+                                                       const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p, float e_rel) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq_total) return;
+    if (q >= nq_valid) { tau[q] = -__builtin_huge_valf(); return; }       // padding queries of a half-filled pair: nothing is appended
+    const unsigned int o = smin[q];
+    float t = __builtin_huge_valf();                                      // no sampled proxy (NaN operands): everything passes, the list cap decides
+    if (o != 0xFF800000u) {
+        const float v1 = fir::f32_from_orderable(o);
+        const float v = v1 + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);  // a NaN window gives a NaN tau: nothing passes, nothing is certified
+        t = v + fabsf(v) * 1e-6f + 1e-30f;
+    }
+    tau[q] = t;
+}
+
+// The one-to-eight-query nomination scan (fir_gemm_search_few_keys_dev in fir_gemm.hip) on the 16-row fragment order: lane l of
 // piece 2 kk + s holds row 16 s + (l & 15), feature quarter l >> 4 of step kk.
 typedef _Float16 f16x2x __attribute__((ext_vector_type(2)));
 template <int NQ>

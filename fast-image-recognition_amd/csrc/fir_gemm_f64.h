@@ -2,7 +2,7 @@
 // KNNClassifier::predict (qt_cpp/classification.cpp:116-170) needs of 10^6 rows is the handful of nearest ones -- the walk over
 // the sorted distances stops as soon as one class has K votes (:154-160) -- so large kNN batches go the way of the L2 matcher:
 //   * an fp16 fragment copy of the centred rows (g - avg, what Classifier::normalize makes of a training row, :103-105, :132)
-//     and the same k_gemm_proxy_f16x passes (the threshold found on the way: <3, *> for one row, <4, *> for K' rows) nominate;
+//     and the same k_gemm_proxy_f16x passes (fir_gemm_f16x.h) (the threshold found on the way: <3, *> for one row, <4, *> for K' rows) nominate;
 //   * k_gemm_rerank_f64 recomputes every nominated row inside the rounding window of the K'-th smallest proxy with the
 //     reference's own arithmetic in double -- diff = (g - avg) - (q - avg), dist += diff * diff, feature by feature, un-fused,
 //     one division by the feature count (:123-143): the bits of k_cls_scan and of the oracle -- and keeps the K' nearest as
@@ -323,14 +323,9 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
     m->v.device = device; m->v.cus = cus; m->v.n = nt; m->v.d = d; m->v.metric = 0; m->v.row_offset = 0; m->v.cls = nullptr; m->v.stream = (hipStream_t)stream;
     m->feat = d;
     m->precision = FIR_GEMM_F16;
-    m->mfma16 = 1;
     m->rerank_group = ngroup;
     m->dk16 = (d + 16 * kRing - 1) / (16 * kRing) * kRing;
-    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE")) m->adaptive = std::atoi(w);
-    if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE_TOPK")) m->adaptive_topk = std::atoi(w) != 0;
-#ifdef FIR_AUDIT      // (the audit build only: shrinks the certificate's bound -- tests/test_gpu_cls.py shows that the suite can see an unsound one)
-    if (const char* w = fir_knob_("FIR_GEMM_EREL_SCALE")) m->erel_scale = (float)std::atof(w);
-#endif
+    gemm_read_knobs_(m);      // (FIR_GEMM_EREL_SCALE, audit build: tests/test_gpu_cls.py shows that the suite can see an unsound bound here too)
     hipError_t e = hipSetDevice(device);
     const int64_t rblocks = (nt + 31) / 32;
     if (e == hipSuccess) e = hipMalloc((void**)&m->gh, (size_t)rblocks * m->dk16 * 64 * sizeof(uint4));
@@ -346,10 +341,7 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
     if (e == hipSuccess) e = hipMalloc((void**)&m->awin[b], kPasses * kQT * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&m->aT[b], (size_t)8 * kPasses * kQT * sizeof(unsigned int));
     m->rt_sample_rows = (int)std::min<int64_t>(nt, std::max<int64_t>(kMinSampleRows, nt / 32));
-#define FIR_X_ATTR(M, S, O) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_f16x<M, S, O>, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-    FIR_X_ATTR(1, 0, 0) FIR_X_ATTR(1, 0, 1) FIR_X_ATTR(1, 1, 0) FIR_X_ATTR(1, 1, 1) FIR_X_ATTR(2, 0, 0) FIR_X_ATTR(2, 0, 1) FIR_X_ATTR(2, 1, 0) FIR_X_ATTR(2, 1, 1)
-    FIR_X_ATTR(3, 0, 0) FIR_X_ATTR(3, 0, 1) FIR_X_ATTR(3, 1, 0) FIR_X_ATTR(3, 1, 1) FIR_X_ATTR(4, 0, 0) FIR_X_ATTR(4, 0, 1) FIR_X_ATTR(4, 1, 0) FIR_X_ATTR(4, 1, 1)
-#undef FIR_X_ATTR
+    if (e == hipSuccess) e = gemm_x_lds_attr_();
     if (e == hipSuccess && row_lds > 48 * 1024)
         e = hipFuncSetAttribute((const void*)k_gemm_rerank_f64, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     if (e == hipSuccess) {
@@ -393,7 +385,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
     const int64_t n = m->v.n;
     const int grid = m->v.cus;
     const float e_rel = m->erel_scale * (8.0f * (float)d * 5.9604645e-8f + 9.765625e-4f * 1.0625f);
-    const bool streamed = m->dk16 > kSlabH;
+    const bool streamed = gemm_streamed_(m);
     const bool odd = (m->dk16 / kRing) & 1;
     const int sbq = std::min(kPasses * kQT, std::max(1024, (qb + 1023) / 1024 * 1024));
     {
@@ -409,15 +401,13 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         }
     }
     const int b = 0;
-    const int share_cap = streamed ? std::min(m->share_max, m->share_streamed) : m->share_max;
+    const int share_cap = streamed ? kShareStreamed : kShareMax;
     const size_t rr_lds = (size_t)m->dp2 * sizeof(double2);
     bool first = true;
     for (int q0 = 0; q0 < qb; q0 += sbq) {
         const int nq = std::min(sbq, qb - q0);
         const int np = (nq + kQT - 1) / kQT, pairs = (np + 1) / 2;
         const double* dq = d_qc + (size_t)q0 * d;
-        int Pmax = 1;
-        while (Pmax * 2 <= pairs && Pmax * 2 <= share_cap) Pmax *= 2;
         // (every super-batch: the pass starts from a threshold seeded by the row sample, so it is tight from its first row block on whatever the
         // number of row groups a workgroup sees -- 128 queries per call over 1M x 512: 1.83 -> 1.45 ms; profiles/r04_adaptive_cutoff.txt)
         const bool adaptive = m->adaptive > 0 && (kp == 1 || m->adaptive_topk);
@@ -432,8 +422,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
             const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
             const int rb_stride = (int)std::max<int64_t>(1, ((n + 31) / 32) / sample_blocks);
             for (int p0 = 0; p0 < pairs;) {
-                int P = 1;
-                while (P * 2 <= pairs - p0 && P * 2 <= m->share_max) P *= 2;
+                const int P = launch_pairs_(pairs - p0, kShareMax);
                 const size_t qo = (size_t)p0;
                 hipLaunchKernelGGL(pick_x(2, streamed, odd), dim3(grid), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n,
                                    (int64_t)0, sample_blocks * 32, m->dk16, m->tau[b], m->lists[b], m->counts[b], (float*)nullptr, 0, P, P <= 1 ? 1 : 0, rb_stride,
@@ -449,8 +438,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
                 hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, m->smin[b], m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, e_rel);
         }
         for (int p0 = 0; p0 < pairs;) {
-            int P = 1;
-            while (P * 2 <= pairs - p0 && P * 2 <= share_cap) P *= 2;
+            const int P = launch_pairs_(pairs - p0, share_cap);
             const size_t qo = (size_t)p0;
             const int nt_flag = P <= 1 ? 1 : 0;
             if (ev_pair && first) GEMM_HIP(hipEventRecord(ev_pair[0], st));
@@ -465,7 +453,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
             if (ev_pair && first) {
                 GEMM_HIP(hipEventRecord(ev_pair[1], st));
                 if (flops_per_launch) *flops_per_launch = 2.0 * (double)n * d * 128.0 * P;
-                if (kernel_name) *kernel_name = name_x(streamed, odd, adaptive, kp > 1);
+                if (kernel_name) *kernel_name = find_x(adaptive ? (kp > 1 ? 4 : 3) : 1, streamed, odd).name;
                 first = false;
             }
             p0 += P;
@@ -476,7 +464,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
                            m->rerank_group, d_rows + (size_t)q0 * kp, d_dist + (size_t)q0 * kp, d_ok + q0);
         m->passes += np;
 #ifdef FIR_AUDIT
-        if (fir_knob_("FIR_GEMM_DEBUG_COUNTS")) {      // audit builds: appended rows / certified queries of this super-batch (synchronises)
+        if (m->debug_counts) {      // audit builds: appended rows / certified queries of this super-batch (synchronises)
             GEMM_HIP(hipStreamSynchronize(st));
             std::vector<int> hc((size_t)nq), hok((size_t)nq);
             std::vector<float> ht((size_t)nq);

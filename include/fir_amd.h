@@ -272,10 +272,15 @@ typedef struct fir_gemm fir_gemm;
 enum {
     FIR_GEMM_F32 = 0,        /* v_mfma_f32_32x32x2_f32: exact products (157 TF peak)                                */
     FIR_GEMM_BF16_SPLIT = 1, /* x = hi + lo in bf16, hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16           */
-    FIR_GEMM_F16 = 2         /* (default) one v_mfma_f32_32x32x16_f16 term on power-of-two-scaled fp16 copies: half the gallery
+    FIR_GEMM_F16 = 2         /* (default) one v_mfma_f32_16x16x32_f16 term on power-of-two-scaled fp16 copies: half the gallery
                               * bytes and a third of the MFMAs per 128 queries; the proxy is good to 2^-10 |q||g|, which the
                               * certificate carries: more rows fall inside the rounding window and are re-ranked exactly */
 };
+/* Limits, every precision: rows of at most 4608 features (the exact fallback scan keeps eight queries in LDS); longer rows
+ * return FIR_ERR_ARG. FIR_GEMM_F16 also wants a device whose compute-unit count is a multiple of 8 and at least 8 (its kernels
+ * place the readers of one row range on one XCD): anything else returns FIR_ERR_ARG -- no gfx950 partition mode has such a count,
+ * and gfx950 is the only device fir_gallery_create accepts. In both cases the search entry points that create this state by
+ * themselves keep the exact streaming scan for the gallery (automatic mode; an explicit fir_gallery_set_large_batch_mfma threshold gets the error). */
 int fir_gemm_create(fir_gallery* g, fir_gemm** out);   /* = fir_gemm_create_ex(g, FIR_GEMM_F16, out) */
 int fir_gemm_create_ex(fir_gallery* g, int32_t precision, fir_gemm** out);
 /* ... over a feature prefix [0, end_pos) of every row (0 or d: the whole row): end_pos a multiple of 16, FIR_GEMM_F16 only.
