@@ -39,18 +39,13 @@ int fail(int code, const char* fmt, ...) {
                                           "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-#ifndef FIR_U
-#define FIR_U 8
-#endif
-#ifndef FIR_WPS
-#define FIR_WPS 4
-#endif
-constexpr int kU = FIR_U;    // float4 chunks per lane per load group (FIR_U KiB per wave in flight per group)
-constexpr int kWps = FIR_WPS;     // waves per SIMD the scan kernels are register-budgeted for (<= 128 VGPRs)
-// The plain-range chi-square / KL kernels pair their operands for v_pk_fma_f32 and want more registers (with 128 the
-// chi-square loop spills, and every reload waits for the gallery loads in flight); pick_waves never asks for more than 3.
+constexpr int kU = 8;        // float4 chunks per lane per load group (8 KiB per wave in flight per group)
+constexpr int kUDeep = 16;   // ... of the few-tiles form of a one-query tile
+constexpr int kUSub = 8;     // ... of k_scan_subranges: sub-ranges are multiples of 32 features
+constexpr int kWps = 4;      // waves per SIMD the scan kernels are register-budgeted for (<= 128 VGPRs)
+// The plain-range chi-square / KL kernels and the nomination metrics pair their operands for v_pk_fma_f32 and want more registers
+// (with 128 the chi-square loop spills, and every reload waits for the gallery loads in flight); pick_waves never asks for more than 3.
 constexpr int kWpsPlain = 3;
-constexpr int wps_of(int metric) { return metric >= kChi2InRange ? kWpsPlain : kWps; }
 constexpr int kKMax = 8;     // per-lane candidate list length of the top-K scan
 
 }  // namespace
@@ -142,92 +137,88 @@ int grow(T*& p, size_t& cap, size_t need) {
 
 typedef void (*scan_fn)(const ScanArgs);
 
-template <int EPI>
-scan_fn pick_kernel(int qb, int metric) {
-#define FIR_CASE(QB, M) if (qb == QB && metric == M) return (scan_fn)k_scan<QB, M, kU, EPI, kKMax, wps_of(M)>;
-#ifdef FIR_MINIMAL   // experiment builds: only the L2 top-1 kernels
-    if constexpr (EPI == kEpiTop1) { FIR_CASE(8, 0) FIR_CASE(4, 0) FIR_CASE(2, 0) FIR_CASE(1, 0) }
-    return nullptr;
-#endif
-    FIR_CASE(1, 0) FIR_CASE(2, 0) FIR_CASE(4, 0)
-    FIR_CASE(1, 1) FIR_CASE(2, 1) FIR_CASE(4, 1)
-    FIR_CASE(1, 2) FIR_CASE(2, 2) FIR_CASE(4, 2)
-    FIR_CASE(1, 3) FIR_CASE(2, 3) FIR_CASE(4, 3)      // 3, 4: the plain-range forms of 1, 2 (fir_common.h)
-    FIR_CASE(1, 4) FIR_CASE(2, 4) FIR_CASE(4, 4)
-    if constexpr (EPI != kEpiTopK) {   // the top-K scan keeps 2*kKMax registers per query: 4 queries at most
-        FIR_CASE(8, 0) FIR_CASE(8, 1) FIR_CASE(8, 2) FIR_CASE(8, 3) FIR_CASE(8, 4)
-    }
-#undef FIR_CASE
-    return nullptr;
-}
-
-#ifndef FIR_FAST
-#define FIR_FAST 1
-#endif
-#ifndef FIR_FAST_U
-#define FIR_FAST_U 8
-#endif
-#ifndef FIR_FAST_WPS
-#define FIR_FAST_WPS 4
-#endif
-#ifndef FIR_FAST_MODE
-#define FIR_FAST_MODE 2   // 1: query tile through the scalar cache (SGPR operands), 2: staged in LDS
-#endif
-// The hand-scheduled L2 top-1 kernels cover whole-chunk feature ranges with 8 or 16 queries.
-// *lds_bytes receives the dynamic LDS size the kernel must be launched with.
-constexpr size_t kMaxQueryTileLds = 144 * 1024;   // of the CU's 160 KiB; one workgroup per CU above 80 KiB
-scan_fn pick_fast(int epi, int qb, int metric, int start, int end, int dp4, size_t* lds_bytes) {
-    if (lds_bytes) *lds_bytes = 0;
-#if FIR_FAST
-    if (epi != kEpiTop1 || metric != kL2 || (start & 3) || (end & 3)) return nullptr;
-    if (qb != 8 && qb != 16) return nullptr;
-#if FIR_FAST_MODE == 2
-    const size_t need = (size_t)(dp4 + 1) * qb * 16;     // query tile + one zero chunk of slack
-    if (need <= kMaxQueryTileLds) {                        // above 64 KiB the launch opts in (run_pass)
-        if (lds_bytes) *lds_bytes = need;
-        if (qb == 8) return (scan_fn)k_scan_l2_lds<1, FIR_FAST_U, FIR_FAST_WPS>;
-        // 16 queries per read: two rows per lane (fir_kernels.h, l2_chunk_lds). FIR_SCAN16_FORM (experiments): 0 = one row per lane (rounds 1-3)
-        static const int form16 = fir_knob_("FIR_SCAN16_FORM") ? std::atoi(fir_knob_("FIR_SCAN16_FORM")) : 3;
-        switch (form16) {
-            // (profiles/r04_scan16_forms.txt: 1M x 512 32.3 k q/s -> 33.2-33.5 k with two rows per lane whatever U / waves per SIMD; the vector
-            // pipes are the bound at the clock the chip holds, not the LDS reads)
-            case 0: return (scan_fn)k_scan_l2_lds<2, FIR_FAST_U, FIR_FAST_WPS>;
-            case 1: return (scan_fn)k_scan_l2_lds<2, 4, 4, false, 2>;
-            case 2: return (scan_fn)k_scan_l2_lds<2, 8, 3, false, 2>;
-            case 4: return (scan_fn)k_scan_l2_lds<2, 2, 4, false, 2>;
-            default: return (scan_fn)k_scan_l2_lds<2, 4, 3, false, 2>;
-        }
-    }
-#endif
-    if (qb == 8) return (scan_fn)k_scan_l2_fast<1, FIR_FAST_U, FIR_FAST_WPS>;
-    return (scan_fn)k_scan_l2_fast<2, FIR_FAST_U, FIR_FAST_WPS>;
-#endif
-    return nullptr;
-}
-
-// Few tiles (a gallery of a few thousand rows): every wave owns a whole tile and streams it alone, so what limits a
-// single-query call is how many gallery loads the wave keeps in flight. One- and two-query tiles have the registers
-// for 16 chunks (16 KiB per wave) per load group.
-constexpr int kUDeep = 16;
-scan_fn pick_deep(int epi, int qb, int metric, int dp4, size_t* lds_bytes) {
-    const size_t need = (size_t)dp4 * 4 * qb * sizeof(float);
-    if (need > 64 * 1024) return nullptr;
-#ifndef FIR_MINIMAL
-#define FIR_DEEP(QB, M, E) if (epi == E && qb == QB && metric == M) { *lds_bytes = need; return (scan_fn)k_scan<QB, M, kUDeep, E, kKMax, wps_of(M), 1>; }
-    FIR_DEEP(1, 0, kEpiTop1) FIR_DEEP(1, 1, kEpiTop1) FIR_DEEP(1, 2, kEpiTop1)
-    FIR_DEEP(1, 0, kEpiStore) FIR_DEEP(1, 1, kEpiStore) FIR_DEEP(1, 2, kEpiStore)
-    FIR_DEEP(1, 3, kEpiTop1) FIR_DEEP(1, 4, kEpiTop1) FIR_DEEP(1, 3, kEpiStore) FIR_DEEP(1, 4, kEpiStore)
+// ---- the scan kernels: one table, one selector -------------------------------------------------------------------------------
+// Every kernel launched through a scan_fn is a row of kScanTable. FIR_ROW writes the pointer and the name that fir_dispatch_info
+// reports from the SAME template arguments, so the record cannot name a kernel that did not run. The arguments are spelled as
+// the numbers those names have always carried:
+//   metric     0 L2, 1 chi-square, 2 KL, 3 / 4 their plain-range forms, 5-7 the nomination metrics (fir_common.h)
+//   U          kU chunks per load group, kUDeep in the few-tiles form, kUSub in k_scan_subranges
+//   epilogue   0 top-1, 1 top-K, 2 store, 3 append
+//   KMAX       kKMax
+//   waves per SIMD   kWps; kWpsPlain for the metrics from 3 on
+enum ScanKind { kGeneric, kDeep, kL2Lds, kL2Scalar, kNominate, kSubranges };
+constexpr int kEpiSubranges = 4;   // selector only: k_scan_subranges (one stored distance per sub-range)
+static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
+                  kKLInRange == 4 && kChi2Approx == 5 && kChi2Harm == 6 && kKLEnt == 7 && kU == 8 && kUDeep == 16 && kUSub == 8 && kKMax == 8 && kWps == 4 && kWpsPlain == 3,
+              "kScanTable spells these as numbers");
+struct ScanRow { int kind, epi, qb, metric; scan_fn fn; const char* name; };
+#define FIR_ROW(KIND, EPI, QB, M, KERNEL, ...) {KIND, EPI, QB, M, (scan_fn)KERNEL<__VA_ARGS__>, "fir::" #KERNEL "<" #__VA_ARGS__ ">"},
+#define FIR_SCAN(EPI, QB, M, WPS) FIR_ROW(kGeneric, EPI, QB, M, k_scan, QB, M, 8, EPI, 8, WPS, 0)
+#define FIR_SCAN_M(EPI, QB) FIR_SCAN(EPI, QB, 0, 4) FIR_SCAN(EPI, QB, 1, 4) FIR_SCAN(EPI, QB, 2, 4) FIR_SCAN(EPI, QB, 3, 3) FIR_SCAN(EPI, QB, 4, 3)
+#define FIR_DEEP(EPI, M, WPS) FIR_ROW(kDeep, EPI, 1, M, k_scan, 1, M, 16, EPI, 8, WPS, 1)
+#define FIR_APPEND(M, WPS) FIR_ROW(kGeneric, 3, 8, M, k_scan, 8, M, 8, 3, 8, WPS)
+#define FIR_SUB(QB) FIR_ROW(kSubranges, 4, QB, 0, k_scan_subranges, QB, 0, 8, 4) FIR_ROW(kSubranges, 4, QB, 1, k_scan_subranges, QB, 1, 8, 4) \
+                    FIR_ROW(kSubranges, 4, QB, 2, k_scan_subranges, QB, 2, 8, 4)
+static const ScanRow kScanTable[] = {
+    // the hand-scheduled L2 top-1 kernels (whole-chunk feature ranges): the query tile staged in LDS -- 8 queries, 16 queries (two
+    // rows per lane: fir_kernels.h, l2_chunk_lds), the append form of the top-K lists -- or, for a tile beyond LDS (rows longer
+    // than ~4600 features), read through the scalar cache
+    FIR_ROW(kL2Lds, 0, 8, 0, k_scan_l2_lds, 1, 8, 4, false) FIR_ROW(kL2Lds, 0, 16, 0, k_scan_l2_lds, 2, 4, 3, false, 2)
+    FIR_ROW(kL2Lds, 3, 8, 0, k_scan_l2_lds, 1, 8, 4, true) FIR_ROW(kL2Scalar, 0, 8, 0, k_scan_l2_fast, 1, 8, 4)
+    // few tiles (a gallery of a few thousand rows): every wave owns a whole tile and streams it alone, so what limits a one-query
+    // call is how many gallery loads the wave keeps in flight; a one-query tile has the registers for 16 chunks per load group
+    FIR_DEEP(0, 0, 4) FIR_DEEP(0, 1, 4) FIR_DEEP(0, 2, 4) FIR_DEEP(0, 3, 3) FIR_DEEP(0, 4, 3)
+    FIR_DEEP(2, 0, 4) FIR_DEEP(2, 1, 4) FIR_DEEP(2, 2, 4) FIR_DEEP(2, 3, 3) FIR_DEEP(2, 4, 3)
+    // the generic scan, any feature range (the top-K scan keeps 2 * KMAX registers per query: 4 queries at most)
+    FIR_SCAN_M(0, 1) FIR_SCAN_M(0, 2) FIR_SCAN_M(0, 4) FIR_SCAN_M(0, 8)
+    FIR_SCAN_M(1, 1) FIR_SCAN_M(1, 2) FIR_SCAN_M(1, 4)
+    FIR_SCAN_M(2, 1) FIR_SCAN_M(2, 2) FIR_SCAN_M(2, 4) FIR_SCAN_M(2, 8)
+    // topk_lists_dev: the row samples in a nomination metric, the append scan, and its two-tiles-per-read form, the only
+    // append scan of metrics 6 and 7
+    FIR_ROW(kGeneric, 0, 8, 6, k_scan, 8, 6, 8, 0, 8, 3) FIR_ROW(kGeneric, 0, 8, 7, k_scan, 8, 7, 8, 0, 8, 3)
+    FIR_APPEND(0, 4) FIR_APPEND(1, 4) FIR_APPEND(2, 4) FIR_APPEND(3, 3) FIR_APPEND(4, 3) FIR_APPEND(5, 3)
+    FIR_ROW(kNominate, 3, 16, 6, k_nominate, 6, 2, 8, 3) FIR_ROW(kNominate, 3, 16, 7, k_nominate, 7, 2, 8, 3)
+    FIR_SUB(1) FIR_SUB(2) FIR_SUB(4) FIR_SUB(8)
+};
+#undef FIR_ROW
+#undef FIR_SCAN
+#undef FIR_SCAN_M
 #undef FIR_DEEP
-#endif
+#undef FIR_APPEND
+#undef FIR_SUB
+
+const ScanRow* scan_row(int kind, int epi, int qb, int metric) {
+    for (const ScanRow& r : kScanTable)
+        if (r.kind == kind && r.epi == epi && r.qb == qb && r.metric == metric) return &r;
     return nullptr;
 }
 
-scan_fn pick(int epi, int qb, int metric) {
-    switch (epi) {
-        case kEpiTop1: return pick_kernel<kEpiTop1>(qb, metric);
-        case kEpiTopK: return pick_kernel<kEpiTopK>(qb, metric);
-        default: return pick_kernel<kEpiStore>(qb, metric);
-    }
+// What one scan launches: fn, for chi-square / KL its plain-range twin (launched next to it with the same grid -- which of the
+// two does the pass is decided on the device from the range flags, the other returns at once), the name of fn for the dispatch
+// record, and the dynamic LDS both are launched with. fn == nullptr: no kernel takes this shape.
+struct ScanKernel { scan_fn fn = nullptr, fn_plain = nullptr; const char* name = ""; size_t lds_bytes = 0; };
+constexpr size_t kMaxQueryTileLds = 144 * 1024;   // of the CU's 160 KiB; one workgroup per CU above 80 KiB (above 64 KiB the launch opts in: run_pass)
+// whole_chunks: start and end are multiples of 4 features; few_tiles: no more tiles than SIMDs (one-query tiles then take the
+// 16-chunk form when the query fits 64 KiB of LDS). The append epilogue with 16 queries is the two-tiles-per-read nomination scan.
+ScanKernel select_scan(int epi, int qb, int metric, bool whole_chunks, int dp4, bool few_tiles) {
+    const bool l2_hand = metric == kL2 && whole_chunks && (epi == kEpiTop1 || epi == kEpiAppend);
+    const size_t tile = (size_t)(dp4 + 1) * qb * 16;                       // query tile + one zero chunk of slack
+    const size_t tile_max = epi == kEpiAppend ? 64 * 1024 : kMaxQueryTileLds;
+    const size_t deep_tile = (size_t)dp4 * 4 * qb * sizeof(float);
+    ScanKernel k;
+    const ScanRow* r = nullptr;
+    if (epi == kEpiSubranges) r = scan_row(kSubranges, epi, qb, metric);
+    else if (l2_hand && tile <= tile_max && (r = scan_row(kL2Lds, epi, qb, metric))) k.lds_bytes = tile;
+    else if (l2_hand && (r = scan_row(kL2Scalar, epi, qb, metric))) k.lds_bytes = 0;
+    else if (few_tiles && deep_tile <= 64 * 1024 && (r = scan_row(kDeep, epi, qb, metric))) k.lds_bytes = deep_tile;
+    else if (epi == kEpiAppend && qb == 16) r = scan_row(kNominate, epi, qb, metric);
+    else r = scan_row(kGeneric, epi, qb, metric);
+    if (!r) return k;
+    k.fn = r->fn;
+    k.name = r->name;
+    if (metric == kChi2 || metric == kKL)
+        if (const ScanRow* p = scan_row(r->kind, epi, qb, metric + 2)) k.fn_plain = p->fn;
+    return k;
 }
 
 // Number of waves for `tiles` tiles. All waves are resident at once (waves <= capacity) and each
@@ -247,11 +238,6 @@ int pick_waves(int64_t tiles, int max_waves, int simds) {
 // cache-resident is VALU-bound either way, and 16 queries per pass halve its cache traffic
 // (profiles/r01_qb_table_100kx512.txt: 295k vs 175k queries/s at 100k x 512).
 double gallery_bytes(const fir_gallery* g) { return (double)g->tiles * 64.0 * g->dp4 * 16.0; }
-// Galleries up to this size are read with plain loads instead of the non-temporal hint. 0: measured no gain from
-// plain loads even for an 18 MB gallery that fits the L2s (one-query calls unchanged, multi-pass calls slower --
-// profiles/r01_small_gallery_sweep.txt), so every gallery is streamed.
-constexpr double kL2ResidentBytes = 0.0;
-
 int effective_qpp(const fir_gallery* g) {
     if (g->qpp > 0) return g->qpp;
     return gallery_bytes(g) <= 384.0 * 1024 * 1024 ? 16 : 8;
@@ -382,6 +368,29 @@ int max_waves_for(fir_gallery* g, scan_fn fn, size_t lds_bytes) {
     return waves;
 }
 
+// The ScanArgs fields every scan shares: the tiled gallery -- tiles [tile_begin, tile_begin + tiles_limit) of it while a row sample
+// is being taken (tiles_limit > 0) --, the feature range and the grid's wave count. Every gallery is read with the non-temporal
+// hint: plain loads gained nothing even for an 18 MB gallery that fits the L2s (one-query calls unchanged, multi-pass calls
+// slower -- profiles/r01_small_gallery_sweep.txt).
+ScanArgs scan_args(const fir_gallery* g, int32_t start, int32_t end, int waves) {
+    ScanArgs a{};
+    const int64_t tile0 = g->tiles_limit > 0 ? std::min<int64_t>(g->tile_begin, g->tiles) : 0;
+    const int64_t tiles = g->tiles_limit > 0 ? std::min<int64_t>(g->tiles_limit, g->tiles - tile0) : g->tiles;
+    a.gal4 = g->gal4 + (size_t)tile0 * g->dp4 * 64;
+    a.row_offset = g->row_offset + tile0 * kTileRows;
+    a.n = std::min<int64_t>(g->n - tile0 * kTileRows, tiles * kTileRows);
+    a.tiles = (int32_t)tiles;
+    a.dp4 = g->dp4;
+    a.start = start;
+    a.end = end;
+    a.waves = waves;
+    a.nt = 1;
+    return a;
+}
+
+bool whole_chunks(int32_t start, int32_t end) { return ((start | end) & 3) == 0; }
+bool few_tiles(const fir_gallery* g) { return g->tiles <= (int64_t)g->cus * 4; }
+
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
 int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
@@ -395,84 +404,40 @@ int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, in
         hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, qb_tile * ny,
                            g->d, g->dp4, qb_tile, qt, init_keys > 0 ? keys : nullptr, init_keys, g->range, next_serial(g));
     }
-    size_t lds_bytes = 0;
-    char kname[160];
-    scan_fn fn = pick_fast(epi, qb_tile, g->metric, start, end, g->dp4, &lds_bytes);
-    if (fn) std::snprintf(kname, sizeof kname, "fir::%s<%d, %d, %d, false>", lds_bytes ? "k_scan_l2_lds" : "k_scan_l2_fast", qb_tile / 8, FIR_FAST_U, FIR_FAST_WPS);
-    if (!fn && g->tiles <= (int64_t)g->cus * 4) {
-        fn = pick_deep(epi, qb_tile, g->metric, g->dp4, &lds_bytes);
-        if (fn) std::snprintf(kname, sizeof kname, "fir::k_scan<%d, %d, %d, %d, %d, %d, 1>", qb_tile, g->metric, kUDeep, epi, kKMax, wps_of(g->metric));
-    }
-    if (!fn) {
-        fn = pick(epi, qb_tile, g->metric);
-        std::snprintf(kname, sizeof kname, "fir::k_scan<%d, %d, %d, %d, %d, %d, 0>", qb_tile, g->metric, kU, epi, kKMax, wps_of(g->metric));
-    }
-    if (!fn) return fail(FIR_ERR_ARG, "no kernel for qb=%d metric=%d", qb_tile, g->metric);
-    if (lds_bytes > 64 * 1024) {   // more than the default dynamic LDS limit: opt in once per kernel
+    const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g));
+    if (!sk.fn) return fail(FIR_ERR_ARG, "no kernel for qb=%d metric=%d", qb_tile, g->metric);
+    if (sk.lds_bytes > 64 * 1024) {   // more than the default dynamic LDS limit: opt in once per kernel
         bool known = false;
-        for (const auto& e : g->occ) known = known || (e.fn == (const void*)fn && e.lds == lds_bytes);
-        if (!known) FIR_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxQueryTileLds));
+        for (const auto& e : g->occ) known = known || (e.fn == (const void*)sk.fn && e.lds == sk.lds_bytes);
+        if (!known) FIR_HIP(hipFuncSetAttribute((const void*)sk.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxQueryTileLds));
     }
-    // chi-square / KL: the plain-range twin of the kernel, launched next to it with the same grid -- which of the two
-    // does the pass is decided on the device from the range flags (k_scan), the other returns at once
-    scan_fn fn_plain = nullptr;
-    if (g->metric != kL2) {
-        size_t lds2 = 0;
-        if (g->tiles <= (int64_t)g->cus * 4 && lds_bytes > 0) fn_plain = pick_deep(epi, qb_tile, g->metric + 2, g->dp4, &lds2);
-        if (!fn_plain && lds_bytes == 0) fn_plain = pick(epi, qb_tile, g->metric + 2);
-    }
-    int max_waves = max_waves_for(g, fn, lds_bytes);
-    if (fn_plain) max_waves = std::min(max_waves, max_waves_for(g, fn_plain, lds_bytes));
+    int max_waves = max_waves_for(g, sk.fn, sk.lds_bytes);
+    if (sk.fn_plain) max_waves = std::min(max_waves, max_waves_for(g, sk.fn_plain, sk.lds_bytes));
     int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
     const int groups = epi == kEpiTop1 && g->sample_groups > 1 && g->metric != kL2 ? g->sample_groups : 0;
     if (groups) waves = std::max(4 * groups, waves / (4 * groups) * (4 * groups));      // a wave's tiles all belong to one group
     g->last_waves = waves;
     if (waves_used) *waves_used = waves;
-    ScanArgs a{};
+    ScanArgs a = scan_args(g, start, end, waves);
     a.groups = groups;
     a.group_stride = g->sample_group_stride;
     a.qt = qt;
-    const int64_t tile0 = g->tiles_limit > 0 ? std::min<int64_t>(g->tile_begin, g->tiles) : 0;
-    const int64_t tiles = g->tiles_limit > 0 ? std::min<int64_t>(g->tiles_limit, g->tiles - tile0) : g->tiles;
-    a.gal4 = g->gal4 + (size_t)tile0 * g->dp4 * 64;
-    a.row_offset = g->row_offset + tile0 * kTileRows;
-    a.n = std::min<int64_t>(g->n - tile0 * kTileRows, tiles * kTileRows);
-    a.tiles = (int32_t)tiles;
-    a.dp4 = g->dp4;
-    a.start = start;
-    a.end = end;
-    a.waves = waves;
     a.keys = keys;
     a.out = out;
     a.out_stride = out_stride;
     a.nq = qb_tile;
     a.k = k;
     a.qt_stride = (int64_t)kk * qb_tile;
-    a.nt = gallery_bytes(g) > kL2ResidentBytes ? 1 : 0;
     a.range = g->range;
     a.serial = g->q_serial;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g->profiling) {
-        if (g->ev_used + 2 > g->ev.size()) {
-            for (int i = 0; i < 64; ++i) {
-                hipEvent_t e;
-                FIR_HIP(hipEventCreate(&e));
-                g->ev.push_back(e);
-            }
-        }
-        e0 = g->ev[g->ev_used++];
-        e1 = g->ev[g->ev_used++];
-        FIR_HIP(hipEventRecord(e0, st));
-    }
-    hipLaunchKernelGGL(fn, dim3(waves / 4, ny), dim3(kBlock), lds_bytes, st, a);
-    if (fn_plain) hipLaunchKernelGGL(fn_plain, dim3(waves / 4, ny), dim3(kBlock), lds_bytes, st, a);
     // algorithmic bytes of one launch: per pass the gallery range once, the query tile, the keys
     const double bytes_alg = ny * ((double)a.n * (end - start) * 4.0 + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
-    if (g->profiling) {
-        FIR_HIP(hipEventRecord(e1, st));
-        g->last_bytes = bytes_alg;
-    }
-    if (!g->quiet) note_dispatch(g, (const void*)fn, kname, g->call_launches++, waves / 4, ny, kBlock, lds_bytes, qb_tile, bytes_alg, 0.0, 0);
+    int rc;
+    if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
+    hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
+    if (sk.fn_plain) hipLaunchKernelGGL(sk.fn_plain, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
+    if ((rc = fir_gallery_profile_end_(g, st, bytes_alg))) return rc;
+    if (!g->quiet) note_dispatch(g, (const void*)sk.fn, sk.name, g->call_launches++, waves / 4, ny, kBlock, sk.lds_bytes, qb_tile, bytes_alg, 0.0, 0);
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
@@ -495,7 +460,7 @@ int top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     int rc = grow(g->qt, g->qt_cap, (size_t)qb * g->dp4 * 4 + 64);   // +64: the fast kernel prefetches one unit past the tile
     if (rc) return rc;
     // 16 queries per pass exist only in the hand-scheduled kernel (whole-chunk L2 ranges)
-    int cap = pick_fast(kEpiTop1, 16, g->metric, start, end, g->dp4, nullptr) ? effective_qpp(g) : std::min(effective_qpp(g), 8);
+    int cap = g->metric == kL2 && whole_chunks(start, end) ? effective_qpp(g) : std::min(effective_qpp(g), 8);
     // 16 queries per pass only while their tile fits the default 64 KiB of LDS (d <= 1020): a larger tile leaves one
     // workgroup per CU, and the 8-query tile then does better
     if (cap > 8 && (size_t)(g->dp4 + 1) * 16 * 16 > 64 * 1024) cap = 8;
@@ -511,9 +476,6 @@ int top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     }
     return FIR_OK;
 }
-
-int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
-                   hipStream_t st);
 
 int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st);
 
@@ -557,257 +519,269 @@ int topk_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     return FIR_OK;
 }
 
-// The K nearest rows of a batch through candidate lists (see k_scan_l2_lds<..., APPEND>). Returns FIR_ERR_STATE (without
-// setting the error text) when a query could not be certified: fewer than K sample rows below 100000, or a list overflow.
+// ---- the K nearest rows of a batch through candidate lists (see k_scan_l2_lds<..., APPEND>) ---------------------------------------
+// A threshold per query from a row sample, an append scan at the speed of the top-1 scan, the K smallest of each list.
 constexpr int kListCap = 4096;
-int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
-                   hipStream_t st) {
-    // the hand-scheduled LDS-tile kernel where it applies (L2, whole-chunk ranges, tile within 64 KiB), else the generic one
-    size_t lds_bytes = 0;
-    scan_fn probe = pick_fast(kEpiTop1, 8, g->metric, start, end, g->dp4, &lds_bytes);
-    const bool fast = probe && lds_bytes > 0 && lds_bytes <= 64 * 1024;
-    if (!fast) lds_bytes = 0;
-    // chi-square over a plain-range gallery: the append scan runs a NOMINATION metric (1-ulp reciprocal, 5.5 instead of 11 issue
-    // slots per element) against a threshold widened by its error bound, and the few hundred appended rows per query are
-    // re-ranked with the reference's arithmetic before the K smallest are taken: the same keys as the exact scan, about twice
-    // as fast. Every row whose reference distance is <= the unwidened threshold is appended (approx <= exact (1 + eps)), and
-    // the K-th smallest reference distance is <= that threshold (K sample rows are), so the K best are all in the list.
-    const bool no_nominate = fir_knob_("FIR_NO_CHI2_NOMINATION") != nullptr;      // experiments
-    const bool nominate = g->metric == kChi2 && g->gallery_plain && !no_nominate && (size_t)g->d * sizeof(float) <= 48 * 1024;
-    // KL over a plain-range gallery, the entropy form: KL = ln2 (Lq + Lg - E), Lq = sum(l log2 l + l), Lg the same over the row (both
-    // added up in double once per query / per row), E = sum_k s_k log2 s_k with s_k = l_k + r_k the only sum the scan runs: a packed
-    // add, a v_log_f32 and a packed fma per (value, query) = 3 issue slots instead of the ~35 of two quotients and two logarithms.
-    // Error against the reference's float value, u = 2^-24, S = sum(l) + sum(r), |log2 s_k| <= 26 in the plain range:
-    //   rounding of s_k: (26 + log2 e) u s_k;  v_log_f32, 1 ulp of a value below 32: 32 u s_k;  the fmas of a 4 U-term group and
-    //   the tail / edge terms: <= 64 * 26.1 u S;  the nf / (4 U) group sums: (nf / 32) 26.1 u S;  Lq, Lg to float and the two
-    //   combining operations: <= 85 u S;  the reference's own chain (two products and two adds per feature, |terms| <= S): (2 nf + 8) u S
-    //   |entropy form - reference| <= B = [ln2 (26.1 (64 + nf / 32) + 150) + 2 nf + 8] 2^-24 (sum(l) + max_rows sum(r)) / nf.
-    // The threshold is widened by 1.5 B (k_query_entropy_widen), the appended rows are re-ranked with the exact scan's arithmetic.
-    const bool klent = g->metric == kKL && g->gallery_plain && !no_nominate && (size_t)g->d * sizeof(float) <= 48 * 1024 && FIR_U == 8;
-    // Two nomination metrics. kChi2Approx: (l - r)^2 * rcp(l + r), within (2 nf + 8) 2^-24 RELATIVE of the reference's value (all
-    // terms >= 0), 5.5-6.6 issue slots per element. kChi2Harm (default): chi2 = sum(l) + sum(r) - 4 sum_k 1/(1/l_k + 1/r_k), two
-    // terms per reciprocal, 1/A + 1/B = (A + B) / (A B) with A = 1/l_k + 1/r_k: 2.25 issue slots per element, 1/r computed once per
-    // gallery value and pass. Its error is relative to sum(l) + sum(r), not to chi2, u = 2^-24: 1/l (IEEE division) u, 1/r (v_rcp_f32,
-    // 1 ulp) 2 u, so A and B within 3 u, A + B 4 u, A B 7 u, its reciprocal 9 u, the pair of terms (4 + 9 + 1) u = 14 u of its value;
-    // harmonic terms <= (l + r)/4, so 4 * their sum <= sum(l) + sum(r): 14 u (sum(l) + sum(r)); the fma chain of nf / 2 non-negative
-    // terms adds nf u / 2, the two plain sums nf u each, the reference's own chain (nf + 3) u of chi2 <= sum(l) + sum(r):
-    //   |harmonic form - reference| <= B = (3 nf + 19) 2^-24 (sum(l) + max_rows sum(r)) / nf.
-    // The threshold is widened by 1.5 B (k_query_sums_widen): every row whose reference distance is within the unwidened one is appended.
+constexpr float kUlp = 5.9604645e-8f;   // u = 2^-24
+
+// chi-square over a plain-range gallery: the append scan runs a NOMINATION metric against a threshold widened by its error bound,
+// and the few hundred appended rows per query are re-ranked with the reference's arithmetic before the K smallest are taken: the
+// same keys as the exact scan, about twice as fast. Every row whose reference distance is <= the unwidened threshold is appended,
+// and the K-th smallest reference distance is <= that threshold (K sample rows are), so the K best are all in the list.
+// Two nomination metrics. kChi2Approx: (l - r)^2 * rcp(l + r), within (2 nf + 8) 2^-24 RELATIVE of the reference's value (all
+// terms >= 0), 5.5-6.6 issue slots per element instead of 11: the threshold is scaled by 1 + 1.5 (2 nf + 16) u (approx_tau_scale).
+// kChi2Harm (default): chi2 = sum(l) + sum(r) - 4 sum_k 1/(1/l_k + 1/r_k), two terms per reciprocal, 1/A + 1/B = (A + B) / (A B)
+// with A = 1/l_k + 1/r_k: 2.25 issue slots per element, 1/r computed once per gallery value and pass. Its error is relative to
+// sum(l) + sum(r), not to chi2, u = 2^-24: 1/l (IEEE division) u, 1/r (v_rcp_f32, 1 ulp) 2 u, so A and B within 3 u, A + B 4 u, A B 7 u,
+// its reciprocal 9 u, the pair of terms (4 + 9 + 1) u = 14 u of its value; harmonic terms <= (l + r)/4, so 4 * their sum <= sum(l) +
+// sum(r): 14 u (sum(l) + sum(r)); the fma chain of nf / 2 non-negative terms adds nf u / 2, the two plain sums nf u each, the
+// reference's own chain (nf + 3) u of chi2 <= sum(l) + sum(r):
+//   |harmonic form - reference| <= B = (3 nf + 19) 2^-24 (sum(l) + max_rows sum(r)) / nf.
+// scale * B's coefficient of sum(l) + max_rows sum(r); k_query_sums_widen widens the threshold by 1.5 times what it is given.
+float harm_bound_coef(float nf, float scale) { return scale * (3.0f * nf + 19.0f) * kUlp / nf; }
+float approx_tau_scale(float nf) { return 1.0f + 1.5f * (2.0f * nf + 16.0f) * kUlp; }
+
+// KL over a plain-range gallery, the entropy form: KL = ln2 (Lq + Lg - E), Lq = sum(l log2 l + l), Lg the same over the row (both
+// added up in double once per query / per row), E = sum_k s_k log2 s_k with s_k = l_k + r_k the only sum the scan runs: a packed
+// add, a v_log_f32 and a packed fma per (value, query) = 3 issue slots instead of the ~35 of two quotients and two logarithms.
+// Error against the reference's float value, u = 2^-24, S = sum(l) + sum(r), |log2 s_k| <= 26 in the plain range:
+//   rounding of s_k: (26 + log2 e) u s_k;  v_log_f32, 1 ulp of a value below 32: 32 u s_k;  the fmas of a 4 U-term group and
+//   the tail / edge terms: <= 64 * 26.1 u S;  the nf / (4 U) group sums: (nf / 32) 26.1 u S;  Lq, Lg to float and the two
+//   combining operations: <= 85 u S;  the reference's own chain (two products and two adds per feature, |terms| <= S): (2 nf + 8) u S
+//   |entropy form - reference| <= B = [ln2 (26.1 (64 + nf / 32) + 150) + 2 nf + 8] 2^-24 (sum(l) + max_rows sum(r)) / nf
+// (U = 8 chunks per load group, as the kernels are instantiated). k_query_entropy_widen widens by 1.5 times what it is given.
+float entropy_bound_coef(float nf, float scale) { return scale * (0.6932f * (26.1f * (64.0f + nf / 32.0f) + 150.0f) + 2.0f * nf + 8.0f) * kUlp / nf; }
+
+// One call of topk_lists_dev: its arguments, the form it takes (list_form) and its workspace (list_workspace).
+struct ListCall {
+    fir_gallery* g; const float* d_queries; int32_t qb, start, end, k; hipStream_t st;
+    bool nominate, harm, klent;   // chi-square nomination (kChi2Approx, or kChi2Harm when harm is set too); KL nomination (kKLEnt)
+    bool approx_samples;          // the row samples run the nomination metric too
+    int nh, qpad;                 // tiles of eight queries per gallery read of the append scan; qb padded to whole reads
+    int sample_stride;            // keys of sample group i: skeys[i * sample_stride + q]
+    bool tiles_ready;             // the query tiles are already in g->qt, in the nomination form (list_row_samples)
+    uint64_t *skeys, *lists; float *tau, *sq; int32_t *counts, *flag;
+    float nf() const { return (float)(end - start); }
+    float bound_coef(float scale) const { return harm ? harm_bound_coef(nf(), scale) : entropy_bound_coef(nf(), scale); }
+    int nomination_metric() const { return klent ? (int)kKLEnt : harm ? (int)kChi2Harm : nominate ? (int)kChi2Approx : g->metric; }
+    int transpose_form() const { return harm ? 1 : klent ? 2 : 0; }    // k_transpose_queries: 1 = 1/l, 2 = l + 2^-100
+};
+
+void list_form(ListCall& c) {
+    const fir_gallery* g = c.g;
+    const bool no_nominate = fir_knob_("FIR_NO_CHI2_NOMINATION") != nullptr;                   // experiments / tests
+    const bool allowed = g->gallery_plain && !no_nominate && (size_t)g->d * sizeof(float) <= 48 * 1024;   // (k_list_rerank stages the query in LDS)
     const char* form_env = fir_knob_("FIR_CHI2_NOMINATION");                                   // experiments / tests: 1 = kChi2Approx
-    const int chi2_form = form_env ? std::atoi(form_env) : 2;
-    const bool harm = nominate && chi2_form == 2;
-    const float tau_scale = nominate && !harm ? 1.0f + 1.5f * (2.0f * (float)(end - start) + 16.0f) * 5.9604645e-8f : 1.0f;
+    c.nominate = g->metric == kChi2 && allowed;
+    c.harm = c.nominate && (form_env ? std::atoi(form_env) : 2) == 2;
+    c.klent = g->metric == kKL && allowed;
     // the two cheap nomination forms take two tiles of 8 queries per gallery read (k_nominate): whole pairs of tiles
-    const int nh = (harm || klent) && !fir_knob_("FIR_NOMINATE_ONE_TILE") ? 2 : 1;
-    const int qpad = (qb + 8 * nh - 1) / (8 * nh) * (8 * nh);
-    void *p_skeys = nullptr, *p_small = nullptr, *p_lists = nullptr;
+    c.nh = c.harm || c.klent ? 2 : 1;
+    c.qpad = (c.qb + 8 * c.nh - 1) / (8 * c.nh) * (8 * c.nh);
+    // chi-square / KL nomination: the row samples run the NOMINATION metric too (2.25 / 3 issue slots per element instead of the
+    // exact metric's 11 / ~35: the samples were 0.9 of a 256-query call's 12.3 ms). A sampled minimum is then within B of the
+    // reference's value of that row, so at least K rows have a reference distance <= max_i(sample_i) + B, and the append scan
+    // (the same metric) has to take everything <= max_i(sample_i) + 2 B: the thresholds are widened by 2.5 B instead of 1.5 B.
+    c.approx_samples = (c.harm || c.klent) && !fir_knob_("FIR_EXACT_SAMPLES");
+    c.sample_stride = c.approx_samples ? c.qpad : c.qb;
+    c.tiles_ready = false;
+}
+
+int list_workspace(ListCall& c) {
+    fir_gallery* g = c.g;
+    void *p_skeys = nullptr, *p_small = nullptr, *p_lists = nullptr, *p_sq = nullptr;
     int rc;
-    if ((rc = fir_gallery_scratch_(g, 12, (size_t)qpad * k * 8, &p_skeys))) return rc;
-    if ((rc = fir_gallery_scratch_(g, 13, (size_t)qpad * 8 + 16, &p_small))) return rc;
-    if ((rc = fir_gallery_scratch_(g, 14, (size_t)qpad * kListCap * 8, &p_lists))) return rc;
-    uint64_t* skeys = (uint64_t*)p_skeys;
-    float* tau = (float*)p_small;
-    int32_t* counts = (int32_t*)(tau + qpad);
-    int32_t* flag = counts + qpad;
-    uint64_t* lists = (uint64_t*)p_lists;
-    if ((rc = grow(g->qt, g->qt_cap, (size_t)qpad * g->dp4 * 4 + 64))) return rc;      // before anything is queued on it
-    float* sq = nullptr;
-    if (harm || klent) {
-        void* p_sq = nullptr;
-        if ((rc = fir_gallery_scratch_(g, 15, (size_t)qpad * sizeof(float), &p_sq))) return rc;
-        sq = (float*)p_sq;
-        if (g->rs_start != start || g->rs_end != end || g->rs_metric != g->metric || !g->rowsum) {
-            if ((rc = grow(g->rowsum, g->rowsum_cap, (size_t)g->n + 4))) return rc;
-            FIR_HIP(hipMemsetAsync(g->rowsum + g->n, 0, 4 * sizeof(float), st));
-            hipLaunchKernelGGL(klent ? k_row_entropy : k_row_sums, dim3((unsigned)((g->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g->gal4, g->n, g->dp4,
-                               start, end, g->rowsum, (unsigned int*)(g->rowsum + g->n));
-            g->rs_start = start;
-            g->rs_end = end;
-            g->rs_metric = g->metric;
-        }
-    }
-    // 1. nearest row inside each of k disjoint groups of sample tiles (k top-1 scans, each over all the queries): the
-    //    largest of the k distances is a threshold at least k rows pass; about 2.3 * n * k / rows_sampled rows will
+    if ((rc = fir_gallery_scratch_(g, 12, (size_t)c.qpad * c.k * 8, &p_skeys))) return rc;
+    if ((rc = fir_gallery_scratch_(g, 13, (size_t)c.qpad * 8 + 16, &p_small))) return rc;
+    if ((rc = fir_gallery_scratch_(g, 14, (size_t)c.qpad * kListCap * 8, &p_lists))) return rc;
+    c.skeys = (uint64_t*)p_skeys;
+    c.tau = (float*)p_small;
+    c.counts = (int32_t*)(c.tau + c.qpad);
+    c.flag = c.counts + c.qpad;
+    c.lists = (uint64_t*)p_lists;
+    if ((rc = grow(g->qt, g->qt_cap, (size_t)c.qpad * g->dp4 * 4 + 64))) return rc;      // before anything is queued on it
+    if ((c.harm || c.klent) && (rc = fir_gallery_scratch_(g, 15, (size_t)c.qpad * sizeof(float), &p_sq))) return rc;
+    c.sq = (float*)p_sq;
+    return FIR_OK;
+}
+
+// kChi2Harm / kKLEnt: the per-row sums (entropies) over [start, end) and their maximum, kept until the range or the metric changes.
+int list_row_sums(ListCall& c) {
+    fir_gallery* g = c.g;
+    if (!(c.harm || c.klent) || (g->rs_start == c.start && g->rs_end == c.end && g->rs_metric == g->metric && g->rowsum)) return FIR_OK;
+    int rc;
+    if ((rc = grow(g->rowsum, g->rowsum_cap, (size_t)g->n + 4))) return rc;
+    FIR_HIP(hipMemsetAsync(g->rowsum + g->n, 0, 4 * sizeof(float), c.st));
+    hipLaunchKernelGGL(c.klent ? k_row_entropy : k_row_sums, dim3((unsigned)((g->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c.st, g->gal4, g->n, g->dp4,
+                       c.start, c.end, g->rowsum, (unsigned int*)(g->rowsum + g->n));
+    g->rs_start = c.start;
+    g->rs_end = c.end;
+    g->rs_metric = g->metric;
+    return FIR_OK;
+}
+
+// The per-query sums (entropies) of the nomination metrics, and tau widened by 1.5 * coef * (sum(l) + max_rows sum(r)).
+void list_widen(const ListCall& c, float coef) {
+    hipLaunchKernelGGL(c.harm ? k_query_sums_widen : k_query_entropy_widen, dim3(c.qpad), dim3(64), 0, c.st, c.d_queries, c.qb, c.g->d, c.start, c.end, c.sq,
+                       c.tau, (const unsigned int*)(c.g->rowsum + c.g->n), coef);
+}
+
+// The nearest row inside each of k disjoint groups of sample tiles (k top-1 scans, each over all the queries): the largest of the
+// k distances is a threshold at least k rows pass; about 2.3 * n * k / rows_sampled rows will.
+int list_row_samples(ListCall& c) {
+    fir_gallery* g = c.g;
+    const int32_t k = c.k, qb = c.qb;
+    const hipStream_t st = c.st;
     const int64_t want_rows = std::max<int64_t>(16384, (int64_t)g->n * k / 256);
     const int64_t group_tiles = std::max<int64_t>(1, std::min<int64_t>(g->tiles / k, (want_rows / k + kTileRows - 1) / kTileRows));
-    // (the row samples are not what a profile of this call is about: the events and the dispatch record belong to the append scan below)
+    // (the row samples are not what a profile of this call is about: the events and the dispatch record belong to the append scan)
+    // they hand the handle back as they found it, on every way out (a failed launch must not leave later calls quiet)
     const bool was_profiling = g->profiling, was_quiet = g->quiet;
     g->profiling = false;
     g->quiet = true;
-    // the row samples hand the handle back as they found it, on every way out (a failed launch must not leave later calls quiet)
-    bool samples_done = false;
-    auto end_samples = [&] {
-        if (samples_done) return;
-        samples_done = true;
+    auto restore = fir_on_exit([&] {
         g->tiles_limit = 0;
         g->tile_begin = 0;
         g->sample_groups = 0;
         g->profiling = was_profiling;
         g->quiet = was_quiet;
-    };
-    auto end_samples_on_exit = fir_on_exit(end_samples);
-    FIR_HIP(hipMemsetAsync(flag, 0, 4, st));
-    // chi-square / KL nomination: the row samples run the NOMINATION metric too (2.25 / 3 issue slots per element instead of the
-    // exact metric's 11 / ~35: the samples were 0.9 of a 256-query call's 12.3 ms). A sampled minimum is then within B of the
-    // reference's value of that row, so at least K rows have a reference distance <= max_i(sample_i) + B, and the append scan
-    // (the same metric) has to take everything <= max_i(sample_i) + 2 B: the thresholds are widened by 2.5 B instead of 1.5 B.
-    const bool approx_samples = (harm || klent) && !fir_knob_("FIR_EXACT_SAMPLES");
-    const int kk_q = g->dp4 * 4;
-    const int sample_stride = approx_samples ? qpad : qb;                  // keys of sample group i: skeys[i * sample_stride + q]
-    bool tiles_ready = false;                                              // the query tiles are already in g->qt, in the nomination form
-    if (approx_samples) {
-        const float nf = (float)(end - start);
-        const float coef = harm ? (3.0f * nf + 19.0f) * 5.9604645e-8f / nf
-                                : (0.6932f * (26.1f * (64.0f + nf / 32.0f) + 150.0f) + 2.0f * nf + 8.0f) * 5.9604645e-8f / nf;
+    });
+    FIR_HIP(hipMemsetAsync(c.flag, 0, 4, st));
+    int rc = FIR_OK;
+    if (c.approx_samples) {
+        const int kk = g->dp4 * 4;
         // the per-query sums first (thresholds at -inf: nothing to widen yet)
-        FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xFF800000u, (size_t)qpad, st));
-        hipLaunchKernelGGL(harm ? k_query_sums_widen : k_query_entropy_widen, dim3(qpad), dim3(64), 0, st, d_queries, qb, g->d, start, end, sq, tau,
-                           (const unsigned int*)(g->rowsum + g->n), coef);
+        FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)c.tau, (int)0xFF800000u, (size_t)c.qpad, st));
+        list_widen(c, c.bound_coef(1.0f));
         // every query tile of the call, once, in the form both scans read
-        hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk_q * qpad + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries, qb, g->d,
-                           g->dp4, 8, g->qt, (uint64_t*)nullptr, 0, g->range, next_serial(g), harm ? 1 : 2);
-        tiles_ready = true;
-        FIR_HIP(hipMemsetAsync(skeys, 0xFF, (size_t)qpad * k * 8, st));
-        const scan_fn sfn = harm ? (scan_fn)k_scan<8, kChi2Harm, kU, kEpiTop1, kKMax, kWpsPlain> : (scan_fn)k_scan<8, kKLEnt, kU, kEpiTop1, kKMax, kWpsPlain>;
-        const int64_t tiles = std::min<int64_t>(group_tiles * k, g->tiles);
-        int waves = pick_waves(tiles, max_waves_for(g, sfn, 0), g->cus * 4);
+        hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * c.qpad + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, c.d_queries, qb, g->d,
+                           g->dp4, 8, g->qt, (uint64_t*)nullptr, 0, g->range, next_serial(g), c.transpose_form());
+        c.tiles_ready = true;
+        FIR_HIP(hipMemsetAsync(c.skeys, 0xFF, (size_t)c.qpad * k * 8, st));
+        const ScanKernel sk = select_scan(kEpiTop1, 8, c.nomination_metric(), whole_chunks(c.start, c.end), g->dp4, false);
+        g->tile_begin = 0;
+        g->tiles_limit = std::min<int64_t>(group_tiles * k, g->tiles);
+        int waves = pick_waves(g->tiles_limit, max_waves_for(g, sk.fn, 0), g->cus * 4);
         if (k > 1) waves = std::max(4 * k, waves / (4 * k) * (4 * k));                  // a wave's tiles all belong to one group
-        ScanArgs a{};
+        ScanArgs a = scan_args(g, c.start, c.end, waves);
         a.groups = k > 1 ? k : 0;
-        a.group_stride = sample_stride;
-        a.qt = g->qt;
-        a.gal4 = g->gal4;
-        a.row_offset = g->row_offset;
-        a.n = std::min<int64_t>(g->n, tiles * kTileRows);
-        a.tiles = (int32_t)tiles;
-        a.dp4 = g->dp4;
-        a.start = start;
-        a.end = end;
-        a.waves = waves;
-        a.keys = skeys;
+        a.group_stride = c.sample_stride;
         a.nq = 8;
-        a.qt_stride = (int64_t)kk_q * 8;
-        a.nt = 0;
+        a.qt_stride = (int64_t)kk * 8;
+        a.nt = 0;                                     // the sample is a small part of the gallery: plain loads
         a.range = g->range;
         a.serial = g->q_serial;
-        a.flag = flag;
+        a.flag = c.flag;
         a.sg = g->rowsum;
-        a.sq = sq;
-        for (int y0 = 0; y0 < qpad / 8; y0 += g->max_tiles_per_launch) {
-            const int ny = std::min(g->max_tiles_per_launch, qpad / 8 - y0);
-            ScanArgs b = a;
-            b.qt = g->qt + (size_t)y0 * 8 * kk_q;
-            b.keys = skeys + (size_t)y0 * 8;
-            b.sq = sq + (size_t)y0 * 8;
-            hipLaunchKernelGGL(sfn, dim3(waves / 4, ny), dim3(kBlock), 0, st, b);
+        for (int y0 = 0; y0 < c.qpad / 8; y0 += g->max_tiles_per_launch) {
+            const int ny = std::min(g->max_tiles_per_launch, c.qpad / 8 - y0);
+            a.qt = g->qt + (size_t)y0 * 8 * kk;
+            a.keys = c.skeys + (size_t)y0 * 8;
+            a.sq = c.sq + (size_t)y0 * 8;
+            hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), 0, st, a);
         }
     } else if (k > 1 && g->metric != kL2) {
         // chi-square / KL: the K samples in ONE launch -- sample tile t belongs to group t mod K, a wave reports into its group's keys
         // (K launches of group_tiles tiles each leave most of the chip idle: a tile is one wave's serial work)
-        FIR_HIP(hipMemsetAsync(skeys, 0xFF, (size_t)qb * k * 8, st));
+        FIR_HIP(hipMemsetAsync(c.skeys, 0xFF, (size_t)qb * k * 8, st));
         g->tile_begin = 0;
         g->tiles_limit = group_tiles * k;
         g->sample_groups = k;
         g->sample_group_stride = qb;
-        rc = top1_dev(g, d_queries, qb, start, end, skeys, st);
-        g->sample_groups = 0;
+        rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys, st);
     } else {
         for (int i = 0; i < k && !rc; ++i) {
             g->tile_begin = i * group_tiles;
             g->tiles_limit = group_tiles;
-            rc = top1_dev(g, d_queries, qb, start, end, skeys + (size_t)i * qb, st);
+            rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys + (size_t)i * qb, st);
         }
     }
-    end_samples();
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_topk_tau, dim3((qpad + 63) / 64), dim3(64), 0, st, skeys, qb, qpad, k, tau, counts, flag, tau_scale, sample_stride);
+    return rc;
+}
+
+// tau[q] = the largest of query q's k sampled minima, widened by the nomination metric's error bound.
+void list_threshold(const ListCall& c) {
+    const float tau_scale = c.nominate && !c.harm ? approx_tau_scale(c.nf()) : 1.0f;
+    hipLaunchKernelGGL(k_topk_tau, dim3((c.qpad + 63) / 64), dim3(64), 0, c.st, c.skeys, c.qb, c.qpad, c.k, c.tau, c.counts, c.flag, tau_scale, c.sample_stride);
     // (1.5 B over an exact sample; 2.5 B over a sample in the nomination metric -- the kernels multiply by 1.5)
-    const float widen = approx_samples ? 1.67f : 1.0f;
-    if (harm) {
-        const float nf = (float)(end - start);
-        hipLaunchKernelGGL(k_query_sums_widen, dim3(qpad), dim3(64), 0, st, d_queries, qb, g->d, start, end, sq, tau, (const unsigned int*)(g->rowsum + g->n),
-                           widen * (3.0f * nf + 19.0f) * 5.9604645e-8f / nf);
-    }
-    if (klent) {
-        const float nf = (float)(end - start);
-        hipLaunchKernelGGL(k_query_entropy_widen, dim3(qpad), dim3(64), 0, st, d_queries, qb, g->d, start, end, sq, tau, (const unsigned int*)(g->rowsum + g->n),
-                           widen * (0.6932f * (26.1f * (64.0f + nf / 32.0f) + 150.0f) + 2.0f * nf + 8.0f) * 5.9604645e-8f / nf);
-    }
-    // 2. the append scan over the whole gallery: 8 queries per tile, every tile of the call in one launch (blockIdx.y)
-    const int kk = g->dp4 * 4;
-    scan_fn fn = fast ? (scan_fn)k_scan_l2_lds<1, FIR_FAST_U, FIR_FAST_WPS, true>
-                      : klent ? (scan_fn)k_scan<8, kKLEnt, kU, kEpiAppend, kKMax, kWpsPlain>
-                      : harm ? (scan_fn)k_scan<8, kChi2Harm, kU, kEpiAppend, kKMax, kWpsPlain>
-                      : nominate ? (scan_fn)k_scan<8, kChi2Approx, kU, kEpiAppend, kKMax, kWpsPlain>
-                      : g->metric == kL2 ? (scan_fn)k_scan<8, kL2, kU, kEpiAppend, kKMax, kWps>
-                      : g->metric == kChi2 ? (scan_fn)k_scan<8, kChi2, kU, kEpiAppend, kKMax, kWps>
-                                           : (scan_fn)k_scan<8, kKL, kU, kEpiAppend, kKMax, kWps>;
-    const scan_fn fn_plain = nominate || klent ? nullptr
-                           : g->metric == kChi2 ? (scan_fn)k_scan<8, kChi2InRange, kU, kEpiAppend, kKMax, kWpsPlain>
-                           : g->metric == kKL ? (scan_fn)k_scan<8, kKLInRange, kU, kEpiAppend, kKMax, kWpsPlain> : nullptr;   // see run_pass
-    if (nh == 2) fn = klent ? (scan_fn)k_nominate<kKLEnt, 2, kU, kWpsPlain> : (scan_fn)k_nominate<kChi2Harm, 2, kU, kWpsPlain>;
-    char fn_name[96];
-    if (nh == 2) std::snprintf(fn_name, sizeof fn_name, "fir::k_nominate<%d, 2, %d, %d>", klent ? (int)kKLEnt : (int)kChi2Harm, kU, kWpsPlain);
-    else if (fast) std::snprintf(fn_name, sizeof fn_name, "fir::k_scan_l2_lds<1, %d, %d, true>", FIR_FAST_U, FIR_FAST_WPS);
-    else std::snprintf(fn_name, sizeof fn_name, "fir::k_scan<8, %d, %d, %d, %d, %d>", klent ? (int)kKLEnt : harm ? (int)kChi2Harm : nominate ? (int)kChi2Approx : g->metric, kU,
-                       (int)kEpiAppend, kKMax, (nominate || klent) ? kWpsPlain : kWps);
-    int launches_noted = 0;
-    int max_waves = max_waves_for(g, fn, lds_bytes);
-    if (fn_plain) max_waves = std::min(max_waves, max_waves_for(g, fn_plain, lds_bytes));
+    if (c.harm || c.klent) list_widen(c, c.bound_coef(c.approx_samples ? 1.67f : 1.0f));
+}
+
+// The append scan over the whole gallery: 8 queries per tile, every tile of the call in one launch (blockIdx.y) -- the hand-scheduled
+// LDS-tile kernel where it applies (L2, whole-chunk ranges, tile within 64 KiB), k_nominate for the two cheap forms, else the generic one.
+int list_append_scan(const ListCall& c) {
+    fir_gallery* g = c.g;
+    const hipStream_t st = c.st;
+    const int nh = c.nh, kk = g->dp4 * 4;
+    const ScanKernel sk = select_scan(kEpiAppend, 8 * nh, c.nomination_metric(), whole_chunks(c.start, c.end), g->dp4, false);
+    int launches_noted = 0, rc;
+    int max_waves = max_waves_for(g, sk.fn, sk.lds_bytes);
+    if (sk.fn_plain) max_waves = std::min(max_waves, max_waves_for(g, sk.fn_plain, sk.lds_bytes));
     const int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
     const int tiles_per_launch = nh == 2 ? std::max(2, g->max_tiles_per_launch & ~1) : g->max_tiles_per_launch;
-    for (int q0 = 0; q0 < qpad; q0 += 8 * tiles_per_launch) {
-        const int ny = std::min(tiles_per_launch, (qpad - q0) / 8);
-        const int live = std::max(0, std::min(qb - q0, ny * 8));
+    for (int q0 = 0; q0 < c.qpad; q0 += 8 * tiles_per_launch) {
+        const int ny = std::min(tiles_per_launch, (c.qpad - q0) / 8);
+        const int live = std::max(0, std::min(c.qb - q0, ny * 8));
         float* qt = g->qt + (size_t)q0 * kk;
-        if (!tiles_ready)
+        if (!c.tiles_ready)
             hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * 8 * ny + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                               d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, 8, qt, (uint64_t*)nullptr, 0, g->range, next_serial(g), harm ? 1 : klent ? 2 : 0);
-        ScanArgs a{};
+                               c.d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, 8, qt, (uint64_t*)nullptr, 0, g->range, next_serial(g), c.transpose_form());
+        ScanArgs a = scan_args(g, c.start, c.end, waves);
         a.range = g->range;
         a.serial = g->q_serial;
-        a.gal4 = g->gal4;
         a.qt = qt;
-        a.n = g->n;
-        a.tiles = (int32_t)g->tiles;
-        a.dp4 = g->dp4;
-        a.start = start;
-        a.end = end;
-        a.waves = waves;
-        a.row_offset = g->row_offset;
-        a.keys = lists + (size_t)q0 * kListCap;
+        a.keys = c.lists + (size_t)q0 * kListCap;
         a.k = kListCap;
-        a.tau = tau + q0;
-        a.counts = counts + q0;
+        a.tau = c.tau + q0;
+        a.counts = c.counts + q0;
         a.qt_stride = (int64_t)kk * 8;
-        a.nt = gallery_bytes(g) > kL2ResidentBytes ? 1 : 0;
-        a.flag = flag;
+        a.flag = c.flag;
         a.sg = g->rowsum;
-        a.sq = harm || klent ? sq + q0 : nullptr;
+        a.sq = c.sq ? c.sq + q0 : nullptr;
         // algorithmic bytes of the launch: one read of the compared features per nh tiles of eight queries, the query tiles, the appended keys aside
-        const double launch_bytes = (double)(ny / nh) * ((double)g->n * (end - start) * 4.0) + (double)ny * ((double)(end - start) * 32.0 + 64.0);
+        const double launch_bytes = (double)(ny / nh) * ((double)g->n * (c.end - c.start) * 4.0) + (double)ny * ((double)(c.end - c.start) * 32.0 + 64.0);
         if (!g->quiet && (rc = fir_gallery_profile_begin_(g, st))) return rc;
-        hipLaunchKernelGGL(fn, dim3(waves / 4, ny / nh), dim3(kBlock), lds_bytes, st, a);
-        if (fn_plain) hipLaunchKernelGGL(fn_plain, dim3(waves / 4, ny), dim3(kBlock), lds_bytes, st, a);
+        hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny / nh), dim3(kBlock), sk.lds_bytes, st, a);
+        if (sk.fn_plain) hipLaunchKernelGGL(sk.fn_plain, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
         if (!g->quiet) {
             if ((rc = fir_gallery_profile_end_(g, st, launch_bytes))) return rc;
-            note_dispatch(g, (const void*)fn, fn_name, launches_noted++, waves / 4, ny / nh, kBlock, lds_bytes, 8 * nh, launch_bytes, 0.0, 0);
+            note_dispatch(g, (const void*)sk.fn, sk.name, launches_noted++, waves / 4, ny / nh, kBlock, sk.lds_bytes, 8 * nh, launch_bytes, 0.0, 0);
         }
     }
-    // 3. (nomination) the reference's distance of every appended row, keys rewritten in place
-    if (klent)
-        hipLaunchKernelGGL(k_list_rerank<kKLInRange>, dim3(qb), dim3(kBlock), (size_t)g->d * sizeof(float), st, lists, counts, kListCap, g->gal4, g->dp4, g->n,
-                           g->row_offset, d_queries, g->d, start, end);
-    if (nominate)
-        hipLaunchKernelGGL(k_list_rerank<kChi2>, dim3(qb), dim3(kBlock), (size_t)g->d * sizeof(float), st, lists, counts, kListCap, g->gal4, g->dp4, g->n,
-                           g->row_offset, d_queries, g->d, start, end);
-    // 4. the K smallest keys of every list
-    hipLaunchKernelGGL(k_topk_select, dim3(qb), dim3(kBlock), 0, st, lists, counts, kListCap, k, d_keys, flag);
+    return FIR_OK;
+}
+
+// (nomination) the reference's distance of every appended row, keys rewritten in place; then the K smallest keys of every list.
+// FIR_ERR_STATE when a list overflowed or a sample fell short (the flag the kernels raise).
+int list_rerank_select(const ListCall& c, uint64_t* d_keys) {
+    const fir_gallery* g = c.g;
+    if (c.klent)
+        hipLaunchKernelGGL(k_list_rerank<kKLInRange>, dim3(c.qb), dim3(kBlock), (size_t)g->d * sizeof(float), c.st, c.lists, c.counts, kListCap, g->gal4, g->dp4, g->n,
+                           g->row_offset, c.d_queries, g->d, c.start, c.end);
+    if (c.nominate)
+        hipLaunchKernelGGL(k_list_rerank<kChi2>, dim3(c.qb), dim3(kBlock), (size_t)g->d * sizeof(float), c.st, c.lists, c.counts, kListCap, g->gal4, g->dp4, g->n,
+                           g->row_offset, c.d_queries, g->d, c.start, c.end);
+    hipLaunchKernelGGL(k_topk_select, dim3(c.qb), dim3(kBlock), 0, c.st, c.lists, c.counts, kListCap, c.k, d_keys, c.flag);
     FIR_HIP(hipGetLastError());
     int32_t h_flag = 0;
-    FIR_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, st));
-    FIR_HIP(hipStreamSynchronize(st));
+    FIR_HIP(hipMemcpyAsync(&h_flag, c.flag, 4, hipMemcpyDeviceToHost, c.st));
+    FIR_HIP(hipStreamSynchronize(c.st));
     return h_flag ? FIR_ERR_STATE : FIR_OK;
+}
+
+// Returns FIR_ERR_STATE (without setting the error text) when a query could not be certified: fewer than K sample rows below
+// 100000, or a list overflow.
+int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
+                   hipStream_t st) {
+    ListCall c{g, d_queries, qb, start, end, k, st};
+    list_form(c);
+    int rc;
+    if ((rc = list_workspace(c))) return rc;
+    if ((rc = list_row_sums(c))) return rc;
+    if ((rc = list_row_samples(c))) return rc;
+    list_threshold(c);
+    if ((rc = list_append_scan(c))) return rc;
+    return list_rerank_select(c, d_keys);
 }
 
 int range_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, float* d_out, hipStream_t st) {
@@ -821,18 +795,6 @@ int range_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start,
         q0 += t;
     }
     return FIR_OK;
-}
-
-constexpr int kUSub = 8;      // chunks per load group of k_scan_subranges: sub-ranges are multiples of 32 features
-scan_fn pick_subranges(int qb, int metric) {
-#ifndef FIR_MINIMAL
-#define FIR_SUB(QB, M) if (qb == QB && metric == M) return (scan_fn)k_scan_subranges<QB, M, kUSub, kWps>;
-    FIR_SUB(1, 0) FIR_SUB(2, 0) FIR_SUB(4, 0) FIR_SUB(8, 0)
-    FIR_SUB(1, 1) FIR_SUB(2, 1) FIR_SUB(4, 1) FIR_SUB(8, 1)
-    FIR_SUB(1, 2) FIR_SUB(2, 2) FIR_SUB(4, 2) FIR_SUB(8, 2)
-#undef FIR_SUB
-#endif
-    return nullptr;
 }
 
 int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t step, float* d_out, hipStream_t st,
@@ -852,28 +814,19 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
     for (int q0 = 0; q0 < qb; q0 += 8) {
         const int live = std::min(8, qb - q0);
         const int qbt = live <= 1 ? 1 : live <= 2 ? 2 : live <= 4 ? 4 : 8;   // kernel tile: the next power of two (extra queries are zero padding)
-        scan_fn fn = pick_subranges(qbt, g->metric);
+        const scan_fn fn = select_scan(kEpiSubranges, qbt, g->metric, whole_chunks(start, end), g->dp4, false).fn;
         if (!fn) return fail(FIR_ERR_ARG, "no sub-range kernel for qb=%d metric=%d", qbt, g->metric);
         hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * qbt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, qbt, g->qt, (uint64_t*)nullptr, 0);
         const int max_waves = max_waves_for(g, fn, 0);
-        ScanArgs a{};
-        a.gal4 = g->gal4;
+        ScanArgs a = scan_args(g, start, end, pick_waves(g->tiles, max_waves, g->cus * 4));
         a.qt = g->qt;
-        a.n = g->n;
-        a.tiles = (int32_t)g->tiles;
-        a.dp4 = g->dp4;
-        a.start = start;
-        a.end = end;
         a.step = step;
         a.step2 = step2;
-        a.waves = pick_waves(g->tiles, max_waves, g->cus * 4);
-        a.row_offset = g->row_offset;
         a.out = d_out + (size_t)q0 * g->n;
         a.out_stride = g->n;
         a.nq = live;
         a.k = qb;
-        a.nt = gallery_bytes(g) > kL2ResidentBytes ? 1 : 0;
         hipLaunchKernelGGL(fn, dim3(a.waves / 4), dim3(kBlock), 0, st, a);
         FIR_HIP(hipGetLastError());
     }
@@ -1533,14 +1486,14 @@ int wait_ticket(fir_gallery* g, volatile uint64_t* flag, uint64_t ticket) {
 // re-arms the device key, and the host spins on the ticket (falling back to hipStreamSynchronize after 2 ms).
 // 3 030 x 1536: 34 instead of 40 us per call (profiles/r01_sweep_notes.md). Returns 1 when the shape does not qualify.
 int top1_one_query(fir_gallery* g, const float* pinned_query, int32_t start, int32_t end, uint64_t* pinned_key) {
-    static const bool off = fir_knob_("FIR_NO_ONE_QUERY") != nullptr;      // experiments
     // up to 256 tiles (16 384 rows): every workgroup of this form ends on a device-wide fence before it is counted, and beyond
     // ~90 workgroups those fences cost more than the two extra launches of the general path (12 000 x 512: 25.5 against
     // 28.1 us; 24 000: 32.8 / 32.2; 50 000: 44.4 / 35.4)
-    if (off || g->metric != kL2 || g->n <= 0 || g->tiles > 256 || g->tiles_limit > 0 || g->profiling) return 1;
-    size_t lds_bytes = 0;
-    scan_fn fn = pick_deep(kEpiTop1, 1, g->metric, g->dp4, &lds_bytes);
-    if (!fn) return 1;
+    if (g->metric != kL2 || g->n <= 0 || g->tiles > 256 || g->tiles_limit > 0 || g->profiling) return 1;
+    const ScanKernel sk = select_scan(kEpiTop1, 1, g->metric, whole_chunks(start, end), g->dp4, /*few_tiles=*/true);
+    if (!sk.fn || sk.lds_bytes == 0) return 1;       // (only the form that stages the query in LDS publishes)
+    const scan_fn fn = sk.fn;
+    const size_t lds_bytes = sk.lds_bytes;
     if (!g->one_keys) {
         FIR_HIP(hipMalloc((void**)&g->one_keys, 64));
         g->one_done = (int32_t*)(g->one_keys + 4);
@@ -1550,20 +1503,11 @@ int top1_one_query(fir_gallery* g, const float* pinned_query, int32_t start, int
     const int max_waves = max_waves_for(g, fn, lds_bytes);
     const int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
     g->last_waves = waves;
-    ScanArgs a{};
+    ScanArgs a = scan_args(g, start, end, waves);
     a.qt = pinned_query;
-    a.gal4 = g->gal4;
-    a.row_offset = g->row_offset;
-    a.n = g->n;
-    a.tiles = (int32_t)g->tiles;
-    a.dp4 = g->dp4;
-    a.start = start;
-    a.end = end;
-    a.waves = waves;
     a.keys = g->one_keys;
     a.nq = 1;
     a.qt_stride = (int64_t)g->dp4 * 4;
-    a.nt = gallery_bytes(g) > kL2ResidentBytes ? 1 : 0;
     a.publish = pinned_key;
     a.done = g->one_done;
     a.ticket = ++g->one_ticket;

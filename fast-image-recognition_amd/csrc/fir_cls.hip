@@ -821,35 +821,6 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
         hipLaunchKernelGGL(k_cls_prep_query_tiles, dim3((unsigned)(((size_t)ntile * kk * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, dq, qb, c->d,
                            c->dp2, c->avg, c->qn);
         const bool one_tile = fir_knob_("FIR_CLS_ONE_TILE") != nullptr;
-        if (const char* form = fir_knob_("FIR_CLS_FORM")) {
-            // experiments (profiles/r04_k3_*.txt): "NT,R,U,BLOCK,WPS" = query tiles per read, rows per lane, double2 in flight per row, threads per
-            // workgroup, waves per SIMD of the launch bounds -- one of the instantiations below; the sums are the same bits in every form
-            int fnt = 2, fr = 1, fu = 8, fb = 256, fw = 2;
-            std::sscanf(form, "%d,%d,%d,%d,%d", &fnt, &fr, &fu, &fb, &fw);
-            typedef void (*scan_fn)(const double2*, const double*, int64_t, int, int, int, int, double*);
-            scan_fn fn = nullptr;
-            const char* nm = "?";
-#define FIR_CLS_PICK(NT_, R_, U_, B_, W_) if (fnt == NT_ && fr == R_ && fu == U_ && fb == B_ && fw == W_) { fn = k_cls_scan_lds<U_, NT_, B_, R_, W_>; nm = "fir::k_cls_scan_lds<" #U_ ", " #NT_ ", " #B_ ", " #R_ ", " #W_ ">"; }
-            FIR_CLS_PICK(2, 1, 8, 256, 2) FIR_CLS_PICK(2, 2, 4, 256, 2) FIR_CLS_PICK(2, 2, 8, 256, 2) FIR_CLS_PICK(2, 2, 4, 512, 2) FIR_CLS_PICK(2, 1, 4, 512, 4)
-            FIR_CLS_PICK(3, 1, 8, 512, 2) FIR_CLS_PICK(3, 2, 4, 512, 2) FIR_CLS_PICK(4, 1, 8, 512, 2) FIR_CLS_PICK(4, 2, 4, 512, 2) FIR_CLS_PICK(4, 1, 4, 512, 2)
-            FIR_CLS_PICK(2, 4, 2, 256, 2) FIR_CLS_PICK(2, 2, 2, 256, 2) FIR_CLS_PICK(4, 2, 2, 512, 2)
-#undef FIR_CLS_PICK
-            if (fn && (size_t)fnt * lds_tile <= 150 * 1024) {
-                CLS_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                const int wpc = fw * 4;                                          // waves per CU the launch bounds (and LDS) allow
-                const int64_t tsteps = (c->tiles + fr - 1) / fr;
-                const int wvf = (int)std::min<int64_t>(std::max<int64_t>((tsteps + fb / 64 - 1) / (fb / 64) * (fb / 64), fb / 64), (int64_t)c->cus * wpc);
-                for (int t0 = 0; t0 < ntile; t0 += 64) {
-                    const int tn = std::min(64, ntile - t0);
-                    cls_prof(c, 0, 0.0, nullptr);
-                    hipLaunchKernelGGL(fn, dim3(wvf / (fb / 64), (tn + fnt - 1) / fnt), dim3(fb), (size_t)fnt * lds_tile, c->stream, c->gal2, c->qn + (size_t)t0 * kk * 8, c->nt,
-                                       (int)c->tiles, c->dp2, wvf, qb - t0 * 8, c->sums + (size_t)t0 * 8 * c->nt);
-                    cls_prof(c, 1, (double)((tn + fnt - 1) / fnt) * ((double)c->tiles * 64.0 * c->dp2 * 16.0) + (double)tn * ((double)kk * 64.0 + 8.0 * 8.0 * (double)c->nt), nm);
-                }
-                CLS_HIP(hipGetLastError());
-                return FIR_OK;
-            }
-        }
         // Forms by tiles of eight queries per read of the training rows (profiles/r04_k3_forms.txt; 1M x 512, 64 queries, kernel ms per call):
         // one tile, one row per lane 5.7 (HBM-bound, 0.72 of the peak); two tiles 4.16 (round 3); two tiles, two rows per lane 3.90; four
         // tiles, two rows per lane 3.74 -- the f64 vector pipes are then 85-90 % busy at the 1.7 GHz the chip holds under this load
@@ -857,10 +828,12 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
         // query value serves two rows (the LDS pipe was two thirds busy at the vector pipes' full rate). A call is cut into groups of 4, 2, 1
         // tiles so that no group computes padding tiles.
         typedef void (*scan_fn)(const double2*, const double*, int64_t, int, int, int, int, double*);
-        struct Form { scan_fn fn; int nt, r, block, wpc; const char* name; };
-        const Form f4 = {k_cls_scan_lds<2, 4, 512, 2, 2>, 4, 2, 512, 8, "fir::k_cls_scan_lds<2, 4, 512, 2, 2>"};
-        const Form f2 = {k_cls_scan_lds<4, 2, 256, 2, 2>, 2, 2, 256, 8, "fir::k_cls_scan_lds<4, 2, 256, 2, 2>"};
-        const Form f1 = {k_cls_scan_lds<8, 1>, 1, 1, 256, 16, "fir::k_cls_scan_lds<8, 1>"};
+#define FIR_CLS_KERNEL(...) k_cls_scan_lds<__VA_ARGS__>, "fir::k_cls_scan_lds<" #__VA_ARGS__ ">"      // pointer and name from the same arguments
+        struct Form { int nt, r, block, wpc; scan_fn fn; const char* name; };
+        const Form f4 = {4, 2, 512, 8, FIR_CLS_KERNEL(2, 4, 512, 2, 2)};
+        const Form f2 = {2, 2, 256, 8, FIR_CLS_KERNEL(4, 2, 256, 2, 2)};
+        const Form f1 = {1, 1, 256, 16, FIR_CLS_KERNEL(8, 1)};
+#undef FIR_CLS_KERNEL
         {
             static bool attr_set[64] = {};                     // (per device: the attribute belongs to the device's copy of the code object)
             const int dv = c->device & 63;

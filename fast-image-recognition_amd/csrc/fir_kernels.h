@@ -26,29 +26,20 @@
 
 namespace fir {
 
-#ifndef FIR_PIPE
-#define FIR_PIPE 0
-#endif
-#ifndef FIR_NT
-#define FIR_NT 1   // +6 % on the 1M x 512 scan (profiles/r01_sweep_notes.md)
-#endif
 // One lane's float4 of a gallery tile. nt: non-temporal hint -- a gallery that is streamed from HBM once per pass
 // should not displace anything in L2; a gallery small enough to live in the L2s keeps the plain load so that the
-// next call finds it there (ScanArgs::nt, set per gallery by its size).
+// next call finds it there (ScanArgs::nt). +6 % on the 1M x 512 scan (profiles/r01_sweep_notes.md).
 __device__ __forceinline__ float4 ld_gallery(const float4* p, bool nt) {
-#if FIR_NT
     if (nt) {
         typedef float v4f __attribute__((ext_vector_type(4)));
         const v4f v = __builtin_nontemporal_load((const v4f*)p);
         return make_float4(v.x, v.y, v.z, v.w);
     }
-#endif
     return *p;
 }
 // U chunks of one lane, `stride` float4 apart; one uniform branch for the whole group.
 template <int U>
 __device__ __forceinline__ void ld_gallery_group(float4 (&g)[U], const float4* p, bool nt) {
-#if FIR_NT
     if (nt) {
         typedef float v4f __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -58,7 +49,6 @@ __device__ __forceinline__ void ld_gallery_group(float4 (&g)[U], const float4* p
         }
         return;
     }
-#endif
 #pragma unroll
     for (int u = 0; u < U; ++u) g[u] = p[(size_t)u * 64];
 }
@@ -309,27 +299,11 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                 TileAcc<QB, METRIC, U>::masked(acc, tile[(size_t)(c_lo - 1) * 64], qc, c_lo - 1, a.start, a.end);
 
             const float4* p = tile + (size_t)c_lo * 64;
-#if FIR_PIPE == 0
             for (int gi = 0; gi < ng; ++gi) {
                 float4 g[U];
                 ld_gallery_group<U>(g, p + (size_t)(gi * U) * 64, a.nt != 0);
                 TileAcc<QB, METRIC, U>::group(acc, g, qc, c_lo + gi * U);
             }
-#else
-            // register double buffer: group gi+1 is in flight while group gi is consumed
-            float4 g[U];
-            if (ng > 0) {
-                ld_gallery_group<U>(g, p, a.nt != 0);
-            }
-            for (int gi = 0; gi < ng; ++gi) {
-                float4 nx[U];
-                const int gn = gi + 1 < ng ? gi + 1 : gi;   // the last group re-reads itself (cache hit, keeps the loop branch-free)
-                ld_gallery_group<U>(nx, p + (size_t)(gn * U) * 64, a.nt != 0);
-                TileAcc<QB, METRIC, U>::group(acc, g, qc, c_lo + gi * U);
-#pragma unroll
-                for (int u = 0; u < U; ++u) g[u] = nx[u];
-            }
-#endif
             for (int c = c_end; c < c_hi; ++c)
                 TileAcc<QB, METRIC, U>::masked(acc, tile[(size_t)c * 64], qc, c, a.start, a.end);
             if ((a.end & 3) != 0)
@@ -816,11 +790,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan_l2_lds(const ScanArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int t = ts * R + r < a.tiles ? ts * R + r : a.tiles - 1;
-#ifdef FIR_DEBUG_TILEMOD   // timing experiments only: every tile reads one of the first few (cache-resident stream)
-            p[r] = a.gal4 + ((size_t)(t % FIR_DEBUG_TILEMOD) * a.dp4 + c_lo) * 64 + lane;
-#else
             p[r] = a.gal4 + ((size_t)t * a.dp4 + c_lo) * 64 + lane;
-#endif
         }
         f2 acc[R][NB][4];
 #pragma unroll
@@ -833,7 +803,6 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan_l2_lds(const ScanArgs a) {
         lds_unit<NB>(cur, lqv, c_lo * 4, 0);
 
         int c = c_lo;
-#if FIR_PIPE == 0
         for (; c + U <= c_hi; c += U) {
             float4 g[R][U];
 #pragma unroll
@@ -846,34 +815,6 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan_l2_lds(const ScanArgs a) {
                 l2_chunk_lds<NB, R>(acc, gu, cur, lqv, c + u);
             }
         }
-#else
-        // register double buffer: the next group's loads are in flight while this group is consumed
-        {
-            const int ng = (c_hi - c_lo) / U;
-            float4 g[R][U];
-            if (ng > 0) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) ld_gallery_group<U>(g[r], p[r], a.nt != 0);
-            }
-            for (int gi = 0; gi < ng; ++gi, c += U) {
-                float4 nxg[R][U];
-                const int gn = gi + 1 < ng ? gi + 1 : gi;   // the last group re-reads itself (L2 hit; keeps the loop branch-free)
-#pragma unroll
-                for (int r = 0; r < R; ++r) ld_gallery_group<U>(nxg[r], p[r] + (size_t)(gn * U) * 64, a.nt != 0);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    float4 gu[R];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) gu[r] = g[r][u];
-                    l2_chunk_lds<NB, R>(acc, gu, cur, lqv, c + u);
-                }
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int u = 0; u < U; ++u) g[r][u] = nxg[r][u];
-            }
-        }
-#endif
         for (; c < c_hi; ++c) {
             float4 gu[R];
 #pragma unroll
