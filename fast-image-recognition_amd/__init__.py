@@ -22,6 +22,7 @@ from .capi import (  # noqa: F401
     SHADOW_NONE,
     ShardedClsModel,
     ShardedGallery,
+    class_keys_merge,
     comm_unique_id,
     device_count,
     device_info,

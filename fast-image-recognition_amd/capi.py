@@ -51,6 +51,9 @@ SYMBOLS = [
     ("fir_gallery_classes_of", C.c_int, [_vp, _vp, C.c_int32, _vp]),
     ("fir_search_topk", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_topk_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_search_top_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_class_keys_merge", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_range_distances", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     ("fir_range_distances_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_twd_conventional", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp]),
@@ -193,6 +196,21 @@ def keys_unpack(keys):
     return idx, dist
 
 
+def class_keys_merge(keys, classes, k):
+    """keys[parts, qb, k] / classes[parts, qb, k] of search_top_classes_keys_dev over row shards -> (keys[qb, k], classes[qb, k])
+    of the whole gallery (fir_class_keys_merge: per class the smallest key, then the k smallest)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    classes = np.ascontiguousarray(classes, dtype=np.int32)
+    if keys.ndim != 3 or keys.shape != classes.shape or keys.shape[2] != k:
+        raise ValueError("keys and classes must both be [parts, qb, k]")
+    parts, qb, _ = keys.shape
+    keys_out = np.empty((qb, k), np.uint64)
+    classes_out = np.empty((qb, k), np.int32)
+    _check(lib().fir_class_keys_merge(keys.ctypes.data_as(_vp), classes.ctypes.data_as(_vp), parts, qb, k, keys_out.ctypes.data_as(_vp),
+                                      classes_out.ctypes.data_as(_vp)))
+    return keys_out, classes_out
+
+
 class DispatchInfo(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("path", C.c_int32), ("kernel", C.c_char * 160), ("launches", C.c_int32), ("grid_x", C.c_int32),
                 ("grid_y", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32), ("vgprs", C.c_int32), ("queries_per_pass", C.c_int32),
@@ -309,6 +327,21 @@ class Gallery:
 
     def search_topk_keys_dev(self, q_ptr, qb, k, keys_ptr, start=0, end=0, stream=None):
         _check(lib().fir_search_topk_keys_dev(self._h, _vp(q_ptr), qb, start, end, k, _vp(keys_ptr), _vp(stream) if stream else None))
+
+    def search_top_classes(self, queries, num_classes, k, start=0, end=0):
+        """The k nearest distinct classes of each query: (classes, idx, dist), each [qb, k]; unused slots -1 / -1 / 100000."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        cls = np.empty((q.shape[0], k), np.int32)
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        _check(lib().fir_search_top_classes(self._h, pq, q.shape[0], start, end, num_classes, k, cls.ctypes.data_as(_vp), idx.ctypes.data_as(_vp),
+                                            dist.ctypes.data_as(_vp)))
+        return cls, idx, dist
+
+    def search_top_classes_keys_dev(self, q_ptr, qb, num_classes, k, keys_ptr, classes_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_top_classes_keys_dev(self._h, _vp(q_ptr), qb, start, end, num_classes, k, _vp(keys_ptr), _vp(classes_ptr),
+                                                     _vp(stream) if stream else None))
 
     def range_distances(self, queries, start=0, end=0):
         q, pq = _f32(queries)

@@ -143,12 +143,12 @@ typedef void (*scan_fn)(const ScanArgs);
 // the numbers those names have always carried:
 //   metric     0 L2, 1 chi-square, 2 KL, 3 / 4 their plain-range forms, 5-7 the nomination metrics (fir_common.h)
 //   U          kU chunks per load group, kUDeep in the few-tiles form, kUSub in k_scan_subranges
-//   epilogue   0 top-1, 1 top-K, 2 store, 3 append
+//   epilogue   0 top-1, 1 top-K, 2 store, 3 append, 5 class minimum
 //   KMAX       kKMax
 //   waves per SIMD   kWps; kWpsPlain for the metrics from 3 on
 enum ScanKind { kGeneric, kDeep, kL2Lds, kL2Scalar, kNominate, kSubranges };
 constexpr int kEpiSubranges = 4;   // selector only: k_scan_subranges (one stored distance per sub-range)
-static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
+static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kEpiClassMin == 5 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
                   kKLInRange == 4 && kChi2Approx == 5 && kChi2Harm == 6 && kKLEnt == 7 && kU == 8 && kUDeep == 16 && kUSub == 8 && kKMax == 8 && kWps == 4 && kWpsPlain == 3,
               "kScanTable spells these as numbers");
 struct ScanRow { int kind, epi, qb, metric; scan_fn fn; const char* name; };
@@ -179,6 +179,8 @@ static const ScanRow kScanTable[] = {
     FIR_APPEND(0, 4) FIR_APPEND(1, 4) FIR_APPEND(2, 4) FIR_APPEND(3, 3) FIR_APPEND(4, 3) FIR_APPEND(5, 3)
     FIR_ROW(kNominate, 3, 16, 6, k_nominate, 6, 2, 8, 3) FIR_ROW(kNominate, 3, 16, 7, k_nominate, 7, 2, 8, 3)
     FIR_SUB(1) FIR_SUB(2) FIR_SUB(4) FIR_SUB(8)
+    // top_classes_dev: the smallest key of every class, tiles of 8 queries
+    FIR_SCAN_M(5, 8)
 };
 #undef FIR_ROW
 #undef FIR_SCAN
@@ -385,23 +387,28 @@ ScanArgs scan_args(const fir_gallery* g, int32_t start, int32_t end, int waves) 
     a.end = end;
     a.waves = waves;
     a.nt = 1;
+    a.cls = g->cls ? g->cls + tile0 * kTileRows : nullptr;
     return a;
 }
 
 bool whole_chunks(int32_t start, int32_t end) { return ((start | end) & 3) == 0; }
 bool few_tiles(const fir_gallery* g) { return g->tiles <= (int64_t)g->cus * 4; }
 
+// What the class-minimum epilogue needs beyond a pass's other arguments (`keys` is then the table cmin[query][class]).
+// nq: live queries of the launch, the last tile may be part full; tiles_ready: the pass before this one left the same tiles in g->qt
+struct ClassPass { const float* tau; int32_t num_classes; int32_t nq; bool tiles_ready; };
+
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
 int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
-             int init_keys = 0) {
-    // ny > 1 (hand-scheduled top-1 kernels only): ny consecutive query tiles of qb_tile queries in ONE launch
+             int init_keys = 0, const ClassPass* cp = nullptr) {
+    // ny > 1 (top-1 kernels and the class-minimum scan only): ny consecutive query tiles of qb_tile queries in ONE launch
     const int kk = g->dp4 * 4;
     float* qt = g->qt + (size_t)q0 * kk;
-    {
+    if (!(cp && cp->tiles_ready)) {
         const int64_t total = std::max<int64_t>((int64_t)kk * qb_tile * ny, init_keys);
         const int blocks = (int)((total + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, qb_tile * ny,
+        hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, cp ? cp->nq : qb_tile * ny,
                            g->d, g->dp4, qb_tile, qt, init_keys > 0 ? keys : nullptr, init_keys, g->range, next_serial(g));
     }
     const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g));
@@ -430,8 +437,13 @@ int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, in
     a.qt_stride = (int64_t)kk * qb_tile;
     a.range = g->range;
     a.serial = g->q_serial;
-    // algorithmic bytes of one launch: per pass the gallery range once, the query tile, the keys
-    const double bytes_alg = ny * ((double)a.n * (end - start) * 4.0 + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
+    if (cp) {
+        a.tau = cp->tau;
+        a.num_classes = cp->num_classes;
+        a.nq = cp->nq;
+    }
+    // algorithmic bytes of one launch: per pass the gallery range once (the class-minimum scan: and a label per row), the query tile, the keys
+    const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
     int rc;
     if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
     hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
@@ -782,6 +794,65 @@ int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t s
     list_threshold(c);
     if ((rc = list_append_scan(c))) return rc;
     return list_rerank_select(c, d_keys);
+}
+
+// ---- the K nearest distinct classes (fir_search_top_classes) -----------------------------------------------------------------
+// ConventionalTWDClassifier::recognize keeps the best row of every class (ImageTesting.cpp:118-122) and then the best classes
+// (:141-149); here that is one gallery scan whose epilogue lowers cmin[query][class] (k_scan, kEpiClassMin) and a select kernel.
+// kClassTableBytes: as many tiles of 8 queries share a launch (blockIdx.y) as keep the table within this budget -- 8 queries x
+// 100 000 classes are 6.4 MB, ten tiles of them 64 MB: scattered 8-byte minima land in the 256 MiB Infinity Cache rather than
+// in HBM -- but never fewer than one tile: num_classes may be as large as n, and the table is then 64 bytes per row.
+constexpr size_t kClassTableBytes = (size_t)64 << 20;
+constexpr int32_t kClassMax = 1 << 24;      // 1 GiB of table per tile of 8 queries: beyond it the call is refused, not attempted
+// Galleries of at least this many tiles take a bound from a row sample first: the scan over the first eighth of the tiles
+// leaves the minima of the classes met there; the K-th smallest of them is an upper bound
+// tau of the final K-th class minimum (a minimum over a subset of the rows), so in the remaining tiles a row above tau -- almost
+// every row -- cannot belong to an answer and never reaches the shuffles or the table. Fewer than K classes in the sample: tau
+// stays 100000 and nothing is filtered.
+constexpr int64_t kClassSampleFromTiles = 128;
+
+int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k,
+                    uint64_t* d_keys, int32_t* d_classes, hipStream_t st) {
+    if (g->n == 0) {                                             // no row: every slot unused (kKeyNone, class -1)
+        if (d_keys) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
+        if (d_classes) FIR_HIP(hipMemsetAsync(d_classes, 0xFF, (size_t)qb * k * sizeof(int32_t), st));
+        return FIR_OK;
+    }
+    const int tiles_q = (qb + 7) / 8;
+    const size_t tile_bytes = (size_t)8 * (size_t)num_classes * sizeof(uint64_t);
+    const int per_launch = (int)std::min<size_t>(std::min(tiles_q, g->max_tiles_per_launch), std::max<size_t>(1, kClassTableBytes / tile_bytes));
+    void *p_table = nullptr, *p_tau = nullptr;
+    int rc;
+    if ((rc = fir_gallery_scratch_(g, 17, tile_bytes * per_launch, &p_table))) return rc;
+    if ((rc = fir_gallery_scratch_(g, 18, (size_t)per_launch * 8 * sizeof(float), &p_tau))) return rc;
+    if ((rc = grow(g->qt, g->qt_cap, (size_t)tiles_q * 8 * g->dp4 * 4 + 64))) return rc;
+    uint64_t* table = (uint64_t*)p_table;
+    float* tau = (float*)p_tau;
+    const int64_t sample_tiles = g->tiles >= kClassSampleFromTiles ? g->tiles / 8 : 0;
+    auto restore = fir_on_exit([&] { g->tiles_limit = 0; g->tile_begin = 0; });
+    for (int q0 = 0; q0 < qb; q0 += 8 * per_launch) {
+        const int nq = std::min(qb - q0, 8 * per_launch), ny = (nq + 7) / 8;
+        // a fresh table for every launch group: nothing of an earlier group, call, num_classes or k is left to see
+        FIR_HIP(hipMemsetAsync(table, 0xFF, tile_bytes * ny, st));
+        ClassPass cp{nullptr, num_classes, nq, false};
+        if (sample_tiles > 0) {
+            g->tile_begin = 0;
+            g->tiles_limit = sample_tiles;
+            if ((rc = run_pass(g, st, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
+            hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, (uint64_t*)nullptr, (int32_t*)nullptr, tau);
+            cp.tau = tau;
+            cp.tiles_ready = true;
+            g->tile_begin = sample_tiles;
+            g->tiles_limit = g->tiles - sample_tiles;
+        }
+        if ((rc = run_pass(g, st, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
+        g->tiles_limit = 0;
+        g->tile_begin = 0;
+        hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, d_keys ? d_keys + (size_t)q0 * k : nullptr,
+                           d_classes ? d_classes + (size_t)q0 * k : nullptr, (float*)nullptr);
+        FIR_HIP(hipGetLastError());
+    }
+    return FIR_OK;
 }
 
 int range_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, float* d_out, hipStream_t st) {
@@ -1692,6 +1763,85 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     FIR_HIP(hipStreamSynchronize(g->stream));
     order.done();
     return fir_keys_unpack(keys.data(), qb * k, idx, dist);
+}
+
+namespace {
+int check_top_classes(const fir_gallery* g, const float* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, int32_t num_classes, int32_t k) {
+    if (!g || (qb > 0 && !queries)) return fail(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > 32) return fail(FIR_ERR_ARG, "k=%d outside [1,32]", k);
+    if (num_classes < 1 || num_classes > kClassMax) return fail(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
+    if (!g->cls && g->n > 0) return fail(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
+    return check_range(g, start_pos, end_pos);
+}
+}  // namespace
+
+int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes,
+                                    int32_t k, uint64_t* d_keys, int32_t* d_classes, void* stream) {
+    int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
+    if (rc) return rc;
+    if (qb > 0 && !d_keys && !d_classes) return fail(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
+    if (qb == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    return top_classes_dev(g, d_queries, qb, start_pos, end_pos, num_classes, k, d_keys, d_classes, st);
+}
+
+int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes, int32_t k,
+                           int32_t* class_out, int32_t* idx, float* dist) {
+    int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k);
+    if (rc) return rc;
+    if (qb == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);               // (a host-pointer call is a call on the handle's own stream)
+    if (order.rc) return order.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    const size_t slots = (size_t)qb * k;
+    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
+    if ((rc = grow(g->dkeys, g->dkeys_cap, slots))) return rc;
+    if ((rc = grow(g->didx, g->didx_cap, slots))) return rc;
+    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    if ((rc = top_classes_dev(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream))) return rc;
+    std::vector<uint64_t> keys(slots);
+    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->didx, slots * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    order.done();
+    return fir_keys_unpack(keys.data(), (int32_t)slots, idx, dist);
+}
+
+int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k, uint64_t* keys_out,
+                         int32_t* classes_out) {
+    if (parts < 0 || qb < 0 || k < 1) return fail(FIR_ERR_ARG, "bad merge shape parts=%d qb=%d k=%d", parts, qb, k);
+    if ((size_t)parts * qb > 0 && (!keys || !classes)) return fail(FIR_ERR_ARG, "NULL argument");
+    if (qb > 0 && (!keys_out || !classes_out)) return fail(FIR_ERR_ARG, "NULL argument");
+    std::vector<std::pair<uint64_t, int32_t>> all;
+    for (int32_t q = 0; q < qb; ++q) {
+        all.clear();
+        for (int32_t p = 0; p < parts; ++p)
+            for (int32_t r = 0; r < k; ++r) {
+                const size_t i = ((size_t)p * qb + q) * k + r;
+                if (keys[i] != kKeyNone) all.emplace_back(keys[i], classes[i]);
+            }
+        // ascending keys: a class's first entry is its smallest key, every later one of that class is dropped
+        std::sort(all.begin(), all.end());
+        int32_t used = 0;
+        for (size_t i = 0; i < all.size() && used < k; ++i) {
+            bool seen = false;
+            for (int32_t j = 0; j < used; ++j) seen = seen || classes_out[(size_t)q * k + j] == all[i].second;
+            if (seen) continue;
+            keys_out[(size_t)q * k + used] = all[i].first;
+            classes_out[(size_t)q * k + used] = all[i].second;
+            ++used;
+        }
+        for (; used < k; ++used) { keys_out[(size_t)q * k + used] = kKeyNone; classes_out[(size_t)q * k + used] = -1; }
+    }
+    return FIR_OK;
 }
 
 int fir_range_distances_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,

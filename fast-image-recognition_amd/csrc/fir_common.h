@@ -16,7 +16,8 @@ enum { kL2 = 0, kChi2 = 1, kKL = 2,
        kChi2Approx = 5,                      // kernel-internal: chi-square with a 1-ulp reciprocal, NOMINATES rows only (fir_capi.hip: topk_lists_dev)
        kChi2Harm = 6,                        // kernel-internal: chi-square as sum(l) + sum(r) - 4 sum 1/(1/l + 1/r): the scan adds up the harmonic terms, NOMINATES only
        kKLEnt = 7 };                         // kernel-internal: KL as ln2 (sum(l log2 l + l) + sum(r log2 r + r) - sum (l + r) log2 (l + r)): the scan adds up the last sum, NOMINATES only
-enum { kEpiTop1 = 0, kEpiTopK = 1, kEpiStore = 2, kEpiAppend = 3 };
+enum { kEpiTop1 = 0, kEpiTopK = 1, kEpiStore = 2, kEpiAppend = 3,
+       kEpiClassMin = 5 };                   // (4 is how fir_capi.hip's kernel table files k_scan_subranges)
 
 typedef const float __attribute__((address_space(4)))* sfloat_p;  // constant AS => s_load when uniform
 

@@ -59,7 +59,7 @@ extern "C" int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4); 
 
 // Device scratch owned by the gallery handle: `slot` in [0, 24), grown on demand, kept until the gallery is destroyed
 // (the per-call hipMalloc / hipFree pairs of the classifier entry points cost more than their kernels on small galleries).
-// Slots 0-7 and 16: fir_twd.hip, 8-11: fir_dem.hip, 12-15: fir_capi.hip.
+// Slots 0-7 and 16: fir_twd.hip, 8-11: fir_dem.hip, 12-15, 17 and 18: fir_capi.hip (17, 18: top_classes_dev); 19-23 are free.
 extern "C" int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out);
 // Per-handle call counters of the other translation units (slot 0: fir_twd.hip's fused classifier): returns the value before the increment.
 extern "C" uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot);

@@ -83,6 +83,9 @@ struct ScanArgs {
     const float* sq;      // ... sq[query] = the same for the queries of the call (indexed like tau)
     int32_t groups;       // k_scan, top-1 epilogue, > 1: the tiles form `groups` disjoint sets (tile index mod groups; a.waves is a multiple of it, so
     int64_t group_stride; // a wave stays inside one set) and set s reports into keys + s * group_stride: the K row samples of topk_lists_dev in ONE launch
+    const int32_t* cls;   // kEpiClassMin: class label of every row of this scan; keys = cmin[query][class], the smallest key of each class so far
+    int32_t num_classes;  // (pre-set to kKeyNone; rows labelled outside [0, num_classes) take no part); nq = live queries of the launch;
+                          // tau (may be NULL) = per query, the distance above which a row cannot be among the answer's classes
 };
 
 template <int QB, int METRIC, int U>
@@ -246,8 +249,8 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     }
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    // blockIdx.y = query tile (top-1 and append forms): several tiles of QB queries share one launch
-    const float* qsrc = a.qt + (EPI == kEpiTop1 || EPI == kEpiAppend ? (size_t)blockIdx.y * a.qt_stride : 0);
+    // blockIdx.y = query tile (top-1, append and class-minimum forms): several tiles of QB queries share one launch
+    const float* qsrc = a.qt + (EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin ? (size_t)blockIdx.y * a.qt_stride : 0);
     extern __shared__ __attribute__((aligned(16))) float lds_q[];
     if constexpr (LDSQ) {
         const int nf = a.dp4 * 4 * QB;
@@ -263,7 +266,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     const int c_hi = a.end >> 2;                  // one past the last whole chunk
     const float fcount = (float)(a.end - a.start);  // db_features.cpp:40 divides by (end_pos-start_pos)
 
-    float best_d[EPI == kEpiTop1 || EPI == kEpiAppend ? QB : 1];      // kEpiAppend: the thresholds tau
+    float best_d[EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin ? QB : 1];      // kEpiAppend, kEpiClassMin: the thresholds tau
     int32_t best_i[EPI == kEpiTop1 ? QB : 1];
     float kd[EPI == kEpiTopK ? QB : 1][EPI == kEpiTopK ? KMAX : 1];
     int32_t ki[EPI == kEpiTopK ? QB : 1][EPI == kEpiTopK ? KMAX : 1];
@@ -274,6 +277,10 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     if constexpr (EPI == kEpiAppend) {
 #pragma unroll
         for (int q = 0; q < QB; ++q) best_d[q] = a.tau[(size_t)blockIdx.y * QB + q];
+    }
+    if constexpr (EPI == kEpiClassMin) {
+#pragma unroll
+        for (int q = 0; q < QB; ++q) best_d[q] = a.tau ? a.tau[(size_t)blockIdx.y * QB + q] : kNotFound;
     }
     if constexpr (EPI == kEpiTopK) {
 #pragma unroll
@@ -311,7 +318,49 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
         }
 
         const int64_t row = (int64_t)t * kTileRows + lane;
-        if (row < a.n) {
+        if constexpr (EPI == kEpiClassMin) {
+            // cmin[query][class] = min(key of every row of the class): an integer minimum of packed keys, so whatever the arrival
+            // order the table ends with the first-minimum row of each class (db_features.cpp:329-332 within the class).
+            // Every lane takes part in the shuffles: rows past n and rows labelled outside [0, num_classes) carry no key.
+            const int32_t lab = row < a.n ? a.cls[row] : -1;                  // one coalesced load per tile
+            const bool counted = (uint32_t)lab < (uint32_t)a.num_classes;
+            // Segmented minimum: same bit j = the lane 2^j below holds the same label. Joining two lanes of one label is right
+            // whatever lies between them, and inside a run of equal labels the steps are the inclusive scan's, so the last lane
+            // of every run ends with (at least) the run's minimum: it alone goes to memory. Class-major galleries: one or two
+            // runs per tile instead of 64 rows.
+            // (the label shuffles wait for the first query of the tile that has a live key: behind a bound most tiles have none)
+            uint32_t same = 0;
+            bool last = false, have_runs = false;
+            const int nq_live = a.nq - (int)blockIdx.y * QB;                  // queries past it are the tile's zero padding
+#pragma unroll
+            for (int q = 0; q < QB; ++q) {
+                if (q >= nq_live) break;                                      // wave-uniform
+                const float dist = acc[q] / fcount;                           // db_features.cpp:40
+                // '<= tau', not '<': a row at the bound's own distance with a lower index still wins its class
+                uint64_t key = counted && dist < kNotFound && dist <= best_d[q] ? key_pack(dist, (uint32_t)(row + a.row_offset)) : kKeyNone;
+                if (__ballot(key != kKeyNone) == 0) continue;                 // wave-uniform: behind a bound from a row sample, most tiles
+                if (!have_runs) {                                             // wave-uniform
+#pragma unroll
+                    for (int j = 0; j < 6; ++j)
+                        if (__shfl_up(lab, 1u << j, 64) == lab && lane >= (1 << j)) same |= 1u << j;
+                    last = __shfl_down(lab, 1u, 64) != lab || lane == 63;
+                    have_runs = true;
+                }
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    const uint64_t o = __shfl_up((unsigned long long)key, 1u << j, 64);
+                    if (((same >> j) & 1u) && o < key) key = o;
+                }
+                if (last && key != kKeyNone) {
+                    // a key only lands in a lane whose label is the key's own row's: lab is inside [0, num_classes) here.
+                    // Most keys lose against what the table holds: read first (a stale value is only ever larger: it costs an
+                    // atomic, never an answer), contend only to win
+                    uint64_t* slot = a.keys + ((size_t)blockIdx.y * QB + q) * (size_t)a.num_classes + lab;
+                    const uint64_t cur = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (key < cur) atomicMin((unsigned long long*)slot, (unsigned long long)key);
+                }
+            }
+        } else if (row < a.n) {
 #pragma unroll
             for (int q = 0; q < QB; ++q) {
                 float dist = acc[q] / fcount;                            // db_features.cpp:40
@@ -889,6 +938,83 @@ __global__ void __launch_bounds__(kBlock) k_topk_merge(const uint64_t* part, int
         prev = m;
         first = false;
     }
+}
+
+// The K smallest entries of cmin[q][0 .. C) (k_scan's class-minimum epilogue), ascending: keys_out[q][K] (kKeyNone past the
+// classes present) and cls_out[q][K] (-1 there), either may be NULL. One block per query. The entry's position is its class.
+// tau != NULL: tau[q] = the distance of the K-th pick, 100000 when fewer than K classes are present: taken over a row sample it
+// bounds the K-th class minimum of the whole gallery from above.
+// Two reads of the row instead of K: every thread takes the minimum of its stride of entries; T = the K-th smallest of those 256
+// minima is an entry with at least K entries at or below it, so the K smallest of the row are all <= T. They -- K of them and a
+// few more -- are gathered into LDS and picked there by K rounds of "smallest key greater than the previous pick" (keys carry their
+// row index, so they are unique and a round removes exactly one). Fewer than K strides with an entry: T stays kKeyNone and every
+// entry is gathered. More than kClassListCap gathered (many entries, all in a few strides): the K rounds read the row itself.
+constexpr int kClassListCap = 1024;
+__global__ void __launch_bounds__(kBlock) k_class_select(const uint64_t* __restrict__ cmin, int C, int K, uint64_t* __restrict__ keys_out,
+                                                          int32_t* __restrict__ cls_out, float* __restrict__ tau) {
+    __shared__ uint64_t red[kBlock / 64];
+    __shared__ uint64_t lkey[kClassListCap];
+    __shared__ int32_t lcls[kClassListCap];
+    __shared__ int lcount;
+    const int q = blockIdx.x;
+    const uint64_t* t = cmin + (size_t)q * C;
+    auto block_min = [&](uint64_t v) {
+        v = wave_min_u64(v);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        uint64_t m = red[0];
+#pragma unroll
+        for (int i = 1; i < kBlock / 64; ++i) m = red[i] < m ? red[i] : m;
+        __syncthreads();
+        return m;
+    };
+    uint64_t mine = kKeyNone;
+    for (int i = threadIdx.x; i < C; i += kBlock) {
+        const uint64_t v = t[i];
+        mine = v < mine ? v : mine;
+    }
+    uint64_t T = 0;
+    for (int r = 0; r < K && T != kKeyNone; ++r) T = block_min(r == 0 || mine > T ? mine : kKeyNone);
+    if (threadIdx.x == 0) lcount = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < C; i += kBlock) {
+        const uint64_t v = t[i];
+        if (v != kKeyNone && v <= T) {
+            const int slot = atomicAdd(&lcount, 1);
+            if (slot < kClassListCap) { lkey[slot] = v; lcls[slot] = i; }
+        }
+    }
+    __syncthreads();
+    const int cnt = lcount;
+    uint64_t prev = 0;
+    int r = 0;
+    for (; r < K; ++r) {
+        uint64_t cand = kKeyNone;
+        int cc = -1;
+        if (cnt <= kClassListCap) {
+            for (int i = threadIdx.x; i < cnt; i += kBlock) {
+                const uint64_t v = lkey[i];
+                if ((r == 0 || v > prev) && v < cand) { cand = v; cc = lcls[i]; }
+            }
+        } else {
+            for (int i = threadIdx.x; i < C; i += kBlock) {
+                const uint64_t v = t[i];
+                if ((r == 0 || v > prev) && v < cand) { cand = v; cc = i; }
+            }
+        }
+        const uint64_t m = block_min(cand);
+        if (m == kKeyNone) break;                                   // (the whole block: m is the block's)
+        if (cand == m) {                                            // one thread: keys are unique
+            if (keys_out) keys_out[(size_t)q * K + r] = m;
+            if (cls_out) cls_out[(size_t)q * K + r] = cc;
+        }
+        prev = m;
+    }
+    for (int i = r + (int)threadIdx.x; i < K; i += kBlock) {
+        if (keys_out) keys_out[(size_t)q * K + i] = kKeyNone;
+        if (cls_out) cls_out[(size_t)q * K + i] = -1;
+    }
+    if (tau && threadIdx.x == 0) tau[q] = r == K ? f32_from_orderable((uint32_t)(prev >> 32)) : kNotFound;
 }
 
 // Thresholds of the append form. gkeys[i][q] = nearest row of query q inside the i-th of K DISJOINT row groups of a

@@ -135,6 +135,32 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
 int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                              int32_t k, uint64_t* d_keys /* [qb*k] ascending */, void* stream);
 
+/* ---- K nearest distinct classes ---------------------------------------------------------------
+ * The k nearest DISTINCT classes of each query: for every class c in [0, num_classes) its nearest row
+ * (first minimum in row order, the rule of db_features.cpp:329-332) over features [start_pos, end_pos)
+ * (end_pos = 0: d), then the k classes whose nearest rows are nearest, ascending by (distance, row index):
+ * the best row of every class and then the best classes of ConventionalTWDClassifier::recognize
+ * (ImageTesting.cpp:118-122, 141-149) for any metric, range and k -- rank-k candidates, not k rows of one class.
+ * 1 <= k <= 32, 1 <= num_classes <= 16777216 (else FIR_ERR_ARG). class_out / idx / dist are [qb*k], any may be NULL; unused slots: class -1, idx -1, dist 100000.
+ * The gallery needs class labels (else FIR_ERR_STATE). Rows labelled outside [0, num_classes) take no part
+ * (as in fir_twd_conventional). A row qualifies only if `dist < 100000.0f` is true (so NaN distances never do).
+ * One exact gallery scan per 8 queries (the arithmetic and distance bits of fir_search_top1's scan; no matrix-core
+ * form); device scratch: 64 bytes per class and 8 queries, and the select step reads a query's 8 bytes per class twice with one
+ * workgroup: with num_classes in the millions that read, not the scan, sets the time of a call of few queries. */
+int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                           int32_t num_classes, int32_t k, int32_t* class_out, int32_t* idx, float* dist);
+/* Device-resident, asynchronous on `stream`, never synchronises once its scratch is large enough.
+ * d_keys[qb*k]: packed keys of the winning rows (index + row offset), ascending, FIR_KEY_NONE for unused slots;
+ * d_classes[qb*k]: their classes, -1 for unused slots. One of the two may be NULL. */
+int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                    int32_t num_classes, int32_t k, uint64_t* d_keys, int32_t* d_classes, void* stream);
+/* Host-side merge of `parts` such lists (keys[parts][qb][k], classes likewise: row shards made with
+ * fir_gallery_set_row_offset, or ranks): per class the smallest key, then the k smallest. Pure integer work, no device.
+ * Exact: a class among the global k best is among the k best of the shard that holds its nearest row -- every class
+ * ahead of it in that shard is ahead of it globally too. */
+int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k,
+                         uint64_t* keys_out, int32_t* classes_out);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
