@@ -22,22 +22,7 @@ using namespace fir;
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define FIR_HIP(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,     \
-                                          "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+thread_local char g_err[512] = "";     // what fir_last_error() returns; written by fir_fail_ and fir_set_last_error_
 
 constexpr int kU = 8;        // float4 chunks per lane per load group (8 KiB per wave in flight per group)
 constexpr int kUDeep = 16;   // ... of the few-tiles form of a one-query tile
@@ -340,7 +325,7 @@ void note_dispatch(fir_gallery* g, const void* fn, const char* name, int launche
 int check_range(const fir_gallery* g, int32_t& start, int32_t& end) {
     if (end == 0) end = g->d;   // db_features.cpp:320-321
     if (start < 0 || end > g->d || start >= end)
-        return fail(FIR_ERR_ARG, "feature range [%d,%d) not inside [0,%d)", start, end, g->d);
+        return fir_fail_(FIR_ERR_ARG, "feature range [%d,%d) not inside [0,%d)", start, end, g->d);
     return FIR_OK;
 }
 
@@ -412,7 +397,7 @@ int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, in
                            g->d, g->dp4, qb_tile, qt, init_keys > 0 ? keys : nullptr, init_keys, g->range, next_serial(g));
     }
     const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g));
-    if (!sk.fn) return fail(FIR_ERR_ARG, "no kernel for qb=%d metric=%d", qb_tile, g->metric);
+    if (!sk.fn) return fir_fail_(FIR_ERR_ARG, "no kernel for qb=%d metric=%d", qb_tile, g->metric);
     if (sk.lds_bytes > 64 * 1024) {   // more than the default dynamic LDS limit: opt in once per kernel
         bool known = false;
         for (const auto& e : g->occ) known = known || (e.fn == (const void*)sk.fn && e.lds == sk.lds_bytes);
@@ -886,7 +871,7 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
         const int live = std::min(8, qb - q0);
         const int qbt = live <= 1 ? 1 : live <= 2 ? 2 : live <= 4 ? 4 : 8;   // kernel tile: the next power of two (extra queries are zero padding)
         const scan_fn fn = select_scan(kEpiSubranges, qbt, g->metric, whole_chunks(start, end), g->dp4, false).fn;
-        if (!fn) return fail(FIR_ERR_ARG, "no sub-range kernel for qb=%d metric=%d", qbt, g->metric);
+        if (!fn) return fir_fail_(FIR_ERR_ARG, "no sub-range kernel for qb=%d metric=%d", qbt, g->metric);
         hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * qbt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, qbt, g->qt, (uint64_t*)nullptr, 0);
         const int max_waves = max_waves_for(g, fn, 0);
@@ -918,25 +903,25 @@ hipError_t device_count(int* cnt) {
 
 int set_device(int device) {
     int cnt = 0;
-    if (device_count(&cnt) != hipSuccess || cnt <= 0) return fail(FIR_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fail(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
+    if (device_count(&cnt) != hipSuccess || cnt <= 0) return fir_fail_(FIR_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
     return fir_runtime_init_(device);
 }
 
 int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gallery** out) {
-    if (!out) return fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (n < 0 || d <= 0) return fail(FIR_ERR_ARG, "bad gallery shape n=%lld d=%d", (long long)n, d);
-    if (n >= ((int64_t)1 << 31) - 64) return fail(FIR_ERR_ARG, "n=%lld does not fit 32-bit row indices", (long long)n);
-    if (metric < 0 || metric > 2) return fail(FIR_ERR_ARG, "bad metric %d", metric);
+    if (n < 0 || d <= 0) return fir_fail_(FIR_ERR_ARG, "bad gallery shape n=%lld d=%d", (long long)n, d);
+    if (n >= ((int64_t)1 << 31) - 64) return fir_fail_(FIR_ERR_ARG, "n=%lld does not fit 32-bit row indices", (long long)n);
+    if (metric < 0 || metric > 2) return fir_fail_(FIR_ERR_ARG, "bad metric %d", metric);
     int rc = set_device(device);
     if (rc) return rc;
     hipDeviceProp_t prop;
     FIR_HIP(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     fir_gallery* g = new (std::nothrow) fir_gallery();
-    if (!g) return fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!g) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     g->device = device;
     g->cus = prop.multiProcessorCount;
     g->n = n;
@@ -947,12 +932,12 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
     g->max_waves = g->cus * 8 * (kBlock / 64);
     hipError_t e;
     e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete g; return fail(FIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete g; return fir_fail_(FIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     e = hipEventCreateWithFlags(&g->last_done, hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipStreamDestroy(g->stream);
         delete g;
-        return fail(FIR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
+        return fir_fail_(FIR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
     }
     const size_t f4 = (size_t)std::max<int64_t>(g->tiles, 1) * g->dp4 * 64;
     e = hipMalloc((void**)&g->gal4, f4 * sizeof(float4));
@@ -960,7 +945,7 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
         (void)hipEventDestroy(g->last_done);
         (void)hipStreamDestroy(g->stream);
         delete g;
-        return fail(FIR_ERR_NOMEM, "hipMalloc of %zu gallery bytes: %s", f4 * sizeof(float4), hipGetErrorString(e));
+        return fir_fail_(FIR_ERR_NOMEM, "hipMalloc of %zu gallery bytes: %s", f4 * sizeof(float4), hipGetErrorString(e));
     }
     e = hipMalloc((void**)&g->range, 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(g->range, 0, 2 * sizeof(int32_t));
@@ -969,7 +954,7 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
         (void)hipEventDestroy(g->last_done);
         (void)hipStreamDestroy(g->stream);
         delete g;
-        return fail(FIR_ERR_NOMEM, "hipMalloc of the range flags: %s", hipGetErrorString(e));
+        return fir_fail_(FIR_ERR_NOMEM, "hipMalloc of the range flags: %s", hipGetErrorString(e));
     }
     *out = g;
     return FIR_OK;
@@ -980,7 +965,7 @@ int retile_slab(fir_gallery* g, const float* d_rows, int64_t slab_rows, int64_t 
     const int64_t total = slab_tiles * g->dp4 * 64;
     if (total == 0) return FIR_OK;
     const int64_t blocks = (total + kBlock - 1) / kBlock;
-    if (blocks > 0x7FFFFFFF) return fail(FIR_ERR_ARG, "slab too large");
+    if (blocks > 0x7FFFFFFF) return fir_fail_(FIR_ERR_ARG, "slab too large");
     hipLaunchKernelGGL(k_retile, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, slab_rows, row0, g->n, g->d, g->dp4, g->gal4,
                        g->range);
     FIR_HIP(hipGetLastError());
@@ -992,6 +977,13 @@ int retile_slab(fir_gallery* g, const float* d_rows, int64_t slab_rows, int64_t 
 extern "C" {
 
 const char* fir_last_error(void) { return g_err; }
+int fir_fail_(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
 int fir_gallery_view_(fir_gallery* g, fir_gallery_view* out) {
     if (!g || !out) return FIR_ERR_ARG;
     out->device = g->device; out->cus = g->cus; out->n = g->n; out->d = g->d; out->metric = g->metric; out->row_offset = g->row_offset;
@@ -1002,7 +994,7 @@ int fir_gallery_call_begin_(fir_gallery* g, hipStream_t st) {
     if (!g || g->call_depth++ > 0) return FIR_OK;
     if (g->last_stream && g->last_stream != st) {          // (same stream: stream order already does it)
         const hipError_t e = hipStreamWaitEvent(st, g->last_done, 0);
-        if (e != hipSuccess) return fail(FIR_ERR_HIP, "hipStreamWaitEvent (call order): %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fir_fail_(FIR_ERR_HIP, "hipStreamWaitEvent (call order): %s", hipGetErrorString(e));
     }
     return FIR_OK;
 }
@@ -1041,7 +1033,7 @@ int fir_runtime_init_(int device) {
         if (st) (void)hipStreamDestroy(st);
         if (p) (void)hipFree(p);
         setstate(caller);                                        // ... and the caller's rand() stream continues where it was
-        if (e != hipSuccess) return fail(FIR_ERR_HIP, "device %d start-up failed: %s", device, hipGetErrorString(e));
+        if (e != hipSuccess) return fir_fail_(FIR_ERR_HIP, "device %d start-up failed: %s", device, hipGetErrorString(e));
         touched[device] = true;
         return FIR_OK;
     }
@@ -1049,7 +1041,7 @@ int fir_runtime_init_(int device) {
     return FIR_OK;
 }
 int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out) {
-    if (!g || !out || slot < 0 || slot >= 24) return fail(FIR_ERR_ARG, "bad scratch request");
+    if (!g || !out || slot < 0 || slot >= 24) return fir_fail_(FIR_ERR_ARG, "bad scratch request");
     if (bytes > g->scratch_cap[slot]) {
         if (g->scratch[slot]) FIR_HIP(hipFree(g->scratch[slot]));
         g->scratch[slot] = nullptr;
@@ -1064,10 +1056,10 @@ int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out) {
 }
 int fir_subrange_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t step, float* d_out,
                                 void* stream) {
-    if (!g || !d_queries || !d_out) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return fail(FIR_ERR_ARG, "qb=%d must be positive", qb);
+    if (!g || !d_queries || !d_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "qb=%d must be positive", qb);
     if (step <= 0 || start < 0 || end > g->d || start >= end || (end - start) % step != 0)
-        return fail(FIR_ERR_ARG, "sub-ranges of %d features do not tile [%d,%d) inside [0,%d)", step, start, end, g->d);
+        return fir_fail_(FIR_ERR_ARG, "sub-ranges of %d features do not tile [%d,%d) inside [0,%d)", step, start, end, g->d);
     if (g->n == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
     const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -1076,9 +1068,9 @@ int fir_subrange_distances_dev_(fir_gallery* g, const float* d_queries, int32_t 
     return subranges_dev(g, d_queries, qb, start, end, step, d_out, st);
 }
 int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t split, int32_t end, float* d_out, void* stream) {
-    if (!g || !d_queries || !d_out) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return fail(FIR_ERR_ARG, "qb=%d must be positive", qb);
-    if (split <= 0 || split >= end || end > g->d) return fail(FIR_ERR_ARG, "split %d / end %d outside (0,%d]", split, end, g->d);
+    if (!g || !d_queries || !d_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "qb=%d must be positive", qb);
+    if (split <= 0 || split >= end || end > g->d) return fir_fail_(FIR_ERR_ARG, "split %d / end %d outside (0,%d]", split, end, g->d);
     if (g->n == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
     hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -1095,7 +1087,6 @@ int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4) {
     *dp4 = g->dp4;
     return FIR_OK;
 }
-// internal: lets the library's other translation units (fir_cls.hip) report through fir_last_error()
 void fir_set_last_error_(const char* msg) {
     strncpy(g_err, msg ? msg : "", sizeof(g_err) - 1);
     g_err[sizeof(g_err) - 1] = 0;
@@ -1111,7 +1102,7 @@ int fir_device_count(void) {
 int fir_device_info(int32_t device, char* name, int32_t cap, int32_t* cus, int64_t* hbm_bytes) {
     int cnt = 0;
     if (device_count(&cnt) != hipSuccess || device < 0 || device >= cnt)
-        return fail(FIR_ERR_NODEVICE, "device %d not available", device);
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d not available", device);
     hipDeviceProp_t prop;
     FIR_HIP(hipGetDeviceProperties(&prop, device));
     if (name && cap > 0) { strncpy(name, prop.gcnArchName, (size_t)cap - 1); name[cap - 1] = 0; }
@@ -1122,19 +1113,19 @@ int fir_device_info(int32_t device, char* name, int32_t cap, int32_t* cus, int64
 
 int fir_device_peak_hbm_gbs(int32_t device, double* gbs) {
     int cnt = 0;
-    if (!gbs) return fail(FIR_ERR_ARG, "gbs is NULL");
+    if (!gbs) return fir_fail_(FIR_ERR_ARG, "gbs is NULL");
     if (device_count(&cnt) != hipSuccess || device < 0 || device >= cnt)
-        return fail(FIR_ERR_NODEVICE, "device %d not available", device);
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d not available", device);
     hipDeviceProp_t prop;
     FIR_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(FIR_ERR_NODEVICE, "device %d is %s, not gfx950", device, prop.gcnArchName);
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s, not gfx950", device, prop.gcnArchName);
     *gbs = 8000.0;   // MI350X / MI355X: 8 stacks of HBM3E, 8 TB/s (the runtime's clock x bus-width fields do not give this)
     return FIR_OK;
 }
 
 int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* class_no, int32_t metric, int32_t device,
                        fir_gallery** out) {
-    if (n > 0 && !rows) return fail(FIR_ERR_ARG, "rows is NULL");
+    if (n > 0 && !rows) return fir_fail_(FIR_ERR_ARG, "rows is NULL");
     fir_gallery* g = nullptr;
     int rc = gallery_alloc(n, d, metric, device, &g);
     if (rc) return rc;
@@ -1143,22 +1134,22 @@ int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* c
     slab = std::min<int64_t>(slab, std::max<int64_t>(g->tiles, 1) * kTileRows);
     float* stage = nullptr;
     hipError_t e = hipMalloc((void**)&stage, (size_t)slab * d * sizeof(float));
-    if (e != hipSuccess) { fir_gallery_destroy(g); return fail(FIR_ERR_NOMEM, "staging hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { fir_gallery_destroy(g); return fir_fail_(FIR_ERR_NOMEM, "staging hipMalloc: %s", hipGetErrorString(e)); }
     for (int64_t r0 = 0; r0 < std::max<int64_t>(g->tiles, 1) * kTileRows && rc == FIR_OK; r0 += slab) {
         const int64_t have = std::max<int64_t>(0, std::min<int64_t>(slab, n - r0));
         if (have > 0) {
             e = hipMemcpyAsync(stage, rows + r0 * d, (size_t)have * d * sizeof(float), hipMemcpyHostToDevice, g->stream);
-            if (e != hipSuccess) { rc = fail(FIR_ERR_HIP, "gallery upload: %s", hipGetErrorString(e)); break; }
+            if (e != hipSuccess) { rc = fir_fail_(FIR_ERR_HIP, "gallery upload: %s", hipGetErrorString(e)); break; }
         }
         if (have > 0) rc = retile_slab(g, stage, have, r0, g->stream);
         e = hipStreamSynchronize(g->stream);   // the staging buffer is reused by the next slab
-        if (e != hipSuccess && rc == FIR_OK) rc = fail(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
+        if (e != hipSuccess && rc == FIR_OK) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
     }
     (void)hipFree(stage);
     if (rc == FIR_OK && class_no && n > 0) {
         e = hipMalloc((void**)&g->cls, (size_t)n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpy(g->cls, class_no, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(FIR_ERR_HIP, "class upload: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class upload: %s", hipGetErrorString(e));
     }
     if (rc) { fir_gallery_destroy(g); return rc; }
     { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
@@ -1168,7 +1159,7 @@ int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* c
 
 int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int32_t* d_class_no, int32_t metric,
                            int32_t device, void* stream, fir_gallery** out) {
-    if (n > 0 && !d_rows) return fail(FIR_ERR_ARG, "d_rows is NULL");
+    if (n > 0 && !d_rows) return fir_fail_(FIR_ERR_ARG, "d_rows is NULL");
     fir_gallery* g = nullptr;
     int rc = gallery_alloc(n, d, metric, device, &g);
     if (rc) return rc;
@@ -1182,11 +1173,11 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
     if (rc == FIR_OK && d_class_no && n > 0) {
         hipError_t e = hipMalloc((void**)&g->cls, (size_t)n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpyAsync(g->cls, d_class_no, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) rc = fail(FIR_ERR_HIP, "class copy: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class copy: %s", hipGetErrorString(e));
     }
     if (rc == FIR_OK) {
         hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
     }
     if (rc) { fir_gallery_destroy(g); return rc; }
     { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
@@ -1213,7 +1204,7 @@ int fir_gallery_destroy(fir_gallery* g) {
 }
 
 int fir_gallery_info(const fir_gallery* g, int64_t* n, int32_t* d, int32_t* metric, int32_t* device) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     if (n) *n = g->n;
     if (d) *d = g->d;
     if (metric) *metric = g->metric;
@@ -1222,14 +1213,14 @@ int fir_gallery_info(const fir_gallery* g, int64_t* n, int32_t* d, int32_t* metr
 }
 
 int fir_gallery_set_metric(fir_gallery* g, int32_t metric) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
-    if (metric < 0 || metric > 2) return fail(FIR_ERR_ARG, "bad metric %d", metric);
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
+    if (metric < 0 || metric > 2) return fir_fail_(FIR_ERR_ARG, "bad metric %d", metric);
     g->metric = metric;
     return FIR_OK;
 }
 
 int fir_gallery_set_large_batch_mfma(fir_gallery* g, int32_t min_queries) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     g->large_batch_min = min_queries < 0 ? -1 : min_queries;
     g->gemm_failed = false;
     if (min_queries == 0 && g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
@@ -1238,7 +1229,7 @@ int fir_gallery_set_large_batch_mfma(fir_gallery* g, int32_t min_queries) {
 }
 
 int fir_gallery_mfma_stats_ex(fir_gallery* g, int64_t out[3]) {
-    if (!g || !out) return fail(FIR_ERR_ARG, "NULL argument");
+    if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     int64_t o[3];
     out[0] = out[1] = out[2] = 0;
     if (g->gemm && fir_gemm_stats_ex(g->gemm, o) == FIR_OK) { out[0] += o[0]; out[1] += o[1]; out[2] += o[2]; }
@@ -1249,7 +1240,7 @@ int fir_gallery_mfma_stats_ex(fir_gallery* g, int64_t out[3]) {
 }
 
 int fir_gallery_mfma_uncertified_notes(fir_gallery* g, float out[32], int32_t* count) {
-    if (!g || !out || !count) return fail(FIR_ERR_ARG, "NULL argument");
+    if (!g || !out || !count) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     *count = 0;
     if (!g->gemm) return FIR_OK;
     return fir_gemm_uncertified_notes(g->gemm, out, count);
@@ -1265,7 +1256,7 @@ int fir_gallery_mfma_stats(fir_gallery* g, int64_t* passes, int64_t* fallback_qu
 }
 
 int fir_gallery_memory_bytes(fir_gallery* g, int64_t* tiled, int64_t* fp16_fragments, int64_t* rowmajor_shadow, int64_t* scratch) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     int64_t fr = 0, rm = 0, sc = 0, a = 0, b = 0, c = 0;
     if (g->gemm) { fir_gemm_memory_bytes_(g->gemm, &a, &b, &c); fr += a; rm += b; sc += c; }
     for (auto& ps : g->gemm_prefix)
@@ -1282,8 +1273,8 @@ int fir_gallery_memory_bytes(fir_gallery* g, int64_t* tiled, int64_t* fp16_fragm
 }
 
 int fir_gallery_set_shadow_copies(fir_gallery* g, int32_t mode) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
-    if (mode != FIR_SHADOW_NONE && mode != FIR_SHADOW_FP16 && mode != FIR_SHADOW_ALL) return fail(FIR_ERR_ARG, "shadow mode %d", mode);
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
+    if (mode != FIR_SHADOW_NONE && mode != FIR_SHADOW_FP16 && mode != FIR_SHADOW_ALL) return fir_fail_(FIR_ERR_ARG, "shadow mode %d", mode);
     if (mode != g->shadow_mode) {
         if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
         for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
@@ -1294,9 +1285,9 @@ int fir_gallery_set_shadow_copies(fir_gallery* g, int32_t mode) {
 }
 
 int fir_gallery_set_row_offset(fir_gallery* g, int64_t first_global_row) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     if (first_global_row < 0 || first_global_row + g->n >= ((int64_t)1 << 31))
-        return fail(FIR_ERR_ARG, "row offset %lld + n does not fit 32-bit indices", (long long)first_global_row);
+        return fir_fail_(FIR_ERR_ARG, "row offset %lld + n does not fit 32-bit indices", (long long)first_global_row);
     g->row_offset = first_global_row;
     if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }   // it caches the offset; rebuilt on next use
     for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
@@ -1305,9 +1296,9 @@ int fir_gallery_set_row_offset(fir_gallery* g, int64_t first_global_row) {
 
 int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_t start_pos, int32_t end_pos,
                          int32_t metric, int32_t device, float* out) {
-    if (!lhs || !rhs || !out) return fail(FIR_ERR_ARG, "NULL argument");
-    if (start_pos < 0 || end_pos > len || start_pos >= end_pos) return fail(FIR_ERR_ARG, "bad range [%d,%d) of %d", start_pos, end_pos, len);
-    if (metric < 0 || metric > 2) return fail(FIR_ERR_ARG, "bad metric %d", metric);
+    if (!lhs || !rhs || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (start_pos < 0 || end_pos > len || start_pos >= end_pos) return fir_fail_(FIR_ERR_ARG, "bad range [%d,%d) of %d", start_pos, end_pos, len);
+    if (metric < 0 || metric > 2) return fir_fail_(FIR_ERR_ARG, "bad metric %d", metric);
     int rc = set_device(device);
     if (rc) return rc;
     float* buf = nullptr;
@@ -1322,7 +1313,7 @@ int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_
     }
     if (e == hipSuccess) e = hipMemcpy(out, buf + 2 * len, sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(buf);
-    if (e != hipSuccess) return fail(FIR_ERR_HIP, "pair distance: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fir_fail_(FIR_ERR_HIP, "pair distance: %s", hipGetErrorString(e));
     return FIR_OK;
 }
 
@@ -1409,9 +1400,9 @@ int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
 }  // namespace
 
 int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return qb < 0 ? fail(FIR_ERR_ARG, "qb < 0") : FIR_OK;
-    if (k < 1 || k > kKMax) return fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb <= 0) return qb < 0 ? fir_fail_(FIR_ERR_ARG, "qb < 0") : FIR_OK;
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     int32_t start_pos = 0;
     const int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1427,8 +1418,8 @@ int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int3
 
 int fir_search_top1_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                              uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
+    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1446,8 +1437,8 @@ int fir_search_top1_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb,
 // The exact streaming scan, whatever the batch size (fir_gemm.hip sends its uncertified queries here).
 int fir_search_top1_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, uint64_t* d_keys,
                                     void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return qb < 0 ? fail(FIR_ERR_ARG, "qb < 0") : FIR_OK;
+    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb <= 0) return qb < 0 ? fir_fail_(FIR_ERR_ARG, "qb < 0") : FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
     FIR_HIP(hipSetDevice(g->device));
@@ -1511,8 +1502,8 @@ extern "C" const char* fir_knob_(const char* name) {
 }
 
 int fir_gallery_last_dispatch(fir_gallery* g, fir_dispatch_info* out) {
-    if (!g || !out) return fail(FIR_ERR_ARG, "NULL argument");
-    if (out->struct_bytes < 8 || out->struct_bytes > (int32_t)sizeof(fir_dispatch_info)) return fail(FIR_ERR_ARG, "fir_dispatch_info.struct_bytes = %d", out->struct_bytes);
+    if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (out->struct_bytes < 8 || out->struct_bytes > (int32_t)sizeof(fir_dispatch_info)) return fir_fail_(FIR_ERR_ARG, "fir_dispatch_info.struct_bytes = %d", out->struct_bytes);
     const int32_t nb = out->struct_bytes;
     fir_dispatch_info tmp = g->last;
     tmp.warmup_calls_left = g->warm_left;
@@ -1526,7 +1517,7 @@ namespace {
 constexpr size_t kPinQueryBytes = 512 * 1024;    // host-pointer calls up to this many query bytes take the pinned path (a 64 x 1536 TWD batch fits)
 constexpr size_t kPinKeys = 4096;                // and up to this many result keys
 // ticket != 0 (single-block launches only): after the keys, host_keys[n] <- ticket -- the host spins on that word instead of
-// synchronising the stream (wait_ticket)
+// synchronising the stream (fir_wait_ticket_)
 __global__ void __launch_bounds__(kBlock) k_publish_keys(const uint64_t* __restrict__ keys, int n, uint64_t* __restrict__ host_keys,
                                                          uint64_t ticket) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -1536,19 +1527,6 @@ __global__ void __launch_bounds__(kBlock) k_publish_keys(const uint64_t* __restr
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(host_keys + n, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-}
-// Spin (2 ms at most, then the stream synchronisation) until the kernels queued on the handle's stream have written
-// `ticket` to the pinned word: cheaper than hipStreamSynchronize for calls that take tens of microseconds.
-int wait_ticket(fir_gallery* g, volatile uint64_t* flag, uint64_t ticket) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket; ++spins) {
-        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-            FIR_HIP(hipStreamSynchronize(g->stream));       // a long or failed launch: let the runtime report it
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket) return fail(FIR_ERR_HIP, "the result ticket was not published");
-            break;
-        }
-    }
-    return FIR_OK;
 }
 // One L2 query against a gallery of few tiles -- the reference's own call pattern, recognize() per test image against
 // ~3 000 rows. Such a call is mostly fixed cost (three launches and a stream synchronisation next to ~20 us of kernels),
@@ -1584,7 +1562,7 @@ int top1_one_query(fir_gallery* g, const float* pinned_query, int32_t start, int
     a.ticket = ++g->one_ticket;
     hipLaunchKernelGGL(fn, dim3(waves / 4, 1), dim3(kBlock), lds_bytes, g->stream, a);
     const hipError_t le = hipGetLastError();
-    if (le == hipSuccess && wait_ticket(g, pinned_key + 1, a.ticket) == FIR_OK) return FIR_OK;
+    if (le == hipSuccess && fir_wait_ticket_(g->stream, pinned_key + 1, a.ticket) == FIR_OK) return FIR_OK;
     // The launch failed or its last workgroup never published: only that workgroup re-arms the device key and the arrival
     // counter, so they are re-armed here (else every later one-query call would wait 2 ms and fail), and this call goes
     // through the general path. If the device itself is gone that path reports it.
@@ -1612,12 +1590,23 @@ int fir_gallery_pin_(fir_gallery* g, void** base, size_t* query_bytes, uint64_t*
 }
 uint64_t fir_gallery_next_ticket_(fir_gallery* g) { return ++g->one_ticket; }
 uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot) { return g->counters[slot & 3]++; }
-int fir_gallery_wait_ticket_(fir_gallery* g, volatile uint64_t* flag, uint64_t ticket) { return wait_ticket(g, flag, ticket); }
+// The one ticket wait (fir_internal.h): cheaper than hipStreamSynchronize for calls that take tens of microseconds.
+int fir_wait_ticket_(hipStream_t st, volatile uint64_t* flag, uint64_t ticket) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket; ++spins) {
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+            FIR_HIP(hipStreamSynchronize(st));       // a long or failed launch: let the runtime report it
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket) return fir_fail_(FIR_ERR_HIP, "the result ticket was not published");
+            break;
+        }
+    }
+    return FIR_OK;
+}
 
 int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* idx,
                     float* dist) {
-    if (!g || (qb > 0 && !queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
+    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1645,7 +1634,7 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         const uint64_t ticket = qb <= kBlock && !g->profiling ? ++g->one_ticket : 0;     // one block publishes: the host can wait on its ticket
         hipLaunchKernelGGL(k_publish_keys, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, g->stream, g->dkeys, qb, hk, ticket);
         FIR_HIP(hipGetLastError());
-        if (ticket) { if ((rc = wait_ticket(g, hk + qb, ticket))) return rc; }
+        if (ticket) { if ((rc = fir_wait_ticket_(g->stream, hk + qb, ticket))) return rc; }
         else FIR_HIP(hipStreamSynchronize(g->stream));
         order.done();
         return fir_keys_unpack(hk, qb, idx, dist);
@@ -1673,7 +1662,7 @@ uint64_t fir_key_pack(float dist, int32_t idx) {
 }
 
 int fir_keys_unpack(const uint64_t* keys, int32_t n, int32_t* idx, float* dist) {
-    if (!keys && n > 0) return fail(FIR_ERR_ARG, "keys is NULL");
+    if (!keys && n > 0) return fir_fail_(FIR_ERR_ARG, "keys is NULL");
     for (int32_t i = 0; i < n; ++i) {
         if (keys[i] == kKeyNone) {
             if (idx) idx[i] = -1;
@@ -1687,8 +1676,8 @@ int fir_keys_unpack(const uint64_t* keys, int32_t n, int32_t* idx, float* dist) 
 }
 
 int fir_gallery_classes_of(fir_gallery* g, const int32_t* idx, int32_t n, int32_t* class_out) {
-    if (!g || !idx || !class_out) return fail(FIR_ERR_ARG, "NULL argument");
-    if (!g->cls) return fail(FIR_ERR_STATE, "gallery was created without class labels");
+    if (!g || !idx || !class_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (!g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
     if (n <= 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
     FirCallOrder order(g, g->stream);
@@ -1706,9 +1695,9 @@ int fir_gallery_classes_of(fir_gallery* g, const int32_t* idx, int32_t n, int32_
 
 int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                              int32_t k, uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     if (qb == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1721,9 +1710,9 @@ int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb,
 
 int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                     int32_t* idx, float* dist) {
-    if (!g || (qb > 0 && !queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     if (qb == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1741,7 +1730,7 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         const uint64_t ticket = ++g->one_ticket;
         hipLaunchKernelGGL(k_publish_keys, dim3(1), dim3(kBlock), 0, g->stream, g->dkeys, qb * k, hk, ticket);
         FIR_HIP(hipGetLastError());
-        if ((rc = wait_ticket(g, hk + qb * k, ticket))) return rc;
+        if ((rc = fir_wait_ticket_(g->stream, hk + qb * k, ticket))) return rc;
         order.done();
         return fir_keys_unpack(hk, qb * k, idx, dist);
     }
@@ -1767,11 +1756,11 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
 
 namespace {
 int check_top_classes(const fir_gallery* g, const float* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, int32_t num_classes, int32_t k) {
-    if (!g || (qb > 0 && !queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > 32) return fail(FIR_ERR_ARG, "k=%d outside [1,32]", k);
-    if (num_classes < 1 || num_classes > kClassMax) return fail(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
-    if (!g->cls && g->n > 0) return fail(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
+    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > 32) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,32]", k);
+    if (num_classes < 1 || num_classes > kClassMax) return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
+    if (!g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
     return check_range(g, start_pos, end_pos);
 }
 }  // namespace
@@ -1780,7 +1769,7 @@ int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int3
                                     int32_t k, uint64_t* d_keys, int32_t* d_classes, void* stream) {
     int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
     if (rc) return rc;
-    if (qb > 0 && !d_keys && !d_classes) return fail(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
+    if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
     if (qb == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(g->device));
     const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -1817,9 +1806,9 @@ int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int
 
 int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k, uint64_t* keys_out,
                          int32_t* classes_out) {
-    if (parts < 0 || qb < 0 || k < 1) return fail(FIR_ERR_ARG, "bad merge shape parts=%d qb=%d k=%d", parts, qb, k);
-    if ((size_t)parts * qb > 0 && (!keys || !classes)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb > 0 && (!keys_out || !classes_out)) return fail(FIR_ERR_ARG, "NULL argument");
+    if (parts < 0 || qb < 0 || k < 1) return fir_fail_(FIR_ERR_ARG, "bad merge shape parts=%d qb=%d k=%d", parts, qb, k);
+    if ((size_t)parts * qb > 0 && (!keys || !classes)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb > 0 && (!keys_out || !classes_out)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     std::vector<std::pair<uint64_t, int32_t>> all;
     for (int32_t q = 0; q < qb; ++q) {
         all.clear();
@@ -1846,8 +1835,8 @@ int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t p
 
 int fir_range_distances_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                             float* d_out, void* stream) {
-    if (!g || !d_out || (qb > 0 && !d_queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
+    if (!g || !d_out || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1859,8 +1848,8 @@ int fir_range_distances_dev(fir_gallery* g, const float* d_queries, int32_t qb, 
 }
 
 int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, float* out) {
-    if (!g || !out || (qb > 0 && !queries)) return fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fail(FIR_ERR_ARG, "qb < 0");
+    if (!g || !out || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0 || g->n == 0) return FIR_OK;
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
@@ -1877,14 +1866,14 @@ int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_
 }
 
 int fir_profile_enable(fir_gallery* g, int32_t on) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     g->profiling = on != 0;
     g->ev_used = 0;
     return FIR_OK;
 }
 
 int fir_profile_read(fir_gallery* g, float* ms, int32_t cap, int32_t* count, double* bytes_per_launch) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     FIR_HIP(hipSetDevice(g->device));
     const int32_t launches = (int32_t)(g->ev_used / 2);
     for (int32_t i = 0; i < launches; ++i) {
@@ -1900,7 +1889,7 @@ int fir_profile_read(fir_gallery* g, float* ms, int32_t cap, int32_t* count, dou
 }
 
 int fir_gallery_sync(fir_gallery* g) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     FIR_HIP(hipSetDevice(g->device));
     const int rc = fir_gallery_wait_calls_(g);      // the most recent call, on whatever stream it was given (and so every call before it)
     if (rc) return rc;
@@ -1909,7 +1898,7 @@ int fir_gallery_sync(fir_gallery* g) {
 }
 
 int fir_gallery_value_range(fir_gallery* g, int32_t* gallery_plain, int32_t* last_queries_plain) {
-    if (!g || !gallery_plain || !last_queries_plain) return fail(FIR_ERR_ARG, "fir_gallery_value_range: null argument");
+    if (!g || !gallery_plain || !last_queries_plain) return fir_fail_(FIR_ERR_ARG, "fir_gallery_value_range: null argument");
     FIR_HIP(hipSetDevice(g->device));
     int32_t h[2] = {0, 0};
     const int rc = fir_gallery_wait_calls_(g);
@@ -1922,21 +1911,21 @@ int fir_gallery_value_range(fir_gallery* g, int32_t* gallery_plain, int32_t* las
 }
 
 int fir_gallery_set_tuning(fir_gallery* g, int32_t queries_per_pass, int32_t waves) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     if (queries_per_pass < 0) g->qpp = 0;   // back to automatic
     if (queries_per_pass > 0) {
         if (queries_per_pass != 1 && queries_per_pass != 2 && queries_per_pass != 4 && queries_per_pass != 8 &&
             queries_per_pass != 16)
-            return fail(FIR_ERR_ARG, "queries_per_pass must be 1, 2, 4, 8 or 16");
+            return fir_fail_(FIR_ERR_ARG, "queries_per_pass must be 1, 2, 4, 8 or 16");
         g->qpp = queries_per_pass;
     }
-    if (waves < 0 || (waves % 4) != 0) return fail(FIR_ERR_ARG, "waves must be a non-negative multiple of 4");
+    if (waves < 0 || (waves % 4) != 0) return fir_fail_(FIR_ERR_ARG, "waves must be a non-negative multiple of 4");
     g->waves_req = waves;
     return FIR_OK;
 }
 
 int fir_gallery_get_tuning(const fir_gallery* g, int32_t* queries_per_pass, int32_t* waves, int32_t* max_waves) {
-    if (!g) return fail(FIR_ERR_ARG, "gallery is NULL");
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     if (queries_per_pass) *queries_per_pass = effective_qpp(g);
     if (waves) *waves = g->last_waves;   // waves of the most recent scan launch (0 before the first)
     if (max_waves) *max_waves = g->max_waves;

@@ -15,8 +15,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -34,8 +32,6 @@ constexpr int kTileRows = 64;
 constexpr int kQB = 4;       // queries per pass of the f64 scan (training sets that stay in the caches, the sequential PNN)
 constexpr int kQBBig = 8;    // ... of a training set streamed from HBM: the pass is HBM-bound up to 8 queries (3 f64 vector ops per element and query)
 constexpr int kKMax = 8;
-
-int cls_fail(int code, const char* fmt, ...);   // defined with the C ABI below
 
 typedef const double __attribute__((address_space(4)))* sdouble_p;
 
@@ -609,7 +605,7 @@ __global__ void __launch_bounds__(64) k_cls_argbest(const double* __restrict__ v
                                                      int mode, int32_t* __restrict__ best_class, unsigned long long* ticket_word = nullptr,
                                                      unsigned long long ticket = 0) {
     // ticket_word (one-query calls, results in pinned host memory): after the class, the call's ticket -- the host spins on
-    // that word instead of synchronising the stream (cls_wait_ticket)
+    // that word instead of synchronising the stream (fir_wait_ticket_)
     // One wave per query: lane l looks at classes l, l + 64, ... in order (its first extremum), then the lanes are folded
     // by (better value, then lower class) -- the first extremum of the reference's single loop.
     const int q = blockIdx.x, lane = threadIdx.x;
@@ -694,27 +690,7 @@ struct fir_cls {
     int64_t mm_queries = 0, mm_unsettled = 0;         // queries that went through the matrix cores / of them sent on to the exact scan
 };
 
-extern "C" void fir_set_last_error_(const char* msg);   // fir_capi.hip: feeds fir_last_error()
-
 namespace {
-
-thread_local char g_cls_err[512];
-
-int cls_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_cls_err, sizeof(g_cls_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_cls_err);
-    return code;
-}
-
-#define CLS_HIP(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return cls_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,        \
-                                              "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 // HIP event pair around one launch of the distance scan (no-ops unless fir_cls_profile_enable is on)
 void cls_prof(fir_cls* c, int end, double bytes, const char* kernel) {
@@ -739,9 +715,9 @@ void cls_prof(fir_cls* c, int end, double bytes, const char* kernel) {
 template <typename T>
 int cls_grow(T*& p, size_t& cap, size_t need) {
     if (need <= cap) return FIR_OK;
-    if (p) CLS_HIP(hipFree(p));
+    if (p) FIR_HIP(hipFree(p));
     p = nullptr; cap = 0;
-    CLS_HIP(hipMalloc((void**)&p, std::max<size_t>(need, 1024) * sizeof(T)));
+    FIR_HIP(hipMalloc((void**)&p, std::max<size_t>(need, 1024) * sizeof(T)));
     cap = std::max<size_t>(need, 1024);
     return FIR_OK;
 }
@@ -754,26 +730,12 @@ constexpr int kPinResults = 4096;                 // int32 slots: classes [0, 20
 bool cls_small(const fir_cls* c, int32_t qb) { return (size_t)qb * c->d * sizeof(double) <= kPinQueryBytes && qb <= kPinResults / 2; }
 int cls_ensure_pin(fir_cls* c) {
     if (c->pin) return FIR_OK;
-    CLS_HIP(hipHostMalloc(&c->pin, kPinQueryBytes + kPinResults * sizeof(int32_t) + 64, hipHostMallocDefault));
+    FIR_HIP(hipHostMalloc(&c->pin, kPinQueryBytes + kPinResults * sizeof(int32_t) + 64, hipHostMallocDefault));
     std::memset((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t), 0, 64);
     return FIR_OK;
 }
 int32_t* cls_pin_results(fir_cls* c) { return (int32_t*)((char*)c->pin + kPinQueryBytes); }
 unsigned long long* cls_pin_ticket(fir_cls* c) { return (unsigned long long*)((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t)); }
-// Spin (2 ms at most, then the stream synchronisation) until the call's last kernel has written `ticket` to the pinned word:
-// cheaper than hipStreamSynchronize for calls that take tens of microseconds (as fir_capi.hip's wait_ticket).
-int cls_wait_ticket(fir_cls* c, unsigned long long ticket) {
-    volatile unsigned long long* flag = cls_pin_ticket(c);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket; ++spins) {
-        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-            CLS_HIP(hipStreamSynchronize(c->stream));
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket) return cls_fail(FIR_ERR_HIP, "the result ticket was not published");
-            break;
-        }
-    }
-    return FIR_OK;
-}
 // -> device-visible pointer to the staged queries
 int cls_stage_queries(fir_cls* c, const double* queries, int32_t qb, const double** d_q) {
     int rc;
@@ -784,7 +746,7 @@ int cls_stage_queries(fir_cls* c, const double* queries, int32_t qb, const doubl
         return FIR_OK;
     }
     if ((rc = cls_grow(c->dq, c->dq_cap, (size_t)qb * c->d))) return rc;
-    CLS_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FIR_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
     *d_q = c->dq;
     return FIR_OK;
 }
@@ -809,7 +771,7 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
     if (qb == 1 && !big) {
         hipLaunchKernelGGL(k_cls_scan_one, dim3(waves / 4), dim3(kBlock), (size_t)kk * sizeof(double), c->stream, c->gal2, dq, c->avg, c->nt,
                            (int)c->tiles, c->dp2, c->d, waves, 0, c->dp2, c->sums, c->dp2, (int64_t)0);
-        CLS_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         return FIR_OK;
     }
     const size_t lds_tile = (size_t)(kk + 1) * 8 * sizeof(double);
@@ -838,8 +800,8 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
             static bool attr_set[64] = {};                     // (per device: the attribute belongs to the device's copy of the code object)
             const int dv = c->device & 63;
             if (!attr_set[dv]) {
-                CLS_HIP(hipFuncSetAttribute((const void*)f4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                CLS_HIP(hipFuncSetAttribute((const void*)f2.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                FIR_HIP(hipFuncSetAttribute((const void*)f4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                FIR_HIP(hipFuncSetAttribute((const void*)f2.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 attr_set[dv] = true;
             }
         }
@@ -858,7 +820,7 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
             cls_prof(c, 1, (double)groups * ((double)c->tiles * 64.0 * c->dp2 * 16.0) + (double)tn * ((double)kk * 64.0 + 8.0 * 8.0 * (double)c->nt), f.name);
             t0 += tn;
         }
-        CLS_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         return FIR_OK;
     }
     for (int q0 = 0; q0 < qb; q0 += qbt) {
@@ -875,7 +837,7 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
                                c->d, waves, nq, 0, c->dp2, c->sums + (size_t)q0 * c->nt, c->dp2, (int64_t)0);
         }
     }
-    CLS_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
 
@@ -898,30 +860,30 @@ int fir_cls_create_dev(const double* d_train_rows, int64_t nt, int32_t d, const 
 
 static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
                       const double* avg, int32_t device, fir_cls** out) {
-    if (!out) return cls_fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (nt < 0 || d <= 0 || num_classes <= 0 || !avg || (nt > 0 && (!train_rows || !train_class)))
-        return cls_fail(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
-    if (nt >= ((int64_t)1 << 31) - 64) return cls_fail(FIR_ERR_ARG, "nt too large");
+        return fir_fail_(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
+    if (nt >= ((int64_t)1 << 31) - 64) return fir_fail_(FIR_ERR_ARG, "nt too large");
     std::vector<int32_t> off((size_t)num_classes + 1, 0);
     for (int64_t t = 0; t < nt; ++t) {
         const int32_t cl = train_class[t];
         if (cl < 0 || cl >= num_classes || (t > 0 && cl < train_class[t - 1]))
-            return cls_fail(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
+            return fir_fail_(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
         off[(size_t)cl + 1]++;
     }
     for (int i = 0; i < num_classes; ++i) off[(size_t)i + 1] += off[(size_t)i];
     int cnt = 0;
     cnt = fir_device_count();        // the guarded first touch of the runtime (fir_runtime_init_)
-    if (cnt <= 0) return cls_fail(FIR_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= cnt) return cls_fail(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
+    if (cnt <= 0) return fir_fail_(FIR_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
     { const int rc0 = fir_runtime_init_(device); if (rc0) return rc0; }
     hipDeviceProp_t prop;
-    CLS_HIP(hipGetDeviceProperties(&prop, device));
+    FIR_HIP(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return cls_fail(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     fir_cls* c = new (std::nothrow) fir_cls();
-    if (!c) return cls_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!c) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     c->device = device;
     c->cus = prop.multiProcessorCount;
     c->nt = nt;
@@ -952,33 +914,33 @@ static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt,
         e = hipStreamSynchronize(c->stream);
     }
     if (stage) (void)hipFree(stage);
-    if (e != hipSuccess) rc = cls_fail(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "training-set upload: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "training-set upload: %s", hipGetErrorString(e));
     if (rc) { fir_cls_destroy(c); return rc; }
     *out = c;
     return FIR_OK;
 }
 
 int fir_cls_set_total_training_size(fir_cls* c, int64_t total) {
-    if (!c || total < 0) return cls_fail(FIR_ERR_ARG, "bad argument");
+    if (!c || total < 0) return fir_fail_(FIR_ERR_ARG, "bad argument");
     c->total_training_size = (double)total;
     return FIR_OK;
 }
 
 int fir_cls_profile_enable(fir_cls* c, int32_t on) {
-    if (!c) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     c->profiling = on != 0;
     c->ev_used = 0;
     return FIR_OK;
 }
 
 int fir_cls_profile_read(fir_cls* c, float* ms, int32_t cap, int32_t* count, double* bytes_per_launch, char* kernel, int32_t kernel_cap) {
-    if (!c) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    CLS_HIP(hipSetDevice(c->device));
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(c->device));
     const int32_t have = (int32_t)(c->ev_used / 2);
     for (int32_t i = 0; i < have; ++i) {
-        CLS_HIP(hipEventSynchronize(c->ev[2 * (size_t)i + 1]));
+        FIR_HIP(hipEventSynchronize(c->ev[2 * (size_t)i + 1]));
         float t = 0.f;
-        CLS_HIP(hipEventElapsedTime(&t, c->ev[2 * (size_t)i], c->ev[2 * (size_t)i + 1]));
+        FIR_HIP(hipEventElapsedTime(&t, c->ev[2 * (size_t)i], c->ev[2 * (size_t)i + 1]));
         if (ms && i < cap) ms[i] = t;
     }
     if (count) *count = have;
@@ -1004,20 +966,20 @@ int fir_cls_destroy(fir_cls* c) {
 }
 
 int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double* sums) {
-    if (!c || !sums || (qb > 0 && !queries)) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return cls_fail(FIR_ERR_ARG, "qb < 0");
+    if (!c || !sums || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0 || c->nt == 0) return FIR_OK;
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
-    CLS_HIP(hipMemcpyAsync(sums, c->sums, (size_t)qb * c->nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipMemcpyAsync(sums, c->sums, (size_t)qb * c->nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
     return FIR_OK;
 }
 
 int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
-    if (!c || (qb > 0 && !queries)) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return cls_fail(FIR_ERR_ARG, "qb < 0");
+    if (!c || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (qb == 0) return FIR_OK;
     if (qb > cls_batch(c)) {
         const int32_t b = cls_batch(c);
@@ -1028,7 +990,7 @@ int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double va
         }
         return FIR_OK;
     }
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:190-193
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
@@ -1043,11 +1005,11 @@ int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double va
     const unsigned long long ticket = one ? ++c->ticket : 0;
     hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 0, dbest,
                        one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    CLS_HIP(hipGetLastError());
-    if (scores) CLS_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (best_class && !small) CLS_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (one) { if ((rc = cls_wait_ticket(c, ticket))) return rc; }
-    else CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipGetLastError());
+    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (best_class && !small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
+    else FIR_HIP(hipStreamSynchronize(c->stream));
     if (best_class && small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
     return FIR_OK;
 }
@@ -1055,11 +1017,11 @@ int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double va
 // PNN class scores of qb <= *max_batch queries, left on the device (valid until the handle's next call), queued on the
 // handle's stream: the row-sharded PNN (fir_shard.hip) adds the shards' partial sums before the arg-max.
 int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, double var, double** d_scores, void** stream, int32_t* max_batch) {
-    if (!c || !d_scores || !stream) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c || !d_scores || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (max_batch) *max_batch = cls_batch(c);
     if (qb == 0) return FIR_OK;
-    if (qb < 0 || qb > cls_batch(c) || !queries) return cls_fail(FIR_ERR_ARG, "bad batch %d (at most %d at a time)", qb, cls_batch(c));
-    CLS_HIP(hipSetDevice(c->device));
+    if (qb < 0 || qb > cls_batch(c) || !queries) return fir_fail_(FIR_ERR_ARG, "bad batch %d (at most %d at a time)", qb, cls_batch(c));
+    FIR_HIP(hipSetDevice(c->device));
     if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:190-193
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
@@ -1067,7 +1029,7 @@ int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, doubl
     const double denom = (double)(2 * (size_t)c->d) * var;
     hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
                        c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
-    CLS_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     *d_scores = c->scores;
     *stream = c->stream;
     return FIR_OK;
@@ -1076,29 +1038,29 @@ int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, doubl
 // The k smallest mean distances per class of qb <= *max_batch queries, [qb][num_classes][k] ascending (DBL_MAX where the class has
 // fewer rows here), left on the device and queued on the handle's stream: the row-sharded kNN vote (fir_shard.hip) merges them.
 int fir_cls_knn_nearest_dev_(fir_cls* c, const double* queries, int32_t qb, int32_t k, double** d_lists, void** stream, int32_t* max_batch) {
-    if (!c || !d_lists || !stream) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c || !d_lists || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (max_batch) *max_batch = cls_batch(c);
     if (qb == 0) return FIR_OK;
-    if (qb < 0 || qb > cls_batch(c) || !queries || k < 1 || k > kKMax) return cls_fail(FIR_ERR_ARG, "bad batch %d / k %d", qb, k);
-    CLS_HIP(hipSetDevice(c->device));
+    if (qb < 0 || qb > cls_batch(c) || !queries || k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "bad batch %d / k %d", qb, k);
+    FIR_HIP(hipSetDevice(c->device));
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
     if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes * (1 + (size_t)k)))) return rc;
     double* lists = c->scores + (size_t)qb * c->num_classes;
     hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, c->d, k, c->scores,
                        lists);
-    CLS_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     *d_lists = lists;
     *stream = c->stream;
     return FIR_OK;
 }
 
 int fir_cls_pnn_predict_seq(fir_cls* c, const double* queries, int32_t qb, double var, int32_t* best_class, int32_t* chunks_out) {
-    if (!c || !best_class || (qb > 0 && !queries)) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return cls_fail(FIR_ERR_ARG, "qb < 0");
-    if ((size_t)c->num_classes * 16 + 4 > 60 * 1024) return cls_fail(FIR_ERR_ARG, "num_classes=%d too large for the LDS tables", c->num_classes);
+    if (!c || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if ((size_t)c->num_classes * 16 + 4 > 60 * 1024) return fir_fail_(FIR_ERR_ARG, "num_classes=%d too large for the LDS tables", c->num_classes);
     if (qb == 0) return FIR_OK;
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:229-233
     const int nchunks = (c->d + 31) / 32;
     const int64_t ntp = std::max<int64_t>(c->nt, 1);
@@ -1142,18 +1104,18 @@ int fir_cls_pnn_predict_seq(fir_cls* c, const double* queries, int32_t qb, doubl
                                c->total_training_size > 0 ? c->total_training_size : (double)c->nt, dbest + q0, dchunks + q0,
                                one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
     }
-    CLS_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     if (one) {
-        if ((rc = cls_wait_ticket(c, ticket))) return rc;
+        if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc;
         best_class[0] = dbest[0];
         if (chunks_out) chunks_out[0] = dchunks[0];
         return FIR_OK;
     }
     if (!small) {
-        CLS_HIP(hipMemcpyAsync(best_class, dbest, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (chunks_out) CLS_HIP(hipMemcpyAsync(chunks_out, dchunks, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FIR_HIP(hipMemcpyAsync(best_class, dbest, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (chunks_out) FIR_HIP(hipMemcpyAsync(chunks_out, dchunks, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     }
-    CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
     if (small) {
         std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
         if (chunks_out) std::memcpy(chunks_out, dchunks, (size_t)qb * sizeof(int32_t));
@@ -1211,7 +1173,7 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
 extern "C" {
 
 int fir_cls_set_knn_mfma(fir_cls* c, int32_t min_queries) {
-    if (!c) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     c->mm_mode = min_queries < 0 ? -1 : min_queries;
     if (min_queries == 0 && c->mm) { (void)fir_gemm_destroy(c->mm); c->mm = nullptr; }
     c->mm_failed = false;
@@ -1219,14 +1181,14 @@ int fir_cls_set_knn_mfma(fir_cls* c, int32_t min_queries) {
 }
 
 int fir_cls_knn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them) {
-    if (!c) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (matrix_core_queries) *matrix_core_queries = c->mm_queries;
     if (exact_scan_queries_of_them) *exact_scan_queries_of_them = c->mm_unsettled;
     return FIR_OK;
 }
 
 int fir_cls_last_dispatch(fir_cls* c, char* kernel, int32_t kernel_cap, double* bytes_per_launch, double* flops_per_launch) {
-    if (!c) return cls_fail(FIR_ERR_ARG, "NULL argument");
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (kernel && kernel_cap > 0) std::snprintf(kernel, (size_t)kernel_cap, "%s", c->last_kernel);
     if (bytes_per_launch) *bytes_per_launch = c->last_bytes;
     if (flops_per_launch) *flops_per_launch = c->last_flops;
@@ -1236,9 +1198,9 @@ int fir_cls_last_dispatch(fir_cls* c, char* kernel, int32_t kernel_cap, double* 
 static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class);
 
 int fir_cls_knn_predict(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
-    if (!c || !best_class || (qb > 0 && !queries)) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return cls_fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return cls_fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (!c || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     if (qb == 0) return FIR_OK;
     // Large batches against a training set that streams from HBM: the matrix cores nominate the K' nearest rows, float64 re-ranks them,
     // the vote is taken over those; what that does not settle falls through to the exact scan below (fir_gemm_f64.h). Same classes.
@@ -1250,7 +1212,7 @@ int fir_cls_knn_predict(fir_cls* c, const double* queries, int32_t qb, int32_t k
         for (int32_t q0 = 0; q0 < qb && all; q0 += b) {
             const int rc0 = cls_knn_mfma(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), k, best_class + q0);
             if (rc0 < 0) return rc0;
-            if (rc0 == 1) { if (q0 != 0) return cls_fail(FIR_ERR_STATE, "the matrix-core kNN path stopped in the middle of a call"); all = false; }
+            if (rc0 == 1) { if (q0 != 0) return fir_fail_(FIR_ERR_STATE, "the matrix-core kNN path stopped in the middle of a call"); all = false; }
         }
         if (all) return FIR_OK;
     }
@@ -1266,7 +1228,7 @@ static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t 
         }
         return FIR_OK;
     }
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
     if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
@@ -1279,10 +1241,10 @@ static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t 
     const unsigned long long ticket = one ? ++c->ticket : 0;
     hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 1, dbest,
                        one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    CLS_HIP(hipGetLastError());
-    if (!small) CLS_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (one) { if ((rc = cls_wait_ticket(c, ticket))) return rc; }
-    else CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipGetLastError());
+    if (!small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
+    else FIR_HIP(hipStreamSynchronize(c->stream));
     if (small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
     return FIR_OK;
 }
@@ -1291,7 +1253,7 @@ static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t 
 
 namespace {
 int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     if (!c->mm) {
         const int rc = fir_gemm_create_f64_(c->device, c->cus, c->stream, c->gal2, c->nt, c->d, c->dp2, &c->mm);
         if (rc) {
@@ -1310,7 +1272,7 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
     if ((rc = cls_grow(c->knn_dist, c->knn_dist_cap, (size_t)qb * 8))) return rc;
     if ((rc = cls_grow(c->knn_ok, c->knn_ok_cap, (size_t)qb))) return rc;
     if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
-    CLS_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FIR_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int64_t count = (int64_t)qb * c->d;
     hipLaunchKernelGGL(k_cls_center_queries, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->dq, count, c->d, c->avg, c->qc);
     hipEvent_t* evp = nullptr;
@@ -1334,9 +1296,9 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
     }
     hipLaunchKernelGGL(k_cls_knn_vote, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->knn_rows, c->knn_dist, c->knn_ok, qb, kp, k, c->class_off, c->num_classes,
                        c->best);
-    CLS_HIP(hipGetLastError());
-    CLS_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
     c->mm_queries += qb;
     // what the K' rows did not settle: the exact scan (classification.cpp's own loop over every row), a tile of queries at a time
     std::vector<int32_t> which;
@@ -1365,9 +1327,9 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
 extern "C" {
 
 int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int32_t k, double* nearest) {
-    if (!c || !nearest || (qb > 0 && !queries)) return cls_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return cls_fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return cls_fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (!c || !nearest || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     if (qb == 0) return FIR_OK;
     const size_t per_query = (size_t)c->num_classes * k;
     if (qb > cls_batch(c)) {
@@ -1378,7 +1340,7 @@ int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int
         }
         return FIR_OK;
     }
-    CLS_HIP(hipSetDevice(c->device));
+    FIR_HIP(hipSetDevice(c->device));
     int rc = cls_scan(c, queries, qb);
     if (rc) return rc;
     // scores: [qb][num_classes] k-th values, then [qb][num_classes][k] lists
@@ -1386,9 +1348,9 @@ int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int
     double* lists = c->scores + (size_t)qb * c->num_classes;
     hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, c->d, k, c->scores,
                        lists);
-    CLS_HIP(hipGetLastError());
-    CLS_HIP(hipMemcpyAsync(nearest, lists, (size_t)qb * per_query * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    CLS_HIP(hipStreamSynchronize(c->stream));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(nearest, lists, (size_t)qb * per_query * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
     return FIR_OK;
 }
 

@@ -23,8 +23,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <cstdarg>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <unordered_map>
@@ -39,21 +37,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 1024;
 
-thread_local char g_dem_err[512];
-int dem_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_dem_err, sizeof(g_dem_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_dem_err);
-    return code;
-}
-#define DEM_HIP(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return dem_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,        \
-                                              "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 struct Part {       // one block's partial result
     double far;     // largest far sum > 0 seen (0 = none)
@@ -262,38 +245,38 @@ int dem_build(fir_gallery* g, const fir_gallery_view& v, int first_pivot, int n_
               int keep_piv, int32_t* d_pivots, float* d_min_other) {
     const void* gal4 = nullptr;
     int dp4 = 0;
-    if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return dem_fail(FIR_ERR_STATE, "gallery has no tiled copy");
+    if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
     const int n = (int)v.n;
     const int nblocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
     Buf dfar, dparts;
-    DEM_HIP(dfar.alloc((size_t)n * 8));
-    DEM_HIP(dparts.alloc((size_t)nblocks * sizeof(Part)));
-    DEM_HIP(hipMemsetAsync(d_pivots, 0xff, (size_t)n_pivots * 4, v.stream));
-    DEM_HIP(hipMemcpyAsync(d_pivots, &first_pivot, 4, hipMemcpyHostToDevice, v.stream));
+    FIR_HIP(dfar.alloc((size_t)n * 8));
+    FIR_HIP(dparts.alloc((size_t)nblocks * sizeof(Part)));
+    FIR_HIP(hipMemsetAsync(d_pivots, 0xff, (size_t)n_pivots * 4, v.stream));
+    FIR_HIP(hipMemcpyAsync(d_pivots, &first_pivot, 4, hipMemcpyHostToDevice, v.stream));
     for (int ii = 0; ii < n_pivots; ++ii) {
         float* row = d_table + (size_t)std::min(ii, keep_rows) * n;
         float* q = d_pivrows + (size_t)std::min(ii, keep_piv) * v.d;
         hipLaunchKernelGGL(k_dem_gather, dim3(std::max(1, std::min(64, (dp4 + kBlock - 1) / kBlock))), dim3(kBlock), 0, v.stream,
                            (const float4*)gal4, dp4, v.d, d_pivots, ii, q);
-        DEM_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         const int rc = fir_range_distances_dev(g, q, 1, 0, v.d, row, v.stream);
         if (rc) return rc;
         hipLaunchKernelGGL(k_dem_step, dim3(nblocks), dim3(kBlock), 0, v.stream, row, v.cls, n, d_pivots, ii, dfar.as<double>(), dparts.as<Part>());
-        DEM_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_dem_pick, dim3(1), dim3(kBlock), 0, v.stream, dparts.as<Part>(), nblocks, ii, n_pivots, d_pivots, d_min_other);
-        DEM_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
     }
-    DEM_HIP(hipStreamSynchronize(v.stream));   // dfar/dparts are freed on return
+    FIR_HIP(hipStreamSynchronize(v.stream));   // dfar/dparts are freed on return
     return FIR_OK;
 }
 
 int check_build_args(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_gallery_view* v) {
-    if (!g) return dem_fail(FIR_ERR_ARG, "NULL gallery");
-    if (fir_gallery_view_(g, v) != FIR_OK) return dem_fail(FIR_ERR_ARG, "bad gallery");
-    if (!v->cls) return dem_fail(FIR_ERR_STATE, "gallery was created without class labels");
-    if (n_pivots <= 0) return dem_fail(FIR_ERR_ARG, "n_pivots=%d must be positive", n_pivots);
-    if (v->n <= 0 || v->n >= (int64_t)1 << 30) return dem_fail(FIR_ERR_ARG, "gallery of %lld rows outside [1, 2^30)", (long long)v->n);
-    if (first_pivot < 0 || first_pivot >= v->n) return dem_fail(FIR_ERR_ARG, "first_pivot=%d outside the gallery", first_pivot);
+    if (!g) return fir_fail_(FIR_ERR_ARG, "NULL gallery");
+    if (fir_gallery_view_(g, v) != FIR_OK) return fir_fail_(FIR_ERR_ARG, "bad gallery");
+    if (!v->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    if (n_pivots <= 0) return fir_fail_(FIR_ERR_ARG, "n_pivots=%d must be positive", n_pivots);
+    if (v->n <= 0 || v->n >= (int64_t)1 << 30) return fir_fail_(FIR_ERR_ARG, "gallery of %lld rows outside [1, 2^30)", (long long)v->n);
+    if (first_pivot < 0 || first_pivot >= v->n) return fir_fail_(FIR_ERR_ARG, "first_pivot=%d outside the gallery", first_pivot);
     return FIR_OK;
 }
 
@@ -328,18 +311,18 @@ int fir_dem_pivot_table(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, i
     fir_gallery_view v;
     int rc = check_build_args(g, first_pivot, n_pivots, &v);
     if (rc) return rc;
-    if (!pivots_out) return dem_fail(FIR_ERR_ARG, "pivots_out is NULL");
-    DEM_HIP(hipSetDevice(v.device));
+    if (!pivots_out) return fir_fail_(FIR_ERR_ARG, "pivots_out is NULL");
+    FIR_HIP(hipSetDevice(v.device));
     const int keep = table_out ? n_pivots - 1 : 0;
     Buf dtable, dq, dpiv, dmo;
-    DEM_HIP(dtable.alloc((size_t)(keep + 1) * v.n * 4));
-    DEM_HIP(dq.alloc((size_t)v.d * 4));
-    DEM_HIP(dpiv.alloc((size_t)n_pivots * 4));
-    DEM_HIP(dmo.alloc((size_t)n_pivots * 4));
+    FIR_HIP(dtable.alloc((size_t)(keep + 1) * v.n * 4));
+    FIR_HIP(dq.alloc((size_t)v.d * 4));
+    FIR_HIP(dpiv.alloc((size_t)n_pivots * 4));
+    FIR_HIP(dmo.alloc((size_t)n_pivots * 4));
     if ((rc = dem_build(g, v, first_pivot, n_pivots, dtable.as<float>(), keep, dq.as<float>(), 0, dpiv.as<int32_t>(), dmo.as<float>()))) return rc;
-    DEM_HIP(hipMemcpy(pivots_out, dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    if (min_other_out) DEM_HIP(hipMemcpy(min_other_out, dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    if (table_out) DEM_HIP(hipMemcpy(table_out, dtable.p, (size_t)n_pivots * v.n * 4, hipMemcpyDeviceToHost));
+    FIR_HIP(hipMemcpy(pivots_out, dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    if (min_other_out) FIR_HIP(hipMemcpy(min_other_out, dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    if (table_out) FIR_HIP(hipMemcpy(table_out, dtable.p, (size_t)n_pivots * v.n * 4, hipMemcpyDeviceToHost));
     if (n_built_out) *n_built_out = count_built(pivots_out, n_pivots);
     return FIR_OK;
 }
@@ -348,27 +331,27 @@ int fir_dem_create(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_de
     fir_gallery_view v;
     int rc = check_build_args(g, first_pivot, n_pivots, &v);
     if (rc) return rc;
-    if (!out) return dem_fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
     int32_t metric = 0;
     if ((rc = fir_gallery_info(g, nullptr, nullptr, &metric, nullptr))) return rc;
-    DEM_HIP(hipSetDevice(v.device));
+    FIR_HIP(hipSetDevice(v.device));
     fir_dem* h = new fir_dem();
     struct Guard { fir_dem* h; ~Guard() { if (h) fir_dem_destroy(h); } } guard{h};
     h->g = g; h->v = v; h->n_pivots = n_pivots;
     const int keep = std::min<int>(n_pivots, kMaxUsed);
     const int n = (int)v.n;
     Buf dpiv, dmo;
-    DEM_HIP(h->table.alloc((size_t)(keep + 1) * n * 4));
-    DEM_HIP(h->pivrows.alloc((size_t)(keep + 1) * v.d * 4));
-    DEM_HIP(dpiv.alloc((size_t)n_pivots * 4));
-    DEM_HIP(dmo.alloc((size_t)n_pivots * 4));
+    FIR_HIP(h->table.alloc((size_t)(keep + 1) * n * 4));
+    FIR_HIP(h->pivrows.alloc((size_t)(keep + 1) * v.d * 4));
+    FIR_HIP(dpiv.alloc((size_t)n_pivots * 4));
+    FIR_HIP(dmo.alloc((size_t)n_pivots * 4));
     if ((rc = dem_build(g, v, first_pivot, n_pivots, h->table.as<float>(), keep, h->pivrows.as<float>(), keep, dpiv.as<int32_t>(), dmo.as<float>())))
         return rc;
     h->pivots.resize((size_t)n_pivots);
     h->min_other.resize((size_t)n_pivots);
-    DEM_HIP(hipMemcpy(h->pivots.data(), dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    DEM_HIP(hipMemcpy(h->min_other.data(), dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    FIR_HIP(hipMemcpy(h->pivots.data(), dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    FIR_HIP(hipMemcpy(h->min_other.data(), dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
     h->built = count_built(h->pivots.data(), n_pivots);
     h->used = std::min(h->built, kMaxUsed);
     if ((rc = fir_gallery_create_dev(h->pivrows.as<float>(), h->used, v.d, nullptr, metric, v.device, v.stream, &h->pivot_rows))) return rc;
@@ -401,16 +384,16 @@ int fir_dem_create(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_de
         if (kv.first != kv.second) h->order_mods.push_back(kv);
     std::sort(h->order_mods.begin(), h->order_mods.end());
     h->nexc = (int)special.size();
-    DEM_HIP(h->exc_rows.alloc(special.size() * 4));
-    DEM_HIP(h->exc_mult.alloc(mult.size()));
-    DEM_HIP(hipMemcpy(h->exc_rows.p, special.data(), special.size() * 4, hipMemcpyHostToDevice));
-    DEM_HIP(hipMemcpy(h->exc_mult.p, mult.data(), mult.size(), hipMemcpyHostToDevice));
-    DEM_HIP(h->q.alloc((size_t)kLikBatch * v.d * 4));
-    DEM_HIP(h->pd.alloc((size_t)kLikBatch * kMaxUsed * 4));
-    DEM_HIP(h->lik.alloc((size_t)kLikBatch * n * 4));
+    FIR_HIP(h->exc_rows.alloc(special.size() * 4));
+    FIR_HIP(h->exc_mult.alloc(mult.size()));
+    FIR_HIP(hipMemcpy(h->exc_rows.p, special.data(), special.size() * 4, hipMemcpyHostToDevice));
+    FIR_HIP(hipMemcpy(h->exc_mult.p, mult.data(), mult.size(), hipMemcpyHostToDevice));
+    FIR_HIP(h->q.alloc((size_t)kLikBatch * v.d * 4));
+    FIR_HIP(h->pd.alloc((size_t)kLikBatch * kMaxUsed * 4));
+    FIR_HIP(h->lik.alloc((size_t)kLikBatch * n * 4));
     if (n <= kPinLikRows) {
         const size_t bytes = (size_t)kLikBatch * ((size_t)v.d + kMaxUsed + (size_t)n) * 4 + 64;
-        DEM_HIP(hipHostMalloc(&h->pin, bytes, hipHostMallocDefault));
+        FIR_HIP(hipHostMalloc(&h->pin, bytes, hipHostMallocDefault));
         std::memset(h->pin, 0, bytes);
     }
     guard.h = nullptr;
@@ -428,7 +411,7 @@ int fir_dem_destroy(fir_dem* h) {
 }
 
 int fir_dem_info(const fir_dem* h, int32_t* n_pivots, int32_t* n_built, int32_t* n_used, int64_t* n) {
-    if (!h) return dem_fail(FIR_ERR_ARG, "NULL handle");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "NULL handle");
     if (n_pivots) *n_pivots = h->n_pivots;
     if (n_built) *n_built = h->built;
     if (n_used) *n_used = h->used;
@@ -437,12 +420,12 @@ int fir_dem_info(const fir_dem* h, int32_t* n_pivots, int32_t* n_built, int32_t*
 }
 
 int fir_dem_get(fir_dem* h, int32_t* pivots_out, float* min_other_out, float* table_out, int32_t* order_out) {
-    if (!h) return dem_fail(FIR_ERR_ARG, "NULL handle");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "NULL handle");
     if (pivots_out) std::copy(h->pivots.begin(), h->pivots.end(), pivots_out);
     if (min_other_out) std::copy(h->min_other.begin(), h->min_other.end(), min_other_out);
     if (table_out) {
-        DEM_HIP(hipSetDevice(h->v.device));
-        DEM_HIP(hipMemcpy(table_out, h->table.p, (size_t)h->used * h->v.n * 4, hipMemcpyDeviceToHost));
+        FIR_HIP(hipSetDevice(h->v.device));
+        FIR_HIP(hipMemcpy(table_out, h->table.p, (size_t)h->used * h->v.n * 4, hipMemcpyDeviceToHost));
     }
     if (order_out) {
         for (int64_t i = 0; i < h->v.n; ++i) order_out[i] = (int32_t)i;
@@ -452,10 +435,10 @@ int fir_dem_get(fir_dem* h, int32_t* pivots_out, float* min_other_out, float* ta
 }
 
 int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* pivot_dist_out, float* lik_out) {
-    if (!h || (qb > 0 && !queries)) return dem_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return dem_fail(FIR_ERR_ARG, "qb < 0");
+    if (!h || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     const fir_gallery_view& v = h->v;
-    DEM_HIP(hipSetDevice(v.device));
+    FIR_HIP(hipSetDevice(v.device));
     const int n = (int)v.n, used = h->used;
     const int nblocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
     float* hq = (float*)h->pin;
@@ -471,35 +454,29 @@ int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* piv
             dq = hq;
             dlik = hlik;
         } else {
-            DEM_HIP(hipMemcpyAsync(h->q.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
+            FIR_HIP(hipMemcpyAsync(h->q.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
         }
         const int rc = fir_range_distances_dev(h->pivot_rows, dq, nq, 0, v.d, h->pd.as<float>(), v.stream);   // pd[q][used]
         if (rc) return rc;
         if (!hq && pivot_dist_out)
-            DEM_HIP(hipMemcpyAsync(pivot_dist_out + (size_t)q0 * used, h->pd.p, (size_t)nq * used * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipMemcpyAsync(pivot_dist_out + (size_t)q0 * used, h->pd.p, (size_t)nq * used * 4, hipMemcpyDeviceToHost, v.stream));
         if (lik_out) {
             hipLaunchKernelGGL(k_dem_lik<kLikBatch>, dim3(nblocks), dim3(kBlock), 0, v.stream, h->table.as<float>(), n, used, h->pd.as<float>(), nq, dlik);
-            DEM_HIP(hipGetLastError());
+            FIR_HIP(hipGetLastError());
             hipLaunchKernelGGL(k_dem_lik_fix, dim3((h->nexc * nq + 63) / 64), dim3(64), 0, v.stream, h->table.as<float>(), n, used, h->pd.as<float>(),
                                nq, h->exc_rows.as<int32_t>(), h->exc_mult.as<uint8_t>(), h->nexc, dlik);
-            DEM_HIP(hipGetLastError());
-            if (!hq) DEM_HIP(hipMemcpyAsync(lik_out + (size_t)q0 * n, h->lik.p, (size_t)nq * n * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipGetLastError());
+            if (!hq) FIR_HIP(hipMemcpyAsync(lik_out + (size_t)q0 * n, h->lik.p, (size_t)nq * n * 4, hipMemcpyDeviceToHost, v.stream));
         }
         if (!hq) {
-            DEM_HIP(hipStreamSynchronize(v.stream));
+            FIR_HIP(hipStreamSynchronize(v.stream));
             continue;
         }
         const unsigned long long ticket = ++h->ticket;
         hipLaunchKernelGGL(k_dem_publish, dim3(1), dim3(64), 0, v.stream, h->pd.as<float>(), nq * used, hpd, tword, ticket);
-        DEM_HIP(hipGetLastError());
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int spins = 0; __atomic_load_n(tword, __ATOMIC_ACQUIRE) != ticket; ++spins) {
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                DEM_HIP(hipStreamSynchronize(v.stream));
-                if (__atomic_load_n(tword, __ATOMIC_ACQUIRE) != ticket) return dem_fail(FIR_ERR_HIP, "the result ticket was not published");
-                break;
-            }
-        }
+        FIR_HIP(hipGetLastError());
+        const int wrc = fir_wait_ticket_(v.stream, (volatile uint64_t*)tword, ticket);
+        if (wrc) return wrc;
         if (pivot_dist_out) std::memcpy(pivot_dist_out + (size_t)q0 * used, hpd, (size_t)nq * used * 4);
         if (lik_out) std::memcpy(lik_out + (size_t)q0 * n, hlik, (size_t)nq * n * 4);
     }
@@ -509,19 +486,19 @@ int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* piv
 int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const int32_t* rows, int32_t m, int32_t start_pos, int32_t end_pos,
                        float* out) {
     fir_gallery_view v;
-    if (!g || (qb > 0 && m > 0 && (!queries || !rows || !out))) return dem_fail(FIR_ERR_ARG, "NULL argument");
-    if (fir_gallery_view_(g, &v) != FIR_OK) return dem_fail(FIR_ERR_ARG, "bad gallery");
-    if (qb < 0 || m < 0 || qb > 65535) return dem_fail(FIR_ERR_ARG, "qb=%d / m=%d out of range", qb, m);
+    if (!g || (qb > 0 && m > 0 && (!queries || !rows || !out))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (fir_gallery_view_(g, &v) != FIR_OK) return fir_fail_(FIR_ERR_ARG, "bad gallery");
+    if (qb < 0 || m < 0 || qb > 65535) return fir_fail_(FIR_ERR_ARG, "qb=%d / m=%d out of range", qb, m);
     if (end_pos == 0) end_pos = v.d;
-    if (start_pos < 0 || end_pos > v.d || start_pos >= end_pos) return dem_fail(FIR_ERR_ARG, "feature range [%d,%d) outside [0,%d)", start_pos, end_pos, v.d);
+    if (start_pos < 0 || end_pos > v.d || start_pos >= end_pos) return fir_fail_(FIR_ERR_ARG, "feature range [%d,%d) outside [0,%d)", start_pos, end_pos, v.d);
     if (qb == 0 || m == 0) return FIR_OK;
     const void* gal4 = nullptr;
     int dp4 = 0;
-    if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return dem_fail(FIR_ERR_STATE, "gallery has no tiled copy");
+    if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
     int32_t metric = 0;
     int rc = fir_gallery_info(g, nullptr, nullptr, &metric, nullptr);
     if (rc) return rc;
-    DEM_HIP(hipSetDevice(v.device));
+    FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
     // candidates per wave: 4 while the workgroup's 1 + 16 rows fit 64 KiB of LDS (d <= 960), else 1; rows beyond 2 048 features
@@ -556,7 +533,7 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
         FIR_ROWS_BY_METRIC(hq, hr, ho);
         hipLaunchKernelGGL(k_dem_ticket, dim3(1), dim3(1), 0, v.stream, tword, ticket);
         const hipError_t le = hipGetLastError();
-        if (le == hipSuccess && fir_gallery_wait_ticket_(g, (volatile uint64_t*)tword, ticket) == FIR_OK) {
+        if (le == hipSuccess && fir_wait_ticket_(v.stream, (volatile uint64_t*)tword, ticket) == FIR_OK) {
             std::memcpy(out, ho, rbytes);
             return FIR_OK;
         }
@@ -566,14 +543,14 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
     if ((rc = fir_gallery_scratch_(g, 8, (size_t)qb * v.d * 4, &dq))) return rc;
     if ((rc = fir_gallery_scratch_(g, 9, rbytes, &drows))) return rc;
     if ((rc = fir_gallery_scratch_(g, 10, rbytes, &dout))) return rc;
-    DEM_HIP(hipMemcpyAsync(dq, queries, (size_t)qb * v.d * 4, hipMemcpyHostToDevice, v.stream));
-    DEM_HIP(hipMemcpyAsync(drows, rows, rbytes, hipMemcpyHostToDevice, v.stream));
+    FIR_HIP(hipMemcpyAsync(dq, queries, (size_t)qb * v.d * 4, hipMemcpyHostToDevice, v.stream));
+    FIR_HIP(hipMemcpyAsync(drows, rows, rbytes, hipMemcpyHostToDevice, v.stream));
     FIR_ROWS_BY_METRIC((const float*)dq, (const int32_t*)drows, (float*)dout);
 #undef FIR_ROWS_BY_METRIC
 #undef FIR_ROWS_LAUNCH
-    DEM_HIP(hipGetLastError());
-    DEM_HIP(hipMemcpyAsync(out, dout, rbytes, hipMemcpyDeviceToHost, v.stream));
-    DEM_HIP(hipStreamSynchronize(v.stream));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(out, dout, rbytes, hipMemcpyDeviceToHost, v.stream));
+    FIR_HIP(hipStreamSynchronize(v.stream));
     return FIR_OK;
 }
 

@@ -24,9 +24,7 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -42,21 +40,6 @@ constexpr int kChunk = 32;        // PNNClassifier::delta_features_count, classi
 constexpr int kMaxJ = 64;
 constexpr int kPredBatch = 64;    // queries per launch (bounds the term scratch)
 
-thread_local char g_fpnn_err[512];
-int fpnn_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_fpnn_err, sizeof(g_fpnn_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_fpnn_err);
-    return code;
-}
-#define FPNN_HIP(expr)                                                                                         \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return fpnn_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,       \
-                                               "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 // FPNNClassifier::normalize, classification.cpp:637-659 (the active `#elif 1` arm + the clamp to [-0.5, 0.5]).
 __device__ __forceinline__ double fpnn_normalize(double x, double avg, double sd, double scale) {
@@ -280,9 +263,9 @@ namespace {
 // so a call is two launches and ONE synchronisation per batch, with no copy engine in between.
 int predict_common(fir_fpnn* h, const double* queries, int32_t qb, bool seq, float output_ratio, int32_t* best_class, float* outputs,
                    int32_t* chunks_out) {
-    if (!h || (qb > 0 && (!queries || !best_class))) return fpnn_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fpnn_fail(FIR_ERR_ARG, "qb < 0");
-    FPNN_HIP(hipSetDevice(h->device));
+    if (!h || (qb > 0 && (!queries || !best_class))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    FIR_HIP(hipSetDevice(h->device));
     const int nsub = (int)std::max<size_t>(1, std::min<size_t>(kChunk, (60 * 1024 - (size_t)h->C * 5) / ((size_t)h->C * 4)));
     const size_t lds = (size_t)h->C * 5 + (size_t)nsub * h->C * 4;
     double* pq = (double*)h->pin;
@@ -298,25 +281,17 @@ int predict_common(fir_fpnn* h, const double* queries, int32_t qb, bool seq, flo
         const int F = std::min(16, std::max(1, kBlock / h->C));   // features per workgroup of the term pass: about one term per thread
         hipLaunchKernelGGL(k_fpnn_terms, dim3((unsigned)((h->d + F - 1) / F), (unsigned)nq), dim3(kBlock), (size_t)F * 2 * h->J * 8, h->stream, pq,
                            h->d, h->C, h->J, F, h->avg.as<double>(), h->sd.as<double>(), h->scale, h->at.as<double>(), h->terms.as<float>());
-        FPNN_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         if (seq)
             hipLaunchKernelGGL(k_fpnn_predict<true>, dim3(nq), dim3(kBlock), lds, h->stream, h->d, h->C, h->terms.as<float>(), output_ratio, nsub, pbest, outputs ? pouts : nullptr, pchunks, one ? pticket : nullptr, ticket);
         else
             hipLaunchKernelGGL(k_fpnn_predict<false>, dim3(nq), dim3(kBlock), lds, h->stream, h->d, h->C, h->terms.as<float>(), output_ratio, nsub, pbest, outputs ? pouts : nullptr, pchunks, one ? pticket : nullptr, ticket);
-        FPNN_HIP(hipGetLastError());
+        FIR_HIP(hipGetLastError());
         if (one) {
-            // tens of microseconds: spin on the pinned ticket (2 ms at most), then fall back to the stream
-            volatile unsigned long long* flag = pticket;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (int spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket; ++spins) {
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                    FPNN_HIP(hipStreamSynchronize(h->stream));
-                    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != ticket) return fpnn_fail(FIR_ERR_HIP, "the result ticket was not published");
-                    break;
-                }
-            }
+            const int rc = fir_wait_ticket_(h->stream, (volatile uint64_t*)pticket, ticket);      // tens of microseconds: no stream synchronisation
+            if (rc) return rc;
         } else {
-            FPNN_HIP(hipStreamSynchronize(h->stream));
+            FIR_HIP(hipStreamSynchronize(h->stream));
         }
         std::memcpy(best_class + q0, pbest, (size_t)nq * 4);
         if (outputs) std::memcpy(outputs + (size_t)q0 * h->C, pouts, (size_t)nq * h->C * 4);
@@ -330,57 +305,57 @@ extern "C" {
 
 int fir_fpnn_train(const double* train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes, const double* avg,
                    const double* sd, double scale, int32_t device, fir_fpnn** out) {
-    if (!out) return fpnn_fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (nt <= 0 || d <= 0 || num_classes <= 0 || !train_rows || !train_class || !avg || !sd)
-        return fpnn_fail(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
-    if (nt >= ((int64_t)1 << 31) - 64) return fpnn_fail(FIR_ERR_ARG, "nt too large");
-    if ((size_t)num_classes * 9 > 60 * 1024) return fpnn_fail(FIR_ERR_ARG, "num_classes=%d exceeds the LDS score table (6826)", num_classes);
+        return fir_fail_(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
+    if (nt >= ((int64_t)1 << 31) - 64) return fir_fail_(FIR_ERR_ARG, "nt too large");
+    if ((size_t)num_classes * 9 > 60 * 1024) return fir_fail_(FIR_ERR_ARG, "num_classes=%d exceeds the LDS score table (6826)", num_classes);
     std::vector<int32_t> off((size_t)num_classes + 1, 0);
     for (int64_t t = 0; t < nt; ++t) {
         const int32_t cl = train_class[t];
         if (cl < 0 || cl >= num_classes || (t > 0 && cl < train_class[t - 1]))
-            return fpnn_fail(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
+            return fir_fail_(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
         off[(size_t)cl + 1]++;
     }
     for (int i = 0; i < num_classes; ++i) off[(size_t)i + 1] += off[(size_t)i];
     // classification.cpp:669-676: J = ceil(cbrt(training rows per class)), at least 3
     int J = (int)std::ceil(std::pow(1.0 * (double)nt / num_classes, 1.0 / 3));
     if (J <= 3) J = 3;
-    if (J > kMaxJ) return fpnn_fail(FIR_ERR_ARG, "J=%d harmonics exceed the supported %d", J, kMaxJ);
+    if (J > kMaxJ) return fir_fail_(FIR_ERR_ARG, "J=%d harmonics exceed the supported %d", J, kMaxJ);
     int cnt = 0;
     cnt = fir_device_count();        // the guarded first touch of the runtime (fir_runtime_init_)
-    if (cnt <= 0) return fpnn_fail(FIR_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fpnn_fail(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
+    if (cnt <= 0) return fir_fail_(FIR_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
     { const int rc0 = fir_runtime_init_(device); if (rc0) return rc0; }
     hipDeviceProp_t prop;
-    FPNN_HIP(hipGetDeviceProperties(&prop, device));
+    FIR_HIP(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fpnn_fail(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     fir_fpnn* h = new (std::nothrow) fir_fpnn();
-    if (!h) return fpnn_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!h) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     struct Guard { fir_fpnn* h; ~Guard() { if (h) fir_fpnn_destroy(h); } } guard{h};
     h->device = device; h->d = d; h->C = num_classes; h->J = J; h->scale = scale;
     const int K = 2 * J + 1;
-    FPNN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    FPNN_HIP(h->at.alloc((size_t)d * K * num_classes * 8));
-    FPNN_HIP(h->avg.alloc((size_t)d * 8));
-    FPNN_HIP(h->sd.alloc((size_t)d * 8));
-    FPNN_HIP(h->terms.alloc((size_t)kPredBatch * d * num_classes * 4));
-    FPNN_HIP(hipHostMalloc(&h->pin, (size_t)kPredBatch * ((size_t)d * 8 + (size_t)num_classes * 4 + 8) + 128, hipHostMallocDefault));
+    FIR_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    FIR_HIP(h->at.alloc((size_t)d * K * num_classes * 8));
+    FIR_HIP(h->avg.alloc((size_t)d * 8));
+    FIR_HIP(h->sd.alloc((size_t)d * 8));
+    FIR_HIP(h->terms.alloc((size_t)kPredBatch * d * num_classes * 4));
+    FIR_HIP(hipHostMalloc(&h->pin, (size_t)kPredBatch * ((size_t)d * 8 + (size_t)num_classes * 4 + 8) + 128, hipHostMallocDefault));
     std::memset((char*)h->pin + (size_t)kPredBatch * ((size_t)d * 8 + (size_t)num_classes * 4 + 8), 0, 128);
     Buf drows, doff;
-    FPNN_HIP(drows.alloc((size_t)nt * d * 8));
-    FPNN_HIP(doff.alloc(off.size() * 4));
-    FPNN_HIP(hipMemcpyAsync(drows.p, train_rows, (size_t)nt * d * 8, hipMemcpyHostToDevice, h->stream));
-    FPNN_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
-    FPNN_HIP(hipMemcpyAsync(h->avg.p, avg, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
-    FPNN_HIP(hipMemcpyAsync(h->sd.p, sd, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+    FIR_HIP(drows.alloc((size_t)nt * d * 8));
+    FIR_HIP(doff.alloc(off.size() * 4));
+    FIR_HIP(hipMemcpyAsync(drows.p, train_rows, (size_t)nt * d * 8, hipMemcpyHostToDevice, h->stream));
+    FIR_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    FIR_HIP(hipMemcpyAsync(h->avg.p, avg, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
+    FIR_HIP(hipMemcpyAsync(h->sd.p, sd, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
     const int64_t total = (int64_t)num_classes * J * d;
     hipLaunchKernelGGL(k_fpnn_train, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, drows.as<double>(), d,
                        doff.as<int32_t>(), num_classes, J, h->avg.as<double>(), h->sd.as<double>(), scale, h->at.as<double>());
-    FPNN_HIP(hipGetLastError());
-    FPNN_HIP(hipStreamSynchronize(h->stream));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipStreamSynchronize(h->stream));
     guard.h = nullptr;
     *out = h;
     return FIR_OK;
@@ -396,7 +371,7 @@ int fir_fpnn_destroy(fir_fpnn* h) {
 }
 
 int fir_fpnn_info(const fir_fpnn* h, int32_t* J, int32_t* d, int32_t* num_classes) {
-    if (!h) return fpnn_fail(FIR_ERR_ARG, "NULL handle");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "NULL handle");
     if (J) *J = h->J;
     if (d) *d = h->d;
     if (num_classes) *num_classes = h->C;
@@ -404,17 +379,17 @@ int fir_fpnn_info(const fir_fpnn* h, int32_t* J, int32_t* d, int32_t* num_classe
 }
 
 int fir_fpnn_get_model(fir_fpnn* h, double* a_out) {
-    if (!h || !a_out) return fpnn_fail(FIR_ERR_ARG, "NULL argument");
-    FPNN_HIP(hipSetDevice(h->device));
+    if (!h || !a_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(h->device));
     const int K = 2 * h->J + 1;
     const int64_t total = (int64_t)h->d * h->C * K;
     Buf da;
-    FPNN_HIP(da.alloc((size_t)total * 8));
+    FIR_HIP(da.alloc((size_t)total * 8));
     hipLaunchKernelGGL(k_fpnn_untranspose, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->at.as<double>(), h->d, h->C,
                        K, da.as<double>());
-    FPNN_HIP(hipGetLastError());
-    FPNN_HIP(hipMemcpyAsync(a_out, da.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
-    FPNN_HIP(hipStreamSynchronize(h->stream));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(a_out, da.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream));
+    FIR_HIP(hipStreamSynchronize(h->stream));
     return FIR_OK;
 }
 

@@ -21,7 +21,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -53,21 +52,6 @@ constexpr int kMinSampleRows = 8192;   // rows whose proxies seed tau: max(8192,
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-thread_local char g_gemm_err[512];
-int gemm_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_gemm_err, sizeof(g_gemm_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_gemm_err);
-    return code;
-}
-#define GEMM_HIP(expr)                                                                                         \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return gemm_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,       \
-                                               "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 // MFMA operand layout shared by gallery and queries ("fragment order"): for a block of 32 vectors
 // and a group kq of 8 features, lane l holds the float4
@@ -1311,21 +1295,21 @@ void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowm
 }
 
 int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos, int32_t rowmajor_mode, fir_gemm** out) {
-    if (!g || !out) return gemm_fail(FIR_ERR_ARG, "NULL argument");
+    if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (precision != FIR_GEMM_F32 && precision != FIR_GEMM_BF16_SPLIT && precision != FIR_GEMM_F16)
-        return gemm_fail(FIR_ERR_ARG, "bad precision %d", precision);
+        return fir_fail_(FIR_ERR_ARG, "bad precision %d", precision);
     *out = nullptr;
     fir_gemm* m = new (std::nothrow) fir_gemm();
-    if (!m) return gemm_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!m) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     m->g = g;
     const void* gp = nullptr;
-    if (fir_gallery_view_(g, &m->v) != FIR_OK || fir_gallery_tiled_(g, &gp, &m->dp4) != FIR_OK) { delete m; return gemm_fail(FIR_ERR_ARG, "bad gallery"); }
+    if (fir_gallery_view_(g, &m->v) != FIR_OK || fir_gallery_tiled_(g, &gp, &m->dp4) != FIR_OK) { delete m; return fir_fail_(FIR_ERR_ARG, "bad gallery"); }
     m->gal4 = (const float4*)gp;
     m->precision = precision;
     if (precision == FIR_GEMM_F16 && !(m->v.cus >= 8 && (m->v.cus & 7) == 0)) {     // (as fir_gemm_create_f64_; no gfx950 partition mode has such a count)
         const int cus = m->v.cus;
         delete m;
-        return gemm_fail(FIR_ERR_ARG, "the 16-row kernels want CUs in eights (%d)", cus);
+        return fir_fail_(FIR_ERR_ARG, "the 16-row kernels want CUs in eights (%d)", cus);
     }
     // a prefix [0, end_pos) of every row (the reference's "BF, 64" / "BF, 256" classifiers, ImageTesting.cpp:526-529): its own
     // fp16 fragments and row norms; whole 16-feature k-blocks, fp16 form only
@@ -1333,7 +1317,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     if (end_pos < 0 || end_pos > m->v.d || (m->feat != m->v.d && (m->feat % 16 != 0 || precision != FIR_GEMM_F16))) {
         const int dd = m->v.d;
         delete m;
-        return gemm_fail(FIR_ERR_ARG, "feature prefix [0,%d) of %d: multiples of 16 inside the row, fp16 form only", end_pos, dd);
+        return fir_fail_(FIR_ERR_ARG, "feature prefix [0,%d) of %d: multiples of 16 inside the row, fp16 form only", end_pos, dd);
     }
     if (const char* w = fir_knob_("FIR_GEMM_WIDE")) m->wide = std::atoi(w) != 0;   // experiments: 0 = one pass per gallery read
     m->dq8 = (m->feat + 31) / 32 * 4;     // feature groups of 8, padded to a multiple of 4 groups (zeros)
@@ -1384,7 +1368,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         if (m->fb_lds > kRerankLdsMax) {
             const int dd = m->v.d;
             fir_gemm_destroy(m);
-            return gemm_fail(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's exact fallback", dd);
+            return fir_fail_(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's exact fallback", dd);
         }
         if (e == hipSuccess && m->fb_lds > 48 * 1024)
             e = hipFuncSetAttribute((const void*)k_gemm_exact_fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
@@ -1401,7 +1385,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     {   // the re-rank keeps the query and up to kRerankGroup candidate rows in LDS
         const size_t row_bytes = (size_t)(m->dp4 + 1) * sizeof(float4);
         m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes > 1 ? kRerankLdsMax / row_bytes - 1 : 0);
-        if (m->rerank_group < 1) { delete m; return gemm_fail(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's re-rank", m->v.d); }
+        if (m->rerank_group < 1) { delete m; return fir_fail_(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's re-rank", m->v.d); }
         if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
             e = hipFuncSetAttribute((const void*)k_gemm_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
         if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
@@ -1464,7 +1448,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         if (e == hipSuccess) e = hipStreamSynchronize(m->v.stream);
     }
     if (e != hipSuccess) {
-        const int rc = gemm_fail(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "GEMM-path setup: %s", hipGetErrorString(e));
+        const int rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "GEMM-path setup: %s", hipGetErrorString(e));
         fir_gemm_destroy(m);
         return rc;
     }
@@ -1499,11 +1483,11 @@ int fir_gemm_destroy(fir_gemm* m) {
 // pass or, beyond its rounds, went straight to the exact device scan), out[2] = queries the exact device scan answered. The two
 // counters live on the device (fir_gemm_fb.h): this call waits for the device's work and reads them.
 int fir_gemm_stats_ex(const fir_gemm* m, int64_t out[3]) {
-    if (!m || !out) return gemm_fail(FIR_ERR_ARG, "NULL argument");
-    GEMM_HIP(hipSetDevice(m->v.device));
-    GEMM_HIP(hipDeviceSynchronize());
+    if (!m || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(m->v.device));
+    FIR_HIP(hipDeviceSynchronize());
     unsigned long long tot[2] = {0, 0};
-    GEMM_HIP(hipMemcpy(tot, m->fb_state + 4, sizeof tot, hipMemcpyDeviceToHost));
+    FIR_HIP(hipMemcpy(tot, m->fb_state + 4, sizeof tot, hipMemcpyDeviceToHost));
     out[0] = m->passes;
     out[1] = (int64_t)tot[0];
     out[2] = (int64_t)tot[1];
@@ -1516,11 +1500,11 @@ int fir_gemm_stats_ex(const fir_gemm* m, int64_t out[3]) {
 // a benchmark line: a bound of +inf with a million entries is a pass that never found its threshold, a finite one with a few
 // thousand a threshold that stayed loose.
 int fir_gemm_uncertified_notes(const fir_gemm* m, float out[32], int32_t* count) {
-    if (!m || !out || !count) return gemm_fail(FIR_ERR_ARG, "NULL argument");
-    GEMM_HIP(hipSetDevice(m->v.device));
-    GEMM_HIP(hipDeviceSynchronize());
+    if (!m || !out || !count) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(m->v.device));
+    FIR_HIP(hipDeviceSynchronize());
     int h[kFbStateWords];
-    GEMM_HIP(hipMemcpy(h, m->fb_state, sizeof h, hipMemcpyDeviceToHost));
+    FIR_HIP(hipMemcpy(h, m->fb_state, sizeof h, hipMemcpyDeviceToHost));
     *count = h[2] < 8 ? h[2] : 8;
     std::memcpy(out, h + 8, 32 * sizeof(float));
     return FIR_OK;
@@ -1565,7 +1549,7 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
     for (int r = 0; r < k; ++r)
         hipLaunchKernelGGL(k_gemm_exact_fb, dim3(m->fb_grid), dim3(256), m->fb_lds, st, m->gal4, n, m->dp4, d, m->v.row_offset, d_queries, qs, (const int*)m->fb_state,
                            (const int*)m->fb_list2, (unsigned long long*)d_keys, k, r);
-    GEMM_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
 
@@ -1627,15 +1611,15 @@ static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
 // the per-call buffers of the uncertified-query lists (and the certificate flags), grown to the largest call seen
 static int gemm_fb_reserve_(fir_gemm* m, int32_t qb) {
     if ((size_t)qb <= m->ok_cap) return FIR_OK;
-    GEMM_HIP(hipDeviceSynchronize());                        // (an earlier call's kernels may still read the old ones)
+    FIR_HIP(hipDeviceSynchronize());                        // (an earlier call's kernels may still read the old ones)
     (void)hipFree(m->ok); (void)hipFree(m->fb_list); (void)hipFree(m->fb_list2); (void)hipFree(m->fb_tau2);
     m->ok = nullptr; m->fb_list = nullptr; m->fb_list2 = nullptr; m->fb_tau2 = nullptr;
     m->ok_cap = 0;
     const size_t cap = (size_t)std::max(qb, 1024);
-    GEMM_HIP(hipMalloc((void**)&m->ok, cap * sizeof(int)));
-    GEMM_HIP(hipMalloc((void**)&m->fb_list, cap * sizeof(int)));
-    GEMM_HIP(hipMalloc((void**)&m->fb_list2, cap * sizeof(int)));
-    GEMM_HIP(hipMalloc((void**)&m->fb_tau2, cap * sizeof(float)));
+    FIR_HIP(hipMalloc((void**)&m->ok, cap * sizeof(int)));
+    FIR_HIP(hipMalloc((void**)&m->fb_list, cap * sizeof(int)));
+    FIR_HIP(hipMalloc((void**)&m->fb_list2, cap * sizeof(int)));
+    FIR_HIP(hipMalloc((void**)&m->fb_tau2, cap * sizeof(float)));
     m->ok_cap = cap;
     return FIR_OK;
 }
@@ -1648,21 +1632,21 @@ static int gemm_reserve_(fir_gemm* m, const GemmCall& c) {
     if (rcr) return rcr;
     const int need = (std::min(c.sbq, c.qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
     if (need > m->lists_cap) {
-        GEMM_HIP(hipStreamSynchronize(c.st));
-        GEMM_HIP(hipStreamSynchronize(m->side));
+        FIR_HIP(hipStreamSynchronize(c.st));
+        FIR_HIP(hipStreamSynchronize(m->side));
         for (int b = 0; b < 2; ++b) {
             (void)hipFree(m->lists[b]); (void)hipFree(m->counts[b]);
             m->lists[b] = nullptr; m->counts[b] = nullptr;
         }
         m->lists_cap = 0;
         for (int b = 0; b < 2; ++b) {
-            GEMM_HIP(hipMalloc((void**)&m->lists[b], (size_t)need * kListCap * sizeof(unsigned long long)));
-            GEMM_HIP(hipMalloc((void**)&m->counts[b], (size_t)need * sizeof(int)));
+            FIR_HIP(hipMalloc((void**)&m->lists[b], (size_t)need * kListCap * sizeof(unsigned long long)));
+            FIR_HIP(hipMalloc((void**)&m->counts[b], (size_t)need * sizeof(int)));
         }
         m->lists_cap = need;
     }
     if (m->precision != FIR_GEMM_F16 && !m->sample)
-        GEMM_HIP(hipMalloc((void**)&m->sample, (size_t)kPasses * kQT * m->sample_rows * sizeof(float)));
+        FIR_HIP(hipMalloc((void**)&m->sample, (size_t)kPasses * kQT * m->sample_rows * sizeof(float)));
     return FIR_OK;
 }
 
@@ -1684,7 +1668,7 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
                        m->qbf[b], c.qs);
     if (adaptive) return FIR_OK;
     const int sub_stride = k > 1 ? kPasses * kQT : 0;      // top-K: the sample as kRtSubsets subset minima per query
-    GEMM_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
+    FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
     // every rb_stride-th row block: the sample is spread over the whole gallery
     const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
     const int rb_stride = (int)std::max<int64_t>(1, ((c.n + 31) / 32) / sample_blocks);
@@ -1711,7 +1695,7 @@ static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, i
     const float* dq = c.sb_first(sb);
     const int sample_rows = m->sample_rows, sample_grid = (sample_rows + 63) / 64;
     hipLaunchKernelGGL(k_gemm_qnorm, dim3(np * kQT), dim3(64), 0, ps, dq, nq, c.d, m->qnorm[b]);
-    GEMM_HIP(hipMemsetAsync(m->counts[b], 0, (size_t)np * kQT * sizeof(int), ps));
+    FIR_HIP(hipMemsetAsync(m->counts[b], 0, (size_t)np * kQT * sizeof(int), ps));
     if (m->precision == FIR_GEMM_F32) {
         hipLaunchKernelGGL(k_gemm_pack_queries, dim3(((kQT / 32) * m->dq8 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dq8, m->qm[b]);
         hipLaunchKernelGGL(k_gemm_proxy<0>, dim3(sample_grid, np), dim3(128), c.lds, ps, m->gm, m->gnorm, m->qm[b], c.n, (int64_t)0,
@@ -1731,17 +1715,17 @@ static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, i
 static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
     hipStream_t ps = c.serial_prep ? c.st : m->side;
     const int b = sb & 1;
-    if (c.serial_prep && sb >= 2) GEMM_HIP(hipStreamWaitEvent(c.st, m->rerank_done[b], 0));      // the re-rank of sb - 2 read this buffer
+    if (c.serial_prep && sb >= 2) FIR_HIP(hipStreamWaitEvent(c.st, m->rerank_done[b], 0));      // the re-rank of sb - 2 read this buffer
     if (c.h_queries) {
         const size_t off = (size_t)sb * c.sbq * c.qs;
-        GEMM_HIP(hipMemcpyAsync((void*)(c.d_queries + off), c.h_queries + off, (size_t)c.sb_queries(sb) * c.qs * sizeof(float), hipMemcpyHostToDevice, m->copy));
-        GEMM_HIP(hipEventRecord(m->copy_done[b], m->copy));
-        GEMM_HIP(hipStreamWaitEvent(ps, m->copy_done[b], 0));
+        FIR_HIP(hipMemcpyAsync((void*)(c.d_queries + off), c.h_queries + off, (size_t)c.sb_queries(sb) * c.qs * sizeof(float), hipMemcpyHostToDevice, m->copy));
+        FIR_HIP(hipEventRecord(m->copy_done[b], m->copy));
+        FIR_HIP(hipStreamWaitEvent(ps, m->copy_done[b], 0));
     }
     const int rc = m->precision == FIR_GEMM_F16 ? gemm_prep_f16_(m, c, ps, sb) : gemm_prep_f32_bf16_(m, c, ps, sb);
     if (rc) return rc;
-    GEMM_HIP(hipGetLastError());
-    GEMM_HIP(hipEventRecord(m->prep_done[b], ps));
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipEventRecord(m->prep_done[b], ps));
     return FIR_OK;
 }
 
@@ -1833,9 +1817,9 @@ static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs)
 static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
     const int last = c.nsb - 1, b = last & 1;
     if (!m->dump_phases.empty()) {                     // with FIR_GEMM_DBG_SKIP=256: the load-burst timestamps of the first pair
-        GEMM_HIP(hipStreamSynchronize(c.st));
+        FIR_HIP(hipStreamSynchronize(c.st));
         std::vector<unsigned long long> h(8 * 256);
-        GEMM_HIP(hipMemcpy(h.data(), m->lists[b] + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(h.data(), m->lists[b] + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(m->dump_phases.c_str(), "w")) {
             for (int w = 0; w < 8; ++w)
                 for (int u = 0; u < 240; ++u) std::fprintf(f, "%d %d %llu %llu\n", w, u, h[(size_t)w * 256 + u] >> 20, h[(size_t)w * 256 + u] & 0xFFFFFull);
@@ -1843,17 +1827,17 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
         }
     }
     if (m->debug_counts) {                             // appended rows per query
-        GEMM_HIP(hipStreamSynchronize(c.st));
+        FIR_HIP(hipStreamSynchronize(c.st));
         const int nql = c.sb_queries(last);
         std::vector<int> hc((size_t)nql), h_ok((size_t)nql);
-        GEMM_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
-        GEMM_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)last * c.sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)last * c.sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
         long long sum = 0;
         int mx = 0, bad = 0;
         for (int v : hc) { sum += v; mx = std::max(mx, v); }
         for (int v : h_ok) bad += v ? 0 : 1;
         std::vector<float> ht((size_t)nql);
-        GEMM_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
         double ts = 0;
         int ninf = 0;
         for (float v : ht) { if (v < 1e30f) ts += v; else ++ninf; }
@@ -1866,18 +1850,18 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
 
 // The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev)
 static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr) {
-    if (!m || !d_keys || (qb > 0 && !d_queries)) return gemm_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return gemm_fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kTopKMax) return gemm_fail(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kTopKMax);
+    if (!m || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > kTopKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kTopKMax);
     if (qb == 0) return FIR_OK;
-    GEMM_HIP(hipSetDevice(m->v.device));
+    FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);   // this state's scratch, and the gallery's, is shared with every other call on the gallery
     if (order.rc) return order.rc;
     GemmCall c;
     c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
     c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
-    if (c.n == 0 && h_queries) GEMM_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
+    if (c.n == 0 && h_queries) FIR_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
     if (c.n == 0)
         return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
                       : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
@@ -1904,10 +1888,10 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     int rc = gemm_reserve_(m, c);
     if (rc) return rc;
     // this call's two list lengths (the fp16 form clears them in the first super-batch's query preparation: one launch less per call)
-    if (m->precision != FIR_GEMM_F16) GEMM_HIP(hipMemsetAsync(m->fb_state, 0, 2 * sizeof(int), st));
+    if (m->precision != FIR_GEMM_F16) FIR_HIP(hipMemsetAsync(m->fb_state, 0, 2 * sizeof(int), st));
     if (!c.one_stream) {
-        GEMM_HIP(hipEventRecord(m->queries_ready, st));
-        GEMM_HIP(hipStreamWaitEvent(m->side, m->queries_ready, 0));
+        FIR_HIP(hipEventRecord(m->queries_ready, st));
+        FIR_HIP(hipStreamWaitEvent(m->side, m->queries_ready, 0));
     }
     // order on `side` when it prepares: prep(0) prep(1) rerank(0) prep(2) rerank(1) ...
     if ((rc = gemm_prep_(m, c, 0))) return rc;
@@ -1915,19 +1899,19 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
         const int b = sb & 1;
         if (c.serial_prep) { if (sb >= 1 && (rc = gemm_prep_(m, c, sb))) return rc; }
         else if (sb + 1 < c.nsb && (rc = gemm_prep_(m, c, sb + 1))) return rc;
-        GEMM_HIP(hipStreamWaitEvent(st, m->prep_done[b], 0));
+        FIR_HIP(hipStreamWaitEvent(st, m->prep_done[b], 0));
         if (m->precision == FIR_GEMM_F16) { if ((rc = gemm_pass_f16_(m, c, sb))) return rc; }
         else gemm_pass_f32_bf16_(m, c, sb);
-        GEMM_HIP(hipEventRecord(m->main_done[b], st));
+        FIR_HIP(hipEventRecord(m->main_done[b], st));
         // on the side stream, the re-rank runs under the next super-batch's full passes
         hipStream_t rs = c.one_stream ? st : m->side;
-        if (!c.one_stream) GEMM_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
+        if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
         gemm_rerank_(m, c, sb, rs);
-        GEMM_HIP(hipEventRecord(m->rerank_done[b], rs));
+        FIR_HIP(hipEventRecord(m->rerank_done[b], rs));
         m->passes += (c.sb_queries(sb) + kQT - 1) / kQT;
     }
-    if (!c.one_stream) GEMM_HIP(hipStreamWaitEvent(st, m->rerank_done[(c.nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
-    GEMM_HIP(hipGetLastError());
+    if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(st, m->rerank_done[(c.nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
+    FIR_HIP(hipGetLastError());
 #ifdef FIR_AUDIT
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
@@ -1951,10 +1935,10 @@ int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t q
 // 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one
 // window of the smallest proxy of ALL rows, exact re-rank, certificate; everything on `stream`, one synchronisation.
 int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, uint64_t* d_keys, void* stream) {
-    if (!m || !d_keys || !d_queries) return gemm_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 1 || qb > 8) return gemm_fail(FIR_ERR_ARG, "qb=%d outside [1,8]", qb);
-    if (m->precision != FIR_GEMM_F16) return gemm_fail(FIR_ERR_ARG, "the few-query form needs the fp16 copy");
-    GEMM_HIP(hipSetDevice(m->v.device));
+    if (!m || !d_keys || !d_queries) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 1 || qb > 8) return fir_fail_(FIR_ERR_ARG, "qb=%d outside [1,8]", qb);
+    if (m->precision != FIR_GEMM_F16) return fir_fail_(FIR_ERR_ARG, "the few-query form needs the fp16 copy");
+    FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);
     if (order.rc) return order.rc;
@@ -1963,10 +1947,10 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (n == 0) return fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, d, d_keys, st);
     const int nqt = qb <= 1 ? 1 : qb <= 2 ? 2 : qb <= 4 ? 4 : 8;
     if (nqt > m->proxies_nq) {
-        if (m->proxies) GEMM_HIP(hipFree(m->proxies));
+        if (m->proxies) FIR_HIP(hipFree(m->proxies));
         m->proxies = nullptr;
         m->proxies_nq = 0;
-        GEMM_HIP(hipMalloc((void**)&m->proxies, (size_t)nqt * n * sizeof(float)));     // (FIR_ERR_NOMEM: the caller takes the exact scan)
+        FIR_HIP(hipMalloc((void**)&m->proxies, (size_t)nqt * n * sizeof(float)));     // (FIR_ERR_NOMEM: the caller takes the exact scan)
         m->proxies_nq = nqt;
     }
     if (m->lists_cap < 2 * kQT) {
@@ -1976,8 +1960,8 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
         }
         m->lists_cap = 0;
         for (int bb = 0; bb < 2; ++bb) {
-            GEMM_HIP(hipMalloc((void**)&m->lists[bb], (size_t)2 * kQT * kListCap * sizeof(unsigned long long)));
-            GEMM_HIP(hipMalloc((void**)&m->counts[bb], (size_t)2 * kQT * sizeof(int)));
+            FIR_HIP(hipMalloc((void**)&m->lists[bb], (size_t)2 * kQT * kListCap * sizeof(unsigned long long)));
+            FIR_HIP(hipMalloc((void**)&m->counts[bb], (size_t)2 * kQT * sizeof(int)));
         }
         m->lists_cap = 2 * kQT;
     }
@@ -2007,7 +1991,7 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0};
     hipLaunchKernelGGL(k_gemm_rerank, dim3(qb), dim3(64), (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4), st, m->lists[b], m->counts[b], m->tau[b], m->gal4,
                        d_queries, m->qnorm[b], m->gmax, n, d, m->dp4, m->v.row_offset, e_rel, m->rerank_group, (unsigned long long*)d_keys, m->ok, qs, m->rowmajor, fb);
-    GEMM_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     m->passes += 1;
     // (the bound of this form already is the smallest proxy of ALL rows + one window: a second pass could not do better; what is
     // not certified -- NaN operands, thousands of ties -- goes to the exact device scan, in stream order)
@@ -2017,7 +2001,7 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
 // Host-pointer form for fir_search_top1 / fir_search_topk: h_queries -> d_stage (qb rows of the gallery's length) super-batch by
 // super-batch, under the full passes of the one before; keys as the device-pointer forms.
 int fir_gemm_search_staged_(fir_gemm* m, const float* h_queries, float* d_stage, int32_t qb, int32_t k, uint64_t* d_keys, void* stream) {
-    if (!h_queries || !d_stage) return gemm_fail(FIR_ERR_ARG, "NULL argument");
+    if (!h_queries || !d_stage) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     return gemm_search(m, d_stage, qb, k, d_keys, stream, h_queries);
 }
 

@@ -309,14 +309,14 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_f64(const unsigned long long
 // The nomination state of a float64 training set that lives elsewhere (fir_cls.hip owns gal2): fp16 fragments, row norms, one scratch
 // set. A fir_gemm with f64 = true; only fir_gemm_knn_f64_ and fir_gemm_destroy take it.
 extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const void* gal2v, int64_t nt, int d, int dp2, fir_gemm** out) {
-    if (!out || !gal2v || nt <= 0 || d <= 0) return gemm_fail(FIR_ERR_ARG, "bad argument");
+    if (!out || !gal2v || nt <= 0 || d <= 0) return fir_fail_(FIR_ERR_ARG, "bad argument");
     *out = nullptr;
-    if (!(cus >= 8 && (cus & 7) == 0)) return gemm_fail(FIR_ERR_ARG, "the 16-row kernels want CUs in eights (%d)", cus);
+    if (!(cus >= 8 && (cus & 7) == 0)) return fir_fail_(FIR_ERR_ARG, "the 16-row kernels want CUs in eights (%d)", cus);
     const size_t row_lds = (size_t)dp2 * sizeof(double2);              // the re-rank keeps the centred query in LDS
     const int ngroup = 1;
-    if (row_lds > kRerankLdsMax) return gemm_fail(FIR_ERR_ARG, "rows of %d float64 features are too long for the matrix-core path's re-rank", d);
+    if (row_lds > kRerankLdsMax) return fir_fail_(FIR_ERR_ARG, "rows of %d float64 features are too long for the matrix-core path's re-rank", d);
     fir_gemm* m = new (std::nothrow) fir_gemm();
-    if (!m) return gemm_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!m) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     m->f64 = true;
     m->gal2 = (const double2*)gal2v;
     m->dp2 = dp2;
@@ -364,7 +364,7 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess) {
-        const int rc = gemm_fail(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "float64 matrix-core state: %s", hipGetErrorString(e));
+        const int rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "float64 matrix-core state: %s", hipGetErrorString(e));
         m->v.stream = nullptr;
         fir_gemm_destroy(m);
         return rc;
@@ -377,9 +377,9 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
 // *kernel_name (may be NULL) <- the dominant kernel. The caller turns rows into class votes and sends what is not settled to the exact scan.
 extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, int32_t kp, int32_t* d_rows, double* d_dist, int32_t* d_ok, void* stream,
                                  const char** kernel_name, double* flops_per_launch, hipEvent_t* ev_pair) {
-    if (!m || !m->f64 || !d_qc || !d_rows || !d_dist || !d_ok) return gemm_fail(FIR_ERR_ARG, "bad argument");
-    if (kp < 1 || kp > 8 || qb < 1) return gemm_fail(FIR_ERR_ARG, "kp=%d qb=%d", kp, qb);
-    GEMM_HIP(hipSetDevice(m->v.device));
+    if (!m || !m->f64 || !d_qc || !d_rows || !d_dist || !d_ok) return fir_fail_(FIR_ERR_ARG, "bad argument");
+    if (kp < 1 || kp > 8 || qb < 1) return fir_fail_(FIR_ERR_ARG, "kp=%d qb=%d", kp, qb);
+    FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     const int d = m->feat;
     const int64_t n = m->v.n;
@@ -391,12 +391,12 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
     {
         const int need = (std::min(sbq, qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
         if (need > m->lists_cap) {
-            GEMM_HIP(hipStreamSynchronize(st));
+            FIR_HIP(hipStreamSynchronize(st));
             (void)hipFree(m->lists[0]); (void)hipFree(m->counts[0]);
             m->lists[0] = nullptr; m->counts[0] = nullptr;
             m->lists_cap = 0;
-            GEMM_HIP(hipMalloc((void**)&m->lists[0], (size_t)need * kListCap * sizeof(unsigned long long)));
-            GEMM_HIP(hipMalloc((void**)&m->counts[0], (size_t)need * sizeof(int)));
+            FIR_HIP(hipMalloc((void**)&m->lists[0], (size_t)need * kListCap * sizeof(unsigned long long)));
+            FIR_HIP(hipMalloc((void**)&m->counts[0], (size_t)need * sizeof(int)));
             m->lists_cap = need;
         }
     }
@@ -418,7 +418,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         {
             // the row sample: the smallest (K'-th of 64 subsets' smallest) sampled proxy + one window is the sample flow's bound and the
             // adaptive pass's start value (k_gemm_seed_T)
-            GEMM_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, st));
+            FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, st));
             const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
             const int rb_stride = (int)std::max<int64_t>(1, ((n + 31) / 32) / sample_blocks);
             for (int p0 = 0; p0 < pairs;) {
@@ -441,7 +441,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
             const int P = launch_pairs_(pairs - p0, share_cap);
             const size_t qo = (size_t)p0;
             const int nt_flag = P <= 1 ? 1 : 0;
-            if (ev_pair && first) GEMM_HIP(hipEventRecord(ev_pair[0], st));
+            if (ev_pair && first) FIR_HIP(hipEventRecord(ev_pair[0], st));
             if (adaptive)
                 hipLaunchKernelGGL(pick_x(kp > 1 ? 4 : 3, streamed, odd), dim3(grid, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT,
                                    n, (int64_t)0, n, m->dk16, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->qnorm[b] + qo * 2 * kQT, 0,
@@ -451,7 +451,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
                                    (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, (float*)nullptr, 0, P, nt_flag, 1,
                                    (unsigned int*)nullptr, 0);
             if (ev_pair && first) {
-                GEMM_HIP(hipEventRecord(ev_pair[1], st));
+                FIR_HIP(hipEventRecord(ev_pair[1], st));
                 if (flops_per_launch) *flops_per_launch = 2.0 * (double)n * d * 128.0 * P;
                 if (kernel_name) *kernel_name = find_x(adaptive ? (kp > 1 ? 4 : 3) : 1, streamed, odd).name;
                 first = false;
@@ -465,12 +465,12 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         m->passes += np;
 #ifdef FIR_AUDIT
         if (m->debug_counts) {      // audit builds: appended rows / certified queries of this super-batch (synchronises)
-            GEMM_HIP(hipStreamSynchronize(st));
+            FIR_HIP(hipStreamSynchronize(st));
             std::vector<int> hc((size_t)nq), hok((size_t)nq);
             std::vector<float> ht((size_t)nq);
-            GEMM_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-            GEMM_HIP(hipMemcpy(hok.data(), d_ok + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-            GEMM_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+            FIR_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+            FIR_HIP(hipMemcpy(hok.data(), d_ok + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+            FIR_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
             long long sum = 0; int mx = 0, over = 0, bad = 0;
             for (int i = 0; i < nq; ++i) { sum += hc[i]; mx = std::max(mx, hc[i]); over += hc[i] > kListCap; bad += hok[i] ? 0 : 1; }
             std::fprintf(stderr, "fir_gemm f64: %d queries (adaptive %d, K' %d): appended mean %.1f max %d, %d lists over %d, %d uncertified; tau[0..3] %g %g %g %g\n", nq, (int)adaptive, kp,
@@ -478,6 +478,6 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         }
 #endif
     }
-    GEMM_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     return FIR_OK;
 }

@@ -3,7 +3,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/fir_amd.h"
+
 struct fir_gallery;
+
+// The library's one error path: formats the message straight into the (thread-local) buffer fir_last_error() reads and returns `code`.
+extern "C" int fir_fail_(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define FIR_HIP(expr)                                                                                                  \
+    do {                                                                                                               \
+        hipError_t e_ = (expr);                                                                                        \
+        if (e_ != hipSuccess) return fir_fail_(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,               \
+                                               "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
 
 // Read-only view of a gallery handle for the other translation units (fir_twd.hip).
 struct fir_gallery_view {
@@ -49,7 +60,7 @@ struct FirOnExit {
 };
 template <typename F>
 FirOnExit<F> fir_on_exit(F f) { return FirOnExit<F>{f}; }
-extern "C" void fir_set_last_error_(const char* msg);
+extern "C" void fir_set_last_error_(const char* msg);    // a message kept aside earlier (fir_shard.hip: another rank's or worker's error)
 // Every environment knob the library honours goes through here: getenv(name), and a set one is remembered (once) in the list
 // fir_gallery_last_dispatch reports in fir_dispatch_info::knobs -- a stray variable in a production environment is visible.
 // The knobs that can change ANSWERS (FIR_GEMM_EREL_SCALE, FIR_GEMM_DBG_SKIP, FIR_GEMM_ADAPT_DBG, fir_shard_opts.fail_*) exist
@@ -59,7 +70,8 @@ extern "C" int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4); 
 
 // Device scratch owned by the gallery handle: `slot` in [0, 24), grown on demand, kept until the gallery is destroyed
 // (the per-call hipMalloc / hipFree pairs of the classifier entry points cost more than their kernels on small galleries).
-// Slots 0-7 and 16: fir_twd.hip, 8-11: fir_dem.hip, 12-15, 17 and 18: fir_capi.hip (17, 18: top_classes_dev); 19-23 are free.
+// Slots 0-7 and 16: fir_twd.hip (0 queries, 1 conventional distance tables, 2 k_twd_prop_fused state, 3 verdicts, 4-6 proposed chunk
+// distances / sums / alive flags, 7 segment records of either staged form, 16 k_twd_conv_fused state), 8-11: fir_dem.hip, 12-15, 17 and 18: fir_capi.hip (17, 18: top_classes_dev); 19-23 are free.
 extern "C" int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out);
 // Per-handle call counters of the other translation units (slot 0: fir_twd.hip's fused classifier): returns the value before the increment.
 extern "C" uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot);
@@ -79,13 +91,15 @@ extern "C" int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, 
 // testRecognitionMethod), so the start-up runs on a private random state and the caller's is handed back untouched.
 extern "C" int fir_runtime_init_(int device);
 
-// Small host-pointer calls of the other translation units, without copy engine and without stream synchronisation: the
-// handle's pinned, device-visible buffer (queries go in at `base`, up to *query_bytes; results come back at *results, 4096
-// eight-byte words), a fresh ticket number, and the wait for the word a call's last kernel writes it to (spins for 2 ms,
-// then synchronises the stream). See fir_search_top1 in fir_capi.hip.
+// Small host-pointer calls, without copy engine and without stream synchronisation: the kernels read the queries from pinned,
+// device-visible host memory and the call's last kernel writes the results there, then a ticket number the host is waiting for.
+// fir_wait_ticket_ is that wait for every translation unit (galleries, fir_cls, fir_dem, fir_fpnn, the TWD drivers): it spins on
+// the pinned word for 2 ms at most (the clock is read every 1024 spins), then synchronises `st`, which lets the runtime report a
+// failed launch, and looks once more. A gallery handle lends its pinned buffer to the other translation units: queries go in at
+// `base`, up to *query_bytes; results come back at *results, 4096 eight-byte words; tickets come from fir_gallery_next_ticket_.
+extern "C" int fir_wait_ticket_(hipStream_t st, volatile uint64_t* flag, uint64_t ticket);
 extern "C" int fir_gallery_pin_(fir_gallery* g, void** base, size_t* query_bytes, uint64_t** results);
 extern "C" uint64_t fir_gallery_next_ticket_(fir_gallery* g);
-extern "C" int fir_gallery_wait_ticket_(fir_gallery* g, volatile uint64_t* flag, uint64_t ticket);
 
 // The exact streaming scan whatever the batch size (fir_search_top1_keys_dev may route large L2 batches through fir_gemm_*,
 // whose uncertified queries must not come back to it).

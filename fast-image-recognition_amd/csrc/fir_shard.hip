@@ -39,7 +39,6 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -56,25 +55,10 @@ namespace {
 
 using fir::kKeyNone;
 
-thread_local char g_sh_err[512];
-int sh_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_sh_err, sizeof(g_sh_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_sh_err);
-    return code;
-}
-#define SH_HIP(expr)                                                                                                   \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return sh_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
-                                             hipGetErrorString(e_), __FILE__, __LINE__);                               \
-    } while (0)
 #define SH_NCCL(expr)                                                                                                  \
     do {                                                                                                               \
         ncclResult_t r_ = (expr);                                                                                      \
-        if (r_ != ncclSuccess) return sh_fail(FIR_ERR_COMM, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); \
+        if (r_ != ncclSuccess) return fir_fail_(FIR_ERR_COMM, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), __FILE__, __LINE__); \
     } while (0)
 
 // keys[q] = min over parts p of parts[p][q]   (the shards of one device, before the RCCL call)
@@ -217,11 +201,11 @@ struct Health {
 template <typename T>
 int grow_dev(T*& p, size_t& cap, size_t need) {
     if (need <= cap) return FIR_OK;
-    if (p) SH_HIP(hipFree(p));
+    if (p) FIR_HIP(hipFree(p));
     p = nullptr;
     cap = 0;
     const size_t want = std::max<size_t>(need, 1024);
-    SH_HIP(hipMalloc((void**)&p, want * sizeof(T)));
+    FIR_HIP(hipMalloc((void**)&p, want * sizeof(T)));
     cap = want;
     return FIR_OK;
 }
@@ -229,7 +213,7 @@ int grow_dev(T*& p, size_t& cap, size_t need) {
 int peer_failed(int code) {
     const char* what = code == FIR_ERR_NOMEM ? "allocation failed" : code == FIR_ERR_HIP ? "a HIP call failed" : code == FIR_ERR_COMM ? "an RCCL call failed"
                                                                                                                                     : "its step failed";
-    return sh_fail(code < 0 ? code : FIR_ERR_COMM, "a rank of the sharded handle reported an error (%s): the call fails on every rank and the handle is closed for further calls", what);
+    return fir_fail_(code < 0 ? code : FIR_ERR_COMM, "a rank of the sharded handle reported an error (%s): the call fails on every rank and the handle is closed for further calls", what);
 }
 
 // Abort this device's communicator (a blocked collective returns) and mark the handle dead.
@@ -237,7 +221,7 @@ int comm_dead(DevCtx& dc, Health& hl, int code, const char* why) {
     hl.dead = true;
     hl.dead_code = code;
     if (dc.comm) { (void)ncclCommAbort(dc.comm); dc.comm = nullptr; }
-    return sh_fail(code, "sharded handle: %s; the communicator was aborted and the handle is closed for further calls", why);
+    return fir_fail_(code, "sharded handle: %s; the communicator was aborted and the handle is closed for further calls", why);
 }
 
 // hipStreamSynchronize with a bound: polls the stream and the communicator's asynchronous error state.
@@ -283,7 +267,7 @@ int wait_event(DevCtx& dc, hipEvent_t ev, Health& hl) {
 
 // Every rank contributes its local status (FIR_OK or a negative FIR_ERR_*); all of them get the minimum.
 int agree(DevCtx& dc, hipStream_t st, Health& hl, int local_rc, int* agreed) {
-    if (!dc.comm) return sh_fail(FIR_ERR_STATE, "sharded handle: no communicator");
+    if (!dc.comm) return fir_fail_(FIR_ERR_STATE, "sharded handle: no communicator");
     dc.h_status[0] = local_rc;
     hipError_t e = hipMemcpyAsync(dc.status, dc.h_status, sizeof(int32_t), hipMemcpyHostToDevice, st);
     ncclResult_t nr = e == hipSuccess ? ncclAllReduce(dc.status, dc.status, 1, ncclInt32, ncclMin, dc.comm, st) : ncclSuccess;
@@ -300,7 +284,7 @@ int agree(DevCtx& dc, hipStream_t st, Health& hl, int local_rc, int* agreed) {
 // rank), `alloc` tries the allocations. Everyone leaves with the same verdict.
 int grow_agreed(DevCtx& dc, hipStream_t st, Health& hl, bool need, bool inject, const std::function<int()>& alloc) {
     if (!need) return FIR_OK;
-    int r = inject ? sh_fail(FIR_ERR_NOMEM, "injected allocation failure (fir_shard_opts.fail_step = 2)") : alloc();
+    int r = inject ? fir_fail_(FIR_ERR_NOMEM, "injected allocation failure (fir_shard_opts.fail_step = 2)") : alloc();
     char mine[512];
     if (r) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); mine[sizeof(mine) - 1] = 0; }
     int all = FIR_OK;
@@ -378,18 +362,18 @@ int run_all(std::vector<DevCtx>& devs, const std::function<int(int)>& fn) {
 
 int ensure_pin(fir_sharded* h, size_t bytes) {
     if (bytes <= h->pin_cap) return FIR_OK;
-    if (h->pin) SH_HIP(hipHostFree(h->pin));
+    if (h->pin) FIR_HIP(hipHostFree(h->pin));
     h->pin = nullptr;
     h->pin_cap = 0;
     const size_t want = std::max<size_t>(bytes, 1 << 20);
-    SH_HIP(hipHostMalloc(&h->pin, want, hipHostMallocPortable));
+    FIR_HIP(hipHostMalloc(&h->pin, want, hipHostMallocPortable));
     h->pin_cap = want;
     return FIR_OK;
 }
 
 int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
     if (end == 0) end = h->d;
-    if (start < 0 || end > h->d || start >= end) return sh_fail(FIR_ERR_ARG, "feature range [%d,%d) not inside [0,%d)", start, end, h->d);
+    if (start < 0 || end > h->d || start >= end) return fir_fail_(FIR_ERR_ARG, "feature range [%d,%d) not inside [0,%d)", start, end, h->d);
     return FIR_OK;
 }
 
@@ -429,7 +413,7 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
     for (size_t i = 0; i < dc.shards.size(); ++i) {
         Shard& s = h->shards[dc.shards[i]];
         if (h->health.fail_step == 1 && h->health.fail_shard - 1 == dc.shards[i])
-            return sh_fail(FIR_ERR_NOMEM, "injected scan failure on shard %d (fir_shard_opts.fail_step = 1)", dc.shards[i]);
+            return fir_fail_(FIR_ERR_NOMEM, "injected scan failure on shard %d (fir_shard_opts.fail_step = 1)", dc.shards[i]);
         if (!s.g) continue;
         uint64_t* out = dc.parts + (size_t)live * per;
         rc = k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
@@ -440,7 +424,7 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
     if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.keys, (int)per, kKeyNone);
     else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.parts, live, (int)per, dc.keys);
     else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, dc.parts, live, qb, k, dc.keys, per, (uint64_t*)nullptr);
-    SH_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
 
@@ -506,16 +490,16 @@ int device_classes(fir_sharded* h, int slot, const uint64_t* keys, int32_t qb, h
 }
 
 int dead_handle(const Health& hl) {
-    return sh_fail(FIR_ERR_STATE, "this sharded handle is closed: an earlier call failed on some rank (code %d); destroy it and create a fresh one", hl.dead_code.load());
+    return fir_fail_(FIR_ERR_STATE, "this sharded handle is closed: an earlier call failed on some rank (code %d); destroy it and create a fresh one", hl.dead_code.load());
 }
 
 // Host-pointer search: queries go to every device from pinned memory, keys (and classes) come back from device slot 0.
 int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, int32_t k, int32_t* idx, float* dist,
                 int32_t* class_out) {
-    if (!h || (qb > 0 && !queries)) return sh_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return sh_fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > 8) return sh_fail(FIR_ERR_ARG, "k=%d outside [1,8]", k);
-    if (class_out && !h->has_labels) return sh_fail(FIR_ERR_STATE, "the sharded gallery was created without class labels");
+    if (!h || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > 8) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,8]", k);
+    if (class_out && !h->has_labels) return fir_fail_(FIR_ERR_STATE, "the sharded gallery was created without class labels");
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     int rc = check_range(h, start, end);
@@ -534,7 +518,7 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
     const bool pin_grows = qbytes + kbytes + cbytes > h->pin_cap;            // read before slot 0 changes it: the same answer for every slot
     rc = run_all(h, [&](int slot) -> int {
         DevCtx& dc = h->devs[slot];
-        SH_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipSetDevice(dc.device));
         const CallBuffers nb = call_buffers(h, dc, qb, k, true, class_out != nullptr);
         int r = grow_agreed(dc, dc.stream, h->health, call_grows(dc, nb) || pin_grows, inject_here(h, dc, 2), [&]() -> int {
             int ra = call_alloc(dc, nb);
@@ -560,7 +544,7 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
         // from here on every rank takes part in every collective of the call, whatever happens to it
         int local = FIR_OK;
         char mine[512] = "";
-        if (hipMemcpyAsync(dc.dq, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess) local = sh_fail(FIR_ERR_HIP, "query upload failed");
+        if (hipMemcpyAsync(dc.dq, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess) local = fir_fail_(FIR_ERR_HIP, "query upload failed");
         if (!local) local = device_keys(h, slot, dc.dq, qb, start, end, k, dc.stream);
         if (local) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); (void)hipGetLastError(); }
         if ((r = exchange_keys(h, slot, qb, k, dc.stream, local))) return r;
@@ -597,20 +581,20 @@ int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, i
     for (int s = 0; s < ndev; ++s) {
         DevCtx& dc = devs[(size_t)s];
         dc.device = devices[s];
-        SH_HIP(hipSetDevice(dc.device));
-        SH_HIP(hipStreamCreateWithFlags(&dc.stream, hipStreamNonBlocking));
+        FIR_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipStreamCreateWithFlags(&dc.stream, hipStreamNonBlocking));
     }
     for (int s = 0; s < ndev; ++s) {
         DevCtx& dc = devs[(size_t)s];
-        SH_HIP(hipSetDevice(dc.device));
-        SH_HIP(hipMalloc((void**)&dc.status, 4 * sizeof(int32_t)));
-        SH_HIP(hipMemset(dc.status, 0, 4 * sizeof(int32_t)));
-        SH_HIP(hipHostMalloc((void**)&dc.h_status, 8 * sizeof(int32_t), hipHostMallocPortable | hipHostMallocMapped));
+        FIR_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipMalloc((void**)&dc.status, 4 * sizeof(int32_t)));
+        FIR_HIP(hipMemset(dc.status, 0, 4 * sizeof(int32_t)));
+        FIR_HIP(hipHostMalloc((void**)&dc.h_status, 8 * sizeof(int32_t), hipHostMallocPortable | hipHostMallocMapped));
         std::memset(dc.h_status, 0, 8 * sizeof(int32_t));
         void* dp = nullptr;
-        SH_HIP(hipHostGetDevicePointer(&dp, dc.h_status, 0));
+        FIR_HIP(hipHostGetDevicePointer(&dp, dc.h_status, 0));
         dc.d_hsticky = (int32_t*)dp + 3;
-        SH_HIP(hipEventCreateWithFlags(&dc.async_done, hipEventDisableTiming));
+        FIR_HIP(hipEventCreateWithFlags(&dc.async_done, hipEventDisableTiming));
     }
     // RCCL writes its version banner to STDOUT when a process's FIRST communicator comes up. The callers of this library print
     // results there (the reference's harnesses, whose output must stay diffable): for that one creation -- serialised by a
@@ -641,11 +625,11 @@ int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, i
             banner_done = true;
         }
     }
-    if (nr != ncclSuccess) return sh_fail(FIR_ERR_COMM, "RCCL communicator of %d ranks: %s", nranks, ncclGetErrorString(nr));
+    if (nr != ncclSuccess) return fir_fail_(FIR_ERR_COMM, "RCCL communicator of %d ranks: %s", nranks, ncclGetErrorString(nr));
     if (ndev > 1)
         for (int s = 0; s < ndev; ++s) {
             Worker* w = new (std::nothrow) Worker();
-            if (!w) return sh_fail(FIR_ERR_NOMEM, "host allocation failed");
+            if (!w) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
             devs[(size_t)s].worker = w;
             w->th = std::thread([w] { w->loop(); });
         }
@@ -675,30 +659,30 @@ void teardown_devices(std::vector<DevCtx>& devs, bool dead) {
 }
 
 int check_devices(const int32_t* devices, int32_t ndev) {
-    if (!devices || ndev < 1 || ndev > 64) return sh_fail(FIR_ERR_ARG, "device list of %d entries", ndev);
+    if (!devices || ndev < 1 || ndev > 64) return fir_fail_(FIR_ERR_ARG, "device list of %d entries", ndev);
     for (int i = 0; i < ndev; ++i)
         for (int j = 0; j < i; ++j)
-            if (devices[i] == devices[j]) return sh_fail(FIR_ERR_ARG, "device %d listed twice (use shards_per_device for logical shards)", devices[i]);
+            if (devices[i] == devices[j]) return fir_fail_(FIR_ERR_ARG, "device %d listed twice (use shards_per_device for logical shards)", devices[i]);
     const int cnt = fir_device_count();
     for (int i = 0; i < ndev; ++i)
-        if (devices[i] < 0 || devices[i] >= cnt) return sh_fail(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", devices[i], cnt);
+        if (devices[i] < 0 || devices[i] >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", devices[i], cnt);
     return FIR_OK;
 }
 
 int read_opts(const fir_shard_opts* opts, fir_shard_opts* o) {
     std::memset(o, 0, sizeof *o);
     if (opts) {
-        if (opts->struct_bytes < 8 || opts->struct_bytes > (int32_t)sizeof *o) return sh_fail(FIR_ERR_ARG, "fir_shard_opts.struct_bytes = %d", opts->struct_bytes);
+        if (opts->struct_bytes < 8 || opts->struct_bytes > (int32_t)sizeof *o) return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.struct_bytes = %d", opts->struct_bytes);
         std::memcpy(o, opts, (size_t)opts->struct_bytes);
     }
     if (o->shards_per_device <= 0) o->shards_per_device = 1;
     if (!o->comm_id) { o->nprocs = 1; o->proc_rank = 0; }
-    if (o->shards_per_device > 64) return sh_fail(FIR_ERR_ARG, "shards_per_device = %d", o->shards_per_device);
-    if (o->nprocs < 1 || o->proc_rank < 0 || o->proc_rank >= o->nprocs) return sh_fail(FIR_ERR_ARG, "process %d of %d", o->proc_rank, o->nprocs);
+    if (o->shards_per_device > 64) return fir_fail_(FIR_ERR_ARG, "shards_per_device = %d", o->shards_per_device);
+    if (o->nprocs < 1 || o->proc_rank < 0 || o->proc_rank >= o->nprocs) return fir_fail_(FIR_ERR_ARG, "process %d of %d", o->proc_rank, o->nprocs);
 #ifndef FIR_AUDIT
     // the failure-injection hooks exist in the audit build only (libfir_amd_audit.so): the shipped library refuses them loudly
     if (o->fail_shard != 0 || o->fail_step != 0)
-        return sh_fail(FIR_ERR_ARG, "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none");
+        return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none");
 #endif
     return FIR_OK;
 }
@@ -812,16 +796,16 @@ int fir_cls_sharded_destroy(fir_cls_sharded* h) {
 
 int fir_cls_create_sharded(const double* train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes, const double* avg,
                            const int32_t* devices, int32_t ndev, const fir_shard_opts* opts, fir_cls_sharded** out) {
-    if (!out) return sh_fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (nt < 0 || d <= 0 || num_classes <= 0 || !avg || (nt > 0 && (!train_rows || !train_class))) return sh_fail(FIR_ERR_ARG, "bad training set (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
+    if (nt < 0 || d <= 0 || num_classes <= 0 || !avg || (nt > 0 && (!train_rows || !train_class))) return fir_fail_(FIR_ERR_ARG, "bad training set (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
     int rc = check_devices(devices, ndev);
     if (rc) return rc;
     fir_shard_opts o;
     if ((rc = read_opts(opts, &o))) return rc;
-    if (o.rows_on_device) return sh_fail(FIR_ERR_ARG, "fir_cls_create_sharded takes host rows");
+    if (o.rows_on_device) return fir_fail_(FIR_ERR_ARG, "fir_cls_create_sharded takes host rows");
     fir_cls_sharded* h = new (std::nothrow) fir_cls_sharded();
-    if (!h) return sh_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!h) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     h->d = d; h->num_classes = num_classes; h->ndev = ndev; h->nranks = o.nprocs * ndev; h->nt_local = nt;
     h->health.apply(o);
     h->devs.resize((size_t)ndev);
@@ -849,11 +833,11 @@ int fir_cls_create_sharded(const double* train_rows, int64_t nt, int32_t d, cons
             if (train_class[t] >= 0 && train_class[t] < num_classes) cnt[(size_t)train_class[t]]++;
         rc = run_all(h->devs, [&](int slot) -> int {
             DevCtx& dc = h->devs[(size_t)slot];
-            SH_HIP(hipSetDevice(dc.device));
-            SH_HIP(hipMalloc((void**)&h->class_count[(size_t)slot], (size_t)num_classes * sizeof(int32_t)));
+            FIR_HIP(hipSetDevice(dc.device));
+            FIR_HIP(hipMalloc((void**)&h->class_count[(size_t)slot], (size_t)num_classes * sizeof(int32_t)));
             int32_t* cc = h->class_count[(size_t)slot];
-            if (slot == 0) SH_HIP(hipMemcpyAsync(cc, cnt.data(), (size_t)num_classes * sizeof(int32_t), hipMemcpyHostToDevice, dc.stream));
-            else SH_HIP(hipMemsetAsync(cc, 0, (size_t)num_classes * sizeof(int32_t), dc.stream));      // this process's rows are counted once
+            if (slot == 0) FIR_HIP(hipMemcpyAsync(cc, cnt.data(), (size_t)num_classes * sizeof(int32_t), hipMemcpyHostToDevice, dc.stream));
+            else FIR_HIP(hipMemsetAsync(cc, 0, (size_t)num_classes * sizeof(int32_t), dc.stream));      // this process's rows are counted once
             SH_NCCL(ncclAllReduce(cc, cc, (size_t)num_classes, ncclInt32, ncclSum, dc.comm, dc.stream));
             return wait_stream(dc, dc.stream, h->health);
         });
@@ -872,9 +856,9 @@ static bool cls_inject_dev(const fir_cls_sharded* h, int slot, int step) {
 }
 
 int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
-    if (!h || !best_class || (qb > 0 && !queries)) return sh_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return sh_fail(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > 8) return sh_fail(FIR_ERR_ARG, "k=%d outside [1,8]", k);
+    if (!h || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > 8) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,8]", k);
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     int32_t maxb = 1 << 30;
@@ -903,22 +887,22 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
     const int64_t qc = (int64_t)qb * h->num_classes;
     int rc = run_all(h->devs, [&](int slot) -> int {
         DevCtx& dc = h->devs[(size_t)slot];
-        SH_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipSetDevice(dc.device));
         int r = grow_agreed(dc, dc.stream, h->health, grows, cls_inject_dev(h, slot, 2), [&]() -> int {
             if (need > h->knn_cap) {
-                if (h->knn[(size_t)slot]) SH_HIP(hipFree(h->knn[(size_t)slot]));
+                if (h->knn[(size_t)slot]) FIR_HIP(hipFree(h->knn[(size_t)slot]));
                 h->knn[(size_t)slot] = nullptr;
-                SH_HIP(hipMalloc((void**)&h->knn[(size_t)slot], need * sizeof(double)));
+                FIR_HIP(hipMalloc((void**)&h->knn[(size_t)slot], need * sizeof(double)));
             }
             if ((size_t)qb > h->best_cap) {
-                if (h->best[(size_t)slot]) SH_HIP(hipFree(h->best[(size_t)slot]));
+                if (h->best[(size_t)slot]) FIR_HIP(hipFree(h->best[(size_t)slot]));
                 h->best[(size_t)slot] = nullptr;
-                SH_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
+                FIR_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
             }
             if (slot == 0 && pin_need > h->pin_cap) {
-                if (h->pin) SH_HIP(hipHostFree(h->pin));
+                if (h->pin) FIR_HIP(hipHostFree(h->pin));
                 h->pin = nullptr; h->pin_cap = 0;
-                SH_HIP(hipHostMalloc(&h->pin, std::max<size_t>(pin_need, 4096 * sizeof(int32_t) + 64), hipHostMallocPortable));
+                FIR_HIP(hipHostMalloc(&h->pin, std::max<size_t>(pin_need, 4096 * sizeof(int32_t) + 64), hipHostMallocPortable));
                 h->pin_cap = std::max<size_t>(pin_need, 4096 * sizeof(int32_t) + 64);
             }
             return FIR_OK;
@@ -934,7 +918,7 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
         for (size_t pi = 0; pi < h->parts.size() && !local; ++pi) {
             auto& p = h->parts[pi];
             if (p.slot != slot) continue;
-            if (cls_inject(h, (int)pi, 1)) { local = sh_fail(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
+            if (cls_inject(h, (int)pi, 1)) { local = fir_fail_(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
             if (!p.c) continue;
             double* dl = nullptr;
             void* st = nullptr;
@@ -942,7 +926,7 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
             if (local) break;
             if (hipStreamSynchronize((hipStream_t)st) != hipSuccess ||
                 hipMemcpyAsync(parts + per * (size_t)np, dl, per * sizeof(double), hipMemcpyDeviceToDevice, dc.stream) != hipSuccess)
-                local = sh_fail(FIR_ERR_HIP, "copying a shard's k-nearest table failed");
+                local = fir_fail_(FIR_ERR_HIP, "copying a shard's k-nearest table failed");
             ++np;
         }
         if (local) { strncpy(mine_err, fir_last_error(), sizeof(mine_err) - 1); (void)hipGetLastError(); np = 0; }
@@ -968,8 +952,8 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
 }
 
 int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
-    if (!h || (qb > 0 && !queries)) return sh_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return sh_fail(FIR_ERR_ARG, "qb < 0");
+    if (!h || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     // internal batches: what every shard's distance table allows (fir_cls_pnn_scores_dev_)
@@ -991,22 +975,22 @@ int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32
     const size_t new_best = std::max<size_t>(4096, (size_t)qb);
     int rc = run_all(h->devs, [&](int slot) -> int {
         DevCtx& dc = h->devs[(size_t)slot];
-        SH_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipSetDevice(dc.device));
         int r = grow_agreed(dc, dc.stream, h->health, grows, cls_inject_dev(h, slot, 2), [&]() -> int {
             if (nsc + 1 > h->acc_cap) {
-                if (h->acc[(size_t)slot]) SH_HIP(hipFree(h->acc[(size_t)slot]));
+                if (h->acc[(size_t)slot]) FIR_HIP(hipFree(h->acc[(size_t)slot]));
                 h->acc[(size_t)slot] = nullptr;
-                SH_HIP(hipMalloc((void**)&h->acc[(size_t)slot], (nsc + 1) * sizeof(double)));
+                FIR_HIP(hipMalloc((void**)&h->acc[(size_t)slot], (nsc + 1) * sizeof(double)));
             }
             if ((size_t)qb > h->best_cap) {
-                if (h->best[(size_t)slot]) SH_HIP(hipFree(h->best[(size_t)slot]));
+                if (h->best[(size_t)slot]) FIR_HIP(hipFree(h->best[(size_t)slot]));
                 h->best[(size_t)slot] = nullptr;
-                SH_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
+                FIR_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
             }
             if (slot == 0 && pin_need > h->pin_cap) {
-                if (h->pin) SH_HIP(hipHostFree(h->pin));
+                if (h->pin) FIR_HIP(hipHostFree(h->pin));
                 h->pin = nullptr; h->pin_cap = 0;
-                SH_HIP(hipHostMalloc(&h->pin, pin_need, hipHostMallocPortable));
+                FIR_HIP(hipHostMalloc(&h->pin, pin_need, hipHostMallocPortable));
                 h->pin_cap = pin_need;
             }
             return FIR_OK;
@@ -1019,13 +1003,13 @@ int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32
         for (size_t pi = 0; pi < h->parts.size() && !local; ++pi) {
             auto& p = h->parts[pi];
             if (p.slot != slot) continue;
-            if (cls_inject(h, (int)pi, 1)) { local = sh_fail(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
+            if (cls_inject(h, (int)pi, 1)) { local = fir_fail_(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
             if (!p.c) continue;
             double* ds = nullptr;
             void* st = nullptr;
             local = fir_cls_pnn_scores_dev_(p.c, queries, qb, var, &ds, &st, nullptr);
             if (local) break;
-            if (hipStreamSynchronize((hipStream_t)st) != hipSuccess) { local = sh_fail(FIR_ERR_HIP, "a shard's class scores did not complete"); break; }   // the shard's own stream
+            if (hipStreamSynchronize((hipStream_t)st) != hipSuccess) { local = fir_fail_(FIR_ERR_HIP, "a shard's class scores did not complete"); break; }   // the shard's own stream
             hipLaunchKernelGGL(k_shard_add_f64, dim3((unsigned)((nsc + 255) / 256)), dim3(256), 0, dc.stream, acc, ds, (int64_t)nsc, first);
             first = 0;
         }
@@ -1055,7 +1039,7 @@ int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32
 }
 
 int fir_comm_unique_id(void* id_out) {
-    if (!id_out) return sh_fail(FIR_ERR_ARG, "id_out is NULL");
+    if (!id_out) return fir_fail_(FIR_ERR_ARG, "id_out is NULL");
     static_assert(sizeof(ncclUniqueId) <= FIR_COMM_ID_BYTES, "FIR_COMM_ID_BYTES too small");
     ncclUniqueId id;
     SH_NCCL(ncclGetUniqueId(&id));
@@ -1076,40 +1060,40 @@ int fir_sharded_destroy(fir_sharded* h) {
 
 int fir_gallery_create_sharded_ex(const float* rows, int64_t n, int32_t d, const int32_t* class_no, int32_t metric, const int32_t* devices,
                                   int32_t ndev, const fir_shard_opts* opts, fir_sharded** out) {
-    if (!out) return sh_fail(FIR_ERR_ARG, "out is NULL");
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!devices || ndev < 1 || ndev > 64) return sh_fail(FIR_ERR_ARG, "device list of %d entries", ndev);
-    if (n < 0 || d <= 0 || (n > 0 && !rows)) return sh_fail(FIR_ERR_ARG, "bad gallery shape n=%lld d=%d", (long long)n, d);
+    if (!devices || ndev < 1 || ndev > 64) return fir_fail_(FIR_ERR_ARG, "device list of %d entries", ndev);
+    if (n < 0 || d <= 0 || (n > 0 && !rows)) return fir_fail_(FIR_ERR_ARG, "bad gallery shape n=%lld d=%d", (long long)n, d);
     fir_shard_opts o;
     std::memset(&o, 0, sizeof o);
     if (opts) {
-        if (opts->struct_bytes < 8 || opts->struct_bytes > (int32_t)sizeof o) return sh_fail(FIR_ERR_ARG, "fir_shard_opts.struct_bytes = %d", opts->struct_bytes);
+        if (opts->struct_bytes < 8 || opts->struct_bytes > (int32_t)sizeof o) return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.struct_bytes = %d", opts->struct_bytes);
         std::memcpy(&o, opts, (size_t)opts->struct_bytes);
     }
     const int spd = o.shards_per_device > 0 ? o.shards_per_device : 1;
     const int nprocs = o.comm_id ? o.nprocs : 1, proc = o.comm_id ? o.proc_rank : 0;
-    if (spd > 64) return sh_fail(FIR_ERR_ARG, "shards_per_device = %d", spd);
-    if (nprocs < 1 || proc < 0 || proc >= nprocs) return sh_fail(FIR_ERR_ARG, "process %d of %d", proc, nprocs);
-    if (o.rows_on_device && ndev != 1) return sh_fail(FIR_ERR_ARG, "device-resident rows need a one-entry device list (they live on one device)");
+    if (spd > 64) return fir_fail_(FIR_ERR_ARG, "shards_per_device = %d", spd);
+    if (nprocs < 1 || proc < 0 || proc >= nprocs) return fir_fail_(FIR_ERR_ARG, "process %d of %d", proc, nprocs);
+    if (o.rows_on_device && ndev != 1) return fir_fail_(FIR_ERR_ARG, "device-resident rows need a one-entry device list (they live on one device)");
 #ifndef FIR_AUDIT
     if (o.fail_shard != 0 || o.fail_step != 0)       // (as read_opts: the hooks exist in the audit build only)
-        return sh_fail(FIR_ERR_ARG, "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none");
+        return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none");
 #endif
-    if (o.first_global_row < 0 || o.first_global_row + n >= ((int64_t)1 << 31)) return sh_fail(FIR_ERR_ARG, "rows [%lld, +%lld) do not fit 32-bit indices", (long long)o.first_global_row, (long long)n);
+    if (o.first_global_row < 0 || o.first_global_row + n >= ((int64_t)1 << 31)) return fir_fail_(FIR_ERR_ARG, "rows [%lld, +%lld) do not fit 32-bit indices", (long long)o.first_global_row, (long long)n);
     for (int i = 0; i < ndev; ++i)
         for (int j = 0; j < i; ++j)
-            if (devices[i] == devices[j]) return sh_fail(FIR_ERR_ARG, "device %d listed twice (use shards_per_device for logical shards)", devices[i]);
+            if (devices[i] == devices[j]) return fir_fail_(FIR_ERR_ARG, "device %d listed twice (use shards_per_device for logical shards)", devices[i]);
     const int cnt = fir_device_count();
     for (int i = 0; i < ndev; ++i)
-        if (devices[i] < 0 || devices[i] >= cnt) return sh_fail(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", devices[i], cnt);
+        if (devices[i] < 0 || devices[i] >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", devices[i], cnt);
 
     fir_sharded* h = new (std::nothrow) fir_sharded();
-    if (!h) return sh_fail(FIR_ERR_NOMEM, "host allocation failed");
+    if (!h) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     h->d = d; h->metric = metric; h->n_local = n; h->first_row = o.first_global_row;
     h->ndev = ndev; h->spd = spd; h->nranks = nprocs * ndev; h->rank0 = proc * ndev;
     h->has_labels = class_no != nullptr;
     h->health.apply(o);
-    if (h->health.fail_shard < 0 || h->health.fail_shard > ndev * spd) { delete h; return sh_fail(FIR_ERR_ARG, "fail_shard = %d of %d shards", o.fail_shard, ndev * spd); }
+    if (h->health.fail_shard < 0 || h->health.fail_shard > ndev * spd) { delete h; return fir_fail_(FIR_ERR_ARG, "fail_shard = %d of %d shards", o.fail_shard, ndev * spd); }
     h->devs.resize((size_t)ndev);
     int rc = FIR_OK;
     auto bail = [&](int code) { fir_sharded_destroy(h); return code; };
@@ -1151,7 +1135,7 @@ int fir_gallery_create_sharded(const float* rows, int64_t n, int32_t d, const in
 }
 
 int fir_sharded_info(const fir_sharded* h, int64_t* n_local, int32_t* d, int32_t* ndev, int32_t* nshards, int32_t* nranks, int32_t* first_rank) {
-    if (!h) return sh_fail(FIR_ERR_ARG, "handle is NULL");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     if (n_local) *n_local = h->n_local;
     if (d) *d = h->d;
     if (ndev) *ndev = h->ndev;
@@ -1162,7 +1146,7 @@ int fir_sharded_info(const fir_sharded* h, int64_t* n_local, int32_t* d, int32_t
 }
 
 int fir_sharded_shard(fir_sharded* h, int32_t i, fir_gallery** g, int64_t* first_global_row, int64_t* rows) {
-    if (!h || i < 0 || i >= (int32_t)h->shards.size()) return sh_fail(FIR_ERR_ARG, "shard %d of %d", i, h ? (int)h->shards.size() : 0);
+    if (!h || i < 0 || i >= (int32_t)h->shards.size()) return fir_fail_(FIR_ERR_ARG, "shard %d of %d", i, h ? (int)h->shards.size() : 0);
     if (g) *g = h->shards[(size_t)i].g;
     if (first_global_row) *first_global_row = h->shards[(size_t)i].lo;
     if (rows) *rows = h->shards[(size_t)i].hi - h->shards[(size_t)i].lo;
@@ -1170,7 +1154,7 @@ int fir_sharded_shard(fir_sharded* h, int32_t i, fir_gallery** g, int64_t* first
 }
 
 int fir_sharded_set_metric(fir_sharded* h, int32_t metric) {
-    if (!h) return sh_fail(FIR_ERR_ARG, "handle is NULL");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     for (Shard& s : h->shards)
         if (s.g) { const int rc = fir_gallery_set_metric(s.g, metric); if (rc) return rc; }
     h->metric = metric;
@@ -1188,21 +1172,21 @@ int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, in
 
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* class_out,
                               int32_t* idx, float* dist) {
-    if (!class_out) return sh_fail(FIR_ERR_ARG, "class_out is NULL");
+    if (!class_out) return fir_fail_(FIR_ERR_ARG, "class_out is NULL");
     return search_host(h, queries, qb, start_pos, end_pos, 1, idx, dist, class_out);
 }
 
 int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, uint64_t* d_keys,
                                      void* stream) {
-    if (!h || !d_keys || (qb > 0 && !d_queries)) return sh_fail(FIR_ERR_ARG, "NULL argument");
-    if (h->ndev != 1) return sh_fail(FIR_ERR_STATE, "device-pointer calls need a one-device handle (one process per GPU); this one lists %d", h->ndev);
-    if (qb < 0) return sh_fail(FIR_ERR_ARG, "qb < 0");
+    if (!h || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (h->ndev != 1) return fir_fail_(FIR_ERR_STATE, "device-pointer calls need a one-device handle (one process per GPU); this one lists %d", h->ndev);
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     int rc = check_range(h, start_pos, end_pos);
     if (rc) return rc;
     DevCtx& dc = h->devs[0];
-    SH_HIP(hipSetDevice(dc.device));
+    FIR_HIP(hipSetDevice(dc.device));
     hipStream_t st = stream ? (hipStream_t)stream : dc.stream;
     // What the previous asynchronous call found, if it is through (no waiting here): a peer's failure closes the handle BEFORE this rank
     // enqueues another collective that the failed peer -- dead since that call -- will never enter. A previous call that is still in
@@ -1225,15 +1209,15 @@ int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int
     (void)hipEventRecord(dc.async_done, st);           // what fir_sharded_sync (and the next call's look at the status) waits for: `st` may be the caller's stream
     dc.async_pending = true;
     if (local) { h->health.dead = true; h->health.dead_code = local; fir_set_last_error_(mine); return local; }
-    SH_HIP(hipGetLastError());
+    FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
 
 int fir_sharded_sync(fir_sharded* h) {
-    if (!h) return sh_fail(FIR_ERR_ARG, "handle is NULL");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     if (h->health.dead) return dead_handle(h->health);
     for (DevCtx& dc : h->devs) {
-        SH_HIP(hipSetDevice(dc.device));
+        FIR_HIP(hipSetDevice(dc.device));
         int rc;
         // the last asynchronous call ran on whatever stream its caller named: its completion is the event recorded behind it, waited for
         // with the same bound as every other wait behind a collective (the handle's own stream says nothing about it)
@@ -1241,7 +1225,7 @@ int fir_sharded_sync(fir_sharded* h) {
         dc.async_pending = false;
         if ((rc = wait_stream(dc, dc.stream, h->health))) return rc;
         // the asynchronous calls' record: the worst status any exchange since the last sync came back with (device word and its host mirror)
-        SH_HIP(hipMemcpyAsync(dc.h_status + 2, dc.status + 1, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream));
+        FIR_HIP(hipMemcpyAsync(dc.h_status + 2, dc.status + 1, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream));
         if ((rc = wait_stream(dc, dc.stream, h->health))) return rc;
         const int32_t worst = std::min(dc.h_status[2], dc.h_status[3]);
         if (worst < 0) { h->health.dead = true; h->health.dead_code = worst; return peer_failed(worst); }
@@ -1250,21 +1234,21 @@ int fir_sharded_sync(fir_sharded* h) {
 }
 
 int fir_sharded_profile_enable(fir_sharded* h, int32_t on) {
-    if (!h) return sh_fail(FIR_ERR_ARG, "handle is NULL");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     h->profiling = on != 0;
     h->devs[0].ev_used = 0;
     return FIR_OK;
 }
 
 int fir_sharded_profile_read(fir_sharded* h, float* exchange_ms, int32_t cap, int32_t* count) {
-    if (!h) return sh_fail(FIR_ERR_ARG, "handle is NULL");
+    if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     DevCtx& dc = h->devs[0];
-    SH_HIP(hipSetDevice(dc.device));
+    FIR_HIP(hipSetDevice(dc.device));
     const int32_t have = (int32_t)(dc.ev_used / 2);
     for (int32_t i = 0; i < have; ++i) {
-        SH_HIP(hipEventSynchronize(dc.evs[2 * (size_t)i + 1]));
+        FIR_HIP(hipEventSynchronize(dc.evs[2 * (size_t)i + 1]));
         float ms = 0.f;
-        SH_HIP(hipEventElapsedTime(&ms, dc.evs[2 * (size_t)i], dc.evs[2 * (size_t)i + 1]));
+        FIR_HIP(hipEventElapsedTime(&ms, dc.evs[2 * (size_t)i], dc.evs[2 * (size_t)i + 1]));
         if (exchange_ms && i < cap) exchange_ms[i] = ms;
     }
     if (count) *count = have;

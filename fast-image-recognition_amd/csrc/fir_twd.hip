@@ -16,7 +16,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -32,21 +31,6 @@ constexpr int kBatch = 64;         // queries per internal batch at most: all th
                                    // before ONE synchronisation (a range-distance pass serves 8 of them)
 constexpr int kLastFeature = 256;  // ImageTesting.cpp:169-171, 226-228
 
-thread_local char g_twd_err[512];
-int twd_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_twd_err, sizeof(g_twd_err), fmt, ap);
-    va_end(ap);
-    fir_set_last_error_(g_twd_err);
-    return code;
-}
-#define TWD_HIP(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) return twd_fail(e_ == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP,        \
-                                              "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 struct DI {
     double d;
@@ -1146,29 +1130,27 @@ int batch_for(int64_t n, size_t bytes_per_query_row, size_t budget = (size_t)512
     return (int)std::max<size_t>(8, std::min<size_t>(kBatch, fit / 8 * 8));
 }
 
-// A slot of the gallery handle's scratch pool (fir_gallery_scratch_): grown on demand, reused by every later call.
+// A slot of the gallery handle's scratch pool (fir_gallery_scratch_; fir_internal.h has the slot map): grown on demand, reused by every later call.
 struct Slot {
     void* p = nullptr;
     template <typename T> T* as() { return (T*)p; }
 };
-#define TWD_SLOT(var, slot, bytes)                                                       \
-    Slot var;                                                                            \
-    if ((rc = fir_gallery_scratch_(g, slot, std::max<size_t>(bytes, 16), &var.p))) return rc
+int take_slot(fir_gallery* g, int slot, size_t bytes, Slot* out) { return fir_gallery_scratch_(g, slot, std::max<size_t>(bytes, 16), &out->p); }
 
 int check_common(fir_gallery* g, const float* queries, int32_t qb, int32_t reduced, fir_gallery_view* v) {
-    if (!g || (qb > 0 && !queries)) return twd_fail(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return twd_fail(FIR_ERR_ARG, "qb < 0");
-    if (fir_gallery_view_(g, v) != FIR_OK) return twd_fail(FIR_ERR_ARG, "bad gallery");
-    if (!v->cls) return twd_fail(FIR_ERR_STATE, "gallery was created without class labels");
-    if (v->d < kLastFeature) return twd_fail(FIR_ERR_ARG, "the TWD classifiers use features [0,%d); the gallery has %d", kLastFeature, v->d);
-    if (reduced <= 0 || reduced >= kLastFeature) return twd_fail(FIR_ERR_ARG, "reduced_features_count=%d outside (0,%d)", reduced, kLastFeature);
-    if (v->n >= (int64_t)1 << 30) return twd_fail(FIR_ERR_ARG, "gallery too large for the TWD drivers");
+    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (fir_gallery_view_(g, v) != FIR_OK) return fir_fail_(FIR_ERR_ARG, "bad gallery");
+    if (!v->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    if (v->d < kLastFeature) return fir_fail_(FIR_ERR_ARG, "the TWD classifiers use features [0,%d); the gallery has %d", kLastFeature, v->d);
+    if (reduced <= 0 || reduced >= kLastFeature) return fir_fail_(FIR_ERR_ARG, "reduced_features_count=%d outside (0,%d)", reduced, kLastFeature);
+    if (v->n >= (int64_t)1 << 30) return fir_fail_(FIR_ERR_ARG, "gallery too large for the TWD drivers");
     return FIR_OK;
 }
 
 }  // namespace
 
-// The verdicts of a batch go to pinned host memory, then the ticket the host is spinning on (fir_gallery_wait_ticket_).
+// The verdicts of a batch go to pinned host memory, then the ticket the host is spinning on (fir_wait_ticket_).
 __global__ void __launch_bounds__(256) k_twd_publish(const int32_t* __restrict__ res, int count, int32_t* __restrict__ host_res,
                                                      uint64_t* __restrict__ host_ticket, uint64_t ticket) {
     for (int i = threadIdx.x; i < count; i += 256) host_res[i] = res[i];
@@ -1177,12 +1159,36 @@ __global__ void __launch_bounds__(256) k_twd_publish(const int32_t* __restrict__
     if (threadIdx.x == 0) __hip_atomic_store(host_ticket, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-extern "C" {
+namespace {
+
+// Every instantiation of the two one-launch kernels: a row per (metric, tiles per wave), both pointers written from the same template
+// arguments. The occupancy query and the launch take the pointer from the row select_fused found once.
+typedef void (*conv_fused_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, int, double, ConvState*, unsigned long long, int32_t*,
+                              int32_t*, int32_t*, int, uint64_t*, uint64_t, unsigned int*);
+typedef void (*prop_fused_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, double, FusedState*, int, unsigned long long, int32_t*,
+                              int32_t*, int32_t*, int32_t*, int, uint64_t*, uint64_t);
+struct FusedRow {
+    int metric, T;
+    conv_fused_fn conv;
+    prop_fused_fn prop;
+};
+#define FIR_TWD_ROW(M, T) {M, T, k_twd_conv_fused<M, T>, k_twd_prop_fused<M, T>}
+const FusedRow kFusedTable[] = {
+    FIR_TWD_ROW(fir::kL2, 1),   FIR_TWD_ROW(fir::kL2, 2),   FIR_TWD_ROW(fir::kL2, 4),   FIR_TWD_ROW(fir::kL2, 8),   FIR_TWD_ROW(fir::kL2, 16),
+    FIR_TWD_ROW(fir::kChi2, 1), FIR_TWD_ROW(fir::kChi2, 2), FIR_TWD_ROW(fir::kChi2, 4), FIR_TWD_ROW(fir::kChi2, 8), FIR_TWD_ROW(fir::kChi2, 16),
+};
+#undef FIR_TWD_ROW
+static_assert(sizeof(kFusedTable) / sizeof(kFusedTable[0]) == 10, "one row per (L2, chi-square) x (1, 2, 4, 8, 16 tiles per wave)");
+const FusedRow* select_fused(int metric, int T) {
+    for (const FusedRow& r : kFusedTable)
+        if (r.metric == metric && r.T == T) return &r;
+    return nullptr;
+}
 
 // The hand-rolled grid meetings of the fused kernels need every workgroup of the launch resident at the same time: checked against the
 // occupancy query before the launch (MI355X_MICROARCH.md: the API can read one block per CU high near register-file edges, so one block of
 // margin is kept whenever more than one per CU is counted on), and bounded by kFusedPatienceTicks inside the kernel whatever else runs.
-static bool fused_grid_fits(const void* fn, int block, size_t dyn_lds, int workgroups, int cus) {
+bool fused_grid_fits(const void* fn, int block, size_t dyn_lds, int workgroups, int cus) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, dyn_lds) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (per_cu < 1) return false;
@@ -1190,168 +1196,296 @@ static bool fused_grid_fits(const void* fn, int block, size_t dyn_lds, int workg
     return workgroups <= safe * std::max(cus, 1);
 }
 
+// What one call will launch, decided before anything is queued.
+struct TwdPlan {
+    bool fused = false;              // ONE launch per batch (k_twd_conv_fused / k_twd_prop_fused); a launch whose workgroups do not meet
+                                     // in time is answered by the staged form
+    int fq = 0, fG = 0, fT = 0;      // of that launch: queries counted on, workgroups per query, tiles per wave
+    const FusedRow* row = nullptr;   // its kernels
+    int batch = 0, step = 0;         // queries the scratch is sized for / per turn of the driver's loop
+    int nseg = 1, seg_rows = 0, nseg_eff = 1;   // staged form: workgroups per query asked for, rows of each, workgroups that have rows
+};
+// FIR_TWD_FUSED: 0 = never the fused form, 1 (default) = for up to kFusedMaxQueries queries, 2 = whatever the batch (tests)
+int fused_mode() {
+    const char* fenv = fir_knob_("FIR_TWD_FUSED");
+    return fenv ? std::atoi(fenv) : 1;
+}
+
+TwdPlan plan_conventional(const fir_gallery_view& v, int qb, int num_classes, int type, int reduced) {
+    TwdPlan p;
+    const int n = (int)v.n;
+    p.batch = std::min(batch_for(n, 8), std::max(8, (qb + 7) / 8 * 8));
+    // galleries beyond a few spans: the rows of every query are split over `nseg` workgroups (see k_twd_conv_stage1)
+    p.nseg = n > 4 * kSpan ? std::min(256, (n + 2 * kSpan - 1) / (2 * kSpan)) : 1;
+    p.seg_rows = p.nseg > 1 ? ((n + p.nseg - 1) / p.nseg + kSpan - 1) / kSpan * kSpan : n;
+    p.nseg_eff = p.nseg > 1 ? (n + p.seg_rows - 1) / p.seg_rows : 1;
+    // Few queries: ONE launch per internal batch (k_twd_conv_fused), as for the proposed classifier.
+    const int fmode = fused_mode();
+    const int64_t tiles64 = ((int64_t)n + 63) / 64;
+    p.fused = fmode != 0 && n > 0 && (fmode == 2 || qb <= kFusedMaxQueries) && (v.metric == 0 || v.metric == 1) && reduced % 4 == 0 &&
+              num_classes <= 4096;                                      // (the posteriors of a workgroup sit in LDS next to 6 KiB of static tables)
+    p.fq = std::min(qb, kFusedMaxQueries);
+    if (p.fused) {
+        for (int t : {1, 2, 4, 8, 16}) {
+            const int64_t g_need = (tiles64 + 8 * t - 1) / (8 * t);
+            if (g_need <= std::min(256, std::max(1, v.cus / p.fq))) { p.fT = t; p.fG = (int)g_need; break; }
+        }
+        // every query of a fused launch reads the rows for itself: beyond one tile per wave that costs more than the launches it saves
+        // (100 000 x 512, 8 queries: 146 against 96 us), so several queries go this way only while every wave has a single tile
+        if (!p.fT || (p.fq > 1 && p.fT > 1)) p.fused = false;
+        // every workgroup of the launch must be resident at once: the occupancy query decides, not an assumption
+        p.row = p.fused ? select_fused(v.metric, p.fT) : nullptr;
+        if (!p.row || !fused_grid_fits((const void*)p.row->conv, kFusedBlock, type == 0 ? (size_t)num_classes * 8 : 8, p.fG * p.fq, v.cus)) p.fused = false;
+    }
+    p.step = p.fused ? kFusedMaxQueries : p.batch;
+    return p;
+}
+
+TwdPlan plan_proposed(const fir_gallery_view& v, int qb, int reduced, int nchunks) {
+    TwdPlan p;
+    const int n = (int)v.n;
+    // Few queries: ONE launch per internal batch (k_twd_prop_fused).
+    const int fmode = fused_mode();
+    const int64_t tiles = ((int64_t)n + 63) / 64;
+    p.fused = fmode != 0 && n > 0 && (fmode == 2 || qb <= kFusedMaxQueries) && (v.metric == 0 || v.metric == 1) && reduced % 4 == 0 && reduced <= 128 &&
+              nchunks <= kFusedMaxChunks;
+    p.fq = std::min(qb, kFusedMaxQueries);                             // queries per fused launch
+    if (p.fused) {
+        // at most one workgroup per CU over all the queries of a launch: the workgroups of a query wait for each other
+        p.fG = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, v.cus / p.fq), (tiles + 7) / 8));
+        const int64_t need = (tiles + (int64_t)p.fG * 8 - 1) / ((int64_t)p.fG * 8);
+        p.fT = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 16 ? 16 : 0;
+        if (!p.fT) p.fused = false;
+        // every workgroup of the launch must be resident at once: the occupancy query decides, not an assumption
+        p.row = p.fused ? select_fused(v.metric, p.fT) : nullptr;
+        if (!p.row || !fused_grid_fits((const void*)p.row->prop, kFusedBlock, 0, p.fG * p.fq, v.cus)) p.fused = false;
+    }
+    p.batch = p.step = p.fused ? 8 : std::min(batch_for(n, (size_t)nchunks * 4 + 9, (size_t)1 << 30), std::max(8, (qb + 7) / 8 * 8));
+    // large galleries: the rows of every query are split over `nseg` workgroups, one launch per chunk
+    p.nseg = n > 16384 ? std::min(256, (n + 8191) / 8192) : 1;
+    p.seg_rows = p.nseg > 1 ? ((n + p.nseg - 1) / p.nseg + 255) / 256 * 256 : n;
+    p.nseg_eff = p.nseg > 1 ? (n + p.seg_rows - 1) / p.seg_rows : 1;
+    return p;
+}
+
+// The queries of one batch in, its verdicts out. Small batches go through the handle's pinned, device-visible buffer: the kernels read
+// the queries from it and the verdicts come back through it, behind a ticket instead of a stream synchronisation (no copy engine on
+// either side); the others are copied into slot 0 and out of slot 3.
+struct TwdIo {
+    fir_gallery* g;
+    const fir_gallery_view& v;
+    Slot dq, dres;                   // slot 0: the batch's queries; slot 3: kBatch int32 words per verdict column
+    uint64_t* pin_res = nullptr;
+    bool pinned = false;             // (as stage() found it)
+
+    int stage(const float* queries, int nq, const float** qsrc) {
+        void* pin_base = nullptr;
+        size_t pin_cap = 0;
+        const size_t bytes = (size_t)nq * v.d * 4;
+        pinned = fir_gallery_pin_(g, &pin_base, &pin_cap, &pin_res) == FIR_OK && bytes <= pin_cap;
+        if (pinned) std::memcpy(pin_base, queries, bytes);
+        else FIR_HIP(hipMemcpyAsync(dq.p, queries, bytes, hipMemcpyHostToDevice, v.stream));
+        *qsrc = pinned ? (const float*)pin_base : dq.as<float>();
+        return FIR_OK;
+    }
+    // one per launch sequence that ends in collect(); what a kernel that publishes for itself is given (NULL: it does not)
+    uint64_t next_ticket() { return pinned ? fir_gallery_next_ticket_(g) : 0; }
+    int32_t* host_res(bool self_publish) { return self_publish ? (int32_t*)pin_res : nullptr; }
+    uint64_t* host_ticket(bool self_publish, int ticket_word) { return self_publish ? pin_res + ticket_word : nullptr; }
+    // `words` int32 of slot 3 into h_res; pinned: k_twd_publish unless the deciding workgroup published itself, then the ticket
+    int collect(int32_t* h_res, int words, int ticket_word, uint64_t ticket, bool self_published) {
+        if (!pinned) {
+            FIR_HIP(hipMemcpyAsync(h_res, dres.p, (size_t)words * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipStreamSynchronize(v.stream));
+            return FIR_OK;
+        }
+        if (!self_published) {
+            hipLaunchKernelGGL(k_twd_publish, dim3(1), dim3(256), 0, v.stream, dres.as<int32_t>(), words, (int32_t*)pin_res, pin_res + ticket_word, ticket);
+            FIR_HIP(hipGetLastError());
+        }
+        const int rc = fir_wait_ticket_(v.stream, pin_res + ticket_word, ticket);
+        if (rc) return rc;
+        std::memcpy(h_res, pin_res, (size_t)words * 4);
+        return FIR_OK;
+    }
+};
+
+struct ConvArgs {
+    int num_classes, type;
+    double threshold;
+    int reduced;
+};
+constexpr int kConvWords = 2 * kBatch, kConvTicket = kBatch;        // class[kBatch], unreliable[kBatch]; the ticket's eight-byte word behind them
+constexpr int kPropWords = 3 * kBatch, kPropTicket = 2 * kBatch;    // class, unreliable, chunks
+
+// One fused launch for nq <= kFusedMaxQueries queries. *answered: every query's workgroups met in time.
+int conv_fused(TwdIo& io, const TwdPlan& p, const ConvArgs& a, const float* qsrc, int nq, int32_t* h_res, bool* answered) {
+    const fir_gallery_view& v = io.v;
+    int rc;
+    Slot cst;                                                           // (a fresh slot reads as zeros; the kernel leaves it so)
+    const size_t cst_bytes = (size_t)kFusedMaxQueries * sizeof(ConvState) + 64;
+    if ((rc = take_slot(io.g, 16, cst_bytes, &cst))) return rc;
+    ConvState* cstate = cst.as<ConvState>();
+    unsigned int* done_ctr = (unsigned int*)(cstate + kFusedMaxQueries);
+    const void* gal4 = nullptr;
+    int dp4 = 0;
+    if ((rc = fir_gallery_tiled_(io.g, &gal4, &dp4))) return fir_fail_(rc, "no tiled gallery");
+    const uint64_t ticket = io.next_ticket();
+    const unsigned long long gen_base = (unsigned long long)(fir_gallery_next_counter_(io.g, 1) + 1) << 7;      // meeting numbers that never repeat
+    const size_t flds = a.type == 0 ? (size_t)a.num_classes * 8 : 8;      // <= 32 KiB
+    int32_t* dcls = io.dres.as<int32_t>();
+    hipLaunchKernelGGL(p.row->conv, dim3(p.fG, nq), dim3(kFusedBlock), flds, v.stream, (const float4*)gal4, dp4, (int)v.n, (int)((v.n + 63) / 64), v.cls, qsrc,
+                       v.d, a.reduced, a.num_classes, a.type, a.threshold, cstate, gen_base, dcls, dcls + kBatch, io.host_res(io.pinned), kBatch,
+                       io.host_ticket(io.pinned, kConvTicket), ticket, done_ctr);
+    FIR_HIP(hipGetLastError());
+    if ((rc = io.collect(h_res, kConvWords, kConvTicket, ticket, true))) return rc;
+    *answered = true;
+    for (int i = 0; i < nq; ++i) *answered = *answered && h_res[kBatch + i] != 2;        // 2: the workgroups did not meet in time
+    if (!*answered) {
+        FIR_HIP(hipStreamSynchronize(v.stream));
+        FIR_HIP(hipMemsetAsync(cst.p, 0, cst_bytes, v.stream));      // whatever the launch left behind
+    }
+    return FIR_OK;
+}
+
+// The launch-per-stage form: both partial distances from one pass over features [0, 256), then both stages queued back to back -- the
+// second one decides on the device which queries it concerns -- and the verdicts come back with ONE collect per batch.
+int conv_staged(TwdIo& io, const TwdPlan& p, const ConvArgs& a, const float* qsrc, int nq, int32_t* h_res) {
+    const fir_gallery_view& v = io.v;
+    const int n = (int)v.n;
+    int rc;
+    Slot d1, dpart;      // [0, reduced) distances of the batch, then [reduced, 256); the segment records
+    if ((rc = take_slot(io.g, 1, (size_t)2 * p.batch * std::max(n, 1) * 4, &d1))) return rc;
+    if ((rc = take_slot(io.g, 7, (size_t)p.batch * p.nseg_eff * (sizeof(DI) * 2 + sizeof(S1Chg)) + (size_t)p.batch * a.num_classes * 8, &dpart))) return rc;
+    DI* part1 = dpart.as<DI>();
+    DI* part2 = part1 + (size_t)p.batch * p.nseg_eff;
+    S1Chg* chg = (S1Chg*)(part2 + (size_t)p.batch * p.nseg_eff);
+    unsigned long long* gprob = (unsigned long long*)(chg + (size_t)p.batch * p.nseg_eff);
+    if ((rc = fir_split_distances_dev_(io.g, qsrc, nq, a.reduced, kLastFeature, d1.as<float>(), v.stream))) return rc;
+    const float* d2 = d1.as<float>() + (size_t)nq * n;
+    const size_t plds = (size_t)a.num_classes * 8;
+    int32_t* dcls = io.dres.as<int32_t>();
+    int32_t* dunrel = dcls + kBatch;
+    // a one-query call: the deciding workgroup writes the verdict to pinned host memory and the ticket itself
+    const bool self_publish = io.pinned && nq == 1;
+    const uint64_t ticket = io.next_ticket();
+    int32_t* hres = io.host_res(self_publish);
+    uint64_t* hticket = io.host_ticket(self_publish, kConvTicket);
+    if (p.nseg_eff == 1) {
+        hipLaunchKernelGGL(k_twd_conv_stage1<kS1Single>, dim3(nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, a.num_classes, a.type,
+                           a.threshold, dcls, dunrel, (DI*)nullptr, (S1Chg*)nullptr, (unsigned long long*)nullptr, n, d2, a.reduced, (DI*)nullptr, hres,
+                           kBatch, hticket, ticket);
+    } else {
+        if (a.type == 0) FIR_HIP(hipMemsetAsync(gprob, 0, (size_t)nq * a.num_classes * 8, v.stream));
+        hipLaunchKernelGGL(k_twd_conv_stage1<kS1Part>, dim3(p.nseg_eff, nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, a.num_classes, a.type,
+                           a.threshold, dcls, dunrel, part1, chg, gprob, p.seg_rows, d2, a.reduced, part2, (int32_t*)nullptr, 0, (uint64_t*)nullptr,
+                           (uint64_t)0);
+        hipLaunchKernelGGL(k_twd_conv_stage1<kS1Records>, dim3(p.nseg_eff, nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, a.num_classes,
+                           a.type, a.threshold, dcls, dunrel, part1, chg, gprob, p.seg_rows, d2, a.reduced, part2, (int32_t*)nullptr, 0,
+                           (uint64_t*)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(k_twd_conv_stage1<kS1Final>, dim3(nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, a.num_classes, a.type,
+                           a.threshold, dcls, dunrel, part1, chg, gprob, p.seg_rows, d2, a.reduced, part2, hres, kBatch, hticket, ticket);
+    }
+    FIR_HIP(hipGetLastError());
+    return io.collect(h_res, kConvWords, kConvTicket, ticket, self_publish);
+}
+
+// One fused launch for nq <= kFusedMaxQueries queries. *answered: every query's workgroups met in time.
+int prop_fused(TwdIo& io, const TwdPlan& p, int reduced, int nchunks, double threshold, const float* qsrc, int nq, int32_t* h_res, bool* answered) {
+    const fir_gallery_view& v = io.v;
+    int rc;
+    Slot fst;
+    if ((rc = take_slot(io.g, 2, (size_t)2 * kFusedMaxQueries * sizeof(FusedState), &fst))) return rc;
+    const void* gal4 = nullptr;
+    int dp4 = 0;
+    if ((rc = fir_gallery_tiled_(io.g, &gal4, &dp4))) return fir_fail_(rc, "no tiled gallery");
+    const uint64_t call_no = fir_gallery_next_counter_(io.g, 0);
+    const int parity = (int)(call_no & 1);
+    const unsigned long long gen_base = (unsigned long long)(call_no + 1) << 7;                        // meeting numbers that never repeat
+    const uint64_t ticket = io.next_ticket();
+    int32_t* dcls = io.dres.as<int32_t>();
+    hipLaunchKernelGGL(p.row->prop, dim3(p.fG, nq), dim3(kFusedBlock), 0, v.stream, (const float4*)gal4, dp4, (int)v.n, (int)((v.n + 63) / 64), v.cls, qsrc, v.d,
+                       reduced, nchunks, 1.0 / threshold, fst.as<FusedState>(), parity, gen_base, dcls, dcls + kBatch, dcls + 2 * kBatch,
+                       io.host_res(io.pinned), kBatch, io.host_ticket(io.pinned, kPropTicket), ticket);
+    FIR_HIP(hipGetLastError());
+    if ((rc = io.collect(h_res, kPropWords, kPropTicket, ticket, true))) return rc;
+    *answered = true;
+    for (int i = 0; i < nq; ++i) *answered = *answered && h_res[2 * kBatch + i] >= 0;      // -1: the workgroups did not meet in time
+    if (!*answered) FIR_HIP(hipStreamSynchronize(v.stream));
+    return FIR_OK;
+}
+
+// The launch-per-chunk form: all chunk distances cd[c][slot][n] from ONE pass over features [0, 256), then the decision kernels.
+int prop_staged(TwdIo& io, const TwdPlan& p, int reduced, int nchunks, double threshold, const float* qsrc, int nq, int32_t* h_res) {
+    const fir_gallery_view& v = io.v;
+    const int n = (int)v.n, nseg = p.nseg_eff;
+    int rc;
+    const int ob = std::max(8, (nq + 7) / 8 * 8);
+    Slot cd, acc, alive, pws;
+    if ((rc = take_slot(io.g, 4, (size_t)nchunks * ob * std::max(n, 1) * 4, &cd))) return rc;
+    if ((rc = take_slot(io.g, 5, (size_t)ob * std::max(n, 1) * 8, &acc))) return rc;
+    if ((rc = take_slot(io.g, 6, (size_t)ob * std::max(n, 1), &alive))) return rc;
+    if ((rc = take_slot(io.g, 7, (size_t)2 * ob * sizeof(PropState) + (size_t)nchunks * ob * sizeof(int) + (size_t)nchunks * ob * nseg * sizeof(DI) + 64, &pws))) return rc;
+    DI* ppart = pws.as<DI>();
+    PropState* pstate = (PropState*)(ppart + (size_t)nchunks * ob * nseg);
+    int* pcnt = (int*)(pstate + 2 * ob);
+    if ((rc = fir_subrange_distances_dev_(io.g, qsrc, nq, 0, kLastFeature, reduced, cd.as<float>(), v.stream))) return rc;
+    int32_t* dcls = io.dres.as<int32_t>();
+    int32_t* dunrel = dcls + kBatch;
+    int32_t* dchunks = dcls + 2 * kBatch;
+    const bool self_publish = io.pinned && nq == 1 && nseg == 1;    // the deciding workgroup writes verdict and ticket itself
+    const uint64_t ticket = io.next_ticket();
+    if (nseg == 1) {
+        hipLaunchKernelGGL(k_twd_proposed, dim3(nq), dim3(kBlock), 0, v.stream, cd.as<float>(), nq, nchunks, acc.as<double>(), alive.as<uint8_t>(), v.cls, n,
+                           1.0 / threshold, dcls, dunrel, dchunks, io.host_res(self_publish), kBatch, io.host_ticket(self_publish, kPropTicket), ticket);
+    } else {
+        // nchunks + 1 launches + the finish (three launches per chunk before); the two state buffers swap roles every launch
+        hipLaunchKernelGGL(k_twd_prop_init, dim3((2 * ob + 63) / 64), dim3(64), 0, v.stream, pstate, 2 * ob);
+        FIR_HIP(hipMemsetAsync(pcnt, 0, (size_t)nchunks * nq * sizeof(int), v.stream));
+        for (int c = 0; c <= nchunks; ++c)
+            hipLaunchKernelGGL(k_twd_prop_chunk, dim3(nseg, nq), dim3(kBlock), 0, v.stream, cd.as<float>(), nq, c, nchunks, acc.as<double>(),
+                               alive.as<uint8_t>(), v.cls, n, p.seg_rows, 1.0 / threshold, pstate + (size_t)((c + 1) & 1) * ob,
+                               pstate + (size_t)(c & 1) * ob, ppart, pcnt);
+        hipLaunchKernelGGL(k_twd_prop_finish, dim3((nq + 63) / 64), dim3(64), 0, v.stream, nq, nchunks, nseg, ppart, pcnt, v.cls,
+                           pstate + (size_t)(nchunks & 1) * ob, dcls, dunrel, dchunks);
+    }
+    FIR_HIP(hipGetLastError());
+    return io.collect(h_res, kPropWords, kPropTicket, ticket, self_publish);
+}
+
+}  // namespace
+
+extern "C" {
+
 int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32_t num_classes, int32_t type, double threshold,
                          int32_t reduced_features_count, int32_t* class_out, int32_t* unreliable_out) {
     fir_gallery_view v;
     int rc = check_common(g, queries, qb, reduced_features_count, &v);
     if (rc) return rc;
-    if (!class_out) return twd_fail(FIR_ERR_ARG, "class_out is NULL");
-    if (type < 0 || type > 2) return twd_fail(FIR_ERR_ARG, "type %d outside [0,2]", type);
+    if (!class_out) return fir_fail_(FIR_ERR_ARG, "class_out is NULL");
+    if (type < 0 || type > 2) return fir_fail_(FIR_ERR_ARG, "type %d outside [0,2]", type);
     if (num_classes < 5 || (size_t)num_classes * 8 > 60 * 1024)
-        return twd_fail(FIR_ERR_ARG, "num_classes=%d outside [5, 7680] (top-5 posteriors, ImageTesting.cpp:141; LDS table)", num_classes);
+        return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [5, 7680] (top-5 posteriors, ImageTesting.cpp:141; LDS table)", num_classes);
     if (qb == 0) return FIR_OK;
-    TWD_HIP(hipSetDevice(v.device));
+    FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
-    const int n = (int)v.n;
-    const int batch = std::min(batch_for(n, 8), std::max(8, (qb + 7) / 8 * 8));
-    TWD_SLOT(dq, 0, (size_t)batch * v.d * 4);
-    TWD_SLOT(dres, 3, (size_t)2 * kBatch * 4);                 // class[kBatch], unreliable[kBatch]
-    int32_t* dcls = dres.as<int32_t>();
-    int32_t* dunrel = dcls + kBatch;
-    // galleries beyond a few spans: the rows of every query are split over `nseg` workgroups (see k_twd_conv_stage1)
-    const int nseg = n > 4 * kSpan ? std::min(256, (n + 2 * kSpan - 1) / (2 * kSpan)) : 1;
-    const int seg_rows = nseg > 1 ? ((n + nseg - 1) / nseg + kSpan - 1) / kSpan * kSpan : n;
-    const int nseg_eff = nseg > 1 ? (n + seg_rows - 1) / seg_rows : 1;
-    // (the distance tables and segment records of the launch-per-stage form are taken from the handle's scratch when that form runs)
-    Slot d1, dpart;
-    DI *part1 = nullptr, *part2 = nullptr;
-    S1Chg* chg = nullptr;
-    unsigned long long* gprob = nullptr;
-    auto stage_scratch = [&]() -> int {
-        int rc2;
-        if ((rc2 = fir_gallery_scratch_(g, 1, std::max<size_t>((size_t)2 * batch * std::max(n, 1) * 4, 16), &d1.p))) return rc2;    // [0, reduced) distances of the batch, then [reduced, 256)
-        if ((rc2 = fir_gallery_scratch_(g, 7, std::max<size_t>((size_t)batch * nseg_eff * (sizeof(DI) * 2 + sizeof(S1Chg)) + (size_t)batch * num_classes * 8, 16), &dpart.p)))
-            return rc2;
-        part1 = dpart.as<DI>();
-        part2 = part1 + (size_t)batch * nseg_eff;
-        chg = (S1Chg*)(part2 + (size_t)batch * nseg_eff);
-        gprob = (unsigned long long*)(chg + (size_t)batch * nseg_eff);
-        return FIR_OK;
-    };
-    // Few queries: ONE launch per internal batch (k_twd_conv_fused), as for the proposed classifier (FIR_TWD_FUSED).
-    const char* fenv = fir_knob_("FIR_TWD_FUSED");
-    const int fmode = fenv ? std::atoi(fenv) : 1;
-    const int64_t tiles64 = ((int64_t)n + 63) / 64;
-    bool fused = fmode != 0 && n > 0 && (fmode == 2 || qb <= kFusedMaxQueries) && (v.metric == 0 || v.metric == 1) && reduced_features_count % 4 == 0 &&
-                 num_classes <= 4096;                                   // (the posteriors of a workgroup sit in LDS next to 6 KiB of static tables)
-    const int fq = std::min(qb, kFusedMaxQueries);
-    int fG = 0, fT = 0;
-    if (fused) {
-        for (int t : {1, 2, 4, 8, 16}) {
-            const int64_t g_need = (tiles64 + 8 * t - 1) / (8 * t);
-            if (g_need <= std::min(256, std::max(1, v.cus / fq))) { fT = t; fG = (int)g_need; break; }
-        }
-        // every query of a fused launch reads the rows for itself: beyond one tile per wave that costs more than the launches it saves
-        // (100 000 x 512, 8 queries: 146 against 96 us), so several queries go this way only while every wave has a single tile
-        if (!fT || (fq > 1 && fT > 1)) fused = false;
-        if (fused) {      // every workgroup of the launch must be resident at once: the occupancy query decides, not an assumption
-            const void* f16 = v.metric == 0 ? (fT == 1 ? (const void*)k_twd_conv_fused<fir::kL2, 1> : fT == 2 ? (const void*)k_twd_conv_fused<fir::kL2, 2>
-                                                     : fT == 4 ? (const void*)k_twd_conv_fused<fir::kL2, 4> : fT == 8 ? (const void*)k_twd_conv_fused<fir::kL2, 8>
-                                                                                                                      : (const void*)k_twd_conv_fused<fir::kL2, 16>)
-                                            : (fT == 1 ? (const void*)k_twd_conv_fused<fir::kChi2, 1> : fT == 2 ? (const void*)k_twd_conv_fused<fir::kChi2, 2>
-                                                     : fT == 4 ? (const void*)k_twd_conv_fused<fir::kChi2, 4> : fT == 8 ? (const void*)k_twd_conv_fused<fir::kChi2, 8>
-                                                                                                                        : (const void*)k_twd_conv_fused<fir::kChi2, 16>);
-            if (!fused_grid_fits(f16, kFusedBlock, type == 0 ? (size_t)num_classes * 8 : 8, fG * fq, v.cus)) fused = false;
-        }
-    }
-    const int fbatch = fused ? kFusedMaxQueries : batch;
-    for (int q0 = 0; q0 < qb; q0 += fbatch) {
-        const int nq = std::min(fbatch, qb - q0);
-        int32_t h_res[2 * kBatch];
-        bool answered = false;
-        if (fused) {
-            void* pin_base = nullptr; size_t pin_cap = 0; uint64_t* pin_res = nullptr;
-            const bool pinned = fir_gallery_pin_(g, &pin_base, &pin_cap, &pin_res) == FIR_OK && (size_t)nq * v.d * 4 <= pin_cap;
-            const float* qsrc = dq.as<float>();
-            if (pinned) { std::memcpy(pin_base, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4); qsrc = (const float*)pin_base; }
-            else TWD_HIP(hipMemcpyAsync(dq.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
-            TWD_SLOT(cst, 16, (size_t)kFusedMaxQueries * sizeof(ConvState) + 64);        // (a fresh slot reads as zeros; the kernel leaves it so)
-            ConvState* cstate = cst.as<ConvState>();
-            unsigned int* done_ctr = (unsigned int*)(cstate + kFusedMaxQueries);
-            const void* gal4 = nullptr;
-            int dp4 = 0;
-            if ((rc = fir_gallery_tiled_(g, &gal4, &dp4))) return twd_fail(rc, "no tiled gallery");
-            const uint64_t ticket = pinned ? fir_gallery_next_ticket_(g) : 0;
-            typedef void (*conv_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, int, double, ConvState*, unsigned long long, int32_t*,
-                                    int32_t*, int32_t*, int, uint64_t*, uint64_t, unsigned int*);
-            const unsigned long long gen_base = (unsigned long long)(fir_gallery_next_counter_(g, 1) + 1) << 7;      // meeting numbers that never repeat
-            conv_fn fn = nullptr;
-#define FIR_CONV_PICK(M)                                                                                               \
-    fn = fT == 1 ? k_twd_conv_fused<M, 1> : fT == 2 ? k_twd_conv_fused<M, 2> : fT == 4 ? k_twd_conv_fused<M, 4>        \
-       : fT == 8 ? k_twd_conv_fused<M, 8> : k_twd_conv_fused<M, 16>
-            if (v.metric == 0) { FIR_CONV_PICK(fir::kL2); } else { FIR_CONV_PICK(fir::kChi2); }
-#undef FIR_CONV_PICK
-            const size_t flds = type == 0 ? (size_t)num_classes * 8 : 8;      // <= 32 KiB
-            hipLaunchKernelGGL(fn, dim3(fG, nq), dim3(kFusedBlock), flds, v.stream, (const float4*)gal4, dp4, n, (int)tiles64, v.cls, qsrc, v.d,
-                               reduced_features_count, num_classes, type, threshold, cstate, gen_base, dcls, dunrel, pinned ? (int32_t*)pin_res : (int32_t*)nullptr, kBatch,
-                               pinned ? pin_res + kBatch : (uint64_t*)nullptr, ticket, done_ctr);
-            TWD_HIP(hipGetLastError());
-            if (pinned) {
-                if ((rc = fir_gallery_wait_ticket_(g, pin_res + kBatch, ticket))) return rc;
-                std::memcpy(h_res, pin_res, sizeof(h_res));
-            } else {
-                TWD_HIP(hipMemcpyAsync(h_res, dres.p, sizeof(h_res), hipMemcpyDeviceToHost, v.stream));
-                TWD_HIP(hipStreamSynchronize(v.stream));
-            }
-            answered = true;
-            for (int i = 0; i < nq; ++i) answered = answered && h_res[kBatch + i] != 2;        // 2: the workgroups did not meet in time
-            if (!answered) {
-                TWD_HIP(hipStreamSynchronize(v.stream));
-                TWD_HIP(hipMemsetAsync(cst.p, 0, (size_t)kFusedMaxQueries * sizeof(ConvState) + 64, v.stream));      // whatever the launch left behind
-            }
-        }
-        if (answered) {
-        } else if (n == 0) {
+    const TwdPlan p = plan_conventional(v, qb, num_classes, type, reduced_features_count);
+    const ConvArgs a{num_classes, type, threshold, reduced_features_count};
+    TwdIo io{g, v};
+    if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
+    if ((rc = take_slot(g, 3, (size_t)kConvWords * 4, &io.dres))) return rc;
+    for (int q0 = 0; q0 < qb; q0 += p.step) {
+        const int nq = std::min(p.step, qb - q0);
+        int32_t h_res[kConvWords];
+        if (v.n == 0) {
             for (int i = 0; i < nq; ++i) { h_res[i] = -1; h_res[kBatch + i] = 1; }
         } else {
-            if ((rc = stage_scratch())) return rc;
-            // both stages are queued back to back -- the second one decides on the device which queries it concerns -- and
-            // the verdicts come back with ONE copy and ONE synchronisation per batch
-            // small batches: the kernels read the queries from pinned host memory and the verdicts come back through it, with
-            // a ticket instead of a stream synchronisation (no copy engine on either side)
-            void* pin_base = nullptr; size_t pin_cap = 0; uint64_t* pin_res = nullptr;
-            const bool pinned = fir_gallery_pin_(g, &pin_base, &pin_cap, &pin_res) == FIR_OK && (size_t)nq * v.d * 4 <= pin_cap;
-            const float* qsrc = dq.as<float>();
-            if (pinned) { std::memcpy(pin_base, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4); qsrc = (const float*)pin_base; }
-            else TWD_HIP(hipMemcpyAsync(dq.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
-            // both partial distances from one pass over features [0, 256); every stage is queued back to back
-            if ((rc = fir_split_distances_dev_(g, qsrc, nq, reduced_features_count, kLastFeature, d1.as<float>(), v.stream))) return rc;
-            const float* d2 = d1.as<float>() + (size_t)nq * n;
-            const size_t plds = (size_t)num_classes * 8;
-            // a one-query call: the deciding workgroup writes the verdict to pinned host memory and the ticket itself
-            const bool self_publish = pinned && nq == 1;
-            const uint64_t ticket = pinned ? fir_gallery_next_ticket_(g) : 0;
-            int32_t* hres = self_publish ? (int32_t*)pin_res : (int32_t*)nullptr;
-            uint64_t* hticket = self_publish ? pin_res + kBatch : (uint64_t*)nullptr;
-            if (nseg_eff == 1) {
-                hipLaunchKernelGGL(k_twd_conv_stage1<kS1Single>, dim3(nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, num_classes, type,
-                                   threshold, dcls, dunrel, (DI*)nullptr, (S1Chg*)nullptr, (unsigned long long*)nullptr, n, d2,
-                                   reduced_features_count, (DI*)nullptr, hres, kBatch, hticket, ticket);
-            } else {
-                if (type == 0) TWD_HIP(hipMemsetAsync(gprob, 0, (size_t)nq * num_classes * 8, v.stream));
-                hipLaunchKernelGGL(k_twd_conv_stage1<kS1Part>, dim3(nseg_eff, nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, num_classes,
-                                   type, threshold, dcls, dunrel, part1, chg, gprob, seg_rows, d2, reduced_features_count, part2, (int32_t*)nullptr, 0,
-                                   (uint64_t*)nullptr, (uint64_t)0);
-                hipLaunchKernelGGL(k_twd_conv_stage1<kS1Records>, dim3(nseg_eff, nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n,
-                                   num_classes, type, threshold, dcls, dunrel, part1, chg, gprob, seg_rows, d2, reduced_features_count, part2,
-                                   (int32_t*)nullptr, 0, (uint64_t*)nullptr, (uint64_t)0);
-                hipLaunchKernelGGL(k_twd_conv_stage1<kS1Final>, dim3(nq), dim3(kBlock), plds, v.stream, d1.as<float>(), v.cls, n, num_classes, type,
-                                   threshold, dcls, dunrel, part1, chg, gprob, seg_rows, d2, reduced_features_count, part2, hres, kBatch, hticket,
-                                   ticket);
-            }
-            TWD_HIP(hipGetLastError());
-            if (pinned) {
-                if (!self_publish) {
-                    hipLaunchKernelGGL(k_twd_publish, dim3(1), dim3(256), 0, v.stream, dcls, 2 * kBatch, (int32_t*)pin_res, pin_res + kBatch, ticket);
-                    TWD_HIP(hipGetLastError());
-                }
-                if ((rc = fir_gallery_wait_ticket_(g, pin_res + kBatch, ticket))) return rc;
-                std::memcpy(h_res, pin_res, sizeof(h_res));
-            } else {
-                TWD_HIP(hipMemcpyAsync(h_res, dres.p, sizeof(h_res), hipMemcpyDeviceToHost, v.stream));
-                TWD_HIP(hipStreamSynchronize(v.stream));
-            }
+            const float* qsrc = nullptr;
+            bool answered = false;
+            if ((rc = io.stage(queries + (size_t)q0 * v.d, nq, &qsrc))) return rc;
+            if (p.fused && (rc = conv_fused(io, p, a, qsrc, nq, h_res, &answered))) return rc;
+            if (!answered && (rc = conv_staged(io, p, a, qsrc, nq, h_res))) return rc;
         }
         for (int i = 0; i < nq; ++i) {
             class_out[q0 + i] = h_res[i];
@@ -1366,146 +1500,37 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
     fir_gallery_view v;
     int rc = check_common(g, queries, qb, reduced_features_count, &v);
     if (rc) return rc;
-    if (!class_out) return twd_fail(FIR_ERR_ARG, "class_out is NULL");
-    if (!(threshold > 0)) return twd_fail(FIR_ERR_ARG, "threshold must be > 0");
+    if (!class_out) return fir_fail_(FIR_ERR_ARG, "class_out is NULL");
+    if (!(threshold > 0)) return fir_fail_(FIR_ERR_ARG, "threshold must be > 0");
     if (qb == 0) return FIR_OK;
-    TWD_HIP(hipSetDevice(v.device));
+    FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
-    const int n = (int)v.n;
     // chunks cover [0,256) in steps of reduced_features_count; the reference reads past 256 when the step does not
     // divide it (ImageTesting.cpp:229,250) -- only steps that divide 256 are accepted here
     if (kLastFeature % reduced_features_count != 0)
-        return twd_fail(FIR_ERR_ARG, "reduced_features_count=%d must divide %d", reduced_features_count, kLastFeature);
+        return fir_fail_(FIR_ERR_ARG, "reduced_features_count=%d must divide %d", reduced_features_count, kLastFeature);
     const int nchunks = kLastFeature / reduced_features_count;
-    // Few queries: ONE launch per internal batch (k_twd_prop_fused). FIR_TWD_FUSED=0 never, 2 = whatever the batch (tests).
-    const char* fenv = fir_knob_("FIR_TWD_FUSED");
-    const int fmode = fenv ? std::atoi(fenv) : 1;
-    const int64_t tiles = ((int64_t)n + 63) / 64;
-    bool fused = fmode != 0 && n > 0 && (fmode == 2 || qb <= kFusedMaxQueries) && (v.metric == 0 || v.metric == 1) &&
-                 reduced_features_count % 4 == 0 && reduced_features_count <= 128 && nchunks <= kFusedMaxChunks;
-    const int fq = std::min(qb, kFusedMaxQueries);                       // queries per fused launch
-    int fG = 0, fT = 0;
-    if (fused) {
-        // at most one workgroup per CU over all the queries of a launch: the workgroups of a query wait for each other
-        fG = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, v.cus / fq), (tiles + 7) / 8));
-        const int64_t need = (tiles + (int64_t)fG * 8 - 1) / ((int64_t)fG * 8);
-        fT = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 16 ? 16 : 0;
-        if (!fT) fused = false;
-        if (fused) {      // every workgroup of the launch must be resident at once: the occupancy query decides, not an assumption
-            const void* f16 = v.metric == 0 ? (fT == 1 ? (const void*)k_twd_prop_fused<fir::kL2, 1> : fT == 2 ? (const void*)k_twd_prop_fused<fir::kL2, 2>
-                                                     : fT == 4 ? (const void*)k_twd_prop_fused<fir::kL2, 4> : fT == 8 ? (const void*)k_twd_prop_fused<fir::kL2, 8>
-                                                                                                                      : (const void*)k_twd_prop_fused<fir::kL2, 16>)
-                                            : (fT == 1 ? (const void*)k_twd_prop_fused<fir::kChi2, 1> : fT == 2 ? (const void*)k_twd_prop_fused<fir::kChi2, 2>
-                                                     : fT == 4 ? (const void*)k_twd_prop_fused<fir::kChi2, 4> : fT == 8 ? (const void*)k_twd_prop_fused<fir::kChi2, 8>
-                                                                                                                        : (const void*)k_twd_prop_fused<fir::kChi2, 16>);
-            if (!fused_grid_fits(f16, kFusedBlock, 0, fG * fq, v.cus)) fused = false;
-        }
-    }
-    const int batch = fused ? 8 : std::min(batch_for(n, (size_t)nchunks * 4 + 9, (size_t)1 << 30), std::max(8, (qb + 7) / 8 * 8));
-    TWD_SLOT(dq, 0, (size_t)batch * v.d * 4);
-    TWD_SLOT(dres, 3, (size_t)3 * kBatch * 4);                 // class, unreliable, chunks
-    int32_t* dcls = dres.as<int32_t>();
-    int32_t* dunrel = dcls + kBatch;
-    int32_t* dchunks = dcls + 2 * kBatch;
-    // large galleries: the rows of every query are split over `nseg` workgroups, one launch per chunk
-    const int nseg_want = n > 16384 ? std::min(256, (n + 8191) / 8192) : 1;
-    const int seg_rows = nseg_want > 1 ? ((n + nseg_want - 1) / nseg_want + 255) / 256 * 256 : n;
-    const int nseg = nseg_want > 1 ? (n + seg_rows - 1) / seg_rows : 1;
-    for (int q0 = 0; q0 < qb; q0 += batch) {
-        const int nq = std::min(batch, qb - q0);
-        int32_t h_res[3 * kBatch];
-        int32_t* h_cls = h_res;
-        int32_t* h_unrel = h_res + kBatch;
-        int32_t* h_chunks = h_res + 2 * kBatch;
-        if (n == 0) {
-            for (int i = 0; i < nq; ++i) { h_cls[i] = -1; h_unrel[i] = 0; h_chunks[i] = 0; }
+    const TwdPlan p = plan_proposed(v, qb, reduced_features_count, nchunks);
+    TwdIo io{g, v};
+    if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
+    if ((rc = take_slot(g, 3, (size_t)kPropWords * 4, &io.dres))) return rc;
+    for (int q0 = 0; q0 < qb; q0 += p.step) {
+        const int nq = std::min(p.step, qb - q0);
+        int32_t h_res[kPropWords];
+        if (v.n == 0) {
+            for (int i = 0; i < nq; ++i) { h_res[i] = -1; h_res[kBatch + i] = 0; h_res[2 * kBatch + i] = 0; }
         } else {
-            void* pin_base = nullptr; size_t pin_cap = 0; uint64_t* pin_res = nullptr;      // as in fir_twd_conventional
-            const bool pinned = fir_gallery_pin_(g, &pin_base, &pin_cap, &pin_res) == FIR_OK && (size_t)nq * v.d * 4 <= pin_cap;
-            const float* qsrc = dq.as<float>();
-            if (pinned) { std::memcpy(pin_base, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4); qsrc = (const float*)pin_base; }
-            else TWD_HIP(hipMemcpyAsync(dq.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
+            const float* qsrc = nullptr;
             bool answered = false;
-            if (fused) {
-                TWD_SLOT(fst, 2, (size_t)2 * kFusedMaxQueries * sizeof(FusedState));
-                const void* gal4 = nullptr;
-                int dp4 = 0;
-                if ((rc = fir_gallery_tiled_(g, &gal4, &dp4))) return twd_fail(rc, "no tiled gallery");
-                const uint64_t call_no = fir_gallery_next_counter_(g, 0);
-                const int parity = (int)(call_no & 1);
-                const unsigned long long gen_base = (unsigned long long)(call_no + 1) << 7;                        // meeting numbers that never repeat
-                const uint64_t ticket = pinned ? fir_gallery_next_ticket_(g) : 0;
-                typedef void (*fused_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, double, FusedState*, int, unsigned long long,
-                                         int32_t*, int32_t*, int32_t*, int32_t*, int, uint64_t*, uint64_t);
-                fused_fn fn = nullptr;
-#define FIR_FUSED_PICK(M)                                                                                              \
-    fn = fT == 1 ? k_twd_prop_fused<M, 1> : fT == 2 ? k_twd_prop_fused<M, 2> : fT == 4 ? k_twd_prop_fused<M, 4>        \
-       : fT == 8 ? k_twd_prop_fused<M, 8> : k_twd_prop_fused<M, 16>
-                if (v.metric == 0) { FIR_FUSED_PICK(fir::kL2); } else { FIR_FUSED_PICK(fir::kChi2); }
-#undef FIR_FUSED_PICK
-                hipLaunchKernelGGL(fn, dim3(fG, nq), dim3(kFusedBlock), 0, v.stream, (const float4*)gal4, dp4, n, (int)tiles, v.cls, qsrc, v.d,
-                                   reduced_features_count, nchunks, 1.0 / threshold, fst.as<FusedState>(), parity, gen_base, dcls, dunrel, dchunks,
-                                   pinned ? (int32_t*)pin_res : (int32_t*)nullptr, kBatch, pinned ? pin_res + 2 * kBatch : (uint64_t*)nullptr, ticket);
-                TWD_HIP(hipGetLastError());
-                if (pinned) {
-                    if ((rc = fir_gallery_wait_ticket_(g, pin_res + 2 * kBatch, ticket))) return rc;
-                    std::memcpy(h_res, pin_res, sizeof(h_res));
-                } else {
-                    TWD_HIP(hipMemcpyAsync(h_res, dres.p, sizeof(h_res), hipMemcpyDeviceToHost, v.stream));
-                    TWD_HIP(hipStreamSynchronize(v.stream));
-                }
-                answered = true;
-                for (int i = 0; i < nq; ++i) answered = answered && h_chunks[i] >= 0;      // -1: the workgroups did not meet in time
-                if (!answered) TWD_HIP(hipStreamSynchronize(v.stream));
-            }
-            if (!answered) {
-                const int ob = std::max(8, (nq + 7) / 8 * 8);
-                TWD_SLOT(cd, 4, (size_t)nchunks * ob * std::max(n, 1) * 4);
-                TWD_SLOT(acc, 5, (size_t)ob * std::max(n, 1) * 8);
-                TWD_SLOT(alive, 6, (size_t)ob * std::max(n, 1));
-                TWD_SLOT(pws, 7, (size_t)2 * ob * sizeof(PropState) + (size_t)nchunks * ob * sizeof(int) + (size_t)nchunks * ob * nseg * sizeof(DI) + 64);
-                DI* ppart = pws.as<DI>();
-                PropState* pstate = (PropState*)(ppart + (size_t)nchunks * ob * nseg);
-                int* pcnt = (int*)(pstate + 2 * ob);
-                // all chunk distances cd[c][slot][n] from ONE pass over features [0, 256)
-                if ((rc = fir_subrange_distances_dev_(g, qsrc, nq, 0, kLastFeature, reduced_features_count, cd.as<float>(), v.stream))) return rc;
-                const bool self_publish = pinned && nq == 1 && nseg == 1;    // the deciding workgroup writes verdict and ticket itself
-                const uint64_t ticket = pinned ? fir_gallery_next_ticket_(g) : 0;
-                if (nseg == 1) {
-                    hipLaunchKernelGGL(k_twd_proposed, dim3(nq), dim3(kBlock), 0, v.stream, cd.as<float>(), nq, nchunks, acc.as<double>(),
-                                       alive.as<uint8_t>(), v.cls, n, 1.0 / threshold, dcls, dunrel, dchunks,
-                                       self_publish ? (int32_t*)pin_res : (int32_t*)nullptr, kBatch,
-                                       self_publish ? pin_res + 2 * kBatch : (uint64_t*)nullptr, ticket);
-                } else {
-                    // nchunks + 1 launches + the finish (three launches per chunk before); the two state buffers swap roles every launch
-                    hipLaunchKernelGGL(k_twd_prop_init, dim3((2 * ob + 63) / 64), dim3(64), 0, v.stream, pstate, 2 * ob);
-                    TWD_HIP(hipMemsetAsync(pcnt, 0, (size_t)nchunks * nq * sizeof(int), v.stream));
-                    for (int c = 0; c <= nchunks; ++c)
-                        hipLaunchKernelGGL(k_twd_prop_chunk, dim3(nseg, nq), dim3(kBlock), 0, v.stream, cd.as<float>(), nq, c, nchunks, acc.as<double>(),
-                                           alive.as<uint8_t>(), v.cls, n, seg_rows, 1.0 / threshold, pstate + (size_t)((c + 1) & 1) * ob,
-                                           pstate + (size_t)(c & 1) * ob, ppart, pcnt);
-                    hipLaunchKernelGGL(k_twd_prop_finish, dim3((nq + 63) / 64), dim3(64), 0, v.stream, nq, nchunks, nseg, ppart, pcnt, v.cls,
-                                       pstate + (size_t)(nchunks & 1) * ob, dcls, dunrel, dchunks);
-                }
-                TWD_HIP(hipGetLastError());
-                if (pinned) {
-                    if (!self_publish) {
-                        hipLaunchKernelGGL(k_twd_publish, dim3(1), dim3(256), 0, v.stream, dcls, 3 * kBatch, (int32_t*)pin_res, pin_res + 2 * kBatch, ticket);
-                        TWD_HIP(hipGetLastError());
-                    }
-                    if ((rc = fir_gallery_wait_ticket_(g, pin_res + 2 * kBatch, ticket))) return rc;
-                    std::memcpy(h_res, pin_res, sizeof(h_res));
-                } else {
-                    TWD_HIP(hipMemcpyAsync(h_res, dres.p, sizeof(h_res), hipMemcpyDeviceToHost, v.stream));
-                    TWD_HIP(hipStreamSynchronize(v.stream));
-                }
-            }
+            if ((rc = io.stage(queries + (size_t)q0 * v.d, nq, &qsrc))) return rc;
+            if (p.fused && (rc = prop_fused(io, p, reduced_features_count, nchunks, threshold, qsrc, nq, h_res, &answered))) return rc;
+            if (!answered && (rc = prop_staged(io, p, reduced_features_count, nchunks, threshold, qsrc, nq, h_res))) return rc;
         }
         for (int i = 0; i < nq; ++i) {
-            class_out[q0 + i] = h_cls[i];
-            if (unreliable_out) unreliable_out[q0 + i] = h_unrel[i];
-            if (chunks_out) chunks_out[q0 + i] = h_chunks[i];
+            class_out[q0 + i] = h_res[i];
+            if (unreliable_out) unreliable_out[q0 + i] = h_res[kBatch + i];
+            if (chunks_out) chunks_out[q0 + i] = h_res[2 * kBatch + i];
         }
     }
     return FIR_OK;
