@@ -58,6 +58,7 @@ SYMBOLS = [
     ("fir_range_distances_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_twd_conventional", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp]),
     ("fir_twd_proposed", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    ("fir_twd_last_dispatch", C.c_int, [_vp, _vp]),
     ("fir_cls_create", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(_vp)]),
     ("fir_cls_create_dev", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(_vp)]),
     ("fir_cls_destroy", C.c_int, [_vp]),
@@ -216,6 +217,12 @@ class DispatchInfo(C.Structure):
                 ("grid_y", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32), ("vgprs", C.c_int32), ("queries_per_pass", C.c_int32),
                 ("bytes_per_launch", C.c_double), ("flops_per_launch", C.c_double), ("warmup_calls_left", C.c_int32), ("reserved", C.c_int32),
                 ("knobs", C.c_char * 160)]
+
+
+class TwdDispatchInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("classifier", C.c_int32), ("planned_fused", C.c_int32), ("tiles_per_wave", C.c_int32),
+                ("workgroups_per_query", C.c_int32), ("queries_per_launch", C.c_int32), ("fused_launches", C.c_int32),
+                ("fused_gave_up", C.c_int32), ("staged_batches", C.c_int32), ("reserved", C.c_int32), ("kernel", C.c_char * 160)]
 
 
 SHADOW_NONE, SHADOW_FP16, SHADOW_ALL = 0, 1, 2
@@ -390,6 +397,17 @@ class Gallery:
         _check(lib().fir_twd_proposed(self._h, pq, q.shape[0], reduced_features_count, threshold, cls.ctypes.data_as(_vp),
                                       unrel.ctypes.data_as(_vp), chunks.ctypes.data_as(_vp)))
         return cls, unrel, chunks
+
+    def twd_last_dispatch(self):
+        """Which form answered the most recent twd_conventional / twd_proposed call on this handle (fir_twd_last_dispatch): a host-side
+        record, reading it does not touch the device."""
+        o = TwdDispatchInfo()
+        o.struct_bytes = C.sizeof(TwdDispatchInfo)
+        _check(lib().fir_twd_last_dispatch(self._h, C.byref(o)))
+        return {"classifier": {0: "conventional", 1: "proposed"}.get(o.classifier), "planned_fused": o.planned_fused,
+                "tiles_per_wave": o.tiles_per_wave, "workgroups_per_query": o.workgroups_per_query, "queries_per_launch": o.queries_per_launch,
+                "fused_launches": o.fused_launches, "fused_gave_up": o.fused_gave_up, "staged_batches": o.staged_batches,
+                "kernel": o.kernel.decode()}
 
     def classes_of(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

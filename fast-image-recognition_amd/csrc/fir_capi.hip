@@ -87,6 +87,7 @@ struct fir_gallery {
     bool gemm_failed = false; // automatic mode: the matrix-core path could not be set up for this shape (rows too long): scan
     fir_gemm* gemm = nullptr; // created on first use
     fir_dispatch_info last{}; // dominant kernel of the most recent search
+    fir_twd_dispatch_info twd_last{0, -1};   // fir_twd_last_dispatch (fir_twd.hip writes it through fir_gallery_twd_record_); classifier -1: no call yet
     int call_launches = 0;    // scan launches of the current call (note_dispatch)
     bool quiet = false;       // scans on behalf of another path (the matrix-core path's uncertified queries): not recorded, not timed
     int sample_groups = 0; int64_t sample_group_stride = 0;   // run_pass (generic k_scan, top-1): ScanArgs::groups / group_stride
@@ -1590,6 +1591,7 @@ int fir_gallery_pin_(fir_gallery* g, void** base, size_t* query_bytes, uint64_t*
 }
 uint64_t fir_gallery_next_ticket_(fir_gallery* g) { return ++g->one_ticket; }
 uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot) { return g->counters[slot & 3]++; }
+fir_twd_dispatch_info* fir_gallery_twd_record_(fir_gallery* g) { return &g->twd_last; }
 // The one ticket wait (fir_internal.h): cheaper than hipStreamSynchronize for calls that take tens of microseconds.
 int fir_wait_ticket_(hipStream_t st, volatile uint64_t* flag, uint64_t ticket) {
     const auto t0 = std::chrono::steady_clock::now();

@@ -75,6 +75,8 @@ extern "C" int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4); 
 extern "C" int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out);
 // Per-handle call counters of the other translation units (slot 0: fir_twd.hip's fused classifier): returns the value before the increment.
 extern "C" uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot);
+// The handle's record of its most recent fir_twd_* call (fir_twd_last_dispatch): host memory, written by fir_twd.hip's drivers.
+extern "C" fir_twd_dispatch_info* fir_gallery_twd_record_(fir_gallery* g);
 
 // d_out[(ci * qb + q) * n + row] = distance(query q, row) over sub-range ci = [start + ci*step, start + (ci+1)*step), for
 // every sub-range of [start, end): ONE gallery pass (k_scan_subranges) when step is a multiple of 32 features, one

@@ -36,6 +36,13 @@ struct DI {
     double d;
     int i;
 };
+// exp(-100 d) of one row (DIST_WEIGHT = 100, ImageTesting.cpp:113,119). A NaN distance gives a NaN posterior, which the reference's
+// `probab > probabs[c]` (:120) never takes: it counts as 0 here, because the kernels take the class maximum on the BIT PATTERN, where
+// a NaN would beat every number and then be passed over by the top-5 sum -- the class would lose its posterior.
+__device__ __forceinline__ double posterior(double d) {
+    const double probab = exp(-d * 100);
+    return probab == probab ? probab : 0.0;
+}
 __device__ __forceinline__ DI later_wins_if_smaller(const DI earlier, const DI later) { return later.d < earlier.d ? later : earlier; }
 __device__ __forceinline__ DI shfl_up_di(const DI v, int off) {
     DI o;
@@ -161,7 +168,7 @@ __global__ void __launch_bounds__(kBlock) k_twd_conv_stage1(const float* __restr
                 const double d = (double)sd[r];                                     // distances[j] (double) (:117)
                 if (d < own.d) { own.d = d; own.i = base + r; }
                 if (with_prob) {
-                    const double probab = exp(-d * 100);                            // DIST_WEIGHT = 100 (:113,119)
+                    const double probab = posterior(d);                             // (:119)
                     const int cl = sc[r];
                     if (cl != run_class) {
                         if (run_class >= 0 && run_class < num_classes) atomicMax(&probabs[run_class], (unsigned long long)__double_as_longlong(run_max));
@@ -937,7 +944,7 @@ __global__ void __launch_bounds__(kFusedBlock) k_twd_conv_fused(const float4* __
         mloc = d1[i] < mloc ? d1[i] : mloc;                            // (NaN never enters, as it never sets a record)
         if (v2[i] < m2d) { m2d = v2[i]; m2r = row; }
         if (with_prob) {
-            const double probab = exp(-(double)d1[i] * 100);           // DIST_WEIGHT = 100 (:113,119)
+            const double probab = posterior((double)d1[i]);            // (:119)
             const int c = cl[i];
             if (c >= 0 && c < num_classes) atomicMax(&probabs[c], (unsigned long long)__double_as_longlong(probab));      // :120-121
         }
@@ -1161,8 +1168,10 @@ __global__ void __launch_bounds__(256) k_twd_publish(const int32_t* __restrict__
 
 namespace {
 
-// Every instantiation of the two one-launch kernels: a row per (metric, tiles per wave), both pointers written from the same template
-// arguments. The occupancy query and the launch take the pointer from the row select_fused found once.
+// Every instantiation of the two one-launch kernels: a row per (metric, tiles per wave), both pointers and the names that
+// fir_twd_dispatch_info reports written from the same template arguments, so the record cannot name a kernel that did not run (the metric
+// is spelled as the number those names carry: 0 L2, 1 chi-square). The occupancy query and the launch take the pointer from the row
+// select_fused found once.
 typedef void (*conv_fused_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, int, double, ConvState*, unsigned long long, int32_t*,
                               int32_t*, int32_t*, int, uint64_t*, uint64_t, unsigned int*);
 typedef void (*prop_fused_fn)(const float4*, int, int, int, const int32_t*, const float*, int, int, int, double, FusedState*, int, unsigned long long, int32_t*,
@@ -1171,11 +1180,13 @@ struct FusedRow {
     int metric, T;
     conv_fused_fn conv;
     prop_fused_fn prop;
+    const char *conv_name, *prop_name;
 };
-#define FIR_TWD_ROW(M, T) {M, T, k_twd_conv_fused<M, T>, k_twd_prop_fused<M, T>}
+static_assert(fir::kL2 == 0 && fir::kChi2 == 1, "kFusedTable spells the metrics as numbers");
+#define FIR_TWD_ROW(M, T) {M, T, k_twd_conv_fused<M, T>, k_twd_prop_fused<M, T>, "fir::k_twd_conv_fused<" #M ", " #T ">", "fir::k_twd_prop_fused<" #M ", " #T ">"}
 const FusedRow kFusedTable[] = {
-    FIR_TWD_ROW(fir::kL2, 1),   FIR_TWD_ROW(fir::kL2, 2),   FIR_TWD_ROW(fir::kL2, 4),   FIR_TWD_ROW(fir::kL2, 8),   FIR_TWD_ROW(fir::kL2, 16),
-    FIR_TWD_ROW(fir::kChi2, 1), FIR_TWD_ROW(fir::kChi2, 2), FIR_TWD_ROW(fir::kChi2, 4), FIR_TWD_ROW(fir::kChi2, 8), FIR_TWD_ROW(fir::kChi2, 16),
+    FIR_TWD_ROW(0, 1), FIR_TWD_ROW(0, 2), FIR_TWD_ROW(0, 4), FIR_TWD_ROW(0, 8), FIR_TWD_ROW(0, 16),
+    FIR_TWD_ROW(1, 1), FIR_TWD_ROW(1, 2), FIR_TWD_ROW(1, 4), FIR_TWD_ROW(1, 8), FIR_TWD_ROW(1, 16),
 };
 #undef FIR_TWD_ROW
 static_assert(sizeof(kFusedTable) / sizeof(kFusedTable[0]) == 10, "one row per (L2, chi-square) x (1, 2, 4, 8, 16 tiles per wave)");
@@ -1210,6 +1221,14 @@ int fused_mode() {
     const char* fenv = fir_knob_("FIR_TWD_FUSED");
     return fenv ? std::atoi(fenv) : 1;
 }
+// FIR_TWD_GROUPS=N, 1 <= N <= 256 (experiments / tests, re-read per call): at most N workgroups per query in a fused launch, so that a
+// gallery of a few thousand rows takes the tiles-per-wave form a gallery of a million rows gets. It changes no answer. Unset or out of
+// range: no cap.
+int fused_groups_cap() {
+    const char* genv = fir_knob_("FIR_TWD_GROUPS");
+    const int cap = genv ? std::atoi(genv) : 0;
+    return cap >= 1 && cap <= 256 ? cap : 256;
+}
 
 TwdPlan plan_conventional(const fir_gallery_view& v, int qb, int num_classes, int type, int reduced) {
     TwdPlan p;
@@ -1226,9 +1245,10 @@ TwdPlan plan_conventional(const fir_gallery_view& v, int qb, int num_classes, in
               num_classes <= 4096;                                      // (the posteriors of a workgroup sit in LDS next to 6 KiB of static tables)
     p.fq = std::min(qb, kFusedMaxQueries);
     if (p.fused) {
+        const int g_max = std::min({256, std::max(1, v.cus / p.fq), fused_groups_cap()});
         for (int t : {1, 2, 4, 8, 16}) {
             const int64_t g_need = (tiles64 + 8 * t - 1) / (8 * t);
-            if (g_need <= std::min(256, std::max(1, v.cus / p.fq))) { p.fT = t; p.fG = (int)g_need; break; }
+            if (g_need <= g_max) { p.fT = t; p.fG = (int)g_need; break; }
         }
         // every query of a fused launch reads the rows for itself: beyond one tile per wave that costs more than the launches it saves
         // (100 000 x 512, 8 queries: 146 against 96 us), so several queries go this way only while every wave has a single tile
@@ -1252,7 +1272,7 @@ TwdPlan plan_proposed(const fir_gallery_view& v, int qb, int reduced, int nchunk
     p.fq = std::min(qb, kFusedMaxQueries);                             // queries per fused launch
     if (p.fused) {
         // at most one workgroup per CU over all the queries of a launch: the workgroups of a query wait for each other
-        p.fG = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, v.cus / p.fq), (tiles + 7) / 8));
+        p.fG = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(std::max(1, v.cus / p.fq), fused_groups_cap()), (tiles + 7) / 8));
         const int64_t need = (tiles + (int64_t)p.fG * 8 - 1) / ((int64_t)p.fG * 8);
         p.fT = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 16 ? 16 : 0;
         if (!p.fT) p.fused = false;
@@ -1266,6 +1286,22 @@ TwdPlan plan_proposed(const fir_gallery_view& v, int qb, int reduced, int nchunk
     p.seg_rows = p.nseg > 1 ? ((n + p.nseg - 1) / p.nseg + 255) / 256 * 256 : n;
     p.nseg_eff = p.nseg > 1 ? (n + p.seg_rows - 1) / p.seg_rows : 1;
     return p;
+}
+
+// The handle's record of the call (fir_twd_last_dispatch) starts from the plan; the drivers count their batches into it. Host stores only.
+fir_twd_dispatch_info* note_plan(fir_gallery* g, int classifier, const TwdPlan& p) {
+    fir_twd_dispatch_info* r = fir_gallery_twd_record_(g);
+    *r = fir_twd_dispatch_info{};
+    r->struct_bytes = (int32_t)sizeof *r;
+    r->classifier = classifier;
+    r->planned_fused = p.fused ? 1 : 0;
+    if (p.fused) {
+        r->tiles_per_wave = p.fT;
+        r->workgroups_per_query = p.fG;
+        r->queries_per_launch = p.fq;
+        std::snprintf(r->kernel, sizeof r->kernel, "%s", classifier == 0 ? p.row->conv_name : p.row->prop_name);
+    }
+    return r;
 }
 
 // The queries of one batch in, its verdicts out. Small batches go through the handle's pinned, device-visible buffer: the kernels read
@@ -1472,6 +1508,7 @@ int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32
     if (order.rc) return order.rc;
     const TwdPlan p = plan_conventional(v, qb, num_classes, type, reduced_features_count);
     const ConvArgs a{num_classes, type, threshold, reduced_features_count};
+    fir_twd_dispatch_info* rec = note_plan(g, 0, p);
     TwdIo io{g, v};
     if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
     if ((rc = take_slot(g, 3, (size_t)kConvWords * 4, &io.dres))) return rc;
@@ -1485,7 +1522,9 @@ int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32
             bool answered = false;
             if ((rc = io.stage(queries + (size_t)q0 * v.d, nq, &qsrc))) return rc;
             if (p.fused && (rc = conv_fused(io, p, a, qsrc, nq, h_res, &answered))) return rc;
+            if (p.fused) { ++rec->fused_launches; rec->fused_gave_up += answered ? 0 : 1; }
             if (!answered && (rc = conv_staged(io, p, a, qsrc, nq, h_res))) return rc;
+            if (!answered) ++rec->staged_batches;
         }
         for (int i = 0; i < nq; ++i) {
             class_out[q0 + i] = h_res[i];
@@ -1512,6 +1551,7 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
         return fir_fail_(FIR_ERR_ARG, "reduced_features_count=%d must divide %d", reduced_features_count, kLastFeature);
     const int nchunks = kLastFeature / reduced_features_count;
     const TwdPlan p = plan_proposed(v, qb, reduced_features_count, nchunks);
+    fir_twd_dispatch_info* rec = note_plan(g, 1, p);
     TwdIo io{g, v};
     if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
     if ((rc = take_slot(g, 3, (size_t)kPropWords * 4, &io.dres))) return rc;
@@ -1525,7 +1565,9 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
             bool answered = false;
             if ((rc = io.stage(queries + (size_t)q0 * v.d, nq, &qsrc))) return rc;
             if (p.fused && (rc = prop_fused(io, p, reduced_features_count, nchunks, threshold, qsrc, nq, h_res, &answered))) return rc;
+            if (p.fused) { ++rec->fused_launches; rec->fused_gave_up += answered ? 0 : 1; }
             if (!answered && (rc = prop_staged(io, p, reduced_features_count, nchunks, threshold, qsrc, nq, h_res))) return rc;
+            if (!answered) ++rec->staged_batches;
         }
         for (int i = 0; i < nq; ++i) {
             class_out[q0 + i] = h_res[i];
@@ -1533,6 +1575,17 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
             if (chunks_out) chunks_out[q0 + i] = h_res[2 * kBatch + i];
         }
     }
+    return FIR_OK;
+}
+
+int fir_twd_last_dispatch(fir_gallery* g, fir_twd_dispatch_info* out) {
+    if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (out->struct_bytes < 8 || out->struct_bytes > (int32_t)sizeof(fir_twd_dispatch_info))
+        return fir_fail_(FIR_ERR_ARG, "fir_twd_dispatch_info.struct_bytes = %d", out->struct_bytes);
+    const int32_t nb = out->struct_bytes;
+    fir_twd_dispatch_info tmp = *fir_gallery_twd_record_(g);
+    tmp.struct_bytes = nb;
+    std::memcpy(out, &tmp, (size_t)nb);
     return FIR_OK;
 }
 

@@ -183,6 +183,28 @@ int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32
  * best * (1 / threshold) dropped, stop when one class is left. chunks_out (may be NULL) <- chunks used. */
 int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t reduced_features_count, double threshold,
                      int32_t* class_out, int32_t* unreliable_out, int32_t* chunks_out);
+/* Which form answered the most recent fir_twd_* call on this handle. Small calls are answered by ONE launch
+ * (k_twd_conv_fused / k_twd_prop_fused), the others -- and a one-launch call whose workgroups did not meet in
+ * time -- by the launch-per-stage / launch-per-chunk kernels; the verdicts are the same either way, so only this
+ * record tells a test or a benchmark which kernels it ran. Every fir_twd_* call that passes its argument checks
+ * overwrites the record; the counts add up over the internal batches of that one call (8 queries per one-launch
+ * batch). Reading it copies a few words kept in the handle on the host: it does not touch the device, launches
+ * and synchronises nothing. FIR_ERR_ARG for a NULL argument or a struct_bytes outside [8, sizeof]. */
+typedef struct fir_twd_dispatch_info {
+    int32_t struct_bytes;          /* in: sizeof(fir_twd_dispatch_info) */
+    int32_t classifier;            /* 0 = fir_twd_conventional, 1 = fir_twd_proposed; -1 = no TWD call on this handle yet */
+    int32_t planned_fused;         /* 1 = the call's plan chose the one-launch form (shape, FIR_TWD_FUSED and the occupancy query allowed it) */
+    int32_t tiles_per_wave;        /* of that plan: 64-row tiles each wave owns (the kernel's T: 1, 2, 4, 8 or 16); 0 when not fused */
+    int32_t workgroups_per_query;  /* grid.x of a one-launch kernel (its workgroups meet each other); 0 when not fused */
+    int32_t queries_per_launch;    /* grid.y of a full one-launch batch: min(qb, 8); 0 when not fused */
+    int32_t fused_launches;        /* one-launch kernels the call queued (its internal batches) */
+    int32_t fused_gave_up;         /* of them: launches whose workgroups did not meet in time (re-answered by the staged form) */
+    int32_t staged_batches;        /* internal batches the launch-per-stage / launch-per-chunk form answered */
+    int32_t reserved;
+    char kernel[160];              /* the one-launch kernel as instantiated, e.g. "fir::k_twd_conv_fused<0, 4>"
+                                    * (<metric: 0 L2, 1 chi-square; tiles per wave>); "" when not fused */
+} fir_twd_dispatch_info;
+int fir_twd_last_dispatch(fir_gallery* g, fir_twd_dispatch_info* out);
 
 /* ---- double-precision classifiers (qt_cpp/classification.cpp) ---------------------------------
  * The training set of KNNClassifier / PNNClassifier (classification.cpp:116-226): train_rows[nt][d]

@@ -1,6 +1,8 @@
 """What fir_last_error() says after a bad-argument call into each of the library's seven translation units: the
 texts are the ones the argument checks have always produced, and a later failure replaces an earlier one's text.
 Argument checks only: nothing here faults or fails a launch."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -27,6 +29,12 @@ def unsorted_fpnn(fir, h):
     return fir.Fpnn(h["x"], lab, 3, h["x"].mean(0), h["x"].std(0), 1.0, 0)
 
 
+def short_twd_report(fir, h):
+    info = fir.capi.TwdDispatchInfo()
+    info.struct_bytes = 4
+    fir.capi._check(fir.lib().fir_twd_last_dispatch(h["g"]._h, ctypes.byref(info)))
+
+
 # (translation unit, the failing call, the message its argument check writes)
 CASES = [
     ("fir_capi.hip", lambda fir, h: h["g"].search_topk(h["q"], 9), "k=9 outside [1,8]"),
@@ -40,6 +48,7 @@ CASES = [
     ("fir_fpnn.hip", unsorted_fpnn, "train_class must be non-decreasing in [0,3) (row 6)"),
     ("fir_shard.hip", lambda fir, h: fir.ShardedGallery(h["rows"], h["cls"], gc.L2, devices=(0, 0)),
      "device 0 listed twice (use shards_per_device for logical shards)"),
+    ("fir_twd.hip", short_twd_report, "fir_twd_dispatch_info.struct_bytes = 4"),
 ]
 
 

@@ -109,11 +109,34 @@ class _FusedMode:
             os.environ["FIR_TWD_FUSED"] = self.old
 
 
+class _Verdicts(tuple):
+    """The outputs of one call as lists, and which kernels answered it (fir_twd_last_dispatch)."""
+    answered_by = ""
+
+
+def _reported(g, mode, outputs):
+    """FIR_TWD_FUSED says what a call may use, the report what it used: mode 0 never queues a one-launch kernel, and a plan that
+    chose the one-launch form queued it. A leg labelled "fused" that was planned staged (a conventional call of 8 queries beyond
+    16 384 rows, say) is the staged form compared with itself: the assertion messages carry `answered_by`."""
+    got = _Verdicts(np.asarray(x).tolist() for x in outputs)
+    rep = g.twd_last_dispatch()
+    if mode == 0:
+        assert rep["planned_fused"] == 0 and rep["fused_launches"] == 0 and rep["staged_batches"] >= 1, rep
+    if rep["planned_fused"] == 1:
+        assert rep["fused_launches"] >= 1, rep
+    else:
+        assert rep["fused_launches"] == 0 and rep["kernel"] == "", rep
+    assert rep["staged_batches"] >= rep["fused_gave_up"], rep
+    got.answered_by = ("staged" if rep["fused_launches"] == 0 else
+                       f"{rep['kernel']}: {rep['fused_launches']} launches, {rep['fused_gave_up']} gave up, {rep['staged_batches']} staged batches")
+    return got
+
+
 def _proposed_all_forms(g, q, fc, th):
     out = []
     for mode in (0, 1, 2):
         with _FusedMode(mode):
-            out.append(tuple(np.asarray(x).tolist() for x in g.twd_proposed(q, fc, th)))
+            out.append(_reported(g, mode, g.twd_proposed(q, fc, th)))
     return out
 
 
@@ -135,7 +158,7 @@ def test_proposed_twd_as_one_launch_matches_the_oracle_and_the_other_forms(fir, 
             exp = [oracle.twd_proposed(rows, cls, qi, fc, th, metric) for qi in q]
             exp = ([e[0] for e in exp], [e[1] for e in exp], [e[2] for e in exp])
             for form, got in zip(("per-chunk", "auto", "fused"), _proposed_all_forms(g, q, fc, th)):
-                assert got == exp, (form, fc, th)
+                assert got == exp, (form, got.answered_by, fc, th)
             with _FusedMode(1):
                 c1, u1, k1 = g.twd_proposed(q[6:7], fc, th)             # the one-query call (all CUs on one query)
             assert (int(c1[0]), int(u1[0]), int(k1[0])) == (exp[0][6], exp[1][6], exp[2][6]), (fc, th)
@@ -158,7 +181,7 @@ def test_proposed_twd_fused_ties_duplicates_and_rows_nothing_qualifies(fir, orac
             exp = [oracle.twd_proposed(rows, cls, qi, fc, th) for qi in q]
             exp = ([e[0] for e in exp], [e[1] for e in exp], [e[2] for e in exp])
             for form, got in zip(("per-chunk", "auto", "fused"), _proposed_all_forms(g, q, fc, th)):
-                assert got == exp, (form, fc, th)
+                assert got == exp, (form, got.answered_by, fc, th)
     rows2 = rows.copy()
     rows2[5] = np.nan
     rows2[12345, 40] = np.nan
@@ -166,7 +189,7 @@ def test_proposed_twd_fused_ties_duplicates_and_rows_nothing_qualifies(fir, orac
         exp = [oracle.twd_proposed(rows2, cls, qi, 32, 0.7) for qi in q]
         exp = ([e[0] for e in exp], [e[1] for e in exp], [e[2] for e in exp])
         for form, got in zip(("per-chunk", "auto", "fused"), _proposed_all_forms(g, q, 32, 0.7)):
-            assert got == exp, form
+            assert got == exp, (form, got.answered_by)
     far = np.full((700, 256), 3.0e4, np.float32)                       # every chunk distance is 9e8 > 100000
     with fir.Gallery(far, np.arange(700, dtype=np.int32) % 7, gc.L2, 0) as g:
         forms = _proposed_all_forms(g, np.zeros((2, 256), np.float32), 32, 0.7)
@@ -231,7 +254,7 @@ def _conventional_all_forms(g, q, ncls, typ, th, fc=64):
     out = []
     for mode in (0, 1, 2):
         with _FusedMode(mode):
-            out.append(tuple(np.asarray(x).tolist() for x in g.twd_conventional(q, ncls, typ, th, fc)))
+            out.append(_reported(g, mode, g.twd_conventional(q, ncls, typ, th, fc)))
     return out
 
 
@@ -254,7 +277,7 @@ def test_conventional_twd_as_one_launch_matches_the_oracle_and_the_other_forms(f
                 exp = [oracle.twd_conventional(rows, cls, qi, ncls, typ, th, fc, metric) for qi in q]
                 exp = ([e[0] for e in exp], [e[1] for e in exp])
                 for form, got in zip(("per-stage", "auto", "fused"), _conventional_all_forms(g, q, ncls, typ, th, fc)):
-                    assert got == exp, (form, typ, th, fc)
+                    assert got == exp, (form, got.answered_by, typ, th, fc)
                 with _FusedMode(1):
                     c1, u1 = g.twd_conventional(q[6:7], ncls, typ, th, fc)
                 assert (int(c1[0]), int(u1[0])) == (exp[0][6], exp[1][6]), (typ, th, fc)
@@ -280,7 +303,7 @@ def test_conventional_twd_fused_second_best_follows_the_scan_order(fir, oracle):
                 exp = [oracle.twd_conventional(rr, cls, qi, ncls, typ, th, 64) for qi in q]
                 exp = ([e[0] for e in exp], [e[1] for e in exp])
                 for form, got in zip(("per-stage", "auto", "fused"), _conventional_all_forms(g, q, ncls, typ, th)):
-                    assert got == exp, (form, typ, th)
+                    assert got == exp, (form, got.answered_by, typ, th)
     far = np.full((700, 256), 3.0e4, np.float32)
     with fir.Gallery(far, np.arange(700, dtype=np.int32) % 7, gc.L2, 0) as g:
         for typ, th in ((0, 0.24), (1, 0.003), (2, 0.7)):
