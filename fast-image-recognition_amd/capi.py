@@ -92,6 +92,8 @@ SYMBOLS = [
     ("fir_dem_info", C.c_int, [_vp, _i32p, _i32p, _i32p, _i64p]),
     ("fir_dem_get", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("fir_dem_likelihoods", C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
+    ("fir_dem_recognize", C.c_int, [_vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("fir_dem_recognize_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("fir_rows_distances", C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     ("fir_fpnn_train", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_double, C.c_int32, C.POINTER(_vp)]),
     ("fir_fpnn_destroy", C.c_int, [_vp]),
@@ -654,6 +656,19 @@ class Dem:
         lik = np.empty((q.shape[0], self.n), np.float32) if want_lik else None
         _check(lib().fir_dem_likelihoods(self._h, pq, q.shape[0], pd.ctypes.data_as(_vp), lik.ctypes.data_as(_vp) if want_lik else None))
         return pd, lik
+
+    def recognize(self, queries, threshold, image_count=0):
+        """DirectedEnumeration::recognize for every query in one call -> (row, dist, found, calc, tie)."""
+        q, pq = _f32(queries)
+        qb = q.reshape(-1, self._g.d).shape[0]
+        row, found, calc, tie = (np.empty(qb, np.int32) for _ in range(4))
+        dist = np.empty(qb, np.float32)
+        _check(lib().fir_dem_recognize(self._h, pq, qb, threshold, image_count, *(a.ctypes.data_as(_vp) for a in (row, dist, found, calc, tie))))
+        return row, dist, found, calc, tie
+
+    def recognize_dev(self, q_ptr, qb, threshold, image_count, row_ptr, dist_ptr, found_ptr, calc_ptr, tie_ptr, stream=None):
+        _check(lib().fir_dem_recognize_dev(self._h, _vp(q_ptr), qb, threshold, image_count, *(_vp(p) if p else None for p in
+                                           (row_ptr, dist_ptr, found_ptr, calc_ptr, tie_ptr)), _vp(stream) if stream else None))
 
 
 class Fpnn:

@@ -12,8 +12,11 @@
 //   k_dem_pick     one workgroup folds the partials, writes min_other[ii] and pivots[ii+1]
 // The running far[j] is the reference's inner `ind` loop evaluated incrementally: the same additions in the same order.
 //
-// Query time (DirectedEnumeration::recognize, ann.cpp:411-507) is a sequential, early-exit walk that stays on the
-// host (host/fir_classifiers.cpp); its two data-parallel pieces are here:
+// Query time (DirectedEnumeration::recognize, ann.cpp:411-507) looks like a sequential, early-exit walk, but it is one
+// selection threshold, two minima and a count: fir_dem_recognize answers a batch on the device with no host step
+// (the kernels are further down, "DirectedEnumeration::recognize on the device"); its tie flag marks the queries whose
+// answer hangs on the order of equal likelihoods. The C++ shim (host/fir_classifiers.cpp) still walks on the host over the
+// two pieces below until the new call has been timed against them (profiles/dem_recognize.txt):
 //   k_dem_lik      likelihoods[nu] += (dist(query, pivot i) - table[i][nu])^2 for the <= 32 pivots kept (:437-446):
 //                  one lane per gallery row, the pivots in order, float adds in the reference's order; n*P*4 bytes of
 //                  table per batch of 8 queries instead of n*d*4 bytes of gallery
@@ -216,6 +219,388 @@ __global__ void __launch_bounds__(kBlock) k_rows_dist(const float4* __restrict__
     if (lane < cpw && k0 + lane < m) out[(size_t)q * m + k0 + lane] = my_valid ? acc / (float)(end - start) : fir::kNotFound;
 }
 
+// The launch of k_rows_dist for nq queries with m candidate rows each (rows[nq][m] -> out[nq][m]), all pointers the device can read.
+// Candidates per wave: 4 while the workgroup's 1 + 16 rows fit 64 KiB of LDS (d <= 960), else 1; rows beyond 2 048 features
+// go through LDS in pieces of 512 float4.
+void launch_rows_dist(const void* gal4, int dp4, int64_t n, int metric, int d, const float* queries, int nq, const int32_t* rows, int m, int start,
+                      int end, float* out, hipStream_t st) {
+    const int cpw = (size_t)17 * dp4 * 16 <= 64 * 1024 ? 4 : 1;
+    const int span = std::min(dp4, 512);
+    const size_t lds = (size_t)(1 + (kBlock / 64) * cpw) * span * 16;
+    const int per_block = (kBlock / 64) * cpw;
+    const dim3 grid((m + per_block - 1) / per_block, nq);
+#define FIR_ROWS_LAUNCH(M) \
+    hipLaunchKernelGGL(k_rows_dist<M>, grid, dim3(kBlock), lds, st, (const float4*)gal4, dp4, n, queries, d, rows, m, start, end, out, cpw, span)
+    if (metric == FIR_METRIC_L2) FIR_ROWS_LAUNCH(fir::kL2);
+    else if (metric == FIR_METRIC_CHI2) FIR_ROWS_LAUNCH(fir::kChi2);
+    else FIR_ROWS_LAUNCH(fir::kKL);
+#undef FIR_ROWS_LAUNCH
+}
+
+// ---- DirectedEnumeration::recognize on the device (fir_dem_recognize; the formulation is in include/fir_amd.h) ------------------
+// After the pivot loop the walk of ann.cpp:455-462 needs no sort: the candidates are the Mc = imageCountToCheck - used POSITIONS
+// p >= used of likelihood_indices with the smallest keys (likelihood bits, p), found by a radix select; the early exit is "the
+// smallest selected key whose distance is below the threshold" (the running best is >= threshold while the walk goes on, so
+// such a candidate always also beats it), the full walk "the smallest (distance, key)". Per internal batch of kLikBatch queries:
+//   k_dem_head          replays the pivot loop (CHECK_FOR_BEST_DIST, :427-430) per query; queries that leave there are inactive below
+//   k_dem_select_one    T = the Mc-th smallest key, 8-bit digits from the top, histogram in LDS: one workgroup per query with the
+//                       likelihood bits parked in LDS (up to kSelOneGroupRows candidates), or
+//   k_dem_select_pass   one launch per digit, workgroups of kSelSlice positions adding their LDS histogram to the query's
+//   k_dem_mark          flags an unselected position that shares its likelihood with a selected one; for the gather form compacts
+//                       the selected positions into an unordered list
+//   candidate distances k_rows_dist over that list (Mc < n / kGatherDiv), else the range scan into [8][n] read under key <= T
+//   k_dem_fold          per-block partials of the two minima, k_dem_finish one workgroup per query: row / dist / found
+//   k_dem_count         distanceCalcCount of an early exit and the tie flag's counts, added to calc / tie
+constexpr int kSelOneGroupRows = 8192;   // n - used up to which one workgroup per query selects (32 KiB of likelihood bits in LDS)
+constexpr int kSelSlice = 2048;          // positions per workgroup and digit in the several-workgroups form
+constexpr int kWalkMaxBlocks = 128;      // workgroups per query of mark / fold / count
+// Gather while Mc < n / kGatherDiv. Per batch of 8 queries the gather reads 8 * Mc rows, the dense form the gallery once: by
+// bytes the two meet at Mc = n / 8, and that is the value until the crossover has been measured on the device: the sweep of
+// tools/dem_recognize_probe.py forces either form (fir_dem_probe_) over Mc / n; profiles/dem_recognize.txt holds what is known.
+constexpr int kGatherDiv = 8;
+constexpr unsigned long long kNoKey = ~0ull;
+static_assert(kBlock == 256, "thread t of a workgroup is bin t of the 8-bit digit histograms (hist[threadIdx.x], sel_advance)");
+
+struct DemQ {               // one query of the batch
+    float piv_best;         // the pivot loop's bestDistance / bestIndex
+    int32_t piv_row;
+    int32_t exit_k;         // the pivot at which the walk left (-1: it did not)
+    int32_t active;         // candidates are checked for this query
+    int32_t nan_piv;
+    int32_t tie_a;
+    int32_t n_listed;       // gather form: slots of the candidate list handed out
+    int32_t same;           // k_dem_count: selected positions that share the winner's likelihood (and distance)
+    int32_t mode;           // 0 nothing to count, 1 early exit at a candidate, 2 a candidate won the full walk
+    uint32_t win_lik, win_dist;
+    unsigned long long win_key;
+    unsigned long long T;
+};
+struct SelState { unsigned long long prefix; int32_t rank; int32_t done; };   // before a digit: key bits decided, rank inside them
+struct FoldPart { unsigned long long exit_key; float exit_dist; uint32_t best_dist; unsigned long long best_key; };
+
+__device__ __forceinline__ unsigned long long dem_key(const float* __restrict__ lik, const int32_t* __restrict__ order, int p) {
+    return ((unsigned long long)fir::f32_orderable(lik[order[p]]) << 32) | (unsigned)p;
+}
+__device__ __forceinline__ bool sel_match(unsigned long long key, unsigned long long prefix, int pass) {
+    return pass == 0 ? true : ((key ^ prefix) >> (64 - 8 * pass)) == 0;
+}
+
+// hist[digit] += 1 for the lanes with `match`; every lane of the wave calls it. Likelihoods of one query share their top bytes,
+// so the lanes of a wave mostly hit one bin: the first two distinct digits found are counted with a ballot and added once per
+// wave, whatever is left lane by lane.
+__device__ __forceinline__ void hist_add(unsigned* hist, bool match, unsigned digit) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long rem = __ballot(match);
+    for (int it = 0; it < 2 && rem; ++it) {
+        const int leader = __ffsll((long long)rem) - 1;
+        const unsigned d0 = __shfl(digit, leader, 64);
+        const unsigned long long m = __ballot(match && digit == d0);
+        if (lane == leader) atomicAdd(&hist[d0], (unsigned)__popcll(m));
+        rem &= ~m;
+    }
+    if ((rem >> lane) & 1) atomicAdd(&hist[digit], 1u);
+}
+
+// The state after digit `pass`, from the state before it and the digit's histogram (thread t holds bin t): the bin the rank falls
+// into (inclusive sums folded across the wave with shuffles, across the four waves through LDS). When the rank is the bin's
+// whole count, everything in the bin is selected and the remaining digits are all ones: done. All kBlock threads call it.
+__device__ SelState sel_advance(SelState s, unsigned count, int pass, unsigned* wsum, SelState* box) {
+    if (s.done) return s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, shift = 56 - 8 * pass;
+    unsigned incl = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    if (threadIdx.x == 0) *box = SelState{s.prefix, s.rank, 1};   // (a rank outside the histogram: cannot happen, and must not hang)
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) incl += wsum[w];
+    const unsigned excl = incl - count, rank = (unsigned)s.rank;
+    if (count > 0 && excl < rank && rank <= incl) {
+        const int all = rank - excl == count;
+        unsigned long long prefix = s.prefix | ((unsigned long long)threadIdx.x << shift);
+        if (all) prefix |= (1ull << shift) - 1;
+        *box = SelState{prefix, (int32_t)(rank - excl), all};
+    }
+    __syncthreads();
+    s = *box;
+    __syncthreads();
+    return s;
+}
+
+__global__ void __launch_bounds__(64) k_dem_head(const float* __restrict__ pd, int used, int nq, float thr, const int32_t* __restrict__ pivots, int mc,
+                                                 int cnt, DemQ* __restrict__ Q, SelState* __restrict__ sel0) {
+    const int q = threadIdx.x;
+    if (q >= nq) return;
+    DemQ s = {};
+    s.piv_best = FLT_MAX;
+    s.piv_row = -1;
+    s.exit_k = -1;
+    for (int k = 0; k < used; ++k) {
+        const float dk = pd[q * used + k];
+        if (dk != dk) s.nan_piv = 1;
+        if (dk < s.piv_best) {
+            s.piv_best = dk;
+            s.piv_row = pivots[k];
+            if (dk < thr) { s.exit_k = k; break; }
+        }
+    }
+    s.active = s.exit_k < 0 && mc > 0;
+    const int all = mc >= cnt;
+    s.T = s.active && all ? kNoKey : 0ull;
+    Q[q] = s;
+    sel0[q] = SelState{s.T, mc, !s.active || all};
+}
+
+__global__ void __launch_bounds__(kBlock) k_dem_select_one(const float* __restrict__ lik, int n, int used, const int32_t* __restrict__ order,
+                                                           DemQ* __restrict__ Q, const SelState* __restrict__ sel0) {
+    __shared__ unsigned bits[kSelOneGroupRows];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wsum[kBlock / 64];
+    __shared__ SelState box;
+    const int q = blockIdx.x, cnt = min(n - used, kSelOneGroupRows);
+    SelState s = sel0[q];
+    if (s.done) return;                                               // (head has written T)
+    const float* __restrict__ lq = lik + (size_t)q * n;
+    for (int i = threadIdx.x; i < cnt; i += kBlock) bits[i] = fir::f32_orderable(lq[order[used + i]]);
+    for (int pass = 0; pass < 8 && !s.done; ++pass) {
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        const int shift = 56 - 8 * pass;
+        for (int i0 = 0; i0 < cnt; i0 += kBlock) {
+            const int i = i0 + threadIdx.x;
+            const unsigned long long key = i < cnt ? ((unsigned long long)bits[i] << 32) | (unsigned)(used + i) : 0ull;
+            hist_add(hist, i < cnt && sel_match(key, s.prefix, pass), (unsigned)(key >> shift) & 255u);
+        }
+        __syncthreads();
+        s = sel_advance(s, hist[threadIdx.x], pass, wsum, &box);
+    }
+    if (threadIdx.x == 0) Q[q].T = s.prefix;
+}
+
+// Digit `pass` (0..7) of the several-workgroups form; pass 8 only turns the last histogram into T. sel[j][q] is the state before
+// digit j: every workgroup works it out from sel[j-1] and hist[j-1] (complete: the launch before this one), workgroup 0 keeps it.
+__global__ void __launch_bounds__(kBlock) k_dem_select_pass(const float* __restrict__ lik, int n, int used, const int32_t* __restrict__ order,
+                                                            DemQ* __restrict__ Q, SelState* __restrict__ sel, unsigned* __restrict__ ghist, int pass) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wsum[kBlock / 64];
+    __shared__ SelState box;
+    const int q = blockIdx.y, cnt = n - used;
+    SelState s = sel[(pass == 0 ? 0 : pass - 1) * kLikBatch + q];
+    if (pass > 0) {
+        s = sel_advance(s, ghist[((size_t)(pass - 1) * kLikBatch + q) * 256 + threadIdx.x], pass - 1, wsum, &box);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && pass < 8) sel[pass * kLikBatch + q] = s;
+    }
+    if (pass == 8) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && Q[q].active) Q[q].T = s.prefix;
+        return;
+    }
+    if (s.done) return;
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const float* __restrict__ lq = lik + (size_t)q * n;
+    const int shift = 56 - 8 * pass;
+    const int i_end = min(cnt, (blockIdx.x + 1) * kSelSlice);
+    for (int i0 = blockIdx.x * kSelSlice; i0 < i_end; i0 += kBlock) {
+        const int i = i0 + threadIdx.x;
+        const unsigned long long key = i < i_end ? dem_key(lq, order, used + i) : 0ull;
+        hist_add(hist, i < i_end && sel_match(key, s.prefix, pass), (unsigned)(key >> shift) & 255u);
+    }
+    __syncthreads();
+    if (hist[threadIdx.x]) atomicAdd(&ghist[((size_t)pass * kLikBatch + q) * 256 + threadIdx.x], hist[threadIdx.x]);
+}
+
+// rows == NULL: the dense form (only the flag). Otherwise pos[q][mc] / rows[q][mc] <- the selected positions and their rows, in
+// no particular order (exactly mc of them; the slot is checked all the same); an inactive query's rows are -1.
+__global__ void __launch_bounds__(kBlock) k_dem_mark(const float* __restrict__ lik, int n, int used, const int32_t* __restrict__ order,
+                                                     DemQ* __restrict__ Q, int mc, int32_t* __restrict__ pos, int32_t* __restrict__ rows) {
+    const int q = blockIdx.y, cnt = n - used, lane = threadIdx.x & 63;
+    if (!Q[q].active) {
+        if (rows)
+            for (int i = blockIdx.x * kBlock + threadIdx.x; i < mc; i += gridDim.x * kBlock) rows[(size_t)q * mc + i] = -1;
+        return;
+    }
+    const unsigned long long T = Q[q].T;
+    const float* __restrict__ lq = lik + (size_t)q * n;
+    int flag = 0;
+    for (int i0 = blockIdx.x * kBlock; i0 < cnt; i0 += gridDim.x * kBlock) {
+        const int i = i0 + threadIdx.x, p = used + i;
+        const unsigned long long key = i < cnt ? dem_key(lq, order, p) : kNoKey;
+        const bool sel = i < cnt && key <= T;
+        // (a select that ended early left T's undecided low bits all ones: a key with T's likelihood bits is then never above T)
+        if (i < cnt && !sel && (key >> 32) == (T >> 32)) flag = 1;
+        if (rows) {
+            const unsigned long long m = __ballot(sel);
+            if (m) {
+                const int leader = __ffsll((long long)m) - 1;
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&Q[q].n_listed, (int)__popcll(m));
+                base = __shfl(base, leader, 64);
+                const int slot = base + (int)__popcll(m & ((1ull << lane) - 1));
+                if (sel && slot < mc) {
+                    pos[(size_t)q * mc + slot] = p;
+                    rows[(size_t)q * mc + slot] = order[p];
+                }
+            }
+        }
+    }
+    if (flag) atomicOr(&Q[q].tie_a, 1);
+}
+
+// The selected candidates of query q as mark / the scans left them: pos != NULL: slot i of the list, distance dist[q][mc];
+// pos == NULL: position used + i under key <= T, distance dist[q][n] at its row.
+struct DemCands {
+    const float* __restrict__ lq;
+    const int32_t* __restrict__ order;
+    const int32_t* __restrict__ pos;
+    const float* __restrict__ dist;
+    unsigned long long T;
+    int n, used, mc;
+    __device__ int domain() const { return pos ? mc : n - used; }
+    __device__ bool get(int i, unsigned long long* key, float* d) const {
+        if (pos) {
+            const int p = pos[i];
+            if (p < used || p >= n) return false;
+            *key = dem_key(lq, order, p);
+            *d = dist[i] + 0.0f;
+            return true;
+        }
+        const int p = used + i;
+        *key = dem_key(lq, order, p);
+        if (*key > T) return false;
+        *d = dist[order[p]] + 0.0f;
+        return true;
+    }
+};
+__device__ __forceinline__ DemCands dem_cands(const float* lik, int n, int used, const int32_t* order, const DemQ& s, int mc, const int32_t* pos,
+                                              const float* dist, int q) {
+    return DemCands{lik + (size_t)q * n, order, pos ? pos + (size_t)q * mc : nullptr, dist + (size_t)q * (pos ? mc : n), s.T, n, used, mc};
+}
+
+__device__ __forceinline__ FoldPart fold_min(const FoldPart& a, const FoldPart& b) {
+    FoldPart r = a;
+    if (b.exit_key < r.exit_key) { r.exit_key = b.exit_key; r.exit_dist = b.exit_dist; }
+    if (b.best_dist < r.best_dist || (b.best_dist == r.best_dist && b.best_key < r.best_key)) { r.best_dist = b.best_dist; r.best_key = b.best_key; }
+    return r;
+}
+__device__ FoldPart fold_block(FoldPart v, FoldPart* sm) {
+    sm[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] = fold_min(sm[threadIdx.x], sm[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return sm[0];
+}
+
+// parts[q][block]: the smallest key with distance < thr (the early exit, :397-398) and the smallest (distance, key) (the full walk).
+// A NaN distance is never "< bestDistance": it takes no part.
+__global__ void __launch_bounds__(kBlock) k_dem_fold(const float* __restrict__ lik, int n, int used, const int32_t* __restrict__ order,
+                                                     const DemQ* __restrict__ Q, int mc, const int32_t* __restrict__ pos, const float* __restrict__ dist,
+                                                     float thr, FoldPart* __restrict__ parts) {
+    __shared__ FoldPart sm[kBlock];
+    const int q = blockIdx.y;
+    const DemQ s = Q[q];
+    if (!s.active) return;
+    const DemCands c = dem_cands(lik, n, used, order, s, mc, pos, dist, q);
+    FoldPart v = {kNoKey, 0.0f, 0xFFFFFFFFu, kNoKey};
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < c.domain(); i += gridDim.x * kBlock) {
+        unsigned long long key;
+        float d;
+        if (!c.get(i, &key, &d) || d != d) continue;
+        if (d < thr && key < v.exit_key) { v.exit_key = key; v.exit_dist = d; }
+        const uint32_t ob = fir::f32_orderable(d);
+        if (ob < v.best_dist || (ob == v.best_dist && key < v.best_key)) { v.best_dist = ob; v.best_key = key; }
+    }
+    v = fold_block(v, sm);
+    if (threadIdx.x == 0) parts[(size_t)q * gridDim.x + blockIdx.x] = v;
+}
+
+// One workgroup per query: the pivots' result, or the candidates' when they change it. calc and tie are never NULL (k_dem_count
+// adds to them); an early exit's calc starts at `used`.
+__global__ void __launch_bounds__(kBlock) k_dem_finish(DemQ* __restrict__ Q, const FoldPart* __restrict__ parts, int nparts, int used, int mc,
+                                                       const int32_t* __restrict__ order, int32_t* __restrict__ row, float* __restrict__ dist,
+                                                       int32_t* __restrict__ found, int32_t* __restrict__ calc, int32_t* __restrict__ tie) {
+    __shared__ FoldPart sm[kBlock];
+    const int q = blockIdx.x;
+    const DemQ s = Q[q];
+    FoldPart v = {kNoKey, 0.0f, 0xFFFFFFFFu, kNoKey};
+    if (s.active)
+        for (int b = threadIdx.x; b < nparts; b += kBlock) v = fold_min(v, parts[(size_t)q * nparts + b]);
+    v = fold_block(v, sm);
+    if (threadIdx.x != 0) return;
+    int r_row = s.piv_row, r_found = s.exit_k >= 0, r_calc = s.exit_k >= 0 ? s.exit_k + 1 : used, r_tie = 0, mode = 0;
+    float r_dist = s.piv_best;
+    unsigned long long win_key = kNoKey;
+    if (s.active) {
+        r_tie = s.tie_a | s.nan_piv;
+        if (v.exit_key != kNoKey) {
+            win_key = v.exit_key;
+            r_dist = v.exit_dist;
+            r_found = 1;
+            mode = 1;                                                  // calc = used + #{selected keys <= win_key}
+        } else {
+            r_calc = used + mc;
+            const float bd = fir::f32_from_orderable(v.best_dist);
+            if (v.best_key != kNoKey && bd < s.piv_best) {
+                win_key = v.best_key;
+                r_dist = bd;
+                mode = 2;
+            }
+        }
+        if (mode) r_row = order[(unsigned)win_key];
+    }
+    uint32_t db;
+    __builtin_memcpy(&db, &r_dist, 4);
+    Q[q].mode = mode;
+    Q[q].win_key = win_key;
+    Q[q].win_lik = (uint32_t)(win_key >> 32);
+    Q[q].win_dist = db;
+    if (row) row[q] = r_row;
+    if (dist) dist[q] = r_dist;
+    if (found) found[q] = r_found;
+    calc[q] = r_calc;
+    tie[q] = r_tie;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dem_count(const float* __restrict__ lik, int n, int used, const int32_t* __restrict__ order,
+                                                      DemQ* __restrict__ Q, int mc, const int32_t* __restrict__ pos, const float* __restrict__ dist,
+                                                      int32_t* __restrict__ calc, int32_t* __restrict__ tie) {
+    __shared__ int sm[2][kBlock / 64];
+    const int q = blockIdx.y;
+    const DemQ s = Q[q];
+    if (!s.active || s.mode == 0) return;
+    const DemCands c = dem_cands(lik, n, used, order, s, mc, pos, dist, q);
+    int upto = 0, same = 0;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < c.domain(); i += gridDim.x * kBlock) {
+        unsigned long long key;
+        float d;
+        if (!c.get(i, &key, &d)) continue;
+        uint32_t db;
+        __builtin_memcpy(&db, &d, 4);
+        if (s.mode == 1) {
+            upto += key <= s.win_key;
+            same += (uint32_t)(key >> 32) == s.win_lik;
+        } else {
+            same += (uint32_t)(key >> 32) == s.win_lik && db == s.win_dist;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        upto += __shfl_xor(upto, off, 64);
+        same += __shfl_xor(same, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = upto; sm[1][threadIdx.x >> 6] = same; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    upto = same = 0;
+    for (int w = 0; w < kBlock / 64; ++w) { upto += sm[0][w]; same += sm[1][w]; }
+    if (upto) atomicAdd(&calc[q], upto);
+    if (same && atomicAdd(&Q[q].same, same) + same > 1) atomicOr(&tie[q], 1);   // the winner itself counts once
+}
+
 // One thread, queued behind the kernels of a small host-pointer call whose results went to pinned host memory: the call's
 // ticket. (A device-wide fence + arrival counter inside the producing kernel costs more than this launch: every
 // workgroup's fence is an L2 write-back.)
@@ -236,6 +621,7 @@ struct Buf {
     void* p = nullptr;
     ~Buf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
     template <typename T> T* as() { return (T*)p; }
 };
 
@@ -302,7 +688,180 @@ struct fir_dem {
     // memory the kernels address directly, completion by a ticket word (no copy engine, no stream synchronisation)
     void* pin = nullptr;
     unsigned long long ticket = 0;
+    // fir_dem_recognize: allocated by its first call, of a size that depends on n only, its own (fir_dem_likelihoods may run
+    // between two asynchronous calls). r_q / r_out: the host-pointer form's queries and results, grown to the largest qb seen.
+    bool rec_ready = false;
+    Buf d_order, d_pivots, r_state, r_pd, r_lik, r_dist, r_pos, r_rows, r_q, r_out;
+    size_t r_q_cap = 0, r_out_cap = 0;
+    size_t r_dist_cap = 0, r_pos_cap = 0, r_rows_cap = 0;   // candidate distances ([8][Mc] gather, [8][n] dense) and the gather's lists, grown to the call's need
+    // measurement (fir_dem_probe_, tools/dem_recognize_probe.py): a forced candidate-distance form, events between the stages
+    int probe_form = 0;
+    bool probe_timing = false;
+    std::vector<hipEvent_t> probe_ev;
+    size_t probe_ev_used = 0;
 };
+
+namespace {
+
+// r_state: DemQ[8] | SelState[9][8] | FoldPart[8][kWalkMaxBlocks] | calc[8], tie[8] stand-ins | histograms [8 digits][8][256]
+struct RecState {
+    DemQ* Q;
+    SelState* sel;
+    FoldPart* parts;
+    int32_t *calc, *tie;
+    unsigned* hist;
+    static constexpr size_t kHistBytes = (size_t)8 * kLikBatch * 256 * sizeof(unsigned);
+    static size_t bytes() {
+        return sizeof(DemQ) * kLikBatch + sizeof(SelState) * 9 * kLikBatch + sizeof(FoldPart) * kLikBatch * kWalkMaxBlocks + 2 * 4 * kLikBatch + kHistBytes;
+    }
+    explicit RecState(void* p) {
+        Q = (DemQ*)p;
+        sel = (SelState*)(Q + kLikBatch);
+        parts = (FoldPart*)(sel + 9 * kLikBatch);
+        calc = (int32_t*)(parts + kLikBatch * kWalkMaxBlocks);
+        tie = calc + kLikBatch;
+        hist = (unsigned*)(tie + kLikBatch);
+    }
+};
+
+int dem_recognize_prepare(fir_dem* h) {
+    if (h->rec_ready) return FIR_OK;
+    const size_t n = (size_t)h->v.n;
+    std::vector<int32_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = (int32_t)i;
+    for (const auto& kv : h->order_mods) order[(size_t)kv.first] = kv.second;
+    FIR_HIP(h->d_order.alloc(n * 4));
+    FIR_HIP(h->d_pivots.alloc((size_t)kMaxUsed * 4));
+    FIR_HIP(h->r_state.alloc(RecState::bytes()));
+    FIR_HIP(h->r_pd.alloc((size_t)kLikBatch * kMaxUsed * 4));
+    FIR_HIP(h->r_lik.alloc((size_t)kLikBatch * n * 4));
+    FIR_HIP(hipMemset(h->r_lik.p, 0, (size_t)kLikBatch * n * 4));
+    FIR_HIP(hipMemset(h->r_state.p, 0, RecState::bytes()));
+    FIR_HIP(hipMemcpy(h->d_order.p, order.data(), n * 4, hipMemcpyHostToDevice));
+    FIR_HIP(hipMemcpy(h->d_pivots.p, h->pivots.data(), (size_t)h->used * 4, hipMemcpyHostToDevice));
+    h->rec_ready = true;
+    return FIR_OK;
+}
+
+// Scratch whose size depends on the call (Mc, the form): grown before anything is queued, after the handle's earlier calls have
+// finished with the old buffer.
+int dem_grow(fir_dem* h, Buf& b, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return FIR_OK;
+    const int rc = fir_gallery_wait_calls_(h->g);
+    if (rc) return rc;
+    FIR_HIP(hipStreamSynchronize(h->v.stream));
+    b.release();
+    cap = 0;
+    const size_t want = bytes + bytes / 4;
+    FIR_HIP(b.alloc(want));
+    FIR_HIP(hipMemset(b.p, 0, want));
+    cap = want;
+    return FIR_OK;
+}
+
+enum { kStagePivots, kStageLik, kStageSelect, kStageMark, kStageDist, kStageWalk, kStages };
+int dem_stage_mark(fir_dem* h, hipStream_t st) {
+    if (!h->probe_timing) return FIR_OK;
+    if (h->probe_ev_used == h->probe_ev.size()) {
+        hipEvent_t e;
+        FIR_HIP(hipEventCreate(&e));
+        h->probe_ev.push_back(e);
+    }
+    FIR_HIP(hipEventRecord(h->probe_ev[h->probe_ev_used++], st));
+    return FIR_OK;
+}
+
+// The kernels of one call, queued on st; every pointer is the device's. calc / tie may be NULL like the rest.
+int dem_recognize_queue(fir_dem* h, const float* dq, int qb, float thr, int image_count, int32_t* row, float* dist, int32_t* found, int32_t* calc,
+                        int32_t* tie, hipStream_t st) {
+    const fir_gallery_view& v = h->v;
+    const int n = (int)v.n, used = h->used, cnt = n - used;
+    const int M = image_count > 0 && image_count < n ? image_count : n;
+    const int mc = M - used;
+    const void* gal4 = nullptr;
+    int dp4 = 0;
+    if (fir_gallery_tiled_(h->g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
+    int32_t metric = 0;
+    int rc = fir_gallery_info(h->g, nullptr, nullptr, &metric, nullptr);
+    if (rc) return rc;
+    const bool gather = h->probe_form ? h->probe_form == 1 : mc < n / kGatherDiv;
+    if (mc > 0) {
+        if ((rc = dem_grow(h, h->r_dist, h->r_dist_cap, (size_t)kLikBatch * (gather ? mc : n) * 4))) return rc;
+        if (gather && ((rc = dem_grow(h, h->r_pos, h->r_pos_cap, (size_t)kLikBatch * mc * 4)) ||
+                       (rc = dem_grow(h, h->r_rows, h->r_rows_cap, (size_t)kLikBatch * mc * 4))))
+            return rc;
+    }
+    const RecState rs(h->r_state.p);
+    const int32_t* order = h->d_order.as<int32_t>();
+    float *pd = h->r_pd.as<float>(), *lik = h->r_lik.as<float>(), *cdist = h->r_dist.as<float>();
+    int32_t* pos = gather ? h->r_pos.as<int32_t>() : nullptr;
+    const int lik_blocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
+    const int walk_blocks = std::max(1, std::min(kWalkMaxBlocks, (cnt + 4 * kBlock - 1) / (4 * kBlock)));
+    for (int q0 = 0; q0 < qb; q0 += kLikBatch) {
+        const int nq = std::min(kLikBatch, qb - q0);
+        const float* q = dq + (size_t)q0 * v.d;
+        int32_t* bcalc = calc ? calc + q0 : rs.calc;
+        int32_t* btie = tie ? tie + q0 : rs.tie;
+        if ((rc = dem_stage_mark(h, st))) return rc;
+        if ((rc = fir_range_distances_dev(h->pivot_rows, q, nq, 0, v.d, pd, st))) return rc;   // pd[q][used]
+        hipLaunchKernelGGL(k_dem_head, dim3(1), dim3(64), 0, st, pd, used, nq, thr, h->d_pivots.as<int32_t>(), mc, cnt, rs.Q, rs.sel);
+        FIR_HIP(hipGetLastError());
+        if ((rc = dem_stage_mark(h, st))) return rc;
+        if (mc > 0) {
+            hipLaunchKernelGGL(k_dem_lik<kLikBatch>, dim3(lik_blocks), dim3(kBlock), 0, st, h->table.as<float>(), n, used, pd, nq, lik);
+            hipLaunchKernelGGL(k_dem_lik_fix, dim3((h->nexc * nq + 63) / 64), dim3(64), 0, st, h->table.as<float>(), n, used, pd, nq,
+                               h->exc_rows.as<int32_t>(), h->exc_mult.as<uint8_t>(), h->nexc, lik);
+            FIR_HIP(hipGetLastError());
+            if ((rc = dem_stage_mark(h, st))) return rc;
+            if (mc < cnt) {                                               // (mc == cnt: every position is selected, head has said so)
+                if (cnt <= kSelOneGroupRows) {
+                    hipLaunchKernelGGL(k_dem_select_one, dim3(nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, rs.sel);
+                } else {
+                    FIR_HIP(hipMemsetAsync(rs.hist, 0, RecState::kHistBytes, st));
+                    const dim3 grid((cnt + kSelSlice - 1) / kSelSlice, nq);
+                    for (int pass = 0; pass <= 8; ++pass)
+                        hipLaunchKernelGGL(k_dem_select_pass, pass < 8 ? grid : dim3(1, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, rs.sel,
+                                           rs.hist, pass);
+                }
+                FIR_HIP(hipGetLastError());
+            }
+            if ((rc = dem_stage_mark(h, st))) return rc;
+            hipLaunchKernelGGL(k_dem_mark, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos,
+                               gather ? h->r_rows.as<int32_t>() : nullptr);
+            FIR_HIP(hipGetLastError());
+            if ((rc = dem_stage_mark(h, st))) return rc;
+            if (gather) {
+                launch_rows_dist(gal4, dp4, v.n, metric, v.d, q, nq, h->r_rows.as<int32_t>(), mc, 0, v.d, cdist, st);
+                FIR_HIP(hipGetLastError());
+            } else if ((rc = fir_range_distances_dev(h->g, q, nq, 0, v.d, cdist, st))) {
+                return rc;
+            }
+            if ((rc = dem_stage_mark(h, st))) return rc;
+            hipLaunchKernelGGL(k_dem_fold, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos, cdist, thr, rs.parts);
+            FIR_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_dem_finish, dim3(nq), dim3(kBlock), 0, st, rs.Q, rs.parts, mc > 0 ? walk_blocks : 0, used, mc, order,
+                           row ? row + q0 : nullptr, dist ? dist + q0 : nullptr, found ? found + q0 : nullptr, bcalc, btie);
+        FIR_HIP(hipGetLastError());
+        if (mc > 0) {
+            hipLaunchKernelGGL(k_dem_count, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos, cdist, bcalc, btie);
+            FIR_HIP(hipGetLastError());
+            if ((rc = dem_stage_mark(h, st))) return rc;                  // (kStages + 1 marks per batch; timing needs mc > 0)
+        }
+    }
+    return FIR_OK;
+}
+
+int dem_recognize_check(fir_dem* h, const float* queries, int32_t qb, const void* row, const void* dist, const void* found, const void* calc,
+                        const void* tie) {
+    if (!h) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: NULL handle");
+    if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: qb=%d must be positive", qb);
+    if (!queries) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: queries is NULL");
+    if (!row && !dist && !found && !calc && !tie) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: every output is NULL");
+    return FIR_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -406,6 +965,7 @@ int fir_dem_destroy(fir_dem* h) {
     (void)hipSetDevice(h->v.device);
     if (h->pivot_rows) fir_gallery_destroy(h->pivot_rows);
     if (h->pin) (void)hipHostFree(h->pin);
+    for (hipEvent_t e : h->probe_ev) (void)hipEventDestroy(e);
     delete h;
     return FIR_OK;
 }
@@ -501,21 +1061,7 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
     FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
-    // candidates per wave: 4 while the workgroup's 1 + 16 rows fit 64 KiB of LDS (d <= 960), else 1; rows beyond 2 048 features
-    // go through LDS in pieces of 512 float4
-    const int cpw = (size_t)17 * dp4 * 16 <= 64 * 1024 ? 4 : 1;
-    const int span = std::min(dp4, 512);
-    const size_t lds = (size_t)(1 + (kBlock / 64) * cpw) * span * 16;
-    const int per_block = (kBlock / 64) * cpw;
-    const dim3 grid((m + per_block - 1) / per_block, qb);
-#define FIR_ROWS_LAUNCH(M, Q, R, O)                                                                                                       \
-    hipLaunchKernelGGL(k_rows_dist<M>, grid, dim3(kBlock), lds, v.stream, (const float4*)gal4, dp4, v.n, Q, v.d, R, m, start_pos, end_pos, O, cpw, span)
-#define FIR_ROWS_BY_METRIC(Q, R, O)                                                                                                       \
-    do {                                                                                                                                  \
-        if (metric == FIR_METRIC_L2) FIR_ROWS_LAUNCH(fir::kL2, Q, R, O);                                                                  \
-        else if (metric == FIR_METRIC_CHI2) FIR_ROWS_LAUNCH(fir::kChi2, Q, R, O);                                                         \
-        else FIR_ROWS_LAUNCH(fir::kKL, Q, R, O);                                                                                          \
-    } while (0)
+#define FIR_ROWS_BY_METRIC(Q, R, O) launch_rows_dist(gal4, dp4, v.n, metric, v.d, Q, qb, R, m, start_pos, end_pos, O, v.stream)
     const size_t qbytes = ((size_t)qb * v.d * 4 + 15) & ~(size_t)15, rbytes = (size_t)qb * m * 4;
     // Small calls (the DEM walk: one query, a few hundred candidate rows): everything through the handle's pinned,
     // device-visible buffer -- no allocation, no copy engine, no stream synchronisation (a ticket written behind the kernel).
@@ -547,10 +1093,84 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
     FIR_HIP(hipMemcpyAsync(drows, rows, rbytes, hipMemcpyHostToDevice, v.stream));
     FIR_ROWS_BY_METRIC((const float*)dq, (const int32_t*)drows, (float*)dout);
 #undef FIR_ROWS_BY_METRIC
-#undef FIR_ROWS_LAUNCH
     FIR_HIP(hipGetLastError());
     FIR_HIP(hipMemcpyAsync(out, dout, rbytes, hipMemcpyDeviceToHost, v.stream));
     FIR_HIP(hipStreamSynchronize(v.stream));
+    return FIR_OK;
+}
+
+// Measurement hooks of tools/dem_recognize_probe.py (not in include/fir_amd.h; the tool resolves them by name). form: 0 = the library's choice, 1 = gather, 2 = dense
+// candidate distances (the answers are the same); timing != 0: events between the stages of every internal batch from now on.
+int fir_dem_probe_(fir_dem* h, int32_t form, int32_t timing) {
+    if (!h || form < 0 || form > 2) return fir_fail_(FIR_ERR_ARG, "fir_dem_probe_: bad argument");
+    h->probe_form = form;
+    h->probe_timing = timing != 0;
+    h->probe_ev_used = 0;
+    return FIR_OK;
+}
+// ms[6] <- the device time of each stage (pivots, likelihoods, select, mark, candidate distances, fold + finish + count), summed
+// over the batches queued since fir_dem_probe_ (calls with candidates to check only); starts the sums again.
+int fir_dem_probe_times_(fir_dem* h, float* ms) {
+    if (!h || !ms) return fir_fail_(FIR_ERR_ARG, "fir_dem_probe_times_: NULL argument");
+    FIR_HIP(hipSetDevice(h->v.device));
+    for (int k = 0; k < kStages; ++k) ms[k] = 0.0f;
+    if (h->probe_ev_used % (kStages + 1)) return fir_fail_(FIR_ERR_STATE, "fir_dem_probe_times_: a timed call had no candidates to check");
+    for (size_t b = 0; b + kStages < h->probe_ev_used; b += kStages + 1) {
+        FIR_HIP(hipEventSynchronize(h->probe_ev[b + kStages]));
+        for (int k = 0; k < kStages; ++k) {
+            float t = 0.0f;
+            FIR_HIP(hipEventElapsedTime(&t, h->probe_ev[b + k], h->probe_ev[b + k + 1]));
+            ms[k] += t;
+        }
+    }
+    h->probe_ev_used = 0;
+    return FIR_OK;
+}
+
+int fir_dem_recognize_dev(fir_dem* h, const float* d_queries, int32_t qb, float threshold, int32_t image_count_to_check, int32_t* d_row,
+                          float* d_dist, int32_t* d_found, int32_t* d_calc, int32_t* d_tie, void* stream) {
+    int rc = dem_recognize_check(h, d_queries, qb, d_row, d_dist, d_found, d_calc, d_tie);
+    if (rc) return rc;
+    FIR_HIP(hipSetDevice(h->v.device));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->v.stream;
+    FirCallOrder order(h->g, st);
+    if (order.rc) return order.rc;
+    if ((rc = dem_recognize_prepare(h))) return rc;
+    return dem_recognize_queue(h, d_queries, qb, threshold, image_count_to_check, d_row, d_dist, d_found, d_calc, d_tie, st);
+}
+
+int fir_dem_recognize(fir_dem* h, const float* queries, int32_t qb, float threshold, int32_t image_count_to_check, int32_t* row, float* dist,
+                      int32_t* found, int32_t* calc, int32_t* tie) {
+    int rc = dem_recognize_check(h, queries, qb, row, dist, found, calc, tie);
+    if (rc) return rc;
+    const fir_gallery_view& v = h->v;
+    FIR_HIP(hipSetDevice(v.device));
+    FirCallOrder order(h->g, v.stream);
+    if (order.rc) return order.rc;
+    if ((rc = dem_recognize_prepare(h))) return rc;
+    const size_t qbytes = (size_t)qb * v.d * 4, obytes = (size_t)qb * 4;
+    if (qbytes > h->r_q_cap) {                                            // (no call is using them: this form waits for its kernels)
+        h->r_q.release();
+        h->r_q_cap = 0;
+        FIR_HIP(h->r_q.alloc(qbytes));
+        h->r_q_cap = qbytes;
+    }
+    if (5 * obytes > h->r_out_cap) {
+        h->r_out.release();
+        h->r_out_cap = 0;
+        FIR_HIP(h->r_out.alloc(5 * obytes));
+        h->r_out_cap = 5 * obytes;
+    }
+    int32_t* o = h->r_out.as<int32_t>();
+    FIR_HIP(hipMemcpyAsync(h->r_q.p, queries, qbytes, hipMemcpyHostToDevice, v.stream));
+    if ((rc = dem_recognize_queue(h, h->r_q.as<float>(), qb, threshold, image_count_to_check, o, (float*)(o + qb), o + 2 * (size_t)qb, o + 3 * (size_t)qb,
+                                  o + 4 * (size_t)qb, v.stream)))
+        return rc;
+    void* outs[5] = {row, dist, found, calc, tie};
+    for (int k = 0; k < 5; ++k)
+        if (outs[k]) FIR_HIP(hipMemcpyAsync(outs[k], o + (size_t)k * qb, obytes, hipMemcpyDeviceToHost, v.stream));
+    FIR_HIP(hipStreamSynchronize(v.stream));
+    order.done();
     return FIR_OK;
 }
 

@@ -305,6 +305,33 @@ int fir_dem_get(fir_dem* h, int32_t* pivots_out, float* min_other_out, float* ta
  * float, each row visited as often as the reference's index bookkeeping visits it. Either may be NULL. */
 int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* pivot_dist_out, float* lik_out);
 
+/* DirectedEnumeration::recognize, ann.cpp:416-507 (PIVOT build), for qb queries in one call. threshold = the
+ * object's `threshold`; image_count_to_check as setImageCountToCheck takes it (<= 0 or >= n: n).
+ * row[qb] (bestIndex or -1), dist[qb] (bestDistance; FLT_MAX when no row was ever best), found[qb]
+ * (isFoundLessThreshold), calc[qb] (distanceCalcCount), tie[qb]; any may be NULL.
+ * Per query, with `used` kept pivots, M the count to check, order[] and the likelihoods as fir_dem_get /
+ * fir_dem_likelihoods report them:
+ *  1. the pivots in order, bestDistance from FLT_MAX with a strict <; a pivot that becomes the best below the
+ *     threshold is the answer (found = 1, calc = its number + 1, tie = 0);
+ *  2. Mc = M - used; Mc <= 0: the pivots' best, found = 0, calc = used, tie = 0;
+ *  3. the candidates are the POSITIONS p in [used, n) of order[] (it may hold a row twice), with the key
+ *     (orderable bits of likelihood[order[p]], p): equal likelihoods are walked in position order;
+ *  4. the Mc smallest keys are selected, and distance(query, order[p]) over all features is taken for them;
+ *  5. if a selected candidate is below the threshold, the one with the smallest key is the answer: found = 1,
+ *     calc = used + the number of selected keys up to its own;
+ *  6. otherwise found = 0, calc = used + Mc, and the selected candidate with the smallest (distance, key) is the
+ *     answer if its distance is strictly below the pivots' best, which stands otherwise.
+ * The reference's std::partial_sort leaves the order of equal likelihoods open. tie = 1 says that another order
+ * could give another answer: an unselected position shares its likelihood with a selected one; in 5, another
+ * selected position has the answer's likelihood; in 6, when a candidate wins, another selected position has both
+ * its likelihood and its distance; or a pivot distance is NaN. With tie = 0 every such order gives this answer. */
+int fir_dem_recognize(fir_dem* h, const float* queries, int32_t qb, float threshold, int32_t image_count_to_check,
+                      int32_t* row, float* dist, int32_t* found, int32_t* calc, int32_t* tie);
+/* Device pointers, asynchronous on `stream` (NULL: the gallery handle's), never synchronises once its scratch is
+ * large enough; ordered with the other calls on the gallery handle like every *_dev call. */
+int fir_dem_recognize_dev(fir_dem* h, const float* d_queries, int32_t qb, float threshold, int32_t image_count_to_check,
+                          int32_t* d_row, float* d_dist, int32_t* d_found, int32_t* d_calc, int32_t* d_tie, void* stream);
+
 /* out[qb][m] = distance(query q, gallery row rows[q][m]) over [start_pos, end_pos) (end_pos 0 = d): the candidate
  * checks of an enumeration (CHECK_FOR_BEST_DIST, ann.cpp:389-399) as one gather. Rows are LOCAL indices; a row
  * outside the gallery yields 100000. */
