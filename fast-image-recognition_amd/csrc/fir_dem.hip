@@ -13,20 +13,17 @@
 // The running far[j] is the reference's inner `ind` loop evaluated incrementally: the same additions in the same order.
 //
 // Query time (DirectedEnumeration::recognize, ann.cpp:411-507) looks like a sequential, early-exit walk, but it is one
-// selection threshold, two minima and a count: fir_dem_recognize answers a batch on the device with no host step
-// (the kernels are further down, "DirectedEnumeration::recognize on the device"); its tie flag marks the queries whose
-// answer hangs on the order of equal likelihoods. The C++ shim (host/fir_classifiers.cpp) still walks on the host over the
-// two pieces below until the new call has been timed against them (profiles/dem_recognize.txt):
-//   k_dem_lik      likelihoods[nu] += (dist(query, pivot i) - table[i][nu])^2 for the <= 32 pivots kept (:437-446):
-//                  one lane per gallery row, the pivots in order, float adds in the reference's order; n*P*4 bytes of
-//                  table per batch of 8 queries instead of n*d*4 bytes of gallery
-//   k_rows_dist    distance(query, row) for a per-query list of candidate rows (CHECK_FOR_BEST_DIST, :389-399)
+// selection threshold, two minima and a count: fir_dem_recognize answers a batch on the device with no host step (the kernels
+// are further down, "DirectedEnumeration::recognize on the device"; the host decides a call's shape once, RecPlan, and queues
+// one step per stage, kRecSteps); its tie flag marks the queries whose answer hangs on the order of equal likelihoods. The C++
+// shim (host/fir_classifiers.cpp) still walks on the host over two pieces until the new call has been timed against them
+// (profiles/dem_recognize.txt): fir_dem_likelihoods (k_dem_lik + k_dem_lik_fix, the stage recognize queues too: n*P*4 bytes
+// of table per batch of 8 queries instead of n*d*4 bytes of gallery) and fir_rows_distances (k_rows_dist, CHECK_FOR_BEST_DIST).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <cstdio>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -39,7 +36,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 1024;
-
 
 struct Part {       // one block's partial result
     double far;     // largest far sum > 0 seen (0 = none)
@@ -617,42 +613,42 @@ __global__ void __launch_bounds__(64) k_dem_publish(const float* __restrict__ pd
     if (threadIdx.x == 0) __hip_atomic_store(ticket_word, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    template <typename T> T* as() { return (T*)p; }
-};
-
 // The PIVOT build. Table row ii goes to d_table + min(ii, keep_rows) * n (rows past keep_rows share one scratch row), the
-// pivot's features to d_pivrows + min(ii, keep_piv) * d. pivots/min_other are left on the device.
+// pivot's features to d_pivrows + min(ii, keep_piv) * d. Back on the host: pivots[n_pivots], min_other[n_pivots] and the
+// number of pivots built (the rest are -1); the last two may be NULL.
 int dem_build(fir_gallery* g, const fir_gallery_view& v, int first_pivot, int n_pivots, float* d_table, int keep_rows, float* d_pivrows,
-              int keep_piv, int32_t* d_pivots, float* d_min_other) {
+              int keep_piv, int32_t* pivots, float* min_other, int32_t* built) {
     const void* gal4 = nullptr;
     int dp4 = 0;
     if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
     const int n = (int)v.n;
     const int nblocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
-    Buf dfar, dparts;
-    FIR_HIP(dfar.alloc((size_t)n * 8));
-    FIR_HIP(dparts.alloc((size_t)nblocks * sizeof(Part)));
-    FIR_HIP(hipMemsetAsync(d_pivots, 0xff, (size_t)n_pivots * 4, v.stream));
-    FIR_HIP(hipMemcpyAsync(d_pivots, &first_pivot, 4, hipMemcpyHostToDevice, v.stream));
+    FirBuf dfar, dparts, dpiv, dmo;
+    FIR_HIP(dfar.reserve((size_t)n * 8));
+    FIR_HIP(dparts.reserve((size_t)nblocks * sizeof(Part)));
+    FIR_HIP(dpiv.reserve((size_t)n_pivots * 4));
+    FIR_HIP(dmo.reserve((size_t)n_pivots * 4));
+    FIR_HIP(hipMemsetAsync(dpiv.p, 0xff, (size_t)n_pivots * 4, v.stream));
+    FIR_HIP(hipMemcpyAsync(dpiv.p, &first_pivot, 4, hipMemcpyHostToDevice, v.stream));
     for (int ii = 0; ii < n_pivots; ++ii) {
         float* row = d_table + (size_t)std::min(ii, keep_rows) * n;
         float* q = d_pivrows + (size_t)std::min(ii, keep_piv) * v.d;
         hipLaunchKernelGGL(k_dem_gather, dim3(std::max(1, std::min(64, (dp4 + kBlock - 1) / kBlock))), dim3(kBlock), 0, v.stream,
-                           (const float4*)gal4, dp4, v.d, d_pivots, ii, q);
+                           (const float4*)gal4, dp4, v.d, dpiv.as<int32_t>(), ii, q);
         FIR_HIP(hipGetLastError());
         const int rc = fir_range_distances_dev(g, q, 1, 0, v.d, row, v.stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_dem_step, dim3(nblocks), dim3(kBlock), 0, v.stream, row, v.cls, n, d_pivots, ii, dfar.as<double>(), dparts.as<Part>());
+        hipLaunchKernelGGL(k_dem_step, dim3(nblocks), dim3(kBlock), 0, v.stream, row, v.cls, n, dpiv.as<int32_t>(), ii, dfar.as<double>(),
+                           dparts.as<Part>());
         FIR_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_dem_pick, dim3(1), dim3(kBlock), 0, v.stream, dparts.as<Part>(), nblocks, ii, n_pivots, d_pivots, d_min_other);
+        hipLaunchKernelGGL(k_dem_pick, dim3(1), dim3(kBlock), 0, v.stream, dparts.as<Part>(), nblocks, ii, n_pivots, dpiv.as<int32_t>(),
+                           dmo.as<float>());
         FIR_HIP(hipGetLastError());
     }
-    FIR_HIP(hipStreamSynchronize(v.stream));   // dfar/dparts are freed on return
+    FIR_HIP(hipStreamSynchronize(v.stream));   // the four buffers are freed on return
+    FIR_HIP(hipMemcpy(pivots, dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    if (min_other) FIR_HIP(hipMemcpy(min_other, dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    if (built) *built = (int32_t)(std::find_if(pivots, pivots + n_pivots, [](int32_t p) { return p < 0; }) - pivots);
     return FIR_OK;
 }
 
@@ -666,10 +662,34 @@ int check_build_args(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_
     return FIR_OK;
 }
 
-int count_built(const int32_t* pivots, int n_pivots) {
-    for (int ii = 0; ii < n_pivots; ++ii)
-        if (pivots[ii] < 0) return ii;
-    return n_pivots;
+// The reference keeps the candidates in an index array and moves each pivot to its front with two plain writes (ann.cpp:431-432);
+// the update loop (:437-446) then runs over the POSITIONS behind the front. Replay that on a sparse copy: which rows does each pivot's
+// loop visit, and how often? Only rows in {0..used-1} + {pivots} can deviate from "once per pivot": they are `special`, mult[e][i] =
+// visits of special[e] by the loop of pivot i, and order_mods = (position, value) wherever the index array is not the identity at the end.
+void dem_replay_index(const int32_t* pivots, int used, std::vector<int32_t>* special, std::vector<uint8_t>* mult,
+                      std::vector<std::pair<int32_t, int32_t> >* order_mods) {
+    std::unordered_map<int32_t, int32_t> mod;   // position -> value, where it is not the identity
+    auto at = [&](int32_t pos) { auto it = mod.find(pos); return it == mod.end() ? pos : it->second; };
+    for (int i = 0; i < used; ++i) special->push_back(i);
+    special->insert(special->end(), pivots, pivots + used);
+    std::sort(special->begin(), special->end());
+    special->erase(std::unique(special->begin(), special->end()), special->end());
+    mult->assign(special->size() * kMaxUsed, 0);
+    for (int i = 0; i < used; ++i) {
+        const int32_t p = pivots[i];
+        mod[p] = at(i);
+        mod[i] = p;
+        for (size_t e = 0; e < special->size(); ++e) {
+            const int32_t w = (*special)[e];
+            int cnt = (w > i && mod.find(w) == mod.end()) ? 1 : 0;
+            for (const auto& kv : mod)
+                if (kv.first > i && kv.second == w) ++cnt;
+            (*mult)[e * kMaxUsed + i] = (uint8_t)std::min(cnt, 255);
+        }
+    }
+    for (const auto& kv : mod)
+        if (kv.first != kv.second) order_mods->push_back(kv);
+    std::sort(order_mods->begin(), order_mods->end());
 }
 
 }  // namespace
@@ -678,22 +698,21 @@ struct fir_dem {
     fir_gallery* g = nullptr;        // borrowed
     fir_gallery* pivot_rows = nullptr;   // the kept pivots as a gallery of their own: distance(query, pivot i) is one tiny scan
     fir_gallery_view v;
-    int n_pivots = 0, used = 0, built = 0;
+    int n_pivots = 0, used = 0, built = 0, nexc = 0;   // nexc: exception rows of the likelihood update (exc_rows, exc_mult)
     std::vector<int32_t> pivots;
     std::vector<float> min_other;
     std::vector<std::pair<int32_t, int32_t> > order_mods;   // (position, value): where likelihood_indices differs from identity after the pivots
-    Buf table, pivrows, exc_rows, exc_mult, q, pd, lik;
-    int nexc = 0;
+    FirBuf table, pivrows, exc_rows, exc_mult, q, pd, lik;
     // galleries up to kPinLikRows rows: queries in and pivot distances / likelihoods out through pinned, device-visible host
-    // memory the kernels address directly, completion by a ticket word (no copy engine, no stream synchronisation)
-    void* pin = nullptr;
+    // memory the kernels address directly, completion by a ticket word (no copy engine, no stream synchronisation): one block,
+    // laid out at create, q[8][d] | pd[8][32] | lik[8][n] | the ticket word on the next 8-byte boundary; q == NULL: none
+    struct Pin { float *q = nullptr, *pd = nullptr, *lik = nullptr; unsigned long long* tword = nullptr; } pin;
     unsigned long long ticket = 0;
-    // fir_dem_recognize: allocated by its first call, of a size that depends on n only, its own (fir_dem_likelihoods may run
-    // between two asynchronous calls). r_q / r_out: the host-pointer form's queries and results, grown to the largest qb seen.
+    // fir_dem_recognize: allocated by its first call, of a size that depends on n only, its own (fir_dem_likelihoods may run between two
+    // asynchronous calls); r_q / r_out (the host-pointer form's queries and results), r_dist (candidate distances, [8][Mc] gather, [8][n]
+    // dense) and r_pos / r_rows (the gather's lists) are the call-sized scratch dem_grow grows.
     bool rec_ready = false;
-    Buf d_order, d_pivots, r_state, r_pd, r_lik, r_dist, r_pos, r_rows, r_q, r_out;
-    size_t r_q_cap = 0, r_out_cap = 0;
-    size_t r_dist_cap = 0, r_pos_cap = 0, r_rows_cap = 0;   // candidate distances ([8][Mc] gather, [8][n] dense) and the gather's lists, grown to the call's need
+    FirBuf d_order, d_pivots, r_state, r_pd, r_lik, r_dist, r_pos, r_rows, r_q, r_out;
     // measurement (fir_dem_probe_, tools/dem_recognize_probe.py): a forced candidate-distance form, events between the stages
     int probe_form = 0;
     bool probe_timing = false;
@@ -703,26 +722,55 @@ struct fir_dem {
 
 namespace {
 
-// r_state: DemQ[8] | SelState[9][8] | FoldPart[8][kWalkMaxBlocks] | calc[8], tie[8] stand-ins | histograms [8 digits][8][256]
+// lik[nq][n] <- the likelihoods of nq <= kLikBatch queries from their pivot distances pd[nq][used]: every row once per pivot,
+// then the exception rows with their multiplicities. Device-visible pointers.
+int dem_queue_lik(fir_dem* h, const float* pd, int nq, float* lik, hipStream_t st) {
+    const int n = (int)h->v.n;
+    hipLaunchKernelGGL(k_dem_lik<kLikBatch>, dim3(std::min(kMaxBlocks, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, h->table.as<float>(), n,
+                       h->used, pd, nq, lik);
+    FIR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_dem_lik_fix, dim3((h->nexc * nq + 63) / 64), dim3(64), 0, st, h->table.as<float>(), n, h->used, pd, nq,
+                       h->exc_rows.as<int32_t>(), h->exc_mult.as<uint8_t>(), h->nexc, lik);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+
+// fir_dem_create's query side: the exception rows of the likelihood update, fir_dem_likelihoods' scratch and (up to kPinLikRows rows) pinned block.
+int dem_create_query_side(fir_dem* h) {
+    const fir_gallery_view& v = h->v;
+    std::vector<int32_t> special;
+    std::vector<uint8_t> mult;
+    dem_replay_index(h->pivots.data(), h->used, &special, &mult, &h->order_mods);
+    h->nexc = (int)special.size();
+    FIR_HIP(h->exc_rows.reserve(special.size() * 4));
+    FIR_HIP(h->exc_mult.reserve(mult.size()));
+    FIR_HIP(hipMemcpy(h->exc_rows.p, special.data(), special.size() * 4, hipMemcpyHostToDevice));
+    FIR_HIP(hipMemcpy(h->exc_mult.p, mult.data(), mult.size(), hipMemcpyHostToDevice));
+    FIR_HIP(h->q.reserve((size_t)kLikBatch * v.d * 4));
+    FIR_HIP(h->pd.reserve((size_t)kLikBatch * kMaxUsed * 4));
+    FIR_HIP(h->lik.reserve((size_t)kLikBatch * v.n * 4));
+    if (v.n > kPinLikRows) return FIR_OK;
+    const size_t bytes = (size_t)kLikBatch * ((size_t)v.d + kMaxUsed + (size_t)v.n) * 4 + 64;
+    void* pin = nullptr;
+    FIR_HIP(hipHostMalloc(&pin, bytes, hipHostMallocDefault));
+    std::memset(pin, 0, bytes);
+    h->pin.q = (float*)pin;
+    h->pin.pd = h->pin.q + (size_t)kLikBatch * v.d;
+    h->pin.lik = h->pin.pd + (size_t)kLikBatch * kMaxUsed;
+    h->pin.tword = (unsigned long long*)(((uintptr_t)(h->pin.lik + (size_t)kLikBatch * v.n) + 7) & ~(uintptr_t)7);
+    return FIR_OK;
+}
+
+// r_state, in device memory and addressed by member. sel[j]: the select's state before digit j; parts[q]: the fold's partials of query q
+// (walk_blocks of them); calc / tie: stand-ins for outputs not asked for; hist[j]: digit j's histograms of the several-workgroups select.
 struct RecState {
-    DemQ* Q;
-    SelState* sel;
-    FoldPart* parts;
-    int32_t *calc, *tie;
-    unsigned* hist;
-    static constexpr size_t kHistBytes = (size_t)8 * kLikBatch * 256 * sizeof(unsigned);
-    static size_t bytes() {
-        return sizeof(DemQ) * kLikBatch + sizeof(SelState) * 9 * kLikBatch + sizeof(FoldPart) * kLikBatch * kWalkMaxBlocks + 2 * 4 * kLikBatch + kHistBytes;
-    }
-    explicit RecState(void* p) {
-        Q = (DemQ*)p;
-        sel = (SelState*)(Q + kLikBatch);
-        parts = (FoldPart*)(sel + 9 * kLikBatch);
-        calc = (int32_t*)(parts + kLikBatch * kWalkMaxBlocks);
-        tie = calc + kLikBatch;
-        hist = (unsigned*)(tie + kLikBatch);
-    }
+    DemQ Q[kLikBatch];
+    SelState sel[9][kLikBatch];
+    FoldPart parts[kLikBatch][kWalkMaxBlocks];
+    int32_t calc[kLikBatch], tie[kLikBatch];
+    unsigned hist[8][kLikBatch][256];
 };
+static_assert(sizeof(RecState) == kLikBatch * (sizeof(DemQ) + 9 * sizeof(SelState) + kWalkMaxBlocks * sizeof(FoldPart) + 2 * 4 + 8 * 256 * 4), "no padding");
 
 int dem_recognize_prepare(fir_dem* h) {
     if (h->rec_ready) return FIR_OK;
@@ -730,36 +778,136 @@ int dem_recognize_prepare(fir_dem* h) {
     std::vector<int32_t> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = (int32_t)i;
     for (const auto& kv : h->order_mods) order[(size_t)kv.first] = kv.second;
-    FIR_HIP(h->d_order.alloc(n * 4));
-    FIR_HIP(h->d_pivots.alloc((size_t)kMaxUsed * 4));
-    FIR_HIP(h->r_state.alloc(RecState::bytes()));
-    FIR_HIP(h->r_pd.alloc((size_t)kLikBatch * kMaxUsed * 4));
-    FIR_HIP(h->r_lik.alloc((size_t)kLikBatch * n * 4));
+    FIR_HIP(h->d_order.reserve(n * 4));
+    FIR_HIP(h->d_pivots.reserve((size_t)kMaxUsed * 4));
+    FIR_HIP(h->r_state.reserve(sizeof(RecState)));
+    FIR_HIP(h->r_pd.reserve((size_t)kLikBatch * kMaxUsed * 4));
+    FIR_HIP(h->r_lik.reserve((size_t)kLikBatch * n * 4));
     FIR_HIP(hipMemset(h->r_lik.p, 0, (size_t)kLikBatch * n * 4));
-    FIR_HIP(hipMemset(h->r_state.p, 0, RecState::bytes()));
+    FIR_HIP(hipMemset(h->r_state.p, 0, sizeof(RecState)));
     FIR_HIP(hipMemcpy(h->d_order.p, order.data(), n * 4, hipMemcpyHostToDevice));
     FIR_HIP(hipMemcpy(h->d_pivots.p, h->pivots.data(), (size_t)h->used * 4, hipMemcpyHostToDevice));
     h->rec_ready = true;
     return FIR_OK;
 }
 
-// Scratch whose size depends on the call (Mc, the form): grown before anything is queued, after the handle's earlier calls have
-// finished with the old buffer.
-int dem_grow(fir_dem* h, Buf& b, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return FIR_OK;
+// Scratch whose size depends on the call (qb, Mc, the form): grown before anything is queued, after the handle's earlier calls have
+// finished with the old buffer; a quarter more than asked for, zero-filled.
+int dem_grow(fir_dem* h, FirBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return FIR_OK;
     const int rc = fir_gallery_wait_calls_(h->g);
     if (rc) return rc;
     FIR_HIP(hipStreamSynchronize(h->v.stream));
-    b.release();
-    cap = 0;
-    const size_t want = bytes + bytes / 4;
-    FIR_HIP(b.alloc(want));
-    FIR_HIP(hipMemset(b.p, 0, want));
-    cap = want;
+    FIR_HIP(b.reserve(bytes + bytes / 4));
+    FIR_HIP(hipMemset(b.p, 0, b.cap));
+    return FIR_OK;
+}
+
+// One call's shape, decided before anything is queued (dem_recognize_plan), and the device pointers its steps share (dem_recognize_reserve).
+struct RecPlan {
+    int M, mc, cnt;                       // images to check; candidates among them (M - used) out of cnt = n - used positions
+    bool gather;                          // candidate distances by gather (else the dense scan)
+    enum { kSelNone, kSelOne, kSelPasses } select;   // none: mc == cnt, every position is selected and head has said so
+    int walk_blocks;                      // workgroups per query of mark / fold / count
+    const void* gal4;                     // the gather's gallery, its row pitch and metric
+    int dp4, metric;
+    RecState* rs;                         // the handle's buffers, typed
+    const int32_t* order;
+    float *pd, *lik, *cdist;
+    int32_t *pos, *rows;                  // NULL in the dense form
+};
+
+int dem_recognize_plan(fir_dem* h, int image_count, RecPlan* p) {
+    const int n = (int)h->v.n, used = h->used;
+    p->cnt = n - used;
+    p->M = image_count > 0 && image_count < n ? image_count : n;
+    p->mc = p->M - used;
+    if (fir_gallery_tiled_(h->g, &p->gal4, &p->dp4) != FIR_OK || !p->gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
+    // (the gallery's metric now, not h->v.metric: fir_gallery_set_metric may have run since create)
+    const int rc = fir_gallery_info(h->g, nullptr, nullptr, &p->metric, nullptr);
+    if (rc) return rc;
+    p->gather = h->probe_form ? h->probe_form == 1 : p->mc < n / kGatherDiv;
+    p->select = p->mc >= p->cnt ? RecPlan::kSelNone : p->cnt <= kSelOneGroupRows ? RecPlan::kSelOne : RecPlan::kSelPasses;
+    p->walk_blocks = std::max(1, std::min(kWalkMaxBlocks, (p->cnt + 4 * kBlock - 1) / (4 * kBlock)));
+    return FIR_OK;
+}
+
+// The plan's call-sized scratch, grown to its need, and the buffers bound.
+int dem_recognize_reserve(fir_dem* h, RecPlan* p) {
+    const size_t list = (size_t)kLikBatch * p->mc * 4;
+    int rc;
+    if (p->mc > 0 && (rc = dem_grow(h, h->r_dist, p->gather ? list : (size_t)kLikBatch * h->v.n * 4))) return rc;
+    if (p->mc > 0 && p->gather && ((rc = dem_grow(h, h->r_pos, list)) || (rc = dem_grow(h, h->r_rows, list)))) return rc;
+    p->rs = h->r_state.as<RecState>();
+    p->order = h->d_order.as<int32_t>();
+    p->pd = h->r_pd.as<float>();
+    p->lik = h->r_lik.as<float>();
+    p->cdist = h->r_dist.as<float>();
+    p->pos = p->gather ? h->r_pos.as<int32_t>() : nullptr;
+    p->rows = p->gather ? h->r_rows.as<int32_t>() : nullptr;
+    return FIR_OK;
+}
+
+// The five results of a call or of one of its batches, any may be NULL; one internal batch (its calc / tie never are).
+struct RecOut { int32_t* row; float* dist; int32_t *found, *calc, *tie; };
+struct RecBatch { const float* q; int nq; float thr; RecOut out; hipStream_t st; };
+
+// The steps of a batch, one per stage and probe interval, in the order of kStage*. The driver checks a step's last launch.
+int rec_pivots(fir_dem* h, const RecPlan& p, const RecBatch& b) {
+    const int rc = fir_range_distances_dev(h->pivot_rows, b.q, b.nq, 0, h->v.d, p.pd, b.st);   // pd[q][used]
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_dem_head, dim3(1), dim3(64), 0, b.st, p.pd, h->used, b.nq, b.thr, h->d_pivots.as<int32_t>(), p.mc, p.cnt, p.rs->Q, p.rs->sel[0]);
+    return FIR_OK;
+}
+
+int rec_lik(fir_dem* h, const RecPlan& p, const RecBatch& b) { return dem_queue_lik(h, p.pd, b.nq, p.lik, b.st); }
+
+int rec_select(fir_dem* h, const RecPlan& p, const RecBatch& b) {
+    const int n = (int)h->v.n;
+    if (p.select == RecPlan::kSelOne) {
+        hipLaunchKernelGGL(k_dem_select_one, dim3(b.nq), dim3(kBlock), 0, b.st, p.lik, n, h->used, p.order, p.rs->Q, p.rs->sel[0]);
+    } else if (p.select == RecPlan::kSelPasses) {
+        FIR_HIP(hipMemsetAsync(p.rs->hist, 0, sizeof(p.rs->hist), b.st));
+        const dim3 grid((p.cnt + kSelSlice - 1) / kSelSlice, b.nq);
+        for (int pass = 0; pass <= 8; ++pass)
+            hipLaunchKernelGGL(k_dem_select_pass, pass < 8 ? grid : dim3(1, b.nq), dim3(kBlock), 0, b.st, p.lik, n, h->used, p.order, p.rs->Q,
+                               p.rs->sel[0], p.rs->hist[0][0], pass);
+    }
+    return FIR_OK;
+}
+
+int rec_mark(fir_dem* h, const RecPlan& p, const RecBatch& b) {
+    hipLaunchKernelGGL(k_dem_mark, dim3(p.walk_blocks, b.nq), dim3(kBlock), 0, b.st, p.lik, (int)h->v.n, h->used, p.order, p.rs->Q, p.mc, p.pos, p.rows);
+    return FIR_OK;
+}
+
+int rec_dist(fir_dem* h, const RecPlan& p, const RecBatch& b) {
+    const fir_gallery_view& v = h->v;
+    if (!p.gather) return fir_range_distances_dev(h->g, b.q, b.nq, 0, v.d, p.cdist, b.st);
+    launch_rows_dist(p.gal4, p.dp4, v.n, p.metric, v.d, b.q, b.nq, p.rows, p.mc, 0, v.d, p.cdist, b.st);
+    return FIR_OK;
+}
+
+int rec_walk(fir_dem* h, const RecPlan& p, const RecBatch& b) {
+    const int n = (int)h->v.n, used = h->used;
+    if (p.mc > 0) {                                                     // (without candidates finish alone, over no partials)
+        hipLaunchKernelGGL(k_dem_fold, dim3(p.walk_blocks, b.nq), dim3(kBlock), 0, b.st, p.lik, n, used, p.order, p.rs->Q, p.mc, p.pos, p.cdist, b.thr,
+                           p.rs->parts[0]);
+        FIR_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_dem_finish, dim3(b.nq), dim3(kBlock), 0, b.st, p.rs->Q, p.rs->parts[0], p.mc > 0 ? p.walk_blocks : 0, used, p.mc, p.order,
+                       b.out.row, b.out.dist, b.out.found, b.out.calc, b.out.tie);
+    FIR_HIP(hipGetLastError());
+    if (p.mc > 0)
+        hipLaunchKernelGGL(k_dem_count, dim3(p.walk_blocks, b.nq), dim3(kBlock), 0, b.st, p.lik, n, used, p.order, p.rs->Q, p.mc, p.pos, p.cdist,
+                           b.out.calc, b.out.tie);
     return FIR_OK;
 }
 
 enum { kStagePivots, kStageLik, kStageSelect, kStageMark, kStageDist, kStageWalk, kStages };
+using RecStep = int (*)(fir_dem*, const RecPlan&, const RecBatch&);
+constexpr RecStep kRecSteps[kStages] = {rec_pivots, rec_lik, rec_select, rec_mark, rec_dist, rec_walk};
+
 int dem_stage_mark(fir_dem* h, hipStream_t st) {
     if (!h->probe_timing) return FIR_OK;
     if (h->probe_ev_used == h->probe_ev.size()) {
@@ -771,94 +919,80 @@ int dem_stage_mark(fir_dem* h, hipStream_t st) {
     return FIR_OK;
 }
 
-// The kernels of one call, queued on st; every pointer is the device's. calc / tie may be NULL like the rest.
-int dem_recognize_queue(fir_dem* h, const float* dq, int qb, float thr, int image_count, int32_t* row, float* dist, int32_t* found, int32_t* calc,
-                        int32_t* tie, hipStream_t st) {
-    const fir_gallery_view& v = h->v;
-    const int n = (int)v.n, used = h->used, cnt = n - used;
-    const int M = image_count > 0 && image_count < n ? image_count : n;
-    const int mc = M - used;
-    const void* gal4 = nullptr;
-    int dp4 = 0;
-    if (fir_gallery_tiled_(h->g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
-    int32_t metric = 0;
-    int rc = fir_gallery_info(h->g, nullptr, nullptr, &metric, nullptr);
-    if (rc) return rc;
-    const bool gather = h->probe_form ? h->probe_form == 1 : mc < n / kGatherDiv;
-    if (mc > 0) {
-        if ((rc = dem_grow(h, h->r_dist, h->r_dist_cap, (size_t)kLikBatch * (gather ? mc : n) * 4))) return rc;
-        if (gather && ((rc = dem_grow(h, h->r_pos, h->r_pos_cap, (size_t)kLikBatch * mc * 4)) ||
-                       (rc = dem_grow(h, h->r_rows, h->r_rows_cap, (size_t)kLikBatch * mc * 4))))
-            return rc;
-    }
-    const RecState rs(h->r_state.p);
-    const int32_t* order = h->d_order.as<int32_t>();
-    float *pd = h->r_pd.as<float>(), *lik = h->r_lik.as<float>(), *cdist = h->r_dist.as<float>();
-    int32_t* pos = gather ? h->r_pos.as<int32_t>() : nullptr;
-    const int lik_blocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
-    const int walk_blocks = std::max(1, std::min(kWalkMaxBlocks, (cnt + 4 * kBlock - 1) / (4 * kBlock)));
+// The kernels of one call, queued on st; every pointer is the device's. A probe mark in front of every stage and, with candidates,
+// one behind the last: kStages + 1 per batch. Without candidates the batch is the pivots and finish (timing needs mc > 0).
+int dem_recognize_queue(fir_dem* h, const RecPlan& p, const float* dq, int qb, float thr, const RecOut& out, hipStream_t st) {
     for (int q0 = 0; q0 < qb; q0 += kLikBatch) {
-        const int nq = std::min(kLikBatch, qb - q0);
-        const float* q = dq + (size_t)q0 * v.d;
-        int32_t* bcalc = calc ? calc + q0 : rs.calc;
-        int32_t* btie = tie ? tie + q0 : rs.tie;
-        if ((rc = dem_stage_mark(h, st))) return rc;
-        if ((rc = fir_range_distances_dev(h->pivot_rows, q, nq, 0, v.d, pd, st))) return rc;   // pd[q][used]
-        hipLaunchKernelGGL(k_dem_head, dim3(1), dim3(64), 0, st, pd, used, nq, thr, h->d_pivots.as<int32_t>(), mc, cnt, rs.Q, rs.sel);
-        FIR_HIP(hipGetLastError());
-        if ((rc = dem_stage_mark(h, st))) return rc;
-        if (mc > 0) {
-            hipLaunchKernelGGL(k_dem_lik<kLikBatch>, dim3(lik_blocks), dim3(kBlock), 0, st, h->table.as<float>(), n, used, pd, nq, lik);
-            hipLaunchKernelGGL(k_dem_lik_fix, dim3((h->nexc * nq + 63) / 64), dim3(64), 0, st, h->table.as<float>(), n, used, pd, nq,
-                               h->exc_rows.as<int32_t>(), h->exc_mult.as<uint8_t>(), h->nexc, lik);
-            FIR_HIP(hipGetLastError());
-            if ((rc = dem_stage_mark(h, st))) return rc;
-            if (mc < cnt) {                                               // (mc == cnt: every position is selected, head has said so)
-                if (cnt <= kSelOneGroupRows) {
-                    hipLaunchKernelGGL(k_dem_select_one, dim3(nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, rs.sel);
-                } else {
-                    FIR_HIP(hipMemsetAsync(rs.hist, 0, RecState::kHistBytes, st));
-                    const dim3 grid((cnt + kSelSlice - 1) / kSelSlice, nq);
-                    for (int pass = 0; pass <= 8; ++pass)
-                        hipLaunchKernelGGL(k_dem_select_pass, pass < 8 ? grid : dim3(1, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, rs.sel,
-                                           rs.hist, pass);
-                }
-                FIR_HIP(hipGetLastError());
-            }
-            if ((rc = dem_stage_mark(h, st))) return rc;
-            hipLaunchKernelGGL(k_dem_mark, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos,
-                               gather ? h->r_rows.as<int32_t>() : nullptr);
-            FIR_HIP(hipGetLastError());
-            if ((rc = dem_stage_mark(h, st))) return rc;
-            if (gather) {
-                launch_rows_dist(gal4, dp4, v.n, metric, v.d, q, nq, h->r_rows.as<int32_t>(), mc, 0, v.d, cdist, st);
-                FIR_HIP(hipGetLastError());
-            } else if ((rc = fir_range_distances_dev(h->g, q, nq, 0, v.d, cdist, st))) {
-                return rc;
-            }
-            if ((rc = dem_stage_mark(h, st))) return rc;
-            hipLaunchKernelGGL(k_dem_fold, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos, cdist, thr, rs.parts);
+        const RecOut o = {out.row ? out.row + q0 : nullptr, out.dist ? out.dist + q0 : nullptr, out.found ? out.found + q0 : nullptr,
+                          out.calc ? out.calc + q0 : p.rs->calc, out.tie ? out.tie + q0 : p.rs->tie};
+        const RecBatch b = {dq + (size_t)q0 * h->v.d, std::min(kLikBatch, qb - q0), thr, o, st};
+        int rc;
+        for (int s = 0; s < kStages; ++s) {
+            if (p.mc <= 0 && s != kStagePivots && s != kStageWalk) continue;
+            if ((rc = dem_stage_mark(h, st)) || (rc = kRecSteps[s](h, p, b))) return rc;
             FIR_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_dem_finish, dim3(nq), dim3(kBlock), 0, st, rs.Q, rs.parts, mc > 0 ? walk_blocks : 0, used, mc, order,
-                           row ? row + q0 : nullptr, dist ? dist + q0 : nullptr, found ? found + q0 : nullptr, bcalc, btie);
-        FIR_HIP(hipGetLastError());
-        if (mc > 0) {
-            hipLaunchKernelGGL(k_dem_count, dim3(walk_blocks, nq), dim3(kBlock), 0, st, lik, n, used, order, rs.Q, mc, pos, cdist, bcalc, btie);
-            FIR_HIP(hipGetLastError());
-            if ((rc = dem_stage_mark(h, st))) return rc;                  // (kStages + 1 marks per batch; timing needs mc > 0)
-        }
+        if (p.mc > 0 && (rc = dem_stage_mark(h, st))) return rc;
     }
     return FIR_OK;
 }
 
-int dem_recognize_check(fir_dem* h, const float* queries, int32_t qb, const void* row, const void* dist, const void* found, const void* calc,
-                        const void* tie) {
+// Both entry points. host: queries and results are the host's: the call runs on the handle's own stream, the results come back
+// through one device block of five columns [row | dist | found | calc | tie][qb], and it waits for them.
+int dem_recognize_call(fir_dem* h, const float* queries, int32_t qb, float thr, int32_t image_count, const RecOut& out, bool host, void* stream) {
     if (!h) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: NULL handle");
     if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: qb=%d must be positive", qb);
     if (!queries) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: queries is NULL");
-    if (!row && !dist && !found && !calc && !tie) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: every output is NULL");
+    if (!out.row && !out.dist && !out.found && !out.calc && !out.tie) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: every output is NULL");
+    const fir_gallery_view& v = h->v;
+    FIR_HIP(hipSetDevice(v.device));
+    const hipStream_t st = !host && stream ? (hipStream_t)stream : v.stream;
+    FirCallOrder order(h->g, st);
+    if (order.rc) return order.rc;
+    RecPlan p{};
+    int rc;
+    if ((rc = dem_recognize_prepare(h)) || (rc = dem_recognize_plan(h, image_count, &p)) || (rc = dem_recognize_reserve(h, &p))) return rc;
+    if (!host) return dem_recognize_queue(h, p, queries, qb, thr, out, st);
+    const size_t qbytes = (size_t)qb * v.d * 4, obytes = (size_t)qb * 4;
+    if ((rc = dem_grow(h, h->r_q, qbytes)) || (rc = dem_grow(h, h->r_out, 5 * obytes))) return rc;
+    int32_t* o = h->r_out.as<int32_t>();
+    FIR_HIP(hipMemcpyAsync(h->r_q.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    const RecOut dev = {o, (float*)(o + qb), o + 2 * (size_t)qb, o + 3 * (size_t)qb, o + 4 * (size_t)qb};
+    if ((rc = dem_recognize_queue(h, p, h->r_q.as<float>(), qb, thr, dev, st))) return rc;
+    void* outs[5] = {out.row, out.dist, out.found, out.calc, out.tie};
+    for (int k = 0; k < 5; ++k)
+        if (outs[k]) FIR_HIP(hipMemcpyAsync(outs[k], o + (size_t)k * qb, obytes, hipMemcpyDeviceToHost, st));
+    FIR_HIP(hipStreamSynchronize(st));
+    order.done();
     return FIR_OK;
+}
+
+// The pinned, device-visible buffer a gallery handle lends to a small fir_rows_distances call: queries and rows share its query
+// block (the rows on the next 16-byte boundary), the distances come back in its results block, whose last word (of 4096) is the ticket's.
+struct RowsPin { float* q; int32_t* rows; float* out; unsigned long long* tword; };
+
+// Small calls (the DEM walk: one query, a few hundred candidate rows): everything through the lent buffer -- no allocation, no
+// copy engine, no stream synchronisation (a ticket written behind the kernel). false: the call does not fit, or the launch failed
+// or never published -- the general path then runs it and reports why.
+bool rows_dist_small(fir_gallery* g, const fir_gallery_view& v, const void* gal4, int dp4, const float* queries, int qb, const int32_t* rows, int m,
+                     int start, int end, float* out) {
+    const size_t qbytes = (size_t)qb * v.d * 4, rows_at = (qbytes + 15) & ~(size_t)15, rbytes = (size_t)qb * m * 4;
+    void* base = nullptr;
+    size_t cap = 0;
+    uint64_t* res = nullptr;
+    if ((size_t)qb * m > 8000 || fir_gallery_pin_(g, &base, &cap, &res) != FIR_OK || rows_at + rbytes > cap) return false;
+    const RowsPin pin = {(float*)base, (int32_t*)((char*)base + rows_at), (float*)res, (unsigned long long*)(res + 4095)};
+    std::memcpy(pin.q, queries, qbytes);
+    std::memcpy(pin.rows, rows, rbytes);
+    const unsigned long long ticket = fir_gallery_next_ticket_(g);
+    launch_rows_dist(gal4, dp4, v.n, v.metric, v.d, pin.q, qb, pin.rows, m, start, end, pin.out, v.stream);
+    hipLaunchKernelGGL(k_dem_ticket, dim3(1), dim3(1), 0, v.stream, pin.tword, ticket);
+    if (hipGetLastError() == hipSuccess && fir_wait_ticket_(v.stream, (volatile uint64_t*)pin.tword, ticket) == FIR_OK) {
+        std::memcpy(out, pin.out, rbytes);
+        return true;
+    }
+    (void)hipStreamSynchronize(v.stream);
+    return false;
 }
 
 }  // namespace
@@ -873,16 +1007,11 @@ int fir_dem_pivot_table(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, i
     if (!pivots_out) return fir_fail_(FIR_ERR_ARG, "pivots_out is NULL");
     FIR_HIP(hipSetDevice(v.device));
     const int keep = table_out ? n_pivots - 1 : 0;
-    Buf dtable, dq, dpiv, dmo;
-    FIR_HIP(dtable.alloc((size_t)(keep + 1) * v.n * 4));
-    FIR_HIP(dq.alloc((size_t)v.d * 4));
-    FIR_HIP(dpiv.alloc((size_t)n_pivots * 4));
-    FIR_HIP(dmo.alloc((size_t)n_pivots * 4));
-    if ((rc = dem_build(g, v, first_pivot, n_pivots, dtable.as<float>(), keep, dq.as<float>(), 0, dpiv.as<int32_t>(), dmo.as<float>()))) return rc;
-    FIR_HIP(hipMemcpy(pivots_out, dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    if (min_other_out) FIR_HIP(hipMemcpy(min_other_out, dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
+    FirBuf dtable, dq;
+    FIR_HIP(dtable.reserve((size_t)(keep + 1) * v.n * 4));
+    FIR_HIP(dq.reserve((size_t)v.d * 4));
+    if ((rc = dem_build(g, v, first_pivot, n_pivots, dtable.as<float>(), keep, dq.as<float>(), 0, pivots_out, min_other_out, n_built_out))) return rc;
     if (table_out) FIR_HIP(hipMemcpy(table_out, dtable.p, (size_t)n_pivots * v.n * 4, hipMemcpyDeviceToHost));
-    if (n_built_out) *n_built_out = count_built(pivots_out, n_pivots);
     return FIR_OK;
 }
 
@@ -892,69 +1021,21 @@ int fir_dem_create(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_de
     if (rc) return rc;
     if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
-    int32_t metric = 0;
-    if ((rc = fir_gallery_info(g, nullptr, nullptr, &metric, nullptr))) return rc;
     FIR_HIP(hipSetDevice(v.device));
     fir_dem* h = new fir_dem();
     struct Guard { fir_dem* h; ~Guard() { if (h) fir_dem_destroy(h); } } guard{h};
     h->g = g; h->v = v; h->n_pivots = n_pivots;
     const int keep = std::min<int>(n_pivots, kMaxUsed);
-    const int n = (int)v.n;
-    Buf dpiv, dmo;
-    FIR_HIP(h->table.alloc((size_t)(keep + 1) * n * 4));
-    FIR_HIP(h->pivrows.alloc((size_t)(keep + 1) * v.d * 4));
-    FIR_HIP(dpiv.alloc((size_t)n_pivots * 4));
-    FIR_HIP(dmo.alloc((size_t)n_pivots * 4));
-    if ((rc = dem_build(g, v, first_pivot, n_pivots, h->table.as<float>(), keep, h->pivrows.as<float>(), keep, dpiv.as<int32_t>(), dmo.as<float>())))
-        return rc;
+    FIR_HIP(h->table.reserve((size_t)(keep + 1) * v.n * 4));
+    FIR_HIP(h->pivrows.reserve((size_t)(keep + 1) * v.d * 4));
     h->pivots.resize((size_t)n_pivots);
     h->min_other.resize((size_t)n_pivots);
-    FIR_HIP(hipMemcpy(h->pivots.data(), dpiv.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    FIR_HIP(hipMemcpy(h->min_other.data(), dmo.p, (size_t)n_pivots * 4, hipMemcpyDeviceToHost));
-    h->built = count_built(h->pivots.data(), n_pivots);
+    if ((rc = dem_build(g, v, first_pivot, n_pivots, h->table.as<float>(), keep, h->pivrows.as<float>(), keep, h->pivots.data(), h->min_other.data(),
+                        &h->built)))
+        return rc;
     h->used = std::min(h->built, kMaxUsed);
-    if ((rc = fir_gallery_create_dev(h->pivrows.as<float>(), h->used, v.d, nullptr, metric, v.device, v.stream, &h->pivot_rows))) return rc;
-
-    // The reference keeps the candidates in an index array and moves each pivot to its front with two plain writes
-    // (ann.cpp:431-432); the update loop (:437-446) then runs over the POSITIONS behind the front. Replay that on a
-    // sparse copy: which rows does each pivot's loop visit, and how often? Only rows in {0..used-1} + {pivots} can
-    // deviate from "once per pivot".
-    std::unordered_map<int32_t, int32_t> mod;   // position -> value, where it is not the identity
-    auto at = [&](int32_t pos) { auto it = mod.find(pos); return it == mod.end() ? pos : it->second; };
-    std::vector<int32_t> special;
-    for (int i = 0; i < h->used; ++i) special.push_back(i);
-    for (int i = 0; i < h->used; ++i) special.push_back(h->pivots[(size_t)i]);
-    std::sort(special.begin(), special.end());
-    special.erase(std::unique(special.begin(), special.end()), special.end());
-    std::vector<uint8_t> mult(special.size() * kMaxUsed, 0);
-    for (int i = 0; i < h->used; ++i) {
-        const int32_t p = h->pivots[(size_t)i];
-        mod[p] = at(i);
-        mod[i] = p;
-        for (size_t e = 0; e < special.size(); ++e) {
-            const int32_t w = special[e];
-            int cnt = (w > i && mod.find(w) == mod.end()) ? 1 : 0;
-            for (const auto& kv : mod)
-                if (kv.first > i && kv.second == w) ++cnt;
-            mult[e * kMaxUsed + i] = (uint8_t)std::min(cnt, 255);
-        }
-    }
-    for (const auto& kv : mod)
-        if (kv.first != kv.second) h->order_mods.push_back(kv);
-    std::sort(h->order_mods.begin(), h->order_mods.end());
-    h->nexc = (int)special.size();
-    FIR_HIP(h->exc_rows.alloc(special.size() * 4));
-    FIR_HIP(h->exc_mult.alloc(mult.size()));
-    FIR_HIP(hipMemcpy(h->exc_rows.p, special.data(), special.size() * 4, hipMemcpyHostToDevice));
-    FIR_HIP(hipMemcpy(h->exc_mult.p, mult.data(), mult.size(), hipMemcpyHostToDevice));
-    FIR_HIP(h->q.alloc((size_t)kLikBatch * v.d * 4));
-    FIR_HIP(h->pd.alloc((size_t)kLikBatch * kMaxUsed * 4));
-    FIR_HIP(h->lik.alloc((size_t)kLikBatch * n * 4));
-    if (n <= kPinLikRows) {
-        const size_t bytes = (size_t)kLikBatch * ((size_t)v.d + kMaxUsed + (size_t)n) * 4 + 64;
-        FIR_HIP(hipHostMalloc(&h->pin, bytes, hipHostMallocDefault));
-        std::memset(h->pin, 0, bytes);
-    }
+    if ((rc = fir_gallery_create_dev(h->pivrows.as<float>(), h->used, v.d, nullptr, v.metric, v.device, v.stream, &h->pivot_rows))) return rc;
+    if ((rc = dem_create_query_side(h))) return rc;
     guard.h = nullptr;
     *out = h;
     return FIR_OK;
@@ -964,7 +1045,7 @@ int fir_dem_destroy(fir_dem* h) {
     if (!h) return FIR_OK;
     (void)hipSetDevice(h->v.device);
     if (h->pivot_rows) fir_gallery_destroy(h->pivot_rows);
-    if (h->pin) (void)hipHostFree(h->pin);
+    if (h->pin.q) (void)hipHostFree(h->pin.q);
     for (hipEvent_t e : h->probe_ev) (void)hipEventDestroy(e);
     delete h;
     return FIR_OK;
@@ -1000,45 +1081,35 @@ int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* piv
     const fir_gallery_view& v = h->v;
     FIR_HIP(hipSetDevice(v.device));
     const int n = (int)v.n, used = h->used;
-    const int nblocks = std::min(kMaxBlocks, (n + kBlock - 1) / kBlock);
-    float* hq = (float*)h->pin;
-    float* hpd = hq ? hq + (size_t)kLikBatch * v.d : nullptr;
-    float* hlik = hq ? hpd + (size_t)kLikBatch * kMaxUsed : nullptr;
-    unsigned long long* tword = hq ? (unsigned long long*)(((uintptr_t)(hlik + (size_t)kLikBatch * n) + 7) & ~(uintptr_t)7) : nullptr;
+    const fir_dem::Pin& pin = h->pin;
+    float* pd = h->pd.as<float>();
+    const float* dq = pin.q ? pin.q : h->q.as<float>();          // what the kernels read and write: the pinned block, or device scratch
+    float* dlik = pin.q ? pin.lik : h->lik.as<float>();
     for (int q0 = 0; q0 < qb; q0 += kLikBatch) {
         const int nq = std::min(kLikBatch, qb - q0);
-        const float* dq = h->q.as<float>();
-        float* dlik = h->lik.as<float>();
-        if (hq) {
-            std::memcpy(hq, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4);
-            dq = hq;
-            dlik = hlik;
+        const float* q = queries + (size_t)q0 * v.d;
+        float* pd_out = pivot_dist_out ? pivot_dist_out + (size_t)q0 * used : nullptr;
+        float* l_out = lik_out ? lik_out + (size_t)q0 * n : nullptr;
+        int rc;
+        if (pin.q) {
+            std::memcpy(pin.q, q, (size_t)nq * v.d * 4);
         } else {
-            FIR_HIP(hipMemcpyAsync(h->q.p, queries + (size_t)q0 * v.d, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
+            FIR_HIP(hipMemcpyAsync(h->q.p, q, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
         }
-        const int rc = fir_range_distances_dev(h->pivot_rows, dq, nq, 0, v.d, h->pd.as<float>(), v.stream);   // pd[q][used]
-        if (rc) return rc;
-        if (!hq && pivot_dist_out)
-            FIR_HIP(hipMemcpyAsync(pivot_dist_out + (size_t)q0 * used, h->pd.p, (size_t)nq * used * 4, hipMemcpyDeviceToHost, v.stream));
-        if (lik_out) {
-            hipLaunchKernelGGL(k_dem_lik<kLikBatch>, dim3(nblocks), dim3(kBlock), 0, v.stream, h->table.as<float>(), n, used, h->pd.as<float>(), nq, dlik);
-            FIR_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_dem_lik_fix, dim3((h->nexc * nq + 63) / 64), dim3(64), 0, v.stream, h->table.as<float>(), n, used, h->pd.as<float>(),
-                               nq, h->exc_rows.as<int32_t>(), h->exc_mult.as<uint8_t>(), h->nexc, dlik);
-            FIR_HIP(hipGetLastError());
-            if (!hq) FIR_HIP(hipMemcpyAsync(lik_out + (size_t)q0 * n, h->lik.p, (size_t)nq * n * 4, hipMemcpyDeviceToHost, v.stream));
-        }
-        if (!hq) {
+        if ((rc = fir_range_distances_dev(h->pivot_rows, dq, nq, 0, v.d, pd, v.stream))) return rc;   // pd[q][used]
+        if (!pin.q && pd_out) FIR_HIP(hipMemcpyAsync(pd_out, pd, (size_t)nq * used * 4, hipMemcpyDeviceToHost, v.stream));
+        if (l_out && (rc = dem_queue_lik(h, pd, nq, dlik, v.stream))) return rc;
+        if (!pin.q) {
+            if (l_out) FIR_HIP(hipMemcpyAsync(l_out, dlik, (size_t)nq * n * 4, hipMemcpyDeviceToHost, v.stream));
             FIR_HIP(hipStreamSynchronize(v.stream));
             continue;
         }
         const unsigned long long ticket = ++h->ticket;
-        hipLaunchKernelGGL(k_dem_publish, dim3(1), dim3(64), 0, v.stream, h->pd.as<float>(), nq * used, hpd, tword, ticket);
+        hipLaunchKernelGGL(k_dem_publish, dim3(1), dim3(64), 0, v.stream, pd, nq * used, pin.pd, pin.tword, ticket);
         FIR_HIP(hipGetLastError());
-        const int wrc = fir_wait_ticket_(v.stream, (volatile uint64_t*)tword, ticket);
-        if (wrc) return wrc;
-        if (pivot_dist_out) std::memcpy(pivot_dist_out + (size_t)q0 * used, hpd, (size_t)nq * used * 4);
-        if (lik_out) std::memcpy(lik_out + (size_t)q0 * n, hlik, (size_t)nq * n * 4);
+        if ((rc = fir_wait_ticket_(v.stream, (volatile uint64_t*)pin.tword, ticket))) return rc;
+        if (pd_out) std::memcpy(pd_out, pin.pd, (size_t)nq * used * 4);
+        if (l_out) std::memcpy(l_out, pin.lik, (size_t)nq * n * 4);
     }
     return FIR_OK;
 }
@@ -1055,44 +1126,19 @@ int fir_rows_distances(fir_gallery* g, const float* queries, int32_t qb, const i
     const void* gal4 = nullptr;
     int dp4 = 0;
     if (fir_gallery_tiled_(g, &gal4, &dp4) != FIR_OK || !gal4) return fir_fail_(FIR_ERR_STATE, "gallery has no tiled copy");
-    int32_t metric = 0;
-    int rc = fir_gallery_info(g, nullptr, nullptr, &metric, nullptr);
-    if (rc) return rc;
     FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
-#define FIR_ROWS_BY_METRIC(Q, R, O) launch_rows_dist(gal4, dp4, v.n, metric, v.d, Q, qb, R, m, start_pos, end_pos, O, v.stream)
-    const size_t qbytes = ((size_t)qb * v.d * 4 + 15) & ~(size_t)15, rbytes = (size_t)qb * m * 4;
-    // Small calls (the DEM walk: one query, a few hundred candidate rows): everything through the handle's pinned,
-    // device-visible buffer -- no allocation, no copy engine, no stream synchronisation (a ticket written behind the kernel).
-    void* pin_base = nullptr;
-    size_t pin_cap = 0;
-    uint64_t* pin_res = nullptr;
-    if ((size_t)qb * m <= 8000 && fir_gallery_pin_(g, &pin_base, &pin_cap, &pin_res) == FIR_OK && qbytes + rbytes <= pin_cap) {
-        float* hq = (float*)pin_base;
-        int32_t* hr = (int32_t*)((char*)pin_base + qbytes);
-        float* ho = (float*)pin_res;
-        unsigned long long* tword = (unsigned long long*)(pin_res + 4095);
-        std::memcpy(hq, queries, (size_t)qb * v.d * 4);
-        std::memcpy(hr, rows, rbytes);
-        const unsigned long long ticket = fir_gallery_next_ticket_(g);
-        FIR_ROWS_BY_METRIC(hq, hr, ho);
-        hipLaunchKernelGGL(k_dem_ticket, dim3(1), dim3(1), 0, v.stream, tword, ticket);
-        const hipError_t le = hipGetLastError();
-        if (le == hipSuccess && fir_wait_ticket_(v.stream, (volatile uint64_t*)tword, ticket) == FIR_OK) {
-            std::memcpy(out, ho, rbytes);
-            return FIR_OK;
-        }
-        (void)hipStreamSynchronize(v.stream);   // the launch failed or never published: the general path below reports why
-    }
+    if (rows_dist_small(g, v, gal4, dp4, queries, qb, rows, m, start_pos, end_pos, out)) return FIR_OK;
+    const size_t qbytes = (size_t)qb * v.d * 4, rbytes = (size_t)qb * m * 4;
     void *dq = nullptr, *drows = nullptr, *dout = nullptr;
-    if ((rc = fir_gallery_scratch_(g, 8, (size_t)qb * v.d * 4, &dq))) return rc;
+    int rc;
+    if ((rc = fir_gallery_scratch_(g, 8, qbytes, &dq))) return rc;
     if ((rc = fir_gallery_scratch_(g, 9, rbytes, &drows))) return rc;
     if ((rc = fir_gallery_scratch_(g, 10, rbytes, &dout))) return rc;
-    FIR_HIP(hipMemcpyAsync(dq, queries, (size_t)qb * v.d * 4, hipMemcpyHostToDevice, v.stream));
+    FIR_HIP(hipMemcpyAsync(dq, queries, qbytes, hipMemcpyHostToDevice, v.stream));
     FIR_HIP(hipMemcpyAsync(drows, rows, rbytes, hipMemcpyHostToDevice, v.stream));
-    FIR_ROWS_BY_METRIC((const float*)dq, (const int32_t*)drows, (float*)dout);
-#undef FIR_ROWS_BY_METRIC
+    launch_rows_dist(gal4, dp4, v.n, v.metric, v.d, (const float*)dq, qb, (const int32_t*)drows, m, start_pos, end_pos, (float*)dout, v.stream);
     FIR_HIP(hipGetLastError());
     FIR_HIP(hipMemcpyAsync(out, dout, rbytes, hipMemcpyDeviceToHost, v.stream));
     FIR_HIP(hipStreamSynchronize(v.stream));
@@ -1129,49 +1175,12 @@ int fir_dem_probe_times_(fir_dem* h, float* ms) {
 
 int fir_dem_recognize_dev(fir_dem* h, const float* d_queries, int32_t qb, float threshold, int32_t image_count_to_check, int32_t* d_row,
                           float* d_dist, int32_t* d_found, int32_t* d_calc, int32_t* d_tie, void* stream) {
-    int rc = dem_recognize_check(h, d_queries, qb, d_row, d_dist, d_found, d_calc, d_tie);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(h->v.device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->v.stream;
-    FirCallOrder order(h->g, st);
-    if (order.rc) return order.rc;
-    if ((rc = dem_recognize_prepare(h))) return rc;
-    return dem_recognize_queue(h, d_queries, qb, threshold, image_count_to_check, d_row, d_dist, d_found, d_calc, d_tie, st);
+    return dem_recognize_call(h, d_queries, qb, threshold, image_count_to_check, RecOut{d_row, d_dist, d_found, d_calc, d_tie}, false, stream);
 }
 
 int fir_dem_recognize(fir_dem* h, const float* queries, int32_t qb, float threshold, int32_t image_count_to_check, int32_t* row, float* dist,
                       int32_t* found, int32_t* calc, int32_t* tie) {
-    int rc = dem_recognize_check(h, queries, qb, row, dist, found, calc, tie);
-    if (rc) return rc;
-    const fir_gallery_view& v = h->v;
-    FIR_HIP(hipSetDevice(v.device));
-    FirCallOrder order(h->g, v.stream);
-    if (order.rc) return order.rc;
-    if ((rc = dem_recognize_prepare(h))) return rc;
-    const size_t qbytes = (size_t)qb * v.d * 4, obytes = (size_t)qb * 4;
-    if (qbytes > h->r_q_cap) {                                            // (no call is using them: this form waits for its kernels)
-        h->r_q.release();
-        h->r_q_cap = 0;
-        FIR_HIP(h->r_q.alloc(qbytes));
-        h->r_q_cap = qbytes;
-    }
-    if (5 * obytes > h->r_out_cap) {
-        h->r_out.release();
-        h->r_out_cap = 0;
-        FIR_HIP(h->r_out.alloc(5 * obytes));
-        h->r_out_cap = 5 * obytes;
-    }
-    int32_t* o = h->r_out.as<int32_t>();
-    FIR_HIP(hipMemcpyAsync(h->r_q.p, queries, qbytes, hipMemcpyHostToDevice, v.stream));
-    if ((rc = dem_recognize_queue(h, h->r_q.as<float>(), qb, threshold, image_count_to_check, o, (float*)(o + qb), o + 2 * (size_t)qb, o + 3 * (size_t)qb,
-                                  o + 4 * (size_t)qb, v.stream)))
-        return rc;
-    void* outs[5] = {row, dist, found, calc, tie};
-    for (int k = 0; k < 5; ++k)
-        if (outs[k]) FIR_HIP(hipMemcpyAsync(outs[k], o + (size_t)k * qb, obytes, hipMemcpyDeviceToHost, v.stream));
-    FIR_HIP(hipStreamSynchronize(v.stream));
-    order.done();
-    return FIR_OK;
+    return dem_recognize_call(h, queries, qb, threshold, image_count_to_check, RecOut{row, dist, found, calc, tie}, true, nullptr);
 }
 
 }  // extern "C"

@@ -239,13 +239,6 @@ __global__ void __launch_bounds__(kBlock) k_fpnn_untranspose(const double* __res
     a[o] = at[((int64_t)f * K + k) * C + c];
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
-    template <typename T> T* as() { return (T*)p; }
-};
-
 }  // namespace
 
 struct fir_fpnn {
@@ -253,7 +246,7 @@ struct fir_fpnn {
     int d = 0, C = 0, J = 0;
     double scale = 1.0;
     hipStream_t stream = nullptr;
-    Buf at, avg, sd, terms;
+    FirBuf at, avg, sd, terms;
     void* pin = nullptr;        // pinned staging: queries in, outputs / classes / chunk counts out, then the ticket word
     unsigned long long ticket = 0;    // one-query calls so far
 };
@@ -338,15 +331,15 @@ int fir_fpnn_train(const double* train_rows, int64_t nt, int32_t d, const int32_
     h->device = device; h->d = d; h->C = num_classes; h->J = J; h->scale = scale;
     const int K = 2 * J + 1;
     FIR_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    FIR_HIP(h->at.alloc((size_t)d * K * num_classes * 8));
-    FIR_HIP(h->avg.alloc((size_t)d * 8));
-    FIR_HIP(h->sd.alloc((size_t)d * 8));
-    FIR_HIP(h->terms.alloc((size_t)kPredBatch * d * num_classes * 4));
+    FIR_HIP(h->at.reserve((size_t)d * K * num_classes * 8));
+    FIR_HIP(h->avg.reserve((size_t)d * 8));
+    FIR_HIP(h->sd.reserve((size_t)d * 8));
+    FIR_HIP(h->terms.reserve((size_t)kPredBatch * d * num_classes * 4));
     FIR_HIP(hipHostMalloc(&h->pin, (size_t)kPredBatch * ((size_t)d * 8 + (size_t)num_classes * 4 + 8) + 128, hipHostMallocDefault));
     std::memset((char*)h->pin + (size_t)kPredBatch * ((size_t)d * 8 + (size_t)num_classes * 4 + 8), 0, 128);
-    Buf drows, doff;
-    FIR_HIP(drows.alloc((size_t)nt * d * 8));
-    FIR_HIP(doff.alloc(off.size() * 4));
+    FirBuf drows, doff;
+    FIR_HIP(drows.reserve((size_t)nt * d * 8));
+    FIR_HIP(doff.reserve(off.size() * 4));
     FIR_HIP(hipMemcpyAsync(drows.p, train_rows, (size_t)nt * d * 8, hipMemcpyHostToDevice, h->stream));
     FIR_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
     FIR_HIP(hipMemcpyAsync(h->avg.p, avg, (size_t)d * 8, hipMemcpyHostToDevice, h->stream));
@@ -383,8 +376,8 @@ int fir_fpnn_get_model(fir_fpnn* h, double* a_out) {
     FIR_HIP(hipSetDevice(h->device));
     const int K = 2 * h->J + 1;
     const int64_t total = (int64_t)h->d * h->C * K;
-    Buf da;
-    FIR_HIP(da.alloc((size_t)total * 8));
+    FirBuf da;
+    FIR_HIP(da.reserve((size_t)total * 8));
     hipLaunchKernelGGL(k_fpnn_untranspose, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->at.as<double>(), h->d, h->C,
                        K, da.as<double>());
     FIR_HIP(hipGetLastError());

@@ -60,6 +60,25 @@ struct FirOnExit {
 };
 template <typename F>
 FirOnExit<F> fir_on_exit(F f) { return FirOnExit<F>{f}; }
+// Device memory owned by a handle or a scope: pointer + capacity, freed on destruction. reserve() is a no-op when the bytes
+// fit; otherwise it frees and allocates afresh (nothing is carried over, and nobody may still be using the old block).
+struct FirBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    FirBuf() = default;
+    FirBuf(const FirBuf&) = delete;
+    FirBuf& operator=(const FirBuf&) = delete;
+    ~FirBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t bytes) {
+        if (p && bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&p, bytes < 16 ? 16 : bytes);
+        if (e == hipSuccess) cap = bytes < 16 ? 16 : bytes; else p = nullptr;
+        return e;
+    }
+    template <typename T> T* as() const { return (T*)p; }
+};
 extern "C" void fir_set_last_error_(const char* msg);    // a message kept aside earlier (fir_shard.hip: another rank's or worker's error)
 // Every environment knob the library honours goes through here: getenv(name), and a set one is remembered (once) in the list
 // fir_gallery_last_dispatch reports in fir_dispatch_info::knobs -- a stray variable in a production environment is visible.

@@ -104,6 +104,39 @@ def test_matches_oracle_on_fresh_data(fir, oracle, seed, n, d, ncls, npiv, metri
         dem.close()
 
 
+@pytest.mark.parametrize("mixed_thr", [False, True])
+def test_one_handle_whose_calls_grow_and_shrink(fir, oracle, mixed_thr):
+    """One handle, calls of changing size: the host-pointer form's query / result buffers and the candidate scratch grow,
+    the candidate distances go from gather (Mc < n // GATHER_DIV) to dense and back, fir_dem_likelihoods runs in between,
+    and the last call has no candidates. Every answer is the oracle's walk and, bit for bit, a fresh handle's."""
+    n, npiv = 300, 5
+    rows, cls, q, first, piv, table, mixed = fresh_case(oracle, 35, n, 64, 10, npiv, gc.L2)
+    thr = mixed if mixed_thr else 0.0
+    used = len(piv)
+    assert used == npiv and 30 < n // GATHER_DIV                # 3 and 30 candidates are gathered, n - used are not
+
+    def fresh(call):
+        d = fir.Dem(g, first, npiv)
+        try:
+            return call(d)
+        finally:
+            d.close()
+
+    with fir.Gallery(rows, cls, gc.L2, 0) as g:
+        dem = fir.Dem(g, first, npiv)
+        try:
+            for step, (qb, m) in enumerate([(1, used + 3), (11, used + 30), (3, n), (11, used + 3), (2, used)]):
+                if step == 2:
+                    got, want = dem.likelihoods(q), fresh(lambda d: d.likelihoods(q))
+                    assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(got, want))
+                got = dem.recognize(q[:qb], thr, m)
+                assert as_tuples(*got[:4]) == oracle_tuples(oracle, rows, piv, table, thr, m, q[:qb], gc.L2), (qb, m)
+                want = fresh(lambda d: d.recognize(q[:qb], thr, m))
+                assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(got, want)), (qb, m)
+        finally:
+            dem.close()
+
+
 def test_index_quirk_and_its_equal_likelihoods(fir, oracle):
     """ann.cpp:431-432 leaves a row twice in the index array (tests/test_gpu_dem.py builds the same case): the two positions
     have one likelihood and one distance. The answers are the position-order walk's, the flag the restatement's."""
