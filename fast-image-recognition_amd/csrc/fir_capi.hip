@@ -248,13 +248,20 @@ int top1_qpp(const fir_gallery* g, int qb, int cap) {
 // scan's 16-queries-per-pass form is within reach of it for small batches: a cost model of the two forms decides there.
 constexpr int kAutoMfmaQueries = 128;
 constexpr int64_t kAutoMfmaRows = 65536;
-bool wants_mfma(const fir_gallery* g, int32_t qb, int32_t start, int32_t end) {
+// The K nearest distinct classes (fir_gemm_search_top_classes_keys_dev) from kAutoMfmaQueries queries over kAutoMfmaRows rows on:
+// 1M x 512, 100 000 classes, K = 5, 128 .. 32 768 queries per call: 4.1-6.5 x the scan form's rate on class-major labels, 3.9-5.2 x
+// on permuted ones, every case far beyond the 15 % the cost model above asks for (profiles/class_rank_matrix_cores.txt). Smaller
+// galleries were not measured: they stay with the scan unless the caller sets a threshold.
+constexpr bool kAutoMfmaClasses = true;
+// classes (fir_search_top_classes): the same ranges and the same caller's threshold; the automatic rule is kAutoMfmaClasses
+bool wants_mfma(const fir_gallery* g, int32_t qb, int32_t start, int32_t end, bool classes = false) {
     // the whole row, or a prefix of whole 16-feature k-blocks (>= 64 features: below that the scan's prefix pass is cheap)
     if (g->metric != FIR_METRIC_L2 || start != 0 || g->n <= 0 || g->tiles_limit > 0) return false;
     if (end != g->d && (end < 64 || end % 16 != 0)) return false;
     if (g->large_batch_min == 0 || g->gemm_failed) return false;
     if (g->large_batch_min > 0) return qb >= g->large_batch_min;
     if (g->qpp != 0) return false;                                              // a pinned queries-per-pass asks for the scan
+    if (classes) return kAutoMfmaClasses && qb >= kAutoMfmaQueries && g->n >= kAutoMfmaRows;
     if (g->n < kAutoMfmaRows) {
         // Cache-resident galleries: the scan folds its 16-query passes into one launch, ~40 us + (2 us + 0.25 us per MB) per pass;
         // the matrix-core call ~125 us (225 us with rows longer than 512 features: streamed query slabs) + 0.06 (0.12) us per MB and
@@ -797,8 +804,9 @@ constexpr int32_t kClassMax = 1 << 24;      // 1 GiB of table per tile of 8 quer
 // stays 100000 and nothing is filtered.
 constexpr int64_t kClassSampleFromTiles = 128;
 
+// bound_tiles > 0 (fir_class_scan_dev_): only the scan over the leading bound_tiles tiles runs, and d_bound[q] gets its bound.
 int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k,
-                    uint64_t* d_keys, int32_t* d_classes, hipStream_t st) {
+                    uint64_t* d_keys, int32_t* d_classes, hipStream_t st, int64_t bound_tiles = 0, float* d_bound = nullptr) {
     if (g->n == 0) {                                             // no row: every slot unused (kKeyNone, class -1)
         if (d_keys) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
         if (d_classes) FIR_HIP(hipMemsetAsync(d_classes, 0xFF, (size_t)qb * k * sizeof(int32_t), st));
@@ -814,7 +822,7 @@ int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t 
     if ((rc = grow(g->qt, g->qt_cap, (size_t)tiles_q * 8 * g->dp4 * 4 + 64))) return rc;
     uint64_t* table = (uint64_t*)p_table;
     float* tau = (float*)p_tau;
-    const int64_t sample_tiles = g->tiles >= kClassSampleFromTiles ? g->tiles / 8 : 0;
+    const int64_t sample_tiles = bound_tiles > 0 ? std::min(bound_tiles, g->tiles) : g->tiles >= kClassSampleFromTiles ? g->tiles / 8 : 0;
     auto restore = fir_on_exit([&] { g->tiles_limit = 0; g->tile_begin = 0; });
     for (int q0 = 0; q0 < qb; q0 += 8 * per_launch) {
         const int nq = std::min(qb - q0, 8 * per_launch), ny = (nq + 7) / 8;
@@ -825,7 +833,9 @@ int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t 
             g->tile_begin = 0;
             g->tiles_limit = sample_tiles;
             if ((rc = run_pass(g, st, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
-            hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, (uint64_t*)nullptr, (int32_t*)nullptr, tau);
+            hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, (uint64_t*)nullptr, (int32_t*)nullptr,
+                               bound_tiles > 0 ? d_bound + q0 : tau);
+            if (bound_tiles > 0) { FIR_HIP(hipGetLastError()); continue; }
             cp.tau = tau;
             cp.tiles_ready = true;
             g->tile_begin = sample_tiles;
@@ -1398,6 +1408,20 @@ int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
     }
     return rcs;
 }
+// ... and for the K nearest distinct classes of a host-pointer batch (fir_search_top_classes): the gallery needs its labels
+int try_mfma_classes(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k, uint64_t* d_keys,
+                     int32_t* d_classes, hipStream_t st) {
+    if (!g->cls || !wants_mfma(g, qb, start, end, true)) return 1;
+    fir_gemm* m = nullptr;
+    const int rc = ensure_gemm(g, end, &m);
+    if (rc) return rc;
+    const int rcs = fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, num_classes, k, d_keys, d_classes, st);
+    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    return rcs;
+}
 }  // namespace
 
 int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream) {
@@ -1782,6 +1806,27 @@ int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int3
     return top_classes_dev(g, d_queries, qb, start_pos, end_pos, num_classes, k, d_keys, d_classes, st);
 }
 
+// The class-minimum scan on behalf of fir_gemm_search_top_classes_keys_dev, neither recorded nor timed (fir_internal.h).
+int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k, int64_t sample_rows,
+                        uint64_t* d_keys, int32_t* d_classes, float* d_bound, void* stream) {
+    int32_t start_pos = 0;
+    int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
+    if (rc) return rc;
+    if (sample_rows > 0 ? !d_bound : (!d_keys && !d_classes)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    FirCallOrder order(g, st);
+    if (order.rc) return order.rc;
+    const bool was_profiling = g->profiling, was_quiet = g->quiet;
+    g->profiling = false;
+    g->quiet = true;
+    rc = top_classes_dev(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, st, (sample_rows + kTileRows - 1) / kTileRows, d_bound);
+    g->quiet = was_quiet;
+    g->profiling = was_profiling;
+    return rc;
+}
+
 int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes, int32_t k,
                            int32_t* class_out, int32_t* idx, float* dist) {
     int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k);
@@ -1797,7 +1842,9 @@ int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int
     if ((rc = grow(g->dkeys, g->dkeys_cap, slots))) return rc;
     if ((rc = grow(g->didx, g->didx_cap, slots))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    if ((rc = top_classes_dev(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream))) return rc;
+    rc = try_mfma_classes(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
+    if (rc > 0) rc = top_classes_dev(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
+    if (rc) return rc;
     std::vector<uint64_t> keys(slots);
     FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
     if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->didx, slots * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));

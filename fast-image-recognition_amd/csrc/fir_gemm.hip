@@ -48,6 +48,7 @@ constexpr int kCand = 8;               // tau = the kCand-th smallest SAMPLED pr
 constexpr int kRerankGroup = 8;         // candidate rows staged in LDS at a time by the re-rank (fewer when rows are longer than ~4000 features)
 constexpr size_t kRerankLdsMax = 144 * 1024;
 constexpr int kListCap = 4096;         // appended (proxy, row) entries per query before "overflow"
+constexpr int kClassSampleRows = 16384; // distinct classes: the bound comes from max(this, n K / 64) leading rows (exact class minima)
 constexpr int kMinSampleRows = 8192;   // rows whose proxies seed tau: max(8192, n / 64) -> ~512 appended rows per query
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1041,6 +1042,189 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_topk(const unsigned long lon
     }
 }
 
+// ---- the K nearest distinct classes (fir_gemm_search_top_classes_keys_dev) ----
+// tau[q] holds D_s on entry: the exact K-th smallest class minimum of a row sample (fir_class_scan_dev_), an upper bound of the
+// gallery's K-th class distance D_K. On exit it is that bound in proxy units plus one rounding window, as k_gemm_tau_min hangs
+// it on a sampled proxy: a row whose reference distance is <= D_s has a true |g|^2 - 2 q.g within E d of D_s d - |q|^2 and a
+// proxy within E d of that, so it lies below tau and is appended. D_s = 100000 (fewer than K classes in the sample): no bound,
+// +inf appends everything and the list cap decides. A NaN norm gives a NaN tau: nothing is appended, nothing certified.
+__global__ void __launch_bounds__(256) k_gemm_tau_class(float* __restrict__ tau, int nq_total, int nq_valid, int d, const float* __restrict__ qnorm,
+                                                         const float* __restrict__ gnorm_max_p, float e_rel) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq_total) return;
+    if (q >= nq_valid) { tau[q] = -__builtin_huge_valf(); return; }       // padding queries of a half-filled pair: nothing is appended
+    const float ds = tau[q];
+    float t = __builtin_huge_valf();
+    if (ds < fir::kNotFound) {
+        const float v = (ds * (float)d - qnorm[q]) + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);
+        t = v + fabsf(v) * 1e-6f + 1e-30f;
+    }
+    tau[q] = t;
+}
+
+// The K nearest distinct classes (K <= 32) from the lists of one append pass below k_gemm_tau_class's bound. One wave per query.
+//   1. p_K = the K-th smallest proxy over DISTINCT classes of the list (rows labelled outside [0, num_classes) take no part):
+//      K rounds of "smallest key of a class not yet taken"; fewer than K classes: the whole list is re-ranked.
+//   2. every entry with a proxy <= p_K + 2 E d is re-ranked in the reference's arithmetic (as k_gemm_rerank_topk) and its exact
+//      key written back over its list entry; entries outside the window, and rows that do not qualify (label, dist >= 100000),
+//      become kKeyNone.
+//   3. K rounds over the exact keys pick the classes: the smallest key of a class is its first minimum in row order, and the
+//      rounds return the classes ascending by (distance, row).
+// Certificate, against the K-th exact class distance D (100000 with fewer than K classes found): the list did not overflow and
+// (|q|^2 + p_excl)/d - E > D, p_excl = min(smallest proxy not re-ranked, tau). Every row that was not appended or not re-ranked
+// then has a reference distance above D. Each of the K classes found has a re-ranked row at or below D, so such a row can
+// neither bring a new class in among the K nor be the best row of one that is among them (that row, at or below D, was
+// re-ranked): keys and classes are the exact scan's. Strict '>': a NaN never certifies, a tie with the K-th does not either.
+__global__ void __launch_bounds__(64) k_gemm_rerank_classes(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
+                                                             const float4* __restrict__ gal4, const float* __restrict__ queries,
+                                                             const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p,
+                                                             const int32_t* __restrict__ cls, int num_classes, int64_t n, int d, int dp4,
+                                                             int64_t row_offset, float e_rel, int ngroup, int k, unsigned long long* __restrict__ out_key,
+                                                             int32_t* __restrict__ out_cls, int* __restrict__ ok, int qstride,
+                                                             const float4* __restrict__ rowmajor) {
+    __shared__ int32_t taken[32];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int cnt = counts[q];
+    if (cnt > kListCap) {                           // rows below tau were dropped: the exact form answers this query
+        if (lane == 0) ok[q] = 0;
+        return;
+    }
+    const int have = cnt;
+    unsigned long long* L = lists + (size_t)q * kListCap;
+    // round r of "the smallest key of a class not yet taken" (keys carry rows roff + local row): every key at or below the previous
+    // pick belongs to a taken class; a label is only looked up for a key that would improve the lane's candidate
+    auto pick = [&](int r, unsigned long long prev, int64_t roff, int32_t& c_out) -> unsigned long long {
+        unsigned long long cand = kKeyNone;
+        int32_t cc = -1;
+        for (int i = lane; i < have; i += 64) {
+            const unsigned long long v = L[i];
+            if (v >= cand || (r > 0 && v <= prev)) continue;
+            const int32_t c = cls[(int64_t)(uint32_t)(v & 0xFFFFFFFFull) - roff];
+            bool skip = (uint32_t)c >= (uint32_t)num_classes;
+            for (int j = 0; j < r; ++j) skip = skip || taken[j] == c;
+            if (!skip) { cand = v; cc = c; }
+        }
+        const unsigned long long m = fir::wave_min_u64(cand);
+        const unsigned long long who = __ballot(m != kKeyNone && cand == m);      // keys are unique (the row is part of the key)
+        c_out = who ? __shfl(cc, __ffsll((long long)who) - 1, 64) : -1;
+        return m;
+    };
+    unsigned long long prev = 0;
+    int found = 0;
+    for (int r = 0; r < k; ++r) {
+        int32_t c;
+        const unsigned long long m = pick(r, prev, 0, c);
+        if (m == kKeyNone) break;
+        if (lane == 0) taken[r] = c;
+        __syncthreads();
+        prev = m;
+        ++found;
+    }
+    const float qn = qnorm[q], gmax = gnorm_max_p[0];
+    const float E = e_rel * (qn + gmax) / (float)d;                   // see k_gemm_rerank
+    const float pk = found == k ? fir::f32_from_orderable((uint32_t)(prev >> 32)) : __builtin_huge_valf();   // a list short of classes is re-ranked whole
+    float win = pk + 2.0f * E * (float)d;
+    win += fabsf(win) * 1e-6f;
+    const float* qv = queries + (size_t)q * qstride;
+    const int d4 = (d + 3) >> 2;                                  // float4 chunks of the compared features (a prefix of the row when d < its length)
+    float p_out = __builtin_huge_valf();            // smallest proxy NOT re-ranked
+    int reranked = 0;
+    extern __shared__ __attribute__((aligned(16))) float4 crow[];     // [ngroup][dp4] candidate rows, then [dp4] the query
+    const int cs = dp4 | 1;                                       // candidate-row stride in LDS, odd: the lanes' rows start in different banks
+    float4* qrow = crow + (size_t)ngroup * cs;
+    for (int c = lane; c < dp4 * 4; c += 64) ((float*)qrow)[c] = c < d ? qv[c] : 0.0f;
+    __syncthreads();
+    for (int base = 0; base < have; base += 64) {
+        const int i = base + lane;
+        const unsigned long long v = i < have ? L[i] : kKeyNone;
+        const float p = fir::f32_from_orderable((uint32_t)(v >> 32));
+        const bool in = i < have && p <= win;
+        if (i < have && !in) {
+            p_out = fminf(p_out, p);
+            L[i] = kKeyNone;
+        }
+        unsigned long long mask = __ballot(in);
+        reranked += __popcll(mask);
+        while (mask) {                                                  // wave-uniform
+            unsigned long long mine = kKeyNone;
+            int mine_i = 0, ng = 0;
+            for (int g = 0; g < ngroup; ++g) {
+                if (mask) {
+                    const int src = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const unsigned long long cv = __shfl((unsigned long long)v, src, 64);
+                    const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
+                    if (rowmajor) {                                     // the row-major shadow copy: one contiguous row, coalesced
+                        const float4* gr = rowmajor + (size_t)row * d4;
+                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[c];
+                    } else {                                            // the tiled gallery: 16 bytes per KiB
+                        const float4* gr = gal4 + (size_t)(row >> 6) * dp4 * 64 + (row & 63);
+                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[(size_t)c * 64];
+                    }
+                    if (lane == g) { mine = cv; mine_i = base + src; }
+                    ++ng;
+                }
+            }
+            __syncthreads();
+            if (lane < ng) {
+                const float4* my = crow + (size_t)lane * cs;
+                float acc = 0.0f;
+                for (int c = 0; c < d4; ++c) {
+                    const float4 g4 = my[c], q4 = qrow[c];
+                    acc = fir::accum<fir::kL2>(acc, q4.x, g4.x);
+                    acc = fir::accum<fir::kL2>(acc, q4.y, g4.y);
+                    acc = fir::accum<fir::kL2>(acc, q4.z, g4.z);
+                    acc = fir::accum<fir::kL2>(acc, q4.w, g4.w);
+                }
+                const float dist = acc / (float)d;
+                const int64_t row = (int64_t)(uint32_t)(mine & 0xFFFFFFFFull);
+                const bool counted = (uint32_t)cls[row] < (uint32_t)num_classes && dist < fir::kNotFound;
+                L[mine_i] = counted ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
+            }
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) p_out = fminf(p_out, __shfl_xor(p_out, off, 64));
+    __threadfence_block();                                              // the exact keys, written by other lanes, are read below
+    __syncthreads();
+    unsigned long long kth_exact = kKeyNone;
+    prev = 0;
+    int r = 0;
+    for (; r < k; ++r) {
+        int32_t c;
+        const unsigned long long m = pick(r, prev, row_offset, c);
+        if (m == kKeyNone) break;
+        if (lane == 0) {
+            taken[r] = c;
+            if (out_key) out_key[(size_t)q * k + r] = m;
+            if (out_cls) out_cls[(size_t)q * k + r] = c;
+        }
+        __syncthreads();
+        prev = m;
+        if (r == k - 1) kth_exact = m;
+    }
+    for (int i = r + lane; i < k; i += 64) {                            // unused slots
+        if (out_key) out_key[(size_t)q * k + i] = kKeyNone;
+        if (out_cls) out_cls[(size_t)q * k + i] = -1;
+    }
+    if (lane == 0) {
+        const float t = tau[q];
+        const float p_excl = t != t ? t : fminf(p_out, t);          // a NaN bound must not certify anything
+        const float lower = (qn + p_excl) / (float)d - E;
+        // fewer than K classes found: any qualifying row outside the re-ranked set could bring one in
+        const float bd = kth_exact != kKeyNone ? fir::f32_from_orderable((uint32_t)(kth_exact >> 32)) : fir::kNotFound;
+        ok[q] = (lower > bd || n <= reranked) ? 1 : 0;              // (false for NaN; every row was re-ranked)
+    }
+}
+
+// the running totals fir_gemm_stats_ex reads (fir_gemm_fb.h), for a call whose uncertified queries the host sent to the exact form
+__global__ void k_gemm_fb_count(int* __restrict__ state, int count) {
+    unsigned long long* tot = (unsigned long long*)(state + 4);
+    tot[0] += (unsigned long long)count;
+    tot[1] += (unsigned long long)count;
+}
+
 // rowmajor[row * d4 + c] = chunk c of row `row`: the re-rank's copy of the compared features. A row of the tiled gallery is d4
 // separate 16-byte pieces 1 KiB apart (~4x its size in 64-byte sectors per gather); here it is one contiguous run.
 __global__ void __launch_bounds__(256) k_gemm_untile(const float4* __restrict__ gal4, int64_t n, int dp4, int d4, float4* __restrict__ rowmajor) {
@@ -1171,6 +1355,7 @@ struct fir_gemm {
     const double2* gal2 = nullptr; int dp2 = 0;
     int adaptive = 1;                     // fp16 top-1: the append threshold is found during the full pass (k_gemm_proxy_f16x<3, *>), no sample pass
                                           // (profiles/r03_adaptive_threshold.txt); FIR_GEMM_ADAPTIVE=0: the sample flow, 2: the pass on the way whatever the shape
+    int class_sample_div = 64;            // distinct classes: the bound's row sample is max(kClassSampleRows, n K / this) rows (FIR_GEMM_CLASS_SAMPLE_DIV: experiments; any size is sound)
     int adaptive_topk = 1;                // ... and for the K nearest rows (k_gemm_proxy_f16x<4, *>: K slot minima per query); FIR_GEMM_ADAPTIVE_TOPK=0: the sample flow
     float* awin[2] = {nullptr, nullptr};  // ... its per-query windows
     unsigned int* aT[2] = {nullptr, nullptr};   // ... and the ranks' shared T (float bits)
@@ -1182,6 +1367,7 @@ struct fir_gemm {
     int adapt_dbg = 0;                    // nt_flags bits 2, 3 of the adaptive pass (FIR_GEMM_ADAPT_DBG): 1 = no refresh, 2 = no exchange of the bound between workgroups (still
                                           // sound: a looser bound appends more -- this is how the tests drive lists into overflow and the second-chance pass on benign data)
     bool debug_counts = false;            // appended rows per query of a call's last super-batch on stderr (FIR_GEMM_DEBUG_COUNTS; synchronises)
+    hipEvent_t phase_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... and its phases: before / after its preparation, after its full passes, after its re-rank
     std::string dump_phases;              // with FIR_GEMM_DBG_SKIP=256: the file the load-burst timestamps of the last super-batch's first pair go to (FIR_GEMM_DUMP_PHASES)
 };
 
@@ -1189,6 +1375,7 @@ struct fir_gemm {
 static void gemm_read_knobs_(fir_gemm* m) {
     if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE")) m->adaptive = std::atoi(w);
     if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE_TOPK")) m->adaptive_topk = std::atoi(w) != 0;
+    if (const char* w = fir_knob_("FIR_GEMM_CLASS_SAMPLE_DIV")) m->class_sample_div = std::max(1, std::atoi(w));
 #ifdef FIR_AUDIT      // knobs that change answers: the audit build only (libfir_amd_audit.so; fir_internal.h)
     if (const char* w = fir_knob_("FIR_GEMM_DBG_SKIP")) m->dbg_skip = std::atoi(w) & 1023;
     if (const char* w = fir_knob_("FIR_GEMM_DBG_BLOCK")) m->dbg_block = std::atoi(w) == 256 ? 256 : kGemmBlock;     // timing experiments only: the answers are wrong
@@ -1390,6 +1577,8 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
             e = hipFuncSetAttribute((const void*)k_gemm_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
         if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
             e = hipFuncSetAttribute((const void*)k_gemm_rerank_topk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
+        if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
+            e = hipFuncSetAttribute((const void*)k_gemm_rerank_classes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
     if (e == hipSuccess && precision == FIR_GEMM_F16) e = gemm_x_lds_attr_();
     gemm_read_knobs_(m);
@@ -1469,6 +1658,7 @@ int fir_gemm_destroy(fir_gemm* m) {
         if (m->prep_done[b]) (void)hipEventDestroy(m->prep_done[b]);
     }
     if (m->queries_ready) (void)hipEventDestroy(m->queries_ready);
+    for (hipEvent_t ev : m->phase_ev) if (ev) (void)hipEventDestroy(ev);
     (void)hipFree(m->gm); (void)hipFree(m->gb); (void)hipFree(m->gh); (void)hipFree(m->rowmajor); (void)hipFree(m->proxies); (void)hipFree(m->gnorm); (void)hipFree(m->gmax); (void)hipFree(m->sample); (void)hipFree(m->ok);
     (void)hipFree(m->fb_state); (void)hipFree(m->fb_list); (void)hipFree(m->fb_list2); (void)hipFree(m->fb_tau2);
     (void)hipFree(m->sc_qnorm); (void)hipFree(m->sc_qmul); (void)hipFree(m->sc_qinv); (void)hipFree(m->sc_tau); (void)hipFree(m->sc_counts);
@@ -1568,6 +1758,8 @@ struct GemmCall {
     int32_t qb;
     int k;                      // the K nearest rows of every query: d_keys[q * k + r], ascending
     uint64_t* d_keys;
+    int32_t num_classes;        // > 0: the K nearest distinct CLASSES (fir_gemm_search_top_classes_keys_dev) -- a bound from a row sample's class
+    int32_t* d_classes;         // minima, the append pass below it, k_gemm_rerank_classes; d_keys or d_classes may then be NULL
     hipStream_t st;
     int d, qs;                  // features compared; floats between consecutive queries (and gallery rows): the whole row
     int64_t n;
@@ -1599,6 +1791,7 @@ struct GemmCall {
 // pairs per launch on and on cache-sized galleries, and loses 3-35 % with one or two pairs over 100 000+ rows: those keep the sample flow.
 static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
     if (m->precision != FIR_GEMM_F16 || m->adaptive <= 0 || (c.k > 1 && !m->adaptive_topk)) return false;
+    if (c.num_classes > 0) return false;                                // (a bound on the K-th CLASS is not a row order statistic: the sample flow)
     if (m->adaptive > 1 || c.k == 1) return true;                       // FIR_GEMM_ADAPTIVE=2: always
     const int pairs_sb = ((nq_sb + kQT - 1) / kQT + 1) / 2;
     const int P = launch_pairs_(pairs_sb, c.streamed ? kShareStreamed : kShareMax);
@@ -1667,6 +1860,15 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
     hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk16, m->qmul[b],
                        m->qbf[b], c.qs);
     if (adaptive) return FIR_OK;
+    if (c.num_classes > 0) {
+        // distinct classes: D_s = the exact K-th smallest class minimum over the leading sample rows (four times list_row_samples' sizing:
+        // profiles/class_rank_matrix_cores.txt), turned into the append pass's bound in place; padding queries get -inf
+        const int64_t rows = std::min<int64_t>(c.n, std::max<int64_t>(kClassSampleRows, c.n * k / m->class_sample_div));
+        const int rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.num_classes, k, rows, nullptr, nullptr, m->tau[b], ps);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->tau[b], pairs * 2 * kQT, nq, c.d, m->qnorm[b], m->gmax, c.e_rel);
+        return FIR_OK;
+    }
     const int sub_stride = k > 1 ? kPasses * kQT : 0;      // top-K: the sample as kRtSubsets subset minima per query
     FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
     // every rb_stride-th row block: the sample is spread over the whole gallery
@@ -1711,6 +1913,17 @@ static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, i
     return FIR_OK;
 }
 
+// audit builds with FIR_GEMM_DEBUG_COUNTS: phase boundary i of the super-batch in hand, on the stream the phase runs on
+static void gemm_audit_mark_(fir_gemm* m, int i, hipStream_t s) {
+#ifdef FIR_AUDIT
+    if (!m->debug_counts) return;
+    if (!m->phase_ev[i]) (void)hipEventCreate(&m->phase_ev[i]);
+    if (m->phase_ev[i]) (void)hipEventRecord(m->phase_ev[i], s);
+#else
+    (void)m; (void)i; (void)s;
+#endif
+}
+
 // Preparation of super-batch sb: (host-pointer calls) its upload, then everything its full passes need, on the stream GemmCall::serial_prep names
 static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
     hipStream_t ps = c.serial_prep ? c.st : m->side;
@@ -1722,9 +1935,11 @@ static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
         FIR_HIP(hipEventRecord(m->copy_done[b], m->copy));
         FIR_HIP(hipStreamWaitEvent(ps, m->copy_done[b], 0));
     }
+    gemm_audit_mark_(m, 0, ps);
     const int rc = m->precision == FIR_GEMM_F16 ? gemm_prep_f16_(m, c, ps, sb) : gemm_prep_f32_bf16_(m, c, ps, sb);
     if (rc) return rc;
     FIR_HIP(hipGetLastError());
+    gemm_audit_mark_(m, 1, ps);
     FIR_HIP(hipEventRecord(m->prep_done[b], ps));
     return FIR_OK;
 }
@@ -1804,7 +2019,12 @@ static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs)
     const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
     const size_t rr_lds = (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4);
     const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0};
-    if (c.k == 1)
+    if (c.num_classes > 0)
+        hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax,
+                           m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
+                           c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
+                           c.qs, m->rowmajor);
+    else if (c.k == 1)
         hipLaunchKernelGGL(k_gemm_rerank, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax, c.n, c.d,
                            m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, (unsigned long long*)c.d_keys + q0, m->ok + q0, c.qs, m->rowmajor, fb);
     else
@@ -1833,26 +2053,54 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
         FIR_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
         FIR_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)last * c.sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
         long long sum = 0;
-        int mx = 0, bad = 0;
-        for (int v : hc) { sum += v; mx = std::max(mx, v); }
+        int mx = 0, bad = 0, over = 0;
+        for (int v : hc) { sum += v; mx = std::max(mx, v); over += v > kListCap ? 1 : 0; }
         for (int v : h_ok) bad += v ? 0 : 1;
         std::vector<float> ht((size_t)nql);
         FIR_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
         double ts = 0;
         int ninf = 0;
         for (float v : ht) { if (v < 1e30f) ts += v; else ++ninf; }
-        std::fprintf(stderr, "fir_gemm: appended rows per query (last super-batch of %d): mean %.1f, max %d; tau: mean %.6f, %d not finite; %d uncertified\n", nql,
-                     (double)sum / nql, mx, ts / std::max(1, nql - ninf), ninf, bad);
+        float ms[3] = {0.f, 0.f, 0.f};                 // (serial preparation: the three phases follow one another on the device)
+        if (c.serial_prep && m->phase_ev[3])
+            for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], m->phase_ev[i], m->phase_ev[i + 1]);
+        std::fprintf(stderr, "fir_gemm: appended rows per query (last super-batch of %d): mean %.1f, max %d; tau: mean %.6f, %d not finite; %d uncertified; "
+                     "%d lists overflowed; preparation %.3f ms, full passes %.3f ms, re-rank %.3f ms\n", nql,
+                     (double)sum / nql, mx, ts / std::max(1, nql - ninf), ninf, bad, over, ms[0], ms[1], ms[2]);
     }
     return FIR_OK;
 }
 #endif
 
-// The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev)
-static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr) {
-    if (!m || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+// The uncertified queries of a distinct-class call: the call's one synchronisation of `st`, then the exact scan form for every
+// run of consecutive uncertified queries, straight into that run's output slots (no second-chance rounds)
+static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
+    std::vector<int> h_ok((size_t)c.qb);
+    FIR_HIP(hipMemcpyAsync(h_ok.data(), m->ok, (size_t)c.qb * sizeof(int), hipMemcpyDeviceToHost, c.st));
+    FIR_HIP(hipStreamSynchronize(c.st));
+    int uncertified = 0;
+    for (int q0 = 0; q0 < c.qb;) {
+        int q1 = q0;
+        while (q1 < c.qb && !h_ok[q1]) ++q1;
+        if (q1 == q0) { ++q0; continue; }
+        const int rc = fir_class_scan_dev_(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, c.d, c.num_classes, c.k, 0, c.d_keys ? c.d_keys + (size_t)q0 * c.k : nullptr,
+                                           c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, nullptr, c.st);
+        if (rc) return rc;
+        uncertified += q1 - q0;
+        q0 = q1;
+    }
+    if (uncertified) hipLaunchKernelGGL(k_gemm_fb_count, dim3(1), dim3(1), 0, c.st, m->fb_state, uncertified);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+
+// The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev), or -- num_classes > 0 --
+// the K <= 32 nearest distinct classes (fir_gemm_search_top_classes_keys_dev, which checks its own arguments)
+static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr,
+                       int32_t num_classes = 0, int32_t* d_classes = nullptr) {
+    if (!m || (!d_keys && !(num_classes > 0 && d_classes)) || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kTopKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kTopKMax);
+    if (k < 1 || k > (num_classes > 0 ? 32 : kTopKMax)) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, num_classes > 0 ? 32 : kTopKMax);
     if (qb == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
@@ -1860,8 +2108,10 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     if (order.rc) return order.rc;
     GemmCall c;
     c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
+    c.num_classes = num_classes; c.d_classes = d_classes;
     c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
     if (c.n == 0 && h_queries) FIR_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
+    if (c.n == 0 && num_classes > 0) return fir_class_scan_dev_(m->g, d_queries, qb, c.d, num_classes, k, 0, d_keys, d_classes, nullptr, st);   // every slot unused
     if (c.n == 0)
         return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
                       : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
@@ -1903,10 +2153,12 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
         if (m->precision == FIR_GEMM_F16) { if ((rc = gemm_pass_f16_(m, c, sb))) return rc; }
         else gemm_pass_f32_bf16_(m, c, sb);
         FIR_HIP(hipEventRecord(m->main_done[b], st));
+        gemm_audit_mark_(m, 2, st);
         // on the side stream, the re-rank runs under the next super-batch's full passes
         hipStream_t rs = c.one_stream ? st : m->side;
         if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
         gemm_rerank_(m, c, sb, rs);
+        gemm_audit_mark_(m, 3, rs);
         FIR_HIP(hipEventRecord(m->rerank_done[b], rs));
         m->passes += (c.sb_queries(sb) + kQT - 1) / kQT;
     }
@@ -1915,6 +2167,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
 #ifdef FIR_AUDIT
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
+    if (num_classes > 0) return gemm_finish_classes_(m, c);
     // uncertified queries: a second matrix-core pass with the tightest bound the first one can justify, then the exact device scan
     // (calls of at most 32 queries skip the second-chance rounds: the exact device scan reads the gallery once per eight queries, about what
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
@@ -1930,6 +2183,19 @@ int fir_gemm_search_top1_keys_dev(fir_gemm* m, const float* d_queries, int32_t q
 
 int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream) {
     return gemm_search(m, d_queries, qb, k, d_keys, stream);
+}
+
+int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t num_classes, int32_t k, uint64_t* d_keys,
+                                         int32_t* d_classes, void* stream) {
+    if (!m || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the distinct-class form needs a FIR_GEMM_F16 state");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > 32) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,32]", k);
+    if (num_classes < 1 || num_classes > (1 << 24)) return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, 1 << 24);
+    if (!m->v.cls && m->v.n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
+    if (qb == 0) return FIR_OK;
+    return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, num_classes, d_classes);
 }
 
 // 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one

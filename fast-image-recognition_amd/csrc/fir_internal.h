@@ -130,6 +130,14 @@ extern "C" int fir_search_top1_exact_keys_dev_(fir_gallery* g, const float* d_qu
 // ... and the exact K-nearest-rows form over features [0, end_pos), never through fir_gemm_*.
 extern "C" int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream);
 
+// The exact class-minimum scan of fir_search_top_classes_keys_dev over features [0, end_pos), on behalf of
+// fir_gemm_search_top_classes_keys_dev: not recorded as the handle's dispatch, not timed. sample_rows == 0: the whole gallery,
+// keys and classes as the public call writes them (its uncertified queries). sample_rows > 0: only the leading sample_rows rows
+// (whole tiles of 64) are scanned and d_bound[q] = the exact K-th smallest class minimum among them, 100000 when fewer than K
+// classes qualify there: a minimum over a subset of the rows, so an upper bound of the gallery's K-th class distance.
+extern "C" int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k,
+                                   int64_t sample_rows, uint64_t* d_keys, int32_t* d_classes, float* d_bound, void* stream);
+
 // fir_profile_enable / fir_profile_read / fir_gallery_last_dispatch for kernels launched by the other translation units:
 // an event pair around ONE launch on `st` (no-ops unless profiling is on), and the record of the call's dominant kernel.
 extern "C" int fir_gallery_profile_begin_(fir_gallery* g, void* st);

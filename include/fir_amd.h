@@ -144,8 +144,13 @@ int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb,
  * 1 <= k <= 32, 1 <= num_classes <= 16777216 (else FIR_ERR_ARG). class_out / idx / dist are [qb*k], any may be NULL; unused slots: class -1, idx -1, dist 100000.
  * The gallery needs class labels (else FIR_ERR_STATE). Rows labelled outside [0, num_classes) take no part
  * (as in fir_twd_conventional). A row qualifies only if `dist < 100000.0f` is true (so NaN distances never do).
- * One exact gallery scan per 8 queries (the arithmetic and distance bits of fir_search_top1's scan; no matrix-core
- * form); device scratch: 64 bytes per class and 8 queries, and the select step reads a query's 8 bytes per class twice with one
+ * One exact gallery scan per 8 queries (the arithmetic and distance bits of fir_search_top1's scan). fir_search_top_classes (the
+ * host-pointer call) sends an L2 batch over features [0, end_pos) -- whole rows, or a prefix with end_pos % 16 == 0, end_pos >= 64 --
+ * of a labelled gallery through fir_gemm_search_top_classes_keys_dev instead, same classes, rows and distance bits: by default
+ * from 128 queries against 65536 rows on (3.9 - 6.5 x the scan's rate at 1M x 512, 100 000 classes, 128 .. 32 768 queries per call: profiles/class_rank_matrix_cores.txt),
+ * with fir_gallery_set_large_batch_mfma(g, min_queries > 0) from the caller's threshold on at any gallery size, never after
+ * fir_gallery_set_large_batch_mfma(g, 0) or with FIR_SHADOW_NONE; fir_search_top_classes_keys_dev always takes the scan.
+ * Device scratch of the scan: 64 bytes per class and 8 queries, and the select step reads a query's 8 bytes per class twice with one
  * workgroup: with num_classes in the millions that read, not the scan, sets the time of a call of few queries. */
 int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                            int32_t num_classes, int32_t k, int32_t* class_out, int32_t* idx, float* dist);
@@ -374,6 +379,17 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
  * on the k-th smallest proxy and the certificate is taken against the k-th exact distance. fir_search_topk[_keys_dev] route
  * whole-range L2 batches here under the same rule as the top-1 calls (fir_gallery_set_large_batch_mfma). */
 int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream);
+/* The keys and classes of fir_search_top_classes_keys_dev, bit for bit, for the feature range the state covers (whole rows or
+ * its prefix), through the matrix cores: 1 <= k <= 32, 1 <= num_classes <= 16777216 (else FIR_ERR_ARG), one of d_keys / d_classes
+ * may be NULL, a gallery without labels gives FIR_ERR_STATE, a state that is not FIR_GEMM_F16 FIR_ERR_ARG. An exact class-minimum
+ * scan over a row sample (the leading max(16384, n k / 64) rows) bounds the k-th class distance from above; the fp16 pass appends
+ * every row below that bound (plus one rounding window); the re-rank drops duplicate classes, re-computes every row that can still
+ * matter in the reference's arithmetic and certifies against the k-th exact class distance. Unlike the calls above this one
+ * SYNCHRONISES `stream` once before returning: it has to learn which queries were not certified (list overflow, window reaching
+ * the bound, NaN) and runs the exact scan form for them, straight into their slots (fir_gemm_stats_ex counts them in out[1] and
+ * out[2]). fir_search_top_classes routes batches here under fir_gallery_set_large_batch_mfma's rule (see there). */
+int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t num_classes, int32_t k,
+                                         uint64_t* d_keys, int32_t* d_classes, void* stream);
 /* fir_search_top1 and fir_search_top1_keys_dev send L2 whole-range batches through this path BY DEFAULT when the batch
  * has >= 128 queries and the gallery >= 65536 rows (smaller, cache-resident galleries: where a cost model of the two forms gives the
  * matrix cores 15 % or more -- e.g. 128 queries against 40 000 x 512, 1 024 against 8 192 x 512 --, from the gallery's fourth such
