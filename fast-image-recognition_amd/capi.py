@@ -67,6 +67,7 @@ SYMBOLS = [
     ("fir_cls_sharded_pnn_predict", C.c_int, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp]),
     ("fir_cls_sharded_knn_predict", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     ("fir_cls_set_total_training_size", C.c_int, [_vp, C.c_int64]),
+    ("fir_cls_kmedoids", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     ("fir_cls_distance_sums", C.c_int, [_vp, _vp, C.c_int32, _vp]),
     ("fir_cls_pnn_predict", C.c_int, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp]),
     ("fir_cls_pnn_predict_seq", C.c_int, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp]),
@@ -777,6 +778,16 @@ class ClsModel:
 
     def set_total_training_size(self, total):
         _check(lib().fir_cls_set_total_training_size(self._h, int(total)))
+
+    def kmedoids(self, num_clusters, steps=0, scratch_bytes=0):
+        """k-medoids inside every class (PNNwithClusteringClassifier::train): rows[num_classes, num_clusters] = positions in
+        train_rows of the live medoids in cluster order (-1 padded), their count and the steps computed per class."""
+        rows = np.empty((self.num_classes, max(int(num_clusters), 0)), np.int32)
+        count = np.empty(self.num_classes, np.int32)
+        steps_run = np.empty(self.num_classes, np.int32)
+        _check(lib().fir_cls_kmedoids(self._h, int(num_clusters), int(steps), int(scratch_bytes), rows.ctypes.data_as(_vp),
+                                      count.ctypes.data_as(_vp), steps_run.ctypes.data_as(_vp)))
+        return rows, count, steps_run
 
     def distance_sums(self, queries):
         q, pq = self._q(queries)

@@ -688,6 +688,8 @@ struct fir_cls {
     double* knn_dist = nullptr; size_t knn_dist_cap = 0;
     int32_t* knn_ok = nullptr; size_t knn_ok_cap = 0;
     int64_t mm_queries = 0, mm_unsettled = 0;         // queries that went through the matrix cores / of them sent on to the exact scan
+    std::vector<int32_t> class_off_h;                 // host copy of class_off
+    FirBuf km, km_meta;                               // fir_cls_kmedoids: distance tables + de-tiled rows + candidate sums / descriptors + results
 };
 
 namespace {
@@ -891,6 +893,7 @@ static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt,
     c->dp2 = (d + 1) / 2;
     c->num_classes = num_classes;
     c->tiles = (nt + kTileRows - 1) / kTileRows;
+    c->class_off_h = off;
     int rc = FIR_OK;
     double* stage = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -1355,3 +1358,5 @@ int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int
 }
 
 }  // extern "C"
+
+#include "fir_cls_kmedoids.h"

@@ -2,6 +2,7 @@
 // every distance, exp and vote on the GPU (fir_cls_*).
 #include "fir_classification.h"
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -214,53 +215,26 @@ void PNNwithClusteringClassifier::train() {
     fir::ClassificationState& st = classification_state();
     const size_t D = st.num_of_cont_features;
     clustered_training_set.assign(st.num_of_classes, std::vector<size_t>());
+    // k-medoids inside every class on the device (fir_cls_kmedoids): one handle over the raw training rows, class-major, with a
+    // zero mean -- the n x n tables of mean squared distances are then the reference's own (:339-343, 360-365)
+    std::vector<size_t> order;                                                        // position in the handle -> dataset index
+    std::vector<int32_t> cls_of;
+    for (size_t i = 0; i < st.num_of_classes; ++i)
+        for (size_t t : st.training_set[i]) { order.push_back(t); cls_of.push_back((int32_t)i); }
+    std::vector<double> raw(order.size() * D);
+    for (size_t t = 0; t < order.size(); ++t)
+        for (size_t f = 0; f < D; ++f) raw[t * D + f] = st.dataset[order[t]].features[f];
     const std::vector<double> zero_mean(D, 0.0);
+    std::vector<int32_t> medoid_rows(st.num_of_classes * (size_t)std::max(num_clusters, 1)), medoid_count(st.num_of_classes);
+    fir_cls* pairs = nullptr;
+    const bool clustered =
+        fir_cls_create(raw.data(), (int64_t)order.size(), (int32_t)D, cls_of.data(), (int32_t)st.num_of_classes, zero_mean.data(), fir::classification_device(), &pairs) == FIR_OK &&
+        fir_cls_kmedoids(pairs, num_clusters, 0, 0, medoid_rows.data(), medoid_count.data(), nullptr) == FIR_OK;
+    if (!clustered) std::fprintf(stderr, "fir: clustering: %s\n", fir_last_error());
+    if (pairs) fir_cls_destroy(pairs);
     for (size_t i = 0; i < st.num_of_classes; ++i) {
-        const std::vector<size_t>& members = st.training_set[i];
-        const size_t n = members.size();
-        if (n <= (size_t)num_clusters) { clustered_training_set[i] = members; continue; }   // :381-385
-        // n x n table of mean squared distances between the class's raw rows (:339-343, 360-365), from the GPU
-        std::vector<double> rows(n * D);
-        for (size_t t = 0; t < n; ++t)
-            for (size_t f = 0; f < D; ++f) rows[t * D + f] = st.dataset[members[t]].features[f];
-        std::vector<int32_t> one_class(n, 0);
-        std::vector<double> table(n * n);
-        fir_cls* pair = nullptr;
-        if (fir_cls_create(rows.data(), (int64_t)n, (int32_t)D, one_class.data(), 1, zero_mean.data(), fir::classification_device(), &pair) != FIR_OK ||
-            fir_cls_distance_sums(pair, rows.data(), (int32_t)n, table.data()) != FIR_OK) {
-            std::fprintf(stderr, "fir: clustering distances: %s\n", fir_last_error());
-            if (pair) fir_cls_destroy(pair);
-            clustered_training_set[i] = members;
-            continue;
-        }
-        fir_cls_destroy(pair);
-        for (double& v : table) v /= (double)D;                                           // dist /= num_of_cont_features
-        std::vector<long> centroid((size_t)num_clusters), assign(n);
-        for (int c = 0; c < num_clusters; ++c) centroid[(size_t)c] = c;
-        for (int step = 0; step < 100; ++step) {
-            for (size_t t = 0; t < n; ++t) {                                              // nearest medoid, first on ties (:331-350)
-                assign[t] = -1;
-                double best = DBL_MAX;
-                for (int c = 0; c < num_clusters; ++c) {
-                    if (centroid[(size_t)c] < 0) continue;
-                    const double dist = table[(size_t)centroid[(size_t)c] * n + t];
-                    if (dist < best) { best = dist; assign[t] = c; }
-                }
-            }
-            for (int c = 0; c < num_clusters; ++c) {                                      // member with the smallest summed distance (:351-375)
-                double best = DBL_MAX;
-                centroid[(size_t)c] = -1;
-                for (size_t t = 0; t < n; ++t) {
-                    if (assign[t] != c) continue;
-                    double sum = 0;
-                    for (size_t t1 = 0; t1 < n; ++t1)
-                        if (assign[t1] == c) sum += table[t * n + t1];
-                    if (sum < best) { best = sum; centroid[(size_t)c] = (long)t; }
-                }
-            }
-        }
-        for (int c = 0; c < num_clusters; ++c)
-            if (centroid[(size_t)c] >= 0) clustered_training_set[i].push_back(members[(size_t)centroid[(size_t)c]]);
+        if (!clustered) { clustered_training_set[i] = st.training_set[i]; continue; }
+        for (int32_t j = 0; j < medoid_count[i]; ++j) clustered_training_set[i].push_back(order[(size_t)medoid_rows[i * (size_t)num_clusters + (size_t)j]]);
     }
     // device model over the medoids; the PNN denominator stays the full training size (:390,393)
     if (medoid_model) { fir_cls_destroy(medoid_model); medoid_model = nullptr; }

@@ -232,6 +232,31 @@ int fir_cls_profile_read(fir_cls* c, float* ms, int32_t cap, int32_t* count, dou
 /* PNNwithClusteringClassifier::predict (classification.cpp:389-428) runs the PNN over the medoid rows
  * only but still divides by the FULL training size: set it here (0 = the number of rows held). */
 int fir_cls_set_total_training_size(fir_cls* c, int64_t total);
+/* PNNwithClusteringClassifier::train, classification.cpp:320-388: k-medoids inside every class of the handle, on the device.
+ * Classes: class i holds the rows [class_off[i], class_off[i+1]) of train_rows (the handle's own classes; a class may be
+ *   empty). A class with n <= num_clusters rows keeps every row in order (:381-385): medoid_count = n, steps_run = 0.
+ * Distance table of a class: T[t][t1] = S / d, S = what fir_cls_distance_sums returns for query = training row t and row t1
+ *   (((g - avg) - (q - avg))^2 summed in feature order, un-fused), the division the IEEE double division. With avg all zeros
+ *   these are the reference's bits (:337-343, :358-364). T is symmetric bit for bit: the difference only changes sign.
+ * One step. Assign: every t goes to the first cluster c (ascending) whose medoid is alive and whose T[medoid_c][t] is the
+ *   strict minimum starting from DBL_MAX; when no cluster qualifies (NaN) t belongs to none. Update: the new medoid of a
+ *   cluster is its first member t (ascending) whose sum over the members t1 of T[t][t1] -- a plain double sum in ascending t1
+ *   -- is the strict minimum starting from DBL_MAX. A cluster with no such member is dead (-1) and stays dead (the reference
+ *   indexes [-1] there; it is skipped).
+ * Start: medoid c = member c. steps = 0 means the reference's 100 steps, otherwise steps is the upper bound. A step that
+ *   leaves the medoid vector unchanged ends the iteration: every later step would repeat it, so the result is that of all
+ *   `steps` steps. steps_run[i] (may be NULL) <- the steps computed, the one that confirmed the fixed point included.
+ * medoid_rows[i * num_clusters + j] <- position in train_rows of the j-th live medoid of class i, in cluster order; unused
+ *   slots hold -1. medoid_count[i] <- how many.
+ * scratch_bytes bounds the bytes of distance tables (n^2 * 8 per clustered class) held at once: classes are processed in
+ *   groups of consecutive classes whose tables fit. 0 = automatic: half of the device memory free at the time of the call.
+ *   Only what the largest group needs is allocated (plus that group's rows in scan order and nt doubles); the handle keeps it.
+ * FIR_ERR_ARG: NULL c / medoid_rows / medoid_count, num_clusters outside [1, 256], steps < 0, scratch_bytes < 0, a class of
+ *   more than 32768 rows that needs clustering. FIR_ERR_NOMEM: one class's table exceeds the bound, or an allocation failed.
+ *   Arguments are checked before anything is allocated or launched. The call synchronises the handle's stream before it
+ *   returns and leaves every other call on the handle unaffected. One class runs on one compute unit. */
+int fir_cls_kmedoids(fir_cls* c, int32_t num_clusters, int32_t steps, int64_t scratch_bytes, int32_t* medoid_rows /* [num_classes * num_clusters] */,
+                     int32_t* medoid_count /* [num_classes] */, int32_t* steps_run /* [num_classes], may be NULL */);
 /* sums[qb][nt] <- sum_f ((g_f - avg_f) - (q_f - avg_f))^2 per training row, accumulated in feature
  * order in double (classification.cpp:123-141 before the division, :199-211). */
 int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double* sums);
