@@ -59,6 +59,7 @@ SYMBOLS = [
     ("fir_twd_conventional", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp]),
     ("fir_twd_proposed", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
     ("fir_twd_last_dispatch", C.c_int, [_vp, _vp]),
+    ("fir_twd_last_mfma", C.c_int, [_vp, _vp]),
     ("fir_cls_create", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(_vp)]),
     ("fir_cls_create_dev", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(_vp)]),
     ("fir_cls_destroy", C.c_int, [_vp]),
@@ -412,6 +413,13 @@ class Gallery:
                 "tiles_per_wave": o.tiles_per_wave, "workgroups_per_query": o.workgroups_per_query, "queries_per_launch": o.queries_per_launch,
                 "fused_launches": o.fused_launches, "fused_gave_up": o.fused_gave_up, "staged_batches": o.staged_batches,
                 "kernel": o.kernel.decode()}
+
+    def twd_last_mfma(self):
+        """What the most recent twd_conventional call on this handle did with the matrix cores (fir_twd_last_mfma): six host-side counters,
+        all zero when the call was not routed."""
+        o = (C.c_int64 * 6)()
+        _check(lib().fir_twd_last_mfma(self._h, o))
+        return {"queries": o[0], "reliable": o[1], "second_stage": o[2], "band": o[3], "uncertified": o[4], "class_scan": o[5]}
 
     def classes_of(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

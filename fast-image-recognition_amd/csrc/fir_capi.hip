@@ -88,6 +88,9 @@ struct fir_gallery {
     fir_gemm* gemm = nullptr; // created on first use
     fir_dispatch_info last{}; // dominant kernel of the most recent search
     fir_twd_dispatch_info twd_last{0, -1};   // fir_twd_last_dispatch (fir_twd.hip writes it through fir_gallery_twd_record_); classifier -1: no call yet
+    int64_t twd_mfma[6] = {};                // fir_twd_last_mfma (fir_twd.hip writes it through fir_gallery_twd_mfma_record_)
+    bool label_known = false;                // fir_gallery_label_range_: smallest and largest label, found once (the labels never change)
+    int32_t label_lo = 0, label_hi = -1;
     int call_launches = 0;    // scan launches of the current call (note_dispatch)
     bool quiet = false;       // scans on behalf of another path (the matrix-core path's uncertified queries): not recorded, not timed
     int sample_groups = 0; int64_t sample_group_stride = 0;   // run_pass (generic k_scan, top-1): ScanArgs::groups / group_stride
@@ -1423,6 +1426,98 @@ int try_mfma_classes(fir_gallery* g, const float* d_queries, int32_t qb, int32_t
     return rcs;
 }
 }  // namespace
+
+// ---- the matrix-core steps of fir_twd_conventional's batch form (fir_twd.hip; fir_internal.h has the contracts) ----
+// The automatic rule (kAutoMfmaQueries queries over kAutoMfmaRows rows) for fir_twd_conventional's batch form: on. Measured against the
+// launch-per-stage form of the commit before it, 7 680 classes, reduced 64, 128 .. 32 768 queries per call (profiles/twd_conventional_batch.txt):
+// 230 400 x 256 1.7-24 x faster class-major and 2.5-13 x permuted; 1M x 256 1.6-3.9 x class-major (a fifth of the class lists overflow
+// into the exact class scan there) and 4.5-11 x permuted, with every query reliable and with every query unreliable -- every case
+// beyond the 15 % the other automatic routes ask for. Smaller galleries were not measured: a caller's threshold only.
+constexpr bool kAutoMfmaTwd = true;
+int fir_twd_wants_mfma_(fir_gallery* g, int32_t qb, int32_t end_pos) {
+    if (!g || !g->cls) return 0;
+    if (g->large_batch_min < 0 && !kAutoMfmaTwd) return 0;
+    if (g->shadow_mode == FIR_SHADOW_NONE) return 0;       // the caller forbade every copy; this form needs two fp16 copies, whatever the threshold
+    return wants_mfma(g, qb, 0, end_pos, true) ? 1 : 0;
+}
+int fir_twd_mfma_classes_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k, uint64_t* d_keys,
+                          int32_t* d_classes, void* stream, int64_t* exact_answered) {
+    if (!g || !d_queries || !exact_answered) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    // the exact-scan total of the state for [0, end_pos), before and after: the difference is this call's share (a state built by
+    // this call starts from zero)
+    auto state_of = [&]() -> fir_gemm* {
+        if (end_pos == g->d) return g->gemm;
+        for (auto& c : g->gemm_prefix) if (c.m && c.end == end_pos) return c.m;
+        return nullptr;
+    };
+    int64_t before[3] = {0, 0, 0}, after[3] = {0, 0, 0};
+    if (fir_gemm* m0 = state_of()) { const int rs = fir_gemm_stats_ex(m0, before); if (rs) return rs; }
+    const int rc = try_mfma_classes(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, st);
+    if (rc) return rc;
+    if (fir_gemm* m1 = state_of()) { const int rs = fir_gemm_stats_ex(m1, after); if (rs) return rs; }
+    *exact_answered = after[2] - before[2];
+    return FIR_OK;
+}
+int fir_twd_mfma_topk_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t qb_call, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream) {
+    if (!g || !d_queries || !d_keys) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    // the rule for these qb queries; under a caller's threshold the batch that was admitted (qb_call queries) decides for its parts too
+    const bool by_call = g->large_batch_min > 0 && wants_mfma(g, qb_call, 0, end_pos);
+    if (k < 2 || g->shadow_mode == FIR_SHADOW_NONE || !(by_call || wants_mfma(g, qb, 0, end_pos))) return 1;
+    fir_gemm* m = nullptr;
+    const int rc = ensure_gemm(g, end_pos, &m);
+    if (rc) return rc;
+    const int rcs = fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, stream ? (hipStream_t)stream : g->stream);
+    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {       // no room for this call's candidate lists (automatic mode): the staged form answers
+        (void)hipGetLastError();
+        return 1;
+    }
+    return rcs;
+}
+int64_t* fir_gallery_twd_mfma_record_(fir_gallery* g) { return g->twd_mfma; }
+
+namespace {
+// out[0] = smallest label, out[1] = largest (entered with INT32_MAX, INT32_MIN)
+__global__ void __launch_bounds__(kBlock) k_label_range(const int32_t* __restrict__ cls, int64_t n, int32_t* __restrict__ out) {
+    int32_t lo = INT32_MAX, hi = INT32_MIN;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int32_t c = cls[i];
+        lo = c < lo ? c : lo;
+        hi = c > hi ? c : hi;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int32_t l2 = __shfl_xor(lo, off, 64), h2 = __shfl_xor(hi, off, 64);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63) == 0) { atomicMin(&out[0], lo); atomicMax(&out[1], hi); }
+}
+}  // namespace
+
+int fir_gallery_label_range_(fir_gallery* g, int32_t* lo, int32_t* hi) {
+    if (!g || !lo || !hi) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (!g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    if (!g->label_known) {
+        FIR_HIP(hipSetDevice(g->device));
+        void* p = nullptr;
+        const int rc = fir_gallery_scratch_(g, 23, 16, &p);
+        if (rc) return rc;
+        int32_t h[2] = {INT32_MAX, INT32_MIN};
+        FIR_HIP(hipMemcpyAsync(p, h, sizeof h, hipMemcpyHostToDevice, g->stream));
+        const int grid = (int)std::min<int64_t>(std::max<int64_t>((g->n + kBlock - 1) / kBlock, 1), 4 * std::max(g->cus, 1));
+        hipLaunchKernelGGL(k_label_range, dim3(grid), dim3(kBlock), 0, g->stream, g->cls, g->n, (int32_t*)p);
+        FIR_HIP(hipGetLastError());
+        FIR_HIP(hipMemcpyAsync(h, p, sizeof h, hipMemcpyDeviceToHost, g->stream));
+        FIR_HIP(hipStreamSynchronize(g->stream));
+        g->label_lo = h[0];
+        g->label_hi = h[1];
+        g->label_known = true;
+    }
+    *lo = g->label_lo;
+    *hi = g->label_hi;
+    return FIR_OK;
+}
 
 int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream) {
     if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");

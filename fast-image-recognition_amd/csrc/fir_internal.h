@@ -90,7 +90,8 @@ extern "C" int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4); 
 // Device scratch owned by the gallery handle: `slot` in [0, 24), grown on demand, kept until the gallery is destroyed
 // (the per-call hipMalloc / hipFree pairs of the classifier entry points cost more than their kernels on small galleries).
 // Slots 0-7 and 16: fir_twd.hip (0 queries, 1 conventional distance tables, 2 k_twd_prop_fused state, 3 verdicts, 4-6 proposed chunk
-// distances / sums / alive flags, 7 segment records of either staged form, 16 k_twd_conv_fused state), 8-11: fir_dem.hip, 12-15, 17 and 18: fir_capi.hip (17, 18: top_classes_dev); 19-23 are free.
+// distances / sums / alive flags, 7 segment records of either staged form, 16 k_twd_conv_fused state), 8-11: fir_dem.hip, 12-15, 17, 18 and 23: fir_capi.hip (17, 18: top_classes_dev; 23: label range);
+// 19-22: fir_twd.hip's matrix-core batch form (fir_twd_batch.h: 19 the chunk's queries, 20 the unreliable queries' vectors, 21 keys and classes, 22 flags and lists).
 extern "C" int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out);
 // Per-handle call counters of the other translation units (slot 0: fir_twd.hip's fused classifier): returns the value before the increment.
 extern "C" uint64_t fir_gallery_next_counter_(fir_gallery* g, int slot);
@@ -137,6 +138,26 @@ extern "C" int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_qu
 // classes qualify there: a minimum over a subset of the rows, so an upper bound of the gallery's K-th class distance.
 extern "C" int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k,
                                    int64_t sample_rows, uint64_t* d_keys, int32_t* d_classes, float* d_bound, void* stream);
+
+// The matrix-core steps of fir_twd_conventional's batch form (fir_twd.hip), on a prefix [0, end_pos) of the rows (end_pos == d: the
+// whole-row state; the handle's two prefix slots hold the others).
+// fir_twd_wants_mfma_: 1 when wants_mfma(g, qb, 0, end_pos, classes) holds -- the caller's fir_gallery_set_large_batch_mfma threshold or the
+// automatic rule, the pinned-tuning exclusions, gemm_failed -- and the shadow mode is not FIR_SHADOW_NONE; 0 otherwise. Host only.
+extern "C" int fir_twd_wants_mfma_(fir_gallery* g, int32_t qb, int32_t end_pos);
+// try_mfma_classes / try_mfma_topk: 0 = the keys (and classes) of fir_search_top_classes_keys_dev / fir_search_topk_keys_dev over
+// [0, end_pos) are queued or written, 1 = this call stays with the scan (nothing was queued), < 0 = error. The class form synchronises
+// `stream`; *exact_answered <- the queries of this call its own exact class scan answered (fir_gemm_stats_ex out[2], this call's share).
+// The row form is asked for a part of a batch (the unreliable queries of qb_call): it takes the matrix cores when the rule holds for
+// its own qb queries or, under a caller's threshold, for the qb_call queries of the batch that was admitted.
+extern "C" int fir_twd_mfma_classes_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k,
+                                     uint64_t* d_keys, int32_t* d_classes, void* stream, int64_t* exact_answered);
+extern "C" int fir_twd_mfma_topk_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t qb_call, int32_t end_pos, int32_t k, uint64_t* d_keys,
+                                  void* stream);
+// The smallest and the largest label of the gallery: one small reduction kernel on the handle's stream the first time (it
+// synchronises that stream), the cached words afterwards. FIR_ERR_STATE without labels; an empty gallery gives lo > hi.
+extern "C" int fir_gallery_label_range_(fir_gallery* g, int32_t* lo, int32_t* hi);
+// The handle's six counters of its most recent fir_twd_conventional call (fir_twd_last_mfma): host memory, written by fir_twd.hip.
+extern "C" int64_t* fir_gallery_twd_mfma_record_(fir_gallery* g);
 
 // fir_profile_enable / fir_profile_read / fir_gallery_last_dispatch for kernels launched by the other translation units:
 // an event pair around ONE launch on `st` (no-ops unless profiling is on), and the record of the call's dominant kernel.

@@ -1130,6 +1130,8 @@ __global__ void __launch_bounds__(kFusedBlock) k_twd_conv_fused(const float4* __
     }
 }
 
+#include "fir_twd_batch.h"
+
 // Queries per internal batch: as many as keep the per-batch distance tables under `budget` bytes (a multiple of 8, <= kBatch).
 int batch_for(int64_t n, size_t bytes_per_query_row, size_t budget = (size_t)512 << 20) {
     const size_t per_query = (size_t)std::max<int64_t>(n, 1) * bytes_per_query_row;
@@ -1489,6 +1491,134 @@ int prop_staged(TwdIo& io, const TwdPlan& p, int reduced, int nchunks, double th
     return io.collect(h_res, kPropWords, kPropTicket, ticket, self_publish);
 }
 
+
+// ---- the matrix-core batch form (type 0, L2; kernels: fir_twd_batch.h) ----
+// A call takes it when its first stage is one the class search sends through the matrix cores (fir_twd_wants_mfma_: the caller's
+// fir_gallery_set_large_batch_mfma threshold or the automatic rule) and every label lies in [0, num_classes): k_twd_conv_stage1 lets a
+// row labelled outside be the best row while it contributes no posterior, fir_search_top_classes leaves such rows out altogether.
+// The automatic rule (>= 128 queries over >= 65 536 rows) is the class search's, switched for this form by kAutoMfmaTwd of fir_capi.hip.
+bool mfma_form_applies(fir_gallery* g, const fir_gallery_view& v, int qb, const ConvArgs& a, int* rc) {
+    *rc = FIR_OK;
+    if (a.type != 0 || v.metric != FIR_METRIC_L2 || v.n <= 0) return false;
+    if (a.reduced % 16 != 0 || a.reduced < 64 || a.reduced >= kLastFeature) return false;
+    if (!fir_twd_wants_mfma_(g, qb, a.reduced)) return false;
+    int32_t lo = 0, hi = -1;
+    if ((*rc = fir_gallery_label_range_(g, &lo, &hi))) return false;
+    return lo >= 0 && hi < a.num_classes;
+}
+// Queries per chunk: the scratch (two copies of the chunk's vectors) stays within 256 MiB, and the chunks of a call are equal to
+// within one query (a ragged last chunk below the caller's threshold would fall back to the staged form whole).
+int mfma_chunk_for(int qb, int d) {
+    const int cap = (int)std::max<size_t>(1024, std::min<size_t>(32768, ((size_t)128 << 20) / ((size_t)d * 4)));
+    const int chunks = (qb + cap - 1) / cap;
+    return (qb + chunks - 1) / chunks;
+}
+
+// One routed call. The leftovers (threshold band, second stage not certified) go through conv_staged in its batches.
+int conv_mfma(fir_gallery* g, const fir_gallery_view& v, const ConvArgs& a, const float* queries, int qb, int32_t* class_out, int32_t* unreliable_out) {
+    int rc;
+    int64_t* cnt = fir_gallery_twd_mfma_record_(g);
+    TwdPlan p = plan_conventional(v, qb, a.num_classes, a.type, a.reduced);
+    p.fused = false;
+    p.step = p.batch;
+    fir_twd_dispatch_info* rec = note_plan(g, 0, p);
+    TwdIo io{g, v};
+    if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
+    if ((rc = take_slot(g, 3, (size_t)kConvWords * 4, &io.dres))) return rc;
+    const int chunk = mfma_chunk_for(qb, v.d);
+    Slot sq, sg, sk, sf;
+    if ((rc = take_slot(g, 19, (size_t)chunk * v.d * 4, &sq))) return rc;
+    if ((rc = take_slot(g, 20, (size_t)chunk * v.d * 4, &sg))) return rc;
+    if ((rc = take_slot(g, 21, (size_t)chunk * ((kMfmaClasses + kMfmaRows) * 8 + kMfmaClasses * 4), &sk))) return rc;
+    if ((rc = take_slot(g, 22, ((size_t)chunk * 6 + 2) * 4, &sf))) return rc;
+    unsigned long long* ckeys = sk.as<unsigned long long>();
+    unsigned long long* rkeys = ckeys + (size_t)chunk * kMfmaClasses;
+    int32_t* cclasses = (int32_t*)(rkeys + (size_t)chunk * kMfmaRows);
+    int32_t* dverdict = sf.as<int32_t>();
+    int32_t* dclass = dverdict + chunk;
+    int32_t* dpos = dclass + chunk;
+    int32_t* dok = dpos + chunk;
+    int32_t* dlists = dok + chunk;                                     // [2 + 2 * chunk]
+    const void* gal4 = nullptr;
+    int dp4 = 0;
+    if ((rc = fir_gallery_tiled_(g, &gal4, &dp4))) return fir_fail_(rc, "no tiled gallery");
+    std::vector<int32_t> h_lists((size_t)2 + 2 * chunk), h_verdict(chunk), h_class(chunk), h_ok(chunk), left;
+    std::vector<float> h_left;
+    for (int q0 = 0; q0 < qb; q0 += chunk) {
+        const int nq = std::min(chunk, qb - q0);
+        const float* hq = queries + (size_t)q0 * v.d;
+        left.clear();
+        FIR_HIP(hipMemcpyAsync(sq.p, hq, (size_t)nq * v.d * 4, hipMemcpyHostToDevice, v.stream));
+        // 1. the five nearest distinct classes over [0, reduced): the exact scan's keys (the class call answers its own uncertified queries)
+        int64_t exact = 0;
+        rc = fir_twd_mfma_classes_(g, sq.as<float>(), nq, a.reduced, a.num_classes, kMfmaClasses, (uint64_t*)ckeys, cclasses, v.stream, &exact);
+        if (rc < 0) return rc;
+        if (rc > 0) {
+            for (int i = 0; i < nq; ++i) left.push_back(i);                // (this chunk is below the threshold after all: the staged form)
+        } else {
+            // 2. + 3. the reliability test, the lists of the unreliable and the marked queries, the unreliable queries' vectors
+            hipLaunchKernelGGL(k_twd_batch_decide, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, v.stream, ckeys, cclasses, nq, a.threshold, dclass, dverdict);
+            hipLaunchKernelGGL(k_twd_batch_compact, dim3(1), dim3(kBlock), 0, v.stream, dverdict, nq, dlists, dpos);
+            hipLaunchKernelGGL(k_twd_batch_gather, dim3(nq), dim3(64), 0, v.stream, sq.as<float>(), dpos, v.d, sg.as<float>());
+            FIR_HIP(hipGetLastError());
+            FIR_HIP(hipMemcpyAsync(h_lists.data(), dlists, ((size_t)2 + 2 * nq) * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipStreamSynchronize(v.stream));
+            const int n_unrel = h_lists[0], n_marked = h_lists[1];
+            const int32_t* h_unrel = h_lists.data() + 2;
+            for (int i = 0; i < n_marked; ++i) left.push_back(h_lists[(size_t)2 + nq + i]);
+            // 4. the eight nearest rows over [0, 256) of the unreliable queries, then the reference's second-stage arithmetic among them
+            bool stage2 = false;
+            if (n_unrel > 0) {
+                rc = fir_twd_mfma_topk_(g, sg.as<float>(), n_unrel, qb, kLastFeature, kMfmaRows, (uint64_t*)rkeys, v.stream);
+                if (rc < 0) return rc;
+                stage2 = rc == 0;
+            }
+            if (stage2) {
+                hipLaunchKernelGGL(k_twd_batch_stage2, dim3(n_unrel), dim3(64), 0, v.stream, (const float4*)gal4, dp4, v.n, v.row_offset, v.cls, sg.as<float>(),
+                                   v.d, a.reduced, rkeys, dlists + 2, dclass, dok);
+                FIR_HIP(hipGetLastError());
+                FIR_HIP(hipMemcpyAsync(h_ok.data(), dok, (size_t)n_unrel * 4, hipMemcpyDeviceToHost, v.stream));
+            }
+            FIR_HIP(hipMemcpyAsync(h_verdict.data(), dverdict, (size_t)nq * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipMemcpyAsync(h_class.data(), dclass, (size_t)nq * 4, hipMemcpyDeviceToHost, v.stream));
+            FIR_HIP(hipStreamSynchronize(v.stream));
+            int certified = 0;
+            for (int i = 0; i < n_unrel; ++i) {
+                if (stage2 && h_ok[i]) ++certified;
+                else left.push_back(h_unrel[i]);
+            }
+            std::sort(left.begin(), left.end());
+            // 6. the verdicts of the queries this form answered
+            for (int i = 0; i < nq; ++i) {
+                class_out[q0 + i] = h_class[i];
+                if (unreliable_out) unreliable_out[q0 + i] = h_verdict[i] == kVerdictReliable ? 0 : 1;
+            }
+            cnt[0] += nq;
+            cnt[1] += nq - n_unrel - n_marked;
+            cnt[2] += certified;
+            cnt[3] += n_marked;
+            cnt[4] += n_unrel - certified;
+            cnt[5] += exact;
+        }
+        // 5. leftovers: both words are the staged form's
+        for (size_t l0 = 0; l0 < left.size(); l0 += (size_t)p.batch) {
+            const int nl = (int)std::min<size_t>((size_t)p.batch, left.size() - l0);
+            h_left.resize((size_t)nl * v.d);
+            for (int i = 0; i < nl; ++i) std::memcpy(h_left.data() + (size_t)i * v.d, hq + (size_t)left[l0 + i] * v.d, (size_t)v.d * 4);
+            const float* qsrc = nullptr;
+            int32_t h_res[kConvWords];
+            if ((rc = io.stage(h_left.data(), nl, &qsrc))) return rc;
+            if ((rc = conv_staged(io, p, a, qsrc, nl, h_res))) return rc;
+            ++rec->staged_batches;
+            for (int i = 0; i < nl; ++i) {
+                class_out[q0 + left[l0 + i]] = h_res[i];
+                if (unreliable_out) unreliable_out[q0 + left[l0 + i]] = h_res[kBatch + i];
+            }
+        }
+    }
+    return FIR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1506,8 +1636,11 @@ int fir_twd_conventional(fir_gallery* g, const float* queries, int32_t qb, int32
     FIR_HIP(hipSetDevice(v.device));
     FirCallOrder order(g, v.stream);               // (a host-pointer call: on the handle's own stream, after its earlier calls)
     if (order.rc) return order.rc;
-    const TwdPlan p = plan_conventional(v, qb, num_classes, type, reduced_features_count);
     const ConvArgs a{num_classes, type, threshold, reduced_features_count};
+    std::memset(fir_gallery_twd_mfma_record_(g), 0, 6 * sizeof(int64_t));
+    if (mfma_form_applies(g, v, qb, a, &rc)) return conv_mfma(g, v, a, queries, qb, class_out, unreliable_out);
+    if (rc) return rc;
+    const TwdPlan p = plan_conventional(v, qb, num_classes, type, reduced_features_count);
     fir_twd_dispatch_info* rec = note_plan(g, 0, p);
     TwdIo io{g, v};
     if ((rc = take_slot(g, 0, (size_t)p.batch * v.d * 4, &io.dq))) return rc;
@@ -1575,6 +1708,12 @@ int fir_twd_proposed(fir_gallery* g, const float* queries, int32_t qb, int32_t r
             if (chunks_out) chunks_out[q0 + i] = h_res[2 * kBatch + i];
         }
     }
+    return FIR_OK;
+}
+
+int fir_twd_last_mfma(fir_gallery* g, int64_t out[6]) {
+    if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    std::memcpy(out, fir_gallery_twd_mfma_record_(g), 6 * sizeof(int64_t));
     return FIR_OK;
 }
 

@@ -210,6 +210,31 @@ typedef struct fir_twd_dispatch_info {
                                     * (<metric: 0 L2, 1 chi-square; tiles per wave>); "" when not fused */
 } fir_twd_dispatch_info;
 int fir_twd_last_dispatch(fir_gallery* g, fir_twd_dispatch_info* out);
+/* Batches through the matrix cores. A fir_twd_conventional call with type 0 on an L2 gallery, reduced_features_count a multiple of
+ * 16 in [64, 256) and every label of the gallery in [0, num_classes) takes another form when fir_search_top_classes would send a batch
+ * of qb queries over [0, reduced_features_count) through the matrix cores (see there and fir_gallery_set_large_batch_mfma: the
+ * caller's threshold at any gallery size, never with threshold 0 or FIR_SHADOW_NONE; by default from 128 queries over 65536 rows on:
+ * 1.6 - 24 x the launch-per-stage form's speed at 230 400 and 1M rows x 256, 7 680 classes, 128 .. 32 768 queries per call,
+ * profiles/twd_conventional_batch.txt; smaller galleries were not measured). Same class_out and unreliable_out for every query:
+ *   first stage   the 5 nearest distinct classes over [0, reduced_features_count) (fir_gemm_search_top_classes_keys_dev: the exact
+ *                 scan's keys) give the nearest row and the 5 largest class posteriors; max_probab is formed from them in the
+ *                 arithmetic of :130,141-148. A query whose max_probab lies within 2^-40 (relative) of the threshold, or is a NaN,
+ *                 is answered by the launch-per-stage form instead;
+ *   second stage  the 8 nearest rows over [0, 256) of the unreliable queries (fir_gemm_search_topk_keys_dev) are re-evaluated in the
+ *                 arithmetic of :173-174, first minimum by (value, row); the answer stands when the 8th row's distance, lowered by
+ *                 2^-14 (relative), is still above the winner's value -- no row outside the 8 can then win or tie. A query without
+ *                 that certificate (duplicated rows, fewer than 8 rows) is answered by the launch-per-stage form.
+ * The call costs the fp16 copies of the two feature prefixes (0.5 x their bytes each; with d == 256 the second is the whole-row
+ * state) and synchronises the handle's stream a few times per 32768 queries. fir_twd_last_dispatch then reports classifier 0,
+ * planned_fused 0, fused_launches 0, kernel "" and staged_batches = the batches of queries handed to the launch-per-stage form.
+ * Types 1 and 2 keep the forms above: their secondBestDist depends on the scan order (:123-126).
+ *
+ * What the most recent fir_twd_conventional call on this handle did with the matrix cores (host memory, no device access):
+ * out[0] queries the matrix-core form took (0: the call was not routed), out[1] of them reliable after stage 1,
+ * out[2] unreliable ones answered by the matrix-core second stage, out[3] queries inside the threshold band,
+ * out[4] second-stage queries not certified, out[5] stage-1 queries the class call's own exact scan answered.
+ * out[3] and out[4] are the queries that went to the launch-per-stage form. FIR_ERR_ARG for a NULL argument. */
+int fir_twd_last_mfma(fir_gallery* g, int64_t out[6]);
 
 /* ---- double-precision classifiers (qt_cpp/classification.cpp) ---------------------------------
  * The training set of KNNClassifier / PNNClassifier (classification.cpp:116-226): train_rows[nt][d]
