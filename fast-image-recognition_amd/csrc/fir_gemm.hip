@@ -1435,6 +1435,8 @@ static fir_x_fn pick_x(int mode, bool streamed, bool odd, int dbg = 0, int njb =
             case 7: return k_gemm_proxy_f16x<3, 0, 0, 7>;
             case 512: return k_gemm_proxy_f16x<3, 0, 0, 512>;   // (not a wrong-answer form: the L2 touch two units ahead by one workgroup in sixteen)
             case 256: return k_gemm_proxy_f16x<3, 0, 0, 256>;   // (not a wrong-answer form: timestamps of workgroup 0's load bursts, FIR_GEMM_DUMP_PHASES)
+            case 128: return k_gemm_proxy_f16x<3, 0, 0, 128>;   // (not a wrong-answer form: wave w owns row blocks w, w + 8, ... of the range, for A/B runs)
+            case 384: return k_gemm_proxy_f16x<3, 0, 0, 384>;   // ... with the timestamps
             case 64: return k_gemm_proxy_f16x<3, 0, 0, 64>;     // (not a wrong-answer form: the gallery pieces one behind each MFMA pair of a unit's first step)
             case 33: return k_gemm_proxy_f16x<3, 0, 0, 33>;     // no MFMAs, no epilogue: the gallery stream + the query-fragment re-reads
             case 37: return k_gemm_proxy_f16x<3, 0, 0, 37>;     // ... the gallery stream alone
@@ -2043,6 +2045,9 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
         if (FILE* f = std::fopen(m->dump_phases.c_str(), "w")) {
             for (int w = 0; w < 8; ++w)
                 for (int u = 0; u < 240; ++u) std::fprintf(f, "%d %d %llu %llu\n", w, u, h[(size_t)w * 256 + u] >> 20, h[(size_t)w * 256 + u] & 0xFFFFFull);
+            // the end of every wave's walk: units walked, s_memtime at the kernel's entry, behind the row loop, behind the workgroup's flush
+            for (int w = 0; w < 8; ++w)
+                std::fprintf(f, "# end %d %llu %llu %llu %llu\n", w, h[(size_t)w * 256 + 240], h[(size_t)w * 256 + 241], h[(size_t)w * 256 + 242], h[(size_t)w * 256 + 243]);
             std::fclose(f);
         }
     }

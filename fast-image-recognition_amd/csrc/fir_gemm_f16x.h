@@ -124,7 +124,8 @@ constexpr int kXStage = 16;             // staged appends per query and workgrou
 // of the fp16 fragments at the rate the memory system gives (the tile's layout in LDS and in `qh` is unchanged).
 // DBG (timing experiments only, FIR_GEMM_DBG_SKIP; own instantiations so that the production kernels' register allocation is not
 // touched -- as runtime flags the two tests made the row loop spill): bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no
-// re-read of the query fragments, bit 5 = no MFMAs. The answers of such a kernel are wrong.
+// re-read of the query fragments, bit 5 = no MFMAs. The answers of such a kernel are wrong. (Right answers, for A/B runs: bit 7 = static
+// ownership of the row blocks, bit 8 = timestamps of workgroup 0's waves.)
 template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8>
 __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* qh,
                                                                     const float* __restrict__ qinv, int64_t n, int64_t row_begin, int64_t row_end,
@@ -174,6 +175,15 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // the value of an OLDER (larger) T: harmless -- any T the pass ever held is >= the final one, so whatever fails the test against
     // it has a proxy >= fl(T_final - |q|^2), the bound the certificate is given
     __shared__ float tq_s[kAdapt ? 2 * kQT : 1];
+    // The shared form of the resident adaptive passes hands its row blocks out at run time (`next_blk`, below); everything else --
+    // the streamed ring (a barrier per unit: every wave has to walk the same units), the sample pass (its subsets go by wave), MODE 1 --
+    // keeps the static ownership. These forms know the shared form only (every caller launches them with share >= 1 and gridDim.y == 1,
+    // where share <= 0 means the same as 1: it is taken as 1). DBG & 128: the static ownership, for A/B runs.
+    constexpr bool kDynForm = !STREAMED && kAdapt && !(DBG & 128);
+    if (kDynForm && share <= 0) share = 1;
+    __shared__ int next_blk;
+    unsigned long long t_entry = 0;                   // (DBG & 256)
+    if (DBG & 256) t_entry = __builtin_amdgcn_s_memtime();
     int pair_of_wg = (int)blockIdx.y;
     int64_t rg_first = blockIdx.x, rg_step = gridDim.x, rg_last = -1;
     int range = (int)blockIdx.x;
@@ -216,6 +226,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         tau_s[threadIdx.x] = MODE == 1 ? tau[threadIdx.x] : MODE == 3 ? __uint_as_float(atomicMin(&smin[threadIdx.x], 0xFFFFFFFFu)) : 0.f;    // (MODE 3: an atomic, see the refresh below)
         qinv_s[threadIdx.x] = qinv[threadIdx.x];
         if (kAppend) scnt[threadIdx.x] = 0;
+        if (kDynForm && threadIdx.x == 0) next_blk = wpb;          // (published by the barrier behind the tile's staging)
         if (kAdapt) {
             qn_s[threadIdx.x] = sample[threadIdx.x];
             win_s[threadIdx.x] = tau[threadIdx.x];
@@ -229,13 +240,26 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // query blocks). Resident tiles only (the streamed ring's slots and its vmcnt(12) are sized for eight pieces).
     constexpr int RING = (!STREAMED && NJB < 8) ? 2 * kRing : kRing;
     const int units = dk16 / RING;
-    const int64_t rg_end = rg_last >= 0 ? rg_last : nrg;
+    int64_t rg_end = rg_last >= 0 ? rg_last : nrg;
     int64_t rg = rg_first;
     if (rg >= rg_end) return;                        // uniform per workgroup
+    // Dynamic hand-out (the shared form of kDynForm): the two waves of a SIMD do not share the matrix pipe evenly -- the older one
+    // walks at 1.4 times the pace of the younger (profiles/r04_wave_phases.txt) -- so with an equal share of the range's row blocks
+    // each the older four were done while the younger four still had a quarter of theirs, and the workgroup ran one wave per SIMD,
+    // with nobody to hide the deferred epilogue, to the end of every launch (profiles/top1_wave_balance.txt). The range's row blocks
+    // are counted one by one here (`rg` is a row BLOCK, not a group of wpb); wave w starts with block w of the range -- every wave has
+    // a first block, the warm-up rule and its barrier stay uniform -- and takes every further one from `next_blk`, in ascending order:
+    // the workgroups that share the range still walk it together.
+    const int64_t blk0 = rb_begin + rg_first * wpb;         // (kDynForm: `rg` is the row block of the pass itself)
+    if (kDynForm) {
+        rg = blk0 + wave;
+        rg_end = rb_begin + rg_end * wpb;
+    }
 #define FIR_X_LD(P) (nt ? ld_nt(P) : *(P))
     // (wave-uniform block pointers: the lane index is added in the load itself, so that the loads take the scalar-base form --
     // one 32-bit lane offset register instead of a 64-bit address per pointer)
-#define FIR_X_BLOCK(RG) (gh + (size_t)(((rb_begin + (RG) * wpb + wave) < rb_end ? (rb_begin + (RG) * wpb + wave) : rb_end - 1) * rbs) * dk16 * 64)
+#define FIR_X_RBP(RG) (kDynForm ? (RG) : rb_begin + (RG) * wpb + wave)
+#define FIR_X_BLOCK(RG) (gh + (size_t)((FIR_X_RBP(RG) < rb_end ? FIR_X_RBP(RG) : rb_end - 1) * rbs) * dk16 * 64)
     const uint4* a_cur = FIR_X_BLOCK(rg);
     uint4 cur[RING], nxt[RING];
 #pragma unroll
@@ -380,7 +404,13 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         const bool warm_it = warm;                        // this wave's first row block: T is still what it was preset to
         warm = false;
         rg_next = rg + rg_step;
-        const int64_t rbp = rb_begin + rg * wpb + wave;   // row block of the pass ...
+        if (kDynForm) {
+            // the block after this one: ONE lane asks, a row block ahead of the burst that needs its address (this block's last unit)
+            int tk = 0;
+            if (lane == 0) tk = atomicAdd(&next_blk, 1);
+            rg_next = blk0 + __builtin_amdgcn_readfirstlane(tk);
+        }
+        const int64_t rbp = FIR_X_RBP(rg);                // row block of the pass ...
         const int64_t rb = rbp * rbs;                     // ... and of the gallery
         const bool active = rbp < rb_end;
         const int64_t rgn = rg_next;
@@ -693,15 +723,19 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             continue;
         }
         // a block that straddles the end of the rows (or of the sample): row by row
+        int ls = lane;
+        // (kDynForm: the lane index from the hardware, as in check_jb -- from `lane` the compiler built this path's eight list addresses
+        // in front of the row loop and spilled them)
+        if (kDynForm) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ls));
 #pragma unroll
         for (int jb = 0; jb < NJB; ++jb) {
-            const int q = jb * 16 + (lane & 15);
+            const int q = jb * 16 + (ls & 15);
             const float m2 = 2.0f * qinv_s[q];
             const float tq = kAdapt ? tq_s[q] : tau_s[q];
             float mn = __builtin_huge_valf();
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int64_t row = rb * 32 + 16 * (i >> 2) + 4 * (lane >> 4) + (i & 3);
+                const int64_t row = rb * 32 + 16 * (i >> 2) + 4 * (ls >> 4) + (i & 3);
                 if (row >= n || (MODE != 2 && (row < row_begin || row >= row_end))) continue;
                 const float p = __builtin_fmaf(-m2, acc[i >> 2][jb][i & 3], gnorm[row]);
                 if (MODE == 0) {
@@ -724,6 +758,13 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 else if (lane < 16 && mn < __builtin_huge_valf()) atomicMin(&smin_blk[q], fir::f32_orderable(mn));     // (a straddling block: one subset takes its minimum)
             }
         }
+    }
+    if ((DBG & 256) && blockIdx.x == 0 && lane == 0) {
+        // (the end of the wave's walk: units walked, the kernel's entry and now -- slots 240.. of the wave's 256)
+        unsigned long long* dst = lists + (size_t)(2 * kQT - 1) * kListCap + 2048 + (size_t)wave * 256;
+        dst[240] = (unsigned long long)dbg_units;
+        dst[241] = t_entry;
+        dst[242] = __builtin_amdgcn_s_memtime();
     }
     if (kDefer && pend) {
         // the last full row block of this wave (no first step followed it); check_jb is the row loop's lambda -- the same code, here
@@ -773,6 +814,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             }
         }
     }
+    if ((DBG & 256) && blockIdx.x == 0 && lane == 0)      // (... and the workgroup's end: behind the flush of the staged appends)
+        lists[(size_t)(2 * kQT - 1) * kListCap + 2048 + (size_t)wave * 256 + 243] = __builtin_amdgcn_s_memtime();
     if (MODE == 2 && !sub_stride) {
 #pragma unroll
         for (int jb = 0; jb < NJB; ++jb) {
@@ -783,6 +826,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         }
     }
 #undef FIR_X_BLOCK
+#undef FIR_X_RBP
 #undef FIR_X_LD
 }
 
