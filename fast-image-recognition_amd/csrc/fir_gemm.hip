@@ -1391,6 +1391,9 @@ static void gemm_read_knobs_(fir_gemm* m) {
 constexpr int kShareMax = 16, kShareStreamed = 8;
 // fp16: rows longer than the 512 features whose 128-query tile fits LDS take the kernels that stream the query slabs (STREAMED = 1)
 static bool gemm_streamed_(const fir_gemm* m) { return m->dk16 > kSlabH; }
+// fp16: units (of kRing pieces) per row block as the kernels' ODD has them -- 0 = an even number, 1 = an odd one from three on, 2 = ONE
+// unit. Every launch of a 16-row kernel takes its form from here: an ODD = 1 kernel walks a first, a middle and a last unit at least.
+static int gemm_odd_(const fir_gemm* m) { return m->dk16 == kRing ? 2 : (m->dk16 / kRing) & 1; }
 // pairs of passes the next launch takes: the largest power of two within what is left and within cap
 static int launch_pairs_(int left, int cap) {
     int P = 1;
@@ -1398,7 +1401,7 @@ static int launch_pairs_(int left, int cap) {
     return P;
 }
 
-// The 16-row kernels by (mode, query slabs streamed, odd number of units per row block, live query blocks): ONE table gives the
+// The 16-row kernels by (mode, query slabs streamed, units per row block: 0 = even, 1 = odd, 2 = one, live query blocks): ONE table gives the
 // function and the name fir_gallery_last_dispatch reports for it.
 typedef void (*fir_x_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int64_t, int64_t, int, const float*, unsigned long long*, int*, float*,
                          int, int, int, int, unsigned int*, int);
@@ -1413,18 +1416,24 @@ static const fir_x_entry kXTable[] = {
     FIR_X(1, 0, 0), FIR_X(1, 0, 1), FIR_X(1, 1, 0), FIR_X(1, 1, 1), FIR_X(2, 0, 0), FIR_X(2, 0, 1), FIR_X(2, 1, 0), FIR_X(2, 1, 1),
     FIR_X(3, 0, 0), FIR_X(3, 0, 1), FIR_X(3, 1, 0), FIR_X(3, 1, 1), FIR_X(4, 0, 0), FIR_X(4, 0, 1), FIR_X(4, 1, 0), FIR_X(4, 1, 1),
     FIR_X_FEW(0, 1), FIR_X_FEW(1, 1), FIR_X_FEW(0, 2), FIR_X_FEW(1, 2),     // a call of <= 16 / <= 32 queries (top-1, threshold found on the way)
+    FIR_X(1, 0, 2), FIR_X(2, 0, 2), FIR_X(3, 0, 2), FIR_X(4, 0, 2),         // one unit per row block (at most 128 features; resident by definition)
 };
 #undef FIR_X
 #undef FIR_X_FEW
 // mode: 1 = append below tau, 2 = the sample pass, 3 / 4 = the threshold found on the way (top-1 / the K nearest); njb < 8 exists for
 // mode 3 with an even number of units only, anything else takes the whole tile
-static const fir_x_entry& find_x(int mode, bool streamed, bool odd, int njb = 8) {
-    if (!(mode == 3 && !odd && (njb == 1 || njb == 2))) njb = 8;
+static const fir_x_entry* lookup_x(int mode, bool streamed, int odd, int njb) {
     for (const fir_x_entry& e : kXTable)
-        if (e.mode == mode && e.streamed == (int)streamed && e.odd == (int)odd && e.njb == njb) return e;
-    return kXTable[4 + 2 * (int)streamed + (int)odd];      // (not a mode: as the sample pass)
+        if (e.mode == mode && e.streamed == (int)streamed && e.odd == odd && e.njb == njb) return &e;
+    return nullptr;
 }
-static fir_x_fn pick_x(int mode, bool streamed, bool odd, int dbg = 0, int njb = 8) {
+static const fir_x_entry& find_x(int mode, bool streamed, int odd, int njb = 8) {
+    if (!(mode == 3 && !odd && (njb == 1 || njb == 2))) njb = 8;
+    if (const fir_x_entry* e = lookup_x(mode, streamed, odd, njb)) return *e;
+    if (const fir_x_entry* e = lookup_x(2, streamed, odd, 8)) return *e;       // (not a mode: as the sample pass, which the table has for every shape)
+    return *lookup_x(2, false, 0, 8);                                          // (not a shape either: the sample pass of the even resident form)
+}
+static fir_x_fn pick_x(int mode, bool streamed, int odd, int dbg = 0, int njb = 8) {
 #ifdef FIR_AUDIT      // (the timing forms are instantiated in the audit build only: the shipped library cannot select them)
     if (dbg && mode == 3 && !streamed && !odd) {       // timing experiments (FIR_GEMM_DBG_SKIP): wrong answers
         switch (dbg & 1023) {
@@ -1726,7 +1735,7 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
         hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, m->dk16, (const float*)m->sc_qmul,
                            m->sc_qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
         // one pair over all CUs (share = 1: 256 row ranges), the gallery stream read once (nt)
-        hipLaunchKernelGGL(pick_x(1, streamed, (m->dk16 / kRing) & 1), dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
+        hipLaunchKernelGGL(pick_x(1, streamed, gemm_odd_(m)), dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
                            (int64_t)0, n, m->dk16, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
                            (unsigned int*)m->fb_state, off);
         const RerankFb fb = {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off};
@@ -1777,7 +1786,8 @@ struct GemmCall {
     // a call of ONE super-batch whose preparation runs on `st` has nothing to put under anything: its re-rank follows its pass on `st`
     // as well -- every hop to the side stream and back is 10-12 us of a 300-us call
     bool one_stream;
-    bool streamed, odd;         // fp16: gemm_streamed_, an odd number of units per row block
+    bool streamed;              // fp16: gemm_streamed_
+    int odd;                    // fp16: units per row block -- 0 = an even number, 1 = an odd one, 2 = one unit (the kernels' ODD)
     size_t lds;                 // f32 / bf16: dynamic LDS of the pass kernels
 
     int sb_queries(int sb) const { return std::min(sbq, qb - sb * sbq); }
@@ -2121,7 +2131,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
         return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
                       : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
     c.streamed = gemm_streamed_(m);
-    c.odd = (m->dk16 / kRing) & 1;
+    c.odd = gemm_odd_(m);
     c.lds = m->precision == FIR_GEMM_F32 ? (size_t)(kQT / 32) * std::min(m->dq8, kSlab8) * 64 * sizeof(float4)
                                          : (size_t)(kQT / 32) * std::min(m->dk16, kSlab16) * 128 * sizeof(uint4);
     // fp16: both operands rounded to 11 bits -> |q~.g~ - q.g| <= (2^-10 + 2^-22) sum|q_k g_k| + the sub-normal tails

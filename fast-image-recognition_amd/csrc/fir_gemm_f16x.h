@@ -90,7 +90,9 @@ __global__ void __launch_bounds__(256) k_gemm_pack_queries_f16x(const float* q, 
 // step: one memory latency per k-block -- measured 358 us per pass against 158 us of gallery stream.)
 // ODD = units (of kRing pieces) per row block is odd: only then do the two gallery buffers end a row block in swapped roles
 // and need a copy; with the even form compiled separately the common row lengths (256, 512, 1280 features) carry neither the
-// copy nor the merge point the compiler hung an s_waitcnt vmcnt(0) on.
+// copy nor the merge point the compiler hung an s_waitcnt vmcnt(0) on. ODD = 1: three units or more; ODD = 2: ONE unit (at most 128
+// features), which is the row block's first and last unit at once -- a form of its own, so that every kernel's row loop is one
+// sequence of units (as two run-time paths inside the ODD = 1 kernels it cost those 500 bytes of scratch per lane).
 // MODE 0: one minimum per (row block, query) of rows [row_begin, row_end) -> sample (the order-statistic flow, k_gemm_tau; not
 // instantiated any more: the 16-row kernels always run the smallest-proxy flow);
 // MODE 3: the full pass with the threshold found ON THE WAY (top-1; no sample pass, no threshold kernel): per query the ranks
@@ -116,8 +118,9 @@ __global__ void __launch_bounds__(256) k_gemm_pack_queries_f16x(const float* q, 
 // the next step right behind the two MFMAs that used it, fourteen MFMAs before its next use.
 // `nt_flags` bit 0: the gallery stream is read once per launch (non-temporal loads; pairs that share it use ordinary loads, so that
 // the line stays in L2 for the other readers). Bits 2, 3: the audit build's looser adaptive bound (no refresh / no exchange).
-// Bits 1, 4, 5, 6 belonged to experiments that were measured and not kept (partner waves staggered by half a unit or half a row
-// block, s_setprio around the MFMA phase, all eight proxies of every query block: DESIGN.md section 4, "The 16-row kernels") -- every caller passes 0.
+// No other bit is read: the experiments that bits 1, 4, 5 and 6 once switched (partner waves staggered by half a unit or half a row
+// block, s_setprio around the MFMA phase, all eight proxies of every query block: DESIGN.md section 4, "The 16-row kernels") were
+// measured, not kept, and their run-time tests are gone from the row loop.
 constexpr int kXStage = 16;             // staged appends per query and workgroup
 // NJB: query blocks of 16 the wave multiplies against (8 = the whole 128-query tile). A call of at most 16 / 32 queries fills one / two
 // blocks; with NJB = 1 / 2 the pass does an eighth / a quarter of the MFMAs and LDS reads and is what such a call should be: one read
@@ -265,7 +268,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
     for (int u = 0; u < RING; ++u) cur[u] = FIR_X_LD(a_cur + (size_t)u * 64 + lane);
     constexpr int kUnitsPerSlab = kSlabH / RING;                         // units of the LDS-resident tile (512 features)
-    const bool resident = !STREAMED;                                      // (the caller streams whatever does not fit: dk16 > kSlabH)
+    // (the caller streams whatever does not fit: dk16 > kSlabH)
     // STREAMED (rows longer than the 512 features whose 128-query tile fits LDS): the query fragments go through a ring of FOUR
     // 32-KiB LDS slots of one unit (four steps x eight query blocks) each. Units are numbered c = 0, 1, 2, ... over the whole walk of
     // the workgroup (slab of unit c: c mod units); slot c & 3 holds unit c. The slab of unit c + 3 is requested DURING unit c -- this
@@ -309,15 +312,6 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     uint4 B[NJB];                                    // the fragments of the first step of the first unit (slot 0 / the resident tile's start)
 #pragma unroll
     for (int j = 0; j < NJB; ++j) B[j] = lqx[lane + j * 64];
-    if (NJB == 8 && (nt_flags & 2) && resident && wave >= wpb / 2) {
-        // half a unit of MFMAs whose result goes nowhere the kernel's outputs are computed from: it only delays this wave
-        f32x4 junk = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 32; ++r) junk = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(B[r & (NJB - 1)]), as_f16x8(B[(r + 1) & (NJB - 1)]), junk, 0, 0, 0);
-        if (nt_flags & 32)                               // (half a row block at 512 features instead of half a unit)
-            for (int r = 0; r < 96; ++r) junk = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(B[r & (NJB - 1)]), as_f16x8(B[(r + 1) & (NJB - 1)]), junk, 0, 0, 0);
-        asm volatile("" ::"v"(junk));
-    }
     // The append forms DEFER a full row block's epilogue into the next row block's first step: the first step's MFMAs start the sums
     // from a zero C operand, so query block j's sixteen sums stay readable until the two MFMAs of index j of that step overwrite
     // them -- the check of query block j (four v_max3, an fma, a compare; rarely the eight proxies and an append) sits right in
@@ -325,11 +319,19 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // alone, waits for its own LDS reads (profiles/r03_gemm_time_decomposition.txt: the epilogue cost 0.18 of 1.56 ms). DBG & 8: the
     // epilogue where it was, for A/B runs.
     constexpr bool kDefer = kAppend && !(DBG & 8) && !(DBG & 1);
-    f32x4 acc[2][NJB];                               // (first written by the MFMAs of a row block's first step, against a zero C operand)
-    bool pend = false;                               // a full row block's checks are still owed
+    f32x4 acc[2][NJB];                               // (written by the MFMAs of a row block's first step, against a zero C operand)
+    if (kDefer) {                                    // (a wave's first first step reads them, against p_gmin = +inf: see `pend`)
+#pragma unroll
+        for (int j = 0; j < NJB; ++j) acc[0][j] = acc[1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // `pend`: a full row block's checks are still owed. The first step does NOT test it: what it is given when nothing is owed -- a
+    // wave's first row block, the block behind one that was not full -- is p_gmin = +inf, against which the check's lower bound is
+    // +inf or NaN and below no bound at all, so the check of a query block is the same seven instructions either way and carries no
+    // scalar test (the sums it then reads are zeros or a block's nobody needs). `pend` itself is read behind the row loop only.
+    bool pend = false;
     int64_t p_rb = 0;
     float4 pg[2] = {};
-    float p_gmin = 0.f;
+    float p_gmin = __builtin_huge_valf();
     float m2r[kDefer ? NJB : 1], tqr[kDefer ? NJB : 1];  // per query block of this lane: 2 / scale, and the bound as of the last row block's end
     if (kDefer) {
 #pragma unroll
@@ -404,17 +406,26 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         const bool warm_it = warm;                        // this wave's first row block: T is still what it was preset to
         warm = false;
         rg_next = rg + rg_step;
-        if (kDynForm) {
-            // the block after this one: ONE lane asks, a row block ahead of the burst that needs its address (this block's last unit)
-            int tk = 0;
-            if (lane == 0) tk = atomicAdd(&next_blk, 1);
-            rg_next = blk0 + __builtin_amdgcn_readfirstlane(tk);
-        }
+        // kDynForm, the block after this one: ONE lane asks here, a row block ahead of the burst that needs its address, and the answer
+        // is taken where that burst is issued -- at the head of this block's last unit (`next_block`). Taken here it was waited for
+        // here: an s_waitcnt lgkmcnt(0) at the head of every row block, i.e. behind the query fragments the last step had just
+        // re-read for the first step. Three units later the answer has long landed.
+        // (atomicInc, not atomicAdd: the compiler rewrites an add for a whole wave -- count the active lanes, one lane adds, the
+        // result goes through v_readfirstlane right behind the atomic -- which puts the wait back here for an "optimisation" of one lane.
+        // With a limit of 2^32 - 1 the increment is the add.)
+        int tk = 0;
+        if (kDynForm && lane == 0) tk = (int)atomicInc((unsigned int*)&next_blk, 0xFFFFFFFFu);
         const int64_t rbp = FIR_X_RBP(rg);                // row block of the pass ...
         const int64_t rb = rbp * rbs;                     // ... and of the gallery
         const bool active = rbp < rb_end;
-        const int64_t rgn = rg_next;
-        const uint4* a_nxt = FIR_X_BLOCK(rgn < rg_end ? rgn : rg);
+        const uint4* a_nxt = a_cur;                       // (the next block's fragments: set by next_block)
+        auto next_block = [&]() {
+            if (kDynForm) rg_next = blk0 + __builtin_amdgcn_readfirstlane(tk);
+            const int64_t rgn = rg_next;
+            a_nxt = FIR_X_BLOCK(rgn < rg_end ? rgn : rg);
+        };
+        constexpr bool kNextLate = kDynForm && !(DBG & 512);   // (DBG & 512 reads a_nxt two units ahead)
+        if (!kNextLate) next_block();
         if (kAdapt) {
             if (!warm_it && wave < NJB && !(nt_flags & 4)) {
                 // What the other workgroups have reached since. Only ATOMICS read `smin`: they execute at the memory side, so what they
@@ -425,9 +436,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 // registers that spills), on a schedule that thins out: row blocks 2, 3, 4, 6, 8, 12, 16, 24, ... (T settles early).
                 const int v = blk_no >> __builtin_ctz((unsigned)blk_no | 0x40000000u);
                 if ((v == 1 || v == 3) && lane < 16) {
-                    int zl;                                   // (an opaque zero: keeps the addresses from being hoisted out of the row loop and spilled)
-                    asm volatile("v_mov_b32 %0, 0" : "=v"(zl));
-                    const int ql = 16 * wave + lane + zl;
+                    int zl;                                   // (the lane index from the hardware, as in check_jb: keeps the addresses from being hoisted out of the row loop and spilled)
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(zl));
+                    const int ql = 16 * wave + zl;
                     if (kSlots) {
                         // (all eight round trips in flight together: one after the other they cost a refresh eight memory latencies)
                         unsigned int mine[8], old[8];
@@ -450,6 +461,14 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             ++blk_no;
         }
         float4 gns[2];                               // squared norms of rows 16 s + 4 (lane >> 4) + 0..3 of the block
+        // Where the block's last unit reads them from -- ALWAYS, whether the block is full or not (see `unit`), so the 32 floats have to
+        // lie inside an allocation for every block a wave can walk: a straddling one, one past the end of the range, a sample block
+        // (rb = rbp * rbs). `gnorm` holds exactly max(n, 1) floats -- nothing behind row n - 1 -- so it is the CLAMP that makes the
+        // access safe, not the allocation: the window starts at min(32 rb, (n - 32) & ~3) (a multiple of four floats: the loads stay
+        // 16-byte aligned), which is 32 rb itself for every full block (32 rb + 32 <= n). With fewer than 32 rows there is no such
+        // window in `gnorm` at all (and no full block): the loads then read the head of the fp16 fragments, one row block = dk16 KiB
+        // >= 8 KiB that every gallery has. The values are used under `full_block` only.
+        const float* gn_blk = n >= 32 ? gnorm + (rb * 32 < ((n - 32) & ~(int64_t)3) ? rb * 32 : ((n - 32) & ~(int64_t)3)) : (const float*)gh;
         const bool full_block = active && rbp * 32 >= row_begin && rbp * 32 + 32 <= row_end && rb * 32 + 32 <= n && (MODE != 0 || rb * 32 + 32 <= sample_rows);
         // MODE 2, sub_stride: eight positions x eight waves = kRtSubsets disjoint subsets of the sampled rows (below)
         unsigned int* smin_blk = MODE == 2 ? smin + (size_t)(wave & 7) * sub_stride : nullptr;       // (position 0's subset of this wave)
@@ -461,17 +480,17 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             // fragments just requested for the next step; a bound that is a row block old is a larger one: it appends more, never less)
             const float m2 = kDefer ? m2r[jb] : 2.0f * qinv_s[q];
             const float tq = kDefer ? tqr[jb] : kAdapt ? tq_s[q] : tau_s[q];
-            if (!(nt_flags & 64)) {
-                // with m2 > 0, fl(gmin - m2 amax) <= fl(gn_r - m2 acc_r) for every row r of the lane (gmin <= gn_r, amax >= acc_r, rounding is
-                // monotone): `lb >= tq` proves that no row of the block is appended -- seven instructions instead of sixteen. NaN sums never
-                // enter amax, as they never enter the minimum below. (v_max3_f32 by hand: fmaxf() on MFMA results quiets every operand first.)
-                float amax;
-                asm("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %0, %0, %6, %7\n\tv_max_f32 %0, %0, %8"
-                    : "=&v"(amax)
-                    : "v"(acc[0][jb][0]), "v"(acc[0][jb][1]), "v"(acc[0][jb][2]), "v"(acc[0][jb][3]), "v"(acc[1][jb][0]), "v"(acc[1][jb][1]),
-                      "v"(acc[1][jb][2]), "v"(acc[1][jb][3]));
-                if (!(__builtin_fmaf(-m2, amax, gminq) < tq)) return;
-            }
+            // with m2 > 0, fl(gmin - m2 amax) <= fl(gn_r - m2 acc_r) for every row r of the lane (gmin <= gn_r, amax >= acc_r, rounding is
+            // monotone): `lb >= tq` proves that no row of the block is appended -- seven instructions instead of sixteen. NaN sums never
+            // enter amax, as they never enter the minimum below. (v_max3_f32 by hand: fmaxf() on MFMA results quiets every operand first.)
+            // Everything behind the test is the rare path: marked unlikely, so that it is laid out of line and the common path falls
+            // through into the query block's MFMAs.
+            float amax;
+            asm("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %0, %0, %6, %7\n\tv_max_f32 %0, %0, %8"
+                : "=&v"(amax)
+                : "v"(acc[0][jb][0]), "v"(acc[0][jb][1]), "v"(acc[0][jb][2]), "v"(acc[0][jb][3]), "v"(acc[1][jb][0]), "v"(acc[1][jb][1]),
+                  "v"(acc[1][jb][2]), "v"(acc[1][jb][3]));
+            if (__builtin_expect(!(__builtin_fmaf(-m2, amax, gminq) < tq), 1)) return;
             const float gnv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
             float pv[8];
             float mn = __builtin_huge_valf();
@@ -510,9 +529,28 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 if (kAdapt) lower_T(qr, pv, mn);
             }
         };
-        auto unit = [&](uint4 (&C)[RING], uint4 (&N)[RING], int h, auto first_tag) {
+        // RULE of the row loop: on its common path there must be no vector-memory operation that some other path into the same unit
+        // head lacks. The compiler's wait at a unit head -- "all but the N youngest vector-memory operations have returned" -- has to
+        // hold on every path that joins there, so it takes the smallest N of them; an operation that only SOME paths issue behind a burst
+        // makes the head's wait, on the paths that have it, reach into the burst issued a few instructions earlier: a whole memory round
+        // trip with nothing to wait for. (The row norms used to be loaded under `h == units - 1 && full_block`: once per row block every
+        // wave stood still for it -- profiles/top1_last_unit.txt.) Hence the last unit is a compile-time place (`last_tag`; the unit
+        // sequences below peel it) and loads the norms unconditionally.
+        auto unit = [&](uint4 (&C)[RING], uint4 (&N)[RING], int h, auto first_tag, auto last_tag) {
             constexpr bool kFirst = decltype(first_tag)::value;      // the first unit of the row block: its first step starts the sums
-            const uint4* src = h + 1 < units ? a_cur + (size_t)(h + 1) * RING * 64 : a_nxt;
+            constexpr bool kLast = decltype(last_tag)::value;        // the last one: its burst is the next row block's first unit, the norms follow it
+            if (kLast && !kFirst && kDefer && kAdapt) {
+                // The bounds the NEXT row block's first step checks this block's sums against, read a unit early: in front of this unit's
+                // fragment re-reads, so that the first deferred check finds them landed instead of draining the rolling re-reads to get
+                // at the last LDS operations in front of it. A bound that is one unit older is a larger one (T only ever falls): it
+                // appends more, never less, and what is not appended still has a proxy >= fl(T_final - |q|^2). (A one-unit row block
+                // checks against these registers in this very unit: it refreshes them behind its steps, below. A wave's warm-up block
+                // reads them again behind the exchange: what stands in tq_s before it is the preset.)
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
+            }
+            if (kLast && kNextLate) next_block();
+            const uint4* src = kLast ? a_nxt : a_cur + (size_t)(h + 1) * RING * 64;
             const uint4* bq = STREAMED ? lqx + lane + (size_t)(ring_c & 3) * 4 * RING * 64 : lqx + lane + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64;
             // The next unit's eight gallery pieces are requested in one burst in front of the unit. (DBG & 16, measured and not kept: two per
             // step, behind the fourth and the eighth pair of MFMAs -- every piece still exactly one unit before its use -- ran 6 % slower at
@@ -548,18 +586,22 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 }
                 ++dbg_units;
             }
-            if (h == units - 1 && full_block) {
+            if (kLast) {
+                // the block's row norms, directly behind the burst and on every path (the rule above; gn_blk is always readable)
                 // (wave-uniform base + a lane offset made here: hoisted out of the row loop, `gnorm + 4 (lane >> 4)` is a 64-bit register
                 // pair per lane that the K-nearest form spilled -- a scratch reload and an s_waitcnt vmcnt(0) in every row block)
                 unsigned int zl;
                 asm volatile("v_mov_b32 %0, 0" : "=v"(zl));
-                const float* gb = gnorm + rb * 32;
+                const float* gb = gn_blk;
                 const unsigned int off = 4u * ((unsigned int)lane >> 4) + zl;
                 gns[0] = *(const float4*)(gb + off);
                 gns[1] = *(const float4*)(gb + off + 16);
             }
+            // the unit's vector-memory operations stay in front of its steps: sunk behind the first MFMAs, a burst leaves the unit head's
+            // wait with nothing younger than the data it waits for, and the exact count for that is "everything"
+            __builtin_amdgcn_sched_barrier(0);
             const uint4* bq_after = STREAMED ? lqx + lane + (size_t)((ring_c + 1) & 3) * 4 * RING * 64
-                                             : lqx + lane + (size_t)((h + 1 < units ? h + 1 : 0) % kUnitsPerSlab) * RING * 4 * 64;
+                                             : lqx + lane + (size_t)((kLast ? 0 : h + 1) % kUnitsPerSlab) * RING * 4 * 64;
 #pragma unroll
             for (int t = 0; t < RING / 2; ++t) {
                 const uint4* bn = t + 1 < RING / 2 ? bq + (size_t)(t + 1) * 8 * 64 : bq_after;
@@ -567,7 +609,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
                 for (int j = 0; j < NJB; ++j) {
                     if (kDefer && kFirst && t == 0) {
-                        if (pend) check_jb(j, p_rb, pg[0], pg[1], p_gmin);      // the previous row block's sums of query block j, about to be overwritten
+                        check_jb(j, p_rb, pg[0], pg[1], p_gmin);      // the previous row block's sums of query block j, about to be overwritten (nothing owed: p_gmin = +inf)
                     }
                     const f16x8 b = as_f16x8(B[j]);
                     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -591,33 +633,61 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 if (STREAMED) request_piece(hq3, (ring_c + 3) & 3, t);      // unit ring_c + 3's slab, into the slot unit ring_c - 1 has left
             }
             if (STREAMED) {
+                // vmcnt(12): all but the twelve youngest vector-memory operations have returned. Younger than this wave's pieces of unit
+                // ring_c + 2 (requested during the unit before this one) are this unit's eight gallery loads and four requests -- twelve --
+                // and, in a row block's last unit, the two norm loads behind the burst: fourteen. The count is the same 12 there: the pieces
+                // are older than all fourteen, so they have landed a fortiori, and what the wait asks for beyond them is the first two
+                // loads of a burst issued a whole unit (64 MFMAs) earlier. (12 there on purpose, not the exact 14: one instruction text for
+                // every unit of the ring, and a wait that asks for loads a unit old costs nothing that has been measured; vmcnt(14) in the
+                // last unit was not measured.)
                 asm volatile("s_waitcnt vmcnt(12)" ::: "memory");          // this wave's pieces of unit ring_c + 2 have landed ...
                 __builtin_amdgcn_s_barrier();                               // ... and everyone's: published
                 ++ring_c;
                 hq3 = hq3 + 1 == units ? 0 : hq3 + 1;
             }
-        };
-        if (nt_flags & 16) __builtin_amdgcn_s_setprio(2);       // (experiment: the wave in its MFMA phase goes ahead of its partner's epilogue)
-        if (!ODD) {
-            unit(cur, nxt, 0, std::true_type());
-            pend = false;
-            unit(nxt, cur, 1, std::false_type());
-            for (int h = 2; h < units; h += 2) {
-                unit(cur, nxt, h, std::false_type());
-                unit(nxt, cur, h + 1, std::false_type());
+            if (kLast && kFirst && kDefer && kAdapt) {                      // (a one-unit row block: see the unit's head)
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
             }
-        } else {
-            unit(cur, nxt, 0, std::true_type());
-            pend = false;
+            if (kFirst) {                                                   // the checks are done: nothing is owed until this block's end says so
+                pend = false;
+                p_gmin = __builtin_huge_valf();
+            }
+        };
+        // first unit, the middle units two by two, the peeled last unit (an even number of units: at least two, no middle with two; an odd
+        // number: three or more have the one middle unit that pairs up with nothing in front of the last; ODD = 2: the one unit is both)
+        const std::true_type yes;
+        const std::false_type no;
+        if (!ODD) {
+            unit(cur, nxt, 0, yes, no);
             for (int h = 1; h + 1 < units; h += 2) {
-                unit(nxt, cur, h, std::false_type());
-                unit(cur, nxt, h + 1, std::false_type());
+                unit(nxt, cur, h, no, no);
+                unit(cur, nxt, h + 1, no, no);
+            }
+            unit(nxt, cur, units - 1, no, yes);
+        } else {
+            if (ODD == 2) {
+                unit(cur, nxt, 0, yes, yes);
+            } else {
+                unit(cur, nxt, 0, yes, no);
+                for (int h = 1; h + 2 < units; h += 2) {
+                    unit(nxt, cur, h, no, no);
+                    unit(cur, nxt, h + 1, no, no);
+                }
+                unit(nxt, cur, units - 2, no, no);
+                unit(cur, nxt, units - 1, no, yes);
             }
 #pragma unroll
             for (int u = 0; u < RING; ++u) cur[u] = nxt[u];         // an odd number of units: the next row block's first unit sits in nxt
         }
         a_cur = a_nxt;
-        if (nt_flags & 16) __builtin_amdgcn_s_setprio(0);
+        // (The rule of `unit` once more: the norms are used under `full_block` only; behind a block that is not full they would still be
+        // on their way when the next last unit loads into the same registers, and the wait for that would sit between its burst and its
+        // norm loads -- in the one-unit form it waited for the burst just issued. Used here on the paths that do not use them below,
+        // where the common path waits for them anyway -- under the condition, so that the wait stays out of the last unit's block. The
+        // one-unit form needs it on every path: there the compiler kept the wait between burst and norm loads otherwise, and the norms
+        // of a block whose only unit has just ended are waited for right here in any case.)
+        if (ODD == 2 || !full_block) asm volatile("" ::"v"(gns[0].x), "v"(gns[0].y), "v"(gns[0].z), "v"(gns[0].w), "v"(gns[1].x), "v"(gns[1].y), "v"(gns[1].z), "v"(gns[1].w));
         if (DBG & 1) {                   // (no epilogue: the sums are only kept alive)
 #pragma unroll
             for (int jb = 0; jb < NJB; ++jb) asm volatile("" ::"v"(acc[0][jb]), "v"(acc[1][jb]));
@@ -628,9 +698,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             // workgroup exchanges with `smin` -- then, still in their registers, for the block's checks like any other block's. (Until
             // round 4 the block was WALKED twice: one row block in ~120 of a large launch, one in 15 of a one-pair launch over 1M rows.)
             if (active && full_block) {
+                int lw;                                          // (the lane index from the hardware, as in check_jb: nothing of this once-per-wave path is prepared in front of the row loop)
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lw));
 #pragma unroll
                 for (int jb = 0; jb < NJB; ++jb) {
-                    const int q = jb * 16 + (lane & 15);
+                    const int q = jb * 16 + (lw & 15);
                     const float m2 = 2.0f * qinv_s[q];
                     float pv[8];
                     float mn = __builtin_huge_valf();
@@ -657,11 +729,18 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         o = __shfl_xor(mn, 32, 64);
                         mn = o < mn ? o : mn;
                         const float tn = fmaxf((mn + qn_s[q]) + win_s[q], 0.f);     // (NaN operands: fmaxf gives 0 only if both are NaN; a NaN tn fails the test below)
-                        if (lane < 16 && tn < tau_s[q]) atomicMin((unsigned int*)&tau_s[q], __float_as_uint(tn));
+                        if (lw < 16 && tn < tau_s[q]) atomicMin((unsigned int*)&tau_s[q], __float_as_uint(tn));
                     }
                 }
             }
             exchange_T();
+            if (kDefer) {                                                    // (the last unit read the preset: the exchanged bounds)
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
+                // (used here, so waited for here, once per wave -- not by every row block's first check: see the straddling block below)
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) asm volatile("" ::"v"(tqr[jb]));
+            }
         }
         if (!active) continue;
         if (full_block) {
@@ -669,11 +748,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             if (kAppend) {
                 if (kDefer) {
                     pend = true;                                             // checked in the next row block's first step (or behind the loop)
-                    if (kAdapt) {
-#pragma unroll
-                        for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
-                    }
-                    p_rb = rb;
+                    p_rb = rb;                                               // (against tqr, which the last unit refreshed)
                     pg[0] = gns[0];
                     pg[1] = gns[1];
                     p_gmin = gmin;
@@ -723,10 +798,10 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             continue;
         }
         // a block that straddles the end of the rows (or of the sample): row by row
-        int ls = lane;
-        // (kDynForm: the lane index from the hardware, as in check_jb -- from `lane` the compiler built this path's eight list addresses
-        // in front of the row loop and spilled them)
-        if (kDynForm) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ls));
+        int ls;
+        // (the lane index from the hardware, as in check_jb -- from `lane` the compiler built this path's eight list addresses in front
+        // of the row loop and spilled them)
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ls));
 #pragma unroll
         for (int jb = 0; jb < NJB; ++jb) {
             const int q = jb * 16 + (ls & 15);
@@ -747,6 +822,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                     if (slot < kListCap) lists[(size_t)q * kListCap + slot] = fir::key_pack(p, (uint32_t)row);
                 }
             }
+            // (The rule of `unit`, for LDS: the bound is looked at under `p < tq` only; where no row of the lane gets that far, its read
+            // would still be on its way at the row loop's head, and the compiler would have the COMMON path wait for every LDS
+            // operation there -- the fragments just re-read for the first step -- before it reuses the register. Used here, it is
+            // waited for here.)
+            asm volatile("" ::"v"(tq), "v"(m2));
             if (MODE == 2 && !sub_stride) {
                 smallest[jb] = fminf(smallest[jb], mn);
             } else if (MODE != 1 && !kAdapt) {
@@ -769,8 +849,10 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     if (kDefer && pend) {
         // the last full row block of this wave (no first step followed it); check_jb is the row loop's lambda -- the same code, here
         // against the values the loop left behind
+        int lt;                                          // (the lane index from the hardware: the tail's addresses are not held across the row loop)
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lt));
         auto last_jb = [&](int jb) {
-            const int q = jb * 16 + (lane & 15);
+            const int q = jb * 16 + (lt & 15);
             const float m2 = 2.0f * qinv_s[q];
             const float tq = kAdapt ? tq_s[q] : tau_s[q];
             const float gnv[8] = {pg[0].x, pg[0].y, pg[0].z, pg[0].w, pg[1].x, pg[1].y, pg[1].z, pg[1].w};
@@ -785,7 +867,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (pv[i] < tq) {
-                        const int64_t row = p_rb * 32 + 16 * (i >> 2) + 4 * (lane >> 4) + (i & 3);
+                        const int64_t row = p_rb * 32 + 16 * (i >> 2) + 4 * (lt >> 4) + (i & 3);
                         const unsigned long long key = fir::key_pack(pv[i], (uint32_t)row);
                         const int st = atomicAdd(&scnt[q], 1);
                         if (st < kXStage) {

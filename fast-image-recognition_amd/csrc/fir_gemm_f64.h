@@ -386,7 +386,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
     const int grid = m->v.cus;
     const float e_rel = m->erel_scale * (8.0f * (float)d * 5.9604645e-8f + 9.765625e-4f * 1.0625f);
     const bool streamed = gemm_streamed_(m);
-    const bool odd = (m->dk16 / kRing) & 1;
+    const int odd = gemm_odd_(m);
     const int sbq = std::min(kPasses * kQT, std::max(1024, (qb + 1023) / 1024 * 1024));
     {
         const int need = (std::min(sbq, qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
