@@ -75,6 +75,8 @@ SYMBOLS = [
     ("fir_cls_knn_predict", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     ("fir_cls_set_knn_mfma", C.c_int, [_vp, C.c_int32]),
     ("fir_cls_knn_stats", C.c_int, [_vp, _i64p, _i64p]),
+    ("fir_cls_set_pnn_mfma", C.c_int, [_vp, C.c_int32]),
+    ("fir_cls_pnn_stats", C.c_int, [_vp, _i64p, _i64p]),
     ("fir_cls_last_dispatch", C.c_int, [_vp, C.c_char_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("fir_cls_knn_class_nearest", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     ("fir_gemm_create", C.c_int, [_vp, C.POINTER(_vp)]),
@@ -823,6 +825,14 @@ class ClsModel:
     def knn_stats(self):
         a, b = C.c_int64(), C.c_int64()
         _check(lib().fir_cls_knn_stats(self._h, C.byref(a), C.byref(b)))
+        return {"matrix_core_queries": a.value, "exact_scan_queries_of_them": b.value}
+
+    def set_pnn_mfma(self, min_queries):
+        _check(lib().fir_cls_set_pnn_mfma(self._h, min_queries))
+
+    def pnn_stats(self):
+        a, b = C.c_int64(), C.c_int64()
+        _check(lib().fir_cls_pnn_stats(self._h, C.byref(a), C.byref(b)))
         return {"matrix_core_queries": a.value, "exact_scan_queries_of_them": b.value}
 
     def last_dispatch(self):

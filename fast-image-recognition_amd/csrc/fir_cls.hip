@@ -690,6 +690,11 @@ struct fir_cls {
     int64_t mm_queries = 0, mm_unsettled = 0;         // queries that went through the matrix cores / of them sent on to the exact scan
     std::vector<int32_t> class_off_h;                 // host copy of class_off
     FirBuf km, km_meta;                               // fir_cls_kmedoids: distance tables + de-tiled rows + candidate sums / descriptors + results
+    // PNN batches on the float64 matrix cores (fir_cls_pnn_mfma.h)
+    int pm_mode = 0;                                  // fir_cls_set_pnn_mfma: 0 never, > 0 from that many queries on, -1 automatic (in this version: never)
+    FirBuf pm_ng, pm_q, pm_flags;                     // max + |g-avg|^2 per row (once per handle); query operands + norms; band flags
+    bool pm_ng_ready = false;
+    int64_t pm_queries = 0, pm_fallback = 0;          // queries that took the form / of them answered by the scan after all
 };
 
 namespace {
@@ -710,6 +715,7 @@ void cls_prof(fir_cls* c, int end, double bytes, const char* kernel) {
         (void)hipEventRecord(c->ev[c->ev_used + 1], c->stream);
         c->ev_used += 2;
         c->last_bytes = bytes;
+        c->last_flops = 0.0;              // a scan launch has no dot-product flops (the matrix-core callers set theirs after this)
         if (kernel) std::snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kernel);
     }
 }
@@ -842,6 +848,34 @@ int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
+
+// PNN of one internal batch (qb <= cls_batch, var > 0, the device current) by the exact scan
+int cls_pnn_exact(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
+    int rc = cls_scan(c, queries, qb);
+    if (rc) return rc;
+    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
+    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
+    const double denom = (double)(2 * (size_t)c->d) * var;                       // 2*num_of_cont_features*var, :213
+    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
+                       c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
+    const bool small = cls_small(c, qb);
+    int32_t* dbest = small ? cls_pin_results(c) : c->best;
+    const bool one = small && qb == 1 && !scores;       // the reference's predict() per test vector: no stream synchronisation
+    const unsigned long long ticket = one ? ++c->ticket : 0;
+    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 0, dbest,
+                       one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
+    FIR_HIP(hipGetLastError());
+    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (best_class && !small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
+    else FIR_HIP(hipStreamSynchronize(c->stream));
+    if (best_class && small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
+    return FIR_OK;
+}
+
+// ... and by the matrix-core form (fir_cls_pnn_mfma.h, included at the end of this file): 0 = answered, 1 = the shape stays with the
+// scan, < 0 = error
+int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class);
 
 }  // namespace
 
@@ -980,40 +1014,50 @@ int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double*
     return FIR_OK;
 }
 
-int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
-    if (!c || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0) return FIR_OK;
+static int cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class, bool routed) {
     if (qb > cls_batch(c)) {
         const int32_t b = cls_batch(c);
         for (int32_t q0 = 0; q0 < qb; q0 += b) {
-            const int rc0 = fir_cls_pnn_predict(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), var,
-                                                scores ? scores + (size_t)q0 * c->num_classes : nullptr, best_class ? best_class + q0 : nullptr);
+            const int rc0 = cls_pnn_predict(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), var,
+                                            scores ? scores + (size_t)q0 * c->num_classes : nullptr, best_class ? best_class + q0 : nullptr, routed);
             if (rc0) return rc0;
         }
         return FIR_OK;
     }
     FIR_HIP(hipSetDevice(c->device));
     if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:190-193
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
-    const double denom = (double)(2 * (size_t)c->d) * var;                       // 2*num_of_cont_features*var, :213
-    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
-                       c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
-    const bool small = cls_small(c, qb);
-    int32_t* dbest = small ? cls_pin_results(c) : c->best;
-    const bool one = small && qb == 1 && !scores;       // the reference's predict() per test vector: no stream synchronisation
-    const unsigned long long ticket = one ? ++c->ticket : 0;
-    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 0, dbest,
-                       one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    FIR_HIP(hipGetLastError());
-    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (best_class && !small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
-    else FIR_HIP(hipStreamSynchronize(c->stream));
-    if (best_class && small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
+    if (routed) {
+        const int rc = cls_pnn_mfma(c, queries, qb, var, scores, best_class);
+        if (rc <= 0) return rc;
+    }
+    return cls_pnn_exact(c, queries, qb, var, scores, best_class);
+}
+
+int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
+    if (!c || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (qb == 0) return FIR_OK;
+    // batches the caller opted in (fir_cls_set_pnn_mfma) take the matrix cores; a one-query call without scores keeps its ticket path
+    const bool routed = c->pm_mode > 0 && qb >= c->pm_mode && c->nt > 0 && !(qb == 1 && !scores);
+    return cls_pnn_predict(c, queries, qb, var, scores, best_class, routed);
+}
+
+int fir_cls_set_pnn_mfma(fir_cls* c, int32_t min_queries) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    c->pm_mode = min_queries < 0 ? -1 : min_queries;
+    if (min_queries == 0) {
+        FIR_HIP(hipSetDevice(c->device));
+        FIR_HIP(hipStreamSynchronize(c->stream));
+        c->pm_ng.release(); c->pm_q.release(); c->pm_flags.release();
+        c->pm_ng_ready = false;
+    }
+    return FIR_OK;
+}
+
+int fir_cls_pnn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (matrix_core_queries) *matrix_core_queries = c->pm_queries;
+    if (exact_scan_queries_of_them) *exact_scan_queries_of_them = c->pm_fallback;
     return FIR_OK;
 }
 
@@ -1360,3 +1404,4 @@ int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int
 }  // extern "C"
 
 #include "fir_cls_kmedoids.h"
+#include "fir_cls_pnn_mfma.h"

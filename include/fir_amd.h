@@ -287,8 +287,36 @@ int fir_cls_kmedoids(fir_cls* c, int32_t num_clusters, int32_t steps, int64_t sc
 int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double* sums);
 /* PNNClassifier::predict_bf, classification.cpp:188-226. var <= 0 selects the reference's value
  * (2e-5, divided by 10 when d > 2000, :190-193). scores[qb][num_classes] (may be NULL) <-
- * sum_t exp(-dist / (2 d var)) / nt per class; best_class[qb] <- first maximum. */
+ * sum_t exp(-dist / (2 d var)) / nt per class; best_class[qb] <- first maximum.
+ * Batches the caller routes with fir_cls_set_pnn_mfma (never by default) take the float64 matrix cores: the distance table is computed as
+ *   |q-avg|^2 + |g-avg|^2 - 2 (q-avg).(g-avg), the dot products by v_mfma_f64_16x16x4_f64, and exp, class sums and arg-max run on it as
+ * before (no atomics: the same bits from run to run). Contract of a routed call:
+ *   Scores. Every class score lies within a relative E(q) + 2^-40 of the scan's,
+ *     E(q) = 2 * 2^-53 * (d + 2) * (|q-avg|^2 + max_t |g_t-avg|^2) / (2 d var)
+ *   (first order, |dS| <= 2u(d+2)(|q|^2+|g|^2) for the three-term form in any summation order, divided by the PNN denominator; 2^-40
+ *   covers the device exp and the summation order of the class sums).
+ *   E(q) is a first-order bound of the form against exact arithmetic; the scan's own sum carries rounding of the same kind (about
+ *   (d+2) u S), so the worst case against the scan's score approaches 2 E(q) -- which the class rule below allows for -- while the
+ *   differences measured are a thousandth of E(q).
+ *   Classes. best_class is the scan's class for every query: a query whose two largest scores s1 >= s2 do not satisfy
+ *   s2 (1 + B) < s1 (1 - B), B = 2 (E(q) + 2^-40), or with a NaN score, or with all scores 0 (underflow), is answered by the scan form,
+ *   class and scores, written into its slots; fir_cls_pnn_stats counts such queries.
+ *   Costs. One double per training row (|g-avg|^2, made on first use, freed by fir_cls_set_pnn_mfma(c, 0) and by destroy) and the centred
+ *   queries in the order the instruction's A operand reads them (the tiled training rows are its B operand as they are).
+ *   Shapes. 32 queries share one read of the rows while their operands fit the 160 KiB of LDS (d <= 640), 16 up to d <= 1280; a longer
+ *   row is answered by the scan and not counted as routed -- never an error. A one-query call with scores == NULL is never routed.
+ *   With fir_cls_profile_enable on, the launches of the kernel are bracketed like the scan's and fir_cls_last_dispatch reports its name
+ *   (it contains k_cls_pnn_mfma), its bytes and flops_per_launch = 2 * rows * d * queries.
+ *   fir_cls_profile_read then holds three times per internal batch, in this order: that kernel, the class sums (k_cls_pnn), the band test.
+ *   The scan of the queries sent back is not bracketed: three times per batch whatever the band decides.
+ * The row-sharded PNN (fir_cls_create_sharded), fir_cls_pnn_predict_seq and fir_cls_distance_sums keep the scan whatever is set. */
 int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class);
+/* min_queries > 0: PNN batches of at least that many queries take the f64 matrix cores; 0: never (frees what the form keeps);
+ * < 0: the automatic choice -- in this version: never (profiles/pnn_matrix_cores.txt holds the measurements a later default would
+ * rest on). A fresh handle is at 0. */
+int fir_cls_set_pnn_mfma(fir_cls* c, int32_t min_queries);
+/* queries that took the matrix-core form so far, and how many of them the exact scan answered after all */
+int fir_cls_pnn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them);
 /* PNNClassifier::predict_sequentional, classification.cpp:228-295: 32-feature chunks, running per-row
  * sums, class outputs with 2*var*max_fi, classes below max/1e9 dropped, stop when one class is left.
  * chunks_out[qb] (may be NULL) <- chunks used. */
