@@ -1369,6 +1369,10 @@ struct fir_gemm {
     bool debug_counts = false;            // appended rows per query of a call's last super-batch on stderr (FIR_GEMM_DEBUG_COUNTS; synchronises)
     hipEvent_t phase_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... and its phases: before / after its preparation, after its full passes, after its re-rank
     std::string dump_phases;              // with FIR_GEMM_DBG_SKIP=256: the file the load-burst timestamps of the last super-batch's first pair go to (FIR_GEMM_DUMP_PHASES)
+    // host-side record of the most recent call, for fir_gemm_nominations_ (tests): 0 = no call yet, 1 = gemm_search, 2 = the few-query scan
+    int last_kind = 0;
+    int last_b = 0, last_nq = 0;          // ... the scratch set of its last super-batch and that super-batch's queries
+    int last_sc_rounds = 0;               // ... the second-chance rounds it queued
 };
 
 // The knobs every kind of state honours (this file's and fir_gemm_f64.h's): each is read once, when the state is created.
@@ -2179,6 +2183,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     }
     if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(st, m->rerank_done[(c.nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
     FIR_HIP(hipGetLastError());
+    m->last_kind = 1; m->last_b = (c.nsb - 1) & 1; m->last_nq = c.sb_queries(c.nsb - 1); m->last_sc_rounds = 0;
 #ifdef FIR_AUDIT
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
@@ -2187,6 +2192,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     // (calls of at most 32 queries skip the second-chance rounds: the exact device scan reads the gallery once per eight queries, about what
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
     const int sc_rounds = m->precision == FIR_GEMM_F16 && qb > 32 ? std::min(kScRounds, (qb + kScQueries - 1) / kScQueries) : 0;
+    m->last_sc_rounds = sc_rounds;
     return gemm_finish_(m, d_queries, k, d_keys, st, c.e_rel, sc_rounds, c.streamed);
 }
 
@@ -2274,9 +2280,59 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
                        d_queries, m->qnorm[b], m->gmax, n, d, m->dp4, m->v.row_offset, e_rel, m->rerank_group, (unsigned long long*)d_keys, m->ok, qs, m->rowmajor, fb);
     FIR_HIP(hipGetLastError());
     m->passes += 1;
+    m->last_kind = 2; m->last_b = b; m->last_nq = qb; m->last_sc_rounds = 0;
     // (the bound of this form already is the smallest proxy of ALL rows + one window: a second pass could not do better; what is
     // not certified -- NaN operands, thousands of ties -- goes to the exact device scan, in stream order)
     return gemm_finish_(m, d_queries, 1, d_keys, st, e_rel, 0, gemm_streamed_(m));
+}
+
+// Read-only diagnostics for the tests of the nomination pass (not part of the public ABI; declared in fir_internal.h): waits for the
+// device's work, then copies out what the re-rank of the most recent call's LAST super-batch was handed for query slots
+// [q0, q0 + nq) of that super-batch -- counts[i], tau[i] (after k_gemm_adapt_final where the bound is found on the way), qnorm[i] and
+// the first min(count, kListCap, max_entries) list entries of each slot (orderable proxy bits << 32 | row) at lists[i * max_entries ..].
+// which = 1: the same for the scratch of the call's last second-chance round that had queries (fir_gemm_fb.h); qmap[i] = the query of
+// the call slot q0 + i stands for, *live = the slots of that round that hold a query (0: no round ran). which = 0: qmap[i] = q0 + i,
+// *live = the super-batch's queries. proxies (the few-query scan only): row i = all n proxies of query q0 + i. *gmax = the largest
+// squared row norm as the windows use it. Any output pointer may be NULL. It changes no scratch and launches nothing.
+int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, int32_t max_entries, int32_t* counts, float* tau, float* qnorm,
+                          uint64_t* lists, float* proxies, float* gmax, int32_t* qmap, int32_t* live) {
+    if (!m || m->f64) return fir_fail_(FIR_ERR_ARG, "not a fir_gemm nomination state");
+    if (which < 0 || which > 1 || q0 < 0 || nq < 0 || max_entries < 0 || max_entries > kListCap) return fir_fail_(FIR_ERR_ARG, "bad range");
+    if (!m->last_kind) return fir_fail_(FIR_ERR_STATE, "no call has run on this state yet");
+    FIR_HIP(hipSetDevice(m->v.device));
+    FIR_HIP(hipDeviceSynchronize());
+    const int b = m->last_b;
+    int have = m->last_nq, off = 0;
+    if (which == 1) {
+        int cnt = 0;
+        FIR_HIP(hipMemcpy(&cnt, m->fb_state, sizeof(int), hipMemcpyDeviceToHost));
+        const int rounds = std::min(m->last_sc_rounds, (cnt + kScQueries - 1) / kScQueries);
+        if (m->last_kind != 1 || rounds <= 0 || !m->sc_lists) have = 0;
+        else { off = (rounds - 1) * kScQueries; have = std::min(kScQueries, cnt - off); }
+    }
+    if (live) *live = have;
+    if (gmax) FIR_HIP(hipMemcpy(gmax, m->gmax, sizeof(float), hipMemcpyDeviceToHost));
+    if (nq == 0) return FIR_OK;
+    if (q0 + nq > have) return fir_fail_(FIR_ERR_ARG, "slots [%d,%d) of %d", q0, q0 + nq, have);
+    const int* d_counts = which ? m->sc_counts : m->counts[b];
+    const float* d_tau = which ? m->sc_tau : m->tau[b];
+    const float* d_qnorm = which ? m->sc_qnorm : m->qnorm[b];
+    const unsigned long long* d_lists = which ? m->sc_lists : m->lists[b];
+    if (counts) FIR_HIP(hipMemcpy(counts, d_counts + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+    if (tau) FIR_HIP(hipMemcpy(tau, d_tau + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+    if (qnorm) FIR_HIP(hipMemcpy(qnorm, d_qnorm + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+    if (lists && max_entries > 0)
+        FIR_HIP(hipMemcpy2D(lists, (size_t)max_entries * 8, d_lists + (size_t)q0 * kListCap, (size_t)kListCap * 8, (size_t)max_entries * 8, (size_t)nq,
+                            hipMemcpyDeviceToHost));
+    if (qmap) {
+        if (which) FIR_HIP(hipMemcpy(qmap, m->fb_list + off + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+        else for (int i = 0; i < nq; ++i) qmap[i] = q0 + i;
+    }
+    if (proxies) {
+        if (m->last_kind != 2 || !m->proxies) return fir_fail_(FIR_ERR_STATE, "the most recent call was not the few-query scan");
+        FIR_HIP(hipMemcpy(proxies, m->proxies + (size_t)q0 * m->v.n, (size_t)nq * m->v.n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return FIR_OK;
 }
 
 // Host-pointer form for fir_search_top1 / fir_search_topk: h_queries -> d_stage (qb rows of the gallery's length) super-batch by

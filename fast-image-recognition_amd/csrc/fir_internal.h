@@ -175,6 +175,9 @@ extern "C" int fir_gemm_search_staged_(fir_gemm* m, const float* h_queries, floa
 // FIR_GEMM_ROWMAJOR says), 0 = never, 1 = whenever it can be allocated.
 extern "C" int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos, int32_t rowmajor_mode, fir_gemm** out);
 // device bytes one matrix-core state holds: the fp16 (bf16 / f32) fragment copy, the row-major shadow, everything else (scratch)
+// tests only: what the most recent call's last super-batch handed its re-rank (fir_gemm.hip); reads, computes and allocates nothing
+extern "C" int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, int32_t max_entries, int32_t* counts, float* tau, float* qnorm,
+                                     uint64_t* lists, float* proxies, float* gmax, int32_t* qmap, int32_t* live);
 extern "C" void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch);
 
 struct fir_cls;

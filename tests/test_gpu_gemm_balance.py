@@ -30,6 +30,12 @@ def both_on_one_handle(fir, rows, q, threshold=-1):
     return got, want, st, disp
 
 
+def assert_no_detours(st):
+    """random data: every first certificate held -- no query took a second matrix-core pass, none the exact device scan (the
+    keys alone cannot tell: either detour returns the right ones)"""
+    assert st["second_pass_queries"] == 0 and st["fallback_queries"] == 0, st
+
+
 def assert_same_keys(got, want):
     assert np.array_equal(got[0], want[0])
     assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
@@ -49,6 +55,7 @@ def test_two_pairs_share_a_range(fir, n, d):
     assert ("<3, 0, 1>" in disp["kernel"]) == (d == 384), disp["kernel"]
     assert_same_keys(got, want)
     assert got[0][5] == 11
+    assert_no_detours(st)
 
 
 def test_sixteen_pairs_share_a_range(fir):
@@ -59,6 +66,7 @@ def test_sixteen_pairs_share_a_range(fir):
     q, _ = synth.make_queries(41, rows, 2048, 0)
     got, want, st, _ = both_on_one_handle(fir, rows, q)
     assert_same_keys(got, want)
+    assert_no_detours(st)
 
 
 def test_fewer_row_blocks_than_waves(fir):
@@ -70,6 +78,7 @@ def test_fewer_row_blocks_than_waves(fir):
     q, _ = synth.make_queries(43, rows, 128, 0)
     got, want, st, _ = both_on_one_handle(fir, rows, q, threshold=128)
     assert_same_keys(got, want)
+    assert_no_detours(st)
 
 
 def test_class_ordered_near_duplicates_append_often(fir):

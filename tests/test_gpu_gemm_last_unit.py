@@ -41,6 +41,12 @@ def assert_same_keys(got, want):
     assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
 
 
+def assert_no_detours(st):
+    """random data: every first certificate held -- no query took a second matrix-core pass, none the exact device scan (the
+    keys alone cannot tell: either detour returns the right ones)"""
+    assert st["second_pass_queries"] == 0 and st["fallback_queries"] == 0, st
+
+
 def gallery_and_queries(seed, n, d, qb):
     """Query 5 is row 11, which the LAST row is a copy of (a tie between the first row block and the last: the lower row wins);
     query 6 is the row before the last (the winner lies in the last block, short or not)."""
@@ -67,6 +73,7 @@ def test_units_per_row_block(fir, d, units, odd):
     assert f"<3, 0, {odd}>" in kern, kern
     assert_same_keys(got, want)
     check_planted(got, N_MULTI)
+    assert_no_detours(st)
 
 
 @pytest.mark.parametrize("d,odd", [(640, 1), (1280, 0)])
@@ -78,6 +85,7 @@ def test_streamed_units(fir, d, odd):
     assert f"<3, 1, {odd}>" in kern, kern
     assert_same_keys(got, want)
     check_planted(got, N_MULTI)
+    assert_no_detours(st)
 
 
 @pytest.mark.parametrize("d", [100, 512, 1280])
@@ -90,6 +98,7 @@ def test_few_row_blocks_and_clamped_norm_loads(fir, n, d):
     got, want, st, kern = both_on_one_handle(fir, rows, q)
     assert_same_keys(got, want)
     check_planted(got, n)
+    assert_no_detours(st)
 
 
 def test_two_pairs_share_a_range(fir):
@@ -101,6 +110,7 @@ def test_two_pairs_share_a_range(fir):
     assert "<3, 0, 0>" in kern, kern
     assert_same_keys(got, want)
     check_planted(got, n)
+    assert_no_detours(st)
 
 
 @pytest.mark.parametrize("n,d,streamed", [(N_SMALL, 512, 0), (32 * 2187 + 5, 512, 0), (N_SMALL, 1280, 1)])
@@ -113,6 +123,7 @@ def test_few_block_forms(fir, qb, njb, n, d, streamed):
     assert f"<3, {streamed}, 0, 0, {njb}>" in kern, kern
     assert_same_keys(got, want)
     check_planted(got, n)
+    assert_no_detours(st)
 
 
 @pytest.mark.parametrize("d,streamed,odd", [(100, 0, 2), (512, 0, 0), (1280, 1, 0)])
@@ -126,6 +137,7 @@ def test_top5(fir, d, streamed, odd):
     assert f"<4, {streamed}, {odd}>" in kern, kern
     assert_same_keys(got, want)
     assert list(got[0][7][:4]) == [200, 201, 202, N_MULTI - 9]
+    assert_no_detours(st)
 
 
 def test_class_ordered_near_duplicates_append_often(fir):
