@@ -599,6 +599,8 @@ constexpr int kSlabH = 32;                                              // k-blo
 constexpr int kHalfLds = 4 * kSlabH * 64 * (int)sizeof(uint4);          // 128 KiB
 constexpr int kRing = 8;                                                // gallery k-blocks per double-buffer unit (8 KiB per wave); the fp16 dk16 is padded to it
 
+#include "fir_gemm_rerank.h"
+
 // max |x| over the tiled gallery (padding is zero) -> out[0]; out must be zeroed first. Non-finite values poison it (NaN -> +inf).
 __global__ void __launch_bounds__(256) k_gemm_absmax(const float4* __restrict__ gal4, int64_t count4, float* __restrict__ out) {
     float m = 0.f;
@@ -664,8 +666,7 @@ __global__ void __launch_bounds__(64) k_gemm_qprep_f16(const float* __restrict__
             const unsigned int start = qi >= nq ? 0u : 0x7F800000u;
             if (qi >= nq) win[qi] = 0.f;
             else {
-                const float w = 2.5f * e_rel * (qn + gnorm_max_p[0]);
-                win[qi] = w + fabsf(w) * 1e-6f + 1e-30f;
+                win[qi] = nudge_up_(rounding_window_(e_rel, qn, gnorm_max_p[0]));
             }
             if (nslot > 0) { for (int sl = 0; sl < 8; ++sl) atomicExch(&t_bits[(size_t)qi * 8 + sl], start); }
             else atomicExch(&t_bits[qi], start);
@@ -683,25 +684,22 @@ __global__ void __launch_bounds__(64) k_gemm_qprep_f16(const float* __restrict__
 // certificate could never hold (measured: 75 of 200 queries of a 600-identity gallery went to the exact scan).
 __global__ void __launch_bounds__(256) k_gemm_tau(const float* __restrict__ sample, int sample_rows, float* __restrict__ tau,
                                                    int nq_valid, const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p, float e_rel,
-                                                   int qgroup = 1, int kth_window = 0) {
+                                                   int kth_window = 0) {
     // kth_window (top-K, K <= kCand): the bound is the kCand-th smallest sampled proxy PLUS one window -- at least K rows
     // lie at or below the kCand-th smallest, and every row within a window of the K-th best one must be appended for the
     // certificate of rank K to be able to hold
-    // qgroup > 1 (the fp16 order-statistic flow, removed; every caller passes 1): the sample of a group of qgroup queries is laid out [value][query of the group] and holds one
-    // MINIMUM per 32-row block instead of every proxy: the kCand-th smallest block minimum still has kCand sampled rows at or
-    // below it, which is all the append pass needs, and is within a rank or two of the exact order statistic
     __shared__ unsigned long long red[4];
     const int q = blockIdx.x;
     if (q >= nq_valid) {        // padding queries of a half-filled pass pair: nothing is appended for them
         if (threadIdx.x == 0) tau[q] = -__builtin_huge_valf();
         return;
     }
-    const float* s = sample + (size_t)(q / qgroup) * qgroup * sample_rows + (q % qgroup);
+    const float* s = sample + (size_t)q * sample_rows;
     unsigned long long best[kCand];
 #pragma unroll
     for (int i = 0; i < kCand; ++i) best[i] = kKeyNone;
     for (int i = threadIdx.x; i < sample_rows; i += 256) {
-        unsigned long long v = fir::key_pack(s[(size_t)i * qgroup], (uint32_t)i);
+        unsigned long long v = fir::key_pack(s[i], (uint32_t)i);
         if (v < best[kCand - 1]) {
 #pragma unroll
             for (int j = 0; j < kCand; ++j) {
@@ -734,9 +732,9 @@ __global__ void __launch_bounds__(256) k_gemm_tau(const float* __restrict__ samp
         if (m != kKeyNone) {
             float v = fir::f32_from_orderable((uint32_t)(m >> 32));
             const float v1 = fir::f32_from_orderable((uint32_t)(smallest >> 32));
-            const float window = 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);       // 2 E d of the re-rank, with room
+            const float window = rounding_window_(e_rel, qnorm[q], gnorm_max_p[0]);
             v = kth_window ? v + window : fmaxf(v, v1 + window);                     // (top-1) a NaN window leaves v as it is
-            t = v + fabsf(v) * 1e-6f + 1e-30f;
+            t = nudge_up_(v);
         }
         tau[q] = t;
     }
@@ -744,19 +742,20 @@ __global__ void __launch_bounds__(256) k_gemm_tau(const float* __restrict__ samp
 
 #include "fir_gemm_fb.h"
 
-// Per query: every appended entry that could still be the nearest row is re-ranked with the reference's arithmetic, then
-// the certificate. One wave per query. out_key[q] = exact packed key; ok[q] = 1 when the certificate holds.
-// Each proxy is within E d of its row's true |g|^2 - 2 q.g, so a row whose proxy exceeds the smallest proxy p1 by more than
-// 2 E d cannot beat the row that has p1: the window [p1, p1 + 2 E d] holds every possible winner -- a handful of rows on
-// ordinary data, all the near-duplicates on clustered data (a fixed number of candidates, as used before, could not
-// certify those and sent them to the exact scan). The window is only how candidates are CHOSEN; what proves the answer
-// is the certificate at the end, which is independent of that reasoning.
+// The K nearest rows of every query (K <= KMAX; KMAX = 1: the nearest row, K a constant) from its candidate list: every appended
+// entry inside the window of the K-th smallest proxy of the list (rerank_window_; a list of fewer than K is re-ranked whole) is
+// re-ranked with the reference's arithmetic, every lane keeping the K smallest exact keys it computed, K rounds of wave-minimum at
+// the end, and the certificate taken against the K-th exact distance: no row outside the re-ranked set can be among the K nearest,
+// nor tie with the K-th. One wave per query. out_key[q * k + r], ascending; kKeyNone where fewer than K rows are below 100000;
+// ok[q] = 1 when the certificate holds.
+template <int KMAX>
 __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __restrict__ lists, const int* __restrict__ counts,
                                                      const float* __restrict__ tau, const float4* __restrict__ gal4,
                                                      const float* __restrict__ queries, const float* __restrict__ qnorm,
-                                                     const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset, float e_rel,
-                                                     int ngroup, unsigned long long* __restrict__ out_key, int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor,
-                                                     const RerankFb fb) {
+                                                     const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset,
+                                                     float e_rel, int ngroup, int k_arg, unsigned long long* __restrict__ out_key,
+                                                     int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor, const RerankFb fb) {
+    const int k = KMAX == 1 ? 1 : k_arg;
     // q: the query's scratch slot (lists, counts, tau, qnorm); qo: its place in queries / out_key / ok -- the same for a super-batch's
     // own re-rank, the query's index in the call for a second-chance round (fir_gemm_fb.h)
     const int q = blockIdx.x, lane = threadIdx.x;
@@ -768,111 +767,48 @@ __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __
     const int cnt = counts[q];
     const int have = cnt < kListCap ? cnt : kListCap;
     const unsigned long long* L = lists + (size_t)q * kListCap;
-    unsigned long long kmin = kKeyNone;
-    for (int i = lane; i < have; i += 64) {
-        const unsigned long long v = L[i];
-        kmin = v < kmin ? v : kmin;
-    }
-    kmin = fir::wave_min_u64(kmin);
+    int found;
+    const unsigned long long kth = list_kth_smallest_(L, have, k, lane, found);
     const float qn = qnorm[q], gmax = gnorm_max_p[0];
-    // E bounds every rounding on both sides, in distance units: the f32 fma chain of the dot product (<= d u |q||g|,
-    // doubled), the two float norms (<= d u each), the reference's own d+3 roundings of the (q-g)^2 sum and its divide:
-    // (4d + 11) u (|q|^2 + |g|^2) / d in total; 8 d u (...) / d is used.  u = 2^-24.
-    // e_rel = 8 d u, plus 2^-14 for the bf16-split variant (dropped lo.lo / residual terms, 3 * 2^-18 |g||q|, doubled in p)
-    // or 2^-10 (1 + 2^-4) for the single fp16 term (both operands rounded to 11 bits)
-    const float E = e_rel * (qn + gmax) / (float)d;
-    const float p1 = kmin != kKeyNone ? fir::f32_from_orderable((uint32_t)(kmin >> 32)) : __builtin_huge_valf();
-    float win = p1 + 2.0f * E * (float)d;
-    win += fabsf(win) * 1e-6f;
-    const float* qv = queries + (size_t)qo * qstride;
-    const int d4 = (d + 3) >> 2;                                  // float4 chunks of the compared features (a prefix of the row when d < its length)
-    unsigned long long best = kKeyNone;
-    float p_out = __builtin_huge_valf();            // smallest proxy NOT re-ranked
-    int reranked = 0;
-    extern __shared__ __attribute__((aligned(16))) float4 crow[];     // [ngroup][dp4]: candidate rows, loaded by the whole wave
-    const int cs = dp4 | 1;                                       // candidate-row stride in LDS, odd: the lanes' rows start in different banks
-    float4* qrow = crow + (size_t)ngroup * cs;                 // [dp4]: the query, zero-padded like the gallery rows (a (0-0)^2 term adds +0)
-    for (int k = lane; k < dp4 * 4; k += 64) ((float*)qrow)[k] = k < d ? qv[k] : 0.0f;
-    __syncthreads();
-    for (int base = 0; base < have; base += 64) {
-        const int i = base + lane;
-        const unsigned long long v = i < have ? L[i] : kKeyNone;
-        const float p = fir::f32_from_orderable((uint32_t)(v >> 32));
-        const bool in = i < have && p <= win;
-        if (i < have && !in) p_out = fminf(p_out, p);
-        unsigned long long mask = __ballot(in);
-        reranked += __popcll(mask);
-        while (mask) {                                                  // wave-uniform
-            // up to ngroup (<= kRerankGroup) candidates at a time: all lanes fetch their rows into LDS, then lane g re-computes
-            // candidate g's distance from there: db_features.cpp:22-42 order, un-fused (fir::accum<kL2>)
-            unsigned long long mine = kKeyNone;
-            int ng = 0;
-            for (int g = 0; g < ngroup; ++g) {
-                if (mask) {
-                    const int src = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const unsigned long long cv = __shfl((unsigned long long)v, src, 64);
-                    const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
-                    if (rowmajor) {                                     // the row-major shadow copy: one contiguous row, coalesced
-                        const float4* gr = rowmajor + (size_t)row * d4;
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[c];
-                    } else {                                            // the tiled gallery: 16 bytes per KiB
-                        const float4* gr = gal4 + (size_t)(row >> 6) * dp4 * 64 + (row & 63);
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[(size_t)c * 64];
-                    }
-                    if (lane == g) mine = cv;
-                    ++ng;
+    const float pk = found == k ? fir::f32_from_orderable((uint32_t)(kth >> 32)) : __builtin_huge_valf();
+    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, pk);
+    extern __shared__ __attribute__((aligned(16))) float4 crow[];
+    const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)qo * qstride, lane);
+    unsigned long long best[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) best[i] = kKeyNone;
+    const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int base, unsigned long long v, bool, unsigned long long mask) {
+        rerank_gather_f32_(mask, v, base, lane, ngroup, lds, gal4, rowmajor, dp4, d, [&](int, unsigned long long cv, float dist) {
+            if (dist < fir::kNotFound) {
+                const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
+                unsigned long long key = fir::key_pack(dist, (uint32_t)(row + row_offset));
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) {                    // sorted insert
+                    const bool sw = key < best[j];
+                    const unsigned long long t = best[j];
+                    best[j] = sw ? key : t;
+                    key = sw ? t : key;
                 }
             }
-            __syncthreads();
-            if (lane < ng) {
-                const float4* my = crow + (size_t)lane * cs;
-                float acc = 0.0f;
-                for (int c = 0; c < d4; ++c) {
-                    const float4 g4 = my[c], q4 = qrow[c];
-                    acc = fir::accum<fir::kL2>(acc, q4.x, g4.x);
-                    acc = fir::accum<fir::kL2>(acc, q4.y, g4.y);
-                    acc = fir::accum<fir::kL2>(acc, q4.z, g4.z);
-                    acc = fir::accum<fir::kL2>(acc, q4.w, g4.w);
-                }
-                const float dist = acc / (float)d;
-                if (dist < fir::kNotFound) {
-                    const int64_t row = (int64_t)(uint32_t)(mine & 0xFFFFFFFFull);
-                    const unsigned long long key = fir::key_pack(dist, (uint32_t)(row + row_offset));
-                    best = key < best ? key : best;
-                }
-            }
-            __syncthreads();
+        });
+    });
+    unsigned long long kth_exact = kKeyNone;
+    for (int r = 0; r < k; ++r) {
+        const unsigned long long m = fir::wave_min_u64(best[0]);
+        if (lane == 0) out_key[(size_t)qo * k + r] = m;
+        kth_exact = m;
+        if (m != kKeyNone && best[0] == m) {                            // exactly one lane holds it
+#pragma unroll
+            for (int j = 0; j + 1 < KMAX; ++j) best[j] = best[j + 1];
+            best[KMAX - 1] = kKeyNone;
         }
     }
-    best = fir::wave_min_u64(best);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p_out = fminf(p_out, __shfl_xor(p_out, off, 64));
     if (lane == 0) {
-        out_key[qo] = best;
-        // Certificate. Every row NOT re-ranked has a proxy >= p_excl: the smallest list entry outside the window, or tau
-        // for rows that were never appended. Its reference distance is then >= (|q|^2 + p_excl)/d - E.
-        bool certified = false;
-        if (cnt <= kListCap) {                      // nothing below tau was dropped from the list
-            const float t = tau[q];
-            const float p_excl = t != t ? t : fminf(p_out, t);      // a NaN bound must not certify anything
-            const float lower = (qn + p_excl) / (float)d - E;
-            const float bd = best != kKeyNone ? fir::f32_from_orderable((uint32_t)(best >> 32)) : fir::kNotFound;
-            certified = lower > bd;                 // false for NaN
-            if (n <= reranked) certified = true;    // every row was re-ranked
-        }
+        const float t = tau[q];
+        const bool certified = rerank_certified_<float>(cnt, t, walk.p_out, qn, d, w.E, kth_exact != kKeyNone,
+                                                        fir::f32_from_orderable((uint32_t)(kth_exact >> 32)), n, walk.reranked);
         ok[qo] = certified ? 1 : 0;
-        if (!certified && fb.list && !fb.qmap) {
-            // a second pass may append below min(this pass's bound, smallest stored proxy + one window): at or above the smallest proxy of
-            // ALL rows + the window (a stored proxy is some row's), so that list will hold every possible winner. NaN bounds stay NaN
-            // (nothing is appended, nothing certified: the exact scan answers).
-            const float w = 2.5f * e_rel * (qn + gmax);
-            const float c = p1 + (w + fabsf(w) * 1e-6f + 1e-30f);
-            const float t = tau[q];
-            fb.tau2[fb.q_base + q] = c < t ? c : t;
-            fb.list[atomicAdd(&fb.state[0], 1)] = fb.q_base + q;
-            fb_note(fb.state, cnt, t, p1, qn);
-        }
+        if (!certified && fb.list && !fb.qmap) rerank_hand_over_(fb, q, cnt, t, pk, qn, gmax, e_rel);
     }
 }
 
@@ -898,150 +834,6 @@ __global__ void __launch_bounds__(256) k_gemm_select(const float* __restrict__ p
     }
 }
 
-// The K nearest rows (K <= kTopKMax) from the same lists: as k_gemm_rerank with the window hung on the K-th smallest proxy
-// of the list, every lane keeping the K smallest exact keys it computed, K rounds of wave-minimum at the end, and the
-// certificate taken against the K-th exact distance: no row outside the re-ranked set can be among the K nearest, nor tie
-// with the K-th (strict '>'). out_key[q * k + r], ascending; kKeyNone where fewer than K rows are below 100000.
-constexpr int kTopKMax = 8;
-__global__ void __launch_bounds__(64) k_gemm_rerank_topk(const unsigned long long* __restrict__ lists, const int* __restrict__ counts,
-                                                          const float* __restrict__ tau, const float4* __restrict__ gal4,
-                                                          const float* __restrict__ queries, const float* __restrict__ qnorm,
-                                                          const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset,
-                                                          float e_rel, int ngroup, int k, unsigned long long* __restrict__ out_key,
-                                                          int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor, const RerankFb fb) {
-    const int q = blockIdx.x, lane = threadIdx.x;                 // (q, qo: as k_gemm_rerank)
-    int qo = q;
-    if (fb.qmap) {
-        if (q >= fb.state[0] - fb.live_off) return;
-        qo = fb.qmap[q];
-    }
-    const int cnt = counts[q];
-    const int have = cnt < kListCap ? cnt : kListCap;
-    const unsigned long long* L = lists + (size_t)q * kListCap;
-    // the K-th smallest list entry (keys are unique: the row is part of the key)
-    unsigned long long prev = 0, kth = kKeyNone;
-    int found = 0;
-    for (int r = 0; r < k; ++r) {
-        unsigned long long m = kKeyNone;
-        for (int i = lane; i < have; i += 64) {
-            const unsigned long long v = L[i];
-            if ((r == 0 || v > prev) && v < m) m = v;
-        }
-        m = fir::wave_min_u64(m);
-        if (m == kKeyNone) break;
-        prev = m;
-        kth = m;
-        ++found;
-    }
-    const float qn = qnorm[q], gmax = gnorm_max_p[0];
-    const float E = e_rel * (qn + gmax) / (float)d;                   // see k_gemm_rerank
-    const float pk = found == k ? fir::f32_from_orderable((uint32_t)(kth >> 32)) : __builtin_huge_valf();   // a short list is re-ranked whole
-    float win = pk + 2.0f * E * (float)d;
-    win += fabsf(win) * 1e-6f;
-    const float* qv = queries + (size_t)qo * qstride;
-    const int d4 = (d + 3) >> 2;                                  // float4 chunks of the compared features (a prefix of the row when d < its length)
-    unsigned long long best[kTopKMax];
-#pragma unroll
-    for (int i = 0; i < kTopKMax; ++i) best[i] = kKeyNone;
-    float p_out = __builtin_huge_valf();            // smallest proxy NOT re-ranked
-    int reranked = 0;
-    extern __shared__ __attribute__((aligned(16))) float4 crow[];     // [ngroup][dp4] candidate rows, then [dp4] the query
-    const int cs = dp4 | 1;                                       // candidate-row stride in LDS, odd: the lanes' rows start in different banks
-    float4* qrow = crow + (size_t)ngroup * cs;
-    for (int c = lane; c < dp4 * 4; c += 64) ((float*)qrow)[c] = c < d ? qv[c] : 0.0f;
-    __syncthreads();
-    for (int base = 0; base < have; base += 64) {
-        const int i = base + lane;
-        const unsigned long long v = i < have ? L[i] : kKeyNone;
-        const float p = fir::f32_from_orderable((uint32_t)(v >> 32));
-        const bool in = i < have && p <= win;
-        if (i < have && !in) p_out = fminf(p_out, p);
-        unsigned long long mask = __ballot(in);
-        reranked += __popcll(mask);
-        while (mask) {                                                  // wave-uniform
-            unsigned long long mine = kKeyNone;
-            int ng = 0;
-            for (int g = 0; g < ngroup; ++g) {
-                if (mask) {
-                    const int src = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const unsigned long long cv = __shfl((unsigned long long)v, src, 64);
-                    const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
-                    if (rowmajor) {                                     // the row-major shadow copy: one contiguous row, coalesced
-                        const float4* gr = rowmajor + (size_t)row * d4;
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[c];
-                    } else {                                            // the tiled gallery: 16 bytes per KiB
-                        const float4* gr = gal4 + (size_t)(row >> 6) * dp4 * 64 + (row & 63);
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[(size_t)c * 64];
-                    }
-                    if (lane == g) mine = cv;
-                    ++ng;
-                }
-            }
-            __syncthreads();
-            if (lane < ng) {
-                const float4* my = crow + (size_t)lane * cs;
-                float acc = 0.0f;
-                for (int c = 0; c < d4; ++c) {
-                    const float4 g4 = my[c], q4 = qrow[c];
-                    acc = fir::accum<fir::kL2>(acc, q4.x, g4.x);
-                    acc = fir::accum<fir::kL2>(acc, q4.y, g4.y);
-                    acc = fir::accum<fir::kL2>(acc, q4.z, g4.z);
-                    acc = fir::accum<fir::kL2>(acc, q4.w, g4.w);
-                }
-                const float dist = acc / (float)d;
-                if (dist < fir::kNotFound) {
-                    const int64_t row = (int64_t)(uint32_t)(mine & 0xFFFFFFFFull);
-                    unsigned long long key = fir::key_pack(dist, (uint32_t)(row + row_offset));
-#pragma unroll
-                    for (int j = 0; j < kTopKMax; ++j) {                // sorted insert
-                        const bool sw = key < best[j];
-                        const unsigned long long t = best[j];
-                        best[j] = sw ? key : t;
-                        key = sw ? t : key;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p_out = fminf(p_out, __shfl_xor(p_out, off, 64));
-    unsigned long long kth_exact = kKeyNone;
-    for (int r = 0; r < k; ++r) {
-        const unsigned long long m = fir::wave_min_u64(best[0]);
-        if (lane == 0) out_key[(size_t)qo * k + r] = m;
-        kth_exact = m;
-        if (m != kKeyNone && best[0] == m) {                            // exactly one lane holds it
-#pragma unroll
-            for (int j = 0; j + 1 < kTopKMax; ++j) best[j] = best[j + 1];
-            best[kTopKMax - 1] = kKeyNone;
-        }
-    }
-    if (lane == 0) {
-        bool certified = false;
-        if (cnt <= kListCap) {                      // nothing below tau was dropped from the list
-            const float t = tau[q];
-            const float p_excl = t != t ? t : fminf(p_out, t);      // a NaN bound must not certify anything
-            const float lower = (qn + p_excl) / (float)d - E;
-            // fewer than K rows found so far: any row below 100000 outside the re-ranked set would belong to the answer
-            const float bd = kth_exact != kKeyNone ? fir::f32_from_orderable((uint32_t)(kth_exact >> 32)) : fir::kNotFound;
-            certified = lower > bd;                 // false for NaN
-            if (n <= reranked) certified = true;    // every row was re-ranked
-        }
-        ok[qo] = certified ? 1 : 0;
-        if (!certified && fb.list && !fb.qmap) {
-            // (as k_gemm_rerank, hung on the K-th smallest stored proxy: the K-th smallest proxy of ALL rows is at or below it)
-            const float w = 2.5f * e_rel * (qn + gmax);
-            const float c = pk + (w + fabsf(w) * 1e-6f + 1e-30f);
-            const float t = tau[q];
-            fb.tau2[fb.q_base + q] = c < t ? c : t;
-            fb.list[atomicAdd(&fb.state[0], 1)] = fb.q_base + q;
-            fb_note(fb.state, cnt, t, pk, qn);
-        }
-    }
-}
-
 // ---- the K nearest distinct classes (fir_gemm_search_top_classes_keys_dev) ----
 // tau[q] holds D_s on entry: the exact K-th smallest class minimum of a row sample (fir_class_scan_dev_), an upper bound of the
 // gallery's K-th class distance D_K. On exit it is that bound in proxy units plus one rounding window, as k_gemm_tau_min hangs
@@ -1056,8 +848,8 @@ __global__ void __launch_bounds__(256) k_gemm_tau_class(float* __restrict__ tau,
     const float ds = tau[q];
     float t = __builtin_huge_valf();
     if (ds < fir::kNotFound) {
-        const float v = (ds * (float)d - qnorm[q]) + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);
-        t = v + fabsf(v) * 1e-6f + 1e-30f;
+        const float v = (ds * (float)d - qnorm[q]) + rounding_window_(e_rel, qnorm[q], gnorm_max_p[0]);
+        t = nudge_up_(v);
     }
     tau[q] = t;
 }
@@ -1065,7 +857,7 @@ __global__ void __launch_bounds__(256) k_gemm_tau_class(float* __restrict__ tau,
 // The K nearest distinct classes (K <= 32) from the lists of one append pass below k_gemm_tau_class's bound. One wave per query.
 //   1. p_K = the K-th smallest proxy over DISTINCT classes of the list (rows labelled outside [0, num_classes) take no part):
 //      K rounds of "smallest key of a class not yet taken"; fewer than K classes: the whole list is re-ranked.
-//   2. every entry with a proxy <= p_K + 2 E d is re-ranked in the reference's arithmetic (as k_gemm_rerank_topk) and its exact
+//   2. every entry with a proxy <= p_K + 2 E d is re-ranked in the reference's arithmetic (rerank_gather_f32_) and its exact
 //      key written back over its list entry; entries outside the window, and rows that do not qualify (label, dist >= 100000),
 //      become kKeyNone.
 //   3. K rounds over the exact keys pick the classes: the smallest key of a class is its first minimum in row order, and the
@@ -1121,71 +913,18 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_classes(unsigned long long* 
         ++found;
     }
     const float qn = qnorm[q], gmax = gnorm_max_p[0];
-    const float E = e_rel * (qn + gmax) / (float)d;                   // see k_gemm_rerank
     const float pk = found == k ? fir::f32_from_orderable((uint32_t)(prev >> 32)) : __builtin_huge_valf();   // a list short of classes is re-ranked whole
-    float win = pk + 2.0f * E * (float)d;
-    win += fabsf(win) * 1e-6f;
-    const float* qv = queries + (size_t)q * qstride;
-    const int d4 = (d + 3) >> 2;                                  // float4 chunks of the compared features (a prefix of the row when d < its length)
-    float p_out = __builtin_huge_valf();            // smallest proxy NOT re-ranked
-    int reranked = 0;
-    extern __shared__ __attribute__((aligned(16))) float4 crow[];     // [ngroup][dp4] candidate rows, then [dp4] the query
-    const int cs = dp4 | 1;                                       // candidate-row stride in LDS, odd: the lanes' rows start in different banks
-    float4* qrow = crow + (size_t)ngroup * cs;
-    for (int c = lane; c < dp4 * 4; c += 64) ((float*)qrow)[c] = c < d ? qv[c] : 0.0f;
-    __syncthreads();
-    for (int base = 0; base < have; base += 64) {
-        const int i = base + lane;
-        const unsigned long long v = i < have ? L[i] : kKeyNone;
-        const float p = fir::f32_from_orderable((uint32_t)(v >> 32));
-        const bool in = i < have && p <= win;
-        if (i < have && !in) {
-            p_out = fminf(p_out, p);
-            L[i] = kKeyNone;
-        }
-        unsigned long long mask = __ballot(in);
-        reranked += __popcll(mask);
-        while (mask) {                                                  // wave-uniform
-            unsigned long long mine = kKeyNone;
-            int mine_i = 0, ng = 0;
-            for (int g = 0; g < ngroup; ++g) {
-                if (mask) {
-                    const int src = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const unsigned long long cv = __shfl((unsigned long long)v, src, 64);
-                    const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
-                    if (rowmajor) {                                     // the row-major shadow copy: one contiguous row, coalesced
-                        const float4* gr = rowmajor + (size_t)row * d4;
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[c];
-                    } else {                                            // the tiled gallery: 16 bytes per KiB
-                        const float4* gr = gal4 + (size_t)(row >> 6) * dp4 * 64 + (row & 63);
-                        for (int c = lane; c < d4; c += 64) crow[(size_t)g * cs + c] = gr[(size_t)c * 64];
-                    }
-                    if (lane == g) { mine = cv; mine_i = base + src; }
-                    ++ng;
-                }
-            }
-            __syncthreads();
-            if (lane < ng) {
-                const float4* my = crow + (size_t)lane * cs;
-                float acc = 0.0f;
-                for (int c = 0; c < d4; ++c) {
-                    const float4 g4 = my[c], q4 = qrow[c];
-                    acc = fir::accum<fir::kL2>(acc, q4.x, g4.x);
-                    acc = fir::accum<fir::kL2>(acc, q4.y, g4.y);
-                    acc = fir::accum<fir::kL2>(acc, q4.z, g4.z);
-                    acc = fir::accum<fir::kL2>(acc, q4.w, g4.w);
-                }
-                const float dist = acc / (float)d;
-                const int64_t row = (int64_t)(uint32_t)(mine & 0xFFFFFFFFull);
-                const bool counted = (uint32_t)cls[row] < (uint32_t)num_classes && dist < fir::kNotFound;
-                L[mine_i] = counted ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
-            }
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p_out = fminf(p_out, __shfl_xor(p_out, off, 64));
+    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, pk);
+    extern __shared__ __attribute__((aligned(16))) float4 crow[];
+    const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)q * qstride, lane);
+    const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int base, unsigned long long v, bool in, unsigned long long mask) {
+        if (base + lane < have && !in) L[base + lane] = kKeyNone;
+        rerank_gather_f32_(mask, v, base, lane, ngroup, lds, gal4, rowmajor, dp4, d, [&](int i, unsigned long long cv, float dist) {
+            const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
+            const bool counted = (uint32_t)cls[row] < (uint32_t)num_classes && dist < fir::kNotFound;
+            L[i] = counted ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
+        });
+    });
     __threadfence_block();                                              // the exact keys, written by other lanes, are read below
     __syncthreads();
     unsigned long long kth_exact = kKeyNone;
@@ -1208,17 +947,12 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_classes(unsigned long long* 
         if (out_key) out_key[(size_t)q * k + i] = kKeyNone;
         if (out_cls) out_cls[(size_t)q * k + i] = -1;
     }
-    if (lane == 0) {
-        const float t = tau[q];
-        const float p_excl = t != t ? t : fminf(p_out, t);          // a NaN bound must not certify anything
-        const float lower = (qn + p_excl) / (float)d - E;
-        // fewer than K classes found: any qualifying row outside the re-ranked set could bring one in
-        const float bd = kth_exact != kKeyNone ? fir::f32_from_orderable((uint32_t)(kth_exact >> 32)) : fir::kNotFound;
-        ok[q] = (lower > bd || n <= reranked) ? 1 : 0;              // (false for NaN; every row was re-ranked)
-    }
+    if (lane == 0)      // (fewer than K classes found: any qualifying row outside the re-ranked set could bring one in)
+        ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, kth_exact != kKeyNone, fir::f32_from_orderable((uint32_t)(kth_exact >> 32)), n,
+                                         walk.reranked) ? 1 : 0;
 }
 
-// the running totals fir_gemm_stats_ex reads (fir_gemm_fb.h), for a call whose uncertified queries the host sent to the exact form
+// the running totals fir_gemm_stats_ex reads (kFbStateWords), for a call whose uncertified queries the host sent to the exact form
 __global__ void k_gemm_fb_count(int* __restrict__ state, int count) {
     unsigned long long* tot = (unsigned long long*)(state + 4);
     tot[0] += (unsigned long long)count;
@@ -1274,8 +1008,7 @@ __global__ void __launch_bounds__(256) k_gemm_adapt_init(float* __restrict__ win
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= nq_total) return;
     if (q >= nq_valid) { win[q] = 0.f; t_bits[q] = 0u; return; }
-    const float w = 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);
-    win[q] = w + fabsf(w) * 1e-6f + 1e-30f;                   // (a NaN window: T never falls, nothing is certified)
+    win[q] = nudge_up_(rounding_window_(e_rel, qnorm[q], gnorm_max_p[0]));        // (a NaN window: T never falls, nothing is certified)
     t_bits[q] = 0x7F800000u;
 }
 // ... and, after the pass, the bound the re-rank's certificate gets: every row that was not appended has a proxy >= tau
@@ -1336,7 +1069,7 @@ struct fir_gemm {
     int* ok = nullptr; size_t ok_cap = 0;  // certificate flags of one call
     int sample_rows = 0;
     // uncertified queries, handled on the device in stream order (fir_gemm_fb.h)
-    int* fb_state = nullptr;              // int[kFbStateWords]: count, count2, notes taken, -, running totals (2 x 64 bit), the first uncertified queries' numbers (fir_gemm_fb.h)
+    int* fb_state = nullptr;              // int[kFbStateWords]: count, count2, notes taken, -, running totals (2 x 64 bit), the first uncertified queries' numbers (fir_gemm_rerank.h)
     int* fb_list = nullptr;               // [ok_cap] queries the first certificate did not hold for
     int* fb_list2 = nullptr;              // [ok_cap] ... still uncertified after the second-chance rounds
     float* fb_tau2 = nullptr;             // [ok_cap] the bound a second pass may append below
@@ -1388,6 +1121,24 @@ static void gemm_read_knobs_(fir_gemm* m) {
     if (fir_knob_("FIR_GEMM_DEBUG_COUNTS")) m->debug_counts = true;
     if (const char* w = fir_knob_("FIR_GEMM_DUMP_PHASES")) m->dump_phases = w;
 #endif
+}
+
+// The exact re-rank + certificate of nq queries on `st` (one wave each; k_gemm_rerank<1> for the nearest row, <kTopKMax> for the K
+// nearest), from one scratch slot: a scratch set of a super-batch, or a second-chance round's. out_key / ok: of block 0's query, or of
+// the call's query 0 for a second-chance round (fb.qmap).
+struct RerankSlot {
+    const unsigned long long* lists;
+    const int* counts;
+    const float* tau;
+    const float* qnorm;
+};
+// dynamic LDS of the f32 re-rank kernels: rerank_group candidate rows and the query (rerank_lds_f32_)
+static size_t gemm_rerank_lds_(const fir_gemm* m) { return (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4); }
+static void gemm_launch_rerank_(fir_gemm* m, hipStream_t st, int nq, const RerankSlot& s, const float* d_queries, float e_rel, int k, uint64_t* out_key, int* ok,
+                                const RerankFb& fb) {
+    hipLaunchKernelGGL(k == 1 ? k_gemm_rerank<1> : k_gemm_rerank<kTopKMax>, dim3(nq), dim3(64), gemm_rerank_lds_(m), st, s.lists, s.counts, s.tau, m->gal4, d_queries,
+                       s.qnorm, (const float*)m->gmax, m->v.n, m->feat, m->dp4, m->v.row_offset, e_rel, m->rerank_group, k, (unsigned long long*)out_key, ok, m->v.d,
+                       (const float4*)m->rowmajor, fb);
 }
 
 // fp16: up to kShareMax pairs of passes (x 128 queries) read the gallery together in one launch (k_gemm_proxy_f16x, `share`). Rows longer
@@ -1588,12 +1339,9 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         const size_t row_bytes = (size_t)(m->dp4 + 1) * sizeof(float4);
         m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes > 1 ? kRerankLdsMax / row_bytes - 1 : 0);
         if (m->rerank_group < 1) { delete m; return fir_fail_(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's re-rank", m->v.d); }
-        if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
-            e = hipFuncSetAttribute((const void*)k_gemm_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
-        if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
-            e = hipFuncSetAttribute((const void*)k_gemm_rerank_topk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
-        if (e == hipSuccess && (size_t)(m->rerank_group + 1) * row_bytes > 48 * 1024)
-            e = hipFuncSetAttribute((const void*)k_gemm_rerank_classes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
+        if (gemm_rerank_lds_(m) > 48 * 1024)
+            for (const void* fn : {(const void*)k_gemm_rerank<1>, (const void*)k_gemm_rerank<kTopKMax>, (const void*)k_gemm_rerank_classes})
+                if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
     if (e == hipSuccess && precision == FIR_GEMM_F16) e = gemm_x_lds_attr_();
     gemm_read_knobs_(m);
@@ -1731,7 +1479,6 @@ int fir_gemm_stats(const fir_gemm* m, int64_t* passes, int64_t* fallback_queries
 static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds, bool streamed) {
     const int d = m->feat, qs = m->v.d;
     const int64_t n = m->v.n;
-    const size_t rr_lds = (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4);
     for (int r = 0; r < sc_rounds; ++r) {
         const int off = r * kScQueries;
         hipLaunchKernelGGL(k_gemm_sc_prep, dim3(kScQueries), dim3(64), 0, st, d_queries, d, qs, m->gallery_exp, (const int*)m->fb_state, (const int*)m->fb_list, off,
@@ -1742,13 +1489,8 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
         hipLaunchKernelGGL(pick_x(1, streamed, gemm_odd_(m)), dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
                            (int64_t)0, n, m->dk16, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
                            (unsigned int*)m->fb_state, off);
-        const RerankFb fb = {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off};
-        if (k == 1)
-            hipLaunchKernelGGL(k_gemm_rerank, dim3(kScQueries), dim3(64), rr_lds, st, m->sc_lists, m->sc_counts, m->sc_tau, m->gal4, d_queries, m->sc_qnorm, m->gmax, n, d,
-                               m->dp4, m->v.row_offset, e_rel, m->rerank_group, (unsigned long long*)d_keys, m->ok, qs, m->rowmajor, fb);
-        else
-            hipLaunchKernelGGL(k_gemm_rerank_topk, dim3(kScQueries), dim3(64), rr_lds, st, m->sc_lists, m->sc_counts, m->sc_tau, m->gal4, d_queries, m->sc_qnorm, m->gmax, n,
-                               d, m->dp4, m->v.row_offset, e_rel, m->rerank_group, k, (unsigned long long*)d_keys, m->ok, qs, m->rowmajor, fb);
+        gemm_launch_rerank_(m, st, kScQueries, {m->sc_lists, m->sc_counts, m->sc_tau, m->sc_qnorm}, d_queries, e_rel, k, d_keys, m->ok,
+                            {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
     }
     hipLaunchKernelGGL(k_gemm_fb_collect, dim3(1), dim3(256), 0, st, m->fb_state, (const int*)m->fb_list, (const int*)m->ok, m->fb_list2, (unsigned long long*)d_keys, k);
     for (int r = 0; r < k; ++r)
@@ -1924,7 +1666,7 @@ static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, i
         hipLaunchKernelGGL(k_gemm_proxy_bf16<0>, dim3(sample_grid, np), dim3(128), 0, ps, m->gb, m->gnorm, m->qbf[b], c.n, (int64_t)0,
                            (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
     }
-    hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, m->tau[b], 0x7FFFFFFF, m->qnorm[b], m->gmax, c.e_rel, 1,
+    hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, m->tau[b], 0x7FFFFFFF, m->qnorm[b], m->gmax, c.e_rel,
                        c.k > 1 ? 1 : 0);
     return FIR_OK;
 }
@@ -2033,19 +1775,14 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
 // exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list
 static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
     const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
-    const size_t rr_lds = (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4);
-    const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0};
     if (c.num_classes > 0)
-        hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax,
+        hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax,
                            m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
                            c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
                            c.qs, m->rowmajor);
-    else if (c.k == 1)
-        hipLaunchKernelGGL(k_gemm_rerank, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax, c.n, c.d,
-                           m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, (unsigned long long*)c.d_keys + q0, m->ok + q0, c.qs, m->rowmajor, fb);
     else
-        hipLaunchKernelGGL(k_gemm_rerank_topk, dim3(nq), dim3(64), rr_lds, rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax, c.n,
-                           c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k, (unsigned long long*)c.d_keys + (size_t)q0 * c.k, m->ok + q0, c.qs, m->rowmajor, fb);
+        gemm_launch_rerank_(m, rs, nq, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b]}, c.sb_first(sb), c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0,
+                            {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
 }
 
 #ifdef FIR_AUDIT
@@ -2275,9 +2012,8 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     fir_gallery_note_dispatch_(m->g, (const void*)scan, "fir::k_gemm_scan_f16x", 1, (int)grid.x, 1, 256, lds, nqt, bytes, 2.0 * (double)n * d * nqt);
     hipLaunchKernelGGL(k_gemm_tau_min, dim3(1), dim3(256), 0, st, m->smin[b], m->tau[b], 2 * kQT, qb, m->qnorm[b], m->gmax, e_rel);
     hipLaunchKernelGGL(k_gemm_select, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256), qb), dim3(256), 0, st, m->proxies, n, m->tau[b], m->lists[b], m->counts[b]);
-    const RerankFb fb = {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0};
-    hipLaunchKernelGGL(k_gemm_rerank, dim3(qb), dim3(64), (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4), st, m->lists[b], m->counts[b], m->tau[b], m->gal4,
-                       d_queries, m->qnorm[b], m->gmax, n, d, m->dp4, m->v.row_offset, e_rel, m->rerank_group, (unsigned long long*)d_keys, m->ok, qs, m->rowmajor, fb);
+    gemm_launch_rerank_(m, st, qb, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b]}, d_queries, e_rel, 1, d_keys, m->ok,
+                        {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0});
     FIR_HIP(hipGetLastError());
     m->passes += 1;
     m->last_kind = 2; m->last_b = b; m->last_nq = qb; m->last_sc_rounds = 0;

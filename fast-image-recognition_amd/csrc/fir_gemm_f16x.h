@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // lane holds in position i of its eight (rows 16 (i >> 2) + 4 (lane >> 4) + (i & 3) of every row block): four rows of EVERY block feed
     // every slot, so a cluster of a few dozen near rows fills all eight at once (slots by row block left the slots of a class-ordered
     // training set to different classes: profiles/r04_knn_matrix_cores.txt) -- the K smallest slot minima belong to K distinct rows, so T = (the K-th smallest slot minimum + |q|^2) +
-    // window bounds the K-th smallest proxy of all rows from above -- what the K-nearest re-rank's certificate needs (k_gemm_rerank_topk:
+    // window bounds the K-th smallest proxy of all rows from above -- what the K-nearest re-rank's certificate needs (k_gemm_rerank<kTopKMax>:
     // window hung on the K-th smallest proxy of the list). Every slot only falls, so T only falls, and the MODE 3 argument carries over
     // word for word. The slots live in LDS (slot_s, as the float bits of (slot minimum + |q|^2) + window, >= 0) and in `smin` (8 words
     // per query), exchanged by the same atomics on the same schedule; the hot path still compares against one bound per query (tq_s / tqr).
@@ -948,8 +948,8 @@ __global__ void __launch_bounds__(256) k_gemm_tau_kmin(const unsigned int* __res
     for (int i = 0; i < 8; ++i) kth = i == k - 1 ? best[i] : kth;
     float t = __builtin_huge_valf();                                      // fewer than K sampled subsets: everything passes, the list cap decides
     if (kth != 0xFFFFFFFFu) {
-        const float v = fir::f32_from_orderable(kth) + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);
-        t = v + fabsf(v) * 1e-6f + 1e-30f;
+        const float v = fir::f32_from_orderable(kth) + rounding_window_(e_rel, qnorm[q], gnorm_max_p[0]);
+        t = nudge_up_(v);
     }
     tau[q] = t;
 }
@@ -963,8 +963,8 @@ __global__ void __launch_bounds__(256) k_gemm_tau_min(const unsigned int* __rest
     float t = __builtin_huge_valf();                                      // no sampled proxy (NaN operands): everything passes, the list cap decides
     if (o != 0xFF800000u) {
         const float v1 = fir::f32_from_orderable(o);
-        const float v = v1 + 2.5f * e_rel * (qnorm[q] + gnorm_max_p[0]);  // a NaN window gives a NaN tau: nothing passes, nothing is certified
-        t = v + fabsf(v) * 1e-6f + 1e-30f;
+        const float v = v1 + rounding_window_(e_rel, qnorm[q], gnorm_max_p[0]);      // a NaN window gives a NaN tau: nothing passes, nothing is certified
+        t = nudge_up_(v);
     }
     tau[q] = t;
 }

@@ -101,8 +101,7 @@ __global__ void __launch_bounds__(64) k_gemm_qprep_f16_f64(const double* __restr
         qmul[qi] = bad ? 0.f : ldexpf(1.0f, sh);
         qinv[qi] = qi >= nq ? 0.f : bad ? __builtin_nanf("") : ldexpf(1.0f, -sh - gallery_exp);
         counts[qi] = 0;
-        const float w = 2.5f * e_rel * (qn + gnorm_max_p[0]);
-        win[qi] = qi >= nq ? 0.f : w + fabsf(w) * 1e-6f + 1e-30f;
+        win[qi] = qi >= nq ? 0.f : nudge_up_(rounding_window_(e_rel, qn, gnorm_max_p[0]));
         if (t_bits) {
             const unsigned int start = qi >= nq ? 0u : 0x7F800000u;
             if (nslot > 0) { for (int sl = 0; sl < 8; ++sl) atomicExch(&t_bits[(size_t)qi * 8 + sl], start); }
@@ -187,26 +186,11 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_f64(const unsigned long long
     const int cnt = counts[q];
     const int have = cnt < kListCap ? cnt : kListCap;
     const unsigned long long* L = lists + (size_t)q * kListCap;
-    // the K'-th smallest list entry (keys are unique: the row is part of the key)
-    unsigned long long prev = 0, kth = kKeyNone;
-    int found = 0;
-    for (int r = 0; r < kp; ++r) {
-        unsigned long long m = kKeyNone;
-        for (int i = lane; i < have; i += 64) {
-            const unsigned long long v = L[i];
-            if ((r == 0 || v > prev) && v < m) m = v;
-        }
-        m = fir::wave_min_u64(m);
-        if (m == kKeyNone) break;
-        prev = m;
-        kth = m;
-        ++found;
-    }
+    int found;
+    const unsigned long long kth = list_kth_smallest_(L, have, kp, lane, found);
     const float qn = qnorm[q], gmax = gnorm_max_p[0];
-    const float E = e_rel * (qn + gmax) / (float)d;
     const float pk = found == kp ? fir::f32_from_orderable((uint32_t)(kth >> 32)) : __builtin_huge_valf();   // a short list is re-ranked whole
-    float win = pk + 2.0f * E * (float)d;
-    win += fabsf(win) * 1e-6f;
+    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, pk);
     // LDS: the centred query (dp2 double2; every lane reads the same element: a broadcast). Every lane re-ranks ONE candidate, straight from the
     // tiled rows with eight 16-byte loads in flight -- candidates of a class-major training set are runs of consecutive rows of one tile, whose
     // loads coalesce -- and sums it in feature order; up to 64 candidates at a time (staging four at a time in LDS took 19 of the 22 ms of a
@@ -220,18 +204,9 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_f64(const unsigned long long
     __shared__ int br_s[8];
     if (lane < 8) { bd_s[lane] = __builtin_huge_val(); br_s[lane] = -1; }
     __syncthreads();
-    float p_out = __builtin_huge_valf();            // smallest proxy NOT re-ranked
-    int reranked = 0;
     (void)ngroup;
-    for (int base = 0; base < have; base += 64) {
-        const int i = base + lane;
-        const unsigned long long v = i < have ? L[i] : kKeyNone;
-        const float p = fir::f32_from_orderable((uint32_t)(v >> 32));
-        const bool in = i < have && p <= win;
-        if (i < have && !in) p_out = fminf(p_out, p);
-        const unsigned long long mask = __ballot(in);
-        if (!mask) continue;                                            // wave-uniform
-        reranked += __popcll(mask);
+    const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int, unsigned long long v, bool in, unsigned long long mask) {
+        if (!mask) return;                                              // wave-uniform
         double dist = __builtin_huge_val();
         int row = -1;
         if (in) {
@@ -287,21 +262,10 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_f64(const unsigned long long
             if (row == mr) { row = -1; dist = __builtin_huge_val(); }    // taken (rows are unique within a list)
             __syncthreads();                                             // (one wave: orders lane 0's LDS writes before the next round's reads)
         }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p_out = fminf(p_out, __shfl_xor(p_out, off, 64));
+    });
     if (lane == 0) {
         for (int j = 0; j < kp; ++j) { out_rows[(size_t)q * kp + j] = br_s[j]; out_dist[(size_t)q * kp + j] = bd_s[j]; }
-        bool certified = false;
-        if (cnt <= kListCap) {
-            const float t = tau[q];
-            const float p_excl = t != t ? t : fminf(p_out, t);
-            const double lower = ((double)qn + (double)p_excl) / (double)d - (double)E;
-            const double bd = br_s[kp - 1] >= 0 ? bd_s[kp - 1] : __builtin_huge_val();     // fewer than K' rows: any row outside would belong to the answer
-            certified = lower > bd;                                  // false for NaN
-            if (n <= reranked) certified = true;                      // every row was re-ranked
-        }
-        ok[q] = certified ? 1 : 0;
+        ok[q] = rerank_certified_<double>(cnt, tau[q], walk.p_out, qn, d, w.E, br_s[kp - 1] >= 0, bd_s[kp - 1], n, walk.reranked) ? 1 : 0;
     }
 }
 

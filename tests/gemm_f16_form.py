@@ -3,7 +3,7 @@ from the code and not from a kernel's output: plain numpy, no GPU. The passes on
 the nominees in the reference's arithmetic and a certificate decides whether the answer stands -- and that certificate rests on
 two premises about the pass:
 
-  1. every proxy is within E d of its row's true |g|^2 - 2 q.g (comment above k_gemm_rerank);
+  1. every proxy is within E d of its row's true |g|^2 - 2 q.g (comment above rerank_window_, fir_gemm_rerank.h);
   2. whatever was not appended has a proxy >= tau, and every row within one window of the smallest proxy of ALL rows is
      appended (header of fir_gemm_f16x.h, MODE 3).
 
@@ -39,7 +39,7 @@ The internal 32-term sum of v_mfma_f32_16x16x32_f16 (and the 16-term one of the 
 chain, so the tests allow kMargin * B with kMargin = 4. That hides nothing: a pass that drops or repeats ONE 32-feature step is
 off by about |q.g| / (d / 32) -- two to three orders of magnitude above 4 B at these shapes.
 
-The project's own quantities are formed in float32 exactly as gemm_search, k_gemm_qprep_f16, k_gemm_rerank and
+The project's own quantities are formed in float32 exactly as gemm_search, k_gemm_qprep_f16, the pieces of fir_gemm_rerank.h and
 k_gemm_adapt_final form them, with erel_scale = 1:
 
   e_rel = 8 d u + {0, 2^-14, 2^-10 (1 + 2^-4)}          (f32, bf16 split, fp16)
@@ -87,7 +87,8 @@ def f32_share_of(d):
 
 
 def window_of(e_rel, qn, gmax):
-    """k_gemm_qprep_f16 / k_gemm_tau_min / k_gemm_rerank's second-pass bound: 2.5 E d with its nudge (float32)"""
+    """nudge_up_(rounding_window_()) of fir_gemm_rerank.h -- k_gemm_qprep_f16 / k_gemm_tau_min / rerank_hand_over_'s second-pass bound: 2.5 E d
+    with its nudge (float32)"""
     w = F32(2.5) * F32(e_rel) * (np.asarray(qn, F32) + F32(gmax))
     return (w + np.abs(w) * F32(1e-6) + F32(1e-30)).astype(F32)
 
@@ -169,7 +170,7 @@ class Form:
 
 
 def certificate(form, p_emu, p_true, qn64, k=1, qn_dev=None, gmax_dev=None, tau=None):
-    """The re-rank's certificate (k_gemm_rerank / k_gemm_rerank_topk) on the emulated proxies, per query of p_emu [c, n]:
+    """The re-rank's certificate (k_gemm_rerank<KMAX>: rerank_window_, rerank_walk_, rerank_certified_<float>) on the emulated proxies, per query of p_emu [c, n]:
     dict of p1 (the K-th smallest proxy), E d, w, tau (the emulated one unless given), margin = (|q|^2 + p_excl) / d - E - (the
     K-th exact distance among the re-ranked rows): the certificate holds where margin > 0, by that much (distance units)."""
     c, n = p_emu.shape
