@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/fir_amd.h"
@@ -654,526 +655,8 @@ __global__ void __launch_bounds__(64) k_cls_argbest(const double* __restrict__ v
     }
 }
 
-}  // namespace
-
-struct fir_cls {
-    int device = 0, cus = 0;
-    int64_t nt = 0;
-    int d = 0, dp2 = 0, num_classes = 0;
-    int64_t tiles = 0;
-    double2* gal2 = nullptr;
-    double* avg = nullptr;
-    int32_t* class_off = nullptr;
-    hipStream_t stream = nullptr;
-    double* dq = nullptr; size_t dq_cap = 0;
-    double* qn = nullptr; size_t qn_cap = 0;
-    double* sums = nullptr; size_t sums_cap = 0;
-    double* scores = nullptr; size_t scores_cap = 0;
-    int32_t* best = nullptr; size_t best_cap = 0;
-    void* pin = nullptr;              // pinned, device-visible staging of small calls: queries in, classes (+ chunk counts) out
-    unsigned long long ticket = 0;    // one-query calls so far: the word the host waits for
-    double total_training_size = 0;   // 0: nt. PNNwithClustering keeps the full size as denominator (classification.cpp:390,393)
-    bool profiling = false;           // fir_cls_profile_enable: HIP event pairs around the launches of the distance scan
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    double last_bytes = 0.0;          // algorithmic bytes of the last timed launch
-    double last_flops = 0.0;          // ... its dot-product flops when it was a matrix-core pass (kNN batches), else 0
-    char last_kernel[64] = "";
-    // large kNN batches: the matrix cores nominate, float64 re-ranks, the exact scan takes what is not settled (fir_gemm_f64.h)
-    fir_gemm* mm = nullptr;           // created on the first such call
-    bool mm_failed = false;           // ... or not (rows too long, no memory): the exact scan answers
-    int mm_mode = -1;                 // fir_cls_set_knn_mfma: -1 automatic (>= kKnnMfmaQueries queries against a training set streamed from HBM), 0 never, > 0 from that many queries on
-    double* qc = nullptr; size_t qc_cap = 0;          // centred queries, row-major
-    int32_t* knn_rows = nullptr; size_t knn_rows_cap = 0;
-    double* knn_dist = nullptr; size_t knn_dist_cap = 0;
-    int32_t* knn_ok = nullptr; size_t knn_ok_cap = 0;
-    int64_t mm_queries = 0, mm_unsettled = 0;         // queries that went through the matrix cores / of them sent on to the exact scan
-    std::vector<int32_t> class_off_h;                 // host copy of class_off
-    FirBuf km, km_meta;                               // fir_cls_kmedoids: distance tables + de-tiled rows + candidate sums / descriptors + results
-    // PNN batches on the float64 matrix cores (fir_cls_pnn_mfma.h)
-    int pm_mode = 0;                                  // fir_cls_set_pnn_mfma: 0 never, > 0 from that many queries on, -1 automatic (in this version: never)
-    FirBuf pm_ng, pm_q, pm_flags;                     // max + |g-avg|^2 per row (once per handle); query operands + norms; band flags
-    bool pm_ng_ready = false;
-    int64_t pm_queries = 0, pm_fallback = 0;          // queries that took the form / of them answered by the scan after all
-};
-
-namespace {
-
-// HIP event pair around one launch of the distance scan (no-ops unless fir_cls_profile_enable is on)
-void cls_prof(fir_cls* c, int end, double bytes, const char* kernel) {
-    if (!c->profiling) return;
-    if (!end && c->ev_used + 2 > c->ev.size())
-        for (int i = 0; i < 64; ++i) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            c->ev.push_back(e);
-        }
-    if (c->ev_used + 2 > c->ev.size()) return;
-    if (!end) {
-        (void)hipEventRecord(c->ev[c->ev_used], c->stream);
-    } else {
-        (void)hipEventRecord(c->ev[c->ev_used + 1], c->stream);
-        c->ev_used += 2;
-        c->last_bytes = bytes;
-        c->last_flops = 0.0;              // a scan launch has no dot-product flops (the matrix-core callers set theirs after this)
-        if (kernel) std::snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kernel);
-    }
-}
-
-template <typename T>
-int cls_grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return FIR_OK;
-    if (p) FIR_HIP(hipFree(p));
-    p = nullptr; cap = 0;
-    FIR_HIP(hipMalloc((void**)&p, std::max<size_t>(need, 1024) * sizeof(T)));
-    cap = std::max<size_t>(need, 1024);
-    return FIR_OK;
-}
-
-// distance sums of all qb queries into c->sums (device), in passes of kQB queries
-// Small calls (what a per-image predict() loop makes): the queries are read from, and the class ids written to, pinned
-// host memory by the kernels themselves -- no copy engine, one synchronisation per call.
-constexpr size_t kPinQueryBytes = 256 * 1024;
-constexpr int kPinResults = 4096;                 // int32 slots: classes [0, 2048), chunk counts [2048, 4096)
-bool cls_small(const fir_cls* c, int32_t qb) { return (size_t)qb * c->d * sizeof(double) <= kPinQueryBytes && qb <= kPinResults / 2; }
-int cls_ensure_pin(fir_cls* c) {
-    if (c->pin) return FIR_OK;
-    FIR_HIP(hipHostMalloc(&c->pin, kPinQueryBytes + kPinResults * sizeof(int32_t) + 64, hipHostMallocDefault));
-    std::memset((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t), 0, 64);
-    return FIR_OK;
-}
-int32_t* cls_pin_results(fir_cls* c) { return (int32_t*)((char*)c->pin + kPinQueryBytes); }
-unsigned long long* cls_pin_ticket(fir_cls* c) { return (unsigned long long*)((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t)); }
-// -> device-visible pointer to the staged queries
-int cls_stage_queries(fir_cls* c, const double* queries, int32_t qb, const double** d_q) {
-    int rc;
-    if (cls_small(c, qb)) {
-        if ((rc = cls_ensure_pin(c))) return rc;
-        std::memcpy(c->pin, queries, (size_t)qb * c->d * sizeof(double));
-        *d_q = (const double*)c->pin;
-        return FIR_OK;
-    }
-    if ((rc = cls_grow(c->dq, c->dq_cap, (size_t)qb * c->d))) return rc;
-    FIR_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    *d_q = c->dq;
-    return FIR_OK;
-}
-
-// Queries per internal batch: the distance table (qb x nt doubles) stays under 1 GiB whatever the caller's batch is.
-int32_t cls_batch(const fir_cls* c) {
-    const int64_t per_query = std::max<int64_t>(c->nt, 1) * (int64_t)sizeof(double);
-    // ... and within gridDim.y of the per-(class, query) kernels (65535)
-    return (int32_t)std::max<int64_t>(kQBBig, std::min<int64_t>(65528, ((int64_t)1 << 30) / per_query / kQBBig * kQBBig));
-}
-
-int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
-    int rc;
-    const double* dq = nullptr;
-    if ((rc = cls_stage_queries(c, queries, qb, &dq))) return rc;
-    if ((rc = cls_grow(c->sums, c->sums_cap, (size_t)qb * std::max<int64_t>(c->nt, 1)))) return rc;
-    const int kk = c->dp2 * 2;
-    const int waves = (int)std::min<int64_t>(std::max<int64_t>((c->tiles + 3) / 4 * 4, 4), (int64_t)c->cus * 16);
-    // a training set streamed from HBM takes 8 queries per pass (the pass stays HBM-bound), a cache-resident one 4
-    const bool big = (double)c->tiles * 64.0 * c->dp2 * 16.0 > 256.0 * 1024 * 1024;
-    const int qbt = big ? kQBBig : kQB;
-    if (qb == 1 && !big) {
-        hipLaunchKernelGGL(k_cls_scan_one, dim3(waves / 4), dim3(kBlock), (size_t)kk * sizeof(double), c->stream, c->gal2, dq, c->avg, c->nt,
-                           (int)c->tiles, c->dp2, c->d, waves, 0, c->dp2, c->sums, c->dp2, (int64_t)0);
-        FIR_HIP(hipGetLastError());
-        return FIR_OK;
-    }
-    const size_t lds_tile = (size_t)(kk + 1) * 8 * sizeof(double);
-    if (big && lds_tile <= 64 * 1024) {
-        // the LDS-tile scan: every tile of eight queries in ONE launch (blockIdx.y), at most 64 tiles per launch; two tiles per read of
-        // the training rows when the call has them and both fit LDS (FIR_CLS_ONE_TILE=1: one, for A/B runs)
-        const int ntile = (qb + 7) / 8;
-        if ((rc = cls_grow(c->qn, c->qn_cap, (size_t)ntile * kk * 8))) return rc;
-        hipLaunchKernelGGL(k_cls_prep_query_tiles, dim3((unsigned)(((size_t)ntile * kk * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, dq, qb, c->d,
-                           c->dp2, c->avg, c->qn);
-        const bool one_tile = fir_knob_("FIR_CLS_ONE_TILE") != nullptr;
-        // Forms by tiles of eight queries per read of the training rows (profiles/r04_k3_forms.txt; 1M x 512, 64 queries, kernel ms per call):
-        // one tile, one row per lane 5.7 (HBM-bound, 0.72 of the peak); two tiles 4.16 (round 3); two tiles, two rows per lane 3.90; four
-        // tiles, two rows per lane 3.74 -- the f64 vector pipes are then 85-90 % busy at the 1.7 GHz the chip holds under this load
-        // (profiles/r04_rocprofv3_pmc_k3.json): that, not the 2.4 GHz issue rate, is the roof. Two rows per lane: every broadcast LDS read of a
-        // query value serves two rows (the LDS pipe was two thirds busy at the vector pipes' full rate). A call is cut into groups of 4, 2, 1
-        // tiles so that no group computes padding tiles.
-        typedef void (*scan_fn)(const double2*, const double*, int64_t, int, int, int, int, double*);
-#define FIR_CLS_KERNEL(...) k_cls_scan_lds<__VA_ARGS__>, "fir::k_cls_scan_lds<" #__VA_ARGS__ ">"      // pointer and name from the same arguments
-        struct Form { int nt, r, block, wpc; scan_fn fn; const char* name; };
-        const Form f4 = {4, 2, 512, 8, FIR_CLS_KERNEL(2, 4, 512, 2, 2)};
-        const Form f2 = {2, 2, 256, 8, FIR_CLS_KERNEL(4, 2, 256, 2, 2)};
-        const Form f1 = {1, 1, 256, 16, FIR_CLS_KERNEL(8, 1)};
-#undef FIR_CLS_KERNEL
-        {
-            static bool attr_set[64] = {};                     // (per device: the attribute belongs to the device's copy of the code object)
-            const int dv = c->device & 63;
-            if (!attr_set[dv]) {
-                FIR_HIP(hipFuncSetAttribute((const void*)f4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                FIR_HIP(hipFuncSetAttribute((const void*)f2.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                attr_set[dv] = true;
-            }
-        }
-        for (int t0 = 0; t0 < ntile;) {
-            const int rem = ntile - t0;
-            const Form& f = (rem >= 4 && 4 * lds_tile <= 150 * 1024 && !one_tile) ? f4 : (rem >= 2 && 2 * lds_tile <= 150 * 1024 && !one_tile) ? f2 : f1;
-            const int groups = std::min(rem / f.nt, 64 / f.nt);                   // at most 64 tiles per launch (blockIdx.y = group of nt tiles)
-            const int tn = groups * f.nt;
-            const int wpb = f.block / 64;
-            const int64_t tsteps = (c->tiles + f.r - 1) / f.r;
-            const int wv = (int)std::min<int64_t>(std::max<int64_t>((tsteps + wpb - 1) / wpb * wpb, wpb), (int64_t)c->cus * f.wpc);
-            cls_prof(c, 0, 0.0, nullptr);
-            hipLaunchKernelGGL(f.fn, dim3(wv / wpb, groups), dim3(f.block), (size_t)f.nt * lds_tile, c->stream, c->gal2, c->qn + (size_t)t0 * kk * 8, c->nt, (int)c->tiles,
-                               c->dp2, wv, std::min(qb - t0 * 8, tn * 8), c->sums + (size_t)t0 * 8 * c->nt);
-            // algorithmic bytes of the launch: every read of the training rows serves nt tiles of eight queries (+ the query tiles, + the sums written)
-            cls_prof(c, 1, (double)groups * ((double)c->tiles * 64.0 * c->dp2 * 16.0) + (double)tn * ((double)kk * 64.0 + 8.0 * 8.0 * (double)c->nt), f.name);
-            t0 += tn;
-        }
-        FIR_HIP(hipGetLastError());
-        return FIR_OK;
-    }
-    for (int q0 = 0; q0 < qb; q0 += qbt) {
-        const int nq = std::min(qbt, qb - q0);
-        if (big) {
-            hipLaunchKernelGGL(k_cls_prep_queries<kQBBig>, dim3((kk * kQBBig + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                               dq + (size_t)q0 * c->d, nq, c->d, c->dp2, c->avg, c->qn);
-            hipLaunchKernelGGL(k_cls_scan<kQBBig>, dim3(waves / 4), dim3(kBlock), 0, c->stream, c->gal2, c->qn, c->nt, (int)c->tiles, c->dp2,
-                               c->d, waves, nq, 0, c->dp2, c->sums + (size_t)q0 * c->nt, c->dp2, (int64_t)0);
-        } else {
-            hipLaunchKernelGGL(k_cls_prep_queries<kQB>, dim3((kk * kQB + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                               dq + (size_t)q0 * c->d, nq, c->d, c->dp2, c->avg, c->qn);
-            hipLaunchKernelGGL(k_cls_scan<kQB>, dim3(waves / 4), dim3(kBlock), 0, c->stream, c->gal2, c->qn, c->nt, (int)c->tiles, c->dp2,
-                               c->d, waves, nq, 0, c->dp2, c->sums + (size_t)q0 * c->nt, c->dp2, (int64_t)0);
-        }
-    }
-    FIR_HIP(hipGetLastError());
-    return FIR_OK;
-}
-
-// PNN of one internal batch (qb <= cls_batch, var > 0, the device current) by the exact scan
-int cls_pnn_exact(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
-    const double denom = (double)(2 * (size_t)c->d) * var;                       // 2*num_of_cont_features*var, :213
-    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
-                       c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
-    const bool small = cls_small(c, qb);
-    int32_t* dbest = small ? cls_pin_results(c) : c->best;
-    const bool one = small && qb == 1 && !scores;       // the reference's predict() per test vector: no stream synchronisation
-    const unsigned long long ticket = one ? ++c->ticket : 0;
-    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 0, dbest,
-                       one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    FIR_HIP(hipGetLastError());
-    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (best_class && !small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
-    else FIR_HIP(hipStreamSynchronize(c->stream));
-    if (best_class && small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
-    return FIR_OK;
-}
-
-// ... and by the matrix-core form (fir_cls_pnn_mfma.h, included at the end of this file): 0 = answered, 1 = the shape stays with the
-// scan, < 0 = error
-int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class);
-
-}  // namespace
-
-extern "C" {
-
-static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
-                      const double* avg, int32_t device, fir_cls** out);
-
-int fir_cls_create(const double* train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
-                   const double* avg, int32_t device, fir_cls** out) {
-    return cls_create(train_rows, false, nt, d, train_class, num_classes, avg, device, out);
-}
-
-int fir_cls_create_dev(const double* d_train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
-                       const double* avg, int32_t device, fir_cls** out) {
-    return cls_create(d_train_rows, true, nt, d, train_class, num_classes, avg, device, out);
-}
-
-static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
-                      const double* avg, int32_t device, fir_cls** out) {
-    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    if (nt < 0 || d <= 0 || num_classes <= 0 || !avg || (nt > 0 && (!train_rows || !train_class)))
-        return fir_fail_(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
-    if (nt >= ((int64_t)1 << 31) - 64) return fir_fail_(FIR_ERR_ARG, "nt too large");
-    std::vector<int32_t> off((size_t)num_classes + 1, 0);
-    for (int64_t t = 0; t < nt; ++t) {
-        const int32_t cl = train_class[t];
-        if (cl < 0 || cl >= num_classes || (t > 0 && cl < train_class[t - 1]))
-            return fir_fail_(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
-        off[(size_t)cl + 1]++;
-    }
-    for (int i = 0; i < num_classes; ++i) off[(size_t)i + 1] += off[(size_t)i];
-    int cnt = 0;
-    cnt = fir_device_count();        // the guarded first touch of the runtime (fir_runtime_init_)
-    if (cnt <= 0) return fir_fail_(FIR_ERR_NODEVICE, "no HIP device visible");
-    if (device < 0 || device >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
-    { const int rc0 = fir_runtime_init_(device); if (rc0) return rc0; }
-    hipDeviceProp_t prop;
-    FIR_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-    fir_cls* c = new (std::nothrow) fir_cls();
-    if (!c) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
-    c->device = device;
-    c->cus = prop.multiProcessorCount;
-    c->nt = nt;
-    c->d = d;
-    c->dp2 = (d + 1) / 2;
-    c->num_classes = num_classes;
-    c->tiles = (nt + kTileRows - 1) / kTileRows;
-    c->class_off_h = off;
-    int rc = FIR_OK;
-    double* stage = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    const size_t g2 = (size_t)std::max<int64_t>(c->tiles, 1) * c->dp2 * 64;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->gal2, g2 * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->avg, (size_t)d * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->qn, (size_t)c->dp2 * 2 * kQBBig * sizeof(double));
-    if (e == hipSuccess) c->qn_cap = (size_t)c->dp2 * 2 * kQBBig;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->class_off, ((size_t)num_classes + 1) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(c->avg, avg, (size_t)d * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->class_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    const int64_t slab = std::max<int64_t>(kTileRows, ((int64_t)(256u << 20) / ((int64_t)d * 8)) / kTileRows * kTileRows);
-    if (e == hipSuccess && nt > 0 && !rows_on_device) e = hipMalloc((void**)&stage, (size_t)std::min<int64_t>(slab, c->tiles * kTileRows) * d * sizeof(double));
-    for (int64_t r0 = 0; e == hipSuccess && r0 < nt; r0 += slab) {
-        const int64_t have = std::min<int64_t>(slab, nt - r0);
-        if (!rows_on_device) e = hipMemcpyAsync(stage, train_rows + r0 * d, (size_t)have * d * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) break;
-        const int64_t total = ((have + kTileRows - 1) / kTileRows) * c->dp2 * 64;
-        hipLaunchKernelGGL(k_cls_retile, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                           rows_on_device ? train_rows + r0 * d : stage, have, r0, nt, d, c->dp2, c->avg, c->gal2);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (stage) (void)hipFree(stage);
-    if (e != hipSuccess) rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "training-set upload: %s", hipGetErrorString(e));
-    if (rc) { fir_cls_destroy(c); return rc; }
-    *out = c;
-    return FIR_OK;
-}
-
-int fir_cls_set_total_training_size(fir_cls* c, int64_t total) {
-    if (!c || total < 0) return fir_fail_(FIR_ERR_ARG, "bad argument");
-    c->total_training_size = (double)total;
-    return FIR_OK;
-}
-
-int fir_cls_profile_enable(fir_cls* c, int32_t on) {
-    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    c->profiling = on != 0;
-    c->ev_used = 0;
-    return FIR_OK;
-}
-
-int fir_cls_profile_read(fir_cls* c, float* ms, int32_t cap, int32_t* count, double* bytes_per_launch, char* kernel, int32_t kernel_cap) {
-    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    FIR_HIP(hipSetDevice(c->device));
-    const int32_t have = (int32_t)(c->ev_used / 2);
-    for (int32_t i = 0; i < have; ++i) {
-        FIR_HIP(hipEventSynchronize(c->ev[2 * (size_t)i + 1]));
-        float t = 0.f;
-        FIR_HIP(hipEventElapsedTime(&t, c->ev[2 * (size_t)i], c->ev[2 * (size_t)i + 1]));
-        if (ms && i < cap) ms[i] = t;
-    }
-    if (count) *count = have;
-    if (bytes_per_launch) *bytes_per_launch = c->last_bytes;
-    if (kernel && kernel_cap > 0) std::snprintf(kernel, (size_t)kernel_cap, "%s", c->last_kernel);
-    c->ev_used = 0;
-    return FIR_OK;
-}
-
-int fir_cls_destroy(fir_cls* c) {
-    if (!c) return FIR_OK;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    (void)hipFree(c->gal2); (void)hipFree(c->avg); (void)hipFree(c->class_off); (void)hipFree(c->dq); (void)hipFree(c->qn);
-    (void)hipFree(c->sums); (void)hipFree(c->scores); (void)hipFree(c->best);
-    if (c->mm) (void)fir_gemm_destroy(c->mm);
-    (void)hipFree(c->qc); (void)hipFree(c->knn_rows); (void)hipFree(c->knn_dist); (void)hipFree(c->knn_ok);
-    if (c->pin) (void)hipHostFree(c->pin);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-    return FIR_OK;
-}
-
-int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double* sums) {
-    if (!c || !sums || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0 || c->nt == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(c->device));
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    FIR_HIP(hipMemcpyAsync(sums, c->sums, (size_t)qb * c->nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FIR_HIP(hipStreamSynchronize(c->stream));
-    return FIR_OK;
-}
-
-static int cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class, bool routed) {
-    if (qb > cls_batch(c)) {
-        const int32_t b = cls_batch(c);
-        for (int32_t q0 = 0; q0 < qb; q0 += b) {
-            const int rc0 = cls_pnn_predict(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), var,
-                                            scores ? scores + (size_t)q0 * c->num_classes : nullptr, best_class ? best_class + q0 : nullptr, routed);
-            if (rc0) return rc0;
-        }
-        return FIR_OK;
-    }
-    FIR_HIP(hipSetDevice(c->device));
-    if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:190-193
-    if (routed) {
-        const int rc = cls_pnn_mfma(c, queries, qb, var, scores, best_class);
-        if (rc <= 0) return rc;
-    }
-    return cls_pnn_exact(c, queries, qb, var, scores, best_class);
-}
-
-int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
-    if (!c || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0) return FIR_OK;
-    // batches the caller opted in (fir_cls_set_pnn_mfma) take the matrix cores; a one-query call without scores keeps its ticket path
-    const bool routed = c->pm_mode > 0 && qb >= c->pm_mode && c->nt > 0 && !(qb == 1 && !scores);
-    return cls_pnn_predict(c, queries, qb, var, scores, best_class, routed);
-}
-
-int fir_cls_set_pnn_mfma(fir_cls* c, int32_t min_queries) {
-    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    c->pm_mode = min_queries < 0 ? -1 : min_queries;
-    if (min_queries == 0) {
-        FIR_HIP(hipSetDevice(c->device));
-        FIR_HIP(hipStreamSynchronize(c->stream));
-        c->pm_ng.release(); c->pm_q.release(); c->pm_flags.release();
-        c->pm_ng_ready = false;
-    }
-    return FIR_OK;
-}
-
-int fir_cls_pnn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them) {
-    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (matrix_core_queries) *matrix_core_queries = c->pm_queries;
-    if (exact_scan_queries_of_them) *exact_scan_queries_of_them = c->pm_fallback;
-    return FIR_OK;
-}
-
-// PNN class scores of qb <= *max_batch queries, left on the device (valid until the handle's next call), queued on the
-// handle's stream: the row-sharded PNN (fir_shard.hip) adds the shards' partial sums before the arg-max.
-int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, double var, double** d_scores, void** stream, int32_t* max_batch) {
-    if (!c || !d_scores || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (max_batch) *max_batch = cls_batch(c);
-    if (qb == 0) return FIR_OK;
-    if (qb < 0 || qb > cls_batch(c) || !queries) return fir_fail_(FIR_ERR_ARG, "bad batch %d (at most %d at a time)", qb, cls_batch(c));
-    FIR_HIP(hipSetDevice(c->device));
-    if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:190-193
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
-    const double denom = (double)(2 * (size_t)c->d) * var;
-    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
-                       c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
-    FIR_HIP(hipGetLastError());
-    *d_scores = c->scores;
-    *stream = c->stream;
-    return FIR_OK;
-}
-
-// The k smallest mean distances per class of qb <= *max_batch queries, [qb][num_classes][k] ascending (DBL_MAX where the class has
-// fewer rows here), left on the device and queued on the handle's stream: the row-sharded kNN vote (fir_shard.hip) merges them.
-int fir_cls_knn_nearest_dev_(fir_cls* c, const double* queries, int32_t qb, int32_t k, double** d_lists, void** stream, int32_t* max_batch) {
-    if (!c || !d_lists || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (max_batch) *max_batch = cls_batch(c);
-    if (qb == 0) return FIR_OK;
-    if (qb < 0 || qb > cls_batch(c) || !queries || k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "bad batch %d / k %d", qb, k);
-    FIR_HIP(hipSetDevice(c->device));
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes * (1 + (size_t)k)))) return rc;
-    double* lists = c->scores + (size_t)qb * c->num_classes;
-    hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, c->d, k, c->scores,
-                       lists);
-    FIR_HIP(hipGetLastError());
-    *d_lists = lists;
-    *stream = c->stream;
-    return FIR_OK;
-}
-
-int fir_cls_pnn_predict_seq(fir_cls* c, const double* queries, int32_t qb, double var, int32_t* best_class, int32_t* chunks_out) {
-    if (!c || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if ((size_t)c->num_classes * 16 + 4 > 60 * 1024) return fir_fail_(FIR_ERR_ARG, "num_classes=%d too large for the LDS tables", c->num_classes);
-    if (qb == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(c->device));
-    if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }                // classification.cpp:229-233
-    const int nchunks = (c->d + 31) / 32;
-    const int64_t ntp = std::max<int64_t>(c->nt, 1);
-    int rc;
-    const double* dq = nullptr;
-    if ((rc = cls_stage_queries(c, queries, qb, &dq))) return rc;
-    if ((rc = cls_grow(c->sums, c->sums_cap, (size_t)(nchunks + 2) * kQB * ntp))) return rc;   // chunk sums + running sums + their exp()
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)2 * std::max(qb, kQB)))) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)kQB * nchunks * c->num_classes))) return rc;   // k_cls_pnn_seq_par's table
-    const bool small = cls_small(c, qb);
-    int32_t* dbest = small ? cls_pin_results(c) : c->best;
-    int32_t* dchunks = small ? cls_pin_results(c) + kPinResults / 2 : c->best + std::max(qb, kQB);
-    const int kk = c->dp2 * 2;
-    const int waves = (int)std::min<int64_t>(std::max<int64_t>((c->tiles + 3) / 4 * 4, 4), (int64_t)c->cus * 16);
-    double* run = c->sums + (size_t)nchunks * kQB * ntp;
-    const bool one = small && qb == 1;
-    const unsigned long long ticket = one ? ++c->ticket : 0;
-    for (int q0 = 0; q0 < qb; q0 += kQB) {
-        const int nq = std::min(kQB, qb - q0);
-        // all 32-feature chunk sums (16 double2 chunks each) from one pass: chunk ch lands at sums + ch * nq * nt
-        if (qb == 1) {
-            hipLaunchKernelGGL(k_cls_scan_one, dim3(waves / 4), dim3(kBlock), (size_t)kk * sizeof(double), c->stream, c->gal2, dq, c->avg, c->nt,
-                               (int)c->tiles, c->dp2, c->d, waves, 0, c->dp2, c->sums, 16, (int64_t)c->nt);
-        } else {
-            hipLaunchKernelGGL(k_cls_prep_queries<kQB>, dim3((kk * kQB + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                               dq + (size_t)q0 * c->d, nq, c->d, c->dp2, c->avg, c->qn);
-            hipLaunchKernelGGL(k_cls_scan<kQB>, dim3(waves / 4), dim3(kBlock), 0, c->stream, c->gal2, c->qn, c->nt, (int)c->tiles, c->dp2, c->d, waves,
-                               nq, 0, c->dp2, c->sums, 16, (int64_t)nq * c->nt);
-        }
-        const size_t flags_lds = ((size_t)c->num_classes + 1) / 2 * 8, table_lds = (size_t)nchunks * c->num_classes * 8;
-        const int table_in_lds = flags_lds + table_lds <= 48 * 1024;
-        if (c->nt <= kSeqParRows && flags_lds <= 48 * 1024) {
-            hipLaunchKernelGGL(k_cls_pnn_seq_par, dim3(c->num_classes, nchunks, nq), dim3(64), 0, c->stream, c->sums, nq, nchunks, c->class_off, c->nt,
-                               c->num_classes, c->d, var, c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
-            hipLaunchKernelGGL(k_cls_pnn_seq_walk, dim3(nq), dim3(64), flags_lds + (table_in_lds ? table_lds : 0), c->stream, c->scores, nchunks,
-                               c->num_classes, dbest + q0, dchunks + q0, table_in_lds, one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-        }
-        else
-            hipLaunchKernelGGL(k_cls_pnn_seq, dim3(nq), dim3(kSeqBlock), (size_t)c->num_classes * 16 + 4, c->stream, c->sums, nq, nchunks, run,
-                               run + (size_t)kQB * ntp, c->class_off, c->nt, c->num_classes, c->d, var,
-                               c->total_training_size > 0 ? c->total_training_size : (double)c->nt, dbest + q0, dchunks + q0,
-                               one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    }
-    FIR_HIP(hipGetLastError());
-    if (one) {
-        if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc;
-        best_class[0] = dbest[0];
-        if (chunks_out) chunks_out[0] = dchunks[0];
-        return FIR_OK;
-    }
-    if (!small) {
-        FIR_HIP(hipMemcpyAsync(best_class, dbest, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (chunks_out) FIR_HIP(hipMemcpyAsync(chunks_out, dchunks, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    }
-    FIR_HIP(hipStreamSynchronize(c->stream));
-    if (small) {
-        std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
-        if (chunks_out) std::memcpy(chunks_out, dchunks, (size_t)qb * sizeof(int32_t));
-    }
-    return FIR_OK;
-}
-
-}  // extern "C"
-
-namespace {
 constexpr int kKnnMfmaQueries = 128;       // automatic mode: kNN batches from this size on take the matrix cores (training sets streamed from HBM)
+constexpr int32_t kKnnMfmaBatch = 16384;   // queries per internal batch of that path (its scratch: two copies of the queries, 8 rows + distances per query)
 
 // qc[i][k] = q[i][k] - avg[k]: the query side of normalize() (classification.cpp:103-105, :135), row-major
 __global__ void __launch_bounds__(kBlock) k_cls_center_queries(const double* __restrict__ q, int64_t count, int d, const double* __restrict__ avg, double* __restrict__ qc) {
@@ -1212,12 +695,661 @@ __global__ void __launch_bounds__(kBlock) k_cls_knn_vote(const int32_t* __restri
     best[q] = res;
 }
 
-// kNN through the matrix cores for the queries of one call (qb <= cls_batch): 0 = best_class filled for every query, 1 = not taken (the
-// exact path answers the call), < 0 = error.
-int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class);
+}  // namespace
+
+// The record fir_cls_last_dispatch and fir_cls_profile_read report: the call's dominant kernel, the algorithmic bytes of the last
+// timed launch and its dot-product flops when it was a matrix-core pass (else 0)
+struct ClsDispatch { char kernel[64] = ""; double bytes = 0.0, flops = 0.0; };
+
+struct fir_cls {
+    int device = 0, cus = 0;
+    int64_t nt = 0;
+    int d = 0, dp2 = 0, num_classes = 0;
+    int64_t tiles = 0;
+    FirBuf gal2_mem, avg_mem, class_off_mem;   // the training set as the kernels read it, and typed views of the three
+    double2* gal2 = nullptr;
+    double* avg = nullptr;
+    int32_t* class_off = nullptr;
+    hipStream_t stream = nullptr;
+    // Device scratch, grown on demand (FIR_RESERVE) and shared by the entry points: a call owns all of it until it returns.
+    FirBuf dq;                        // the queries of a call too large for the pin
+    FirBuf qn;                        // q - avg as the scan reads it; one pass's worth from creation on, so that a one-query call never allocates
+    FirBuf sums;                      // [query][row] distance sums; the sequential PNN's chunk sums, running sums and their exp()
+    FirBuf scores;                    // [query][class] PNN scores | kNN k-th distances, then [query][class][k] lists | the sequential PNN's table
+    FirBuf best;                      // [query] classes (then chunk counts) of a call too large for the pin
+    void* pin = nullptr;              // pinned, device-visible staging of small calls: queries in, classes (+ chunk counts) out
+    unsigned long long ticket = 0;    // one-query calls so far: the word the host waits for
+    double total_training_size = 0;   // 0: nt. PNNwithClustering keeps the full size as denominator (classification.cpp:390,393)
+    bool profiling = false;           // fir_cls_profile_enable: HIP event pairs around the launches of the distance scan
+    std::vector<hipEvent_t> ev;
+    size_t ev_used = 0;
+    ClsDispatch last;
+    // large kNN batches: the matrix cores nominate, float64 re-ranks, the exact scan takes what is not settled (fir_gemm_f64.h)
+    fir_gemm* mm = nullptr;           // created on the first such call
+    bool mm_failed = false;           // ... or not (rows too long, no memory): the exact scan answers
+    int mm_mode = -1;                 // fir_cls_set_knn_mfma: -1 automatic (>= kKnnMfmaQueries queries against a training set streamed from HBM), 0 never, > 0 from that many queries on
+    FirBuf qc;                        // centred queries, row-major
+    FirBuf knn_rows, knn_dist, knn_ok;
+    int64_t mm_queries = 0, mm_unsettled = 0;         // queries that went through the matrix cores / of them sent on to the exact scan
+    std::vector<int32_t> class_off_h;                 // host copy of class_off
+    FirBuf km, km_meta;                               // fir_cls_kmedoids: distance tables + de-tiled rows + candidate sums / descriptors + results
+    // PNN batches on the float64 matrix cores (fir_cls_pnn_mfma.h)
+    int pm_mode = 0;                                  // fir_cls_set_pnn_mfma: 0 never, > 0 from that many queries on, -1 automatic (in this version: never)
+    FirBuf pm_ng, pm_q, pm_flags;                     // max + |g-avg|^2 per row (once per handle); query operands + norms; band flags
+    bool pm_ng_ready = false;
+    int64_t pm_queries = 0, pm_fallback = 0;          // queries that took the form / of them answered by the scan after all
+};
+
+namespace {
+
+// The next free HIP event pair of a profiled handle, NULL when profiling is off or no pair is to be had (grow: 64 more events are
+// created when none is left).
+hipEvent_t* cls_event_pair(fir_cls* c, bool grow = true) {
+    if (!c->profiling) return nullptr;
+    if (grow && c->ev_used + 2 > c->ev.size())
+        for (int i = 0; i < 64; ++i) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) break;
+            c->ev.push_back(e);
+        }
+    return c->ev_used + 2 <= c->ev.size() ? &c->ev[c->ev_used] : nullptr;
+}
+
+// HIP event pair around one launch of the distance scan (no-ops unless fir_cls_profile_enable is on)
+void cls_prof(fir_cls* c, int end, double bytes, const char* kernel) {
+    hipEvent_t* ev = cls_event_pair(c, !end);
+    if (!ev) return;
+    (void)hipEventRecord(ev[end], c->stream);
+    if (!end) return;
+    c->ev_used += 2;
+    c->last.bytes = bytes;
+    c->last.flops = 0.0;                  // a scan launch has no dot-product flops (the matrix-core callers set theirs after this)
+    if (kernel) std::snprintf(c->last.kernel, sizeof c->last.kernel, "%s", kernel);
+}
+
+// Small calls (what a per-image predict() loop makes): the queries are read from, and the class ids written to, pinned
+// host memory by the kernels themselves -- no copy engine, one synchronisation per call.
+constexpr size_t kPinQueryBytes = 256 * 1024;
+constexpr int kPinResults = 4096;                 // int32 slots: classes [0, 2048), chunk counts [2048, 4096)
+bool cls_small(const fir_cls* c, int32_t qb) { return (size_t)qb * c->d * sizeof(double) <= kPinQueryBytes && qb <= kPinResults / 2; }
+int cls_ensure_pin(fir_cls* c) {
+    if (c->pin) return FIR_OK;
+    FIR_HIP(hipHostMalloc(&c->pin, kPinQueryBytes + kPinResults * sizeof(int32_t) + 64, hipHostMallocDefault));
+    std::memset((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t), 0, 64);
+    return FIR_OK;
+}
+int32_t* cls_pin_results(fir_cls* c) { return (int32_t*)((char*)c->pin + kPinQueryBytes); }
+unsigned long long* cls_pin_ticket(fir_cls* c) { return (unsigned long long*)((char*)c->pin + kPinQueryBytes + kPinResults * sizeof(int32_t)); }
+// -> device-visible pointer to the staged queries
+int cls_stage_queries(fir_cls* c, const double* queries, int32_t qb, const double** d_q) {
+    int rc;
+    const size_t bytes = (size_t)qb * c->d * sizeof(double);
+    if (cls_small(c, qb)) {
+        if ((rc = cls_ensure_pin(c))) return rc;
+        std::memcpy(c->pin, queries, bytes);
+        *d_q = (const double*)c->pin;
+        return FIR_OK;
+    }
+    if ((rc = FIR_RESERVE(c->dq, bytes))) return rc;
+    FIR_HIP(hipMemcpyAsync(c->dq.p, queries, bytes, hipMemcpyHostToDevice, c->stream));
+    *d_q = c->dq.as<double>();
+    return FIR_OK;
+}
+
+// Queries per internal batch: the distance table (qb x nt doubles) stays under 1 GiB whatever the caller's batch is.
+int32_t cls_batch(const fir_cls* c) {
+    const int64_t per_query = std::max<int64_t>(c->nt, 1) * (int64_t)sizeof(double);
+    // ... and within gridDim.y of the per-(class, query) kernels (65535)
+    return (int32_t)std::max<int64_t>(kQBBig, std::min<int64_t>(65528, ((int64_t)1 << 30) / per_query / kQBBig * kQBBig));
+}
+// A call cut into internal batches: f(q0, nq) over [0, qb), `batch` queries at a time, until one returns non-zero (which is returned).
+template <typename F>
+int cls_batches(int32_t qb, int32_t batch, F f) {
+    for (int32_t q0 = 0; q0 < qb; q0 += batch) {
+        const int rc = f(q0, std::min(batch, qb - q0));
+        if (rc) return rc;
+    }
+    return FIR_OK;
+}
+
+// ---- the distance scan: sums[q][row] of qb queries into c->sums ----
+// a training set streamed from HBM takes 8 queries per pass (the pass stays HBM-bound), a cache-resident one 4
+bool cls_streams_from_hbm(const fir_cls* c) { return (double)c->tiles * 64.0 * c->dp2 * 16.0 > 256.0 * 1024 * 1024; }
+int cls_scan_waves(const fir_cls* c) { return (int)std::min<int64_t>(std::max<int64_t>((c->tiles + 3) / 4 * 4, 4), (int64_t)c->cus * 16); }
+
+// The forms of the LDS-tile scan by tiles of eight queries per read of the training rows (profiles/r04_k3_forms.txt; 1M x 512, 64 queries,
+// kernel ms per call): one tile, one row per lane 5.7 (HBM-bound, 0.72 of the peak); two tiles 4.16 (round 3); two tiles, two rows per lane
+// 3.90; four tiles, two rows per lane 3.74 -- the f64 vector pipes are then 85-90 % busy at the 1.7 GHz the chip holds under this load
+// (profiles/r04_rocprofv3_pmc_k3.json): that, not the 2.4 GHz issue rate, is the roof. Two rows per lane: every broadcast LDS read of a
+// query value serves two rows (the LDS pipe was two thirds busy at the vector pipes' full rate).
+// FIR_CLS_FORM: tiles per read, rows per lane, threads per workgroup, waves per compute unit, then k_cls_scan_lds's template arguments --
+// the pointer and the reported name come from the same arguments.
+typedef void (*cls_lds_scan_fn)(const double2*, const double*, int64_t, int, int, int, int, double*);
+struct ClsScanForm { int nt, r, block, wpc; cls_lds_scan_fn fn; const char* name; };
+#define FIR_CLS_FORM(NT, R, BLOCK, WPC, ...) {NT, R, BLOCK, WPC, k_cls_scan_lds<__VA_ARGS__>, "fir::k_cls_scan_lds<" #__VA_ARGS__ ">"}
+const ClsScanForm kClsScanTable[] = {
+    FIR_CLS_FORM(4, 2, 512, 8, 2, 4, 512, 2, 2),
+    FIR_CLS_FORM(2, 2, 256, 8, 4, 2, 256, 2, 2),
+    FIR_CLS_FORM(1, 1, 256, 16, 8, 1),
+};
+#undef FIR_CLS_FORM
+constexpr size_t kClsLdsMax = 150 * 1024;         // dynamic LDS the forms of more than one tile may ask for
+// The form of the next launch of a call with `rem` tiles left: as many tiles per read as the call still has and LDS holds
+// (FIR_CLS_ONE_TILE=1: one, for A/B runs), so that no group computes padding tiles.
+const ClsScanForm& cls_scan_form(int rem, size_t lds_tile, bool one_tile) {
+    const ClsScanForm* best = nullptr;             // (the one-tile row always fits: cls_scan takes this path only when one tile fits LDS)
+    for (const ClsScanForm& f : kClsScanTable)
+        if ((f.nt == 1 || (!one_tile && rem >= f.nt && f.nt * lds_tile <= kClsLdsMax)) && (!best || f.nt > best->nt)) best = &f;
+    return *best;
+}
+// Raises the dynamic-LDS limit of every kernel of this translation unit that needs it, once per device (defined at the end of the
+// file, below the headers that hold the other kernels).
+int cls_lds_attributes(const fir_cls* c);
+
+// One query of a cache-resident training set: feature chunks [0, dp2) cut every cstep chunks, the sub-sums sub_stride doubles apart
+void cls_queue_scan_one(fir_cls* c, const double* dq, double* sums, int cstep, int64_t sub_stride) {
+    const int waves = cls_scan_waves(c);
+    hipLaunchKernelGGL(k_cls_scan_one, dim3(waves / 4), dim3(kBlock), (size_t)c->dp2 * 2 * sizeof(double), c->stream, c->gal2, dq, c->avg, c->nt,
+                       (int)c->tiles, c->dp2, c->d, waves, 0, c->dp2, sums, cstep, sub_stride);
+}
+// ... and one pass of nq <= QB queries by the compiler-scheduled scan (through c->qn)
+template <int QB>
+void cls_queue_scan_pass(fir_cls* c, const double* dq, int nq, double* sums, int cstep, int64_t sub_stride) {
+    const int kk = c->dp2 * 2, waves = cls_scan_waves(c);
+    hipLaunchKernelGGL(k_cls_prep_queries<QB>, dim3((kk * QB + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, dq, nq, c->d, c->dp2, c->avg,
+                       c->qn.as<double>());
+    hipLaunchKernelGGL(k_cls_scan<QB>, dim3(waves / 4), dim3(kBlock), 0, c->stream, c->gal2, c->qn.as<double>(), c->nt, (int)c->tiles, c->dp2, c->d,
+                       waves, nq, 0, c->dp2, sums, cstep, sub_stride);
+}
+// The LDS-tile scan: every tile of eight queries of a group in ONE launch (blockIdx.y = group of f.nt consecutive tiles), at most 64
+// tiles per launch; a call is cut into groups of 4, 2, 1 tiles.
+int cls_queue_scan_tiles(fir_cls* c, const double* dq, int32_t qb, size_t lds_tile) {
+    const int kk = c->dp2 * 2, ntile = (qb + 7) / 8;
+    int rc;
+    if ((rc = FIR_RESERVE(c->qn, (size_t)ntile * kk * 8 * sizeof(double)))) return rc;
+    double* qn = c->qn.as<double>();
+    double* sums = c->sums.as<double>();
+    hipLaunchKernelGGL(k_cls_prep_query_tiles, dim3((unsigned)(((size_t)ntile * kk * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, dq, qb, c->d,
+                       c->dp2, c->avg, qn);
+    const bool one_tile = fir_knob_("FIR_CLS_ONE_TILE") != nullptr;
+    if ((rc = cls_lds_attributes(c))) return rc;
+    for (int t0 = 0; t0 < ntile;) {
+        const int rem = ntile - t0;
+        const ClsScanForm& f = cls_scan_form(rem, lds_tile, one_tile);
+        const int groups = std::min(rem / f.nt, 64 / f.nt);
+        const int tn = groups * f.nt;
+        const int wpb = f.block / 64;
+        const int64_t tsteps = (c->tiles + f.r - 1) / f.r;
+        const int wv = (int)std::min<int64_t>(std::max<int64_t>((tsteps + wpb - 1) / wpb * wpb, wpb), (int64_t)c->cus * f.wpc);
+        cls_prof(c, 0, 0.0, nullptr);
+        hipLaunchKernelGGL(f.fn, dim3(wv / wpb, groups), dim3(f.block), (size_t)f.nt * lds_tile, c->stream, c->gal2, qn + (size_t)t0 * kk * 8, c->nt, (int)c->tiles,
+                           c->dp2, wv, std::min(qb - t0 * 8, tn * 8), sums + (size_t)t0 * 8 * c->nt);
+        // algorithmic bytes of the launch: every read of the training rows serves nt tiles of eight queries (+ the query tiles, + the sums written)
+        cls_prof(c, 1, (double)groups * ((double)c->tiles * 64.0 * c->dp2 * 16.0) + (double)tn * ((double)kk * 64.0 + 8.0 * 8.0 * (double)c->nt), f.name);
+        t0 += tn;
+    }
+    return FIR_OK;
+}
+
+int cls_scan(fir_cls* c, const double* queries, int32_t qb) {
+    int rc;
+    const double* dq = nullptr;
+    if ((rc = cls_stage_queries(c, queries, qb, &dq))) return rc;
+    if ((rc = FIR_RESERVE(c->sums, (size_t)qb * std::max<int64_t>(c->nt, 1) * sizeof(double)))) return rc;
+    double* sums = c->sums.as<double>();
+    const bool big = cls_streams_from_hbm(c);
+    const size_t lds_tile = (size_t)(c->dp2 * 2 + 1) * 8 * sizeof(double);
+    const int qbt = big ? kQBBig : kQB;
+    if (qb == 1 && !big) cls_queue_scan_one(c, dq, sums, c->dp2, 0);
+    else if (big && lds_tile <= 64 * 1024) rc = cls_queue_scan_tiles(c, dq, qb, lds_tile);
+    else
+        for (int q0 = 0; q0 < qb; q0 += qbt) {
+            const int nq = std::min(qbt, qb - q0);
+            if (big) cls_queue_scan_pass<kQBBig>(c, dq + (size_t)q0 * c->d, nq, sums + (size_t)q0 * c->nt, c->dp2, 0);
+            else cls_queue_scan_pass<kQB>(c, dq + (size_t)q0 * c->d, nq, sums + (size_t)q0 * c->nt, c->dp2, 0);
+        }
+    if (rc) return rc;
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+
+// ---- the stages behind the scan, each queued on the handle's stream; the caller checks the launches (hipGetLastError) ----
+double cls_var(const fir_cls* c, double var) {                                  // classification.cpp:190-193, 229-233
+    if (var <= 0) { var = 0.00002; if (c->d > 2000) var /= 10; }
+    return var;
+}
+// total_training_size (classification.cpp:244): the rows held, unless fir_cls_set_total_training_size said otherwise
+double cls_total(const fir_cls* c) { return c->total_training_size > 0 ? c->total_training_size : (double)c->nt; }
+
+// c->scores[q][class] <- the PNN class outputs of c->sums
+int cls_queue_pnn(fir_cls* c, int32_t qb, double var) {
+    const int rc = FIR_RESERVE(c->scores, (size_t)qb * c->num_classes * sizeof(double));
+    if (rc) return rc;
+    const double denom = (double)(2 * (size_t)c->d) * var;                       // 2*num_of_cont_features*var, :213
+    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums.as<double>(), c->class_off, c->nt, c->num_classes, denom,
+                       cls_total(c), c->scores.as<double>());
+    return FIR_OK;
+}
+// c->scores[q][class] <- the k-th smallest mean distance per class of c->sums; with_lists: behind them [q][class][k], the k smallest
+// ascending (*lists <- where)
+int cls_queue_knn_kth(fir_cls* c, int32_t qb, int32_t k, bool with_lists, double** lists) {
+    const size_t kth = (size_t)qb * c->num_classes;
+    const int rc = FIR_RESERVE(c->scores, kth * (with_lists ? 1 + (size_t)k : 1) * sizeof(double));
+    if (rc) return rc;
+    double* l = with_lists ? c->scores.as<double>() + kth : nullptr;
+    hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums.as<double>(), c->class_off, c->nt, c->num_classes, c->d, k,
+                       c->scores.as<double>(), l);
+    if (lists) *lists = l;
+    return FIR_OK;
+}
+// dst[q] <- the best class of c->scores (mode 0: PNN arg-max, 1: kNN arg-min), then `ticket` into `word` when there is one
+void cls_queue_argbest(fir_cls* c, int32_t qb, int mode, int32_t* dst, unsigned long long* word = nullptr, unsigned long long ticket = 0) {
+    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores.as<double>(), c->class_off, c->num_classes, mode, dst, word, ticket);
+}
+
+// ---- how a call's classes (and the sequential PNN's chunk counts) reach the caller ----
+// Decided once per call, after its queries are staged: a small call's kernels write into the pinned result slots, a larger one's into
+// c->best, copied out afterwards; a one-query call (ticket_ok: and nothing else to copy) has its last kernel write the call's ticket
+// behind the results, and the host waits for that word instead of synchronising the stream -- the reference's predict() per test vector.
+struct ClsDelivery {
+    int32_t qb;
+    bool small, one;
+    int32_t *cls, *aux;               // where the kernels write the classes / the second array (NULL without one)
+    unsigned long long* word;         // one: the ticket word and the ticket, else NULL and 0
+    unsigned long long ticket;
+};
+int cls_deliver_begin(fir_cls* c, int32_t qb, bool ticket_ok, bool with_aux, ClsDelivery* dl) {
+    dl->qb = qb;
+    dl->small = cls_small(c, qb);
+    dl->one = dl->small && qb == 1 && ticket_ok;
+    const size_t stride = (size_t)std::max(qb, kQB);
+    if (dl->small) {
+        dl->cls = cls_pin_results(c);
+        dl->aux = with_aux ? dl->cls + kPinResults / 2 : nullptr;
+    } else {
+        const int rc = FIR_RESERVE(c->best, (with_aux ? 2 : 1) * stride * sizeof(int32_t));
+        if (rc) return rc;
+        dl->cls = c->best.as<int32_t>();
+        dl->aux = with_aux ? dl->cls + stride : nullptr;
+    }
+    dl->word = dl->one ? cls_pin_ticket(c) : nullptr;
+    dl->ticket = dl->one ? ++c->ticket : 0;
+    return FIR_OK;
+}
+// The end of the call: the copies, the wait, the results out of the pin. Either output may be NULL.
+int cls_deliver_finish(fir_cls* c, const ClsDelivery& dl, int32_t* out_cls, int32_t* out_aux) {
+    const size_t bytes = (size_t)dl.qb * sizeof(int32_t);
+    if (!dl.small) {
+        if (out_cls) FIR_HIP(hipMemcpyAsync(out_cls, dl.cls, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (out_aux) FIR_HIP(hipMemcpyAsync(out_aux, dl.aux, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!dl.one) FIR_HIP(hipStreamSynchronize(c->stream));
+    else if (const int rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)dl.word, dl.ticket)) return rc;
+    if (dl.small) {
+        if (out_cls) std::memcpy(out_cls, dl.cls, bytes);
+        if (out_aux) std::memcpy(out_aux, dl.aux, bytes);
+    }
+    return FIR_OK;
+}
+
+// ---- one internal batch (qb <= cls_batch, the device current) by the exact scan ----
+int cls_pnn_exact(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
+    int rc;
+    ClsDelivery dl;
+    if ((rc = cls_scan(c, queries, qb)) || (rc = cls_deliver_begin(c, qb, !scores, false, &dl)) || (rc = cls_queue_pnn(c, qb, var))) return rc;
+    cls_queue_argbest(c, qb, 0, dl.cls, dl.word, dl.ticket);
+    FIR_HIP(hipGetLastError());
+    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores.p, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return cls_deliver_finish(c, dl, best_class, nullptr);
+}
+
+int cls_knn_exact_batch(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
+    int rc;
+    ClsDelivery dl;
+    if ((rc = cls_scan(c, queries, qb)) || (rc = cls_deliver_begin(c, qb, true, false, &dl)) || (rc = cls_queue_knn_kth(c, qb, k, false, nullptr))) return rc;
+    cls_queue_argbest(c, qb, 1, dl.cls, dl.word, dl.ticket);
+    FIR_HIP(hipGetLastError());
+    return cls_deliver_finish(c, dl, best_class, nullptr);
+}
+// ... and a whole call
+int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
+    FIR_HIP(hipSetDevice(c->device));
+    return cls_batches(qb, cls_batch(c), [&](int32_t q0, int32_t nq) { return cls_knn_exact_batch(c, queries + (size_t)q0 * c->d, nq, k, best_class + q0); });
+}
+
+// ---- the matrix-core forms ----
+// The queries `which` of a batch that a matrix-core form did not settle: gathered, answered by exact(queries, count, scores or NULL,
+// classes), scattered into the batch's results (best_class / scores may be NULL). The dispatch record stays the form's pass either
+// way. The two forms differ in what a profiled call shows of this step, and fir_cls_profile_read's count is theirs to keep: the kNN
+// form's scan launches are timed like any other (timed), the PNN form's are not -- its batch is three event pairs whatever the band
+// sends on.
+template <typename F>
+int cls_answer_exactly(fir_cls* c, const double* queries, const std::vector<int32_t>& which, bool timed, int32_t* best_class, double* scores, F exact) {
+    if (which.empty()) return FIR_OK;
+    const size_t n = which.size(), d = (size_t)c->d, nc = (size_t)c->num_classes;
+    std::vector<double> sub(n * d), sub_scores(scores ? n * nc : 0);
+    std::vector<int32_t> sub_best(n);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&sub[i * d], queries + (size_t)which[i] * d, d * sizeof(double));
+    const ClsDispatch keep = c->last;
+    const bool prof = c->profiling;
+    if (!timed) c->profiling = false;
+    const int rc = exact(sub.data(), (int32_t)n, scores ? sub_scores.data() : nullptr, sub_best.data());
+    c->profiling = prof;
+    if (rc) return rc;
+    c->last = keep;
+    for (size_t i = 0; i < n; ++i) {
+        if (best_class) best_class[which[i]] = sub_best[i];
+        if (scores) std::memcpy(scores + (size_t)which[i] * nc, &sub_scores[i * nc], nc * sizeof(double));
+    }
+    return FIR_OK;
+}
+
+// PNN of one internal batch by the matrix-core form (fir_cls_pnn_mfma.h, included at the end of this file): 0 = answered, 1 = the shape
+// stays with the scan, < 0 = error
+int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class);
+
+// kNN through the matrix cores for the queries of one call (qb <= kKnnMfmaBatch): 0 = best_class filled for every query, 1 = not taken
+// (the exact path answers the call), < 0 = error.
+int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
+    FIR_HIP(hipSetDevice(c->device));
+    if (!c->mm) {
+        const int rc = fir_gemm_create_f64_(c->device, c->cus, c->stream, c->gal2, c->nt, c->d, c->dp2, &c->mm);
+        if (rc) {
+            c->mm = nullptr;
+            if (c->mm_mode > 0 || (rc != FIR_ERR_ARG && rc != FIR_ERR_NOMEM)) return rc;     // asked for explicitly, or a real failure
+            (void)hipGetLastError();
+            c->mm_failed = true;                                                             // automatic: this shape (or this much HBM) stays with the exact scan
+            return 1;
+        }
+    }
+    const int kp = k == 1 ? 1 : 8;           // rows nominated per query: the walk of kNN-K ends inside the 8 nearest rows unless the classes are very mixed
+    int rc;
+    const size_t qbytes = (size_t)qb * c->d * sizeof(double);
+    if ((rc = FIR_RESERVE(c->dq, qbytes)) || (rc = FIR_RESERVE(c->qc, qbytes)) || (rc = FIR_RESERVE(c->knn_rows, (size_t)qb * 8 * sizeof(int32_t))) ||
+        (rc = FIR_RESERVE(c->knn_dist, (size_t)qb * 8 * sizeof(double))) || (rc = FIR_RESERVE(c->knn_ok, (size_t)qb * sizeof(int32_t))) ||
+        (rc = FIR_RESERVE(c->best, (size_t)qb * sizeof(int32_t))))
+        return rc;
+    FIR_HIP(hipMemcpyAsync(c->dq.p, queries, qbytes, hipMemcpyHostToDevice, c->stream));
+    const int64_t count = (int64_t)qb * c->d;
+    hipLaunchKernelGGL(k_cls_center_queries, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->dq.as<double>(), count, c->d, c->avg,
+                       c->qc.as<double>());
+    hipEvent_t* evp = cls_event_pair(c);
+    const char* kname = nullptr;
+    double flops = 0.0;
+    if ((rc = fir_gemm_knn_f64_(c->mm, c->qc.as<double>(), qb, kp, c->knn_rows.as<int32_t>(), c->knn_dist.as<double>(), c->knn_ok.as<int32_t>(), c->stream, &kname,
+                                &flops, evp)))
+        return rc;
+    if (evp) {
+        c->ev_used += 2;
+        c->last.bytes = 0.0;
+        c->last.flops = flops;
+        if (kname) std::snprintf(c->last.kernel, sizeof c->last.kernel, "%s", kname);
+    }
+    hipLaunchKernelGGL(k_cls_knn_vote, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->knn_rows.as<int32_t>(), c->knn_dist.as<double>(),
+                       c->knn_ok.as<int32_t>(), qb, kp, k, c->class_off, c->num_classes, c->best.as<int32_t>());
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(best_class, c->best.p, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
+    c->mm_queries += qb;
+    // what the K' rows did not settle: the exact scan (classification.cpp's own loop over every row)
+    std::vector<int32_t> which;
+    for (int32_t i = 0; i < qb; ++i)
+        if (best_class[i] < 0) which.push_back(i);
+    c->mm_unsettled += (int64_t)which.size();
+    return cls_answer_exactly(c, queries, which, true, best_class, nullptr,
+                              [&](const double* q, int32_t n, double*, int32_t* best) { return cls_knn_exact(c, q, n, k, best); });
+}
+
 }  // namespace
 
 extern "C" {
+
+static int cls_create(const double* train_rows, bool rows_on_device, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
+                      const double* avg, int32_t device, fir_cls** out) {
+    if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (nt < 0 || d <= 0 || num_classes <= 0 || !avg || (nt > 0 && (!train_rows || !train_class)))
+        return fir_fail_(FIR_ERR_ARG, "bad arguments (nt=%lld d=%d classes=%d)", (long long)nt, d, num_classes);
+    if (nt >= ((int64_t)1 << 31) - 64) return fir_fail_(FIR_ERR_ARG, "nt too large");
+    std::vector<int32_t> off((size_t)num_classes + 1, 0);
+    for (int64_t t = 0; t < nt; ++t) {
+        const int32_t cl = train_class[t];
+        if (cl < 0 || cl >= num_classes || (t > 0 && cl < train_class[t - 1]))
+            return fir_fail_(FIR_ERR_ARG, "train_class must be non-decreasing in [0,%d) (row %lld)", num_classes, (long long)t);
+        off[(size_t)cl + 1]++;
+    }
+    for (int i = 0; i < num_classes; ++i) off[(size_t)i + 1] += off[(size_t)i];
+    const int cnt = fir_device_count();        // the guarded first touch of the runtime (fir_runtime_init_)
+    if (cnt <= 0) return fir_fail_(FIR_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", device, cnt);
+    { const int rc0 = fir_runtime_init_(device); if (rc0) return rc0; }
+    hipDeviceProp_t prop;
+    FIR_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fir_fail_(FIR_ERR_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    fir_cls* c = new (std::nothrow) fir_cls();
+    if (!c) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
+    c->device = device;
+    c->cus = prop.multiProcessorCount;
+    c->nt = nt;
+    c->d = d;
+    c->dp2 = (d + 1) / 2;
+    c->num_classes = num_classes;
+    c->tiles = (nt + kTileRows - 1) / kTileRows;
+    c->class_off_h = off;
+    int rc = FIR_OK;
+    FirBuf stage;
+    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    // (four allocations in this order: where the small ones land decides the latency of a two-query call, profiles/cls_host_side.txt)
+    if (e == hipSuccess) e = c->gal2_mem.reserve((size_t)std::max<int64_t>(c->tiles, 1) * c->dp2 * 64 * sizeof(double2));
+    if (e == hipSuccess) e = c->avg_mem.reserve((size_t)d * sizeof(double));
+    if (e == hipSuccess) e = c->qn.reserve((size_t)c->dp2 * 2 * kQBBig * sizeof(double));
+    if (e == hipSuccess) e = c->class_off_mem.reserve(off.size() * sizeof(int32_t));
+    c->gal2 = c->gal2_mem.as<double2>();
+    c->avg = c->avg_mem.as<double>();
+    c->class_off = c->class_off_mem.as<int32_t>();
+    if (e == hipSuccess) e = hipMemcpy(c->avg, avg, (size_t)d * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->class_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    const int64_t slab = std::max<int64_t>(kTileRows, ((int64_t)(256u << 20) / ((int64_t)d * 8)) / kTileRows * kTileRows);
+    if (e == hipSuccess && nt > 0 && !rows_on_device) e = stage.reserve((size_t)std::min<int64_t>(slab, c->tiles * kTileRows) * d * sizeof(double));
+    for (int64_t r0 = 0; e == hipSuccess && r0 < nt; r0 += slab) {
+        const int64_t have = std::min<int64_t>(slab, nt - r0);
+        if (!rows_on_device) e = hipMemcpyAsync(stage.p, train_rows + r0 * d, (size_t)have * d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        const int64_t total = ((have + kTileRows - 1) / kTileRows) * c->dp2 * 64;
+        hipLaunchKernelGGL(k_cls_retile, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                           rows_on_device ? train_rows + r0 * d : stage.as<double>(), have, r0, nt, d, c->dp2, c->avg, c->gal2);
+        e = hipStreamSynchronize(c->stream);
+    }
+    if (e != hipSuccess) rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "training-set upload: %s", hipGetErrorString(e));
+    if (rc) { fir_cls_destroy(c); return rc; }
+    *out = c;
+    return FIR_OK;
+}
+
+int fir_cls_create(const double* train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
+                   const double* avg, int32_t device, fir_cls** out) {
+    return cls_create(train_rows, false, nt, d, train_class, num_classes, avg, device, out);
+}
+
+int fir_cls_create_dev(const double* d_train_rows, int64_t nt, int32_t d, const int32_t* train_class, int32_t num_classes,
+                       const double* avg, int32_t device, fir_cls** out) {
+    return cls_create(d_train_rows, true, nt, d, train_class, num_classes, avg, device, out);
+}
+
+int fir_cls_set_total_training_size(fir_cls* c, int64_t total) {
+    if (!c || total < 0) return fir_fail_(FIR_ERR_ARG, "bad argument");
+    c->total_training_size = (double)total;
+    return FIR_OK;
+}
+
+int fir_cls_profile_enable(fir_cls* c, int32_t on) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    c->profiling = on != 0;
+    c->ev_used = 0;
+    return FIR_OK;
+}
+
+int fir_cls_profile_read(fir_cls* c, float* ms, int32_t cap, int32_t* count, double* bytes_per_launch, char* kernel, int32_t kernel_cap) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(c->device));
+    const int32_t have = (int32_t)(c->ev_used / 2);
+    for (int32_t i = 0; i < have; ++i) {
+        FIR_HIP(hipEventSynchronize(c->ev[2 * (size_t)i + 1]));
+        float t = 0.f;
+        FIR_HIP(hipEventElapsedTime(&t, c->ev[2 * (size_t)i], c->ev[2 * (size_t)i + 1]));
+        if (ms && i < cap) ms[i] = t;
+    }
+    if (count) *count = have;
+    if (bytes_per_launch) *bytes_per_launch = c->last.bytes;
+    if (kernel && kernel_cap > 0) std::snprintf(kernel, (size_t)kernel_cap, "%s", c->last.kernel);
+    c->ev_used = 0;
+    return FIR_OK;
+}
+
+int fir_cls_last_dispatch(fir_cls* c, char* kernel, int32_t kernel_cap, double* bytes_per_launch, double* flops_per_launch) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (kernel && kernel_cap > 0) std::snprintf(kernel, (size_t)kernel_cap, "%s", c->last.kernel);
+    if (bytes_per_launch) *bytes_per_launch = c->last.bytes;
+    if (flops_per_launch) *flops_per_launch = c->last.flops;
+    return FIR_OK;
+}
+
+// The device current and the stream drained, then the handle goes: its FirBuf members free the device memory.
+int fir_cls_destroy(fir_cls* c) {
+    if (!c) return FIR_OK;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+    if (c->mm) (void)fir_gemm_destroy(c->mm);
+    if (c->pin) (void)hipHostFree(c->pin);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+    return FIR_OK;
+}
+
+int fir_cls_distance_sums(fir_cls* c, const double* queries, int32_t qb, double* sums) {
+    if (!c || !sums || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (qb == 0 || c->nt == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(c->device));
+    int rc = cls_scan(c, queries, qb);
+    if (rc) return rc;
+    FIR_HIP(hipMemcpyAsync(sums, c->sums.p, (size_t)qb * c->nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
+    return FIR_OK;
+}
+
+int fir_cls_pnn_predict(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class) {
+    if (!c || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (qb == 0) return FIR_OK;
+    // batches the caller opted in (fir_cls_set_pnn_mfma) take the matrix cores; a one-query call without scores keeps its ticket path
+    const bool routed = c->pm_mode > 0 && qb >= c->pm_mode && c->nt > 0 && !(qb == 1 && !scores);
+    FIR_HIP(hipSetDevice(c->device));
+    var = cls_var(c, var);
+    return cls_batches(qb, cls_batch(c), [&](int32_t q0, int32_t nq) {
+        const double* q = queries + (size_t)q0 * c->d;
+        double* s = scores ? scores + (size_t)q0 * c->num_classes : nullptr;
+        int32_t* b = best_class ? best_class + q0 : nullptr;
+        if (routed) {
+            const int rc = cls_pnn_mfma(c, q, nq, var, s, b);
+            if (rc <= 0) return rc;
+        }
+        return cls_pnn_exact(c, q, nq, var, s, b);
+    });
+}
+
+int fir_cls_set_pnn_mfma(fir_cls* c, int32_t min_queries) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    c->pm_mode = min_queries < 0 ? -1 : min_queries;
+    if (min_queries == 0) {
+        FIR_HIP(hipSetDevice(c->device));
+        FIR_HIP(hipStreamSynchronize(c->stream));
+        c->pm_ng.release(); c->pm_q.release(); c->pm_flags.release();
+        c->pm_ng_ready = false;
+    }
+    return FIR_OK;
+}
+
+int fir_cls_pnn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them) {
+    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (matrix_core_queries) *matrix_core_queries = c->pm_queries;
+    if (exact_scan_queries_of_them) *exact_scan_queries_of_them = c->pm_fallback;
+    return FIR_OK;
+}
+
+// PNN class scores of qb <= *max_batch queries, left on the device (valid until the handle's next call), queued on the
+// handle's stream: the row-sharded PNN (fir_shard.hip) adds the shards' partial sums before the arg-max.
+int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, double var, double** d_scores, void** stream, int32_t* max_batch) {
+    if (!c || !d_scores || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (max_batch) *max_batch = cls_batch(c);
+    if (qb == 0) return FIR_OK;
+    if (qb < 0 || qb > cls_batch(c) || !queries) return fir_fail_(FIR_ERR_ARG, "bad batch %d (at most %d at a time)", qb, cls_batch(c));
+    FIR_HIP(hipSetDevice(c->device));
+    int rc;
+    if ((rc = cls_scan(c, queries, qb)) || (rc = cls_queue_pnn(c, qb, cls_var(c, var)))) return rc;
+    FIR_HIP(hipGetLastError());
+    *d_scores = c->scores.as<double>();
+    *stream = c->stream;
+    return FIR_OK;
+}
+
+// The k smallest mean distances per class of qb <= *max_batch queries, [qb][num_classes][k] ascending (DBL_MAX where the class has
+// fewer rows here), left on the device and queued on the handle's stream: the row-sharded kNN vote (fir_shard.hip) merges them.
+int fir_cls_knn_nearest_dev_(fir_cls* c, const double* queries, int32_t qb, int32_t k, double** d_lists, void** stream, int32_t* max_batch) {
+    if (!c || !d_lists || !stream) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (max_batch) *max_batch = cls_batch(c);
+    if (qb == 0) return FIR_OK;
+    if (qb < 0 || qb > cls_batch(c) || !queries || k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "bad batch %d / k %d", qb, k);
+    FIR_HIP(hipSetDevice(c->device));
+    int rc;
+    if ((rc = cls_scan(c, queries, qb)) || (rc = cls_queue_knn_kth(c, qb, k, true, d_lists))) return rc;
+    FIR_HIP(hipGetLastError());
+    *stream = c->stream;
+    return FIR_OK;
+}
+
+int fir_cls_pnn_predict_seq(fir_cls* c, const double* queries, int32_t qb, double var, int32_t* best_class, int32_t* chunks_out) {
+    if (!c || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if ((size_t)c->num_classes * 16 + 4 > 60 * 1024) return fir_fail_(FIR_ERR_ARG, "num_classes=%d too large for the LDS tables", c->num_classes);
+    if (qb == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(c->device));
+    var = cls_var(c, var);
+    const int nchunks = (c->d + 31) / 32;
+    const int64_t ntp = std::max<int64_t>(c->nt, 1);
+    int rc;
+    const double* dq = nullptr;
+    ClsDelivery dl;
+    if ((rc = cls_stage_queries(c, queries, qb, &dq))) return rc;
+    if ((rc = FIR_RESERVE(c->sums, (size_t)(nchunks + 2) * kQB * ntp * sizeof(double)))) return rc;       // chunk sums + running sums + their exp()
+    if ((rc = cls_deliver_begin(c, qb, true, true, &dl))) return rc;                                      // second array: the chunk counts
+    if ((rc = FIR_RESERVE(c->scores, (size_t)kQB * nchunks * c->num_classes * sizeof(double)))) return rc;   // k_cls_pnn_seq_par's table
+    double* sums = c->sums.as<double>();
+    double* table = c->scores.as<double>();
+    double* run = sums + (size_t)nchunks * kQB * ntp;
+    const double den = cls_total(c);
+    for (int q0 = 0; q0 < qb; q0 += kQB) {
+        const int nq = std::min(kQB, qb - q0);
+        // all 32-feature chunk sums (16 double2 chunks each) from one pass: chunk ch lands at sums + ch * nq * nt
+        if (qb == 1) cls_queue_scan_one(c, dq, sums, 16, (int64_t)c->nt);
+        else cls_queue_scan_pass<kQB>(c, dq + (size_t)q0 * c->d, nq, sums, 16, (int64_t)nq * c->nt);
+        const size_t flags_lds = ((size_t)c->num_classes + 1) / 2 * 8, table_lds = (size_t)nchunks * c->num_classes * 8;
+        const int table_in_lds = flags_lds + table_lds <= 48 * 1024;
+        if (c->nt <= kSeqParRows && flags_lds <= 48 * 1024) {
+            hipLaunchKernelGGL(k_cls_pnn_seq_par, dim3(c->num_classes, nchunks, nq), dim3(64), 0, c->stream, sums, nq, nchunks, c->class_off, c->nt,
+                               c->num_classes, c->d, var, den, table);
+            hipLaunchKernelGGL(k_cls_pnn_seq_walk, dim3(nq), dim3(64), flags_lds + (table_in_lds ? table_lds : 0), c->stream, table, nchunks,
+                               c->num_classes, dl.cls + q0, dl.aux + q0, table_in_lds, dl.word, dl.ticket);
+        } else {
+            hipLaunchKernelGGL(k_cls_pnn_seq, dim3(nq), dim3(kSeqBlock), (size_t)c->num_classes * 16 + 4, c->stream, sums, nq, nchunks, run,
+                               run + (size_t)kQB * ntp, c->class_off, c->nt, c->num_classes, c->d, var, den, dl.cls + q0, dl.aux + q0, dl.word, dl.ticket);
+        }
+    }
+    FIR_HIP(hipGetLastError());
+    return cls_deliver_finish(c, dl, best_class, chunks_out);
+}
 
 int fir_cls_set_knn_mfma(fir_cls* c, int32_t min_queries) {
     if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
@@ -1234,16 +1366,6 @@ int fir_cls_knn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_s
     return FIR_OK;
 }
 
-int fir_cls_last_dispatch(fir_cls* c, char* kernel, int32_t kernel_cap, double* bytes_per_launch, double* flops_per_launch) {
-    if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (kernel && kernel_cap > 0) std::snprintf(kernel, (size_t)kernel_cap, "%s", c->last_kernel);
-    if (bytes_per_launch) *bytes_per_launch = c->last_bytes;
-    if (flops_per_launch) *flops_per_launch = c->last_flops;
-    return FIR_OK;
-}
-
-static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class);
-
 int fir_cls_knn_predict(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
     if (!c || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
@@ -1251,157 +1373,52 @@ int fir_cls_knn_predict(fir_cls* c, const double* queries, int32_t qb, int32_t k
     if (qb == 0) return FIR_OK;
     // Large batches against a training set that streams from HBM: the matrix cores nominate the K' nearest rows, float64 re-ranks them,
     // the vote is taken over those; what that does not settle falls through to the exact scan below (fir_gemm_f64.h). Same classes.
-    const bool big = (double)c->tiles * 64.0 * c->dp2 * 16.0 > 256.0 * 1024 * 1024;
-    const bool want = c->mm_mode > 0 ? qb >= c->mm_mode : (c->mm_mode < 0 && big && qb >= kKnnMfmaQueries);
+    const bool want = c->mm_mode > 0 ? qb >= c->mm_mode : (c->mm_mode < 0 && cls_streams_from_hbm(c) && qb >= kKnnMfmaQueries);
     if (want && !c->mm_failed && c->nt > 0) {
-        const int32_t b = 16384;                   // queries per internal batch of the matrix-core path (its scratch: two copies of the queries, 8 rows + distances per query)
-        bool all = true;
-        for (int32_t q0 = 0; q0 < qb && all; q0 += b) {
-            const int rc0 = cls_knn_mfma(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), k, best_class + q0);
-            if (rc0 < 0) return rc0;
-            if (rc0 == 1) { if (q0 != 0) return fir_fail_(FIR_ERR_STATE, "the matrix-core kNN path stopped in the middle of a call"); all = false; }
-        }
-        if (all) return FIR_OK;
+        const int rc = cls_batches(qb, kKnnMfmaBatch, [&](int32_t q0, int32_t nq) {
+            const int rc0 = cls_knn_mfma(c, queries + (size_t)q0 * c->d, nq, k, best_class + q0);
+            return rc0 == 1 && q0 != 0 ? fir_fail_(FIR_ERR_STATE, "the matrix-core kNN path stopped in the middle of a call") : rc0;
+        });
+        if (rc <= 0) return rc;                    // answered, or failed; 1: the first batch was not taken, the exact scan answers the call
     }
     return cls_knn_exact(c, queries, qb, k, best_class);
 }
-
-static int cls_knn_exact(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
-    if (qb > cls_batch(c)) {
-        const int32_t b = cls_batch(c);
-        for (int32_t q0 = 0; q0 < qb; q0 += b) {
-            const int rc0 = cls_knn_exact(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), k, best_class + q0);
-            if (rc0) return rc0;
-        }
-        return FIR_OK;
-    }
-    FIR_HIP(hipSetDevice(c->device));
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
-    hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, c->d, k, c->scores,
-                       (double*)nullptr);
-    const bool small = cls_small(c, qb);
-    int32_t* dbest = small ? cls_pin_results(c) : c->best;
-    const bool one = small && qb == 1;
-    const unsigned long long ticket = one ? ++c->ticket : 0;
-    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 1, dbest,
-                       one ? cls_pin_ticket(c) : (unsigned long long*)nullptr, ticket);
-    FIR_HIP(hipGetLastError());
-    if (!small) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (one) { if ((rc = fir_wait_ticket_(c->stream, (volatile uint64_t*)cls_pin_ticket(c), ticket))) return rc; }
-    else FIR_HIP(hipStreamSynchronize(c->stream));
-    if (small) std::memcpy(best_class, dbest, (size_t)qb * sizeof(int32_t));
-    return FIR_OK;
-}
-
-}  // extern "C"
-
-namespace {
-int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
-    FIR_HIP(hipSetDevice(c->device));
-    if (!c->mm) {
-        const int rc = fir_gemm_create_f64_(c->device, c->cus, c->stream, c->gal2, c->nt, c->d, c->dp2, &c->mm);
-        if (rc) {
-            c->mm = nullptr;
-            if (c->mm_mode > 0 || (rc != FIR_ERR_ARG && rc != FIR_ERR_NOMEM)) return rc;     // asked for explicitly, or a real failure
-            (void)hipGetLastError();
-            c->mm_failed = true;                                                             // automatic: this shape (or this much HBM) stays with the exact scan
-            return 1;
-        }
-    }
-    const int kp = k == 1 ? 1 : 8;           // rows nominated per query: the walk of kNN-K ends inside the 8 nearest rows unless the classes are very mixed
-    int rc;
-    if ((rc = cls_grow(c->dq, c->dq_cap, (size_t)qb * c->d))) return rc;
-    if ((rc = cls_grow(c->qc, c->qc_cap, (size_t)qb * c->d))) return rc;
-    if ((rc = cls_grow(c->knn_rows, c->knn_rows_cap, (size_t)qb * 8))) return rc;
-    if ((rc = cls_grow(c->knn_dist, c->knn_dist_cap, (size_t)qb * 8))) return rc;
-    if ((rc = cls_grow(c->knn_ok, c->knn_ok_cap, (size_t)qb))) return rc;
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
-    FIR_HIP(hipMemcpyAsync(c->dq, queries, (size_t)qb * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int64_t count = (int64_t)qb * c->d;
-    hipLaunchKernelGGL(k_cls_center_queries, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->dq, count, c->d, c->avg, c->qc);
-    hipEvent_t* evp = nullptr;
-    if (c->profiling) {
-        if (c->ev_used + 2 > c->ev.size())
-            for (int i = 0; i < 64; ++i) {
-                hipEvent_t e;
-                if (hipEventCreate(&e) != hipSuccess) break;
-                c->ev.push_back(e);
-            }
-        if (c->ev_used + 2 <= c->ev.size()) evp = &c->ev[c->ev_used];
-    }
-    const char* kname = nullptr;
-    double flops = 0.0;
-    if ((rc = fir_gemm_knn_f64_(c->mm, c->qc, qb, kp, c->knn_rows, c->knn_dist, c->knn_ok, c->stream, &kname, &flops, evp))) return rc;
-    if (evp) {
-        c->ev_used += 2;
-        c->last_bytes = 0.0;
-        c->last_flops = flops;
-        if (kname) std::snprintf(c->last_kernel, sizeof c->last_kernel, "%s", kname);
-    }
-    hipLaunchKernelGGL(k_cls_knn_vote, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->knn_rows, c->knn_dist, c->knn_ok, qb, kp, k, c->class_off, c->num_classes,
-                       c->best);
-    FIR_HIP(hipGetLastError());
-    FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FIR_HIP(hipStreamSynchronize(c->stream));
-    c->mm_queries += qb;
-    // what the K' rows did not settle: the exact scan (classification.cpp's own loop over every row), a tile of queries at a time
-    std::vector<int32_t> which;
-    for (int32_t i = 0; i < qb; ++i)
-        if (best_class[i] < 0) which.push_back(i);
-    if (!which.empty()) {
-        c->mm_unsettled += (int64_t)which.size();
-        std::vector<double> sub(which.size() * (size_t)c->d);
-        for (size_t i = 0; i < which.size(); ++i) std::memcpy(&sub[i * (size_t)c->d], queries + (size_t)which[i] * c->d, (size_t)c->d * sizeof(double));
-        std::vector<int32_t> cls(which.size());
-        char keep[sizeof c->last_kernel];
-        std::memcpy(keep, c->last_kernel, sizeof keep);
-        const double keep_flops = c->last_flops;
-        if ((rc = cls_knn_exact(c, sub.data(), (int32_t)which.size(), k, cls.data()))) return rc;
-        for (size_t i = 0; i < which.size(); ++i) best_class[which[i]] = cls[i];
-        if (evp) {                                       // the call's dominant kernel stays the matrix-core pass
-            std::memcpy(c->last_kernel, keep, sizeof keep);
-            c->last_flops = keep_flops;
-            c->last_bytes = 0.0;
-        }
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" {
 
 int fir_cls_knn_class_nearest(fir_cls* c, const double* queries, int32_t qb, int32_t k, double* nearest) {
     if (!c || !nearest || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     if (qb == 0) return FIR_OK;
-    const size_t per_query = (size_t)c->num_classes * k;
-    if (qb > cls_batch(c)) {
-        const int32_t b = cls_batch(c);
-        for (int32_t q0 = 0; q0 < qb; q0 += b) {
-            const int rc0 = fir_cls_knn_class_nearest(c, queries + (size_t)q0 * c->d, std::min(b, qb - q0), k, nearest + (size_t)q0 * per_query);
-            if (rc0) return rc0;
-        }
-        return FIR_OK;
-    }
     FIR_HIP(hipSetDevice(c->device));
-    int rc = cls_scan(c, queries, qb);
-    if (rc) return rc;
-    // scores: [qb][num_classes] k-th values, then [qb][num_classes][k] lists
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes * (1 + (size_t)k)))) return rc;
-    double* lists = c->scores + (size_t)qb * c->num_classes;
-    hipLaunchKernelGGL(k_cls_knn_kth, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, c->d, k, c->scores,
-                       lists);
-    FIR_HIP(hipGetLastError());
-    FIR_HIP(hipMemcpyAsync(nearest, lists, (size_t)qb * per_query * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FIR_HIP(hipStreamSynchronize(c->stream));
-    return FIR_OK;
+    const size_t per_query = (size_t)c->num_classes * k;
+    return cls_batches(qb, cls_batch(c), [&](int32_t q0, int32_t nq) {
+        int rc;
+        double* lists = nullptr;
+        if ((rc = cls_scan(c, queries + (size_t)q0 * c->d, nq)) || (rc = cls_queue_knn_kth(c, nq, k, true, &lists))) return rc;
+        FIR_HIP(hipGetLastError());
+        FIR_HIP(hipMemcpyAsync(nearest + (size_t)q0 * per_query, lists, (size_t)nq * per_query * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FIR_HIP(hipStreamSynchronize(c->stream));
+        return (int)FIR_OK;
+    });
 }
 
 }  // extern "C"
 
 #include "fir_cls_kmedoids.h"
 #include "fir_cls_pnn_mfma.h"
+
+namespace {
+int cls_lds_attributes(const fir_cls* c) {
+    static bool done[64] = {};                    // (per device: the attribute belongs to the device's copy of the code object)
+    const int dv = c->device & 63;
+    if (done[dv]) return FIR_OK;
+    std::vector<std::pair<const void*, size_t>> need = {{(const void*)k_cls_pnn_mfma<2>, kPmLdsMax},
+                                                        {(const void*)k_cls_pnn_mfma<1>, kPmLdsMax},
+                                                        {(const void*)k_kmed_iterate, (size_t)kKmMaxClusters * 16 + kKmMaxRows * 2}};
+    for (const ClsScanForm& f : kClsScanTable)
+        if (f.nt > 1) need.push_back({(const void*)f.fn, kClsLdsMax});       // (one tile fits the default limit, or the scan does not take this path)
+    for (const auto& n : need) FIR_HIP(hipFuncSetAttribute(n.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n.second));
+    done[dv] = true;
+    return FIR_OK;
+}
+}  // namespace

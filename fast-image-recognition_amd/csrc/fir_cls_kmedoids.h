@@ -253,8 +253,8 @@ extern "C" int fir_cls_kmedoids(fir_cls* c, int32_t num_clusters, int32_t steps,
     // device scratch: tables of a group | its de-tiled rows | the candidates' sums; descriptors: table offsets | query blocks | results
     const size_t b_table = up256((size_t)max_table * 8), b_qn = up256((size_t)max_qb * kk * kKmQB * 8), b_col = up256((size_t)std::max<int64_t>(c->nt, 1) * 8);
     const size_t b_toff = up256((size_t)nc * 8), b_qd = up256(qdesc.size() * sizeof(int2)), b_res = (size_t)nc * (K + 2) * sizeof(int32_t);
-    FIR_HIP(c->km.reserve(b_table + b_qn + b_col));
-    FIR_HIP(c->km_meta.reserve(b_toff + b_qd + b_res));
+    int rc;
+    if ((rc = FIR_RESERVE(c->km, b_table + b_qn + b_col)) || (rc = FIR_RESERVE(c->km_meta, b_toff + b_qd + b_res)) || (rc = cls_lds_attributes(c))) return rc;
     double* d_table = c->km.as<double>();
     double* d_qn = (double*)(c->km.as<char>() + b_table);
     double* d_col = (double*)(c->km.as<char>() + b_table + b_qn);
@@ -267,14 +267,6 @@ extern "C" int fir_cls_kmedoids(fir_cls* c, int32_t num_clusters, int32_t steps,
     for (const Group& g : groups) {
         const int nqb = g.qb1 - g.qb0;
         const size_t lds = (size_t)K * 16 + (((size_t)g.max_n * 2 + 15) & ~(size_t)15);
-        if (lds > 48 * 1024) {
-            static bool attr_set[64] = {};                                          // (per device, as in cls_scan)
-            const int dv = c->device & 63;
-            if (!attr_set[dv]) {
-                FIR_HIP(hipFuncSetAttribute((const void*)k_kmed_iterate, hipFuncAttributeMaxDynamicSharedMemorySize, kKmMaxClusters * 16 + kKmMaxRows * 2));
-                attr_set[dv] = true;
-            }
-        }
         if (nqb > 0) {
             const int64_t total = (int64_t)nqb * kk * kKmQB;
             hipLaunchKernelGGL(k_kmed_detile, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->gal2, c->dp2, c->class_off,

@@ -209,18 +209,10 @@ int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, doub
     typedef void (*mfma_fn)(const double2*, const double2*, const double*, const double*, int64_t, int, int, int, double*);
     const mfma_fn fn = nqt == 32 ? k_cls_pnn_mfma<2> : k_cls_pnn_mfma<1>;
     const char* name = nqt == 32 ? "fir::k_cls_pnn_mfma<2>" : "fir::k_cls_pnn_mfma<1>";
-    {
-        static bool attr_set[64] = {};                     // (per device, as in cls_scan)
-        const int dv = c->device & 63;
-        if (!attr_set[dv]) {
-            FIR_HIP(hipFuncSetAttribute((const void*)k_cls_pnn_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPmLdsMax));
-            FIR_HIP(hipFuncSetAttribute((const void*)k_cls_pnn_mfma<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPmLdsMax));
-            attr_set[dv] = true;
-        }
-    }
+    if ((rc = cls_lds_attributes(c))) return rc;
     // |g-avg|^2 per row: word 0 of the buffer is the maximum, the norms follow
     if (!c->pm_ng_ready) {
-        FIR_HIP(c->pm_ng.reserve(((size_t)c->nt + 1) * sizeof(double)));
+        if ((rc = FIR_RESERVE(c->pm_ng, ((size_t)c->nt + 1) * sizeof(double)))) return rc;
         FIR_HIP(hipMemsetAsync(c->pm_ng.p, 0, sizeof(double), c->stream));
         hipLaunchKernelGGL(k_cls_row_norms, dim3((unsigned)((c->nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, c->gal2, c->nt, c->dp2,
                            c->pm_ng.as<double>() + 1, c->pm_ng.as<unsigned long long>());
@@ -232,43 +224,41 @@ int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, doub
     const int groups = (qb + nqt - 1) / nqt, slots = groups * nqt;
     const double* dq = nullptr;
     if ((rc = cls_stage_queries(c, queries, qb, &dq))) return rc;
-    if ((rc = cls_grow(c->qc, c->qc_cap, (size_t)qb * c->d))) return rc;
-    if ((rc = cls_grow(c->sums, c->sums_cap, (size_t)qb * c->nt))) return rc;
-    if ((rc = cls_grow(c->scores, c->scores_cap, (size_t)qb * c->num_classes))) return rc;
-    if ((rc = cls_grow(c->best, c->best_cap, (size_t)qb))) return rc;
     const size_t qp_count = (size_t)groups * c->dp2 * nqt;                     // double2 each, then the query norms
-    FIR_HIP(c->pm_q.reserve(qp_count * sizeof(double2) + (size_t)slots * sizeof(double)));
-    FIR_HIP(c->pm_flags.reserve((size_t)qb * sizeof(int32_t)));
+    if ((rc = FIR_RESERVE(c->qc, (size_t)qb * c->d * sizeof(double))) || (rc = FIR_RESERVE(c->sums, (size_t)qb * c->nt * sizeof(double))) ||
+        (rc = FIR_RESERVE(c->scores, (size_t)qb * c->num_classes * sizeof(double))) ||     // (before anything is queued: not inside cls_queue_pnn's event pair)
+        (rc = FIR_RESERVE(c->best, (size_t)qb * sizeof(int32_t))) || (rc = FIR_RESERVE(c->pm_q, qp_count * sizeof(double2) + (size_t)slots * sizeof(double))) ||
+        (rc = FIR_RESERVE(c->pm_flags, (size_t)qb * sizeof(int32_t))))
+        return rc;
     double2* qp = c->pm_q.as<double2>();
     double* nqv = (double*)(qp + qp_count);
     int32_t* flags = c->pm_flags.as<int32_t>();
     const int64_t count = (int64_t)qb * c->d;
-    hipLaunchKernelGGL(k_cls_center_queries, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, dq, count, c->d, c->avg, c->qc);
-    hipLaunchKernelGGL(k_cls_pnn_prep, dim3(slots / (kBlock / 64)), dim3(kBlock), 0, c->stream, c->qc, qb, c->d, c->dp2, nqt, qp, nqv);
+    hipLaunchKernelGGL(k_cls_center_queries, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, dq, count, c->d, c->avg, c->qc.as<double>());
+    hipLaunchKernelGGL(k_cls_pnn_prep, dim3(slots / (kBlock / 64)), dim3(kBlock), 0, c->stream, c->qc.as<double>(), qb, c->d, c->dp2, nqt, qp, nqv);
     const int wgs = (int)std::min<int64_t>((c->tiles + kPmBlock / 64 - 1) / (kPmBlock / 64), c->cus);
     const size_t lds = (size_t)nqt * per_query;
     // profiled: three event pairs per batch, in this order -- the matrix-core pass, k_cls_pnn, k_cls_pnn_band; the dispatch record is the first's
     cls_prof(c, 0, 0.0, nullptr);
-    hipLaunchKernelGGL(fn, dim3(wgs, groups), dim3(kPmBlock), lds, c->stream, c->gal2, qp, nqv, ng, c->nt, (int)c->tiles, c->dp2, qb, c->sums);
+    hipLaunchKernelGGL(fn, dim3(wgs, groups), dim3(kPmBlock), lds, c->stream, c->gal2, qp, nqv, ng, c->nt, (int)c->tiles, c->dp2, qb, c->sums.as<double>());
     cls_prof(c, 1, 0.0, name);
-    const double denom = (double)(2 * (size_t)c->d) * var;                       // 2*num_of_cont_features*var, :213
     cls_prof(c, 0, 0.0, nullptr);
-    hipLaunchKernelGGL(k_cls_pnn, dim3(c->num_classes, qb), dim3(64), 0, c->stream, c->sums, c->class_off, c->nt, c->num_classes, denom,
-                       c->total_training_size > 0 ? c->total_training_size : (double)c->nt, c->scores);
+    if ((rc = cls_queue_pnn(c, qb, var))) return rc;
     cls_prof(c, 1, 0.0, nullptr);
-    hipLaunchKernelGGL(k_cls_argbest, dim3(qb), dim3(64), 0, c->stream, c->scores, c->class_off, c->num_classes, 0, c->best, (unsigned long long*)nullptr, 0ull);
+    cls_queue_argbest(c, qb, 0, c->best.as<int32_t>());
     cls_prof(c, 0, 0.0, nullptr);
-    hipLaunchKernelGGL(k_cls_pnn_band, dim3(qb), dim3(64), 0, c->stream, c->scores, c->num_classes, nqv, ng_max, 2.0 * 0x1p-53 * (double)(c->d + 2) / denom, flags);
+    hipLaunchKernelGGL(k_cls_pnn_band, dim3(qb), dim3(64), 0, c->stream, c->scores.as<double>(), c->num_classes, nqv, ng_max,
+                       2.0 * 0x1p-53 * (double)(c->d + 2) / ((double)(2 * (size_t)c->d) * var), flags);
     cls_prof(c, 1, 0.0, nullptr);
     if (c->profiling) {
         // algorithmic bytes of the pass: one read of the training rows (and their norms) per group of queries, the query operands, the sums written
-        c->last_bytes = (double)groups * ((double)c->tiles * 64.0 * c->dp2 * 16.0 + 8.0 * (double)c->nt) + (double)groups * (double)lds + 8.0 * (double)qb * (double)c->nt;
-        c->last_flops = 2.0 * (double)c->nt * (double)c->d * (double)qb;
+        c->last.bytes = (double)groups * ((double)c->tiles * 64.0 * c->dp2 * 16.0 + 8.0 * (double)c->nt) + (double)groups * (double)lds + 8.0 * (double)qb * (double)c->nt;
+        c->last.flops = 2.0 * (double)c->nt * (double)c->d * (double)qb;
     }
     FIR_HIP(hipGetLastError());
     std::vector<int32_t> hflags((size_t)qb);
-    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (best_class) FIR_HIP(hipMemcpyAsync(best_class, c->best, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (scores) FIR_HIP(hipMemcpyAsync(scores, c->scores.p, (size_t)qb * c->num_classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (best_class) FIR_HIP(hipMemcpyAsync(best_class, c->best.p, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     FIR_HIP(hipMemcpyAsync(hflags.data(), flags, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     FIR_HIP(hipStreamSynchronize(c->stream));
     c->pm_queries += qb;
@@ -276,22 +266,9 @@ int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, doub
     std::vector<int32_t> which;
     for (int32_t i = 0; i < qb; ++i)
         if (hflags[(size_t)i]) which.push_back(i);
-    if (which.empty()) return 0;
     c->pm_fallback += (int64_t)which.size();
-    const size_t d = (size_t)c->d, nc = (size_t)c->num_classes;
-    std::vector<double> sub(which.size() * d), sub_scores(scores ? which.size() * nc : 0);
-    std::vector<int32_t> sub_best(which.size());
-    for (size_t i = 0; i < which.size(); ++i) std::memcpy(&sub[i * d], queries + (size_t)which[i] * d, d * sizeof(double));
-    const bool prof = c->profiling;                      // the scan of these few queries is not bracketed: a profiled batch stays three event pairs and
-    c->profiling = false;                                // the dispatch record stays the matrix-core pass
-    rc = cls_pnn_exact(c, sub.data(), (int32_t)which.size(), var, scores ? sub_scores.data() : nullptr, sub_best.data());
-    c->profiling = prof;
-    if (rc) return rc;
-    for (size_t i = 0; i < which.size(); ++i) {
-        if (best_class) best_class[which[i]] = sub_best[i];
-        if (scores) std::memcpy(scores + (size_t)which[i] * nc, &sub_scores[i * nc], nc * sizeof(double));
-    }
-    return 0;
+    return cls_answer_exactly(c, queries, which, false, best_class, scores,
+                              [&](const double* q, int32_t n, double* sc, int32_t* best) { return cls_pnn_exact(c, q, n, var, sc, best); });
 }
 
 }  // namespace

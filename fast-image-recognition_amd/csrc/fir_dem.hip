@@ -795,10 +795,10 @@ int dem_recognize_prepare(fir_dem* h) {
 // finished with the old buffer; a quarter more than asked for, zero-filled.
 int dem_grow(fir_dem* h, FirBuf& b, size_t bytes) {
     if (bytes <= b.cap) return FIR_OK;
-    const int rc = fir_gallery_wait_calls_(h->g);
+    int rc = fir_gallery_wait_calls_(h->g);
     if (rc) return rc;
     FIR_HIP(hipStreamSynchronize(h->v.stream));
-    FIR_HIP(b.reserve(bytes + bytes / 4));
+    if ((rc = FIR_RESERVE(b, bytes + bytes / 4))) return rc;
     FIR_HIP(hipMemset(b.p, 0, b.cap));
     return FIR_OK;
 }

@@ -79,6 +79,14 @@ struct FirBuf {
     }
     template <typename T> T* as() const { return (T*)p; }
 };
+// FIR_RESERVE(buffer, bytes): buffer.reserve(bytes) as a return code on the library's error path -- FIR_ERR_NOMEM when the device
+// has no memory left, FIR_ERR_HIP otherwise --, the message naming the buffer and the place of the call as FIR_HIP's does.
+inline int fir_reserve_(FirBuf& b, size_t bytes, const char* what, const char* file, int line) {
+    const hipError_t e = b.reserve(bytes);
+    if (e == hipSuccess) return FIR_OK;
+    return fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "%s.reserve(%zu) failed: %s (%s:%d)", what, bytes, hipGetErrorString(e), file, line);
+}
+#define FIR_RESERVE(buf, bytes) fir_reserve_(buf, bytes, #buf, __FILE__, __LINE__)
 extern "C" void fir_set_last_error_(const char* msg);    // a message kept aside earlier (fir_shard.hip: another rank's or worker's error)
 // Every environment knob the library honours goes through here: getenv(name), and a set one is remembered (once) in the list
 // fir_gallery_last_dispatch reports in fir_dispatch_info::knobs -- a stray variable in a production environment is visible.
