@@ -43,6 +43,7 @@ SYMBOLS = [
     ("fir_gallery_set_metric", C.c_int, [_vp, C.c_int32]),
     ("fir_gallery_set_row_offset", C.c_int, [_vp, C.c_int64]),
     ("fir_gallery_set_large_batch_mfma", C.c_int, [_vp, C.c_int32]),
+    ("fir_gallery_set_int8_nomination", C.c_int, [_vp, C.c_int32]),
     ("fir_feature_distance", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p]),
     ("fir_search_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_top1_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
@@ -284,6 +285,10 @@ class Gallery:
 
     def set_large_batch_mfma(self, min_queries):
         _check(lib().fir_gallery_set_large_batch_mfma(self._h, min_queries))
+
+    def set_int8_nomination(self, mode):
+        """-1: the library's rule, 0: never, 1: every eligible large L2 top-1 call nominates on the int8 matrix cores"""
+        _check(lib().fir_gallery_set_int8_nomination(self._h, mode))
 
     def set_shadow_copies(self, mode):
         _check(lib().fir_gallery_set_shadow_copies(self._h, mode))

@@ -75,6 +75,7 @@ struct fir_gallery {
     // L2 whole-range batches of at least this many queries go through fir_gemm_* (same keys): -1 = automatic
     // (kAutoMfmaQueries queries against at least kAutoMfmaRows rows), 0 = never, > 0 = the caller's threshold
     int large_batch_min = -1;
+    int int8_mode = -1;       // fir_gallery_set_int8_nomination: -1 = automatic, 0 = never, 1 = every eligible call
     // the matrix-core states of the last TWO feature prefixes [0, end) asked for: the reference's harness alternates "BF, 64" and
     // "BF, 256" (ImageTesting.cpp:526-529); one slot would rebuild fragments and scratch on every call
     struct PrefixSlot { fir_gemm* m = nullptr; int end = 0; uint64_t used = 0; } gemm_prefix[2];
@@ -1242,6 +1243,13 @@ int fir_gallery_set_large_batch_mfma(fir_gallery* g, int32_t min_queries) {
     return FIR_OK;
 }
 
+int fir_gallery_set_int8_nomination(fir_gallery* g, int32_t mode) {
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
+    if (mode < -1 || mode > 1) return fir_fail_(FIR_ERR_ARG, "int8 nomination mode %d outside [-1,1]", mode);
+    g->int8_mode = mode;
+    return FIR_OK;
+}
+
 int fir_gallery_mfma_stats_ex(fir_gallery* g, int64_t out[3]) {
     if (!g || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     int64_t o[3];
@@ -1391,6 +1399,9 @@ int try_mfma(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     fir_gemm* m = nullptr;
     const int rc = g->n < kAutoMfmaRows ? ensure_gemm(g, end, &m, &g->small_hits, 3) : ensure_gemm(g, end, &m);
     if (rc) return rc;
+    // the int8 nomination (fir_gemm.hip: gemm_wants_i8_): the caller's switch; by itself only where the matrix cores were chosen
+    // automatically, for the whole row, over at least kAutoMfmaRows rows
+    fir_gemm_set_int8_(m, g->int8_mode > 0 ? 1 : (g->int8_mode < 0 && g->large_batch_min < 0 && end == g->d && g->n >= kAutoMfmaRows) ? -1 : 0);
     const int rcs = h_queries ? fir_gemm_search_staged_(m, h_queries, (float*)d_queries, qb, 1, d_keys, st)
                               : fir_gemm_search_top1_keys_dev(m, d_queries, qb, d_keys, st);
     if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {       // no room for this call's candidate lists: the exact scan answers (automatic mode)

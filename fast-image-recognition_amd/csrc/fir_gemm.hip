@@ -35,6 +35,9 @@ namespace {
 
 using fir::kKeyNone;
 
+#ifndef FIR_I8_AUTO_MIN_QUERIES
+#define FIR_I8_AUTO_MIN_QUERIES 2048      // (0 compiles the automatic int8 rule out: gemm_wants_i8_)
+#endif
 #ifndef FIR_GEMM_BLOCK
 #define FIR_GEMM_BLOCK 512
 #endif
@@ -741,6 +744,7 @@ __global__ void __launch_bounds__(256) k_gemm_tau(const float* __restrict__ samp
 }
 
 #include "fir_gemm_fb.h"
+#include "fir_gemm_i8.h"
 
 // The K nearest rows of every query (K <= KMAX; KMAX = 1: the nearest row, K a constant) from its candidate list: every appended
 // entry inside the window of the K-th smallest proxy of the list (rerank_window_; a list of fewer than K is re-ranked whole) is
@@ -754,7 +758,10 @@ __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __
                                                      const float* __restrict__ queries, const float* __restrict__ qnorm,
                                                      const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset,
                                                      float e_rel, int ngroup, int k_arg, unsigned long long* __restrict__ out_key,
-                                                     int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor, const RerankFb fb) {
+                                                     int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor, const RerankFb fb,
+                                                     const float* __restrict__ eabs = nullptr) {
+    // eabs != NULL (an int8 super-batch, fir_gemm_i8.h): qnorm, gnorm_max_p and the proxies are those of the CENTRED vectors and the
+    // windows carry eabs[q]; the distances below are still the reference's, on the rows and queries as they are
     const int k = KMAX == 1 ? 1 : k_arg;
     // q: the query's scratch slot (lists, counts, tau, qnorm); qo: its place in queries / out_key / ok -- the same for a super-batch's
     // own re-rank, the query's index in the call for a second-chance round (fir_gemm_fb.h)
@@ -771,7 +778,7 @@ __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __
     const unsigned long long kth = list_kth_smallest_(L, have, k, lane, found);
     const float qn = qnorm[q], gmax = gnorm_max_p[0];
     const float pk = found == k ? fir::f32_from_orderable((uint32_t)(kth >> 32)) : __builtin_huge_valf();
-    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, pk);
+    const RerankWindow w = eabs ? rerank_window_(e_rel, qn, gmax, d, pk, eabs[q]) : rerank_window_(e_rel, qn, gmax, d, pk);
     extern __shared__ __attribute__((aligned(16))) float4 crow[];
     const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)qo * qstride, lane);
     unsigned long long best[KMAX];
@@ -808,7 +815,7 @@ __global__ void __launch_bounds__(64) k_gemm_rerank(const unsigned long long* __
         const bool certified = rerank_certified_<float>(cnt, t, walk.p_out, qn, d, w.E, kth_exact != kKeyNone,
                                                         fir::f32_from_orderable((uint32_t)(kth_exact >> 32)), n, walk.reranked);
         ok[qo] = certified ? 1 : 0;
-        if (!certified && fb.list && !fb.qmap) rerank_hand_over_(fb, q, cnt, t, pk, qn, gmax, e_rel);
+        if (!certified && fb.list && !fb.qmap) rerank_hand_over_(fb, q, cnt, t, pk, qn, gmax, e_rel, eabs);
     }
 }
 
@@ -1106,6 +1113,25 @@ struct fir_gemm {
     int last_kind = 0;
     int last_b = 0, last_nq = 0;          // ... the scratch set of its last super-batch and that super-batch's queries
     int last_sc_rounds = 0;               // ... the second-chance rounds it queued
+    bool last_i8 = false;                 // ... and whether it took the int8 pass (its norms and maximum are then the centred ones)
+    // The int8 nomination of large top-1 batches (fir_gemm_i8.h). The query fragments, norms and scales of an int8 super-batch use the
+    // fp16 flow's scratch (an int8 tile is never larger); what is listed here is what it holds on top, built by the first call that takes it.
+    int i8_mode = 0;                      // what the gallery handle allows the next call (fir_gemm_set_int8_): 0 never, 1 every eligible call, -1 the automatic rule
+    bool i8_built = false, i8_off = false;   // i8_off: this gallery went back to fp16 for good (the automatic rule's R / G, or too many second passes)
+    const char* i8_off_why = "";
+    std::string i8_note;                  // the kernel name fir_gallery_last_dispatch reports for a call that would have been int8 but for i8_off
+    int dk8 = 0;                          // one-KiB int8 pieces per row block: whole units of 256 features
+    uint4* g8 = nullptr;                  // the int8 copy
+    float* i8_mu = nullptr;               // column means
+    float* i8_gnorm = nullptr;            // |c_g|^2
+    float* i8_par = nullptr;              // max|c_g|, s_g, G^2, R (fir_gemm_i8.h)
+    float* i8_eabs[2] = {nullptr, nullptr};
+    float* sc_eabs = nullptr;
+    float i8_R = 0.f, i8_G = 0.f;         // host copies, read once when the copy is built
+    int* i8_pin = nullptr;                // pinned: the second-pass counter of the most recent int8 call, copied behind it ...
+    hipEvent_t i8_ev = nullptr;           // ... and the event that says it has arrived (queried, never waited for)
+    bool i8_pending = false;
+    int i8_pending_qb = 0;
 };
 
 // The knobs every kind of state honours (this file's and fir_gemm_f64.h's): each is read once, when the state is created.
@@ -1131,14 +1157,16 @@ struct RerankSlot {
     const int* counts;
     const float* tau;
     const float* qnorm;
+    const float* eabs = nullptr;          // an int8 super-batch: the per-query absolute term, and the centred rows' largest norm
+    const float* gmax = nullptr;
 };
 // dynamic LDS of the f32 re-rank kernels: rerank_group candidate rows and the query (rerank_lds_f32_)
 static size_t gemm_rerank_lds_(const fir_gemm* m) { return (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4); }
 static void gemm_launch_rerank_(fir_gemm* m, hipStream_t st, int nq, const RerankSlot& s, const float* d_queries, float e_rel, int k, uint64_t* out_key, int* ok,
                                 const RerankFb& fb) {
     hipLaunchKernelGGL(k == 1 ? k_gemm_rerank<1> : k_gemm_rerank<kTopKMax>, dim3(nq), dim3(64), gemm_rerank_lds_(m), st, s.lists, s.counts, s.tau, m->gal4, d_queries,
-                       s.qnorm, (const float*)m->gmax, m->v.n, m->feat, m->dp4, m->v.row_offset, e_rel, m->rerank_group, k, (unsigned long long*)out_key, ok, m->v.d,
-                       (const float4*)m->rowmajor, fb);
+                       s.qnorm, s.gmax ? s.gmax : (const float*)m->gmax, m->v.n, m->feat, m->dp4, m->v.row_offset, e_rel, m->rerank_group, k, (unsigned long long*)out_key,
+                       ok, m->v.d, (const float4*)m->rowmajor, fb, s.eabs);
 }
 
 // fp16: up to kShareMax pairs of passes (x 128 queries) read the gallery together in one launch (k_gemm_proxy_f16x, `share`). Rows longer
@@ -1149,6 +1177,7 @@ static bool gemm_streamed_(const fir_gemm* m) { return m->dk16 > kSlabH; }
 // fp16: units (of kRing pieces) per row block as the kernels' ODD has them -- 0 = an even number, 1 = an odd one from three on, 2 = ONE
 // unit. Every launch of a 16-row kernel takes its form from here: an ODD = 1 kernel walks a first, a middle and a last unit at least.
 static int gemm_odd_(const fir_gemm* m) { return m->dk16 == kRing ? 2 : (m->dk16 / kRing) & 1; }
+static int gemm_odd8_(const fir_gemm* m) { return m->dk8 == kRing ? 2 : (m->dk8 / kRing) & 1; }       // ... the int8 form's: units of 256 features
 // pairs of passes the next launch takes: the largest power of two within what is left and within cap
 static int launch_pairs_(int left, int cap) {
     int P = 1;
@@ -1213,13 +1242,43 @@ static fir_x_fn pick_x(int mode, bool streamed, int odd, int dbg = 0, int njb = 
 #endif
     return find_x(mode, streamed, odd, dbg ? 8 : njb).fn;
 }
-// every kernel of the table may take the whole query tile as dynamic LDS
+// The int8 form of the pass (fir_gemm_i8.h): resident tiles only, the threshold found on the way (3) and the second-chance rounds'
+// append below tau (1), by units of 256 features per row: 0 = an even number (512, 1 024 features), 1 = three (768), 2 = one (<= 256).
+struct fir_x8_entry {
+    int mode, odd;
+    fir_x_fn fn;
+    const char* name;
+};
+#define FIR_X8(M, O) {M, O, k_gemm_proxy_f16x<M, 0, O, 0, 8, 1>, "fir::k_gemm_proxy_i8x<" #M ", " #O ">"}
+static const fir_x8_entry kX8Table[] = {FIR_X8(3, 0), FIR_X8(3, 1), FIR_X8(3, 2), FIR_X8(1, 0), FIR_X8(1, 1), FIR_X8(1, 2)};
+#undef FIR_X8
+static const fir_x8_entry& find_x8(int mode, int odd) {
+    for (const fir_x8_entry& e : kX8Table)
+        if (e.mode == mode && e.odd == odd) return e;
+    return kX8Table[0];
+}
+// every kernel of the two tables may take the whole query tile as dynamic LDS
 static hipError_t gemm_x_lds_attr_() {
     for (const fir_x_entry& e : kXTable) {
         const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
         if (err != hipSuccess) return err;
     }
+    for (const fir_x8_entry& e : kX8Table) {
+        const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
+        if (err != hipSuccess) return err;
+    }
     return hipSuccess;
+}
+
+// (the int8 copy and what goes with it; also what a build that ran out of memory gives back)
+static void gemm_free_i8_(fir_gemm* m) {
+    (void)hipFree(m->g8); (void)hipFree(m->i8_mu); (void)hipFree(m->i8_gnorm); (void)hipFree(m->i8_par); (void)hipFree(m->i8_eabs[0]); (void)hipFree(m->i8_eabs[1]);
+    (void)hipFree(m->sc_eabs);
+    if (m->i8_pin) (void)hipHostFree(m->i8_pin);
+    if (m->i8_ev) (void)hipEventDestroy(m->i8_ev);
+    m->g8 = nullptr; m->i8_mu = m->i8_gnorm = m->i8_par = m->i8_eabs[0] = m->i8_eabs[1] = m->sc_eabs = nullptr;
+    m->i8_pin = nullptr; m->i8_ev = nullptr;
+    m->i8_built = false;
 }
 
 extern "C" {
@@ -1242,7 +1301,12 @@ void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowm
     sc += (int64_t)m->ok_cap * 16 + 32;                                                           // certificate flags, the two lists of uncertified queries, their bounds
     if (m->sc_lists) sc += (int64_t)kScQueries * kListCap * 8 + (int64_t)4 * m->dk16 * 1024 + (int64_t)kScQueries * 20;   // one pair's second-chance scratch
     if (m->proxies) sc += (int64_t)m->proxies_nq * np * 4;
-    if (fragments) *fragments = fr;
+    int64_t fr8 = 0;
+    if (m->g8) {                                                                                  // the int8 copy and what goes with it
+        fr8 = rblocks * m->dk8 * 1024;
+        sc += np * 4 + (int64_t)((m->feat + 3) / 4) * 16 + 32 + 2 * (int64_t)kPasses * kQT * 4 + (int64_t)kScQueries * 4;
+    }
+    if (fragments) *fragments = fr + fr8;
     if (rowmajor) *rowmajor = rm;
     if (scratch) *scratch = sc;
 }
@@ -1426,6 +1490,7 @@ int fir_gemm_destroy(fir_gemm* m) {
     (void)hipFree(m->fb_state); (void)hipFree(m->fb_list); (void)hipFree(m->fb_list2); (void)hipFree(m->fb_tau2);
     (void)hipFree(m->sc_qnorm); (void)hipFree(m->sc_qmul); (void)hipFree(m->sc_qinv); (void)hipFree(m->sc_tau); (void)hipFree(m->sc_counts);
     (void)hipFree(m->sc_lists); (void)hipFree(m->sc_qbf);
+    gemm_free_i8_(m);
         if (m->copy) { (void)hipStreamSynchronize(m->copy); (void)hipStreamDestroy(m->copy); }
     for (int b = 0; b < 2; ++b) if (m->copy_done[b]) (void)hipEventDestroy(m->copy_done[b]);
     delete m;
@@ -1476,11 +1541,25 @@ int fir_gemm_stats(const fir_gemm* m, int64_t* passes, int64_t* fallback_queries
 
 // Everything a call still owes its uncertified queries, queued on `st` behind the last re-rank (fir_gemm_fb.h): second-chance rounds
 // (sc_rounds > 0: the 16-row fp16 flow only), the collection of what is left, the exact device scan (K launches for the K nearest).
-static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds, bool streamed) {
+static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds, bool streamed, bool i8 = false) {
     const int d = m->feat, qs = m->v.d;
     const int64_t n = m->v.n;
     for (int r = 0; r < sc_rounds; ++r) {
         const int off = r * kScQueries;
+        if (i8) {
+            // (an int8 call's rounds stay int8: tau2 is in the units of the centred int8 proxies)
+            hipLaunchKernelGGL(k_gemm_qprep_i8, dim3(kScQueries), dim3(64), 0, st, d_queries, kScQueries, d, qs, (const float*)m->i8_mu, (const float*)m->i8_par, e_rel,
+                               m->erel_scale, m->sc_qnorm, m->sc_qmul, m->sc_qinv, m->sc_eabs, m->sc_counts, (float*)nullptr, (unsigned int*)nullptr, (int*)nullptr,
+                               (const int*)m->fb_state, (const int*)m->fb_list, off, (const float*)m->fb_tau2, m->sc_tau);
+            hipLaunchKernelGGL(k_gemm_pack_queries_i8, dim3((4 * m->dk8 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, m->dk8, (const float*)m->i8_mu,
+                               (const float*)m->sc_qmul, m->sc_qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
+            hipLaunchKernelGGL(find_x8(1, gemm_odd8_(m)).fn, dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->g8, m->i8_gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
+                               (int64_t)0, n, m->dk8, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
+                               (unsigned int*)m->fb_state, off);
+            gemm_launch_rerank_(m, st, kScQueries, {m->sc_lists, m->sc_counts, m->sc_tau, m->sc_qnorm, m->sc_eabs, m->i8_par + 2}, d_queries, e_rel, k, d_keys, m->ok,
+                                {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
+            continue;
+        }
         hipLaunchKernelGGL(k_gemm_sc_prep, dim3(kScQueries), dim3(64), 0, st, d_queries, d, qs, m->gallery_exp, (const int*)m->fb_state, (const int*)m->fb_list, off,
                            (const float*)m->fb_tau2, m->sc_qnorm, m->sc_qmul, m->sc_qinv, m->sc_tau, m->sc_counts);
         hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, m->dk16, (const float*)m->sc_qmul,
@@ -1535,10 +1614,98 @@ struct GemmCall {
     bool streamed;              // fp16: gemm_streamed_
     int odd;                    // fp16: units per row block -- 0 = an even number, 1 = an odd one, 2 = one unit (the kernels' ODD)
     size_t lds;                 // f32 / bf16: dynamic LDS of the pass kernels
+    bool i8 = false;            // this call's passes are the int8 form (gemm_wants_i8_): odd is then in units of 256 features, streamed false
+    bool i8_went_back = false;  // the automatic rule would have taken the int8 pass, but this gallery went back to fp16: last_dispatch says so
 
     int sb_queries(int sb) const { return std::min(sbq, qb - sb * sbq); }
     const float* sb_first(int sb) const { return d_queries + (size_t)sb * sbq * qs; }
 };
+
+// ---- the int8 nomination: which calls take it, and the copy they need (fir_gemm_i8.h) ----
+// The automatic rule's two constants, measured on one MI355X at 1M x 512 (profiles/int8_nomination.txt, tools/int8_nomination_sweep.py;
+// fp16 -> int8, M queries/s, identical keys, no second pass anywhere):
+//   kI8AutoMinQueries, the smallest call the rule sends to the int8 pass: 2 048 queries per call 1.09 -> 1.90 (x 1.73), 8 192 1.31 -> 2.27,
+//     32 768 1.38 -> 2.39, 131 072 1.40 -> 2.43; 512 still gains (0.99 -> 1.37) but was measured once only and stays fp16. 0 compiles
+//     the rule out: only fir_gallery_set_int8_nomination(g, 1) then reaches the pass.
+//   kI8AutoMaxRG, the largest R / G (the worst row's quantisation residual over the largest centred norm) it is taken at: one row in a
+//     thousand with one outlier coordinate of growing size, 32 768 queries per call -- R / G 0.0047 (none) x 1.73, 0.0053 x 1.71, 0.0084
+//     x 1.62, 0.0123 x 1.43, 0.0162 x 1.08, 0.0206 x 0.62 (the lists reach into the tail of the row distances), 0.037 x 0.012 (nearly
+//     every query ends in the exact device scan). The limit sits behind the last clear gain.
+constexpr int kI8AutoMinQueries = FIR_I8_AUTO_MIN_QUERIES;
+constexpr float kI8AutoMaxRG = 0.0125f;
+static int gemm_build_i8_(fir_gemm* m, hipStream_t st) {
+    const int64_t n = m->v.n, rblocks = (std::max<int64_t>(n, 1) + 31) / 32, tiles = (n + 63) / 64;
+    const int d4 = (m->feat + 3) / 4;
+    m->dk8 = (m->feat + 32 * kRing - 1) / (32 * kRing) * kRing;
+    double* partial = nullptr;
+    FIR_HIP(hipMalloc((void**)&m->g8, (size_t)rblocks * m->dk8 * 64 * sizeof(uint4)));
+    FIR_HIP(hipMalloc((void**)&m->i8_mu, (size_t)d4 * 4 * sizeof(float)));
+    FIR_HIP(hipMalloc((void**)&m->i8_gnorm, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
+    FIR_HIP(hipMalloc((void**)&m->i8_par, 8 * sizeof(float)));
+    for (int b = 0; b < 2; ++b) FIR_HIP(hipMalloc((void**)&m->i8_eabs[b], kPasses * kQT * sizeof(float)));
+    FIR_HIP(hipMalloc((void**)&m->sc_eabs, kScQueries * sizeof(float)));
+    FIR_HIP(hipHostMalloc((void**)&m->i8_pin, 64, hipHostMallocDefault));
+    FIR_HIP(hipEventCreateWithFlags(&m->i8_ev, hipEventDisableTiming));
+    FIR_HIP(hipMalloc((void**)&partial, (size_t)kI8Slices * d4 * 4 * sizeof(double)));
+    hipLaunchKernelGGL(k_i8_colsum, dim3(d4, kI8Slices), dim3(256), 0, st, m->gal4, tiles, m->dp4, partial);
+    hipLaunchKernelGGL(k_i8_mean, dim3((d4 * 4 + 255) / 256), dim3(256), 0, st, (const double*)partial, d4, m->feat, n, m->i8_mu, m->i8_par);
+    hipLaunchKernelGGL(k_i8_rows<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->feat, (const float*)m->i8_mu, m->i8_gnorm, m->i8_par);
+    hipLaunchKernelGGL(k_i8_scale, dim3(1), dim3(1), 0, st, m->i8_par);
+    hipLaunchKernelGGL(k_i8_rows<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->feat, (const float*)m->i8_mu, m->i8_gnorm, m->i8_par);
+    const int64_t total = rblocks * m->dk8 * 64;
+    hipLaunchKernelGGL(k_i8_pack_gallery, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->dk8, m->feat, (const float*)m->i8_mu,
+                       (const float*)m->i8_par, m->g8);
+    float h[4] = {0.f, 0.f, 0.f, 0.f};
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h, m->i8_par, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);                  // the copy's one synchronisation
+    (void)hipFree(partial);
+    FIR_HIP(e);
+    m->i8_G = std::sqrt(h[2]);
+    m->i8_R = h[3];
+    m->i8_built = true;
+    return FIR_OK;
+}
+// L2 (every fir_gemm state is), top-1, the whole row of at most 1 024 features (the 128-query int8 tile is resident), more than 32
+// queries (the few-block forms stay fp16), the fp16 state of an f32 gallery. i8_mode 1 takes every such call; -1 (the gallery handle
+// sets it for automatic matrix-core dispatch over at least kAutoMfmaRows rows only) asks the rule, and goes back to fp16 for good
+// when more than one query in sixteen of an int8 call needed a second pass -- seen without waiting: the counter is copied to pinned
+// memory behind the call and looked at here only once its event has fired.
+static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
+    *out = false;
+    if (m->i8_pending) {
+        const hipError_t eq = hipEventQuery(m->i8_ev);
+        if (eq == hipSuccess) {
+            m->i8_pending = false;
+            if ((int64_t)m->i8_pin[0] * 16 > (int64_t)m->i8_pending_qb) { m->i8_off = true; m->i8_off_why = "second passes"; }
+        } else if (eq == hipErrorNotReady) (void)hipGetLastError();     // (not an error: the counter is looked at by a later call)
+    }
+    if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.k != 1 || c.num_classes > 0 || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
+        c.qb <= 32 || m->dbg_skip)
+        return FIR_OK;
+    if (m->i8_mode < 0 && (kI8AutoMinQueries <= 0 || c.qb < kI8AutoMinQueries)) return FIR_OK;
+    if (m->i8_mode < 0 && m->i8_off) { c.i8_went_back = true; return FIR_OK; }
+    if (!m->i8_built && m->i8_off) { c.i8_went_back = true; return FIR_OK; }      // (the copy could not be built: not tried again)
+    if (!m->i8_built) {
+        const int rc = gemm_build_i8_(m, c.st);
+        if (rc) {
+            // No room for the copy: in EVERY mode this call and all later ones are answered by the fp16 pass (the same keys), what was
+            // allocated is given back, and fir_gallery_last_dispatch says "int8 nomination off for this gallery: no memory". Any other
+            // failure is the call's error.
+            (void)hipGetLastError();
+            gemm_free_i8_(m);
+            if (rc != FIR_ERR_NOMEM) return rc;
+            m->i8_off = true; m->i8_off_why = "no memory";
+            c.i8_went_back = true;
+            return FIR_OK;
+        }
+        if (!(m->i8_R <= kI8AutoMaxRG * m->i8_G)) { m->i8_off = true; m->i8_off_why = "R / G"; }
+    }
+    if (m->i8_mode < 0 && m->i8_off) { c.i8_went_back = true; return FIR_OK; }
+    if (!m->i8_built) return FIR_OK;
+    *out = true;
+    return FIR_OK;
+}
 
 // Which fp16 super-batches find their threshold on the way. Until round 4's second half the answer depended on how many row groups a
 // workgroup sees ((row groups) * (pairs per launch) / CUs: below a dozen the bound is still loose when the workgroup ends, 1 000-2 400
@@ -1609,6 +1776,14 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
     const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;        // 128 queries per gallery read; a half-filled pair is zero-padded
     const float* dq = c.sb_first(sb);
+    if (c.i8) {                                             // (fir_gemm_i8.h: always the threshold found on the way)
+        hipLaunchKernelGGL(k_gemm_qprep_i8, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, c.d, c.qs, (const float*)m->i8_mu, (const float*)m->i8_par, c.e_rel,
+                           m->erel_scale, m->qnorm[b], m->qmul[b], m->qinv[b], m->i8_eabs[b], m->counts[b], m->awin[b], m->aT[b], sb == 0 ? m->fb_state : (int*)nullptr,
+                           (const int*)nullptr, (const int*)nullptr, 0, (const float*)nullptr, (float*)nullptr);
+        hipLaunchKernelGGL(k_gemm_pack_queries_i8, dim3((4 * m->dk8 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk8, (const float*)m->i8_mu,
+                           (const float*)m->qmul[b], m->qbf[b], c.qs);
+        return FIR_OK;
+    }
     const bool adaptive = adaptive_for_(m, c, nq);
     // (the candidate counts are cleared, the call's two list lengths by its first super-batch and, for the adaptive pass, the per-query
     // windows and start values are set by the same launch)
@@ -1709,6 +1884,26 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
     const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;
     const int64_t n = c.n;
+    if (c.i8) {
+        // the int8 form: the same launches over the int8 copy -- half the pieces per row block, the centred rows' norms
+        auto bytes8 = [&](int P) { return (double)((n + 31) / 32) * m->dk8 * 1024.0 + P * (4.0 * m->dk8 * 1024.0 + 128.0 * 8.0); };
+        const fir_x8_entry& ran8 = find_x8(3, c.odd);
+        int nl = 0, pf = 1, rc8 = FIR_OK;
+        for (int p0 = 0; p0 < pairs; ++nl) {
+            const int P = launch_pairs_(pairs - p0, kShareMax);
+            if (p0 == 0) pf = P;
+            const size_t qo = (size_t)p0;
+            if ((rc8 = fir_gallery_profile_begin_(m->g, c.st))) return rc8;
+            hipLaunchKernelGGL(ran8.fn, dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->g8, m->i8_gnorm, m->qbf[b] + qo * 4 * m->dk8 * 64, m->qinv[b] + qo * 2 * kQT,
+                               n, (int64_t)0, n, m->dk8, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT,
+                               m->qnorm[b] + qo * 2 * kQT, m->sample_rows, P, (P <= 1 ? 1 : 0) | m->adapt_dbg, 1, m->aT[b] + qo * 2 * kQT, 0);
+            if ((rc8 = fir_gallery_profile_end_(m->g, c.st, bytes8(P)))) return rc8;
+            p0 += P;
+        }
+        fir_gallery_note_dispatch_(m->g, (const void*)ran8.fn, ran8.name, sb == 0, c.grid, nl, kGemmBlock, kHalfLds, 128 * pf, bytes8(pf), 2.0 * (double)n * c.d * 128.0 * pf);
+        hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, 0);
+        return FIR_OK;
+    }
     const bool adaptive = adaptive_for_(m, c, nq);
     // (a super-batch of at most 16 / 32 queries: one / two query blocks of the tile are live -- the pass multiplies against those only;
     // whole, even numbers of the form's units per row: eight pieces streamed, sixteen resident)
@@ -1738,7 +1933,12 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
         p0 += P;
     }
     const fir_x_entry& ran = find_x(mode, c.streamed, c.odd, njb);
-    fir_gallery_note_dispatch_(m->g, (const void*)ran.fn, ran.name, sb == 0, c.grid, nlaunch, kGemmBlock, kHalfLds, 128 * p_first, launch_bytes(p_first),
+    const char* ran_name = ran.name;
+    if (c.i8_went_back) {
+        if (sb == 0) m->i8_note = std::string(ran.name) + " (int8 nomination off for this gallery: " + m->i8_off_why + ")";
+        ran_name = m->i8_note.c_str();
+    }
+    fir_gallery_note_dispatch_(m->g, (const void*)ran.fn, ran_name, sb == 0, c.grid, nlaunch, kGemmBlock, kHalfLds, 128 * p_first, launch_bytes(p_first),
                                2.0 * (double)n * c.d * 128.0 * p_first);
     if (adaptive)
         hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, k > 1 ? k : 0);
@@ -1781,8 +1981,8 @@ static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs)
                            c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
                            c.qs, m->rowmajor);
     else
-        gemm_launch_rerank_(m, rs, nq, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b]}, c.sb_first(sb), c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0,
-                            {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
+        gemm_launch_rerank_(m, rs, nq, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b], c.i8 ? m->i8_eabs[b] : nullptr, c.i8 ? m->i8_par + 2 : nullptr}, c.sb_first(sb),
+                            c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0, {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
 }
 
 #ifdef FIR_AUDIT
@@ -1873,12 +2073,18 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
                       : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
     c.streamed = gemm_streamed_(m);
     c.odd = gemm_odd_(m);
+    {
+        const int rc8 = gemm_wants_i8_(m, c, &c.i8);
+        if (rc8) return rc8;
+    }
+    if (c.i8) { c.streamed = false; c.odd = gemm_odd8_(m); }
     c.lds = m->precision == FIR_GEMM_F32 ? (size_t)(kQT / 32) * std::min(m->dq8, kSlab8) * 64 * sizeof(float4)
                                          : (size_t)(kQT / 32) * std::min(m->dk16, kSlab16) * 128 * sizeof(uint4);
     // fp16: both operands rounded to 11 bits -> |q~.g~ - q.g| <= (2^-10 + 2^-22) sum|q_k g_k| + the sub-normal tails
     // (< 2^-27 |q||g| for d <= 2^20), doubled in p and with |q||g| <= (|q|^2 + max|g|^2) / 2: 2^-10 (1 + 2^-4) covers it
     c.e_rel = m->erel_scale * (8.0f * (float)c.d * 5.9604645e-8f +
               (m->precision == FIR_GEMM_BF16_SPLIT ? 6.1035156e-5f : m->precision == FIR_GEMM_F16 ? 9.765625e-4f * 1.0625f : 0.0f));
+    if (c.i8) c.e_rel = m->erel_scale * (8.0f * (float)c.d * 5.9604645e-8f);      // int8: what is not relative is the query's eabs (fir_gemm_i8.h)
     // Large super-batches amortise the boundaries between full passes (where the small kernels run: they cannot share a CU with a
     // full-pass workgroup), but a call needs a few super-batches for its preparation / re-rank to overlap anything: a quarter of the
     // call, in whole 1 024-query launches.
@@ -1920,7 +2126,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     }
     if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(st, m->rerank_done[(c.nsb - 1) & 1], 0));   // join the side stream (it is in order: the last re-rank is the last thing on it)
     FIR_HIP(hipGetLastError());
-    m->last_kind = 1; m->last_b = (c.nsb - 1) & 1; m->last_nq = c.sb_queries(c.nsb - 1); m->last_sc_rounds = 0;
+    m->last_kind = 1; m->last_b = (c.nsb - 1) & 1; m->last_nq = c.sb_queries(c.nsb - 1); m->last_sc_rounds = 0; m->last_i8 = c.i8;
 #ifdef FIR_AUDIT
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
@@ -1930,10 +2136,20 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
     const int sc_rounds = m->precision == FIR_GEMM_F16 && qb > 32 ? std::min(kScRounds, (qb + kScQueries - 1) / kScQueries) : 0;
     m->last_sc_rounds = sc_rounds;
-    return gemm_finish_(m, d_queries, k, d_keys, st, c.e_rel, sc_rounds, c.streamed);
+    if ((rc = gemm_finish_(m, d_queries, k, d_keys, st, c.e_rel, sc_rounds, c.streamed, c.i8))) return rc;
+    if (c.i8 && m->i8_mode < 0 && !m->i8_pending) {
+        // (the automatic rule's way back, gemm_wants_i8_: how many queries of this call needed a second pass, copied behind the call)
+        FIR_HIP(hipMemcpyAsync(m->i8_pin, m->fb_state, sizeof(int), hipMemcpyDeviceToHost, st));
+        FIR_HIP(hipEventRecord(m->i8_ev, st));
+        m->i8_pending = true;
+        m->i8_pending_qb = qb;
+    }
+    return FIR_OK;
 }
 
 extern "C" {
+
+void fir_gemm_set_int8_(fir_gemm* m, int32_t mode) { if (m) m->i8_mode = mode > 0 ? 1 : mode < 0 ? -1 : 0; }
 
 int fir_gemm_search_top1_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, uint64_t* d_keys, void* stream) {
     return gemm_search(m, d_queries, qb, 1, d_keys, stream);
@@ -2016,7 +2232,7 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
                         {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0});
     FIR_HIP(hipGetLastError());
     m->passes += 1;
-    m->last_kind = 2; m->last_b = b; m->last_nq = qb; m->last_sc_rounds = 0;
+    m->last_kind = 2; m->last_b = b; m->last_nq = qb; m->last_sc_rounds = 0; m->last_i8 = false;
     // (the bound of this form already is the smallest proxy of ALL rows + one window: a second pass could not do better; what is
     // not certified -- NaN operands, thousands of ties -- goes to the exact device scan, in stream order)
     return gemm_finish_(m, d_queries, 1, d_keys, st, e_rel, 0, gemm_streamed_(m));
@@ -2047,7 +2263,7 @@ int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, in
         else { off = (rounds - 1) * kScQueries; have = std::min(kScQueries, cnt - off); }
     }
     if (live) *live = have;
-    if (gmax) FIR_HIP(hipMemcpy(gmax, m->gmax, sizeof(float), hipMemcpyDeviceToHost));
+    if (gmax) FIR_HIP(hipMemcpy(gmax, m->last_i8 ? m->i8_par + 2 : m->gmax, sizeof(float), hipMemcpyDeviceToHost));
     if (nq == 0) return FIR_OK;
     if (q0 + nq > have) return fir_fail_(FIR_ERR_ARG, "slots [%d,%d) of %d", q0, q0 + nq, have);
     const int* d_counts = which ? m->sc_counts : m->counts[b];

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // rows of the tiled f32 gallery * scale (a power of two) -> 16-row fragment order (see above), round to nearest even
 // kmax: features [0, kmax) of every row are packed, the rest of the fragments is zero (kmax = dp4 * 4: the whole row)
@@ -77,6 +78,15 @@ __global__ void __launch_bounds__(256) k_gemm_pack_queries_f16x(const float* q, 
     qh[o] = u;
 }
 
+// the MFMA of the 16-row kernels by accumulator type: f32 sums of fp16 products, or (the int8 form) i32 sums of the same registers' bytes
+__device__ __forceinline__ f32x4 mfma_x_(const f16x8 a, const f16x8 b, const f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ i32x4 mfma_x_(const f16x8 a, const f16x8 b, const i32x4 c) {
+    i32x4 ai, bi;
+    __builtin_memcpy(&ai, &a, 16);
+    __builtin_memcpy(&bi, &b, 16);
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(ai, bi, c, 0, 0, 0);
+}
+
 // One wave: 32 rows x 128 queries. Dynamic LDS: kHalfLds. All per-pass scratch is laid out pass-major (128 consecutive queries
 // per pair of passes). Which pair and which row groups a workgroup takes:
 // share == 0: blockIdx.y = pair, row groups blockIdx.x, + gridDim.x, ...
@@ -129,7 +139,13 @@ constexpr int kXStage = 16;             // staged appends per query and workgrou
 // touched -- as runtime flags the two tests made the row loop spill): bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no
 // re-read of the query fragments, bit 5 = no MFMAs. The answers of such a kernel are wrong. (Right answers, for A/B runs: bit 7 = static
 // ownership of the row blocks, bit 8 = timestamps of workgroup 0's waves.)
-template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8>
+// I8: the int8 form (v_mfma_i32_16x16x64_i8, twice the features per instruction). A one-KiB piece is then 16 rows x 64 features -- lane
+// l holds row l & 15, the sixteen features 64 kk + 16 (l >> 4) + 0..15 as bytes -- so a unit of kRing pieces is 256 features and the loop
+// over `dk16` pieces is the fp16 form's at half the features: the gallery is `g8` of fir_gemm_i8.h (rows minus the column means, one
+// scale), `gnorm` the norms of the centred rows, `qinv` 1 / (s_q s_g). The sums are exact integers (|sum| <= 1024 * 127^2 < 2^24: their
+// conversion to f32 is exact); the check takes the lane's maximum on the integers and converts once (conversion is monotone: the
+// argument of check_jb holds), everything else converts the sum it reads. Resident tiles only, MODE 1 and 3.
+template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8, int I8 = 0>
 __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* qh,
                                                                     const float* __restrict__ qinv, int64_t n, int64_t row_begin, int64_t row_end,
                                                                     int dk16, const float* tau, unsigned long long* lists, int* counts,
@@ -319,10 +335,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // alone, waits for its own LDS reads (profiles/r03_gemm_time_decomposition.txt: the epilogue cost 0.18 of 1.56 ms). DBG & 8: the
     // epilogue where it was, for A/B runs.
     constexpr bool kDefer = kAppend && !(DBG & 8) && !(DBG & 1);
-    f32x4 acc[2][NJB];                               // (written by the MFMAs of a row block's first step, against a zero C operand)
+    using acc_t = typename std::conditional<I8 != 0, i32x4, f32x4>::type;
+    acc_t acc[2][NJB];                               // (written by the MFMAs of a row block's first step, against a zero C operand)
     if (kDefer) {                                    // (a wave's first first step reads them, against p_gmin = +inf: see `pend`)
 #pragma unroll
-        for (int j = 0; j < NJB; ++j) acc[0][j] = acc[1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NJB; ++j) acc[0][j] = acc[1][j] = acc_t{0, 0, 0, 0};
     }
     // `pend`: a full row block's checks are still owed. The first step does NOT test it: what it is given when nothing is owed -- a
     // wave's first row block, the block behind one that was not full -- is p_gmin = +inf, against which the check's lower bound is
@@ -486,6 +503,14 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             // Everything behind the test is the rare path: marked unlikely, so that it is laid out of line and the common path falls
             // through into the query block's MFMAs.
             float amax;
+            if (I8) {                        // (the maximum on the integers, one conversion)
+                int imax;
+                asm("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5\n\tv_max3_i32 %0, %0, %6, %7\n\tv_max_i32 %0, %0, %8"
+                    : "=&v"(imax)
+                    : "v"(acc[0][jb][0]), "v"(acc[0][jb][1]), "v"(acc[0][jb][2]), "v"(acc[0][jb][3]), "v"(acc[1][jb][0]), "v"(acc[1][jb][1]),
+                      "v"(acc[1][jb][2]), "v"(acc[1][jb][3]));
+                amax = (float)imax;
+            } else
             asm("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %0, %0, %6, %7\n\tv_max_f32 %0, %0, %8"
                 : "=&v"(amax)
                 : "v"(acc[0][jb][0]), "v"(acc[0][jb][1]), "v"(acc[0][jb][2]), "v"(acc[0][jb][3]), "v"(acc[1][jb][0]), "v"(acc[1][jb][1]),
@@ -496,7 +521,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             float mn = __builtin_huge_valf();
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                pv[i] = __builtin_fmaf(-m2, acc[i >> 2][jb][i & 3], gnv[i]);
+                pv[i] = __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnv[i]);
                 mn = fminf(mn, pv[i]);                                   // NaN never enters, like k_gemm_tau's ordering
             }
             if (mn < tq) {
@@ -612,10 +637,10 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         check_jb(j, p_rb, pg[0], pg[1], p_gmin);      // the previous row block's sums of query block j, about to be overwritten (nothing owed: p_gmin = +inf)
                     }
                     const f16x8 b = as_f16x8(B[j]);
-                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+                    const acc_t zero = {0, 0, 0, 0};
                     if (!(DBG & 32)) {
-                        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b, kFirst && t == 0 ? zero : acc[0][j], 0, 0, 0);
-                        acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b, kFirst && t == 0 ? zero : acc[1][j], 0, 0, 0);
+                        acc[0][j] = mfma_x_(a0, b, kFirst && t == 0 ? zero : acc[0][j]);
+                        acc[1][j] = mfma_x_(a1, b, kFirst && t == 0 ? zero : acc[1][j]);
                     } else {                                      // (DBG & 32: no MFMAs -- the operands are only kept alive: what the two streams cost by themselves)
                         asm volatile("" ::"v"(a0), "v"(a1), "v"(b));
                         if (kFirst && t == 0) { acc[0][j] = zero; acc[1][j] = zero; }
@@ -711,7 +736,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         const float gnv[4] = {gns[s].x, gns[s].y, gns[s].z, gns[s].w};
 #pragma unroll
                         for (int reg = 0; reg < 4; ++reg) {
-                            pv[4 * s + reg] = __builtin_fmaf(-m2, acc[s][jb][reg], gnv[reg]);
+                            pv[4 * s + reg] = __builtin_fmaf(-m2, (float)acc[s][jb][reg], gnv[reg]);
                             mn = fminf(mn, pv[4 * s + reg]);                   // NaN never enters, like k_gemm_tau's ordering
                         }
                     }
@@ -769,7 +794,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                     const float gnv[4] = {gns[s].x, gns[s].y, gns[s].z, gns[s].w};
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
-                        pv[4 * s + reg] = __builtin_fmaf(-m2, acc[s][jb][reg], gnv[reg]);
+                        pv[4 * s + reg] = __builtin_fmaf(-m2, (float)acc[s][jb][reg], gnv[reg]);
                         mn = fminf(mn, pv[4 * s + reg]);                   // NaN never enters, like k_gemm_tau's ordering
                     }
                 }
@@ -812,7 +837,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             for (int i = 0; i < 8; ++i) {
                 const int64_t row = rb * 32 + 16 * (i >> 2) + 4 * (ls >> 4) + (i & 3);
                 if (row >= n || (MODE != 2 && (row < row_begin || row >= row_end))) continue;
-                const float p = __builtin_fmaf(-m2, acc[i >> 2][jb][i & 3], gnorm[row]);
+                const float p = __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnorm[row]);
                 if (MODE == 0) {
                     if (row < sample_rows) mn = p < mn ? p : mn;
                 } else if (MODE == 2) {
@@ -860,7 +885,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             float mn = __builtin_huge_valf();
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                pv[i] = __builtin_fmaf(-m2, acc[i >> 2][jb][i & 3], gnv[i]);
+                pv[i] = __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnv[i]);
                 mn = fminf(mn, pv[i]);
             }
             if (mn < tq) {

@@ -12,6 +12,9 @@ constexpr int kTopKMax = 8;             // the K nearest rows: K at most this
 
 // One rounding window in proxy units, with room: 2.5 E d against the re-rank's own 2 E d (rerank_window_).
 __device__ __forceinline__ float rounding_window_(float e_rel, float qn, float gmax) { return 2.5f * e_rel * (qn + gmax); }
+// ... with a per-query ABSOLUTE term next to the relative one (the int8 nomination, fir_gemm_i8.h: eabs_q, the measured
+// quantisation residuals; already in proxy units). The forms without it are what every fp16, bf16 and f32 flow computes.
+__device__ __forceinline__ float rounding_window_(float e_rel, float qn, float gmax, float eabs) { return 2.5f * (e_rel * (qn + gmax) + eabs); }
 // A bound moved up by a relative 1e-6 (and off zero), so that ties with it are still below it.
 __device__ __forceinline__ float nudge_up_(float v) { return v + fabsf(v) * 1e-6f + 1e-30f; }
 
@@ -55,6 +58,13 @@ struct RerankWindow {
 };
 __device__ __forceinline__ RerankWindow rerank_window_(float e_rel, float qn, float gmax, int d, float anchor) {
     const float E = e_rel * (qn + gmax) / (float)d;
+    float win = anchor + 2.0f * E * (float)d;
+    win += fabsf(win) * 1e-6f;
+    return {E, win};
+}
+
+__device__ __forceinline__ RerankWindow rerank_window_(float e_rel, float qn, float gmax, int d, float anchor, float eabs) {
+    const float E = (e_rel * (qn + gmax) + eabs) / (float)d;
     float win = anchor + 2.0f * E * (float)d;
     win += fabsf(win) * 1e-6f;
     return {E, win};
@@ -186,8 +196,10 @@ __device__ __forceinline__ bool rerank_certified_(int cnt, float tau, float p_ou
 // bound, anchor + one window). The anchor is the (K-th) smallest stored proxy, at or above the (K-th) smallest proxy of ALL rows (a
 // stored proxy is some row's), so that list will hold every possible winner. NaN bounds stay NaN (nothing is appended, nothing
 // certified: the exact scan answers).
-__device__ __forceinline__ void rerank_hand_over_(const RerankFb& fb, int q, int cnt, float tau, float anchor, float qn, float gmax, float e_rel) {
-    const float c = anchor + nudge_up_(rounding_window_(e_rel, qn, gmax));
+// eabs != NULL: the windows carry the query's absolute term (above).
+__device__ __forceinline__ void rerank_hand_over_(const RerankFb& fb, int q, int cnt, float tau, float anchor, float qn, float gmax, float e_rel,
+                                                  const float* eabs = nullptr) {
+    const float c = anchor + nudge_up_(eabs ? rounding_window_(e_rel, qn, gmax, eabs[q]) : rounding_window_(e_rel, qn, gmax));
     fb.tau2[fb.q_base + q] = c < tau ? c : tau;
     fb.list[atomicAdd(&fb.state[0], 1)] = fb.q_base + q;
     fb_note(fb.state, cnt, tau, anchor, qn);

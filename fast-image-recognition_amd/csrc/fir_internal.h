@@ -186,6 +186,9 @@ extern "C" int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int3
 // tests only: what the most recent call's last super-batch handed its re-rank (fir_gemm.hip); reads, computes and allocates nothing
 extern "C" int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, int32_t max_entries, int32_t* counts, float* tau, float* qnorm,
                                      uint64_t* lists, float* proxies, float* gmax, int32_t* qmap, int32_t* live);
+// what the gallery handle allows the state's next top-1 call (fir_gallery_set_int8_nomination): 0 = fp16, 1 = the int8 pass for every
+// eligible call, -1 = the automatic rule (fir_gemm.hip: gemm_wants_i8_)
+extern "C" void fir_gemm_set_int8_(fir_gemm* m, int32_t mode);
 extern "C" void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch);
 
 struct fir_cls;

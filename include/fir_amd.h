@@ -475,6 +475,20 @@ int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, in
  * bytes; identical keys). min_queries > 0: the caller's threshold instead (any gallery size); 0: never, frees the copy
  * (the exact streaming scan answers everything); < 0: back to the default. */
 int fir_gallery_set_large_batch_mfma(fir_gallery* g, int32_t min_queries);
+/* The int8 nomination pass of large L2 top-1 batches: the batch's rows and queries minus the gallery's column means, quantised to
+ * int8 (one scale for the gallery, one per query), nominated on v_mfma_i32_16x16x64_i8 at half the fp16 pass's instructions and
+ * gallery bytes; the certificate carries the MEASURED quantisation residuals, the re-rank is the reference's arithmetic on the
+ * f32 rows: identical keys. Eligible: top-1 over the whole row of at most 1024 features, more than 32 queries, a call the matrix
+ * cores take anyway; top-K, classes, feature prefixes and longer rows keep the fp16 pass. mode 1: every eligible call; 0: never;
+ * -1 (default): the library's rule -- automatic matrix-core dispatch over >= 65536 rows only, never under a caller's
+ * fir_gallery_set_large_batch_mfma threshold, and back to fp16 for good on a gallery the window does not suit (more than one
+ * query in sixteen of a call needing a second pass; learnt without synchronising). The first int8 call builds the int8 copy
+ * (n*d bytes next to the fp16 one, reported with the fragments by fir_gallery_memory_bytes) and synchronises its stream once.
+ * If there is no memory for the copy, that call and every later one on the gallery are answered by the fp16 pass instead, in
+ * every mode (the same keys, no error; fir_gallery_last_dispatch then reads "... (int8 nomination off for this gallery: no
+ * memory)"), and what the attempt allocated is freed. A query whose own scale, or its product with the gallery's, leaves
+ * (1e-30, 1e30) is left to the exact device scan like a non-finite one. */
+int fir_gallery_set_int8_nomination(fir_gallery* g, int32_t mode);
 /* passes = 64-query GEMM passes queued so far, fallback_queries = queries answered by the exact device scan instead (results
  * identical either way). Uncertified queries are dealt with on the device, in stream order (a second matrix-core pass with the
  * tightest bound the first one justifies, then the exact scan): the search calls never synchronise; this call waits for the
