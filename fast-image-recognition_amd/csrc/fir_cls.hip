@@ -1048,9 +1048,11 @@ int cls_answer_exactly(fir_cls* c, const double* queries, const std::vector<int3
 // stays with the scan, < 0 = error
 int cls_pnn_mfma(fir_cls* c, const double* queries, int32_t qb, double var, double* scores, int32_t* best_class);
 
-// kNN through the matrix cores for the queries of one call (qb <= kKnnMfmaBatch): 0 = best_class filled for every query, 1 = not taken
-// (the exact path answers the call), < 0 = error.
-int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
+// kNN through the matrix cores for the queries of one call (qb <= kKnnMfmaBatch), in two steps.
+// Nominate + re-rank: creates the state, stages and centres the queries and leaves the K' = kp nearest rows of every query in
+// knn_rows / knn_dist (ascending by (distance, row), -1 / +inf padded) and the certificate in knn_ok -- device, in stream order.
+// 0 = done, 1 = not taken (the exact path answers the call), < 0 = error.
+int cls_knn_mfma_rows(fir_cls* c, const double* queries, int32_t qb, int32_t kp) {
     FIR_HIP(hipSetDevice(c->device));
     if (!c->mm) {
         const int rc = fir_gemm_create_f64_(c->device, c->cus, c->stream, c->gal2, c->nt, c->d, c->dp2, &c->mm);
@@ -1062,7 +1064,6 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
             return 1;
         }
     }
-    const int kp = k == 1 ? 1 : 8;           // rows nominated per query: the walk of kNN-K ends inside the 8 nearest rows unless the classes are very mixed
     int rc;
     const size_t qbytes = (size_t)qb * c->d * sizeof(double);
     if ((rc = FIR_RESERVE(c->dq, qbytes)) || (rc = FIR_RESERVE(c->qc, qbytes)) || (rc = FIR_RESERVE(c->knn_rows, (size_t)qb * 8 * sizeof(int32_t))) ||
@@ -1085,6 +1086,15 @@ int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32
         c->last.flops = flops;
         if (kname) std::snprintf(c->last.kernel, sizeof c->last.kernel, "%s", kname);
     }
+    return FIR_OK;
+}
+
+// Vote + deliver: the K' rows become a class (k_cls_knn_vote); what they do not settle takes the exact scan. 0 = best_class filled for
+// every query, 1 = not taken, < 0 = error.
+int cls_knn_mfma(fir_cls* c, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
+    const int kp = k == 1 ? 1 : 8;           // rows nominated per query: the walk of kNN-K ends inside the 8 nearest rows unless the classes are very mixed
+    const int rc = cls_knn_mfma_rows(c, queries, qb, kp);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_cls_knn_vote, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->knn_rows.as<int32_t>(), c->knn_dist.as<double>(),
                        c->knn_ok.as<int32_t>(), qb, kp, k, c->class_off, c->num_classes, c->best.as<int32_t>());
     FIR_HIP(hipGetLastError());
@@ -1358,6 +1368,26 @@ int fir_cls_set_knn_mfma(fir_cls* c, int32_t min_queries) {
     c->mm_failed = false;
     return FIR_OK;
 }
+
+// Tests only (fir_internal.h): the nominate + re-rank step of the matrix-core kNN path for one super-batch of host queries, and what it
+// hands the vote -- rows[qb][kp], dist[qb][kp], ok[qb], host memory. The kNN counters stay as they are.
+int fir_cls_knn_rows_(fir_cls* c, const double* queries, int32_t qb, int32_t kp, int32_t* rows, double* dist, int32_t* ok) {
+    if (!c || !queries || !rows || !dist || !ok) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (kp != 1 && kp != 8) return fir_fail_(FIR_ERR_ARG, "kp=%d: the vote takes 1 or 8 rows", kp);
+    if (qb < 1 || qb > 8192) return fir_fail_(FIR_ERR_ARG, "qb=%d outside [1,8192]", qb);
+    if (c->nt <= 0) return fir_fail_(FIR_ERR_ARG, "an empty training set");
+    const int rc = cls_knn_mfma_rows(c, queries, qb, kp);
+    if (rc == 1) return fir_fail_(FIR_ERR_ARG, "the matrix-core kNN path does not take this training set");
+    if (rc) return rc;
+    FIR_HIP(hipMemcpyAsync(rows, c->knn_rows.p, (size_t)qb * kp * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipMemcpyAsync(dist, c->knn_dist.p, (size_t)qb * kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipMemcpyAsync(ok, c->knn_ok.p, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FIR_HIP(hipStreamSynchronize(c->stream));
+    return FIR_OK;
+}
+
+// Tests only: the handle's float64 matrix-core state, for fir_gemm_nominations_ (NULL: none yet)
+fir_gemm* fir_cls_knn_state_(fir_cls* c) { return c ? c->mm : nullptr; }
 
 int fir_cls_knn_stats(fir_cls* c, int64_t* matrix_core_queries, int64_t* exact_scan_queries_of_them) {
     if (!c) return fir_fail_(FIR_ERR_ARG, "NULL argument");

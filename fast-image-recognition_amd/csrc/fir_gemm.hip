@@ -2246,9 +2246,10 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
 // the call slot q0 + i stands for, *live = the slots of that round that hold a query (0: no round ran). which = 0: qmap[i] = q0 + i,
 // *live = the super-batch's queries. proxies (the few-query scan only): row i = all n proxies of query q0 + i. *gmax = the largest
 // squared row norm as the windows use it. Any output pointer may be NULL. It changes no scratch and launches nothing.
+// A float64 state (fir_gemm_f64.h, through fir_cls_knn_state_) is read the same way with which = 0: fir_gemm_knn_f64_ keeps the record.
 int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, int32_t max_entries, int32_t* counts, float* tau, float* qnorm,
                           uint64_t* lists, float* proxies, float* gmax, int32_t* qmap, int32_t* live) {
-    if (!m || m->f64) return fir_fail_(FIR_ERR_ARG, "not a fir_gemm nomination state");
+    if (!m || (m->f64 && which != 0)) return fir_fail_(FIR_ERR_ARG, "not a fir_gemm nomination state");     // (a float64 state has no second chance)
     if (which < 0 || which > 1 || q0 < 0 || nq < 0 || max_entries < 0 || max_entries > kListCap) return fir_fail_(FIR_ERR_ARG, "bad range");
     if (!m->last_kind) return fir_fail_(FIR_ERR_STATE, "no call has run on this state yet");
     FIR_HIP(hipSetDevice(m->v.device));

@@ -96,6 +96,14 @@ __global__ void __launch_bounds__(64) k_gemm_qprep_f16_f64(const double* __restr
         if (m > 0.f) (void)frexpf(m, &ex);
         const int sh = m > 0.f ? 14 - ex : 0;
         if (sh < -100 || sh > 100 || gallery_exp < -100 || gallery_exp > 100) bad = true;
+        // (the two together as well: doubles reach where floats do not. qinv = 2^-(sh + gallery_exp) is 0 from 150 on -- every proxy is then
+        // the row's norm alone, whatever the query -- and E = e_rel (|q'|^2 + max |g'|^2) / d goes denormal, then 0, a little before the
+        // norms do; the certificate took both for exact and certified wrong rows for elements of 2^-66 .. 2^-78
+        // (tests/test_gpu_knn_rows.py, case F). |sh + gallery_exp| <= 120: max |q'| max |g'| >= 2^-94, so |q'|^2 + max |g'|^2 >= 2^-93 and
+        // E >= 2^-118 for every row length the path takes: normal floats, with room. Beyond it the exact scan answers. A centred query of
+        // zeros has no scale of its own: it counts as one of the rows' magnitude.)
+        const int se = (m > 0.f ? sh : gallery_exp) + gallery_exp;
+        if (se < -120 || se > 120) bad = true;
         const float qn = (bad && qi < nq) ? __builtin_nanf("") : (float)s;
         qnorm[qi] = qn;
         qmul[qi] = bad ? 0.f : ldexpf(1.0f, sh);
@@ -427,6 +435,7 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         hipLaunchKernelGGL(k_gemm_rerank_f64, dim3(nq), dim3(64), rr_lds, st, m->lists[b], m->counts[b], m->tau[b], m->gal2, dq, m->qnorm[b], m->gmax, n, d, m->dp2, e_rel, kp,
                            m->rerank_group, d_rows + (size_t)q0 * kp, d_dist + (size_t)q0 * kp, d_ok + q0);
         m->passes += np;
+        m->last_kind = 1; m->last_b = b; m->last_nq = nq; m->last_sc_rounds = 0; m->last_i8 = false;      // (fir_gemm_nominations_, which = 0)
 #ifdef FIR_AUDIT
         if (m->debug_counts) {      // audit builds: appended rows / certified queries of this super-batch (synchronises)
             FIR_HIP(hipStreamSynchronize(st));

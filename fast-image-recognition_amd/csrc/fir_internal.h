@@ -200,3 +200,8 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
 extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, int32_t kp, int32_t* d_rows, double* d_dist, int32_t* d_ok, void* stream,
                                  const char** kernel_name, double* flops_per_launch, hipEvent_t* ev_pair);
 extern "C" int fir_gemm_destroy(fir_gemm* m);
+// tests only: the nominate + re-rank step of fir_cls_knn_predict's matrix-core path for qb <= 8192 host queries (one super-batch), kp = 1
+// or 8 -- rows[qb][kp] (-1 padded), dist[qb][kp] (+inf padded), ok[qb], host memory; the kNN counters are not touched -- and the
+// handle's float64 nomination state (NULL: none yet), which fir_gemm_nominations_ reads with which = 0
+extern "C" int fir_cls_knn_rows_(fir_cls* c, const double* queries, int32_t qb, int32_t kp, int32_t* rows, double* dist, int32_t* ok);
+extern "C" fir_gemm* fir_cls_knn_state_(fir_cls* c);

@@ -1,7 +1,8 @@
 """The exact re-rank behind every matrix-core search form (k_gemm_rerank<1>, k_gemm_rerank<kTopKMax>, k_gemm_rerank_classes, and
 the few-query form's k_gemm_rerank<1>; fir_gemm_rerank.h holds what they share), aimed at the seams of that shared code: the LDS
 group of 8 candidate rows, the batch of 64 list entries, the two row sources (row-major shadow / tiled gallery) and rows that are
-not whole float4s.
+not whole float4s. The float64 re-rank, k_gemm_rerank_f64 (fir_gemm_f64.h), shares the window, the walk and the certificate but has
+its own K'-best merge and is not reached from here: test_gpu_knn_rows.py tests it, with the same seams (case C there).
 
 Six queries are rows of the gallery that exist 1, 8, 9, 64, 65 and 200 times: every copy has the same proxy, so exactly that many
 list entries lie inside the query's rounding window -- one candidate, one full LDS group, a group plus one, one full batch, a
