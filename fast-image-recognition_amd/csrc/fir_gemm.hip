@@ -1116,6 +1116,7 @@ struct fir_gemm {
     bool last_i8 = false;                 // ... and whether it took the int8 pass (its norms and maximum are then the centred ones)
     // The int8 nomination of large top-1 batches (fir_gemm_i8.h). The query fragments, norms and scales of an int8 super-batch use the
     // fp16 flow's scratch (an int8 tile is never larger); what is listed here is what it holds on top, built by the first call that takes it.
+    int i8_tile = -1;                     // the int8 pass's 256-query tile (fir_gemm_set_int8_tile_): -1 the rule, 0 never, 1 whenever the shape allows
     int i8_mode = 0;                      // what the gallery handle allows the next call (fir_gemm_set_int8_): 0 never, 1 every eligible call, -1 the automatic rule
     bool i8_built = false, i8_off = false;   // i8_off: this gallery went back to fp16 for good (the automatic rule's R / G, or too many second passes)
     const char* i8_off_why = "";
@@ -1252,10 +1253,45 @@ struct fir_x8_entry {
 #define FIR_X8(M, O) {M, O, k_gemm_proxy_f16x<M, 0, O, 0, 8, 1>, "fir::k_gemm_proxy_i8x<" #M ", " #O ">"}
 static const fir_x8_entry kX8Table[] = {FIR_X8(3, 0), FIR_X8(3, 1), FIR_X8(3, 2), FIR_X8(1, 0), FIR_X8(1, 1), FIR_X8(1, 2)};
 #undef FIR_X8
+// <3, 0> on a 256-query tile (QH = 2 of fir_gemm_f16x.h): two pairs per workgroup, every gallery fragment multiplied against both
+static const fir_x8_entry kX8Tile256 = {3, 0, k_gemm_proxy_f16x<3, 0, 0, 0, 8, 1, 2>, "fir::k_gemm_proxy_i8x<3, 0> (256-query tile)"};
 static const fir_x8_entry& find_x8(int mode, int odd) {
     for (const fir_x8_entry& e : kX8Table)
         if (e.mode == mode && e.odd == odd) return e;
     return kX8Table[0];
+}
+static fir_x_fn pick_x8(int mode, int odd, int dbg = 0) {
+#ifdef FIR_AUDIT      // (the int8 timing forms, as pick_x's: the audit build only, wrong answers)
+    if (dbg && mode == 3 && !odd) {
+        switch (dbg & 1023) {
+            case 1: return k_gemm_proxy_f16x<3, 0, 0, 1, 8, 1>;      // no epilogue
+            case 3: return k_gemm_proxy_f16x<3, 0, 0, 3, 8, 1>;      // MFMAs + the query-fragment re-reads
+            case 5: return k_gemm_proxy_f16x<3, 0, 0, 5, 8, 1>;      // MFMAs + the gallery stream
+            case 7: return k_gemm_proxy_f16x<3, 0, 0, 7, 8, 1>;      // MFMAs alone
+            case 33: return k_gemm_proxy_f16x<3, 0, 0, 33, 8, 1>;    // no MFMAs, no epilogue: both streams
+            case 35: return k_gemm_proxy_f16x<3, 0, 0, 35, 8, 1>;    // ... the query-fragment re-reads alone
+            case 37: return k_gemm_proxy_f16x<3, 0, 0, 37, 8, 1>;    // ... the gallery stream alone
+            default: break;
+        }
+    }
+#endif
+    return find_x8(mode, odd).fn;
+}
+static fir_x_fn pick_x8_tile256(int dbg = 0) {
+#ifdef FIR_AUDIT      // (its timing forms)
+    switch (dbg & 1023) {
+        case 1: return k_gemm_proxy_f16x<3, 0, 0, 1, 8, 1, 2>;
+        case 3: return k_gemm_proxy_f16x<3, 0, 0, 3, 8, 1, 2>;
+        case 5: return k_gemm_proxy_f16x<3, 0, 0, 5, 8, 1, 2>;
+        case 7: return k_gemm_proxy_f16x<3, 0, 0, 7, 8, 1, 2>;
+        case 33: return k_gemm_proxy_f16x<3, 0, 0, 33, 8, 1, 2>;
+        case 35: return k_gemm_proxy_f16x<3, 0, 0, 35, 8, 1, 2>;
+        case 37: return k_gemm_proxy_f16x<3, 0, 0, 37, 8, 1, 2>;
+        default: break;
+    }
+#endif
+    (void)dbg;
+    return kX8Tile256.fn;
 }
 // every kernel of the two tables may take the whole query tile as dynamic LDS
 static hipError_t gemm_x_lds_attr_() {
@@ -1267,7 +1303,7 @@ static hipError_t gemm_x_lds_attr_() {
         const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
         if (err != hipSuccess) return err;
     }
-    return hipSuccess;
+    return hipFuncSetAttribute((const void*)kX8Tile256.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
 }
 
 // (the int8 copy and what goes with it; also what a build that ran out of memory gives back)
@@ -1681,7 +1717,7 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
         } else if (eq == hipErrorNotReady) (void)hipGetLastError();     // (not an error: the counter is looked at by a later call)
     }
     if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.k != 1 || c.num_classes > 0 || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
-        c.qb <= 32 || m->dbg_skip)
+        c.qb <= 32 || (m->dbg_skip && m->i8_mode != 1))        // (the timing forms reach int8 only where the handle asks for int8 outright)
         return FIR_OK;
     if (m->i8_mode < 0 && (kI8AutoMinQueries <= 0 || c.qb < kI8AutoMinQueries)) return FIR_OK;
     if (m->i8_mode < 0 && m->i8_off) { c.i8_went_back = true; return FIR_OK; }
@@ -1887,16 +1923,24 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
     if (c.i8) {
         // the int8 form: the same launches over the int8 copy -- half the pieces per row block, the centred rows' norms
         auto bytes8 = [&](int P) { return (double)((n + 31) / 32) * m->dk8 * 1024.0 + P * (4.0 * m->dk8 * 1024.0 + 128.0 * 8.0); };
-        const fir_x8_entry& ran8 = find_x8(3, c.odd);
+        // Two units per row block (257-512 features) and two pairs or more in the launch: the 256-query tile -- P / 2 workgroups share a
+        // row range, each with two pairs' queries in LDS (two 64-KiB images fill what the fp16 tile takes) and every gallery fragment
+        // multiplied against both, so the fragments cross from L2 to the CUs half as often. A one-pair launch (the odd pair of a call)
+        // and every other row length keep the 128-query forms. Such a launch takes up to 2 kShareMax pairs -- sixteen tiles over sixteen
+        // row ranges, 4 096 queries per read of the gallery -- which measured 3 % over sixteen pairs from 32 768 queries per call on. The
+        // rule: always (profiles/int8_tile256.txt).
+        const bool tile256 = m->i8_tile != 0 && m->dk8 == 2 * kRing && pairs >= 2;
+        const fir_x8_entry& ran8 = tile256 ? kX8Tile256 : find_x8(3, c.odd);
         int nl = 0, pf = 1, rc8 = FIR_OK;
         for (int p0 = 0; p0 < pairs; ++nl) {
-            const int P = launch_pairs_(pairs - p0, kShareMax);
+            const int P = launch_pairs_(pairs - p0, tile256 ? 2 * kShareMax : kShareMax);
             if (p0 == 0) pf = P;
             const size_t qo = (size_t)p0;
+            const bool tile = tile256 && P >= 2;
             if ((rc8 = fir_gallery_profile_begin_(m->g, c.st))) return rc8;
-            hipLaunchKernelGGL(ran8.fn, dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->g8, m->i8_gnorm, m->qbf[b] + qo * 4 * m->dk8 * 64, m->qinv[b] + qo * 2 * kQT,
+            hipLaunchKernelGGL(tile ? pick_x8_tile256(m->dbg_skip) : pick_x8(3, c.odd, m->dbg_skip), dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->g8, m->i8_gnorm, m->qbf[b] + qo * 4 * m->dk8 * 64, m->qinv[b] + qo * 2 * kQT,
                                n, (int64_t)0, n, m->dk8, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT,
-                               m->qnorm[b] + qo * 2 * kQT, m->sample_rows, P, (P <= 1 ? 1 : 0) | m->adapt_dbg, 1, m->aT[b] + qo * 2 * kQT, 0);
+                               m->qnorm[b] + qo * 2 * kQT, m->sample_rows, tile ? P / 2 : P, (P <= 1 ? 1 : 0) | m->adapt_dbg, 1, m->aT[b] + qo * 2 * kQT, 0);
             if ((rc8 = fir_gallery_profile_end_(m->g, c.st, bytes8(P)))) return rc8;
             p0 += P;
         }
@@ -2150,6 +2194,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
 extern "C" {
 
 void fir_gemm_set_int8_(fir_gemm* m, int32_t mode) { if (m) m->i8_mode = mode > 0 ? 1 : mode < 0 ? -1 : 0; }
+void fir_gemm_set_int8_tile_(fir_gemm* m, int32_t mode) { if (m) m->i8_tile = mode > 0 ? 1 : mode < 0 ? -1 : 0; }
 
 int fir_gemm_search_top1_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, uint64_t* d_keys, void* stream) {
     return gemm_search(m, d_queries, qb, 1, d_keys, stream);

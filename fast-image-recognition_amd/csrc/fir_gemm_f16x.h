@@ -145,7 +145,9 @@ constexpr int kXStage = 16;             // staged appends per query and workgrou
 // scale), `gnorm` the norms of the centred rows, `qinv` 1 / (s_q s_g). The sums are exact integers (|sum| <= 1024 * 127^2 < 2^24: their
 // conversion to f32 is exact); the check takes the lane's maximum on the integers and converts once (conversion is monotone: the
 // argument of check_jb holds), everything else converts the sum it reads. Resident tiles only, MODE 1 and 3.
-template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8, int I8 = 0>
+// QH: tile halves of 128 queries a workgroup holds (2: the 256-query tile of <3, 0, 0, DBG, 8, I8 = 1> -- two pairs' int8 images of up to
+// 512 features in the 128 KiB of dynamic LDS, `share` counts tiles, every gallery fragment is multiplied against both halves: see `unit`).
+template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8, int I8 = 0, int QH = 1>
 __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* qh,
                                                                     const float* __restrict__ qinv, int64_t n, int64_t row_begin, int64_t row_end,
                                                                     int dk16, const float* tau, unsigned long long* lists, int* counts,
@@ -156,7 +158,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // nothing left for this round: every workgroup returns at once (a kernel boundary lies between the writers and this load)
     if (MODE == 1 && smin != nullptr && (int)smin[0] - sub_stride <= 0) return;
     const int nt = nt_flags & 1;
-    __shared__ float tau_s[2 * kQT], qinv_s[2 * kQT];
+    static_assert(QH == 1 || (QH == 2 && MODE == 3 && !STREAMED && !ODD && NJB == 8 && I8 && !(DBG & (8 | 16 | 64 | 128 | 256 | 512))), "QH = 2: the int8 top-1 pass of two units only");
+    constexpr int kTQ = 2 * kQT * QH;                // queries of the workgroup's tile
+    constexpr int kStage = QH == 2 ? kXStage / 2 : kXStage;      // (256 queries: eight staged slots each, the same 16 KiB)
+    constexpr int kHalfImg = 4 * kRing * 2 * 64;     // QH = 2: uint4 per 128-query image of 512 int8 features (64 KiB)
+    __shared__ float tau_s[kTQ], qinv_s[kTQ];
     // MODE 1: appends are staged per workgroup in LDS (an LDS atomic counts in lgkmcnt and returns in ~100 cycles; a returning GLOBAL
     // atomic sits in the in-order vmcnt queue behind the prefetched gallery loads -- every append drained the wave's stream) and
     // flushed to the global lists once, at the end; a query that fills its kXStage slots appends directly (rare, correct)
@@ -186,14 +192,14 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         return res;
     };
     constexpr bool kAppend = MODE == 1 || kAdapt;
-    __shared__ unsigned long long skeys[kAppend ? 2 * kQT * kXStage : 1];
-    __shared__ int scnt[kAppend ? 2 * kQT : 1];
-    __shared__ float qn_s[kAdapt ? 2 * kQT : 1], win_s[kAdapt ? 2 * kQT : 1];
+    __shared__ unsigned long long skeys[kAppend ? kTQ * kStage : 1];
+    __shared__ int scnt[kAppend ? kTQ : 1];
+    __shared__ float qn_s[kAdapt ? kTQ : 1], win_s[kAdapt ? kTQ : 1];
     __shared__ __attribute__((aligned(16))) unsigned int slot_s[kSlots ? 2 * kQT * 8 : 8];
     // MODE 3: tq_s = T - |q|^2 as the hot path compares it, rewritten by whoever lowers T (tau_s holds T itself). A racing store may leave
     // the value of an OLDER (larger) T: harmless -- any T the pass ever held is >= the final one, so whatever fails the test against
     // it has a proxy >= fl(T_final - |q|^2), the bound the certificate is given
-    __shared__ float tq_s[kAdapt ? 2 * kQT : 1];
+    __shared__ float tq_s[kAdapt ? kTQ : 1];
     // The shared form of the resident adaptive passes hands its row blocks out at run time (`next_blk`, below); everything else --
     // the streamed ring (a barrier per unit: every wave has to walk the same units), the sample pass (its subsets go by wave), MODE 1 --
     // keeps the static ownership. These forms know the shared form only (every caller launches them with share >= 1 and gridDim.y == 1,
@@ -219,7 +225,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     }
     const int dk32 = dk16 >> 1;
     {
-        const size_t pr = (size_t)pair_of_wg;
+        const size_t pr = (size_t)pair_of_wg * QH;        // (QH = 2: the workgroup's tile is pairs 2 t and 2 t + 1, contiguous in every per-pair array)
         qh += pr * 8 * dk32 * 64;
         qinv += pr * 2 * kQT;
         tau += pr * 2 * kQT;
@@ -233,7 +239,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     const int64_t rbs = MODE == 2 ? rb_stride : 1;                        // gallery row blocks per row block of the pass
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wpb = blockDim.x >> 6;
-    if (threadIdx.x < 2 * kQT) {
+    if (threadIdx.x < kTQ) {
         if (kSlots) {
             unsigned int v8[8];
 #pragma unroll
@@ -320,6 +326,12 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             const int jb = i / (dk32 * 64), r = i - jb * dk32 * 64;
             lqx[(size_t)((r >> 6) * 8 + jb) * 64 + (r & 63)] = qh[(size_t)jb * dk32 * 64 + r];
         }
+        if (QH == 2) {                                                   // the second pair's image, in the same layout, behind the first's
+            for (int i = threadIdx.x; i < NJB * dk32 * 64; i += blockDim.x) {
+                const int jb = i / (dk32 * 64), r = i - jb * dk32 * 64;
+                lqx[kHalfImg + (size_t)((r >> 6) * 8 + jb) * 64 + (r & 63)] = qh[(size_t)(8 + jb) * dk32 * 64 + r];
+            }
+        }
         __syncthreads();
     }
     float smallest[NJB];                             // MODE 2: running minima of this lane's NJB queries
@@ -396,7 +408,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     auto exchange_T = [&]() {
             // the workgroup's warm-up minima go out, everybody else's come in
         __syncthreads();
-        if (threadIdx.x < 2 * kQT) {
+        if (threadIdx.x < kTQ) {
             if (kSlots) {
                 unsigned int mine[8], old[8];
 #pragma unroll
@@ -408,7 +420,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 tau_s[threadIdx.x] = __uint_as_float(kth_of_slots(&slot_s[threadIdx.x * 8]));
             } else {
             const unsigned int mine = __float_as_uint(tau_s[threadIdx.x]);
-            const unsigned int old = (nt_flags & 8) ? mine : atomicMin(&smin[threadIdx.x], mine);
+            unsigned int zx = 0;                         // (QH = 2: the address is made here -- prepared in front of the row loop it was spilled)
+            if (QH == 2) asm volatile("v_mov_b32 %0, 0" : "=v"(zx));
+            const unsigned int old = (nt_flags & 8) ? mine : atomicMin(&smin[threadIdx.x + zx], mine);
             tau_s[threadIdx.x] = __uint_as_float(old < mine ? old : mine);
             }
             tq_s[threadIdx.x] = tau_s[threadIdx.x] - qn_s[threadIdx.x];
@@ -431,13 +445,14 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         // result goes through v_readfirstlane right behind the atomic -- which puts the wait back here for an "optimisation" of one lane.
         // With a limit of 2^32 - 1 the increment is the add.)
         int tk = 0;
-        if (kDynForm && lane == 0) tk = (int)atomicInc((unsigned int*)&next_blk, 0xFFFFFFFFu);
+        // (QH = 2: a wave's warm-up walk only observes -- the same block is walked again, for real, so it takes no ticket)
+        if (kDynForm && lane == 0 && !(QH == 2 && warm_it)) tk = (int)atomicInc((unsigned int*)&next_blk, 0xFFFFFFFFu);
         const int64_t rbp = FIR_X_RBP(rg);                // row block of the pass ...
         const int64_t rb = rbp * rbs;                     // ... and of the gallery
         const bool active = rbp < rb_end;
         const uint4* a_nxt = a_cur;                       // (the next block's fragments: set by next_block)
         auto next_block = [&]() {
-            if (kDynForm) rg_next = blk0 + __builtin_amdgcn_readfirstlane(tk);
+            if (kDynForm) rg_next = (QH == 2 && warm_it) ? rg : blk0 + __builtin_amdgcn_readfirstlane(tk);
             const int64_t rgn = rg_next;
             a_nxt = FIR_X_BLOCK(rgn < rg_end ? rgn : rg);
         };
@@ -452,10 +467,10 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 // queries' T and fetches the global one; its result is used at once (nothing is held across the row block -- at 256
                 // registers that spills), on a schedule that thins out: row blocks 2, 3, 4, 6, 8, 12, 16, 24, ... (T settles early).
                 const int v = blk_no >> __builtin_ctz((unsigned)blk_no | 0x40000000u);
-                if ((v == 1 || v == 3) && lane < 16) {
+                if ((v == 1 || v == 3) && lane < 16 * QH) {
                     int zl;                                   // (the lane index from the hardware, as in check_jb: keeps the addresses from being hoisted out of the row loop and spilled)
                     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(zl));
-                    const int ql = 16 * wave + zl;
+                    const int ql = QH == 2 ? 128 * (zl >> 4) + 16 * wave + (zl & 15) : 16 * wave + zl;    // (QH = 2: the wave's query block of either half)
                     if (kSlots) {
                         // (all eight round trips in flight together: one after the other they cost a refresh eight memory latencies)
                         unsigned int mine[8], old[8];
@@ -491,8 +506,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         unsigned int* smin_blk = MODE == 2 ? smin + (size_t)(wave & 7) * sub_stride : nullptr;       // (position 0's subset of this wave)
         // one query block of a full row block `rbq` against the bound (the append forms, not the warm-up walk); g0 / g1 / gminq = the
         // block's row norms and their minimum
-        auto check_jb = [&](int jb, int64_t rbq, const float4 g0, const float4 g1, float gminq) {
-            const int q = jb * 16 + (lane & 15);
+        auto check_jb = [&](int jb, int64_t rbq, const float4 g0, const float4 g1, float gminq, int half = 0) {
+            const int q = half * 2 * kQT + jb * 16 + (lane & 15);
             // (kDefer: the lane's scale and bound come from registers -- an LDS read here would wait, in order, behind the query
             // fragments just requested for the next step; a bound that is a row block old is a larger one: it appends more, never less)
             const float m2 = kDefer ? m2r[jb] : 2.0f * qinv_s[q];
@@ -532,15 +547,15 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 // profiles/r04_append_path.txt).
                 int lz;                                               // the lane index, from the hardware: no register of the hot loop is read
                 asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lz));
-                const int qr = jb * 16 + (lz & 15);
+                const int qr = half * 2 * kQT + jb * 16 + (lz & 15);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (pv[i] < tq) {
                         const int64_t row = rbq * 32 + 16 * (i >> 2) + 4 * (lz >> 4) + (i & 3);
                         const unsigned long long key = fir::key_pack(pv[i], (uint32_t)row);
                         const int st = atomicAdd(&scnt[qr], 1);
-                        if (st < kXStage) {
-                            skeys[qr * kXStage + st] = key;
+                        if (st < kStage) {
+                            skeys[qr * kStage + st] = key;
                         } else {
                             const int slot = atomicAdd(&counts[qr], 1);
                             if (slot < kListCap) lists[(size_t)qr * kListCap + slot] = key;
@@ -554,6 +569,49 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 if (kAdapt) lower_T(qr, pv, mn);
             }
         };
+        // QH = 2, between the halves of a row block (MODE 3 only), on half `half`'s sums as they stand in the accumulators:
+        // observe_half -- a wave's warm-up walk: the smallest proxy of the block's 32 rows lowers T in LDS, nothing is appended (what the
+        // one-half forms do behind their first row block, below);
+        // straddle_half -- a block that straddles the end of the rows, row by row against the bound in LDS (as behind the units, below).
+        auto observe_half = [&](int half) __attribute__((always_inline)) {
+            int lw;                                              // (the lane index from the hardware, as in check_jb)
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lw));
+#pragma unroll
+            for (int jb = 0; jb < NJB; ++jb) {
+                const int q = half * 2 * kQT + jb * 16 + (lw & 15);
+                const float m2 = 2.0f * qinv_s[q];
+                const float gnv[8] = {gns[0].x, gns[0].y, gns[0].z, gns[0].w, gns[1].x, gns[1].y, gns[1].z, gns[1].w};
+                float mn = __builtin_huge_valf();
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mn = fminf(mn, __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnv[i]));      // NaN never enters
+                float o = __shfl_xor(mn, 16, 64);
+                mn = o < mn ? o : mn;
+                o = __shfl_xor(mn, 32, 64);
+                mn = o < mn ? o : mn;
+                const float tn = fmaxf((mn + qn_s[q]) + win_s[q], 0.f);
+                if (lw < 16 && tn < tau_s[q]) atomicMin((unsigned int*)&tau_s[q], __float_as_uint(tn));
+            }
+        };
+        auto straddle_half = [&](int half) __attribute__((always_inline)) {
+            int ls;                                              // (the lane index from the hardware, as in check_jb)
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ls));
+#pragma unroll
+            for (int jb = 0; jb < NJB; ++jb) {
+                const int q = half * 2 * kQT + jb * 16 + (ls & 15);
+                const float m2 = 2.0f * qinv_s[q];
+                const float tq = tq_s[q];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int64_t row = rb * 32 + 16 * (i >> 2) + 4 * (ls >> 4) + (i & 3);
+                    if (row >= n || row < row_begin || row >= row_end) continue;
+                    const float p = __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnorm[row]);
+                    if (p < tq) {
+                        const int slot = atomicAdd(&counts[q], 1);
+                        if (slot < kListCap) lists[(size_t)q * kListCap + slot] = fir::key_pack(p, (uint32_t)row);
+                    }
+                }
+            }
+        };
         // RULE of the row loop: on its common path there must be no vector-memory operation that some other path into the same unit
         // head lacks. The compiler's wait at a unit head -- "all but the N youngest vector-memory operations have returned" -- has to
         // hold on every path that joins there, so it takes the smallest N of them; an operation that only SOME paths issue behind a burst
@@ -561,10 +619,22 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         // trip with nothing to wait for. (The row norms used to be loaded under `h == units - 1 && full_block`: once per row block every
         // wave stood still for it -- profiles/top1_last_unit.txt.) Hence the last unit is a compile-time place (`last_tag`; the unit
         // sequences below peel it) and loads the norms unconditionally.
-        auto unit = [&](uint4 (&C)[RING], uint4 (&N)[RING], int h, auto first_tag, auto last_tag) {
+        // QH = 2 (the 256-query tile of the int8 pass): the block's two units are walked once per tile half, half 0 (queries 0..127 of the
+        // tile: the first image in LDS) then half 1, into the same accumulators -- four units h0.U0, h0.U1, h1.U0, h1.U1 per gallery
+        // fragment read. `first_tag` then says "U0 of a half" (its first step starts the half's sums and checks the sums before them: half
+        // 1's of the previous block in h0.U0, half 0's of THIS block in h1.U0), `last_tag` marks h1.U1 alone. Bursts: h0.U0 requests U1,
+        // h1.U1 the next block's U0; h0.U1 loads the block's norms (h1.U0 needs them already; at h0.U0 they would be in flight while
+        // the previous block's, in pg, are still being checked against: eight registers more) and h1.U0 requests nothing, so
+        // every burst is still one unit ahead of its use. The bounds (and scales) of the half whose sums are checked next are read from
+        // LDS in front of the unit before (the row loop does that, not `unit`): half 0's before h0.U1, half 1's before h1.U1 -- sixteen
+        // registers, as with one half.
+        auto unit = [&](uint4 (&C)[RING], uint4 (&N)[RING], int h, auto first_tag, auto last_tag, auto half_tag) {
             constexpr bool kFirst = decltype(first_tag)::value;      // the first unit of the row block: its first step starts the sums
             constexpr bool kLast = decltype(last_tag)::value;        // the last one: its burst is the next row block's first unit, the norms follow it
-            if (kLast && !kFirst && kDefer && kAdapt) {
+            constexpr int kHalf = decltype(half_tag)::value;         // QH = 2: the tile half this unit multiplies against
+            constexpr bool kBurst = QH == 1 || (kHalf == 0 ? kFirst : kLast);
+            constexpr bool kNorms = QH == 1 ? kLast : (kHalf == 0 && !kFirst);
+            if (QH == 1 && kLast && !kFirst && kDefer && kAdapt) {
                 // The bounds the NEXT row block's first step checks this block's sums against, read a unit early: in front of this unit's
                 // fragment re-reads, so that the first deferred check finds them landed instead of draining the rolling re-reads to get
                 // at the last LDS operations in front of it. A bound that is one unit older is a larger one (T only ever falls): it
@@ -576,13 +646,27 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             }
             if (kLast && kNextLate) next_block();
             const uint4* src = kLast ? a_nxt : a_cur + (size_t)(h + 1) * RING * 64;
-            const uint4* bq = STREAMED ? lqx + lane + (size_t)(ring_c & 3) * 4 * RING * 64 : lqx + lane + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64;
+            // QH = 2: this lane's address in the image of tile half `half`, as ONE 32-bit LDS address the compiler cannot see through: every
+            // fragment of the half is then that register plus an immediate offset (< 64 KiB). From `lqx + constant` it built the second
+            // image's addresses -- all beyond the 16-bit offset field -- as sixteen registers of their own, some of them inside the loop.
+            auto image_of_half = [&](int half) __attribute__((always_inline)) -> const uint4* {
+                uint32_t o = (uint32_t)(uintptr_t)(void __attribute__((address_space(3)))*)lqx + (uint32_t)(half * kHalfImg + lane) * 16u;
+                asm volatile("" : "+v"(o));
+#if defined(__HIP_DEVICE_COMPILE__)
+                return (const uint4*)(const uint4 __attribute__((address_space(3)))*)o;
+#else
+                return lqx + o;                              // (the host pass only parses this: its pointers are not 32 bits wide)
+#endif
+            };
+            const uint4* bq = STREAMED ? lqx + lane + (size_t)(ring_c & 3) * 4 * RING * 64
+                              : QH == 2 ? image_of_half(kHalf) + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64
+                                       : lqx + lane + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64;
             // The next unit's eight gallery pieces are requested in one burst in front of the unit. (DBG & 16, measured and not kept: two per
             // step, behind the fourth and the eighth pair of MFMAs -- every piece still exactly one unit before its use -- ran 6 % slower at
             // 512 features and 5 % at 256: profiles/r03_gemm_time_decomposition.txt.)
             unsigned long long t_burst0 = 0;
             if (DBG & 256) t_burst0 = __builtin_amdgcn_s_memtime();
-            if (!(DBG & 16) && !(DBG & 2) && !(DBG & 64)) {
+            if (kBurst && !(DBG & 16) && !(DBG & 2) && !(DBG & 64)) {
                 if (nt) {
 #pragma unroll
                     for (int u = 0; u < RING; ++u) N[u] = ld_nt(src + (size_t)u * 64 + lane);
@@ -611,7 +695,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 }
                 ++dbg_units;
             }
-            if (kLast) {
+            if (kNorms) {
                 // the block's row norms, directly behind the burst and on every path (the rule above; gn_blk is always readable)
                 // (wave-uniform base + a lane offset made here: hoisted out of the row loop, `gnorm + 4 (lane >> 4)` is a 64-bit register
                 // pair per lane that the K-nearest form spilled -- a scratch reload and an s_waitcnt vmcnt(0) in every row block)
@@ -625,7 +709,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             // the unit's vector-memory operations stay in front of its steps: sunk behind the first MFMAs, a burst leaves the unit head's
             // wait with nothing younger than the data it waits for, and the exact count for that is "everything"
             __builtin_amdgcn_sched_barrier(0);
+            // (QH = 2: behind U0 the half's U1, behind U1 the other half's U0)
             const uint4* bq_after = STREAMED ? lqx + lane + (size_t)((ring_c + 1) & 3) * 4 * RING * 64
+                                    : QH == 2 ? (kFirst ? image_of_half(kHalf) + (size_t)RING * 4 * 64 : image_of_half(kHalf ^ 1))
                                              : lqx + lane + (size_t)((kLast ? 0 : h + 1) % kUnitsPerSlab) * RING * 4 * 64;
 #pragma unroll
             for (int t = 0; t < RING / 2; ++t) {
@@ -634,7 +720,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
                 for (int j = 0; j < NJB; ++j) {
                     if (kDefer && kFirst && t == 0) {
-                        check_jb(j, p_rb, pg[0], pg[1], p_gmin);      // the previous row block's sums of query block j, about to be overwritten (nothing owed: p_gmin = +inf)
+                        // (QH = 2: h0.U0 checks half 1's sums of the previous block, h1.U0 half 0's of this one -- both as p_rb / pg / p_gmin name them)
+                        check_jb(j, p_rb, pg[0], pg[1], p_gmin, QH == 2 ? kHalf ^ 1 : 0);      // the previous row block's sums of query block j, about to be overwritten (nothing owed: p_gmin = +inf)
                     }
                     const f16x8 b = as_f16x8(B[j]);
                     const acc_t zero = {0, 0, 0, 0};
@@ -683,24 +770,64 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         // number: three or more have the one middle unit that pairs up with nothing in front of the last; ODD = 2: the one unit is both)
         const std::true_type yes;
         const std::false_type no;
-        if (!ODD) {
-            unit(cur, nxt, 0, yes, no);
-            for (int h = 1; h + 1 < units; h += 2) {
-                unit(nxt, cur, h, no, no);
-                unit(cur, nxt, h + 1, no, no);
+        const std::integral_constant<int, 0> h0;
+        const std::integral_constant<int, 1> h1;
+        float gmin_blk = 0.f;                        // QH = 2: the smallest row norm of this block
+        if (QH == 2) {
+            // the bounds and scales of tile half `half`, read from LDS a unit ahead of the first step that checks against them
+            auto bounds_of_half = [&](int half) __attribute__((always_inline)) {
+                if (!kDefer) return;
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) {
+                    tqr[jb] = tq_s[half * 2 * kQT + jb * 16 + (lane & 15)];
+                    m2r[jb] = 2.0f * qinv_s[half * 2 * kQT + jb * 16 + (lane & 15)];
+                }
+            };
+            unit(cur, nxt, 0, yes, no, h0);                  // burst nxt <- U1
+            bounds_of_half(0);
+            unit(nxt, cur, 1, no, no, h0);                   // the block's norms (no burst: cur keeps U0)
+            // Between the halves: half 0's sums are complete and h1.U0's first step overwrites them. A full block's are checked there,
+            // beside the MFMAs, as a deferred check like any other (p_rb / pg / p_gmin); a warm-up walk only lowers T with them (nothing
+            // is checked: +inf); a block that straddles the end of the rows is taken row by row here. Nothing a unit needs is in flight
+            // at this point -- the last burst is two units old -- so the rare paths' memory operations tighten no wait of the common path.
+            gmin_blk = fminf(fminf(fminf(gns[0].x, gns[0].y), fminf(gns[0].z, gns[0].w)), fminf(fminf(gns[1].x, gns[1].y), fminf(gns[1].z, gns[1].w)));
+            p_rb = rb;
+            pg[0] = gns[0];
+            pg[1] = gns[1];
+            p_gmin = (full_block && !warm_it) ? gmin_blk : __builtin_huge_valf();
+            if (DBG & 1) {                                   // (no epilogue: half 0's sums are only kept alive, as half 1's are behind the units)
+#pragma unroll
+                for (int jb = 0; jb < NJB; ++jb) asm volatile("" ::"v"(acc[0][jb]), "v"(acc[1][jb]));
+                if (DBG & 4) {                               // (no re-reads: half 1 multiplies against the same registers -- made opaque, or its MFMAs are half 0's and go)
+#pragma unroll
+                    for (int jb = 0; jb < NJB; ++jb) asm volatile("" : "+v"(B[jb].x));
+                }
+            } else {
+                if (__builtin_expect(warm_it, 0)) { if (full_block) observe_half(0); }
+                else if (__builtin_expect(active && !full_block, 0)) straddle_half(0);
             }
-            unit(nxt, cur, units - 1, no, yes);
+            unit(cur, nxt, 0, yes, no, h1);                  // (no burst)
+            bounds_of_half(1);
+            unit(nxt, cur, 1, no, yes, h1);                  // the ticket; burst cur <- the next block's U0
+        } else
+        if (!ODD) {
+            unit(cur, nxt, 0, yes, no, h0);
+            for (int h = 1; h + 1 < units; h += 2) {
+                unit(nxt, cur, h, no, no, h0);
+                unit(cur, nxt, h + 1, no, no, h0);
+            }
+            unit(nxt, cur, units - 1, no, yes, h0);
         } else {
             if (ODD == 2) {
-                unit(cur, nxt, 0, yes, yes);
+                unit(cur, nxt, 0, yes, yes, h0);
             } else {
-                unit(cur, nxt, 0, yes, no);
+                unit(cur, nxt, 0, yes, no, h0);
                 for (int h = 1; h + 2 < units; h += 2) {
-                    unit(nxt, cur, h, no, no);
-                    unit(cur, nxt, h + 1, no, no);
+                    unit(nxt, cur, h, no, no, h0);
+                    unit(cur, nxt, h + 1, no, no, h0);
                 }
-                unit(nxt, cur, units - 2, no, no);
-                unit(cur, nxt, units - 1, no, yes);
+                unit(nxt, cur, units - 2, no, no, h0);
+                unit(cur, nxt, units - 1, no, yes, h0);
             }
 #pragma unroll
             for (int u = 0; u < RING; ++u) cur[u] = nxt[u];         // an odd number of units: the next row block's first unit sits in nxt
@@ -727,7 +854,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lw));
 #pragma unroll
                 for (int jb = 0; jb < NJB; ++jb) {
-                    const int q = jb * 16 + (lw & 15);
+                    const int q = (QH - 1) * 2 * kQT + jb * 16 + (lw & 15);          // (QH = 2: half 1's sums; half 0's were observed between the halves)
                     const float m2 = 2.0f * qinv_s[q];
                     float pv[8];
                     float mn = __builtin_huge_valf();
@@ -759,6 +886,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 }
             }
             exchange_T();
+            // QH = 2: half 0's sums are gone, so the walk above only observed -- both halves' queries now hold an exchanged T, and the same
+            // block comes again (next_block), for real. No other block is walked twice.
+            if (QH == 2) continue;
             if (kDefer) {                                                    // (the last unit read the preset: the exchanged bounds)
 #pragma unroll
                 for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
@@ -769,7 +899,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         }
         if (!active) continue;
         if (full_block) {
-            const float gmin = fminf(fminf(fminf(gns[0].x, gns[0].y), fminf(gns[0].z, gns[0].w)), fminf(fminf(gns[1].x, gns[1].y), fminf(gns[1].z, gns[1].w)));
+            const float gmin = QH == 2 ? gmin_blk : fminf(fminf(fminf(gns[0].x, gns[0].y), fminf(gns[0].z, gns[0].w)), fminf(fminf(gns[1].x, gns[1].y), fminf(gns[1].z, gns[1].w)));
             if (kAppend) {
                 if (kDefer) {
                     pend = true;                                             // checked in the next row block's first step (or behind the loop)
@@ -829,7 +959,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ls));
 #pragma unroll
         for (int jb = 0; jb < NJB; ++jb) {
-            const int q = jb * 16 + (ls & 15);
+            const int q = (QH - 1) * 2 * kQT + jb * 16 + (ls & 15);                  // (QH = 2: half 1's sums; half 0's were taken between the halves)
             const float m2 = 2.0f * qinv_s[q];
             const float tq = kAdapt ? tq_s[q] : tau_s[q];
             float mn = __builtin_huge_valf();
@@ -877,7 +1007,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         int lt;                                          // (the lane index from the hardware: the tail's addresses are not held across the row loop)
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lt));
         auto last_jb = [&](int jb) {
-            const int q = jb * 16 + (lt & 15);
+            const int q = (QH - 1) * 2 * kQT + jb * 16 + (lt & 15);                  // (QH = 2: half 1's sums; half 0's were checked in h1.U0)
             const float m2 = 2.0f * qinv_s[q];
             const float tq = kAdapt ? tq_s[q] : tau_s[q];
             const float gnv[8] = {pg[0].x, pg[0].y, pg[0].z, pg[0].w, pg[1].x, pg[1].y, pg[1].z, pg[1].w};
@@ -895,8 +1025,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         const int64_t row = p_rb * 32 + 16 * (i >> 2) + 4 * (lt >> 4) + (i & 3);
                         const unsigned long long key = fir::key_pack(pv[i], (uint32_t)row);
                         const int st = atomicAdd(&scnt[q], 1);
-                        if (st < kXStage) {
-                            skeys[q * kXStage + st] = key;
+                        if (st < kStage) {
+                            skeys[q * kStage + st] = key;
                         } else {
                             const int slot = atomicAdd(&counts[q], 1);
                             if (slot < kListCap) lists[(size_t)q * kListCap + slot] = key;
@@ -911,13 +1041,13 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     }
     if (kAppend) {
         __syncthreads();                             // every wave's staged appends are in
-        if (threadIdx.x < 2 * kQT) {
+        if (threadIdx.x < kTQ) {
             const int q = threadIdx.x;
-            const int cnt = scnt[q] < kXStage ? scnt[q] : kXStage;
+            const int cnt = scnt[q] < kStage ? scnt[q] : kStage;
             if (cnt > 0) {
                 const int base = atomicAdd(&counts[q], cnt);
                 for (int st = 0; st < cnt; ++st)
-                    if (base + st < kListCap) lists[(size_t)q * kListCap + base + st] = skeys[q * kXStage + st];
+                    if (base + st < kListCap) lists[(size_t)q * kListCap + base + st] = skeys[q * kStage + st];
             }
         }
     }

@@ -189,6 +189,9 @@ extern "C" int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int
 // what the gallery handle allows the state's next top-1 call (fir_gallery_set_int8_nomination): 0 = fp16, 1 = the int8 pass for every
 // eligible call, -1 = the automatic rule (fir_gemm.hip: gemm_wants_i8_)
 extern "C" void fir_gemm_set_int8_(fir_gemm* m, int32_t mode);
+// the int8 pass's 256-query tile (two pairs per workgroup, every gallery fragment against both; 257-512 features, launches of two
+// pairs or more): -1 = the rule (fir_gemm.hip: gemm_pass_f16_), 0 = never, 1 = whenever the shape allows
+extern "C" void fir_gemm_set_int8_tile_(fir_gemm* m, int32_t mode);
 extern "C" void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch);
 
 struct fir_cls;

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""One form of L2 top-K at 1M x d, 32768 queries per call, 4 calls (for rocprofv3 --kernel-trace --stats). usage: topk_one.py [d] [k]"""
+"""One form of L2 top-K at 1M x d, 32768 queries per call, 4 calls (for rocprofv3 --kernel-trace --stats). usage: topk_one.py [d] [k] [int8]
+int8 (top-1 only): -1 the library's rule (default), 0 fp16 nomination, 1 int8 nomination on every call -- the only mode in which the audit
+build's FIR_GEMM_DBG_SKIP reaches the int8 timing forms"""
 import os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,6 +11,7 @@ fir = ge.load_package()
 dev = torch.device("cuda", 0)
 d = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+i8 = int(sys.argv[3]) if len(sys.argv) > 3 else -1
 n, qb = 1_000_000, 32768
 torch.manual_seed(9)
 x = torch.rand((n, d), device=dev); x = x / x.norm(dim=1, keepdim=True)
@@ -16,6 +19,7 @@ q = torch.rand((qb, d), device=dev); q = (q / q.norm(dim=1, keepdim=True)).conti
 torch.cuda.synchronize()
 st = torch.cuda.Stream()
 g = fir.Gallery(dev_ptr=x.data_ptr(), n=n, d=d, metric=0, device=0, stream=st.cuda_stream)
+if i8 >= 0: g.set_int8_nomination(i8)
 keys = torch.empty(qb * k, device=dev, dtype=torch.int64)
 for i in range(5):
     t0 = time.perf_counter()
