@@ -559,6 +559,11 @@ float approx_tau_scale(float nf) { return 1.0f + 1.5f * (2.0f * nf + 16.0f) * kU
 //   combining operations: <= 85 u S;  the reference's own chain (two products and two adds per feature, |terms| <= S): (2 nf + 8) u S
 //   |entropy form - reference| <= B = [ln2 (26.1 (64 + nf / 32) + 150) + 2 nf + 8] 2^-24 (sum(l) + max_rows sum(r)) / nf
 // (U = 8 chunks per load group, as the kernels are instantiated). k_query_entropy_widen widens by 1.5 times what it is given.
+// The 2^-100 the query tile adds to l changes s_k only where l_k = r_k = 0 (anything else is >= 2^-26 and absorbs it): the term is then
+// -100 * 2^-100 where the reference skips the pair, at most ln2 * 100 * 2^-100 < 2^-93 of the value whatever nf. Where sum(l) + max_rows
+// sum(r) > 0 that vanishes in B's slack (B >= 2^-50 then); where it is 0 -- the query and every row 0 over the whole range -- B is 0
+// and the value ln2 * 100 * 2^-100, not the reference's 0: the bound is B + 2^-93, and k_query_entropy_widen adds 2^-92 to what it multiplies
+// by 1.5 (>= 2.5 * 2^-93, the widening owed over a sample in the nomination metric).
 float entropy_bound_coef(float nf, float scale) { return scale * (0.6932f * (26.1f * (64.0f + nf / 32.0f) + 150.0f) + 2.0f * nf + 8.0f) * kUlp / nf; }
 
 // One call of topk_lists_dev: its arguments, the form it takes (list_form) and its workspace (list_workspace).
@@ -569,6 +574,7 @@ struct ListCall {
     int nh, qpad;                 // tiles of eight queries per gallery read of the append scan; qb padded to whole reads
     int sample_stride;            // keys of sample group i: skeys[i * sample_stride + q]
     bool tiles_ready;             // the query tiles are already in g->qt, in the nomination form (list_row_samples)
+    int64_t group_tiles;          // tiles per sample group (list_row_samples)
     uint64_t *skeys, *lists; float *tau, *sq; int32_t *counts, *flag;
     float nf() const { return (float)(end - start); }
     float bound_coef(float scale) const { return harm ? harm_bound_coef(nf(), scale) : entropy_bound_coef(nf(), scale); }
@@ -643,6 +649,7 @@ int list_row_samples(ListCall& c) {
     const hipStream_t st = c.st;
     const int64_t want_rows = std::max<int64_t>(16384, (int64_t)g->n * k / 256);
     const int64_t group_tiles = std::max<int64_t>(1, std::min<int64_t>(g->tiles / k, (want_rows / k + kTileRows - 1) / kTileRows));
+    c.group_tiles = group_tiles;
     // (the row samples are not what a profile of this call is about: the events and the dispatch record belong to the append scan)
     // they hand the handle back as they found it, on every way out (a failed launch must not leave later calls quiet)
     const bool was_profiling = g->profiling, was_quiet = g->quiet;
@@ -778,19 +785,27 @@ int list_rerank_select(const ListCall& c, uint64_t* d_keys) {
     return h_flag ? FIR_ERR_STATE : FIR_OK;
 }
 
-// Returns FIR_ERR_STATE (without setting the error text) when a query could not be certified: fewer than K sample rows below
-// 100000, or a list overflow.
-int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
-                   hipStream_t st) {
-    ListCall c{g, d_queries, qb, start, end, k, st};
+// Every step of a call up to the candidate lists, queued on c.st: what list_rerank_select is handed, and what
+// fir_gallery_list_nominations_ (tests) reads out instead. all_rows (tests only): every live query's threshold becomes +inf once it
+// has been formed, so the append scan lists every row with its nomination value.
+int list_nominate(ListCall& c, bool all_rows = false) {
     list_form(c);
     int rc;
     if ((rc = list_workspace(c))) return rc;
     if ((rc = list_row_sums(c))) return rc;
     if ((rc = list_row_samples(c))) return rc;
     list_threshold(c);
-    if ((rc = list_append_scan(c))) return rc;
-    return list_rerank_select(c, d_keys);
+    if (all_rows) FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)c.tau, (int)0x7F800000u, (size_t)c.qb, c.st));
+    return list_append_scan(c);
+}
+
+// Returns FIR_ERR_STATE (without setting the error text) when a query could not be certified: fewer than K sample rows below
+// 100000, or a list overflow.
+int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
+                   hipStream_t st) {
+    ListCall c{g, d_queries, qb, start, end, k, st};
+    const int rc = list_nominate(c);
+    return rc ? rc : list_rerank_select(c, d_keys);
 }
 
 // ---- the K nearest distinct classes (fir_search_top_classes) -----------------------------------------------------------------
@@ -2017,6 +2032,50 @@ int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_
     if ((rc = range_dev(g, g->dq, qb, start_pos, end_pos, g->dout, g->stream))) return rc;
     FIR_HIP(hipMemcpyAsync(out, g->dout, (size_t)qb * g->n * sizeof(float), hipMemcpyDeviceToHost, g->stream));
     FIR_HIP(hipStreamSynchronize(g->stream));
+    return FIR_OK;
+}
+
+// Tests only (declared in fir_internal.h): the candidate-list path of fir_search_top1 / fir_search_topk for qb <= 1024 host queries
+// up to the lists themselves -- list_nominate, the steps topk_lists_dev runs, on the handle's stream -- without the re-rank, which
+// rewrites the nomination values in place, and without the dispatch gates (n >= 65536, qb >= 8): small galleries go through it too.
+// FIR_CHI2_NOMINATION, FIR_EXACT_SAMPLES and FIR_NO_CHI2_NOMINATION are honoured as the public calls honour them. Then it
+// synchronises and copies out (any output pointer may be NULL; qpad = qb rounded up to whole gallery reads, at most qb + 15):
+//   info[4]      the metric the append scan ran (0 / 1 / 2 the exact ones, 5 / 6 / 7 the nomination metrics), qpad, the stride of
+//                skeys, the tiles per sample group
+//   counts, tau  [qpad]: rows appended per query (a count above 4096 = overflow) and the widened threshold, -inf for the padding
+//   sq, rowsum   metrics 6 and 7 only: the per-query constants [qpad], the per-row constants [n] and, at rowsum[n], the largest row sum
+//   skeys        [k][info[2]]: the packed (value, row) key of every sample group's nearest row
+//   lists        [qpad][4096]: the packed (nomination value, row) keys, counts[q] of them (at most 4096) per query
+//   flag         what the kernels raised (operands outside the plain range, a sample group without a row)
+// all_rows = 1 (n <= 4096 only): the thresholds of the live queries are +inf, every row is appended.
+int fir_gallery_list_nominations_(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t all_rows,
+                                  int32_t* info, int32_t* counts, float* tau, float* sq, float* rowsum, uint64_t* skeys, uint64_t* lists, int32_t* flag) {
+    if (!g || !queries) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 1 || qb > 1024) return fir_fail_(FIR_ERR_ARG, "qb=%d outside [1,1024]", qb);
+    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
+    if (g->n < 1) return fir_fail_(FIR_ERR_ARG, "empty gallery");
+    if (all_rows && g->n > kListCap) return fir_fail_(FIR_ERR_ARG, "all_rows: %lld rows, a list holds %d", (long long)g->n, kListCap);
+    int rc = check_range(g, start_pos, end_pos);
+    if (rc) return rc;
+    FIR_HIP(hipSetDevice(g->device));
+    FirCallOrder order(g, g->stream);
+    if (order.rc) return order.rc;
+    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
+    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    ListCall c{g, g->dq, qb, start_pos, end_pos, k, g->stream};
+    g->call_launches = 0;
+    if ((rc = list_nominate(c, all_rows != 0))) return rc;
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    order.done();
+    if (info) { info[0] = c.nomination_metric(); info[1] = c.qpad; info[2] = c.sample_stride; info[3] = (int32_t)c.group_tiles; }
+    if (counts) FIR_HIP(hipMemcpy(counts, c.counts, (size_t)c.qpad * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (tau) FIR_HIP(hipMemcpy(tau, c.tau, (size_t)c.qpad * sizeof(float), hipMemcpyDeviceToHost));
+    if (sq && c.sq) FIR_HIP(hipMemcpy(sq, c.sq, (size_t)c.qpad * sizeof(float), hipMemcpyDeviceToHost));
+    if (rowsum && c.sq) FIR_HIP(hipMemcpy(rowsum, g->rowsum, (size_t)(g->n + 1) * sizeof(float), hipMemcpyDeviceToHost));
+    if (skeys) FIR_HIP(hipMemcpy(skeys, c.skeys, (size_t)c.sample_stride * k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (lists) FIR_HIP(hipMemcpy(lists, c.lists, (size_t)c.qpad * kListCap * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (flag) FIR_HIP(hipMemcpy(flag, c.flag, sizeof(int32_t), hipMemcpyDeviceToHost));
     return FIR_OK;
 }
 

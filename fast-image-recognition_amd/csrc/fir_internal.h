@@ -174,6 +174,13 @@ extern "C" int fir_gallery_profile_end_(fir_gallery* g, void* st, double bytes_a
 extern "C" void fir_gallery_note_dispatch_(fir_gallery* g, const void* fn, const char* name, int first, int gx, int gy, int block, size_t dyn_lds,
                                            int qpp, double bytes, double flops);
 
+// tests only: the candidate-list path of the scan (fir_capi.hip: list_nominate, the steps of topk_lists_dev before the re-rank) for
+// qb <= 1024 host queries, whatever the gallery's size -- the metric the append scan ran, counts, widened thresholds, per-query and
+// per-row constants, sample keys and lists, copied out; all_rows = 1 (n <= 4096): thresholds at +inf, every row listed. See its definition.
+extern "C" int fir_gallery_list_nominations_(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t all_rows,
+                                             int32_t* info, int32_t* counts, float* tau, float* sq, float* rowsum, uint64_t* skeys, uint64_t* lists,
+                                             int32_t* flag);
+
 struct fir_gemm;
 // fir_gemm_search_top1 / _topk_keys_dev for queries still in host memory: uploaded into d_stage one super-batch at a time, each
 // upload under the previous super-batch's full passes.

@@ -1228,7 +1228,9 @@ __global__ void __launch_bounds__(64) k_query_entropy_widen(const float* __restr
     for (int off = 32; off >= 1; off >>= 1) { s += __shfl_xor(s, off, 64); e += __shfl_xor(e, off, 64); }
     if (threadIdx.x == 0) {
         sq[qi] = (float)e;
-        if (qi < nq && tau[qi] > -__builtin_huge_valf()) tau[qi] += 1.5f * coef * (s + __uint_as_float(smax[0]));    // (every sampled threshold is widened, a slightly negative one too: ADVICE r3)
+        // (every sampled threshold is widened, a slightly negative one too: ADVICE r3; 2^-92: what the tile's l + 2^-100 costs where
+        // l = r = 0 -- fir_capi.hip, entropy_bound_coef -- the whole of the bound when the sums are 0)
+        if (qi < nq && tau[qi] > -__builtin_huge_valf()) tau[qi] += 1.5f * (coef * (s + __uint_as_float(smax[0])) + 0x1p-92f);
     }
 }
 // sq[q] = sum of query q over [start, end); tau[q] += 1.5 * B, B = coef * (sq[q] + smax) the bound on |harmonic form - reference|
