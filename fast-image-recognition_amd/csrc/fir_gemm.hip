@@ -1040,66 +1040,95 @@ __global__ void __launch_bounds__(256) k_gemm_adapt_final(unsigned int* __restri
 
 }  // namespace
 
+// A FirBuf that reads as the T* it holds.
+template <typename T>
+struct GemmBuf : FirBuf {
+    operator T*() const { return (T*)p; }
+};
+
+// One set of what a super-batch's preparation, passes and re-rank hand each other. A state's two sets and a float64 state's one are
+// sized for kPasses passes; the second-chance round's (fir_gemm::sc) for one pair. Members a set never uses stay empty.
+struct GemmScratch {
+    GemmBuf<uint4> qbf;                   // query fragments: fp16 / int8, bf16 hi + lo; the f32 form reads them as<float4>()
+    GemmBuf<float> qnorm, qmul, qinv;     // per query: |q|^2, the fragments' scale and what turns a sum back into a proxy
+    GemmBuf<float> tau;                   // the bound the re-rank's certificate gets: every row that was not appended has a proxy >= tau
+    GemmBuf<float> awin;                  // threshold found on the way (k_gemm_proxy_f16x<3 | 4, *>): the per-query windows ...
+    GemmBuf<unsigned int> aT;             // ... and the workgroups' shared T (float bits; x 8: the K slot words of the K-nearest form)
+    GemmBuf<unsigned int> smin;           // sample flow: smallest sampled proxy per query (orderable bits; top-K: per subset)
+    GemmBuf<unsigned long long> lists;    // candidate lists (kListCap entries per query) and their lengths: grown to the super-batch in use
+    GemmBuf<int> counts;                  //   by gemm_grow_lists_, the round's at creation
+    GemmBuf<float> eabs;                  // int8 calls: the per-query absolute term (gemm_build_i8_)
+    size_t bytes() const { return qbf.cap + qnorm.cap + qmul.cap + qinv.cap + tau.cap + awin.cap + aT.cap + smin.cap + lists.cap + counts.cap + eabs.cap; }
+};
+
+static void gemm_free_i8_(struct fir_gemm* m);
+
+// The matrix-core state of one gallery (or of a prefix of its rows; or, f64, of a float64 training set). It owns everything it points
+// to except the gallery: the buffers free themselves, the destructor releases the rest.
 struct fir_gemm {
-    fir_gallery* g = nullptr;
+    // ---- what is searched: set when the state is created, never changed ----
+    fir_gallery* g = nullptr;             // not owned (NULL for a float64 state)
     fir_gallery_view v;
-    const float4* gal4 = nullptr;
+    const float4* gal4 = nullptr;         // the gallery's tiled f32 rows: not owned
     int dp4 = 0, dq8 = 0;
-    int feat = 0;               // features compared: the gallery's d, or a prefix [0, feat) of every row (fir_gemm_create_range); v.d stays the row length
-    int precision = 0;          // 0: f32 MFMA, 1: bf16 split (hi.hi + hi.lo + lo.hi), 2: one fp16 term
-    uint4* gh = nullptr;        // fp16 fragments (precision 2)
-    float* proxies = nullptr;   // few-query calls: every row's proxy, proxies_nq x n floats (grown on first use)
-    int proxies_nq = 0;
-    int lists_cap = 0;          // queries the candidate lists / counts of one scratch set are sized for (grown to the super-batch in use)
-    float4* rowmajor = nullptr; // row-major f32 copy of the compared features for the re-rank's gathers (absent when HBM is short: the tiled gallery serves)
-    int gallery_exp = 0;        // fp16: the gallery was multiplied by 2^gallery_exp
-    float* qmul[2] = {nullptr, nullptr};
-    float* qinv[2] = {nullptr, nullptr};
-    int dk16 = 0;               // bf16 variant: k-blocks of 16 features (padded to a multiple of 4)
-    float4* gm = nullptr;       // f32 fragments
-    uint4* gb = nullptr;        // bf16 hi/lo fragments
-    uint4* qbf[2] = {nullptr, nullptr};
-    float* gnorm = nullptr;
-    float* gmax = nullptr;
-    // two sets of per-pass scratch: the re-rank of pass i runs on a side stream while pass i+1 is computed
-    float4* qm[2] = {nullptr, nullptr};
-    float* qnorm[2] = {nullptr, nullptr};
-    float* tau[2] = {nullptr, nullptr};
-    float* sample = nullptr;    // f32 / bf16: every sampled proxy of a super-batch (k_gemm_tau), allocated on first use
-    unsigned long long* lists[2] = {nullptr, nullptr};
-    int* counts[2] = {nullptr, nullptr};
-    hipStream_t side = nullptr;
-    hipEvent_t main_done[2] = {nullptr, nullptr}, rerank_done[2] = {nullptr, nullptr}, prep_done[2] = {nullptr, nullptr};
-    hipEvent_t queries_ready = nullptr;
-    hipStream_t copy = nullptr;           // host-pointer calls: the queries of super-batch i + 1 are uploaded under super-batch i's full passes
-    hipEvent_t copy_done[2] = {nullptr, nullptr};
-    int* ok = nullptr; size_t ok_cap = 0;  // certificate flags of one call
+    int feat = 0;                         // features compared: the gallery's d, or a prefix [0, feat) of every row (fir_gemm_create_range); v.d stays the row length
+    int precision = 0;                    // 0: f32 MFMA, 1: bf16 split (hi.hi + hi.lo + lo.hi), 2: one fp16 term
+    int dk16 = 0;                         // fp16: k-blocks of 16 features, whole double-buffer units; bf16: padded to a multiple of 8
+    int gallery_exp = 0;                  // fp16: the gallery was multiplied by 2^gallery_exp (gemm_gallery_scale_)
+    bool f64 = false;                     // the nomination state of a float64 training set owned by fir_cls.hip (fir_gemm_f64.h): gh, gnorm, gmax and set[0] only
+    const double2* gal2 = nullptr; int dp2 = 0;   // ... its tiled rows: not owned
+    // ---- the copies, built by the create ----
+    GemmBuf<uint4> gh;                    // fp16 fragments (precision 2)
+    GemmBuf<float4> gm;                   // f32 fragments (precision 0)
+    GemmBuf<uint4> gb;                    // bf16 hi/lo fragments (precision 1)
+    GemmBuf<float> gnorm, gmax;           // |g|^2 per row, and the largest
+    GemmBuf<float4> rowmajor;             // row-major f32 copy of the compared features for the re-rank's gathers (absent when HBM is short: the tiled gallery serves)
+    // ---- scratch of the calls ----
+    GemmScratch set[2];                   // two sets: the re-rank of super-batch i runs on a side stream while super-batch i + 1 is computed
+    GemmScratch sc;                       // one pair's scratch of a second-chance round (fir_gemm_fb.h)
+    int lists_cap = 0;                    // queries the lists / counts of a set are sized for
+    GemmBuf<float> sample;                // f32 / bf16: every sampled proxy of a super-batch (k_gemm_tau), allocated by the first call
     int sample_rows = 0;
-    // uncertified queries, handled on the device in stream order (fir_gemm_fb.h)
-    int* fb_state = nullptr;              // int[kFbStateWords]: count, count2, notes taken, -, running totals (2 x 64 bit), the first uncertified queries' numbers (fir_gemm_rerank.h)
-    int* fb_list = nullptr;               // [ok_cap] queries the first certificate did not hold for
-    int* fb_list2 = nullptr;              // [ok_cap] ... still uncertified after the second-chance rounds
-    float* fb_tau2 = nullptr;             // [ok_cap] the bound a second pass may append below
-    float* sc_qnorm = nullptr; float* sc_qmul = nullptr; float* sc_qinv = nullptr; float* sc_tau = nullptr;   // one pair's scratch of a second-chance round
-    int* sc_counts = nullptr;
-    unsigned long long* sc_lists = nullptr;
-    uint4* sc_qbf = nullptr;
+    int rt_sample_rows = 0;               // fp16 sample flow: rows sampled (n / 32)
+    GemmBuf<float> proxies;               // few-query calls: every row's proxy, proxies_nq x n floats (grown on first use)
+    int proxies_nq = 0;
+    // ---- uncertified queries, handled on the device in stream order (fir_gemm_fb.h); grown to the largest call seen (gemm_fb_reserve_) ----
+    GemmBuf<int> fb_state;                // int[kFbStateWords]: count, count2, notes taken, -, running totals (2 x 64 bit), the first uncertified queries' numbers (fir_gemm_rerank.h)
+    GemmBuf<int> ok; size_t ok_cap = 0;   // certificate flags of one call
+    GemmBuf<int> fb_list;                 // [ok_cap] queries the first certificate did not hold for
+    GemmBuf<int> fb_list2;                // [ok_cap] ... still uncertified after the second-chance rounds
+    GemmBuf<float> fb_tau2;               // [ok_cap] the bound a second pass may append below
     size_t fb_lds = 0;                    // dynamic LDS of k_gemm_exact_fb
     int fb_grid = 0;
-    int64_t passes = 0;
     int rerank_group = kRerankGroup;      // candidate rows the re-rank stages in LDS at a time
+    // ---- streams and events (created with the state, none for a float64 state) ----
+    hipStream_t side = nullptr;           // re-ranks, and a host-pointer call's preparations
+    hipStream_t copy = nullptr;           // host-pointer calls: the queries of super-batch i + 1 are uploaded under super-batch i's full passes
+    hipEvent_t main_done[2] = {nullptr, nullptr}, rerank_done[2] = {nullptr, nullptr}, prep_done[2] = {nullptr, nullptr}, copy_done[2] = {nullptr, nullptr};
+    hipEvent_t queries_ready = nullptr;
+    // ---- the int8 nomination of large top-1 batches (fir_gemm_i8.h): built by the first call that takes it (gemm_build_i8_), given back
+    // whole when that fails (gemm_free_i8_). Query fragments, norms and scales of an int8 super-batch use the sets above ----
+    int i8_tile = -1;                     // the int8 pass's 256-query tile (fir_gemm_set_int8_tile_): -1 the rule, 0 never, 1 whenever the shape allows
+    int i8_mode = 0;                      // what the gallery handle allows the next call (fir_gemm_set_int8_): 0 never, 1 every eligible call, -1 the automatic rule
+    bool i8_built = false, i8_off = false;   // i8_off: this gallery went back to fp16 for good (the automatic rule's R / G, too many second passes, no memory)
+    const char* i8_off_why = "";
+    std::string i8_note;                  // the kernel name fir_gallery_last_dispatch reports for a call that would have been int8 but for i8_off
+    int dk8 = 0;                          // one-KiB int8 pieces per row block: whole units of 256 features
+    GemmBuf<uint4> g8;                    // the int8 copy
+    GemmBuf<float> i8_mu, i8_gnorm;       // column means; |c_g|^2
+    GemmBuf<float> i8_par;                // max|c_g|, s_g, G^2, R
+    float i8_R = 0.f, i8_G = 0.f;         // host copies, read once when the copy is built
+    int* i8_pin = nullptr;                // pinned: the second-pass counter of the most recent int8 call, copied behind it ...
+    hipEvent_t i8_ev = nullptr;           // ... and the event that says it has arrived (queried, never waited for)
+    bool i8_pending = false;
+    int i8_pending_qb = 0;
+    // ---- knobs, each read once when the state is created (gemm_read_knobs_) ----
     bool wide = true;                     // bf16: pairs of passes through k_gemm_proxy_bf16_wide (FIR_GEMM_WIDE=0 turns it off)
-    unsigned int* smin[2] = {nullptr, nullptr};   // fp16 sample flow: smallest sampled proxy per query (orderable bits; top-K: per subset)
-    int rt_sample_rows = 0;                // ... over this many rows (n / 32)
-    bool f64 = false;                     // the nomination state of a float64 training set owned by fir_cls.hip (fir_gemm_f64.h)
-    const double2* gal2 = nullptr; int dp2 = 0;
     int adaptive = 1;                     // fp16 top-1: the append threshold is found during the full pass (k_gemm_proxy_f16x<3, *>), no sample pass
                                           // (profiles/r03_adaptive_threshold.txt); FIR_GEMM_ADAPTIVE=0: the sample flow, 2: the pass on the way whatever the shape
-    int class_sample_div = 64;            // distinct classes: the bound's row sample is max(kClassSampleRows, n K / this) rows (FIR_GEMM_CLASS_SAMPLE_DIV: experiments; any size is sound)
     int adaptive_topk = 1;                // ... and for the K nearest rows (k_gemm_proxy_f16x<4, *>: K slot minima per query); FIR_GEMM_ADAPTIVE_TOPK=0: the sample flow
-    float* awin[2] = {nullptr, nullptr};  // ... its per-query windows
-    unsigned int* aT[2] = {nullptr, nullptr};   // ... and the ranks' shared T (float bits)
-    // AUDIT KNOBS, honoured by the audit build only and never set in production (gemm_read_knobs_)
+    int class_sample_div = 64;            // distinct classes: the bound's row sample is max(kClassSampleRows, n K / this) rows (FIR_GEMM_CLASS_SAMPLE_DIV: experiments; any size is sound)
+    // audit knobs, honoured by the audit build only and never set in production
     float erel_scale = 1.0f;              // the certificate's relative error bound is multiplied by this (FIR_GEMM_EREL_SCALE); tests/test_gpu_gemm.py shows that a bound
                                           // shrunk to a quarter returns a wrong row on a crafted near-tie, i.e. that the suite can see an unsound bound
     int dbg_block = kGemmBlock;           // timing experiments (FIR_GEMM_DBG_BLOCK=256): the resident adaptive pass with four waves per workgroup = ONE wave per SIMD
@@ -1109,30 +1138,29 @@ struct fir_gemm {
     bool debug_counts = false;            // appended rows per query of a call's last super-batch on stderr (FIR_GEMM_DEBUG_COUNTS; synchronises)
     hipEvent_t phase_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... and its phases: before / after its preparation, after its full passes, after its re-rank
     std::string dump_phases;              // with FIR_GEMM_DBG_SKIP=256: the file the load-burst timestamps of the last super-batch's first pair go to (FIR_GEMM_DUMP_PHASES)
-    // host-side record of the most recent call, for fir_gemm_nominations_ (tests): 0 = no call yet, 1 = gemm_search, 2 = the few-query scan
-    int last_kind = 0;
+    // ---- host-side record of the calls ----
+    int64_t passes = 0;
+    int last_kind = 0;                    // the most recent call, for fir_gemm_nominations_ (tests): 0 = none yet, 1 = gemm_search, 2 = the few-query scan
     int last_b = 0, last_nq = 0;          // ... the scratch set of its last super-batch and that super-batch's queries
     int last_sc_rounds = 0;               // ... the second-chance rounds it queued
     bool last_i8 = false;                 // ... and whether it took the int8 pass (its norms and maximum are then the centred ones)
-    // The int8 nomination of large top-1 batches (fir_gemm_i8.h). The query fragments, norms and scales of an int8 super-batch use the
-    // fp16 flow's scratch (an int8 tile is never larger); what is listed here is what it holds on top, built by the first call that takes it.
-    int i8_tile = -1;                     // the int8 pass's 256-query tile (fir_gemm_set_int8_tile_): -1 the rule, 0 never, 1 whenever the shape allows
-    int i8_mode = 0;                      // what the gallery handle allows the next call (fir_gemm_set_int8_): 0 never, 1 every eligible call, -1 the automatic rule
-    bool i8_built = false, i8_off = false;   // i8_off: this gallery went back to fp16 for good (the automatic rule's R / G, or too many second passes)
-    const char* i8_off_why = "";
-    std::string i8_note;                  // the kernel name fir_gallery_last_dispatch reports for a call that would have been int8 but for i8_off
-    int dk8 = 0;                          // one-KiB int8 pieces per row block: whole units of 256 features
-    uint4* g8 = nullptr;                  // the int8 copy
-    float* i8_mu = nullptr;               // column means
-    float* i8_gnorm = nullptr;            // |c_g|^2
-    float* i8_par = nullptr;              // max|c_g|, s_g, G^2, R (fir_gemm_i8.h)
-    float* i8_eabs[2] = {nullptr, nullptr};
-    float* sc_eabs = nullptr;
-    float i8_R = 0.f, i8_G = 0.f;         // host copies, read once when the copy is built
-    int* i8_pin = nullptr;                // pinned: the second-pass counter of the most recent int8 call, copied behind it ...
-    hipEvent_t i8_ev = nullptr;           // ... and the event that says it has arrived (queried, never waited for)
-    bool i8_pending = false;
-    int i8_pending_qb = 0;
+
+    fir_gemm() = default;
+    fir_gemm(const fir_gemm&) = delete;
+    fir_gemm& operator=(const fir_gemm&) = delete;
+    // (whoever deletes a state that has run calls waits for them first: fir_gemm_destroy)
+    ~fir_gemm() {
+        for (hipStream_t s : {side, copy}) if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t ev : {main_done[0], main_done[1], rerank_done[0], rerank_done[1], prep_done[0], prep_done[1], copy_done[0], copy_done[1], queries_ready,
+                              phase_ev[0], phase_ev[1], phase_ev[2], phase_ev[3]})
+            if (ev) (void)hipEventDestroy(ev);
+        gemm_free_i8_(this);                // (the pinned word and its event; the buffers would go by themselves)
+    }
+    // device bytes beyond the fragment copies and the row-major one (fir_gemm_memory_bytes_)
+    size_t scratch_bytes() const {
+        return gnorm.cap + gmax.cap + set[0].bytes() + set[1].bytes() + sc.bytes() + sample.cap + proxies.cap + fb_state.cap + ok.cap + fb_list.cap + fb_list2.cap +
+               fb_tau2.cap + i8_mu.cap + i8_gnorm.cap + i8_par.cap;
+    }
 };
 
 // The knobs every kind of state honours (this file's and fir_gemm_f64.h's): each is read once, when the state is created.
@@ -1161,6 +1189,9 @@ struct RerankSlot {
     const float* eabs = nullptr;          // an int8 super-batch: the per-query absolute term, and the centred rows' largest norm
     const float* gmax = nullptr;
 };
+static RerankSlot gemm_slot_(const fir_gemm* m, const GemmScratch& s, bool i8) {
+    return {s.lists, s.counts, s.tau, s.qnorm, i8 ? (const float*)s.eabs : nullptr, i8 ? (const float*)m->i8_par + 2 : nullptr};
+}
 // dynamic LDS of the f32 re-rank kernels: rerank_group candidate rows and the query (rerank_lds_f32_)
 static size_t gemm_rerank_lds_(const fir_gemm* m) { return (size_t)(m->rerank_group + 1) * (m->dp4 + 1) * sizeof(float4); }
 static void gemm_launch_rerank_(fir_gemm* m, hipStream_t st, int nq, const RerankSlot& s, const float* d_queries, float e_rel, int k, uint64_t* out_key, int* ok,
@@ -1186,135 +1217,172 @@ static int launch_pairs_(int left, int cap) {
     return P;
 }
 
-// The 16-row kernels by (mode, query slabs streamed, units per row block: 0 = even, 1 = odd, 2 = one, live query blocks): ONE table gives the
-// function and the name fir_gallery_last_dispatch reports for it.
+// The 16-row kernels: ONE table gives the function and the name fir_gallery_last_dispatch reports for it.
 typedef void (*fir_x_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int64_t, int64_t, int, const float*, unsigned long long*, int*, float*,
                          int, int, int, int, unsigned int*, int);
+struct fir_x_key {
+    int mode;               // 1 = append below tau, 2 = the sample pass, 3 / 4 = the threshold found on the way (top-1 / the K nearest)
+    bool streamed;          // the query slabs are streamed per unit (gemm_streamed_)
+    int odd;                // units per row block: 0 = an even number, 1 = an odd one from three on, 2 = one (gemm_odd_, gemm_odd8_)
+    int njb = 8;            // live query blocks: < 8 exists for mode 3 with an even number of units only, anything else takes the whole tile
+    bool i8 = false;        // the int8 form (fir_gemm_i8.h): resident tiles only, modes 3 and 1 (the second-chance rounds), units of 256 features
+    bool tile = false;      // ... its <3, 0> on a 256-query tile (QH = 2 of fir_gemm_f16x.h): two pairs per workgroup, every gallery fragment multiplied against both
+    int dbg = 0;            // the timing forms of FIR_GEMM_DBG_SKIP: instantiated in the audit build only, the shipped library cannot select them
+};
 struct fir_x_entry {
-    int mode, streamed, odd, njb;
+    fir_x_key key;
     fir_x_fn fn;
     const char* name;
 };
-#define FIR_X(M, S, O) {M, S, O, 8, k_gemm_proxy_f16x<M, S, O>, "fir::k_gemm_proxy_f16x<" #M ", " #S ", " #O ">"}
-#define FIR_X_FEW(S, J) {3, S, 0, J, k_gemm_proxy_f16x<3, S, 0, 0, J>, "fir::k_gemm_proxy_f16x<3, " #S ", 0, 0, " #J ">"}
+#define FIR_X(M, S, O) {{M, S, O}, k_gemm_proxy_f16x<M, S, O>, "fir::k_gemm_proxy_f16x<" #M ", " #S ", " #O ">"}
+#define FIR_X_FEW(S, J) {{3, S, 0, J}, k_gemm_proxy_f16x<3, S, 0, 0, J>, "fir::k_gemm_proxy_f16x<3, " #S ", 0, 0, " #J ">"}
+#define FIR_X8(M, O) {{M, false, O, 8, true}, k_gemm_proxy_f16x<M, 0, O, 0, 8, 1>, "fir::k_gemm_proxy_i8x<" #M ", " #O ">"}
+#define FIR_X_DBG(D) {{3, false, 0, 8, false, false, D}, k_gemm_proxy_f16x<3, 0, 0, D>, "fir::k_gemm_proxy_f16x<3, 0, 0, " #D ">"}
+#define FIR_X8_DBG(D) {{3, false, 0, 8, true, false, D}, k_gemm_proxy_f16x<3, 0, 0, D, 8, 1>, "fir::k_gemm_proxy_i8x<3, 0> (timing form " #D ")"}
+#define FIR_X8T_DBG(D) {{3, false, 0, 8, true, true, D}, k_gemm_proxy_f16x<3, 0, 0, D, 8, 1, 2>, "fir::k_gemm_proxy_i8x<3, 0> (256-query tile, timing form " #D ")"}
 static const fir_x_entry kXTable[] = {
     FIR_X(1, 0, 0), FIR_X(1, 0, 1), FIR_X(1, 1, 0), FIR_X(1, 1, 1), FIR_X(2, 0, 0), FIR_X(2, 0, 1), FIR_X(2, 1, 0), FIR_X(2, 1, 1),
     FIR_X(3, 0, 0), FIR_X(3, 0, 1), FIR_X(3, 1, 0), FIR_X(3, 1, 1), FIR_X(4, 0, 0), FIR_X(4, 0, 1), FIR_X(4, 1, 0), FIR_X(4, 1, 1),
     FIR_X_FEW(0, 1), FIR_X_FEW(1, 1), FIR_X_FEW(0, 2), FIR_X_FEW(1, 2),     // a call of <= 16 / <= 32 queries (top-1, threshold found on the way)
     FIR_X(1, 0, 2), FIR_X(2, 0, 2), FIR_X(3, 0, 2), FIR_X(4, 0, 2),         // one unit per row block (at most 128 features; resident by definition)
+#ifdef FIR_AUDIT
+    // wrong answers: 1, 2, 3, 5, 7 (bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no query-fragment re-reads), 33 / 37 / 35 (no MFMAs, no epilogue:
+    // both streams / the gallery stream alone / the re-reads alone). Right answers, for A/B runs: 512 the L2 touch two units ahead by one workgroup in sixteen,
+    // 256 timestamps of workgroup 0's load bursts (FIR_GEMM_DUMP_PHASES), 128 wave w owns row blocks w, w + 8, ..., 384 the two together, 64 the gallery pieces
+    // one behind each MFMA pair of a unit's first step, 16 the pieces of a unit requested two per step instead of in one burst, 8 the epilogue behind its own row block
+    FIR_X_DBG(1), FIR_X_DBG(2), FIR_X_DBG(3), FIR_X_DBG(5), FIR_X_DBG(7), FIR_X_DBG(512), FIR_X_DBG(256), FIR_X_DBG(128), FIR_X_DBG(384), FIR_X_DBG(64),
+    FIR_X_DBG(33), FIR_X_DBG(37), FIR_X_DBG(35), FIR_X_DBG(16), FIR_X_DBG(8),
+#endif
+    FIR_X8(3, 0), FIR_X8(3, 1), FIR_X8(3, 2), FIR_X8(1, 0), FIR_X8(1, 1), FIR_X8(1, 2),
+    {{3, false, 0, 8, true, true}, k_gemm_proxy_f16x<3, 0, 0, 0, 8, 1, 2>, "fir::k_gemm_proxy_i8x<3, 0> (256-query tile)"},
+#ifdef FIR_AUDIT
+    FIR_X8_DBG(1), FIR_X8_DBG(3), FIR_X8_DBG(5), FIR_X8_DBG(7), FIR_X8_DBG(33), FIR_X8_DBG(35), FIR_X8_DBG(37),
+    FIR_X8T_DBG(1), FIR_X8T_DBG(3), FIR_X8T_DBG(5), FIR_X8T_DBG(7), FIR_X8T_DBG(33), FIR_X8T_DBG(35), FIR_X8T_DBG(37),
+#endif
 };
 #undef FIR_X
 #undef FIR_X_FEW
-// mode: 1 = append below tau, 2 = the sample pass, 3 / 4 = the threshold found on the way (top-1 / the K nearest); njb < 8 exists for
-// mode 3 with an even number of units only, anything else takes the whole tile
-static const fir_x_entry* lookup_x(int mode, bool streamed, int odd, int njb) {
+#undef FIR_X8
+#undef FIR_X_DBG
+#undef FIR_X8_DBG
+#undef FIR_X8T_DBG
+static const fir_x_entry* lookup_x(const fir_x_key& k) {
     for (const fir_x_entry& e : kXTable)
-        if (e.mode == mode && e.streamed == (int)streamed && e.odd == odd && e.njb == njb) return &e;
+        if (e.key.mode == k.mode && e.key.streamed == k.streamed && e.key.odd == k.odd && e.key.njb == k.njb && e.key.i8 == k.i8 && e.key.tile == k.tile && e.key.dbg == k.dbg)
+            return &e;
     return nullptr;
 }
-static const fir_x_entry& find_x(int mode, bool streamed, int odd, int njb = 8) {
-    if (!(mode == 3 && !odd && (njb == 1 || njb == 2))) njb = 8;
-    if (const fir_x_entry* e = lookup_x(mode, streamed, odd, njb)) return *e;
-    if (const fir_x_entry* e = lookup_x(2, streamed, odd, 8)) return *e;       // (not a mode: as the sample pass, which the table has for every shape)
-    return *lookup_x(2, false, 0, 8);                                          // (not a shape either: the sample pass of the even resident form)
+// the shipped form a call of this shape runs, and is reported as running (dbg is not looked at)
+static const fir_x_entry& find_x(fir_x_key k) {
+    k.dbg = 0;
+    if (k.i8) {
+        k.streamed = false; k.njb = 8;
+        if (k.tile) { k.mode = 3; k.odd = 0; }
+        const fir_x_entry* e = lookup_x(k);
+        return e ? *e : *lookup_x({3, false, 0, 8, true});                     // (not a form of the int8 pass: as its <3, 0>)
+    }
+    k.tile = false;
+    if (!(k.mode == 3 && !k.odd && (k.njb == 1 || k.njb == 2))) k.njb = 8;
+    if (const fir_x_entry* e = lookup_x(k)) return *e;
+    if (const fir_x_entry* e = lookup_x({2, k.streamed, k.odd})) return *e;    // (not a mode: as the sample pass, which the table has for every shape)
+    return *lookup_x({2, false, 0});                                           // (not a shape either: the sample pass of the even resident form)
 }
-static fir_x_fn pick_x(int mode, bool streamed, int odd, int dbg = 0, int njb = 8) {
-#ifdef FIR_AUDIT      // (the timing forms are instantiated in the audit build only: the shipped library cannot select them)
-    if (dbg && mode == 3 && !streamed && !odd) {       // timing experiments (FIR_GEMM_DBG_SKIP): wrong answers
-        switch (dbg & 1023) {
-            case 1: return k_gemm_proxy_f16x<3, 0, 0, 1>;
-            case 2: return k_gemm_proxy_f16x<3, 0, 0, 2>;
-            case 3: return k_gemm_proxy_f16x<3, 0, 0, 3>;
-            case 5: return k_gemm_proxy_f16x<3, 0, 0, 5>;
-            case 7: return k_gemm_proxy_f16x<3, 0, 0, 7>;
-            case 512: return k_gemm_proxy_f16x<3, 0, 0, 512>;   // (not a wrong-answer form: the L2 touch two units ahead by one workgroup in sixteen)
-            case 256: return k_gemm_proxy_f16x<3, 0, 0, 256>;   // (not a wrong-answer form: timestamps of workgroup 0's load bursts, FIR_GEMM_DUMP_PHASES)
-            case 128: return k_gemm_proxy_f16x<3, 0, 0, 128>;   // (not a wrong-answer form: wave w owns row blocks w, w + 8, ... of the range, for A/B runs)
-            case 384: return k_gemm_proxy_f16x<3, 0, 0, 384>;   // ... with the timestamps
-            case 64: return k_gemm_proxy_f16x<3, 0, 0, 64>;     // (not a wrong-answer form: the gallery pieces one behind each MFMA pair of a unit's first step)
-            case 33: return k_gemm_proxy_f16x<3, 0, 0, 33>;     // no MFMAs, no epilogue: the gallery stream + the query-fragment re-reads
-            case 37: return k_gemm_proxy_f16x<3, 0, 0, 37>;     // ... the gallery stream alone
-            case 35: return k_gemm_proxy_f16x<3, 0, 0, 35>;     // ... the query-fragment re-reads alone
-            case 16: return k_gemm_proxy_f16x<3, 0, 0, 16>;     // (not a wrong-answer form either: the gallery pieces of a unit requested two per step instead of in one burst)
-            case 8: return k_gemm_proxy_f16x<3, 0, 0, 8>;       // (not a wrong-answer form: the epilogue behind its own row block, for A/B runs)
-            default: break;
-        }
+// the function a launch takes: a timing form where one is asked for and exists (whatever njb), the shipped form otherwise
+static fir_x_fn pick_x(fir_x_key k) {
+    if (k.dbg) k.njb = 8;
+#ifdef FIR_AUDIT
+    if (k.dbg && k.mode == 3 && !k.streamed && !k.odd) {
+        k.dbg &= 1023;
+        if (const fir_x_entry* e = lookup_x(k)) return e->fn;
     }
 #endif
-    return find_x(mode, streamed, odd, dbg ? 8 : njb).fn;
+    return find_x(k).fn;
 }
-// The int8 form of the pass (fir_gemm_i8.h): resident tiles only, the threshold found on the way (3) and the second-chance rounds'
-// append below tau (1), by units of 256 features per row: 0 = an even number (512, 1 024 features), 1 = three (768), 2 = one (<= 256).
-struct fir_x8_entry {
-    int mode, odd;
-    fir_x_fn fn;
-    const char* name;
-};
-#define FIR_X8(M, O) {M, O, k_gemm_proxy_f16x<M, 0, O, 0, 8, 1>, "fir::k_gemm_proxy_i8x<" #M ", " #O ">"}
-static const fir_x8_entry kX8Table[] = {FIR_X8(3, 0), FIR_X8(3, 1), FIR_X8(3, 2), FIR_X8(1, 0), FIR_X8(1, 1), FIR_X8(1, 2)};
-#undef FIR_X8
-// <3, 0> on a 256-query tile (QH = 2 of fir_gemm_f16x.h): two pairs per workgroup, every gallery fragment multiplied against both
-static const fir_x8_entry kX8Tile256 = {3, 0, k_gemm_proxy_f16x<3, 0, 0, 0, 8, 1, 2>, "fir::k_gemm_proxy_i8x<3, 0> (256-query tile)"};
-static const fir_x8_entry& find_x8(int mode, int odd) {
-    for (const fir_x8_entry& e : kX8Table)
-        if (e.mode == mode && e.odd == odd) return e;
-    return kX8Table[0];
-}
-static fir_x_fn pick_x8(int mode, int odd, int dbg = 0) {
-#ifdef FIR_AUDIT      // (the int8 timing forms, as pick_x's: the audit build only, wrong answers)
-    if (dbg && mode == 3 && !odd) {
-        switch (dbg & 1023) {
-            case 1: return k_gemm_proxy_f16x<3, 0, 0, 1, 8, 1>;      // no epilogue
-            case 3: return k_gemm_proxy_f16x<3, 0, 0, 3, 8, 1>;      // MFMAs + the query-fragment re-reads
-            case 5: return k_gemm_proxy_f16x<3, 0, 0, 5, 8, 1>;      // MFMAs + the gallery stream
-            case 7: return k_gemm_proxy_f16x<3, 0, 0, 7, 8, 1>;      // MFMAs alone
-            case 33: return k_gemm_proxy_f16x<3, 0, 0, 33, 8, 1>;    // no MFMAs, no epilogue: both streams
-            case 35: return k_gemm_proxy_f16x<3, 0, 0, 35, 8, 1>;    // ... the query-fragment re-reads alone
-            case 37: return k_gemm_proxy_f16x<3, 0, 0, 37, 8, 1>;    // ... the gallery stream alone
-            default: break;
-        }
-    }
-#endif
-    return find_x8(mode, odd).fn;
-}
-static fir_x_fn pick_x8_tile256(int dbg = 0) {
-#ifdef FIR_AUDIT      // (its timing forms)
-    switch (dbg & 1023) {
-        case 1: return k_gemm_proxy_f16x<3, 0, 0, 1, 8, 1, 2>;
-        case 3: return k_gemm_proxy_f16x<3, 0, 0, 3, 8, 1, 2>;
-        case 5: return k_gemm_proxy_f16x<3, 0, 0, 5, 8, 1, 2>;
-        case 7: return k_gemm_proxy_f16x<3, 0, 0, 7, 8, 1, 2>;
-        case 33: return k_gemm_proxy_f16x<3, 0, 0, 33, 8, 1, 2>;
-        case 35: return k_gemm_proxy_f16x<3, 0, 0, 35, 8, 1, 2>;
-        case 37: return k_gemm_proxy_f16x<3, 0, 0, 37, 8, 1, 2>;
-        default: break;
-    }
-#endif
-    (void)dbg;
-    return kX8Tile256.fn;
-}
-// every kernel of the two tables may take the whole query tile as dynamic LDS
+// every shipped kernel of the table may take the whole query tile as dynamic LDS
 static hipError_t gemm_x_lds_attr_() {
     for (const fir_x_entry& e : kXTable) {
+        if (e.key.dbg) continue;
         const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
         if (err != hipSuccess) return err;
     }
-    for (const fir_x8_entry& e : kX8Table) {
-        const hipError_t err = hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
-        if (err != hipSuccess) return err;
-    }
-    return hipFuncSetAttribute((const void*)kX8Tile256.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kHalfLds);
+    return hipSuccess;
 }
 
-// (the int8 copy and what goes with it; also what a build that ran out of memory gives back)
+// What a launch of the 16-row pass reads of the gallery: the fp16 copy, or the int8 one with the centred rows' norms.
+struct GemmOperand {
+    const uint4* frag;
+    const float* gnorm;
+    int dk;                 // one-KiB pieces per row block (dk16 | dk8)
+};
+static GemmOperand gemm_operand_(const fir_gemm* m, bool i8) {
+    if (i8) return {m->g8, m->i8_gnorm, m->dk8};
+    return {m->gh, m->gnorm, m->dk16};
+}
+// the set's per-query bound a launch appends below; the sample pass appends nothing and gets tau, lists and counts as the set has them
+enum GemmBound { kBelowTau, kBelowAwin, kSampleOnly };
+// the kernel's remaining arguments
+struct GemmXRest {
+    bool qnorm;             // `sample` <- the pairs' |q|^2 (the threshold found on the way), NULL otherwise
+    int sample_rows;
+    int nt_flags;
+    unsigned int* words;    // `smin`: smin (the sample pass) or aT of the set, or the uncertified list's length (a second-chance round), ...
+    int words_per_query;    // ... and how far a query of the set moves it
+    int sub_stride;
+    int tile_pairs = 1;     // pairs of a workgroup's tile: `share` counts tiles
+};
+// ONE launch of a 16-row kernel on `st`: pairs [p0, p0 + P) of scratch set s against rows [0, row_end) of the n, every rb_stride-th row block
+static void gemm_launch_x_(fir_x_fn fn, dim3 grid, int block, hipStream_t st, const GemmOperand& op, const GemmScratch& s, int p0, int P, int64_t n, int64_t row_end,
+                           int rb_stride, GemmBound bound, const GemmXRest& r) {
+    const size_t q0 = (size_t)p0 * 2 * kQT, qa = bound == kSampleOnly ? 0 : q0;
+    hipLaunchKernelGGL(fn, grid, dim3(block), kHalfLds, st, op.frag, op.gnorm, s.qbf + (size_t)p0 * 4 * op.dk * 64, s.qinv + q0, n, (int64_t)0, row_end,
+                       op.dk, (bound == kBelowAwin ? s.awin : s.tau) + qa, s.lists + qa * kListCap, s.counts + qa, r.qnorm ? s.qnorm + q0 : (float*)nullptr, r.sample_rows,
+                       P / r.tile_pairs, r.nt_flags, rb_stride, r.words ? r.words + q0 * r.words_per_query : (unsigned int*)nullptr, r.sub_stride);
+}
+
+// (the int8 copy and what goes with it; also what a build that failed gives back)
 static void gemm_free_i8_(fir_gemm* m) {
-    (void)hipFree(m->g8); (void)hipFree(m->i8_mu); (void)hipFree(m->i8_gnorm); (void)hipFree(m->i8_par); (void)hipFree(m->i8_eabs[0]); (void)hipFree(m->i8_eabs[1]);
-    (void)hipFree(m->sc_eabs);
+    for (FirBuf* b : std::initializer_list<FirBuf*>{&m->g8, &m->i8_mu, &m->i8_gnorm, &m->i8_par, &m->set[0].eabs, &m->set[1].eabs, &m->sc.eabs}) b->release();
     if (m->i8_pin) (void)hipHostFree(m->i8_pin);
     if (m->i8_ev) (void)hipEventDestroy(m->i8_ev);
-    m->g8 = nullptr; m->i8_mu = m->i8_gnorm = m->i8_par = m->i8_eabs[0] = m->i8_eabs[1] = m->sc_eabs = nullptr;
     m->i8_pin = nullptr; m->i8_ev = nullptr;
     m->i8_built = false;
+}
+
+// ---- what the two creates (fir_gemm_create_range_ex_ here, fir_gemm_create_f64_ in fir_gemm_f64.h) share ----
+// The buffers a create allocates, in the order it allocates them: states live next to small per-handle buffers whose placement a
+// call's time depends on (profiles/cls_host_side.txt section 3), so number, sizes and order of the allocations are part of the design.
+struct GemmAlloc {
+    FirBuf* buf;
+    size_t bytes;
+    bool wanted;
+};
+static hipError_t gemm_alloc_(hipError_t e, std::initializer_list<GemmAlloc> table) {
+    for (const GemmAlloc& a : table)
+        if (e == hipSuccess && a.wanted) e = a.buf->reserve(a.bytes);
+    return e;
+}
+// one scratch set for kPasses passes, all but lists and counts (gemm_grow_lists_) and eabs (gemm_build_i8_)
+static hipError_t gemm_alloc_set_(hipError_t e, GemmScratch& s, size_t qbf_bytes) {
+    const size_t per_query = (size_t)kPasses * kQT * 4;
+    return gemm_alloc_(e, {{&s.qbf, qbf_bytes, true}, {&s.qnorm, per_query, true}, {&s.qmul, per_query, true}, {&s.qinv, per_query, true},
+                           {&s.smin, kRtSubsets * per_query, true},       // top-K: one minimum per subset
+                           {&s.tau, per_query, true}, {&s.awin, per_query, true},
+                           {&s.aT, 8 * per_query, true}});                // (x 8: the K slot words of the K-nearest form)
+}
+// fp16: one power-of-two scale for the whole gallery -- its largest |value|, h_max, lands in [2^13, 2^14). Sets gallery_exp and returns
+// the factor the packer multiplies by; 0 with a non-finite gallery value, where every query is left to the exact scan.
+static float gemm_gallery_scale_(fir_gemm* m, float h_max) {
+    int ex = 0;
+    if (h_max > 0.f && h_max < __builtin_huge_valf()) { (void)std::frexp(h_max, &ex); m->gallery_exp = 14 - ex; }
+    else m->gallery_exp = h_max > 0.f ? 1000 : 0;
+    return (m->gallery_exp >= -100 && m->gallery_exp <= 100) ? std::ldexp(1.0f, m->gallery_exp) : 0.f;
+}
+// The certificate's relative error bound. fp16: both operands rounded to 11 bits -> |q~.g~ - q.g| <= (2^-10 + 2^-22) sum|q_k g_k| + the
+// sub-normal tails (< 2^-27 |q||g| for d <= 2^20), doubled in p and with |q||g| <= (|q|^2 + max|g|^2) / 2: 2^-10 (1 + 2^-4) covers it.
+// An int8 call: what is not relative is the query's eabs (fir_gemm_i8.h).
+static float gemm_e_rel_(const fir_gemm* m, bool i8) {
+    const float products = i8 ? 0.0f : m->precision == FIR_GEMM_BF16_SPLIT ? 6.1035156e-5f : m->precision == FIR_GEMM_F16 ? 9.765625e-4f * 1.0625f : 0.0f;
+    return m->erel_scale * (8.0f * (float)m->feat * 5.9604645e-8f + products);
 }
 
 extern "C" {
@@ -1326,25 +1394,9 @@ int fir_gemm_create_ex(fir_gallery* g, int32_t precision, fir_gemm** out) { retu
 int fir_gemm_create_range(fir_gallery* g, int32_t precision, int32_t end_pos, fir_gemm** out) { return fir_gemm_create_range_ex_(g, precision, end_pos, -1, out); }
 
 void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch) {
-    const int64_t rblocks = (std::max<int64_t>(m->v.n, 1) + 31) / 32, np = std::max<int64_t>(m->v.n, 1);
-    const int64_t fr = m->gh ? rblocks * m->dk16 * 1024 : m->gb ? rblocks * m->dk16 * 2048 : m->gm ? rblocks * m->dq8 * 1024 : 0;
-    const int64_t rm = m->rowmajor ? m->v.n * (int64_t)((m->feat + 3) / 4) * 16 : 0;
-    int64_t sc = np * 4 + 16;                                                                     // row norms, their maximum
-    sc += 2 * ((int64_t)m->lists_cap * kListCap * 8 + (int64_t)m->lists_cap * 4);                 // candidate lists and counts
-    sc += 2 * (m->precision == FIR_GEMM_F32 ? (int64_t)kPasses * (kQT / 32) * m->dq8 * 1024
-                                            : (int64_t)kPasses * (kQT / 32) * m->dk16 * (m->precision == FIR_GEMM_BF16_SPLIT ? 2048 : 1024));   // query fragments
-    sc += 2 * (int64_t)kPasses * kQT * 4 * 4 + 2 * (int64_t)kRtSubsets * kPasses * kQT * 4;      // per-query scalars, subset minima
-    sc += (int64_t)m->ok_cap * 16 + 32;                                                           // certificate flags, the two lists of uncertified queries, their bounds
-    if (m->sc_lists) sc += (int64_t)kScQueries * kListCap * 8 + (int64_t)4 * m->dk16 * 1024 + (int64_t)kScQueries * 20;   // one pair's second-chance scratch
-    if (m->proxies) sc += (int64_t)m->proxies_nq * np * 4;
-    int64_t fr8 = 0;
-    if (m->g8) {                                                                                  // the int8 copy and what goes with it
-        fr8 = rblocks * m->dk8 * 1024;
-        sc += np * 4 + (int64_t)((m->feat + 3) / 4) * 16 + 32 + 2 * (int64_t)kPasses * kQT * 4 + (int64_t)kScQueries * 4;
-    }
-    if (fragments) *fragments = fr + fr8;
-    if (rowmajor) *rowmajor = rm;
-    if (scratch) *scratch = sc;
+    if (fragments) *fragments = (int64_t)(m->gh.cap + m->gb.cap + m->gm.cap + m->g8.cap);
+    if (rowmajor) *rowmajor = (int64_t)m->rowmajor.cap;
+    if (scratch) *scratch = (int64_t)m->scratch_bytes();
 }
 
 int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos, int32_t rowmajor_mode, fir_gemm** out) {
@@ -1376,28 +1428,20 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     m->dq8 = (m->feat + 31) / 32 * 4;     // feature groups of 8, padded to a multiple of 4 groups (zeros)
     m->dk16 = (m->feat + 127) / 128 * 8;  // k-blocks of 16, padded to a multiple of 8 (the paired-pass kernel's double-buffer unit)
     if (precision == FIR_GEMM_F16) m->dk16 = (m->feat + 16 * kRing - 1) / (16 * kRing) * kRing;   // ... to whole double-buffer units
+    const bool f32 = precision == FIR_GEMM_F32, bf16 = precision == FIR_GEMM_BF16_SPLIT, f16 = precision == FIR_GEMM_F16;
     hipError_t e = hipSetDevice(m->v.device);
     const int64_t rblocks = (std::max<int64_t>(m->v.n, 1) + 31) / 32;
     const int64_t np = std::max<int64_t>(m->v.n, 1);
-    if (e == hipSuccess && precision == FIR_GEMM_F32) e = hipMalloc((void**)&m->gm, (size_t)rblocks * m->dq8 * 64 * sizeof(float4));
-    if (e == hipSuccess && precision == FIR_GEMM_BF16_SPLIT) e = hipMalloc((void**)&m->gb, (size_t)rblocks * m->dk16 * 128 * sizeof(uint4));
-    if (e == hipSuccess && precision == FIR_GEMM_F16) e = hipMalloc((void**)&m->gh, (size_t)rblocks * m->dk16 * 64 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->gnorm, (size_t)np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->gmax, 16);
+    e = gemm_alloc_(e, {{&m->gm, (size_t)rblocks * m->dq8 * 64 * sizeof(float4), f32},
+                        {&m->gb, (size_t)rblocks * m->dk16 * 128 * sizeof(uint4), bf16},
+                        {&m->gh, (size_t)rblocks * m->dk16 * 64 * sizeof(uint4), f16},
+                        {&m->gnorm, (size_t)np * sizeof(float), true},
+                        {&m->gmax, 16, true}});
+    const size_t qbf_bytes = f32 ? (size_t)kPasses * (kQT / 32) * m->dq8 * 64 * sizeof(float4) : (size_t)kPasses * (kQT / 32) * m->dk16 * (bf16 ? 128 : 64) * sizeof(uint4);
     for (int b = 0; b < 2; ++b) {
-        if (e == hipSuccess && precision == FIR_GEMM_F32) e = hipMalloc((void**)&m->qm[b], (size_t)kPasses * (kQT / 32) * m->dq8 * 64 * sizeof(float4));
-        if (e == hipSuccess && precision != FIR_GEMM_F32)
-            e = hipMalloc((void**)&m->qbf[b], (size_t)kPasses * (kQT / 32) * m->dk16 * (precision == FIR_GEMM_BF16_SPLIT ? 128 : 64) * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->qnorm[b], kPasses * kQT * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->qmul[b], kPasses * kQT * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->qinv[b], kPasses * kQT * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->smin[b], (size_t)kRtSubsets * kPasses * kQT * sizeof(unsigned int));   // top-K: one minimum per subset
-        if (e == hipSuccess) e = hipMalloc((void**)&m->tau[b], kPasses * kQT * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->awin[b], kPasses * kQT * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&m->aT[b], (size_t)8 * kPasses * kQT * sizeof(unsigned int));     // (x 8: the K slot words of the K-nearest form)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->main_done[b], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->rerank_done[b], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->prep_done[b], hipEventDisableTiming);
+        e = gemm_alloc_set_(e, m->set[b], qbf_bytes);
+        for (hipEvent_t* ev : {&m->main_done[b], &m->rerank_done[b], &m->prep_done[b]})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&m->queries_ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking);
@@ -1407,15 +1451,15 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
     m->rt_sample_rows = (int)std::min<int64_t>(np, std::max<int64_t>(kMinSampleRows, np / 32));    // n/16 .. n/48 measured: 1.022 / 1.038 / 1.028 M queries/s at 1M x 512
     if (const char* w = fir_knob_("FIR_GEMM_SAMPLE_DIV"))      // experiments
         m->rt_sample_rows = (int)std::min<int64_t>(np, std::max<int64_t>(kMinSampleRows, np / std::max(1, std::atoi(w))));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->fb_state, kFbStateWords * sizeof(int));
+    e = gemm_alloc_(e, {{&m->fb_state, kFbStateWords * sizeof(int), true}});
     if (e == hipSuccess) e = hipMemset(m->fb_state, 0, kFbStateWords * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sc_qnorm, kScQueries * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sc_qmul, kScQueries * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sc_qinv, kScQueries * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sc_tau, kScQueries * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sc_counts, kScQueries * sizeof(int));
-    if (e == hipSuccess && precision == FIR_GEMM_F16) e = hipMalloc((void**)&m->sc_lists, (size_t)kScQueries * kListCap * sizeof(unsigned long long));
-    if (e == hipSuccess && precision == FIR_GEMM_F16) e = hipMalloc((void**)&m->sc_qbf, (size_t)4 * m->dk16 * 64 * sizeof(uint4));
+    e = gemm_alloc_(e, {{&m->sc.qnorm, kScQueries * sizeof(float), true},
+                        {&m->sc.qmul, kScQueries * sizeof(float), true},
+                        {&m->sc.qinv, kScQueries * sizeof(float), true},
+                        {&m->sc.tau, kScQueries * sizeof(float), true},
+                        {&m->sc.counts, kScQueries * sizeof(int), true},
+                        {&m->sc.lists, (size_t)kScQueries * kListCap * sizeof(unsigned long long), f16},
+                        {&m->sc.qbf, (size_t)4 * m->dk16 * 64 * sizeof(uint4), f16}});
     {   // the exact device scan of the uncertified rest keeps eight queries in LDS
         m->fb_lds = (size_t)m->dp4 * 4 * 8 * sizeof(float);
         if (m->fb_lds > kRerankLdsMax) {
@@ -1428,76 +1472,67 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(160 * 1024) / std::max<size_t>(m->fb_lds, 1)));
         m->fb_grid = std::max(1, m->v.cus) * per_cu;
     }
-    const int lds_bytes = precision == FIR_GEMM_F32 ? (kQT / 32) * std::min(m->dq8, kSlab8) * 64 * (int)sizeof(float4)
-                                                    : (kQT / 32) * std::min(m->dk16, kSlab16) * 128 * (int)sizeof(uint4);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_bf16<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    const int lds_bytes = f32 ? (kQT / 32) * std::min(m->dq8, kSlab8) * 64 * (int)sizeof(float4) : (kQT / 32) * std::min(m->dk16, kSlab16) * 128 * (int)sizeof(uint4);
+    for (const void* fn : {(const void*)k_gemm_proxy<0>, (const void*)k_gemm_proxy<1>, (const void*)k_gemm_proxy_bf16<0>, (const void*)k_gemm_proxy_bf16<1>})
+        if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm_proxy_bf16_wide, hipFuncAttributeMaxDynamicSharedMemorySize, kWideLds);
-    {   // the re-rank keeps the query and up to kRerankGroup candidate rows in LDS
+    {   // The re-rank keeps the query and up to kRerankGroup candidate rows in LDS. At least six fit: the check above has let through rows
+        // of at most kRerankLdsMax / 128 = 1152 float4, 18 448 bytes with the padding, and kRerankLdsMax holds seven of those and the query.
         const size_t row_bytes = (size_t)(m->dp4 + 1) * sizeof(float4);
-        m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes > 1 ? kRerankLdsMax / row_bytes - 1 : 0);
-        if (m->rerank_group < 1) { delete m; return fir_fail_(FIR_ERR_ARG, "rows of %d features are too long for the matrix-core path's re-rank", m->v.d); }
+        m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes - 1);
         if (gemm_rerank_lds_(m) > 48 * 1024)
             for (const void* fn : {(const void*)k_gemm_rerank<1>, (const void*)k_gemm_rerank<kTopKMax>, (const void*)k_gemm_rerank_classes})
                 if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
-    if (e == hipSuccess && precision == FIR_GEMM_F16) e = gemm_x_lds_attr_();
+    if (e == hipSuccess && f16) e = gemm_x_lds_attr_();
     gemm_read_knobs_(m);
     if (e == hipSuccess && m->v.n > 0) {
+        const int64_t n = m->v.n;
+        const int d4 = (m->feat + 3) / 4;
+        hipStream_t st = m->v.stream;
         // row norms come from the f32 packer (run on a one-group scratch when only the bf16 fragments are kept)
-        if (precision == FIR_GEMM_BF16_SPLIT) {
+        if (bf16) {
             const int64_t totalb = rblocks * m->dk16 * 64;
-            hipLaunchKernelGGL(k_gemm_pack_gallery_bf16, dim3((unsigned)((totalb + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4,
-                               m->dk16, m->gb);
-            hipLaunchKernelGGL(k_gemm_row_norms, dim3((unsigned)((m->v.n + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4, m->gnorm, (m->feat + 3) / 4);
+            hipLaunchKernelGGL(k_gemm_pack_gallery_bf16, dim3((unsigned)((totalb + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->dk16, m->gb);
+            hipLaunchKernelGGL(k_gemm_row_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->gnorm, d4);
         }
-        if (precision == FIR_GEMM_F16) {
-            // one power-of-two scale for the whole gallery: its largest |value| lands in [2^13, 2^14)
+        if (f16) {
             float h_max = 0.f;
-            e = hipMemsetAsync(m->gmax, 0, 16, m->v.stream);
-            const int64_t count4 = (int64_t)((m->v.n + 63) / 64) * m->dp4 * 64;
-            hipLaunchKernelGGL(k_gemm_absmax, dim3((unsigned)std::min<int64_t>((count4 + 255) / 256, 4096)), dim3(256), 0, m->v.stream, m->gal4, count4, m->gmax);
-            if (e == hipSuccess) e = hipMemcpyAsync(&h_max, m->gmax, sizeof(float), hipMemcpyDeviceToHost, m->v.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(m->v.stream);
-            int ex = 0;
-            if (h_max > 0.f && h_max < __builtin_huge_valf()) { (void)std::frexp(h_max, &ex); m->gallery_exp = 14 - ex; }
-            else m->gallery_exp = h_max > 0.f ? 1000 : 0;      // non-finite gallery value: every query is left to the exact scan
-            const float scale = (m->gallery_exp >= -100 && m->gallery_exp <= 100) ? std::ldexp(1.0f, m->gallery_exp) : 0.f;
+            e = hipMemsetAsync(m->gmax, 0, 16, st);
+            const int64_t count4 = (int64_t)((n + 63) / 64) * m->dp4 * 64;
+            hipLaunchKernelGGL(k_gemm_absmax, dim3((unsigned)std::min<int64_t>((count4 + 255) / 256, 4096)), dim3(256), 0, st, m->gal4, count4, m->gmax);
+            if (e == hipSuccess) e = hipMemcpyAsync(&h_max, m->gmax, sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            const float scale = gemm_gallery_scale_(m, h_max);
             const int64_t totalh = rblocks * m->dk16 * 64;
-            hipLaunchKernelGGL(k_gemm_pack_gallery_f16x, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4,
-                               m->dk16, scale, m->gh, m->feat == m->v.d ? m->dp4 * 4 : m->feat);
-            hipLaunchKernelGGL(k_gemm_row_norms, dim3((unsigned)((m->v.n + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4, m->gnorm, (m->feat + 3) / 4);
+            hipLaunchKernelGGL(k_gemm_pack_gallery_f16x, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->dk16, scale, m->gh,
+                               m->feat == m->v.d ? m->dp4 * 4 : m->feat);
+            hipLaunchKernelGGL(k_gemm_row_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->gnorm, d4);
         }
-        const int64_t total = precision == FIR_GEMM_F32 ? rblocks * m->dq8 * 64 : 0;
-        if (total > 0)
-        hipLaunchKernelGGL(k_gemm_pack_gallery, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, m->v.stream, m->gal4, m->v.n, m->dp4, m->dq8,
-                           m->gm, m->gnorm);
-        hipLaunchKernelGGL(k_gemm_max, dim3(1), dim3(256), 0, m->v.stream, m->gnorm, m->v.n, m->gmax);
+        if (f32) {
+            const int64_t total = rblocks * m->dq8 * 64;
+            hipLaunchKernelGGL(k_gemm_pack_gallery, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->dq8, m->gm, m->gnorm);
+        }
+        hipLaunchKernelGGL(k_gemm_max, dim3(1), dim3(256), 0, st, m->gnorm, n, m->gmax);
         // The re-rank's row-major copy of the compared features, when it leaves at least three times its size of HBM free
         // (FIR_GEMM_ROWMAJOR=0 / 1: never / whenever it can be allocated)
         {
-            const int d4 = (m->feat + 3) / 4;
-            const size_t want = (size_t)m->v.n * d4 * sizeof(float4);
+            const size_t want = (size_t)n * d4 * sizeof(float4);
             size_t free_b = 0, total_b = 0;
             int mode = rowmajor_mode;
             if (const char* w = fir_knob_("FIR_GEMM_ROWMAJOR")) { if (mode < 0) mode = std::atoi(w); }
             const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= 4 * want;
-            if (mode != 0 && (room || mode > 0) && hipMalloc((void**)&m->rowmajor, want) == hipSuccess) {
-                const int64_t tiles = (m->v.n + 63) / 64;
+            if (mode != 0 && (room || mode > 0) && m->rowmajor.reserve(want) == hipSuccess) {
+                const int64_t tiles = (n + 63) / 64;
                 for (int64_t t0 = 0; t0 < tiles; t0 += 65535 * 16) {      // gridDim.x limit: slabs of tiles
                     const int64_t nt = std::min<int64_t>(tiles - t0, 65535 * 16);
-                    hipLaunchKernelGGL(k_gemm_untile, dim3((unsigned)nt, (unsigned)((d4 + 31) / 32)), dim3(256), 0, m->v.stream, m->gal4 + (size_t)t0 * m->dp4 * 64,
-                                       m->v.n - t0 * 64, m->dp4, d4, m->rowmajor + (size_t)t0 * 64 * d4);
+                    hipLaunchKernelGGL(k_gemm_untile, dim3((unsigned)nt, (unsigned)((d4 + 31) / 32)), dim3(256), 0, st, m->gal4 + (size_t)t0 * m->dp4 * 64,
+                                       n - t0 * 64, m->dp4, d4, m->rowmajor + (size_t)t0 * 64 * d4);
                 }
-            } else {
-                (void)hipGetLastError();
-                m->rowmajor = nullptr;
-            }
+            } else (void)hipGetLastError();         // (no copy: a failed reserve leaves the buffer empty)
         }
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(m->v.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess) {
         const int rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "GEMM-path setup: %s", hipGetErrorString(e));
@@ -1511,24 +1546,9 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
 int fir_gemm_destroy(fir_gemm* m) {
     if (!m) return FIR_OK;
     (void)hipSetDevice(m->v.device);
-    (void)fir_gallery_wait_calls_(m->g);      // calls queued on the callers' streams may still use what is freed below
+    (void)fir_gallery_wait_calls_(m->g);      // calls queued on the callers' streams may still use what the state frees
     if (m->v.stream || !m->f64) (void)hipStreamSynchronize(m->v.stream);
-    if (m->side) { (void)hipStreamSynchronize(m->side); (void)hipStreamDestroy(m->side); }
-    for (int b = 0; b < 2; ++b) {
-        (void)hipFree(m->qm[b]); (void)hipFree(m->qbf[b]); (void)hipFree(m->qnorm[b]); (void)hipFree(m->qmul[b]); (void)hipFree(m->qinv[b]); (void)hipFree(m->smin[b]); (void)hipFree(m->tau[b]); (void)hipFree(m->awin[b]); (void)hipFree(m->aT[b]); (void)hipFree(m->lists[b]); (void)hipFree(m->counts[b]);
-        if (m->main_done[b]) (void)hipEventDestroy(m->main_done[b]);
-        if (m->rerank_done[b]) (void)hipEventDestroy(m->rerank_done[b]);
-        if (m->prep_done[b]) (void)hipEventDestroy(m->prep_done[b]);
-    }
-    if (m->queries_ready) (void)hipEventDestroy(m->queries_ready);
-    for (hipEvent_t ev : m->phase_ev) if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(m->gm); (void)hipFree(m->gb); (void)hipFree(m->gh); (void)hipFree(m->rowmajor); (void)hipFree(m->proxies); (void)hipFree(m->gnorm); (void)hipFree(m->gmax); (void)hipFree(m->sample); (void)hipFree(m->ok);
-    (void)hipFree(m->fb_state); (void)hipFree(m->fb_list); (void)hipFree(m->fb_list2); (void)hipFree(m->fb_tau2);
-    (void)hipFree(m->sc_qnorm); (void)hipFree(m->sc_qmul); (void)hipFree(m->sc_qinv); (void)hipFree(m->sc_tau); (void)hipFree(m->sc_counts);
-    (void)hipFree(m->sc_lists); (void)hipFree(m->sc_qbf);
-    gemm_free_i8_(m);
-        if (m->copy) { (void)hipStreamSynchronize(m->copy); (void)hipStreamDestroy(m->copy); }
-    for (int b = 0; b < 2; ++b) if (m->copy_done[b]) (void)hipEventDestroy(m->copy_done[b]);
+    for (hipStream_t s : {m->side, m->copy}) if (s) (void)hipStreamSynchronize(s);
     delete m;
     return FIR_OK;
 }
@@ -1580,32 +1600,27 @@ int fir_gemm_stats(const fir_gemm* m, int64_t* passes, int64_t* fallback_queries
 static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_keys, hipStream_t st, float e_rel, int sc_rounds, bool streamed, bool i8 = false) {
     const int d = m->feat, qs = m->v.d;
     const int64_t n = m->v.n;
+    const GemmOperand op = gemm_operand_(m, i8);
+    GemmScratch& s = m->sc;
+    // (an int8 call's rounds stay int8: tau2 is in the units of the centred int8 proxies)
+    const fir_x_fn round_fn = pick_x({1, i8 ? false : streamed, i8 ? gemm_odd8_(m) : gemm_odd_(m), 8, i8});
     for (int r = 0; r < sc_rounds; ++r) {
         const int off = r * kScQueries;
         if (i8) {
-            // (an int8 call's rounds stay int8: tau2 is in the units of the centred int8 proxies)
             hipLaunchKernelGGL(k_gemm_qprep_i8, dim3(kScQueries), dim3(64), 0, st, d_queries, kScQueries, d, qs, (const float*)m->i8_mu, (const float*)m->i8_par, e_rel,
-                               m->erel_scale, m->sc_qnorm, m->sc_qmul, m->sc_qinv, m->sc_eabs, m->sc_counts, (float*)nullptr, (unsigned int*)nullptr, (int*)nullptr,
-                               (const int*)m->fb_state, (const int*)m->fb_list, off, (const float*)m->fb_tau2, m->sc_tau);
-            hipLaunchKernelGGL(k_gemm_pack_queries_i8, dim3((4 * m->dk8 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, m->dk8, (const float*)m->i8_mu,
-                               (const float*)m->sc_qmul, m->sc_qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
-            hipLaunchKernelGGL(find_x8(1, gemm_odd8_(m)).fn, dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->g8, m->i8_gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
-                               (int64_t)0, n, m->dk8, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
-                               (unsigned int*)m->fb_state, off);
-            gemm_launch_rerank_(m, st, kScQueries, {m->sc_lists, m->sc_counts, m->sc_tau, m->sc_qnorm, m->sc_eabs, m->i8_par + 2}, d_queries, e_rel, k, d_keys, m->ok,
-                                {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
-            continue;
+                               m->erel_scale, s.qnorm, s.qmul, s.qinv, s.eabs, s.counts, (float*)nullptr, (unsigned int*)nullptr, (int*)nullptr,
+                               (const int*)m->fb_state, (const int*)m->fb_list, off, (const float*)m->fb_tau2, s.tau);
+            hipLaunchKernelGGL(k_gemm_pack_queries_i8, dim3((4 * op.dk * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, op.dk, (const float*)m->i8_mu,
+                               (const float*)s.qmul, s.qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
+        } else {
+            hipLaunchKernelGGL(k_gemm_sc_prep, dim3(kScQueries), dim3(64), 0, st, d_queries, d, qs, m->gallery_exp, (const int*)m->fb_state, (const int*)m->fb_list, off,
+                               (const float*)m->fb_tau2, s.qnorm, s.qmul, s.qinv, s.tau, s.counts);
+            hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * op.dk * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, op.dk, (const float*)s.qmul,
+                               s.qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
         }
-        hipLaunchKernelGGL(k_gemm_sc_prep, dim3(kScQueries), dim3(64), 0, st, d_queries, d, qs, m->gallery_exp, (const int*)m->fb_state, (const int*)m->fb_list, off,
-                           (const float*)m->fb_tau2, m->sc_qnorm, m->sc_qmul, m->sc_qinv, m->sc_tau, m->sc_counts);
-        hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, kScQueries, d, m->dk16, (const float*)m->sc_qmul,
-                           m->sc_qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
         // one pair over all CUs (share = 1: 256 row ranges), the gallery stream read once (nt)
-        hipLaunchKernelGGL(pick_x(1, streamed, gemm_odd_(m)), dim3(m->v.cus, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->sc_qbf, (const float*)m->sc_qinv, n,
-                           (int64_t)0, n, m->dk16, (const float*)m->sc_tau, m->sc_lists, m->sc_counts, (float*)nullptr, 0, 1, 1, 1,
-                           (unsigned int*)m->fb_state, off);
-        gemm_launch_rerank_(m, st, kScQueries, {m->sc_lists, m->sc_counts, m->sc_tau, m->sc_qnorm}, d_queries, e_rel, k, d_keys, m->ok,
-                            {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
+        gemm_launch_x_(round_fn, dim3(m->v.cus, 1), kGemmBlock, st, op, s, 0, 1, n, n, 1, kBelowTau, {false, 0, 1, m->fb_state.as<unsigned int>(), 0, off});
+        gemm_launch_rerank_(m, st, kScQueries, gemm_slot_(m, s, i8), d_queries, e_rel, k, d_keys, m->ok, {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
     }
     hipLaunchKernelGGL(k_gemm_fb_collect, dim3(1), dim3(256), 0, st, m->fb_state, (const int*)m->fb_list, (const int*)m->ok, m->fb_list2, (unsigned long long*)d_keys, k);
     for (int r = 0; r < k; ++r)
@@ -1669,20 +1684,24 @@ struct GemmCall {
 //     every query ends in the exact device scan). The limit sits behind the last clear gain.
 constexpr int kI8AutoMinQueries = FIR_I8_AUTO_MIN_QUERIES;
 constexpr float kI8AutoMaxRG = 0.0125f;
+// Builds the int8 copy on `st` (one synchronisation). On any failure the state is left as gemm_free_i8_ leaves it.
 static int gemm_build_i8_(fir_gemm* m, hipStream_t st) {
     const int64_t n = m->v.n, rblocks = (std::max<int64_t>(n, 1) + 31) / 32, tiles = (n + 63) / 64;
     const int d4 = (m->feat + 3) / 4;
     m->dk8 = (m->feat + 32 * kRing - 1) / (32 * kRing) * kRing;
-    double* partial = nullptr;
-    FIR_HIP(hipMalloc((void**)&m->g8, (size_t)rblocks * m->dk8 * 64 * sizeof(uint4)));
-    FIR_HIP(hipMalloc((void**)&m->i8_mu, (size_t)d4 * 4 * sizeof(float)));
-    FIR_HIP(hipMalloc((void**)&m->i8_gnorm, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
-    FIR_HIP(hipMalloc((void**)&m->i8_par, 8 * sizeof(float)));
-    for (int b = 0; b < 2; ++b) FIR_HIP(hipMalloc((void**)&m->i8_eabs[b], kPasses * kQT * sizeof(float)));
-    FIR_HIP(hipMalloc((void**)&m->sc_eabs, kScQueries * sizeof(float)));
+    auto undo = fir_on_exit([m] { if (!m->i8_built) gemm_free_i8_(m); });
+    GemmBuf<double> partial;              // column sums per row slice: this build's only
+    int rc = FIR_OK;
+    if ((rc = FIR_RESERVE(m->g8, (size_t)rblocks * m->dk8 * 64 * sizeof(uint4)))) return rc;
+    if ((rc = FIR_RESERVE(m->i8_mu, (size_t)d4 * 4 * sizeof(float)))) return rc;
+    if ((rc = FIR_RESERVE(m->i8_gnorm, (size_t)std::max<int64_t>(n, 1) * sizeof(float)))) return rc;
+    if ((rc = FIR_RESERVE(m->i8_par, 8 * sizeof(float)))) return rc;
+    for (int b = 0; b < 2; ++b)
+        if ((rc = FIR_RESERVE(m->set[b].eabs, kPasses * kQT * sizeof(float)))) return rc;
+    if ((rc = FIR_RESERVE(m->sc.eabs, kScQueries * sizeof(float)))) return rc;
     FIR_HIP(hipHostMalloc((void**)&m->i8_pin, 64, hipHostMallocDefault));
     FIR_HIP(hipEventCreateWithFlags(&m->i8_ev, hipEventDisableTiming));
-    FIR_HIP(hipMalloc((void**)&partial, (size_t)kI8Slices * d4 * 4 * sizeof(double)));
+    if ((rc = FIR_RESERVE(partial, (size_t)kI8Slices * d4 * 4 * sizeof(double)))) return rc;
     hipLaunchKernelGGL(k_i8_colsum, dim3(d4, kI8Slices), dim3(256), 0, st, m->gal4, tiles, m->dp4, partial);
     hipLaunchKernelGGL(k_i8_mean, dim3((d4 * 4 + 255) / 256), dim3(256), 0, st, (const double*)partial, d4, m->feat, n, m->i8_mu, m->i8_par);
     hipLaunchKernelGGL(k_i8_rows<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->feat, (const float*)m->i8_mu, m->i8_gnorm, m->i8_par);
@@ -1692,11 +1711,9 @@ static int gemm_build_i8_(fir_gemm* m, hipStream_t st) {
     hipLaunchKernelGGL(k_i8_pack_gallery, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, m->gal4, n, m->dp4, m->dk8, m->feat, (const float*)m->i8_mu,
                        (const float*)m->i8_par, m->g8);
     float h[4] = {0.f, 0.f, 0.f, 0.f};
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, m->i8_par, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                  // the copy's one synchronisation
-    (void)hipFree(partial);
-    FIR_HIP(e);
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(h, m->i8_par, sizeof h, hipMemcpyDeviceToHost, st));
+    FIR_HIP(hipStreamSynchronize(st));                  // the copy's one synchronisation
     m->i8_G = std::sqrt(h[2]);
     m->i8_R = h[3];
     m->i8_built = true;
@@ -1726,10 +1743,9 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
         const int rc = gemm_build_i8_(m, c.st);
         if (rc) {
             // No room for the copy: in EVERY mode this call and all later ones are answered by the fp16 pass (the same keys), what was
-            // allocated is given back, and fir_gallery_last_dispatch says "int8 nomination off for this gallery: no memory". Any other
-            // failure is the call's error.
+            // allocated has been given back, and fir_gallery_last_dispatch says "int8 nomination off for this gallery: no memory". Any
+            // other failure is the call's error.
             (void)hipGetLastError();
-            gemm_free_i8_(m);
             if (rc != FIR_ERR_NOMEM) return rc;
             m->i8_off = true; m->i8_off_why = "no memory";
             c.i8_went_back = true;
@@ -1766,96 +1782,106 @@ static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
 static int gemm_fb_reserve_(fir_gemm* m, int32_t qb) {
     if ((size_t)qb <= m->ok_cap) return FIR_OK;
     FIR_HIP(hipDeviceSynchronize());                        // (an earlier call's kernels may still read the old ones)
-    (void)hipFree(m->ok); (void)hipFree(m->fb_list); (void)hipFree(m->fb_list2); (void)hipFree(m->fb_tau2);
-    m->ok = nullptr; m->fb_list = nullptr; m->fb_list2 = nullptr; m->fb_tau2 = nullptr;
     m->ok_cap = 0;
+    for (FirBuf* b : std::initializer_list<FirBuf*>{&m->ok, &m->fb_list, &m->fb_list2, &m->fb_tau2}) b->release();
     const size_t cap = (size_t)std::max(qb, 1024);
-    FIR_HIP(hipMalloc((void**)&m->ok, cap * sizeof(int)));
-    FIR_HIP(hipMalloc((void**)&m->fb_list, cap * sizeof(int)));
-    FIR_HIP(hipMalloc((void**)&m->fb_list2, cap * sizeof(int)));
-    FIR_HIP(hipMalloc((void**)&m->fb_tau2, cap * sizeof(float)));
+    int rc = FIR_OK;
+    if ((rc = FIR_RESERVE(m->ok, cap * sizeof(int))) || (rc = FIR_RESERVE(m->fb_list, cap * sizeof(int))) || (rc = FIR_RESERVE(m->fb_list2, cap * sizeof(int))) ||
+        (rc = FIR_RESERVE(m->fb_tau2, cap * sizeof(float))))
+        return rc;
     m->ok_cap = cap;
     return FIR_OK;
 }
 
-// What a call needs beyond the state's fixed scratch. Candidate lists and counts: sized by the super-batch in use (whole 128-query
-// pairs), not by the largest one possible -- a cache-resident gallery that gets 128-query calls holds 8 MiB of lists, not 512
-// (ADVICE r2). f32 / bf16: the sample of the order-statistic flow (every sampled proxy), on first use.
-static int gemm_reserve_(fir_gemm* m, const GemmCall& c) {
-    const int rcr = gemm_fb_reserve_(m, c.qb);
-    if (rcr) return rcr;
-    const int need = (std::min(c.sbq, c.qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
-    if (need > m->lists_cap) {
-        FIR_HIP(hipStreamSynchronize(c.st));
-        FIR_HIP(hipStreamSynchronize(m->side));
-        for (int b = 0; b < 2; ++b) {
-            (void)hipFree(m->lists[b]); (void)hipFree(m->counts[b]);
-            m->lists[b] = nullptr; m->counts[b] = nullptr;
-        }
-        m->lists_cap = 0;
-        for (int b = 0; b < 2; ++b) {
-            FIR_HIP(hipMalloc((void**)&m->lists[b], (size_t)need * kListCap * sizeof(unsigned long long)));
-            FIR_HIP(hipMalloc((void**)&m->counts[b], (size_t)need * sizeof(int)));
-        }
-        m->lists_cap = need;
+// Candidate lists and counts of the first `sets` scratch sets, for super-batches of up to nq queries: sized by the super-batch in use
+// (whole 128-query pairs), not by the largest one possible -- a cache-resident gallery that gets 128-query calls holds 8 MiB of lists,
+// not 512. Before the old ones go, `wait` is synchronised: the streams whose queued work may still use them.
+static int gemm_grow_lists_(fir_gemm* m, int sets, int nq, std::initializer_list<hipStream_t> wait) {
+    const int need = (nq + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
+    if (need <= m->lists_cap) return FIR_OK;
+    for (hipStream_t s : wait) FIR_HIP(hipStreamSynchronize(s));
+    m->lists_cap = 0;
+    for (int b = 0; b < sets; ++b) { m->set[b].lists.release(); m->set[b].counts.release(); }
+    for (int b = 0; b < sets; ++b) {
+        int rc = FIR_OK;
+        if ((rc = FIR_RESERVE(m->set[b].lists, (size_t)need * kListCap * sizeof(unsigned long long))) || (rc = FIR_RESERVE(m->set[b].counts, (size_t)need * sizeof(int)))) return rc;
     }
-    if (m->precision != FIR_GEMM_F16 && !m->sample)
-        FIR_HIP(hipMalloc((void**)&m->sample, (size_t)kPasses * kQT * m->sample_rows * sizeof(float)));
+    m->lists_cap = need;
     return FIR_OK;
 }
 
+// What a call needs beyond the state's fixed scratch: the lists of its uncertified queries, candidate lists for its super-batches and,
+// f32 / bf16, the sample of the order-statistic flow (every sampled proxy), on first use.
+static int gemm_reserve_(fir_gemm* m, const GemmCall& c) {
+    int rc = gemm_fb_reserve_(m, c.qb);
+    if (rc || (rc = gemm_grow_lists_(m, 2, std::min(c.sbq, c.qb), {c.st, m->side}))) return rc;
+    if (m->precision != FIR_GEMM_F16) return FIR_RESERVE(m->sample, (size_t)kPasses * kQT * m->sample_rows * sizeof(float));
+    return FIR_OK;
+}
+
+// The sample flow's sample pass on `st` (k_gemm_proxy_f16x<2, *>): per query of the set's first `pairs` pairs, smin <- the smallest proxy over
+// rt_sample_rows rows -- for the K > 1 nearest as kRtSubsets disjoint subsets' minima, kPasses * kQT words apart ...
+static int gemm_sample_stride_(int k) { return k > 1 ? kPasses * kQT : 0; }
+static int gemm_sample_pass_(fir_gemm* m, const GemmScratch& s, hipStream_t st, bool streamed, int odd, int pairs, int k) {
+    const int sub_stride = gemm_sample_stride_(k);
+    FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)s.smin, (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, st));
+    // every rb_stride-th row block: the sample is spread over the whole gallery
+    const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
+    const int rb_stride = (int)std::max<int64_t>(1, ((m->v.n + 31) / 32) / sample_blocks);
+    for (int p0 = 0; p0 < pairs;) {
+        const int P = launch_pairs_(pairs - p0, kShareMax);
+        gemm_launch_x_(pick_x({2, streamed, odd}), dim3(m->v.cus), kGemmBlock, st, gemm_operand_(m, false), s, p0, P, m->v.n, sample_blocks * 32, rb_stride, kSampleOnly,
+                       {false, 0, P <= 1 ? 1 : 0, s.smin, 1, sub_stride});
+        p0 += P;
+    }
+    return FIR_OK;
+}
+// ... and the bound from it: tau = the smallest sampled proxy + one window (top-1: k_gemm_tau_min), the K-th smallest of the subsets'
+// minima + one window (top-K: k_gemm_tau_kmin)
+static void gemm_sample_tau_(fir_gemm* m, const GemmScratch& s, hipStream_t st, int pairs, int nq, int k, float e_rel) {
+    if (k > 1)
+        hipLaunchKernelGGL(k_gemm_tau_kmin, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, s.smin, gemm_sample_stride_(k), k, s.tau, pairs * 2 * kQT, nq, s.qnorm,
+                           m->gmax, e_rel);
+    else
+        hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, s.smin, s.tau, pairs * 2 * kQT, nq, s.qnorm, m->gmax, e_rel);
+}
+
 // fp16 preparation of one super-batch on `ps`: per-query norms and scales, the query fragments and -- unless the full pass finds its
-// threshold on the way -- the sample flow: the smallest proxy of a row sample per query (k_gemm_proxy_f16x<2, *> over rt_sample_rows
-// rows), tau = that + one window (top-1: k_gemm_tau_min), the K-th smallest of kRtSubsets disjoint subsets' minima + one window
-// (top-K: k_gemm_tau_kmin).
+// threshold on the way -- the sample flow (gemm_sample_pass_, gemm_sample_tau_).
 static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb) {
     const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
+    GemmScratch& s = m->set[b];
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;        // 128 queries per gallery read; a half-filled pair is zero-padded
     const float* dq = c.sb_first(sb);
     if (c.i8) {                                             // (fir_gemm_i8.h: always the threshold found on the way)
         hipLaunchKernelGGL(k_gemm_qprep_i8, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, c.d, c.qs, (const float*)m->i8_mu, (const float*)m->i8_par, c.e_rel,
-                           m->erel_scale, m->qnorm[b], m->qmul[b], m->qinv[b], m->i8_eabs[b], m->counts[b], m->awin[b], m->aT[b], sb == 0 ? m->fb_state : (int*)nullptr,
+                           m->erel_scale, s.qnorm, s.qmul, s.qinv, s.eabs, s.counts, s.awin, s.aT, sb == 0 ? m->fb_state : (int*)nullptr,
                            (const int*)nullptr, (const int*)nullptr, 0, (const float*)nullptr, (float*)nullptr);
         hipLaunchKernelGGL(k_gemm_pack_queries_i8, dim3((4 * m->dk8 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk8, (const float*)m->i8_mu,
-                           (const float*)m->qmul[b], m->qbf[b], c.qs);
+                           (const float*)s.qmul, s.qbf, c.qs);
         return FIR_OK;
     }
     const bool adaptive = adaptive_for_(m, c, nq);
     // (the candidate counts are cleared, the call's two list lengths by its first super-batch and, for the adaptive pass, the per-query
     // windows and start values are set by the same launch)
-    hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, c.d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], c.qs,
-                       m->counts[b], adaptive ? m->awin[b] : (float*)nullptr, adaptive ? m->aT[b] : (unsigned int*)nullptr,
+    hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(pairs * 2 * kQT), dim3(64), 0, ps, dq, nq, c.d, m->gallery_exp, s.qnorm, s.qmul, s.qinv, c.qs,
+                       s.counts, adaptive ? s.awin : (float*)nullptr, adaptive ? s.aT : (unsigned int*)nullptr,
                        (const float*)m->gmax, c.e_rel, k > 1 ? k : 0, (unsigned int*)nullptr, sb == 0 ? m->fb_state : (int*)nullptr);
-    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk16, m->qmul[b],
-                       m->qbf[b], c.qs);
+    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk16, s.qmul,
+                       s.qbf, c.qs);
     if (adaptive) return FIR_OK;
     if (c.num_classes > 0) {
         // distinct classes: D_s = the exact K-th smallest class minimum over the leading sample rows (four times list_row_samples' sizing:
         // profiles/class_rank_matrix_cores.txt), turned into the append pass's bound in place; padding queries get -inf
         const int64_t rows = std::min<int64_t>(c.n, std::max<int64_t>(kClassSampleRows, c.n * k / m->class_sample_div));
-        const int rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.num_classes, k, rows, nullptr, nullptr, m->tau[b], ps);
+        const int rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.num_classes, k, rows, nullptr, nullptr, s.tau, ps);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->tau[b], pairs * 2 * kQT, nq, c.d, m->qnorm[b], m->gmax, c.e_rel);
+        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
         return FIR_OK;
     }
-    const int sub_stride = k > 1 ? kPasses * kQT : 0;      // top-K: the sample as kRtSubsets subset minima per query
-    FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, ps));
-    // every rb_stride-th row block: the sample is spread over the whole gallery
-    const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
-    const int rb_stride = (int)std::max<int64_t>(1, ((c.n + 31) / 32) / sample_blocks);
-    for (int p0 = 0; p0 < pairs;) {
-        const int P = launch_pairs_(pairs - p0, kShareMax);
-        const size_t qo = (size_t)p0;
-        hipLaunchKernelGGL(pick_x(2, c.streamed, c.odd), dim3(c.grid), dim3(kGemmBlock), kHalfLds, ps, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
-                           m->qinv[b] + qo * 2 * kQT, c.n, (int64_t)0, sample_blocks * 32, m->dk16, m->tau[b], m->lists[b], m->counts[b], (float*)nullptr,
-                           0, P, P <= 1 ? 1 : 0, rb_stride, m->smin[b] + qo * 2 * kQT, sub_stride);
-        p0 += P;
-    }
-    if (sub_stride)
-        hipLaunchKernelGGL(k_gemm_tau_kmin, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], sub_stride, k, m->tau[b], pairs * 2 * kQT, nq,
-                           m->qnorm[b], m->gmax, c.e_rel);
-    else
-        hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, m->smin[b], m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, c.e_rel);
+    const int rc = gemm_sample_pass_(m, s, ps, c.streamed, c.odd, pairs, k);
+    if (rc) return rc;
+    gemm_sample_tau_(m, s, ps, pairs, nq, k, c.e_rel);
     return FIR_OK;
 }
 
@@ -1863,21 +1889,22 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
 // kCand-th smallest of them (k_gemm_tau)
 static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb) {
     const int b = sb & 1, nq = c.sb_queries(sb), np = (nq + kQT - 1) / kQT;
+    GemmScratch& s = m->set[b];
     const float* dq = c.sb_first(sb);
     const int sample_rows = m->sample_rows, sample_grid = (sample_rows + 63) / 64;
-    hipLaunchKernelGGL(k_gemm_qnorm, dim3(np * kQT), dim3(64), 0, ps, dq, nq, c.d, m->qnorm[b]);
-    FIR_HIP(hipMemsetAsync(m->counts[b], 0, (size_t)np * kQT * sizeof(int), ps));
+    hipLaunchKernelGGL(k_gemm_qnorm, dim3(np * kQT), dim3(64), 0, ps, dq, nq, c.d, s.qnorm);
+    FIR_HIP(hipMemsetAsync(s.counts, 0, (size_t)np * kQT * sizeof(int), ps));
     if (m->precision == FIR_GEMM_F32) {
-        hipLaunchKernelGGL(k_gemm_pack_queries, dim3(((kQT / 32) * m->dq8 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dq8, m->qm[b]);
-        hipLaunchKernelGGL(k_gemm_proxy<0>, dim3(sample_grid, np), dim3(128), c.lds, ps, m->gm, m->gnorm, m->qm[b], c.n, (int64_t)0,
-                           (int64_t)sample_rows, m->dq8, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+        hipLaunchKernelGGL(k_gemm_pack_queries, dim3(((kQT / 32) * m->dq8 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dq8, s.qbf.as<float4>());
+        hipLaunchKernelGGL(k_gemm_proxy<0>, dim3(sample_grid, np), dim3(128), c.lds, ps, m->gm, m->gnorm, s.qbf.as<float4>(), c.n, (int64_t)0,
+                           (int64_t)sample_rows, m->dq8, s.tau, s.lists, s.counts, m->sample, sample_rows);
     } else {
         hipLaunchKernelGGL(k_gemm_pack_queries_bf16, dim3(((kQT / 32) * m->dk16 * 64 + 255) / 256, np), dim3(256), 0, ps, dq, nq, c.d, m->dk16,
-                           m->qbf[b]);
-        hipLaunchKernelGGL(k_gemm_proxy_bf16<0>, dim3(sample_grid, np), dim3(128), 0, ps, m->gb, m->gnorm, m->qbf[b], c.n, (int64_t)0,
-                           (int64_t)sample_rows, m->dk16, m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+                           s.qbf);
+        hipLaunchKernelGGL(k_gemm_proxy_bf16<0>, dim3(sample_grid, np), dim3(128), 0, ps, m->gb, m->gnorm, s.qbf, c.n, (int64_t)0,
+                           (int64_t)sample_rows, m->dk16, s.tau, s.lists, s.counts, m->sample, sample_rows);
     }
-    hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, m->tau[b], 0x7FFFFFFF, m->qnorm[b], m->gmax, c.e_rel,
+    hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, s.tau, 0x7FFFFFFF, s.qnorm, m->gmax, c.e_rel,
                        c.k > 1 ? 1 : 0);
     return FIR_OK;
 }
@@ -1916,67 +1943,48 @@ static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
 // The fp16 full passes of one super-batch on `st` -- the launches fir_profile_read times and fir_gallery_last_dispatch names. The pairs
 // of the super-batch read the gallery together, a power of two of them per launch. Two shapes: the threshold found on the way
 // (k_gemm_proxy_f16x<3 | 4, *>, then k_gemm_adapt_final hands the re-rank its bound) or, after the sample flow, append below tau (<1, *>).
+// An int8 call (always the threshold found on the way) makes the same launches over the int8 copy -- half the pieces per row block, the
+// centred rows' norms -- and differs in its tile: with two units per row block (257-512 features) and two pairs or more in the launch it
+// takes the 256-query tile -- P / 2 workgroups share a row range, each with two pairs' queries in LDS (two 64-KiB images fill what the
+// fp16 tile takes) and every gallery fragment multiplied against both, so the fragments cross from L2 to the CUs half as often. A
+// one-pair launch (the odd pair of a call) and every other row length keep the 128-query forms. Such a launch takes up to 2 kShareMax
+// pairs -- sixteen tiles over sixteen row ranges, 4 096 queries per read of the gallery -- which measured 3 % over sixteen pairs from
+// 32 768 queries per call on. The rule: always (profiles/int8_tile256.txt).
 static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
     const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;
     const int64_t n = c.n;
-    if (c.i8) {
-        // the int8 form: the same launches over the int8 copy -- half the pieces per row block, the centred rows' norms
-        auto bytes8 = [&](int P) { return (double)((n + 31) / 32) * m->dk8 * 1024.0 + P * (4.0 * m->dk8 * 1024.0 + 128.0 * 8.0); };
-        // Two units per row block (257-512 features) and two pairs or more in the launch: the 256-query tile -- P / 2 workgroups share a
-        // row range, each with two pairs' queries in LDS (two 64-KiB images fill what the fp16 tile takes) and every gallery fragment
-        // multiplied against both, so the fragments cross from L2 to the CUs half as often. A one-pair launch (the odd pair of a call)
-        // and every other row length keep the 128-query forms. Such a launch takes up to 2 kShareMax pairs -- sixteen tiles over sixteen
-        // row ranges, 4 096 queries per read of the gallery -- which measured 3 % over sixteen pairs from 32 768 queries per call on. The
-        // rule: always (profiles/int8_tile256.txt).
-        const bool tile256 = m->i8_tile != 0 && m->dk8 == 2 * kRing && pairs >= 2;
-        const fir_x8_entry& ran8 = tile256 ? kX8Tile256 : find_x8(3, c.odd);
-        int nl = 0, pf = 1, rc8 = FIR_OK;
-        for (int p0 = 0; p0 < pairs; ++nl) {
-            const int P = launch_pairs_(pairs - p0, tile256 ? 2 * kShareMax : kShareMax);
-            if (p0 == 0) pf = P;
-            const size_t qo = (size_t)p0;
-            const bool tile = tile256 && P >= 2;
-            if ((rc8 = fir_gallery_profile_begin_(m->g, c.st))) return rc8;
-            hipLaunchKernelGGL(tile ? pick_x8_tile256(m->dbg_skip) : pick_x8(3, c.odd, m->dbg_skip), dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->g8, m->i8_gnorm, m->qbf[b] + qo * 4 * m->dk8 * 64, m->qinv[b] + qo * 2 * kQT,
-                               n, (int64_t)0, n, m->dk8, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT,
-                               m->qnorm[b] + qo * 2 * kQT, m->sample_rows, tile ? P / 2 : P, (P <= 1 ? 1 : 0) | m->adapt_dbg, 1, m->aT[b] + qo * 2 * kQT, 0);
-            if ((rc8 = fir_gallery_profile_end_(m->g, c.st, bytes8(P)))) return rc8;
-            p0 += P;
-        }
-        fir_gallery_note_dispatch_(m->g, (const void*)ran8.fn, ran8.name, sb == 0, c.grid, nl, kGemmBlock, kHalfLds, 128 * pf, bytes8(pf), 2.0 * (double)n * c.d * 128.0 * pf);
-        hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, 0);
-        return FIR_OK;
-    }
-    const bool adaptive = adaptive_for_(m, c, nq);
-    // (a super-batch of at most 16 / 32 queries: one / two query blocks of the tile are live -- the pass multiplies against those only;
+    const GemmOperand op = gemm_operand_(m, c.i8);
+    const GemmScratch& s = m->set[b];
+    const bool adaptive = c.i8 || adaptive_for_(m, c, nq);
+    const bool tile256 = c.i8 && m->i8_tile != 0 && m->dk8 == 2 * kRing && pairs >= 2;
+    const int share_cap = tile256 ? 2 * kShareMax : c.streamed ? kShareStreamed : kShareMax;
+    // (a super-batch of at most 16 / 32 queries: one / two query blocks of the tile are live -- the fp16 pass multiplies against those only;
     // whole, even numbers of the form's units per row: eight pieces streamed, sixteen resident)
     const bool njb_shape = c.streamed ? !c.odd : (m->dk16 % (4 * kRing)) == 0;
-    const int njb = (k == 1 && adaptive && !m->dbg_skip && njb_shape) ? (nq <= 16 ? 1 : nq <= 32 ? 2 : 8) : 8;
+    const int njb = (!c.i8 && k == 1 && adaptive && !m->dbg_skip && njb_shape) ? (nq <= 16 ? 1 : nq <= 32 ? 2 : 8) : 8;
     const int mode = adaptive ? (k > 1 ? 4 : 3) : 1;
-    // algorithmic bytes of ONE launch (what fir_profile_read's event pairs bracket): the fp16 fragments once for the pairs that
+    const int block = adaptive && !c.i8 && !c.streamed ? m->dbg_block : kGemmBlock;
+    // algorithmic bytes of ONE launch (what fir_profile_read's event pairs bracket): the fragments once for the pairs that
     // read them together, every pair's query tile and keys
-    auto launch_bytes = [&](int P) { return (double)((n + 31) / 32) * m->dk16 * 1024.0 + P * (4.0 * m->dk16 * 1024.0 + 128.0 * 8.0); };
+    auto launch_bytes = [&](int P) { return (double)((n + 31) / 32) * op.dk * 1024.0 + P * (4.0 * op.dk * 1024.0 + 128.0 * 8.0); };
     int nlaunch = 0, p_first = 1, rc = FIR_OK;
     for (int p0 = 0; p0 < pairs; ++nlaunch) {
-        const int P = launch_pairs_(pairs - p0, c.streamed ? kShareStreamed : kShareMax);
+        const int P = launch_pairs_(pairs - p0, share_cap);
         if (p0 == 0) p_first = P;
         const int nt = P <= 1 ? 1 : 0;                           // read once per launch: non-temporal
-        const size_t qo = (size_t)p0;
+        const bool tile = tile256 && P >= 2;
+        const fir_x_fn fn = pick_x({mode, c.streamed, c.odd, njb, c.i8, tile, k > 1 ? 0 : m->dbg_skip});
         if ((rc = fir_gallery_profile_begin_(m->g, c.st))) return rc;
         if (adaptive)
-            hipLaunchKernelGGL(pick_x(mode, c.streamed, c.odd, k > 1 ? 0 : m->dbg_skip, njb), dim3(c.grid, 1), dim3(c.streamed ? kGemmBlock : m->dbg_block), kHalfLds, c.st,
-                               m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->awin[b] + qo * 2 * kQT,
-                               m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->qnorm[b] + qo * 2 * kQT, m->sample_rows, P, nt | m->adapt_dbg, 1,
-                               m->aT[b] + qo * 2 * kQT * (k > 1 ? 8 : 1), k > 1 ? k : 0);
+            gemm_launch_x_(fn, dim3(c.grid, 1), block, c.st, op, s, p0, P, n, n, 1, kBelowAwin,
+                           {true, m->sample_rows, nt | m->adapt_dbg, s.aT, k > 1 ? 8 : 1, k > 1 ? k : 0, tile ? 2 : 1});
         else
-            hipLaunchKernelGGL(pick_x(mode, c.streamed, c.odd), dim3(c.grid, 1), dim3(kGemmBlock), kHalfLds, c.st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64,
-                               m->qinv[b] + qo * 2 * kQT, n, (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap,
-                               m->counts[b] + qo * 2 * kQT, (float*)nullptr, m->sample_rows, P, nt, 1, (unsigned int*)nullptr, 0);
+            gemm_launch_x_(fn, dim3(c.grid, 1), block, c.st, op, s, p0, P, n, n, 1, kBelowTau, {false, m->sample_rows, nt, nullptr, 0, 0});
         if ((rc = fir_gallery_profile_end_(m->g, c.st, launch_bytes(P)))) return rc;
         p0 += P;
     }
-    const fir_x_entry& ran = find_x(mode, c.streamed, c.odd, njb);
+    const fir_x_entry& ran = find_x({mode, c.streamed, c.odd, njb, c.i8, tile256});
     const char* ran_name = ran.name;
     if (c.i8_went_back) {
         if (sb == 0) m->i8_note = std::string(ran.name) + " (int8 nomination off for this gallery: " + m->i8_off_why + ")";
@@ -1985,17 +1993,18 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
     fir_gallery_note_dispatch_(m->g, (const void*)ran.fn, ran_name, sb == 0, c.grid, nlaunch, kGemmBlock, kHalfLds, 128 * p_first, launch_bytes(p_first),
                                2.0 * (double)n * c.d * 128.0 * p_first);
     if (adaptive)
-        hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, k > 1 ? k : 0);
+        hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, c.st, s.aT, s.qnorm, s.tau, pairs * 2 * kQT, nq, k > 1 ? k : 0);
     return FIR_OK;
 }
 
 // The f32 / bf16-split full passes of one super-batch on `st`: every row below tau is appended
 static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
     const int b = sb & 1, np = (c.sb_queries(sb) + kQT - 1) / kQT, grid = c.grid, sample_rows = m->sample_rows;
+    GemmScratch& s = m->set[b];
     const int64_t n = c.n;
     if (m->precision == FIR_GEMM_F32) {
-        hipLaunchKernelGGL(k_gemm_proxy<1>, dim3(grid, np), dim3(kGemmBlock), c.lds, c.st, m->gm, m->gnorm, m->qm[b], n, (int64_t)0, n, m->dq8,
-                           m->tau[b], m->lists[b], m->counts[b], m->sample, sample_rows);
+        hipLaunchKernelGGL(k_gemm_proxy<1>, dim3(grid, np), dim3(kGemmBlock), c.lds, c.st, m->gm, m->gnorm, s.qbf.as<float4>(), n, (int64_t)0, n, m->dq8,
+                           s.tau, s.lists, s.counts, m->sample, sample_rows);
         fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy<1>, "fir::k_gemm_proxy<1>", sb == 0, grid, np, kGemmBlock, c.lds, 64,
                                    np * ((double)((n + 31) / 32) * m->dq8 * 1024.0), 2.0 * (double)n * c.d * 64.0 * np);
         return;
@@ -2003,13 +2012,13 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
     // pairs of passes share one read of the gallery (128 queries per wave); an odd last pass goes alone
     const int pairs = m->wide ? np / 2 : 0;
     if (pairs > 0)
-        hipLaunchKernelGGL(k_gemm_proxy_bf16_wide, dim3(grid, pairs), dim3(kGemmBlock), kWideLds, c.st, m->gb, m->gnorm, m->qbf[b], n, m->dk16,
-                           m->tau[b], m->lists[b], m->counts[b]);
+        hipLaunchKernelGGL(k_gemm_proxy_bf16_wide, dim3(grid, pairs), dim3(kGemmBlock), kWideLds, c.st, m->gb, m->gnorm, s.qbf, n, m->dk16,
+                           s.tau, s.lists, s.counts);
     if (np > 2 * pairs) {
         const size_t p0 = (size_t)2 * pairs;
         hipLaunchKernelGGL(k_gemm_proxy_bf16<1>, dim3(grid, np - 2 * pairs), dim3(kGemmBlock), c.lds, c.st, m->gb, m->gnorm,
-                           m->qbf[b] + p0 * (kQT / 32) * m->dk16 * 128, n, (int64_t)0, n, m->dk16, m->tau[b] + p0 * kQT,
-                           m->lists[b] + p0 * kQT * kListCap, m->counts[b] + p0 * kQT, m->sample + p0 * kQT * sample_rows, sample_rows);
+                           s.qbf + p0 * (kQT / 32) * m->dk16 * 128, n, (int64_t)0, n, m->dk16, s.tau + p0 * kQT,
+                           s.lists + p0 * kQT * kListCap, s.counts + p0 * kQT, m->sample + p0 * kQT * sample_rows, sample_rows);
     }
     fir_gallery_note_dispatch_(m->g, (const void*)k_gemm_proxy_bf16_wide, pairs > 0 ? "fir::k_gemm_proxy_bf16_wide" : "fir::k_gemm_proxy_bf16<1>", sb == 0,
                                grid, pairs > 0 ? pairs : np, kGemmBlock, pairs > 0 ? (size_t)kWideLds : c.lds, pairs > 0 ? 128 : 64,
@@ -2019,13 +2028,14 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
 // exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list
 static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
     const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
+    GemmScratch& s = m->set[b];
     if (c.num_classes > 0)
-        hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, m->lists[b], m->counts[b], m->tau[b], m->gal4, c.sb_first(sb), m->qnorm[b], m->gmax,
+        hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, m->gal4, c.sb_first(sb), s.qnorm, m->gmax,
                            m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
                            c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
                            c.qs, m->rowmajor);
     else
-        gemm_launch_rerank_(m, rs, nq, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b], c.i8 ? m->i8_eabs[b] : nullptr, c.i8 ? m->i8_par + 2 : nullptr}, c.sb_first(sb),
+        gemm_launch_rerank_(m, rs, nq, gemm_slot_(m, s, c.i8), c.sb_first(sb),
                             c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0, {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
 }
 
@@ -2033,10 +2043,11 @@ static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs)
 // audit builds: what FIR_GEMM_DUMP_PHASES / FIR_GEMM_DEBUG_COUNTS ask for about the call's last super-batch (synchronises)
 static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
     const int last = c.nsb - 1, b = last & 1;
+    GemmScratch& s = m->set[b];
     if (!m->dump_phases.empty()) {                     // with FIR_GEMM_DBG_SKIP=256: the load-burst timestamps of the first pair
         FIR_HIP(hipStreamSynchronize(c.st));
         std::vector<unsigned long long> h(8 * 256);
-        FIR_HIP(hipMemcpy(h.data(), m->lists[b] + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(h.data(), s.lists + (size_t)(2 * kQT - 1) * kListCap + 2048, h.size() * 8, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(m->dump_phases.c_str(), "w")) {
             for (int w = 0; w < 8; ++w)
                 for (int u = 0; u < 240; ++u) std::fprintf(f, "%d %d %llu %llu\n", w, u, h[(size_t)w * 256 + u] >> 20, h[(size_t)w * 256 + u] & 0xFFFFFull);
@@ -2050,14 +2061,14 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
         FIR_HIP(hipStreamSynchronize(c.st));
         const int nql = c.sb_queries(last);
         std::vector<int> hc((size_t)nql), h_ok((size_t)nql);
-        FIR_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(hc.data(), s.counts, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
         FIR_HIP(hipMemcpy(h_ok.data(), m->ok + (size_t)last * c.sbq, (size_t)nql * sizeof(int), hipMemcpyDeviceToHost));
         long long sum = 0;
         int mx = 0, bad = 0, over = 0;
         for (int v : hc) { sum += v; mx = std::max(mx, v); over += v > kListCap ? 1 : 0; }
         for (int v : h_ok) bad += v ? 0 : 1;
         std::vector<float> ht((size_t)nql);
-        FIR_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
+        FIR_HIP(hipMemcpy(ht.data(), s.tau, (size_t)nql * sizeof(float), hipMemcpyDeviceToHost));
         double ts = 0;
         int ninf = 0;
         for (float v : ht) { if (v < 1e30f) ts += v; else ++ninf; }
@@ -2124,11 +2135,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     if (c.i8) { c.streamed = false; c.odd = gemm_odd8_(m); }
     c.lds = m->precision == FIR_GEMM_F32 ? (size_t)(kQT / 32) * std::min(m->dq8, kSlab8) * 64 * sizeof(float4)
                                          : (size_t)(kQT / 32) * std::min(m->dk16, kSlab16) * 128 * sizeof(uint4);
-    // fp16: both operands rounded to 11 bits -> |q~.g~ - q.g| <= (2^-10 + 2^-22) sum|q_k g_k| + the sub-normal tails
-    // (< 2^-27 |q||g| for d <= 2^20), doubled in p and with |q||g| <= (|q|^2 + max|g|^2) / 2: 2^-10 (1 + 2^-4) covers it
-    c.e_rel = m->erel_scale * (8.0f * (float)c.d * 5.9604645e-8f +
-              (m->precision == FIR_GEMM_BF16_SPLIT ? 6.1035156e-5f : m->precision == FIR_GEMM_F16 ? 9.765625e-4f * 1.0625f : 0.0f));
-    if (c.i8) c.e_rel = m->erel_scale * (8.0f * (float)c.d * 5.9604645e-8f);      // int8: what is not relative is the query's eabs (fir_gemm_i8.h)
+    c.e_rel = gemm_e_rel_(m, c.i8);
     // Large super-batches amortise the boundaries between full passes (where the small kernels run: they cannot share a CU with a
     // full-pass workgroup), but a call needs a few super-batches for its preparation / re-rank to overlap anything: a quarter of the
     // call, in whole 1 024-query launches.
@@ -2232,33 +2239,22 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (n == 0) return fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, d, d_keys, st);
     const int nqt = qb <= 1 ? 1 : qb <= 2 ? 2 : qb <= 4 ? 4 : 8;
     if (nqt > m->proxies_nq) {
-        if (m->proxies) FIR_HIP(hipFree(m->proxies));
-        m->proxies = nullptr;
         m->proxies_nq = 0;
-        FIR_HIP(hipMalloc((void**)&m->proxies, (size_t)nqt * n * sizeof(float)));     // (FIR_ERR_NOMEM: the caller takes the exact scan)
+        m->proxies.release();
+        const int rcp = FIR_RESERVE(m->proxies, (size_t)nqt * n * sizeof(float));     // (FIR_ERR_NOMEM: the caller takes the exact scan)
+        if (rcp) return rcp;
         m->proxies_nq = nqt;
     }
-    if (m->lists_cap < 2 * kQT) {
-        for (int bb = 0; bb < 2; ++bb) {
-            (void)hipFree(m->lists[bb]); (void)hipFree(m->counts[bb]);
-            m->lists[bb] = nullptr; m->counts[bb] = nullptr;
-        }
-        m->lists_cap = 0;
-        for (int bb = 0; bb < 2; ++bb) {
-            FIR_HIP(hipMalloc((void**)&m->lists[bb], (size_t)2 * kQT * kListCap * sizeof(unsigned long long)));
-            FIR_HIP(hipMalloc((void**)&m->counts[bb], (size_t)2 * kQT * sizeof(int)));
-        }
-        m->lists_cap = 2 * kQT;
-    }
     {
-        const int rcr = gemm_fb_reserve_(m, qb);
-        if (rcr) return rcr;
+        int rcr = gemm_grow_lists_(m, 2, 2 * kQT, {});          // (no wait of its own: the first growth of a state, or none)
+        if (rcr || (rcr = gemm_fb_reserve_(m, qb))) return rcr;
     }
-    const float e_rel = m->erel_scale * (8.0f * (float)d * 5.9604645e-8f + 9.765625e-4f * 1.0625f);     // as gemm_search (one fp16 term)
+    const float e_rel = gemm_e_rel_(m, false);
     const int b = 0;
-    hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(2 * kQT), dim3(64), 0, st, d_queries, qb, d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], qs, m->counts[b],
-                       (float*)nullptr, (unsigned int*)nullptr, (const float*)nullptr, 0.f, 0, m->smin[b], m->fb_state);
-    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, qb, d, m->dk16, m->qmul[b], m->qbf[b], qs);
+    GemmScratch& s = m->set[b];
+    hipLaunchKernelGGL(k_gemm_qprep_f16, dim3(2 * kQT), dim3(64), 0, st, d_queries, qb, d, m->gallery_exp, s.qnorm, s.qmul, s.qinv, qs, s.counts,
+                       (float*)nullptr, (unsigned int*)nullptr, (const float*)nullptr, 0.f, 0, s.smin, m->fb_state);
+    hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, 1), dim3(256), 0, st, d_queries, qb, d, m->dk16, s.qmul, s.qbf, qs);
     const dim3 grid((unsigned)std::min<int64_t>((int64_t)m->v.cus * 8, ((n + 31) / 32 + 3) / 4));
     const size_t lds = (size_t)m->dk16 * 2 * nqt * sizeof(uint4);
     typedef void (*scan_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int, float*, unsigned int*);
@@ -2267,13 +2263,13 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     {
         int rcp = fir_gallery_profile_begin_(m->g, st);              // (no-ops unless profiling is on: a profiled run takes the same path as an unprofiled one)
         if (rcp) return rcp;
-        hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, m->gh, m->gnorm, m->qbf[b], m->qinv[b], n, m->dk16, m->proxies, m->smin[b]);
+        hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, m->gh, m->gnorm, s.qbf, s.qinv, n, m->dk16, m->proxies, s.smin);
         if ((rcp = fir_gallery_profile_end_(m->g, st, bytes))) return rcp;
     }
     fir_gallery_note_dispatch_(m->g, (const void*)scan, "fir::k_gemm_scan_f16x", 1, (int)grid.x, 1, 256, lds, nqt, bytes, 2.0 * (double)n * d * nqt);
-    hipLaunchKernelGGL(k_gemm_tau_min, dim3(1), dim3(256), 0, st, m->smin[b], m->tau[b], 2 * kQT, qb, m->qnorm[b], m->gmax, e_rel);
-    hipLaunchKernelGGL(k_gemm_select, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256), qb), dim3(256), 0, st, m->proxies, n, m->tau[b], m->lists[b], m->counts[b]);
-    gemm_launch_rerank_(m, st, qb, {m->lists[b], m->counts[b], m->tau[b], m->qnorm[b]}, d_queries, e_rel, 1, d_keys, m->ok,
+    hipLaunchKernelGGL(k_gemm_tau_min, dim3(1), dim3(256), 0, st, s.smin, s.tau, 2 * kQT, qb, s.qnorm, m->gmax, e_rel);
+    hipLaunchKernelGGL(k_gemm_select, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256), qb), dim3(256), 0, st, m->proxies, n, s.tau, s.lists, s.counts);
+    gemm_launch_rerank_(m, st, qb, gemm_slot_(m, s, false), d_queries, e_rel, 1, d_keys, m->ok,
                         {m->fb_state, m->fb_list, m->fb_tau2, 0, nullptr, 0});
     FIR_HIP(hipGetLastError());
     m->passes += 1;
@@ -2299,28 +2295,24 @@ int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, in
     if (!m->last_kind) return fir_fail_(FIR_ERR_STATE, "no call has run on this state yet");
     FIR_HIP(hipSetDevice(m->v.device));
     FIR_HIP(hipDeviceSynchronize());
-    const int b = m->last_b;
+    const GemmScratch& s = which ? m->sc : m->set[m->last_b];
     int have = m->last_nq, off = 0;
     if (which == 1) {
         int cnt = 0;
         FIR_HIP(hipMemcpy(&cnt, m->fb_state, sizeof(int), hipMemcpyDeviceToHost));
         const int rounds = std::min(m->last_sc_rounds, (cnt + kScQueries - 1) / kScQueries);
-        if (m->last_kind != 1 || rounds <= 0 || !m->sc_lists) have = 0;
+        if (m->last_kind != 1 || rounds <= 0 || !m->sc.lists) have = 0;
         else { off = (rounds - 1) * kScQueries; have = std::min(kScQueries, cnt - off); }
     }
     if (live) *live = have;
     if (gmax) FIR_HIP(hipMemcpy(gmax, m->last_i8 ? m->i8_par + 2 : m->gmax, sizeof(float), hipMemcpyDeviceToHost));
     if (nq == 0) return FIR_OK;
     if (q0 + nq > have) return fir_fail_(FIR_ERR_ARG, "slots [%d,%d) of %d", q0, q0 + nq, have);
-    const int* d_counts = which ? m->sc_counts : m->counts[b];
-    const float* d_tau = which ? m->sc_tau : m->tau[b];
-    const float* d_qnorm = which ? m->sc_qnorm : m->qnorm[b];
-    const unsigned long long* d_lists = which ? m->sc_lists : m->lists[b];
-    if (counts) FIR_HIP(hipMemcpy(counts, d_counts + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-    if (tau) FIR_HIP(hipMemcpy(tau, d_tau + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
-    if (qnorm) FIR_HIP(hipMemcpy(qnorm, d_qnorm + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+    if (counts) FIR_HIP(hipMemcpy(counts, s.counts + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+    if (tau) FIR_HIP(hipMemcpy(tau, s.tau + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+    if (qnorm) FIR_HIP(hipMemcpy(qnorm, s.qnorm + q0, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
     if (lists && max_entries > 0)
-        FIR_HIP(hipMemcpy2D(lists, (size_t)max_entries * 8, d_lists + (size_t)q0 * kListCap, (size_t)kListCap * 8, (size_t)max_entries * 8, (size_t)nq,
+        FIR_HIP(hipMemcpy2D(lists, (size_t)max_entries * 8, s.lists + (size_t)q0 * kListCap, (size_t)kListCap * 8, (size_t)max_entries * 8, (size_t)nq,
                             hipMemcpyDeviceToHost));
     if (qmap) {
         if (which) FIR_HIP(hipMemcpy(qmap, m->fb_list + off + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));

@@ -300,18 +300,8 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
     gemm_read_knobs_(m);      // (FIR_GEMM_EREL_SCALE, audit build: tests/test_gpu_cls.py shows that the suite can see an unsound bound here too)
     hipError_t e = hipSetDevice(device);
     const int64_t rblocks = (nt + 31) / 32;
-    if (e == hipSuccess) e = hipMalloc((void**)&m->gh, (size_t)rblocks * m->dk16 * 64 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->gnorm, (size_t)nt * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->gmax, 16);
-    const int b = 0;
-    if (e == hipSuccess) e = hipMalloc((void**)&m->qbf[b], (size_t)kPasses * (kQT / 32) * m->dk16 * 64 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->qnorm[b], kPasses * kQT * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->qmul[b], kPasses * kQT * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->qinv[b], kPasses * kQT * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->smin[b], (size_t)kRtSubsets * kPasses * kQT * sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->tau[b], kPasses * kQT * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->awin[b], kPasses * kQT * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&m->aT[b], (size_t)8 * kPasses * kQT * sizeof(unsigned int));
+    e = gemm_alloc_(e, {{&m->gh, (size_t)rblocks * m->dk16 * 64 * sizeof(uint4), true}, {&m->gnorm, (size_t)nt * sizeof(float), true}, {&m->gmax, 16, true}});
+    e = gemm_alloc_set_(e, m->set[0], (size_t)kPasses * (kQT / 32) * m->dk16 * 64 * sizeof(uint4));
     m->rt_sample_rows = (int)std::min<int64_t>(nt, std::max<int64_t>(kMinSampleRows, nt / 32));
     if (e == hipSuccess) e = gemm_x_lds_attr_();
     if (e == hipSuccess && row_lds > 48 * 1024)
@@ -324,10 +314,7 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
         hipLaunchKernelGGL(k_gemm_absmax_f64, dim3((unsigned)std::min<int64_t>((count2 + 255) / 256, 4096)), dim3(256), 0, st, m->gal2, count2, m->gmax);
         if (e == hipSuccess) e = hipMemcpyAsync(&h_max, m->gmax, sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        int ex = 0;
-        if (h_max > 0.f && h_max < __builtin_huge_valf()) { (void)std::frexp(h_max, &ex); m->gallery_exp = 14 - ex; }
-        else m->gallery_exp = h_max > 0.f ? 1000 : 0;
-        const float scale = (m->gallery_exp >= -100 && m->gallery_exp <= 100) ? std::ldexp(1.0f, m->gallery_exp) : 0.f;
+        const float scale = gemm_gallery_scale_(m, h_max);
         const int64_t totalh = rblocks * m->dk16 * 64;
         hipLaunchKernelGGL(k_gemm_pack_gallery_f16x_f64, dim3((unsigned)((totalh + 255) / 256)), dim3(256), 0, st, m->gal2, nt, dp2, m->dk16, scale, m->gh, d);
         hipLaunchKernelGGL(k_gemm_row_norms_f64, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, m->gal2, nt, dp2, m->gnorm);
@@ -337,7 +324,7 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
     }
     if (e != hipSuccess) {
         const int rc = fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "float64 matrix-core state: %s", hipGetErrorString(e));
-        m->v.stream = nullptr;
+        m->v.stream = nullptr;      // (the caller's stream: a float64 state without one is not waited for)
         fir_gemm_destroy(m);
         return rc;
     }
@@ -356,23 +343,14 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
     const int d = m->feat;
     const int64_t n = m->v.n;
     const int grid = m->v.cus;
-    const float e_rel = m->erel_scale * (8.0f * (float)d * 5.9604645e-8f + 9.765625e-4f * 1.0625f);
+    const float e_rel = gemm_e_rel_(m, false);
     const bool streamed = gemm_streamed_(m);
     const int odd = gemm_odd_(m);
     const int sbq = std::min(kPasses * kQT, std::max(1024, (qb + 1023) / 1024 * 1024));
-    {
-        const int need = (std::min(sbq, qb) + 2 * kQT - 1) / (2 * kQT) * (2 * kQT);
-        if (need > m->lists_cap) {
-            FIR_HIP(hipStreamSynchronize(st));
-            (void)hipFree(m->lists[0]); (void)hipFree(m->counts[0]);
-            m->lists[0] = nullptr; m->counts[0] = nullptr;
-            m->lists_cap = 0;
-            FIR_HIP(hipMalloc((void**)&m->lists[0], (size_t)need * kListCap * sizeof(unsigned long long)));
-            FIR_HIP(hipMalloc((void**)&m->counts[0], (size_t)need * sizeof(int)));
-            m->lists_cap = need;
-        }
-    }
+    if (const int rcl = gemm_grow_lists_(m, 1, std::min(sbq, qb), {st})) return rcl;
     const int b = 0;
+    const GemmScratch& s = m->set[b];
+    const GemmOperand op = gemm_operand_(m, false);
     const int share_cap = streamed ? kShareStreamed : kShareMax;
     const size_t rr_lds = (size_t)m->dp2 * sizeof(double2);
     bool first = true;
@@ -383,56 +361,36 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
         // (every super-batch: the pass starts from a threshold seeded by the row sample, so it is tight from its first row block on whatever the
         // number of row groups a workgroup sees -- 128 queries per call over 1M x 512: 1.83 -> 1.45 ms; profiles/r04_adaptive_cutoff.txt)
         const bool adaptive = m->adaptive > 0 && (kp == 1 || m->adaptive_topk);
-        hipLaunchKernelGGL(k_gemm_qprep_f16_f64, dim3(pairs * 2 * kQT), dim3(64), 0, st, dq, nq, d, m->gallery_exp, m->qnorm[b], m->qmul[b], m->qinv[b], m->counts[b], m->awin[b],
-                           adaptive ? m->aT[b] : (unsigned int*)nullptr, (const float*)m->gmax, e_rel, kp > 1 ? kp : 0);
-        hipLaunchKernelGGL(k_gemm_pack_queries_f16x_f64, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, st, dq, nq, d, m->dk16, (const float*)m->qmul[b], m->qbf[b]);
-        const int sub_stride = kp > 1 ? kPasses * kQT : 0;
-        {
-            // the row sample: the smallest (K'-th of 64 subsets' smallest) sampled proxy + one window is the sample flow's bound and the
-            // adaptive pass's start value (k_gemm_seed_T)
-            FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)m->smin[b], (int)0xFF800000u, sub_stride ? (size_t)kRtSubsets * sub_stride : (size_t)pairs * 2 * kQT, st));
-            const int64_t sample_blocks = ((int64_t)m->rt_sample_rows + 31) / 32;
-            const int rb_stride = (int)std::max<int64_t>(1, ((n + 31) / 32) / sample_blocks);
-            for (int p0 = 0; p0 < pairs;) {
-                const int P = launch_pairs_(pairs - p0, kShareMax);
-                const size_t qo = (size_t)p0;
-                hipLaunchKernelGGL(pick_x(2, streamed, odd), dim3(grid), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n,
-                                   (int64_t)0, sample_blocks * 32, m->dk16, m->tau[b], m->lists[b], m->counts[b], (float*)nullptr, 0, P, P <= 1 ? 1 : 0, rb_stride,
-                                   m->smin[b] + qo * 2 * kQT, sub_stride);
-                p0 += P;
-            }
-            if (adaptive)
-                hipLaunchKernelGGL(k_gemm_seed_T, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, (const unsigned int*)m->smin[b], sub_stride, kp, m->aT[b], (const float*)m->qnorm[b],
-                                   (const float*)m->awin[b], nq);
-            else if (sub_stride)
-                hipLaunchKernelGGL(k_gemm_tau_kmin, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, m->smin[b], sub_stride, kp, m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, e_rel);
-            else
-                hipLaunchKernelGGL(k_gemm_tau_min, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, m->smin[b], m->tau[b], pairs * 2 * kQT, nq, m->qnorm[b], m->gmax, e_rel);
-        }
+        hipLaunchKernelGGL(k_gemm_qprep_f16_f64, dim3(pairs * 2 * kQT), dim3(64), 0, st, dq, nq, d, m->gallery_exp, s.qnorm, s.qmul, s.qinv, s.counts, s.awin,
+                           adaptive ? s.aT : (unsigned int*)nullptr, (const float*)m->gmax, e_rel, kp > 1 ? kp : 0);
+        hipLaunchKernelGGL(k_gemm_pack_queries_f16x_f64, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, st, dq, nq, d, m->dk16, (const float*)s.qmul, s.qbf);
+        // the row sample: the smallest (K'-th of 64 subsets' smallest) sampled proxy + one window is the sample flow's bound and the
+        // adaptive pass's start value (k_gemm_seed_T)
+        if (const int rcs = gemm_sample_pass_(m, s, st, streamed, odd, pairs, kp)) return rcs;
+        if (adaptive)
+            hipLaunchKernelGGL(k_gemm_seed_T, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, (const unsigned int*)s.smin, gemm_sample_stride_(kp), kp, s.aT,
+                               (const float*)s.qnorm, (const float*)s.awin, nq);
+        else gemm_sample_tau_(m, s, st, pairs, nq, kp, e_rel);
         for (int p0 = 0; p0 < pairs;) {
             const int P = launch_pairs_(pairs - p0, share_cap);
-            const size_t qo = (size_t)p0;
             const int nt_flag = P <= 1 ? 1 : 0;
             if (ev_pair && first) FIR_HIP(hipEventRecord(ev_pair[0], st));
             if (adaptive)
-                hipLaunchKernelGGL(pick_x(kp > 1 ? 4 : 3, streamed, odd), dim3(grid, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT,
-                                   n, (int64_t)0, n, m->dk16, m->awin[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, m->qnorm[b] + qo * 2 * kQT, 0,
-                                   P, nt_flag, 1, m->aT[b] + qo * 2 * kQT * (kp > 1 ? 8 : 1), kp > 1 ? kp : 0);
+                gemm_launch_x_(pick_x({kp > 1 ? 4 : 3, streamed, odd}), dim3(grid, 1), kGemmBlock, st, op, s, p0, P, n, n, 1, kBelowAwin,
+                               {true, 0, nt_flag, s.aT, kp > 1 ? 8 : 1, kp > 1 ? kp : 0});
             else
-                hipLaunchKernelGGL(pick_x(1, streamed, odd), dim3(grid, 1), dim3(kGemmBlock), kHalfLds, st, m->gh, m->gnorm, m->qbf[b] + qo * 4 * m->dk16 * 64, m->qinv[b] + qo * 2 * kQT, n,
-                                   (int64_t)0, n, m->dk16, m->tau[b] + qo * 2 * kQT, m->lists[b] + qo * 2 * kQT * kListCap, m->counts[b] + qo * 2 * kQT, (float*)nullptr, 0, P, nt_flag, 1,
-                                   (unsigned int*)nullptr, 0);
+                gemm_launch_x_(pick_x({1, streamed, odd}), dim3(grid, 1), kGemmBlock, st, op, s, p0, P, n, n, 1, kBelowTau, {false, 0, nt_flag, nullptr, 0, 0});
             if (ev_pair && first) {
                 FIR_HIP(hipEventRecord(ev_pair[1], st));
                 if (flops_per_launch) *flops_per_launch = 2.0 * (double)n * d * 128.0 * P;
-                if (kernel_name) *kernel_name = find_x(adaptive ? (kp > 1 ? 4 : 3) : 1, streamed, odd).name;
+                if (kernel_name) *kernel_name = find_x({adaptive ? (kp > 1 ? 4 : 3) : 1, streamed, odd}).name;
                 first = false;
             }
             p0 += P;
         }
         if (adaptive)
-            hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, m->aT[b], m->qnorm[b], m->tau[b], pairs * 2 * kQT, nq, kp > 1 ? kp : 0);
-        hipLaunchKernelGGL(k_gemm_rerank_f64, dim3(nq), dim3(64), rr_lds, st, m->lists[b], m->counts[b], m->tau[b], m->gal2, dq, m->qnorm[b], m->gmax, n, d, m->dp2, e_rel, kp,
+            hipLaunchKernelGGL(k_gemm_adapt_final, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, st, s.aT, s.qnorm, s.tau, pairs * 2 * kQT, nq, kp > 1 ? kp : 0);
+        hipLaunchKernelGGL(k_gemm_rerank_f64, dim3(nq), dim3(64), rr_lds, st, s.lists, s.counts, s.tau, m->gal2, dq, s.qnorm, m->gmax, n, d, m->dp2, e_rel, kp,
                            m->rerank_group, d_rows + (size_t)q0 * kp, d_dist + (size_t)q0 * kp, d_ok + q0);
         m->passes += np;
         m->last_kind = 1; m->last_b = b; m->last_nq = nq; m->last_sc_rounds = 0; m->last_i8 = false;      // (fir_gemm_nominations_, which = 0)
@@ -441,9 +399,9 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
             FIR_HIP(hipStreamSynchronize(st));
             std::vector<int> hc((size_t)nq), hok((size_t)nq);
             std::vector<float> ht((size_t)nq);
-            FIR_HIP(hipMemcpy(hc.data(), m->counts[b], (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
+            FIR_HIP(hipMemcpy(hc.data(), s.counts, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
             FIR_HIP(hipMemcpy(hok.data(), d_ok + q0, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-            FIR_HIP(hipMemcpy(ht.data(), m->tau[b], (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+            FIR_HIP(hipMemcpy(ht.data(), s.tau, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
             long long sum = 0; int mx = 0, over = 0, bad = 0;
             for (int i = 0; i < nq; ++i) { sum += hc[i]; mx = std::max(mx, hc[i]); over += hc[i] > kListCap; bad += hok[i] ? 0 : 1; }
             std::fprintf(stderr, "fir_gemm f64: %d queries (adaptive %d, K' %d): appended mean %.1f max %d, %d lists over %d, %d uncertified; tau[0..3] %g %g %g %g\n", nq, (int)adaptive, kp,

@@ -19,7 +19,7 @@ too LARGE for one (row, position in its block, block's place in a wave's walk) s
 Every entry of kXTable is reached by a call of the shipped library: <3, *> and <4, *> by default; <2, *> and <1, *> with the
 sample flow (FIR_GEMM_ADAPTIVE=0, a knob the shipped library honours; the K-nearest and distinct-class calls take it by default at
 some shapes). The sample pass <2, *> writes no list: it is checked through the bound it produces. <1, *> also runs as the
-second-chance round, whose lists live elsewhere (sc_lists): fir_gemm_nominations_ reads them with which = 1
+second-chance round, whose lists live elsewhere (the state's `sc` set): fir_gemm_nominations_ reads them with which = 1
 (test_second_pass_lists). MODE 0 is not instantiated. The distinct-classes flow rewrites its list entries in the re-rank and is not
 covered here."""
 import ctypes as C
@@ -214,7 +214,7 @@ def test_no_call_yet_is_a_state_error(fir):
 
 
 def test_second_pass_lists(fir, monkeypatch):
-    """MODE 1 as the second-chance round: its lists (sc_lists, which = 1) are held to the same assertions, against the bound
+    """MODE 1 as the second-chance round: its lists (the `sc` set, which = 1) are held to the same assertions, against the bound
     k_gemm_sc_prep handed it; the detour is explained -- every query that took it had overflowed its first list."""
     rows, q = cases.second_pass_data()
     n, qb = rows.shape[0], q.shape[0]
