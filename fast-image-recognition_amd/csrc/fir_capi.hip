@@ -35,6 +35,20 @@ constexpr int kKMax = 8;     // per-lane candidate list length of the top-K scan
 
 }  // namespace
 
+// A FirBuf that reads as the T* it holds (fir_gemm.hip's GemmBuf). need(): the handle's workspaces -- `elems` elements are
+// max(elems, 4096) of them when the buffer has to be (re)allocated; one that is large enough is not touched.
+template <typename T>
+struct GalleryBuf : FirBuf {
+    operator T*() const { return (T*)p; }
+    int need(size_t elems, const char* what, const char* file, int line) {
+        if (elems * sizeof(T) <= cap) return FIR_OK;
+        return fir_reserve_(*this, std::max(elems, (size_t)4096) * sizeof(T), what, file, line);
+    }
+};
+#define FIR_NEED(buf, elems) (buf).need(elems, #buf, __FILE__, __LINE__)
+
+// Everything the handle holds releases itself: the buffers below are FirBufs, and the destructor takes care of what is not
+// memory. Nothing in this file frees by hand.
 struct fir_gallery {
     int device = 0;
     int cus = 0;
@@ -43,30 +57,37 @@ struct fir_gallery {
     int64_t tiles = 0;
     int metric = FIR_METRIC_L2;
     int64_t row_offset = 0;
-    float4* gal4 = nullptr;
-    int32_t* cls = nullptr;
+    GalleryBuf<float4> gal4;      // the tiled rows (fir_kernels.h layout) ...
+    GalleryBuf<int32_t> cls;      // ... and their labels (empty: created without): fir_gallery_memory_bytes' `tiled`
     hipStream_t stream = nullptr;
     // chi-square / KL: range[0] = a gallery value outside in_plain_range() was uploaded, range[1] = serial of the last query
     // transposition that met one (fir_common.h); the scans read both and pick their division sequence on the device
-    int32_t* range = nullptr;
+    GalleryBuf<int32_t> range;
     int q_serial = 0;
     bool gallery_plain = false;   // host copy of range[0] == 0, read once after the upload (chi-square nomination, topk_lists_dev)
-    uint64_t* one_keys = nullptr;   // one-query calls on small galleries (top1_one_query): device key + completion counter, armed once
-    int32_t* one_done = nullptr;    // and re-armed by the kernel itself
+    GalleryBuf<uint64_t> one_keys;  // one-query calls on small galleries (top1_one_query): device key + completion counter, armed once
+    int32_t* one_done = nullptr;    // (a word of one_keys) and re-armed by the kernel itself
     uint64_t one_ticket = 0;        // number of such calls so far: the word the host waits for
 
-    // workspaces (grown on demand, never inside a *_dev call once large enough)
-    float* qt = nullptr;      size_t qt_cap = 0;      // transposed query tiles
-    float* dq = nullptr;      size_t dq_cap = 0;      // staged host queries
-    uint64_t* dkeys = nullptr; size_t dkeys_cap = 0;  // keys for the host-pointer API
-    uint64_t* part = nullptr; size_t part_cap = 0;    // top-K per-wave partials
-    float* dout = nullptr;    size_t dout_cap = 0;    // range distances for the host-pointer API
-    int32_t* didx = nullptr;  size_t didx_cap = 0;
+    // workspaces (grown on demand with FIR_NEED, never inside a *_dev call once large enough) and the scratch slots of
+    // fir_gallery_scratch_ (classifier entry points in the other translation units): fir_gallery_memory_bytes' `scratch`
+    GalleryBuf<float> qt;         // transposed query tiles
+    GalleryBuf<float> dq;         // staged host queries
+    GalleryBuf<uint64_t> dkeys;   // keys for the host-pointer API
+    GalleryBuf<uint64_t> part;    // top-K per-wave partials
+    GalleryBuf<float> dout;       // range distances for the host-pointer API
+    GalleryBuf<int32_t> didx;
+    GalleryBuf<float> rowsum;     // chi-square nomination (kChi2Harm): per-row sums over [rs_start, rs_end) + their maximum (rowsum[n])
+    FirBuf scratch[24];
+    size_t scratch_bytes() const {
+        size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap;
+        for (const FirBuf& s : scratch) sum += s.cap;
+        return sum;
+    }
     // pinned, device-visible host staging of the small host-pointer calls: queries go in, packed keys come out, with
     // no copy engine in between (the kernels read / write it over PCIe) and one stream synchronisation per call
     void* pin = nullptr;
     uint64_t counters[4] = {};  // fir_gallery_next_counter_
-    void* scratch[24] = {};   size_t scratch_cap[24] = {};   // fir_gallery_scratch_ (classifier entry points in the other translation units)
 
     int qpp = 0;              // queries per gallery pass; 0 = automatic (effective_qpp)
     int waves_req = 0;        // 0 = automatic
@@ -80,7 +101,6 @@ struct fir_gallery {
     // "BF, 256" (ImageTesting.cpp:526-529); one slot would rebuild fragments and scratch on every call
     struct PrefixSlot { fir_gemm* m = nullptr; int end = 0; uint64_t used = 0; } gemm_prefix[2];
     uint64_t prefix_clock = 0;
-    float* rowsum = nullptr; size_t rowsum_cap = 0;    // chi-square nomination (kChi2Harm): per-row sums over [rs_start, rs_end) + their maximum (rowsum[n])
     int rs_start = -1, rs_end = -1, rs_metric = -1;   // (what g->rowsum holds: row sums for chi-square, row entropies for KL)
     int warm_left = 0;                  // fir_dispatch_info::warmup_calls_left of the most recent call
     int shadow_mode = FIR_SHADOW_ALL;   // which copies of the gallery the automatic dispatch may keep next to the tiled f32 rows (fir_gallery_set_shadow_copies)
@@ -93,9 +113,6 @@ struct fir_gallery {
     bool label_known = false;                // fir_gallery_label_range_: smallest and largest label, found once (the labels never change)
     int32_t label_lo = 0, label_hi = -1;
     int call_launches = 0;    // scan launches of the current call (note_dispatch)
-    bool quiet = false;       // scans on behalf of another path (the matrix-core path's uncertified queries): not recorded, not timed
-    int sample_groups = 0; int64_t sample_group_stride = 0;   // run_pass (generic k_scan, top-1): ScanArgs::groups / group_stride
-    int64_t tiles_limit = 0, tile_begin = 0;  // tiles_limit > 0: scans cover tiles [tile_begin, tile_begin + tiles_limit) only (row samples of the top-K threshold)
     int max_tiles_per_launch = 64;   // query tiles (gallery passes) folded into one launch of the hand-scheduled kernels
 
     struct Occ { const void* fn; size_t lds; int waves; };
@@ -110,20 +127,34 @@ struct fir_gallery {
     hipEvent_t last_done = nullptr;
     hipStream_t last_stream = nullptr;   // the stream last_done was recorded on (nullptr: no call yet)
     int call_depth = 0;                  // > 0 inside a call
+
+    void drop_gemm_states() {            // the whole-row state and both prefix slots (they cache the offset, the shadow mode, ...)
+        if (gemm) { fir_gemm_destroy(gemm); gemm = nullptr; }
+        for (auto& ps : gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
+    }
+    // The matrix-core states first (they queue on this stream and hang off these buffers), the stream last; then the members.
+    ~fir_gallery() {
+        drop_gemm_states();
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        if (last_done) (void)hipEventDestroy(last_done);
+        if (pin) (void)hipHostFree(pin);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace {
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return FIR_OK;
-    if (p) FIR_HIP(hipFree(p));
-    p = nullptr; cap = 0;
-    size_t want = std::max(need, (size_t)4096);
-    FIR_HIP(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    return FIR_OK;
-}
+// What one scan covers, and on whose behalf: tiles [tile_begin, tile_begin + tiles) of the gallery (tiles == 0: all of it), the
+// groups a row sample's tiles form (ScanArgs::groups / group_stride, chi-square / KL top-1 scans only), and quiet: a scan on
+// behalf of another path -- the matrix-core path's uncertified queries, a threshold's row samples -- is not recorded in g->last,
+// gets no event pair and takes no candidate-list path of its own.
+struct ScanScope {
+    int64_t tile_begin = 0, tiles = 0;
+    int groups = 0;
+    int64_t group_stride = 0;
+    bool quiet = false;
+};
+const ScanScope kOnBehalf{0, 0, 0, 0, true};      // the whole gallery, quietly
 
 typedef void (*scan_fn)(const ScanArgs);
 
@@ -238,11 +269,11 @@ int effective_qpp(const fir_gallery* g) {
 // Queries per pass of one top-1 call of qb queries. A wave owns whole 64-row tiles, so a gallery of few tiles gives
 // few waves per pass: the automatic choice halves the query tile until the launch (tiles x passes) has a wave for
 // every SIMD (profiles/r01_small_gallery_sweep.txt).
-int top1_qpp(const fir_gallery* g, int qb, int cap) {
+int top1_qpp(const fir_gallery* g, const ScanScope& scope, int qb, int cap) {
     if (g->qpp > 0) return cap;
     const int64_t simds = (int64_t)g->cus * 4;
     int q = cap;
-    const int64_t tiles = g->tiles_limit > 0 ? std::min<int64_t>(g->tiles_limit, g->tiles) : g->tiles;
+    const int64_t tiles = scope.tiles > 0 ? std::min<int64_t>(scope.tiles, g->tiles) : g->tiles;
     while (q > 1 && tiles * ((qb + q - 1) / q) < simds) q /= 2;
     return q;
 }
@@ -260,7 +291,7 @@ constexpr bool kAutoMfmaClasses = true;
 // classes (fir_search_top_classes): the same ranges and the same caller's threshold; the automatic rule is kAutoMfmaClasses
 bool wants_mfma(const fir_gallery* g, int32_t qb, int32_t start, int32_t end, bool classes = false) {
     // the whole row, or a prefix of whole 16-feature k-blocks (>= 64 features: below that the scan's prefix pass is cheap)
-    if (g->metric != FIR_METRIC_L2 || start != 0 || g->n <= 0 || g->tiles_limit > 0) return false;
+    if (g->metric != FIR_METRIC_L2 || start != 0 || g->n <= 0) return false;
     if (end != g->d && (end < 64 || end % 16 != 0)) return false;
     if (g->large_batch_min == 0 || g->gemm_failed) return false;
     if (g->large_batch_min > 0) return qb >= g->large_batch_min;
@@ -305,7 +336,7 @@ bool wants_mfma(const fir_gallery* g, int32_t qb, int32_t start, int32_t end, bo
 // 332 -> 253 us, 1M x 1280 790 -> 550 us, 300 000 x 512 116 -> 173 us (not taken). With 2 queries the two forms tie, from 3 on
 // the dot products (v_dot2 + one LDS read per query and fragment) cost more than the bytes saved: those stay with the f32 scan.
 bool wants_few(const fir_gallery* g, int32_t qb, int32_t start, int32_t end) {
-    if (g->metric != FIR_METRIC_L2 || start != 0 || g->n < kAutoMfmaRows || g->tiles_limit > 0 || g->qpp != 0 || g->few_hits < 0) return false;
+    if (g->metric != FIR_METRIC_L2 || start != 0 || g->n < kAutoMfmaRows || g->qpp != 0 || g->few_hits < 0) return false;
     if (end != g->d && (end < 64 || end % 16 != 0)) return false;
     if (g->large_batch_min >= 0 || g->gemm_failed) return false;
     return qb == 1 && (double)g->n * (double)end * 4.0 >= 1500.0e6;
@@ -367,14 +398,15 @@ int max_waves_for(fir_gallery* g, scan_fn fn, size_t lds_bytes) {
     return waves;
 }
 
-// The ScanArgs fields every scan shares: the tiled gallery -- tiles [tile_begin, tile_begin + tiles_limit) of it while a row sample
-// is being taken (tiles_limit > 0) --, the feature range and the grid's wave count. Every gallery is read with the non-temporal
-// hint: plain loads gained nothing even for an 18 MB gallery that fits the L2s (one-query calls unchanged, multi-pass calls
-// slower -- profiles/r01_small_gallery_sweep.txt).
-ScanArgs scan_args(const fir_gallery* g, int32_t start, int32_t end, int waves) {
+// The ScanArgs fields every scan shares: the tiled gallery -- the scope's window of it --, the scope's sample groups, the feature
+// range and the grid's wave count. Every gallery is read with the non-temporal hint: plain loads gained nothing even for an 18 MB
+// gallery that fits the L2s (one-query calls unchanged, multi-pass calls slower -- profiles/r01_small_gallery_sweep.txt).
+ScanArgs scan_args(const fir_gallery* g, const ScanScope& scope, int32_t start, int32_t end, int waves) {
     ScanArgs a{};
-    const int64_t tile0 = g->tiles_limit > 0 ? std::min<int64_t>(g->tile_begin, g->tiles) : 0;
-    const int64_t tiles = g->tiles_limit > 0 ? std::min<int64_t>(g->tiles_limit, g->tiles - tile0) : g->tiles;
+    const int64_t tile0 = scope.tiles > 0 ? std::min<int64_t>(scope.tile_begin, g->tiles) : 0;
+    const int64_t tiles = scope.tiles > 0 ? std::min<int64_t>(scope.tiles, g->tiles - tile0) : g->tiles;
+    a.groups = scope.groups;
+    a.group_stride = scope.group_stride;
     a.gal4 = g->gal4 + (size_t)tile0 * g->dp4 * 64;
     a.row_offset = g->row_offset + tile0 * kTileRows;
     a.n = std::min<int64_t>(g->n - tile0 * kTileRows, tiles * kTileRows);
@@ -396,7 +428,7 @@ bool few_tiles(const fir_gallery* g) { return g->tiles <= (int64_t)g->cus * 4; }
 struct ClassPass { const float* tau; int32_t num_classes; int32_t nq; bool tiles_ready; };
 
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
-int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
+int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
              int init_keys = 0, const ClassPass* cp = nullptr) {
     // ny > 1 (top-1 kernels and the class-minimum scan only): ny consecutive query tiles of qb_tile queries in ONE launch
@@ -418,13 +450,12 @@ int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, in
     int max_waves = max_waves_for(g, sk.fn, sk.lds_bytes);
     if (sk.fn_plain) max_waves = std::min(max_waves, max_waves_for(g, sk.fn_plain, sk.lds_bytes));
     int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
-    const int groups = epi == kEpiTop1 && g->sample_groups > 1 && g->metric != kL2 ? g->sample_groups : 0;
+    const int groups = epi == kEpiTop1 && scope.groups > 1 && g->metric != kL2 ? scope.groups : 0;
     if (groups) waves = std::max(4 * groups, waves / (4 * groups) * (4 * groups));      // a wave's tiles all belong to one group
     g->last_waves = waves;
     if (waves_used) *waves_used = waves;
-    ScanArgs a = scan_args(g, start, end, waves);
+    ScanArgs a = scan_args(g, scope, start, end, waves);
     a.groups = groups;
-    a.group_stride = g->sample_group_stride;
     a.qt = qt;
     a.keys = keys;
     a.out = out;
@@ -442,11 +473,11 @@ int run_pass(fir_gallery* g, hipStream_t st, int epi, const float* d_queries, in
     // algorithmic bytes of one launch: per pass the gallery range once (the class-minimum scan: and a label per row), the query tile, the keys
     const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
     int rc;
-    if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
+    if (!scope.quiet && (rc = fir_gallery_profile_begin_(g, st))) return rc;
     hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
     if (sk.fn_plain) hipLaunchKernelGGL(sk.fn_plain, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
-    if ((rc = fir_gallery_profile_end_(g, st, bytes_alg))) return rc;
-    if (!g->quiet) note_dispatch(g, (const void*)sk.fn, sk.name, g->call_launches++, waves / 4, ny, kBlock, sk.lds_bytes, qb_tile, bytes_alg, 0.0, 0);
+    if (!scope.quiet && (rc = fir_gallery_profile_end_(g, st, bytes_alg))) return rc;
+    if (!scope.quiet) note_dispatch(g, (const void*)sk.fn, sk.name, g->call_launches++, waves / 4, ny, kBlock, sk.lds_bytes, qb_tile, bytes_alg, 0.0, 0);
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
@@ -455,31 +486,31 @@ int topk_lists_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t s
                    hipStream_t st);
 
 int top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, uint64_t* d_keys,
-             hipStream_t st) {
+             hipStream_t st, const ScanScope& scope = {}) {
     // chi-square batches over a large plain-range gallery: nomination scan + exact re-rank (topk_lists_dev with K = 1), the same
     // keys at about twice the rate; it synchronises `st` once (it has to know that no list overflowed) and leaves the call to the
     // exact scan below when it cannot answer (operands outside the plain range, list overflow)
-    if ((g->metric == kChi2 || g->metric == kKL) && g->gallery_plain && g->tiles_limit == 0 && !g->quiet && qb >= 8 && g->n >= 65536 &&
+    if ((g->metric == kChi2 || g->metric == kKL) && g->gallery_plain && scope.tiles == 0 && !scope.quiet && qb >= 8 && g->n >= 65536 &&
         g->qpp == 0) {
         int rc0 = FIR_OK;
         for (int q0 = 0; q0 < qb && rc0 == FIR_OK; q0 += 1024)       // candidate lists are 32 KiB per query: bounded scratch for any qb
             rc0 = topk_lists_dev(g, d_queries + (size_t)q0 * g->d, std::min(1024, qb - q0), start, end, 1, d_keys + q0, st);
         if (rc0 != FIR_ERR_STATE) return rc0;
     }
-    int rc = grow(g->qt, g->qt_cap, (size_t)qb * g->dp4 * 4 + 64);   // +64: the fast kernel prefetches one unit past the tile
+    int rc = FIR_NEED(g->qt, (size_t)qb * g->dp4 * 4 + 64);   // +64: the fast kernel prefetches one unit past the tile
     if (rc) return rc;
     // 16 queries per pass exist only in the hand-scheduled kernel (whole-chunk L2 ranges)
     int cap = g->metric == kL2 && whole_chunks(start, end) ? effective_qpp(g) : std::min(effective_qpp(g), 8);
     // 16 queries per pass only while their tile fits the default 64 KiB of LDS (d <= 1020): a larger tile leaves one
     // workgroup per CU, and the 8-query tile then does better
     if (cap > 8 && (size_t)(g->dp4 + 1) * 16 * 16 > 64 * 1024) cap = 8;
-    cap = top1_qpp(g, qb, cap);
+    cap = top1_qpp(g, scope, qb, cap);
     int q0 = 0;
     while (q0 < qb) {
         const int t = largest_pow2_le(qb - q0, cap);
         // all the whole tiles of t queries go into one launch (blockIdx.y)
         const int ny = std::min((qb - q0) / t, g->max_tiles_per_launch);
-        rc = run_pass(g, st, kEpiTop1, d_queries, q0, t, start, end, d_keys + q0, nullptr, 0, 0, nullptr, ny, /*init_keys=*/t * ny);
+        rc = run_pass(g, st, scope, kEpiTop1, d_queries, q0, t, start, end, d_keys + q0, nullptr, 0, 0, nullptr, ny, /*init_keys=*/t * ny);
         if (rc) return rc;
         q0 += t * ny;
     }
@@ -498,7 +529,7 @@ int topk_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     }
     // batches over a large gallery: threshold from a row sample, append scan at the speed of the top-1 scan, K smallest
     // of each candidate list (exact distances throughout); anything it cannot certify falls back to the scan below
-    if (allow_lists && g->tiles_limit == 0 && qb >= 8 && g->n >= 65536) {
+    if (allow_lists && qb >= 8 && g->n >= 65536) {
         constexpr int kListBatch = 1024;           // candidate lists are 32 KiB per query: bounded scratch for any qb
         if (qb > kListBatch) {
             for (int q0 = 0; q0 < qb; q0 += kListBatch) {
@@ -510,16 +541,16 @@ int topk_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
         const int rc2 = topk_lists_dev(g, d_queries, qb, start, end, k, d_keys, st);
         if (rc2 != FIR_ERR_STATE) return rc2;      // FIR_ERR_STATE: not certified -> the register-list scan answers
     }
-    int rc = grow(g->qt, g->qt_cap, (size_t)qb * g->dp4 * 4);
+    int rc = FIR_NEED(g->qt, (size_t)qb * g->dp4 * 4);
     if (rc) return rc;
     const int qcap = std::min(effective_qpp(g), 4);   // 2*kKMax registers per query per lane
-    rc = grow(g->part, g->part_cap, (size_t)g->max_waves * qcap * k);
+    rc = FIR_NEED(g->part, (size_t)g->max_waves * qcap * k);
     if (rc) return rc;
     int q0 = 0;
     while (q0 < qb) {
         const int t = largest_pow2_le(qb - q0, qcap);
         int waves = 0;
-        rc = run_pass(g, st, kEpiTopK, d_queries, q0, t, start, end, g->part, nullptr, 0, k, &waves);
+        rc = run_pass(g, st, {}, kEpiTopK, d_queries, q0, t, start, end, g->part, nullptr, 0, k, &waves);
         if (rc) return rc;
         hipLaunchKernelGGL(k_topk_merge, dim3(t), dim3(kBlock), 0, st, g->part, waves, t, q0, t, k, d_keys);
         q0 += t;
@@ -614,7 +645,7 @@ int list_workspace(ListCall& c) {
     c.counts = (int32_t*)(c.tau + c.qpad);
     c.flag = c.counts + c.qpad;
     c.lists = (uint64_t*)p_lists;
-    if ((rc = grow(g->qt, g->qt_cap, (size_t)c.qpad * g->dp4 * 4 + 64))) return rc;      // before anything is queued on it
+    if ((rc = FIR_NEED(g->qt, (size_t)c.qpad * g->dp4 * 4 + 64))) return rc;      // before anything is queued on it
     if ((c.harm || c.klent) && (rc = fir_gallery_scratch_(g, 15, (size_t)c.qpad * sizeof(float), &p_sq))) return rc;
     c.sq = (float*)p_sq;
     return FIR_OK;
@@ -625,7 +656,7 @@ int list_row_sums(ListCall& c) {
     fir_gallery* g = c.g;
     if (!(c.harm || c.klent) || (g->rs_start == c.start && g->rs_end == c.end && g->rs_metric == g->metric && g->rowsum)) return FIR_OK;
     int rc;
-    if ((rc = grow(g->rowsum, g->rowsum_cap, (size_t)g->n + 4))) return rc;
+    if ((rc = FIR_NEED(g->rowsum, (size_t)g->n + 4))) return rc;
     FIR_HIP(hipMemsetAsync(g->rowsum + g->n, 0, 4 * sizeof(float), c.st));
     hipLaunchKernelGGL(c.klent ? k_row_entropy : k_row_sums, dim3((unsigned)((g->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c.st, g->gal4, g->n, g->dp4,
                        c.start, c.end, g->rowsum, (unsigned int*)(g->rowsum + g->n));
@@ -651,17 +682,7 @@ int list_row_samples(ListCall& c) {
     const int64_t group_tiles = std::max<int64_t>(1, std::min<int64_t>(g->tiles / k, (want_rows / k + kTileRows - 1) / kTileRows));
     c.group_tiles = group_tiles;
     // (the row samples are not what a profile of this call is about: the events and the dispatch record belong to the append scan)
-    // they hand the handle back as they found it, on every way out (a failed launch must not leave later calls quiet)
-    const bool was_profiling = g->profiling, was_quiet = g->quiet;
-    g->profiling = false;
-    g->quiet = true;
-    auto restore = fir_on_exit([&] {
-        g->tiles_limit = 0;
-        g->tile_begin = 0;
-        g->sample_groups = 0;
-        g->profiling = was_profiling;
-        g->quiet = was_quiet;
-    });
+    ScanScope sample = kOnBehalf;
     FIR_HIP(hipMemsetAsync(c.flag, 0, 4, st));
     int rc = FIR_OK;
     if (c.approx_samples) {
@@ -675,13 +696,12 @@ int list_row_samples(ListCall& c) {
         c.tiles_ready = true;
         FIR_HIP(hipMemsetAsync(c.skeys, 0xFF, (size_t)c.qpad * k * 8, st));
         const ScanKernel sk = select_scan(kEpiTop1, 8, c.nomination_metric(), whole_chunks(c.start, c.end), g->dp4, false);
-        g->tile_begin = 0;
-        g->tiles_limit = std::min<int64_t>(group_tiles * k, g->tiles);
-        int waves = pick_waves(g->tiles_limit, max_waves_for(g, sk.fn, 0), g->cus * 4);
+        sample.tiles = std::min<int64_t>(group_tiles * k, g->tiles);
+        sample.groups = k > 1 ? k : 0;
+        sample.group_stride = c.sample_stride;
+        int waves = pick_waves(sample.tiles, max_waves_for(g, sk.fn, 0), g->cus * 4);
         if (k > 1) waves = std::max(4 * k, waves / (4 * k) * (4 * k));                  // a wave's tiles all belong to one group
-        ScanArgs a = scan_args(g, c.start, c.end, waves);
-        a.groups = k > 1 ? k : 0;
-        a.group_stride = c.sample_stride;
+        ScanArgs a = scan_args(g, sample, c.start, c.end, waves);
         a.nq = 8;
         a.qt_stride = (int64_t)kk * 8;
         a.nt = 0;                                     // the sample is a small part of the gallery: plain loads
@@ -700,16 +720,15 @@ int list_row_samples(ListCall& c) {
         // chi-square / KL: the K samples in ONE launch -- sample tile t belongs to group t mod K, a wave reports into its group's keys
         // (K launches of group_tiles tiles each leave most of the chip idle: a tile is one wave's serial work)
         FIR_HIP(hipMemsetAsync(c.skeys, 0xFF, (size_t)qb * k * 8, st));
-        g->tile_begin = 0;
-        g->tiles_limit = group_tiles * k;
-        g->sample_groups = k;
-        g->sample_group_stride = qb;
-        rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys, st);
+        sample.tiles = group_tiles * k;
+        sample.groups = k;
+        sample.group_stride = qb;
+        rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys, st, sample);
     } else {
+        sample.tiles = group_tiles;
         for (int i = 0; i < k && !rc; ++i) {
-            g->tile_begin = i * group_tiles;
-            g->tiles_limit = group_tiles;
-            rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys + (size_t)i * qb, st);
+            sample.tile_begin = i * group_tiles;
+            rc = top1_dev(g, c.d_queries, qb, c.start, c.end, c.skeys + (size_t)i * qb, st, sample);
         }
     }
     return rc;
@@ -742,7 +761,7 @@ int list_append_scan(const ListCall& c) {
         if (!c.tiles_ready)
             hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * 8 * ny + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                                c.d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, 8, qt, (uint64_t*)nullptr, 0, g->range, next_serial(g), c.transpose_form());
-        ScanArgs a = scan_args(g, c.start, c.end, waves);
+        ScanArgs a = scan_args(g, {}, c.start, c.end, waves);
         a.range = g->range;
         a.serial = g->q_serial;
         a.qt = qt;
@@ -756,13 +775,11 @@ int list_append_scan(const ListCall& c) {
         a.sq = c.sq ? c.sq + q0 : nullptr;
         // algorithmic bytes of the launch: one read of the compared features per nh tiles of eight queries, the query tiles, the appended keys aside
         const double launch_bytes = (double)(ny / nh) * ((double)g->n * (c.end - c.start) * 4.0) + (double)ny * ((double)(c.end - c.start) * 32.0 + 64.0);
-        if (!g->quiet && (rc = fir_gallery_profile_begin_(g, st))) return rc;
+        if ((rc = fir_gallery_profile_begin_(g, st))) return rc;             // (never on behalf of another path: top1_dev)
         hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny / nh), dim3(kBlock), sk.lds_bytes, st, a);
         if (sk.fn_plain) hipLaunchKernelGGL(sk.fn_plain, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
-        if (!g->quiet) {
-            if ((rc = fir_gallery_profile_end_(g, st, launch_bytes))) return rc;
-            note_dispatch(g, (const void*)sk.fn, sk.name, launches_noted++, waves / 4, ny / nh, kBlock, sk.lds_bytes, 8 * nh, launch_bytes, 0.0, 0);
-        }
+        if ((rc = fir_gallery_profile_end_(g, st, launch_bytes))) return rc;
+        note_dispatch(g, (const void*)sk.fn, sk.name, launches_noted++, waves / 4, ny / nh, kBlock, sk.lds_bytes, 8 * nh, launch_bytes, 0.0, 0);
     }
     return FIR_OK;
 }
@@ -824,8 +841,10 @@ constexpr int32_t kClassMax = 1 << 24;      // 1 GiB of table per tile of 8 quer
 constexpr int64_t kClassSampleFromTiles = 128;
 
 // bound_tiles > 0 (fir_class_scan_dev_): only the scan over the leading bound_tiles tiles runs, and d_bound[q] gets its bound.
+// Of `scope` only quiet is the caller's: the windows of the sample and of the remainder are made here.
 int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k,
-                    uint64_t* d_keys, int32_t* d_classes, hipStream_t st, int64_t bound_tiles = 0, float* d_bound = nullptr) {
+                    uint64_t* d_keys, int32_t* d_classes, hipStream_t st, const ScanScope& scope = {}, int64_t bound_tiles = 0,
+                    float* d_bound = nullptr) {
     if (g->n == 0) {                                             // no row: every slot unused (kKeyNone, class -1)
         if (d_keys) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
         if (d_classes) FIR_HIP(hipMemsetAsync(d_classes, 0xFF, (size_t)qb * k * sizeof(int32_t), st));
@@ -838,31 +857,29 @@ int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t 
     int rc;
     if ((rc = fir_gallery_scratch_(g, 17, tile_bytes * per_launch, &p_table))) return rc;
     if ((rc = fir_gallery_scratch_(g, 18, (size_t)per_launch * 8 * sizeof(float), &p_tau))) return rc;
-    if ((rc = grow(g->qt, g->qt_cap, (size_t)tiles_q * 8 * g->dp4 * 4 + 64))) return rc;
+    if ((rc = FIR_NEED(g->qt, (size_t)tiles_q * 8 * g->dp4 * 4 + 64))) return rc;
     uint64_t* table = (uint64_t*)p_table;
     float* tau = (float*)p_tau;
     const int64_t sample_tiles = bound_tiles > 0 ? std::min(bound_tiles, g->tiles) : g->tiles >= kClassSampleFromTiles ? g->tiles / 8 : 0;
-    auto restore = fir_on_exit([&] { g->tiles_limit = 0; g->tile_begin = 0; });
+    ScanScope sample = scope, rest = scope;      // (no sample: the remainder is the whole gallery)
+    sample.tile_begin = 0;
+    sample.tiles = sample_tiles;
+    rest.tile_begin = sample_tiles;
+    rest.tiles = sample_tiles > 0 ? g->tiles - sample_tiles : 0;
     for (int q0 = 0; q0 < qb; q0 += 8 * per_launch) {
         const int nq = std::min(qb - q0, 8 * per_launch), ny = (nq + 7) / 8;
         // a fresh table for every launch group: nothing of an earlier group, call, num_classes or k is left to see
         FIR_HIP(hipMemsetAsync(table, 0xFF, tile_bytes * ny, st));
         ClassPass cp{nullptr, num_classes, nq, false};
         if (sample_tiles > 0) {
-            g->tile_begin = 0;
-            g->tiles_limit = sample_tiles;
-            if ((rc = run_pass(g, st, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
+            if ((rc = run_pass(g, st, sample, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
             hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, (uint64_t*)nullptr, (int32_t*)nullptr,
                                bound_tiles > 0 ? d_bound + q0 : tau);
             if (bound_tiles > 0) { FIR_HIP(hipGetLastError()); continue; }
             cp.tau = tau;
             cp.tiles_ready = true;
-            g->tile_begin = sample_tiles;
-            g->tiles_limit = g->tiles - sample_tiles;
         }
-        if ((rc = run_pass(g, st, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
-        g->tiles_limit = 0;
-        g->tile_begin = 0;
+        if ((rc = run_pass(g, st, rest, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
         hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, d_keys ? d_keys + (size_t)q0 * k : nullptr,
                            d_classes ? d_classes + (size_t)q0 * k : nullptr, (float*)nullptr);
         FIR_HIP(hipGetLastError());
@@ -871,12 +888,12 @@ int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t 
 }
 
 int range_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, float* d_out, hipStream_t st) {
-    int rc = grow(g->qt, g->qt_cap, (size_t)qb * g->dp4 * 4);
+    int rc = FIR_NEED(g->qt, (size_t)qb * g->dp4 * 4);
     if (rc) return rc;
     int q0 = 0;
     while (q0 < qb) {
         const int t = largest_pow2_le(qb - q0, std::min(effective_qpp(g), 8));
-        rc = run_pass(g, st, kEpiStore, d_queries, q0, t, start, end, nullptr, d_out + (size_t)q0 * g->n, g->n, 0);
+        rc = run_pass(g, st, {}, kEpiStore, d_queries, q0, t, start, end, nullptr, d_out + (size_t)q0 * g->n, g->n, 0);
         if (rc) return rc;
         q0 += t;
     }
@@ -894,7 +911,7 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
         }
         return FIR_OK;
     }
-    int rc = grow(g->qt, g->qt_cap, (size_t)8 * g->dp4 * 4);
+    int rc = FIR_NEED(g->qt, (size_t)8 * g->dp4 * 4);
     if (rc) return rc;
     const int kk = g->dp4 * 4;
     for (int q0 = 0; q0 < qb; q0 += 8) {
@@ -905,7 +922,7 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
         hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * qbt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, qbt, g->qt, (uint64_t*)nullptr, 0);
         const int max_waves = max_waves_for(g, fn, 0);
-        ScanArgs a = scan_args(g, start, end, pick_waves(g->tiles, max_waves, g->cus * 4));
+        ScanArgs a = scan_args(g, {}, start, end, pick_waves(g->tiles, max_waves, g->cus * 4));
         a.qt = g->qt;
         a.step = step;
         a.step2 = step2;
@@ -960,32 +977,18 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
     g->tiles = (n + kTileRows - 1) / kTileRows;
     g->metric = metric;
     g->max_waves = g->cus * 8 * (kBlock / 64);
-    hipError_t e;
-    e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete g; return fir_fail_(FIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+    const auto fail = [g](int code) { delete g; return code; };      // (the destructor releases whatever exists by then)
+    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(fir_fail_(FIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     e = hipEventCreateWithFlags(&g->last_done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        (void)hipStreamDestroy(g->stream);
-        delete g;
-        return fir_fail_(FIR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(fir_fail_(FIR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)));
     const size_t f4 = (size_t)std::max<int64_t>(g->tiles, 1) * g->dp4 * 64;
-    e = hipMalloc((void**)&g->gal4, f4 * sizeof(float4));
-    if (e != hipSuccess) {
-        (void)hipEventDestroy(g->last_done);
-        (void)hipStreamDestroy(g->stream);
-        delete g;
-        return fir_fail_(FIR_ERR_NOMEM, "hipMalloc of %zu gallery bytes: %s", f4 * sizeof(float4), hipGetErrorString(e));
-    }
-    e = hipMalloc((void**)&g->range, 2 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(g->range, 0, 2 * sizeof(int32_t));
-    if (e != hipSuccess) {
-        (void)hipFree(g->gal4); (void)hipFree(g->range);
-        (void)hipEventDestroy(g->last_done);
-        (void)hipStreamDestroy(g->stream);
-        delete g;
-        return fir_fail_(FIR_ERR_NOMEM, "hipMalloc of the range flags: %s", hipGetErrorString(e));
-    }
+    e = g->gal4.reserve(f4 * sizeof(float4));
+    if (e != hipSuccess) return fail(fir_fail_(FIR_ERR_NOMEM, "hipMalloc of %zu gallery bytes: %s", f4 * sizeof(float4), hipGetErrorString(e)));
+    e = g->range.reserve(2 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(g->range, 0, 2 * sizeof(int32_t), g->stream);      // (not hipMemset: see fir_gallery_scratch_)
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);                                  // the retile may run on a caller's stream
+    if (e != hipSuccess) return fail(fir_fail_(FIR_ERR_NOMEM, "hipMalloc of the range flags: %s", hipGetErrorString(e)));
     *out = g;
     return FIR_OK;
 }
@@ -1001,6 +1004,38 @@ int retile_slab(fir_gallery* g, const float* d_rows, int64_t slab_rows, int64_t 
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
+
+// ---- what every entry point that queues work on a handle starts with ------------------------------------------------------------
+// The (queries, qb, range) arguments of a search: 0 = go on (end == 0 has become d), kNothingToDo = a call that succeeds without
+// doing anything (qb == 0; or what `extra` says), < 0 = the error. pointers_ok: the entry point's other required pointers.
+// extra(): its own checks, made where they have always been made -- after qb < 0, before qb == 0 and the range -- so that the
+// first error a bad call reports stays the same; it returns as this function does.
+constexpr int kNothingToDo = 1;
+template <typename Extra>
+int check_search(const fir_gallery* g, const void* queries, int32_t qb, int32_t& start, int32_t& end, bool pointers_ok, Extra extra) {
+    if (!g || !pointers_ok || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (const int rc = extra()) return rc;
+    if (qb == 0) return kNothingToDo;
+    return check_range(g, start, end);
+}
+int check_search(const fir_gallery* g, const void* queries, int32_t qb, int32_t& start, int32_t& end, bool pointers_ok = true) {
+    return check_search(g, queries, qb, start, end, pointers_ok, [] { return FIR_OK; });
+}
+int check_k(int32_t k) { return k < 1 || k > kKMax ? fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax) : FIR_OK; }
+
+// One call on a handle: its device made current, the stream it queues on (the caller's, else the handle's own: a host-pointer
+// call is a call on the handle's own stream) and its place in the handle's call order (FirCallOrder, which cannot be copied:
+// this object lives in the entry point's scope). rc != 0: return it, nothing was queued.
+struct GalleryCall {
+    int rc;
+    hipStream_t st;
+    FirCallOrder order;
+    static int make_current(const fir_gallery* g) { FIR_HIP(hipSetDevice(g->device)); return FIR_OK; }
+    explicit GalleryCall(fir_gallery* g, void* stream = nullptr)
+        : rc(make_current(g)), st(stream ? (hipStream_t)stream : g->stream), order(rc ? nullptr : g, st) { if (!rc) rc = order.rc; }
+    void done() { order.done(); }       // all of the call's work has been seen to finish on the device
+};
 
 }  // namespace
 
@@ -1072,16 +1107,17 @@ int fir_runtime_init_(int device) {
 }
 int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out) {
     if (!g || !out || slot < 0 || slot >= 24) return fir_fail_(FIR_ERR_ARG, "bad scratch request");
-    if (bytes > g->scratch_cap[slot]) {
-        if (g->scratch[slot]) FIR_HIP(hipFree(g->scratch[slot]));
-        g->scratch[slot] = nullptr;
-        g->scratch_cap[slot] = 0;
-        const size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-        FIR_HIP(hipMalloc(&g->scratch[slot], want));
-        FIR_HIP(hipMemset(g->scratch[slot], 0, want));        // a fresh slot reads as zeros (fir_rows_distances' arrival counter)
-        g->scratch_cap[slot] = want;
+    FirBuf& s = g->scratch[slot];
+    if (bytes > s.cap) {                                      // a quarter of headroom, a page at least
+        const int rc = FIR_RESERVE(s, std::max<size_t>(bytes + bytes / 4, 4096));
+        if (rc) return rc;
+        // a fresh slot reads as zeros (fir_rows_distances' arrival counter, the fused TWD kernels' state) -- to whoever is handed
+        // it, on whatever stream: hipMemset may return before the fill has run, and it runs on the null stream, which no
+        // non-blocking stream waits for
+        FIR_HIP(hipMemsetAsync(s.p, 0, s.cap, g->stream));
+        FIR_HIP(hipStreamSynchronize(g->stream));
     }
-    *out = g->scratch[slot];
+    *out = s.p;
     return FIR_OK;
 }
 int fir_subrange_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t step, float* d_out,
@@ -1091,21 +1127,18 @@ int fir_subrange_distances_dev_(fir_gallery* g, const float* d_queries, int32_t 
     if (step <= 0 || start < 0 || end > g->d || start >= end || (end - start) % step != 0)
         return fir_fail_(FIR_ERR_ARG, "sub-ranges of %d features do not tile [%d,%d) inside [0,%d)", step, start, end, g->d);
     if (g->n == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    return subranges_dev(g, d_queries, qb, start, end, step, d_out, st);
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return subranges_dev(g, d_queries, qb, start, end, step, d_out, call.st);
 }
 int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t split, int32_t end, float* d_out, void* stream) {
     if (!g || !d_queries || !d_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "qb=%d must be positive", qb);
     if (split <= 0 || split >= end || end > g->d) return fir_fail_(FIR_ERR_ARG, "split %d / end %d outside (0,%d]", split, end, g->d);
     if (g->n == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
     if (split % (4 * kUSub) == 0 && (end - split) % (4 * kUSub) == 0) return subranges_dev(g, d_queries, qb, 0, end, split, d_out, st, end - split);
     const int rc = range_dev(g, d_queries, qb, 0, split, d_out, st);
     if (rc) return rc;
@@ -1162,9 +1195,9 @@ int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* c
     // upload in slabs of whole tiles (<= 256 MiB of rows each) and re-tile on the device
     int64_t slab = std::max<int64_t>(kTileRows, ((int64_t)(256u << 20) / ((int64_t)d * 4)) / kTileRows * kTileRows);
     slab = std::min<int64_t>(slab, std::max<int64_t>(g->tiles, 1) * kTileRows);
-    float* stage = nullptr;
-    hipError_t e = hipMalloc((void**)&stage, (size_t)slab * d * sizeof(float));
-    if (e != hipSuccess) { fir_gallery_destroy(g); return fir_fail_(FIR_ERR_NOMEM, "staging hipMalloc: %s", hipGetErrorString(e)); }
+    GalleryBuf<float> stage;                               // (gone when this function returns)
+    hipError_t e = stage.reserve((size_t)slab * d * sizeof(float));
+    if (e != hipSuccess) { delete g; return fir_fail_(FIR_ERR_NOMEM, "staging hipMalloc: %s", hipGetErrorString(e)); }
     for (int64_t r0 = 0; r0 < std::max<int64_t>(g->tiles, 1) * kTileRows && rc == FIR_OK; r0 += slab) {
         const int64_t have = std::max<int64_t>(0, std::min<int64_t>(slab, n - r0));
         if (have > 0) {
@@ -1175,13 +1208,13 @@ int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* c
         e = hipStreamSynchronize(g->stream);   // the staging buffer is reused by the next slab
         if (e != hipSuccess && rc == FIR_OK) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
     }
-    (void)hipFree(stage);
+    stage.release();                                       // before the labels are allocated, as ever
     if (rc == FIR_OK && class_no && n > 0) {
-        e = hipMalloc((void**)&g->cls, (size_t)n * sizeof(int32_t));
+        e = g->cls.reserve((size_t)n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpy(g->cls, class_no, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class upload: %s", hipGetErrorString(e));
     }
-    if (rc) { fir_gallery_destroy(g); return rc; }
+    if (rc) { delete g; return rc; }
     { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
     *out = g;
     return FIR_OK;
@@ -1201,7 +1234,7 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
         rc = retile_slab(g, d_rows + r0 * d, span, r0, st);
     }
     if (rc == FIR_OK && d_class_no && n > 0) {
-        hipError_t e = hipMalloc((void**)&g->cls, (size_t)n * sizeof(int32_t));
+        hipError_t e = g->cls.reserve((size_t)n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpyAsync(g->cls, d_class_no, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class copy: %s", hipGetErrorString(e));
     }
@@ -1209,7 +1242,7 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
     }
-    if (rc) { fir_gallery_destroy(g); return rc; }
+    if (rc) { delete g; return rc; }
     { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
     *out = g;
     return FIR_OK;
@@ -1220,15 +1253,6 @@ int fir_gallery_destroy(fir_gallery* g) {
     (void)hipSetDevice(g->device);
     (void)fir_gallery_wait_calls_(g);         // calls queued on the callers' streams may still use what is freed below
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
-    for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
-    for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
-    (void)hipFree(g->gal4); (void)hipFree(g->cls); (void)hipFree(g->qt); (void)hipFree(g->dq); (void)hipFree(g->dkeys);
-    (void)hipFree(g->part); (void)hipFree(g->dout); (void)hipFree(g->didx); (void)hipFree(g->range); (void)hipFree(g->one_keys); (void)hipFree(g->rowsum);
-    if (g->pin) (void)hipHostFree(g->pin);
-    for (void* p : g->scratch) if (p) (void)hipFree(p);
-    if (g->last_done) (void)hipEventDestroy(g->last_done);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
     return FIR_OK;
 }
@@ -1253,8 +1277,7 @@ int fir_gallery_set_large_batch_mfma(fir_gallery* g, int32_t min_queries) {
     if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     g->large_batch_min = min_queries < 0 ? -1 : min_queries;
     g->gemm_failed = false;
-    if (min_queries == 0 && g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
-    if (min_queries == 0) for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
+    if (min_queries == 0) g->drop_gemm_states();
     return FIR_OK;
 }
 
@@ -1298,10 +1321,9 @@ int fir_gallery_memory_bytes(fir_gallery* g, int64_t* tiled, int64_t* fp16_fragm
     if (g->gemm) { fir_gemm_memory_bytes_(g->gemm, &a, &b, &c); fr += a; rm += b; sc += c; }
     for (auto& ps : g->gemm_prefix)
         if (ps.m) { fir_gemm_memory_bytes_(ps.m, &a, &b, &c); fr += a; rm += b; sc += c; }
-    sc += (int64_t)(g->qt_cap * sizeof(float) + g->dq_cap * sizeof(float) + g->dkeys_cap * sizeof(uint64_t) + g->part_cap * sizeof(uint64_t) +
-                    g->dout_cap * sizeof(float) + g->didx_cap * sizeof(int32_t));
-    for (size_t i = 0; i < 24; ++i) sc += (int64_t)g->scratch_cap[i];
-    sc += (int64_t)(g->rowsum_cap * sizeof(float));
+    // the capacities of the workspaces and the scratch slots; the range flags and the one-query key block (16 and 64 bytes) are
+    // reported nowhere, as ever
+    sc += (int64_t)g->scratch_bytes();
     if (tiled) *tiled = (int64_t)g->tiles * fir::kTileRows * (int64_t)((g->d + 3) / 4) * 16 + (g->cls ? (int64_t)g->n * 4 : 0);
     if (fp16_fragments) *fp16_fragments = fr;
     if (rowmajor_shadow) *rowmajor_shadow = rm;
@@ -1313,8 +1335,7 @@ int fir_gallery_set_shadow_copies(fir_gallery* g, int32_t mode) {
     if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
     if (mode != FIR_SHADOW_NONE && mode != FIR_SHADOW_FP16 && mode != FIR_SHADOW_ALL) return fir_fail_(FIR_ERR_ARG, "shadow mode %d", mode);
     if (mode != g->shadow_mode) {
-        if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
-        for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
+        g->drop_gemm_states();
         g->gemm_failed = false;
     }
     g->shadow_mode = mode;
@@ -1326,8 +1347,7 @@ int fir_gallery_set_row_offset(fir_gallery* g, int64_t first_global_row) {
     if (first_global_row < 0 || first_global_row + g->n >= ((int64_t)1 << 31))
         return fir_fail_(FIR_ERR_ARG, "row offset %lld + n does not fit 32-bit indices", (long long)first_global_row);
     g->row_offset = first_global_row;
-    if (g->gemm) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }   // it caches the offset; rebuilt on next use
-    for (auto& ps : g->gemm_prefix) if (ps.m) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
+    g->drop_gemm_states();                                           // they cache the offset; rebuilt on next use
     return FIR_OK;
 }
 
@@ -1338,8 +1358,8 @@ int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_
     if (metric < 0 || metric > 2) return fir_fail_(FIR_ERR_ARG, "bad metric %d", metric);
     int rc = set_device(device);
     if (rc) return rc;
-    float* buf = nullptr;
-    FIR_HIP(hipMalloc((void**)&buf, (size_t)(2 * len + 1) * sizeof(float)));
+    GalleryBuf<float> buf;                                 // both vectors and the result; gone when this function returns
+    if ((rc = FIR_RESERVE(buf, (size_t)(2 * len + 1) * sizeof(float)))) return rc;
     hipError_t e = hipMemcpy(buf, lhs, (size_t)len * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(buf + len, rhs, (size_t)len * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -1349,7 +1369,6 @@ int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, buf + 2 * len, sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fir_fail_(FIR_ERR_HIP, "pair distance: %s", hipGetErrorString(e));
     return FIR_OK;
 }
@@ -1397,6 +1416,25 @@ int ensure_gemm(fir_gallery* g, int32_t end, fir_gemm** m, int* warm = nullptr, 
     *m = slot;
     return 0;
 }
+// ... with the warm-up rule by gallery size: a cache-resident gallery (fewer than kAutoMfmaRows rows) gets its state with the
+// fourth call that would have profited from it
+int ensure_gemm_warm(fir_gallery* g, int32_t end, fir_gemm** m) {
+    return g->n < kAutoMfmaRows ? ensure_gemm(g, end, m, &g->small_hits, 3) : ensure_gemm(g, end, m);
+}
+// The state for [0, end) (warm: by the rule above), then run(state). As ensure_gemm: 0 = done, 1 = take the scan, < 0 = error;
+// in automatic mode a call that finds no room for its candidate lists (FIR_ERR_NOMEM) is left to the scan as well.
+extern "C++" template <typename Run>
+int run_mfma(fir_gallery* g, int32_t end, bool warm, Run run) {
+    fir_gemm* m = nullptr;
+    const int rc = warm ? ensure_gemm_warm(g, end, &m) : ensure_gemm(g, end, &m);
+    if (rc) return rc;
+    const int rcs = run(m);
+    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    return rcs;
+}
 // The matrix-core path for this call, if it applies: 0 = done, 1 = take the scan, < 0 = error.
 int try_mfma(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, uint64_t* d_keys, hipStream_t st,
              const float* h_queries = nullptr) {
@@ -1411,45 +1449,24 @@ int try_mfma(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
         return 1;
     }
     if (!wants_mfma(g, qb, start, end)) return 1;
-    fir_gemm* m = nullptr;
-    const int rc = g->n < kAutoMfmaRows ? ensure_gemm(g, end, &m, &g->small_hits, 3) : ensure_gemm(g, end, &m);
-    if (rc) return rc;
-    // the int8 nomination (fir_gemm.hip: gemm_wants_i8_): the caller's switch; by itself only where the matrix cores were chosen
-    // automatically, for the whole row, over at least kAutoMfmaRows rows
-    fir_gemm_set_int8_(m, g->int8_mode > 0 ? 1 : (g->int8_mode < 0 && g->large_batch_min < 0 && end == g->d && g->n >= kAutoMfmaRows) ? -1 : 0);
-    const int rcs = h_queries ? fir_gemm_search_staged_(m, h_queries, (float*)d_queries, qb, 1, d_keys, st)
-                              : fir_gemm_search_top1_keys_dev(m, d_queries, qb, d_keys, st);
-    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {       // no room for this call's candidate lists: the exact scan answers (automatic mode)
-        (void)hipGetLastError();
-        return 1;
-    }
-    return rcs;
+    return run_mfma(g, end, true, [&](fir_gemm* m) {
+        // the int8 nomination (fir_gemm.hip: gemm_wants_i8_): the caller's switch; by itself only where the matrix cores were chosen
+        // automatically, for the whole row, over at least kAutoMfmaRows rows
+        fir_gemm_set_int8_(m, g->int8_mode > 0 ? 1 : (g->int8_mode < 0 && g->large_batch_min < 0 && end == g->d && g->n >= kAutoMfmaRows) ? -1 : 0);
+        return h_queries ? fir_gemm_search_staged_(m, h_queries, (float*)d_queries, qb, 1, d_keys, st)
+                         : fir_gemm_search_top1_keys_dev(m, d_queries, qb, d_keys, st);
+    });
 }
 int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
     if (k < 2 || !wants_mfma(g, qb, start, end)) return 1;       // K = 1 callers use the top-1 entry points
-    fir_gemm* m = nullptr;
-    const int rc = g->n < kAutoMfmaRows ? ensure_gemm(g, end, &m, &g->small_hits, 3) : ensure_gemm(g, end, &m);
-    if (rc) return rc;
-    const int rcs = fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, st);
-    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    return rcs;
+    return run_mfma(g, end, true, [&](fir_gemm* m) { return fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, st); });
 }
 // ... and for the K nearest distinct classes of a host-pointer batch (fir_search_top_classes): the gallery needs its labels
+// (never a warm-up: the automatic rule takes galleries of kAutoMfmaRows rows or more, below that only a caller's threshold does)
 int try_mfma_classes(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k, uint64_t* d_keys,
                      int32_t* d_classes, hipStream_t st) {
     if (!g->cls || !wants_mfma(g, qb, start, end, true)) return 1;
-    fir_gemm* m = nullptr;
-    const int rc = ensure_gemm(g, end, &m);
-    if (rc) return rc;
-    const int rcs = fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, num_classes, k, d_keys, d_classes, st);
-    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    return rcs;
+    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, num_classes, k, d_keys, d_classes, st); });
 }
 }  // namespace
 
@@ -1490,15 +1507,8 @@ int fir_twd_mfma_topk_(fir_gallery* g, const float* d_queries, int32_t qb, int32
     // the rule for these qb queries; under a caller's threshold the batch that was admitted (qb_call queries) decides for its parts too
     const bool by_call = g->large_batch_min > 0 && wants_mfma(g, qb_call, 0, end_pos);
     if (k < 2 || g->shadow_mode == FIR_SHADOW_NONE || !(by_call || wants_mfma(g, qb, 0, end_pos))) return 1;
-    fir_gemm* m = nullptr;
-    const int rc = ensure_gemm(g, end_pos, &m);
-    if (rc) return rc;
-    const int rcs = fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, stream ? (hipStream_t)stream : g->stream);
-    if (rcs == FIR_ERR_NOMEM && g->large_batch_min < 0) {       // no room for this call's candidate lists (automatic mode): the staged form answers
-        (void)hipGetLastError();
-        return 1;
-    }
-    return rcs;
+    // (no warm-up: the batch form has made up its mind; no room for this call's candidate lists in automatic mode: the staged form answers)
+    return run_mfma(g, end_pos, false, [&](fir_gemm* m) { return fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, stream ? (hipStream_t)stream : g->stream); });
 }
 int64_t* fir_gallery_twd_mfma_record_(fir_gallery* g) { return g->twd_mfma; }
 
@@ -1546,58 +1556,39 @@ int fir_gallery_label_range_(fir_gallery* g, int32_t* lo, int32_t* hi) {
 }
 
 int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return qb < 0 ? fir_fail_(FIR_ERR_ARG, "qb < 0") : FIR_OK;
-    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
     int32_t start_pos = 0;
-    const int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    const fir_dispatch_info saved = g->last;          // the caller's dispatch record stays the matrix-core pass's, not this fallback's
-    const int rc2 = topk_dev(g, d_queries, qb, 0, end_pos, k, d_keys, st, true, false);
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr, [&] { return qb == 0 ? kNothingToDo : check_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    // timed like any scan of the call, but the caller's dispatch record stays the matrix-core pass's, not this fallback's
+    const fir_dispatch_info saved = g->last;
+    const int rc2 = topk_dev(g, d_queries, qb, 0, end_pos, k, d_keys, call.st, true, false);
     g->last = saved;
     return rc2;
 }
 
 int fir_search_top1_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                              uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
+    int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
     g->call_launches = 0;
     g->warm_left = 0;
-    rc = try_mfma(g, d_queries, qb, start_pos, end_pos, d_keys, st);
+    rc = try_mfma(g, d_queries, qb, start_pos, end_pos, d_keys, call.st);
     if (rc <= 0) return rc;
-    return top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, st);
+    return top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, call.st);
 }
 
 // The exact streaming scan, whatever the batch size (fir_gemm.hip sends its uncertified queries here).
 int fir_search_top1_exact_keys_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, uint64_t* d_keys,
                                     void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb <= 0) return qb < 0 ? fir_fail_(FIR_ERR_ARG, "qb < 0") : FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    const bool was_profiling = g->profiling, was_quiet = g->quiet;
-    g->profiling = false;
-    g->quiet = true;
-    rc = top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, st);
-    g->quiet = was_quiet;
-    g->profiling = was_profiling;
-    return rc;
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return top1_dev(g, d_queries, qb, start_pos, end_pos, d_keys, call.st, kOnBehalf);
 }
 
 // Profiling hooks for the library's other translation units: an event pair around one launch on `st`.
@@ -1684,13 +1675,14 @@ int top1_one_query(fir_gallery* g, const float* pinned_query, int32_t start, int
     // up to 256 tiles (16 384 rows): every workgroup of this form ends on a device-wide fence before it is counted, and beyond
     // ~90 workgroups those fences cost more than the two extra launches of the general path (12 000 x 512: 25.5 against
     // 28.1 us; 24 000: 32.8 / 32.2; 50 000: 44.4 / 35.4)
-    if (g->metric != kL2 || g->n <= 0 || g->tiles > 256 || g->tiles_limit > 0 || g->profiling) return 1;
+    if (g->metric != kL2 || g->n <= 0 || g->tiles > 256 || g->profiling) return 1;
     const ScanKernel sk = select_scan(kEpiTop1, 1, g->metric, whole_chunks(start, end), g->dp4, /*few_tiles=*/true);
     if (!sk.fn || sk.lds_bytes == 0) return 1;       // (only the form that stages the query in LDS publishes)
     const scan_fn fn = sk.fn;
     const size_t lds_bytes = sk.lds_bytes;
     if (!g->one_keys) {
-        FIR_HIP(hipMalloc((void**)&g->one_keys, 64));
+        const int rc = FIR_RESERVE(g->one_keys, 64);
+        if (rc) return rc;
         g->one_done = (int32_t*)(g->one_keys + 4);
         const uint64_t init[8] = {kKeyNone, kKeyNone, kKeyNone, kKeyNone, 0, 0, 0, 0};
         FIR_HIP(hipMemcpy(g->one_keys, init, sizeof init, hipMemcpyHostToDevice));
@@ -1698,7 +1690,7 @@ int top1_one_query(fir_gallery* g, const float* pinned_query, int32_t start, int
     const int max_waves = max_waves_for(g, fn, lds_bytes);
     const int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
     g->last_waves = waves;
-    ScanArgs a = scan_args(g, start, end, waves);
+    ScanArgs a = scan_args(g, {}, start, end, waves);
     a.qt = pinned_query;
     a.keys = g->one_keys;
     a.nq = 1;
@@ -1723,6 +1715,32 @@ int ensure_pin(fir_gallery* g) {
     FIR_HIP(hipHostMalloc(&g->pin, kPinQueryBytes + kPinKeys * sizeof(uint64_t), hipHostMallocDefault));
     return FIR_OK;
 }
+uint64_t* pin_keys(const fir_gallery* g) { return (uint64_t*)((char*)g->pin + kPinQueryBytes); }
+
+// ---- how a host-pointer call gets its keys home: both end the call (call.done()) and unpack into idx / dist -----------------------
+// Small calls: g->dkeys[0, count) published through the pinned block by a kernel; the host waits for the ticket that kernel writes
+// after them when one block publishes and nobody is profiling, else for the stream.
+int deliver_pinned(fir_gallery* g, GalleryCall& call, int count, int32_t* idx, float* dist) {
+    uint64_t* hk = pin_keys(g);
+    const uint64_t ticket = count <= kBlock && !g->profiling ? ++g->one_ticket : 0;
+    hipLaunchKernelGGL(k_publish_keys, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, g->stream, g->dkeys, count, hk, ticket);
+    FIR_HIP(hipGetLastError());
+    if (ticket) {
+        const int rc = fir_wait_ticket_(g->stream, hk + count, ticket);
+        if (rc) return rc;
+    } else FIR_HIP(hipStreamSynchronize(g->stream));
+    call.done();
+    return fir_keys_unpack(hk, count, idx, dist);
+}
+// Any call: g->dkeys[0, count) -- and g->didx[0, count) into class_out, when asked for -- copied back, one synchronisation.
+int deliver_copied(fir_gallery* g, GalleryCall& call, size_t count, int32_t* class_out, int32_t* idx, float* dist) {
+    std::vector<uint64_t> keys(count);
+    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, count * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->didx, count * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    call.done();
+    return fir_keys_unpack(keys.data(), (int32_t)count, idx, dist);
+}
 }  // namespace
 
 int fir_gallery_pin_(fir_gallery* g, void** base, size_t* query_bytes, uint64_t** results) {
@@ -1731,7 +1749,7 @@ int fir_gallery_pin_(fir_gallery* g, void** base, size_t* query_bytes, uint64_t*
     if (rc) return rc;
     *base = g->pin;
     *query_bytes = kPinQueryBytes;
-    *results = (uint64_t*)((char*)g->pin + kPinQueryBytes);
+    *results = pin_keys(g);
     return FIR_OK;
 }
 uint64_t fir_gallery_next_ticket_(fir_gallery* g) { return ++g->one_ticket; }
@@ -1752,42 +1770,31 @@ int fir_wait_ticket_(hipStream_t st, volatile uint64_t* flag, uint64_t ticket) {
 
 int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* idx,
                     float* dist) {
-    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);               // (a host-pointer call is a call on the handle's own stream)
-    if (order.rc) return order.rc;
+    int rc = check_search(g, queries, qb, start_pos, end_pos);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
     const bool mfma = wants_mfma(g, qb, start_pos, end_pos);
     g->call_launches = 0;
     if (!mfma && (size_t)qb * g->d * sizeof(float) <= kPinQueryBytes && (size_t)qb <= kPinKeys) {
         // small call: queries are read from, and keys written to, pinned host memory by the kernels themselves
         if ((rc = ensure_pin(g))) return rc;
-        if ((rc = grow(g->dkeys, g->dkeys_cap, (size_t)qb))) return rc;
+        if ((rc = FIR_NEED(g->dkeys, (size_t)qb))) return rc;
         float* hq = (float*)g->pin;
-        uint64_t* hk = (uint64_t*)((char*)g->pin + kPinQueryBytes);
         std::memcpy(hq, queries, (size_t)qb * g->d * sizeof(float));
         if (qb == 1) {
             for (int k = g->d; k < g->dp4 * 4; ++k) hq[k] = 0.0f;        // the one-query tile, zero padded
-            rc = top1_one_query(g, hq, start_pos, end_pos, hk);
+            rc = top1_one_query(g, hq, start_pos, end_pos, pin_keys(g));
             if (rc < 0) return rc;
-            if (rc == FIR_OK) { order.done(); return fir_keys_unpack(hk, 1, idx, dist); }
+            if (rc == FIR_OK) { call.done(); return fir_keys_unpack(pin_keys(g), 1, idx, dist); }
         }
         rc = try_mfma(g, hq, qb, start_pos, end_pos, g->dkeys, g->stream);              // (the few-query form on large galleries; else 1)
         if (rc < 0) return rc;
         if (rc > 0 && (rc = top1_dev(g, hq, qb, start_pos, end_pos, g->dkeys, g->stream))) return rc;
-        const uint64_t ticket = qb <= kBlock && !g->profiling ? ++g->one_ticket : 0;     // one block publishes: the host can wait on its ticket
-        hipLaunchKernelGGL(k_publish_keys, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, g->stream, g->dkeys, qb, hk, ticket);
-        FIR_HIP(hipGetLastError());
-        if (ticket) { if ((rc = fir_wait_ticket_(g->stream, hk + qb, ticket))) return rc; }
-        else FIR_HIP(hipStreamSynchronize(g->stream));
-        order.done();
-        return fir_keys_unpack(hk, qb, idx, dist);
+        return deliver_pinned(g, call, qb, idx, dist);
     }
-    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
-    if ((rc = grow(g->dkeys, g->dkeys_cap, (size_t)qb))) return rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    if ((rc = FIR_NEED(g->dkeys, (size_t)qb))) return rc;
     // large L2 batches go through the matrix cores (same keys, fir_gemm.hip) unless switched off; their queries are uploaded
     // super-batch by super-batch under the passes of the one before
     rc = try_mfma(g, g->dq, qb, start_pos, end_pos, g->dkeys, g->stream, queries);
@@ -1796,11 +1803,7 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         rc = top1_dev(g, g->dq, qb, start_pos, end_pos, g->dkeys, g->stream);
     }
     if (rc) return rc;
-    std::vector<uint64_t> keys((size_t)qb);
-    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, (size_t)qb * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    FIR_HIP(hipStreamSynchronize(g->stream));
-    order.done();
-    return fir_keys_unpack(keys.data(), qb, idx, dist);
+    return deliver_copied(g, call, (size_t)qb, nullptr, idx, dist);
 }
 
 uint64_t fir_key_pack(float dist, int32_t idx) {
@@ -1826,10 +1829,9 @@ int fir_gallery_classes_of(fir_gallery* g, const int32_t* idx, int32_t n, int32_
     if (!g || !idx || !class_out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (!g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
     if (n <= 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);
-    if (order.rc) return order.rc;
-    int rc = grow(g->didx, g->didx_cap, (size_t)2 * n);
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    const int rc = FIR_NEED(g->didx, (size_t)2 * n);
     if (rc) return rc;
     FIR_HIP(hipMemcpyAsync(g->didx, idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
     hipLaunchKernelGGL(k_classes_of, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, g->stream, g->cls, g->n, g->row_offset,
@@ -1842,51 +1844,35 @@ int fir_gallery_classes_of(fir_gallery* g, const int32_t* idx, int32_t n, int32_
 
 int fir_search_topk_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                              int32_t k, uint64_t* d_keys, void* stream) {
-    if (!g || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
-    if (qb == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    return topk_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, st);
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr, [&] { return check_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return topk_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, call.st);
 }
 
 int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                     int32_t* idx, float* dist) {
-    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > kKMax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax);
-    if (qb == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);
-    if (order.rc) return order.rc;
-    if ((rc = grow(g->dkeys, g->dkeys_cap, (size_t)qb * k))) return rc;
+    int rc = check_search(g, queries, qb, start_pos, end_pos, true, [&] { return check_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if ((rc = FIR_NEED(g->dkeys, (size_t)qb * k))) return rc;
     if ((size_t)qb * g->d * sizeof(float) <= kPinQueryBytes && qb * k <= kBlock && qb < 8 && !g->profiling) {
         // small call (below the candidate-list form, which synchronises by itself): pinned queries in, keys + ticket out, as in fir_search_top1
         if ((rc = ensure_pin(g))) return rc;
         float* hq = (float*)g->pin;
-        uint64_t* hk = (uint64_t*)((char*)g->pin + kPinQueryBytes);
         std::memcpy(hq, queries, (size_t)qb * g->d * sizeof(float));
         if ((rc = topk_dev(g, hq, qb, start_pos, end_pos, k, g->dkeys, g->stream))) return rc;
-        const uint64_t ticket = ++g->one_ticket;
-        hipLaunchKernelGGL(k_publish_keys, dim3(1), dim3(kBlock), 0, g->stream, g->dkeys, qb * k, hk, ticket);
-        FIR_HIP(hipGetLastError());
-        if ((rc = fir_wait_ticket_(g->stream, hk + qb * k, ticket))) return rc;
-        order.done();
-        return fir_keys_unpack(hk, qb * k, idx, dist);
+        return deliver_pinned(g, call, qb * k, idx, dist);
     }
-    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
-    // large L2 batches: the matrix cores, the queries uploaded super-batch by super-batch under the passes (as fir_search_top1)
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    // large L2 batches: the matrix cores, the queries uploaded super-batch by super-batch under the passes (as fir_search_top1;
+    // here a call that finds no room for its lists fails, as it always has)
     rc = 1;
     if (k >= 2 && wants_mfma(g, qb, start_pos, end_pos)) {
         fir_gemm* m = nullptr;
-        rc = g->n < kAutoMfmaRows ? ensure_gemm(g, end_pos, &m, &g->small_hits, 3) : ensure_gemm(g, end_pos, &m);
+        rc = ensure_gemm_warm(g, end_pos, &m);
         if (rc == 0) rc = fir_gemm_search_staged_(m, queries, g->dq, qb, k, g->dkeys, g->stream);
         if (rc < 0) return rc;
     }
@@ -1894,84 +1880,65 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
         if ((rc = topk_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream, true, false))) return rc;   // (the matrix cores were consulted above)
     }
-    std::vector<uint64_t> keys((size_t)qb * k);
-    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, keys.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    FIR_HIP(hipStreamSynchronize(g->stream));
-    order.done();
-    return fir_keys_unpack(keys.data(), qb * k, idx, dist);
+    return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
 }
 
 namespace {
+// check_search for the class searches: k, num_classes and the labels in its `extra` place -- and the range too, which these entry
+// points have always checked before they look at qb == 0.
 int check_top_classes(const fir_gallery* g, const float* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, int32_t num_classes, int32_t k) {
-    if (!g || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > 32) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,32]", k);
-    if (num_classes < 1 || num_classes > kClassMax) return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
-    if (!g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
-    return check_range(g, start_pos, end_pos);
+    return check_search(g, queries, qb, start_pos, end_pos, true, [&] {
+        if (k < 1 || k > 32) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,32]", k);
+        if (num_classes < 1 || num_classes > kClassMax) return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
+        if (!g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
+        return check_range(g, start_pos, end_pos);
+    });
 }
 }  // namespace
 
 int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes,
                                     int32_t k, uint64_t* d_keys, int32_t* d_classes, void* stream) {
-    int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
-    if (rc) return rc;
+    const int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
+    if (rc < 0) return rc;
     if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
-    if (qb == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
+    if (rc) return FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
     g->call_launches = 0;
     g->warm_left = 0;
-    return top_classes_dev(g, d_queries, qb, start_pos, end_pos, num_classes, k, d_keys, d_classes, st);
+    return top_classes_dev(g, d_queries, qb, start_pos, end_pos, num_classes, k, d_keys, d_classes, call.st);
 }
 
 // The class-minimum scan on behalf of fir_gemm_search_top_classes_keys_dev, neither recorded nor timed (fir_internal.h).
 int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k, int64_t sample_rows,
                         uint64_t* d_keys, int32_t* d_classes, float* d_bound, void* stream) {
     int32_t start_pos = 0;
-    int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
-    if (rc) return rc;
+    const int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k);
+    if (rc < 0) return rc;
     if (sample_rows > 0 ? !d_bound : (!d_keys && !d_classes)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    const bool was_profiling = g->profiling, was_quiet = g->quiet;
-    g->profiling = false;
-    g->quiet = true;
-    rc = top_classes_dev(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, st, (sample_rows + kTileRows - 1) / kTileRows, d_bound);
-    g->quiet = was_quiet;
-    g->profiling = was_profiling;
-    return rc;
+    if (rc) return FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return top_classes_dev(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, call.st, kOnBehalf, (sample_rows + kTileRows - 1) / kTileRows, d_bound);
 }
 
 int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes, int32_t k,
                            int32_t* class_out, int32_t* idx, float* dist) {
     int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k);
-    if (rc) return rc;
-    if (qb == 0) return FIR_OK;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);               // (a host-pointer call is a call on the handle's own stream)
-    if (order.rc) return order.rc;
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
     g->call_launches = 0;
     g->warm_left = 0;
     const size_t slots = (size_t)qb * k;
-    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
-    if ((rc = grow(g->dkeys, g->dkeys_cap, slots))) return rc;
-    if ((rc = grow(g->didx, g->didx_cap, slots))) return rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    if ((rc = FIR_NEED(g->dkeys, slots))) return rc;
+    if ((rc = FIR_NEED(g->didx, slots))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
     rc = try_mfma_classes(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
     if (rc > 0) rc = top_classes_dev(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
     if (rc) return rc;
-    std::vector<uint64_t> keys(slots);
-    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->didx, slots * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    FIR_HIP(hipStreamSynchronize(g->stream));
-    order.done();
-    return fir_keys_unpack(keys.data(), (int32_t)slots, idx, dist);
+    return deliver_copied(g, call, slots, class_out, idx, dist);
 }
 
 int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k, uint64_t* keys_out,
@@ -2005,29 +1972,20 @@ int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t p
 
 int fir_range_distances_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                             float* d_out, void* stream) {
-    if (!g || !d_out || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-    FirCallOrder order(g, st);
-    if (order.rc) return order.rc;
-    return range_dev(g, d_queries, qb, start_pos, end_pos, d_out, st);
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_out != nullptr);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return range_dev(g, d_queries, qb, start_pos, end_pos, d_out, call.st);
 }
 
 int fir_range_distances(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, float* out) {
-    if (!g || !out || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (qb == 0 || g->n == 0) return FIR_OK;
-    int rc = check_range(g, start_pos, end_pos);
-    if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);
-    if (order.rc) return order.rc;
-    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
-    if ((rc = grow(g->dout, g->dout_cap, (size_t)qb * g->n))) return rc;
+    int rc = check_search(g, queries, qb, start_pos, end_pos, out != nullptr, [&] { return g->n == 0 ? kNothingToDo : FIR_OK; });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    if ((rc = FIR_NEED(g->dout, (size_t)qb * g->n))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
     if ((rc = range_dev(g, g->dq, qb, start_pos, end_pos, g->dout, g->stream))) return rc;
     FIR_HIP(hipMemcpyAsync(out, g->dout, (size_t)qb * g->n * sizeof(float), hipMemcpyDeviceToHost, g->stream));
@@ -2057,17 +2015,16 @@ int fir_gallery_list_nominations_(fir_gallery* g, const float* queries, int32_t 
     if (all_rows && g->n > kListCap) return fir_fail_(FIR_ERR_ARG, "all_rows: %lld rows, a list holds %d", (long long)g->n, kListCap);
     int rc = check_range(g, start_pos, end_pos);
     if (rc) return rc;
-    FIR_HIP(hipSetDevice(g->device));
-    FirCallOrder order(g, g->stream);
-    if (order.rc) return order.rc;
-    if ((rc = grow(g->dq, g->dq_cap, (size_t)qb * g->d))) return rc;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
     ListCall c{g, g->dq, qb, start_pos, end_pos, k, g->stream};
     g->call_launches = 0;
     if ((rc = list_nominate(c, all_rows != 0))) return rc;
     FIR_HIP(hipGetLastError());
     FIR_HIP(hipStreamSynchronize(g->stream));
-    order.done();
+    call.done();
     if (info) { info[0] = c.nomination_metric(); info[1] = c.qpad; info[2] = c.sample_stride; info[3] = (int32_t)c.group_tiles; }
     if (counts) FIR_HIP(hipMemcpy(counts, c.counts, (size_t)c.qpad * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (tau) FIR_HIP(hipMemcpy(tau, c.tau, (size_t)c.qpad * sizeof(float), hipMemcpyDeviceToHost));
