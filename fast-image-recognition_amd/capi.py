@@ -52,6 +52,8 @@ SYMBOLS = [
     ("fir_gallery_classes_of", C.c_int, [_vp, _vp, C.c_int32, _vp]),
     ("fir_search_topk", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_topk_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_search_knn", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_search_knn_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_top_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_class_keys_merge", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
@@ -116,6 +118,7 @@ SYMBOLS = [
     ("fir_sharded_set_metric", C.c_int, [_vp, C.c_int32]),
     ("fir_sharded_search_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_search_topk", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_sharded_search_knn", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_classify_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_search_top1_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_sync", C.c_int, [_vp]),
@@ -347,6 +350,19 @@ class Gallery:
     def search_topk_keys_dev(self, q_ptr, qb, k, keys_ptr, start=0, end=0, stream=None):
         _check(lib().fir_search_topk_keys_dev(self._h, _vp(q_ptr), qb, start, end, k, _vp(keys_ptr), _vp(stream) if stream else None))
 
+    def search_knn(self, queries, k, start=0, end=0):
+        """The k nearest rows of each query for 1 <= k <= 1024: (idx, dist), each [qb, k], ascending by (distance, row);
+        unused slots -1 / 100000."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        _check(lib().fir_search_knn(self._h, pq, q.shape[0], start, end, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_knn_keys_dev(self, q_ptr, qb, k, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_knn_keys_dev(self._h, _vp(q_ptr), qb, start, end, k, _vp(keys_ptr), _vp(stream) if stream else None))
+
     def search_top_classes(self, queries, num_classes, k, start=0, end=0):
         """The k nearest distinct classes of each query: (classes, idx, dist), each [qb, k]; unused slots -1 / -1 / 100000."""
         q, pq = _f32(queries)
@@ -565,6 +581,15 @@ class ShardedGallery:
         idx = np.empty((q.shape[0], k), np.int32)
         dist = np.empty((q.shape[0], k), np.float32)
         _check(lib().fir_sharded_search_topk(self._h, pq, q.shape[0], start, end, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_knn(self, queries, k, start=0, end=0):
+        """Gallery.search_knn over the shards: global row indices, the unsharded handle's keys."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        _check(lib().fir_sharded_search_knn(self._h, pq, q.shape[0], start, end, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
         return idx, dist
 
     def classify_top1(self, queries, start=0, end=0):

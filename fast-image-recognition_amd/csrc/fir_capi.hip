@@ -17,6 +17,7 @@
 
 #include "../../include/fir_amd.h"
 #include "fir_internal.h"
+#include "fir_knn_select.h"
 
 using namespace fir;
 
@@ -78,9 +79,10 @@ struct fir_gallery {
     GalleryBuf<float> dout;       // range distances for the host-pointer API
     GalleryBuf<int32_t> didx;
     GalleryBuf<float> rowsum;     // chi-square nomination (kChi2Harm): per-row sums over [rs_start, rs_end) + their maximum (rowsum[n])
+    FirBuf knn;                   // fir_search_knn: one query tile's stored distances + the select's control block (knn_plan)
     FirBuf scratch[24];
     size_t scratch_bytes() const {
-        size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap;
+        size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
         return sum;
     }
@@ -377,12 +379,6 @@ int check_range(const fir_gallery* g, int32_t& start, int32_t& end) {
 int next_serial(fir_gallery* g) {
     g->q_serial = (int)((unsigned)g->q_serial + 1u);
     return g->q_serial;
-}
-
-int largest_pow2_le(int x, int cap) {
-    int p = 1;
-    while (p * 2 <= x && p * 2 <= cap) p *= 2;
-    return p;
 }
 
 // Resident-wave capacity of one scan kernel on this device (cached per kernel / LDS size).
@@ -900,6 +896,63 @@ int range_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start,
     return FIR_OK;
 }
 
+// ---- the K nearest rows for K up to FIR_KNN_MAX: store + select ---------------------------------------------------------------------
+// Per tile of t queries (range_dev's choice of t) ONE gallery read: the store pass of range_dev writes the tile's exact distances
+// into g->knn -- the reference's arithmetic, the bits fir_range_distances returns -- and the radix select of fir_knn_select.h
+// takes the K smallest (distance, row) keys of each row of them. The slot holds one tile whatever qb is; when it cannot be had
+// for t queries the tile is halved, down to one query. Nothing synchronises once the slot is large enough. Not recorded as the
+// handle's dispatch (kOnBehalf): fir_gallery_last_dispatch describes searches that have a dominant scan kernel of their own.
+// With fir_profile_enable on, every tile leaves two event pairs: around the store pass (transposition + scan), then around the select.
+// FIR_KNN_SELECT_BLOCKS: workgroups per query of the select at most, for measurements (1 = one workgroup per query, the form
+// profiles/knn_select.txt refutes: never the default).
+int knn_select_blocks() {
+    const char* e = fir_knob_("FIR_KNN_SELECT_BLOCKS");
+    const int v = e ? atoi(e) : 0;
+    return v >= 1 ? std::min(v, kKnnMaxBlocks) : kKnnMaxBlocks;
+}
+int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
+    if (g->n == 0) {                                         // every slot FIR_KEY_NONE (all bytes 0xFF)
+        FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
+        return FIR_OK;
+    }
+    int t = largest_pow2_le(qb, std::min(effective_qpp(g), 8));
+    KnnPlan plan = knn_plan(g->n, t, sizeof(KnnCtl));
+    while (plan.bytes > g->knn.cap) {
+        const hipError_t e = g->knn.reserve(plan.bytes);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || t == 1)
+            return fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "no room for the distances of one query over %lld rows (%zu bytes): %s",
+                             (long long)g->n, plan.bytes, hipGetErrorString(e));
+        t /= 2;
+        plan = knn_plan(g->n, t, sizeof(KnnCtl));
+    }
+    int rc = FIR_NEED(g->qt, (size_t)t * g->dp4 * 4);
+    if (rc) return rc;
+    const int blocks = knn_select_blocks();
+    float* dist = g->knn.as<float>();
+    for (int q0 = 0; q0 < qb;) {
+        const int tt = largest_pow2_le(qb - q0, t);
+        if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
+        rc = run_pass(g, st, kOnBehalf, kEpiStore, d_queries + (size_t)q0 * g->d, 0, tt, start, end, nullptr, dist, plan.row_stride, 0);
+        if (rc) return rc;
+        if ((rc = fir_gallery_profile_end_(g, st, (double)g->n * (end - start) * 4.0))) return rc;
+        KnnArgs a{};
+        a.dist = dist;
+        a.n = g->n;
+        a.stride = plan.row_stride;
+        a.row_offset = g->row_offset;
+        a.k = k;
+        a.ctl = (KnnCtl*)((char*)g->knn.p + plan.dist_bytes);
+        a.out = d_keys + (size_t)q0 * k;
+        if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
+        FIR_HIP(knn_select_launch<true>(a, tt, blocks, st));
+        if ((rc = fir_gallery_profile_end_(g, st, (double)tt * g->n * 4.0))) return rc;
+        q0 += tt;
+    }
+    return FIR_OK;
+}
+
 int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t step, float* d_out, hipStream_t st,
                   int32_t step2 = 0) {
     // step2 != 0: two sub-ranges, [start, start + step) and [start + step, end) with end - start - step == step2 (whole load groups both)
@@ -1023,6 +1076,7 @@ int check_search(const fir_gallery* g, const void* queries, int32_t qb, int32_t&
     return check_search(g, queries, qb, start, end, pointers_ok, [] { return FIR_OK; });
 }
 int check_k(int32_t k) { return k < 1 || k > kKMax ? fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax) : FIR_OK; }
+int check_knn_k(int32_t k) { return knn_k_ok(k) ? FIR_OK : fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKnnMax); }
 
 // One call on a handle: its device made current, the stream it queues on (the caller's, else the handle's own: a host-pointer
 // call is a call on the handle's own stream) and its place in the handle's call order (FirCallOrder, which cannot be copied:
@@ -1880,6 +1934,27 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
         FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
         if ((rc = topk_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream, true, false))) return rc;   // (the matrix cores were consulted above)
     }
+    return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
+}
+
+int fir_search_knn_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, uint64_t* d_keys,
+                            void* stream) {
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr, [&] { return check_knn_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, call.st);
+}
+
+int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx, float* dist) {
+    int rc = check_search(g, queries, qb, start_pos, end_pos, idx != nullptr && dist != nullptr, [&] { return check_knn_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if ((rc = FIR_NEED(g->dkeys, (size_t)qb * k))) return rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    if ((rc = knn_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream))) return rc;
     return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
 }
 

@@ -31,10 +31,17 @@
 #include "../../include/fir_amd.h"
 #include "fir_common.h"
 #include "fir_internal.h"
+#include "fir_knn_select.h"
 
 namespace {
 
+using fir::SelState;
+using fir::sel_match;
+using fir::hist_add;
+using fir::sel_advance;
+
 constexpr int kBlock = 256;
+static_assert(kBlock == fir::kBlock, "thread t of a workgroup is bin t of the 8-bit digit histograms (hist[threadIdx.x], sel_advance)");
 constexpr int kMaxBlocks = 1024;
 
 struct Part {       // one block's partial result
@@ -255,7 +262,6 @@ constexpr int kWalkMaxBlocks = 128;      // workgroups per query of mark / fold 
 // tools/dem_recognize_probe.py forces either form (fir_dem_probe_) over Mc / n; profiles/dem_recognize.txt holds what is known.
 constexpr int kGatherDiv = 8;
 constexpr unsigned long long kNoKey = ~0ull;
-static_assert(kBlock == 256, "thread t of a workgroup is bin t of the 8-bit digit histograms (hist[threadIdx.x], sel_advance)");
 
 struct DemQ {               // one query of the batch
     float piv_best;         // the pivot loop's bestDistance / bestIndex
@@ -271,61 +277,12 @@ struct DemQ {               // one query of the batch
     unsigned long long win_key;
     unsigned long long T;
 };
-struct SelState { unsigned long long prefix; int32_t rank; int32_t done; };   // before a digit: key bits decided, rank inside them
+// SelState, sel_match, hist_add, sel_advance: fir_knn_select.h (shared with the K-nearest-rows select)
 struct FoldPart { unsigned long long exit_key; float exit_dist; uint32_t best_dist; unsigned long long best_key; };
 
 __device__ __forceinline__ unsigned long long dem_key(const float* __restrict__ lik, const int32_t* __restrict__ order, int p) {
     return ((unsigned long long)fir::f32_orderable(lik[order[p]]) << 32) | (unsigned)p;
 }
-__device__ __forceinline__ bool sel_match(unsigned long long key, unsigned long long prefix, int pass) {
-    return pass == 0 ? true : ((key ^ prefix) >> (64 - 8 * pass)) == 0;
-}
-
-// hist[digit] += 1 for the lanes with `match`; every lane of the wave calls it. Likelihoods of one query share their top bytes,
-// so the lanes of a wave mostly hit one bin: the first two distinct digits found are counted with a ballot and added once per
-// wave, whatever is left lane by lane.
-__device__ __forceinline__ void hist_add(unsigned* hist, bool match, unsigned digit) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long rem = __ballot(match);
-    for (int it = 0; it < 2 && rem; ++it) {
-        const int leader = __ffsll((long long)rem) - 1;
-        const unsigned d0 = __shfl(digit, leader, 64);
-        const unsigned long long m = __ballot(match && digit == d0);
-        if (lane == leader) atomicAdd(&hist[d0], (unsigned)__popcll(m));
-        rem &= ~m;
-    }
-    if ((rem >> lane) & 1) atomicAdd(&hist[digit], 1u);
-}
-
-// The state after digit `pass`, from the state before it and the digit's histogram (thread t holds bin t): the bin the rank falls
-// into (inclusive sums folded across the wave with shuffles, across the four waves through LDS). When the rank is the bin's
-// whole count, everything in the bin is selected and the remaining digits are all ones: done. All kBlock threads call it.
-__device__ SelState sel_advance(SelState s, unsigned count, int pass, unsigned* wsum, SelState* box) {
-    if (s.done) return s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, shift = 56 - 8 * pass;
-    unsigned incl = count;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    if (threadIdx.x == 0) *box = SelState{s.prefix, s.rank, 1};   // (a rank outside the histogram: cannot happen, and must not hang)
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) incl += wsum[w];
-    const unsigned excl = incl - count, rank = (unsigned)s.rank;
-    if (count > 0 && excl < rank && rank <= incl) {
-        const int all = rank - excl == count;
-        unsigned long long prefix = s.prefix | ((unsigned long long)threadIdx.x << shift);
-        if (all) prefix |= (1ull << shift) - 1;
-        *box = SelState{prefix, (int32_t)(rank - excl), all};
-    }
-    __syncthreads();
-    s = *box;
-    __syncthreads();
-    return s;
-}
-
 __global__ void __launch_bounds__(64) k_dem_head(const float* __restrict__ pd, int used, int nq, float thr, const int32_t* __restrict__ pivots, int mc,
                                                  int cnt, DemQ* __restrict__ Q, SelState* __restrict__ sel0) {
     const int q = threadIdx.x;

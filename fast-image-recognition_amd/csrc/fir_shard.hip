@@ -44,16 +44,22 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/fir_amd.h"
 #include "fir_common.h"
 #include "fir_internal.h"
+#include "fir_knn_select.h"
 
 namespace {
 
 using fir::kKeyNone;
+using fir::KnnArgs;
+using fir::KnnCtl;
+using fir::kKnnTile;
+constexpr int kMergeListMax = 8;     // k up to which k_shard_merge_topk merges (fir_sharded_search_topk's range); beyond it merge_knn
 
 #define SH_NCCL(expr)                                                                                                  \
     do {                                                                                                               \
@@ -71,6 +77,17 @@ __global__ void __launch_bounds__(256) k_shard_min_keys(const uint64_t* __restri
         m = v < m ? v : m;
     }
     keys[i] = m;
+}
+
+// *out = min over parts p of first[p * stride]   (the status elements behind gathered parts)
+__global__ void __launch_bounds__(64) k_shard_min_status(const uint64_t* __restrict__ first, int nparts, size_t stride, uint64_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    uint64_t m = kKeyNone;
+    for (int p = 0; p < nparts; ++p) {
+        const uint64_t v = first[(size_t)p * stride];
+        m = v < m ? v : m;
+    }
+    *out = m;
 }
 
 // out[q][0..k) = the k smallest of parts[p][q][0..k), p < nparts, ascending. Every part is ascending and keys are unique
@@ -172,6 +189,7 @@ struct DevCtx {
     uint64_t* keys = nullptr;   size_t keys_cap = 0;      // [qb * k] reduced
     uint64_t* gath = nullptr;   size_t gath_cap = 0;      // [nranks][qb * k]
     int32_t* cls = nullptr;     size_t cls_cap = 0;
+    uint64_t* sel = nullptr;    size_t sel_cap = 0;       // the control block of the K > 8 merge (fir_knn_select.h: KnnCtl)
     std::vector<int> shards;
     Worker* worker = nullptr;
     std::vector<hipEvent_t> evs;                          // pairs around the RCCL calls (profiling, device slot 0)
@@ -379,14 +397,14 @@ int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
 
 // The buffers of one call on one device, grown in the call's agreed step: queries (host-pointer form), the shards' partial
 // keys, the reduced keys + status element, the gathered keys of all ranks (top-K) and the winners' classes + status element.
-struct CallBuffers { size_t dq, parts, keys, gath, cls; };
+struct CallBuffers { size_t dq, parts, keys, gath, cls, sel; };
 CallBuffers call_buffers(const fir_sharded* h, const DevCtx& dc, int32_t qb, int32_t k, bool host_queries, bool classes) {
     const size_t per = (size_t)qb * k;
     return {host_queries ? (size_t)qb * h->d : 0, per * std::max<size_t>(dc.shards.size(), 1), per + 1,
-            k > 1 ? (per + 1) * (size_t)h->nranks : 0, classes ? (size_t)qb + 1 : 0};
+            k > 1 ? (per + 1) * (size_t)h->nranks : 0, classes ? (size_t)qb + 1 : 0, k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 : 0};
 }
 bool call_grows(const DevCtx& dc, const CallBuffers& b) {
-    return b.dq > dc.dq_cap || b.parts > dc.parts_cap || b.keys > dc.keys_cap || b.gath > dc.gath_cap || b.cls > dc.cls_cap;
+    return b.dq > dc.dq_cap || b.parts > dc.parts_cap || b.keys > dc.keys_cap || b.gath > dc.gath_cap || b.cls > dc.cls_cap || b.sel > dc.sel_cap;
 }
 int call_alloc(DevCtx& dc, const CallBuffers& b) {
     int rc;
@@ -394,6 +412,7 @@ int call_alloc(DevCtx& dc, const CallBuffers& b) {
     if ((rc = grow_dev(dc.parts, dc.parts_cap, b.parts))) return rc;
     if ((rc = grow_dev(dc.keys, dc.keys_cap, b.keys))) return rc;
     if ((rc = grow_dev(dc.gath, dc.gath_cap, b.gath))) return rc;
+    if ((rc = grow_dev(dc.sel, dc.sel_cap, b.sel))) return rc;
     return grow_dev(dc.cls, dc.cls_cap, b.cls);
 }
 bool inject_here(const fir_sharded* h, const DevCtx& dc, int step) {
@@ -403,9 +422,29 @@ bool inject_here(const fir_sharded* h, const DevCtx& dc, int step) {
     return false;
 }
 
+// out[q][0..k) = the k smallest of parts[p][q][0..k), p < nparts, ascending, for k > kMergeListMax (fir_sharded_search_knn): the
+// keys are orderable and unique, so the radix select of fir_knn_select.h over each query's nparts * k keys finds exactly them
+// -- k_shard_merge_topk reads every list k times with one lane per query, which holds for 8 keys and not for 1024 x ranks.
+// kKnnTile queries per select; status_out (may be NULL) <- the minimum of the status elements behind the parts.
+int merge_knn(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t k, uint64_t* out, size_t stride, uint64_t* status_out, hipStream_t st) {
+    if (status_out) hipLaunchKernelGGL(k_shard_min_status, dim3(1), dim3(64), 0, st, parts + (size_t)qb * k, nparts, stride, status_out);
+    for (int q0 = 0; q0 < qb; q0 += kKnnTile) {
+        KnnArgs a{};
+        a.keys = parts + (size_t)q0 * k;
+        a.n = (int64_t)nparts * k;
+        a.stride = (int64_t)stride;
+        a.k_in = k;
+        a.k = k;
+        a.ctl = (KnnCtl*)dc.sel;
+        a.out = out + (size_t)q0 * k;
+        FIR_HIP(fir::knn_select_launch<false>(a, std::min<int>(kKnnTile, qb - q0), fir::kKnnMaxBlocks, st));
+    }
+    return FIR_OK;
+}
+
 // The keys of one device: every shard it holds scans the batch (K keys per query, K = 1: top-1), then the minimum /
 // K-way merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc).
-int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st) {
+int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st, bool knn = false) {
     DevCtx& dc = h->devs[slot];
     const size_t per = (size_t)qb * k;
     int rc;
@@ -417,12 +456,14 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
         if (!s.g) continue;
         uint64_t* out = dc.parts + (size_t)live * per;
         rc = k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
+             : knn  ? fir_search_knn_keys_dev(s.g, d_queries, qb, start, end, k, out, st)
                     : fir_search_topk_keys_dev(s.g, d_queries, qb, start, end, k, out, st);
         if (rc) return rc;
         ++live;
     }
     if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.keys, (int)per, kKeyNone);
     else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.parts, live, (int)per, dc.keys);
+    else if (k > kMergeListMax) { if ((rc = merge_knn(dc, dc.parts, live, qb, k, dc.keys, per, nullptr, st))) return rc; }
     else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, dc.parts, live, qb, k, dc.keys, per, (uint64_t*)nullptr);
     FIR_HIP(hipGetLastError());
     return FIR_OK;
@@ -451,7 +492,12 @@ int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t s
         nr = ncclAllReduce(keys, keys, per + 1, ncclUint64, ncclMin, dc.comm, st);
     } else {
         nr = ncclAllGather(keys, dc.gath, per + 1, ncclUint64, dc.comm, st);
-        if (nr == ncclSuccess)
+        if (nr == ncclSuccess && k > kMergeListMax) {
+            if (merge_knn(dc, dc.gath, h->nranks, qb, k, keys, per + 1, keys + per, st)) {
+                const std::string why = fir_last_error();
+                return comm_dead(dc, h->health, FIR_ERR_HIP, why.c_str());
+            }
+        } else if (nr == ncclSuccess)
             hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, dc.gath, h->nranks, qb, k, keys, per + 1, keys + per);
     }
     if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
@@ -495,10 +541,12 @@ int dead_handle(const Health& hl) {
 
 // Host-pointer search: queries go to every device from pinned memory, keys (and classes) come back from device slot 0.
 int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, int32_t k, int32_t* idx, float* dist,
-                int32_t* class_out) {
-    if (!h || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+                int32_t* class_out, bool knn = false) {
+    if (!h || (qb > 0 && !queries) || (knn && (!idx || !dist))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > 8) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,8]", k);
+    const int kmax = knn ? FIR_KNN_MAX : 8;
+    if (k < 1 || k > kmax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kmax);
+    if ((int64_t)qb * k >= ((int64_t)1 << 31)) return fir_fail_(FIR_ERR_ARG, "qb * k = %lld keys do not fit 32-bit counts", (long long)qb * k);
     if (class_out && !h->has_labels) return fir_fail_(FIR_ERR_STATE, "the sharded gallery was created without class labels");
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
@@ -545,7 +593,7 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
         int local = FIR_OK;
         char mine[512] = "";
         if (hipMemcpyAsync(dc.dq, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess) local = fir_fail_(FIR_ERR_HIP, "query upload failed");
-        if (!local) local = device_keys(h, slot, dc.dq, qb, start, end, k, dc.stream);
+        if (!local) local = device_keys(h, slot, dc.dq, qb, start, end, k, dc.stream, knn);
         if (local) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); (void)hipGetLastError(); }
         if ((r = exchange_keys(h, slot, qb, k, dc.stream, local))) return r;
         if (class_out && (r = device_classes(h, slot, dc.keys, qb, dc.stream, local))) return r;
@@ -651,7 +699,7 @@ void teardown_devices(std::vector<DevCtx>& devs, bool dead) {
         (void)hipFree(dc.status);
         if (dc.h_status) (void)hipHostFree(dc.h_status);
         if (dc.async_done) (void)hipEventDestroy(dc.async_done);
-        (void)hipFree(dc.dq); (void)hipFree(dc.parts); (void)hipFree(dc.keys); (void)hipFree(dc.gath); (void)hipFree(dc.cls);
+        (void)hipFree(dc.dq); (void)hipFree(dc.parts); (void)hipFree(dc.keys); (void)hipFree(dc.gath); (void)hipFree(dc.cls); (void)hipFree(dc.sel);
         for (hipEvent_t e : dc.evs) (void)hipEventDestroy(e);
         if (dc.stream) (void)hipStreamDestroy(dc.stream);
         dc = DevCtx();
@@ -1168,6 +1216,11 @@ int fir_sharded_search_top1(fir_sharded* h, const float* queries, int32_t qb, in
 int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
                             float* dist) {
     return search_host(h, queries, qb, start_pos, end_pos, k, idx, dist, nullptr);
+}
+
+int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
+                           float* dist) {
+    return search_host(h, queries, qb, start_pos, end_pos, k, idx, dist, nullptr, true);
 }
 
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* class_out,

@@ -166,6 +166,33 @@ int fir_search_top_classes_keys_dev(fir_gallery* g, const float* d_queries, int3
 int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k,
                          uint64_t* keys_out, int32_t* classes_out);
 
+/* ---- the K nearest rows, K up to 1024 ---------------------------------------------------------
+ * fir_search_topk's result for 1 <= k <= FIR_KNN_MAX (else FIR_ERR_ARG, "k=%d outside [1,1024]"): per query the k smallest
+ * packed keys (orderable(distance bits) << 32) | uint32(row + row offset), ascending -- equal distances by ascending row --
+ * over features [start_pos, end_pos) (end_pos = 0: d), any metric. A row qualifies only if `dist < 100000.0f` is true (so NaN
+ * distances never do); unused slots -- k > n, an empty gallery, fewer than k qualifying rows -- hold FIR_KEY_NONE (idx -1,
+ * dist 100000). For k <= 8 the keys are fir_search_topk_keys_dev's bit for bit, and for any k the first k' keys are those of the
+ * k' call. idx and dist are [qb*k], both required. Arguments are checked in the order of the other searches (NULL, qb < 0, k,
+ * qb == 0: nothing to do, the range) before anything is allocated or queued.
+ * Form: per tile of up to 8 queries ONE exact gallery scan stores the tile's distances (fir_range_distances' pass and bits) in
+ * the handle's scratch, then a radix select over the 64-bit keys finds each query's k-th smallest key, and the keys up to it are
+ * sorted. Keys are unique (the row is part of them), so the k-th key names one row however many rows share its distance: the
+ * result is exact under ties and two calls return the same bytes. Device scratch: 4 bytes per row and query of ONE tile plus
+ * 130 KiB, whatever qb is (counted under `scratch` in fir_gallery_memory_bytes); when a tile of 8 cannot be had the tile is
+ * halved down to one query before the call fails with FIR_ERR_NOMEM. The select re-reads the stored distances, not the gallery:
+ * timed by its own event pair it is 14-20 % of store + select at 1M x 512 for k <= 256 and 32 % at k = 1024; at 100 000 x 512, where
+ * the scan of a tile takes 0.065 ms, it is 45-70 % (profiles/knn_select.txt). There is no candidate-list or matrix-core form for
+ * k > 8: every call pays one exact scan per 8 queries, so for k <= 8 and large batches fir_search_topk is the faster call.
+ * fir_gallery_last_dispatch does not describe these calls. With fir_profile_enable on, fir_profile_read returns two durations per
+ * tile of queries, in call order: the tile's store pass (query transposition + scan), then its select. */
+#define FIR_KNN_MAX 1024
+int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
+                   int32_t* idx, float* dist);
+/* Device-resident, asynchronous on `stream` (NULL: the handle's own), in the handle's call order like every *_dev call; never
+ * synchronises once its scratch is large enough. d_keys[qb*k] ascending per query, FIR_KEY_NONE for unused slots. */
+int fir_search_knn_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
+                            uint64_t* d_keys, void* stream);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
@@ -572,6 +599,12 @@ int fir_sharded_search_top1(fir_sharded* h, const float* queries, int32_t qb, in
                             int32_t* idx, float* dist);
 int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                             int32_t k, int32_t* idx, float* dist);
+/* fir_search_knn over the shards, 1 <= k <= FIR_KNN_MAX, idx and dist required: every shard produces its k keys with global rows
+ * (fir_search_knn_keys_dev), ncclAllGather, and for k > 8 the k smallest of each query's k x ranks gathered keys are taken by the
+ * same radix select the shards ran (the keys are orderable and unique); k <= 8 merges as fir_sharded_search_topk does. The keys
+ * are the unsharded handle's. Failure semantics, agreed buffer growth and the status element as for the other searches. */
+int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
+                           int32_t* idx, float* dist);
 /* Batched BruteForceClassifier::recognize (ImageTesting.cpp:58-71): class_out[qb] <- classNo of the nearest row or -1;
  * idx / dist may be NULL. Needs class labels. */
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
