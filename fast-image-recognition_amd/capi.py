@@ -89,6 +89,7 @@ SYMBOLS = [
     ("fir_gemm_search_top1_keys_dev", C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
     ("fir_gemm_search_topk_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gemm_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_gemm_search_knn_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gemm_search_few_keys_dev", C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
     ("fir_gemm_stats", C.c_int, [_vp, _i64p, _i64p]),
     ("fir_gemm_stats_ex", C.c_int, [_vp, _i64p]),
@@ -658,6 +659,10 @@ class GemmSearch:
         """Gallery.search_top_classes_keys_dev's keys and classes through the matrix cores; synchronises `stream` once."""
         _check(lib().fir_gemm_search_top_classes_keys_dev(self._h, _vp(q_ptr), qb, num_classes, k, _vp(keys_ptr), _vp(classes_ptr),
                                                           _vp(stream) if stream else None))
+
+    def search_knn_keys_dev(self, q_ptr, qb, k, keys_ptr, stream=None):
+        """Gallery.search_knn_keys_dev's keys for k <= GEMM_KNN_MAX through the matrix cores; k > 8 synchronises `stream` once."""
+        _check(lib().fir_gemm_search_knn_keys_dev(self._h, _vp(q_ptr), qb, k, _vp(keys_ptr), _vp(stream) if stream else None))
 
     def stats(self):
         o = (C.c_int64 * 3)()

@@ -80,7 +80,7 @@ struct fir_gallery {
     GalleryBuf<int32_t> didx;
     GalleryBuf<float> rowsum;     // chi-square nomination (kChi2Harm): per-row sums over [rs_start, rs_end) + their maximum (rowsum[n])
     FirBuf knn;                   // fir_search_knn: one query tile's stored distances + the select's control block (knn_plan)
-    FirBuf scratch[24];
+    FirBuf scratch[25];
     size_t scratch_bytes() const {
         size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
@@ -155,6 +155,10 @@ struct ScanScope {
     int groups = 0;
     int64_t group_stride = 0;
     bool quiet = false;
+    // the store scan over a row sample (knn_sample_bound_dev): `tiles` sample tiles in run_count runs of run_len, spread over run_slack more
+    // gallery tiles (ScanArgs::run_len, fir_kernels.h), run_rows rows of the gallery among them; tile_begin 0
+    int32_t run_len = 0, run_count = 0;
+    int64_t run_slack = 0, run_rows = 0;
 };
 const ScanScope kOnBehalf{0, 0, 0, 0, true};      // the whole gallery, quietly
 
@@ -413,6 +417,12 @@ ScanArgs scan_args(const fir_gallery* g, const ScanScope& scope, int32_t start, 
     a.waves = waves;
     a.nt = 1;
     a.cls = g->cls ? g->cls + tile0 * kTileRows : nullptr;
+    if (scope.run_len > 0) {
+        a.n = scope.run_rows;
+        a.run_len = scope.run_len;
+        a.run_count = scope.run_count;
+        a.run_slack = scope.run_slack;
+    }
     return a;
 }
 
@@ -426,14 +436,15 @@ struct ClassPass { const float* tau; int32_t num_classes; int32_t nq; bool tiles
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
 int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
-             int init_keys = 0, const ClassPass* cp = nullptr) {
-    // ny > 1 (top-1 kernels and the class-minimum scan only): ny consecutive query tiles of qb_tile queries in ONE launch
+             int init_keys = 0, const ClassPass* cp = nullptr, int live = 0) {
+    // ny > 1 (top-1 kernels, the class-minimum scan and the store scan only): ny consecutive query tiles of qb_tile queries in ONE launch;
+    // live > 0 (the store scan): the launch's live queries, the last tile may be part full -- query y * qb_tile + q goes to out + that * out_stride
     const int kk = g->dp4 * 4;
     float* qt = g->qt + (size_t)q0 * kk;
     if (!(cp && cp->tiles_ready)) {
         const int64_t total = std::max<int64_t>((int64_t)kk * qb_tile * ny, init_keys);
         const int blocks = (int)((total + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, cp ? cp->nq : qb_tile * ny,
+        hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, cp ? cp->nq : live > 0 ? live : qb_tile * ny,
                            g->d, g->dp4, qb_tile, qt, init_keys > 0 ? keys : nullptr, init_keys, g->range, next_serial(g));
     }
     const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g));
@@ -445,7 +456,7 @@ int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, co
     }
     int max_waves = max_waves_for(g, sk.fn, sk.lds_bytes);
     if (sk.fn_plain) max_waves = std::min(max_waves, max_waves_for(g, sk.fn_plain, sk.lds_bytes));
-    int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(g->tiles, max_waves, g->cus * 4);
+    int waves = g->waves_req > 0 ? std::min(g->waves_req, max_waves) : pick_waves(scope.run_len > 0 ? scope.tiles : g->tiles, max_waves, g->cus * 4);
     const int groups = epi == kEpiTop1 && scope.groups > 1 && g->metric != kL2 ? scope.groups : 0;
     if (groups) waves = std::max(4 * groups, waves / (4 * groups) * (4 * groups));      // a wave's tiles all belong to one group
     g->last_waves = waves;
@@ -456,7 +467,7 @@ int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, co
     a.keys = keys;
     a.out = out;
     a.out_stride = out_stride;
-    a.nq = qb_tile;
+    a.nq = live > 0 ? live : qb_tile;
     a.k = k;
     a.qt_stride = (int64_t)kk * qb_tile;
     a.range = g->range;
@@ -953,6 +964,47 @@ int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, i
     return FIR_OK;
 }
 
+// ---- the sample bound of the matrix-core form for 8 < K <= FIR_GEMM_KNN_MAX (fir_gemm_knn.h) ----
+// d_bound[q] = the exact K-th smallest reference distance of query q over the row sample of knn_sample_plan (fir_knn_select.h):
+// 100000 with fewer than K qualifying rows there. The arithmetic is the store pass's, over features [0, end): the bits
+// fir_range_distances returns. Queries go in groups whose stored distances fit kKnnSampleBytes of scratch slot 24 (and one launch's
+// query tiles); per group one transposition, ONE store pass over the sample -- every tile of 8 queries of the group a blockIdx.y, the
+// runs of the sample found by the kernel (ScanScope::run_len) -- and one select launch (k_knn_sample_kth, a workgroup per query).
+// Nothing grows with qb, nothing synchronises once the slot is large enough.
+int knn_sample_bound_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end, int32_t k, int div, float* d_bound, hipStream_t st) {
+    const KnnSamplePlan plan = knn_sample_plan(g->n, k, div, kKnnSampleBytes);
+    if (plan.rows < k) {                                     // (an empty gallery included) no bound
+        FIR_HIP(hipMemsetD32Async((hipDeviceptr_t)d_bound, 0x47C35000, (size_t)qb, st));      // 100000.0f
+        return FIR_OK;
+    }
+    const int group = std::min(std::min(plan.group, 8 * g->max_tiles_per_launch), (qb + 7) / 8 * 8);
+    void* p_dist = nullptr;
+    int rc;
+    if ((rc = fir_gallery_scratch_(g, 24, (size_t)group * plan.row_stride * sizeof(float), &p_dist))) return rc;
+    if ((rc = FIR_NEED(g->qt, (size_t)((group + 7) / 8 * 8) * g->dp4 * 4))) return rc;
+    float* dist = (float*)p_dist;
+    ScanScope sample = kOnBehalf;
+    sample.tiles = plan.tiles;
+    sample.run_len = (int32_t)plan.run_len;
+    sample.run_count = plan.nruns;
+    sample.run_slack = plan.slack;
+    sample.run_rows = plan.rows;
+    for (int g0 = 0; g0 < qb; g0 += group) {
+        const int ng = std::min(group, qb - g0);
+        // (a group of fewer than 8 queries -- a sample of more than 2M rows -- goes tile by tile, as range_dev sizes them)
+        for (int q0 = 0; q0 < ng;) {
+            const int tile = group >= 8 ? 8 : largest_pow2_le(ng - q0, 8), live = group >= 8 ? ng : tile;
+            if ((rc = run_pass(g, st, sample, kEpiStore, d_queries + (size_t)(g0 + q0) * g->d, 0, tile, 0, end, nullptr, dist + (size_t)q0 * plan.row_stride,
+                               plan.row_stride, 0, nullptr, (live + tile - 1) / tile, 0, nullptr, live)))
+                return rc;
+            q0 += live;
+        }
+        hipLaunchKernelGGL(k_knn_sample_kth, dim3(ng), dim3(kBlock), 0, st, (const float*)dist, plan.row_stride, plan.rows, k, d_bound + g0);
+        FIR_HIP(hipGetLastError());
+    }
+    return FIR_OK;
+}
+
 int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t step, float* d_out, hipStream_t st,
                   int32_t step2 = 0) {
     // step2 != 0: two sub-ranges, [start, start + step) and [start + step, end) with end - start - step == step2 (whole load groups both)
@@ -1160,7 +1212,7 @@ int fir_runtime_init_(int device) {
     return FIR_OK;
 }
 int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out) {
-    if (!g || !out || slot < 0 || slot >= 24) return fir_fail_(FIR_ERR_ARG, "bad scratch request");
+    if (!g || !out || slot < 0 || slot >= 25) return fir_fail_(FIR_ERR_ARG, "bad scratch request");
     FirBuf& s = g->scratch[slot];
     if (bytes > s.cap) {                                      // a quarter of headroom, a page at least
         const int rc = FIR_RESERVE(s, std::max<size_t>(bytes + bytes / 4, 4096));
@@ -1521,6 +1573,19 @@ int try_mfma_classes(fir_gallery* g, const float* d_queries, int32_t qb, int32_t
                      int32_t* d_classes, hipStream_t st) {
     if (!g->cls || !wants_mfma(g, qb, start, end, true)) return 1;
     return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, num_classes, k, d_keys, d_classes, st); });
+}
+// ... and for the K <= FIR_GEMM_KNN_MAX nearest rows of a host-pointer batch (fir_search_knn): the ranges and the caller's threshold of the
+// class form; by itself (kAutoMfmaQueries queries over kAutoMfmaRows rows) for 8 < K <= kAutoMfmaKnnMaxK: the largest measured K that was
+// at least 1.15 x store + select at 1 024 queries and not slower at 128, at 1M x 512 and at 100 000 x 512, together with every smaller
+// measured K (9, 16, 32, 64, 128, 256; profiles/knn_matrix_cores.txt: K = 256 is 1.56 x / 2.12 x at 128 / 1 024 queries over 1M rows and
+// 1.62 x / 5.76 x over 100 000; K = 9 9.2 x / 21 x and 3.7 x / 8.6 x). K <= 8 was not measured through this call: a caller's threshold only
+// (fir_search_topk is that call). Smaller galleries were not measured either: they stay with store + select unless the caller sets a threshold.
+constexpr int kAutoMfmaKnnMaxK = 256;
+int try_mfma_knn(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
+    if (k > FIR_GEMM_KNN_MAX) return 1;
+    if (g->large_batch_min < 0 && (k <= kKMax || k > kAutoMfmaKnnMaxK)) return 1;
+    if (!wants_mfma(g, qb, start, end, true)) return 1;
+    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_knn_keys_dev(m, d_queries, qb, k, d_keys, st); });
 }
 }  // namespace
 
@@ -1954,7 +2019,11 @@ int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t sta
     if ((rc = FIR_NEED(g->dkeys, (size_t)qb * k))) return rc;
     if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
     FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    if ((rc = knn_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream))) return rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    rc = try_mfma_knn(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream);
+    if (rc > 0) rc = knn_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream);
+    if (rc) return rc;
     return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
 }
 
@@ -1995,6 +2064,18 @@ int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int3
     GalleryCall call(g, stream);
     if (call.rc) return call.rc;
     return top_classes_dev(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, call.st, kOnBehalf, (sample_rows + kTileRows - 1) / kTileRows, d_bound);
+}
+
+// The sample bound of fir_gemm_search_knn_keys_dev (fir_internal.h), neither recorded nor timed.
+int fir_knn_sample_bound_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, int32_t sample_div, float* d_bound,
+                              void* stream) {
+    int32_t start_pos = 0;
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_bound != nullptr, [&] { return check_knn_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    if (g->metric != FIR_METRIC_L2) return fir_fail_(FIR_ERR_ARG, "the sample bound is an L2 distance");
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return knn_sample_bound_dev(g, d_queries, qb, end_pos, k, sample_div, d_bound, call.st);
 }
 
 int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t num_classes, int32_t k,

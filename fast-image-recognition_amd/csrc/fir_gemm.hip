@@ -30,6 +30,7 @@
 #include "../../include/fir_amd.h"
 #include "fir_internal.h"
 #include "fir_common.h"
+#include "fir_knn_select.h"
 
 namespace {
 
@@ -966,6 +967,8 @@ __global__ void k_gemm_fb_count(int* __restrict__ state, int count) {
     tot[1] += (unsigned long long)count;
 }
 
+#include "fir_gemm_knn.h"
+
 // rowmajor[row * d4 + c] = chunk c of row `row`: the re-rank's copy of the compared features. A row of the tiled gallery is d4
 // separate 16-byte pieces 1 KiB apart (~4x its size in 64-byte sectors per gather); here it is one contiguous run.
 __global__ void __launch_bounds__(256) k_gemm_untile(const float4* __restrict__ gal4, int64_t n, int dp4, int d4, float4* __restrict__ rowmajor) {
@@ -1480,8 +1483,11 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         // of at most kRerankLdsMax / 128 = 1152 float4, 18 448 bytes with the padding, and kRerankLdsMax holds seven of those and the query.
         const size_t row_bytes = (size_t)(m->dp4 + 1) * sizeof(float4);
         m->rerank_group = (int)std::min<size_t>(kRerankGroup, kRerankLdsMax / row_bytes - 1);
+        // (k_gemm_rerank_knn adds 3 KiB of static LDS -- its histogram and sorted keys -- to the request: 147 KiB of the CU's 160 at most)
+        static_assert(kRerankLdsMax + 256 * sizeof(unsigned) + fir::kKnnGemmMax * sizeof(unsigned long long) <= 160 * 1024, "k_gemm_rerank_knn's LDS");
         if (gemm_rerank_lds_(m) > 48 * 1024)
-            for (const void* fn : {(const void*)k_gemm_rerank<1>, (const void*)k_gemm_rerank<kTopKMax>, (const void*)k_gemm_rerank_classes})
+            for (const void* fn : {(const void*)k_gemm_rerank<1>, (const void*)k_gemm_rerank<kTopKMax>, (const void*)k_gemm_rerank_classes,
+                                   (const void*)k_gemm_rerank_knn})
                 if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
     if (e == hipSuccess && f16) e = gemm_x_lds_attr_();
@@ -1647,6 +1653,8 @@ struct GemmCall {
     uint64_t* d_keys;
     int32_t num_classes;        // > 0: the K nearest distinct CLASSES (fir_gemm_search_top_classes_keys_dev) -- a bound from a row sample's class
     int32_t* d_classes;         // minima, the append pass below it, k_gemm_rerank_classes; d_keys or d_classes may then be NULL
+    bool knn = false;           // the K > kTopKMax nearest rows (fir_gemm_search_knn_keys_dev, fir_gemm_knn.h): the same flow with the bound from
+    int knn_div = fir::kKnnSampleDiv;   // a row sample's exact K-th distance (rows n K / knn_div: FIR_GEMM_KNN_SAMPLE_DIV) and k_gemm_rerank_knn
     hipStream_t st;
     int d, qs;                  // features compared; floats between consecutive queries (and gallery rows): the whole row
     int64_t n;
@@ -1733,7 +1741,7 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
             if ((int64_t)m->i8_pin[0] * 16 > (int64_t)m->i8_pending_qb) { m->i8_off = true; m->i8_off_why = "second passes"; }
         } else if (eq == hipErrorNotReady) (void)hipGetLastError();     // (not an error: the counter is looked at by a later call)
     }
-    if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.k != 1 || c.num_classes > 0 || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
+    if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.k != 1 || c.num_classes > 0 || c.knn || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
         c.qb <= 32 || (m->dbg_skip && m->i8_mode != 1))        // (the timing forms reach int8 only where the handle asks for int8 outright)
         return FIR_OK;
     if (m->i8_mode < 0 && (kI8AutoMinQueries <= 0 || c.qb < kI8AutoMinQueries)) return FIR_OK;
@@ -1769,6 +1777,7 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
 static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
     if (m->precision != FIR_GEMM_F16 || m->adaptive <= 0 || (c.k > 1 && !m->adaptive_topk)) return false;
     if (c.num_classes > 0) return false;                                // (a bound on the K-th CLASS is not a row order statistic: the sample flow)
+    if (c.knn) return false;                                            // (K slot minima per query stop at kTopKMax: the sample flow, fir_gemm_knn.h)
     if (m->adaptive > 1 || c.k == 1) return true;                       // FIR_GEMM_ADAPTIVE=2: always
     const int pairs_sb = ((nq_sb + kQT - 1) / kQT + 1) / 2;
     const int P = launch_pairs_(pairs_sb, c.streamed ? kShareStreamed : kShareMax);
@@ -1875,6 +1884,14 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
         // profiles/class_rank_matrix_cores.txt), turned into the append pass's bound in place; padding queries get -inf
         const int64_t rows = std::min<int64_t>(c.n, std::max<int64_t>(kClassSampleRows, c.n * k / m->class_sample_div));
         const int rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.num_classes, k, rows, nullptr, nullptr, s.tau, ps);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
+        return FIR_OK;
+    }
+    if (c.knn) {
+        // D_s = the exact K-th smallest distance over a row sample spread over the gallery (fir_knn_select.h: knn_sample_plan), turned into
+        // the append pass's bound in place; padding queries get -inf
+        const int rc = fir_knn_sample_bound_dev_(m->g, dq, nq, c.d, k, c.knn_div, s.tau, ps);
         if (rc) return rc;
         hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
         return FIR_OK;
@@ -2025,8 +2042,9 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
                                (pairs + (np - 2 * pairs)) * ((double)((n + 31) / 32) * m->dk16 * 2048.0), 2.0 * (double)n * c.d * 64.0 * np);
 }
 
-// exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list
-static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
+// exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list. A launch the runtime refuses is the
+// call's error: the flags and keys of this super-batch would otherwise be whatever an earlier call left.
+static int gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
     const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
     GemmScratch& s = m->set[b];
     if (c.num_classes > 0)
@@ -2034,9 +2052,14 @@ static void gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs)
                            m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
                            c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
                            c.qs, m->rowmajor);
+    else if (c.knn)
+        hipLaunchKernelGGL(k_gemm_rerank_knn, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, m->gal4, c.sb_first(sb), s.qnorm, m->gmax, c.n,
+                           c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k, (unsigned long long*)c.d_keys + (size_t)q0 * c.k, m->ok + q0, c.qs, m->rowmajor);
     else
         gemm_launch_rerank_(m, rs, nq, gemm_slot_(m, s, c.i8), c.sb_first(sb),
                             c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0, {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
 }
 
 #ifdef FIR_AUDIT
@@ -2105,13 +2128,34 @@ static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
     return FIR_OK;
 }
 
+// ... and of a K > kTopKMax nearest-rows call (fir_gemm_knn.h): the same, through the store + select form of fir_search_knn_keys_dev
+static int gemm_finish_knn_(fir_gemm* m, const GemmCall& c) {
+    std::vector<int> h_ok((size_t)c.qb);
+    FIR_HIP(hipMemcpyAsync(h_ok.data(), m->ok, (size_t)c.qb * sizeof(int), hipMemcpyDeviceToHost, c.st));
+    FIR_HIP(hipStreamSynchronize(c.st));
+    int uncertified = 0;
+    for (int q0 = 0; q0 < c.qb;) {
+        int q1 = q0;
+        while (q1 < c.qb && !h_ok[q1]) ++q1;
+        if (q1 == q0) { ++q0; continue; }
+        const int rc = fir_search_knn_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.k, c.d_keys + (size_t)q0 * c.k, c.st);
+        if (rc) return rc;
+        uncertified += q1 - q0;
+        q0 = q1;
+    }
+    if (uncertified) hipLaunchKernelGGL(k_gemm_fb_count, dim3(1), dim3(1), 0, c.st, m->fb_state, uncertified);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+
 // The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev), or -- num_classes > 0 --
 // the K <= 32 nearest distinct classes (fir_gemm_search_top_classes_keys_dev, which checks its own arguments)
 static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr,
-                       int32_t num_classes = 0, int32_t* d_classes = nullptr) {
+                       int32_t num_classes = 0, int32_t* d_classes = nullptr, bool knn = false) {
     if (!m || (!d_keys && !(num_classes > 0 && d_classes)) || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    if (k < 1 || k > (num_classes > 0 ? 32 : kTopKMax)) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, num_classes > 0 ? 32 : kTopKMax);
+    const int k_max = num_classes > 0 ? 32 : knn ? fir::kKnnGemmMax : kTopKMax;
+    if (k < 1 || k > k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, k_max);
     if (qb == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
@@ -2120,9 +2164,13 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     GemmCall c;
     c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
     c.num_classes = num_classes; c.d_classes = d_classes;
+    c.knn = knn;
+    if (knn)
+        if (const char* w = fir_knob_("FIR_GEMM_KNN_SAMPLE_DIV")) c.knn_div = std::max(1, std::atoi(w));
     c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
     if (c.n == 0 && h_queries) FIR_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
     if (c.n == 0 && num_classes > 0) return fir_class_scan_dev_(m->g, d_queries, qb, c.d, num_classes, k, 0, d_keys, d_classes, nullptr, st);   // every slot unused
+    if (c.n == 0 && knn) return fir_search_knn_keys_dev(m->g, d_queries, qb, 0, c.d, k, d_keys, st);                                      // every slot FIR_KEY_NONE
     if (c.n == 0)
         return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
                       : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
@@ -2170,7 +2218,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
         // on the side stream, the re-rank runs under the next super-batch's full passes
         hipStream_t rs = c.one_stream ? st : m->side;
         if (!c.one_stream) FIR_HIP(hipStreamWaitEvent(m->side, m->main_done[b], 0));
-        gemm_rerank_(m, c, sb, rs);
+        if ((rc = gemm_rerank_(m, c, sb, rs))) return rc;
         gemm_audit_mark_(m, 3, rs);
         FIR_HIP(hipEventRecord(m->rerank_done[b], rs));
         m->passes += (c.sb_queries(sb) + kQT - 1) / kQT;
@@ -2182,6 +2230,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
     if (num_classes > 0) return gemm_finish_classes_(m, c);
+    if (knn) return gemm_finish_knn_(m, c);
     // uncertified queries: a second matrix-core pass with the tightest bound the first one can justify, then the exact device scan
     // (calls of at most 32 queries skip the second-chance rounds: the exact device scan reads the gallery once per eight queries, about what
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
@@ -2222,6 +2271,18 @@ int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, in
     if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
     if (qb == 0) return FIR_OK;
     return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, num_classes, d_classes);
+}
+
+// K <= kTopKMax: the top-1 / top-K forms as they are (they do not synchronise); beyond it the sample flow of fir_gemm_knn.h, which
+// synchronises `stream` once
+int fir_gemm_search_knn_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream) {
+    if (!m || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (k < 1 || k > FIR_GEMM_KNN_MAX) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, FIR_GEMM_KNN_MAX);
+    if (k <= kTopKMax) return gemm_search(m, d_queries, qb, k, d_keys, stream);
+    if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the K > %d nearest-rows form needs a FIR_GEMM_F16 state", kTopKMax);
+    if (qb == 0) return FIR_OK;
+    return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, 0, nullptr, true);
 }
 
 // 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one

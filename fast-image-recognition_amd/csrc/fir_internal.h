@@ -95,10 +95,10 @@ extern "C" void fir_set_last_error_(const char* msg);    // a message kept aside
 extern "C" const char* fir_knob_(const char* name);
 extern "C" int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4);   // the tiled f32 gallery (fir_kernels.h layout)
 
-// Device scratch owned by the gallery handle: `slot` in [0, 24), grown on demand, kept until the gallery is destroyed
+// Device scratch owned by the gallery handle: `slot` in [0, 25), grown on demand, kept until the gallery is destroyed
 // (the per-call hipMalloc / hipFree pairs of the classifier entry points cost more than their kernels on small galleries).
 // Slots 0-7 and 16: fir_twd.hip (0 queries, 1 conventional distance tables, 2 k_twd_prop_fused state, 3 verdicts, 4-6 proposed chunk
-// distances / sums / alive flags, 7 segment records of either staged form, 16 k_twd_conv_fused state), 8-11: fir_dem.hip, 12-15, 17, 18 and 23: fir_capi.hip (17, 18: top_classes_dev; 23: label range);
+// distances / sums / alive flags, 7 segment records of either staged form, 16 k_twd_conv_fused state), 8-11: fir_dem.hip, 12-15, 17, 18, 23 and 24: fir_capi.hip (17, 18: top_classes_dev; 23: label range; 24: knn_sample_bound_dev);
 // 19-22: fir_twd.hip's matrix-core batch form (fir_twd_batch.h: 19 the chunk's queries, 20 the unreliable queries' vectors, 21 keys and classes, 22 flags and lists).
 extern "C" int fir_gallery_scratch_(fir_gallery* g, int slot, size_t bytes, void** out);
 // Per-handle call counters of the other translation units (slot 0: fir_twd.hip's fused classifier): returns the value before the increment.
@@ -146,6 +146,14 @@ extern "C" int fir_search_topk_exact_keys_dev_(fir_gallery* g, const float* d_qu
 // classes qualify there: a minimum over a subset of the rows, so an upper bound of the gallery's K-th class distance.
 extern "C" int fir_class_scan_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t num_classes, int32_t k,
                                    int64_t sample_rows, uint64_t* d_keys, int32_t* d_classes, float* d_bound, void* stream);
+
+// The sample bound of fir_gemm_search_knn_keys_dev (fir_gemm_knn.h) over features [0, end_pos), L2 galleries: d_bound[q] = the exact
+// K-th smallest reference distance of query q -- the store pass's arithmetic, the bits fir_range_distances returns -- over the row
+// sample of knn_sample_plan(n, k, sample_div) (fir_knn_select.h), 100000 when fewer than K rows qualify there: an order statistic of
+// a subset of the rows, so an upper bound of the gallery's K-th distance whatever the sample is. Not recorded as the handle's
+// dispatch, not timed; asynchronous on `stream` once scratch slot 24 is large enough.
+extern "C" int fir_knn_sample_bound_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t end_pos, int32_t k, int32_t sample_div,
+                                         float* d_bound, void* stream);
 
 // The matrix-core steps of fir_twd_conventional's batch form (fir_twd.hip), on a prefix [0, end_pos) of the rows (end_pos == d: the
 // whole-row state; the handle's two prefix slots hold the others).

@@ -63,9 +63,9 @@ struct ScanArgs {
     int32_t waves;        // total waves in the grid
     int64_t row_offset;   // global index of local row 0
     uint64_t* keys;       // kEpiTop1: [QB] packed keys (pre-set to kKeyNone); kEpiTopK: partials [waves][QB][K]
-    float* out;           // kEpiStore: out[q * out_stride + row]
+    float* out;           // kEpiStore: out[(blockIdx.y * QB + q) * out_stride + row]
     int64_t out_stride;
-    int32_t nq;           // live queries in this tile (<= QB); only kEpiStore needs it
+    int32_t nq;           // kEpiStore: live queries of the launch (the last tile of QB may be part full)
     int32_t k;            // kEpiTopK
     int64_t qt_stride;    // floats between the query tiles of consecutive blockIdx.y (top-1 kernels)
     int32_t nt;           // non-temporal gallery loads (galleries that do not fit the L2s)
@@ -86,6 +86,9 @@ struct ScanArgs {
     const int32_t* cls;   // kEpiClassMin: class label of every row of this scan; keys = cmin[query][class], the smallest key of each class so far
     int32_t num_classes;  // (pre-set to kKeyNone; rows labelled outside [0, num_classes) take no part); nq = live queries of the launch;
                           // tau (may be NULL) = per query, the distance above which a row cannot be among the answer's classes
+    int32_t run_len;      // k_scan, kEpiStore, > 0: the scan's `tiles` tiles are a row SAMPLE -- run_count runs of run_len consecutive tiles (the last
+    int32_t run_count;    // one may be shorter), run i moved up by floor(i * run_slack / run_count) tiles: sample tile t is gallery tile
+    int64_t run_slack;    // t + floor((t / run_len) * run_slack / run_count), stored at row 64 t + lane; n = rows of the sample (knn_sample_plan)
 };
 
 template <int QB, int METRIC, int U>
@@ -250,7 +253,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     // blockIdx.y = query tile (top-1, append and class-minimum forms): several tiles of QB queries share one launch
-    const float* qsrc = a.qt + (EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin ? (size_t)blockIdx.y * a.qt_stride : 0);
+    const float* qsrc = a.qt + (EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin || EPI == kEpiStore ? (size_t)blockIdx.y * a.qt_stride : 0);
     extern __shared__ __attribute__((aligned(16))) float lds_q[];
     if constexpr (LDSQ) {
         const int nf = a.dp4 * 4 * QB;
@@ -293,7 +296,11 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     const int c_end = c_lo + ng * U;
 
     for (int t = gw; t < a.tiles; t += a.waves) {
-        const float4* tile = a.gal4 + (size_t)t * a.dp4 * 64 + lane;
+        int64_t gt = t;                                              // the gallery tile of scan tile t
+        if constexpr (EPI == kEpiStore) {
+            if (a.run_len > 0) gt += (int64_t)(t / a.run_len) * a.run_slack / a.run_count;
+        }
+        const float4* tile = a.gal4 + (size_t)gt * a.dp4 * 64 + lane;
         float acc[QB];
 #pragma unroll
         for (int q = 0; q < QB; ++q) acc[q] = 0.0f;
@@ -388,7 +395,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                         if (slot < a.k) a.keys[qy * a.k + slot] = key_pack(dist, (uint32_t)(row + a.row_offset));
                     }
                 } else {
-                    if (q < a.nq) a.out[(size_t)q * a.out_stride + row] = dist;
+                    if ((int)blockIdx.y * QB + q < a.nq) a.out[((size_t)blockIdx.y * QB + q) * a.out_stride + row] = dist;
                 }
             }
         }

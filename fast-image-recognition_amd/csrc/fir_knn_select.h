@@ -56,6 +56,56 @@ inline int largest_pow2_le(int x, int cap) {
     return p;
 }
 
+// ---- the row sample of the matrix-core form (fir_gemm_search_knn_keys_dev, fir_gemm_knn.h) ----
+// The exact K-th smallest distance over a row sample is an upper bound of the gallery's K-th distance whatever the sample is (a
+// subset of the rows); only how many rows the append pass lists below it depends on the choice. R = min(n, max(kKnnSampleFloor,
+// n K / div)) rows in whole 64-row tiles, taken as up to kKnnSampleRuns runs of consecutive tiles spread evenly over the gallery:
+// the reference's galleries are class-major, a leading sample would know nothing of the later classes. Run i holds sample tiles
+// [i run_len, (i + 1) run_len) -- the last run may be shorter -- and starts floor(i slack / nruns) tiles further up in the gallery,
+// slack = the gallery's tiles outside the sample: sample tile t is gallery tile t + floor((t / run_len) slack / nruns), which is
+// what the store scan computes (ScanArgs::run_len, fir_kernels.h). The runs ascend and do not overlap.
+constexpr int kKnnGemmMax = 256;                        // FIR_GEMM_KNN_MAX
+constexpr int kKnnSampleRuns = 16;
+constexpr int64_t kKnnSampleFloor = 32768;
+constexpr int kKnnSampleDiv = 1024;                     // FIR_GEMM_KNN_SAMPLE_DIV replaces it for experiments
+constexpr size_t kKnnSampleBytes = (size_t)64 << 20;    // stored sample distances of one group of queries at most
+struct KnnSamplePlan {
+    int64_t tiles;                          // sample tiles: the runs' tiles sum to it
+    int64_t rows;                           // rows of the gallery among them: the sample tiles are full except, when the last run ends with
+                                            // the gallery, the last one -- only the LAST positions of a query's stored distances can be missing
+    int64_t run_len;                        // tiles per run (the last run: what is left)
+    int64_t slack;                          // gallery tiles outside the sample
+    int nruns;
+    int64_t row_stride;                     // floats from one query's stored distances to the next: tiles * 64
+    int group;                              // queries whose stored distances fit `budget` bytes: at least 1, whole eights from 8 on
+    int64_t run_begin(int i) const { return i * run_len + i * slack / nruns; }                              // first gallery tile of run i
+    int64_t run_tiles(int i) const { return i + 1 < nruns ? run_len : tiles - (int64_t)(nruns - 1) * run_len; }
+};
+inline KnnSamplePlan knn_sample_plan(int64_t n, int32_t k, int div, size_t budget) {
+    KnnSamplePlan p{};
+    if (n < 0) n = 0;
+    if (k < 1) k = 1;
+    if (div < 1) div = 1;
+    const int64_t gallery_tiles = (n + 63) / 64;
+    int64_t want = n / div * k + n % div * k / div;       // n k / div without leaving 64 bits
+    if (want < kKnnSampleFloor) want = kKnnSampleFloor;
+    if (want > n) want = n;
+    p.tiles = (want + 63) / 64;
+    p.run_len = (p.tiles + kKnnSampleRuns - 1) / kKnnSampleRuns;
+    p.nruns = p.run_len > 0 ? (int)((p.tiles + p.run_len - 1) / p.run_len) : 0;
+    p.slack = gallery_tiles - p.tiles;
+    p.rows = p.tiles * 64;
+    if (p.nruns > 0 && p.run_begin(p.nruns - 1) + p.run_tiles(p.nruns - 1) == gallery_tiles) p.rows -= gallery_tiles * 64 - n;
+    p.row_stride = p.tiles * 64;
+    const size_t per_query = (size_t)(p.row_stride > 0 ? p.row_stride : 64) * sizeof(float);
+    size_t group = budget / per_query;
+    if (group < 1) group = 1;
+    if (group > 8192) group = 8192;
+    if (group >= 8) group = group / 8 * 8;
+    p.group = (int)group;
+    return p;
+}
+
 }  // namespace fir
 
 #ifndef FIR_KNN_HOST_ONLY
@@ -116,6 +166,50 @@ __device__ inline SelState sel_advance(SelState s, unsigned count, int pass, uns
     s = *box;
     __syncthreads();
     return s;
+}
+
+// ---- the K-th smallest of a row of stored distances: the sample bound of the matrix-core form ----
+// One workgroup per query (k_dem_select_one's shape), one launch for all queries of a group: bound[q] = the K-th smallest of
+// dist[q * stride + i], i < rows, among the distances that qualify (dist < 100000), 100000 with fewer than K of them. Only the
+// distance is wanted, not the row: four digits over the 32-bit orderable distance. A digit whose bin the rank takes whole does not
+// end the select (sel_advance's `done` fills the lower digits with ones: a key at or above the K-th, not the K-th itself).
+// stride is a multiple of 4 and dist 16-byte aligned.
+static __global__ void __launch_bounds__(kBlock) k_knn_sample_kth(const float* __restrict__ dist, int64_t stride, int64_t rows, int32_t k,
+                                                                   float* __restrict__ bound) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wsum[kBlock / 64];
+    __shared__ SelState box;
+    const int q = blockIdx.x;
+    if (rows < k) {                                                      // (uniform) a rank outside the histogram
+        if (threadIdx.x == 0) bound[q] = kNotFound;
+        return;
+    }
+    const float* __restrict__ row = dist + (size_t)q * stride;
+    SelState s{0ull, k, 0};
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 56 - 8 * pass;
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (int64_t i0 = 0; i0 < rows; i0 += 4 * kBlock) {
+            const int64_t i = i0 + 4 * (int64_t)threadIdx.x;
+            float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (i < rows) v = *(const float4*)(row + i);                 // i + 3 < stride: both are multiples of 4
+            const float d4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const bool valid = i + c < rows;
+                const uint64_t key = valid && d4[c] < kNotFound ? (uint64_t)f32_orderable(d4[c] + 0.0f) << 32 : kKeyNone;
+                hist_add(hist, valid && sel_match(key, s.prefix, pass), (unsigned)(key >> shift) & 255u);
+            }
+        }
+        __syncthreads();
+        s = sel_advance(s, hist[threadIdx.x], pass, wsum, &box);
+        if (s.done) { s.prefix &= ~((1ull << shift) - 1); s.done = 0; }  // the bin taken whole: its digit is decided, the rest is not
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t o = (uint32_t)(s.prefix >> 32);
+        bound[q] = o == 0xFFFFFFFFu ? kNotFound : f32_from_orderable(o);
+    }
 }
 
 // ---- the K smallest keys of each of nq rows of keys ----------------------------------------------------------------------------

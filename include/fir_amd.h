@@ -181,10 +181,21 @@ int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t p
  * 130 KiB, whatever qb is (counted under `scratch` in fir_gallery_memory_bytes); when a tile of 8 cannot be had the tile is
  * halved down to one query before the call fails with FIR_ERR_NOMEM. The select re-reads the stored distances, not the gallery:
  * timed by its own event pair it is 14-20 % of store + select at 1M x 512 for k <= 256 and 32 % at k = 1024; at 100 000 x 512, where
- * the scan of a tile takes 0.065 ms, it is 45-70 % (profiles/knn_select.txt). There is no candidate-list or matrix-core form for
- * k > 8: every call pays one exact scan per 8 queries, so for k <= 8 and large batches fir_search_topk is the faster call.
- * fir_gallery_last_dispatch does not describe these calls. With fir_profile_enable on, fir_profile_read returns two durations per
- * tile of queries, in call order: the tile's store pass (query transposition + scan), then its select. */
+ * the scan of a tile takes 0.065 ms, it is 45-70 % (profiles/knn_select.txt). Every call in this form pays one exact scan per 8
+ * queries whatever the batch size.
+ * Matrix-core form: an L2 batch with k <= FIR_GEMM_KNN_MAX over features [0, end_pos) -- whole rows, or a prefix with end_pos % 16 == 0
+ * and end_pos >= 64 -- goes through fir_gemm_search_knn_keys_dev (same keys, see there) as fir_search_top_classes routes its batches:
+ * with fir_gallery_set_large_batch_mfma(g, min_queries > 0) from the caller's threshold on, at any gallery size; never with threshold
+ * 0 or FIR_SHADOW_NONE; by itself for 8 < k <= 256 from 128 queries over >= 65536 rows on, as for classes -- every measured k
+ * (9 .. 256) was at least 1.15 x store + select at 1 024 queries and not slower at 128, at 1M x 512 (128 / 1 024 / 8 192 queries:
+ * k = 9 9.2 / 21 / 23 x, k = 64 4.7 / 10 / 11 x, k = 256 1.6 / 2.1 / 2.2 x) and at 100 000 x 512 (k = 9 3.7 / 8.6 / 8.4 x, k = 256
+ * 1.6 / 5.8 / 5.6 x; profiles/knn_matrix_cores.txt). Such a call synchronises the handle's stream once more than store + select
+ * does and costs the fp16 gallery copy (n*d*2 bytes, created on first use). fir_search_knn_keys_dev and fir_sharded_search_knn
+ * always keep the store + select form.
+ * fir_gallery_last_dispatch does not describe a store + select call; a routed call it describes as it does a routed class call
+ * (path mfma, the f16x<1, ...> append pass). With fir_profile_enable on, fir_profile_read returns two durations per tile of queries,
+ * in call order -- the tile's store pass (query transposition + scan), then its select -- for the store + select form only; a
+ * routed call leaves the append pass's launches (and the two-per-tile pairs of whatever queries it could not certify). */
 #define FIR_KNN_MAX 1024
 int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                    int32_t* idx, float* dist);
@@ -495,6 +506,18 @@ int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t q
  * out[2]). fir_search_top_classes routes batches here under fir_gallery_set_large_batch_mfma's rule (see there). */
 int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t num_classes, int32_t k,
                                          uint64_t* d_keys, int32_t* d_classes, void* stream);
+/* The keys of fir_search_knn_keys_dev, bit for bit, for the feature range the state covers (whole rows or its prefix), through the
+ * matrix cores: 1 <= k <= FIR_GEMM_KNN_MAX (else FIR_ERR_ARG, "k=%d outside [1,256]"); d_keys[q * k + r] ascending, FIR_KEY_NONE for
+ * unused slots (an empty gallery: every slot). k <= 8 is the top-1 / top-K call above as it is: it does not synchronise. k > 8 needs
+ * a FIR_GEMM_F16 state (else FIR_ERR_ARG) and SYNCHRONISES `stream` once, like the class call: the exact k-th smallest distance over
+ * a row sample -- min(n, max(32768, n k / 1024)) rows in 16 runs spread over the gallery (FIR_GEMM_KNN_SAMPLE_DIV replaces the 1024 for
+ * experiments; any sample is sound) -- bounds the k-th distance from above; the fp16 pass appends every row below that bound (plus one
+ * rounding window); the re-rank re-computes every entry within a window of the k-th smallest proxy in the reference's arithmetic,
+ * returns the k smallest exact keys and certifies against the k-th exact distance. Queries that were not certified (more than 4096
+ * rows below the bound, NaN, a tie at the certificate's bound) are answered by the store + select form, straight into their slots
+ * (fir_gemm_stats_ex counts them in out[1] and out[2]). Argument checks in the order of the other fir_gemm_search_* calls. */
+#define FIR_GEMM_KNN_MAX 256
+int fir_gemm_search_knn_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream);
 /* fir_search_top1 and fir_search_top1_keys_dev send L2 whole-range batches through this path BY DEFAULT when the batch
  * has >= 128 queries and the gallery >= 65536 rows (smaller, cache-resident galleries: where a cost model of the two forms gives the
  * matrix cores 15 % or more -- e.g. 128 queries against 40 000 x 512, 1 024 against 8 192 x 512 --, from the gallery's fourth such
