@@ -79,9 +79,31 @@ struct FirBuf {
     }
     template <typename T> T* as() const { return (T*)p; }
 };
+// The same for pinned host memory (hipHostMalloc with the flags the buffer was made with): the staging areas and status
+// blocks of fir_shard.hip.
+struct FirPinBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    unsigned flags = hipHostMallocPortable;
+    FirPinBuf() = default;
+    explicit FirPinBuf(unsigned flags_) : flags(flags_) {}
+    FirPinBuf(const FirPinBuf&) = delete;
+    FirPinBuf& operator=(const FirPinBuf&) = delete;
+    ~FirPinBuf() { release(); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t bytes) {
+        if (p && bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes, flags);
+        if (e == hipSuccess) cap = bytes; else p = nullptr;
+        return e;
+    }
+    template <typename T> T* as() const { return (T*)p; }
+};
 // FIR_RESERVE(buffer, bytes): buffer.reserve(bytes) as a return code on the library's error path -- FIR_ERR_NOMEM when the device
 // has no memory left, FIR_ERR_HIP otherwise --, the message naming the buffer and the place of the call as FIR_HIP's does.
-inline int fir_reserve_(FirBuf& b, size_t bytes, const char* what, const char* file, int line) {
+template <typename Buf>
+int fir_reserve_(Buf& b, size_t bytes, const char* what, const char* file, int line) {
     const hipError_t e = b.reserve(bytes);
     if (e == hipSuccess) return FIR_OK;
     return fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "%s.reserve(%zu) failed: %s (%s:%d)", what, bytes, hipGetErrorString(e), file, line);

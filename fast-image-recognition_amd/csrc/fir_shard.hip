@@ -38,7 +38,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -52,6 +51,7 @@
 #include "fir_common.h"
 #include "fir_internal.h"
 #include "fir_knn_select.h"
+#include "fir_shard_workers.h"
 
 namespace {
 
@@ -143,35 +143,7 @@ __global__ void __launch_bounds__(256) k_shard_fill_u64(uint64_t* p, int n, uint
     if (i < n) p[i] = v;
 }
 
-struct Worker {       // one thread per device of a multi-device handle: its launches and its RCCL calls
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::function<int()> job;
-    bool has_job = false, done = false, quit = false;
-    int rc = 0;
-    char err[512] = "";
-    void loop() {
-        for (;;) {
-            std::function<int()> j;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return has_job || quit; });
-                if (quit) return;
-                j = job;
-                has_job = false;
-            }
-            const int r = j();
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                rc = r;
-                if (r) { strncpy(err, fir_last_error(), sizeof(err) - 1); err[sizeof(err) - 1] = 0; }
-                done = true;
-            }
-            cv.notify_all();
-        }
-    }
-};
+using fir::KeptError;
 
 struct Shard {
     int slot = 0;              // index into devs
@@ -184,22 +156,32 @@ struct DevCtx {
     int device = 0;
     hipStream_t stream = nullptr;
     ncclComm_t comm = nullptr;
-    float* dq = nullptr;        size_t dq_cap = 0;
-    uint64_t* parts = nullptr;  size_t parts_cap = 0;     // [shards here][qb * k]
-    uint64_t* keys = nullptr;   size_t keys_cap = 0;      // [qb * k] reduced
-    uint64_t* gath = nullptr;   size_t gath_cap = 0;      // [nranks][qb * k]
-    int32_t* cls = nullptr;     size_t cls_cap = 0;
-    uint64_t* sel = nullptr;    size_t sel_cap = 0;       // the control block of the K > 8 merge (fir_knn_select.h: KnnCtl)
+    FirBuf dq;                                            // float: the queries of a host-pointer call
+    FirBuf parts;                                         // uint64_t [shards here][qb * k]
+    FirBuf keys;                                          // uint64_t [qb * k] reduced
+    FirBuf gath;                                          // uint64_t [nranks][qb * k]
+    FirBuf cls;                                           // int32_t: the winners' classes
+    FirBuf sel;                                           // the control block of the K > 8 merge (fir_knn_select.h: KnnCtl)
     std::vector<int> shards;
-    Worker* worker = nullptr;
     std::vector<hipEvent_t> evs;                          // pairs around the RCCL calls (profiling, device slot 0)
     size_t ev_used = 0;
-    int32_t* status = nullptr;                            // device: [0] the agreed-growth word, [1] sticky status of the asynchronous calls
-    int32_t* h_status = nullptr;                          // pinned host: [0] what this rank contributes, [1] what came back, [2] sticky read-back,
+    FirBuf status;                                        // int32_t: [0] the agreed-growth word, [1] sticky status of the asynchronous calls
+    FirPinBuf h_status{hipHostMallocPortable | hipHostMallocMapped};   // int32_t: [0] what this rank contributes, [1] what came back, [2] sticky read-back,
                                                           // [3] the sticky status as the device mirrors it (k_shard_note_status), [4..5] a double (fir_cls_sharded)
     int32_t* d_hsticky = nullptr;                         // device address of h_status[3]
     hipEvent_t async_done = nullptr;                      // behind the last asynchronous device-pointer call, on the stream it ran on
     bool async_pending = false;                           // ... whose status nobody has looked at yet
+    int32_t* dstat() const { return status.as<int32_t>(); }
+    int32_t* hstat() const { return h_status.as<int32_t>(); }
+};
+
+// The devices of a handle and, when it lists several, their worker threads. setup_devices makes what is in here and
+// teardown_devices is the one place that releases it: stream, communicator, status words, events, buffers, workers.
+struct Devices {
+    std::vector<DevCtx> ctx;
+    fir::Workers workers;
+    DevCtx& operator[](int slot) { return ctx[(size_t)slot]; }
+    int run_all(const std::function<int(int)>& fn) { return workers.run_all(fn); }
 };
 
 // What the ranks of a handle have to agree on to stay out of each other's way (see "Failure semantics" above).
@@ -209,24 +191,30 @@ struct Health {
     int timeout_ms = 120000;         // bound of every wait behind a collective
     int fail_shard = 0;              // test hook: 1-based local shard whose step fails, 0 = none
     int fail_step = 0;               // 1 = its scan (after the agreed growth), 2 = its device's buffer growth
+    int exchanges_done = 0;          // (audit build's fail_step = 3)
     void apply(const fir_shard_opts& o) {
         if (o.timeout_ms > 0) timeout_ms = o.timeout_ms;
         fail_shard = o.fail_shard;
         fail_step = o.fail_step;
     }
+    // The handle is dead from here on. The first code stays: every call starts on a live handle, so a later close() of the same
+    // call (another device's, or the caller's after run_all) speaks of the same failure.
+    int close(int code) {
+        int none = 0;
+        dead_code.compare_exchange_strong(none, code);
+        dead = true;
+        return code;
+    }
 };
 
-template <typename T>
-int grow_dev(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return FIR_OK;
-    if (p) FIR_HIP(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(need, 1024);
-    FIR_HIP(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    return FIR_OK;
+// buffer.reserve with the size rule of its call site: nothing when `bytes` fit (no bytes always fit), else a fresh block of
+// max(bytes, floor) -- asked for by what the call needs, never by what a block happens to hold beyond it.
+template <typename Buf>
+int grow_buf(Buf& b, size_t bytes, size_t floor, const char* what, int line) {
+    if (bytes <= b.cap) return FIR_OK;
+    return fir_reserve_(b, std::max(bytes, floor), what, __FILE__, line);
 }
+#define SH_GROW(buf, bytes, floor) grow_buf(buf, bytes, floor, #buf, __LINE__)
 
 int peer_failed(int code) {
     const char* what = code == FIR_ERR_NOMEM ? "allocation failed" : code == FIR_ERR_HIP ? "a HIP call failed" : code == FIR_ERR_COMM ? "an RCCL call failed"
@@ -236,17 +224,18 @@ int peer_failed(int code) {
 
 // Abort this device's communicator (a blocked collective returns) and mark the handle dead.
 int comm_dead(DevCtx& dc, Health& hl, int code, const char* why) {
-    hl.dead = true;
-    hl.dead_code = code;
+    hl.close(code);
     if (dc.comm) { (void)ncclCommAbort(dc.comm); dc.comm = nullptr; }
     return fir_fail_(code, "sharded handle: %s; the communicator was aborted and the handle is closed for further calls", why);
 }
 
-// hipStreamSynchronize with a bound: polls the stream and the communicator's asynchronous error state.
-int wait_stream(DevCtx& dc, hipStream_t st, Health& hl) {
+// A synchronisation with a bound: polls `query` (hipSuccess = done) and the communicator's asynchronous error state; an error
+// or hl.timeout_ms without completion abort the communicator.
+template <typename Query>
+int wait_bounded(DevCtx& dc, Health& hl, Query query, const char* timed_out) {
     const auto t0 = std::chrono::steady_clock::now();
     for (int spins = 0;; ++spins) {
-        const hipError_t q = hipStreamQuery(st);
+        const hipError_t q = query();
         if (q == hipSuccess) return FIR_OK;
         if (q != hipErrorNotReady) { (void)hipGetLastError(); return comm_dead(dc, hl, FIR_ERR_HIP, hipGetErrorString(q)); }
         if (dc.comm && (spins & 63) == 63) {
@@ -256,64 +245,77 @@ int wait_stream(DevCtx& dc, hipStream_t st, Health& hl) {
         }
         if (spins > 2000) {
             if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > hl.timeout_ms)
-                return comm_dead(dc, hl, FIR_ERR_COMM, "a collective did not complete within the time-out (a peer is gone or never entered it)");
+                return comm_dead(dc, hl, FIR_ERR_COMM, timed_out);
             std::this_thread::sleep_for(std::chrono::microseconds(20));
         }
     }
 }
-
+// hipStreamSynchronize with that bound ...
+int wait_stream(DevCtx& dc, hipStream_t st, Health& hl) {
+    return wait_bounded(dc, hl, [st] { return hipStreamQuery(st); }, "a collective did not complete within the time-out (a peer is gone or never entered it)");
+}
 // ... and the same for an event (the asynchronous device-pointer call runs on the CALLER's stream: its completion is an event
 // recorded there, not the state of the handle's own stream)
 int wait_event(DevCtx& dc, hipEvent_t ev, Health& hl) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int spins = 0;; ++spins) {
-        const hipError_t q = hipEventQuery(ev);
-        if (q == hipSuccess) return FIR_OK;
-        if (q != hipErrorNotReady) { (void)hipGetLastError(); return comm_dead(dc, hl, FIR_ERR_HIP, hipGetErrorString(q)); }
-        if (dc.comm && (spins & 63) == 63) {
-            ncclResult_t ar = ncclSuccess;
-            if (ncclCommGetAsyncError(dc.comm, &ar) == ncclSuccess && ar != ncclSuccess && ar != ncclInProgress)
-                return comm_dead(dc, hl, FIR_ERR_COMM, ncclGetErrorString(ar));
-        }
-        if (spins > 2000) {
-            if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > hl.timeout_ms)
-                return comm_dead(dc, hl, FIR_ERR_COMM, "an asynchronous call's exchange did not complete within the time-out (a peer is gone or never entered it)");
-            std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
+    return wait_bounded(dc, hl, [ev] { return hipEventQuery(ev); },
+                        "an asynchronous call's exchange did not complete within the time-out (a peer is gone or never entered it)");
 }
 
 // Every rank contributes its local status (FIR_OK or a negative FIR_ERR_*); all of them get the minimum.
 int agree(DevCtx& dc, hipStream_t st, Health& hl, int local_rc, int* agreed) {
     if (!dc.comm) return fir_fail_(FIR_ERR_STATE, "sharded handle: no communicator");
-    dc.h_status[0] = local_rc;
-    hipError_t e = hipMemcpyAsync(dc.status, dc.h_status, sizeof(int32_t), hipMemcpyHostToDevice, st);
-    ncclResult_t nr = e == hipSuccess ? ncclAllReduce(dc.status, dc.status, 1, ncclInt32, ncclMin, dc.comm, st) : ncclSuccess;
-    if (e == hipSuccess && nr == ncclSuccess) e = hipMemcpyAsync(dc.h_status + 1, dc.status, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    dc.hstat()[0] = local_rc;
+    hipError_t e = hipMemcpyAsync(dc.dstat(), dc.hstat(), sizeof(int32_t), hipMemcpyHostToDevice, st);
+    ncclResult_t nr = e == hipSuccess ? ncclAllReduce(dc.dstat(), dc.dstat(), 1, ncclInt32, ncclMin, dc.comm, st) : ncclSuccess;
+    if (e == hipSuccess && nr == ncclSuccess) e = hipMemcpyAsync(dc.hstat() + 1, dc.dstat(), sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return comm_dead(dc, hl, FIR_ERR_HIP, hipGetErrorString(e));
     if (nr != ncclSuccess) return comm_dead(dc, hl, FIR_ERR_COMM, ncclGetErrorString(nr));
     const int rc = wait_stream(dc, st, hl);
     if (rc) return rc;
-    *agreed = dc.h_status[1];
+    *agreed = dc.hstat()[1];
     return FIR_OK;
 }
 
+// One call of an entry point on one device, in the steps the entry points share: the agreed growth (grow_agreed), this rank's own
+// work with its error kept aside (keep_local) -- the rank enters the exchange whatever happened to it --, and after the wait the
+// verdict: my error, a peer's, or fine. The payload between these steps is the entry point's own.
+struct Call {
+    DevCtx& dc;
+    Health& hl;
+    hipStream_t st;
+    int local = FIR_OK;        // what this rank's own step returned ...
+    KeptError mine;            // ... and said
+};
+
 // The agreed growth step of a call: `need` says whether this call grows anything on this rank (the same answer on every
 // rank), `alloc` tries the allocations. Everyone leaves with the same verdict.
-int grow_agreed(DevCtx& dc, hipStream_t st, Health& hl, bool need, bool inject, const std::function<int()>& alloc) {
+int grow_agreed(Call& c, bool need, bool inject, const std::function<int()>& alloc) {
     if (!need) return FIR_OK;
-    int r = inject ? fir_fail_(FIR_ERR_NOMEM, "injected allocation failure (fir_shard_opts.fail_step = 2)") : alloc();
-    char mine[512];
-    if (r) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); mine[sizeof(mine) - 1] = 0; }
+    const int r = inject ? fir_fail_(FIR_ERR_NOMEM, "injected allocation failure (fir_shard_opts.fail_step = 2)") : alloc();
+    if (r) c.mine.capture();
     int all = FIR_OK;
-    const int ra = agree(dc, st, hl, r, &all);
+    const int ra = agree(c.dc, c.st, c.hl, r, &all);
     if (ra) return ra;
     if (all == FIR_OK) return FIR_OK;
-    hl.dead = true;
-    hl.dead_code = all;
-    if (r) { fir_set_last_error_(mine); return r; }       // this rank's own error text
+    c.hl.close(all);
+    if (r) { c.mine.restore(); return r; }                // this rank's own error text
     return peer_failed(all);
 }
+void keep_local(Call& c, int rc) {
+    c.local = rc;
+    if (rc) { c.mine.capture(); (void)hipGetLastError(); }
+}
+int peer_verdict(Health& hl, int code) {                  // what came back from the other ranks: a FIR_ERR_* of one of them, or FIR_OK
+    if (code == FIR_OK) return FIR_OK;
+    hl.close(code);
+    return peer_failed(code);
+}
+int verdict(Call& c, int peers) {
+    if (c.local) { c.hl.close(c.local); c.mine.restore(); return c.local; }
+    return peer_verdict(c.hl, peers);
+}
+// ... and of the whole call, after the fan-out over the devices
+int call_done(Health& hl, int rc) { return rc ? hl.close(rc) : FIR_OK; }
 
 constexpr uint64_t kStatusOk = kKeyNone;                  // the element behind a key payload: all ones = every rank was fine
 __host__ __device__ inline uint64_t status_key(int rc) { return rc == FIR_OK ? kStatusOk : (uint64_t)(uint32_t)(1000 + rc); }   // smaller = worse under ncclMin
@@ -333,61 +335,18 @@ __global__ void k_shard_note_status(const uint64_t* __restrict__ st, int32_t* __
 }  // namespace
 
 struct fir_sharded {
-    int exchanges_done = 0;          // (audit build's fail_step = 3)
     int d = 0, metric = 0;
     int64_t n_local = 0, first_row = 0;
     int ndev = 0, spd = 1, nranks = 1, rank0 = 0;
     bool has_labels = false;
-    std::vector<DevCtx> devs;
+    Devices devs;
     std::vector<Shard> shards;
-    void* pin = nullptr;  size_t pin_cap = 0;      // pinned host staging: queries in, keys / classes out
+    FirPinBuf pin;                   // pinned host staging: queries in, keys / classes out
     bool profiling = false;
     Health health;
 };
 
 namespace {
-
-int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, int nranks, int first_rank, const void* comm_id);
-void teardown_devices(std::vector<DevCtx>& devs, bool dead = false);
-
-// Run fn(slot) for every device: inline for one device, on the per-device worker threads otherwise.
-int run_all(std::vector<DevCtx>& devs, const std::function<int(int)>& fn);
-int run_all(fir_sharded* h, const std::function<int(int)>& fn) { return run_all(h->devs, fn); }
-int run_all(std::vector<DevCtx>& devs, const std::function<int(int)>& fn) {
-    const int ndev = (int)devs.size();
-    struct { std::vector<DevCtx>& devs; int ndev; } hh{devs, ndev};
-    auto* h = &hh;
-    if (h->ndev == 1) return fn(0);
-    for (int s = 0; s < h->ndev; ++s) {
-        Worker* w = h->devs[s].worker;
-        {
-            std::lock_guard<std::mutex> lk(w->mu);
-            w->job = [fn, s] { return fn(s); };
-            w->has_job = true;
-            w->done = false;
-        }
-        w->cv.notify_all();
-    }
-    int rc = FIR_OK;
-    for (int s = 0; s < h->ndev; ++s) {
-        Worker* w = h->devs[s].worker;
-        std::unique_lock<std::mutex> lk(w->mu);
-        w->cv.wait(lk, [&] { return w->done; });
-        if (w->rc && rc == FIR_OK) { rc = w->rc; fir_set_last_error_(w->err); }
-    }
-    return rc;
-}
-
-int ensure_pin(fir_sharded* h, size_t bytes) {
-    if (bytes <= h->pin_cap) return FIR_OK;
-    if (h->pin) FIR_HIP(hipHostFree(h->pin));
-    h->pin = nullptr;
-    h->pin_cap = 0;
-    const size_t want = std::max<size_t>(bytes, 1 << 20);
-    FIR_HIP(hipHostMalloc(&h->pin, want, hipHostMallocPortable));
-    h->pin_cap = want;
-    return FIR_OK;
-}
 
 int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
     if (end == 0) end = h->d;
@@ -395,25 +354,33 @@ int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
     return FIR_OK;
 }
 
-// The buffers of one call on one device, grown in the call's agreed step: queries (host-pointer form), the shards' partial
-// keys, the reduced keys + status element, the gathered keys of all ranks (top-K) and the winners' classes + status element.
+// The buffers of one call on one device, grown in the call's agreed step, in bytes: queries (host-pointer form), the shards'
+// partial keys, the reduced keys + status element, the gathered keys of all ranks (top-K), the winners' classes + status
+// element and the control block of the K > 8 merge. Every device holds h->spd shards, so the sizes are every device's.
 struct CallBuffers { size_t dq, parts, keys, gath, cls, sel; };
-CallBuffers call_buffers(const fir_sharded* h, const DevCtx& dc, int32_t qb, int32_t k, bool host_queries, bool classes) {
-    const size_t per = (size_t)qb * k;
-    return {host_queries ? (size_t)qb * h->d : 0, per * std::max<size_t>(dc.shards.size(), 1), per + 1,
-            k > 1 ? (per + 1) * (size_t)h->nranks : 0, classes ? (size_t)qb + 1 : 0, k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 : 0};
+CallBuffers call_buffers(const fir_sharded* h, int32_t qb, int32_t k, bool host_queries, bool classes) {
+    const size_t per = (size_t)qb * k, u64 = sizeof(uint64_t);
+    return {host_queries ? (size_t)qb * h->d * sizeof(float) : 0, per * (size_t)h->spd * u64, (per + 1) * u64,
+            k > 1 ? (per + 1) * (size_t)h->nranks * u64 : 0, classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
+            k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 * u64 : 0};
 }
+// Does this call grow anything? Asked ONCE per call, before the fan-out over the devices, of device slot 0's capacities (and
+// the staging area's): a one-int collective hangs on the answer, so it has to be the same on every slot and every rank. It is,
+// because it depends on the history of call shapes only: every device of every rank holds the same number of shards, every
+// growth so far ran in an agreed step that either gave every buffer of every rank its size or closed the handle, and SH_GROW
+// sizes a block by what was asked for. It must never become "is MY buffer too small".
 bool call_grows(const DevCtx& dc, const CallBuffers& b) {
-    return b.dq > dc.dq_cap || b.parts > dc.parts_cap || b.keys > dc.keys_cap || b.gath > dc.gath_cap || b.cls > dc.cls_cap || b.sel > dc.sel_cap;
+    return b.dq > dc.dq.cap || b.parts > dc.parts.cap || b.keys > dc.keys.cap || b.gath > dc.gath.cap || b.cls > dc.cls.cap || b.sel > dc.sel.cap;
 }
 int call_alloc(DevCtx& dc, const CallBuffers& b) {
+    constexpr size_t f4 = 1024 * sizeof(float), f8 = 1024 * sizeof(uint64_t);     // no block below 1 024 elements
     int rc;
-    if ((rc = grow_dev(dc.dq, dc.dq_cap, b.dq))) return rc;
-    if ((rc = grow_dev(dc.parts, dc.parts_cap, b.parts))) return rc;
-    if ((rc = grow_dev(dc.keys, dc.keys_cap, b.keys))) return rc;
-    if ((rc = grow_dev(dc.gath, dc.gath_cap, b.gath))) return rc;
-    if ((rc = grow_dev(dc.sel, dc.sel_cap, b.sel))) return rc;
-    return grow_dev(dc.cls, dc.cls_cap, b.cls);
+    if ((rc = SH_GROW(dc.dq, b.dq, f4))) return rc;
+    if ((rc = SH_GROW(dc.parts, b.parts, f8))) return rc;
+    if ((rc = SH_GROW(dc.keys, b.keys, f8))) return rc;
+    if ((rc = SH_GROW(dc.gath, b.gath, f8))) return rc;
+    if ((rc = SH_GROW(dc.sel, b.sel, f8))) return rc;
+    return SH_GROW(dc.cls, b.cls, f4);
 }
 bool inject_here(const fir_sharded* h, const DevCtx& dc, int step) {
     if (h->health.fail_step != step || h->health.fail_shard <= 0) return false;
@@ -435,7 +402,7 @@ int merge_knn(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t
         a.stride = (int64_t)stride;
         a.k_in = k;
         a.k = k;
-        a.ctl = (KnnCtl*)dc.sel;
+        a.ctl = dc.sel.as<KnnCtl>();
         a.out = out + (size_t)q0 * k;
         FIR_HIP(fir::knn_select_launch<false>(a, std::min<int>(kKnnTile, qb - q0), fir::kKnnMaxBlocks, st));
     }
@@ -446,6 +413,7 @@ int merge_knn(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t
 // K-way merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc).
 int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st, bool knn = false) {
     DevCtx& dc = h->devs[slot];
+    uint64_t *parts = dc.parts.as<uint64_t>(), *keys = dc.keys.as<uint64_t>();
     const size_t per = (size_t)qb * k;
     int rc;
     int live = 0;
@@ -454,17 +422,17 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
         if (h->health.fail_step == 1 && h->health.fail_shard - 1 == dc.shards[i])
             return fir_fail_(FIR_ERR_NOMEM, "injected scan failure on shard %d (fir_shard_opts.fail_step = 1)", dc.shards[i]);
         if (!s.g) continue;
-        uint64_t* out = dc.parts + (size_t)live * per;
+        uint64_t* out = parts + (size_t)live * per;
         rc = k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
              : knn  ? fir_search_knn_keys_dev(s.g, d_queries, qb, start, end, k, out, st)
                     : fir_search_topk_keys_dev(s.g, d_queries, qb, start, end, k, out, st);
         if (rc) return rc;
         ++live;
     }
-    if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.keys, (int)per, kKeyNone);
-    else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, dc.parts, live, (int)per, dc.keys);
-    else if (k > kMergeListMax) { if ((rc = merge_knn(dc, dc.parts, live, qb, k, dc.keys, per, nullptr, st))) return rc; }
-    else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, dc.parts, live, qb, k, dc.keys, per, (uint64_t*)nullptr);
+    if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
+    else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, parts, live, (int)per, keys);
+    else if (k > kMergeListMax) { if ((rc = merge_knn(dc, parts, live, qb, k, keys, per, nullptr, st))) return rc; }
+    else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, parts, live, qb, k, keys, per, (uint64_t*)nullptr);
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
@@ -473,7 +441,7 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
 // status of all ranks out. A rank whose scans failed contributes FIR_KEY_NONE keys. Errors here kill the communicator.
 int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t st, int local_rc) {
     DevCtx& dc = h->devs[slot];
-    uint64_t* keys = dc.keys;
+    uint64_t *keys = dc.keys.as<uint64_t>(), *gath = dc.gath.as<uint64_t>();
     const size_t per = (size_t)qb * k;
     const bool prof = h->profiling && slot == 0;
     if (local_rc) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
@@ -491,21 +459,21 @@ int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t s
     if (k == 1) {
         nr = ncclAllReduce(keys, keys, per + 1, ncclUint64, ncclMin, dc.comm, st);
     } else {
-        nr = ncclAllGather(keys, dc.gath, per + 1, ncclUint64, dc.comm, st);
+        nr = ncclAllGather(keys, gath, per + 1, ncclUint64, dc.comm, st);
         if (nr == ncclSuccess && k > kMergeListMax) {
-            if (merge_knn(dc, dc.gath, h->nranks, qb, k, keys, per + 1, keys + per, st)) {
+            if (merge_knn(dc, gath, h->nranks, qb, k, keys, per + 1, keys + per, st)) {
                 const std::string why = fir_last_error();
                 return comm_dead(dc, h->health, FIR_ERR_HIP, why.c_str());
             }
         } else if (nr == ncclSuccess)
-            hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, dc.gath, h->nranks, qb, k, keys, per + 1, keys + per);
+            hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, gath, h->nranks, qb, k, keys, per + 1, keys + per);
     }
     if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
 #ifdef FIR_AUDIT
     // fail_step = 3 (audit build): from the handle's SECOND exchange on the status element comes BACK poisoned, as if a peer's scan had
     // failed -- this rank's own work is fine (the first call of a handle grows its buffers in the agreed, blocking step: a test of the
     // asynchronous path needs one clean call in front)
-    if (inject_here(h, dc, 3) && h->exchanges_done++ >= 1) hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + per, status_key(FIR_ERR_NOMEM));
+    if (inject_here(h, dc, 3) && h->health.exchanges_done++ >= 1) hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + per, status_key(FIR_ERR_NOMEM));
 #endif
     if (prof && dc.ev_used + 2 <= dc.evs.size()) {
         (void)hipEventRecord(dc.evs[dc.ev_used + 1], st);
@@ -520,15 +488,16 @@ int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t s
 // status element (INT32_MAX = fine, a negative FIR_ERR_* otherwise: the minimum finds it)
 int device_classes(fir_sharded* h, int slot, const uint64_t* keys, int32_t qb, hipStream_t st, int local_rc) {
     DevCtx& dc = h->devs[slot];
-    hipLaunchKernelGGL(k_shard_fill_i32, dim3((qb + 255) / 256), dim3(256), 0, st, dc.cls, qb, 0x7FFFFFFF);
-    hipLaunchKernelGGL(k_shard_set_i32, dim3(1), dim3(1), 0, st, dc.cls + qb, local_rc ? local_rc : 0x7FFFFFFF);
+    int32_t* cls = dc.cls.as<int32_t>();
+    hipLaunchKernelGGL(k_shard_fill_i32, dim3((qb + 255) / 256), dim3(256), 0, st, cls, qb, 0x7FFFFFFF);
+    hipLaunchKernelGGL(k_shard_set_i32, dim3(1), dim3(1), 0, st, cls + qb, local_rc ? local_rc : 0x7FFFFFFF);
     if (!local_rc)
         for (int si : dc.shards) {
             const Shard& s = h->shards[si];
             if (!s.g || !s.cls) continue;
-            hipLaunchKernelGGL(k_shard_class_owned, dim3((qb + 255) / 256), dim3(256), 0, st, keys, qb, s.cls, s.lo, s.hi, dc.cls);
+            hipLaunchKernelGGL(k_shard_class_owned, dim3((qb + 255) / 256), dim3(256), 0, st, keys, qb, s.cls, s.lo, s.hi, cls);
         }
-    const ncclResult_t nr = ncclAllReduce(dc.cls, dc.cls, (size_t)qb + 1, ncclInt32, ncclMin, dc.comm, st);
+    const ncclResult_t nr = ncclAllReduce(cls, cls, (size_t)qb + 1, ncclInt32, ncclMin, dc.comm, st);
     if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return comm_dead(dc, h->health, FIR_ERR_HIP, hipGetErrorString(e));
@@ -559,88 +528,79 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
     float* hq = nullptr;
     uint64_t* hk = nullptr;
     int32_t* hc = nullptr;
-    std::mutex pin_mu;
-    std::condition_variable pin_cv;
-    bool pin_ready = false;
-    int pin_rc = FIR_OK;
-    const bool pin_grows = qbytes + kbytes + cbytes > h->pin_cap;            // read before slot 0 changes it: the same answer for every slot
-    rc = run_all(h, [&](int slot) -> int {
+    fir::Published staged;                                                   // slot 0: the staging area is there (or is not)
+    const CallBuffers nb = call_buffers(h, qb, k, true, class_out != nullptr);
+    const bool grows = call_grows(h->devs[0], nb) || qbytes + kbytes + cbytes > h->pin.cap;   // once, before the fan-out (see call_grows)
+    rc = h->devs.run_all([&](int slot) -> int {
         DevCtx& dc = h->devs[slot];
         FIR_HIP(hipSetDevice(dc.device));
-        const CallBuffers nb = call_buffers(h, dc, qb, k, true, class_out != nullptr);
-        int r = grow_agreed(dc, dc.stream, h->health, call_grows(dc, nb) || pin_grows, inject_here(h, dc, 2), [&]() -> int {
+        Call c{dc, h->health, dc.stream};
+        int r = grow_agreed(c, grows, inject_here(h, dc, 2), [&]() -> int {
             int ra = call_alloc(dc, nb);
-            if (slot == 0 && !ra) ra = ensure_pin(h, qbytes + kbytes + cbytes);
+            if (slot == 0 && !ra) ra = SH_GROW(h->pin, qbytes + kbytes + cbytes, (size_t)1 << 20);
             return ra;
         });
         if (slot == 0) {
             // the other devices of this process read the queries from the staging area slot 0 has just made sure of
             if (!r) {
-                hq = (float*)h->pin;
-                hk = (uint64_t*)((char*)h->pin + qbytes);
-                hc = (int32_t*)((char*)h->pin + qbytes + kbytes);
+                hq = h->pin.as<float>();
+                hk = (uint64_t*)(h->pin.as<char>() + qbytes);
+                hc = (int32_t*)(h->pin.as<char>() + qbytes + kbytes);
                 std::memcpy(hq, queries, qbytes);
             }
-            { std::lock_guard<std::mutex> lk(pin_mu); pin_ready = true; pin_rc = r; }
-            pin_cv.notify_all();
+            staged.publish(r);
         } else {
-            std::unique_lock<std::mutex> lk(pin_mu);
-            pin_cv.wait(lk, [&] { return pin_ready; });
-            if (!r && pin_rc) r = pin_rc;          // (an agreed failure has r != 0 everywhere already)
+            const int r0 = staged.wait();
+            if (!r) r = r0;                        // (an agreed failure has r != 0 everywhere already)
         }
         if (r) return r;
         // from here on every rank takes part in every collective of the call, whatever happens to it
-        int local = FIR_OK;
-        char mine[512] = "";
-        if (hipMemcpyAsync(dc.dq, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess) local = fir_fail_(FIR_ERR_HIP, "query upload failed");
-        if (!local) local = device_keys(h, slot, dc.dq, qb, start, end, k, dc.stream, knn);
-        if (local) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); (void)hipGetLastError(); }
-        if ((r = exchange_keys(h, slot, qb, k, dc.stream, local))) return r;
-        if (class_out && (r = device_classes(h, slot, dc.keys, qb, dc.stream, local))) return r;
+        keep_local(c, hipMemcpyAsync(dc.dq.p, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess
+                          ? fir_fail_(FIR_ERR_HIP, "query upload failed")
+                          : device_keys(h, slot, dc.dq.as<float>(), qb, start, end, k, dc.stream, knn));
+        uint64_t* keys = dc.keys.as<uint64_t>();
+        if ((r = exchange_keys(h, slot, qb, k, dc.stream, c.local))) return r;
+        if (class_out && (r = device_classes(h, slot, keys, qb, dc.stream, c.local))) return r;
         if (slot == 0) {
-            (void)hipMemcpyAsync(hk, dc.keys, kbytes, hipMemcpyDeviceToHost, dc.stream);
-            if (class_out) (void)hipMemcpyAsync(hc, dc.cls, cbytes, hipMemcpyDeviceToHost, dc.stream);
+            (void)hipMemcpyAsync(hk, keys, kbytes, hipMemcpyDeviceToHost, dc.stream);
+            if (class_out) (void)hipMemcpyAsync(hc, dc.cls.p, cbytes, hipMemcpyDeviceToHost, dc.stream);
         } else {
-            (void)hipMemcpyAsync(dc.h_status + 1, dc.keys + per, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);   // low word of the status element
+            (void)hipMemcpyAsync(dc.hstat() + 1, keys + per, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);   // low word of the status element
         }
         if ((r = wait_stream(dc, dc.stream, h->health))) return r;
-        if (local) { h->health.dead = true; h->health.dead_code = local; fir_set_last_error_(mine); return local; }
-        return FIR_OK;
+        return verdict(c, FIR_OK);                 // (the peers' status is slot 0's to read, below)
     });
-    if (rc) { h->health.dead = true; if (!h->health.dead_code.load()) h->health.dead_code = rc; return rc; }
+    if (rc) return call_done(h->health, rc);
     int all = status_code(hk[per]);
     if (!all && class_out && hc[qb] != 0x7FFFFFFF) all = hc[qb];
-    if (all) { h->health.dead = true; h->health.dead_code = all; return peer_failed(all); }
+    if ((rc = peer_verdict(h->health, all))) return rc;
     if (class_out)
         for (int i = 0; i < qb; ++i) class_out[i] = hc[i] == 0x7FFFFFFF ? -1 : hc[i];     // ImageTesting.cpp:63: no row found -> -1
     if (idx || dist) return fir_keys_unpack(hk, qb * k, idx, dist);
     return FIR_OK;
 }
 
-}  // namespace
-
-namespace {
-
 // per-device stream, communicator (rank = first_rank + slot) and, for several devices, worker threads
-int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, int nranks, int first_rank, const void* comm_id) {
+int setup_devices(Devices& devs, const int32_t* devices, int ndev, int nranks, int first_rank, const void* comm_id) {
     ncclUniqueId id;
     if (comm_id) std::memcpy(&id, comm_id, sizeof id);
     else SH_NCCL(ncclGetUniqueId(&id));
     for (int s = 0; s < ndev; ++s) {
-        DevCtx& dc = devs[(size_t)s];
+        DevCtx& dc = devs[s];
         dc.device = devices[s];
         FIR_HIP(hipSetDevice(dc.device));
         FIR_HIP(hipStreamCreateWithFlags(&dc.stream, hipStreamNonBlocking));
     }
     for (int s = 0; s < ndev; ++s) {
-        DevCtx& dc = devs[(size_t)s];
+        DevCtx& dc = devs[s];
         FIR_HIP(hipSetDevice(dc.device));
-        FIR_HIP(hipMalloc((void**)&dc.status, 4 * sizeof(int32_t)));
-        FIR_HIP(hipMemset(dc.status, 0, 4 * sizeof(int32_t)));
-        FIR_HIP(hipHostMalloc((void**)&dc.h_status, 8 * sizeof(int32_t), hipHostMallocPortable | hipHostMallocMapped));
-        std::memset(dc.h_status, 0, 8 * sizeof(int32_t));
+        int rc;
+        if ((rc = FIR_RESERVE(dc.status, 4 * sizeof(int32_t)))) return rc;
+        FIR_HIP(hipMemset(dc.status.p, 0, 4 * sizeof(int32_t)));
+        if ((rc = FIR_RESERVE(dc.h_status, 8 * sizeof(int32_t)))) return rc;
+        std::memset(dc.h_status.p, 0, 8 * sizeof(int32_t));
         void* dp = nullptr;
-        FIR_HIP(hipHostGetDevicePointer(&dp, dc.h_status, 0));
+        FIR_HIP(hipHostGetDevicePointer(&dp, dc.h_status.p, 0));
         dc.d_hsticky = (int32_t*)dp + 3;
         FIR_HIP(hipEventCreateWithFlags(&dc.async_done, hipEventDisableTiming));
     }
@@ -663,8 +623,8 @@ int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, i
         }
         nr = ncclGroupStart();
         for (int s = 0; s < ndev && nr == ncclSuccess; ++s) {
-            (void)hipSetDevice(devs[(size_t)s].device);
-            nr = ncclCommInitRank(&devs[(size_t)s].comm, nranks, id, first_rank + s);
+            (void)hipSetDevice(devs[s].device);
+            nr = ncclCommInitRank(&devs[s].comm, nranks, id, first_rank + s);
         }
         if (nr == ncclSuccess) nr = ncclGroupEnd(); else (void)ncclGroupEnd();
         if (first) {
@@ -674,36 +634,26 @@ int setup_devices(std::vector<DevCtx>& devs, const int32_t* devices, int ndev, i
         }
     }
     if (nr != ncclSuccess) return fir_fail_(FIR_ERR_COMM, "RCCL communicator of %d ranks: %s", nranks, ncclGetErrorString(nr));
-    if (ndev > 1)
-        for (int s = 0; s < ndev; ++s) {
-            Worker* w = new (std::nothrow) Worker();
-            if (!w) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
-            devs[(size_t)s].worker = w;
-            w->th = std::thread([w] { w->loop(); });
-        }
+    if (!devs.workers.start(ndev)) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     return FIR_OK;
 }
 
-void teardown_devices(std::vector<DevCtx>& devs, bool dead) {
-    for (DevCtx& dc : devs) {
-        if (dc.worker) {
-            { std::lock_guard<std::mutex> lk(dc.worker->mu); dc.worker->quit = true; }
-            dc.worker->cv.notify_all();
-            if (dc.worker->th.joinable()) dc.worker->th.join();
-            delete dc.worker;
-            dc.worker = nullptr;
-        }
+// The one release of everything setup_devices and the calls made: a handle's destroy and every failing create end here.
+// dead: the communicators are aborted, not drained (a collective of theirs may never complete).
+void teardown_devices(Devices& devs, bool dead) {
+    devs.workers.stop();
+    for (DevCtx& dc : devs.ctx) {
         (void)hipSetDevice(dc.device);
         if (dc.stream && !dead) (void)hipStreamSynchronize(dc.stream);
         if (dc.comm) { if (dead) (void)ncclCommAbort(dc.comm); else (void)ncclCommDestroy(dc.comm); }
-        (void)hipFree(dc.status);
-        if (dc.h_status) (void)hipHostFree(dc.h_status);
+        dc.status.release();
+        dc.h_status.release();
         if (dc.async_done) (void)hipEventDestroy(dc.async_done);
-        (void)hipFree(dc.dq); (void)hipFree(dc.parts); (void)hipFree(dc.keys); (void)hipFree(dc.gath); (void)hipFree(dc.cls); (void)hipFree(dc.sel);
+        for (FirBuf* b : {&dc.dq, &dc.parts, &dc.keys, &dc.gath, &dc.cls, &dc.sel}) b->release();
         for (hipEvent_t e : dc.evs) (void)hipEventDestroy(e);
         if (dc.stream) (void)hipStreamDestroy(dc.stream);
-        dc = DevCtx();
     }
+    devs.ctx.clear();
 }
 
 int check_devices(const int32_t* devices, int32_t ndev) {
@@ -811,33 +761,67 @@ __global__ void __launch_bounds__(64) k_shard_knn_vote(const double* __restrict_
 struct fir_cls_sharded {
     int d = 0, num_classes = 0, ndev = 0, nranks = 1;
     int64_t nt_local = 0;
-    std::vector<DevCtx> devs;
-    struct Part { int slot; fir_cls* c; };
-    std::vector<Part> parts;
-    std::vector<double*> acc;      size_t acc_cap = 0;     // per device: summed class scores [qb][C]
-    std::vector<int32_t*> best;                            // per device
-    std::vector<int32_t*> class_count;                     // per device: training rows per class over ALL shards and ranks
-    std::vector<double*> knn;      size_t knn_cap = 0;     // per device: [shards here + nranks][qb][C][k] lists being merged
-    size_t best_cap = 0;                                   // per device: ints in best[]
-    void* pin = nullptr;  size_t pin_cap = 0;
+    Devices devs;
+    std::vector<fir_cls*> parts;       // the training-set shards, device-major; nullptr: no rows
+    struct Dev {                       // per device
+        std::vector<int> parts;        // the shards it holds (indices into parts)
+        FirBuf acc;                    // double: summed class scores [qb][C] + the status element
+        FirBuf best;                   // int32_t [qb]
+        FirBuf class_count;            // int32_t: training rows per class over ALL shards and ranks
+        FirBuf knn;                    // double: [shards here + nranks][qb][C][k] lists being merged
+    };
+    std::vector<Dev> cdev;
+    FirPinBuf pin;
     Health health;
 };
+
+namespace {
+
+// the test hook: is this the part whose step is made to fail (by its index among all parts of the handle)? does the device hold it?
+bool cls_inject(const fir_cls_sharded* h, int part_index, int step) { return h->health.fail_step == step && h->health.fail_shard - 1 == part_index; }
+bool cls_inject_dev(const fir_cls_sharded* h, int slot, int step) {
+    for (int pi : h->cdev[(size_t)slot].parts)
+        if (cls_inject(h, pi, step)) return true;
+    return false;
+}
+// scan(shard) for every shard of this device that has rows, until one fails
+template <typename Scan>
+int cls_scan_parts(const fir_cls_sharded* h, const fir_cls_sharded::Dev& cd, Scan scan) {
+    int rc;
+    for (int pi : cd.parts) {
+        if (cls_inject(h, pi, 1)) return fir_fail_(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", pi);
+        if (h->parts[(size_t)pi] && (rc = scan(h->parts[(size_t)pi]))) return rc;
+    }
+    return FIR_OK;
+}
+
+// The allocations of a classifier call on one device, in its agreed step: the call's table (knn or acc, its exact size), best
+// (no fewer than 4 096 ints) and, on slot 0, the staging area (no smaller than pin_floor).
+struct ClsBuffers { size_t table, best, pin, pin_floor; };
+// ... and whether the call grows anything: once per call, before the fan-out, of slot 0's capacities -- see call_grows
+bool cls_grows(const fir_cls_sharded* h, const FirBuf& table0, const ClsBuffers& b) {
+    return b.table > table0.cap || b.best > h->cdev[0].best.cap || b.pin > h->pin.cap;
+}
+int cls_alloc(fir_cls_sharded* h, int slot, FirBuf& table, const ClsBuffers& b) {
+    int rc;
+    if ((rc = SH_GROW(table, b.table, 0))) return rc;
+    if ((rc = SH_GROW(h->cdev[(size_t)slot].best, b.best, 4096 * sizeof(int32_t)))) return rc;
+    return slot == 0 ? SH_GROW(h->pin, b.pin, b.pin_floor) : FIR_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int fir_cls_sharded_destroy(fir_cls_sharded* h) {
     if (!h) return FIR_OK;
-    for (auto& p : h->parts)
-        if (p.c) fir_cls_destroy(p.c);
-    for (size_t s = 0; s < h->devs.size(); ++s) {
-        (void)hipSetDevice(h->devs[s].device);
-        if (s < h->acc.size()) (void)hipFree(h->acc[s]);
-        if (s < h->best.size()) (void)hipFree(h->best[s]);
-        if (s < h->class_count.size()) (void)hipFree(h->class_count[s]);
-        if (s < h->knn.size()) (void)hipFree(h->knn[s]);
+    for (fir_cls* c : h->parts)
+        if (c) fir_cls_destroy(c);
+    for (size_t s = 0; s < h->devs.ctx.size(); ++s) {      // (a device's buffers go while it is the current one)
+        (void)hipSetDevice(h->devs[(int)s].device);
+        for (FirBuf* b : {&h->cdev[s].acc, &h->cdev[s].best, &h->cdev[s].class_count, &h->cdev[s].knn}) b->release();
     }
     teardown_devices(h->devs, h->health.dead);
-    if (h->pin) (void)hipHostFree(h->pin);
     delete h;
     return FIR_OK;
 }
@@ -856,22 +840,20 @@ int fir_cls_create_sharded(const double* train_rows, int64_t nt, int32_t d, cons
     if (!h) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     h->d = d; h->num_classes = num_classes; h->ndev = ndev; h->nranks = o.nprocs * ndev; h->nt_local = nt;
     h->health.apply(o);
-    h->devs.resize((size_t)ndev);
-    h->acc.assign((size_t)ndev, nullptr);
-    h->best.assign((size_t)ndev, nullptr);
-    h->class_count.assign((size_t)ndev, nullptr);
-    h->knn.assign((size_t)ndev, nullptr);
+    h->devs.ctx = std::vector<DevCtx>((size_t)ndev);
+    h->cdev = std::vector<fir_cls_sharded::Dev>((size_t)ndev);
     const int spd = o.shards_per_device, nsh = ndev * spd;
     const int64_t total = o.total_rows > 0 ? o.total_rows : nt;
     const int64_t per = (((nt + 63) / 64 + nsh - 1) / nsh) * 64;
     for (int s = 0; s < nsh && rc == FIR_OK; ++s) {
         const int64_t lo = std::min<int64_t>((int64_t)s * per, nt), hi = std::min<int64_t>((int64_t)(s + 1) * per, nt);
-        fir_cls_sharded::Part p{s / spd, nullptr};
+        fir_cls* c = nullptr;
         if (hi > lo) {
-            rc = fir_cls_create(train_rows + lo * d, hi - lo, d, train_class + lo, num_classes, avg, devices[p.slot], &p.c);
-            if (rc == FIR_OK) rc = fir_cls_set_total_training_size(p.c, total);     // classification.cpp:215: every partial sum over the global N
+            rc = fir_cls_create(train_rows + lo * d, hi - lo, d, train_class + lo, num_classes, avg, devices[s / spd], &c);
+            if (rc == FIR_OK) rc = fir_cls_set_total_training_size(c, total);     // classification.cpp:215: every partial sum over the global N
         }
-        h->parts.push_back(p);
+        h->cdev[(size_t)(s / spd)].parts.push_back(s);
+        h->parts.push_back(c);
     }
     if (rc == FIR_OK) rc = setup_devices(h->devs, devices, ndev, h->nranks, o.proc_rank * ndev, o.comm_id);
     // rows per class over all shards and ranks (the kNN vote's "class has k rows" and its largest-class rule)
@@ -879,11 +861,13 @@ int fir_cls_create_sharded(const double* train_rows, int64_t nt, int32_t d, cons
         std::vector<int32_t> cnt((size_t)num_classes, 0);
         for (int64_t t = 0; t < nt; ++t)
             if (train_class[t] >= 0 && train_class[t] < num_classes) cnt[(size_t)train_class[t]]++;
-        rc = run_all(h->devs, [&](int slot) -> int {
-            DevCtx& dc = h->devs[(size_t)slot];
+        rc = h->devs.run_all([&](int slot) -> int {
+            DevCtx& dc = h->devs[slot];
             FIR_HIP(hipSetDevice(dc.device));
-            FIR_HIP(hipMalloc((void**)&h->class_count[(size_t)slot], (size_t)num_classes * sizeof(int32_t)));
-            int32_t* cc = h->class_count[(size_t)slot];
+            FirBuf& count = h->cdev[(size_t)slot].class_count;
+            const int ra = FIR_RESERVE(count, (size_t)num_classes * sizeof(int32_t));
+            if (ra) return ra;
+            int32_t* cc = count.as<int32_t>();
             if (slot == 0) FIR_HIP(hipMemcpyAsync(cc, cnt.data(), (size_t)num_classes * sizeof(int32_t), hipMemcpyHostToDevice, dc.stream));
             else FIR_HIP(hipMemsetAsync(cc, 0, (size_t)num_classes * sizeof(int32_t), dc.stream));      // this process's rows are counted once
             SH_NCCL(ncclAllReduce(cc, cc, (size_t)num_classes, ncclInt32, ncclSum, dc.comm, dc.stream));
@@ -895,14 +879,6 @@ int fir_cls_create_sharded(const double* train_rows, int64_t nt, int32_t d, cons
     return FIR_OK;
 }
 
-// a part of this device whose step is made to fail (test hook), by its index among all parts of the handle
-static bool cls_inject(const fir_cls_sharded* h, int part_index, int step) { return h->health.fail_step == step && h->health.fail_shard - 1 == part_index; }
-static bool cls_inject_dev(const fir_cls_sharded* h, int slot, int step) {
-    for (size_t i = 0; i < h->parts.size(); ++i)
-        if (h->parts[i].slot == slot && cls_inject(h, (int)i, step)) return true;
-    return false;
-}
-
 int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32_t qb, int32_t k, int32_t* best_class) {
     if (!h || !best_class || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
@@ -910,8 +886,8 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     int32_t maxb = 1 << 30;
-    for (auto& p : h->parts)
-        if (p.c) { int32_t mb = 0; double* ds; void* st; fir_cls_knn_nearest_dev_(p.c, nullptr, 0, k, &ds, &st, &mb); maxb = std::min(maxb, mb); }
+    for (fir_cls* c : h->parts)
+        if (c) { int32_t mb = 0; double* ds; void* st; fir_cls_knn_nearest_dev_(c, nullptr, 0, k, &ds, &st, &mb); maxb = std::min(maxb, mb); }
     maxb = std::min(maxb, 1024);
     if (qb > maxb) {
         for (int32_t q0 = 0; q0 < qb; q0 += maxb) {
@@ -922,80 +898,55 @@ int fir_cls_sharded_knn_predict(fir_cls_sharded* h, const double* queries, int32
     }
     const size_t per = (size_t)qb * h->num_classes * k;                       // doubles in one [qb][C][k] table
     size_t max_parts = 1;
-    for (int s = 0; s < h->ndev; ++s) {
+    for (const auto& cd : h->cdev) {
         size_t np = 0;
-        for (auto& p : h->parts) np += (p.slot == s && p.c) ? 1 : 0;
+        for (int pi : cd.parts) np += h->parts[(size_t)pi] ? 1 : 0;
         max_parts = std::max(max_parts, np);
     }
     // [max_parts] shard tables | their merge + status element | [nranks] gathered tables + status elements | the merge over the ranks + status
     const size_t need = per * max_parts + (per + 1) + (per + 1) * (size_t)h->nranks + (per + 1);
-    const size_t pin_need = ((size_t)qb + 2) * sizeof(int32_t) + sizeof(double);
-    const bool grows = need > h->knn_cap || (size_t)qb > h->best_cap || pin_need > h->pin_cap;     // the same answer on every rank
-    const size_t new_best = std::max<size_t>(4096, (size_t)qb);
+    const ClsBuffers nb{need * sizeof(double), (size_t)qb * sizeof(int32_t), ((size_t)qb + 2) * sizeof(int32_t) + sizeof(double), 4096 * sizeof(int32_t) + 64};
+    const bool grows = cls_grows(h, h->cdev[0].knn, nb);
     const int64_t qc = (int64_t)qb * h->num_classes;
-    int rc = run_all(h->devs, [&](int slot) -> int {
-        DevCtx& dc = h->devs[(size_t)slot];
+    const int rc = h->devs.run_all([&](int slot) -> int {
+        DevCtx& dc = h->devs[slot];
+        fir_cls_sharded::Dev& cd = h->cdev[(size_t)slot];
         FIR_HIP(hipSetDevice(dc.device));
-        int r = grow_agreed(dc, dc.stream, h->health, grows, cls_inject_dev(h, slot, 2), [&]() -> int {
-            if (need > h->knn_cap) {
-                if (h->knn[(size_t)slot]) FIR_HIP(hipFree(h->knn[(size_t)slot]));
-                h->knn[(size_t)slot] = nullptr;
-                FIR_HIP(hipMalloc((void**)&h->knn[(size_t)slot], need * sizeof(double)));
-            }
-            if ((size_t)qb > h->best_cap) {
-                if (h->best[(size_t)slot]) FIR_HIP(hipFree(h->best[(size_t)slot]));
-                h->best[(size_t)slot] = nullptr;
-                FIR_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
-            }
-            if (slot == 0 && pin_need > h->pin_cap) {
-                if (h->pin) FIR_HIP(hipHostFree(h->pin));
-                h->pin = nullptr; h->pin_cap = 0;
-                FIR_HIP(hipHostMalloc(&h->pin, std::max<size_t>(pin_need, 4096 * sizeof(int32_t) + 64), hipHostMallocPortable));
-                h->pin_cap = std::max<size_t>(pin_need, 4096 * sizeof(int32_t) + 64);
-            }
-            return FIR_OK;
-        });
+        Call c{dc, h->health, dc.stream};
+        int r = grow_agreed(c, grows, cls_inject_dev(h, slot, 2), [&]() -> int { return cls_alloc(h, slot, cd.knn, nb); });
         if (r) return r;
-        double* parts = h->knn[(size_t)slot];                                 // [max_parts] tables of the shards held here
+        double* parts = cd.knn.as<double>();                                  // [max_parts] tables of the shards held here
         double* mine = parts + per * max_parts;                               // their merge (+ status element)
         double* gath = mine + per + 1;                                        // [nranks] tables (+ status elements)
         double* all = gath + (per + 1) * (size_t)h->nranks;                   // the merge over the ranks (+ the worst status)
         int np = 0;
-        int local = FIR_OK;
-        char mine_err[512] = "";
-        for (size_t pi = 0; pi < h->parts.size() && !local; ++pi) {
-            auto& p = h->parts[pi];
-            if (p.slot != slot) continue;
-            if (cls_inject(h, (int)pi, 1)) { local = fir_fail_(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
-            if (!p.c) continue;
+        keep_local(c, cls_scan_parts(h, cd, [&](fir_cls* shard) -> int {
             double* dl = nullptr;
             void* st = nullptr;
-            local = fir_cls_knn_nearest_dev_(p.c, queries, qb, k, &dl, &st, nullptr);
-            if (local) break;
+            const int rs = fir_cls_knn_nearest_dev_(shard, queries, qb, k, &dl, &st, nullptr);
+            if (rs) return rs;
             if (hipStreamSynchronize((hipStream_t)st) != hipSuccess ||
-                hipMemcpyAsync(parts + per * (size_t)np, dl, per * sizeof(double), hipMemcpyDeviceToDevice, dc.stream) != hipSuccess)
-                local = fir_fail_(FIR_ERR_HIP, "copying a shard's k-nearest table failed");
-            ++np;
-        }
-        if (local) { strncpy(mine_err, fir_last_error(), sizeof(mine_err) - 1); (void)hipGetLastError(); np = 0; }
+                hipMemcpyAsync(parts + per * (size_t)np++, dl, per * sizeof(double), hipMemcpyDeviceToDevice, dc.stream) != hipSuccess)
+                return fir_fail_(FIR_ERR_HIP, "copying a shard's k-nearest table failed");
+            return FIR_OK;
+        }));
+        const int local = c.local;
+        if (local) np = 0;
         hipLaunchKernelGGL(k_shard_merge_knn, dim3((unsigned)((qc + 255) / 256)), dim3(256), 0, dc.stream, parts, np, qc, k, mine, per, (double*)nullptr);   // np == 0: all DBL_MAX
         hipLaunchKernelGGL(k_shard_set_f64, dim3(1), dim3(1), 0, dc.stream, mine + per, local ? (double)(-local) : 0.0);
         const ncclResult_t nr = ncclAllGather(mine, gath, per + 1, ncclDouble, dc.comm, dc.stream);
         if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
         hipLaunchKernelGGL(k_shard_merge_knn, dim3((unsigned)((qc + 255) / 256)), dim3(256), 0, dc.stream, gath, h->nranks, qc, k, all, per + 1, all + per);
-        hipLaunchKernelGGL(k_shard_knn_vote, dim3((qb + 63) / 64), dim3(64), 0, dc.stream, all, qb, h->num_classes, k, h->class_count[(size_t)slot],
-                           h->best[(size_t)slot]);
-        double* hst = slot == 0 ? (double*)((char*)h->pin + (((size_t)qb * sizeof(int32_t) + 7) & ~(size_t)7)) : (double*)(dc.h_status + 4);
+        hipLaunchKernelGGL(k_shard_knn_vote, dim3((qb + 63) / 64), dim3(64), 0, dc.stream, all, qb, h->num_classes, k, cd.class_count.as<int32_t>(),
+                           cd.best.as<int32_t>());
+        double* hst = slot == 0 ? (double*)(h->pin.as<char>() + (((size_t)qb * sizeof(int32_t) + 7) & ~(size_t)7)) : (double*)(dc.hstat() + 4);
         (void)hipMemcpyAsync(hst, all + per, sizeof(double), hipMemcpyDeviceToHost, dc.stream);
-        if (slot == 0) (void)hipMemcpyAsync(h->pin, h->best[0], (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);
+        if (slot == 0) (void)hipMemcpyAsync(h->pin.p, cd.best.p, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);
         if ((r = wait_stream(dc, dc.stream, h->health))) return r;
-        if (local) { h->health.dead = true; h->health.dead_code = local; fir_set_last_error_(mine_err); return local; }
-        if (*hst != 0.0) { h->health.dead = true; h->health.dead_code = -(int)*hst; return peer_failed(-(int)*hst); }
-        return FIR_OK;
+        return verdict(c, -(int)*hst);                                        // the status element: the largest -FIR_ERR_* of any rank
     });
-    if (grows && !h->health.dead) { h->knn_cap = std::max(h->knn_cap, need); h->best_cap = std::max(h->best_cap, new_best); }
-    if (rc) { h->health.dead = true; if (!h->health.dead_code.load()) h->health.dead_code = rc; return rc; }
-    std::memcpy(best_class, h->pin, (size_t)qb * sizeof(int32_t));
+    if (rc) return call_done(h->health, rc);
+    std::memcpy(best_class, h->pin.p, (size_t)qb * sizeof(int32_t));
     return FIR_OK;
 }
 
@@ -1006,8 +957,8 @@ int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32
     if (qb == 0) return FIR_OK;
     // internal batches: what every shard's distance table allows (fir_cls_pnn_scores_dev_)
     int32_t maxb = 1 << 30;
-    for (auto& p : h->parts)
-        if (p.c) { int32_t mb = 0; double* ds; void* st; fir_cls_pnn_scores_dev_(p.c, nullptr, 0, var, &ds, &st, &mb); maxb = std::min(maxb, mb); }
+    for (fir_cls* c : h->parts)
+        if (c) { int32_t mb = 0; double* ds; void* st; fir_cls_pnn_scores_dev_(c, nullptr, 0, var, &ds, &st, &mb); maxb = std::min(maxb, mb); }
     maxb = std::min(maxb, 4096);
     if (qb > maxb) {
         for (int32_t q0 = 0; q0 < qb; q0 += maxb) {
@@ -1019,70 +970,46 @@ int fir_cls_sharded_pnn_predict(fir_cls_sharded* h, const double* queries, int32
     }
     const size_t nsc = (size_t)qb * h->num_classes;
     const size_t pin_need = (nsc + 1) * sizeof(double) + (size_t)qb * sizeof(int32_t);
-    const bool grows = nsc + 1 > h->acc_cap || (size_t)qb > h->best_cap || pin_need > h->pin_cap;      // the same answer on every rank
-    const size_t new_best = std::max<size_t>(4096, (size_t)qb);
-    int rc = run_all(h->devs, [&](int slot) -> int {
-        DevCtx& dc = h->devs[(size_t)slot];
+    const ClsBuffers nb{(nsc + 1) * sizeof(double), (size_t)qb * sizeof(int32_t), pin_need, 0};
+    const bool grows = cls_grows(h, h->cdev[0].acc, nb);
+    const int rc = h->devs.run_all([&](int slot) -> int {
+        DevCtx& dc = h->devs[slot];
+        fir_cls_sharded::Dev& cd = h->cdev[(size_t)slot];
         FIR_HIP(hipSetDevice(dc.device));
-        int r = grow_agreed(dc, dc.stream, h->health, grows, cls_inject_dev(h, slot, 2), [&]() -> int {
-            if (nsc + 1 > h->acc_cap) {
-                if (h->acc[(size_t)slot]) FIR_HIP(hipFree(h->acc[(size_t)slot]));
-                h->acc[(size_t)slot] = nullptr;
-                FIR_HIP(hipMalloc((void**)&h->acc[(size_t)slot], (nsc + 1) * sizeof(double)));
-            }
-            if ((size_t)qb > h->best_cap) {
-                if (h->best[(size_t)slot]) FIR_HIP(hipFree(h->best[(size_t)slot]));
-                h->best[(size_t)slot] = nullptr;
-                FIR_HIP(hipMalloc((void**)&h->best[(size_t)slot], new_best * sizeof(int32_t)));
-            }
-            if (slot == 0 && pin_need > h->pin_cap) {
-                if (h->pin) FIR_HIP(hipHostFree(h->pin));
-                h->pin = nullptr; h->pin_cap = 0;
-                FIR_HIP(hipHostMalloc(&h->pin, pin_need, hipHostMallocPortable));
-                h->pin_cap = pin_need;
-            }
-            return FIR_OK;
-        });
+        Call c{dc, h->health, dc.stream};
+        int r = grow_agreed(c, grows, cls_inject_dev(h, slot, 2), [&]() -> int { return cls_alloc(h, slot, cd.acc, nb); });
         if (r) return r;
-        double* acc = h->acc[(size_t)slot];
+        double* acc = cd.acc.as<double>();
         int first = 1;
-        int local = FIR_OK;
-        char mine_err[512] = "";
-        for (size_t pi = 0; pi < h->parts.size() && !local; ++pi) {
-            auto& p = h->parts[pi];
-            if (p.slot != slot) continue;
-            if (cls_inject(h, (int)pi, 1)) { local = fir_fail_(FIR_ERR_NOMEM, "injected scan failure on training-set shard %d (fir_shard_opts.fail_step = 1)", (int)pi); break; }
-            if (!p.c) continue;
+        keep_local(c, cls_scan_parts(h, cd, [&](fir_cls* shard) -> int {
             double* ds = nullptr;
             void* st = nullptr;
-            local = fir_cls_pnn_scores_dev_(p.c, queries, qb, var, &ds, &st, nullptr);
-            if (local) break;
-            if (hipStreamSynchronize((hipStream_t)st) != hipSuccess) { local = fir_fail_(FIR_ERR_HIP, "a shard's class scores did not complete"); break; }   // the shard's own stream
+            const int rs = fir_cls_pnn_scores_dev_(shard, queries, qb, var, &ds, &st, nullptr);
+            if (rs) return rs;
+            if (hipStreamSynchronize((hipStream_t)st) != hipSuccess) return fir_fail_(FIR_ERR_HIP, "a shard's class scores did not complete");   // the shard's own stream
             hipLaunchKernelGGL(k_shard_add_f64, dim3((unsigned)((nsc + 255) / 256)), dim3(256), 0, dc.stream, acc, ds, (int64_t)nsc, first);
             first = 0;
-        }
-        if (local) { strncpy(mine_err, fir_last_error(), sizeof(mine_err) - 1); (void)hipGetLastError(); }
+            return FIR_OK;
+        }));
+        const int local = c.local;
         if (first || local) (void)hipMemsetAsync(acc, 0, nsc * sizeof(double), dc.stream);     // a device without rows (or whose step failed) adds nothing
         hipLaunchKernelGGL(k_shard_set_f64, dim3(1), dim3(1), 0, dc.stream, acc + nsc, local ? 1.0 : 0.0);   // the status element: the sum counts the ranks that failed
         const ncclResult_t nr = ncclAllReduce(acc, acc, nsc + 1, ncclDouble, ncclSum, dc.comm, dc.stream);
         if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
-        hipLaunchKernelGGL(k_shard_argmax_first, dim3(qb), dim3(64), 0, dc.stream, acc, h->num_classes, h->best[(size_t)slot]);
-        double* hst = slot == 0 ? (double*)h->pin + nsc : (double*)(dc.h_status + 4);
+        hipLaunchKernelGGL(k_shard_argmax_first, dim3(qb), dim3(64), 0, dc.stream, acc, h->num_classes, cd.best.as<int32_t>());
+        double* hst = slot == 0 ? h->pin.as<double>() + nsc : (double*)(dc.hstat() + 4);
         if (slot == 0) {
-            (void)hipMemcpyAsync(h->pin, acc, (nsc + 1) * sizeof(double), hipMemcpyDeviceToHost, dc.stream);
-            (void)hipMemcpyAsync((char*)h->pin + (nsc + 1) * sizeof(double), h->best[0], (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);
+            (void)hipMemcpyAsync(h->pin.p, acc, (nsc + 1) * sizeof(double), hipMemcpyDeviceToHost, dc.stream);
+            (void)hipMemcpyAsync(h->pin.as<char>() + (nsc + 1) * sizeof(double), cd.best.p, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);
         } else {
             (void)hipMemcpyAsync(hst, acc + nsc, sizeof(double), hipMemcpyDeviceToHost, dc.stream);
         }
         if ((r = wait_stream(dc, dc.stream, h->health))) return r;
-        if (local) { h->health.dead = true; h->health.dead_code = local; fir_set_last_error_(mine_err); return local; }
-        if (*hst != 0.0) { h->health.dead = true; h->health.dead_code = FIR_ERR_COMM; return peer_failed(FIR_ERR_COMM); }
-        return FIR_OK;
+        return verdict(c, *hst != 0.0 ? FIR_ERR_COMM : FIR_OK);               // a count of failed ranks: it cannot say which error
     });
-    if (grows && !h->health.dead) { h->acc_cap = std::max(h->acc_cap, nsc + 1); h->best_cap = std::max(h->best_cap, new_best); }
-    if (rc) { h->health.dead = true; if (!h->health.dead_code.load()) h->health.dead_code = rc; return rc; }
-    if (scores) std::memcpy(scores, h->pin, nsc * sizeof(double));
-    if (best_class) std::memcpy(best_class, (char*)h->pin + (nsc + 1) * sizeof(double), (size_t)qb * sizeof(int32_t));
+    if (rc) return call_done(h->health, rc);
+    if (scores) std::memcpy(scores, h->pin.p, nsc * sizeof(double));
+    if (best_class) std::memcpy(best_class, h->pin.as<char>() + (nsc + 1) * sizeof(double), (size_t)qb * sizeof(int32_t));
     return FIR_OK;
 }
 
@@ -1101,7 +1028,6 @@ int fir_sharded_destroy(fir_sharded* h) {
     for (Shard& s : h->shards)
         if (s.g) fir_gallery_destroy(s.g);
     teardown_devices(h->devs, h->health.dead);
-    if (h->pin) (void)hipHostFree(h->pin);
     delete h;
     return FIR_OK;
 }
@@ -1110,41 +1036,23 @@ int fir_gallery_create_sharded_ex(const float* rows, int64_t n, int32_t d, const
                                   int32_t ndev, const fir_shard_opts* opts, fir_sharded** out) {
     if (!out) return fir_fail_(FIR_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!devices || ndev < 1 || ndev > 64) return fir_fail_(FIR_ERR_ARG, "device list of %d entries", ndev);
+    int rc = check_devices(devices, ndev);
+    if (rc) return rc;
     if (n < 0 || d <= 0 || (n > 0 && !rows)) return fir_fail_(FIR_ERR_ARG, "bad gallery shape n=%lld d=%d", (long long)n, d);
     fir_shard_opts o;
-    std::memset(&o, 0, sizeof o);
-    if (opts) {
-        if (opts->struct_bytes < 8 || opts->struct_bytes > (int32_t)sizeof o) return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.struct_bytes = %d", opts->struct_bytes);
-        std::memcpy(&o, opts, (size_t)opts->struct_bytes);
-    }
-    const int spd = o.shards_per_device > 0 ? o.shards_per_device : 1;
-    const int nprocs = o.comm_id ? o.nprocs : 1, proc = o.comm_id ? o.proc_rank : 0;
-    if (spd > 64) return fir_fail_(FIR_ERR_ARG, "shards_per_device = %d", spd);
-    if (nprocs < 1 || proc < 0 || proc >= nprocs) return fir_fail_(FIR_ERR_ARG, "process %d of %d", proc, nprocs);
+    if ((rc = read_opts(opts, &o))) return rc;
+    const int spd = o.shards_per_device;
     if (o.rows_on_device && ndev != 1) return fir_fail_(FIR_ERR_ARG, "device-resident rows need a one-entry device list (they live on one device)");
-#ifndef FIR_AUDIT
-    if (o.fail_shard != 0 || o.fail_step != 0)       // (as read_opts: the hooks exist in the audit build only)
-        return fir_fail_(FIR_ERR_ARG, "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none");
-#endif
     if (o.first_global_row < 0 || o.first_global_row + n >= ((int64_t)1 << 31)) return fir_fail_(FIR_ERR_ARG, "rows [%lld, +%lld) do not fit 32-bit indices", (long long)o.first_global_row, (long long)n);
-    for (int i = 0; i < ndev; ++i)
-        for (int j = 0; j < i; ++j)
-            if (devices[i] == devices[j]) return fir_fail_(FIR_ERR_ARG, "device %d listed twice (use shards_per_device for logical shards)", devices[i]);
-    const int cnt = fir_device_count();
-    for (int i = 0; i < ndev; ++i)
-        if (devices[i] < 0 || devices[i] >= cnt) return fir_fail_(FIR_ERR_NODEVICE, "device %d out of range (%d visible)", devices[i], cnt);
+    if (o.fail_shard < 0 || o.fail_shard > ndev * spd) return fir_fail_(FIR_ERR_ARG, "fail_shard = %d of %d shards", o.fail_shard, ndev * spd);
 
     fir_sharded* h = new (std::nothrow) fir_sharded();
     if (!h) return fir_fail_(FIR_ERR_NOMEM, "host allocation failed");
     h->d = d; h->metric = metric; h->n_local = n; h->first_row = o.first_global_row;
-    h->ndev = ndev; h->spd = spd; h->nranks = nprocs * ndev; h->rank0 = proc * ndev;
+    h->ndev = ndev; h->spd = spd; h->nranks = o.nprocs * ndev; h->rank0 = o.proc_rank * ndev;
     h->has_labels = class_no != nullptr;
     h->health.apply(o);
-    if (h->health.fail_shard < 0 || h->health.fail_shard > ndev * spd) { delete h; return fir_fail_(FIR_ERR_ARG, "fail_shard = %d of %d shards", o.fail_shard, ndev * spd); }
-    h->devs.resize((size_t)ndev);
-    int rc = FIR_OK;
-    auto bail = [&](int code) { fir_sharded_destroy(h); return code; };
+    h->devs.ctx = std::vector<DevCtx>((size_t)ndev);
 
     // shards: whole 64-row tiles, contiguous, device-major (device i holds shards i*spd .. i*spd+spd-1)
     const int nsh = ndev * spd;
@@ -1157,7 +1065,7 @@ int fir_gallery_create_sharded_ex(const float* rows, int64_t n, int32_t d, const
         const int64_t lo = std::min<int64_t>((int64_t)s * per, n), hi = std::min<int64_t>((int64_t)(s + 1) * per, n);
         sh.lo = o.first_global_row + lo;
         sh.hi = o.first_global_row + hi;
-        h->devs[(size_t)sh.slot].shards.push_back(s);
+        h->devs[sh.slot].shards.push_back(s);
         if (hi <= lo) continue;
         const int dev = devices[sh.slot];
         if (o.rows_on_device) rc = fir_gallery_create_dev(rows + lo * d, hi - lo, d, class_no ? class_no + lo : nullptr, metric, dev, nullptr, &sh.g);
@@ -1169,10 +1077,9 @@ int fir_gallery_create_sharded_ex(const float* rows, int64_t n, int32_t d, const
             sh.cls = v.cls;
         }
     }
-    if (rc) return bail(rc);
-
     // per-device stream, communicator (rank = proc * ndev + slot), worker threads
-    if ((rc = setup_devices(h->devs, devices, ndev, h->nranks, h->rank0, o.comm_id))) return bail(rc);
+    if (rc == FIR_OK) rc = setup_devices(h->devs, devices, ndev, h->nranks, h->rank0, o.comm_id);
+    if (rc) { fir_sharded_destroy(h); return rc; }
     *out = h;
     return FIR_OK;
 }
@@ -1240,28 +1147,27 @@ int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int
     if (rc) return rc;
     DevCtx& dc = h->devs[0];
     FIR_HIP(hipSetDevice(dc.device));
-    hipStream_t st = stream ? (hipStream_t)stream : dc.stream;
+    Call c{dc, h->health, stream ? (hipStream_t)stream : dc.stream};
     // What the previous asynchronous call found, if it is through (no waiting here): a peer's failure closes the handle BEFORE this rank
     // enqueues another collective that the failed peer -- dead since that call -- will never enter. A previous call that is still in
     // flight is the caller's to order (fir_amd.h: fir_sharded_sync between asynchronous calls whose failure must not be outrun).
     if (dc.async_pending && hipEventQuery(dc.async_done) == hipSuccess) {
         dc.async_pending = false;
-        if (dc.h_status[3] < 0) { h->health.dead = true; h->health.dead_code = dc.h_status[3]; return peer_failed(dc.h_status[3]); }
+        if (dc.hstat()[3] < 0) return peer_verdict(h->health, dc.hstat()[3]);
     }
     (void)hipGetLastError();
-    const CallBuffers nb = call_buffers(h, dc, qb, 1, false, false);
-    if ((rc = grow_agreed(dc, st, h->health, call_grows(dc, nb), inject_here(h, dc, 2), [&]() -> int { return call_alloc(dc, nb); }))) return rc;
+    const CallBuffers nb = call_buffers(h, qb, 1, false, false);
+    if ((rc = grow_agreed(c, call_grows(dc, nb), inject_here(h, dc, 2), [&]() -> int { return call_alloc(dc, nb); }))) return rc;
     // every rank enters the exchange; one whose scans failed sends FIR_KEY_NONE keys and a poisoned status element, returns its
     // error here, and the others find it in fir_sharded_sync (the call is asynchronous: nobody waits for the exchange here)
-    int local = device_keys(h, 0, d_queries, qb, start_pos, end_pos, 1, st);
-    char mine[512] = "";
-    if (local) { strncpy(mine, fir_last_error(), sizeof(mine) - 1); (void)hipGetLastError(); }
-    if ((rc = exchange_keys(h, 0, qb, 1, st, local))) return rc;
-    hipLaunchKernelGGL(k_shard_note_status, dim3(1), dim3(1), 0, st, dc.keys + qb, dc.status + 1, dc.d_hsticky);
-    (void)hipMemcpyAsync(d_keys, dc.keys, (size_t)qb * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
-    (void)hipEventRecord(dc.async_done, st);           // what fir_sharded_sync (and the next call's look at the status) waits for: `st` may be the caller's stream
+    keep_local(c, device_keys(h, 0, d_queries, qb, start_pos, end_pos, 1, c.st));
+    if ((rc = exchange_keys(h, 0, qb, 1, c.st, c.local))) return rc;
+    uint64_t* keys = dc.keys.as<uint64_t>();
+    hipLaunchKernelGGL(k_shard_note_status, dim3(1), dim3(1), 0, c.st, keys + qb, dc.dstat() + 1, dc.d_hsticky);
+    (void)hipMemcpyAsync(d_keys, keys, (size_t)qb * sizeof(uint64_t), hipMemcpyDeviceToDevice, c.st);
+    (void)hipEventRecord(dc.async_done, c.st);         // what fir_sharded_sync (and the next call's look at the status) waits for: the stream may be the caller's
     dc.async_pending = true;
-    if (local) { h->health.dead = true; h->health.dead_code = local; fir_set_last_error_(mine); return local; }
+    if ((rc = verdict(c, FIR_OK))) return rc;          // (a peer's error is the next call's, or fir_sharded_sync's, to find)
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
@@ -1269,7 +1175,7 @@ int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int
 int fir_sharded_sync(fir_sharded* h) {
     if (!h) return fir_fail_(FIR_ERR_ARG, "handle is NULL");
     if (h->health.dead) return dead_handle(h->health);
-    for (DevCtx& dc : h->devs) {
+    for (DevCtx& dc : h->devs.ctx) {
         FIR_HIP(hipSetDevice(dc.device));
         int rc;
         // the last asynchronous call ran on whatever stream its caller named: its completion is the event recorded behind it, waited for
@@ -1278,10 +1184,10 @@ int fir_sharded_sync(fir_sharded* h) {
         dc.async_pending = false;
         if ((rc = wait_stream(dc, dc.stream, h->health))) return rc;
         // the asynchronous calls' record: the worst status any exchange since the last sync came back with (device word and its host mirror)
-        FIR_HIP(hipMemcpyAsync(dc.h_status + 2, dc.status + 1, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream));
+        FIR_HIP(hipMemcpyAsync(dc.hstat() + 2, dc.dstat() + 1, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream));
         if ((rc = wait_stream(dc, dc.stream, h->health))) return rc;
-        const int32_t worst = std::min(dc.h_status[2], dc.h_status[3]);
-        if (worst < 0) { h->health.dead = true; h->health.dead_code = worst; return peer_failed(worst); }
+        const int32_t worst = std::min(dc.hstat()[2], dc.hstat()[3]);
+        if (worst < 0) return peer_verdict(h->health, worst);
     }
     return FIR_OK;
 }

@@ -227,3 +227,124 @@ def test_a_peers_failure_reaches_the_asynchronous_caller_whatever_stream_it_used
         with pytest.raises(fir_audit.FirError) as e3:
             s.search_top1_keys_dev(qt.data_ptr(), qb, keys.data_ptr(), stream=mine.cuda_stream)
         assert e3.value.code == -3
+
+
+def test_one_handle_across_growing_and_shrinking_call_shapes(fir):
+    """One ShardedGallery through calls whose buffers grow, stay and are reused: 200 x 32 rows in 3 logical shards (4 tiles: the
+    third shard is empty). Call 3 has k above every shard's row count and brings in the K > 8 merge's control block, call 4 the
+    class buffer and a larger staging area, call 5 is smaller than everything before it. Every call is the unsharded handle's
+    answer bit for bit."""
+    n, d = 200, 32
+    rows = synth.make_gallery(61, n, d, L2)
+    labels = synth.make_labels(n, 9)
+    q, _ = synth.make_queries(61, rows, 300, L2)
+    q[1] = np.float32(1e4)                                       # nothing below 100000 anywhere
+    with fir.Gallery(rows, labels, fir.METRIC_L2, 0) as g:
+        e1 = g.search_top1(q[:3])
+        e2 = g.search_topk(q[:40], 8)
+        e3 = g.search_knn(q[:5], 150)
+        e4 = g.search_top1(q)
+        e5 = g.search_top1(q[:2], 8, 24)
+    with fir.ShardedGallery(rows, labels, fir.METRIC_L2, devices=[0], shards_per_device=3) as s:
+        assert s.shard(2)[2] == 0 and s.shard(1)[2] == 72
+        r1 = s.search_top1(q[:3])
+        r2 = s.search_topk(q[:40], 8)
+        r3 = s.search_knn(q[:5], 150)
+        cls, idx4, dist4 = s.classify_top1(q)
+        r5 = s.search_top1(q[:2], 8, 24)
+    for (idx, dist), (eidx, edist) in [(r1, e1), (r2, e2), (r3, e3), ((idx4, dist4), e4), (r5, e5)]:
+        assert np.array_equal(idx, eidx) and np.array_equal(bits(dist), bits(edist))
+    assert np.array_equal(cls, np.where(e4[0] >= 0, labels[np.maximum(e4[0], 0)], -1)) and cls[1] == -1
+    assert r3[0].shape == (5, 150) and (r3[0][0] >= 0).all() and r3[0][1, 0] == -1
+
+
+def test_one_classifier_handle_across_growing_and_shrinking_call_shapes(fir):
+    """The same for ShardedClsModel: 300 x 16 training rows, 7 classes, 4 logical shards (5 tiles: the last one is empty); PNN and
+    kNN calls alternate on one handle, larger and smaller. kNN classes are the one-handle model's exactly, PNN scores within the
+    1e-12 of test_gpu_cls.py's sharded PNN test (the order of the additions is all that differs)."""
+    nt, d, ncls = 300, 16, 7
+    rng = np.random.default_rng(62)
+    centres = rng.random((ncls, d))
+    tcls = np.sort(rng.integers(0, ncls, nt)).astype(np.int32)
+    tr = centres[tcls] + 0.004 * rng.standard_normal((nt, d))
+    q = centres[rng.integers(0, ncls, 300)] + 0.004 * rng.standard_normal((300, d))
+    avg = tr.mean(axis=0)
+    with fir.ClsModel(tr, tcls, ncls, avg, 0) as m:
+        b0, s0 = m.pnn_predict(q)
+        k3, k1 = m.knn_predict(q[:40], 3), m.knn_predict(q[:7], 1)
+    with fir.ShardedClsModel(tr, tcls, ncls, avg, devices=[0], shards_per_device=4) as s:
+        pa = s.pnn_predict(q[:5])
+        ka = s.knn_predict(q[:40], 3)
+        pb = s.pnn_predict(q)
+        kb = s.knn_predict(q[:7], 1)
+    assert np.array_equal(ka, k3) and np.array_equal(kb, k1)
+    top2 = np.sort(s0, axis=1)[:, -2:]
+    clear = (top2[:, 1] - top2[:, 0]) > 1e-11 * top2[:, 1]
+    assert clear.sum() >= 250
+    for (b, sc), nq in ((pa, 5), (pb, 300)):
+        np.testing.assert_allclose(sc, s0[:nq], rtol=1e-12, atol=1e-300)
+        assert np.array_equal(b[clear[:nq]], b0[:nq][clear[:nq]])
+
+
+def _create_gallery(fir, devices, **opts):
+    import ctypes as C
+
+    rows = np.zeros((100, 16), np.float32)
+    devs = np.asarray(list(devices) + [0], np.int32)            # (one spare entry: an empty list still has an address)
+    o = fir.capi.ShardOpts()
+    o.struct_bytes = C.sizeof(o)
+    for name, v in opts.items():
+        setattr(o, name, v)
+    h = C.c_void_p()
+    rc = fir.lib().fir_gallery_create_sharded_ex(rows.ctypes.data_as(C.c_void_p), 100, 16, None, 0, devs.ctypes.data_as(C.c_void_p), len(devices),
+                                                 C.byref(o), C.byref(h))
+    if rc == 0:
+        fir.lib().fir_sharded_destroy(h)
+    return rc, fir.lib().fir_last_error().decode(), h.value
+
+
+def _create_cls(fir, devices, **opts):
+    import ctypes as C
+
+    tr = np.zeros((100, 16), np.float64)
+    tcls = np.zeros(100, np.int32)
+    devs = np.asarray(list(devices) + [0], np.int32)
+    o = fir.capi.ShardOpts()
+    o.struct_bytes = C.sizeof(o)
+    for name, v in opts.items():
+        setattr(o, name, v)
+    h = C.c_void_p()
+    vp = C.c_void_p
+    rc = fir.lib().fir_cls_create_sharded(tr.ctypes.data_as(vp), 100, 16, tcls.ctypes.data_as(vp), 2, tr[0].ctypes.data_as(vp), devs.ctypes.data_as(vp),
+                                          len(devices), C.byref(o), C.byref(h))
+    if rc == 0:
+        fir.lib().fir_cls_sharded_destroy(h)
+    return rc, fir.lib().fir_last_error().decode(), h.value
+
+
+HOOKS = "fir_shard_opts.fail_shard / fail_step are test hooks of the audit build (libfir_amd_audit.so); this library has none"
+# (what is wrong, the device list (None: [device_count()]), fir_shard_opts fields, which creates, code, message)
+CREATE_ERRORS = [
+    ("empty-list", [], {}, "both", -1, "device list of 0 entries"),
+    ("listed-twice", [0, 0], {}, "both", -1, "device 0 listed twice (use shards_per_device for logical shards)"),
+    ("out-of-range", None, {}, "both", -4, "device {cnt} out of range ({cnt} visible)"),
+    ("65-shards", [0], {"shards_per_device": 65}, "both", -1, "shards_per_device = 65"),
+    ("struct-bytes", [0], {"struct_bytes": 4}, "both", -1, "fir_shard_opts.struct_bytes = 4"),
+    ("fail-shard", [0], {"fail_shard": 1}, "both", -1, HOOKS),
+    ("fail-step", [0], {"fail_step": 1}, "both", -1, HOOKS),
+    ("negative-first-row", [0], {"first_global_row": -1}, "gallery", -1, "rows [-1, +100) do not fit 32-bit indices"),
+    ("cls-rows-on-device", [0], {"rows_on_device": 1}, "cls", -1, "fir_cls_create_sharded takes host rows"),
+]
+
+
+@pytest.mark.parametrize("what,devices,opts,which,code,message", CREATE_ERRORS, ids=[c[0] for c in CREATE_ERRORS])
+def test_single_cause_argument_errors_of_both_creates(fir, what, devices, opts, which, code, message):
+    """One wrong argument at a time: the code and the text fir_last_error() gives, for fir_gallery_create_sharded_ex and
+    fir_cls_create_sharded alike; no handle comes back."""
+    cnt = fir.device_count()
+    devices = [cnt] if devices is None else devices
+    for name, create in (("gallery", _create_gallery), ("cls", _create_cls)):
+        if which not in ("both", name):
+            continue
+        rc, text, handle = create(fir, devices, **opts)
+        assert (rc, text, handle) == (code, message.format(cnt=cnt), None), name
