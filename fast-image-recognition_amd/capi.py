@@ -54,6 +54,8 @@ SYMBOLS = [
     ("fir_search_topk_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_knn", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_knn_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_search_radius", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_radius_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_class_keys_merge", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
@@ -90,6 +92,7 @@ SYMBOLS = [
     ("fir_gemm_search_topk_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gemm_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_gemm_search_knn_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_gemm_search_radius_keys_dev", C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_gemm_search_few_keys_dev", C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
     ("fir_gemm_stats", C.c_int, [_vp, _i64p, _i64p]),
     ("fir_gemm_stats_ex", C.c_int, [_vp, _i64p]),
@@ -120,6 +123,7 @@ SYMBOLS = [
     ("fir_sharded_search_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_search_topk", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_search_knn", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_sharded_search_radius", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_classify_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_search_top1_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_sync", C.c_int, [_vp]),
@@ -364,6 +368,26 @@ class Gallery:
     def search_knn_keys_dev(self, q_ptr, qb, k, keys_ptr, start=0, end=0, stream=None):
         _check(lib().fir_search_knn_keys_dev(self._h, _vp(q_ptr), qb, start, end, k, _vp(keys_ptr), _vp(stream) if stream else None))
 
+    def search_radius(self, queries, radius, max_results, start=0, end=0):
+        """Every row closer than radius (a scalar, or one per query) to each query: (count, idx, dist). count [qb] is exact
+        however large; idx / dist [qb, max_results] hold the min(count, max_results) nearest of them ascending by (distance,
+        row), unused slots -1 / 100000. max_results = 0: counts only, idx and dist are None."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        qb = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (qb,)))
+        count = np.empty(qb, np.int32)
+        idx = np.empty((qb, max_results), np.int32) if max_results != 0 else None
+        dist = np.empty((qb, max_results), np.float32) if max_results != 0 else None
+        _check(lib().fir_search_radius(self._h, pq, qb, start, end, r.ctypes.data_as(_vp), max_results, count.ctypes.data_as(_vp),
+                                       idx.ctypes.data_as(_vp) if idx is not None else None,
+                                       dist.ctypes.data_as(_vp) if dist is not None else None))
+        return count, idx, dist
+
+    def search_radius_keys_dev(self, q_ptr, qb, radius_ptr, max_results, count_ptr, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_radius_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(radius_ptr), max_results, _vp(count_ptr),
+                                                _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
     def search_top_classes(self, queries, num_classes, k, start=0, end=0):
         """The k nearest distinct classes of each query: (classes, idx, dist), each [qb, k]; unused slots -1 / -1 / 100000."""
         q, pq = _f32(queries)
@@ -593,6 +617,20 @@ class ShardedGallery:
         _check(lib().fir_sharded_search_knn(self._h, pq, q.shape[0], start, end, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
         return idx, dist
 
+    def search_radius(self, queries, radius, max_results, start=0, end=0):
+        """Gallery.search_radius over the shards: global row indices, the unsharded handle's counts and keys."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        qb = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (qb,)))
+        count = np.empty(qb, np.int32)
+        idx = np.empty((qb, max_results), np.int32) if max_results != 0 else None
+        dist = np.empty((qb, max_results), np.float32) if max_results != 0 else None
+        _check(lib().fir_sharded_search_radius(self._h, pq, qb, start, end, r.ctypes.data_as(_vp), max_results, count.ctypes.data_as(_vp),
+                                               idx.ctypes.data_as(_vp) if idx is not None else None,
+                                               dist.ctypes.data_as(_vp) if dist is not None else None))
+        return count, idx, dist
+
     def classify_top1(self, queries, start=0, end=0):
         q, pq = _f32(queries)
         q = q.reshape(-1, self.d)
@@ -663,6 +701,12 @@ class GemmSearch:
     def search_knn_keys_dev(self, q_ptr, qb, k, keys_ptr, stream=None):
         """Gallery.search_knn_keys_dev's keys for k <= GEMM_KNN_MAX through the matrix cores; k > 8 synchronises `stream` once."""
         _check(lib().fir_gemm_search_knn_keys_dev(self._h, _vp(q_ptr), qb, k, _vp(keys_ptr), _vp(stream) if stream else None))
+
+    def search_radius_keys_dev(self, q_ptr, qb, radius_ptr, max_results, count_ptr, keys_ptr, stream=None):
+        """Gallery.search_radius_keys_dev's counts and keys for max_results <= GEMM_KNN_MAX through the matrix cores; synchronises
+        `stream` once."""
+        _check(lib().fir_gemm_search_radius_keys_dev(self._h, _vp(q_ptr), qb, _vp(radius_ptr), max_results, _vp(count_ptr),
+                                                     _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
 
     def stats(self):
         o = (C.c_int64 * 3)()

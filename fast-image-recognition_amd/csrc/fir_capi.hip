@@ -921,9 +921,14 @@ int knn_select_blocks() {
     const int v = e ? atoi(e) : 0;
     return v >= 1 ? std::min(v, kKnnMaxBlocks) : kKnnMaxBlocks;
 }
-int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
-    if (g->n == 0) {                                         // every slot FIR_KEY_NONE (all bytes 0xFF)
-        FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
+// The radius form (fir_search_radius: d_radius and d_count given, k = max_results, 0 included): the same store pass, then per tile
+// the count of the rows inside each query's radius (k_knn_count, into d_count) and the select with each query's own rank
+// min(count, k) -- no digit passes for a query whose rows inside all fit. The second event pair is around count + select + sort.
+int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st,
+            const float* d_radius = nullptr, int32_t* d_count = nullptr) {
+    if (g->n == 0) {                                         // every slot FIR_KEY_NONE (all bytes 0xFF), every count 0
+        if (k > 0) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
+        if (d_count) FIR_HIP(hipMemsetAsync(d_count, 0, (size_t)qb * sizeof(int32_t), st));
         return FIR_OK;
     }
     int t = largest_pow2_le(qb, std::min(effective_qpp(g), 8));
@@ -956,8 +961,9 @@ int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, i
         a.k = k;
         a.ctl = (KnnCtl*)((char*)g->knn.p + plan.dist_bytes);
         a.out = d_keys + (size_t)q0 * k;
+        if (d_radius) { a.radius = d_radius + q0; a.inside = d_count + q0; }
         if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
-        FIR_HIP(knn_select_launch<true>(a, tt, blocks, st));
+        FIR_HIP(d_radius ? (knn_select_launch<true, true>(a, tt, blocks, st)) : (knn_select_launch<true>(a, tt, blocks, st)));
         if ((rc = fir_gallery_profile_end_(g, st, (double)tt * g->n * 4.0))) return rc;
         q0 += tt;
     }
@@ -1129,6 +1135,7 @@ int check_search(const fir_gallery* g, const void* queries, int32_t qb, int32_t&
 }
 int check_k(int32_t k) { return k < 1 || k > kKMax ? fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKMax) : FIR_OK; }
 int check_knn_k(int32_t k) { return knn_k_ok(k) ? FIR_OK : fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kKnnMax); }
+int check_max_results(int32_t m) { return m >= 0 && m <= kKnnMax ? FIR_OK : fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", m, kKnnMax); }
 
 // One call on a handle: its device made current, the stream it queues on (the caller's, else the handle's own: a host-pointer
 // call is a call on the handle's own stream) and its place in the handle's call order (FirCallOrder, which cannot be copied:
@@ -1587,6 +1594,16 @@ int try_mfma_knn(fir_gallery* g, const float* d_queries, int32_t qb, int32_t sta
     if (!wants_mfma(g, qb, start, end, true)) return 1;
     return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_knn_keys_dev(m, d_queries, qb, k, d_keys, st); });
 }
+// ... and for the rows within a radius (fir_search_radius): the ranges of the class form, max_results <= FIR_GEMM_KNN_MAX, and ONLY from a
+// caller's threshold on -- never by itself (profiles/radius_search.txt): 1.75 - 74 x store + count + select while the count fits max_results,
+// but a radius that overflows every list costs 0.09 - 0.78 x (every query answered twice) and 1 000 rows inside at 100 000 rows, 128 queries
+// 0.78 x -- far beyond the spread, and (queries, rows, max_results) do not show how many rows lie near a radius.
+int try_mfma_radius(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const float* d_radius, int32_t max_results,
+                    int32_t* d_count, uint64_t* d_keys, hipStream_t st) {
+    if (max_results > FIR_GEMM_KNN_MAX || g->large_batch_min <= 0) return 1;
+    if (!wants_mfma(g, qb, start, end, true)) return 1;
+    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_radius_keys_dev(m, d_queries, qb, d_radius, max_results, d_count, d_keys, st); });
+}
 }  // namespace
 
 // ---- the matrix-core steps of fir_twd_conventional's batch form (fir_twd.hip; fir_internal.h has the contracts) ----
@@ -2025,6 +2042,52 @@ int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t sta
     if (rc > 0) rc = knn_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream);
     if (rc) return rc;
     return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
+}
+
+// ---- every row within a per-query radius (fir_amd.h) ----
+int fir_search_radius_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* d_radius,
+                               int32_t max_results, int32_t* d_count, uint64_t* d_keys, void* stream) {
+    // (a bad max_results is reported as such, not as a NULL argument: the key pointer is judged once max_results is known to be in range)
+    const bool pointers_ok = d_count != nullptr && (qb <= 0 || d_radius != nullptr) &&
+                             (max_results < 0 || max_results > kKnnMax || (max_results == 0 ? d_keys == nullptr : d_keys != nullptr));
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, max_results, d_keys, call.st, d_radius, d_count);
+}
+
+int fir_search_radius(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* radius, int32_t max_results,
+                      int32_t* count, int32_t* idx, float* dist) {
+    const bool pointers_ok = count != nullptr && (qb <= 0 || radius != nullptr) &&
+                             (max_results < 0 || max_results > kKnnMax || (max_results == 0 ? !idx && !dist : idx && dist));
+    int rc = check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    // behind the keys' slot: the radii in, the counts out
+    const size_t slots = (size_t)qb * max_results;
+    if ((rc = FIR_NEED(g->dkeys, slots + (size_t)qb))) return rc;
+    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    uint64_t* tail = g->dkeys;
+    tail += slots;
+    float* d_radius = (float*)tail;
+    int32_t* d_count = (int32_t*)tail + qb;
+    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    FIR_HIP(hipMemcpyAsync(d_radius, radius, (size_t)qb * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    g->call_launches = 0;
+    g->warm_left = 0;
+    uint64_t* d_keys = slots ? (uint64_t*)g->dkeys : nullptr;
+    rc = try_mfma_radius(g, g->dq, qb, start_pos, end_pos, d_radius, max_results, d_count, d_keys, g->stream);
+    if (rc > 0) rc = knn_dev(g, g->dq, qb, start_pos, end_pos, max_results, d_keys, g->stream, d_radius, d_count);
+    if (rc) return rc;
+    FIR_HIP(hipMemcpyAsync(count, d_count, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (slots == 0) {
+        FIR_HIP(hipStreamSynchronize(g->stream));
+        call.done();
+        return FIR_OK;
+    }
+    return deliver_copied(g, call, slots, nullptr, idx, dist);
 }
 
 namespace {

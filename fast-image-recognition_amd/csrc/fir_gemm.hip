@@ -1487,7 +1487,7 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         static_assert(kRerankLdsMax + 256 * sizeof(unsigned) + fir::kKnnGemmMax * sizeof(unsigned long long) <= 160 * 1024, "k_gemm_rerank_knn's LDS");
         if (gemm_rerank_lds_(m) > 48 * 1024)
             for (const void* fn : {(const void*)k_gemm_rerank<1>, (const void*)k_gemm_rerank<kTopKMax>, (const void*)k_gemm_rerank_classes,
-                                   (const void*)k_gemm_rerank_knn})
+                                   (const void*)k_gemm_rerank_knn, (const void*)k_gemm_rerank_radius})
                 if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRerankLdsMax);
     }
     if (e == hipSuccess && f16) e = gemm_x_lds_attr_();
@@ -1655,6 +1655,8 @@ struct GemmCall {
     int32_t* d_classes;         // minima, the append pass below it, k_gemm_rerank_classes; d_keys or d_classes may then be NULL
     bool knn = false;           // the K > kTopKMax nearest rows (fir_gemm_search_knn_keys_dev, fir_gemm_knn.h): the same flow with the bound from
     int knn_div = fir::kKnnSampleDiv;   // a row sample's exact K-th distance (rows n K / knn_div: FIR_GEMM_KNN_SAMPLE_DIV) and k_gemm_rerank_knn
+    const float* d_radius = nullptr;    // with knn: every row within radius[q] (fir_gemm_search_radius_keys_dev) -- the bound IS the radius, no sample;
+    int32_t* d_count = nullptr;         // k = max_results (0: d_keys is NULL), d_count[q] <- the rows inside; k_gemm_rerank_radius
     hipStream_t st;
     int d, qs;                  // features compared; floats between consecutive queries (and gallery rows): the whole row
     int64_t n;
@@ -1891,8 +1893,9 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
     if (c.knn) {
         // D_s = the exact K-th smallest distance over a row sample spread over the gallery (fir_knn_select.h: knn_sample_plan), turned into
         // the append pass's bound in place; padding queries get -inf
-        const int rc = fir_knn_sample_bound_dev_(m->g, dq, nq, c.d, k, c.knn_div, s.tau, ps);
-        if (rc) return rc;
+        // (the radius form: the query's own radius is the bound -- any value: k_gemm_tau_class's guarantee does not ask where it came from)
+        if (c.d_radius) FIR_HIP(hipMemcpyAsync(s.tau, c.d_radius + (size_t)sb * c.sbq, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, ps));
+        else if (const int rc = fir_knn_sample_bound_dev_(m->g, dq, nq, c.d, k, c.knn_div, s.tau, ps)) return rc;
         hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
         return FIR_OK;
     }
@@ -2052,6 +2055,10 @@ static int gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) 
                            m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
                            c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
                            c.qs, m->rowmajor);
+    else if (c.d_radius)
+        hipLaunchKernelGGL(k_gemm_rerank_radius, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, c.d_radius + q0, m->gal4, c.sb_first(sb), s.qnorm,
+                           m->gmax, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
+                           c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_count + q0, m->ok + q0, c.qs, m->rowmajor);
     else if (c.knn)
         hipLaunchKernelGGL(k_gemm_rerank_knn, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, m->gal4, c.sb_first(sb), s.qnorm, m->gmax, c.n,
                            c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k, (unsigned long long*)c.d_keys + (size_t)q0 * c.k, m->ok + q0, c.qs, m->rowmajor);
@@ -2129,6 +2136,7 @@ static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
 }
 
 // ... and of a K > kTopKMax nearest-rows call (fir_gemm_knn.h): the same, through the store + select form of fir_search_knn_keys_dev
+// (a radius call: keys and counts from fir_search_radius_keys_dev's store + count + select)
 static int gemm_finish_knn_(fir_gemm* m, const GemmCall& c) {
     std::vector<int> h_ok((size_t)c.qb);
     FIR_HIP(hipMemcpyAsync(h_ok.data(), m->ok, (size_t)c.qb * sizeof(int), hipMemcpyDeviceToHost, c.st));
@@ -2138,7 +2146,9 @@ static int gemm_finish_knn_(fir_gemm* m, const GemmCall& c) {
         int q1 = q0;
         while (q1 < c.qb && !h_ok[q1]) ++q1;
         if (q1 == q0) { ++q0; continue; }
-        const int rc = fir_search_knn_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.k, c.d_keys + (size_t)q0 * c.k, c.st);
+        const int rc = c.d_radius ? fir_search_radius_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.d_radius + q0, c.k, c.d_count + q0,
+                                                                c.d_keys ? c.d_keys + (size_t)q0 * c.k : nullptr, c.st)
+                                  : fir_search_knn_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.k, c.d_keys + (size_t)q0 * c.k, c.st);
         if (rc) return rc;
         uncertified += q1 - q0;
         q0 = q1;
@@ -2151,11 +2161,12 @@ static int gemm_finish_knn_(fir_gemm* m, const GemmCall& c) {
 // The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev), or -- num_classes > 0 --
 // the K <= 32 nearest distinct classes (fir_gemm_search_top_classes_keys_dev, which checks its own arguments)
 static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr,
-                       int32_t num_classes = 0, int32_t* d_classes = nullptr, bool knn = false) {
-    if (!m || (!d_keys && !(num_classes > 0 && d_classes)) || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+                       int32_t num_classes = 0, int32_t* d_classes = nullptr, bool knn = false, const float* d_radius = nullptr, int32_t* d_count = nullptr) {
+    // (d_radius: fir_gemm_search_radius_keys_dev, which has checked its own arguments -- k = max_results may be 0 and d_keys NULL then)
+    if (!m || (!d_keys && !(num_classes > 0 && d_classes) && !d_radius) || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     const int k_max = num_classes > 0 ? 32 : knn ? fir::kKnnGemmMax : kTopKMax;
-    if (k < 1 || k > k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, k_max);
+    if ((k < 1 && !d_radius) || k > k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, k_max);
     if (qb == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
@@ -2165,11 +2176,13 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
     c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
     c.num_classes = num_classes; c.d_classes = d_classes;
     c.knn = knn;
-    if (knn)
+    c.d_radius = d_radius; c.d_count = d_count;
+    if (knn && !d_radius)
         if (const char* w = fir_knob_("FIR_GEMM_KNN_SAMPLE_DIV")) c.knn_div = std::max(1, std::atoi(w));
     c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
     if (c.n == 0 && h_queries) FIR_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
     if (c.n == 0 && num_classes > 0) return fir_class_scan_dev_(m->g, d_queries, qb, c.d, num_classes, k, 0, d_keys, d_classes, nullptr, st);   // every slot unused
+    if (c.n == 0 && d_radius) return fir_search_radius_keys_dev(m->g, d_queries, qb, 0, c.d, d_radius, k, d_count, d_keys, st);                 // counts 0, every slot FIR_KEY_NONE
     if (c.n == 0 && knn) return fir_search_knn_keys_dev(m->g, d_queries, qb, 0, c.d, k, d_keys, st);                                      // every slot FIR_KEY_NONE
     if (c.n == 0)
         return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
@@ -2283,6 +2296,20 @@ int fir_gemm_search_knn_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the K > %d nearest-rows form needs a FIR_GEMM_F16 state", kTopKMax);
     if (qb == 0) return FIR_OK;
     return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, 0, nullptr, true);
+}
+
+// Every row within radius[q] (fir_amd.h): the flow of fir_gemm_knn.h without its sample -- tau from the radius, the append pass,
+// k_gemm_rerank_radius; synchronises `stream` once, then the store + count + select form answers what was not certified.
+int fir_gemm_search_radius_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, const float* d_radius, int32_t max_results, int32_t* d_count,
+                                    uint64_t* d_keys, void* stream) {
+    const bool in_range = max_results >= 0 && max_results <= FIR_GEMM_KNN_MAX;
+    if (!m || !d_count || (qb > 0 && (!d_queries || !d_radius)) || (in_range && (max_results == 0 ? d_keys != nullptr : d_keys == nullptr)))
+        return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (!in_range) return fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", max_results, FIR_GEMM_KNN_MAX);
+    if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the radius form needs a FIR_GEMM_F16 state");
+    if (qb == 0) return FIR_OK;
+    return gemm_search(m, d_queries, qb, max_results, d_keys, stream, nullptr, 0, nullptr, true, d_radius, d_count);
 }
 
 // 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one

@@ -10,6 +10,8 @@
 //      keys, and the certificate.
 // What is not certified (a list that overflowed, NaN operands, a tie at the certificate's bound) is answered by the store + select
 // form of fir_search_knn_keys_dev after the call's one synchronisation (gemm_finish_knn_, fir_gemm.hip): no second-chance rounds.
+// fir_gemm_search_radius_keys_dev (every row within a per-query radius) is the same flow without step a: the radius is D_s, and
+// k_gemm_rerank_radius at the end of this file takes the place of k_gemm_rerank_knn.
 #pragma once
 
 // The rank-th smallest (rank >= 1, at most `have`) of the wave's list of `have` unique 64-bit keys, by its top `ndig` bytes: an
@@ -49,6 +51,46 @@ __device__ __forceinline__ unsigned long long wave_list_select_(const unsigned l
         __syncthreads();                                                // the histogram is cleared again by the next digit
     }
     return prefix;
+}
+
+// The k smallest of the wave's list of exact keys (kKeyNone entries take no part), ascending, into out[0..k), kKeyNone behind them:
+// a radix select for the take-th smallest key T, take = min(k, keys there are) -- keys are unique, the row is part of the key, so a
+// cut inside a run of equal distances is exact --, the keys <= T compacted into `sorted` and sorted there. Returns how many keys
+// the list holds (`valid`); sorted[0..min(valid, k)) stays readable. k = 0: only the count.
+__device__ __forceinline__ int wave_list_smallest_(const unsigned long long* L, int have, int k, unsigned* hist, unsigned long long* sorted,
+                                                   unsigned long long* out, int lane) {
+    int valid = 0;
+    for (int base = 0; base < have; base += 64) valid += __popcll(__ballot(base + lane < have && L[base + lane] != kKeyNone));
+    const int take = valid < k ? valid : k;
+    int P = 2;
+    while (P < take) P *= 2;
+    for (int i = lane; i < P; i += 64) sorted[i] = kKeyNone;
+    unsigned long long T = 0;
+    if (take > 0) T = wave_list_select_(L, have, take, 8, hist, lane);  // (ends with a barrier: `sorted` is cleared)
+    else __syncthreads();
+    int filled = 0;
+    for (int base = 0; base < have && take > 0; base += 64) {
+        const unsigned long long v = base + lane < have ? L[base + lane] : kKeyNone;
+        const bool mine = v != kKeyNone && v <= T;
+        const unsigned long long m = __ballot(mine);
+        const int slot = filled + (int)__popcll(m & ((1ull << lane) - 1ull));
+        if (mine && slot < P) sorted[slot] = v;                         // (exactly `take` keys are <= T: the check costs nothing)
+        filled += (int)__popcll(m);
+    }
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < P; i += 64) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const unsigned long long x = sorted[i], y = sorted[o];
+                    if ((x > y) == ((i & k2) == 0)) { sorted[i] = y; sorted[o] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = lane; i < k; i += 64) out[i] = i < take ? sorted[i] : kKeyNone;
+    return valid;
 }
 
 // The K nearest rows (kTopKMax < K <= 256) from the lists of one append pass below k_gemm_tau_class's bound. One wave per query.
@@ -95,40 +137,58 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_knn(unsigned long long* list
     });
     __threadfence_block();                                              // the exact keys, written by other lanes, are read below
     __syncthreads();
-    int valid = 0;
-    for (int base = 0; base < have; base += 64) valid += __popcll(__ballot(base + lane < have && L[base + lane] != kKeyNone));
+    const int valid = wave_list_smallest_(L, have, k, hist, sorted, out, lane);
     const int take = valid < k ? valid : k;
-    int P = 2;
-    while (P < take) P *= 2;
-    for (int i = lane; i < P; i += 64) sorted[i] = kKeyNone;
-    unsigned long long T = 0;
-    if (take > 0) T = wave_list_select_(L, have, take, 8, hist, lane);  // (ends with a barrier: `sorted` is cleared)
-    else __syncthreads();
-    int filled = 0;
-    for (int base = 0; base < have && take > 0; base += 64) {
-        const unsigned long long v = base + lane < have ? L[base + lane] : kKeyNone;
-        const bool mine = v != kKeyNone && v <= T;
-        const unsigned long long m = __ballot(mine);
-        const int slot = filled + (int)__popcll(m & ((1ull << lane) - 1ull));
-        if (mine && slot < P) sorted[slot] = v;                         // (exactly `take` keys are <= T: the check costs nothing)
-        filled += (int)__popcll(m);
-    }
-    __syncthreads();
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < P; i += 64) {
-                const int o = i ^ j;
-                if (o > i) {
-                    const unsigned long long x = sorted[i], y = sorted[o];
-                    if ((x > y) == ((i & k2) == 0)) { sorted[i] = y; sorted[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = lane; i < k; i += 64) out[i] = i < take ? sorted[i] : kKeyNone;
     if (lane == 0) {    // (fewer than K found: any qualifying row outside the re-ranked set would belong to the answer)
         const unsigned long long kth_exact = take == k ? sorted[k - 1] : kKeyNone;
         ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, kth_exact != kKeyNone, fir::f32_from_orderable((uint32_t)(kth_exact >> 32)), n,
                                          walk.reranked) ? 1 : 0;
+    }
+}
+
+// Every row within a per-query radius (fir_gemm_search_radius_keys_dev) from the lists of one append pass below k_gemm_tau_class's
+// bound on radius[q] -- the query brings its bound, no row sample is scanned. One wave per query.
+//   1. a list that overflowed is not certified: the store + count + select form answers the query.
+//   2. EVERY entry is re-ranked in the reference's arithmetic (rerank_gather_f32_; the window is +inf) and its exact key written
+//      back over its list entry; rows with dist < radius or dist < 100000 false become kKeyNone. count[q] = the keys left.
+//   3. the min(count, k) smallest exact keys, ascending, padded with kKeyNone (wave_list_smallest_; k = 0: the count alone).
+// Certificate: rerank_certified_ with the radius in the place of the K-th exact distance (the cut-off 100000 for a radius at or
+// above it, or NaN). A row never appended has a proxy >= tau, hence a reference distance >= (|q|^2 + tau) / d - E, which the
+// certificate finds above the radius: `dist < radius` is false for it, it is not part of the answer, and every row that is was
+// appended, re-ranked exactly and counted. Strict '>': a NaN bound certifies nothing.
+__global__ void __launch_bounds__(64) k_gemm_rerank_radius(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
+                                                            const float* __restrict__ radius, const float4* __restrict__ gal4,
+                                                            const float* __restrict__ queries, const float* __restrict__ qnorm,
+                                                            const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset, float e_rel,
+                                                            int ngroup, int k, unsigned long long* __restrict__ out_key, int* __restrict__ out_count,
+                                                            int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long sorted[fir::kKnnGemmMax];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int cnt = counts[q];
+    if (cnt > kListCap) {                           // rows below tau were dropped: the exact form answers this query
+        if (lane == 0) ok[q] = 0;
+        return;
+    }
+    const int have = cnt;
+    unsigned long long* L = lists + (size_t)q * kListCap;
+    unsigned long long* out = out_key + (size_t)q * k;                  // (k = 0: never written)
+    const float qn = qnorm[q], gmax = gnorm_max_p[0], r = radius[q];
+    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, __builtin_huge_valf());
+    extern __shared__ __attribute__((aligned(16))) float4 crow[];
+    const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)q * qstride, lane);
+    const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int base, unsigned long long v, bool in, unsigned long long mask) {
+        if (base + lane < have && !in) L[base + lane] = kKeyNone;       // (a NaN proxy: never appended)
+        rerank_gather_f32_(mask, v, base, lane, ngroup, lds, gal4, rowmajor, dp4, d, [&](int i, unsigned long long cv, float dist) {
+            const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
+            L[i] = dist < r && dist < fir::kNotFound ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
+        });
+    });
+    __threadfence_block();                                              // the exact keys, written by other lanes, are read below
+    __syncthreads();
+    const int valid = wave_list_smallest_(L, have, k, hist, sorted, out, lane);
+    if (lane == 0) {
+        out_count[q] = valid;
+        ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, r < fir::kNotFound, r, n, walk.reranked) ? 1 : 0;
     }
 }

@@ -1,6 +1,8 @@
 // fir_knn_select.h -- the K smallest of many packed keys, exactly: an MSB-first radix select over 64-bit keys, then a sort of
-// the K survivors. Two users: fir_search_knn (fir_capi.hip: the keys are (orderable(distance), row) over a stored distance row)
-// and the sharded handle's merge for K > 8 (fir_shard.hip: the keys are the ranks' gathered keys). The digit histogram, the rank
+// the K survivors. Three users: fir_search_knn (fir_capi.hip: the keys are (orderable(distance), row) over a stored distance row),
+// fir_search_radius (the same with `dist < radius[q]` in the qualification, a count of the qualifying rows in front and each query's
+// own rank min(count, max_results): the RADIUS forms below) and the sharded handle's merge for K > 8 (fir_shard.hip: the keys are
+// the ranks' gathered keys). The digit histogram, the rank
 // step and the prefix test are the ones fir_dem.hip's select (k_dem_select_one / k_dem_select_pass) has always used: they live here
 // and fir_dem.hip includes them.
 //
@@ -221,11 +223,14 @@ struct KnnCtl {
     unsigned hist[8][kKnnTile][256];
     SelState sel[8][kKnnTile];       // [p]: the state before digit p (p >= 1; before digit 0 it is {0, rank, 0})
     int32_t count[kKnnTile];         // keys compacted so far
+    int32_t inside[kKnnTile];        // radius form: the rows that qualify (k_knn_count), however many
 };
 
 // Where the keys come from. dist != NULL: a row of float32 distances per query, dist[q * stride + i], i < n: key i is
 // key_pack(dist, i + row_offset) when dist < 100000, FIR_KEY_NONE otherwise (stride a multiple of 4, dist 16-byte aligned).
 // dist == NULL: parts of ascending key lists, keys[p * stride + q * k_in + j], j < k_in, p < n / k_in (the sharded merge).
+// The radius form (RADIUS, fir_search_radius; dist != NULL): a row qualifies only when dist < radius[q] is true as well, and the
+// rank is each query's own, min(ctl->inside[q], k), read on the device: `rank` is not used.
 struct KnnArgs {
     const float* dist;
     const uint64_t* keys;
@@ -238,15 +243,20 @@ struct KnnArgs {
     int32_t rank;          // min(k, n)
     KnnCtl* ctl;
     uint64_t* out;         // [nq][k]
+    const float* radius;   // [nq] (radius form)
+    int32_t* inside;       // [nq] <- ctl->inside (radius form)
 };
 
 // f(valid, key) for every key of this workgroup's slice of query q, wave-uniformly (every lane of a wave makes every call).
-template <bool DIST, typename F>
+template <bool DIST, bool RADIUS, typename F>
 __device__ __forceinline__ void knn_slice_keys(const KnnArgs& a, int q, F f) {
+    static_assert(DIST || !RADIUS, "a radius is a bound on stored distances");
     const int64_t begin = (int64_t)blockIdx.x * a.slice;
     const int64_t end = begin + a.slice < a.n ? begin + a.slice : a.n;
     if constexpr (DIST) {
         const float* __restrict__ row = a.dist + (size_t)q * a.stride;
+        float radius = 0.0f;
+        if constexpr (RADIUS) radius = a.radius[q];
         for (int64_t i0 = begin; i0 < end; i0 += 4 * kBlock) {
             const int64_t i = i0 + 4 * (int64_t)threadIdx.x;
             float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -255,7 +265,9 @@ __device__ __forceinline__ void knn_slice_keys(const KnnArgs& a, int q, F f) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const bool valid = i + c < end;
-                f(valid, valid && d4[c] < kNotFound ? key_pack(d4[c], (uint32_t)(i + c + a.row_offset)) : kKeyNone);
+                bool inside = valid && d4[c] < kNotFound;
+                if constexpr (RADIUS) inside = inside && d4[c] < radius;      // (false for a NaN radius)
+                f(valid, inside ? key_pack(d4[c], (uint32_t)(i + c + a.row_offset)) : kKeyNone);
             }
         }
     } else {
@@ -272,42 +284,65 @@ __device__ __forceinline__ void knn_slice_keys(const KnnArgs& a, int q, F f) {
     }
 }
 
-// The state before digit `pass` (pass in 1..8), as every workgroup works it out.
-__device__ __forceinline__ SelState knn_state(const KnnArgs& a, int q, int pass, unsigned* wsum, SelState* box) {
-    SelState s = pass == 1 ? SelState{0ull, a.rank, 0} : a.ctl->sel[pass - 1][q];
+// The state before digit `pass` (pass in 1..8), as every workgroup works it out. rank: the query's (a.rank, or a.k in the radius form).
+__device__ __forceinline__ SelState knn_state(const KnnArgs& a, int q, int pass, int32_t rank, unsigned* wsum, SelState* box) {
+    SelState s = pass == 1 ? SelState{0ull, rank, 0} : a.ctl->sel[pass - 1][q];
     return sel_advance(s, a.ctl->hist[pass - 1][q][threadIdx.x], pass - 1, wsum, box);
 }
 
-template <bool DIST>
+// Radius form: ctl->inside[q] += the rows of this workgroup's slice that qualify. k_knn_select's grid.
+static __global__ void __launch_bounds__(kBlock) k_knn_count(const KnnArgs a) {
+    __shared__ int wcount[kBlock / 64];
+    const int q = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int mine = 0;
+    knn_slice_keys<true, true>(a, q, [&](bool, uint64_t key) { mine += key != kKeyNone; });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    if (lane == 0) wcount[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+        for (int w = 0; w < kBlock / 64; ++w) sum += wcount[w];
+        if (sum) atomicAdd(&a.ctl->inside[q], sum);
+    }
+}
+
+template <bool DIST, bool RADIUS>
 __global__ void __launch_bounds__(kBlock) k_knn_select(const KnnArgs a, int pass) {
     __shared__ unsigned hist[256];
     __shared__ unsigned wsum[kBlock / 64];
     __shared__ SelState box;
     const int q = blockIdx.y;
-    SelState s{0ull, a.rank, 0};
+    int32_t rank = a.rank;
+    if constexpr (RADIUS) {
+        if (a.ctl->inside[q] <= a.k) return;          // (uniform) everything that qualifies is selected: no threshold to find
+        rank = a.k;
+    }
+    SelState s{0ull, rank, 0};
     if (pass > 0) {
-        s = knn_state(a, q, pass, wsum, &box);
+        s = knn_state(a, q, pass, rank, wsum, &box);
         if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->sel[pass][q] = s;
     }
     if (s.done) return;
     hist[threadIdx.x] = 0;
     __syncthreads();
     const int shift = 56 - 8 * pass;
-    knn_slice_keys<DIST>(a, q, [&](bool valid, uint64_t key) {
+    knn_slice_keys<DIST, RADIUS>(a, q, [&](bool valid, uint64_t key) {
         hist_add(hist, valid && sel_match(key, s.prefix, pass), (unsigned)(key >> shift) & 255u);
     });
     __syncthreads();
     if (hist[threadIdx.x]) atomicAdd(&a.ctl->hist[pass][q][threadIdx.x], hist[threadIdx.x]);
 }
 
-template <bool DIST>
+template <bool DIST, bool RADIUS>
 __global__ void __launch_bounds__(kBlock) k_knn_compact(const KnnArgs a) {
     __shared__ unsigned wsum[kBlock / 64];
     __shared__ SelState box;
     const int q = blockIdx.y, lane = threadIdx.x & 63;
-    const uint64_t T = knn_state(a, q, 8, wsum, &box).prefix;
+    uint64_t T = kKeyNone;                                                // radius form, at most k rows inside: all of them
+    if (!RADIUS || a.ctl->inside[q] > a.k) T = knn_state(a, q, 8, RADIUS ? a.k : a.rank, wsum, &box).prefix;
     uint64_t* __restrict__ out = a.out + (size_t)q * a.k;
-    knn_slice_keys<DIST>(a, q, [&](bool valid, uint64_t key) {
+    knn_slice_keys<DIST, RADIUS>(a, q, [&](bool valid, uint64_t key) {
         const bool take = valid && key <= T && key != kKeyNone;
         const unsigned long long m = __ballot(take);
         if (m == 0) return;                                               // wave-uniform
@@ -346,15 +381,22 @@ static __global__ void __launch_bounds__(kBlock) k_knn_sort(const KnnArgs a) {
 
 // Queue the select for nq <= kKnnTile queries on st: a.ctl is cleared, then eight digit launches, the compaction and the sort.
 // a.n >= 1. Nothing here synchronises. max_blocks: workgroups per query at most (kKnnMaxBlocks; 1 = the one-workgroup form).
-template <bool DIST>
+// RADIUS: the count goes first and a.inside[0..nq) receives it; a.k == 0 ends there (the count-only call).
+template <bool DIST, bool RADIUS = false>
 inline hipError_t knn_select_launch(KnnArgs a, int nq, int max_blocks, hipStream_t st) {
     a.slice = knn_slice(a.n, max_blocks);
     a.rank = (int32_t)(a.n < a.k ? a.n : a.k);
     const dim3 grid((unsigned)((a.n + a.slice - 1) / a.slice), (unsigned)nq);
     hipError_t e = hipMemsetAsync(a.ctl, 0, sizeof(KnnCtl), st);
     if (e != hipSuccess) return e;
-    for (int pass = 0; pass < 8; ++pass) hipLaunchKernelGGL(k_knn_select<DIST>, grid, dim3(kBlock), 0, st, a, pass);
-    hipLaunchKernelGGL(k_knn_compact<DIST>, grid, dim3(kBlock), 0, st, a);
+    if constexpr (RADIUS) {
+        hipLaunchKernelGGL(k_knn_count, grid, dim3(kBlock), 0, st, a);
+        e = hipMemcpyAsync(a.inside, a.ctl->inside, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return e;
+        if (a.k == 0) return hipGetLastError();
+    }
+    for (int pass = 0; pass < 8; ++pass) hipLaunchKernelGGL((k_knn_select<DIST, RADIUS>), grid, dim3(kBlock), 0, st, a, pass);
+    hipLaunchKernelGGL((k_knn_compact<DIST, RADIUS>), grid, dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(k_knn_sort, dim3(nq), dim3(kBlock), 0, st, a);
     return hipGetLastError();
 }

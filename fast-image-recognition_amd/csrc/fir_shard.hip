@@ -143,6 +143,18 @@ __global__ void __launch_bounds__(256) k_shard_fill_u64(uint64_t* p, int n, uint
     if (i < n) p[i] = v;
 }
 
+// out[q] = sum over parts p of parts[p * stride + q], q < qb: the rows inside each query's radius (fir_sharded_search_radius), over the
+// shards of one device and then over the ranks. The counts ride behind the keys in whole 64-bit words: with an odd qb the last
+// half word is kept 0.
+__global__ void __launch_bounds__(256) k_shard_sum_counts(const int32_t* __restrict__ parts, int nparts, size_t stride, int qb, int32_t* __restrict__ out) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= qb + (qb & 1)) return;
+    int32_t sum = 0;
+    if (q < qb)
+        for (int p = 0; p < nparts; ++p) sum += parts[(size_t)p * stride + q];
+    out[q] = sum;
+}
+
 using fir::KeptError;
 
 struct Shard {
@@ -357,11 +369,16 @@ int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
 // The buffers of one call on one device, grown in the call's agreed step, in bytes: queries (host-pointer form), the shards'
 // partial keys, the reduced keys + status element, the gathered keys of all ranks (top-K), the winners' classes + status
 // element and the control block of the K > 8 merge. Every device holds h->spd shards, so the sizes are every device's.
+// A radius call (fir_sharded_search_radius, k = max_results, 0 included) carries qb counts as well: the radii behind the queries,
+// every shard's counts behind all the shards' keys, and the device's counts in count_words(qb) 64-bit words between its keys and
+// the status element -- one payload, one ncclAllGather.
 struct CallBuffers { size_t dq, parts, keys, gath, cls, sel; };
-CallBuffers call_buffers(const fir_sharded* h, int32_t qb, int32_t k, bool host_queries, bool classes) {
-    const size_t per = (size_t)qb * k, u64 = sizeof(uint64_t);
-    return {host_queries ? (size_t)qb * h->d * sizeof(float) : 0, per * (size_t)h->spd * u64, (per + 1) * u64,
-            k > 1 ? (per + 1) * (size_t)h->nranks * u64 : 0, classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
+inline size_t count_words(int32_t qb, bool radius) { return radius ? ((size_t)qb + 1) / 2 : 0; }
+CallBuffers call_buffers(const fir_sharded* h, int32_t qb, int32_t k, bool host_queries, bool classes, bool radius = false) {
+    const size_t per = (size_t)qb * k, u64 = sizeof(uint64_t), payload = per + count_words(qb, radius);
+    return {host_queries ? ((size_t)qb * h->d + (radius ? (size_t)qb + (qb & 1) : 0)) * sizeof(float) : 0,
+            (per + count_words(qb, radius)) * (size_t)h->spd * u64, (payload + 1) * u64,
+            k > 1 || radius ? (payload + 1) * (size_t)h->nranks * u64 : 0, classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
             k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 * u64 : 0};
 }
 // Does this call grow anything? Asked ONCE per call, before the fan-out over the devices, of device slot 0's capacities (and
@@ -410,11 +427,14 @@ int merge_knn(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t
 }
 
 // The keys of one device: every shard it holds scans the batch (K keys per query, K = 1: top-1), then the minimum /
-// K-way merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc).
-int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st, bool knn = false) {
+// K-way merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc). d_radius: the radius call -- every shard's
+// fir_search_radius_keys_dev with global rows, the sum of their counts in the words behind the keys.
+int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st, bool knn = false,
+                const float* d_radius = nullptr) {
     DevCtx& dc = h->devs[slot];
     uint64_t *parts = dc.parts.as<uint64_t>(), *keys = dc.keys.as<uint64_t>();
     const size_t per = (size_t)qb * k;
+    int32_t* cparts = (int32_t*)(parts + per * (size_t)h->spd);              // [shard here][qb]
     int rc;
     int live = 0;
     for (size_t i = 0; i < dc.shards.size(); ++i) {
@@ -423,13 +443,16 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
             return fir_fail_(FIR_ERR_NOMEM, "injected scan failure on shard %d (fir_shard_opts.fail_step = 1)", dc.shards[i]);
         if (!s.g) continue;
         uint64_t* out = parts + (size_t)live * per;
-        rc = k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
+        rc = d_radius ? fir_search_radius_keys_dev(s.g, d_queries, qb, start, end, d_radius, k, cparts + (size_t)live * qb, k ? out : nullptr, st)
+             : k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
              : knn  ? fir_search_knn_keys_dev(s.g, d_queries, qb, start, end, k, out, st)
                     : fir_search_topk_keys_dev(s.g, d_queries, qb, start, end, k, out, st);
         if (rc) return rc;
         ++live;
     }
-    if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
+    if (d_radius) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, cparts, live, (size_t)qb, qb, (int32_t*)(keys + per));
+    if (per == 0) {}                                                         // the count-only call
+    else if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
     else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, parts, live, (int)per, keys);
     else if (k > kMergeListMax) { if ((rc = merge_knn(dc, parts, live, qb, k, keys, per, nullptr, st))) return rc; }
     else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, parts, live, qb, k, keys, per, (uint64_t*)nullptr);
@@ -439,13 +462,16 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
 
 // The exchange step over all ranks, on `st`, result in dc.keys (in place); dc.keys[qb * k] carries local_rc in and the worst
 // status of all ranks out. A rank whose scans failed contributes FIR_KEY_NONE keys. Errors here kill the communicator.
-int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t st, int local_rc) {
+// radius: the counts travel between the keys and the status element (which is then dc.keys[qb * k + count_words]) in the same
+// ncclAllGather -- for every k, 0 and 1 included --, and the ranks' counts are summed in place.
+int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t st, int local_rc, bool radius = false) {
     DevCtx& dc = h->devs[slot];
     uint64_t *keys = dc.keys.as<uint64_t>(), *gath = dc.gath.as<uint64_t>();
-    const size_t per = (size_t)qb * k;
+    const size_t per = (size_t)qb * k, payload = per + count_words(qb, radius);
     const bool prof = h->profiling && slot == 0;
-    if (local_rc) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
-    hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + per, status_key(local_rc));
+    if (local_rc && per) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
+    if (local_rc && radius) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, (const int32_t*)nullptr, 0, (size_t)0, qb, (int32_t*)(keys + per));
+    hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + payload, status_key(local_rc));
     if (prof) {
         if (dc.ev_used + 2 > dc.evs.size())
             for (int i = 0; i < 64; ++i) {
@@ -456,24 +482,31 @@ int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t s
         if (dc.ev_used + 2 <= dc.evs.size()) (void)hipEventRecord(dc.evs[dc.ev_used], st);
     }
     ncclResult_t nr;
-    if (k == 1) {
+    if (k == 1 && !radius) {
         nr = ncclAllReduce(keys, keys, per + 1, ncclUint64, ncclMin, dc.comm, st);
     } else {
-        nr = ncclAllGather(keys, gath, per + 1, ncclUint64, dc.comm, st);
+        nr = ncclAllGather(keys, gath, payload + 1, ncclUint64, dc.comm, st);
+        // (the merges find the status element right behind the keys; behind the counts it is taken by itself)
+        uint64_t* status_out = radius ? nullptr : keys + per;
+        if (nr == ncclSuccess && radius) {
+            hipLaunchKernelGGL(k_shard_min_status, dim3(1), dim3(64), 0, st, gath + payload, h->nranks, payload + 1, keys + payload);
+            hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, (const int32_t*)(gath + per), h->nranks, 2 * (payload + 1), qb,
+                               (int32_t*)(keys + per));
+        }
         if (nr == ncclSuccess && k > kMergeListMax) {
-            if (merge_knn(dc, gath, h->nranks, qb, k, keys, per + 1, keys + per, st)) {
+            if (merge_knn(dc, gath, h->nranks, qb, k, keys, payload + 1, status_out, st)) {
                 const std::string why = fir_last_error();
                 return comm_dead(dc, h->health, FIR_ERR_HIP, why.c_str());
             }
-        } else if (nr == ncclSuccess)
-            hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, gath, h->nranks, qb, k, keys, per + 1, keys + per);
+        } else if (nr == ncclSuccess && k > 0)
+            hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, gath, h->nranks, qb, k, keys, payload + 1, status_out);
     }
     if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
 #ifdef FIR_AUDIT
     // fail_step = 3 (audit build): from the handle's SECOND exchange on the status element comes BACK poisoned, as if a peer's scan had
     // failed -- this rank's own work is fine (the first call of a handle grows its buffers in the agreed, blocking step: a test of the
     // asynchronous path needs one clean call in front)
-    if (inject_here(h, dc, 3) && h->health.exchanges_done++ >= 1) hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + per, status_key(FIR_ERR_NOMEM));
+    if (inject_here(h, dc, 3) && h->health.exchanges_done++ >= 1) hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + payload, status_key(FIR_ERR_NOMEM));
 #endif
     if (prof && dc.ev_used + 2 <= dc.evs.size()) {
         (void)hipEventRecord(dc.evs[dc.ev_used + 1], st);
@@ -509,12 +542,16 @@ int dead_handle(const Health& hl) {
 }
 
 // Host-pointer search: queries go to every device from pinned memory, keys (and classes) come back from device slot 0.
+// count != NULL: the radius call (fir_sharded_search_radius: k = max_results, radius[qb] in, count[qb] out).
 int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, int32_t k, int32_t* idx, float* dist,
-                int32_t* class_out, bool knn = false) {
+                int32_t* class_out, bool knn = false, const float* radius = nullptr, int32_t* count = nullptr) {
+    const bool rad = count != nullptr;
     if (!h || (qb > 0 && !queries) || (knn && (!idx || !dist))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (rad && ((qb > 0 && !radius) || (k >= 1 && k <= FIR_KNN_MAX && (!idx || !dist)) || (k == 0 && (idx || dist)))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    const int kmax = knn ? FIR_KNN_MAX : 8;
-    if (k < 1 || k > kmax) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kmax);
+    const int kmax = knn || rad ? FIR_KNN_MAX : 8;
+    if (rad && (k < 0 || k > kmax)) return fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", k, kmax);
+    if (!rad && (k < 1 || k > kmax)) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kmax);
     if ((int64_t)qb * k >= ((int64_t)1 << 31)) return fir_fail_(FIR_ERR_ARG, "qb * k = %lld keys do not fit 32-bit counts", (long long)qb * k);
     if (class_out && !h->has_labels) return fir_fail_(FIR_ERR_STATE, "the sharded gallery was created without class labels");
     if (h->health.dead) return dead_handle(h->health);
@@ -522,14 +559,15 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
     int rc = check_range(h, start, end);
     if (rc) return rc;
     // (argument errors above are the same on every rank: nobody has entered a collective yet)
-    const size_t per = (size_t)qb * k;
-    const size_t qbytes = (size_t)qb * h->d * sizeof(float), kbytes = (per + 1) * sizeof(uint64_t), cbytes = ((size_t)qb + 1) * sizeof(int32_t);
+    const size_t per = (size_t)qb * k, payload = per + count_words(qb, rad);
+    const size_t rbytes = rad ? ((size_t)qb + (qb & 1)) * sizeof(float) : 0;           // the radii ride behind the queries, in whole 8 bytes
+    const size_t qbytes = (size_t)qb * h->d * sizeof(float) + rbytes, kbytes = (payload + 1) * sizeof(uint64_t), cbytes = ((size_t)qb + 1) * sizeof(int32_t);
     // the pinned staging area is part of the agreed growth as well: slot 0 tries it inside the step
     float* hq = nullptr;
     uint64_t* hk = nullptr;
     int32_t* hc = nullptr;
     fir::Published staged;                                                   // slot 0: the staging area is there (or is not)
-    const CallBuffers nb = call_buffers(h, qb, k, true, class_out != nullptr);
+    const CallBuffers nb = call_buffers(h, qb, k, true, class_out != nullptr, rad);
     const bool grows = call_grows(h->devs[0], nb) || qbytes + kbytes + cbytes > h->pin.cap;   // once, before the fan-out (see call_grows)
     rc = h->devs.run_all([&](int slot) -> int {
         DevCtx& dc = h->devs[slot];
@@ -546,7 +584,11 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
                 hq = h->pin.as<float>();
                 hk = (uint64_t*)(h->pin.as<char>() + qbytes);
                 hc = (int32_t*)(h->pin.as<char>() + qbytes + kbytes);
-                std::memcpy(hq, queries, qbytes);
+                std::memcpy(hq, queries, qbytes - rbytes);
+                if (rad) {
+                    std::memset(hq + (size_t)qb * h->d, 0, rbytes);
+                    std::memcpy(hq + (size_t)qb * h->d, radius, (size_t)qb * sizeof(float));
+                }
             }
             staged.publish(r);
         } else {
@@ -557,26 +599,27 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
         // from here on every rank takes part in every collective of the call, whatever happens to it
         keep_local(c, hipMemcpyAsync(dc.dq.p, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess
                           ? fir_fail_(FIR_ERR_HIP, "query upload failed")
-                          : device_keys(h, slot, dc.dq.as<float>(), qb, start, end, k, dc.stream, knn));
+                          : device_keys(h, slot, dc.dq.as<float>(), qb, start, end, k, dc.stream, knn, rad ? dc.dq.as<float>() + (size_t)qb * h->d : nullptr));
         uint64_t* keys = dc.keys.as<uint64_t>();
-        if ((r = exchange_keys(h, slot, qb, k, dc.stream, c.local))) return r;
+        if ((r = exchange_keys(h, slot, qb, k, dc.stream, c.local, rad))) return r;
         if (class_out && (r = device_classes(h, slot, keys, qb, dc.stream, c.local))) return r;
         if (slot == 0) {
             (void)hipMemcpyAsync(hk, keys, kbytes, hipMemcpyDeviceToHost, dc.stream);
             if (class_out) (void)hipMemcpyAsync(hc, dc.cls.p, cbytes, hipMemcpyDeviceToHost, dc.stream);
         } else {
-            (void)hipMemcpyAsync(dc.hstat() + 1, keys + per, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);   // low word of the status element
+            (void)hipMemcpyAsync(dc.hstat() + 1, keys + payload, sizeof(int32_t), hipMemcpyDeviceToHost, dc.stream);   // low word of the status element
         }
         if ((r = wait_stream(dc, dc.stream, h->health))) return r;
         return verdict(c, FIR_OK);                 // (the peers' status is slot 0's to read, below)
     });
     if (rc) return call_done(h->health, rc);
-    int all = status_code(hk[per]);
+    int all = status_code(hk[payload]);
     if (!all && class_out && hc[qb] != 0x7FFFFFFF) all = hc[qb];
     if ((rc = peer_verdict(h->health, all))) return rc;
     if (class_out)
         for (int i = 0; i < qb; ++i) class_out[i] = hc[i] == 0x7FFFFFFF ? -1 : hc[i];     // ImageTesting.cpp:63: no row found -> -1
-    if (idx || dist) return fir_keys_unpack(hk, qb * k, idx, dist);
+    if (rad) std::memcpy(count, hk + per, (size_t)qb * sizeof(int32_t));
+    if ((idx || dist) && per) return fir_keys_unpack(hk, qb * k, idx, dist);
     return FIR_OK;
 }
 
@@ -1128,6 +1171,12 @@ int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, in
 int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
                            float* dist) {
     return search_host(h, queries, qb, start_pos, end_pos, k, idx, dist, nullptr, true);
+}
+
+int fir_sharded_search_radius(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* radius,
+                              int32_t max_results, int32_t* count, int32_t* idx, float* dist) {
+    if (!count) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    return search_host(h, queries, qb, start_pos, end_pos, max_results, idx, dist, nullptr, false, radius, count);
 }
 
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* class_out,

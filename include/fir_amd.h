@@ -204,6 +204,49 @@ int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t sta
 int fir_search_knn_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                             uint64_t* d_keys, void* stream);
 
+/* ---- every row within a per-query radius --------------------------------------------------------
+ * The exhaustive answer behind the reference's acceptance rules, which are distance thresholds: DirectedEnumeration stops at the
+ * first row with bestDistance < threshold (ann.cpp:390-400), getThreshold places that threshold at a false-accept rate over
+ * other-class distances (ann.cpp:84-93), ProposedTWDClassifier keeps the rows within best / threshold (ImageTesting.cpp:256-266).
+ * Per query q, over features [start_pos, end_pos) (end_pos = 0: d), any metric: a row qualifies iff `dist < radius[q]` and
+ * `dist < 100000.0f` are both true as float compares -- the strict < of ann.cpp:396 and the cut-off of every other search. NaN
+ * distances never qualify; a NaN, zero or negative radius qualifies nothing; a radius >= 100000 (+inf included) qualifies every
+ * row fir_search_knn would consider. count[q] <- the number of qualifying rows, exact however large, never capped by max_results.
+ * idx / dist [qb*max_results] <- the min(count[q], max_results) smallest packed keys (orderable(distance bits) << 32) |
+ * uint32(row + row offset) of the qualifying rows, ascending -- equal distances by ascending row --, FIR_KEY_NONE (idx -1,
+ * dist 100000) behind them: with radius = +inf they are fir_search_knn's for k = max_results bit for bit, and two calls return
+ * the same bytes. 0 <= max_results <= FIR_KNN_MAX (else FIR_ERR_ARG, "max_results=%d outside [0,1024]"); 0 is the count-only
+ * call, where idx and dist must be NULL; otherwise both are required. count and radius [qb] are always required. Arguments are
+ * checked in the order of the other searches (NULL, qb < 0, max_results, qb == 0: nothing to do, the range) before anything is
+ * allocated or queued. An empty gallery: counts 0, every slot FIR_KEY_NONE.
+ * Form: fir_search_knn's store + select with a count in between. Per tile of up to 8 queries ONE exact gallery scan stores the
+ * tile's distances (fir_range_distances' pass and bits); a count kernel reads them once (4 bytes per row and query) and leaves each
+ * query's number of qualifying rows; the radix select then runs with each query's own rank min(count, max_results), read on the
+ * device: a query whose qualifying rows all fit needs no digit passes (its threshold is "everything that qualifies"), max_results
+ * = 0 stops after the count. Scratch and its halving as for fir_search_knn. With fir_profile_enable on, fir_profile_read returns
+ * two durations per tile of queries: the store pass, then count + select + sort. fir_gallery_last_dispatch does not describe it.
+ * Matrix-core form: an L2 batch with max_results <= FIR_GEMM_KNN_MAX over features [0, end_pos) -- whole rows, or a prefix with
+ * end_pos % 16 == 0 and end_pos >= 64 -- goes through fir_gemm_search_radius_keys_dev (same counts and keys, see there) ONLY with
+ * fir_gallery_set_large_batch_mfma(g, min_queries > 0), from the caller's threshold on, as fir_search_knn routes under a
+ * threshold; never with threshold 0 or FIR_SHADOW_NONE, and never by itself. fir_gallery_last_dispatch describes a routed call as
+ * it does a routed fir_search_knn call. Why the default is "never" (profiles/radius_search.txt: whole host-pointer calls at 100 000 x
+ * 512 and 1M x 512, 128 / 1 024 / 8 192 queries, radii at the K-th distance, K in {1, 9, 64, 256}, max_results = K): the matrix-core
+ * form is 1.75 - 74 x the store + count + select form at every such point, but a default needs 1.15 x at every point of a class the
+ * code can observe (queries, rows, max_results) AND an overflow case that loses no more than the spread -- and with 1 000 rows
+ * inside the radius (max_results 256) it is 0.78 x at 100 000 rows and 128 queries, and with a radius that overflows every list
+ * (4 096 entries; every query is then answered twice) 0.12 / 0.64 / 0.78 x at 100 000 rows and 0.09 / 0.48 / 0.64 x at 1M. How many
+ * rows lie near a radius is not visible beforehand. A later default would rest on a cheap count estimate and the same measurements
+ * (tools/radius_search_probe.py). The store + count + select form itself takes 0.83 - 0.96 x the time of fir_search_knn(k =
+ * max_results)'s store + select while the count fits max_results and 1.03 - 1.10 x when it does not.
+ * fir_search_radius_keys_dev and fir_sharded_search_radius always keep the store + count + select form. */
+int fir_search_radius(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                      const float* radius, int32_t max_results, int32_t* count, int32_t* idx, float* dist);
+/* Device-resident, asynchronous on `stream` (NULL: the handle's own), in the handle's call order like every *_dev call; never
+ * synchronises once its scratch is large enough. d_radius[qb], d_count[qb]; d_keys[qb*max_results] ascending per query,
+ * FIR_KEY_NONE for unused slots (NULL with max_results = 0). */
+int fir_search_radius_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                               const float* d_radius, int32_t max_results, int32_t* d_count, uint64_t* d_keys, void* stream);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
@@ -518,6 +561,19 @@ int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, in
  * (fir_gemm_stats_ex counts them in out[1] and out[2]). Argument checks in the order of the other fir_gemm_search_* calls. */
 #define FIR_GEMM_KNN_MAX 256
 int fir_gemm_search_knn_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream);
+/* The counts and keys of fir_search_radius_keys_dev, bit for bit, for the feature range the state covers (whole rows or its prefix),
+ * through the matrix cores: the rows inside DirectedEnumeration's threshold (ann.cpp:390-400). A FIR_GEMM_F16 state, L2,
+ * 0 <= max_results <= FIR_GEMM_KNN_MAX (else FIR_ERR_ARG, "max_results=%d outside [0,256]"); d_keys NULL exactly when max_results = 0.
+ * The flow of fir_gemm_search_knn_keys_dev without its row sample -- the query brings its bound: the radius, in proxy units plus one
+ * rounding window, is the bound the fp16 append pass lists rows below (every row whose reference distance is <= the radius has a
+ * proxy below it, whatever the radius is; a radius >= 100000 lists everything); then one wave per query re-computes EVERY listed
+ * row in the reference's arithmetic, keeps those with dist < radius and dist < 100000, counts them and sorts the max_results
+ * smallest keys. A query is certified when its list did not overflow (4096 entries) and the bound's distance less the rounding
+ * window lies above the radius -- rows never listed are then outside it. What is not certified (an overflowed list: more than
+ * 4096 rows near the radius, a radius of +inf over more than 4096 rows; NaN operands) gets keys and count from the store + count
+ * + select form after the call's one synchronisation of `stream`; fir_gemm_stats_ex counts those queries. */
+int fir_gemm_search_radius_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, const float* d_radius, int32_t max_results,
+                                    int32_t* d_count, uint64_t* d_keys, void* stream);
 /* fir_search_top1 and fir_search_top1_keys_dev send L2 whole-range batches through this path BY DEFAULT when the batch
  * has >= 128 queries and the gallery >= 65536 rows (smaller, cache-resident galleries: where a cost model of the two forms gives the
  * matrix cores 15 % or more -- e.g. 128 queries against 40 000 x 512, 1 024 against 8 192 x 512 --, from the gallery's fourth such
@@ -628,6 +684,14 @@ int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, in
  * are the unsharded handle's. Failure semantics, agreed buffer growth and the status element as for the other searches. */
 int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                            int32_t* idx, float* dist);
+/* fir_search_radius over the shards (the rows inside DirectedEnumeration's threshold, ann.cpp:390-400, of the whole gallery),
+ * 0 <= max_results <= FIR_KNN_MAX, arguments as there: every shard runs fir_search_radius_keys_dev with global rows; its counts
+ * travel behind its keys in the same ncclAllGather, in front of the status element, and are summed on the device; the keys merge
+ * as fir_sharded_search_knn's do -- the max_results smallest of the union are among every shard's max_results smallest.
+ * max_results = 0 exchanges counts only. Counts and keys are the unsharded handle's. Failure semantics, agreed buffer growth and
+ * the status element as for the other searches. */
+int fir_sharded_search_radius(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                              const float* radius, int32_t max_results, int32_t* count, int32_t* idx, float* dist);
 /* Batched BruteForceClassifier::recognize (ImageTesting.cpp:58-71): class_out[qb] <- classNo of the nearest row or -1;
  * idx / dist may be NULL. Needs class labels. */
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
