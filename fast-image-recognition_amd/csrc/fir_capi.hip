@@ -18,6 +18,7 @@
 #include "../../include/fir_amd.h"
 #include "fir_internal.h"
 #include "fir_knn_select.h"
+#include "fir_search_request.h"
 
 using namespace fir;
 
@@ -524,14 +525,14 @@ int top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     return FIR_OK;
 }
 
-int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st);
+int try_mfma_search(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const FirSearch& s, hipStream_t st);
 
 int topk_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys,
              hipStream_t st, bool allow_lists = true, bool allow_mfma = true) {
     // large whole-range L2 batches over a large gallery: the matrix-core nomination pass + exact re-rank (fir_gemm.hip), the
     // same keys; what it cannot certify comes back through this function with allow_mfma = false
     if (allow_mfma) {
-        const int rcm = try_mfma_topk(g, d_queries, qb, start, end, k, d_keys, st);
+        const int rcm = try_mfma_search(g, d_queries, qb, start, end, FirSearch::rows(k, d_keys), st);
         if (rcm <= 0) return rcm;
     }
     // batches over a large gallery: threshold from a row sample, append scan at the speed of the top-1 scan, K smallest
@@ -921,14 +922,13 @@ int knn_select_blocks() {
     const int v = e ? atoi(e) : 0;
     return v >= 1 ? std::min(v, kKnnMaxBlocks) : kKnnMaxBlocks;
 }
-// The radius form (fir_search_radius: d_radius and d_count given, k = max_results, 0 included): the same store pass, then per tile
-// the count of the rows inside each query's radius (k_knn_count, into d_count) and the select with each query's own rank
+// The radius form (s.kind == kSearchRadius: fir_search_radius, k = max_results, 0 included): the same store pass, then per tile
+// the count of the rows inside each query's radius (k_knn_count, into s.count) and the select with each query's own rank
 // min(count, k) -- no digit passes for a query whose rows inside all fit. The second event pair is around count + select + sort.
-int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st,
-            const float* d_radius = nullptr, int32_t* d_count = nullptr) {
+int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const FirSearch& s, hipStream_t st) {
     if (g->n == 0) {                                         // every slot FIR_KEY_NONE (all bytes 0xFF), every count 0
-        if (k > 0) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
-        if (d_count) FIR_HIP(hipMemsetAsync(d_count, 0, (size_t)qb * sizeof(int32_t), st));
+        if (s.k > 0) FIR_HIP(hipMemsetAsync(s.keys, 0xFF, s.key_words(qb) * sizeof(uint64_t), st));
+        if (s.count) FIR_HIP(hipMemsetAsync(s.count, 0, (size_t)qb * sizeof(int32_t), st));
         return FIR_OK;
     }
     int t = largest_pow2_le(qb, std::min(effective_qpp(g), 8));
@@ -958,12 +958,12 @@ int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, i
         a.n = g->n;
         a.stride = plan.row_stride;
         a.row_offset = g->row_offset;
-        a.k = k;
+        a.k = s.k;
         a.ctl = (KnnCtl*)((char*)g->knn.p + plan.dist_bytes);
-        a.out = d_keys + (size_t)q0 * k;
-        if (d_radius) { a.radius = d_radius + q0; a.inside = d_count + q0; }
+        const FirSearch o = s.at(q0);
+        a.out = o.keys; a.radius = o.radius; a.inside = o.count;
         if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
-        FIR_HIP(d_radius ? (knn_select_launch<true, true>(a, tt, blocks, st)) : (knn_select_launch<true>(a, tt, blocks, st)));
+        FIR_HIP(s.is_radius() ? (knn_select_launch<true, true>(a, tt, blocks, st)) : (knn_select_launch<true>(a, tt, blocks, st)));
         if ((rc = fir_gallery_profile_end_(g, st, (double)tt * g->n * 4.0))) return rc;
         q0 += tt;
     }
@@ -1570,39 +1570,33 @@ int try_mfma(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
                          : fir_gemm_search_top1_keys_dev(m, d_queries, qb, d_keys, st);
     });
 }
-int try_mfma_topk(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
-    if (k < 2 || !wants_mfma(g, qb, start, end)) return 1;       // K = 1 callers use the top-1 entry points
-    return run_mfma(g, end, true, [&](fir_gemm* m) { return fir_gemm_search_topk_keys_dev(m, d_queries, qb, k, d_keys, st); });
-}
-// ... and for the K nearest distinct classes of a host-pointer batch (fir_search_top_classes): the gallery needs its labels
-// (never a warm-up: the automatic rule takes galleries of kAutoMfmaRows rows or more, below that only a caller's threshold does)
-int try_mfma_classes(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k, uint64_t* d_keys,
-                     int32_t* d_classes, hipStream_t st) {
-    if (!g->cls || !wants_mfma(g, qb, start, end, true)) return 1;
-    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, num_classes, k, d_keys, d_classes, st); });
-}
-// ... and for the K <= FIR_GEMM_KNN_MAX nearest rows of a host-pointer batch (fir_search_knn): the ranges and the caller's threshold of the
-// class form; by itself (kAutoMfmaQueries queries over kAutoMfmaRows rows) for 8 < K <= kAutoMfmaKnnMaxK: the largest measured K that was
-// at least 1.15 x store + select at 1 024 queries and not slower at 128, at 1M x 512 and at 100 000 x 512, together with every smaller
-// measured K (9, 16, 32, 64, 128, 256; profiles/knn_matrix_cores.txt: K = 256 is 1.56 x / 2.12 x at 128 / 1 024 queries over 1M rows and
-// 1.62 x / 5.76 x over 100 000; K = 9 9.2 x / 21 x and 3.7 x / 8.6 x). K <= 8 was not measured through this call: a caller's threshold only
-// (fir_search_topk is that call). Smaller galleries were not measured either: they stay with store + select unless the caller sets a threshold.
+// ... and for every kind but top-1 (fir_search_request.h): the kind's own gate, the ranges wants_mfma admits, the state, the kind's fir_gemm entry point
 constexpr int kAutoMfmaKnnMaxK = 256;
-int try_mfma_knn(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, uint64_t* d_keys, hipStream_t st) {
-    if (k > FIR_GEMM_KNN_MAX) return 1;
-    if (g->large_batch_min < 0 && (k <= kKMax || k > kAutoMfmaKnnMaxK)) return 1;
-    if (!wants_mfma(g, qb, start, end, true)) return 1;
-    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_knn_keys_dev(m, d_queries, qb, k, d_keys, st); });
-}
-// ... and for the rows within a radius (fir_search_radius): the ranges of the class form, max_results <= FIR_GEMM_KNN_MAX, and ONLY from a
-// caller's threshold on -- never by itself (profiles/radius_search.txt): 1.75 - 74 x store + count + select while the count fits max_results,
-// but a radius that overflows every list costs 0.09 - 0.78 x (every query answered twice) and 1 000 rows inside at 100 000 rows, 128 queries
-// 0.78 x -- far beyond the spread, and (queries, rows, max_results) do not show how many rows lie near a radius.
-int try_mfma_radius(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const float* d_radius, int32_t max_results,
-                    int32_t* d_count, uint64_t* d_keys, hipStream_t st) {
-    if (max_results > FIR_GEMM_KNN_MAX || g->large_batch_min <= 0) return 1;
-    if (!wants_mfma(g, qb, start, end, true)) return 1;
-    return run_mfma(g, end, false, [&](fir_gemm* m) { return fir_gemm_search_radius_keys_dev(m, d_queries, qb, d_radius, max_results, d_count, d_keys, st); });
+int try_mfma_search(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const FirSearch& s, hipStream_t st) {
+    const bool rows = s.kind == kSearchRows;                         // (the top-1 ranges, and the one kind with a warm-up)
+    if (rows && s.k < 2) return 1;                                   // K = 1 callers use the top-1 entry points
+    // the K nearest distinct classes of a host-pointer batch (fir_search_top_classes): the gallery needs its labels
+    // (never a warm-up: the automatic rule takes galleries of kAutoMfmaRows rows or more, below that only a caller's threshold does)
+    if (s.kind == kSearchClasses && !g->cls) return 1;
+    // the K <= FIR_GEMM_KNN_MAX nearest rows of a host-pointer batch (fir_search_knn): the ranges and the caller's threshold of the
+    // class form; by itself (kAutoMfmaQueries queries over kAutoMfmaRows rows) for 8 < K <= kAutoMfmaKnnMaxK: the largest measured K that was
+    // at least 1.15 x store + select at 1 024 queries and not slower at 128, at 1M x 512 and at 100 000 x 512, together with every smaller
+    // measured K (9, 16, 32, 64, 128, 256; profiles/knn_matrix_cores.txt: K = 256 is 1.56 x / 2.12 x at 128 / 1 024 queries over 1M rows and
+    // 1.62 x / 5.76 x over 100 000; K = 9 9.2 x / 21 x and 3.7 x / 8.6 x). K <= 8 was not measured through this call: a caller's threshold only
+    // (fir_search_topk is that call). Smaller galleries were not measured either: they stay with store + select unless the caller sets a threshold.
+    if (s.kind == kSearchSelect && (s.k > FIR_GEMM_KNN_MAX || (g->large_batch_min < 0 && (s.k <= kKMax || s.k > kAutoMfmaKnnMaxK)))) return 1;
+    // the rows within a radius (fir_search_radius): the ranges of the class form, max_results <= FIR_GEMM_KNN_MAX, and ONLY from a
+    // caller's threshold on -- never by itself (profiles/radius_search.txt): 1.75 - 74 x store + count + select while the count fits max_results,
+    // but a radius that overflows every list costs 0.09 - 0.78 x (every query answered twice) and 1 000 rows inside at 100 000 rows, 128 queries
+    // 0.78 x -- far beyond the spread, and (queries, rows, max_results) do not show how many rows lie near a radius.
+    if (s.is_radius() && (s.k > FIR_GEMM_KNN_MAX || g->large_batch_min <= 0)) return 1;
+    if (!wants_mfma(g, qb, start, end, !rows)) return 1;
+    return run_mfma(g, end, rows, [&](fir_gemm* m) {
+        return rows                      ? fir_gemm_search_topk_keys_dev(m, d_queries, qb, s.k, s.keys, st)
+               : s.kind == kSearchSelect ? fir_gemm_search_knn_keys_dev(m, d_queries, qb, s.k, s.keys, st)
+               : s.is_radius()           ? fir_gemm_search_radius_keys_dev(m, d_queries, qb, s.radius, s.k, s.count, s.keys, st)
+                                         : fir_gemm_search_top_classes_keys_dev(m, d_queries, qb, s.num_classes, s.k, s.keys, s.classes, st);
+    });
 }
 }  // namespace
 
@@ -1632,7 +1626,7 @@ int fir_twd_mfma_classes_(fir_gallery* g, const float* d_queries, int32_t qb, in
     };
     int64_t before[3] = {0, 0, 0}, after[3] = {0, 0, 0};
     if (fir_gemm* m0 = state_of()) { const int rs = fir_gemm_stats_ex(m0, before); if (rs) return rs; }
-    const int rc = try_mfma_classes(g, d_queries, qb, 0, end_pos, num_classes, k, d_keys, d_classes, st);
+    const int rc = try_mfma_search(g, d_queries, qb, 0, end_pos, FirSearch::distinct(num_classes, k, d_keys, d_classes), st);
     if (rc) return rc;
     if (fir_gemm* m1 = state_of()) { const int rs = fir_gemm_stats_ex(m1, after); if (rs) return rs; }
     *exact_answered = after[2] - before[2];
@@ -1871,7 +1865,7 @@ int deliver_pinned(fir_gallery* g, GalleryCall& call, int count, int32_t* idx, f
 // Any call: g->dkeys[0, count) -- and g->didx[0, count) into class_out, when asked for -- copied back, one synchronisation.
 int deliver_copied(fir_gallery* g, GalleryCall& call, size_t count, int32_t* class_out, int32_t* idx, float* dist) {
     std::vector<uint64_t> keys(count);
-    FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, count * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    if (count) FIR_HIP(hipMemcpyAsync(keys.data(), g->dkeys, count * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));    // (0: a count-only radius call)
     if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->didx, count * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     FIR_HIP(hipStreamSynchronize(g->stream));
     call.done();
@@ -2019,75 +2013,73 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
     return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
 }
 
+namespace {
+// The host-pointer body of fir_search_knn, fir_search_radius and fir_search_top_classes, arguments checked. `s` names the kind, K and num_classes; its device
+// pointers are made here, in the handle's buffers (behind the keys' slots the counts out, then the radii in). Matrix cores, else the kind's exact form.
+struct HostOut { int32_t* idx; float* dist; int32_t* class_out = nullptr; const float* radius = nullptr; int32_t* count = nullptr; };
+int search_host(fir_gallery* g, const float* queries, int32_t qb, int32_t start, int32_t end, FirSearch s, const HostOut& out) {
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    const size_t slots = s.key_words(qb);
+    const bool classes = s.kind == kSearchClasses;
+    int rc;
+    if ((rc = FIR_NEED(g->dkeys, s.status_index(qb) + s.radii_bytes(qb) / sizeof(uint64_t))) || (rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    if (classes && (rc = FIR_NEED(g->didx, slots))) return rc;
+    uint64_t* base = g->dkeys;
+    s.keys = slots ? base : nullptr;
+    if (classes) s.classes = g->didx;
+    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    if (s.is_radius()) {
+        s.count = (int32_t*)(base + slots);
+        s.radius = (const float*)(base + s.status_index(qb));
+        FIR_HIP(hipMemcpyAsync((void*)s.radius, out.radius, (size_t)qb * sizeof(float), hipMemcpyHostToDevice, g->stream));
+    }
+    g->call_launches = 0;
+    g->warm_left = 0;
+    rc = try_mfma_search(g, g->dq, qb, start, end, s, g->stream);
+    if (rc > 0) rc = classes ? top_classes_dev(g, g->dq, qb, start, end, s.num_classes, s.k, s.keys, s.classes, g->stream) : knn_dev(g, g->dq, qb, start, end, s, g->stream);
+    if (rc) return rc;
+    if (s.is_radius()) FIR_HIP(hipMemcpyAsync(out.count, s.count, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    return deliver_copied(g, call, slots, out.class_out, out.idx, out.dist);
+}
+// The radius calls' pointers_ok: a bad max_results is reported as such, not as a NULL argument -- the key pointer(s) are judged once it is known to be in range
+bool radius_pointers_ok(int32_t qb, const float* radius, int32_t max_results, const int32_t* count, bool any_out, bool all_out) {
+    return count != nullptr && (qb <= 0 || radius != nullptr) && (max_results < 0 || max_results > kKnnMax || (max_results == 0 ? !any_out : all_out));
+}
+}  // namespace
+
 int fir_search_knn_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, uint64_t* d_keys,
                             void* stream) {
     const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr, [&] { return check_knn_k(k); });
     if (rc) return rc < 0 ? rc : FIR_OK;
     GalleryCall call(g, stream);
     if (call.rc) return call.rc;
-    return knn_dev(g, d_queries, qb, start_pos, end_pos, k, d_keys, call.st);
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, FirSearch::select(k, d_keys), call.st);
 }
 
 int fir_search_knn(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx, float* dist) {
-    int rc = check_search(g, queries, qb, start_pos, end_pos, idx != nullptr && dist != nullptr, [&] { return check_knn_k(k); });
+    const int rc = check_search(g, queries, qb, start_pos, end_pos, idx != nullptr && dist != nullptr, [&] { return check_knn_k(k); });
     if (rc) return rc < 0 ? rc : FIR_OK;
-    GalleryCall call(g);
-    if (call.rc) return call.rc;
-    if ((rc = FIR_NEED(g->dkeys, (size_t)qb * k))) return rc;
-    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
-    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    g->call_launches = 0;
-    g->warm_left = 0;
-    rc = try_mfma_knn(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream);
-    if (rc > 0) rc = knn_dev(g, g->dq, qb, start_pos, end_pos, k, g->dkeys, g->stream);
-    if (rc) return rc;
-    return deliver_copied(g, call, (size_t)qb * k, nullptr, idx, dist);
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::select(k, nullptr), {idx, dist});
 }
 
 // ---- every row within a per-query radius (fir_amd.h) ----
 int fir_search_radius_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* d_radius,
                                int32_t max_results, int32_t* d_count, uint64_t* d_keys, void* stream) {
-    // (a bad max_results is reported as such, not as a NULL argument: the key pointer is judged once max_results is known to be in range)
-    const bool pointers_ok = d_count != nullptr && (qb <= 0 || d_radius != nullptr) &&
-                             (max_results < 0 || max_results > kKnnMax || (max_results == 0 ? d_keys == nullptr : d_keys != nullptr));
+    const bool pointers_ok = radius_pointers_ok(qb, d_radius, max_results, d_count, d_keys != nullptr, d_keys != nullptr);
     const int rc = check_search(g, d_queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
     if (rc) return rc < 0 ? rc : FIR_OK;
     GalleryCall call(g, stream);
     if (call.rc) return call.rc;
-    return knn_dev(g, d_queries, qb, start_pos, end_pos, max_results, d_keys, call.st, d_radius, d_count);
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, FirSearch::within(d_radius, max_results, d_count, d_keys), call.st);
 }
 
 int fir_search_radius(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* radius, int32_t max_results,
                       int32_t* count, int32_t* idx, float* dist) {
-    const bool pointers_ok = count != nullptr && (qb <= 0 || radius != nullptr) &&
-                             (max_results < 0 || max_results > kKnnMax || (max_results == 0 ? !idx && !dist : idx && dist));
-    int rc = check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
+    const bool pointers_ok = radius_pointers_ok(qb, radius, max_results, count, idx || dist, idx && dist);
+    const int rc = check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
     if (rc) return rc < 0 ? rc : FIR_OK;
-    GalleryCall call(g);
-    if (call.rc) return call.rc;
-    // behind the keys' slot: the radii in, the counts out
-    const size_t slots = (size_t)qb * max_results;
-    if ((rc = FIR_NEED(g->dkeys, slots + (size_t)qb))) return rc;
-    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
-    uint64_t* tail = g->dkeys;
-    tail += slots;
-    float* d_radius = (float*)tail;
-    int32_t* d_count = (int32_t*)tail + qb;
-    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    FIR_HIP(hipMemcpyAsync(d_radius, radius, (size_t)qb * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    g->call_launches = 0;
-    g->warm_left = 0;
-    uint64_t* d_keys = slots ? (uint64_t*)g->dkeys : nullptr;
-    rc = try_mfma_radius(g, g->dq, qb, start_pos, end_pos, d_radius, max_results, d_count, d_keys, g->stream);
-    if (rc > 0) rc = knn_dev(g, g->dq, qb, start_pos, end_pos, max_results, d_keys, g->stream, d_radius, d_count);
-    if (rc) return rc;
-    FIR_HIP(hipMemcpyAsync(count, d_count, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (slots == 0) {
-        FIR_HIP(hipStreamSynchronize(g->stream));
-        call.done();
-        return FIR_OK;
-    }
-    return deliver_copied(g, call, slots, nullptr, idx, dist);
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::within(nullptr, max_results, nullptr, nullptr), {idx, dist, nullptr, radius, count});
 }
 
 namespace {
@@ -2145,19 +2137,7 @@ int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int
                            int32_t* class_out, int32_t* idx, float* dist) {
     int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k);
     if (rc) return rc < 0 ? rc : FIR_OK;
-    GalleryCall call(g);
-    if (call.rc) return call.rc;
-    g->call_launches = 0;
-    g->warm_left = 0;
-    const size_t slots = (size_t)qb * k;
-    if ((rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
-    if ((rc = FIR_NEED(g->dkeys, slots))) return rc;
-    if ((rc = FIR_NEED(g->didx, slots))) return rc;
-    FIR_HIP(hipMemcpyAsync(g->dq, queries, (size_t)qb * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
-    rc = try_mfma_classes(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
-    if (rc > 0) rc = top_classes_dev(g, g->dq, qb, start_pos, end_pos, num_classes, k, g->dkeys, g->didx, g->stream);
-    if (rc) return rc;
-    return deliver_copied(g, call, slots, class_out, idx, dist);
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::distinct(num_classes, k, nullptr, nullptr), {idx, dist, class_out});
 }
 
 int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k, uint64_t* keys_out,

@@ -31,9 +31,11 @@
 #include "fir_internal.h"
 #include "fir_common.h"
 #include "fir_knn_select.h"
+#include "fir_search_request.h"
 
 namespace {
 
+using fir::FirSearch;
 using fir::kKeyNone;
 
 #ifndef FIR_I8_AUTO_MIN_QUERIES
@@ -1649,14 +1651,8 @@ struct GemmCall {
     const float* h_queries;     // non-NULL: the queries are still in host memory; d_queries is the device buffer they go to, one super-batch
                                 // at a time, each upload queued (on its own stream) right before that super-batch's preparation
     int32_t qb;
-    int k;                      // the K nearest rows of every query: d_keys[q * k + r], ascending
-    uint64_t* d_keys;
-    int32_t num_classes;        // > 0: the K nearest distinct CLASSES (fir_gemm_search_top_classes_keys_dev) -- a bound from a row sample's class
-    int32_t* d_classes;         // minima, the append pass below it, k_gemm_rerank_classes; d_keys or d_classes may then be NULL
-    bool knn = false;           // the K > kTopKMax nearest rows (fir_gemm_search_knn_keys_dev, fir_gemm_knn.h): the same flow with the bound from
-    int knn_div = fir::kKnnSampleDiv;   // a row sample's exact K-th distance (rows n K / knn_div: FIR_GEMM_KNN_SAMPLE_DIV) and k_gemm_rerank_knn
-    const float* d_radius = nullptr;    // with knn: every row within radius[q] (fir_gemm_search_radius_keys_dev) -- the bound IS the radius, no sample;
-    int32_t* d_count = nullptr;         // k = max_results (0: d_keys is NULL), d_count[q] <- the rows inside; k_gemm_rerank_radius
+    FirSearch s;                // what is searched for (fir_search_request.h): s.keys[q * s.k + r] ascending; kGemmKinds[s.kind] says how this file answers the kind
+    int knn_div = fir::kKnnSampleDiv;   // kSearchSelect: the bound from a row sample's exact K-th distance (rows n K / knn_div: FIR_GEMM_KNN_SAMPLE_DIV)
     hipStream_t st;
     int d, qs;                  // features compared; floats between consecutive queries (and gallery rows): the whole row
     int64_t n;
@@ -1680,6 +1676,25 @@ struct GemmCall {
 
     int sb_queries(int sb) const { return std::min(sbq, qb - sb * sbq); }
     const float* sb_first(int sb) const { return d_queries + (size_t)sb * sbq * qs; }
+};
+// ---- the kinds of search (fir_search_request.h) as this file answers them: one row per kind, in SearchKind's order. A new kind is a new row, its
+// arm in gemm_prep_f16_ (how the bound is made) and in gemm_rerank_ (which kernel), and an exact form. Only kSearchRows has second-chance rounds (gemm_finish_).
+struct GemmKind {
+    int k_min, k_max;           // the k-limit; its error text is "k=%d outside [1,%d]" (a radius call's max_results is the entry point's to report)
+    bool adaptive;              // the fp16 pass may find its bound on the way (adaptive_for_)
+    bool i8;                    // the int8 nomination is eligible (gemm_wants_i8_; top-1 only)
+    // nq queries answered exactly into `out`, over features [0, c.d) on the call's stream: every query of an empty gallery, each run of uncertified ones
+    int (*exact)(fir_gemm* m, const GemmCall& c, const float* dq, int32_t nq, const FirSearch& out);
+};
+static const GemmKind kGemmKinds[fir::kSearchKinds] = {
+    {1, kTopKMax, true, true, [](fir_gemm* m, const GemmCall& c, const float* dq, int32_t nq, const FirSearch& o) {                  // kSearchRows: the exact scans
+         return c.s.k == 1 ? fir_search_top1_exact_keys_dev_(m->g, dq, nq, 0, c.d, o.keys, c.st) : fir_search_topk_exact_keys_dev_(m->g, dq, nq, c.d, c.s.k, o.keys, c.st); }},
+    {1, fir::kKnnGemmMax, false, false, [](fir_gemm* m, const GemmCall& c, const float* dq, int32_t nq, const FirSearch& o) {       // kSearchSelect: store + select
+         return fir_search_knn_keys_dev(m->g, dq, nq, 0, c.d, c.s.k, o.keys, c.st); }},     // (K slot minima per query stop at kTopKMax: the sample flow, fir_gemm_knn.h)
+    {0, fir::kKnnGemmMax, false, false, [](fir_gemm* m, const GemmCall& c, const float* dq, int32_t nq, const FirSearch& o) {       // kSearchRadius: store + count + select
+         return fir_search_radius_keys_dev(m->g, dq, nq, 0, c.d, o.radius, c.s.k, o.count, o.keys, c.st); }},
+    {1, 32, false, false, [](fir_gemm* m, const GemmCall& c, const float* dq, int32_t nq, const FirSearch& o) {                     // kSearchClasses: the class-minimum scan
+         return fir_class_scan_dev_(m->g, dq, nq, c.d, o.num_classes, c.s.k, 0, o.keys, o.classes, nullptr, c.st); }},             // (a bound on the K-th CLASS is not a row order statistic)
 };
 
 // ---- the int8 nomination: which calls take it, and the copy they need (fir_gemm_i8.h) ----
@@ -1743,7 +1758,7 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
             if ((int64_t)m->i8_pin[0] * 16 > (int64_t)m->i8_pending_qb) { m->i8_off = true; m->i8_off_why = "second passes"; }
         } else if (eq == hipErrorNotReady) (void)hipGetLastError();     // (not an error: the counter is looked at by a later call)
     }
-    if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.k != 1 || c.num_classes > 0 || c.knn || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
+    if (m->i8_mode == 0 || m->precision != FIR_GEMM_F16 || m->f64 || c.s.k != 1 || !kGemmKinds[c.s.kind].i8 || m->feat != m->v.d || m->feat > 1024 || m->feat < 8 ||
         c.qb <= 32 || (m->dbg_skip && m->i8_mode != 1))        // (the timing forms reach int8 only where the handle asks for int8 outright)
         return FIR_OK;
     if (m->i8_mode < 0 && (kI8AutoMinQueries <= 0 || c.qb < kI8AutoMinQueries)) return FIR_OK;
@@ -1777,10 +1792,9 @@ static int gemm_wants_i8_(fir_gemm* m, GemmCall& c, bool* out) {
 // profiles/r04_adaptive_cutoff.txt): top-1 always takes it. The K-nearest form (eight slots per query fill more slowly) wins from eight
 // pairs per launch on and on cache-sized galleries, and loses 3-35 % with one or two pairs over 100 000+ rows: those keep the sample flow.
 static bool adaptive_for_(const fir_gemm* m, const GemmCall& c, int nq_sb) {
-    if (m->precision != FIR_GEMM_F16 || m->adaptive <= 0 || (c.k > 1 && !m->adaptive_topk)) return false;
-    if (c.num_classes > 0) return false;                                // (a bound on the K-th CLASS is not a row order statistic: the sample flow)
-    if (c.knn) return false;                                            // (K slot minima per query stop at kTopKMax: the sample flow, fir_gemm_knn.h)
-    if (m->adaptive > 1 || c.k == 1) return true;                       // FIR_GEMM_ADAPTIVE=2: always
+    if (m->precision != FIR_GEMM_F16 || m->adaptive <= 0 || (c.s.k > 1 && !m->adaptive_topk)) return false;
+    if (!kGemmKinds[c.s.kind].adaptive) return false;                   // (kGemmKinds says why not)
+    if (m->adaptive > 1 || c.s.k == 1) return true;                       // FIR_GEMM_ADAPTIVE=2: always
     const int pairs_sb = ((nq_sb + kQT - 1) / kQT + 1) / 2;
     const int P = launch_pairs_(pairs_sb, c.streamed ? kShareStreamed : kShareMax);
     const int64_t row_groups = ((c.n + 31) / 32 + kGemmBlock / 64 - 1) / (kGemmBlock / 64);
@@ -1860,7 +1874,7 @@ static void gemm_sample_tau_(fir_gemm* m, const GemmScratch& s, hipStream_t st, 
 // fp16 preparation of one super-batch on `ps`: per-query norms and scales, the query fragments and -- unless the full pass finds its
 // threshold on the way -- the sample flow (gemm_sample_pass_, gemm_sample_tau_).
 static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb) {
-    const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
+    const int b = sb & 1, nq = c.sb_queries(sb), k = c.s.k;
     GemmScratch& s = m->set[b];
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;        // 128 queries per gallery read; a half-filled pair is zero-padded
     const float* dq = c.sb_first(sb);
@@ -1881,27 +1895,24 @@ static int gemm_prep_f16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, int sb
     hipLaunchKernelGGL(k_gemm_pack_queries_f16x, dim3((4 * m->dk16 * 64 + 255) / 256, pairs), dim3(256), 0, ps, dq, nq, c.d, m->dk16, s.qmul,
                        s.qbf, c.qs);
     if (adaptive) return FIR_OK;
-    if (c.num_classes > 0) {
+    int rc = FIR_OK;
+    if (c.s.kind == fir::kSearchRows) {
+        if ((rc = gemm_sample_pass_(m, s, ps, c.streamed, c.odd, pairs, k))) return rc;
+        gemm_sample_tau_(m, s, ps, pairs, nq, k, c.e_rel);
+        return FIR_OK;
+    }
+    if (c.s.kind == fir::kSearchClasses) {
         // distinct classes: D_s = the exact K-th smallest class minimum over the leading sample rows (four times list_row_samples' sizing:
-        // profiles/class_rank_matrix_cores.txt), turned into the append pass's bound in place; padding queries get -inf
+        // profiles/class_rank_matrix_cores.txt)
         const int64_t rows = std::min<int64_t>(c.n, std::max<int64_t>(kClassSampleRows, c.n * k / m->class_sample_div));
-        const int rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.num_classes, k, rows, nullptr, nullptr, s.tau, ps);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
-        return FIR_OK;
-    }
-    if (c.knn) {
-        // D_s = the exact K-th smallest distance over a row sample spread over the gallery (fir_knn_select.h: knn_sample_plan), turned into
-        // the append pass's bound in place; padding queries get -inf
-        // (the radius form: the query's own radius is the bound -- any value: k_gemm_tau_class's guarantee does not ask where it came from)
-        if (c.d_radius) FIR_HIP(hipMemcpyAsync(s.tau, c.d_radius + (size_t)sb * c.sbq, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, ps));
-        else if (const int rc = fir_knn_sample_bound_dev_(m->g, dq, nq, c.d, k, c.knn_div, s.tau, ps)) return rc;
-        hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
-        return FIR_OK;
-    }
-    const int rc = gemm_sample_pass_(m, s, ps, c.streamed, c.odd, pairs, k);
+        rc = fir_class_scan_dev_(m->g, dq, nq, c.d, c.s.num_classes, k, rows, nullptr, nullptr, s.tau, ps);
+    } else if (c.s.is_radius())     // (the query's own radius is the bound -- any value: k_gemm_tau_class's guarantee does not ask where it came from)
+        FIR_HIP(hipMemcpyAsync(s.tau, c.s.radius + (size_t)sb * c.sbq, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, ps));
+    else                            // D_s = the exact K-th smallest distance over a row sample spread over the gallery (fir_knn_select.h: knn_sample_plan)
+        rc = fir_knn_sample_bound_dev_(m->g, dq, nq, c.d, k, c.knn_div, s.tau, ps);
     if (rc) return rc;
-    gemm_sample_tau_(m, s, ps, pairs, nq, k, c.e_rel);
+    // the exact bound D_s turned into the append pass's bound in place; padding queries get -inf
+    hipLaunchKernelGGL(k_gemm_tau_class, dim3((pairs * 2 * kQT + 255) / 256), dim3(256), 0, ps, s.tau, pairs * 2 * kQT, nq, c.d, s.qnorm, m->gmax, c.e_rel);
     return FIR_OK;
 }
 
@@ -1925,7 +1936,7 @@ static int gemm_prep_f32_bf16_(fir_gemm* m, const GemmCall& c, hipStream_t ps, i
                            (int64_t)sample_rows, m->dk16, s.tau, s.lists, s.counts, m->sample, sample_rows);
     }
     hipLaunchKernelGGL(k_gemm_tau, dim3(np * kQT), dim3(256), 0, ps, m->sample, sample_rows, s.tau, 0x7FFFFFFF, s.qnorm, m->gmax, c.e_rel,
-                       c.k > 1 ? 1 : 0);
+                       c.s.k > 1 ? 1 : 0);
     return FIR_OK;
 }
 
@@ -1971,7 +1982,7 @@ static int gemm_prep_(fir_gemm* m, const GemmCall& c, int sb) {
 // pairs -- sixteen tiles over sixteen row ranges, 4 096 queries per read of the gallery -- which measured 3 % over sixteen pairs from
 // 32 768 queries per call on. The rule: always (profiles/int8_tile256.txt).
 static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
-    const int b = sb & 1, nq = c.sb_queries(sb), k = c.k;
+    const int b = sb & 1, nq = c.sb_queries(sb), k = c.s.k;
     const int pairs = ((nq + kQT - 1) / kQT + 1) / 2;
     const int64_t n = c.n;
     const GemmOperand op = gemm_operand_(m, c.i8);
@@ -2048,23 +2059,20 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
 // exact re-rank + certificate of super-batch sb on `rs`; uncertified queries go on the call's list. A launch the runtime refuses is the
 // call's error: the flags and keys of this super-batch would otherwise be whatever an earlier call left.
 static int gemm_rerank_(fir_gemm* m, const GemmCall& c, int sb, hipStream_t rs) {
-    const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb);
+    const int b = sb & 1, q0 = sb * c.sbq, nq = c.sb_queries(sb), k = c.s.k;
     GemmScratch& s = m->set[b];
-    if (c.num_classes > 0)
+    const FirSearch o = c.s.at(q0);         // the super-batch's slots of the call's outputs
+    if (c.s.kind == fir::kSearchClasses)
         hipLaunchKernelGGL(k_gemm_rerank_classes, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, m->gal4, c.sb_first(sb), s.qnorm, m->gmax,
-                           m->v.cls, c.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
-                           c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, m->ok + q0,
-                           c.qs, m->rowmajor);
-    else if (c.d_radius)
-        hipLaunchKernelGGL(k_gemm_rerank_radius, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, c.d_radius + q0, m->gal4, c.sb_first(sb), s.qnorm,
-                           m->gmax, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k,
-                           c.d_keys ? (unsigned long long*)c.d_keys + (size_t)q0 * c.k : nullptr, c.d_count + q0, m->ok + q0, c.qs, m->rowmajor);
-    else if (c.knn)
+                           m->v.cls, o.num_classes, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, k, (unsigned long long*)o.keys, o.classes, m->ok + q0, c.qs, m->rowmajor);
+    else if (c.s.is_radius())
+        hipLaunchKernelGGL(k_gemm_rerank_radius, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, o.radius, m->gal4, c.sb_first(sb), s.qnorm,
+                           m->gmax, c.n, c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, k, (unsigned long long*)o.keys, o.count, m->ok + q0, c.qs, m->rowmajor);
+    else if (c.s.kind == fir::kSearchSelect)
         hipLaunchKernelGGL(k_gemm_rerank_knn, dim3(nq), dim3(64), gemm_rerank_lds_(m), rs, s.lists, s.counts, s.tau, m->gal4, c.sb_first(sb), s.qnorm, m->gmax, c.n,
-                           c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, c.k, (unsigned long long*)c.d_keys + (size_t)q0 * c.k, m->ok + q0, c.qs, m->rowmajor);
+                           c.d, m->dp4, m->v.row_offset, c.e_rel, m->rerank_group, k, (unsigned long long*)o.keys, m->ok + q0, c.qs, m->rowmajor);
     else
-        gemm_launch_rerank_(m, rs, nq, gemm_slot_(m, s, c.i8), c.sb_first(sb),
-                            c.e_rel, c.k, c.d_keys + (size_t)q0 * c.k, m->ok + q0, {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
+        gemm_launch_rerank_(m, rs, nq, gemm_slot_(m, s, c.i8), c.sb_first(sb), c.e_rel, k, o.keys, m->ok + q0, {m->fb_state, m->fb_list, m->fb_tau2, q0, nullptr, 0});
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
@@ -2113,9 +2121,9 @@ static int gemm_audit_report_(fir_gemm* m, const GemmCall& c) {
 }
 #endif
 
-// The uncertified queries of a distinct-class call: the call's one synchronisation of `st`, then the exact scan form for every
-// run of consecutive uncertified queries, straight into that run's output slots (no second-chance rounds)
-static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
+// The uncertified queries of a call of any kind but kSearchRows (which has gemm_finish_): the call's one synchronisation of `st`, then the kind's
+// exact form for every run of consecutive uncertified queries, straight into that run's output slots (no second-chance rounds)
+static int gemm_finish_runs_(fir_gemm* m, const GemmCall& c) {
     std::vector<int> h_ok((size_t)c.qb);
     FIR_HIP(hipMemcpyAsync(h_ok.data(), m->ok, (size_t)c.qb * sizeof(int), hipMemcpyDeviceToHost, c.st));
     FIR_HIP(hipStreamSynchronize(c.st));
@@ -2124,8 +2132,7 @@ static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
         int q1 = q0;
         while (q1 < c.qb && !h_ok[q1]) ++q1;
         if (q1 == q0) { ++q0; continue; }
-        const int rc = fir_class_scan_dev_(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, c.d, c.num_classes, c.k, 0, c.d_keys ? c.d_keys + (size_t)q0 * c.k : nullptr,
-                                           c.d_classes ? c.d_classes + (size_t)q0 * c.k : nullptr, nullptr, c.st);
+        const int rc = kGemmKinds[c.s.kind].exact(m, c, c.d_queries + (size_t)q0 * c.qs, q1 - q0, c.s.at(q0));
         if (rc) return rc;
         uncertified += q1 - q0;
         q0 = q1;
@@ -2135,58 +2142,24 @@ static int gemm_finish_classes_(fir_gemm* m, const GemmCall& c) {
     return FIR_OK;
 }
 
-// ... and of a K > kTopKMax nearest-rows call (fir_gemm_knn.h): the same, through the store + select form of fir_search_knn_keys_dev
-// (a radius call: keys and counts from fir_search_radius_keys_dev's store + count + select)
-static int gemm_finish_knn_(fir_gemm* m, const GemmCall& c) {
-    std::vector<int> h_ok((size_t)c.qb);
-    FIR_HIP(hipMemcpyAsync(h_ok.data(), m->ok, (size_t)c.qb * sizeof(int), hipMemcpyDeviceToHost, c.st));
-    FIR_HIP(hipStreamSynchronize(c.st));
-    int uncertified = 0;
-    for (int q0 = 0; q0 < c.qb;) {
-        int q1 = q0;
-        while (q1 < c.qb && !h_ok[q1]) ++q1;
-        if (q1 == q0) { ++q0; continue; }
-        const int rc = c.d_radius ? fir_search_radius_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.d_radius + q0, c.k, c.d_count + q0,
-                                                                c.d_keys ? c.d_keys + (size_t)q0 * c.k : nullptr, c.st)
-                                  : fir_search_knn_keys_dev(m->g, c.d_queries + (size_t)q0 * c.qs, q1 - q0, 0, c.d, c.k, c.d_keys + (size_t)q0 * c.k, c.st);
-        if (rc) return rc;
-        uncertified += q1 - q0;
-        q0 = q1;
-    }
-    if (uncertified) hipLaunchKernelGGL(k_gemm_fb_count, dim3(1), dim3(1), 0, c.st, m->fb_state, uncertified);
-    FIR_HIP(hipGetLastError());
-    return FIR_OK;
-}
-
-// The K nearest rows of every query, K = 1 (fir_gemm_search_top1_keys_dev) or 2..kTopKMax (fir_gemm_search_topk_keys_dev), or -- num_classes > 0 --
-// the K <= 32 nearest distinct classes (fir_gemm_search_top_classes_keys_dev, which checks its own arguments)
-static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, uint64_t* d_keys, void* stream, const float* h_queries = nullptr,
-                       int32_t num_classes = 0, int32_t* d_classes = nullptr, bool knn = false, const float* d_radius = nullptr, int32_t* d_count = nullptr) {
-    // (d_radius: fir_gemm_search_radius_keys_dev, which has checked its own arguments -- k = max_results may be 0 and d_keys NULL then)
-    if (!m || (!d_keys && !(num_classes > 0 && d_classes) && !d_radius) || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+// One search of any kind (s: fir_search_request.h) through the matrix cores. The entry points below have made their own checks,
+// in their own order; the ones here are what fir_gemm_search_top1 / _topk_keys_dev and fir_gemm_search_staged_ report.
+static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, const FirSearch& s, void* stream, const float* h_queries = nullptr) {
+    const GemmKind& kind = kGemmKinds[s.kind];
+    if (!m || !s.outputs_ok() || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
-    const int k_max = num_classes > 0 ? 32 : knn ? fir::kKnnGemmMax : kTopKMax;
-    if ((k < 1 && !d_radius) || k > k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, k_max);
+    if (s.k < kind.k_min || s.k > kind.k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", s.k, kind.k_max);
     if (qb == 0) return FIR_OK;
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);   // this state's scratch, and the gallery's, is shared with every other call on the gallery
     if (order.rc) return order.rc;
     GemmCall c;
-    c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.k = k; c.d_keys = d_keys; c.st = st;
-    c.num_classes = num_classes; c.d_classes = d_classes;
-    c.knn = knn;
-    c.d_radius = d_radius; c.d_count = d_count;
-    if (knn && !d_radius)
-        if (const char* w = fir_knob_("FIR_GEMM_KNN_SAMPLE_DIV")) c.knn_div = std::max(1, std::atoi(w));
+    c.d_queries = d_queries; c.h_queries = h_queries; c.qb = qb; c.s = s; c.st = st;
+    if (const char* w = s.kind == fir::kSearchSelect ? fir_knob_("FIR_GEMM_KNN_SAMPLE_DIV") : nullptr) c.knn_div = std::max(1, std::atoi(w));
     c.d = m->feat; c.qs = m->v.d; c.n = m->v.n; c.grid = m->v.cus;
     if (c.n == 0 && h_queries) FIR_HIP(hipMemcpyAsync((void*)d_queries, h_queries, (size_t)qb * c.qs * sizeof(float), hipMemcpyHostToDevice, st));
-    if (c.n == 0 && num_classes > 0) return fir_class_scan_dev_(m->g, d_queries, qb, c.d, num_classes, k, 0, d_keys, d_classes, nullptr, st);   // every slot unused
-    if (c.n == 0 && d_radius) return fir_search_radius_keys_dev(m->g, d_queries, qb, 0, c.d, d_radius, k, d_count, d_keys, st);                 // counts 0, every slot FIR_KEY_NONE
-    if (c.n == 0 && knn) return fir_search_knn_keys_dev(m->g, d_queries, qb, 0, c.d, k, d_keys, st);                                      // every slot FIR_KEY_NONE
-    if (c.n == 0)
-        return k == 1 ? fir_search_top1_exact_keys_dev_(m->g, d_queries, qb, 0, c.d, d_keys, st)
-                      : fir_search_topk_exact_keys_dev_(m->g, d_queries, qb, c.d, k, d_keys, st);
+    if (c.n == 0) return kind.exact(m, c, d_queries, qb, s);        // every slot unused / FIR_KEY_NONE, every count 0
     c.streamed = gemm_streamed_(m);
     c.odd = gemm_odd_(m);
     {
@@ -2242,14 +2215,13 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, int k, u
 #ifdef FIR_AUDIT
     if ((rc = gemm_audit_report_(m, c))) return rc;
 #endif
-    if (num_classes > 0) return gemm_finish_classes_(m, c);
-    if (knn) return gemm_finish_knn_(m, c);
+    if (s.kind != fir::kSearchRows) return gemm_finish_runs_(m, c);
     // uncertified queries: a second matrix-core pass with the tightest bound the first one can justify, then the exact device scan
     // (calls of at most 32 queries skip the second-chance rounds: the exact device scan reads the gallery once per eight queries, about what
     // one more matrix-core pass costs, and four launches fewer are 20 us of such a call)
     const int sc_rounds = m->precision == FIR_GEMM_F16 && qb > 32 ? std::min(kScRounds, (qb + kScQueries - 1) / kScQueries) : 0;
     m->last_sc_rounds = sc_rounds;
-    if ((rc = gemm_finish_(m, d_queries, k, d_keys, st, c.e_rel, sc_rounds, c.streamed, c.i8))) return rc;
+    if ((rc = gemm_finish_(m, d_queries, c.s.k, s.keys, st, c.e_rel, sc_rounds, c.streamed, c.i8))) return rc;
     if (c.i8 && m->i8_mode < 0 && !m->i8_pending) {
         // (the automatic rule's way back, gemm_wants_i8_: how many queries of this call needed a second pass, copied behind the call)
         FIR_HIP(hipMemcpyAsync(m->i8_pin, m->fb_state, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2266,11 +2238,11 @@ void fir_gemm_set_int8_(fir_gemm* m, int32_t mode) { if (m) m->i8_mode = mode > 
 void fir_gemm_set_int8_tile_(fir_gemm* m, int32_t mode) { if (m) m->i8_tile = mode > 0 ? 1 : mode < 0 ? -1 : 0; }
 
 int fir_gemm_search_top1_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, uint64_t* d_keys, void* stream) {
-    return gemm_search(m, d_queries, qb, 1, d_keys, stream);
+    return gemm_search(m, d_queries, qb, FirSearch::rows(1, d_keys), stream);
 }
 
 int fir_gemm_search_topk_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t k, uint64_t* d_keys, void* stream) {
-    return gemm_search(m, d_queries, qb, k, d_keys, stream);
+    return gemm_search(m, d_queries, qb, FirSearch::rows(k, d_keys), stream);
 }
 
 int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb, int32_t num_classes, int32_t k, uint64_t* d_keys,
@@ -2283,7 +2255,7 @@ int fir_gemm_search_top_classes_keys_dev(fir_gemm* m, const float* d_queries, in
     if (!m->v.cls && m->v.n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
     if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
     if (qb == 0) return FIR_OK;
-    return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, num_classes, d_classes);
+    return gemm_search(m, d_queries, qb, FirSearch::distinct(num_classes, k, d_keys, d_classes), stream);
 }
 
 // K <= kTopKMax: the top-1 / top-K forms as they are (they do not synchronise); beyond it the sample flow of fir_gemm_knn.h, which
@@ -2292,10 +2264,10 @@ int fir_gemm_search_knn_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (!m || !d_keys || (qb > 0 && !d_queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (k < 1 || k > FIR_GEMM_KNN_MAX) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, FIR_GEMM_KNN_MAX);
-    if (k <= kTopKMax) return gemm_search(m, d_queries, qb, k, d_keys, stream);
+    if (k <= kTopKMax) return gemm_search(m, d_queries, qb, FirSearch::rows(k, d_keys), stream);
     if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the K > %d nearest-rows form needs a FIR_GEMM_F16 state", kTopKMax);
     if (qb == 0) return FIR_OK;
-    return gemm_search(m, d_queries, qb, k, d_keys, stream, nullptr, 0, nullptr, true);
+    return gemm_search(m, d_queries, qb, FirSearch::select(k, d_keys), stream);
 }
 
 // Every row within radius[q] (fir_amd.h): the flow of fir_gemm_knn.h without its sample -- tau from the radius, the append pass,
@@ -2309,7 +2281,7 @@ int fir_gemm_search_radius_keys_dev(fir_gemm* m, const float* d_queries, int32_t
     if (!in_range) return fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", max_results, FIR_GEMM_KNN_MAX);
     if (m->precision != FIR_GEMM_F16 || m->f64) return fir_fail_(FIR_ERR_ARG, "the radius form needs a FIR_GEMM_F16 state");
     if (qb == 0) return FIR_OK;
-    return gemm_search(m, d_queries, qb, max_results, d_keys, stream, nullptr, 0, nullptr, true, d_radius, d_count);
+    return gemm_search(m, d_queries, qb, FirSearch::within(d_radius, max_results, d_count, d_keys), stream);
 }
 
 // 1..8 queries against a gallery too large for the caches: one pass over the fp16 copy (k_gemm_scan_f16x), the rows within one
@@ -2417,7 +2389,7 @@ int fir_gemm_nominations_(fir_gemm* m, int32_t which, int32_t q0, int32_t nq, in
 // super-batch, under the full passes of the one before; keys as the device-pointer forms.
 int fir_gemm_search_staged_(fir_gemm* m, const float* h_queries, float* d_stage, int32_t qb, int32_t k, uint64_t* d_keys, void* stream) {
     if (!h_queries || !d_stage) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    return gemm_search(m, d_stage, qb, k, d_keys, stream, h_queries);
+    return gemm_search(m, d_stage, qb, FirSearch::rows(k, d_keys), stream, h_queries);
 }
 
 }  // extern "C"

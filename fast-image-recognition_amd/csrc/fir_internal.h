@@ -182,7 +182,7 @@ extern "C" int fir_knn_sample_bound_dev_(fir_gallery* g, const float* d_queries,
 // fir_twd_wants_mfma_: 1 when wants_mfma(g, qb, 0, end_pos, classes) holds -- the caller's fir_gallery_set_large_batch_mfma threshold or the
 // automatic rule, the pinned-tuning exclusions, gemm_failed -- and the shadow mode is not FIR_SHADOW_NONE; 0 otherwise. Host only.
 extern "C" int fir_twd_wants_mfma_(fir_gallery* g, int32_t qb, int32_t end_pos);
-// try_mfma_classes / try_mfma_topk: 0 = the keys (and classes) of fir_search_top_classes_keys_dev / fir_search_topk_keys_dev over
+// try_mfma_search (kSearchClasses) / run_mfma (rows) of fir_capi.hip: 0 = the keys (and classes) of fir_search_top_classes_keys_dev / fir_search_topk_keys_dev over
 // [0, end_pos) are queued or written, 1 = this call stays with the scan (nothing was queued), < 0 = error. The class form synchronises
 // `stream`; *exact_answered <- the queries of this call its own exact class scan answered (fir_gemm_stats_ex out[2], this call's share).
 // The row form is asked for a part of a batch (the unreliable queries of qb_call): it takes the matrix cores when the rule holds for

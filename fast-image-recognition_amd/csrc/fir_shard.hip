@@ -51,10 +51,12 @@
 #include "fir_common.h"
 #include "fir_internal.h"
 #include "fir_knn_select.h"
+#include "fir_search_request.h"
 #include "fir_shard_workers.h"
 
 namespace {
 
+using fir::FirSearch;
 using fir::kKeyNone;
 using fir::KnnArgs;
 using fir::KnnCtl;
@@ -370,16 +372,14 @@ int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
 // partial keys, the reduced keys + status element, the gathered keys of all ranks (top-K), the winners' classes + status
 // element and the control block of the K > 8 merge. Every device holds h->spd shards, so the sizes are every device's.
 // A radius call (fir_sharded_search_radius, k = max_results, 0 included) carries qb counts as well: the radii behind the queries,
-// every shard's counts behind all the shards' keys, and the device's counts in count_words(qb) 64-bit words between its keys and
-// the status element -- one payload, one ncclAllGather.
+// every shard's counts behind all the shards' keys, and the device's counts in FirSearch::count_words(qb) 64-bit words between its keys
+// and the status element (FirSearch::status_index) -- one payload, one ncclAllGather.
 struct CallBuffers { size_t dq, parts, keys, gath, cls, sel; };
-inline size_t count_words(int32_t qb, bool radius) { return radius ? ((size_t)qb + 1) / 2 : 0; }
-CallBuffers call_buffers(const fir_sharded* h, int32_t qb, int32_t k, bool host_queries, bool classes, bool radius = false) {
-    const size_t per = (size_t)qb * k, u64 = sizeof(uint64_t), payload = per + count_words(qb, radius);
-    return {host_queries ? ((size_t)qb * h->d + (radius ? (size_t)qb + (qb & 1) : 0)) * sizeof(float) : 0,
-            (per + count_words(qb, radius)) * (size_t)h->spd * u64, (payload + 1) * u64,
-            k > 1 || radius ? (payload + 1) * (size_t)h->nranks * u64 : 0, classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
-            k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 * u64 : 0};
+CallBuffers call_buffers(const fir_sharded* h, int32_t qb, const FirSearch& s, bool host_queries, bool winners_classes) {
+    const size_t u64 = sizeof(uint64_t), payload = s.status_index(qb);
+    return {host_queries ? (size_t)qb * h->d * sizeof(float) + s.radii_bytes(qb) : 0, payload * (size_t)h->spd * u64, (payload + 1) * u64,
+            s.k != 1 || s.is_radius() ? (payload + 1) * (size_t)h->nranks * u64 : 0, winners_classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
+            s.k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 * u64 : 0};
 }
 // Does this call grow anything? Asked ONCE per call, before the fan-out over the devices, of device slot 0's capacities (and
 // the staging area's): a one-int collective hangs on the answer, so it has to be the same on every slot and every rank. It is,
@@ -426,51 +426,55 @@ int merge_knn(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t
     return FIR_OK;
 }
 
-// The keys of one device: every shard it holds scans the batch (K keys per query, K = 1: top-1), then the minimum /
-// K-way merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc). d_radius: the radius call -- every shard's
-// fir_search_radius_keys_dev with global rows, the sum of their counts in the words behind the keys.
-int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t k, hipStream_t st, bool knn = false,
-                const float* d_radius = nullptr) {
+// The merge of nparts lists of k keys per query, `stride` words apart, into out[qb * k]: none for k = 0, the minimum for one key in back-to-back lists, the list merge up to 8, else the select
+int merge_keys(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_t k, uint64_t* out, size_t stride, uint64_t* status_out, hipStream_t st) {
+    if (k > kMergeListMax) return merge_knn(dc, parts, nparts, qb, k, out, stride, status_out, st);
+    if (k == 1 && stride == (size_t)qb) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((qb + 255) / 256)), dim3(256), 0, st, parts, nparts, qb, out);
+    else if (k > 0) hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, parts, nparts, qb, k, out, stride, status_out);
+    return FIR_OK;
+}
+
+// The keys of one device: every shard it holds scans the batch (s.k keys per query, each kind through its gallery call; K = 1:
+// top-1), then the merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc). s.radius (device memory): the
+// radius call -- every shard's fir_search_radius_keys_dev with global rows, the sum of their counts in the words behind the keys.
+int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, const FirSearch& s, hipStream_t st) {
     DevCtx& dc = h->devs[slot];
     uint64_t *parts = dc.parts.as<uint64_t>(), *keys = dc.keys.as<uint64_t>();
-    const size_t per = (size_t)qb * k;
+    const size_t per = s.key_words(qb);
     int32_t* cparts = (int32_t*)(parts + per * (size_t)h->spd);              // [shard here][qb]
     int rc;
     int live = 0;
     for (size_t i = 0; i < dc.shards.size(); ++i) {
-        Shard& s = h->shards[dc.shards[i]];
+        Shard& sh = h->shards[dc.shards[i]];
         if (h->health.fail_step == 1 && h->health.fail_shard - 1 == dc.shards[i])
             return fir_fail_(FIR_ERR_NOMEM, "injected scan failure on shard %d (fir_shard_opts.fail_step = 1)", dc.shards[i]);
-        if (!s.g) continue;
+        if (!sh.g) continue;
         uint64_t* out = parts + (size_t)live * per;
-        rc = d_radius ? fir_search_radius_keys_dev(s.g, d_queries, qb, start, end, d_radius, k, cparts + (size_t)live * qb, k ? out : nullptr, st)
-             : k == 1 ? fir_search_top1_keys_dev(s.g, d_queries, qb, start, end, out, st)
-             : knn  ? fir_search_knn_keys_dev(s.g, d_queries, qb, start, end, k, out, st)
-                    : fir_search_topk_keys_dev(s.g, d_queries, qb, start, end, k, out, st);
+        rc = s.is_radius() ? fir_search_radius_keys_dev(sh.g, d_queries, qb, start, end, s.radius, s.k, cparts + (size_t)live * qb, s.k ? out : nullptr, st)
+             : s.k == 1 ? fir_search_top1_keys_dev(sh.g, d_queries, qb, start, end, out, st)
+             : s.kind == fir::kSearchSelect ? fir_search_knn_keys_dev(sh.g, d_queries, qb, start, end, s.k, out, st)
+                                            : fir_search_topk_keys_dev(sh.g, d_queries, qb, start, end, s.k, out, st);
         if (rc) return rc;
         ++live;
     }
-    if (d_radius) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, cparts, live, (size_t)qb, qb, (int32_t*)(keys + per));
-    if (per == 0) {}                                                         // the count-only call
-    else if (live == 0) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
-    else if (k == 1) hipLaunchKernelGGL(k_shard_min_keys, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, parts, live, (int)per, keys);
-    else if (k > kMergeListMax) { if ((rc = merge_knn(dc, parts, live, qb, k, keys, per, nullptr, st))) return rc; }
-    else hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, parts, live, qb, k, keys, per, (uint64_t*)nullptr);
+    if (s.is_radius()) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, cparts, live, (size_t)qb, qb, (int32_t*)(keys + per));
+    if (live == 0 && per) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
+    else if ((rc = merge_keys(dc, parts, live, qb, s.k, keys, per, nullptr, st))) return rc;
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
 
 // The exchange step over all ranks, on `st`, result in dc.keys (in place); dc.keys[qb * k] carries local_rc in and the worst
 // status of all ranks out. A rank whose scans failed contributes FIR_KEY_NONE keys. Errors here kill the communicator.
-// radius: the counts travel between the keys and the status element (which is then dc.keys[qb * k + count_words]) in the same
+// radius: the counts travel between the keys and the status element (which is then dc.keys[FirSearch::status_index(qb)]) in the same
 // ncclAllGather -- for every k, 0 and 1 included --, and the ranks' counts are summed in place.
-int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t st, int local_rc, bool radius = false) {
+int exchange_keys(fir_sharded* h, int slot, int32_t qb, const FirSearch& s, hipStream_t st, int local_rc) {
     DevCtx& dc = h->devs[slot];
     uint64_t *keys = dc.keys.as<uint64_t>(), *gath = dc.gath.as<uint64_t>();
-    const size_t per = (size_t)qb * k, payload = per + count_words(qb, radius);
+    const size_t per = s.key_words(qb), payload = s.status_index(qb);
     const bool prof = h->profiling && slot == 0;
     if (local_rc && per) hipLaunchKernelGGL(k_shard_fill_u64, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, keys, (int)per, kKeyNone);
-    if (local_rc && radius) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, (const int32_t*)nullptr, 0, (size_t)0, qb, (int32_t*)(keys + per));
+    if (local_rc && s.is_radius()) hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, (const int32_t*)nullptr, 0, (size_t)0, qb, (int32_t*)(keys + per));
     hipLaunchKernelGGL(k_shard_set_u64, dim3(1), dim3(1), 0, st, keys + payload, status_key(local_rc));
     if (prof) {
         if (dc.ev_used + 2 > dc.evs.size())
@@ -482,24 +486,21 @@ int exchange_keys(fir_sharded* h, int slot, int32_t qb, int32_t k, hipStream_t s
         if (dc.ev_used + 2 <= dc.evs.size()) (void)hipEventRecord(dc.evs[dc.ev_used], st);
     }
     ncclResult_t nr;
-    if (k == 1 && !radius) {
+    if (s.k == 1 && !s.is_radius()) {                   // one key per query and no counts: the minimum is the collective's
         nr = ncclAllReduce(keys, keys, per + 1, ncclUint64, ncclMin, dc.comm, st);
     } else {
         nr = ncclAllGather(keys, gath, payload + 1, ncclUint64, dc.comm, st);
         // (the merges find the status element right behind the keys; behind the counts it is taken by itself)
-        uint64_t* status_out = radius ? nullptr : keys + per;
-        if (nr == ncclSuccess && radius) {
+        uint64_t* status_out = s.is_radius() ? nullptr : keys + per;
+        if (nr == ncclSuccess && s.is_radius()) {
             hipLaunchKernelGGL(k_shard_min_status, dim3(1), dim3(64), 0, st, gath + payload, h->nranks, payload + 1, keys + payload);
             hipLaunchKernelGGL(k_shard_sum_counts, dim3((qb + 256) / 256), dim3(256), 0, st, (const int32_t*)(gath + per), h->nranks, 2 * (payload + 1), qb,
                                (int32_t*)(keys + per));
         }
-        if (nr == ncclSuccess && k > kMergeListMax) {
-            if (merge_knn(dc, gath, h->nranks, qb, k, keys, payload + 1, status_out, st)) {
-                const std::string why = fir_last_error();
-                return comm_dead(dc, h->health, FIR_ERR_HIP, why.c_str());
-            }
-        } else if (nr == ncclSuccess && k > 0)
-            hipLaunchKernelGGL(k_shard_merge_topk, dim3((qb + 63) / 64), dim3(64), 0, st, gath, h->nranks, qb, k, keys, payload + 1, status_out);
+        if (nr == ncclSuccess && merge_keys(dc, gath, h->nranks, qb, s.k, keys, payload + 1, status_out, st)) {
+            const std::string why = fir_last_error();
+            return comm_dead(dc, h->health, FIR_ERR_HIP, why.c_str());
+        }
     }
     if (nr != ncclSuccess) return comm_dead(dc, h->health, FIR_ERR_COMM, ncclGetErrorString(nr));
 #ifdef FIR_AUDIT
@@ -541,13 +542,13 @@ int dead_handle(const Health& hl) {
     return fir_fail_(FIR_ERR_STATE, "this sharded handle is closed: an earlier call failed on some rank (code %d); destroy it and create a fresh one", hl.dead_code.load());
 }
 
-// Host-pointer search: queries go to every device from pinned memory, keys (and classes) come back from device slot 0.
-// count != NULL: the radius call (fir_sharded_search_radius: k = max_results, radius[qb] in, count[qb] out).
-int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, int32_t k, int32_t* idx, float* dist,
-                int32_t* class_out, bool knn = false, const float* radius = nullptr, int32_t* count = nullptr) {
-    const bool rad = count != nullptr;
+// Host-pointer search: queries go to every device from pinned memory, keys (and classes: class_out, fir_sharded_classify_top1) come back from device slot 0. hs: the
+// host-side twin of the request -- kind, K, radius[qb] in and count[qb] out in HOST memory, no keys: they come back unpacked into idx / dist; each device gets its own `dev`.
+int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, const FirSearch& hs, int32_t* idx, float* dist, int32_t* class_out) {
+    const bool rad = hs.is_radius(), knn = hs.kind == fir::kSearchSelect;
+    const int32_t k = hs.k;
     if (!h || (qb > 0 && !queries) || (knn && (!idx || !dist))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    if (rad && ((qb > 0 && !radius) || (k >= 1 && k <= FIR_KNN_MAX && (!idx || !dist)) || (k == 0 && (idx || dist)))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (rad && (!hs.count || (qb > 0 && !hs.radius) || (k >= 1 && k <= FIR_KNN_MAX && (!idx || !dist)) || (k == 0 && (idx || dist)))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     const int kmax = knn || rad ? FIR_KNN_MAX : 8;
     if (rad && (k < 0 || k > kmax)) return fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", k, kmax);
@@ -559,15 +560,15 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
     int rc = check_range(h, start, end);
     if (rc) return rc;
     // (argument errors above are the same on every rank: nobody has entered a collective yet)
-    const size_t per = (size_t)qb * k, payload = per + count_words(qb, rad);
-    const size_t rbytes = rad ? ((size_t)qb + (qb & 1)) * sizeof(float) : 0;           // the radii ride behind the queries, in whole 8 bytes
+    const size_t per = hs.key_words(qb), payload = hs.status_index(qb);
+    const size_t rbytes = hs.radii_bytes(qb);                                          // the radii ride behind the queries, in whole 8 bytes
     const size_t qbytes = (size_t)qb * h->d * sizeof(float) + rbytes, kbytes = (payload + 1) * sizeof(uint64_t), cbytes = ((size_t)qb + 1) * sizeof(int32_t);
     // the pinned staging area is part of the agreed growth as well: slot 0 tries it inside the step
     float* hq = nullptr;
     uint64_t* hk = nullptr;
     int32_t* hc = nullptr;
     fir::Published staged;                                                   // slot 0: the staging area is there (or is not)
-    const CallBuffers nb = call_buffers(h, qb, k, true, class_out != nullptr, rad);
+    const CallBuffers nb = call_buffers(h, qb, hs, true, class_out != nullptr);
     const bool grows = call_grows(h->devs[0], nb) || qbytes + kbytes + cbytes > h->pin.cap;   // once, before the fan-out (see call_grows)
     rc = h->devs.run_all([&](int slot) -> int {
         DevCtx& dc = h->devs[slot];
@@ -587,7 +588,7 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
                 std::memcpy(hq, queries, qbytes - rbytes);
                 if (rad) {
                     std::memset(hq + (size_t)qb * h->d, 0, rbytes);
-                    std::memcpy(hq + (size_t)qb * h->d, radius, (size_t)qb * sizeof(float));
+                    std::memcpy(hq + (size_t)qb * h->d, hs.radius, (size_t)qb * sizeof(float));
                 }
             }
             staged.publish(r);
@@ -596,12 +597,13 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
             if (!r) r = r0;                        // (an agreed failure has r != 0 everywhere already)
         }
         if (r) return r;
+        const FirSearch dev{hs.kind, k, 0, nullptr, nullptr, rad ? dc.dq.as<float>() + (size_t)qb * h->d : nullptr, nullptr};   // no host pointer; its radii lie behind its queries
         // from here on every rank takes part in every collective of the call, whatever happens to it
         keep_local(c, hipMemcpyAsync(dc.dq.p, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess
                           ? fir_fail_(FIR_ERR_HIP, "query upload failed")
-                          : device_keys(h, slot, dc.dq.as<float>(), qb, start, end, k, dc.stream, knn, rad ? dc.dq.as<float>() + (size_t)qb * h->d : nullptr));
+                          : device_keys(h, slot, dc.dq.as<float>(), qb, start, end, dev, dc.stream));
         uint64_t* keys = dc.keys.as<uint64_t>();
-        if ((r = exchange_keys(h, slot, qb, k, dc.stream, c.local, rad))) return r;
+        if ((r = exchange_keys(h, slot, qb, dev, dc.stream, c.local))) return r;
         if (class_out && (r = device_classes(h, slot, keys, qb, dc.stream, c.local))) return r;
         if (slot == 0) {
             (void)hipMemcpyAsync(hk, keys, kbytes, hipMemcpyDeviceToHost, dc.stream);
@@ -618,7 +620,7 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
     if ((rc = peer_verdict(h->health, all))) return rc;
     if (class_out)
         for (int i = 0; i < qb; ++i) class_out[i] = hc[i] == 0x7FFFFFFF ? -1 : hc[i];     // ImageTesting.cpp:63: no row found -> -1
-    if (rad) std::memcpy(count, hk + per, (size_t)qb * sizeof(int32_t));
+    if (rad) std::memcpy(hs.count, hk + per, (size_t)qb * sizeof(int32_t));
     if ((idx || dist) && per) return fir_keys_unpack(hk, qb * k, idx, dist);
     return FIR_OK;
 }
@@ -1160,29 +1162,28 @@ int fir_sharded_set_metric(fir_sharded* h, int32_t metric) {
 }
 
 int fir_sharded_search_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* idx, float* dist) {
-    return search_host(h, queries, qb, start_pos, end_pos, 1, idx, dist, nullptr);
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::rows(1, nullptr), idx, dist, nullptr);
 }
 
 int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
                             float* dist) {
-    return search_host(h, queries, qb, start_pos, end_pos, k, idx, dist, nullptr);
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::rows(k, nullptr), idx, dist, nullptr);
 }
 
 int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
                            float* dist) {
-    return search_host(h, queries, qb, start_pos, end_pos, k, idx, dist, nullptr, true);
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::select(k, nullptr), idx, dist, nullptr);
 }
 
 int fir_sharded_search_radius(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* radius,
                               int32_t max_results, int32_t* count, int32_t* idx, float* dist) {
-    if (!count) return fir_fail_(FIR_ERR_ARG, "NULL argument");
-    return search_host(h, queries, qb, start_pos, end_pos, max_results, idx, dist, nullptr, false, radius, count);
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::within(radius, max_results, count, nullptr), idx, dist, nullptr);
 }
 
 int fir_sharded_classify_top1(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t* class_out,
                               int32_t* idx, float* dist) {
     if (!class_out) return fir_fail_(FIR_ERR_ARG, "class_out is NULL");
-    return search_host(h, queries, qb, start_pos, end_pos, 1, idx, dist, class_out);
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::rows(1, nullptr), idx, dist, class_out);
 }
 
 int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, uint64_t* d_keys,
@@ -1205,12 +1206,13 @@ int fir_sharded_search_top1_keys_dev(fir_sharded* h, const float* d_queries, int
         if (dc.hstat()[3] < 0) return peer_verdict(h->health, dc.hstat()[3]);
     }
     (void)hipGetLastError();
-    const CallBuffers nb = call_buffers(h, qb, 1, false, false);
+    const FirSearch top1 = FirSearch::rows(1, d_keys);
+    const CallBuffers nb = call_buffers(h, qb, top1, false, false);
     if ((rc = grow_agreed(c, call_grows(dc, nb), inject_here(h, dc, 2), [&]() -> int { return call_alloc(dc, nb); }))) return rc;
     // every rank enters the exchange; one whose scans failed sends FIR_KEY_NONE keys and a poisoned status element, returns its
     // error here, and the others find it in fir_sharded_sync (the call is asynchronous: nobody waits for the exchange here)
-    keep_local(c, device_keys(h, 0, d_queries, qb, start_pos, end_pos, 1, c.st));
-    if ((rc = exchange_keys(h, 0, qb, 1, c.st, c.local))) return rc;
+    keep_local(c, device_keys(h, 0, d_queries, qb, start_pos, end_pos, top1, c.st));
+    if ((rc = exchange_keys(h, 0, qb, top1, c.st, c.local))) return rc;
     uint64_t* keys = dc.keys.as<uint64_t>();
     hipLaunchKernelGGL(k_shard_note_status, dim3(1), dim3(1), 0, c.st, keys + qb, dc.dstat() + 1, dc.d_hsticky);
     (void)hipMemcpyAsync(d_keys, keys, (size_t)qb * sizeof(uint64_t), hipMemcpyDeviceToDevice, c.st);
