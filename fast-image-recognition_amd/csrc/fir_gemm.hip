@@ -1128,7 +1128,6 @@ struct fir_gemm {
     bool i8_pending = false;
     int i8_pending_qb = 0;
     // ---- knobs, each read once when the state is created (gemm_read_knobs_) ----
-    bool wide = true;                     // bf16: pairs of passes through k_gemm_proxy_bf16_wide (FIR_GEMM_WIDE=0 turns it off)
     int adaptive = 1;                     // fp16 top-1: the append threshold is found during the full pass (k_gemm_proxy_f16x<3, *>), no sample pass
                                           // (profiles/r03_adaptive_threshold.txt); FIR_GEMM_ADAPTIVE=0: the sample flow, 2: the pass on the way whatever the shape
     int adaptive_topk = 1;                // ... and for the K nearest rows (k_gemm_proxy_f16x<4, *>: K slot minima per query); FIR_GEMM_ADAPTIVE_TOPK=0: the sample flow
@@ -1136,8 +1135,7 @@ struct fir_gemm {
     // audit knobs, honoured by the audit build only and never set in production
     float erel_scale = 1.0f;              // the certificate's relative error bound is multiplied by this (FIR_GEMM_EREL_SCALE); tests/test_gpu_gemm.py shows that a bound
                                           // shrunk to a quarter returns a wrong row on a crafted near-tie, i.e. that the suite can see an unsound bound
-    int dbg_block = kGemmBlock;           // timing experiments (FIR_GEMM_DBG_BLOCK=256): the resident adaptive pass with four waves per workgroup = ONE wave per SIMD
-    int dbg_skip = 0;                     // timing experiments: bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no query-fragment re-reads (FIR_GEMM_DBG_SKIP; wrong answers)
+    int dbg_skip = 0;                     // timing forms (FIR_GEMM_DBG_SKIP): bits 0, 1, 2, 5 = no epilogue / gallery stream / query-fragment re-reads / MFMAs (wrong answers), 8 = stamps
     int adapt_dbg = 0;                    // nt_flags bits 2, 3 of the adaptive pass (FIR_GEMM_ADAPT_DBG): 1 = no refresh, 2 = no exchange of the bound between workgroups (still
                                           // sound: a looser bound appends more -- this is how the tests drive lists into overflow and the second-chance pass on benign data)
     bool debug_counts = false;            // appended rows per query of a call's last super-batch on stderr (FIR_GEMM_DEBUG_COUNTS; synchronises)
@@ -1174,8 +1172,8 @@ static void gemm_read_knobs_(fir_gemm* m) {
     if (const char* w = fir_knob_("FIR_GEMM_ADAPTIVE_TOPK")) m->adaptive_topk = std::atoi(w) != 0;
     if (const char* w = fir_knob_("FIR_GEMM_CLASS_SAMPLE_DIV")) m->class_sample_div = std::max(1, std::atoi(w));
 #ifdef FIR_AUDIT      // knobs that change answers: the audit build only (libfir_amd_audit.so; fir_internal.h)
-    if (const char* w = fir_knob_("FIR_GEMM_DBG_SKIP")) m->dbg_skip = std::atoi(w) & 1023;
-    if (const char* w = fir_knob_("FIR_GEMM_DBG_BLOCK")) m->dbg_block = std::atoi(w) == 256 ? 256 : kGemmBlock;     // timing experiments only: the answers are wrong
+    // (the DBG bits k_gemm_proxy_f16x reads; a combination kXTable has no row for runs the shipped form: pick_x)
+    if (const char* w = fir_knob_("FIR_GEMM_DBG_SKIP")) m->dbg_skip = std::atoi(w) & (1 | 2 | 4 | 32 | 256);
     if (const char* w = fir_knob_("FIR_GEMM_EREL_SCALE")) m->erel_scale = (float)std::atof(w);
     if (const char* w = fir_knob_("FIR_GEMM_ADAPT_DBG")) m->adapt_dbg = (std::atoi(w) & 3) << 2;
     if (fir_knob_("FIR_GEMM_DEBUG_COUNTS")) m->debug_counts = true;
@@ -1224,7 +1222,7 @@ static int launch_pairs_(int left, int cap) {
 
 // The 16-row kernels: ONE table gives the function and the name fir_gallery_last_dispatch reports for it.
 typedef void (*fir_x_fn)(const uint4*, const float*, const uint4*, const float*, int64_t, int64_t, int64_t, int, const float*, unsigned long long*, int*, float*,
-                         int, int, int, int, unsigned int*, int);
+                         int, int, int, unsigned int*, int);
 struct fir_x_key {
     int mode;               // 1 = append below tau, 2 = the sample pass, 3 / 4 = the threshold found on the way (top-1 / the K nearest)
     bool streamed;          // the query slabs are streamed per unit (gemm_streamed_)
@@ -1252,11 +1250,8 @@ static const fir_x_entry kXTable[] = {
     FIR_X(1, 0, 2), FIR_X(2, 0, 2), FIR_X(3, 0, 2), FIR_X(4, 0, 2),         // one unit per row block (at most 128 features; resident by definition)
 #ifdef FIR_AUDIT
     // wrong answers: 1, 2, 3, 5, 7 (bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no query-fragment re-reads), 33 / 37 / 35 (no MFMAs, no epilogue:
-    // both streams / the gallery stream alone / the re-reads alone). Right answers, for A/B runs: 512 the L2 touch two units ahead by one workgroup in sixteen,
-    // 256 timestamps of workgroup 0's load bursts (FIR_GEMM_DUMP_PHASES), 128 wave w owns row blocks w, w + 8, ..., 384 the two together, 64 the gallery pieces
-    // one behind each MFMA pair of a unit's first step, 16 the pieces of a unit requested two per step instead of in one burst, 8 the epilogue behind its own row block
-    FIR_X_DBG(1), FIR_X_DBG(2), FIR_X_DBG(3), FIR_X_DBG(5), FIR_X_DBG(7), FIR_X_DBG(512), FIR_X_DBG(256), FIR_X_DBG(128), FIR_X_DBG(384), FIR_X_DBG(64),
-    FIR_X_DBG(33), FIR_X_DBG(37), FIR_X_DBG(35), FIR_X_DBG(16), FIR_X_DBG(8),
+    // both streams / the gallery stream alone / the re-reads alone). Right answers: 256 timestamps of workgroup 0's load bursts (FIR_GEMM_DUMP_PHASES)
+    FIR_X_DBG(1), FIR_X_DBG(2), FIR_X_DBG(3), FIR_X_DBG(5), FIR_X_DBG(7), FIR_X_DBG(256), FIR_X_DBG(33), FIR_X_DBG(37), FIR_X_DBG(35),
 #endif
     FIR_X8(3, 0), FIR_X8(3, 1), FIR_X8(3, 2), FIR_X8(1, 0), FIR_X8(1, 1), FIR_X8(1, 2),
     {{3, false, 0, 8, true, true}, k_gemm_proxy_f16x<3, 0, 0, 0, 8, 1, 2>, "fir::k_gemm_proxy_i8x<3, 0> (256-query tile)"},
@@ -1297,7 +1292,6 @@ static fir_x_fn pick_x(fir_x_key k) {
     if (k.dbg) k.njb = 8;
 #ifdef FIR_AUDIT
     if (k.dbg && k.mode == 3 && !k.streamed && !k.odd) {
-        k.dbg &= 1023;
         if (const fir_x_entry* e = lookup_x(k)) return e->fn;
     }
 #endif
@@ -1327,8 +1321,7 @@ static GemmOperand gemm_operand_(const fir_gemm* m, bool i8) {
 enum GemmBound { kBelowTau, kBelowAwin, kSampleOnly };
 // the kernel's remaining arguments
 struct GemmXRest {
-    bool qnorm;             // `sample` <- the pairs' |q|^2 (the threshold found on the way), NULL otherwise
-    int sample_rows;
+    bool qnorm;             // the kernel's `qnorm` <- the pairs' |q|^2 (the threshold found on the way), NULL otherwise
     int nt_flags;
     unsigned int* words;    // `smin`: smin (the sample pass) or aT of the set, or the uncertified list's length (a second-chance round), ...
     int words_per_query;    // ... and how far a query of the set moves it
@@ -1336,11 +1329,11 @@ struct GemmXRest {
     int tile_pairs = 1;     // pairs of a workgroup's tile: `share` counts tiles
 };
 // ONE launch of a 16-row kernel on `st`: pairs [p0, p0 + P) of scratch set s against rows [0, row_end) of the n, every rb_stride-th row block
-static void gemm_launch_x_(fir_x_fn fn, dim3 grid, int block, hipStream_t st, const GemmOperand& op, const GemmScratch& s, int p0, int P, int64_t n, int64_t row_end,
+static void gemm_launch_x_(fir_x_fn fn, dim3 grid, hipStream_t st, const GemmOperand& op, const GemmScratch& s, int p0, int P, int64_t n, int64_t row_end,
                            int rb_stride, GemmBound bound, const GemmXRest& r) {
     const size_t q0 = (size_t)p0 * 2 * kQT, qa = bound == kSampleOnly ? 0 : q0;
-    hipLaunchKernelGGL(fn, grid, dim3(block), kHalfLds, st, op.frag, op.gnorm, s.qbf + (size_t)p0 * 4 * op.dk * 64, s.qinv + q0, n, (int64_t)0, row_end,
-                       op.dk, (bound == kBelowAwin ? s.awin : s.tau) + qa, s.lists + qa * kListCap, s.counts + qa, r.qnorm ? s.qnorm + q0 : (float*)nullptr, r.sample_rows,
+    hipLaunchKernelGGL(fn, grid, dim3(kGemmBlock), kHalfLds, st, op.frag, op.gnorm, s.qbf + (size_t)p0 * 4 * op.dk * 64, s.qinv + q0, n, (int64_t)0, row_end,
+                       op.dk, (bound == kBelowAwin ? s.awin : s.tau) + qa, s.lists + qa * kListCap, s.counts + qa, r.qnorm ? s.qnorm + q0 : (float*)nullptr,
                        P / r.tile_pairs, r.nt_flags, rb_stride, r.words ? r.words + q0 * r.words_per_query : (unsigned int*)nullptr, r.sub_stride);
 }
 
@@ -1429,7 +1422,6 @@ int fir_gemm_create_range_ex_(fir_gallery* g, int32_t precision, int32_t end_pos
         delete m;
         return fir_fail_(FIR_ERR_ARG, "feature prefix [0,%d) of %d: multiples of 16 inside the row, fp16 form only", end_pos, dd);
     }
-    if (const char* w = fir_knob_("FIR_GEMM_WIDE")) m->wide = std::atoi(w) != 0;   // experiments: 0 = one pass per gallery read
     m->dq8 = (m->feat + 31) / 32 * 4;     // feature groups of 8, padded to a multiple of 4 groups (zeros)
     m->dk16 = (m->feat + 127) / 128 * 8;  // k-blocks of 16, padded to a multiple of 8 (the paired-pass kernel's double-buffer unit)
     if (precision == FIR_GEMM_F16) m->dk16 = (m->feat + 16 * kRing - 1) / (16 * kRing) * kRing;   // ... to whole double-buffer units
@@ -1627,7 +1619,7 @@ static int gemm_finish_(fir_gemm* m, const float* d_queries, int k, uint64_t* d_
                                s.qbf, qs, (const int*)m->fb_list + off, (const int*)m->fb_state, off);
         }
         // one pair over all CUs (share = 1: 256 row ranges), the gallery stream read once (nt)
-        gemm_launch_x_(round_fn, dim3(m->v.cus, 1), kGemmBlock, st, op, s, 0, 1, n, n, 1, kBelowTau, {false, 0, 1, m->fb_state.as<unsigned int>(), 0, off});
+        gemm_launch_x_(round_fn, dim3(m->v.cus, 1), st, op, s, 0, 1, n, n, 1, kBelowTau, {false, 1, m->fb_state.as<unsigned int>(), 0, off});
         gemm_launch_rerank_(m, st, kScQueries, gemm_slot_(m, s, i8), d_queries, e_rel, k, d_keys, m->ok, {m->fb_state, nullptr, nullptr, 0, (const int*)m->fb_list + off, off});
     }
     hipLaunchKernelGGL(k_gemm_fb_collect, dim3(1), dim3(256), 0, st, m->fb_state, (const int*)m->fb_list, (const int*)m->ok, m->fb_list2, (unsigned long long*)d_keys, k);
@@ -1855,8 +1847,8 @@ static int gemm_sample_pass_(fir_gemm* m, const GemmScratch& s, hipStream_t st, 
     const int rb_stride = (int)std::max<int64_t>(1, ((m->v.n + 31) / 32) / sample_blocks);
     for (int p0 = 0; p0 < pairs;) {
         const int P = launch_pairs_(pairs - p0, kShareMax);
-        gemm_launch_x_(pick_x({2, streamed, odd}), dim3(m->v.cus), kGemmBlock, st, gemm_operand_(m, false), s, p0, P, m->v.n, sample_blocks * 32, rb_stride, kSampleOnly,
-                       {false, 0, P <= 1 ? 1 : 0, s.smin, 1, sub_stride});
+        gemm_launch_x_(pick_x({2, streamed, odd}), dim3(m->v.cus), st, gemm_operand_(m, false), s, p0, P, m->v.n, sample_blocks * 32, rb_stride, kSampleOnly,
+                       {false, P <= 1 ? 1 : 0, s.smin, 1, sub_stride});
         p0 += P;
     }
     return FIR_OK;
@@ -1995,7 +1987,6 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
     const bool njb_shape = c.streamed ? !c.odd : (m->dk16 % (4 * kRing)) == 0;
     const int njb = (!c.i8 && k == 1 && adaptive && !m->dbg_skip && njb_shape) ? (nq <= 16 ? 1 : nq <= 32 ? 2 : 8) : 8;
     const int mode = adaptive ? (k > 1 ? 4 : 3) : 1;
-    const int block = adaptive && !c.i8 && !c.streamed ? m->dbg_block : kGemmBlock;
     // algorithmic bytes of ONE launch (what fir_profile_read's event pairs bracket): the fragments once for the pairs that
     // read them together, every pair's query tile and keys
     auto launch_bytes = [&](int P) { return (double)((n + 31) / 32) * op.dk * 1024.0 + P * (4.0 * op.dk * 1024.0 + 128.0 * 8.0); };
@@ -2008,10 +1999,10 @@ static int gemm_pass_f16_(fir_gemm* m, const GemmCall& c, int sb) {
         const fir_x_fn fn = pick_x({mode, c.streamed, c.odd, njb, c.i8, tile, k > 1 ? 0 : m->dbg_skip});
         if ((rc = fir_gallery_profile_begin_(m->g, c.st))) return rc;
         if (adaptive)
-            gemm_launch_x_(fn, dim3(c.grid, 1), block, c.st, op, s, p0, P, n, n, 1, kBelowAwin,
-                           {true, m->sample_rows, nt | m->adapt_dbg, s.aT, k > 1 ? 8 : 1, k > 1 ? k : 0, tile ? 2 : 1});
+            gemm_launch_x_(fn, dim3(c.grid, 1), c.st, op, s, p0, P, n, n, 1, kBelowAwin,
+                           {true, nt | m->adapt_dbg, s.aT, k > 1 ? 8 : 1, k > 1 ? k : 0, tile ? 2 : 1});
         else
-            gemm_launch_x_(fn, dim3(c.grid, 1), block, c.st, op, s, p0, P, n, n, 1, kBelowTau, {false, m->sample_rows, nt, nullptr, 0, 0});
+            gemm_launch_x_(fn, dim3(c.grid, 1), c.st, op, s, p0, P, n, n, 1, kBelowTau, {false, nt, nullptr, 0, 0});
         if ((rc = fir_gallery_profile_end_(m->g, c.st, launch_bytes(P)))) return rc;
         p0 += P;
     }
@@ -2041,7 +2032,7 @@ static void gemm_pass_f32_bf16_(fir_gemm* m, const GemmCall& c, int sb) {
         return;
     }
     // pairs of passes share one read of the gallery (128 queries per wave); an odd last pass goes alone
-    const int pairs = m->wide ? np / 2 : 0;
+    const int pairs = np / 2;
     if (pairs > 0)
         hipLaunchKernelGGL(k_gemm_proxy_bf16_wide, dim3(grid, pairs), dim3(kGemmBlock), kWideLds, c.st, m->gb, m->gnorm, s.qbf, n, m->dk16,
                            s.tau, s.lists, s.counts);

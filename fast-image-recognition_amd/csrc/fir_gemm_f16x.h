@@ -103,8 +103,11 @@ __device__ __forceinline__ i32x4 mfma_x_(const f16x8 a, const f16x8 b, const i32
 // copy nor the merge point the compiler hung an s_waitcnt vmcnt(0) on. ODD = 1: three units or more; ODD = 2: ONE unit (at most 128
 // features), which is the row block's first and last unit at once -- a form of its own, so that every kernel's row loop is one
 // sequence of units (as two run-time paths inside the ODD = 1 kernels it cost those 500 bytes of scratch per lane).
-// MODE 0: one minimum per (row block, query) of rows [row_begin, row_end) -> sample (the order-statistic flow, k_gemm_tau; not
-// instantiated any more: the 16-row kernels always run the smallest-proxy flow);
+// MODE is 1, 2, 3 or 4 (4 = MODE 3 for the K nearest rows: at kSlots, inside the kernel).
+// MODE 1: the full pass, every row below tau is appended; MODE 2: the sample of the smallest-proxy flow -- row blocks
+// 0, rb_stride, 2 rb_stride, ... of the gallery ((row_end - row_begin) / 32 of them, spread over all of it: the reference's
+// galleries are ordered by class), smin[q] <- the smallest proxy seen (fir::f32_orderable bits, atomicMin, caller presets +inf);
+// with sub_stride != 0 (top-K) as kRtSubsets disjoint subsets' minima, smin[subset * sub_stride + q] (k_gemm_tau_kmin).
 // MODE 3: the full pass with the threshold found ON THE WAY (top-1; no sample pass, no threshold kernel): per query the ranks
 // keep T = (smallest proxy seen so far + |q|^2) + one rounding window, as float bits >= 0 so that an unsigned atomicMin orders
 // them -- in LDS per workgroup, mirrored to `smin` (global) by atomicMin whenever a workgroup lowers it (that is where the final
@@ -118,27 +121,22 @@ __device__ __forceinline__ i32x4 mfma_x_(const f16x8 a, const f16x8 b, const i32
 // re-rank's certificate; and every row within the window of the smallest proxy of ALL rows IS appended (its proxy is below
 // every T the pass ever held). With T = +inf at the start the first row block of a wave would append all its rows: its sums
 // are therefore looked at twice -- once only lowering T (then the workgroup exchanges T with `smin`), then, still in the
-// registers, for real. Here `tau` carries the windows, `sample` the |q|^2, `smin` the global T.
-// MODE 1: the full pass, every row below tau is appended; MODE 2: the sample of the smallest-proxy flow -- row blocks
-// 0, rb_stride, 2 rb_stride, ... of the gallery ((row_end - row_begin) / 32 of them, spread over all of it: the reference's
-// galleries are ordered by class), smin[q] <- the smallest proxy seen (fir::f32_orderable bits, atomicMin, caller presets +inf);
-// with sub_stride != 0 (top-K) as kRtSubsets disjoint subsets' minima, smin[subset * sub_stride + q] (k_gemm_tau_kmin).
+// registers, for real. Here `tau` carries the windows, `qnorm` the |q|^2, `smin` the global T.
 // A unit is kRing = 8 gallery pieces = four 32-feature steps; per step two A fragments (the row halves) against eight B
 // fragments: sixteen MFMAs of 16 cycles. The eight B fragments are ONE register set that rolls: fragment j is re-read for
 // the next step right behind the two MFMAs that used it, fourteen MFMAs before its next use.
 // `nt_flags` bit 0: the gallery stream is read once per launch (non-temporal loads; pairs that share it use ordinary loads, so that
 // the line stays in L2 for the other readers). Bits 2, 3: the audit build's looser adaptive bound (no refresh / no exchange).
-// No other bit is read: the experiments that bits 1, 4, 5 and 6 once switched (partner waves staggered by half a unit or half a row
-// block, s_setprio around the MFMA phase, all eight proxies of every query block: DESIGN.md section 4, "The 16-row kernels") were
-// measured, not kept, and their run-time tests are gone from the row loop.
+// No other bit is read. The experiments that further `nt_flags` bits and further DBG bits once switched were measured, not kept, and are
+// gone from the kernel: what they were and what they gave is in DESIGN.md section 4, "The 16-row kernels", and under profiles/.
 constexpr int kXStage = 16;             // staged appends per query and workgroup
 // NJB: query blocks of 16 the wave multiplies against (8 = the whole 128-query tile). A call of at most 16 / 32 queries fills one / two
 // blocks; with NJB = 1 / 2 the pass does an eighth / a quarter of the MFMAs and LDS reads and is what such a call should be: one read
 // of the fp16 fragments at the rate the memory system gives (the tile's layout in LDS and in `qh` is unchanged).
 // DBG (timing experiments only, FIR_GEMM_DBG_SKIP; own instantiations so that the production kernels' register allocation is not
 // touched -- as runtime flags the two tests made the row loop spill): bit 0 = no epilogue, bit 1 = no gallery stream, bit 2 = no
-// re-read of the query fragments, bit 5 = no MFMAs. The answers of such a kernel are wrong. (Right answers, for A/B runs: bit 7 = static
-// ownership of the row blocks, bit 8 = timestamps of workgroup 0's waves.)
+// re-read of the query fragments, bit 5 = no MFMAs (values 1, 2, 4, 32). The answers of such a kernel are wrong. Right answers: bit 8
+// (value 256) = timestamps of workgroup 0's waves.
 // I8: the int8 form (v_mfma_i32_16x16x64_i8, twice the features per instruction). A one-KiB piece is then 16 rows x 64 features -- lane
 // l holds row l & 15, the sixteen features 64 kk + 16 (l >> 4) + 0..15 as bytes -- so a unit of kRing pieces is 256 features and the loop
 // over `dk16` pieces is the fp16 form's at half the features: the gallery is `g8` of fir_gemm_i8.h (rows minus the column means, one
@@ -151,14 +149,14 @@ template <int MODE, int STREAMED, int ODD, int DBG = 0, int NJB = 8, int I8 = 0,
 __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* __restrict__ gh, const float* __restrict__ gnorm, const uint4* qh,
                                                                     const float* __restrict__ qinv, int64_t n, int64_t row_begin, int64_t row_end,
                                                                     int dk16, const float* tau, unsigned long long* lists, int* counts,
-                                                                    float* sample, int sample_rows, int share, int nt_flags,
+                                                                    float* qnorm, int share, int nt_flags,
                                                                     int rb_stride, unsigned int* smin, int sub_stride) {
     extern __shared__ __attribute__((aligned(16))) uint4 lqx[];
     // MODE 1 as a second-chance round (fir_gemm_fb.h): `smin` is the list's length, `sub_stride` the part of it earlier rounds took --
     // nothing left for this round: every workgroup returns at once (a kernel boundary lies between the writers and this load)
     if (MODE == 1 && smin != nullptr && (int)smin[0] - sub_stride <= 0) return;
     const int nt = nt_flags & 1;
-    static_assert(QH == 1 || (QH == 2 && MODE == 3 && !STREAMED && !ODD && NJB == 8 && I8 && !(DBG & (8 | 16 | 64 | 128 | 256 | 512))), "QH = 2: the int8 top-1 pass of two units only");
+    static_assert(QH == 1 || (QH == 2 && MODE == 3 && !STREAMED && !ODD && NJB == 8 && I8 && !(DBG & 256)), "QH = 2: the int8 top-1 pass of two units only");
     constexpr int kTQ = 2 * kQT * QH;                // queries of the workgroup's tile
     constexpr int kStage = QH == 2 ? kXStage / 2 : kXStage;      // (256 queries: eight staged slots each, the same 16 KiB)
     constexpr int kHalfImg = 4 * kRing * 2 * 64;     // QH = 2: uint4 per 128-query image of 512 int8 features (64 KiB)
@@ -203,8 +201,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // The shared form of the resident adaptive passes hands its row blocks out at run time (`next_blk`, below); everything else --
     // the streamed ring (a barrier per unit: every wave has to walk the same units), the sample pass (its subsets go by wave), MODE 1 --
     // keeps the static ownership. These forms know the shared form only (every caller launches them with share >= 1 and gridDim.y == 1,
-    // where share <= 0 means the same as 1: it is taken as 1). DBG & 128: the static ownership, for A/B runs.
-    constexpr bool kDynForm = !STREAMED && kAdapt && !(DBG & 128);
+    // where share <= 0 means the same as 1: it is taken as 1).
+    constexpr bool kDynForm = !STREAMED && kAdapt;
     if (kDynForm && share <= 0) share = 1;
     __shared__ int next_blk;
     unsigned long long t_entry = 0;                   // (DBG & 256)
@@ -231,10 +229,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         tau += pr * 2 * kQT;
         lists += pr * 2 * kQT * kListCap;
         counts += pr * 2 * kQT;
-        if (MODE == 0) sample += pr * 2 * kQT * ((sample_rows + 31) / 32);
         if (MODE == 2 || MODE == 3) smin += pr * 2 * kQT;
         if (MODE == 4) smin += pr * 2 * kQT * 8;
-        if (kAdapt) sample += pr * 2 * kQT;
+        if (kAdapt) qnorm += pr * 2 * kQT;
     }
     const int64_t rbs = MODE == 2 ? rb_stride : 1;                        // gallery row blocks per row block of the pass
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -253,7 +250,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         if (kAppend) scnt[threadIdx.x] = 0;
         if (kDynForm && threadIdx.x == 0) next_blk = wpb;          // (published by the barrier behind the tile's staging)
         if (kAdapt) {
-            qn_s[threadIdx.x] = sample[threadIdx.x];
+            qn_s[threadIdx.x] = qnorm[threadIdx.x];
             win_s[threadIdx.x] = tau[threadIdx.x];
             tq_s[threadIdx.x] = tau_s[threadIdx.x] - qn_s[threadIdx.x];
         }
@@ -344,9 +341,8 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     // from a zero C operand, so query block j's sixteen sums stay readable until the two MFMAs of index j of that step overwrite
     // them -- the check of query block j (four v_max3, an fma, a compare; rarely the eight proxies and an append) sits right in
     // front of them and runs beside the MFMAs of the blocks before it, instead of leaving the matrix pipe to a partner wave that,
-    // alone, waits for its own LDS reads (profiles/r03_gemm_time_decomposition.txt: the epilogue cost 0.18 of 1.56 ms). DBG & 8: the
-    // epilogue where it was, for A/B runs.
-    constexpr bool kDefer = kAppend && !(DBG & 8) && !(DBG & 1);
+    // alone, waits for its own LDS reads (profiles/r03_gemm_time_decomposition.txt: the epilogue cost 0.18 of 1.56 ms).
+    constexpr bool kDefer = kAppend && !(DBG & 1);
     using acc_t = typename std::conditional<I8 != 0, i32x4, f32x4>::type;
     acc_t acc[2][NJB];                               // (written by the MFMAs of a row block's first step, against a zero C operand)
     if (kDefer) {                                    // (a wave's first first step reads them, against p_gmin = +inf: see `pend`)
@@ -431,7 +427,6 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
     };
     int blk_no = 0;
     int dbg_units = 0;                               // (DBG & 256: units walked so far)
-    int touch_e = 0, touch_o = 0;                    // (DBG & 512)
     int64_t rg_next = rg;
     for (; rg < rg_end; rg = rg_next) {
         const bool warm_it = warm;                        // this wave's first row block: T is still what it was preset to
@@ -456,8 +451,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             const int64_t rgn = rg_next;
             a_nxt = FIR_X_BLOCK(rgn < rg_end ? rgn : rg);
         };
-        constexpr bool kNextLate = kDynForm && !(DBG & 512);   // (DBG & 512 reads a_nxt two units ahead)
-        if (!kNextLate) next_block();
+        if (!kDynForm) next_block();
         if (kAdapt) {
             if (!warm_it && wave < NJB && !(nt_flags & 4)) {
                 // What the other workgroups have reached since. Only ATOMICS read `smin`: they execute at the memory side, so what they
@@ -501,17 +495,17 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         // window in `gnorm` at all (and no full block): the loads then read the head of the fp16 fragments, one row block = dk16 KiB
         // >= 8 KiB that every gallery has. The values are used under `full_block` only.
         const float* gn_blk = n >= 32 ? gnorm + (rb * 32 < ((n - 32) & ~(int64_t)3) ? rb * 32 : ((n - 32) & ~(int64_t)3)) : (const float*)gh;
-        const bool full_block = active && rbp * 32 >= row_begin && rbp * 32 + 32 <= row_end && rb * 32 + 32 <= n && (MODE != 0 || rb * 32 + 32 <= sample_rows);
+        const bool full_block = active && rbp * 32 >= row_begin && rbp * 32 + 32 <= row_end && rb * 32 + 32 <= n;
         // MODE 2, sub_stride: eight positions x eight waves = kRtSubsets disjoint subsets of the sampled rows (below)
         unsigned int* smin_blk = MODE == 2 ? smin + (size_t)(wave & 7) * sub_stride : nullptr;       // (position 0's subset of this wave)
         // one query block of a full row block `rbq` against the bound (the append forms, not the warm-up walk); g0 / g1 / gminq = the
         // block's row norms and their minimum
         auto check_jb = [&](int jb, int64_t rbq, const float4 g0, const float4 g1, float gminq, int half = 0) {
-            const int q = half * 2 * kQT + jb * 16 + (lane & 15);
-            // (kDefer: the lane's scale and bound come from registers -- an LDS read here would wait, in order, behind the query
-            // fragments just requested for the next step; a bound that is a row block old is a larger one: it appends more, never less)
-            const float m2 = kDefer ? m2r[jb] : 2.0f * qinv_s[q];
-            const float tq = kDefer ? tqr[jb] : kAdapt ? tq_s[q] : tau_s[q];
+            // (called by a first step only, i.e. under kDefer. The lane's scale and bound come from registers -- an LDS read here would wait,
+            // in order, behind the query fragments just requested for the next step; a bound that is a row block old is a larger one: it
+            // appends more, never less)
+            const float m2 = m2r[jb];
+            const float tq = tqr[jb];
             // with m2 > 0, fl(gmin - m2 amax) <= fl(gn_r - m2 acc_r) for every row r of the lane (gmin <= gn_r, amax >= acc_r, rounding is
             // monotone): `lb >= tq` proves that no row of the block is appended -- seven instructions instead of sixteen. NaN sums never
             // enter amax, as they never enter the minimum below. (v_max3_f32 by hand: fmaxf() on MFMA results quiets every operand first.)
@@ -644,7 +638,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
                 for (int jb = 0; jb < NJB; ++jb) tqr[jb] = tq_s[jb * 16 + (lane & 15)];
             }
-            if (kLast && kNextLate) next_block();
+            if (kLast && kDynForm) next_block();
             const uint4* src = kLast ? a_nxt : a_cur + (size_t)(h + 1) * RING * 64;
             // QH = 2: this lane's address in the image of tile half `half`, as ONE 32-bit LDS address the compiler cannot see through: every
             // fragment of the half is then that register plus an immediate offset (< 64 KiB). From `lqx + constant` it built the second
@@ -661,12 +655,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             const uint4* bq = STREAMED ? lqx + lane + (size_t)(ring_c & 3) * 4 * RING * 64
                               : QH == 2 ? image_of_half(kHalf) + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64
                                        : lqx + lane + (size_t)(h % kUnitsPerSlab) * RING * 4 * 64;
-            // The next unit's eight gallery pieces are requested in one burst in front of the unit. (DBG & 16, measured and not kept: two per
-            // step, behind the fourth and the eighth pair of MFMAs -- every piece still exactly one unit before its use -- ran 6 % slower at
-            // 512 features and 5 % at 256: profiles/r03_gemm_time_decomposition.txt.)
+            // The next unit's gallery pieces are requested in one burst in front of the unit (two per step measured 5-6 % slower:
+            // profiles/r03_gemm_time_decomposition.txt).
             unsigned long long t_burst0 = 0;
             if (DBG & 256) t_burst0 = __builtin_amdgcn_s_memtime();
-            if (kBurst && !(DBG & 16) && !(DBG & 2) && !(DBG & 64)) {
+            if (kBurst && !(DBG & 2)) {
                 if (nt) {
 #pragma unroll
                     for (int u = 0; u < RING; ++u) N[u] = ld_nt(src + (size_t)u * 64 + lane);
@@ -674,15 +667,6 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
 #pragma unroll
                     for (int u = 0; u < RING; ++u) N[u] = src[(size_t)u * 64 + lane];
                 }
-            }
-            if ((DBG & 512) && pair_of_wg == 0) {
-                // (experiment, audit build: ONE of the workgroups that share a row range asks for the unit after next -- one dword per 128-byte
-                // line, 64 lines = the unit's 8 KiB -- so that the fragments are in the XCD's L2 when the sixteen readers' bursts come for them;
-                // the value is looked at two units later, by the next unit of the same parity)
-                const uint4* tgt = h + 2 < units ? a_cur + (size_t)(h + 2) * RING * 64 : a_nxt + (size_t)(h + 2 - units) * RING * 64;
-                int& tch = (h & 1) ? touch_o : touch_e;
-                asm volatile("" ::"v"(tch));
-                tch = *(const int*)(tgt + (size_t)lane * 8);
             }
             if (DBG & 256) {
                 // (timing probe, audit build: when this wave started issuing the unit's eight loads and when the last of them had been issued --
@@ -733,13 +717,6 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         if (kFirst && t == 0) { acc[0][j] = zero; acc[1][j] = zero; }
                     }
                     if (!(DBG & 4)) B[j] = bn[j * 64];
-                    if ((DBG & 64) && t == 0 && RING == 8) {     // (DBG & 64: the next unit's pieces one at a time, behind each MFMA pair of the unit's first step)
-                        N[j] = nt ? ld_nt(src + (size_t)j * 64 + lane) : src[(size_t)j * 64 + lane];
-                    }
-                    if ((DBG & 16) && !(DBG & 2) && (j == 3 || j == 7)) {
-                        const int u = 2 * t + (j == 7 ? 1 : 0);
-                        N[u] = nt ? ld_nt(src + (size_t)u * 64 + lane) : src[(size_t)u * 64 + lane];
-                    }
                     __builtin_amdgcn_sched_barrier(0);            // the re-read stays right behind its fragment's last use
                 }
                 if (STREAMED) request_piece(hq3, (ring_c + 3) & 3, t);      // unit ring_c + 3's slab, into the slot unit ring_c - 1 has left
@@ -847,8 +824,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         }
         if (kAdapt && warm_it) {
             // This wave's first row block, T still at its preset: the sums are looked at twice. First only to lower T (LDS) -- then the
-            // workgroup exchanges with `smin` -- then, still in their registers, for the block's checks like any other block's. (Until
-            // round 4 the block was WALKED twice: one row block in ~120 of a large launch, one in 15 of a one-pair launch over 1M rows.)
+            // workgroup exchanges with `smin` -- then, still in their registers, for the block's checks like any other block's.
             if (active && full_block) {
                 int lw;                                          // (the lane index from the hardware, as in check_jb: nothing of this once-per-wave path is prepared in front of the row loop)
                 asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lw));
@@ -900,17 +876,12 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
         if (!active) continue;
         if (full_block) {
             const float gmin = QH == 2 ? gmin_blk : fminf(fminf(fminf(gns[0].x, gns[0].y), fminf(gns[0].z, gns[0].w)), fminf(fminf(gns[1].x, gns[1].y), fminf(gns[1].z, gns[1].w)));
-            if (kAppend) {
-                if (kDefer) {
-                    pend = true;                                             // checked in the next row block's first step (or behind the loop)
-                    p_rb = rb;                                               // (against tqr, which the last unit refreshed)
-                    pg[0] = gns[0];
-                    pg[1] = gns[1];
-                    p_gmin = gmin;
-                } else {
-#pragma unroll
-                    for (int jb = 0; jb < NJB; ++jb) check_jb(jb, rb, gns[0], gns[1], gmin);
-                }
+            if (kAppend) {                                                   // (= kDefer here: the form without epilogue has left the loop body)
+                pend = true;                                                 // checked in the next row block's first step (or behind the loop)
+                p_rb = rb;                                                   // (against tqr, which the last unit refreshed)
+                pg[0] = gns[0];
+                pg[1] = gns[1];
+                p_gmin = gmin;
                 continue;
             }
 #pragma unroll
@@ -928,9 +899,9 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         mn = fminf(mn, pv[4 * s + reg]);                   // NaN never enters, like k_gemm_tau's ordering
                     }
                 }
-                if (MODE == 2 && !sub_stride) {
+                if (!sub_stride) {                                           // (MODE 2: every other mode appends and has left above)
                     smallest[jb] = fminf(smallest[jb], mn);
-                } else if (MODE == 2) {
+                } else {
                     // the K-nearest sample: kRtSubsets = 8 positions (of a lane's eight rows) x 8 waves disjoint subsets -- every sampled row
                     // block feeds eight of them (a class of a few dozen rows then shows in eight subsets, not in one)
 #pragma unroll
@@ -942,17 +913,11 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                         v = o < v ? o : v;
                         if (lane < 16 && v < __builtin_huge_valf()) atomicMin(&smin[(size_t)(i * 8 + (wave & 7)) * sub_stride + q], fir::f32_orderable(v));
                     }
-                } else {
-                    float o = __shfl_xor(mn, 16, 64);
-                    mn = o < mn ? o : mn;
-                    o = __shfl_xor(mn, 32, 64);
-                    mn = o < mn ? o : mn;
-                    if (MODE == 0) { if (lane < 16) sample[(size_t)(rb - rb_begin) * (2 * kQT) + q] = mn; }
                 }
             }
             continue;
         }
-        // a block that straddles the end of the rows (or of the sample): row by row
+        // a block that straddles the end of the rows: row by row
         int ls;
         // (the lane index from the hardware, as in check_jb -- from `lane` the compiler built this path's eight list addresses in front
         // of the row loop and spilled them)
@@ -968,9 +933,7 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
                 const int64_t row = rb * 32 + 16 * (i >> 2) + 4 * (ls >> 4) + (i & 3);
                 if (row >= n || (MODE != 2 && (row < row_begin || row >= row_end))) continue;
                 const float p = __builtin_fmaf(-m2, (float)acc[i >> 2][jb][i & 3], gnorm[row]);
-                if (MODE == 0) {
-                    if (row < sample_rows) mn = p < mn ? p : mn;
-                } else if (MODE == 2) {
+                if (MODE == 2) {
                     mn = p < mn ? p : mn;
                 } else if (p < tq) {
                     const int slot = atomicAdd(&counts[q], 1);
@@ -984,13 +947,12 @@ __global__ void __launch_bounds__(kGemmBlock, 1) k_gemm_proxy_f16x(const uint4* 
             asm volatile("" ::"v"(tq), "v"(m2));
             if (MODE == 2 && !sub_stride) {
                 smallest[jb] = fminf(smallest[jb], mn);
-            } else if (MODE != 1 && !kAdapt) {
+            } else if (MODE == 2) {
                 float o = __shfl_xor(mn, 16, 64);
                 mn = o < mn ? o : mn;
                 o = __shfl_xor(mn, 32, 64);
                 mn = o < mn ? o : mn;
-                if (MODE == 0) { if (lane < 16) sample[(size_t)(rb - rb_begin) * (2 * kQT) + q] = mn; }
-                else if (lane < 16 && mn < __builtin_huge_valf()) atomicMin(&smin_blk[q], fir::f32_orderable(mn));     // (a straddling block: one subset takes its minimum)
+                if (lane < 16 && mn < __builtin_huge_valf()) atomicMin(&smin_blk[q], fir::f32_orderable(mn));     // (a straddling block: one subset takes its minimum)
             }
         }
     }

@@ -376,10 +376,10 @@ extern "C" int fir_gemm_knn_f64_(fir_gemm* m, const double* d_qc, int32_t qb, in
             const int nt_flag = P <= 1 ? 1 : 0;
             if (ev_pair && first) FIR_HIP(hipEventRecord(ev_pair[0], st));
             if (adaptive)
-                gemm_launch_x_(pick_x({kp > 1 ? 4 : 3, streamed, odd}), dim3(grid, 1), kGemmBlock, st, op, s, p0, P, n, n, 1, kBelowAwin,
-                               {true, 0, nt_flag, s.aT, kp > 1 ? 8 : 1, kp > 1 ? kp : 0});
+                gemm_launch_x_(pick_x({kp > 1 ? 4 : 3, streamed, odd}), dim3(grid, 1), st, op, s, p0, P, n, n, 1, kBelowAwin,
+                               {true, nt_flag, s.aT, kp > 1 ? 8 : 1, kp > 1 ? kp : 0});
             else
-                gemm_launch_x_(pick_x({1, streamed, odd}), dim3(grid, 1), kGemmBlock, st, op, s, p0, P, n, n, 1, kBelowTau, {false, 0, nt_flag, nullptr, 0, 0});
+                gemm_launch_x_(pick_x({1, streamed, odd}), dim3(grid, 1), st, op, s, p0, P, n, n, 1, kBelowTau, {false, nt_flag, nullptr, 0, 0});
             if (ev_pair && first) {
                 FIR_HIP(hipEventRecord(ev_pair[1], st));
                 if (flops_per_launch) *flops_per_launch = 2.0 * (double)n * d * 128.0 * P;

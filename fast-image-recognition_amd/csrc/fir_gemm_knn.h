@@ -93,24 +93,32 @@ __device__ __forceinline__ int wave_list_smallest_(const unsigned long long* L, 
     return valid;
 }
 
-// The K nearest rows (kTopKMax < K <= 256) from the lists of one append pass below k_gemm_tau_class's bound. One wave per query.
+// The re-rank of one append pass below k_gemm_tau_class's bound, for the K nearest rows (kTopKMax < K <= 256) and, RADIUS, for every
+// row within radius[q]. One wave per query.
 //   1. a list that overflowed is not certified: the exact form answers the query.
 //   2. p_K = the K-th smallest proxy of the list (a radix select over the proxies: K rounds of list_kth_smallest_ would be ~10 000
 //      wave steps at K = 256 over 2 500 entries), +inf for a list shorter than K: everything is re-ranked.
 //   3. every entry with a proxy <= p_K + 2 E d is re-ranked in the reference's arithmetic (rerank_gather_f32_) and its exact key
 //      written back over its list entry; entries outside the window, and rows with dist >= 100000, become kKeyNone.
-//   4. the K smallest exact keys, ascending, padded with kKeyNone: a radix select for the K-th smallest key T (keys are unique --
-//      the row is part of the key --, so a cut inside a run of equal distances is exact), the keys <= T compacted into LDS and
-//      sorted there. LDS: 1 KiB of histogram + 2 KiB of keys next to the re-rank's rows; the list itself stays in global memory
-//      (sorting 4 096 keys in LDS would take 32 KiB per wave and leave the gathers three waves per CU).
-// Certificate, against the K-th exact distance D (100000 with fewer than K found): rerank_certified_ as k_gemm_rerank_classes
-// calls it. Every row not appended or not re-ranked then has a reference distance above D, the K rows found are at or below
-// D, so the K smallest keys over ALL rows are the K found. Strict '>': a NaN never certifies, a tie with the K-th does not either.
-__global__ void __launch_bounds__(64) k_gemm_rerank_knn(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
-                                                         const float4* __restrict__ gal4, const float* __restrict__ queries,
-                                                         const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4,
-                                                         int64_t row_offset, float e_rel, int ngroup, int k, unsigned long long* __restrict__ out_key,
-                                                         int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor) {
+//   4. the K smallest exact keys, ascending, padded with kKeyNone (wave_list_smallest_). LDS: 1 KiB of histogram + 2 KiB of keys
+//      next to the re-rank's rows; the list itself stays in global memory (sorting 4 096 keys in LDS would take 32 KiB per wave
+//      and leave the gathers three waves per CU).
+// Certificate, against the K-th exact distance D (100000 with fewer than K found -- any qualifying row outside the re-ranked set
+// would then belong to the answer): rerank_certified_ as k_gemm_rerank_classes calls it. Every row not appended or not re-ranked
+// then has a reference distance above D, the K rows found are at or below D, so the K smallest keys over ALL rows are the K found.
+// Strict '>': a NaN never certifies, a tie with the K-th does not either.
+// RADIUS (the query brings its bound, no row sample was scanned) differs in three places: the window is +inf, so EVERY entry is
+// re-ranked; a key is kept only if `dist < radius` as well; out_count[q] = the keys left, of which the min(count, k) smallest are
+// written (k = 0: the count alone, `out` is never written), and the radius stands in the place of D (the cut-off 100000 for a
+// radius at or above it, or NaN). A row never appended has a proxy >= tau, hence a reference distance >= (|q|^2 + tau) / d - E,
+// which the certificate finds above the radius: `dist < radius` is false for it, it is not part of the answer, and every row that
+// is was appended, re-ranked exactly and counted.
+template <bool RADIUS>
+__device__ __forceinline__ void gemm_rerank_list_(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
+                                                  const float* __restrict__ radius, const float4* __restrict__ gal4, const float* __restrict__ queries,
+                                                  const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4,
+                                                  int64_t row_offset, float e_rel, int ngroup, int k, unsigned long long* __restrict__ out_key,
+                                                  int* __restrict__ out_count, int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long sorted[fir::kKnnGemmMax];
     const int q = blockIdx.x, lane = threadIdx.x;
@@ -122,73 +130,49 @@ __global__ void __launch_bounds__(64) k_gemm_rerank_knn(unsigned long long* list
     const int have = cnt;
     unsigned long long* L = lists + (size_t)q * kListCap;
     unsigned long long* out = out_key + (size_t)q * k;
-    const float qn = qnorm[q], gmax = gnorm_max_p[0];
-    float pk = __builtin_huge_valf();                                   // a list shorter than K is re-ranked whole
-    if (have >= k) pk = fir::f32_from_orderable((uint32_t)(wave_list_select_(L, have, k, 4, hist, lane) >> 32));
+    const float qn = qnorm[q], gmax = gnorm_max_p[0], r = RADIUS ? radius[q] : 0.f;
+    float pk = __builtin_huge_valf();                                   // a list shorter than K is re-ranked whole, a radius's always
+    if (!RADIUS && have >= k) pk = fir::f32_from_orderable((uint32_t)(wave_list_select_(L, have, k, 4, hist, lane) >> 32));
     const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, pk);
     extern __shared__ __attribute__((aligned(16))) float4 crow[];
     const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)q * qstride, lane);
     const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int base, unsigned long long v, bool in, unsigned long long mask) {
-        if (base + lane < have && !in) L[base + lane] = kKeyNone;
+        if (base + lane < have && !in) L[base + lane] = kKeyNone;       // (RADIUS: a NaN proxy, never appended)
         rerank_gather_f32_(mask, v, base, lane, ngroup, lds, gal4, rowmajor, dp4, d, [&](int i, unsigned long long cv, float dist) {
             const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
-            L[i] = dist < fir::kNotFound ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
+            L[i] = (!RADIUS || dist < r) && dist < fir::kNotFound ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
         });
     });
     __threadfence_block();                                              // the exact keys, written by other lanes, are read below
     __syncthreads();
     const int valid = wave_list_smallest_(L, have, k, hist, sorted, out, lane);
-    const int take = valid < k ? valid : k;
-    if (lane == 0) {    // (fewer than K found: any qualifying row outside the re-ranked set would belong to the answer)
-        const unsigned long long kth_exact = take == k ? sorted[k - 1] : kKeyNone;
+    if (lane != 0) return;
+    if (RADIUS) {
+        out_count[q] = valid;
+        ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, r < fir::kNotFound, r, n, walk.reranked) ? 1 : 0;
+    } else {
+        const unsigned long long kth_exact = valid >= k ? sorted[k - 1] : kKeyNone;
         ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, kth_exact != kKeyNone, fir::f32_from_orderable((uint32_t)(kth_exact >> 32)), n,
                                          walk.reranked) ? 1 : 0;
     }
 }
 
-// Every row within a per-query radius (fir_gemm_search_radius_keys_dev) from the lists of one append pass below k_gemm_tau_class's
-// bound on radius[q] -- the query brings its bound, no row sample is scanned. One wave per query.
-//   1. a list that overflowed is not certified: the store + count + select form answers the query.
-//   2. EVERY entry is re-ranked in the reference's arithmetic (rerank_gather_f32_; the window is +inf) and its exact key written
-//      back over its list entry; rows with dist < radius or dist < 100000 false become kKeyNone. count[q] = the keys left.
-//   3. the min(count, k) smallest exact keys, ascending, padded with kKeyNone (wave_list_smallest_; k = 0: the count alone).
-// Certificate: rerank_certified_ with the radius in the place of the K-th exact distance (the cut-off 100000 for a radius at or
-// above it, or NaN). A row never appended has a proxy >= tau, hence a reference distance >= (|q|^2 + tau) / d - E, which the
-// certificate finds above the radius: `dist < radius` is false for it, it is not part of the answer, and every row that is was
-// appended, re-ranked exactly and counted. Strict '>': a NaN bound certifies nothing.
+__global__ void __launch_bounds__(64) k_gemm_rerank_knn(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
+                                                         const float4* __restrict__ gal4, const float* __restrict__ queries,
+                                                         const float* __restrict__ qnorm, const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4,
+                                                         int64_t row_offset, float e_rel, int ngroup, int k, unsigned long long* __restrict__ out_key,
+                                                         int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor) {
+    gemm_rerank_list_<false>(lists, counts, tau, nullptr, gal4, queries, qnorm, gnorm_max_p, n, d, dp4, row_offset, e_rel, ngroup, k, out_key, nullptr, ok, qstride,
+                             rowmajor);
+}
+
+// Every row within a per-query radius (fir_gemm_search_radius_keys_dev): gemm_rerank_list_'s RADIUS form.
 __global__ void __launch_bounds__(64) k_gemm_rerank_radius(unsigned long long* lists, const int* __restrict__ counts, const float* __restrict__ tau,
                                                             const float* __restrict__ radius, const float4* __restrict__ gal4,
                                                             const float* __restrict__ queries, const float* __restrict__ qnorm,
                                                             const float* __restrict__ gnorm_max_p, int64_t n, int d, int dp4, int64_t row_offset, float e_rel,
                                                             int ngroup, int k, unsigned long long* __restrict__ out_key, int* __restrict__ out_count,
                                                             int* __restrict__ ok, int qstride, const float4* __restrict__ rowmajor) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned long long sorted[fir::kKnnGemmMax];
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const int cnt = counts[q];
-    if (cnt > kListCap) {                           // rows below tau were dropped: the exact form answers this query
-        if (lane == 0) ok[q] = 0;
-        return;
-    }
-    const int have = cnt;
-    unsigned long long* L = lists + (size_t)q * kListCap;
-    unsigned long long* out = out_key + (size_t)q * k;                  // (k = 0: never written)
-    const float qn = qnorm[q], gmax = gnorm_max_p[0], r = radius[q];
-    const RerankWindow w = rerank_window_(e_rel, qn, gmax, d, __builtin_huge_valf());
-    extern __shared__ __attribute__((aligned(16))) float4 crow[];
-    const RerankLds lds = rerank_lds_f32_(crow, ngroup, dp4, d, queries + (size_t)q * qstride, lane);
-    const RerankWalk walk = rerank_walk_(L, have, w.win, lane, [&](int base, unsigned long long v, bool in, unsigned long long mask) {
-        if (base + lane < have && !in) L[base + lane] = kKeyNone;       // (a NaN proxy: never appended)
-        rerank_gather_f32_(mask, v, base, lane, ngroup, lds, gal4, rowmajor, dp4, d, [&](int i, unsigned long long cv, float dist) {
-            const int64_t row = (int64_t)(uint32_t)(cv & 0xFFFFFFFFull);
-            L[i] = dist < r && dist < fir::kNotFound ? fir::key_pack(dist, (uint32_t)(row + row_offset)) : kKeyNone;
-        });
-    });
-    __threadfence_block();                                              // the exact keys, written by other lanes, are read below
-    __syncthreads();
-    const int valid = wave_list_smallest_(L, have, k, hist, sorted, out, lane);
-    if (lane == 0) {
-        out_count[q] = valid;
-        ok[q] = rerank_certified_<float>(cnt, tau[q], walk.p_out, qn, d, w.E, r < fir::kNotFound, r, n, walk.reranked) ? 1 : 0;
-    }
+    gemm_rerank_list_<true>(lists, counts, tau, radius, gal4, queries, qnorm, gnorm_max_p, n, d, dp4, row_offset, e_rel, ngroup, k, out_key, out_count, ok, qstride,
+                            rowmajor);
 }

@@ -2,7 +2,7 @@
 unconditionally, from a clamped address, and reads the bounds the next row block's first step checks against; the first
 step checks the previous block's sums without asking whether anything is owed, and the rare path of that check lies out of
 line. Whatever the unit sequence -- one unit that is first and last at once, two without a middle, an odd number, the
-streamed ring, the sixteen-piece units of the few-block forms, the K-nearest form -- the keys are the exact scan's
+streamed ring, the sixteen-piece units of the few-block forms, the K-nearest form, the sample flow's two passes -- the keys are the exact scan's
 (set_large_batch_mfma(0)) on the same handle, bit for bit. The shapes are the smallest at which each of these paths is
 taken; galleries too small for the automatic rule get the caller's threshold (the number of queries of the call)."""
 import numpy as np
@@ -73,6 +73,23 @@ def test_units_per_row_block(fir, d, units, odd):
     assert f"<3, 0, {odd}>" in kern, kern
     assert_same_keys(got, want)
     check_planted(got, N_MULTI)
+    assert_no_detours(st)
+
+
+@pytest.mark.parametrize("k", [1, 5])
+@pytest.mark.parametrize("d,odd", [(100, 2), (256, 0), (384, 1)])
+def test_sample_flow_units_per_row_block(fir, monkeypatch, d, odd, k):
+    """The smallest-proxy sample flow (FIR_GEMM_ADAPTIVE=0, read when the handle's matrix-core state is made): the sample pass
+    <2, 0, odd> -- for k = 5 with its 64 subsets' minima -- gives the bound, the full pass <1, 0, odd> appends every row below it and
+    is the kernel the call reports. One unit, an even number, an odd number: the epilogues of these two modes are not the ones
+    <3, *> and <4, *> run."""
+    monkeypatch.setenv("FIR_GEMM_ADAPTIVE", "0")
+    rows, q = gallery_and_queries(500 + d, N_MULTI, d, QB_MULTI)
+    got, want, st, kern = both_on_one_handle(fir, rows, q, k=k)
+    assert f"<1, 0, {odd}>" in kern, kern
+    assert_same_keys(got, want)
+    if k == 1:
+        check_planted(got, N_MULTI)
     assert_no_detours(st)
 
 

@@ -20,7 +20,7 @@ Every entry of kXTable is reached by a call of the shipped library: <3, *> and <
 sample flow (FIR_GEMM_ADAPTIVE=0, a knob the shipped library honours; the K-nearest and distinct-class calls take it by default at
 some shapes). The sample pass <2, *> writes no list: it is checked through the bound it produces. <1, *> also runs as the
 second-chance round, whose lists live elsewhere (the state's `sc` set): fir_gemm_nominations_ reads them with which = 1
-(test_second_pass_lists). MODE 0 is not instantiated. The distinct-classes flow rewrites its list entries in the re-rank and is not
+(test_second_pass_lists). The distinct-classes flow rewrites its list entries in the re-rank and is not
 covered here."""
 import ctypes as C
 
