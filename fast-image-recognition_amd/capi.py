@@ -56,6 +56,11 @@ SYMBOLS = [
     ("fir_search_knn_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_search_radius", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_radius_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top1_other_class", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top1_other_class_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_gallery_other_class_keys_dev", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_gallery_other_class", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_gallery_far_threshold", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp]),
     ("fir_search_top_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top_classes_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_class_keys_merge", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
@@ -123,6 +128,7 @@ SYMBOLS = [
     ("fir_sharded_search_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_search_topk", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_sharded_search_knn", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_sharded_search_top1_other_class", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_search_radius", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_classify_top1", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_sharded_search_top1_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
@@ -388,6 +394,40 @@ class Gallery:
         _check(lib().fir_search_radius_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(radius_ptr), max_results, _vp(count_ptr),
                                                 _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
 
+    def search_top1_other_class(self, queries, exclude_class, start=0, end=0):
+        """The nearest row of each query among the rows whose class differs from exclude_class (a scalar, or one per query; any
+        int32): (idx, dist), each [qb]; -1 / 100000 where no row qualifies."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        qb = q.shape[0]
+        ex = np.ascontiguousarray(np.broadcast_to(np.asarray(exclude_class, np.int32).reshape(-1), (qb,)))
+        idx = np.empty(qb, np.int32)
+        dist = np.empty(qb, np.float32)
+        _check(lib().fir_search_top1_other_class(self._h, pq, qb, start, end, ex.ctypes.data_as(_vp), idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_top1_other_class_keys_dev(self, q_ptr, qb, exclude_ptr, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_top1_other_class_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(exclude_ptr) if exclude_ptr else None,
+                                                          _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
+    def other_class(self, start=0, end=0):
+        """Every row of the gallery against the gallery with its own class excluded (row i is the query): (idx, dist), each [n];
+        -1 / 100000 for a row that has no row of another class."""
+        idx = np.empty(self.n, np.int32)
+        dist = np.empty(self.n, np.float32)
+        _check(lib().fir_gallery_other_class(self._h, start, end, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def other_class_keys_dev(self, row0, m, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_gallery_other_class_keys_dev(self._h, row0, m, start, end, _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
+    def far_threshold(self, false_accept_rate, start=0, end=0):
+        """The reference's getThreshold over the distances of other_class(): (threshold, min_dist, max_dist, rows_counted)."""
+        thr, lo, hi = C.c_float(), C.c_float(), C.c_float()
+        cnt = C.c_int64()
+        _check(lib().fir_gallery_far_threshold(self._h, start, end, false_accept_rate, C.byref(thr), C.byref(lo), C.byref(hi), C.byref(cnt)))
+        return np.float32(thr.value), np.float32(lo.value), np.float32(hi.value), int(cnt.value)
+
     def search_top_classes(self, queries, num_classes, k, start=0, end=0):
         """The k nearest distinct classes of each query: (classes, idx, dist), each [qb, k]; unused slots -1 / -1 / 100000."""
         q, pq = _f32(queries)
@@ -615,6 +655,18 @@ class ShardedGallery:
         idx = np.empty((q.shape[0], k), np.int32)
         dist = np.empty((q.shape[0], k), np.float32)
         _check(lib().fir_sharded_search_knn(self._h, pq, q.shape[0], start, end, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_top1_other_class(self, queries, exclude_class, start=0, end=0):
+        """Gallery.search_top1_other_class over the shards: global row indices, the unsharded handle's keys."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        qb = q.shape[0]
+        ex = np.ascontiguousarray(np.broadcast_to(np.asarray(exclude_class, np.int32).reshape(-1), (qb,)))
+        idx = np.empty(qb, np.int32)
+        dist = np.empty(qb, np.float32)
+        _check(lib().fir_sharded_search_top1_other_class(self._h, pq, qb, start, end, ex.ctypes.data_as(_vp), idx.ctypes.data_as(_vp),
+                                                         dist.ctypes.data_as(_vp)))
         return idx, dist
 
     def search_radius(self, queries, radius, max_results, start=0, end=0):

@@ -81,9 +81,18 @@ struct fir_gallery {
     GalleryBuf<int32_t> didx;
     GalleryBuf<float> rowsum;     // chi-square nomination (kChi2Harm): per-row sums over [rs_start, rs_end) + their maximum (rowsum[n])
     FirBuf knn;                   // fir_search_knn: one query tile's stored distances + the select's control block (knn_plan)
+    // fir_search_top1_other_class and the self-join over it: the excluded classes padded to whole tiles; the two nearest classes of a routed
+    // batch (keys, classes); one block of gallery rows back in row-major form, its keys; the statistic's float row + FarStats + the threshold
+    GalleryBuf<int32_t> excl;
+    GalleryBuf<uint64_t> okeys;
+    GalleryBuf<int32_t> ocls;
+    GalleryBuf<float> selfq;
+    GalleryBuf<uint64_t> selfkeys;
+    GalleryBuf<float> fardist;
     FirBuf scratch[25];
     size_t scratch_bytes() const {
-        size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap;
+        size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap + excl.cap + okeys.cap + ocls.cap + selfq.cap +
+                     selfkeys.cap + fardist.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
         return sum;
     }
@@ -171,12 +180,12 @@ typedef void (*scan_fn)(const ScanArgs);
 // the numbers those names have always carried:
 //   metric     0 L2, 1 chi-square, 2 KL, 3 / 4 their plain-range forms, 5-7 the nomination metrics (fir_common.h)
 //   U          kU chunks per load group, kUDeep in the few-tiles form, kUSub in k_scan_subranges
-//   epilogue   0 top-1, 1 top-K, 2 store, 3 append, 5 class minimum
+//   epilogue   0 top-1, 1 top-K, 2 store, 3 append, 5 class minimum, 6 top-1 over the other classes
 //   KMAX       kKMax
 //   waves per SIMD   kWps; kWpsPlain for the metrics from 3 on
 enum ScanKind { kGeneric, kDeep, kL2Lds, kL2Scalar, kNominate, kSubranges };
 constexpr int kEpiSubranges = 4;   // selector only: k_scan_subranges (one stored distance per sub-range)
-static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kEpiClassMin == 5 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
+static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kEpiClassMin == 5 && kEpiTop1Other == 6 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
                   kKLInRange == 4 && kChi2Approx == 5 && kChi2Harm == 6 && kKLEnt == 7 && kU == 8 && kUDeep == 16 && kUSub == 8 && kKMax == 8 && kWps == 4 && kWpsPlain == 3,
               "kScanTable spells these as numbers");
 struct ScanRow { int kind, epi, qb, metric; scan_fn fn; const char* name; };
@@ -209,6 +218,9 @@ static const ScanRow kScanTable[] = {
     FIR_SUB(1) FIR_SUB(2) FIR_SUB(4) FIR_SUB(8)
     // top_classes_dev: the smallest key of every class, tiles of 8 queries
     FIR_SCAN_M(5, 8)
+    // other_class_dev: top-1 over the rows of another class, the tile sizes and the few-tiles form of the generic top-1 scan
+    FIR_DEEP(6, 0, 4) FIR_DEEP(6, 1, 4) FIR_DEEP(6, 2, 4) FIR_DEEP(6, 3, 3) FIR_DEEP(6, 4, 3)
+    FIR_SCAN_M(6, 1) FIR_SCAN_M(6, 2) FIR_SCAN_M(6, 4) FIR_SCAN_M(6, 8)
 };
 #undef FIR_ROW
 #undef FIR_SCAN
@@ -235,12 +247,13 @@ ScanKernel select_scan(int epi, int qb, int metric, bool whole_chunks, int dp4, 
     const size_t tile = (size_t)(dp4 + 1) * qb * 16;                       // query tile + one zero chunk of slack
     const size_t tile_max = epi == kEpiAppend ? 64 * 1024 : kMaxQueryTileLds;
     const size_t deep_tile = (size_t)dp4 * 4 * qb * sizeof(float);
+    const size_t deep_extra = epi == kEpiTop1Other ? 16 : 0;               // the excluded classes behind the staged tile
     ScanKernel k;
     const ScanRow* r = nullptr;
     if (epi == kEpiSubranges) r = scan_row(kSubranges, epi, qb, metric);
     else if (l2_hand && tile <= tile_max && (r = scan_row(kL2Lds, epi, qb, metric))) k.lds_bytes = tile;
     else if (l2_hand && (r = scan_row(kL2Scalar, epi, qb, metric))) k.lds_bytes = 0;
-    else if (few_tiles && deep_tile <= 64 * 1024 && (r = scan_row(kDeep, epi, qb, metric))) k.lds_bytes = deep_tile;
+    else if (few_tiles && deep_tile + deep_extra <= 64 * 1024 && (r = scan_row(kDeep, epi, qb, metric))) k.lds_bytes = deep_tile + deep_extra;
     else if (epi == kEpiAppend && qb == 16) r = scan_row(kNominate, epi, qb, metric);
     else r = scan_row(kGeneric, epi, qb, metric);
     if (!r) return k;
@@ -437,7 +450,7 @@ struct ClassPass { const float* tau; int32_t num_classes; int32_t nq; bool tiles
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
 int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
-             int init_keys = 0, const ClassPass* cp = nullptr, int live = 0) {
+             int init_keys = 0, const ClassPass* cp = nullptr, int live = 0, const int32_t* excl = nullptr) {
     // ny > 1 (top-1 kernels, the class-minimum scan and the store scan only): ny consecutive query tiles of qb_tile queries in ONE launch;
     // live > 0 (the store scan): the launch's live queries, the last tile may be part full -- query y * qb_tile + q goes to out + that * out_stride
     const int kk = g->dp4 * 4;
@@ -473,13 +486,14 @@ int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, co
     a.qt_stride = (int64_t)kk * qb_tile;
     a.range = g->range;
     a.serial = g->q_serial;
+    a.excl = excl;                  // kEpiTop1Other: the tile-padded excluded classes of this launch's first query
     if (cp) {
         a.tau = cp->tau;
         a.num_classes = cp->num_classes;
         a.nq = cp->nq;
     }
     // algorithmic bytes of one launch: per pass the gallery range once (the class-minimum scan: and a label per row), the query tile, the keys
-    const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
+    const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp || excl ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
     int rc;
     if (!scope.quiet && (rc = fir_gallery_profile_begin_(g, st))) return rc;
     hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
@@ -2016,14 +2030,71 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
 namespace {
 // The host-pointer body of fir_search_knn, fir_search_radius and fir_search_top_classes, arguments checked. `s` names the kind, K and num_classes; its device
 // pointers are made here, in the handle's buffers (behind the keys' slots the counts out, then the radii in). Matrix cores, else the kind's exact form.
-struct HostOut { int32_t* idx; float* dist; int32_t* class_out = nullptr; const float* radius = nullptr; int32_t* count = nullptr; };
+struct HostOut { int32_t* idx; float* dist; int32_t* class_out = nullptr; const float* radius = nullptr; int32_t* count = nullptr; const int32_t* exclude = nullptr; };
+
+// ---- the nearest row of another class (fir_search_top1_other_class): the scan form -------------------------------------------
+// top1_dev's passes with the kEpiTop1Other epilogue: tiles of 8, 4, 2, 1 queries (the generic scan's; a 16-query tile exists only in
+// the hand-scheduled L2 kernel), all the whole tiles of one size in one launch. d_exclude[qb] is copied into the handle's scratch,
+// padded to whole tiles, once per call. Nothing synchronises once the scratch is large enough.
+int other_class_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const int32_t* d_exclude, uint64_t* d_keys,
+                    hipStream_t st) {
+    if (g->n == 0) {                                             // no row: FIR_KEY_NONE (all bytes 0xFF)
+        FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * sizeof(uint64_t), st));
+        return FIR_OK;
+    }
+    const int qpad = (qb + 15) / 16 * 16;
+    int rc;
+    if ((rc = FIR_NEED(g->qt, (size_t)qb * g->dp4 * 4 + 64)) || (rc = FIR_NEED(g->excl, (size_t)qpad))) return rc;
+    hipLaunchKernelGGL(k_pad_exclude, dim3((qpad + kBlock - 1) / kBlock), dim3(kBlock), 0, st, d_exclude, qb, (int32_t*)g->excl, qpad);
+    // chi-square / KL, automatic tuning: tiles of 4 -- the 8-query plain-range forms with this epilogue keep 249-328 vector registers in
+    // scratch inside the feature loop (the 4-query forms none), and those scans are bound by the vector pipes, not by gallery reads
+    const int cap = top1_qpp(g, {}, qb, std::min(effective_qpp(g), g->metric != kL2 && g->qpp == 0 ? 4 : 8));
+    int q0 = 0;
+    while (q0 < qb) {
+        const int t = largest_pow2_le(qb - q0, cap);
+        const int ny = std::min((qb - q0) / t, g->max_tiles_per_launch);
+        rc = run_pass(g, st, {}, kEpiTop1Other, d_queries, q0, t, start, end, d_keys + q0, nullptr, 0, 0, nullptr, ny, /*init_keys=*/t * ny, nullptr, 0,
+                      g->excl + q0);
+        if (rc) return rc;
+        q0 += t * ny;
+    }
+    return FIR_OK;
+}
+
+// The routed form of a host call's batch (and of the self-join's host calls): the nearest row of a class other than c is the best row
+// of the best class other than c, and that class is rank 1 or rank 2 among all classes -- the first of
+// fir_gemm_search_top_classes_keys_dev(k = 2)'s two entries whose class differs from c, FIR_KEY_NONE when neither does; the same key
+// bit for bit, keys being unique and ordered by (distance, row). Routed exactly where fir_search_top_classes would route a batch of
+// this size and range, and only when every label lies in [0, 16777216) (the class form's limit; num_classes = largest label + 1).
+// kAutoMfmaOtherClass: it routes by itself from kAutoMfmaQueries queries over kAutoMfmaRows rows on, as the class form does: whole
+// host-pointer calls of 128 / 1 024 / 8 192 queries at 100 000 x 512 and 1M x 512, 10 rows per class (profiles/other_class.txt): 3.8 / 7.7 /
+// 8.7 x and 5.5 / 7.7 / 7.9 x the scan form on class-major labels, 3.1 / 4.9 / 5.3 x and 4.8 / 6.6 / 6.7 x on permuted ones, the same
+// answers and no query left to the exact class scan -- every point far beyond the 15 % the automatic routes ask for. Smaller galleries
+// were not measured: they stay with the scan unless the caller sets a threshold.
+// 0 = queued, 1 = the scan form answers (nothing was queued), < 0 = error.
+constexpr bool kAutoMfmaOtherClass = true;
+int other_class_routed(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const int32_t* d_exclude, uint64_t* d_keys,
+                       hipStream_t st) {
+    if (!g->cls || (g->large_batch_min < 0 && !kAutoMfmaOtherClass) || !wants_mfma(g, qb, start, end, true)) return 1;
+    int32_t lo = 0, hi = -1;
+    int rc = fir_gallery_label_range_(g, &lo, &hi);
+    if (rc) return rc;
+    if (lo < 0 || hi >= kClassMax) return 1;
+    if ((rc = FIR_NEED(g->okeys, (size_t)2 * qb)) || (rc = FIR_NEED(g->ocls, (size_t)2 * qb))) return rc;
+    rc = try_mfma_search(g, d_queries, qb, start, end, FirSearch::distinct(hi + 1, 2, g->okeys, g->ocls), st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pick_other, dim3((qb + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const uint64_t*)g->okeys, (const int32_t*)g->ocls, d_exclude, qb, d_keys);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
 int search_host(fir_gallery* g, const float* queries, int32_t qb, int32_t start, int32_t end, FirSearch s, const HostOut& out) {
     GalleryCall call(g);
     if (call.rc) return call.rc;
     const size_t slots = s.key_words(qb);
     const bool classes = s.kind == kSearchClasses;
     int rc;
-    if ((rc = FIR_NEED(g->dkeys, s.status_index(qb) + s.radii_bytes(qb) / sizeof(uint64_t))) || (rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
+    const bool other = s.kind == kSearchOtherClass;
+    if ((rc = FIR_NEED(g->dkeys, s.status_index(qb) + (s.radii_bytes(qb) + s.exclude_bytes(qb)) / sizeof(uint64_t))) || (rc = FIR_NEED(g->dq, (size_t)qb * g->d))) return rc;
     if (classes && (rc = FIR_NEED(g->didx, slots))) return rc;
     uint64_t* base = g->dkeys;
     s.keys = slots ? base : nullptr;
@@ -2034,10 +2105,17 @@ int search_host(fir_gallery* g, const float* queries, int32_t qb, int32_t start,
         s.radius = (const float*)(base + s.status_index(qb));
         FIR_HIP(hipMemcpyAsync((void*)s.radius, out.radius, (size_t)qb * sizeof(float), hipMemcpyHostToDevice, g->stream));
     }
+    if (other) {                                                 // the excluded classes ride behind the keys as the radii do
+        s.exclude = (const int32_t*)(base + s.status_index(qb));
+        FIR_HIP(hipMemcpyAsync((void*)s.exclude, out.exclude, (size_t)qb * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    }
     g->call_launches = 0;
     g->warm_left = 0;
-    rc = try_mfma_search(g, g->dq, qb, start, end, s, g->stream);
-    if (rc > 0) rc = classes ? top_classes_dev(g, g->dq, qb, start, end, s.num_classes, s.k, s.keys, s.classes, g->stream) : knn_dev(g, g->dq, qb, start, end, s, g->stream);
+    rc = other ? other_class_routed(g, g->dq, qb, start, end, s.exclude, s.keys, g->stream) : try_mfma_search(g, g->dq, qb, start, end, s, g->stream);
+    if (rc > 0)
+        rc = classes ? top_classes_dev(g, g->dq, qb, start, end, s.num_classes, s.k, s.keys, s.classes, g->stream)
+             : other ? other_class_dev(g, g->dq, qb, start, end, s.exclude, s.keys, g->stream)
+                     : knn_dev(g, g->dq, qb, start, end, s, g->stream);
     if (rc) return rc;
     if (s.is_radius()) FIR_HIP(hipMemcpyAsync(out.count, s.count, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     return deliver_copied(g, call, slots, out.class_out, out.idx, out.dist);
@@ -2138,6 +2216,126 @@ int fir_search_top_classes(fir_gallery* g, const float* queries, int32_t qb, int
     int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k);
     if (rc) return rc < 0 ? rc : FIR_OK;
     return search_host(g, queries, qb, start_pos, end_pos, FirSearch::distinct(num_classes, k, nullptr, nullptr), {idx, dist, class_out});
+}
+
+// ---- the nearest row of another class, the gallery's self-join over it, the false-accept threshold (fir_amd.h) ----
+namespace {
+// check_search in fir_search_top_classes' order: NULL, qb < 0, the labels, the range, then qb == 0
+int check_other_class(const fir_gallery* g, const void* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, bool pointers_ok) {
+    return check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] {
+        if (!g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+        return check_range(g, start_pos, end_pos);
+    });
+}
+constexpr int64_t kSelfJoinBlock = 8192;      // gallery rows per self-join block: one call of the search with that many queries
+// Rows [row0, row0 + m) (m <= kSelfJoinBlock) as queries with their own classes excluded: un-tiled into g->selfq (the tiled f32 rows
+// are the one copy every gallery has), then the search -- routed where a host call's batch would be, when the caller is a host call.
+int self_join_block(fir_gallery* g, int64_t row0, int32_t m, int32_t start, int32_t end, uint64_t* d_keys, hipStream_t st, bool may_route) {
+    int rc = FIR_NEED(g->selfq, (size_t)m * g->d);
+    if (rc) return rc;
+    const int64_t chunks = (int64_t)m * g->dp4;
+    hipLaunchKernelGGL(k_untile_rows, dim3((unsigned)((chunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const float4*)g->gal4, g->dp4, g->d, row0, (int64_t)m,
+                       (float*)g->selfq);
+    FIR_HIP(hipGetLastError());
+    if (may_route) {
+        rc = other_class_routed(g, g->selfq, m, start, end, g->cls + row0, d_keys, st);
+        if (rc <= 0) return rc;
+    }
+    return other_class_dev(g, g->selfq, m, start, end, g->cls + row0, d_keys, st);
+}
+int check_self_join(const fir_gallery* g, int32_t& start_pos, int32_t& end_pos, bool pointers_ok) {
+    if (!g || !pointers_ok) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (!g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    return check_range(g, start_pos, end_pos);
+}
+}  // namespace
+
+int fir_search_top1_other_class_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                         const int32_t* d_exclude_class, uint64_t* d_keys, void* stream) {
+    const int rc = check_other_class(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr && (qb <= 0 || d_exclude_class != nullptr));
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    return other_class_dev(g, d_queries, qb, start_pos, end_pos, d_exclude_class, d_keys, call.st);
+}
+
+int fir_search_top1_other_class(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const int32_t* exclude_class,
+                                int32_t* idx, float* dist) {
+    const int rc = check_other_class(g, queries, qb, start_pos, end_pos, idx != nullptr && dist != nullptr && (qb <= 0 || exclude_class != nullptr));
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    HostOut out{idx, dist};
+    out.exclude = exclude_class;
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::other_class(nullptr, nullptr), out);
+}
+
+int fir_gallery_other_class_keys_dev(fir_gallery* g, int64_t row0, int64_t m, int32_t start_pos, int32_t end_pos, uint64_t* d_keys, void* stream) {
+    int rc = check_self_join(g, start_pos, end_pos, d_keys != nullptr);
+    if (rc) return rc;
+    if (row0 < 0 || m < 0 || row0 > g->n || m > g->n - row0) return fir_fail_(FIR_ERR_ARG, "rows [%lld,%lld) not inside [0,%lld)", (long long)row0, (long long)(row0 + m), (long long)g->n);
+    if (m == 0) return FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    for (int64_t r = 0; r < m; r += kSelfJoinBlock)
+        if ((rc = self_join_block(g, row0 + r, (int32_t)std::min(kSelfJoinBlock, m - r), start_pos, end_pos, d_keys + r, call.st, false))) return rc;
+    return FIR_OK;
+}
+
+int fir_gallery_other_class(fir_gallery* g, int32_t start_pos, int32_t end_pos, int32_t* idx, float* dist) {
+    int rc = check_self_join(g, start_pos, end_pos, idx != nullptr && dist != nullptr);
+    if (rc) return rc;
+    if (g->n == 0) return FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if ((rc = FIR_NEED(g->dkeys, (size_t)g->n))) return rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    for (int64_t r = 0; r < g->n; r += kSelfJoinBlock)
+        if ((rc = self_join_block(g, r, (int32_t)std::min(kSelfJoinBlock, g->n - r), start_pos, end_pos, g->dkeys + r, g->stream, true))) return rc;
+    return deliver_copied(g, call, (size_t)g->n, nullptr, idx, dist);
+}
+
+int fir_gallery_far_threshold(fir_gallery* g, int32_t start_pos, int32_t end_pos, float false_accept_rate, float* threshold, float* min_dist,
+                              float* max_dist, int64_t* rows_counted) {
+    int rc = check_self_join(g, start_pos, end_pos, threshold != nullptr);
+    if (rc) return rc;
+    if (!(false_accept_rate >= 0.0f)) return fir_fail_(FIR_ERR_ARG, "false_accept_rate=%g is negative or not a number", (double)false_accept_rate);
+    if (g->n == 0) return fir_fail_(FIR_ERR_STATE, "no row has a row of another class: nothing to place a threshold over");
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    // the statistic as one float row (a multiple of 4 long: k_knn_sample_kth reads float4), FarStats and the threshold behind it
+    const size_t n4 = ((size_t)g->n + 3) / 4 * 4;
+    static_assert(sizeof(FarStats) <= 8 * sizeof(float), "the threshold sits 8 floats behind FarStats");
+    if ((rc = FIR_NEED(g->fardist, n4 + 16)) || (rc = FIR_NEED(g->selfkeys, (size_t)kSelfJoinBlock))) return rc;
+    float* row = g->fardist;
+    FarStats* d_stats = (FarStats*)(row + n4);
+    float* d_bound = row + n4 + 8;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    for (int64_t r = 0; r < g->n; r += kSelfJoinBlock) {
+        const int32_t m = (int32_t)std::min(kSelfJoinBlock, g->n - r);
+        if ((rc = self_join_block(g, r, m, start_pos, end_pos, g->selfkeys, g->stream, true))) return rc;
+        hipLaunchKernelGGL(k_keys_to_dist, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, g->stream, (const uint64_t*)g->selfkeys, (int64_t)m, row + r);
+    }
+    hipLaunchKernelGGL(k_far_stats, dim3(1), dim3(kBlock), 0, g->stream, (const float*)row, g->n, false_accept_rate, d_stats);
+    hipLaunchKernelGGL(k_knn_sample_kth, dim3(1), dim3(kBlock), 0, g->stream, (const float*)row, (int64_t)n4, g->n, 1, d_bound, (const int32_t*)&d_stats->rank);
+    FIR_HIP(hipGetLastError());
+    struct { FarStats st; float pad[8 - sizeof(FarStats) / sizeof(float)]; float bound; } h;
+    FIR_HIP(hipMemcpyAsync(&h, d_stats, 9 * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));                    // the call's one synchronisation
+    call.done();
+    if (rows_counted) *rows_counted = h.st.count;
+    if (h.st.count == 0) return fir_fail_(FIR_ERR_STATE, "no row has a row of another class: nothing to place a threshold over");
+    if (min_dist) *min_dist = h.st.min_dist;
+    if (max_dist) *max_dist = h.st.max_dist;
+    if (!h.st.ind_ok)
+        return fir_fail_(FIR_ERR_ARG, "false_accept_rate=%g: index (int)(%lld * rate) is not below the %lld rows counted", (double)false_accept_rate,
+                         (long long)h.st.count, (long long)h.st.count);
+    *threshold = h.bound;
+    return FIR_OK;
 }
 
 int fir_class_keys_merge(const uint64_t* keys, const int32_t* classes, int32_t parts, int32_t qb, int32_t k, uint64_t* keys_out,

@@ -17,9 +17,11 @@ enum { kL2 = 0, kChi2 = 1, kKL = 2,
        kChi2Harm = 6,                        // kernel-internal: chi-square as sum(l) + sum(r) - 4 sum 1/(1/l + 1/r): the scan adds up the harmonic terms, NOMINATES only
        kKLEnt = 7 };                         // kernel-internal: KL as ln2 (sum(l log2 l + l) + sum(r log2 r + r) - sum (l + r) log2 (l + r)): the scan adds up the last sum, NOMINATES only
 enum { kEpiTop1 = 0, kEpiTopK = 1, kEpiStore = 2, kEpiAppend = 3,
-       kEpiClassMin = 5 };                   // (4 is how fir_capi.hip's kernel table files k_scan_subranges)
+       kEpiClassMin = 5,                     // (4 is how fir_capi.hip's kernel table files k_scan_subranges)
+       kEpiTop1Other = 6 };                  // top-1 over the rows whose label differs from the query's excluded class (fir_search_top1_other_class)
 
 typedef const float __attribute__((address_space(4)))* sfloat_p;  // constant AS => s_load when uniform
+typedef const int32_t __attribute__((address_space(4)))* sint_p;  // ... the same for integers (kEpiTop1Other's excluded classes)
 
 // float bits -> uint32 whose unsigned order equals the float order (negatives included).
 __host__ __device__ __forceinline__ uint32_t f32_orderable(float f) {

@@ -89,6 +89,7 @@ struct ScanArgs {
     int32_t run_len;      // k_scan, kEpiStore, > 0: the scan's `tiles` tiles are a row SAMPLE -- run_count runs of run_len consecutive tiles (the last
     int32_t run_count;    // one may be shorter), run i moved up by floor(i * run_slack / run_count) tiles: sample tile t is gallery tile
     int64_t run_slack;    // t + floor((t / run_len) * run_slack / run_count), stored at row 64 t + lane; n = rows of the sample (knn_sample_plan)
+    const int32_t* excl;  // kEpiTop1Other: excl[blockIdx.y * QB + q] = the class whose rows query q passes over (a copy padded to whole tiles); cls = the labels
 };
 
 template <int QB, int METRIC, int U>
@@ -233,6 +234,9 @@ struct TileAcc {
 
 // Streams whole tiles; lane r of a wave owns row 64 t + r. EPI selects what happens to the
 // finished distances: running first-minimum (top-1), running K smallest (top-K), or store.
+// kEpiTop1Other is the top-1 epilogue over the rows whose label differs from the query's excluded class: the tile's 64 labels are
+// asked for before the feature loop (one coalesced load, rows past n have none), the QB excluded classes come in like the query
+// values (scalar cache, or LDS behind the staged tile), and the end of the kernel is top-1's.
 // LDSQ = 1: the query tile is staged in (dynamic) LDS first -- dp4*4*QB floats -- and read from there; used for
 // one- and two-query tiles over galleries of few tiles, where a wave streams a whole tile alone and the per-chunk
 // scalar-load latency of the default form is what it waits for.
@@ -253,11 +257,15 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     // blockIdx.y = query tile (top-1, append and class-minimum forms): several tiles of QB queries share one launch
-    const float* qsrc = a.qt + (EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin || EPI == kEpiStore ? (size_t)blockIdx.y * a.qt_stride : 0);
+    constexpr bool kTop1Like = EPI == kEpiTop1 || EPI == kEpiTop1Other;
+    const float* qsrc = a.qt + (kTop1Like || EPI == kEpiAppend || EPI == kEpiClassMin || EPI == kEpiStore ? (size_t)blockIdx.y * a.qt_stride : 0);
     extern __shared__ __attribute__((aligned(16))) float lds_q[];
     if constexpr (LDSQ) {
         const int nf = a.dp4 * 4 * QB;
         for (int i = threadIdx.x; i < nf; i += kBlock) lds_q[i] = qsrc[i];
+        if constexpr (EPI == kEpiTop1Other) {      // the excluded classes behind the tile (QB more words of dynamic LDS)
+            if (threadIdx.x < QB) reinterpret_cast<int32_t*>(lds_q)[nf + threadIdx.x] = a.excl[(size_t)blockIdx.y * QB + threadIdx.x];
+        }
         __syncthreads();
     }
     typedef typename std::conditional<LDSQ != 0, const float*, sfloat_p>::type QP;
@@ -269,11 +277,13 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
     const int c_hi = a.end >> 2;                  // one past the last whole chunk
     const float fcount = (float)(a.end - a.start);  // db_features.cpp:40 divides by (end_pos-start_pos)
 
-    float best_d[EPI == kEpiTop1 || EPI == kEpiAppend || EPI == kEpiClassMin ? QB : 1];      // kEpiAppend, kEpiClassMin: the thresholds tau
-    int32_t best_i[EPI == kEpiTop1 ? QB : 1];
+    float best_d[kTop1Like || EPI == kEpiAppend || EPI == kEpiClassMin ? QB : 1];      // kEpiAppend, kEpiClassMin: the thresholds tau
+    int32_t best_i[kTop1Like ? QB : 1];
+    // kEpiTop1Other: the tile's excluded classes -- uniform address, constant AS: s_load (LDSQ: behind the staged tile)
+    const sint_p excl_c = (sint_p)(uintptr_t)(EPI == kEpiTop1Other && !LDSQ ? a.excl + (size_t)blockIdx.y * QB : nullptr);
     float kd[EPI == kEpiTopK ? QB : 1][EPI == kEpiTopK ? KMAX : 1];
     int32_t ki[EPI == kEpiTopK ? QB : 1][EPI == kEpiTopK ? KMAX : 1];
-    if constexpr (EPI == kEpiTop1) {
+    if constexpr (kTop1Like) {
 #pragma unroll
         for (int q = 0; q < QB; ++q) { best_d[q] = kNotFound; best_i[q] = -1; }
     }
@@ -301,6 +311,12 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
             if (a.run_len > 0) gt += (int64_t)(t / a.run_len) * a.run_slack / a.run_count;
         }
         const float4* tile = a.gal4 + (size_t)gt * a.dp4 * 64 + lane;
+        int32_t lab_other = 0;
+        if constexpr (EPI == kEpiTop1Other) {
+            // asked for ahead of the tile's features: the epilogue finds it there. The last tile's padding rows have no label.
+            const int64_t lrow = (int64_t)t * kTileRows + lane;
+            if (lrow < a.n) lab_other = a.cls[lrow];
+        }
         float acc[QB];
 #pragma unroll
         for (int q = 0; q < QB; ++q) acc[q] = 0.0f;
@@ -368,6 +384,20 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                 }
             }
         } else if (row < a.n) {
+            int32_t excl[EPI == kEpiTop1Other ? QB : 1];
+            if constexpr (EPI == kEpiTop1Other) {
+                // fetched here, once per tile, like the query values of a chunk: held across the feature loop they would cost QB scalar
+                // registers the plain-range forms do not have (the opaque copy of the pointer keeps the loads from being hoisted)
+                if constexpr (LDSQ) {
+#pragma unroll
+                    for (int q = 0; q < QB; ++q) excl[q] = reinterpret_cast<const int32_t*>(lds_q)[a.dp4 * 4 * QB + q];
+                } else {
+                    sint_p ec = excl_c;
+                    asm volatile("" : "+s"(ec));
+#pragma unroll
+                    for (int q = 0; q < QB; ++q) excl[q] = ec[q];
+                }
+            }
 #pragma unroll
             for (int q = 0; q < QB; ++q) {
                 float dist = acc[q] / fcount;                            // db_features.cpp:40
@@ -375,6 +405,8 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                 if constexpr (METRIC == kKLEnt) dist = (0.693147181f * ((a.sq[(size_t)blockIdx.y * QB + q] + a.sg[row]) - acc[q])) / fcount;
                 if constexpr (EPI == kEpiTop1) {
                     if (dist < best_d[q]) { best_d[q] = dist; best_i[q] = (int32_t)row; }   // db_features.cpp:329-332
+                } else if constexpr (EPI == kEpiTop1Other) {
+                    if (lab_other != excl[q] && dist < best_d[q]) { best_d[q] = dist; best_i[q] = (int32_t)row; }   // ... over the other classes' rows
                 } else if constexpr (EPI == kEpiTopK) {
                     if (dist < kd[q][KMAX - 1]) {
                         // insert keeping ascending order; strict '<' keeps earlier rows first on ties
@@ -401,7 +433,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
         }
     }
 
-    if constexpr (EPI == kEpiTop1) {
+    if constexpr (kTop1Like) {
         uint64_t* keys = a.keys + (size_t)blockIdx.y * QB + (a.groups > 1 ? (size_t)(gw % a.groups) * a.group_stride : 0);
 #pragma unroll
         for (int q = 0; q < QB; ++q) {
@@ -413,7 +445,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                 if (key < cur) atomicMin((unsigned long long*)(keys + q), (unsigned long long)key);
             }
         }
-        if (a.publish) {
+        if (EPI == kEpiTop1 && a.publish) {
             __shared__ int last_block;
             __threadfence();                                   // this workgroup's minima are out before it is counted
             __syncthreads();
@@ -1271,6 +1303,74 @@ __global__ void __launch_bounds__(kBlock) k_classes_of(const int32_t* __restrict
     if (i >= m) return;
     const int64_t l = (int64_t)idx[i] - row_offset;
     out[i] = (idx[i] >= 0 && l >= 0 && l < n) ? cls[l] : -1;
+}
+
+// ---- the nearest row of another class (fir_search_top1_other_class) and the gallery's self-join over it ----
+// The caller's qb excluded classes, padded to qpad entries (whole query tiles of any size): k_scan reads excl[tile * QB + q].
+__global__ void __launch_bounds__(kBlock) k_pad_exclude(const int32_t* __restrict__ src, int qb, int32_t* __restrict__ dst, int qpad) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < qpad) dst[i] = i < qb ? src[i] : 0;
+}
+// Rows [row0, row0 + m) of the tiled gallery back into row-major out[m][d]: the self-join's queries. One thread per float4 chunk,
+// consecutive threads = consecutive rows of one chunk (the tiled side is the coalesced one).
+__global__ void __launch_bounds__(kBlock) k_untile_rows(const float4* __restrict__ gal4, int dp4, int d, int64_t row0, int64_t m, float* __restrict__ out) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= m * dp4) return;
+    const int64_t i = o % m;                      // row of the block
+    const int c = (int)(o / m);
+    const int64_t row = row0 + i;
+    const float4 g = gal4[((size_t)(row >> 6) * dp4 + c) * 64 + (row & 63)];
+    const float gv[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c * 4 + j < d) out[i * d + c * 4 + j] = gv[j];
+}
+// The routed form: keys2 / cls2 [qb][2] = the two nearest distinct classes of each query (ascending keys); the nearest row of a
+// class other than excl[q] is the best row of the best class other than it, which is rank 1 or rank 2: the first of the two
+// entries whose class differs, FIR_KEY_NONE when neither does (an unused slot is FIR_KEY_NONE already).
+__global__ void __launch_bounds__(kBlock) k_pick_other(const uint64_t* __restrict__ keys2, const int32_t* __restrict__ cls2, const int32_t* __restrict__ excl,
+                                                        int qb, uint64_t* __restrict__ out) {
+    const int q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= qb) return;
+    const uint64_t k0 = keys2[2 * q], k1 = keys2[2 * q + 1];
+    out[q] = (k0 != kKeyNone && cls2[2 * q] != excl[q]) ? k0 : (k1 != kKeyNone && cls2[2 * q + 1] != excl[q]) ? k1 : kKeyNone;
+}
+// dist[i] = the distance of keys[i], 100000 for FIR_KEY_NONE: the float row k_knn_sample_kth and k_far_stats read
+__global__ void __launch_bounds__(kBlock) k_keys_to_dist(const uint64_t* __restrict__ keys, int64_t m, float* __restrict__ dist) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < m) dist[i] = keys[i] == kKeyNone ? kNotFound : f32_from_orderable((uint32_t)(keys[i] >> 32));
+}
+// getThreshold's other numbers (ann.cpp:84-93) over dist[0, n): the entries below 100000 counted, their smallest and largest, and
+// rank = ind + 1 with ind = (int)((float)count * rate) -- a float product, as the reference multiplies size_t by float -- for the
+// select that follows on the stream (1 when ind is outside [0, count): the host reports that). One workgroup.
+struct FarStats { int64_t count; float min_dist, max_dist; int32_t rank; int32_t ind_ok; };
+__global__ void __launch_bounds__(kBlock) k_far_stats(const float* __restrict__ dist, int64_t n, float rate, FarStats* __restrict__ out) {
+    __shared__ long long s_cnt[kBlock / 64];
+    __shared__ float s_lo[kBlock / 64], s_hi[kBlock / 64];
+    long long cnt = 0;
+    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+        const float v = dist[i];
+        if (v < kNotFound) { ++cnt; lo = fminf(lo, v); hi = fmaxf(hi, v); }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, 64);
+        lo = fminf(lo, __shfl_xor(lo, off, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < kBlock / 64; ++i) { cnt += s_cnt[i]; lo = fminf(lo, s_lo[i]); hi = fmaxf(hi, s_hi[i]); }
+        const float pos = (float)(unsigned long long)cnt * rate;
+        const bool ok = pos >= 0.0f && pos < 2147483648.0f && (long long)(int)pos < cnt;      // (a NaN rate fails the first compare)
+        out->count = cnt;
+        out->min_dist = lo;
+        out->max_dist = hi;
+        out->rank = ok ? (int)pos + 1 : 1;
+        out->ind_ok = ok ? 1 : 0;
+    }
 }
 
 }  // namespace fir

@@ -176,12 +176,14 @@ __device__ inline SelState sel_advance(SelState s, unsigned count, int pass, uns
 // distance is wanted, not the row: four digits over the 32-bit orderable distance. A digit whose bin the rank takes whole does not
 // end the select (sel_advance's `done` fills the lower digits with ones: a key at or above the K-th, not the K-th itself).
 // stride is a multiple of 4 and dist 16-byte aligned.
+// k_dev != NULL: the rank is read from the device, k_dev[0] (fir_gallery_far_threshold: it depends on a count made on the stream before).
 static __global__ void __launch_bounds__(kBlock) k_knn_sample_kth(const float* __restrict__ dist, int64_t stride, int64_t rows, int32_t k,
-                                                                   float* __restrict__ bound) {
+                                                                   float* __restrict__ bound, const int32_t* __restrict__ k_dev = nullptr) {
     __shared__ unsigned hist[256];
     __shared__ unsigned wsum[kBlock / 64];
     __shared__ SelState box;
     const int q = blockIdx.x;
+    if (k_dev) k = k_dev[0];                                             // (uniform)
     if (rows < k) {                                                      // (uniform) a rank outside the histogram
         if (threadIdx.x == 0) bound[q] = kNotFound;
         return;

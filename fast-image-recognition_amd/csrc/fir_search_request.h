@@ -11,7 +11,10 @@ enum SearchKind : int {
     kSearchSelect,      // the K nearest rows, select form (fir_search_knn): 1 <= k <= FIR_KNN_MAX, matrix cores up to FIR_GEMM_KNN_MAX
     kSearchRadius,      // every row within radius[q]: k = max_results, 0 <= k <= FIR_KNN_MAX (0: counts only), count[q] out
     kSearchClasses,     // the K nearest distinct classes: 1 <= k <= 32 of num_classes; keys and / or classes out
-    kSearchKinds
+    kSearchKinds,       // the kinds above: the ones fir_gemm.hip answers itself (kGemmKinds has a row for each)
+    // the nearest row of a class other than exclude[q] (fir_search_top1_other_class): k = 1. No matrix-core row of its own: a routed batch is
+    // kSearchClasses with k = 2 and a pick (fir_capi.hip: other_class_routed)
+    kSearchOtherClass = kSearchKinds
 };
 struct FirSearch {
     SearchKind kind;
@@ -21,10 +24,12 @@ struct FirSearch {
     int32_t* classes;           // kSearchClasses: [qb * k]; may be NULL when keys is not
     const float* radius;        // kSearchRadius: [qb]
     int32_t* count;             // kSearchRadius: [qb] <- the rows inside, however many
-    static FirSearch rows(int32_t k, uint64_t* keys) { return {kSearchRows, k, 0, keys, nullptr, nullptr, nullptr}; }
-    static FirSearch select(int32_t k, uint64_t* keys) { return {kSearchSelect, k, 0, keys, nullptr, nullptr, nullptr}; }
-    static FirSearch within(const float* radius, int32_t max_results, int32_t* count, uint64_t* keys) { return {kSearchRadius, max_results, 0, keys, nullptr, radius, count}; }
-    static FirSearch distinct(int32_t num_classes, int32_t k, uint64_t* keys, int32_t* classes) { return {kSearchClasses, k, num_classes, keys, classes, nullptr, nullptr}; }
+    const int32_t* exclude;     // kSearchOtherClass: [qb], the class each query passes over
+    static FirSearch rows(int32_t k, uint64_t* keys) { return {kSearchRows, k, 0, keys, nullptr, nullptr, nullptr, nullptr}; }
+    static FirSearch select(int32_t k, uint64_t* keys) { return {kSearchSelect, k, 0, keys, nullptr, nullptr, nullptr, nullptr}; }
+    static FirSearch within(const float* radius, int32_t max_results, int32_t* count, uint64_t* keys) { return {kSearchRadius, max_results, 0, keys, nullptr, radius, count, nullptr}; }
+    static FirSearch distinct(int32_t num_classes, int32_t k, uint64_t* keys, int32_t* classes) { return {kSearchClasses, k, num_classes, keys, classes, nullptr, nullptr, nullptr}; }
+    static FirSearch other_class(const int32_t* exclude, uint64_t* keys) { return {kSearchOtherClass, 1, 0, keys, nullptr, nullptr, nullptr, exclude}; }
     bool is_radius() const { return kind == kSearchRadius; }
     // which outputs may be NULL: keys only where the kind has another output (the counts alone for k = 0; the classes)
     bool outputs_ok() const { return is_radius() ? count && (k == 0 ? !keys : keys != nullptr) : keys || (kind == kSearchClasses && classes); }
@@ -34,9 +39,12 @@ struct FirSearch {
     size_t status_index(int32_t qb) const { return key_words(qb) + count_words(qb); }
     // the radii riding behind a batch of queries, in whole 8 bytes
     size_t radii_bytes(int32_t qb) const { return is_radius() ? ((size_t)qb + (qb & 1)) * sizeof(float) : 0; }
+    // ... and the excluded classes, the same way
+    size_t exclude_bytes(int32_t qb) const { return kind == kSearchOtherClass ? ((size_t)qb + (qb & 1)) * sizeof(int32_t) : 0; }
     // the same request for queries [q0, ...): every pointer it has, advanced by its stride
     FirSearch at(int32_t q0) const {
-        return {kind, k, num_classes, keys ? keys + (size_t)q0 * k : nullptr, classes ? classes + (size_t)q0 * k : nullptr, radius ? radius + q0 : nullptr, count ? count + q0 : nullptr};
+        return {kind, k, num_classes, keys ? keys + (size_t)q0 * k : nullptr, classes ? classes + (size_t)q0 * k : nullptr, radius ? radius + q0 : nullptr, count ? count + q0 : nullptr,
+                exclude ? exclude + q0 : nullptr};
     }
 };
 }  // namespace fir

@@ -377,7 +377,7 @@ int check_range(const fir_sharded* h, int32_t& start, int32_t& end) {
 struct CallBuffers { size_t dq, parts, keys, gath, cls, sel; };
 CallBuffers call_buffers(const fir_sharded* h, int32_t qb, const FirSearch& s, bool host_queries, bool winners_classes) {
     const size_t u64 = sizeof(uint64_t), payload = s.status_index(qb);
-    return {host_queries ? (size_t)qb * h->d * sizeof(float) + s.radii_bytes(qb) : 0, payload * (size_t)h->spd * u64, (payload + 1) * u64,
+    return {host_queries ? (size_t)qb * h->d * sizeof(float) + s.radii_bytes(qb) + s.exclude_bytes(qb) : 0, payload * (size_t)h->spd * u64, (payload + 1) * u64,
             s.k != 1 || s.is_radius() ? (payload + 1) * (size_t)h->nranks * u64 : 0, winners_classes ? ((size_t)qb + 1) * sizeof(int32_t) : 0,
             s.k > kMergeListMax ? (sizeof(KnnCtl) + 7) / 8 * u64 : 0};
 }
@@ -437,6 +437,7 @@ int merge_keys(DevCtx& dc, const uint64_t* parts, int nparts, int32_t qb, int32_
 // The keys of one device: every shard it holds scans the batch (s.k keys per query, each kind through its gallery call; K = 1:
 // top-1), then the merge over those shards lands in dc.keys[0, qb * k). Buffers exist (call_alloc). s.radius (device memory): the
 // radius call -- every shard's fir_search_radius_keys_dev with global rows, the sum of their counts in the words behind the keys.
+// s.exclude (device memory): the other-class call -- every shard's fir_search_top1_other_class_keys_dev, one key per query like top-1.
 int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, int32_t start, int32_t end, const FirSearch& s, hipStream_t st) {
     DevCtx& dc = h->devs[slot];
     uint64_t *parts = dc.parts.as<uint64_t>(), *keys = dc.keys.as<uint64_t>();
@@ -451,6 +452,7 @@ int device_keys(fir_sharded* h, int slot, const float* d_queries, int32_t qb, in
         if (!sh.g) continue;
         uint64_t* out = parts + (size_t)live * per;
         rc = s.is_radius() ? fir_search_radius_keys_dev(sh.g, d_queries, qb, start, end, s.radius, s.k, cparts + (size_t)live * qb, s.k ? out : nullptr, st)
+             : s.kind == fir::kSearchOtherClass ? fir_search_top1_other_class_keys_dev(sh.g, d_queries, qb, start, end, s.exclude, out, st)
              : s.k == 1 ? fir_search_top1_keys_dev(sh.g, d_queries, qb, start, end, out, st)
              : s.kind == fir::kSearchSelect ? fir_search_knn_keys_dev(sh.g, d_queries, qb, start, end, s.k, out, st)
                                             : fir_search_topk_keys_dev(sh.g, d_queries, qb, start, end, s.k, out, st);
@@ -545,23 +547,23 @@ int dead_handle(const Health& hl) {
 // Host-pointer search: queries go to every device from pinned memory, keys (and classes: class_out, fir_sharded_classify_top1) come back from device slot 0. hs: the
 // host-side twin of the request -- kind, K, radius[qb] in and count[qb] out in HOST memory, no keys: they come back unpacked into idx / dist; each device gets its own `dev`.
 int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start, int32_t end, const FirSearch& hs, int32_t* idx, float* dist, int32_t* class_out) {
-    const bool rad = hs.is_radius(), knn = hs.kind == fir::kSearchSelect;
+    const bool rad = hs.is_radius(), knn = hs.kind == fir::kSearchSelect, other = hs.kind == fir::kSearchOtherClass;
     const int32_t k = hs.k;
-    if (!h || (qb > 0 && !queries) || (knn && (!idx || !dist))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (!h || (qb > 0 && !queries) || ((knn || other) && (!idx || !dist)) || (other && qb > 0 && !hs.exclude)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (rad && (!hs.count || (qb > 0 && !hs.radius) || (k >= 1 && k <= FIR_KNN_MAX && (!idx || !dist)) || (k == 0 && (idx || dist)))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     const int kmax = knn || rad ? FIR_KNN_MAX : 8;
     if (rad && (k < 0 || k > kmax)) return fir_fail_(FIR_ERR_ARG, "max_results=%d outside [0,%d]", k, kmax);
     if (!rad && (k < 1 || k > kmax)) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", k, kmax);
     if ((int64_t)qb * k >= ((int64_t)1 << 31)) return fir_fail_(FIR_ERR_ARG, "qb * k = %lld keys do not fit 32-bit counts", (long long)qb * k);
-    if (class_out && !h->has_labels) return fir_fail_(FIR_ERR_STATE, "the sharded gallery was created without class labels");
+    if ((class_out || other) && !h->has_labels) return fir_fail_(FIR_ERR_STATE, "the sharded gallery was created without class labels");
     if (h->health.dead) return dead_handle(h->health);
     if (qb == 0) return FIR_OK;
     int rc = check_range(h, start, end);
     if (rc) return rc;
     // (argument errors above are the same on every rank: nobody has entered a collective yet)
     const size_t per = hs.key_words(qb), payload = hs.status_index(qb);
-    const size_t rbytes = hs.radii_bytes(qb);                                          // the radii ride behind the queries, in whole 8 bytes
+    const size_t rbytes = hs.radii_bytes(qb) + hs.exclude_bytes(qb);                   // the radii (the excluded classes) ride behind the queries, in whole 8 bytes
     const size_t qbytes = (size_t)qb * h->d * sizeof(float) + rbytes, kbytes = (payload + 1) * sizeof(uint64_t), cbytes = ((size_t)qb + 1) * sizeof(int32_t);
     // the pinned staging area is part of the agreed growth as well: slot 0 tries it inside the step
     float* hq = nullptr;
@@ -590,6 +592,10 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
                     std::memset(hq + (size_t)qb * h->d, 0, rbytes);
                     std::memcpy(hq + (size_t)qb * h->d, hs.radius, (size_t)qb * sizeof(float));
                 }
+                if (other) {
+                    std::memset(hq + (size_t)qb * h->d, 0, rbytes);
+                    std::memcpy(hq + (size_t)qb * h->d, hs.exclude, (size_t)qb * sizeof(int32_t));
+                }
             }
             staged.publish(r);
         } else {
@@ -597,7 +603,8 @@ int search_host(fir_sharded* h, const float* queries, int32_t qb, int32_t start,
             if (!r) r = r0;                        // (an agreed failure has r != 0 everywhere already)
         }
         if (r) return r;
-        const FirSearch dev{hs.kind, k, 0, nullptr, nullptr, rad ? dc.dq.as<float>() + (size_t)qb * h->d : nullptr, nullptr};   // no host pointer; its radii lie behind its queries
+        const FirSearch dev{hs.kind, k, 0, nullptr, nullptr, rad ? dc.dq.as<float>() + (size_t)qb * h->d : nullptr, nullptr,
+                            other ? (const int32_t*)(dc.dq.as<float>() + (size_t)qb * h->d) : nullptr};   // no host pointer; its radii (excluded classes) lie behind its queries
         // from here on every rank takes part in every collective of the call, whatever happens to it
         keep_local(c, hipMemcpyAsync(dc.dq.p, hq, qbytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess
                           ? fir_fail_(FIR_ERR_HIP, "query upload failed")
@@ -1173,6 +1180,11 @@ int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, in
 int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k, int32_t* idx,
                            float* dist) {
     return search_host(h, queries, qb, start_pos, end_pos, FirSearch::select(k, nullptr), idx, dist, nullptr);
+}
+
+int fir_sharded_search_top1_other_class(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const int32_t* exclude_class,
+                                        int32_t* idx, float* dist) {
+    return search_host(h, queries, qb, start_pos, end_pos, FirSearch::other_class(exclude_class, nullptr), idx, dist, nullptr);
 }
 
 int fir_sharded_search_radius(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const float* radius,

@@ -33,6 +33,34 @@ std::vector<float> pack_queries(const std::vector<ImageInfo>& tests, int dim) {
     return q;
 }
 }  // namespace
+
+int other_class_distances(const std::vector<ImageInfo>& dbImages, std::vector<float>& dists) {
+    dists.clear();
+    if (dbImages.empty()) return 0;
+    fir_gallery* g = GalleryCache::get(dbImages, (int)dbImages[0].features.size());
+    if (!g) return -1;
+    std::vector<int32_t> idx(dbImages.size());
+    std::vector<float> all(dbImages.size());
+    if (fir_gallery_other_class(g, 0, 0, idx.data(), all.data()) != FIR_OK) {
+        log_error("other_class_distances");
+        return -1;
+    }
+    for (size_t i = 0; i < all.size(); ++i)
+        if (idx[i] >= 0) dists.push_back(all[i]);                      // ann.cpp:292-297: nothing is pushed for an image without one
+    return (int)dists.size();
+}
+
+float far_threshold(const std::vector<ImageInfo>& dbImages, float falseAcceptRate) {
+    if (dbImages.empty()) return 0;
+    fir_gallery* g = GalleryCache::get(dbImages, (int)dbImages[0].features.size());
+    float threshold = 0, lo = 0, hi = 0;
+    if (!g || fir_gallery_far_threshold(g, 0, 0, falseAcceptRate, &threshold, &lo, &hi, nullptr) != FIR_OK) {
+        log_error("far_threshold");
+        return 0;
+    }
+    std::cout << threshold << " " << lo << " " << hi << std::endl;      // ann.cpp:89-90
+    return threshold;
+}
 }  // namespace fir
 
 std::vector<int> ConventionalTWDClassifier::recognize_batch(const std::vector<ImageInfo>& tests) {

@@ -159,6 +159,17 @@ protected:
     }
 };
 
+// ---- ann.cpp:286-298 and :84-93 for a whole gallery, on the device ----
+namespace fir {
+// otherClassesDists of the reference's full (non-PIVOT) build: for every image of dbImages that has an image of another class, in
+// dbImages order, the distance to the nearest one over all of its features (fir_gallery_other_class: image i is the query). Returns
+// the number of entries, -1 on error (logged).
+int other_class_distances(const std::vector<ImageInfo>& dbImages, std::vector<float>& dists);
+// getThreshold over that statistic without bringing it to the host (fir_gallery_far_threshold); prints the three numbers the
+// reference prints. 0 on error (logged): DirectedEnumeration's "no threshold".
+float far_threshold(const std::vector<ImageInfo>& dbImages, float falseAcceptRate);
+}  // namespace fir
+
 // ---- ann.h:42-47, ann.cpp:113-126: exhaustive nearest neighbour over all FEATURES_COUNT features ----
 class BruteForce : public ClassificationMethod {
 public:

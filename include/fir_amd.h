@@ -247,6 +247,64 @@ int fir_search_radius(fir_gallery* g, const float* queries, int32_t qb, int32_t 
 int fir_search_radius_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
                                const float* d_radius, int32_t max_results, int32_t* d_count, uint64_t* d_keys, void* stream);
 
+/* ---- the nearest row of another class -------------------------------------------------------------
+ * The primitive behind the reference's false-accept threshold (otherClassesDists, ann.cpp:286-298: for every gallery row the
+ * distance to the nearest row of another class), leave-own-class-out evaluation, impostor mining and the "best row of another
+ * class" ConventionalTWDClassifier keeps next to its best row (ImageTesting.cpp:123-131).
+ * Per query q, over features [start_pos, end_pos) (end_pos = 0: d), any metric: a row qualifies iff `class_no[row] !=
+ * exclude_class[q]` (a plain int32 compare: any value is a legal label or exclusion, negatives, INT32_MIN and INT32_MAX included)
+ * and `dist < 100000.0f` is true (so NaN distances never qualify). The answer is the smallest packed key (orderable(distance
+ * bits) << 32) | uint32(row + row offset) among the qualifying rows -- the first-minimum rule of db_features.cpp:329-332 over those
+ * rows --, FIR_KEY_NONE (idx -1, dist 100000) when there is none. An exclude_class[q] no row carries gives fir_search_top1_keys_dev's
+ * key bit for bit; the distance bits are the exact scan's (fir_range_distances'). The gallery needs class labels (else
+ * FIR_ERR_STATE). idx, dist and exclude_class are [qb], all required. Arguments are checked in fir_search_top_classes' order (NULL,
+ * qb < 0, the labels, the range, qb == 0: nothing to do) before anything is allocated or queued.
+ * Form: one exact gallery scan per tile of up to 8 queries -- the generic top-1 scan with one more compare per (row, query): the
+ * tile's 64 labels come in one coalesced load ahead of the features, the tile's excluded classes through the scalar cache from a
+ * copy padded to whole tiles in the handle's scratch. fir_gallery_last_dispatch describes it (k_scan<..., 6, ...>).
+ * Matrix-core form (no pass of its own): the nearest row of a class other than c is the best row of the best class other than c,
+ * which is rank 1 or 2 among all classes -- the first of fir_gemm_search_top_classes_keys_dev(k = 2)'s two entries whose class
+ * differs from c, the same key bit for bit. fir_search_top1_other_class (the host-pointer call) and the host calls of the
+ * self-join below send a batch that way where fir_search_top_classes would route a batch of that size and range, when every label
+ * of the gallery lies in [0, 16777216) (found once by a reduction over the labels; num_classes = largest label + 1): by default
+ * from 128 queries against 65536 rows on, with fir_gallery_set_large_batch_mfma(g, min_queries > 0) from the caller's threshold on
+ * at any gallery size, never after fir_gallery_set_large_batch_mfma(g, 0) or with FIR_SHADOW_NONE. The default rests on whole
+ * host-pointer calls of 128 / 1 024 / 8 192 queries, 10 rows per class (profiles/other_class.txt, tools/other_class_probe.py): at
+ * 100 000 x 512 the routed form is 3.8 / 7.7 / 8.7 x the scan form on class-major labels and 3.1 / 4.9 / 5.3 x on permuted ones, at
+ * 1M x 512 5.5 / 7.7 / 7.9 x and 4.8 / 6.6 / 6.7 x, the same answers, no query left to the exact class scan -- every point beyond the
+ * 1.15 x an automatic route needs. Such a call synchronises the handle's stream and costs the fp16 gallery copy (n*d*2 bytes,
+ * created on first use). fir_gallery_last_dispatch describes a routed call as it does a routed class call. The *_dev call always
+ * takes the scan form; against the exact top-1 scan of the same batch (8 queries per pass) that form takes 1.00 - 1.02 x the time
+ * at 1M x 512, where both wait for HBM, and 1.15 - 1.41 x at 100 000 x 512, where the rows sit in the caches and the top-1 call
+ * runs the hand-scheduled packed kernel, which has no form with this epilogue; over features [1, 512), where the top-1 call runs
+ * the generic scan too, 0.98 - 1.06 x (same file). */
+int fir_search_top1_other_class(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                const int32_t* exclude_class /* [qb] */, int32_t* idx, float* dist);
+/* Device-resident, asynchronous on `stream` (NULL: the handle's own), in the handle's call order like every *_dev call; never
+ * synchronises once its scratch is large enough. d_exclude_class[qb], d_keys[qb]. */
+int fir_search_top1_other_class_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                         const int32_t* d_exclude_class, uint64_t* d_keys, void* stream);
+/* The gallery against itself: d_keys[i] = the key of row row0 + i searched with ITSELF as the query and its own class excluded,
+ * i < m (so the row itself never answers); rows are taken in blocks of up to 8 192 from the tiled copy, no other copy of the
+ * gallery is needed. Argument order: this is feature_distance(row i, row j) -- row i is the query --, the reference's table entry
+ * is distance(dbImages[j], i) = feature_distance(row j, row i): the same bits for L2 and chi-square ((a-b)^2 = (b-a)^2, a+b
+ * commutes); for KL the two terms of a feature are added in the other order, and the contract here is "row i is the query".
+ * FIR_ERR_ARG unless 0 <= row0, 0 <= m, row0 + m <= n; FIR_ERR_STATE without labels. Asynchronous on `stream`, scan form. */
+int fir_gallery_other_class_keys_dev(fir_gallery* g, int64_t row0, int64_t m, int32_t start_pos, int32_t end_pos,
+                                     uint64_t* d_keys /* [m] */, void* stream);
+/* ... of every row, unpacked: idx / dist [n], both required (-1 / 100000 for a row with no row of another class). */
+int fir_gallery_other_class(fir_gallery* g, int32_t start_pos, int32_t end_pos, int32_t* idx /* [n] */, float* dist /* [n] */);
+/* getThreshold (ann.cpp:84-93) over that statistic (ann.cpp:286-298), on the device: rows_counted = the rows that have a row of
+ * another class (the reference's build pushes nothing for the others); ind = (int)((float)rows_counted * false_accept_rate), a
+ * float product as the reference's size_t * float; threshold = the (ind + 1)-th smallest of the rows_counted distances; min_dist /
+ * max_dist = the two other numbers the reference prints. min_dist, max_dist and rows_counted may be NULL. FIR_ERR_ARG: a NaN or
+ * negative rate, or ind >= rows_counted (a rate of 1.0 indexes past the end in the reference); FIR_ERR_STATE: rows_counted == 0, or
+ * no labels. One host synchronisation, at the end (scan form; a routed block synchronises by itself). Whole calls at rate 0.01
+ * (profiles/other_class.txt): 100 000 x 512 0.81 s in the scan form and 0.09 s routed; 1M x 512 5.0 s routed -- the scan form is one
+ * exact scan per 8 rows of the gallery, about n / 26 000 s there, and was not run. */
+int fir_gallery_far_threshold(fir_gallery* g, int32_t start_pos, int32_t end_pos, float false_accept_rate,
+                              float* threshold, float* min_dist, float* max_dist, int64_t* rows_counted);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
@@ -684,6 +742,12 @@ int fir_sharded_search_topk(fir_sharded* h, const float* queries, int32_t qb, in
  * are the unsharded handle's. Failure semantics, agreed buffer growth and the status element as for the other searches. */
 int fir_sharded_search_knn(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, int32_t k,
                            int32_t* idx, float* dist);
+/* fir_search_top1_other_class over the shards, idx, dist and exclude_class required: every shard runs
+ * fir_search_top1_other_class_keys_dev with global rows (the excluded classes ride behind the queries), and the exchange is top-1's
+ * ncclMin over the packed keys. The keys are the unsharded handle's. FIR_ERR_STATE without labels. Failure semantics, agreed buffer
+ * growth and the status element as for the other searches. The self-join over the shards is not provided. */
+int fir_sharded_search_top1_other_class(fir_sharded* h, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                        const int32_t* exclude_class /* [qb] */, int32_t* idx, float* dist);
 /* fir_search_radius over the shards (the rows inside DirectedEnumeration's threshold, ann.cpp:390-400, of the whole gallery),
  * 0 <= max_results <= FIR_KNN_MAX, arguments as there: every shard runs fir_search_radius_keys_dev with global rows; its counts
  * travel behind its keys in the same ncclAllGather, in front of the status element, and are summed on the device; the keys merge
