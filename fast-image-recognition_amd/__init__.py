@@ -32,4 +32,5 @@ from .capi import (  # noqa: F401
     keys_unpack,
     lib,
     lib_path,
+    remove_plan,
 )

@@ -42,6 +42,14 @@ SYMBOLS = [
     ("fir_gallery_info", C.c_int, [_vp, _i64p, _i32p, _i32p, _i32p]),
     ("fir_gallery_set_metric", C.c_int, [_vp, C.c_int32]),
     ("fir_gallery_set_row_offset", C.c_int, [_vp, C.c_int64]),
+    ("fir_gallery_reserve", C.c_int, [_vp, C.c_int64]),
+    ("fir_gallery_capacity", C.c_int, [_vp, _i64p]),
+    ("fir_gallery_append", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("fir_gallery_append_dev", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
+    ("fir_gallery_set_rows", C.c_int, [_vp, _vp, C.c_int32, _vp, _vp]),
+    ("fir_gallery_remove_rows", C.c_int, [_vp, _vp, C.c_int32, _vp]),
+    ("fir_gallery_remove_plan", C.c_int, [C.c_int64, _vp, C.c_int32, _vp]),
+    ("fir_gallery_read_rows", C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
     ("fir_gallery_set_large_batch_mfma", C.c_int, [_vp, C.c_int32]),
     ("fir_gallery_set_int8_nomination", C.c_int, [_vp, C.c_int32]),
     ("fir_feature_distance", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p]),
@@ -234,6 +242,15 @@ def class_keys_merge(keys, classes, k):
     return keys_out, classes_out
 
 
+def remove_plan(n, row_idx):
+    """fir_gallery_remove_rows' rule as pure integer work on the host (fir_gallery_remove_plan): moved_from[m], the former row
+    now sitting at row_idx[i], -1 where row_idx[i] >= n - m. Raises FirError on an index outside [0, n) or a duplicate."""
+    row_idx = np.ascontiguousarray(row_idx, dtype=np.int32).reshape(-1)
+    moved = np.empty(row_idx.size, np.int32)
+    _check(lib().fir_gallery_remove_plan(int(n), row_idx.ctypes.data_as(_vp), row_idx.size, moved.ctypes.data_as(_vp)))
+    return moved
+
+
 class DispatchInfo(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("path", C.c_int32), ("kernel", C.c_char * 160), ("launches", C.c_int32), ("grid_x", C.c_int32),
                 ("grid_y", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32), ("vgprs", C.c_int32), ("queries_per_pass", C.c_int32),
@@ -296,6 +313,68 @@ class Gallery:
 
     def set_row_offset(self, off):
         _check(lib().fir_gallery_set_row_offset(self._h, off))
+
+    # ---- in-place updates (include/fir_amd.h); self.n follows the handle ----
+    def _follow(self):
+        n = C.c_int64()
+        _check(lib().fir_gallery_info(self._h, C.byref(n), None, None, None))
+        self.n = int(n.value)
+
+    def reserve(self, rows):
+        _check(lib().fir_gallery_reserve(self._h, int(rows)))
+
+    def capacity(self):
+        rows = C.c_int64()
+        _check(lib().fir_gallery_capacity(self._h, C.byref(rows)))
+        return int(rows.value)
+
+    def append(self, rows, class_no=None):
+        """rows[m, d] (class_no[m] on a labelled handle) become gallery rows n .. n + m - 1."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.d)
+        cls_p = None
+        if class_no is not None:
+            class_no = np.ascontiguousarray(class_no, dtype=np.int32).reshape(-1)
+            if class_no.size != rows.shape[0]:
+                raise ValueError("class_no must have one entry per row")
+            cls_p = class_no.ctypes.data_as(_vp)
+        _check(lib().fir_gallery_append(self._h, rows.ctypes.data_as(_vp), rows.shape[0], cls_p))
+        self._follow()
+
+    def append_dev(self, rows_ptr, m, class_ptr=None, stream=None):
+        """The same from device memory (raw pointers), asynchronous on `stream`."""
+        _check(lib().fir_gallery_append_dev(self._h, _vp(rows_ptr), int(m), _vp(class_ptr) if class_ptr else None, _vp(stream) if stream else None))
+        self._follow()
+
+    def set_rows(self, row_idx, new_rows, class_no=None):
+        """Rows row_idx (local, distinct) take the values new_rows[m, d]; class_no None keeps their labels."""
+        row_idx = np.ascontiguousarray(row_idx, dtype=np.int32).reshape(-1)
+        new_rows = np.ascontiguousarray(new_rows, dtype=np.float32).reshape(-1, self.d)
+        if new_rows.shape[0] != row_idx.size:
+            raise ValueError("new_rows must have one row per index")
+        cls_p = None
+        if class_no is not None:
+            class_no = np.ascontiguousarray(class_no, dtype=np.int32).reshape(-1)
+            if class_no.size != row_idx.size:
+                raise ValueError("class_no must have one entry per index")
+            cls_p = class_no.ctypes.data_as(_vp)
+        _check(lib().fir_gallery_set_rows(self._h, row_idx.ctypes.data_as(_vp), row_idx.size, new_rows.ctypes.data_as(_vp), cls_p))
+
+    def remove_rows(self, row_idx):
+        """Swap-remove of the rows row_idx (local, distinct); returns moved_from[m] (see remove_plan)."""
+        row_idx = np.ascontiguousarray(row_idx, dtype=np.int32).reshape(-1)
+        moved = np.empty(row_idx.size, np.int32)
+        _check(lib().fir_gallery_remove_rows(self._h, row_idx.ctypes.data_as(_vp), row_idx.size, moved.ctypes.data_as(_vp)))
+        self._follow()
+        return moved
+
+    def read_rows(self, row0=0, m=None, with_classes=False):
+        """Rows row0 .. row0 + m - 1 (m None: to the end) as [m, d] float32; with_classes: (rows, class_no[m])."""
+        self._follow()
+        m = self.n - row0 if m is None else int(m)
+        rows = np.empty((max(m, 0), self.d), np.float32)
+        cls = np.empty(max(m, 0), np.int32) if with_classes else None
+        _check(lib().fir_gallery_read_rows(self._h, int(row0), m, rows.ctypes.data_as(_vp), cls.ctypes.data_as(_vp) if with_classes else None))
+        return (rows, cls) if with_classes else rows
 
     def set_large_batch_mfma(self, min_queries):
         _check(lib().fir_gallery_set_large_batch_mfma(self._h, min_queries))

@@ -61,6 +61,12 @@ struct fir_gallery {
     int64_t row_offset = 0;
     GalleryBuf<float4> gal4;      // the tiled rows (fir_kernels.h layout) ...
     GalleryBuf<int32_t> cls;      // ... and their labels (empty: created without): fir_gallery_memory_bytes' `tiled`
+    // in-place updates (fir_gallery_append ...): gal4 has room for cap_tiles tiles (every one beyond `tiles` zero), cls for cls_rows labels;
+    // generation counts the successful mutations (views and the states built from them carry the number they were made at)
+    int64_t cap_tiles = 0, cls_rows = 0;
+    uint64_t generation = 0;
+    bool borrowed = false;        // a shard of a fir_sharded handle (fir_gallery_set_borrowed_): every mutation is refused
+    bool plain_stale = false;     // gallery_plain has to be read again: a mutation ran since (refresh_plain)
     hipStream_t stream = nullptr;
     // chi-square / KL: range[0] = a gallery value outside in_plain_range() was uploaded, range[1] = serial of the last query
     // transposition that met one (fir_common.h); the scans read both and pick their division sequence on the device
@@ -122,7 +128,7 @@ struct fir_gallery {
     fir_dispatch_info last{}; // dominant kernel of the most recent search
     fir_twd_dispatch_info twd_last{0, -1};   // fir_twd_last_dispatch (fir_twd.hip writes it through fir_gallery_twd_record_); classifier -1: no call yet
     int64_t twd_mfma[6] = {};                // fir_twd_last_mfma (fir_twd.hip writes it through fir_gallery_twd_mfma_record_)
-    bool label_known = false;                // fir_gallery_label_range_: smallest and largest label, found once (the labels never change)
+    bool label_known = false;                // fir_gallery_label_range_: smallest and largest label, found once per generation
     int32_t label_lo = 0, label_hi = -1;
     int call_launches = 0;    // scan launches of the current call (note_dispatch)
     int max_tiles_per_launch = 64;   // query tiles (gallery passes) folded into one launch of the hand-scheduled kernels
@@ -385,6 +391,19 @@ void note_dispatch(fir_gallery* g, const void* fn, const char* name, int launche
     L.flops_per_launch = flops;
 }
 
+// g->gallery_plain after a mutation: the update kernels have set range[0] where a written value asked for it (it is never cleared: an
+// out-of-range value that was overwritten or removed since keeps the full division sequence, the same bits). `st` is the stream of
+// the call that asks, which the call order has made wait for the mutation; it is synchronised once.
+int refresh_plain(fir_gallery* g, hipStream_t st) {
+    if (!g->plain_stale) return FIR_OK;
+    int32_t r0 = 1;
+    FIR_HIP(hipMemcpyAsync(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost, st));
+    FIR_HIP(hipStreamSynchronize(st));
+    g->gallery_plain = r0 == 0;
+    g->plain_stale = false;
+    return FIR_OK;
+}
+
 int check_range(const fir_gallery* g, int32_t& start, int32_t& end) {
     if (end == 0) end = g->d;   // db_features.cpp:320-321
     if (start < 0 || end > g->d || start >= end)
@@ -512,6 +531,8 @@ int top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, 
     // chi-square batches over a large plain-range gallery: nomination scan + exact re-rank (topk_lists_dev with K = 1), the same
     // keys at about twice the rate; it synchronises `st` once (it has to know that no list overflowed) and leaves the call to the
     // exact scan below when it cannot answer (operands outside the plain range, list overflow)
+    if (g->metric == kChi2 || g->metric == kKL)
+        if (const int rcp = refresh_plain(g, st)) return rcp;
     if ((g->metric == kChi2 || g->metric == kKL) && g->gallery_plain && scope.tiles == 0 && !scope.quiet && qb >= 8 && g->n >= 65536 &&
         g->qpp == 0) {
         int rc0 = FIR_OK;
@@ -828,8 +849,9 @@ int list_rerank_select(const ListCall& c, uint64_t* d_keys) {
 // fir_gallery_list_nominations_ (tests) reads out instead. all_rows (tests only): every live query's threshold becomes +inf once it
 // has been formed, so the append scan lists every row with its nomination value.
 int list_nominate(ListCall& c, bool all_rows = false) {
-    list_form(c);
     int rc;
+    if ((rc = refresh_plain(c.g, c.st))) return rc;
+    list_form(c);
     if ((rc = list_workspace(c))) return rc;
     if ((rc = list_row_sums(c))) return rc;
     if ((rc = list_row_samples(c))) return rc;
@@ -1100,6 +1122,7 @@ int gallery_alloc(int64_t n, int32_t d, int32_t metric, int32_t device, fir_gall
     g->d = d;
     g->dp4 = (d + 3) / 4;
     g->tiles = (n + kTileRows - 1) / kTileRows;
+    g->cap_tiles = g->tiles;      // (an empty gallery's one tile is never written: its first append allocates)
     g->metric = metric;
     g->max_waves = g->cus * 8 * (kBlock / 64);
     const auto fail = [g](int code) { delete g; return code; };      // (the destructor releases whatever exists by then)
@@ -1179,7 +1202,7 @@ int fir_fail_(int code, const char* fmt, ...) {
 int fir_gallery_view_(fir_gallery* g, fir_gallery_view* out) {
     if (!g || !out) return FIR_ERR_ARG;
     out->device = g->device; out->cus = g->cus; out->n = g->n; out->d = g->d; out->metric = g->metric; out->row_offset = g->row_offset;
-    out->cls = g->cls; out->stream = g->stream;
+    out->cls = g->cls; out->stream = g->stream; out->generation = g->generation;
     return FIR_OK;
 }
 int fir_gallery_call_begin_(fir_gallery* g, hipStream_t st) {
@@ -1338,6 +1361,7 @@ int fir_gallery_create(const float* rows, int64_t n, int32_t d, const int32_t* c
     stage.release();                                       // before the labels are allocated, as ever
     if (rc == FIR_OK && class_no && n > 0) {
         e = g->cls.reserve((size_t)n * sizeof(int32_t));
+        g->cls_rows = n;
         if (e == hipSuccess) e = hipMemcpy(g->cls, class_no, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class upload: %s", hipGetErrorString(e));
     }
@@ -1362,6 +1386,7 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
     }
     if (rc == FIR_OK && d_class_no && n > 0) {
         hipError_t e = g->cls.reserve((size_t)n * sizeof(int32_t));
+        g->cls_rows = n;
         if (e == hipSuccess) e = hipMemcpyAsync(g->cls, d_class_no, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class copy: %s", hipGetErrorString(e));
     }
@@ -1451,7 +1476,8 @@ int fir_gallery_memory_bytes(fir_gallery* g, int64_t* tiled, int64_t* fp16_fragm
     // the capacities of the workspaces and the scratch slots; the range flags and the one-query key block (16 and 64 bytes) are
     // reported nowhere, as ever
     sc += (int64_t)g->scratch_bytes();
-    if (tiled) *tiled = (int64_t)g->tiles * fir::kTileRows * (int64_t)((g->d + 3) / 4) * 16 + (g->cls ? (int64_t)g->n * 4 : 0);
+    // (the allocated capacity: on a handle that was never updated the tiles and labels of its n rows)
+    if (tiled) *tiled = (int64_t)g->cap_tiles * fir::kTileRows * (int64_t)((g->d + 3) / 4) * 16 + (g->cls ? (int64_t)g->cls_rows * 4 : 0);
     if (fp16_fragments) *fp16_fragments = fr;
     if (rowmajor_shadow) *rowmajor_shadow = rm;
     if (scratch) *scratch = sc;
@@ -1478,6 +1504,317 @@ int fir_gallery_set_row_offset(fir_gallery* g, int64_t first_global_row) {
     return FIR_OK;
 }
 
+// ---- in-place updates: append, overwrite and remove rows (include/fir_amd.h has the contract) -------------------------------------
+// Every successful mutation ends in gallery_changed(): whatever the handle caches about rows, labels or n starts again, and the
+// generation moves on, which the states other code built over the handle compare with theirs (fir_gallery_stale_).
+namespace {
+constexpr int64_t kRowLimit = ((int64_t)1 << 31) - 64;        // gallery_alloc's limit, for n + row offset
+constexpr int64_t kUpdateSlabBytes = (int64_t)64 << 20;       // host rows pass through g->dq in slabs of this size
+
+void gallery_changed(fir_gallery* g) {
+    ++g->generation;
+    g->tiles = (g->n + kTileRows - 1) / kTileRows;
+    g->rs_start = g->rs_end = g->rs_metric = -1;              // row sums / entropies (list_row_sums)
+    g->label_known = false;
+    g->small_hits = g->few_hits = 0;                          // the warm-up and learnt-dispatch counters start again
+    g->gemm_failed = false;
+    g->warm_left = 0;
+    g->plain_stale = true;
+    // (the handle's matrix-core states carry their generation: drop_stale_gemm_states)
+}
+
+int check_mutable(const fir_gallery* g) {
+    if (!g) return fir_fail_(FIR_ERR_ARG, "gallery is NULL");
+    if (g->borrowed) return fir_fail_(FIR_ERR_STATE, "the gallery is a shard of a sharded handle: its rows cannot be changed");
+    return FIR_OK;
+}
+
+int64_t capacity_rows(const fir_gallery* g) {
+    const int64_t rows = g->cap_tiles * kTileRows;
+    return g->cls ? std::min(rows, g->cls_rows) : rows;
+}
+
+// Room for need_rows rows, and for their labels when `labels`. Nothing to do when both are there. Otherwise: wait for the handle's
+// queued calls (they read the old buffers), allocate -- with a quarter of headroom when `headroom`, the exact size when that cannot
+// be had --, copy on the device, clear the new tiles, free the old buffers. Old and new buffers exist side by side until the copy
+// is done. On failure the handle is as it was.
+int gallery_room(fir_gallery* g, int64_t need_rows, bool headroom, bool labels) {
+    const bool grow_tiles = need_rows > g->cap_tiles * kTileRows;
+    const bool grow_cls = labels && need_rows > g->cls_rows;
+    if (!grow_tiles && !grow_cls) return FIR_OK;
+    int rc = fir_gallery_wait_calls_(g);
+    if (rc) return rc;
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    const size_t tile_bytes = (size_t)g->dp4 * 64 * sizeof(float4);
+    for (int attempt = headroom ? 0 : 1; attempt < 2; ++attempt) {
+        const int64_t rows = attempt == 0 ? need_rows + need_rows / 4 : need_rows;
+        const int64_t new_tiles = grow_tiles ? (rows + kTileRows - 1) / kTileRows : g->cap_tiles;
+        const int64_t new_cls_rows = new_tiles * kTileRows;
+        GalleryBuf<float4> ngal;
+        GalleryBuf<int32_t> ncls;
+        hipError_t e = hipSuccess;
+        if (grow_tiles) e = ngal.reserve((size_t)new_tiles * tile_bytes);
+        if (e == hipSuccess && (grow_cls || (grow_tiles && g->cls))) e = ncls.reserve((size_t)new_cls_rows * sizeof(int32_t));
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); continue; }        // (what was allocated goes with this scope)
+        if (e != hipSuccess) return fir_fail_(FIR_ERR_HIP, "hipMalloc of the grown gallery: %s", hipGetErrorString(e));
+        if (grow_tiles) {
+            const size_t used = (size_t)g->tiles * tile_bytes;
+            if (used) FIR_HIP(hipMemcpyAsync(ngal.p, g->gal4.p, used, hipMemcpyDeviceToDevice, g->stream));
+            FIR_HIP(hipMemsetAsync((char*)ngal.p + used, 0, (size_t)new_tiles * tile_bytes - used, g->stream));
+        }
+        if (ncls.p && g->cls && g->n > 0) FIR_HIP(hipMemcpyAsync(ncls.p, g->cls.p, (size_t)g->n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
+        FIR_HIP(hipStreamSynchronize(g->stream));
+        if (grow_tiles) { std::swap(g->gal4.p, ngal.p); std::swap(g->gal4.cap, ngal.cap); g->cap_tiles = new_tiles; }
+        if (ncls.p) { std::swap(g->cls.p, ncls.p); std::swap(g->cls.cap, ncls.cap); g->cls_rows = new_cls_rows; }
+        g->drop_gemm_states();                  // they hold the old buffer's address
+        const bool plain_stale = g->plain_stale;
+        gallery_changed(g);
+        g->plain_stale = plain_stale;           // (the rows were copied, not changed: range[0] still says what gallery_plain says)
+        return FIR_OK;                         // (ngal / ncls now own the old buffers: freed here)
+    }
+    return fir_fail_(FIR_ERR_NOMEM, "no device memory for a gallery of %lld rows", (long long)need_rows);
+}
+
+// The checks of both appends, in the order of the other calls. 0 = go on, kNothingToDo, < 0 = the error.
+int check_append(const fir_gallery* g, const void* rows, int64_t m, const void* class_no) {
+    const int rc = check_mutable(g);
+    if (rc) return rc;
+    if (m > 0 && !rows) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (m == 0) return kNothingToDo;
+    if (g->n > 0 && g->cls && !class_no) return fir_fail_(FIR_ERR_ARG, "the gallery has class labels: appended rows need class_no");
+    if (g->n > 0 && !g->cls && class_no) return fir_fail_(FIR_ERR_ARG, "the gallery has no class labels: class_no must be NULL");
+    if (g->n + m + g->row_offset >= kRowLimit)
+        return fir_fail_(FIR_ERR_ARG, "n + m + row offset = %lld does not fit 32-bit row indices", (long long)(g->n + m + g->row_offset));
+    return FIR_OK;
+}
+
+// The room for n + m rows. An empty handle takes its labelled-ness from its first append: it holds no labels (one created empty keeps
+// none, one emptied by fir_gallery_remove_rows gives them up there), so `labels` alone decides whether a label buffer is made.
+int append_room(fir_gallery* g, int64_t m, bool labels) { return gallery_room(g, g->n + m, true, labels); }
+
+int launch_append(fir_gallery* g, const float* d_rows, int64_t m, int64_t first, hipStream_t st) {
+    const int64_t ntiles = (first + m + kTileRows - 1) / kTileRows - first / kTileRows;
+    const int64_t blocks = (ntiles * g->dp4 * 64 + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_append_rows, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, m, first, g->d, g->dp4, (float4*)g->gal4, (int32_t*)g->range);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+// rows per slab of a host-pointer update: the launch grid stays inside 2^31 blocks, the staging buffer inside kUpdateSlabBytes
+int64_t update_slab_rows(const fir_gallery* g) { return std::max<int64_t>(kTileRows, kUpdateSlabBytes / ((int64_t)g->dp4 * 16) / kTileRows * kTileRows); }
+
+// row_idx[m]: inside [0, n) and distinct. sorted <- the indices ascending.
+int check_row_list(int64_t n, const int32_t* row_idx, int32_t m, std::vector<int32_t>& sorted) {
+    sorted.assign(row_idx, row_idx + m);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= n) return fir_fail_(FIR_ERR_ARG, "row index %d outside [0,%lld)", sorted.front() < 0 ? sorted.front() : sorted.back(), (long long)n);
+    for (int32_t i = 1; i < m; ++i)
+        if (sorted[i] == sorted[i - 1]) return fir_fail_(FIR_ERR_ARG, "row index %d is listed twice", sorted[i]);
+    return FIR_OK;
+}
+
+// The removal rule. dst_of (may be NULL) <- for each tail row n' + i its hole, -1 when the row is removed itself.
+int remove_plan(int64_t n, const int32_t* row_idx, int32_t m, int32_t* moved_from, std::vector<int32_t>* dst_of) {
+    if (n < 0 || (m > 0 && !row_idx)) return fir_fail_(FIR_ERR_ARG, n < 0 ? "n < 0" : "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (dst_of) dst_of->clear();
+    if (m == 0) return FIR_OK;
+    std::vector<int32_t> sorted;
+    const int rc = check_row_list(n, row_idx, m, sorted);
+    if (rc) return rc;
+    const int64_t n_new = n - m;
+    const size_t holes = (size_t)(std::lower_bound(sorted.begin(), sorted.end(), n_new) - sorted.begin());     // sorted[0, holes): the holes, ascending
+    std::vector<int32_t> survivors;                                  // the rows of [n', n) that stay, ascending: as many as holes
+    survivors.reserve(holes);
+    if (dst_of) dst_of->assign((size_t)m, -1);
+    size_t t = holes;
+    for (int64_t r = n_new; r < n; ++r) {
+        if (t < sorted.size() && sorted[t] == r) { ++t; continue; }
+        if (dst_of) (*dst_of)[(size_t)(r - n_new)] = sorted[survivors.size()];
+        survivors.push_back((int32_t)r);
+    }
+    if (moved_from)
+        for (int32_t i = 0; i < m; ++i)
+            moved_from[i] = row_idx[i] >= n_new ? -1 : survivors[(size_t)(std::lower_bound(sorted.begin(), sorted.begin() + (long)holes, row_idx[i]) - sorted.begin())];
+    return FIR_OK;
+}
+}  // namespace
+
+void fir_gallery_set_borrowed_(fir_gallery* g, int borrowed) { if (g) g->borrowed = borrowed != 0; }
+uint64_t fir_gallery_generation_(const fir_gallery* g) { return g ? g->generation : 0; }
+int fir_gallery_stale_(const fir_gallery* g, uint64_t built_at, const char* what) {
+    if (!g || g->generation == built_at) return FIR_OK;
+    return fir_fail_(FIR_ERR_STATE, "the gallery changed after this %s state was built (rows were appended, overwritten or removed): destroy it and create it again", what);
+}
+
+int fir_gallery_reserve(fir_gallery* g, int64_t rows) {
+    const int rc = check_mutable(g);
+    if (rc) return rc;
+    if (rows <= g->n) return FIR_OK;
+    if (rows + g->row_offset >= kRowLimit) return fir_fail_(FIR_ERR_ARG, "rows + row offset = %lld does not fit 32-bit row indices", (long long)(rows + g->row_offset));
+    FIR_HIP(hipSetDevice(g->device));
+    return gallery_room(g, rows, false, g->cls != nullptr);
+}
+
+int fir_gallery_capacity(const fir_gallery* g, int64_t* rows) {
+    if (!g || !rows) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    *rows = std::max(capacity_rows(g), g->n);
+    return FIR_OK;
+}
+
+int fir_gallery_append_dev(fir_gallery* g, const float* d_rows, int64_t m, const int32_t* d_class_no, void* stream) {
+    int rc = check_append(g, d_rows, m, d_class_no);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    if ((rc = append_room(g, m, d_class_no != nullptr))) return rc;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    const int64_t slab = update_slab_rows(g);
+    for (int64_t r0 = 0; r0 < m; r0 += slab)
+        if ((rc = launch_append(g, d_rows + r0 * g->d, std::min(slab, m - r0), g->n + r0, call.st))) return rc;
+    if (d_class_no) FIR_HIP(hipMemcpyAsync(g->cls + g->n, d_class_no, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToDevice, call.st));
+    g->n += m;
+    gallery_changed(g);
+    return FIR_OK;
+}
+
+int fir_gallery_append(fir_gallery* g, const float* rows, int64_t m, const int32_t* class_no) {
+    int rc = check_append(g, rows, m, class_no);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    // the staging buffer first (only host-pointer calls use it, and those have finished): if it cannot be had, nothing has grown yet
+    const int64_t slab = std::min(update_slab_rows(g), m);
+    if ((rc = FIR_NEED(g->dq, (size_t)slab * g->d))) return rc;
+    if ((rc = append_room(g, m, class_no != nullptr))) return rc;
+    g->drop_gemm_states();                                 // (this call waits anyway: their memory goes now, not with the next routed call)
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    for (int64_t r0 = 0; r0 < m; r0 += slab) {
+        const int64_t have = std::min(slab, m - r0);
+        FIR_HIP(hipMemcpyAsync(g->dq, rows + r0 * g->d, (size_t)have * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+        if ((rc = launch_append(g, g->dq, have, g->n + r0, g->stream))) return rc;
+        FIR_HIP(hipStreamSynchronize(g->stream));           // the staging buffer is reused by the next slab
+    }
+    if (class_no) FIR_HIP(hipMemcpyAsync(g->cls + g->n, class_no, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    g->n += m;
+    gallery_changed(g);
+    call.done();
+    return refresh_plain(g, g->stream);
+}
+
+int fir_gallery_set_rows(fir_gallery* g, const int32_t* row_idx, int32_t m, const float* new_rows, const int32_t* class_no) {
+    int rc = check_mutable(g);
+    if (rc) return rc;
+    if (m > 0 && (!row_idx || !new_rows)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (m == 0) return FIR_OK;
+    if (class_no && !g->cls) return fir_fail_(FIR_ERR_ARG, "the gallery has no class labels: class_no must be NULL");
+    std::vector<int32_t> sorted;
+    if ((rc = check_row_list(g->n, row_idx, m, sorted))) return rc;
+    FIR_HIP(hipSetDevice(g->device));
+    const int64_t slab = std::min<int64_t>(update_slab_rows(g), m);
+    if ((rc = FIR_NEED(g->dq, (size_t)slab * g->d)) || (rc = FIR_NEED(g->didx, (size_t)2 * m))) return rc;
+    g->drop_gemm_states();
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    FIR_HIP(hipMemcpyAsync(g->didx, row_idx, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    if (class_no) FIR_HIP(hipMemcpyAsync(g->didx + m, class_no, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    for (int64_t r0 = 0; r0 < m; r0 += slab) {
+        const int64_t have = std::min<int64_t>(slab, m - r0);
+        FIR_HIP(hipMemcpyAsync(g->dq, new_rows + r0 * g->d, (size_t)have * g->d * sizeof(float), hipMemcpyHostToDevice, g->stream));
+        hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((have * g->dp4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, g->stream, (const float*)g->dq,
+                           (const int32_t*)(g->didx + r0), have, g->d, g->dp4, (float4*)g->gal4, (int32_t*)g->range,
+                           class_no ? (const int32_t*)(g->didx + m + r0) : (const int32_t*)nullptr, (int32_t*)g->cls);
+        FIR_HIP(hipGetLastError());
+        FIR_HIP(hipStreamSynchronize(g->stream));
+    }
+    gallery_changed(g);
+    call.done();
+    return refresh_plain(g, g->stream);
+}
+
+int fir_gallery_remove_plan(int64_t n, const int32_t* row_idx, int32_t m, int32_t* moved_from) { return remove_plan(n, row_idx, m, moved_from, nullptr); }
+
+int fir_gallery_remove_rows(fir_gallery* g, const int32_t* row_idx, int32_t m, int32_t* moved_from) {
+    int rc = check_mutable(g);
+    if (rc) return rc;
+    std::vector<int32_t> dst_of, moved((size_t)std::max(m, 0));       // (moved_from is the caller's: written only after the checks and the allocation have passed)
+    if ((rc = remove_plan(g->n, row_idx, m, moved_from ? moved.data() : nullptr, &dst_of))) return rc;
+    if (m == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    if ((rc = FIR_NEED(g->didx, (size_t)m))) return rc;
+    g->drop_gemm_states();
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    if (moved_from) std::copy(moved.begin(), moved.end(), moved_from);
+    const int64_t n_new = g->n - m;
+    FIR_HIP(hipMemcpyAsync(g->didx, dst_of.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    hipLaunchKernelGGL(k_move_rows, dim3((unsigned)(((int64_t)m * g->dp4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, g->stream, (float4*)g->gal4, g->dp4, n_new,
+                       (int64_t)m, (const int32_t*)g->didx, (int32_t*)g->cls);
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    g->n = n_new;
+    if (n_new == 0 && g->cls) {                             // as fir_gallery_create with n == 0: an empty handle keeps no labels
+        g->cls.release();
+        g->cls_rows = 0;
+    }
+    const bool plain_stale = g->plain_stale;
+    gallery_changed(g);
+    g->plain_stale = plain_stale;                           // (rows moved and cleared: no value a row did not hold before)
+    call.done();
+    return FIR_OK;
+}
+
+int fir_gallery_read_rows(fir_gallery* g, int64_t row0, int64_t m, float* rows_out, int32_t* class_out) {
+    if (!g || (m > 0 && !rows_out)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (m == 0) return FIR_OK;
+    if (class_out && !g->cls) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    if (row0 < 0 || row0 > g->n || m > g->n - row0) return fir_fail_(FIR_ERR_ARG, "rows [%lld,+%lld) outside [0,%lld)", (long long)row0, (long long)m, (long long)g->n);
+    FIR_HIP(hipSetDevice(g->device));
+    const int64_t slab = std::min(update_slab_rows(g), m);
+    int rc = FIR_NEED(g->dq, (size_t)slab * g->d);
+    if (rc) return rc;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    for (int64_t r0 = 0; r0 < m; r0 += slab) {
+        const int64_t have = std::min(slab, m - r0);
+        hipLaunchKernelGGL(k_untile_rows, dim3((unsigned)((have * g->dp4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, g->stream, (const float4*)g->gal4, g->dp4, g->d,
+                           row0 + r0, have, (float*)g->dq);
+        FIR_HIP(hipGetLastError());
+        FIR_HIP(hipMemcpyAsync(rows_out + r0 * g->d, g->dq, (size_t)have * g->d * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+        FIR_HIP(hipStreamSynchronize(g->stream));
+    }
+    if (class_out) FIR_HIP(hipMemcpyAsync(class_out, g->cls + row0, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    call.done();
+    return FIR_OK;
+}
+
+int fir_gallery_padding_words_(fir_gallery* g, int64_t* words) {
+    if (!g || !words) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    *words = 0;
+    if (g->cap_tiles == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    void* p = nullptr;
+    int rc = fir_gallery_scratch_(g, 23, 16, &p);            // (the label range's two words are entered afresh by every use; words 2 and 3 are this counter)
+    if (rc) return rc;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    unsigned long long* cnt = (unsigned long long*)p + 1;
+    unsigned long long h = 0;
+    FIR_HIP(hipMemsetAsync(cnt, 0, sizeof h, g->stream));
+    hipLaunchKernelGGL(k_count_padding, dim3((unsigned)((g->cap_tiles * g->dp4 * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, g->stream, (const float4*)g->gal4,
+                       g->n, g->cap_tiles, g->d, g->dp4, cnt);
+    FIR_HIP(hipGetLastError());
+    FIR_HIP(hipMemcpyAsync(&h, cnt, sizeof h, hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    call.done();
+    *words = (int64_t)h;
+    return FIR_OK;
+}
+
 int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_t start_pos, int32_t end_pos,
                          int32_t metric, int32_t device, float* out) {
     if (!lhs || !rhs || !out) return fir_fail_(FIR_ERR_ARG, "NULL argument");
@@ -1501,6 +1838,13 @@ int fir_feature_distance(const float* lhs, const float* rhs, int32_t len, int32_
 }
 
 namespace {
+// The handle's own states that were built before its most recent mutation (fir_gallery_append_dev does not wait, so it leaves them
+// to the next call that wants one): freed here, which waits for the handle's calls, and rebuilt by that call.
+void drop_stale_gemm_states(fir_gallery* g) {
+    if (g->gemm && fir_gemm_generation_(g->gemm) != g->generation) { fir_gemm_destroy(g->gemm); g->gemm = nullptr; }
+    for (auto& ps : g->gemm_prefix)
+        if (ps.m && fir_gemm_generation_(ps.m) != g->generation) { fir_gemm_destroy(ps.m); ps.m = nullptr; ps.end = 0; }
+}
 // 0 = *m is the handle's fir_gemm for features [0, end), 1 = this shape stays with the scan, < 0 = error
 int ensure_gemm(fir_gallery* g, int32_t end, fir_gemm** m, int* warm = nullptr, int warm_calls = 0) {
     // warm / warm_calls (automatic dispatch of cases that save tens to hundreds of microseconds per call: cache-resident galleries,
@@ -1508,6 +1852,7 @@ int ensure_gemm(fir_gallery* g, int32_t end, fir_gemm** m, int* warm = nullptr, 
     // a gallery that keeps getting such calls; the first warm_calls of them take the scan (a test harness that makes ONE batched call
     // against a 3 030-row gallery would pay 16 ms to save 2)
     const bool whole = end == g->d;
+    drop_stale_gemm_states(g);
     if (g->shadow_mode == FIR_SHADOW_NONE && g->large_batch_min <= 0) return 1;     // the caller forbade every copy: the scan
     fir_gallery::PrefixSlot* ps = nullptr;
     if (!whole) {
@@ -1631,6 +1976,7 @@ int fir_twd_mfma_classes_(fir_gallery* g, const float* d_queries, int32_t qb, in
                           int32_t* d_classes, void* stream, int64_t* exact_answered) {
     if (!g || !d_queries || !exact_answered) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     const hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+    drop_stale_gemm_states(g);      // (a state the call below would replace must not lend its total to `before`)
     // the exact-scan total of the state for [0, end_pos), before and after: the difference is this call's share (a state built by
     // this call starts from zero)
     auto state_of = [&]() -> fir_gemm* {
@@ -1684,6 +2030,8 @@ int fir_gallery_label_range_(fir_gallery* g, int32_t* lo, int32_t* hi) {
         const int rc = fir_gallery_scratch_(g, 23, 16, &p);
         if (rc) return rc;
         int32_t h[2] = {INT32_MAX, INT32_MIN};
+        // (the labels may have been appended by a call on another stream: the handle's own waits for the handle's last call)
+        if (g->last_stream && g->last_stream != g->stream) FIR_HIP(hipStreamWaitEvent(g->stream, g->last_done, 0));
         FIR_HIP(hipMemcpyAsync(p, h, sizeof h, hipMemcpyHostToDevice, g->stream));
         const int grid = (int)std::min<int64_t>(std::max<int64_t>((g->n + kBlock - 1) / kBlock, 1), 4 * std::max(g->cus, 1));
         hipLaunchKernelGGL(k_label_range, dim3(grid), dim3(kBlock), 0, g->stream, g->cls, g->n, (int32_t*)p);

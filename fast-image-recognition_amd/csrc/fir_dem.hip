@@ -901,6 +901,7 @@ int dem_recognize_call(fir_dem* h, const float* queries, int32_t qb, float thr, 
     if (qb <= 0) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: qb=%d must be positive", qb);
     if (!queries) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: queries is NULL");
     if (!out.row && !out.dist && !out.found && !out.calc && !out.tie) return fir_fail_(FIR_ERR_ARG, "fir_dem_recognize: every output is NULL");
+    if (const int rcg = fir_gallery_stale_(h->g, h->v.generation, "fir_dem")) return rcg;     // (the table is [pivot][n of then])
     const fir_gallery_view& v = h->v;
     FIR_HIP(hipSetDevice(v.device));
     const hipStream_t st = !host && stream ? (hipStream_t)stream : v.stream;
@@ -1035,6 +1036,7 @@ int fir_dem_get(fir_dem* h, int32_t* pivots_out, float* min_other_out, float* ta
 int fir_dem_likelihoods(fir_dem* h, const float* queries, int32_t qb, float* pivot_dist_out, float* lik_out) {
     if (!h || (qb > 0 && !queries)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
+    if (const int rcg = fir_gallery_stale_(h->g, h->v.generation, "fir_dem")) return rcg;
     const fir_gallery_view& v = h->v;
     FIR_HIP(hipSetDevice(v.device));
     const int n = (int)v.n, used = h->used;

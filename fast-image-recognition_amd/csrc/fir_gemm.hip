@@ -1391,6 +1391,8 @@ int fir_gemm_create_ex(fir_gallery* g, int32_t precision, fir_gemm** out) { retu
 
 int fir_gemm_create_range(fir_gallery* g, int32_t precision, int32_t end_pos, fir_gemm** out) { return fir_gemm_create_range_ex_(g, precision, end_pos, -1, out); }
 
+uint64_t fir_gemm_generation_(const fir_gemm* m) { return m ? m->v.generation : 0; }
+
 void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch) {
     if (fragments) *fragments = (int64_t)(m->gh.cap + m->gb.cap + m->gm.cap + m->g8.cap);
     if (rowmajor) *rowmajor = (int64_t)m->rowmajor.cap;
@@ -2141,6 +2143,7 @@ static int gemm_search(fir_gemm* m, const float* d_queries, int32_t qb, const Fi
     if (qb < 0) return fir_fail_(FIR_ERR_ARG, "qb < 0");
     if (s.k < kind.k_min || s.k > kind.k_max) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,%d]", s.k, kind.k_max);
     if (qb == 0) return FIR_OK;
+    if (const int rcg = fir_gallery_stale_(m->g, m->v.generation, "fir_gemm")) return rcg;      // (m->v.n and the tiled buffer are the gallery's of then)
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);   // this state's scratch, and the gallery's, is shared with every other call on the gallery
@@ -2281,6 +2284,7 @@ int fir_gemm_search_few_keys_dev(fir_gemm* m, const float* d_queries, int32_t qb
     if (!m || !d_keys || !d_queries) return fir_fail_(FIR_ERR_ARG, "NULL argument");
     if (qb < 1 || qb > 8) return fir_fail_(FIR_ERR_ARG, "qb=%d outside [1,8]", qb);
     if (m->precision != FIR_GEMM_F16) return fir_fail_(FIR_ERR_ARG, "the few-query form needs the fp16 copy");
+    if (const int rcg = fir_gallery_stale_(m->g, m->v.generation, "fir_gemm")) return rcg;
     FIR_HIP(hipSetDevice(m->v.device));
     hipStream_t st = stream ? (hipStream_t)stream : m->v.stream;
     FirCallOrder order(m->g, st);

@@ -292,7 +292,7 @@ extern "C" int fir_gemm_create_f64_(int device, int cus, void* stream, const voi
     m->f64 = true;
     m->gal2 = (const double2*)gal2v;
     m->dp2 = dp2;
-    m->v.device = device; m->v.cus = cus; m->v.n = nt; m->v.d = d; m->v.metric = 0; m->v.row_offset = 0; m->v.cls = nullptr; m->v.stream = (hipStream_t)stream;
+    m->v.device = device; m->v.cus = cus; m->v.n = nt; m->v.d = d; m->v.metric = 0; m->v.row_offset = 0; m->v.cls = nullptr; m->v.stream = (hipStream_t)stream; m->v.generation = 0;
     m->feat = d;
     m->precision = FIR_GEMM_F16;
     m->rerank_group = ngroup;

@@ -26,8 +26,21 @@ struct fir_gallery_view {
     int64_t row_offset;
     const int32_t* cls;     // device, may be NULL
     hipStream_t stream;     // the handle's own stream
+    uint64_t generation;    // bumped by every successful fir_gallery_append / _set_rows / _remove_rows / growth (fir_gallery_generation_)
 };
 extern "C" int fir_gallery_view_(fir_gallery* g, fir_gallery_view* out);
+// In-place updates (include/fir_amd.h: fir_gallery_append ...). A view, or anything built from one (fir_gemm, fir_dem), is good while its
+// generation is the handle's: after a mutation n, the labels and -- after a growth -- the buffers behind cls / fir_gallery_tiled_ are
+// other ones. fir_gallery_stale_: FIR_OK, or FIR_ERR_STATE ("the gallery changed after this state was built") for the entry points
+// of such states to return before they queue anything. g NULL (a float64 state has no gallery): FIR_OK.
+extern "C" uint64_t fir_gallery_generation_(const fir_gallery* g);
+extern "C" int fir_gallery_stale_(const fir_gallery* g, uint64_t built_at, const char* what);
+// fir_shard.hip marks the shards it owns: every mutation of a marked handle fails with FIR_ERR_STATE (their row ranges are the
+// sharded handle's bookkeeping).
+extern "C" void fir_gallery_set_borrowed_(fir_gallery* g, int borrowed);
+// tests only: the number of non-zero 32-bit words among what the layout invariant says is zero -- the rows at or beyond n of every
+// allocated tile and the features beyond d. Waits for the handle's calls; one small kernel on its own stream.
+extern "C" int fir_gallery_padding_words_(fir_gallery* g, int64_t* words);
 
 // Call order of one gallery handle (include/fir_amd.h: calls on one handle take effect in call order, whatever stream they are
 // given). Every entry point that queues work on the handle -- or on a fir_gemm state over it: they share its scratch -- holds a
@@ -230,6 +243,8 @@ extern "C" void fir_gemm_set_int8_(fir_gemm* m, int32_t mode);
 // pairs or more): -1 = the rule (fir_gemm.hip: gemm_pass_f16_), 0 = never, 1 = whenever the shape allows
 extern "C" void fir_gemm_set_int8_tile_(fir_gemm* m, int32_t mode);
 extern "C" void fir_gemm_memory_bytes_(const fir_gemm* m, int64_t* fragments, int64_t* rowmajor, int64_t* scratch);
+// the gallery generation the state was built at (the handle's own states are rebuilt when it is no longer the handle's)
+extern "C" uint64_t fir_gemm_generation_(const fir_gemm* m);
 
 struct fir_cls;
 extern "C" int fir_cls_pnn_scores_dev_(fir_cls* c, const double* queries, int32_t qb, double var, double** d_scores, void** stream, int32_t* max_batch);

@@ -1,6 +1,7 @@
 // fir_kernels.h -- gfx950 (MI355X / CDNA4) device code of the gallery matcher.
 //
-// One idea carries every kernel here: the gallery is re-tiled ONCE, at create time, into
+// One idea carries every kernel here: the gallery is re-tiled ONCE, at create time (rows that are appended, overwritten or moved
+// later are written straight into the same layout: k_append_rows, k_scatter_rows, k_move_rows), into
 //
 //     tile t (64 consecutive rows)  x  chunk c (4 consecutive features)  x  lane r (row in tile)
 //     float4 at  gal4[(t * dp4 + c) * 64 + r]            dp4 = ceil(d / 4)
@@ -1175,6 +1176,89 @@ __global__ void __launch_bounds__(kBlock) k_retile(const float* __restrict__ row
     }
     if (range && !(in_plain_range(v[0]) && in_plain_range(v[1]) && in_plain_range(v[2]) && in_plain_range(v[3]))) range[0] = 1;
     gal4[((row0 / kTileRows + tl) * dp4 + c) * 64 + r] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// ---- in-place gallery updates (fir_gallery_append / _set_rows / _remove_rows) ----
+// They keep the layout invariant the scans rely on: over tiles [0, ceil(n / 64)) the rows at or beyond n and the features beyond d are
+// zero. Like k_retile each sets range[0] when a value it writes is outside in_plain_range().
+//
+// Append: rows[m][d] row-major become gallery rows first .. first + m - 1 -- k_retile for a first row that is no multiple of 64. One
+// thread per float4 of tiles [first / 64, ceil((first + m) / 64)): a wave writes one contiguous KiB of a tile chunk. Rows below `first`
+// are never touched; rows beyond first + m are zero already (a grown buffer is cleared, a removal clears what it vacates) and stay so.
+__global__ void __launch_bounds__(kBlock) k_append_rows(const float* __restrict__ rows, int64_t m, int64_t first, int d, int dp4,
+                                                         float4* __restrict__ gal4, int32_t* __restrict__ range) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t tile0 = first / kTileRows;
+    const int64_t ntiles = (first + m + kTileRows - 1) / kTileRows - tile0;
+    if (o >= ntiles * dp4 * 64) return;
+    const int r = (int)(o & 63);
+    const int64_t tc = o >> 6;
+    const int c = (int)(tc % dp4);
+    const int64_t t = tile0 + tc / dp4;
+    const int64_t row = t * kTileRows + r;
+    if (row < first || row >= first + m) return;
+    const float* src = rows + (row - first) * d + (int64_t)c * 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c * 4 + j < d) v[j] = src[j];
+    if (!(in_plain_range(v[0]) && in_plain_range(v[1]) && in_plain_range(v[2]) && in_plain_range(v[3]))) range[0] = 1;
+    gal4[((size_t)t * dp4 + c) * 64 + r] = make_float4(v[0], v[1], v[2], v[3]);
+}
+// Scatter: rows[m][d] row-major replace gallery rows idx[0 .. m) (distinct, below n: the host checked), and cls_src[m] (may be NULL)
+// their labels. One thread per float4 of a source row: consecutive threads read consecutive chunks of one row (the source is the
+// coalesced side; a listed row's chunks lie a KiB apart in its tile whatever is done).
+__global__ void __launch_bounds__(kBlock) k_scatter_rows(const float* __restrict__ rows, const int32_t* __restrict__ idx, int64_t m, int d, int dp4,
+                                                          float4* __restrict__ gal4, int32_t* __restrict__ range, const int32_t* __restrict__ cls_src,
+                                                          int32_t* __restrict__ cls) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= m * dp4) return;
+    const int c = (int)(o % dp4);
+    const int64_t i = o / dp4;
+    const int64_t row = idx[i];
+    const float* src = rows + i * d + (int64_t)c * 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c * 4 + j < d) v[j] = src[j];
+    if (!(in_plain_range(v[0]) && in_plain_range(v[1]) && in_plain_range(v[2]) && in_plain_range(v[3]))) range[0] = 1;
+    gal4[((size_t)(row >> 6) * dp4 + c) * 64 + (row & 63)] = make_float4(v[0], v[1], v[2], v[3]);
+    if (c == 0 && cls_src) cls[row] = cls_src[i];
+}
+// Move: the tail rows [n_new, n_new + m) of a removal. dst_of[i] >= 0: row n_new + i survives and goes to the hole dst_of[i] < n_new,
+// features and label; every tail row is then cleared. The thread that clears a float4 is the one that read it, and holes lie below
+// n_new, so one launch has no race. One thread per float4, consecutive threads = consecutive tail rows of one chunk.
+__global__ void __launch_bounds__(kBlock) k_move_rows(float4* __restrict__ gal4, int dp4, int64_t n_new, int64_t m, const int32_t* __restrict__ dst_of,
+                                                       int32_t* __restrict__ cls) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= m * dp4) return;
+    const int64_t i = o % m;
+    const int c = (int)(o / m);
+    const int64_t row = n_new + i;
+    const size_t at = ((size_t)(row >> 6) * dp4 + c) * 64 + (row & 63);
+    const int64_t dst = dst_of[i];
+    if (dst >= 0) {
+        gal4[((size_t)(dst >> 6) * dp4 + c) * 64 + (dst & 63)] = gal4[at];
+        if (c == 0 && cls) cls[dst] = cls[row];
+    }
+    gal4[at] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// tests only (fir_gallery_padding_words_): *count += the non-zero 32-bit words among what the layout invariant says is zero -- rows at
+// or beyond n and features beyond d -- over tiles [0, tiles). One thread per float4.
+__global__ void __launch_bounds__(kBlock) k_count_padding(const float4* __restrict__ gal4, int64_t n, int64_t tiles, int d, int dp4,
+                                                           unsigned long long* __restrict__ count) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= tiles * dp4 * 64) return;
+    const int r = (int)(o & 63);
+    const int64_t tc = o >> 6;
+    const int c = (int)(tc % dp4);
+    const int64_t row = tc / dp4 * kTileRows + r;
+    const float4 g = gal4[o];
+    const uint32_t w[4] = {__float_as_uint(g.x), __float_as_uint(g.y), __float_as_uint(g.z), __float_as_uint(g.w)};
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bad += (row >= n || c * 4 + j >= d) && w[j] != 0u;
+    if (bad) atomicAdd(count, (unsigned long long)bad);
 }
 
 // queries[nq][d] row-major -> tiles of QB queries, transposed: qt[tile][k][QB], k < dp4*4.

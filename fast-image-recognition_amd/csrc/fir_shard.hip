@@ -1123,6 +1123,7 @@ int fir_gallery_create_sharded_ex(const float* rows, int64_t n, int32_t d, const
         if (o.rows_on_device) rc = fir_gallery_create_dev(rows + lo * d, hi - lo, d, class_no ? class_no + lo : nullptr, metric, dev, nullptr, &sh.g);
         else rc = fir_gallery_create(rows + lo * d, hi - lo, d, class_no ? class_no + lo : nullptr, metric, dev, &sh.g);
         if (rc == FIR_OK) rc = fir_gallery_set_row_offset(sh.g, sh.lo);
+        if (rc == FIR_OK) fir_gallery_set_borrowed_(sh.g, 1);      // (fir_sharded_shard lends it: its rows are this handle's bookkeeping)
         if (rc == FIR_OK) {
             fir_gallery_view v;
             fir_gallery_view_(sh.g, &v);

@@ -49,18 +49,21 @@ inline uint64_t mix(uint64_t h, uint64_t v) {
     return h * 0x94D049BB133111EBull + 0x632BE59BD9B4E019ull;
 }
 
-uint64_t signature_of(const std::vector<ImageInfo>& db) {
-    uint64_t h = 0x243F6A8885A308D3ull ^ db.size();
-    for (const ImageInfo& im : db) {
+// (count: the leading rows the value covers -- all of them, or the rows an entry held before push_backs: GalleryCache::appended)
+uint64_t signature_of(const std::vector<ImageInfo>& db, size_t count) {
+    uint64_t h = 0x243F6A8885A308D3ull ^ count;
+    for (size_t j = 0; j < count; ++j) {
+        const ImageInfo& im = db[j];
         h = mix(h, (uint64_t)(uintptr_t)im.features.data());
         h = mix(h, ((uint64_t)im.features.size() << 32) ^ (uint32_t)im.classNo);
     }
     return h;
 }
 
-uint64_t content_of(const std::vector<ImageInfo>& db, int dim) {
+uint64_t content_of(const std::vector<ImageInfo>& db, int dim, size_t count) {
     uint64_t h[4] = {1, 2, 3, 4};                              // four independent lanes: the multiplies overlap
-    for (const ImageInfo& im : db) {
+    for (size_t j = 0; j < count; ++j) {
+        const ImageInfo& im = db[j];
         const size_t have = std::min<size_t>(im.features.size(), (size_t)dim);
         const float* f = im.features.data();
         size_t k = 0;
@@ -81,11 +84,23 @@ void drop(Entry& e) {
     e.s = nullptr;
 }
 
+// rows [first, db.size()) as one row-major block of `dim` floats each (rows shorter than dim are zero padded) and their classes
+void pack_rows(const std::vector<ImageInfo>& db, size_t first, int dim, std::vector<float>& rows, std::vector<int32_t>& cls) {
+    rows.assign((db.size() - first) * (size_t)dim, 0.0f);
+    cls.resize(db.size() - first);
+    for (size_t j = first; j < db.size(); ++j) {
+        const FeaturesVector& f = db[j].features;
+        const size_t have = std::min<size_t>(f.size(), (size_t)dim);
+        std::memcpy(&rows[(j - first) * dim], f.data(), have * sizeof(float));
+        cls[j - first] = db[j].classNo;
+    }
+}
+
 bool sharded_mode() { return g_devices.size() > 1 || g_shards_per_device > 1; }
 
 // The entry for (db, dim) under the current metric / device set, uploaded if it is not there or no longer valid.
 Entry* lookup(const std::vector<ImageInfo>& db, int dim) {
-    const uint64_t sig = signature_of(db);
+    const uint64_t sig = signature_of(db, db.size());
     const auto now = std::chrono::steady_clock::now();
     for (size_t i = 0; i < g_cache.size(); ++i) {
         Entry& e = g_cache[i];
@@ -93,7 +108,7 @@ Entry* lookup(const std::vector<ImageInfo>& db, int dim) {
         bool valid = e.n == db.size() && e.signature == sig;
         if (valid && (g_validation == FIR_CACHE_VALIDATE_ALWAYS ||
                       (g_validation == FIR_CACHE_VALIDATE_THROTTLED && now - e.verified >= std::chrono::milliseconds(20)))) {
-            valid = content_of(db, dim) == e.content;
+            valid = content_of(db, dim, db.size()) == e.content;
             e.verified = std::chrono::steady_clock::now();
         }
         if (valid) return &e;
@@ -103,17 +118,12 @@ Entry* lookup(const std::vector<ImageInfo>& db, int dim) {
     }
     // every other upload of this vector with these features is stale too if the rows changed; uploads of other widths are
     // checked when they are looked up
-    std::vector<float> rows((size_t)db.size() * dim);
-    std::vector<int32_t> cls(db.size());
-    for (size_t j = 0; j < db.size(); ++j) {
-        const FeaturesVector& f = db[j].features;
-        const size_t have = std::min<size_t>(f.size(), (size_t)dim);
-        std::memcpy(&rows[j * dim], f.data(), have * sizeof(float));   // rows shorter than dim are zero padded
-        cls[j] = db[j].classNo;
-    }
+    std::vector<float> rows;
+    std::vector<int32_t> cls;
+    pack_rows(db, 0, dim, rows, cls);
     Entry e;
     e.vec = &db; e.n = db.size(); e.dim = dim; e.metric = g_metric; e.signature = sig;
-    e.content = content_of(db, dim);
+    e.content = content_of(db, dim, db.size());
     e.verified = std::chrono::steady_clock::now();
     if (sharded_mode()) {
         std::vector<int32_t> devs(g_devices.begin(), g_devices.end());
@@ -176,6 +186,32 @@ void GalleryCache::invalidate(const std::vector<ImageInfo>& db) {
     for (size_t i = 0; i < g_cache.size();) {
         if (g_cache[i].vec == (const void*)&db) { drop(g_cache[i]); g_cache.erase(g_cache.begin() + (long)i); } else ++i;
     }
+}
+
+int GalleryCache::appended(const std::vector<ImageInfo>& db, size_t old_n) {
+    int extended = 0;
+    for (size_t i = 0; i < g_cache.size();) {
+        Entry& e = g_cache[i];
+        if (e.vec != (const void*)&db) { ++i; continue; }
+        // in place: a single-device upload of exactly the first old_n rows as they are now (the vector may have reallocated: the views
+        // it holds still point at the same features); anything else is dropped and uploaded again by the next lookup
+        bool ok = e.g && !e.s && e.n == old_n && old_n <= db.size() && e.signature == signature_of(db, old_n) && e.content == content_of(db, e.dim, old_n);
+        if (ok && db.size() > old_n) {
+            std::vector<float> rows;
+            std::vector<int32_t> cls;
+            pack_rows(db, old_n, e.dim, rows, cls);
+            ok = fir_gallery_append(e.g, rows.data(), (int64_t)cls.size(), cls.data()) == FIR_OK;
+            if (!ok) log_error("gallery append");
+        }
+        if (!ok) { drop(e); g_cache.erase(g_cache.begin() + (long)i); continue; }
+        e.n = db.size();
+        e.signature = signature_of(db, db.size());
+        e.content = content_of(db, e.dim, db.size());
+        e.verified = std::chrono::steady_clock::now();
+        ++extended;
+        ++i;
+    }
+    return extended;
 }
 
 void GalleryCache::clear() {

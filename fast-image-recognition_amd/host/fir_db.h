@@ -92,6 +92,11 @@ class GalleryCache {
 public:
     static fir_gallery* get(const std::vector<ImageInfo>& dbImages, int dim);
     static void invalidate(const std::vector<ImageInfo>& dbImages);
+    // Rows [old_n, dbImages.size()) were pushed back onto a vector the cache holds: every single-device upload of it that still
+    // matches the first old_n rows (size, signature, content hash) gets only the new rows (fir_gallery_append) and its size,
+    // signature and hash refreshed; an upload that is sharded, or whose first old_n rows were edited, reordered or relabelled, is
+    // dropped, and the next lookup uploads the whole vector as ever. Returns the number of uploads that were extended in place.
+    static int appended(const std::vector<ImageInfo>& dbImages, size_t old_n);
     static void clear();
 };
 inline void invalidate(const std::vector<ImageInfo>& dbImages) { GalleryCache::invalidate(dbImages); }

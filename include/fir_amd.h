@@ -78,6 +78,59 @@ int fir_gallery_set_metric(fir_gallery* g, int32_t metric);
 /* Row-sharded galleries: global index of this shard's row 0 (added to every reported index). */
 int fir_gallery_set_row_offset(fir_gallery* g, int64_t first_global_row);
 
+/* ---- in-place updates: append, overwrite and remove rows ---------------------------------------
+ * Enrolment, re-enrolment with a better template and removal without a new upload of the gallery. After any sequence of the
+ * calls below the handle answers every call as a handle fresh from fir_gallery_create over the array the sequence describes
+ * would: the same indices, distance bits, keys, counts, classes and thresholds, for every metric and feature range, in the scan
+ * forms and in the routed matrix-core forms. The handle's settings (metric, row offset, tuning, large_batch_mfma, int8 mode,
+ * shadow mode, profiling) survive. Two things may read differently from a fresh handle, neither changes an answer:
+ * fir_gallery_value_range's gallery_plain is sticky (a value outside the plain range that was overwritten or removed since
+ * keeps the full division sequence: the same bits), and the warm-up / learnt-dispatch counters of the automatic matrix-core
+ * dispatch start again with every mutation.
+ *   Indices are LOCAL rows (as in fir_rows_distances: without the row offset); n + m + row offset must stay below 2^31 - 64.
+ *   Labels: a handle with labels requires class_no on append, a handle without refuses it (FIR_ERR_ARG either way); an empty
+ * handle (n == 0) takes its labelled-ness from its first append; any int32 is a label.
+ *   Checks: NULL, m < 0, m == 0 (nothing to do), labels, index range and duplicates, the 32-bit limit -- before anything is
+ * allocated or queued. A call that returns FIR_ERR_ARG, FIR_ERR_STATE or FIR_ERR_NOMEM leaves rows, labels, n, capacity and
+ * every answer as they were. A shard lent by fir_sharded_shard refuses every mutation with FIR_ERR_STATE.
+ *   Order: a mutation is a call on the handle in the sense of "Streams" below: it takes effect in call order whatever stream each
+ * call was given. The host-pointer calls return when the change is in place.
+ *   Derived state: what the handle caches about its rows (matrix-core states with their fp16 / int8 / row-major copies, row sums,
+ * the label range) is dropped and rebuilt by the next call that wants it: the first routed call after a mutation pays for the
+ * copies again (1M x 512, 1 024 queries: 4.2 ms against 1.0 ms in steady state, the cost of a fresh handle's first call). States the CALLER made over the handle (fir_gemm_create*, fir_dem_create) are not rebuilt: every
+ * search / recognize / likelihood call on them returns FIR_ERR_STATE ("the gallery changed after this ... state was built")
+ * without queueing anything; destroy them and create them again.
+ *   Cost: with room reserved an append moves O(m d) bytes and allocates nothing proportional to n; set_rows and remove_rows move
+ * O(m d) bytes. When n + m exceeds the capacity the buffers grow to n + m plus a quarter of headroom in whole 64-row tiles
+ * (the exact size when the headroom cannot be had, then FIR_ERR_NOMEM): the call first waits for the handle's queued calls,
+ * allocates the new buffers, copies on the device and frees the old ones -- old and new buffers exist side by side for that
+ * moment. fir_gallery_memory_bytes' `tiled` reports the allocated capacity. Measured (profiles/gallery_update.txt; whole
+ * host-pointer calls, 512 features, labelled): appending 64 / 4 096 / 65 536 rows with room reserved 0.09 / 0.23 / 2.6 ms at 100 000
+ * and at 1M rows (destroy + create of n + m rows: 39 - 42 ms at 1M, 4.6 - 7.1 ms at 100 000), 1.6 / 1.8 / 4.1 ms when the 1M-row
+ * buffers have to grow; set_rows 0.12 / 0.38 ms and remove_rows 0.05 / 0.21 ms for 64 / 4 096 rows at 1M.
+ *
+ * fir_gallery_reserve: room for at least `rows` rows (and their labels on a labelled handle) without another allocation; never
+ * shrinks; rows <= n is a no-op. fir_gallery_capacity: *rows <- the rows the handle holds room for. */
+int fir_gallery_reserve(fir_gallery* g, int64_t rows);
+int fir_gallery_capacity(const fir_gallery* g, int64_t* rows);
+/* rows[m][d] (class_no[m]) become gallery rows n .. n + m - 1, n grows by m. The _dev form reads d_rows / d_class_no on `stream`
+ * and is asynchronous; once the capacity is there and the handle's labelled-ness is settled it never synchronises. */
+int fir_gallery_append(fir_gallery* g, const float* rows, int64_t m, const int32_t* class_no);
+int fir_gallery_append_dev(fir_gallery* g, const float* d_rows, int64_t m, const int32_t* d_class_no, void* stream);
+/* Rows row_idx[i] (distinct, < n) take the values new_rows[i][d]; class_no NULL keeps their labels (a handle without labels
+ * refuses class_no). */
+int fir_gallery_set_rows(fir_gallery* g, const int32_t* row_idx, int32_t m, const float* new_rows, const int32_t* class_no);
+/* Swap-remove of the m distinct rows row_idx, deterministic: n' = n - m; the holes are the removed rows below n', ascending; the
+ * survivors are the rows of [n', n) that are not removed, ascending (as many as holes); the j-th hole receives the j-th survivor,
+ * features and label; every other row keeps its index. moved_from[m] (may be NULL): the former row now at row_idx[i], -1 when
+ * row_idx[i] >= n'. fir_gallery_remove_plan is the rule alone -- pure integer work on the host, no device (like
+ * fir_keys_unpack) -- with the argument checks: an index outside [0, n), a duplicate, m < 0 give FIR_ERR_ARG. */
+int fir_gallery_remove_rows(fir_gallery* g, const int32_t* row_idx, int32_t m, int32_t* moved_from);
+int fir_gallery_remove_plan(int64_t n, const int32_t* row_idx, int32_t m, int32_t* moved_from);
+/* Rows row0 .. row0 + m - 1 back in row-major form, rows_out[m][d], and their labels (class_out[m], may be NULL; FIR_ERR_STATE when
+ * asked for labels the handle does not have). */
+int fir_gallery_read_rows(fir_gallery* g, int64_t row0, int64_t m, float* rows_out, int32_t* class_out);
+
 /* ---- single pair ----------------------------------------------------------------------------
  * feature_distance(lhs, rhs, start_pos, end_pos), db_features.cpp:22-42 (ImageInfo::distance,
  * db_features.h:24). len = number of floats in each vector. Computed on the device. */
@@ -102,7 +155,11 @@ int fir_search_top1(fir_gallery* g, const float* queries, int32_t qb, int32_t st
  * makes `stream` wait for whatever produced the queries, and waits for `stream` (or fir_gallery_sync) before reading the keys.
  * fir_gallery_sync, fir_gallery_destroy, fir_gemm_destroy, and the settings that free a matrix-core state
  * (fir_gallery_set_large_batch_mfma(g, 0), fir_gallery_set_shadow_copies, fir_gallery_set_row_offset) first wait on the host
- * for the handle's most recent call.
+ * for the handle's most recent call; so do the in-place updates above that take host pointers, and any of them that has to grow
+ * the handle's buffers (fir_gallery_append_dev with room reserved does not wait). After fir_gallery_append_dev the NEXT chi-square
+ * / KL search on the handle, its *_keys_dev forms included, synchronises its `stream` once: it has to read whether an appended value
+ * left the plain range before it picks its form (the host-pointer updates read that themselves; a growth alone changes no value
+ * and causes no such wait).
  *
  * Device-resident form. d_keys[qb] receives one packed key per query:
  *   (orderable(float bits of distance) << 32) | uint32(row index + row offset),
@@ -513,7 +570,9 @@ int fir_dem_pivot_table(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, i
                         float* min_other_out, int32_t* n_built_out);
 
 /* The same build kept on the device for query time: the table rows of the first min(n_built, 32) pivots
- * (ann.cpp:333-334 keeps 32) and those pivots as a small gallery of their own. The gallery handle must outlive it. */
+ * (ann.cpp:333-334 keeps 32) and those pivots as a small gallery of their own. The gallery handle must outlive it, and stay
+ * as it is: after fir_gallery_append / _set_rows / _remove_rows / a growth, fir_dem_likelihoods and fir_dem_recognize(_dev) return
+ * FIR_ERR_STATE (destroy, info and get keep working). */
 typedef struct fir_dem fir_dem;
 int fir_dem_create(fir_gallery* g, int32_t first_pivot, int32_t n_pivots, fir_dem** out);
 int fir_dem_destroy(fir_dem* h);
@@ -577,7 +636,9 @@ enum {
  * return FIR_ERR_ARG. FIR_GEMM_F16 also wants a device whose compute-unit count is a multiple of 8 and at least 8 (its kernels
  * place the readers of one row range on one XCD): anything else returns FIR_ERR_ARG -- no gfx950 partition mode has such a count,
  * and gfx950 is the only device fir_gallery_create accepts. In both cases the search entry points that create this state by
- * themselves keep the exact streaming scan for the gallery (automatic mode; an explicit fir_gallery_set_large_batch_mfma threshold gets the error). */
+ * themselves keep the exact streaming scan for the gallery (automatic mode; an explicit fir_gallery_set_large_batch_mfma threshold gets the error).
+ * A state is built over the gallery's rows as they are: after an in-place update of the gallery (fir_gallery_append ...) every
+ * fir_gemm_search_* call on it returns FIR_ERR_STATE before queueing anything; fir_gemm_destroy and fir_gemm_stats* keep working. */
 int fir_gemm_create(fir_gallery* g, fir_gemm** out);   /* = fir_gemm_create_ex(g, FIR_GEMM_F16, out) */
 int fir_gemm_create_ex(fir_gallery* g, int32_t precision, fir_gemm** out);
 /* ... over a feature prefix [0, end_pos) of every row (0 or d: the whole row): end_pos a multiple of 16, FIR_GEMM_F16 only.
