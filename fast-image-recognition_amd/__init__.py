@@ -32,5 +32,7 @@ from .capi import (  # noqa: F401
     keys_unpack,
     lib,
     lib_path,
+    mask_words,
+    pack_row_mask,
     remove_plan,
 )

@@ -66,6 +66,16 @@ SYMBOLS = [
     ("fir_search_radius_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top1_other_class", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_search_top1_other_class_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top1_masked", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top1_masked_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_knn_masked", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    ("fir_search_knn_masked_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp]),
+    ("fir_search_radius_masked", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_radius_masked_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top_classes_masked", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_search_top_classes_masked_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    ("fir_gallery_mask_of_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
+    ("fir_gallery_mask_of_classes_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gallery_other_class_keys_dev", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gallery_other_class", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gallery_far_threshold", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp]),
@@ -240,6 +250,19 @@ def class_keys_merge(keys, classes, k):
     _check(lib().fir_class_keys_merge(keys.ctypes.data_as(_vp), classes.ctypes.data_as(_vp), parts, qb, k, keys_out.ctypes.data_as(_vp),
                                       classes_out.ctypes.data_as(_vp)))
     return keys_out, classes_out
+
+
+def mask_words(n):
+    """FIR_MASK_WORDS(n): the 64-bit words of a row mask over n rows."""
+    return (int(n) + 63) // 64
+
+
+def pack_row_mask(take):
+    """bool[n] -> uint64[FIR_MASK_WORDS(n)]: row r takes part iff bit r & 63 of word r >> 6 is set; the bits past n are zero."""
+    take = np.asarray(take).astype(bool).reshape(-1)
+    bits = np.zeros(mask_words(take.size) * 64, np.uint8)
+    bits[:take.size] = take
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u8").astype(np.uint64))
 
 
 def remove_plan(n, row_idx):
@@ -488,6 +511,99 @@ class Gallery:
     def search_top1_other_class_keys_dev(self, q_ptr, qb, exclude_ptr, keys_ptr, start=0, end=0, stream=None):
         _check(lib().fir_search_top1_other_class_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(exclude_ptr) if exclude_ptr else None,
                                                           _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
+    # ---- searches over a subset of the rows (include/fir_amd.h). mask: bool[n], or the packed uint64 words of pack_row_mask ----
+    def _mask(self, mask):
+        if mask is None:
+            return None, None
+        m = np.asarray(mask)
+        if m.dtype == np.bool_:
+            if m.size != self.n:
+                raise ValueError(f"a bool mask over {self.n} rows has {self.n} entries, got {m.size}")
+            m = pack_row_mask(m)
+        else:
+            m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
+        if m.size != mask_words(self.n):
+            raise ValueError(f"a packed mask over {self.n} rows has {mask_words(self.n)} words, got {m.size}")
+        return m, m.ctypes.data_as(_vp)
+
+    def search_top1_masked(self, queries, mask, start=0, end=0):
+        """search_top1 over the rows of the mask: (idx, dist), each [qb]; -1 / 100000 where no row qualifies."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        m, pm = self._mask(mask)
+        idx = np.empty(q.shape[0], np.int32)
+        dist = np.empty(q.shape[0], np.float32)
+        _check(lib().fir_search_top1_masked(self._h, pq, q.shape[0], start, end, pm, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_top1_masked_keys_dev(self, q_ptr, qb, mask_ptr, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_top1_masked_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(mask_ptr) if mask_ptr else None,
+                                                     _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
+    def search_knn_masked(self, queries, mask, k, start=0, end=0):
+        """search_knn over the rows of the mask: (idx, dist), each [qb, k]."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        m, pm = self._mask(mask)
+        idx = np.empty((q.shape[0], max(k, 0)), np.int32)
+        dist = np.empty((q.shape[0], max(k, 0)), np.float32)
+        _check(lib().fir_search_knn_masked(self._h, pq, q.shape[0], start, end, pm, k, idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return idx, dist
+
+    def search_knn_masked_keys_dev(self, q_ptr, qb, mask_ptr, k, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_knn_masked_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(mask_ptr) if mask_ptr else None, k,
+                                                    _vp(keys_ptr) if keys_ptr else None, _vp(stream) if stream else None))
+
+    def search_radius_masked(self, queries, mask, radius, max_results, start=0, end=0):
+        """search_radius over the rows of the mask: (count, idx, dist); the counts count masked-in rows only."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        qb = q.shape[0]
+        m, pm = self._mask(mask)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32).reshape(-1), (qb,)))
+        count = np.empty(qb, np.int32)
+        idx = np.empty((qb, max_results), np.int32) if max_results > 0 else None
+        dist = np.empty((qb, max_results), np.float32) if max_results > 0 else None
+        _check(lib().fir_search_radius_masked(self._h, pq, qb, start, end, pm, r.ctypes.data_as(_vp), max_results, count.ctypes.data_as(_vp),
+                                              idx.ctypes.data_as(_vp) if idx is not None else None,
+                                              dist.ctypes.data_as(_vp) if dist is not None else None))
+        return count, idx, dist
+
+    def search_radius_masked_keys_dev(self, q_ptr, qb, mask_ptr, radius_ptr, max_results, count_ptr, keys_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_radius_masked_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(mask_ptr) if mask_ptr else None, _vp(radius_ptr),
+                                                       max_results, _vp(count_ptr), _vp(keys_ptr) if keys_ptr else None,
+                                                       _vp(stream) if stream else None))
+
+    def search_top_classes_masked(self, queries, mask, num_classes, k, start=0, end=0):
+        """search_top_classes over the rows of the mask: (classes, idx, dist), each [qb, k]; a class with no masked-in row does not appear."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.d)
+        m, pm = self._mask(mask)
+        cls = np.empty((q.shape[0], max(k, 0)), np.int32)
+        idx = np.empty((q.shape[0], max(k, 0)), np.int32)
+        dist = np.empty((q.shape[0], max(k, 0)), np.float32)
+        _check(lib().fir_search_top_classes_masked(self._h, pq, q.shape[0], start, end, pm, num_classes, k, cls.ctypes.data_as(_vp),
+                                                   idx.ctypes.data_as(_vp), dist.ctypes.data_as(_vp)))
+        return cls, idx, dist
+
+    def search_top_classes_masked_keys_dev(self, q_ptr, qb, mask_ptr, num_classes, k, keys_ptr, classes_ptr, start=0, end=0, stream=None):
+        _check(lib().fir_search_top_classes_masked_keys_dev(self._h, _vp(q_ptr), qb, start, end, _vp(mask_ptr) if mask_ptr else None, num_classes, k,
+                                                            _vp(keys_ptr) if keys_ptr else None, _vp(classes_ptr) if classes_ptr else None,
+                                                            _vp(stream) if stream else None))
+
+    def mask_of_classes(self, classes, invert=False):
+        """The packed mask of the rows whose class is (invert: is not) one of `classes` (any int32 values, any order): uint64[FIR_MASK_WORDS(n)]."""
+        c = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+        out = np.zeros(mask_words(self.n), np.uint64)
+        _check(lib().fir_gallery_mask_of_classes(self._h, c.ctypes.data_as(_vp) if c.size else None, c.size, 1 if invert else 0,
+                                                 out.ctypes.data_as(_vp) if out.size else None))
+        return out
+
+    def mask_of_classes_dev(self, classes_ptr, m, mask_ptr, invert=False, stream=None):
+        """... on the device: classes_ptr -> m ascending int32 (duplicates allowed), mask_ptr -> FIR_MASK_WORDS(n) words; asynchronous."""
+        _check(lib().fir_gallery_mask_of_classes_dev(self._h, _vp(classes_ptr) if classes_ptr else None, m, 1 if invert else 0,
+                                                     _vp(mask_ptr) if mask_ptr else None, _vp(stream) if stream else None))
 
     def other_class(self, start=0, end=0):
         """Every row of the gallery against the gallery with its own class excluded (row i is the query): (idx, dist), each [n];

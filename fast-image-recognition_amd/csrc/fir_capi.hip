@@ -95,10 +95,13 @@ struct fir_gallery {
     GalleryBuf<float> selfq;
     GalleryBuf<uint64_t> selfkeys;
     GalleryBuf<float> fardist;
+    // the masked searches: a host call's mask words; fir_gallery_mask_of_classes' sorted class list, and behind it room for the words it returns
+    GalleryBuf<uint64_t> dmask;
+    GalleryBuf<uint64_t> mclasses;
     FirBuf scratch[25];
     size_t scratch_bytes() const {
         size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap + excl.cap + okeys.cap + ocls.cap + selfq.cap +
-                     selfkeys.cap + fardist.cap;
+                     selfkeys.cap + fardist.cap + dmask.cap + mclasses.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
         return sum;
     }
@@ -189,7 +192,8 @@ typedef void (*scan_fn)(const ScanArgs);
 //   epilogue   0 top-1, 1 top-K, 2 store, 3 append, 5 class minimum, 6 top-1 over the other classes
 //   KMAX       kKMax
 //   waves per SIMD   kWps; kWpsPlain for the metrics from 3 on
-enum ScanKind { kGeneric, kDeep, kL2Lds, kL2Scalar, kNominate, kSubranges };
+//   LDSQ, MASKED     1 = the query tile staged in LDS (the few-tiles form); 1 = only the rows of a mask take part (kMasked rows)
+enum ScanKind { kGeneric, kDeep, kL2Lds, kL2Scalar, kNominate, kSubranges, kMasked };
 constexpr int kEpiSubranges = 4;   // selector only: k_scan_subranges (one stored distance per sub-range)
 static_assert(kEpiTop1 == 0 && kEpiTopK == 1 && kEpiStore == 2 && kEpiAppend == 3 && kEpiClassMin == 5 && kEpiTop1Other == 6 && kL2 == 0 && kChi2 == 1 && kKL == 2 && kChi2InRange == 3 &&
                   kKLInRange == 4 && kChi2Approx == 5 && kChi2Harm == 6 && kKLEnt == 7 && kU == 8 && kUDeep == 16 && kUSub == 8 && kKMax == 8 && kWps == 4 && kWpsPlain == 3,
@@ -198,6 +202,8 @@ struct ScanRow { int kind, epi, qb, metric; scan_fn fn; const char* name; };
 #define FIR_ROW(KIND, EPI, QB, M, KERNEL, ...) {KIND, EPI, QB, M, (scan_fn)KERNEL<__VA_ARGS__>, "fir::" #KERNEL "<" #__VA_ARGS__ ">"},
 #define FIR_SCAN(EPI, QB, M, WPS) FIR_ROW(kGeneric, EPI, QB, M, k_scan, QB, M, 8, EPI, 8, WPS, 0)
 #define FIR_SCAN_M(EPI, QB) FIR_SCAN(EPI, QB, 0, 4) FIR_SCAN(EPI, QB, 1, 4) FIR_SCAN(EPI, QB, 2, 4) FIR_SCAN(EPI, QB, 3, 3) FIR_SCAN(EPI, QB, 4, 3)
+#define FIR_MASKED(EPI, QB, M, WPS) FIR_ROW(kMasked, EPI, QB, M, k_scan, QB, M, 8, EPI, 8, WPS, 0, 1)
+#define FIR_MASKED_M(EPI, QB) FIR_MASKED(EPI, QB, 0, 4) FIR_MASKED(EPI, QB, 1, 4) FIR_MASKED(EPI, QB, 2, 4) FIR_MASKED(EPI, QB, 3, 3) FIR_MASKED(EPI, QB, 4, 3)
 #define FIR_DEEP(EPI, M, WPS) FIR_ROW(kDeep, EPI, 1, M, k_scan, 1, M, 16, EPI, 8, WPS, 1)
 #define FIR_APPEND(M, WPS) FIR_ROW(kGeneric, 3, 8, M, k_scan, 8, M, 8, 3, 8, WPS)
 #define FIR_SUB(QB) FIR_ROW(kSubranges, 4, QB, 0, k_scan_subranges, QB, 0, 8, 4) FIR_ROW(kSubranges, 4, QB, 1, k_scan_subranges, QB, 1, 8, 4) \
@@ -227,11 +233,18 @@ static const ScanRow kScanTable[] = {
     // other_class_dev: top-1 over the rows of another class, the tile sizes and the few-tiles form of the generic top-1 scan
     FIR_DEEP(6, 0, 4) FIR_DEEP(6, 1, 4) FIR_DEEP(6, 2, 4) FIR_DEEP(6, 3, 3) FIR_DEEP(6, 4, 3)
     FIR_SCAN_M(6, 1) FIR_SCAN_M(6, 2) FIR_SCAN_M(6, 4) FIR_SCAN_M(6, 8)
+    // the masked searches (masked_top1_dev, knn_dev, top_classes_dev with a mask): the generic scan's top-1, store and class-minimum
+    // forms over the rows of a mask; no few-tiles form -- a one-query masked call on a small gallery takes these
+    FIR_MASKED_M(0, 1) FIR_MASKED_M(0, 2) FIR_MASKED_M(0, 4) FIR_MASKED_M(0, 8)
+    FIR_MASKED_M(2, 1) FIR_MASKED_M(2, 2) FIR_MASKED_M(2, 4) FIR_MASKED_M(2, 8)
+    FIR_MASKED_M(5, 8)
 };
 #undef FIR_ROW
 #undef FIR_SCAN
 #undef FIR_SCAN_M
 #undef FIR_DEEP
+#undef FIR_MASKED
+#undef FIR_MASKED_M
 #undef FIR_APPEND
 #undef FIR_SUB
 
@@ -248,15 +261,17 @@ struct ScanKernel { scan_fn fn = nullptr, fn_plain = nullptr; const char* name =
 constexpr size_t kMaxQueryTileLds = 144 * 1024;   // of the CU's 160 KiB; one workgroup per CU above 80 KiB (above 64 KiB the launch opts in: run_pass)
 // whole_chunks: start and end are multiples of 4 features; few_tiles: no more tiles than SIMDs (one-query tiles then take the
 // 16-chunk form when the query fits 64 KiB of LDS). The append epilogue with 16 queries is the two-tiles-per-read nomination scan.
-ScanKernel select_scan(int epi, int qb, int metric, bool whole_chunks, int dp4, bool few_tiles) {
-    const bool l2_hand = metric == kL2 && whole_chunks && (epi == kEpiTop1 || epi == kEpiAppend);
+// masked: the kMasked row of the shape and nothing else -- neither the hand-scheduled L2 kernels nor the few-tiles form has one.
+ScanKernel select_scan(int epi, int qb, int metric, bool whole_chunks, int dp4, bool few_tiles, bool masked = false) {
+    const bool l2_hand = !masked && metric == kL2 && whole_chunks && (epi == kEpiTop1 || epi == kEpiAppend);
     const size_t tile = (size_t)(dp4 + 1) * qb * 16;                       // query tile + one zero chunk of slack
     const size_t tile_max = epi == kEpiAppend ? 64 * 1024 : kMaxQueryTileLds;
     const size_t deep_tile = (size_t)dp4 * 4 * qb * sizeof(float);
     const size_t deep_extra = epi == kEpiTop1Other ? 16 : 0;               // the excluded classes behind the staged tile
     ScanKernel k;
     const ScanRow* r = nullptr;
-    if (epi == kEpiSubranges) r = scan_row(kSubranges, epi, qb, metric);
+    if (masked) r = scan_row(kMasked, epi, qb, metric);
+    else if (epi == kEpiSubranges) r = scan_row(kSubranges, epi, qb, metric);
     else if (l2_hand && tile <= tile_max && (r = scan_row(kL2Lds, epi, qb, metric))) k.lds_bytes = tile;
     else if (l2_hand && (r = scan_row(kL2Scalar, epi, qb, metric))) k.lds_bytes = 0;
     else if (few_tiles && deep_tile + deep_extra <= 64 * 1024 && (r = scan_row(kDeep, epi, qb, metric))) k.lds_bytes = deep_tile + deep_extra;
@@ -469,7 +484,8 @@ struct ClassPass { const float* tau; int32_t num_classes; int32_t nq; bool tiles
 // Queue: transpose (+ key init) of one query tile, then one gallery pass.
 int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, const float* d_queries, int q0, int qb_tile, int32_t start,
              int32_t end, uint64_t* keys, float* out, int64_t out_stride, int k, int* waves_used = nullptr, int ny = 1,
-             int init_keys = 0, const ClassPass* cp = nullptr, int live = 0, const int32_t* excl = nullptr) {
+             int init_keys = 0, const ClassPass* cp = nullptr, int live = 0, const int32_t* excl = nullptr, const uint64_t* mask = nullptr) {
+    // mask != NULL (top-1, store and class-minimum epilogues): the masked form of the scan over the rows whose bit is set (word 0 = local tile 0)
     // ny > 1 (top-1 kernels, the class-minimum scan and the store scan only): ny consecutive query tiles of qb_tile queries in ONE launch;
     // live > 0 (the store scan): the launch's live queries, the last tile may be part full -- query y * qb_tile + q goes to out + that * out_stride
     const int kk = g->dp4 * 4;
@@ -480,7 +496,7 @@ int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, co
         hipLaunchKernelGGL(k_transpose_queries, dim3(blocks), dim3(kBlock), 0, st, d_queries + (size_t)q0 * g->d, cp ? cp->nq : live > 0 ? live : qb_tile * ny,
                            g->d, g->dp4, qb_tile, qt, init_keys > 0 ? keys : nullptr, init_keys, g->range, next_serial(g));
     }
-    const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g));
+    const ScanKernel sk = select_scan(epi, qb_tile, g->metric, whole_chunks(start, end), g->dp4, few_tiles(g), mask != nullptr);
     if (!sk.fn) return fir_fail_(FIR_ERR_ARG, "no kernel for qb=%d metric=%d", qb_tile, g->metric);
     if (sk.lds_bytes > 64 * 1024) {   // more than the default dynamic LDS limit: opt in once per kernel
         bool known = false;
@@ -506,13 +522,15 @@ int run_pass(fir_gallery* g, hipStream_t st, const ScanScope& scope, int epi, co
     a.range = g->range;
     a.serial = g->q_serial;
     a.excl = excl;                  // kEpiTop1Other: the tile-padded excluded classes of this launch's first query
+    a.mask = mask ? mask + (scope.tiles > 0 ? std::min<int64_t>(scope.tile_begin, g->tiles) : 0) : nullptr;      // the scope's window of the words, as scan_args takes the tiles'
     if (cp) {
         a.tau = cp->tau;
         a.num_classes = cp->num_classes;
         a.nq = cp->nq;
     }
     // algorithmic bytes of one launch: per pass the gallery range once (the class-minimum scan: and a label per row), the query tile, the keys
-    const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp || excl ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0);
+    // (a masked pass: the unmasked figure plus the mask words -- how many tiles a device mask lets the scan skip is not known here)
+    const double bytes_alg = ny * ((double)a.n * ((end - start) * 4.0 + (cp || excl ? 4.0 : 0.0)) + (double)qb_tile * (end - start) * 4.0 + qb_tile * 8.0 + (mask ? a.tiles * 8.0 : 0.0));
     int rc;
     if (!scope.quiet && (rc = fir_gallery_profile_begin_(g, st))) return rc;
     hipLaunchKernelGGL(sk.fn, dim3(waves / 4, ny), dim3(kBlock), sk.lds_bytes, st, a);
@@ -888,7 +906,9 @@ constexpr int64_t kClassSampleFromTiles = 128;
 // Of `scope` only quiet is the caller's: the windows of the sample and of the remainder are made here.
 int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, int32_t num_classes, int32_t k,
                     uint64_t* d_keys, int32_t* d_classes, hipStream_t st, const ScanScope& scope = {}, int64_t bound_tiles = 0,
-                    float* d_bound = nullptr) {
+                    float* d_bound = nullptr, const uint64_t* mask = nullptr) {
+    // mask: both scans take their masked form -- the sample's bound is then the K-th smallest minimum over masked-in rows of the sample,
+    // an upper bound of the masked answer's K-th class minimum for the same reason
     if (g->n == 0) {                                             // no row: every slot unused (kKeyNone, class -1)
         if (d_keys) FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * k * sizeof(uint64_t), st));
         if (d_classes) FIR_HIP(hipMemsetAsync(d_classes, 0xFF, (size_t)qb * k * sizeof(int32_t), st));
@@ -916,14 +936,14 @@ int top_classes_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t 
         FIR_HIP(hipMemsetAsync(table, 0xFF, tile_bytes * ny, st));
         ClassPass cp{nullptr, num_classes, nq, false};
         if (sample_tiles > 0) {
-            if ((rc = run_pass(g, st, sample, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
+            if ((rc = run_pass(g, st, sample, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp, 0, nullptr, mask))) return rc;
             hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, (uint64_t*)nullptr, (int32_t*)nullptr,
                                bound_tiles > 0 ? d_bound + q0 : tau);
             if (bound_tiles > 0) { FIR_HIP(hipGetLastError()); continue; }
             cp.tau = tau;
             cp.tiles_ready = true;
         }
-        if ((rc = run_pass(g, st, rest, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp))) return rc;
+        if ((rc = run_pass(g, st, rest, kEpiClassMin, d_queries, q0, 8, start, end, table, nullptr, 0, k, nullptr, ny, 0, &cp, 0, nullptr, mask))) return rc;
         hipLaunchKernelGGL(k_class_select, dim3(nq), dim3(kBlock), 0, st, table, num_classes, k, d_keys ? d_keys + (size_t)q0 * k : nullptr,
                            d_classes ? d_classes + (size_t)q0 * k : nullptr, (float*)nullptr);
         FIR_HIP(hipGetLastError());
@@ -986,9 +1006,10 @@ int knn_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, i
     for (int q0 = 0; q0 < qb;) {
         const int tt = largest_pow2_le(qb - q0, t);
         if ((rc = fir_gallery_profile_begin_(g, st))) return rc;
-        rc = run_pass(g, st, kOnBehalf, kEpiStore, d_queries + (size_t)q0 * g->d, 0, tt, start, end, nullptr, dist, plan.row_stride, 0);
+        // s.mask: the masked store pass -- masked-out rows are stored as 100000, which count and select reject like any row that far
+        rc = run_pass(g, st, kOnBehalf, kEpiStore, d_queries + (size_t)q0 * g->d, 0, tt, start, end, nullptr, dist, plan.row_stride, 0, nullptr, 1, 0, nullptr, 0, nullptr, s.mask);
         if (rc) return rc;
-        if ((rc = fir_gallery_profile_end_(g, st, (double)g->n * (end - start) * 4.0))) return rc;
+        if ((rc = fir_gallery_profile_end_(g, st, (double)g->n * (end - start) * 4.0 + (s.mask ? g->tiles * 8.0 : 0.0)))) return rc;
         KnnArgs a{};
         a.dist = dist;
         a.n = g->n;
@@ -2378,7 +2399,10 @@ int fir_search_topk(fir_gallery* g, const float* queries, int32_t qb, int32_t st
 namespace {
 // The host-pointer body of fir_search_knn, fir_search_radius and fir_search_top_classes, arguments checked. `s` names the kind, K and num_classes; its device
 // pointers are made here, in the handle's buffers (behind the keys' slots the counts out, then the radii in). Matrix cores, else the kind's exact form.
-struct HostOut { int32_t* idx; float* dist; int32_t* class_out = nullptr; const float* radius = nullptr; int32_t* count = nullptr; const int32_t* exclude = nullptr; };
+struct HostOut {
+    int32_t* idx; float* dist; int32_t* class_out = nullptr; const float* radius = nullptr; int32_t* count = nullptr; const int32_t* exclude = nullptr;
+    bool masked = false;      // a masked call: the request's mask is a HOST pointer (NULL only over an empty gallery) and the exact scan form answers
+};
 
 // ---- the nearest row of another class (fir_search_top1_other_class): the scan form -------------------------------------------
 // top1_dev's passes with the kEpiTop1Other epilogue: tiles of 8, 4, 2, 1 queries (the generic scan's; a 16-query tile exists only in
@@ -2435,6 +2459,34 @@ int other_class_routed(fir_gallery* g, const float* d_queries, int32_t qb, int32
     FIR_HIP(hipGetLastError());
     return FIR_OK;
 }
+// ---- the nearest row among the rows of a mask (fir_search_top1_masked): the scan form, the only one --------------------------------
+// top1_dev's passes with the masked form of the generic top-1 scan: tiles of 8, 4, 2, 1 queries, all the whole tiles of one size in
+// one launch. No nomination lists, no matrix cores, no hand-scheduled kernel: none of them has a masked form, and this function asks
+// for none (as other_class_dev does not). Nothing synchronises once the scratch is large enough.
+int masked_top1_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start, int32_t end, const uint64_t* d_mask, uint64_t* d_keys,
+                    hipStream_t st) {
+    if (g->n == 0) {                                             // no row: FIR_KEY_NONE (all bytes 0xFF); the mask is not read
+        FIR_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)qb * sizeof(uint64_t), st));
+        return FIR_OK;
+    }
+    int rc;
+    if ((rc = FIR_NEED(g->qt, (size_t)qb * g->dp4 * 4 + 64))) return rc;
+    // chi-square / KL, automatic tuning: tiles of 4, as other_class_dev -- the 8-query plain-range forms keep 232-318 vector registers in
+    // scratch with this epilogue (their unmasked siblings 8-78, the 4-query forms none), and those scans wait for the vector pipes
+    const int cap = top1_qpp(g, {}, qb, std::min(effective_qpp(g), g->metric != kL2 && g->qpp == 0 ? 4 : 8));
+    int q0 = 0;
+    while (q0 < qb) {
+        const int t = largest_pow2_le(qb - q0, cap);
+        const int ny = std::min((qb - q0) / t, g->max_tiles_per_launch);
+        rc = run_pass(g, st, {}, kEpiTop1, d_queries, q0, t, start, end, d_keys + q0, nullptr, 0, 0, nullptr, ny, /*init_keys=*/t * ny, nullptr, 0, nullptr, d_mask);
+        if (rc) return rc;
+        q0 += t * ny;
+    }
+    return FIR_OK;
+}
+// A masked entry point's mask among its NULL checks: required unless the gallery is empty (it is then not read)
+bool mask_ok(const fir_gallery* g, const void* mask) { return !g || mask != nullptr || g->n == 0; }
+
 int search_host(fir_gallery* g, const float* queries, int32_t qb, int32_t start, int32_t end, FirSearch s, const HostOut& out) {
     GalleryCall call(g);
     if (call.rc) return call.rc;
@@ -2457,13 +2509,24 @@ int search_host(fir_gallery* g, const float* queries, int32_t qb, int32_t start,
         s.exclude = (const int32_t*)(base + s.status_index(qb));
         FIR_HIP(hipMemcpyAsync((void*)s.exclude, out.exclude, (size_t)qb * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
     }
+    if (out.masked) {                                            // the mask words into the handle's scratch (an empty gallery has none)
+        const uint64_t* host_mask = s.mask;
+        s.mask = nullptr;
+        if (g->n > 0) {
+            if ((rc = FIR_NEED(g->dmask, (size_t)g->tiles))) return rc;
+            FIR_HIP(hipMemcpyAsync(g->dmask, host_mask, (size_t)g->tiles * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
+            s.mask = g->dmask;
+        }
+    }
     g->call_launches = 0;
     g->warm_left = 0;
-    rc = other ? other_class_routed(g, g->dq, qb, start, end, s.exclude, s.keys, g->stream) : try_mfma_search(g, g->dq, qb, start, end, s, g->stream);
+    // (a masked call is never routed: no matrix-core pass reads a mask)
+    rc = out.masked ? 1 : other ? other_class_routed(g, g->dq, qb, start, end, s.exclude, s.keys, g->stream) : try_mfma_search(g, g->dq, qb, start, end, s, g->stream);
     if (rc > 0)
-        rc = classes ? top_classes_dev(g, g->dq, qb, start, end, s.num_classes, s.k, s.keys, s.classes, g->stream)
+        rc = classes ? top_classes_dev(g, g->dq, qb, start, end, s.num_classes, s.k, s.keys, s.classes, g->stream, {}, 0, nullptr, s.mask)
              : other ? other_class_dev(g, g->dq, qb, start, end, s.exclude, s.keys, g->stream)
-                     : knn_dev(g, g->dq, qb, start, end, s, g->stream);
+             : s.kind == kSearchRows ? masked_top1_dev(g, g->dq, qb, start, end, s.mask, s.keys, g->stream)      // (only the masked top-1 call comes here as kSearchRows)
+                                     : knn_dev(g, g->dq, qb, start, end, s, g->stream);
     if (rc) return rc;
     if (s.is_radius()) FIR_HIP(hipMemcpyAsync(out.count, s.count, (size_t)qb * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     return deliver_copied(g, call, slots, out.class_out, out.idx, out.dist);
@@ -2511,8 +2574,9 @@ int fir_search_radius(fir_gallery* g, const float* queries, int32_t qb, int32_t 
 namespace {
 // check_search for the class searches: k, num_classes and the labels in its `extra` place -- and the range too, which these entry
 // points have always checked before they look at qb == 0.
-int check_top_classes(const fir_gallery* g, const float* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, int32_t num_classes, int32_t k) {
-    return check_search(g, queries, qb, start_pos, end_pos, true, [&] {
+int check_top_classes(const fir_gallery* g, const float* queries, int32_t qb, int32_t& start_pos, int32_t& end_pos, int32_t num_classes, int32_t k,
+                      bool pointers_ok = true) {
+    return check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] {
         if (k < 1 || k > 32) return fir_fail_(FIR_ERR_ARG, "k=%d outside [1,32]", k);
         if (num_classes < 1 || num_classes > kClassMax) return fir_fail_(FIR_ERR_ARG, "num_classes=%d outside [1,%d]", num_classes, kClassMax);
         if (!g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
@@ -2616,6 +2680,132 @@ int fir_search_top1_other_class(fir_gallery* g, const float* queries, int32_t qb
     HostOut out{idx, dist};
     out.exclude = exclude_class;
     return search_host(g, queries, qb, start_pos, end_pos, FirSearch::other_class(nullptr, nullptr), out);
+}
+
+// ---- searches over a subset of the rows (fir_amd.h): each the unmasked sibling's checks with the mask among the NULL checks, then the
+// exact scan form of its kind with the mask -- no route is consulted ----
+int fir_search_top1_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* d_mask,
+                                    uint64_t* d_keys, void* stream) {
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr && mask_ok(g, d_mask));
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    return masked_top1_dev(g, d_queries, qb, start_pos, end_pos, d_mask, d_keys, call.st);
+}
+
+int fir_search_top1_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* mask, int32_t* idx,
+                           float* dist) {
+    const int rc = check_search(g, queries, qb, start_pos, end_pos, mask_ok(g, mask));
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    HostOut out{idx, dist};
+    out.masked = true;
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::rows(1, nullptr).masked(mask), out);
+}
+
+int fir_search_knn_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* d_mask,
+                                   int32_t k, uint64_t* d_keys, void* stream) {
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, d_keys != nullptr && mask_ok(g, d_mask), [&] { return check_knn_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, FirSearch::select(k, d_keys).masked(g->n > 0 ? d_mask : nullptr), call.st);
+}
+
+int fir_search_knn_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* mask, int32_t k,
+                          int32_t* idx, float* dist) {
+    const int rc = check_search(g, queries, qb, start_pos, end_pos, idx != nullptr && dist != nullptr && mask_ok(g, mask), [&] { return check_knn_k(k); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    HostOut out{idx, dist};
+    out.masked = true;
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::select(k, nullptr).masked(mask), out);
+}
+
+int fir_search_radius_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* d_mask,
+                                      const float* d_radius, int32_t max_results, int32_t* d_count, uint64_t* d_keys, void* stream) {
+    const bool pointers_ok = radius_pointers_ok(qb, d_radius, max_results, d_count, d_keys != nullptr, d_keys != nullptr) && mask_ok(g, d_mask);
+    const int rc = check_search(g, d_queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return knn_dev(g, d_queries, qb, start_pos, end_pos, FirSearch::within(d_radius, max_results, d_count, d_keys).masked(g->n > 0 ? d_mask : nullptr), call.st);
+}
+
+int fir_search_radius_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* mask,
+                             const float* radius, int32_t max_results, int32_t* count, int32_t* idx, float* dist) {
+    const bool pointers_ok = radius_pointers_ok(qb, radius, max_results, count, idx || dist, idx && dist) && mask_ok(g, mask);
+    const int rc = check_search(g, queries, qb, start_pos, end_pos, pointers_ok, [&] { return check_max_results(max_results); });
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    HostOut out{idx, dist, nullptr, radius, count};
+    out.masked = true;
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::within(nullptr, max_results, nullptr, nullptr).masked(mask), out);
+}
+
+int fir_search_top_classes_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* d_mask,
+                                           int32_t num_classes, int32_t k, uint64_t* d_keys, int32_t* d_classes, void* stream) {
+    const int rc = check_top_classes(g, d_queries, qb, start_pos, end_pos, num_classes, k, mask_ok(g, d_mask));
+    if (rc < 0) return rc;
+    if (qb > 0 && !d_keys && !d_classes) return fir_fail_(FIR_ERR_ARG, "d_keys and d_classes are both NULL");
+    if (rc) return FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    g->call_launches = 0;
+    g->warm_left = 0;
+    return top_classes_dev(g, d_queries, qb, start_pos, end_pos, num_classes, k, d_keys, d_classes, call.st, {}, 0, nullptr, g->n > 0 ? d_mask : nullptr);
+}
+
+int fir_search_top_classes_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos, const uint64_t* mask,
+                                  int32_t num_classes, int32_t k, int32_t* class_out, int32_t* idx, float* dist) {
+    const int rc = check_top_classes(g, queries, qb, start_pos, end_pos, num_classes, k, mask_ok(g, mask));
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    HostOut out{idx, dist, class_out};
+    out.masked = true;
+    return search_host(g, queries, qb, start_pos, end_pos, FirSearch::distinct(num_classes, k, nullptr, nullptr).masked(mask), out);
+}
+
+namespace {
+// The builders' checks, device and host form alike: 0 = go on, kNothingToDo = an empty gallery (no word to write), < 0 = the error
+int check_mask_of_classes(const fir_gallery* g, const int32_t* classes, int32_t m, const uint64_t* mask_out) {
+    if (!g || (m > 0 && !classes) || (!mask_out && g->n > 0)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (!g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");      // (an empty gallery keeps none)
+    return g->n == 0 ? kNothingToDo : FIR_OK;
+}
+int mask_of_classes_launch(fir_gallery* g, const int32_t* d_classes, int32_t m, int32_t invert, uint64_t* d_mask_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_mask_of_classes, dim3((unsigned)((g->tiles + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, (const int32_t*)g->cls, g->n, g->tiles,
+                       d_classes, m, invert, d_mask_out);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+}  // namespace
+
+int fir_gallery_mask_of_classes_dev(fir_gallery* g, const int32_t* d_classes, int32_t m, int32_t invert, uint64_t* d_mask_out, void* stream) {
+    const int rc = check_mask_of_classes(g, d_classes, m, d_mask_out);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    return mask_of_classes_launch(g, d_classes, m, invert, d_mask_out, call.st);
+}
+
+int fir_gallery_mask_of_classes(fir_gallery* g, const int32_t* classes, int32_t m, int32_t invert, uint64_t* mask_out) {
+    int rc = check_mask_of_classes(g, classes, m, mask_out);
+    if (rc) return rc < 0 ? rc : FIR_OK;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    std::vector<int32_t> sorted(classes, classes + m);
+    std::sort(sorted.begin(), sorted.end());
+    // scratch: the tile words first (8-byte aligned), the sorted list behind them
+    const size_t list_words = ((size_t)m + 1) / 2;
+    if ((rc = FIR_NEED(g->mclasses, (size_t)g->tiles + list_words + 1))) return rc;
+    uint64_t* d_words = g->mclasses;
+    int32_t* d_list = (int32_t*)(d_words + g->tiles);
+    if (m > 0) FIR_HIP(hipMemcpyAsync(d_list, sorted.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    if ((rc = mask_of_classes_launch(g, d_list, m, invert, d_words, g->stream))) return rc;
+    FIR_HIP(hipMemcpyAsync(mask_out, d_words, (size_t)g->tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    call.done();
+    return FIR_OK;
 }
 
 int fir_gallery_other_class_keys_dev(fir_gallery* g, int64_t row0, int64_t m, int32_t start_pos, int32_t end_pos, uint64_t* d_keys, void* stream) {

@@ -22,6 +22,7 @@ enum { kEpiTop1 = 0, kEpiTopK = 1, kEpiStore = 2, kEpiAppend = 3,
 
 typedef const float __attribute__((address_space(4)))* sfloat_p;  // constant AS => s_load when uniform
 typedef const int32_t __attribute__((address_space(4)))* sint_p;  // ... the same for integers (kEpiTop1Other's excluded classes)
+typedef const uint64_t __attribute__((address_space(4)))* smask_p; // ... and for the row-mask word of a tile (k_scan<..., MASKED = 1>)
 
 // float bits -> uint32 whose unsigned order equals the float order (negatives included).
 __host__ __device__ __forceinline__ uint32_t f32_orderable(float f) {

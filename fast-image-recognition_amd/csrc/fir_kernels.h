@@ -91,6 +91,7 @@ struct ScanArgs {
     int32_t run_count;    // one may be shorter), run i moved up by floor(i * run_slack / run_count) tiles: sample tile t is gallery tile
     int64_t run_slack;    // t + floor((t / run_len) * run_slack / run_count), stored at row 64 t + lane; n = rows of the sample (knn_sample_plan)
     const int32_t* excl;  // kEpiTop1Other: excl[blockIdx.y * QB + q] = the class whose rows query q passes over (a copy padded to whole tiles); cls = the labels
+    const uint64_t* mask; // k_scan<..., MASKED = 1>: mask[t] = the rows of scan tile t that take part, bit r = lane r (row 64 t + r); bits past n are ignored
 };
 
 template <int QB, int METRIC, int U>
@@ -241,8 +242,15 @@ struct TileAcc {
 // LDSQ = 1: the query tile is staged in (dynamic) LDS first -- dp4*4*QB floats -- and read from there; used for
 // one- and two-query tiles over galleries of few tiles, where a wave streams a whole tile alone and the per-chunk
 // scalar-load latency of the default form is what it waits for.
-template <int QB, int METRIC, int U, int EPI, int KMAX, int WPS, int LDSQ = 0>
+// MASKED = 1 (top-1, store and class-minimum epilogues): a row takes part only if its bit of a.mask is set. A 64-row tile is one
+// 64-bit word and the word is wave-uniform: one scalar load per tile, asked for ahead of the tile's features. A tile none of whose
+// rows below n has its bit set is not read at all -- one wave-uniform branch around the feature loop; the store epilogue still writes
+// kNotFound for its rows, the value the count and select kernels of fir_knn_select.h reject (`dist < kNotFound`), so a stored row of
+// distances never shows what an earlier call left. In every other tile the feature loop is the unmasked one -- the same accumulation
+// order, the same bits -- and lane r applies bit r in the epilogue. MASKED = 0 compiles to the code it always has.
+template <int QB, int METRIC, int U, int EPI, int KMAX, int WPS, int LDSQ = 0, int MASKED = 0>
 __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
+    static_assert(!MASKED || ((EPI == kEpiTop1 || EPI == kEpiStore || EPI == kEpiClassMin) && !LDSQ), "masked forms: top-1, store, class minimum; generic scan");
     if constexpr (METRIC != kL2) {
         // chi-square / KL come as a pair of launches: the kernel whose arithmetic matches the operands of this call runs
         // (every value in the plain range -> the kChi2InRange / kKLInRange form, fir_common.h), the other one returns here
@@ -311,6 +319,26 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
         if constexpr (EPI == kEpiStore) {
             if (a.run_len > 0) gt += (int64_t)(t / a.run_len) * a.run_slack / a.run_count;
         }
+        bool take = true;                                            // MASKED: this lane's row takes part
+        if constexpr (MASKED) {
+            // t is the same in every lane of the wave: the word's address is uniform, constant AS => s_load_dwordx2
+            const int tu = __builtin_amdgcn_readfirstlane(t);
+            uint64_t word = ((smask_p)(uintptr_t)a.mask)[tu];
+            const int64_t left = a.n - (int64_t)tu * kTileRows;      // rows of this tile below n: 1 .. (a whole tile: >= 64)
+            if (left < kTileRows) word &= (1ull << left) - 1ull;
+            if (word == 0) {                                         // wave-uniform: nothing of the tile is read
+                if constexpr (EPI == kEpiStore) {
+                    const int64_t srow = (int64_t)tu * kTileRows + lane;
+                    if (srow < a.n) {
+#pragma unroll
+                        for (int q = 0; q < QB; ++q)
+                            if ((int)blockIdx.y * QB + q < a.nq) a.out[((size_t)blockIdx.y * QB + q) * a.out_stride + srow] = kNotFound;
+                    }
+                }
+                continue;
+            }
+            take = ((word >> lane) & 1ull) != 0;
+        }
         const float4* tile = a.gal4 + (size_t)gt * a.dp4 * 64 + lane;
         int32_t lab_other = 0;
         if constexpr (EPI == kEpiTop1Other) {
@@ -347,7 +375,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
             // order the table ends with the first-minimum row of each class (db_features.cpp:329-332 within the class).
             // Every lane takes part in the shuffles: rows past n and rows labelled outside [0, num_classes) carry no key.
             const int32_t lab = row < a.n ? a.cls[row] : -1;                  // one coalesced load per tile
-            const bool counted = (uint32_t)lab < (uint32_t)a.num_classes;
+            const bool counted = (uint32_t)lab < (uint32_t)a.num_classes && take;      // (a masked-out row carries no key, like a row past n)
             // Segmented minimum: same bit j = the lane 2^j below holds the same label. Joining two lanes of one label is right
             // whatever lies between them, and inside a run of equal labels the steps are the inclusive scan's, so the last lane
             // of every run ends with (at least) the run's minimum: it alone goes to memory. Class-major galleries: one or two
@@ -404,7 +432,9 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                 float dist = acc[q] / fcount;                            // db_features.cpp:40
                 if constexpr (METRIC == kChi2Harm) dist = ((a.sq[(size_t)blockIdx.y * QB + q] + a.sg[row]) - 4.0f * acc[q]) / fcount;
                 if constexpr (METRIC == kKLEnt) dist = (0.693147181f * ((a.sq[(size_t)blockIdx.y * QB + q] + a.sg[row]) - acc[q])) / fcount;
-                if constexpr (EPI == kEpiTop1) {
+                if constexpr (EPI == kEpiTop1 && MASKED) {
+                    if (take && dist < best_d[q]) { best_d[q] = dist; best_i[q] = (int32_t)row; }   // ... over the rows of the mask
+                } else if constexpr (EPI == kEpiTop1) {
                     if (dist < best_d[q]) { best_d[q] = dist; best_i[q] = (int32_t)row; }   // db_features.cpp:329-332
                 } else if constexpr (EPI == kEpiTop1Other) {
                     if (lab_other != excl[q] && dist < best_d[q]) { best_d[q] = dist; best_i[q] = (int32_t)row; }   // ... over the other classes' rows
@@ -428,6 +458,7 @@ __global__ void __launch_bounds__(kBlock, WPS) k_scan(const ScanArgs a) {
                         if (slot < a.k) a.keys[qy * a.k + slot] = key_pack(dist, (uint32_t)(row + a.row_offset));
                     }
                 } else {
+                    if constexpr (MASKED) dist = take ? dist : kNotFound;   // what the count and select kernels reject
                     if ((int)blockIdx.y * QB + q < a.nq) a.out[((size_t)blockIdx.y * QB + q) * a.out_stride + row] = dist;
                 }
             }
@@ -1418,6 +1449,29 @@ __global__ void __launch_bounds__(kBlock) k_pick_other(const uint64_t* __restric
     if (q >= qb) return;
     const uint64_t k0 = keys2[2 * q], k1 = keys2[2 * q + 1];
     out[q] = (k0 != kKeyNone && cls2[2 * q] != excl[q]) ? k0 : (k1 != kKeyNone && cls2[2 * q + 1] != excl[q]) ? k1 : kKeyNone;
+}
+// The row mask of a class filter (fir_gallery_mask_of_classes): bit r of mask[t] = (cls[64 t + r] is in classes[0, m)) != invert, rows
+// at or past n false. One wave per tile: every lane binary-searches its row's label in the ascending list (duplicates allowed), the
+// ballot is the tile's word, lane 0 stores it (an ordinary vector store).
+__global__ void __launch_bounds__(kBlock) k_mask_of_classes(const int32_t* __restrict__ cls, int64_t n, int64_t tiles, const int32_t* __restrict__ classes,
+                                                             int32_t m, int32_t invert, uint64_t* __restrict__ mask) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (t >= tiles) return;                                           // wave-uniform
+    const int64_t row = t * kTileRows + lane;
+    bool in = false;
+    if (row < n) {
+        const int32_t lab = cls[row];
+        int32_t lo = 0, hi = m;                                       // first entry >= lab
+        while (lo < hi) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (classes[mid] < lab) lo = mid + 1;
+            else hi = mid;
+        }
+        in = (lo < m && classes[lo] == lab) != (invert != 0);
+    }
+    const uint64_t word = __ballot(in);
+    if (lane == 0) mask[t] = word;
 }
 // dist[i] = the distance of keys[i], 100000 for FIR_KEY_NONE: the float row k_knn_sample_kth and k_far_stats read
 __global__ void __launch_bounds__(kBlock) k_keys_to_dist(const uint64_t* __restrict__ keys, int64_t m, float* __restrict__ dist) {

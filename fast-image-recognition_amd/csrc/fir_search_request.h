@@ -25,6 +25,10 @@ struct FirSearch {
     const float* radius;        // kSearchRadius: [qb]
     int32_t* count;             // kSearchRadius: [qb] <- the rows inside, however many
     const int32_t* exclude;     // kSearchOtherClass: [qb], the class each query passes over
+    // the rows that take part (fir_amd.h, "searches over a subset of the rows"): FIR_MASK_WORDS(n) words, NULL = every row. Last, with a
+    // default: the factories and every older aggregate initialisation leave it NULL; masked() sets it
+    const uint64_t* mask = nullptr;
+    FirSearch masked(const uint64_t* m) const { FirSearch s = *this; s.mask = m; return s; }
     static FirSearch rows(int32_t k, uint64_t* keys) { return {kSearchRows, k, 0, keys, nullptr, nullptr, nullptr, nullptr}; }
     static FirSearch select(int32_t k, uint64_t* keys) { return {kSearchSelect, k, 0, keys, nullptr, nullptr, nullptr, nullptr}; }
     static FirSearch within(const float* radius, int32_t max_results, int32_t* count, uint64_t* keys) { return {kSearchRadius, max_results, 0, keys, nullptr, radius, count, nullptr}; }
@@ -44,7 +48,7 @@ struct FirSearch {
     // the same request for queries [q0, ...): every pointer it has, advanced by its stride
     FirSearch at(int32_t q0) const {
         return {kind, k, num_classes, keys ? keys + (size_t)q0 * k : nullptr, classes ? classes + (size_t)q0 * k : nullptr, radius ? radius + q0 : nullptr, count ? count + q0 : nullptr,
-                exclude ? exclude + q0 : nullptr};
+                exclude ? exclude + q0 : nullptr, mask};
     }
 };
 }  // namespace fir

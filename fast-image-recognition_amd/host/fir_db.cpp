@@ -25,6 +25,7 @@ int g_large_batch = -1;
 std::vector<int> g_devices;          // more than one entry (or g_shards_per_device > 1): galleries are row-sharded (fir_sharded_*)
 int g_shards_per_device = 1;
 int g_validation = FIR_CACHE_VALIDATE_THROTTLED;
+long g_uploads = 0;                  // GalleryCache::uploads
 
 // One uploaded gallery. What identifies the caller's `std::vector<ImageInfo>` is checked on EVERY lookup: the vector
 // object, its size, and a signature over every row's (feature pointer, length, classNo) -- any reallocation, reorder or
@@ -151,6 +152,7 @@ Entry* lookup(const std::vector<ImageInfo>& db, int dim) {
         }
         if (g_large_batch >= 0) fir_gallery_set_large_batch_mfma(e.g, g_large_batch);
     }
+    ++g_uploads;
     g_cache.push_back(e);
     return &g_cache.back();
 }
@@ -214,6 +216,8 @@ int GalleryCache::appended(const std::vector<ImageInfo>& db, size_t old_n) {
     return extended;
 }
 
+long GalleryCache::uploads() { return g_uploads; }
+
 void GalleryCache::clear() {
     for (Entry& e : g_cache) drop(e);
     g_cache.clear();
@@ -241,6 +245,42 @@ std::vector<int> recognize_images_bf(const std::vector<ImageInfo>& dbImages, con
                         : fir_search_top1(e->g, q.data(), (int32_t)tests.size(), 0, max_features, idx.data(), dist.data());
     if (rc != FIR_OK) {
         log_error("search_top1");
+        return out;
+    }
+    for (size_t i = 0; i < tests.size(); ++i) out[i] = idx[i];
+    if (best_dist) *best_dist = dist;
+    return out;
+}
+
+std::vector<int> recognize_images_bf_subset(const std::vector<ImageInfo>& dbImages, const std::vector<char>& take,
+                                            const std::vector<ImageInfo>& tests, int max_features, std::vector<float>* best_dist) {
+    if (max_features == 0) max_features = FEATURES_COUNT;          // db_features.cpp:320-321
+    std::vector<int> out(tests.size(), -1);
+    if (best_dist) best_dist->assign(tests.size(), FIR_NOT_FOUND_DIST);
+    if (tests.empty() || dbImages.empty()) return out;
+    if (take.size() != dbImages.size()) {
+        std::fprintf(stderr, "fir: recognize_images_bf_subset: %zu marks for %zu rows\n", take.size(), dbImages.size());
+        return out;
+    }
+    if (sharded_mode()) {
+        std::fprintf(stderr, "fir: recognize_images_bf_subset: no masked search on a sharded gallery\n");
+        return out;
+    }
+    const int dim = max_features;
+    Entry* e = lookup(dbImages, dim);
+    if (!e) return out;
+    std::vector<uint64_t> mask(FIR_MASK_WORDS(dbImages.size()), 0);
+    for (size_t j = 0; j < take.size(); ++j)
+        if (take[j]) mask[j >> 6] |= (uint64_t)1 << (j & 63);
+    std::vector<float> q((size_t)tests.size() * dim, 0.0f);
+    for (size_t i = 0; i < tests.size(); ++i) {
+        const FeaturesVector& f = tests[i].features;
+        std::memcpy(&q[i * dim], f.data(), std::min<size_t>(f.size(), (size_t)dim) * sizeof(float));
+    }
+    std::vector<int32_t> idx(tests.size());
+    std::vector<float> dist(tests.size());
+    if (fir_search_top1_masked(e->g, q.data(), (int32_t)tests.size(), 0, max_features, mask.data(), idx.data(), dist.data()) != FIR_OK) {
+        log_error("search_top1_masked");
         return out;
     }
     for (size_t i = 0; i < tests.size(); ++i) out[i] = idx[i];

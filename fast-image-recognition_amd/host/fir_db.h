@@ -80,6 +80,14 @@ namespace fir {
 std::vector<int> recognize_images_bf(const std::vector<ImageInfo>& dbImages, const std::vector<ImageInfo>& tests,
                                      int max_features = 0, std::vector<float>* best_dist = nullptr);
 
+// The random-split loop of the reference's experiments (testRecognitionMethod, ImageTesting.cpp:445-466: TESTS splits of one image
+// set by getTrainingAndTestImages) without one upload per split: dbImages is the TOTAL set, uploaded once through GalleryCache, and
+// take[j] != 0 marks the rows of this split's training side (take.size() == dbImages.size()). out[i] = the index INTO dbImages of
+// the nearest row of tests[i] among them (first minimum in row order), -1 without one -- fir_search_top1_masked, n / 8 bytes per
+// split. Single device only: with fir::set_devices in force it logs an error and returns -1 for every test.
+std::vector<int> recognize_images_bf_subset(const std::vector<ImageInfo>& dbImages, const std::vector<char>& take,
+                                            const std::vector<ImageInfo>& tests, int max_features = 0, std::vector<float>* best_dist = nullptr);
+
 // The device copy of one `std::vector<ImageInfo>` gallery. The reference's classifiers only keep
 // a pointer to the caller's vector (ImageTesting.cpp:40, ann.h:28) and read it afresh on every call; here the rows are
 // packed and uploaded on first use and the handle is reused while the SAME gallery is presented again, which is checked
@@ -97,6 +105,8 @@ public:
     // signature and hash refreshed; an upload that is sharded, or whose first old_n rows were edited, reordered or relabelled, is
     // dropped, and the next lookup uploads the whole vector as ever. Returns the number of uploads that were extended in place.
     static int appended(const std::vector<ImageInfo>& dbImages, size_t old_n);
+    // Whole-gallery uploads made so far in this process (an in-place extension by appended() is not one).
+    static long uploads();
     static void clear();
 };
 inline void invalidate(const std::vector<ImageInfo>& dbImages) { GalleryCache::invalidate(dbImages); }

@@ -362,6 +362,78 @@ int fir_gallery_other_class(fir_gallery* g, int32_t start_pos, int32_t end_pos, 
 int fir_gallery_far_threshold(fir_gallery* g, int32_t start_pos, int32_t end_pos, float false_accept_rate,
                               float* threshold, float* min_dist, float* max_dist, int64_t* rows_counted);
 
+/* ---- searches over a subset of the rows ---------------------------------------------------------
+ * "This handle, these rows only": the random train / test splits of the reference's experiments (getTrainingAndTestImages,
+ * db_features.cpp:117-162, called TESTS times by testRecognitionMethod, ImageTesting.cpp:445-466), watch-lists, consent or expiry
+ * flags, soft delete without fir_gallery_remove_rows' renumbering, leave-several-classes-out evaluation -- over ONE upload of the
+ * whole set, a subset being n / 8 bytes.
+ * The mask: FIR_MASK_WORDS(n) 64-bit words, n = the handle's row count at the time of the call (after in-place updates: the current
+ * n, whatever the capacity). LOCAL row r (without the row offset, as in fir_rows_distances and the update calls; on a shard lent by
+ * fir_sharded_shard: the shard's local row) takes part iff bit r & 63 of word r >> 6 is set. Bits at or past n in the last word are
+ * ignored, whatever they hold. The mask must be 8-byte aligned. Keys still carry row + row offset.
+ * A row qualifies iff its bit is set AND it qualifies in the unmasked call of the same name; everything else is the unmasked
+ * call's contract word for word: ordering, the first-minimum rule, padding with FIR_KEY_NONE (idx -1, dist 100000; class -1), exact
+ * counts never capped by max_results, `dist < 100000.0f`, NaN never qualifying, which outputs may be NULL. Equivalently: the answer
+ * of a handle freshly created over the selected rows in their order, every returned row mapped back to its index in the full
+ * gallery (the map is monotone, so ties keep their order; the distance bits are fir_range_distances'). A class with no masked-in
+ * row does not appear in a class answer. An all-ones mask gives the unmasked call's bytes.
+ * Each call has its unmasked sibling's arguments with the mask directly after end_pos. A NULL mask is FIR_ERR_ARG unless n == 0:
+ * the mask is then not read and the unmasked empty-gallery results apply. Arguments are checked in the sibling's order, the mask
+ * among the NULL checks, before anything is allocated or queued. fir_search_knn_masked: 1 <= k <= FIR_KNN_MAX; for k <= 8 it is also
+ * the masked fir_search_topk (the same keys), there is no separate call. fir_search_radius_masked: the counts count masked-in rows
+ * only; max_results = 0 stays the count-only call.
+ * Form: a masked call ALWAYS takes the exact scan form of its kind -- the generic scan (k_scan<..., MASKED = 1>) with the top-1
+ * epilogue, the store pass of store + select (+ count), or the class-minimum scan + select. It never takes the matrix-core routes,
+ * the int8 or fp16 nomination, the chi-square / KL nomination lists of the top-1 call or the hand-scheduled L2 kernels, whatever
+ * fir_gallery_set_large_batch_mfma and the batch size say (as fir_search_top1_other_class_keys_dev always takes the scan): none of
+ * those has a masked form. A 64-row tile is one mask word: the scan reads it once per tile through the scalar cache; a tile none
+ * of whose rows below n has its bit set is not read at all (the store pass writes 100000 for its rows, which count and select
+ * reject), every other tile is read whole. A mask much sparser than one row per tile therefore still reads every tile it touches;
+ * there is no gather form. fir_gallery_last_dispatch describes a masked top-1 and class call by the kernel instantiation that ran
+ * (path 0, "fir::k_scan<..., 0, 1>": the last template argument is MASKED); a masked kNN / radius call it does not describe, like
+ * the unmasked one. fir_profile_read's bytes_per_launch is the unmasked figure plus the mask words: the host cannot know how many
+ * tiles a device mask skips without a synchronisation, so skipped tiles are still counted.
+ * Measured (profiles/masked_search.txt, tools/masked_search_probe.py: whole host-pointer calls, L2, 512 features, 100 000 and 1M rows,
+ * 8 / 128 / 1 024 queries): the all-ones mask takes 0.98 - 1.05 x the time of the unmasked generic scan (top-1 and kNN); a clustered mask
+ * (runs of 16 whole tiles) of density 1/64 takes 0.06 - 0.13 of the all-ones top-1 time from 128 queries on, one of density 1/8 0.12 - 0.19 at
+ * 100 000 rows but 0.61 at 1M rows, where the probe's 128-tile period divides the 3 072 waves of a pass and an eighth of the waves read
+ * everything (a wave strides over the tiles); scattered masks read nearly every tile (0.97 - 1.10 at 1/2 and 1/8); masked kNN at k = 64 stays
+ * within 0.70 - 1.02 of all-ones, its select reading 4 bytes per row and query whatever the mask. A second handle over the compacted rows
+ * answers a large L2 batch far faster once it is uploaded (it may take the matrix cores); the mask saves the copy and the upload.
+ * Left out: masked calls on fir_sharded handles (shards are whole 64-row tiles, so the words can be sliced by shard
+ * later); masked matrix-core forms; a gather form for very sparse masks; masked other-class search (fir_gallery_mask_of_classes
+ * with invert = 1 composes it); masks for fir_cls / TWD / DEM. */
+#define FIR_MASK_WORDS(n) (((n) + 63) / 64)
+int fir_search_top1_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                           const uint64_t* mask, int32_t* idx, float* dist);
+int fir_search_knn_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                          const uint64_t* mask, int32_t k, int32_t* idx, float* dist);
+int fir_search_radius_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                             const uint64_t* mask, const float* radius, int32_t max_results, int32_t* count, int32_t* idx, float* dist);
+int fir_search_top_classes_masked(fir_gallery* g, const float* queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                  const uint64_t* mask, int32_t num_classes, int32_t k, int32_t* class_out, int32_t* idx, float* dist);
+/* The host forms above copy the mask into the handle's scratch. The device forms read d_mask on `stream` (NULL: the handle's own),
+ * are asynchronous, take effect in the handle's call order ("Streams") and never synchronise once the scratch is large enough; a
+ * mask written on the same stream just before -- by fir_gallery_mask_of_classes_dev, say -- needs no synchronisation in between. */
+int fir_search_top1_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                    const uint64_t* d_mask, uint64_t* d_keys, void* stream);
+int fir_search_knn_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                   const uint64_t* d_mask, int32_t k, uint64_t* d_keys, void* stream);
+int fir_search_radius_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                      const uint64_t* d_mask, const float* d_radius, int32_t max_results, int32_t* d_count,
+                                      uint64_t* d_keys, void* stream);
+int fir_search_top_classes_masked_keys_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t start_pos, int32_t end_pos,
+                                           const uint64_t* d_mask, int32_t num_classes, int32_t k, uint64_t* d_keys,
+                                           int32_t* d_classes, void* stream);
+/* The mask of a class filter: bit r = (class_no[r] is one of classes[0, m)) XOR (invert != 0), bits past n in the last word zero.
+ * Any int32 is a class; m = 0 is legal and gives all zeros, or all ones with invert. FIR_ERR_STATE without labels; an empty gallery
+ * has no word to write. The host form has everything in host memory (mask_out [FIR_MASK_WORDS(n)]) and sorts a copy of `classes`
+ * itself; one synchronisation. The device form is asynchronous on `stream`; d_classes must be ascending, duplicates allowed -- this
+ * is not checked. One wave per tile, a binary search per row. */
+int fir_gallery_mask_of_classes(fir_gallery* g, const int32_t* classes, int32_t m, int32_t invert, uint64_t* mask_out);
+int fir_gallery_mask_of_classes_dev(fir_gallery* g, const int32_t* d_classes, int32_t m, int32_t invert, uint64_t* d_mask_out,
+                                    void* stream);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
