@@ -29,6 +29,7 @@ from .capi import (  # noqa: F401
     device_peak_hbm_gbs,
     feature_distance,
     key_pack,
+    keys_map_rows,
     keys_unpack,
     lib,
     lib_path,

@@ -76,6 +76,16 @@ SYMBOLS = [
     ("fir_search_top_classes_masked_keys_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     ("fir_gallery_mask_of_classes", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     ("fir_gallery_mask_of_classes_dev", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    ("fir_gallery_rows_of_mask", C.c_int, [_vp, _vp, _vp, C.c_int64, _i64p]),
+    ("fir_gallery_rows_of_mask_dev", C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    ("fir_gallery_gather_rows_dev", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    ("fir_gallery_create_from_rows", C.c_int, [_vp, _vp, C.c_int64, C.POINTER(_vp)]),
+    ("fir_gallery_create_from_rows_dev", C.c_int, [_vp, _vp, C.c_int64, _vp, C.POINTER(_vp)]),
+    ("fir_gallery_create_subset", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    ("fir_gallery_create_subset_dev", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    ("fir_gallery_origin_rows", C.c_int, [_vp, C.c_int64, C.c_int64, _vp]),
+    ("fir_keys_to_origin_dev", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("fir_keys_map_rows", C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.c_int64]),
     ("fir_gallery_other_class_keys_dev", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gallery_other_class", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("fir_gallery_far_threshold", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp]),
@@ -263,6 +273,16 @@ def pack_row_mask(take):
     bits = np.zeros(mask_words(take.size) * 64, np.uint8)
     bits[:take.size] = take
     return np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u8").astype(np.uint64))
+
+
+def keys_map_rows(keys, row_map, row_add=0):
+    """fir_keys_map_rows on a copy: every key's low word r becomes uint32(row_map[r] + row_add), the distance bits and FIR_KEY_NONE
+    stay. Pure host code. Raises FirError when a low word is at or beyond len(row_map)."""
+    out = np.array(keys, dtype=np.uint64, order="C", copy=True)
+    row_map = np.ascontiguousarray(row_map, dtype=np.int32).reshape(-1)
+    _check(lib().fir_keys_map_rows(out.ctypes.data_as(_vp) if out.size else None, out.size, row_map.ctypes.data_as(_vp) if row_map.size else None,
+                                   row_map.size, int(row_add)))
+    return out
 
 
 def remove_plan(n, row_idx):
@@ -604,6 +624,71 @@ class Gallery:
         """... on the device: classes_ptr -> m ascending int32 (duplicates allowed), mask_ptr -> FIR_MASK_WORDS(n) words; asynchronous."""
         _check(lib().fir_gallery_mask_of_classes_dev(self._h, _vp(classes_ptr) if classes_ptr else None, m, 1 if invert else 0,
                                                      _vp(mask_ptr) if mask_ptr else None, _vp(stream) if stream else None))
+
+    # ---- device-side subsets (include/fir_amd.h): compact by mask or row list, map back ----
+    @classmethod
+    def _adopt(cls, handle, device):
+        """A Gallery over a handle the library created (fir_gallery_create_subset ...): it owns it from here on."""
+        g = cls.__new__(cls)
+        g._h = handle
+        g.device = device
+        n, d = C.c_int64(), C.c_int32()
+        _check(lib().fir_gallery_info(handle, C.byref(n), C.byref(d), None, None))
+        g.n, g.d = int(n.value), int(d.value)
+        return g
+
+    def rows_of_mask(self, mask, cap=None):
+        """(count, rows): the exact number of rows the mask selects and the first min(count, cap) of them, ascending int32 (cap None:
+        all of them; cap 0: the count-only call)."""
+        m, pm = self._mask(mask)
+        cap = self.n if cap is None else int(cap)
+        rows = np.empty(max(cap, 0), np.int32)
+        count = C.c_int64()
+        _check(lib().fir_gallery_rows_of_mask(self._h, pm, rows.ctypes.data_as(_vp) if cap > 0 else None, cap, C.byref(count)))
+        return int(count.value), rows[:min(int(count.value), max(cap, 0))]
+
+    def rows_of_mask_dev(self, mask_ptr, rows_ptr, cap, count_ptr, stream=None):
+        """... on the device: mask_ptr -> FIR_MASK_WORDS(n) words, rows_ptr -> cap int32, count_ptr -> one int64; asynchronous."""
+        _check(lib().fir_gallery_rows_of_mask_dev(self._h, _vp(mask_ptr) if mask_ptr else None, _vp(rows_ptr) if rows_ptr else None, int(cap),
+                                                  _vp(count_ptr) if count_ptr else None, _vp(stream) if stream else None))
+
+    def gather_rows_dev(self, idx_ptr, m, rows_ptr, class_ptr=None, stream=None):
+        """rows_ptr[m, d] (class_ptr[m]) <- rows idx_ptr[0 .. m) of the gallery, row-major, on the device; asynchronous."""
+        _check(lib().fir_gallery_gather_rows_dev(self._h, _vp(idx_ptr) if idx_ptr else None, int(m), _vp(rows_ptr) if rows_ptr else None,
+                                                 _vp(class_ptr) if class_ptr else None, _vp(stream) if stream else None))
+
+    def subset(self, mask=None, *, mask_ptr=None, stream=None):
+        """A new Gallery holding the rows the mask selects, ascending (mask: bool[n] or packed words; mask_ptr: device words)."""
+        h = _vp()
+        if mask_ptr is not None:
+            _check(lib().fir_gallery_create_subset_dev(self._h, _vp(mask_ptr) if mask_ptr else None, _vp(stream) if stream else None, C.byref(h)))
+        else:
+            m, pm = self._mask(mask)
+            _check(lib().fir_gallery_create_subset(self._h, pm, C.byref(h)))
+        return Gallery._adopt(h, self.device)
+
+    def from_rows(self, rows=None, *, rows_ptr=None, m=None, stream=None):
+        """A new Gallery holding rows `rows` of this one in that order, repeats allowed (rows_ptr / m: a device list of int32)."""
+        h = _vp()
+        if rows_ptr is not None:
+            _check(lib().fir_gallery_create_from_rows_dev(self._h, _vp(rows_ptr) if rows_ptr else None, int(m), _vp(stream) if stream else None, C.byref(h)))
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+            _check(lib().fir_gallery_create_from_rows(self._h, r.ctypes.data_as(_vp) if r.size else None, r.size, C.byref(h)))
+        return Gallery._adopt(h, self.device)
+
+    def origin_rows(self, row0=0, m=None):
+        """The source's LOCAL rows of this subset's rows [row0, row0 + m) (m None: to the end of the row list): int32[m]."""
+        if m is None:
+            self._follow()
+            m = self.n - row0
+        out = np.empty(max(int(m), 0), np.int32)
+        _check(lib().fir_gallery_origin_rows(self._h, int(row0), int(m), out.ctypes.data_as(_vp) if out.size else None))
+        return out
+
+    def keys_to_origin_dev(self, keys_ptr, count, stream=None):
+        """Device keys of a search over this subset -> keys over its source, in place; asynchronous."""
+        _check(lib().fir_keys_to_origin_dev(self._h, _vp(keys_ptr) if keys_ptr else None, int(count), _vp(stream) if stream else None))
 
     def other_class(self, start=0, end=0):
         """Every row of the gallery against the gallery with its own class excluded (row i is the query): (idx, dist), each [n];

@@ -98,10 +98,18 @@ struct fir_gallery {
     // the masked searches: a host call's mask words; fir_gallery_mask_of_classes' sorted class list, and behind it room for the words it returns
     GalleryBuf<uint64_t> dmask;
     GalleryBuf<uint64_t> mclasses;
+    // subsets. On a source: the mask -> row list scan's total (one int64) and, behind it, the segment sums (rows_of_mask_launch).
+    // On a handle made by fir_gallery_create_subset / _from_rows (is_subset): origin[origin_n] = the source's LOCAL row of each row and
+    // the source's row offset at creation; origin_ok ends with the handle's first in-place update (gallery_changed), the buffer stays --
+    // queued key maps may still read it
+    GalleryBuf<int32_t> mseg;
+    GalleryBuf<int32_t> origin;
+    int64_t origin_n = 0, origin_offset = 0;
+    bool is_subset = false, origin_ok = false;
     FirBuf scratch[25];
     size_t scratch_bytes() const {
         size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap + excl.cap + okeys.cap + ocls.cap + selfq.cap +
-                     selfkeys.cap + fardist.cap + dmask.cap + mclasses.cap;
+                     selfkeys.cap + fardist.cap + dmask.cap + mclasses.cap + mseg.cap + origin.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
         return sum;
     }
@@ -1174,6 +1182,26 @@ int retile_slab(fir_gallery* g, const float* d_rows, int64_t slab_rows, int64_t 
     return FIR_OK;
 }
 
+// What the device-side constructors (fir_gallery_create_dev, fir_gallery_create_subset / _from_rows) share after gallery_alloc.
+// labels_alloc: room for the labels of the handle's n > 0 rows; what fills them follows on the constructor's stream.
+hipError_t labels_alloc(fir_gallery* g) {
+    const hipError_t e = g->cls.reserve((size_t)g->n * sizeof(int32_t));
+    g->cls_rows = g->n;
+    return e;
+}
+// created_dev: the end of such a constructor -- rc is what queueing the rows and labels on `st` returned. One synchronisation, the
+// plain-range flag read once, the handle handed out; on an error it is destroyed.
+int created_dev(fir_gallery* g, int rc, hipStream_t st, fir_gallery** out) {
+    if (rc == FIR_OK) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
+    }
+    if (rc) { delete g; return rc; }
+    { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
+    *out = g;
+    return FIR_OK;
+}
+
 // ---- what every entry point that queues work on a handle starts with ------------------------------------------------------------
 // The (queries, qb, range) arguments of a search: 0 = go on (end == 0 has become d), kNothingToDo = a call that succeeds without
 // doing anything (qb == 0; or what `extra` says), < 0 = the error. pointers_ok: the entry point's other required pointers.
@@ -1406,19 +1434,11 @@ int fir_gallery_create_dev(const float* d_rows, int64_t n, int32_t d, const int3
         rc = retile_slab(g, d_rows + r0 * d, span, r0, st);
     }
     if (rc == FIR_OK && d_class_no && n > 0) {
-        hipError_t e = g->cls.reserve((size_t)n * sizeof(int32_t));
-        g->cls_rows = n;
+        hipError_t e = labels_alloc(g);
         if (e == hipSuccess) e = hipMemcpyAsync(g->cls, d_class_no, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "class copy: %s", hipGetErrorString(e));
     }
-    if (rc == FIR_OK) {
-        hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "gallery retile: %s", hipGetErrorString(e));
-    }
-    if (rc) { delete g; return rc; }
-    { int32_t r0 = 1; if (hipMemcpy(&r0, g->range, sizeof r0, hipMemcpyDeviceToHost) == hipSuccess) g->gallery_plain = r0 == 0; }
-    *out = g;
-    return FIR_OK;
+    return created_dev(g, rc, st, out);
 }
 
 int fir_gallery_destroy(fir_gallery* g) {
@@ -1541,6 +1561,7 @@ void gallery_changed(fir_gallery* g) {
     g->gemm_failed = false;
     g->warm_left = 0;
     g->plain_stale = true;
+    g->origin_ok = false;                                     // a subset handle's rows are no longer its row list's (the buffer stays: queued key maps read it)
     // (the handle's matrix-core states carry their generation: drop_stale_gemm_states)
 }
 
@@ -1588,9 +1609,10 @@ int gallery_room(fir_gallery* g, int64_t need_rows, bool headroom, bool labels) 
         if (grow_tiles) { std::swap(g->gal4.p, ngal.p); std::swap(g->gal4.cap, ngal.cap); g->cap_tiles = new_tiles; }
         if (ncls.p) { std::swap(g->cls.p, ncls.p); std::swap(g->cls.cap, ncls.cap); g->cls_rows = new_cls_rows; }
         g->drop_gemm_states();                  // they hold the old buffer's address
-        const bool plain_stale = g->plain_stale;
+        const bool plain_stale = g->plain_stale, origin_ok = g->origin_ok;
         gallery_changed(g);
         g->plain_stale = plain_stale;           // (the rows were copied, not changed: range[0] still says what gallery_plain says)
+        g->origin_ok = origin_ok;               // (... and a subset handle's rows are still its row list's)
         return FIR_OK;                         // (ngal / ncls now own the old buffers: freed here)
     }
     return fir_fail_(FIR_ERR_NOMEM, "no device memory for a gallery of %lld rows", (long long)need_rows);
@@ -2805,6 +2827,241 @@ int fir_gallery_mask_of_classes(fir_gallery* g, const int32_t* classes, int32_t 
     FIR_HIP(hipMemcpyAsync(mask_out, d_words, (size_t)g->tiles * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
     FIR_HIP(hipStreamSynchronize(g->stream));
     call.done();
+    return FIR_OK;
+}
+
+// ---- device-side subsets: compact by mask or row list, map back (include/fir_amd.h has the contract) --------------------------------
+namespace {
+// g->mseg: the total of the mask scan (one int64, two words) and the segment sums behind it
+int64_t mask_segments(const fir_gallery* g) { return (FIR_MASK_WORDS(g->n) + kMaskSegWords - 1) / kMaskSegWords; }
+int mseg_room(fir_gallery* g) { return FIR_NEED(g->mseg, (size_t)mask_segments(g) + 2); }
+int64_t* mseg_total(const fir_gallery* g) { return (int64_t*)(int32_t*)g->mseg; }
+// The first two launches of mask -> row list on `st`: the segment sums become their exclusive prefix sums, the total goes to
+// mseg_total(g) and to d_count (may be NULL). n == 0: the scan alone, which writes 0.
+int mask_count_launch(fir_gallery* g, const uint64_t* d_mask, int64_t* d_count, hipStream_t st) {
+    const int64_t words = FIR_MASK_WORDS(g->n), nseg = mask_segments(g);
+    int32_t* seg = g->mseg + 2;
+    if (nseg > 0)
+        hipLaunchKernelGGL(k_mask_seg_counts, dim3((unsigned)((nseg + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, d_mask, g->n, words, seg);
+    hipLaunchKernelGGL(k_mask_seg_scan, dim3(1), dim3(kBlock), 0, st, seg, nseg, mseg_total(g), d_count);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+// ... and the third: d_rows_out[0, min(count, cap)) = the selected rows, ascending
+int mask_rows_launch(fir_gallery* g, const uint64_t* d_mask, int32_t* d_rows_out, int64_t cap, hipStream_t st) {
+    const int64_t nseg = mask_segments(g);
+    if (nseg == 0 || cap <= 0) return FIR_OK;
+    hipLaunchKernelGGL(k_mask_rows, dim3((unsigned)((nseg + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, d_mask, g->n, (int64_t)FIR_MASK_WORDS(g->n),
+                       (const int32_t*)(g->mseg + 2), d_rows_out, cap);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+int check_rows_of_mask(const fir_gallery* g, const void* mask, const void* rows_out, int64_t cap, const void* count) {
+    if (!g || !count || !mask_ok(g, mask) || (cap > 0 && !rows_out)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (cap < 0) return fir_fail_(FIR_ERR_ARG, "cap < 0");
+    return FIR_OK;
+}
+
+// A fresh handle for m rows of src, labelled iff src is (and m > 0), with room for its row list. Nothing is queued.
+int subset_alloc(fir_gallery* src, int64_t m, fir_gallery** out) {
+    fir_gallery* g = nullptr;
+    int rc = gallery_alloc(m, src->d, src->metric, src->device, &g);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (m > 0) e = g->origin.reserve((size_t)m * sizeof(int32_t));
+    if (e == hipSuccess && m > 0 && src->cls) e = labels_alloc(g);
+    if (e != hipSuccess) {
+        delete g;
+        return fir_fail_(e == hipErrorOutOfMemory ? FIR_ERR_NOMEM : FIR_ERR_HIP, "hipMalloc of a subset's row list and labels: %s", hipGetErrorString(e));
+    }
+    g->is_subset = g->origin_ok = true;
+    g->origin_n = m;
+    g->origin_offset = src->row_offset;
+    *out = g;
+    return FIR_OK;
+}
+// Rows d_idx[0, g->n) of src into every tile of g, on `st`; own_list: d_idx is g->origin itself (else the kernel fills it in).
+// Slabs of whole tiles keep the launch grid inside 2^31 blocks, as in fir_gallery_create_dev.
+int gather_tiles_launch(fir_gallery* src, fir_gallery* g, const int32_t* d_idx, bool own_list, hipStream_t st) {
+    const int64_t slab = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)g->dp4 * 4) / kTileRows);      // tiles
+    for (int64_t t0 = 0; t0 < g->tiles; t0 += slab) {
+        const int64_t tiles = std::min(slab, g->tiles - t0);
+        const int64_t blocks = (tiles * g->dp4 * 64 + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(k_gather_tiles, dim3((unsigned)blocks), dim3(kBlock), 0, st, (const float4*)src->gal4, src->n, g->dp4, d_idx, g->n, t0, tiles,
+                           (float4*)g->gal4, (int32_t*)g->range, (const int32_t*)src->cls, (int32_t*)g->cls, own_list ? (int32_t*)nullptr : (int32_t*)g->origin);
+        FIR_HIP(hipGetLastError());
+    }
+    return FIR_OK;
+}
+// fir_gallery_create_from_rows[_dev] after the checks: the list is in host memory (checked) or in device memory.
+int subset_from_list(fir_gallery* src, const int32_t* row_idx, int64_t m, bool host_list, void* stream, fir_gallery** out) {
+    FIR_HIP(hipSetDevice(src->device));
+    fir_gallery* g = nullptr;
+    int rc = subset_alloc(src, m, &g);
+    if (rc) return rc;
+    if (m == 0) { *out = g; return FIR_OK; }
+    GalleryCall call(src, stream);                         // a call on the SOURCE: after its queued appends, before its later mutations
+    if (call.rc) { delete g; return call.rc; }
+    if (host_list) {
+        const hipError_t e = hipMemcpyAsync(g->origin, row_idx, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, call.st);
+        if (e != hipSuccess) rc = fir_fail_(FIR_ERR_HIP, "row list upload: %s", hipGetErrorString(e));
+    }
+    if (rc == FIR_OK) rc = gather_tiles_launch(src, g, host_list ? (const int32_t*)g->origin : row_idx, host_list, call.st);
+    rc = created_dev(g, rc, call.st, out);
+    if (rc == FIR_OK) call.done();
+    return rc;
+}
+// fir_gallery_create_subset[_dev] after the checks: d_mask is in device memory and readable on `st` (a host mask was queued there).
+int subset_from_mask(fir_gallery* src, GalleryCall& call, const uint64_t* d_mask, fir_gallery** out) {
+    int rc = mseg_room(src);
+    if (rc) return rc;
+    if ((rc = mask_count_launch(src, d_mask, nullptr, call.st))) return rc;
+    int64_t m = 0;
+    FIR_HIP(hipMemcpyAsync(&m, mseg_total(src), sizeof m, hipMemcpyDeviceToHost, call.st));
+    FIR_HIP(hipStreamSynchronize(call.st));                // the count decides the allocation
+    fir_gallery* g = nullptr;
+    if ((rc = subset_alloc(src, m, &g))) return rc;
+    if (m == 0) { *out = g; call.done(); return FIR_OK; }
+    rc = mask_rows_launch(src, d_mask, g->origin, m, call.st);
+    if (rc == FIR_OK) rc = gather_tiles_launch(src, g, g->origin, true, call.st);
+    rc = created_dev(g, rc, call.st, out);
+    if (rc == FIR_OK) call.done();
+    return rc;
+}
+int check_origin(const fir_gallery* sub) {
+    if (!sub->is_subset) return fir_fail_(FIR_ERR_STATE, "the gallery was not made by fir_gallery_create_subset / fir_gallery_create_from_rows: it has no origin rows");
+    if (!sub->origin_ok) return fir_fail_(FIR_ERR_STATE, "the subset was changed in place (rows were appended, overwritten or removed): its origin rows no longer apply");
+    return FIR_OK;
+}
+}  // namespace
+
+int fir_gallery_rows_of_mask_dev(fir_gallery* g, const uint64_t* d_mask, int32_t* d_rows_out, int64_t cap, int64_t* d_count, void* stream) {
+    int rc = check_rows_of_mask(g, d_mask, d_rows_out, cap, d_count);
+    if (rc) return rc;
+    FIR_HIP(hipSetDevice(g->device));
+    if ((rc = mseg_room(g))) return rc;
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    if ((rc = mask_count_launch(g, d_mask, d_count, call.st))) return rc;
+    return mask_rows_launch(g, d_mask, d_rows_out, cap, call.st);
+}
+
+int fir_gallery_rows_of_mask(fir_gallery* g, const uint64_t* mask, int32_t* rows_out, int64_t cap, int64_t* count) {
+    int rc = check_rows_of_mask(g, mask, rows_out, cap, count);
+    if (rc) return rc;
+    *count = 0;
+    if (g->n == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(g->device));
+    const int64_t words = FIR_MASK_WORDS(g->n), room = std::min(cap, g->n);       // (no more than n rows can come out)
+    if ((rc = mseg_room(g)) || (rc = FIR_NEED(g->dmask, (size_t)words)) || (room > 0 && (rc = FIR_NEED(g->didx, (size_t)room)))) return rc;
+    GalleryCall call(g);
+    if (call.rc) return call.rc;
+    FIR_HIP(hipMemcpyAsync(g->dmask, mask, (size_t)words * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
+    if ((rc = mask_count_launch(g, g->dmask, nullptr, g->stream)) || (rc = mask_rows_launch(g, g->dmask, g->didx, room, g->stream))) return rc;
+    int64_t total = 0;
+    FIR_HIP(hipMemcpyAsync(&total, mseg_total(g), sizeof total, hipMemcpyDeviceToHost, g->stream));
+    FIR_HIP(hipStreamSynchronize(g->stream));
+    const int64_t have = std::min(total, room);
+    if (have > 0) FIR_HIP(hipMemcpy(rows_out, g->didx, (size_t)have * sizeof(int32_t), hipMemcpyDeviceToHost));
+    call.done();
+    *count = total;
+    return FIR_OK;
+}
+
+int fir_gallery_gather_rows_dev(fir_gallery* g, const int32_t* d_row_idx, int64_t m, float* d_rows_out, int32_t* d_class_out, void* stream) {
+    if (!g || (m > 0 && (!d_row_idx || !d_rows_out))) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if (m == 0) return FIR_OK;
+    if (d_class_out && !g->cls && g->n > 0) return fir_fail_(FIR_ERR_STATE, "gallery was created without class labels");
+    GalleryCall call(g, stream);
+    if (call.rc) return call.rc;
+    const int64_t slab = std::max<int64_t>(kTileRows, ((int64_t)1 << 30) / g->dp4);      // list entries per launch: the grid stays inside 2^31 blocks
+    for (int64_t r0 = 0; r0 < m; r0 += slab) {
+        const int64_t have = std::min(slab, m - r0);
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((have * g->dp4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, call.st, (const float4*)g->gal4, g->n, g->dp4, g->d,
+                           d_row_idx + r0, have, d_rows_out + r0 * g->d, (const int32_t*)g->cls, d_class_out ? d_class_out + r0 : (int32_t*)nullptr);
+        FIR_HIP(hipGetLastError());
+    }
+    return FIR_OK;
+}
+
+int fir_gallery_create_from_rows_dev(fir_gallery* src, const int32_t* d_row_idx, int64_t m, void* stream, fir_gallery** out) {
+    if (out) *out = nullptr;
+    if (!src || !out || (m > 0 && !d_row_idx)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    return subset_from_list(src, d_row_idx, m, false, stream, out);
+}
+
+int fir_gallery_create_from_rows(fir_gallery* src, const int32_t* row_idx, int64_t m, fir_gallery** out) {
+    if (out) *out = nullptr;
+    if (!src || !out || (m > 0 && !row_idx)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    for (int64_t i = 0; i < m; ++i)                        // every index before anything is allocated
+        if (row_idx[i] < 0 || row_idx[i] >= src->n)
+            return fir_fail_(FIR_ERR_ARG, "row index %d (entry %lld of the list) outside [0,%lld)", row_idx[i], (long long)i, (long long)src->n);
+    return subset_from_list(src, row_idx, m, true, nullptr, out);
+}
+
+int fir_gallery_create_subset_dev(fir_gallery* src, const uint64_t* d_mask, void* stream, fir_gallery** out) {
+    if (out) *out = nullptr;
+    if (!src || !out || !mask_ok(src, d_mask)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(src->device));
+    GalleryCall call(src, stream);
+    if (call.rc) return call.rc;
+    return subset_from_mask(src, call, d_mask, out);
+}
+
+int fir_gallery_create_subset(fir_gallery* src, const uint64_t* mask, fir_gallery** out) {
+    if (out) *out = nullptr;
+    if (!src || !out || !mask_ok(src, mask)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    FIR_HIP(hipSetDevice(src->device));
+    const int64_t words = FIR_MASK_WORDS(src->n);
+    int rc = FIR_NEED(src->dmask, (size_t)words);
+    if (rc) return rc;
+    GalleryCall call(src);
+    if (call.rc) return call.rc;
+    if (words > 0) FIR_HIP(hipMemcpyAsync(src->dmask, mask, (size_t)words * sizeof(uint64_t), hipMemcpyHostToDevice, src->stream));
+    return subset_from_mask(src, call, src->dmask, out);
+}
+
+int fir_gallery_origin_rows(fir_gallery* sub, int64_t row0, int64_t m, int32_t* rows_out) {
+    if (!sub || (m > 0 && !rows_out)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    const int rc = check_origin(sub);
+    if (rc) return rc;
+    if (row0 < 0 || row0 > sub->origin_n || m > sub->origin_n - row0)
+        return fir_fail_(FIR_ERR_ARG, "rows [%lld,+%lld) outside [0,%lld)", (long long)row0, (long long)m, (long long)sub->origin_n);
+    if (m == 0) return FIR_OK;
+    FIR_HIP(hipSetDevice(sub->device));
+    FIR_HIP(hipMemcpy(rows_out, sub->origin + row0, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));      // (written before creation returned)
+    return FIR_OK;
+}
+
+int fir_keys_to_origin_dev(fir_gallery* sub, uint64_t* d_keys, int64_t count, void* stream) {
+    if (!sub || (count > 0 && !d_keys)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    if (count < 0) return fir_fail_(FIR_ERR_ARG, "count < 0");
+    const int rc = check_origin(sub);
+    if (rc) return rc;
+    if (count == 0) return FIR_OK;
+    GalleryCall call(sub, stream);                         // after the search that wrote the keys, whatever stream it ran on
+    if (call.rc) return call.rc;
+    const int64_t blocks = (count + kBlock - 1) / kBlock;
+    if (blocks > 0x7FFFFFFF) return fir_fail_(FIR_ERR_ARG, "count=%lld keys in one call", (long long)count);
+    hipLaunchKernelGGL(k_keys_to_origin, dim3((unsigned)blocks), dim3(kBlock), 0, call.st, d_keys, count, (const int32_t*)sub->origin, sub->origin_n, sub->row_offset,
+                       sub->origin_offset);
+    FIR_HIP(hipGetLastError());
+    return FIR_OK;
+}
+
+int fir_keys_map_rows(uint64_t* keys, int64_t count, const int32_t* row_map, int64_t m, int64_t row_add) {
+    if (count < 0) return fir_fail_(FIR_ERR_ARG, "count < 0");
+    if (m < 0) return fir_fail_(FIR_ERR_ARG, "m < 0");
+    if ((count > 0 && !keys) || (m > 0 && !row_map)) return fir_fail_(FIR_ERR_ARG, "NULL argument");
+    for (int64_t i = 0; i < count; ++i)                    // every key before anything is written
+        if (keys[i] != kKeyNone && (int64_t)(uint32_t)keys[i] >= m)
+            return fir_fail_(FIR_ERR_ARG, "key %lld: row %u outside [0,%lld)", (long long)i, (uint32_t)keys[i], (long long)m);
+    for (int64_t i = 0; i < count; ++i)
+        if (keys[i] != kKeyNone) keys[i] = (keys[i] & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)((int64_t)row_map[(uint32_t)keys[i]] + row_add);
     return FIR_OK;
 }
 

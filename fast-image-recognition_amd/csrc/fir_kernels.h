@@ -1511,4 +1511,142 @@ __global__ void __launch_bounds__(kBlock) k_far_stats(const float* __restrict__ 
     }
 }
 
+// ---- device-side subsets of a gallery (fir_gallery_rows_of_mask, fir_gallery_create_subset / _from_rows, fir_gallery_gather_rows_dev) ----
+// Mask -> ascending row list in three launches, no atomics (two runs write the same bytes). A segment is the 64 mask words of one
+// wave, kMaskSegRows rows; n < 2^31, so every count fits an int32.
+constexpr int kMaskSegWords = 64;
+constexpr int kMaskSegRows = kMaskSegWords * 64;
+// word i of the mask with the bits at or past n cleared (i < words)
+__device__ __forceinline__ uint64_t mask_word_below_n(const uint64_t* __restrict__ mask, int64_t i, int64_t words, int64_t n) {
+    const uint64_t w = mask[i];
+    return (i == words - 1 && (n & 63)) ? w & ((1ull << (n & 63)) - 1ull) : w;
+}
+// 1: seg[s] = the set bits below n in words [64 s, 64 s + 64). One wave per segment, one word per lane.
+__global__ void __launch_bounds__(kBlock) k_mask_seg_counts(const uint64_t* __restrict__ mask, int64_t n, int64_t words, int32_t* __restrict__ seg) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t i = s * kMaskSegWords + lane;
+    if (s * kMaskSegWords >= words) return;                            // wave-uniform
+    int c = i < words ? (int)__popcll(mask_word_below_n(mask, i, words, n)) : 0;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    if (lane == 0) seg[s] = c;
+}
+// 2: seg[0, nseg) <- its exclusive prefix sums, *total (and *total2, may be NULL) <- the sum. One workgroup: kBlock entries per
+// round, shuffles inside a wave, LDS across the four waves, the carry in a register of every thread.
+__global__ void __launch_bounds__(kBlock) k_mask_seg_scan(int32_t* __restrict__ seg, int64_t nseg, int64_t* __restrict__ total, int64_t* __restrict__ total2) {
+    __shared__ int s_wave[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < nseg; base += kBlock) {
+        const int64_t i = base + threadIdx.x;
+        const int v = i < nseg ? seg[i] : 0;
+        int x = v;                                                     // inclusive inside the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int y = __shfl_up(x, off, 64);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) {
+            if (w < wave) before += s_wave[w];
+            all += s_wave[w];
+        }
+        if (i < nseg) seg[i] = carry + before + x - v;
+        carry += all;
+        __syncthreads();                                               // s_wave is written again by the next round
+    }
+    if (threadIdx.x == 0) {
+        *total = carry;
+        if (total2) *total2 = carry;
+    }
+}
+// 3: rows_out[p] = the p-th selected row for p < cap. seg[] holds the exclusive sums of 2; every wave scans its 64 popcounts with
+// shuffles, every lane then writes the set bits of its word from its own prefix on, lowest bit first; the cut at cap is per element.
+__global__ void __launch_bounds__(kBlock) k_mask_rows(const uint64_t* __restrict__ mask, int64_t n, int64_t words, const int32_t* __restrict__ seg,
+                                                       int32_t* __restrict__ rows_out, int64_t cap) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t i = s * kMaskSegWords + lane;
+    if (s * kMaskSegWords >= words) return;                            // wave-uniform
+    uint64_t w = i < words ? mask_word_below_n(mask, i, words, n) : 0ull;
+    const int c = (int)__popcll(w);
+    int x = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    int64_t p = (int64_t)seg[s] + (x - c);
+    while (w != 0ull && p < cap) {
+        rows_out[p++] = (int32_t)(i * 64 + (int64_t)__ffsll((unsigned long long)w) - 1);
+        w &= w - 1ull;
+    }
+}
+// Tiled -> tiled gather, the hot path of a subset: destination row j = source row idx[j] (any order, repeats allowed), features
+// and label. One thread per float4 of destination tiles [tile0, tile0 + tiles), indexed as k_append_rows indexes them: a wave is
+// one (tile, chunk) and writes one contiguous KiB; lane r reads chunk c of source row idx[64 t + r] -- for an ascending dense list
+// neighbouring lanes read neighbouring 16-byte pieces of one source tile. Rows at or beyond m are written as zeros, so is the row of
+// an index outside [0, src_n) (label -1, origin -1); features beyond d are zero in the source already. range[0] is set like
+// k_retile sets it. The c == 0 thread copies the label (src_cls / dst_cls NULL: no labels) and, when origin is not idx itself,
+// writes origin[j] = the index it used, -1 for a bad one.
+__global__ void __launch_bounds__(kBlock) k_gather_tiles(const float4* __restrict__ src4, int64_t src_n, int dp4, const int32_t* __restrict__ idx, int64_t m,
+                                                          int64_t tile0, int64_t tiles, float4* __restrict__ dst4, int32_t* __restrict__ range,
+                                                          const int32_t* __restrict__ src_cls, int32_t* __restrict__ dst_cls, int32_t* origin) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= tiles * dp4 * 64) return;
+    const int r = (int)(o & 63);
+    const int64_t tc = o >> 6;
+    const int c = (int)(tc % dp4);
+    const int64_t t = tile0 + tc / dp4;
+    const int64_t row = t * kTileRows + r;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < m) {
+        const int64_t s = idx[row];
+        const bool ok = s >= 0 && s < src_n;
+        if (ok) v = src4[((size_t)(s >> 6) * dp4 + c) * 64 + (s & 63)];
+        if (c == 0) {
+            if (dst_cls) dst_cls[row] = ok && src_cls ? src_cls[s] : -1;
+            if (origin && origin != idx) origin[row] = ok ? (int32_t)s : -1;
+        }
+    }
+    if (!(in_plain_range(v.x) && in_plain_range(v.y) && in_plain_range(v.z) && in_plain_range(v.w))) range[0] = 1;
+    dst4[((size_t)t * dp4 + c) * 64 + r] = v;
+}
+// Tiled -> row-major gather: k_untile_rows with a row list. out[i][d] = row idx[i] for i < m (zeros for an index outside [0, n)),
+// cls_out[i] (may be NULL) its label, -1 for a bad index or without labels. One thread per float4 chunk, consecutive threads =
+// consecutive list entries of one chunk.
+__global__ void __launch_bounds__(kBlock) k_gather_rows(const float4* __restrict__ gal4, int64_t n, int dp4, int d, const int32_t* __restrict__ idx, int64_t m,
+                                                         float* __restrict__ out, const int32_t* __restrict__ cls, int32_t* __restrict__ cls_out) {
+    const int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (o >= m * dp4) return;
+    const int64_t i = o % m;
+    const int c = (int)(o / m);
+    const int64_t row = idx[i];
+    const bool ok = row >= 0 && row < n;
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) g = gal4[((size_t)(row >> 6) * dp4 + c) * 64 + (row & 63)];
+    const float gv[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c * 4 + j < d) out[i * d + c * 4 + j] = gv[j];
+    if (c == 0 && cls_out) cls_out[i] = ok && cls ? cls[row] : -1;
+}
+// Keys of a search over a subset handle -> keys over its source (fir_keys_to_origin_dev), in place, one thread per key: the low word
+// is r + sub_offset; it becomes origin[r] + src_offset, the distance bits stay. FIR_KEY_NONE stays; a row outside [0, m), or one
+// whose origin is -1 (a bad index of the device list form), becomes FIR_KEY_NONE.
+__global__ void __launch_bounds__(kBlock) k_keys_to_origin(uint64_t* __restrict__ keys, int64_t count, const int32_t* __restrict__ origin, int64_t m,
+                                                            int64_t sub_offset, int64_t src_offset) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t key = keys[i];
+    if (key == kKeyNone) return;
+    const int64_t r = (int64_t)(uint32_t)key - sub_offset;
+    const int64_t from = (r >= 0 && r < m) ? (int64_t)origin[r] : -1;
+    keys[i] = from < 0 ? kKeyNone : (key & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)(from + src_offset);
+}
+
 }  // namespace fir

@@ -5,6 +5,8 @@
 #include <iostream>
 #include "fir_loader.h"
 
+#include <hip/hip_runtime_api.h>      // recognize_split_bf's device buffers: memory and one stream, no kernel of its own
+
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -286,6 +288,94 @@ std::vector<int> recognize_images_bf_subset(const std::vector<ImageInfo>& dbImag
     for (size_t i = 0; i < tests.size(); ++i) out[i] = idx[i];
     if (best_dist) *best_dist = dist;
     return out;
+}
+
+namespace {
+// what recognize_split_bf holds on the device for the length of one call
+struct DevMem {
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
+};
+struct DevStream {
+    hipStream_t s = nullptr;
+    ~DevStream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct SubsetHandle {
+    fir_gallery* g = nullptr;
+    ~SubsetHandle() { if (g) fir_gallery_destroy(g); }
+};
+}  // namespace
+
+std::vector<int> recognize_split_bf(const std::vector<ImageInfo>& total, const std::vector<char>& take, int max_features,
+                                    std::vector<float>* best_dist, std::vector<int>* test_rows) {
+    if (max_features == 0) max_features = FEATURES_COUNT;          // db_features.cpp:320-321
+    if (test_rows) test_rows->clear();
+    if (best_dist) best_dist->clear();
+    if (take.size() != total.size()) {
+        std::fprintf(stderr, "fir: recognize_split_bf: %zu marks for %zu rows\n", take.size(), total.size());
+        return std::vector<int>();
+    }
+    size_t tests = 0;
+    for (size_t j = 0; j < take.size(); ++j) tests += take[j] == 0;
+    std::vector<int> out(tests, -1);
+    if (best_dist) best_dist->assign(tests, FIR_NOT_FOUND_DIST);
+    if (test_rows)
+        for (size_t j = 0; j < take.size(); ++j)
+            if (!take[j]) test_rows->push_back((int)j);
+    if (tests == 0 || tests == total.size()) return out;           // no test row, or no gallery row to find
+    if (sharded_mode()) {
+        std::fprintf(stderr, "fir: recognize_split_bf: no subset of a sharded gallery\n");
+        return out;
+    }
+    const int dim = max_features;
+    Entry* e = lookup(total, dim);
+    if (!e) return out;
+    std::vector<uint64_t> train(FIR_MASK_WORDS(total.size()), 0), test(FIR_MASK_WORDS(total.size()), 0);
+    for (size_t j = 0; j < take.size(); ++j) (take[j] ? train : test)[j >> 6] |= (uint64_t)1 << (j & 63);
+    // the split's gallery: the `take` rows compacted inside device memory (the mask is the only thing that goes up) ...
+    SubsetHandle sub;
+    if (fir_gallery_create_subset(e->g, train.data(), &sub.g) != FIR_OK) { log_error("create_subset"); return out; }
+    if (g_large_batch >= 0) fir_gallery_set_large_batch_mfma(sub.g, g_large_batch);
+    // ... and its queries: the complement rows, listed by the inverted mask and taken out of the same upload in batches
+    std::vector<int32_t> rows(tests);
+    int64_t count = 0;
+    if (fir_gallery_rows_of_mask(e->g, test.data(), rows.data(), (int64_t)tests, &count) != FIR_OK || count != (int64_t)tests) {
+        log_error("rows_of_mask");
+        return out;
+    }
+    const size_t batch = std::min<size_t>(tests, 8192);
+    DevMem d_idx, d_q, d_keys;
+    DevStream st;
+    if (hipSetDevice(g_device) != hipSuccess || hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking) != hipSuccess || !d_idx.alloc(tests * sizeof(int32_t)) ||
+        !d_q.alloc(batch * (size_t)dim * sizeof(float)) || !d_keys.alloc(batch * sizeof(uint64_t)) ||
+        hipMemcpyAsync(d_idx.p, rows.data(), tests * sizeof(int32_t), hipMemcpyHostToDevice, st.s) != hipSuccess) {
+        std::fprintf(stderr, "fir: recognize_split_bf: no device memory for %zu test rows\n", tests);
+        return out;
+    }
+    std::vector<uint64_t> keys(batch);
+    std::vector<int32_t> idx(batch);
+    std::vector<float> dist(batch);
+    for (size_t b0 = 0; b0 < tests; b0 += batch) {
+        const size_t nb = std::min(batch, tests - b0);
+        // one stream for the three calls: they are calls on two handles, and only a stream orders those
+        if (fir_gallery_gather_rows_dev(e->g, (const int32_t*)d_idx.p + b0, (int64_t)nb, (float*)d_q.p, nullptr, st.s) != FIR_OK ||
+            fir_search_top1_keys_dev(sub.g, (const float*)d_q.p, (int32_t)nb, 0, max_features, (uint64_t*)d_keys.p, st.s) != FIR_OK ||
+            fir_keys_to_origin_dev(sub.g, (uint64_t*)d_keys.p, (int64_t)nb, st.s) != FIR_OK) {
+            log_error("split search");
+            return std::vector<int>(tests, -1);
+        }
+        if (hipMemcpyAsync(keys.data(), d_keys.p, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, st.s) != hipSuccess || hipStreamSynchronize(st.s) != hipSuccess) {
+            std::fprintf(stderr, "fir: recognize_split_bf: reading the keys back failed\n");
+            return std::vector<int>(tests, -1);
+        }
+        fir_keys_unpack(keys.data(), (int32_t)nb, idx.data(), dist.data());
+        for (size_t i = 0; i < nb; ++i) {
+            out[b0 + i] = idx[i];
+            if (best_dist) (*best_dist)[b0 + i] = dist[i];
+        }
+    }
+    return out;                                                    // (the subset handle and the buffers go here)
 }
 
 }  // namespace fir

@@ -88,6 +88,17 @@ std::vector<int> recognize_images_bf(const std::vector<ImageInfo>& dbImages, con
 std::vector<int> recognize_images_bf_subset(const std::vector<ImageInfo>& dbImages, const std::vector<char>& take,
                                             const std::vector<ImageInfo>& tests, int max_features = 0, std::vector<float>* best_dist = nullptr);
 
+// One whole split of that loop on the device, over the same cached upload of the TOTAL set: the gallery is the subset handle of
+// the take[j] != 0 rows (fir_gallery_create_subset: compacted inside device memory, so the search may take every routed form, the
+// matrix cores included), the queries are ALL the other rows, taken out of the upload in batches (fir_gallery_rows_of_mask of the
+// inverted mask + fir_gallery_gather_rows_dev), searched with fir_search_top1_keys_dev and mapped back with fir_keys_to_origin_dev.
+// out[i] = the index INTO total of the nearest taken row of the i-th test row (test rows ascending; *test_rows, when asked for, =
+// their indices into total), -1 without one -- the answers recognize_images_bf_subset gives for the same split and test rows. No
+// upload beyond the cached one (GalleryCache::uploads() does not move for a cached set); the subset handle lives for the call and
+// costs the taken rows' bytes a second time while it does. Single device only, like the masked form.
+std::vector<int> recognize_split_bf(const std::vector<ImageInfo>& total, const std::vector<char>& take, int max_features = 0,
+                                    std::vector<float>* best_dist = nullptr, std::vector<int>* test_rows = nullptr);
+
 // The device copy of one `std::vector<ImageInfo>` gallery. The reference's classifiers only keep
 // a pointer to the caller's vector (ImageTesting.cpp:40, ann.h:28) and read it afresh on every call; here the rows are
 // packed and uploaded on first use and the handle is reused while the SAME gallery is presented again, which is checked

@@ -434,6 +434,68 @@ int fir_gallery_mask_of_classes(fir_gallery* g, const int32_t* classes, int32_t 
 int fir_gallery_mask_of_classes_dev(fir_gallery* g, const int32_t* d_classes, int32_t m, int32_t invert, uint64_t* d_mask_out,
                                     void* stream);
 
+/* ---- device-side subsets of a gallery: compact by mask or row list, map back ------------------------
+ * A masked call always takes the exact generic scan. A NEW handle over the selected rows takes every routed form there is (the
+ * hand-scheduled kernels, the fp16 / int8 matrix-core top-1, top-K, kNN, classes, radius, other-class, the conventional TWD), and
+ * building it here costs one gather inside HBM instead of a host-side compaction and an upload: the random train / test splits of
+ * the reference's experiments (a dense mask, a large L2 batch per split), bootstrap samples and medoid-only galleries (row lists
+ * with repeats, which no mask expresses). Rows are LOCAL rows of the source throughout, as in the masked searches.
+ *
+ * fir_gallery_rows_of_mask: *count = the exact number of set bits below n (bits at or past n are ignored), rows_out[0 ..
+ * min(count, cap)) = those rows ascending; rows_out == NULL with cap == 0 is the count-only call. A NULL mask is FIR_ERR_ARG
+ * unless n == 0 (count 0). The _dev form has everything in device memory (d_count one int64), is asynchronous on `stream`, runs in
+ * the handle's call order ("Streams") and never synchronises once the handle's scratch is large enough. Three small launches over
+ * the FIR_MASK_WORDS(n) words -- popcounts per 64 words, an exclusive scan of those sums in one workgroup, then every wave scans
+ * its 64 popcounts with shuffles and every lane writes the set bits of its word at its prefix -- with plain stores and no
+ * atomics: two calls return the same bytes.
+ *
+ * fir_gallery_gather_rows_dev: d_rows_out[m][d] row-major = rows d_row_idx[0 .. m) of the handle (any order, repeats allowed),
+ * d_class_out[m] (may be NULL; FIR_ERR_STATE on a non-empty handle without labels) their labels: queries taken from the upload
+ * itself, no host round trip. Asynchronous. An index outside [0, n) gives a row of zeros and label -1 -- a device call cannot
+ * fail late.
+ *
+ * fir_gallery_create_from_rows[_dev] / fir_gallery_create_subset[_dev]: *out = a new, independent handle on the source's device
+ * holding rows row_idx[0 .. m) of src in that order -- the mask forms: the rows the mask selects, ascending, the list never leaving
+ * the device -- with their labels iff src has labels. It answers every call with the bytes of a handle made by fir_gallery_create
+ * over rows[row_idx] and class_no[row_idx] with the source's metric: every metric, range, scan form and routed form. It starts with
+ * default settings and row offset 0 and owns its memory: the source may be changed or destroyed afterwards; source and subset exist
+ * side by side, which is the only extra memory. The chi-square / KL plain-range flag is recomputed from the gathered values (a
+ * subset that leaves the offending rows out is plain again), and the layout invariant holds (rows at or beyond m and features beyond
+ * d are zero: the gather writes every float4 of tiles [0, ceil(m / 64))). m == 0 or a mask without a set bit gives an empty handle,
+ * like fir_gallery_create with n = 0; m must stay below 2^31 - 64. The host list form checks every index before anything is allocated
+ * (FIR_ERR_ARG, the message names it); the device list form writes a row of zeros with label -1 for an index outside [0, n), and
+ * keys that name such a row map to FIR_KEY_NONE below. A NULL mask is FIR_ERR_ARG unless n == 0. Creation is a call on src in the
+ * sense of "Streams": it sees an earlier fir_gallery_append_dev on any stream; like fir_gallery_create_dev it synchronises before
+ * it returns (the mask forms twice: they read the count first). A shard lent by fir_sharded_shard may be the source -- creation
+ * only reads it. Not offered: fir_sharded sources as a whole, subsets of fir_cls handles.
+ *
+ * Where the rows came from. The new handle keeps its row list on the device (4 bytes per row, under `scratch` in
+ * fir_gallery_memory_bytes) and the source's row offset at creation time. fir_gallery_origin_rows: rows_out[0 .. m) = the source's
+ * LOCAL rows of the handle's rows [row0, row0 + m). fir_keys_to_origin_dev rewrites d_keys[0 .. count) in place, asynchronously, as
+ * a call on the subset handle: a key's low word r + the subset's own row offset becomes origin[r] + the source's offset, the
+ * distance bits stay, FIR_KEY_NONE stays; a low word outside the handle's rows becomes FIR_KEY_NONE. fir_keys_map_rows is the same
+ * map as pure host code (no device, like fir_keys_unpack) over a caller's table: low word r -> uint32(row_map[r] + row_add); a low
+ * word at or beyond m is FIR_ERR_ARG and nothing is written.
+ * A mask subset's map is strictly increasing, so mapped keys stay ascending and ties keep their order: they are the bytes of the
+ * _masked call of the same name on the source. That equality is the contract. An arbitrary list keeps each query's order by
+ * distance only (equal distances may come out in another row order than a masked call's), and repeated rows give equal keys.
+ * A handle not made by these calls: FIR_ERR_STATE. So is a subset handle after an in-place update of its own (fir_gallery_append /
+ * _set_rows / _remove_rows): its rows are no longer the list's. The origin is the immediate source's: subsets of subsets do not
+ * compose (map twice). The library's _masked calls never compact by themselves -- that would double the memory silently.
+ * Measured: profiles/gallery_subset.txt (tools/subset_probe.py). */
+int fir_gallery_rows_of_mask(fir_gallery* g, const uint64_t* mask, int32_t* rows_out, int64_t cap, int64_t* count);
+int fir_gallery_rows_of_mask_dev(fir_gallery* g, const uint64_t* d_mask, int32_t* d_rows_out, int64_t cap, int64_t* d_count,
+                                 void* stream);
+int fir_gallery_gather_rows_dev(fir_gallery* g, const int32_t* d_row_idx, int64_t m, float* d_rows_out, int32_t* d_class_out,
+                                void* stream);
+int fir_gallery_create_from_rows(fir_gallery* src, const int32_t* row_idx, int64_t m, fir_gallery** out);
+int fir_gallery_create_from_rows_dev(fir_gallery* src, const int32_t* d_row_idx, int64_t m, void* stream, fir_gallery** out);
+int fir_gallery_create_subset(fir_gallery* src, const uint64_t* mask, fir_gallery** out);
+int fir_gallery_create_subset_dev(fir_gallery* src, const uint64_t* d_mask, void* stream, fir_gallery** out);
+int fir_gallery_origin_rows(fir_gallery* sub, int64_t row0, int64_t m, int32_t* rows_out);
+int fir_keys_to_origin_dev(fir_gallery* sub, uint64_t* d_keys, int64_t count, void* stream);
+int fir_keys_map_rows(uint64_t* keys, int64_t count, const int32_t* row_map, int64_t m, int64_t row_add);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
