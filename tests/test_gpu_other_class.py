@@ -14,6 +14,7 @@ import torch
 
 import knn_select_ref as ks
 import other_class_ref as ref
+import scan_forms
 import synth
 from test_gpu_knn_select import host_keys
 
@@ -122,9 +123,12 @@ def test_a_negative_gallery_value_takes_the_full_division_sequence(fir, metric):
 def test_every_instantiation_through_the_tuning(fir, metric):
     """queries_per_pass 1, 2, 4, 8 pick the tile (16 asks for the largest there is, 8); automatic wave counts, one workgroup and
     three: a wave then strides over several tiles. 17 queries: a launch of two tiles and a single query. 200 rows are few tiles (the
-    one-query tile staged in LDS), 20 000 rows are not."""
-    d, qb = 100, 17
-    for n in (200, 20000):
+    one-query tile staged in LDS). Few means at most 4 * CUs tiles, so the gallery that is not few is sized from the device: one tile
+    more than that and a part-full one, of short rows (65 637 x 64 on 256 CUs) -- there the one-query tile is the generic
+    k_scan<1, m, 8, 6, 8, WPS, 0> (tests/scan_forms.py: OTHER_CLASS_GENERIC_ONE), and the test says so."""
+    qb = 17
+    many = (4 * fir.device_info()["cus"] + 1) * 64 + 37
+    for n, d in ((200, 100), (many, 64)):
         rows = synth.make_gallery(221 + n, n, d, metric)
         labels = permuted(n, 11, 222)
         q, _ = synth.make_queries(223, rows, qb, metric)
@@ -145,6 +149,9 @@ def test_every_instantiation_through_the_tuning(fir, metric):
             seen.add(g.last_dispatch()["kernel"])
         if n == 200:
             assert any(k.startswith("fir::k_scan<1, %d, 16, 6, 8, " % metric) for k in seen), seen       # the few-tiles form
+        else:
+            assert scan_forms.OTHER_CLASS_GENERIC_ONE[metric] in seen, seen                                # the generic one-query form
+            assert not any(k.startswith("fir::k_scan<1, %d, 16, 6, 8, " % metric) for k in seen), seen
 
 
 def test_label_kinds(fir):
