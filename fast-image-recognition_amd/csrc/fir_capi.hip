@@ -139,6 +139,7 @@ struct fir_gallery {
     fir_dispatch_info last{}; // dominant kernel of the most recent search
     fir_twd_dispatch_info twd_last{0, -1};   // fir_twd_last_dispatch (fir_twd.hip writes it through fir_gallery_twd_record_); classifier -1: no call yet
     int64_t twd_mfma[6] = {};                // fir_twd_last_mfma (fir_twd.hip writes it through fir_gallery_twd_mfma_record_)
+    const char* last_subrange_kernel = "";   // fir_gallery_last_subrange_kernel_: subranges_dev's most recent one-pass kernel, "" after the per-range branch
     bool label_known = false;                // fir_gallery_label_range_: smallest and largest label, found once per generation
     int32_t label_lo = 0, label_hi = -1;
     int call_launches = 0;    // scan launches of the current call (note_dispatch)
@@ -1081,6 +1082,7 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
     // step2 != 0: two sub-ranges, [start, start + step) and [start + step, end) with end - start - step == step2 (whole load groups both)
     const int nsub = step2 ? 2 : (end - start) / step;
     if (!step2 && (step % (4 * kUSub) != 0 || start % 4 != 0)) {   // one pass per sub-range (any step)
+        g->last_subrange_kernel = "";
         for (int ci = 0; ci < nsub; ++ci) {
             const int rc = range_dev(g, d_queries, qb, start + ci * step, start + (ci + 1) * step, d_out + (size_t)ci * qb * g->n, st);
             if (rc) return rc;
@@ -1093,8 +1095,10 @@ int subranges_dev(fir_gallery* g, const float* d_queries, int32_t qb, int32_t st
     for (int q0 = 0; q0 < qb; q0 += 8) {
         const int live = std::min(8, qb - q0);
         const int qbt = live <= 1 ? 1 : live <= 2 ? 2 : live <= 4 ? 4 : 8;   // kernel tile: the next power of two (extra queries are zero padding)
-        const scan_fn fn = select_scan(kEpiSubranges, qbt, g->metric, whole_chunks(start, end), g->dp4, false).fn;
+        const ScanKernel sk = select_scan(kEpiSubranges, qbt, g->metric, whole_chunks(start, end), g->dp4, false);
+        const scan_fn fn = sk.fn;
         if (!fn) return fir_fail_(FIR_ERR_ARG, "no sub-range kernel for qb=%d metric=%d", qbt, g->metric);
+        g->last_subrange_kernel = sk.name;
         hipLaunchKernelGGL(k_transpose_queries, dim3((unsigned)(((int64_t)kk * qbt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            d_queries + (size_t)q0 * g->d, live, g->d, g->dp4, qbt, g->qt, (uint64_t*)nullptr, 0);
         const int max_waves = max_waves_for(g, fn, 0);
@@ -1339,10 +1343,12 @@ int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb,
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
     if (split % (4 * kUSub) == 0 && (end - split) % (4 * kUSub) == 0) return subranges_dev(g, d_queries, qb, 0, end, split, d_out, st, end - split);
+    g->last_subrange_kernel = "";
     const int rc = range_dev(g, d_queries, qb, 0, split, d_out, st);
     if (rc) return rc;
     return range_dev(g, d_queries, qb, split, end, d_out + (size_t)qb * g->n, st);
 }
+const char* fir_gallery_last_subrange_kernel_(fir_gallery* g) { return g ? g->last_subrange_kernel : ""; }
 int fir_gallery_tiled_(fir_gallery* g, const void** gal4, int* dp4) {
     if (!g || !gal4 || !dp4) return FIR_ERR_ARG;
     *gal4 = g->gal4;

@@ -151,6 +151,10 @@ extern "C" int fir_subrange_distances_dev_(fir_gallery* g, const float* d_querie
 // both widths are multiples of 32 features (the two stages of the conventional TWD: 64 and 192), two otherwise.
 extern "C" int fir_split_distances_dev_(fir_gallery* g, const float* d_queries, int32_t qb, int32_t split, int32_t end, float* d_out, void* stream);
 
+// Tests only: the kScanTable name of the kernel of the most recent one-pass launch of the two entries above on this handle, "" when
+// their most recent call went range by range (or none was made). A host-side pointer; reading it does not touch the device.
+extern "C" const char* fir_gallery_last_subrange_kernel_(fir_gallery* g);
+
 // First touch of a device by this library. The HIP runtime's start-up draws from libc's rand(); the reference's harnesses
 // lean on that stream (std::random_shuffle in getTrainingAndTestImages and DirectedEnumeration::init, srand(13) in
 // testRecognitionMethod), so the start-up runs on a private random state and the caller's is handed back untouched.

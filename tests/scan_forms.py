@@ -71,6 +71,14 @@ CASES = _cases()
 OTHER_CLASS_GENERIC_ONE = [k_scan(1, m, 6) for m in (L2, CHI2, KL)]
 
 
+def k_scan_subranges(qbt, metric):
+    return "fir::k_scan_subranges<%d, %d, 8, 4>" % (qbt, metric)
+
+
+# the sub-range scans behind the staged three-way-decision drivers: asserted by name and slot by slot by tests/test_gpu_subrange_scans.py
+SUBRANGE_ROWS = [k_scan_subranges(qbt, m) for qbt in (1, 2, 4, 8) for m in (L2, CHI2, KL)]
+
+
 def _exempt():
     ex = {}
     nom = "append / nomination scans: tests/test_gpu_nomination_scans.py"
@@ -80,10 +88,8 @@ def _exempt():
         ex["fir::k_nominate<%d, 2, 8, 3>" % m] = nom
     for m in range(6):
         ex["fir::k_scan<8, %d, 8, 3, 8, %d>" % (m, 4 if m < 3 else 3)] = nom
-    for qb in (1, 2, 4, 8):
-        for m in (0, 1, 2):
-            ex["fir::k_scan_subranges<%d, %d, 8, 4>" % (qb, m)] = ("k_scan_subranges: its output is not visible through the public API; its callers: "
-                                                                  "tests/test_gpu_twd_forms.py")
+    for name in SUBRANGE_ROWS:
+        ex[name] = "k_scan_subranges, read through the library's internal entries: tests/test_gpu_subrange_scans.py"
     for m in range(5):
         wps = 4 if m < 3 else 3
         ex[k_scan(8, m, 5)] = "class minimum: tests/test_gpu_class_rank.py, tests/test_gpu_gallery_handle.py"

@@ -40,6 +40,9 @@ def test_every_row_is_a_case_or_exempt_and_every_name_is_a_row():
     assert exempt - rows == set(), "exemptions that name no row of kScanTable: %s" % sorted(exempt - rows)
     assert all(sf.EXEMPT[n] for n in exempt)
     assert set(sf.OTHER_CLASS_GENERIC_ONE) <= exempt
+    assert len(sf.SUBRANGE_ROWS) == 12 == len(set(sf.SUBRANGE_ROWS))
+    assert set(sf.SUBRANGE_ROWS) == {r for r in rows if r.startswith("fir::k_scan_subranges<")}, "SUBRANGE_ROWS is not the source's k_scan_subranges rows"
+    assert set(sf.SUBRANGE_ROWS) <= exempt and all("tests/test_gpu_subrange_scans.py" in sf.EXEMPT[n] for n in sf.SUBRANGE_ROWS)
 
 
 def test_the_table_is_well_formed():
