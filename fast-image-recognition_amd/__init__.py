@@ -17,6 +17,7 @@ from .capi import (  # noqa: F401
     METRIC_CHI2,
     METRIC_KL,
     METRIC_L2,
+    Projection,
     SHADOW_ALL,
     SHADOW_FP16,
     SHADOW_NONE,

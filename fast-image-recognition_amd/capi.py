@@ -176,6 +176,14 @@ SYMBOLS = [
     ("fir_gallery_mfma_stats_ex", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("fir_gallery_memory_bytes", C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fir_gallery_set_shadow_copies", C.c_int, [_vp, C.c_int32]),
+    ("fir_gallery_feature_stats", C.c_int, [_vp, _vp, _i64p, _vp, _vp, _vp, _vp]),
+    ("fir_gallery_scatter", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64p]),
+    ("fir_projection_create", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(_vp)]),
+    ("fir_projection_destroy", C.c_int, [_vp]),
+    ("fir_projection_info", C.c_int, [_vp, _i32p, _i32p, _i32p]),
+    ("fir_projection_apply", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("fir_projection_apply_dev", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
+    ("fir_gallery_create_projected", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
 ]
 
 _lib = None
@@ -690,6 +698,37 @@ class Gallery:
         """Device keys of a search over this subset -> keys over its source, in place; asynchronous."""
         _check(lib().fir_keys_to_origin_dev(self._h, _vp(keys_ptr) if keys_ptr else None, int(count), _vp(stream) if stream else None))
 
+    # ---- linear projection / PCA (include/fir_amd.h) ----
+    def feature_stats(self, mask=None):
+        """(count, min, max, avg, std) of the rows the mask selects (None: every row), float64[d] each: split_train_test's statistics."""
+        m, pm = self._mask(mask)
+        count = C.c_int64()
+        out = np.empty((4, self.d), np.float64)
+        _check(lib().fir_gallery_feature_stats(self._h, pm, C.byref(count), *(out[i].ctypes.data_as(_vp) for i in range(4))))
+        return int(count.value), out[0], out[1], out[2], out[3]
+
+    def scatter(self, mask=None, center=None):
+        """(S, mean, count): S[d, d] = sum over the selected rows of (x - c)(x - c)^T in float64, c = center or, for None, their mean
+        (returned as `mean`; with a center it is the center itself)."""
+        m, pm = self._mask(mask)
+        pc = None
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+            if center.size != self.d:
+                raise ValueError(f"center must have {self.d} entries")
+            pc = center.ctypes.data_as(_vp)
+        s = np.empty((self.d, self.d), np.float64)
+        mean = np.empty(self.d, np.float64)
+        count = C.c_int64()
+        _check(lib().fir_gallery_scatter(self._h, pm, pc, s.ctypes.data_as(_vp), mean.ctypes.data_as(_vp), C.byref(count)))
+        return s, mean, int(count.value)
+
+    def projected(self, projection):
+        """A new Gallery: every row mapped by `projection` (a Projection), labels, metric and row offset carried."""
+        h = _vp()
+        _check(lib().fir_gallery_create_projected(self._h, projection._h, C.byref(h)))
+        return Gallery._adopt(h, self.device)
+
     def other_class(self, start=0, end=0):
         """Every row of the gallery against the gallery with its own class excluded (row i is the query): (idx, dist), each [n];
         -1 / 100000 for a row that has no row of another class."""
@@ -820,6 +859,60 @@ class Gallery:
 
 
 COMM_ID_BYTES = 128
+
+
+class Projection:
+    """Owns one fir_projection handle: y = f32(W x - W c) for basis W [p, d] (rows = eigenvectors) and center c [d] (None: zeros)."""
+
+    def __init__(self, basis, center=None, device=0):
+        basis = np.ascontiguousarray(basis, dtype=np.float64)
+        if basis.ndim != 2:
+            raise ValueError("basis must be [p, d]")
+        pc = None
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+            if center.size != basis.shape[1]:
+                raise ValueError(f"center must have {basis.shape[1]} entries")
+            pc = center.ctypes.data_as(_vp)
+        self._h = _vp()
+        _check(lib().fir_projection_create(basis.ctypes.data_as(_vp), basis.shape[0], basis.shape[1], pc, device, C.byref(self._h)))
+        self.p, self.d = basis.shape
+        self.device = device
+
+    def close(self):
+        if self._h:
+            lib().fir_projection_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        p, d, dev = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().fir_projection_info(self._h, C.byref(p), C.byref(d), C.byref(dev)))
+        return int(p.value), int(d.value), int(dev.value)
+
+    def apply(self, rows):
+        """rows[m, d] -> float32[m, p], through host memory."""
+        q, pq = _f32(rows)
+        q = q.reshape(-1, self.d)
+        out = np.empty((q.shape[0], self.p), np.float32)
+        _check(lib().fir_projection_apply(self._h, pq if q.size else None, q.shape[0], out.ctypes.data_as(_vp) if out.size else None))
+        return out
+
+    def apply_dev(self, rows_ptr, m, out_ptr, stream=None):
+        """rows_ptr -> m x d float32 on the device, out_ptr -> m x p float32; asynchronous."""
+        _check(lib().fir_projection_apply_dev(self._h, _vp(rows_ptr) if rows_ptr else None, int(m), _vp(out_ptr) if out_ptr else None,
+                                              _vp(stream) if stream else None))
 
 
 def comm_unique_id():

@@ -5,7 +5,9 @@
 #include "fir_kernels.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -106,10 +108,12 @@ struct fir_gallery {
     GalleryBuf<int32_t> origin;
     int64_t origin_n = 0, origin_offset = 0;
     bool is_subset = false, origin_ok = false;
+    // linear projection / PCA (fir_projection.h): the column statistics' partials and folded sums; the scatter's centre, partials and result
+    GalleryBuf<double> pjstat, pjcen, pjpart, pjout;
     FirBuf scratch[25];
     size_t scratch_bytes() const {
         size_t sum = qt.cap + dq.cap + dkeys.cap + part.cap + dout.cap + didx.cap + rowsum.cap + knn.cap + excl.cap + okeys.cap + ocls.cap + selfq.cap +
-                     selfkeys.cap + fardist.cap + dmask.cap + mclasses.cap + mseg.cap + origin.cap;
+                     selfkeys.cap + fardist.cap + dmask.cap + mclasses.cap + mseg.cap + origin.cap + pjstat.cap + pjcen.cap + pjpart.cap + pjout.cap;
         for (const FirBuf& s : scratch) sum += s.cap;
         return sum;
     }
@@ -3302,3 +3306,5 @@ int fir_gallery_get_tuning(const fir_gallery* g, int32_t* queries_per_pass, int3
 }
 
 }  // extern "C"
+
+#include "fir_projection.h"

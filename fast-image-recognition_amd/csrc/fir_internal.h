@@ -41,6 +41,9 @@ extern "C" void fir_gallery_set_borrowed_(fir_gallery* g, int borrowed);
 // tests only: the number of non-zero 32-bit words among what the layout invariant says is zero -- the rows at or beyond n of every
 // allocated tile and the features beyond d. Waits for the handle's calls; one small kernel on its own stream.
 extern "C" int fir_gallery_padding_words_(fir_gallery* g, int64_t* words);
+// tests only: the two device sums behind fir_gallery_feature_stats' avg and std -- sum[d] and sum_sq[d] over the rows of the host
+// mask (NULL: every row), as the fold kernel left them.
+extern "C" int fir_gallery_feature_sums_(fir_gallery* g, const uint64_t* mask, double* sum, double* sum_sq);
 
 // Call order of one gallery handle (include/fir_amd.h: calls on one handle take effect in call order, whatever stream they are
 // given). Every entry point that queues work on the handle -- or on a fir_gemm state over it: they share its scratch -- holds a

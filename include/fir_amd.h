@@ -496,6 +496,59 @@ int fir_gallery_origin_rows(fir_gallery* sub, int64_t row0, int64_t m, int32_t* 
 int fir_keys_to_origin_dev(fir_gallery* sub, uint64_t* d_keys, int64_t count, void* stream);
 int fir_keys_map_rows(uint64_t* keys, int64_t count, const int32_t* row_map, int64_t m, int64_t row_add);
 
+/* ---- linear projection / PCA ------------------------------------------------------------------
+ * The device side of extract_pca_features (classification.cpp:864-940) and extractPCA (db_features.cpp:218-315): the feature
+ * statistics and the scatter matrix of the rows a mask selects, and a linear map (an eigenvector basis, or any p x d matrix)
+ * applied to every row of a handle into a new handle. The eigen-decomposition of the d x d matrix is the caller's (host/fir_eigen.h
+ * has one). Masks are host words as in "searches over a subset of the rows": FIR_MASK_WORDS(n) of them, bits at or past n ignored,
+ * NULL = every row. Every call takes part in the handle's call order ("Streams"); the host-pointer calls synchronise before
+ * they return. An empty gallery is FIR_ERR_ARG for all of them.
+ *
+ * All sums are float64 over exactly widened f32 values. The rows are cut into fixed segments of whole tiles (a function of n and d
+ * alone), every segment's partial result is written to scratch and a second small kernel folds the partials in ascending segment
+ * order: no floating-point atomics, two calls return the same bytes.
+ *
+ * fir_gallery_feature_stats -- split_train_test's statistics (classification.cpp:969-989) over the selected rows, per feature:
+ *   *count = the selected rows; min / max exact, starting from FLT_MAX / -FLT_MAX as the reference does; avg = sum(x) / count;
+ *   std = sqrt((sum(x^2) - avg * avg * count) / (count - 1)), evaluated literally, un-fused, in IEEE double on the host from the
+ *   device's two sums -- whatever that yields for count 0 or 1. Each output array holds d doubles and may be NULL.
+ *
+ * fir_gallery_scatter -- S[a][b] = sum_j (x_ja - c_a)(x_jb - c_b) over the selected rows, the numerator of the covariance (the caller
+ *   divides by count or count - 1). center NULL: c = the mean of the selected rows (the column sums above / count; zeros when no row
+ *   is selected), returned in mean_out. The products run on the float64 matrix cores; only the 64 x 64 feature blocks a <= b are
+ *   computed and the other triangle is mirrored: S is symmetric bit for bit. d <= 4096. Scratch (owned by the handle, reported by
+ *   fir_gallery_memory_bytes): segments x computed blocks x 32 KiB of partials, held at or below 256 MiB by the choice of the segment
+ *   count (at least one segment; d = 4096 has 2080 blocks, 65 MiB a segment), plus d x d x 8 bytes for S itself. It is reserved
+ *   before anything is queued: FIR_ERR_NOMEM leaves the handle as it was.
+ *
+ * fir_projection -- y[k] = f32(sum_f x_f W[k][f] - b[k]), b[k] = sum_f c_f W[k][f] (float64, computed once at creation): inputs
+ *   widened exactly, products and sums in float64 on the matrix cores, ONE rounding to f32 at the end. basis is [p][d] row-major
+ *   (rows = OpenCV's eigenvectors layout), 1 <= p <= 4096, p may exceed d; center NULL = zeros. The handle keeps the basis on
+ *   `device` in the order the kernel's operand reads it.
+ *   fir_projection_apply[_dev]: rows[m][d] row-major -> out[m][p] row-major; the _dev form is asynchronous on `stream` (NULL = the
+ *   projection's own) and calls on one projection are ordered among themselves whatever their streams.
+ *   fir_gallery_create_projected: a new independent handle on the source's device holding the source's n rows mapped to p features,
+ *   with the source's labels, metric and row offset, default settings and no origin list; written straight into the new handle's
+ *   tiles (the only extra memory is the new handle). It answers every call with the bytes of a handle made by fir_gallery_create
+ *   over its own rows. The source may be changed or destroyed afterwards; a shard lent by fir_sharded_shard may be the source.
+ *   FIR_ERR_ARG when the projection's d is not the source's or the two are on different devices.
+ *   The same row gives the same bits through either path (one kernel, one order of summation: the row-major form re-tiles its
+ *   input), so a gallery row projected as a query finds itself at distance 0 in the projected handle.
+ *
+ * Not offered: sharded handles as a whole (scatter matrices and column sums of shards add; the caller adds them), fir_cls handles,
+ * device-resident masks, any normalisation after the projection. */
+int fir_gallery_feature_stats(fir_gallery* g, const uint64_t* mask, int64_t* count, double* min, double* max, double* avg, double* std);
+int fir_gallery_scatter(fir_gallery* g, const uint64_t* mask, const double* center /* [d] or NULL */, double* scatter /* [d][d] */,
+                        double* mean_out /* [d], may be NULL */, int64_t* count);
+typedef struct fir_projection fir_projection;
+int fir_projection_create(const double* basis /* [p][d] */, int32_t p, int32_t d, const double* center /* [d] or NULL */, int32_t device,
+                          fir_projection** out);
+int fir_projection_destroy(fir_projection* pr);
+int fir_projection_info(const fir_projection* pr, int32_t* p, int32_t* d, int32_t* device);
+int fir_projection_apply(fir_projection* pr, const float* rows /* [m][d] */, int64_t m, float* out /* [m][p] */);
+int fir_projection_apply_dev(fir_projection* pr, const float* d_rows, int64_t m, float* d_out, void* stream);
+int fir_gallery_create_projected(fir_gallery* src, fir_projection* pr, fir_gallery** out);
+
 /* ---- all distances of a feature sub-range ---------------------------------------------------
  * out[qb][n] <- distance(query, row j) over [start_pos,end_pos): the per-row loops of
  * ConventionalTWDClassifier / ProposedTWDClassifier (ImageTesting.cpp:117,174,243). */
